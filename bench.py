@@ -2,10 +2,12 @@
 all-reduce + AdamW), default config, bsz = 64 genes per GPU, synthetic 7-mark inputs resident
 in HBM (BASELINE.json: configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]      (N > 1: starts its own N ranks through torch.distributed.run)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]      (N > 1: starts its own N ranks through torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (see DESIGN.md section 6 for how `roofline` is defined).
+Prints ONE JSON line on rank 0 (see DESIGN.md section 6 for how `roofline` is defined).  `--dump-outputs DIR` also writes what the
+last timed step computed as DIR/<name>.npy (float32), from inputs and a model state fixed by the arguments alone: two builds run
+with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -19,6 +21,23 @@ sys.path.insert(0, ROOT)
 import torch
 
 BSZ = 64
+
+
+def dump_arrays(path, arrays, keep):
+    """--dump-outputs: write {name: tensor} as path/<name>.npy in float32.  A tensor of more than `keep` elements is written as `keep` of its
+    flattened elements at fixed positions: torch.randint(0, numel, (keep,)) from a CPU generator seeded with 0, sorted.  -> {name: shape written}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    shapes = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > keep:
+            idx = torch.randint(0, t.numel(), (keep,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 def usable_cores():
@@ -186,7 +205,7 @@ def dp_path_ms(model, batch, steps, warmup, dev):
     return out
 
 
-def stress_record(steps, warmup):
+def stress_record(steps, warmup, dump=None):
     """BASELINE.json configs[3] -- i_max = 16, one 100-bp resolution over 80 kb (800-bin sequences), bsz 128 -- as SURVEY.md
     section 8-d defines it (the reference cannot run it): the roofline run of the DENSE attention core, all L x L rows,
     forward + backward, on the N = 128 * 17 sequences of a batch (cf_op_attention_fwd / _bwd, csrc/cf_attn.h).  A step is
@@ -237,10 +256,11 @@ def stress_record(steps, warmup):
         torch.cuda.synchronize()
         return time.perf_counter() - t0, e0.elapsed_time(e1) / n
 
-    steps, warmup = min(steps, 20), min(warmup, 3)
     for _ in range(warmup):
         step()
     el, dev_ms = timed(step, steps)
+    # (o and stats: the forward's outputs; dproj holds dq | dk | dv, the backward's: 3 x 4 MB of samples)
+    dumped = dump_arrays(dump, {"o": o, "stats": stats, "dproj": dproj}, 1 << 20) if dump else None
     _, fwd_ms = timed(fwd, max(3, steps // 2))
     _, bwd_ms = timed(bwd, max(3, steps // 2))
     flops = 14.0 * N * H * L * L * 64
@@ -268,13 +288,15 @@ def stress_record(steps, warmup):
                         "bwd_tflops_no_recompute": round(8.0 * N * H * L * L * 64 / (bwd_ms * 1e-3) / 1e12, 2),
                         "compulsory_io_gb_per_step": round(io_gb, 3),
                         "algorithmic_gflop_per_launch": round(flops / 1e9, 2)}}
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": dump, "arrays": dumped}
     del proj, dproj, d_o, o, stats, ws, valid, q, k, v, dq, dk, dv
     torch.cuda.empty_cache()
     return out
 
 
 def stress_main(args, json_out):
-    json_out.write(json.dumps(stress_record(args.steps, args.warmup)) + "\n")
+    json_out.write(json.dumps(stress_record(args.steps, args.warmup, args.dump_outputs)) + "\n")
     json_out.flush()
 
 
@@ -408,12 +430,18 @@ def main():
                     help="also run the entrypoint end to end on a small planted-signal cell line and report its validation AUROC (`val_auroc`; ~10 s)")
     ap.add_argument("--no-val-auroc", dest="val_auroc", action="store_false")
     ap.add_argument("--prewarm-s", type=float, default=0.5,
-                    help="un-timed device pre-warm in front of the W warm-up steps: the same step issued for this many seconds of wall clock (a fresh box "
+                    help="un-timed device pre-warm in front of the W warm-up steps: the same step, on a second model of the same construction, issued for "
+                         "this many seconds of wall clock (a fresh box "
                          "runs its first ~100 ms of kernels 5 %% slower: clock / power state); reported as `prewarm_s` / `prewarm_steps`; 0 = none.  "
                          "--steps / --warmup are honoured as given and what is timed does not change")
     ap.add_argument("--launch-timeout-s", type=int, default=1500, help="--gpus N > 1 started without torch.distributed.run: end the ranks this process started after so many seconds")
     ap.add_argument("--no-extras", action="store_true", help="skip the `stress` and `binning` sub-records of the default line (~3 s)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy, float32: rank 0's logits and loss and the "
+                         "trainable parameters the step left (--config stress: a fixed sample of the attention outputs and gradients)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     # (multi-process GPU work on this platform needs dmabuf IPC: the variable must be in place before the HIP runtime starts in any rank)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
@@ -491,7 +519,14 @@ def main():
     # idle -- its kernels run ~5 % longer than 100 ms later (BENCH_r04: 134.3 against 128.3 us for k_reg8_bwd)
     # (under data parallelism every rank must issue the SAME number of steps -- each one is a set of all-reduces --: a count derived from rank 0's
     # measured cold step time, broadcast)
+    # (the pre-warm steps run on a second model of the same construction: their number follows the wall clock, and the model that is timed
+    #  must reach its last step along a path fixed by the arguments alone -- same parameters, moments and step count in every run, which is
+    #  what makes --dump-outputs comparable between runs and builds)
     prewarm_steps, tp0 = 0, time.perf_counter()
+    if args.prewarm_s > 0:
+        warm_trainer = Trainer(ChromoformerClassifier(seed=42, max_batch=BSZ).cuda(local), lr=3e-5, world_size=world, process_group=pg,
+                               use_graph=args.graph, timed_kernel=args.roofline_kernel)
+        warm_slot = warm_trainer.stage(batch)
     fixed = None
     if world > 1:
         n = torch.tensor([int(args.prewarm_s / max(cold_ms * 1e-3, 1e-5)) // 10 * 10], device=dev, dtype=torch.int64)
@@ -499,7 +534,7 @@ def main():
         fixed = min(int(n.item()), 5000)
     while args.prewarm_s > 0 and (prewarm_steps < fixed if fixed is not None else time.perf_counter() - tp0 < args.prewarm_s):
         for _ in range(10):
-            trainer.step(slot)
+            warm_trainer.step(warm_slot)
         torch.cuda.synchronize()
         prewarm_steps += 10
     prewarm_s = time.perf_counter() - tp0 if prewarm_steps else 0.0
@@ -511,7 +546,7 @@ def main():
     trainer.timing_reset()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        trainer.step(slot)
+        last = trainer.step(slot)
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
@@ -521,6 +556,11 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         el = t.item()
     kernel_ms, kernel_n = trainer.timing_read()
+    # what the last timed step handed back (logits, loss) and the parameters it left, before any later leg below steps this model again
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_arrays(args.dump_outputs, {"logits": last[0], "loss": last[1], "params": model._flat[: model._layout.n_active]},
+                             1 << 23)      # (all 5.3 M parameters of the default config: 21 MB)
 
     # self-check 2 (outside the timed region): data parallelism means every rank holds the SAME parameters after the same number of
     # steps -- an all-reduce that silently did nothing (or ran on a subset of the ranks) shows here.  Bit-level checksum of the
@@ -564,6 +604,8 @@ def main():
         }
         if checks is not None:
             out["dp_self_check"] = checks
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if world == 1 and not args.graph:      # the same step replayed as ONE hipGraph + AdamW (what train_epoch does), no events inside
             tg = Trainer(model, lr=3e-5)
             sg = tg.stage(batch)

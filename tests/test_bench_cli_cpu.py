@@ -27,3 +27,9 @@ def test_world_size_mismatch_is_refused_by_name():
     env = dict(os.environ, WORLD_SIZE="4", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "WORLD_SIZE=4" in (r.stdout + r.stderr)
+
+
+def test_steps_below_one_is_refused_before_any_work():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
+    assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -1,10 +1,11 @@
 """How far the HIP gradients and the fp32 oracle are from an fp64 run of the oracle, per tensor, for variants of tests/test_config_variants_gpu.py:
 python tools/variant_err.py [--no64] VARIANT...   (--no64: HIP against the fp32 oracle only)"""
-import sys, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 from oracle import chromoformer_oracle as orc
 from chromoformer_amd import ChromoformerClassifier
-sys.path.insert(0, "/root/repo/tests")
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import importlib
 tv = importlib.import_module("tests.test_config_variants_gpu")
 NO64 = "--no64" in sys.argv
