@@ -181,20 +181,24 @@ class EpochFeed:
 class Trainer:
     """One optimisation step = forward, loss, backward, gradient reductions, [all-reduce], AdamW.
 
-    Single GPU: everything up to the optimiser is one captured hipGraph (the launch sequence is static); AdamW is
-    launched eagerly behind it because its bias corrections change every step (`opt_in_graph=True` moves it inside,
-    reading the scalars from device memory -- measured slower, see __init__).
-    Data parallel: two graphs.  The first ends with the Regulation + head gradient bucket (78 % of the bytes), whose
-    RCCL all-reduce then runs on a side stream while the second graph (Pairwise + Embedding backward and their
-    bucket) runs on the main one.
+    Single GPU, three schedules:
+    - fused (the default): [graph: batch gather, forward, head + Regulation backward] -> cf_rider_arm -> the trunk's backward launch
+      -> one cf_reduce_opt_part over both buckets, AdamW in the epilogue of the reductions (`_step_fused`; without riders the trunk's
+      backward is in the graph);
+    - merged (`fuse_opt=False`, or a model the fused form does not serve: embed.n_layers > 1): [graph: the backward pass and the
+      Regulation + head bucket's reduction] -> cf_reduce_adamw_part -> cf_adamw_step_part (`_step_merged`);
+    - separate launches (`merge_opt=False`, and bench.py's k_wgrad / k_colsum / k_adamw timing): [graph: the whole backward pass with
+      its reductions] -> model.adamw_step (`_step_separate`); the reference of the parity tests.
+    Data parallel (`_step_dp`): the Regulation + head bucket (in halves where cf_reg_halves offers them) is all-reduced on the side stream
+    under the rest of the backward pass, then AdamW over its range runs there as well; `overlap_allreduce=False` issues the all-reduces
+    behind the whole backward pass and steps both ranges on the main stream.
     ``timed_kernel``: bench.py's roofline kernel; its launches are bracketed by HIP events.  The library splits the
     capture around a Regulation kernel and launches it eagerly between the two graph pieces (event-record nodes
     inside a graph cost ~60 us per replay with this runtime; an eager launch between two graphs costs nothing)."""
 
     def __init__(self, model, lr=3e-5, gamma=0.87, world_size=1, process_group=None, use_graph=True,
-                 betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, timed_kernel=None, opt_in_graph=False, overlap_opt=False,
-                 overlap_allreduce=None, merge_opt=True, overlap_reduce=None, fuse_opt=None, keep_grads=False, fuse_one=None, rider_tiles=None,
-                 keep_tiled=None, dp_halves=None, dp_early_opt=None, dp_side_reduce=None):
+                 betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, timed_kernel=None, overlap_allreduce=None, merge_opt=True,
+                 fuse_opt=True, keep_grads=False, rider_tiles=None, keep_tiled=True, dp_side_reduce=None):
         self.model, self.lr, self.gamma = model, float(lr), gamma
         self.world, self.pg, self.use_graph = world_size, process_group, use_graph
         self.dp = world_size > 1 or process_group is not None
@@ -214,31 +218,21 @@ class Trainer:
         self.stream = torch.cuda.Stream(device=model._device)
         self.side = torch.cuda.Stream(device=model._device)       # all-reduce of the early gradient bucket
         torch.cuda.synchronize(model._device)      # parameter upload / buffer fills of the model ran on the default stream
-        # four events, created once: a fresh torch.cuda.Event per step is a hipEventCreate on the critical path of the host loop
+        # events created once: a fresh torch.cuda.Event per step is a hipEventCreate on the critical path of the host loop
         self._ev_fork, self._ev_join, self._ev_late, self._ev_done = (torch.cuda.Event() for _ in range(4))
-        # Data parallel, round 5: the Regulation + head bucket goes on the wire in two HALVES.  Its all-reduce (16.6 MB, ~0.17 ms per-link
-        # bound on eight ranks) is the critical path of the step; as one piece it starts behind the whole Regulation backward and the
-        # reduction of 1,008 tiles (~180 us after that launch began).  With the backward as two launches -- upper half of the layers, then
-        # the lower half -- the upper half's + the head's tiles are reduced and sent while the lower half still runs (~90 us earlier),
-        # the lower half's follow under the Pairwise + Embedding backward.  Same gradients, same bits (tests/test_engine_gpu.py);
-        # dp_halves=False / CF_DP_HALVES=0: the two-bucket schedule of rounds 2-4.
-        if dp_halves is None:
-            import os
-            dp_halves = os.environ.get("CF_DP_HALVES", "1") != "0"
-        self.halves = bool(dp_halves) and self.dp and not opt_in_graph and int(self._L.cf_reg_halves(model._handle)) > 0
-        if dp_early_opt is None:
-            import os
-            dp_early_opt = os.environ.get("CF_DP_EARLY_OPT", "1") != "0"
-        self.dp_early_opt = bool(dp_early_opt) and self.dp
-        # Data parallel, round 6: the weight-gradient reductions of the two Regulation halves run on the SIDE stream, in front of the all-reduce that
-        # ships them -- beside the next backward launch of the main stream (192 workgroups on 256 CUs) instead of between two of them.  The main
-        # stream's chain loses two `k_reduce` launches (2 x 30 us); the all-reduces start where they did (the reduction that precedes each is the
-        # same launch, one stream over).  Same kernels on the same data in the same order per bucket: same bits (tests/test_engine_gpu.py).  Eager
-        # launches only (what chromoformer_amd.train and bench.py run under data parallelism); dp_side_reduce=False / CF_DP_SIDE_REDUCE=0: round 5.
-        if dp_side_reduce is None:
-            import os
-            dp_side_reduce = os.environ.get("CF_DP_SIDE_REDUCE", "1") != "0"
-        self.dp_side_reduce = bool(dp_side_reduce) and self.halves and self.overlap_allreduce and not use_graph and not opt_in_graph
+        # Data parallel: the Regulation + head bucket goes on the wire in two HALVES.  Its all-reduce (16.6 MB, ~0.17 ms per-link bound on
+        # eight ranks) is the critical path of the step; as one piece it starts behind the whole Regulation backward and the reduction of
+        # 1,008 tiles.  With the backward as two launches -- upper half of the layers, then the lower half -- the upper half's + the head's
+        # tiles are reduced and sent while the lower half still runs (~90 us earlier), the lower half's follow under the Pairwise + Embedding
+        # backward.  Models without halves (CF_REG_FUSED=0: cf_reg_halves is 0) send the bucket whole.
+        self.halves = self.dp and int(self._L.cf_reg_halves(model._handle)) > 0
+        # early AdamW when the all-reduces overlap: the Regulation + head range is stepped on the side stream straight behind its last
+        # all-reduce (reported True for every data-parallel trainer; the serialised schedule steps it on the main stream)
+        self.dp_early_opt = self.dp
+        # Data parallel, eager, in halves, overlapped: the weight-gradient reductions of the two Regulation halves run on the SIDE stream, in
+        # front of the all-reduce that ships them -- beside the next backward launch of the main stream instead of between two of them (the
+        # main stream's chain loses two `k_reduce` launches).  Same kernels on the same data in the same order per bucket: same bits.
+        self.dp_side_reduce = (dp_side_reduce is None or bool(dp_side_reduce)) and self.halves and self.overlap_allreduce and not use_graph
         self._ev_mid = torch.cuda.Event()
         self._buckets = {}
         for b in (_lib.BUCKET_REG, _lib.BUCKET_PE) + ((_lib.BUCKET_REG_HI, _lib.BUCKET_REG_LO) if self.halves else ()):
@@ -248,63 +242,32 @@ class Trainer:
         self.timed_kernel = timed_kernel
         if timed_kernel in ("k_wgrad", "k_colsum", "k_adamw", "k_trunk_fwd", "k_trunk_bwd"):
             self.use_graph = False        # launched once per bucket: timed on the eager path, where every launch gets its events
-        # Measured and left off by default: AdamW inside the graph (scalars from device memory) costs +5 us per step (one
-        # more launch per bucket plus cf_adamw_set), and running the early bucket's update as a parallel branch under the
-        # Pairwise + Embedding backward costs +36 us -- its 116 MB stream evicts the L2-resident tables those
-        # latency-bound kernels live on.  The default is one eager launch over the whole range behind the graph.
-        self.opt_in_graph = opt_in_graph and timed_kernel != "k_adamw"
-        self.overlap_opt = overlap_opt and self.opt_in_graph
         # Single GPU: the Embedding + Pairwise bucket's gradient reduction (~300 latency-bound tiles, 21 us on a mostly idle chip)
         # and the Regulation + head bucket's AdamW (a 116 MB stream, 19 us) are independent of each other: ONE launch runs them
-        # side by side (cf_reduce_adamw_part), the small bucket's AdamW follows.  Three host calls per step instead of two.
-        self.merge_opt = bool(merge_opt) and not self.dp and not self.opt_in_graph and timed_kernel not in ("k_wgrad", "k_colsum", "k_adamw")
-        # Single GPU: the Regulation + head bucket's gradient reduction (55 us) depends on the Regulation backward only, the Pairwise +
-        # Embedding backward (k_trunk_bwd, 135 us on 192 of the 256 CUs) does not depend on it: with overlap_reduce the reduction is
-        # issued on the side stream BEHIND the trunk launch and runs beside it (CF_OVERLAP_REDUCE=1; see DESIGN.md for the numbers).
-        if overlap_reduce is None:
-            import os
-            overlap_reduce = os.environ.get("CF_OVERLAP_REDUCE", "0") != "0"
-        self.overlap_reduce = bool(overlap_reduce) and self.merge_opt
-        # Single GPU: AdamW in the EPILOGUE of the two gradient reductions (cf_reduce_opt_part): the tile that finishes a gradient
-        # element updates the parameter and its moments -- no optimiser launches, no second pass over gradients and state.  The step
-        # is then [graph: gather, forward, head, Regulation backward] -> reduction + AdamW of the Regulation + head bucket -> Pairwise +
-        # Embedding backward -> reduction + AdamW of their bucket.  The flat gradient buffer is only written with keep_grads=True.
-        # Bit-identical parameters and moments (tests/test_engine_gpu.py); CF_FUSE_OPT=0 restores the merged schedule above.
-        if fuse_opt is None:
-            import os
-            fuse_opt = os.environ.get("CF_FUSE_OPT", "1") != "0"
-        self.fuse_opt = (bool(fuse_opt) and self.merge_opt and not self.overlap_reduce and model._kws[0].get("n_layers", 1) == 1)
+        # side by side (cf_reduce_adamw_part), the small bucket's AdamW follows.
+        self.merge_opt = bool(merge_opt) and not self.dp and timed_kernel not in ("k_wgrad", "k_colsum", "k_adamw")
+        # Single GPU: AdamW in the EPILOGUE of the gradient reductions (cf_reduce_opt_part): the tile that finishes a gradient element
+        # updates the parameter and its moments -- no optimiser launches, no second pass over gradients and state.  Both buckets' tiles
+        # in ONE launch behind the whole backward pass (the Embedding + Pairwise bucket's ~300 latency-bound tiles fill the gaps of the
+        # Regulation bucket's 1,008).  The flat gradient buffer is only written with keep_grads=True.  Bit-identical parameters and
+        # moments (tests/test_engine_gpu.py).
+        self.fuse_opt = bool(fuse_opt) and self.merge_opt and model._kws[0].get("n_layers", 1) == 1
+        self.fuse_one = True          # (one fused reduction launch per step; bench.py reads it)
         self.keep_grads = bool(keep_grads)
-        # ... and both buckets' tiles in ONE launch behind the whole backward pass (the Embedding + Pairwise bucket's ~300 latency-bound
-        # tiles fill the gaps of the Regulation bucket's 1,008): [graph: gather, forward, head, both backward launches] -> reduction +
-        # AdamW.  7 launches, 2 host calls per step; 0.600 -> 0.590 ms.  fuse_one=False / CF_FUSE_ONE=0: one launch per bucket.
-        if fuse_one is None:
-            import os
-            fuse_one = os.environ.get("CF_FUSE_ONE", "1") != "0"
-        self.fuse_one = bool(fuse_one)
         # ... and part of the Regulation bucket's tiles as RIDERS of the trunk's backward launch (cf_rider_arm): the trunk's 192 workgroups
         # occupy one CU each for ~130 us of latency chains, the other 64 CUs reduce (and step) rider_tiles of that bucket's 1,008
         # weight-gradient tiles meanwhile, one tile per wave.  0.590 -> 0.564 ms; more than one tile per rider wave outlasts the trunk
-        # (768: 0.650 ms).  rider_tiles=0 / CF_RIDER_TILES=0: everything in the reduction launch.
-        if rider_tiles is None:
-            import os
-            rider_tiles = int(os.environ.get("CF_RIDER_TILES", "512"))
-        self.rider_tiles = int(rider_tiles) if self.fuse_opt and self.fuse_one else 0
+        # (768: 0.650 ms).  rider_tiles=0: everything in the reduction launch.
+        self.rider_tiles = (512 if rider_tiles is None else int(rider_tiles)) if self.fuse_opt else 0
         if self.rider_tiles > 0 and self._L.cf_rider_arm(model._handle, 0.0, 0.9, 0.999, 1e-8, 0.0, 1, 0, 0) != 0:
             self.rider_tiles = 0          # (configurations without the fused trunk kernels)
         # riders fit on the CUs the trunk's n_res x B one-per-CU workgroups leave idle: sized from the device's CU count (256 on an
         # MI355X; a partition or another part has fewer / more), none when the trunk alone fills the device
         self._n_cu = int(self._L.cf_cu_count(model._handle)) or 256
         # ... and the fused optimiser keeps the tiled copies of the Embedding + Pairwise weights fresh (its epilogue writes every stepped
-        # element in both layouts): no re-tiling launch in front of a step -- 6 -> 5 launches where no batch gather shares that launch.
-        # keep_tiled=False / CF_KEEP_TILED=0: every forward pass re-tiles (model.keep_tiled has the contract).
-        if keep_tiled is None:
-            import os
-            keep_tiled = os.environ.get("CF_KEEP_TILED", "1") != "0"
-        # Data parallel (round 5): the separate AdamW launch over the Embedding + Pairwise bucket writes the tiled copies as well
-        # (k_adamw_tiled), so the mode -- and the step without a re-tiling launch in front -- holds there too.
-        tiled_dp = self.dp and not self.opt_in_graph
-        self.keep_tiled = model.keep_tiled(True) if (keep_tiled and (self.fuse_opt or tiled_dp)) else (model.keep_tiled(False) and False)
+        # element in both layouts): no re-tiling launch in front of a step.  Data parallel: the separate AdamW launch over the Embedding +
+        # Pairwise bucket writes them as well (k_adamw_tiled).  keep_tiled=False: every forward pass re-tiles (model.keep_tiled has the contract).
+        self.keep_tiled = model.keep_tiled(bool(keep_tiled) and (self.fuse_opt or self.dp))
         self._t_ms, self._t_n = 0.0, 0
         _lib.check(self._L.cf_timing_select(model._handle, timed_kernel.encode() if timed_kernel else None), "cf_timing_select")
 
@@ -334,7 +297,7 @@ class Trainer:
 
     def _seq_early(self, slot, st, reduce=True, gather=True):     # [batch gather,] forward, loss, head + Regulation backward, [step log,] Regulation + head gradient bucket
         m, L = self.model, self._L
-        feed = getattr(slot, "feed", None) if gather else None      # (gather=False: the batch is in place already, see _pregather)
+        feed = getattr(slot, "feed", None) if gather else None      # (gather=False: the batch is in place already, see _step_fused)
         if feed is not None:
             # (shares a launch with the prologue of the forward below: cf_gather_batch_fwd)
             _lib.check(L.cf_gather_batch_fwd(m._handle, C.byref(feed.struct), feed.order.data_ptr(), feed.cursor.data_ptr(),
@@ -357,15 +320,7 @@ class Trainer:
         if reduce:
             self._reduce(slot, st, _lib.BUCKET_REG_LO)
 
-    def _seq_main(self, slot, st):      # single GPU, merged optimiser: everything up to the Pairwise + Embedding backward (its bucket is reduced beside AdamW)
-        if self.overlap_reduce:
-            side = self.side.cuda_stream
-            self._seq_early(slot, st, reduce=False)
-            self._wait(side, st)                             # fork behind the Regulation backward
-            self._part(slot, st, 4)                          # the trunk's 192 big workgroups are dispatched first ...
-            self._reduce(slot, side, _lib.BUCKET_REG)        # ... the reduction tiles fill what is left
-            self._wait(st, side)                             # join
-            return
+    def _seq_main(self, slot, st):      # merged optimiser: everything up to the Pairwise + Embedding backward (its bucket is reduced beside AdamW)
         self._seq_early(slot, st)
         self._part(slot, st, 4)
 
@@ -373,30 +328,11 @@ class Trainer:
         self._part(slot, st, 4)
         self._reduce(slot, st, _lib.BUCKET_PE)
 
-    def _opt(self, bucket, st):
-        _lib.check(self._L.cf_adamw_step_dev(self.model._handle, bucket, st), "cf_adamw_step_dev")
-
-    def _wait(self, waiter, signaller):
-        _lib.check(self._L.cf_stream_wait(self.model._handle, waiter, signaller), "cf_stream_wait")
-
-    def _seq_all(self, slot, st, opt=True):
-        """The whole single-GPU step.  With `opt`, AdamW of the early bucket (78 % of the 150 MB of optimiser traffic) runs
-        on the side stream under the Pairwise + Embedding backward -- an HBM stream next to latency-bound kernels."""
-        side = self.side.cuda_stream
+    def _seq_all(self, slot, st):       # the whole backward pass with every gradient reduction, no optimiser
         self._seq_early(slot, st)
         if self.halves:
             self._seq_mid(slot, st)
-        if opt:
-            if self.overlap_opt:
-                self._wait(side, st)
-                self._opt(_lib.BUCKET_REG, side)
-            else:
-                self._opt(_lib.BUCKET_REG, st)
         self._seq_late(slot, st)
-        if opt:
-            self._opt(_lib.BUCKET_PE, st)
-            if self.overlap_opt:
-                self._wait(st, side)
 
     def _capture(self, fn, slot, st):
         m, L = self.model, self._L
@@ -411,179 +347,168 @@ class Trainer:
     def _launch(self, gid, st):
         _lib.check(self._L.cf_graph_launch(self.model._handle, gid, st), "cf_graph_launch")
 
+    def _hp(self):      # AdamW hyper-parameters of the coming step (the caller advances model._step)
+        return (self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.model._step + 1)
+
+    # ---- one step
     def step(self, slot):
         """One optimisation step on a staged batch (train.py:182-196)."""
         with torch.cuda.stream(self.stream):
-            return self._step(slot)
-
-    def _step(self, slot):
-        m, L = self.model, self._L
-        st = self._stream()
-        # keep_tiled is a mode of the MODEL, the captured graphs are this Trainer's: another Trainer on the same model may have switched the
-        # mode since (its constructor does).  A graph captured with the mode on holds no Embedding + Pairwise re-tiling and would replay on
-        # stale tiled weights once the optimiser stops writing them -- so the mode this Trainer was built (and captured) with is put back
-        # in front of every step; switching it drops the version stamp, and _sync_tiled below rebuilds the copies once.
-        if bool(getattr(m, "_keep_tiled", False)) != bool(self.keep_tiled):
-            m.keep_tiled(self.keep_tiled)
-        m._sync_tiled(st)          # (keep_tiled: parameters written through torch since the last step are re-tiled here, also in front of a graph replay)
-        feed = getattr(slot, "feed", None)
-        if feed is not None:
-            if feed.taken >= feed.n_batches:           # the device-side bound would skip the gather; refuse on the host, loudly
+            m, st = self.model, self._stream()
+            # keep_tiled is a mode of the MODEL, the captured graphs are this Trainer's: another Trainer on the same model may have switched the
+            # mode since (its constructor does).  A graph captured with the mode on holds no Embedding + Pairwise re-tiling and would replay on
+            # stale tiled weights once the optimiser stops writing them -- so the mode this Trainer was built (and captured) with is put back
+            # in front of every step; switching it drops the version stamp, and _sync_tiled below rebuilds the copies once.
+            if bool(getattr(m, "_keep_tiled", False)) != bool(self.keep_tiled):
+                m.keep_tiled(self.keep_tiled)
+            m._sync_tiled(st)          # (keep_tiled: parameters written through torch since the last step are re-tiled here, also in front of a graph replay)
+            feed = getattr(slot, "feed", None)
+            if feed is not None and feed.taken >= feed.n_batches:      # the device-side bound would skip the gather; refuse on the host, loudly
                 raise RuntimeError("Trainer.step: the feed's epoch of %d batches is exhausted (call begin_epoch)" % feed.n_batches)
-        # Fused single-GPU step fed from an EpochFeed: the batch of step k + 1 is gathered inside step k's last launch (cf_gather_batch_next,
-        # behind the reduction tiles), the first batch of an epoch by a launch of its own (cf_gather_batch_only): no launch in front of a step.
-        pre = feed is not None and self.fuse_opt and self.fuse_one
-        gargs = None
-        if pre:
-            gargs = (m._handle, C.byref(feed.struct), feed.order.data_ptr(), feed.cursor.data_ptr(), C.byref(slot.struct), slot.label.data_ptr(), st)
-        if self.use_graph and slot.graph is None:
-            self._seq_all(slot, st, opt=False)         # eager once (validates the arguments before anything is captured)
-            if getattr(slot, "feed", None) is not None:
-                slot.feed.rewind()                     # the validation pass consumed a batch: rewind (no parameter was updated)
-            torch.cuda.synchronize()
-            first = self._seq_early if self.dp else (self._seq_main if self.merge_opt else (lambda s_, t_: self._seq_all(s_, t_, opt=self.opt_in_graph)))
-            if self.fuse_opt and self.fuse_one and self.rider_tiles == 0:
-                first = lambda s_, t_: (self._seq_early(s_, t_, reduce=False, gather=not pre), self._part(s_, t_, 4))
-            elif self.fuse_opt:
-                first = lambda s_, t_: self._seq_early(s_, t_, reduce=False, gather=not pre)
-            if pre:      # (the captured trunk launch advances the cursor because a gathered batch is waiting at capture time)
-                _lib.check(L.cf_gather_batch_only(*gargs), "cf_gather_batch_only")
-                feed.pregathered = True
-            slot.graph = {"first": self._capture(first, slot, st), "mid": self._capture(self._seq_mid, slot, st) if self.halves else None,
-                          "late": self._capture(self._seq_late, slot, st) if self.dp else None}
-        if feed is not None:
-            feed.taken += 1
-        oig = self.opt_in_graph
-        if oig:      # this step's AdamW scalars go to device memory before anything is replayed
-            m._step += 1
-            _lib.check(L.cf_adamw_set(m._handle, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, m._step, st), "cf_adamw_set")
-        if self.fuse_opt:
-            if pre and not feed.pregathered:           # first step of an epoch
-                _lib.check(L.cf_gather_batch_only(*gargs), "cf_gather_batch_only")
-            if self.use_graph:
-                self._launch(slot.graph["first"], st)
+            # Fused step fed from an EpochFeed: the batch of step k + 1 is gathered inside step k's last launch (cf_gather_batch_next,
+            # behind the reduction tiles), the first batch of an epoch by a launch of its own (cf_gather_batch_only): no launch in front of a step.
+            gargs = None
+            if feed is not None and self.fuse_opt:
+                gargs = (m._handle, C.byref(feed.struct), feed.order.data_ptr(), feed.cursor.data_ptr(), C.byref(slot.struct), slot.label.data_ptr(), st)
+            if self.use_graph and slot.graph is None:
+                self._capture_graphs(slot, st, gargs)
+            if feed is not None:
+                feed.taken += 1
+            if self.fuse_opt:
+                self._step_fused(slot, st, gargs)
+            elif self.dp:
+                self._step_dp(slot, st)
+            elif self.merge_opt:
+                self._step_merged(slot, st)
             else:
-                self._seq_early(slot, st, reduce=False, gather=not pre)
-            if pre:                                    # the next step's batch rides in this step's reduction launch
-                feed.pregathered = feed.taken < feed.n_batches
-                if feed.pregathered:
-                    _lib.check(L.cf_gather_batch_next(*gargs), "cf_gather_batch_next")
-            m._step += 1
-            hp = (self.lr, self.betas[0], self.betas[1], self.eps, self.wd, m._step)
-            kg = 1 if self.keep_grads else 0
-            if self.fuse_one and self.rider_tiles > 0:
-                # riders: part of the Regulation bucket's tiles (with their AdamW) inside the trunk's backward launch, on the CUs it leaves idle
-                # (one tile per rider wave, eight waves per idle CU: 256 CUs minus the trunk's n_res x B workgroups)
-                n_rd = min(self.rider_tiles, 8 * max(0, self._n_cu - len(m.binsizes) * slot.B))
-                _lib.check(L.cf_rider_arm(m._handle, *hp, kg, n_rd), "cf_rider_arm")      # (n_rd = 0 disarms: no idle CU)
-                self._part(slot, st, 4)
-                _lib.check(L.cf_reduce_opt_part(m._handle, slot.B, _lib.BUCKET_REG | _lib.BUCKET_PE, *hp, kg, st), "cf_reduce_opt_part")
-            elif self.fuse_one:       # both buckets' tiles in ONE launch behind the whole backward pass
-                if not self.use_graph:
-                    self._part(slot, st, 4)
-                _lib.check(L.cf_reduce_opt_part(m._handle, slot.B, _lib.BUCKET_REG | _lib.BUCKET_PE, *hp, kg, st), "cf_reduce_opt_part")
-            else:
-                _lib.check(L.cf_reduce_opt_part(m._handle, slot.B, _lib.BUCKET_REG, *hp, kg, st), "cf_reduce_opt_part")
-                self._part(slot, st, 4)
-                _lib.check(L.cf_reduce_opt_part(m._handle, slot.B, _lib.BUCKET_PE, *hp, kg, st), "cf_reduce_opt_part")
-        elif not self.dp and self.merge_opt:
-            if self.use_graph:
-                self._launch(slot.graph["first"], st)
-            else:
-                self._seq_main(slot, st)
-            m._step += 1
-            hp = (self.lr, self.betas[0], self.betas[1], self.eps, self.wd, m._step)
-            _lib.check(L.cf_reduce_adamw_part(m._handle, slot.B, _lib.BUCKET_PE, *hp, _lib.BUCKET_REG, st), "cf_reduce_adamw_part")
-            _lib.check(L.cf_adamw_step_part(m._handle, *hp, _lib.BUCKET_PE, st), "cf_adamw_step_part")
-        elif not self.dp:
-            if self.use_graph:
-                self._launch(slot.graph["first"], st)
-            else:
-                self._seq_all(slot, st, opt=oig)
+                self._step_separate(slot, st)
+            self._last = slot
+            m._mark_grads(self.fuse_opt and not self.keep_grads)
+            return slot.logits, slot.loss
+
+    def _capture_graphs(self, slot, st, gargs):
+        """First step on a slot under use_graph: one eager pass validates the arguments, then the graph pieces are captured."""
+        self._seq_all(slot, st)
+        if getattr(slot, "feed", None) is not None:
+            slot.feed.rewind()                     # the validation pass consumed a batch: rewind (no parameter was updated)
+        torch.cuda.synchronize()
+        if self.fuse_opt:          # the trunk's backward joins the graph only when no rider has to be armed in front of it
+            def first(s_, t_):
+                self._seq_early(s_, t_, reduce=False, gather=gargs is None)
+                if self.rider_tiles == 0:
+                    self._part(s_, t_, 4)
         else:
-            side_red = self.dp_side_reduce and not self.use_graph
-            if self.use_graph:
-                self._launch(slot.graph["first"], st)
-            else:
-                self._seq_early(slot, st, reduce=not side_red)
-            # (dp_early_opt: AdamW over the Regulation + head range on the SIDE stream, straight behind that range's last all-reduce -- under the
-            #  Pairwise + Embedding backward -- instead of on the main stream behind everything: its streaming loads and stores (CF_ADAM_NT) no longer
-            #  sweep the L2s the trunk works in, which is what made this lose in round 3)
-            early_opt = self.dp_early_opt and not oig and self.overlap_allreduce
-            hp_next = (self.lr, self.betas[0], self.betas[1], self.eps, self.wd, m._step + 1)
+            first = self._seq_early if self.dp else (self._seq_main if self.merge_opt else self._seq_all)
+        if gargs is not None:      # (the captured trunk launch advances the cursor because a gathered batch is waiting at capture time)
+            _lib.check(self._L.cf_gather_batch_only(*gargs), "cf_gather_batch_only")
+            slot.feed.pregathered = True
+        slot.graph = {"first": self._capture(first, slot, st), "mid": self._capture(self._seq_mid, slot, st) if self.halves else None,
+                      "late": self._capture(self._seq_late, slot, st) if self.dp else None}
 
-            def early_allreduce(bucket=_lib.BUCKET_REG, ev=None, last=True):      # an early bucket is complete: all-reduce it on the side stream
-                ev = ev or self._ev_fork
-                ev.record(self.stream)
-                with torch.cuda.stream(self.side):
-                    self.side.wait_event(ev)
-                    if side_red:      # the bucket's weight-gradient tiles, here instead of on the main stream (dp_side_reduce)
-                        self._reduce(slot, self.side.cuda_stream, bucket)
-                    torch.distributed.all_reduce(self._buckets[bucket], group=self.pg)     # SUM; dloss carries 1/world
-                    if last:
-                        if self.overlap_opt:
-                            self._opt(_lib.BUCKET_REG, self.side.cuda_stream)
-                        elif early_opt:
-                            _lib.check(L.cf_adamw_step_part(m._handle, *hp_next, _lib.BUCKET_REG, self.side.cuda_stream), "cf_adamw_step_part")
-                        self._ev_join.record(self.side)
+    def _step_fused(self, slot, st, gargs):
+        """[graph: gather, forward, head + Regulation backward] -> riders armed -> trunk backward -> one reduction + AdamW launch."""
+        m, L, feed = self.model, self._L, getattr(slot, "feed", None)
+        if gargs is not None and not feed.pregathered:      # first step of an epoch
+            _lib.check(L.cf_gather_batch_only(*gargs), "cf_gather_batch_only")
+        if self.use_graph:
+            self._launch(slot.graph["first"], st)
+        else:
+            self._seq_early(slot, st, reduce=False, gather=gargs is None)
+        if gargs is not None:                               # the next step's batch rides in this step's reduction launch
+            feed.pregathered = feed.taken < feed.n_batches
+            if feed.pregathered:
+                _lib.check(L.cf_gather_batch_next(*gargs), "cf_gather_batch_next")
+        hp, kg = self._hp(), 1 if self.keep_grads else 0
+        m._step += 1
+        if self.rider_tiles > 0:
+            # riders: part of the Regulation bucket's tiles (with their AdamW) inside the trunk's backward launch, on the CUs it leaves idle
+            # (one tile per rider wave, eight waves per idle CU: 256 CUs minus the trunk's n_res x B workgroups)
+            n_rd = min(self.rider_tiles, 8 * max(0, self._n_cu - len(m.binsizes) * slot.B))
+            _lib.check(L.cf_rider_arm(m._handle, *hp, kg, n_rd), "cf_rider_arm")      # (n_rd = 0 disarms: no idle CU)
+            self._part(slot, st, 4)
+        elif not self.use_graph:
+            self._part(slot, st, 4)
+        _lib.check(L.cf_reduce_opt_part(m._handle, slot.B, _lib.BUCKET_REG | _lib.BUCKET_PE, *hp, kg, st), "cf_reduce_opt_part")
 
-            if self.halves:             # the upper half + head are on the wire while the lower half's backward runs
-                if self.overlap_allreduce:
-                    early_allreduce(_lib.BUCKET_REG_HI, self._ev_fork, last=False)
-                if self.use_graph:
-                    self._launch(slot.graph["mid"], st)
-                else:
-                    self._seq_mid(slot, st, reduce=not side_red)
-                if self.overlap_allreduce:
-                    early_allreduce(_lib.BUCKET_REG_LO, self._ev_mid, last=True)
-            elif self.overlap_allreduce:
-                early_allreduce()       # ... under the rest of the backward pass
+    def _step_merged(self, slot, st):
+        """[graph: the backward pass up to the Pairwise + Embedding bucket] -> its reduction beside the Regulation + head AdamW -> its AdamW."""
+        m, L = self.model, self._L
+        if self.use_graph:
+            self._launch(slot.graph["first"], st)
+        else:
+            self._seq_main(slot, st)
+        hp = self._hp()
+        m._step += 1
+        _lib.check(L.cf_reduce_adamw_part(m._handle, slot.B, _lib.BUCKET_PE, *hp, _lib.BUCKET_REG, st), "cf_reduce_adamw_part")
+        _lib.check(L.cf_adamw_step_part(m._handle, *hp, _lib.BUCKET_PE, st), "cf_adamw_step_part")
+
+    def _step_separate(self, slot, st):
+        """[graph: the whole backward pass with its reductions] -> AdamW launches of their own."""
+        if self.use_graph:
+            self._launch(slot.graph["first"], st)
+        else:
+            self._seq_all(slot, st)
+        self.model.adamw_step(self.lr, self.betas, self.eps, self.wd)
+
+    def _step_dp(self, slot, st):
+        """The early bucket(s) all-reduced on the side stream under the rest of the backward pass (overlap_allreduce) or behind it."""
+        m, L, side = self.model, self._L, self.side
+        side_red = self.dp_side_reduce
+        if self.use_graph:
+            self._launch(slot.graph["first"], st)
+        else:
+            self._seq_early(slot, st, reduce=not side_red)
+        hp = self._hp()
+
+        def early_allreduce(bucket, ev, last):      # an early bucket is complete: all-reduce it on the side stream
+            ev.record(self.stream)
+            with torch.cuda.stream(side):
+                side.wait_event(ev)
+                if side_red:      # the bucket's weight-gradient tiles, here instead of on the main stream
+                    self._reduce(slot, side.cuda_stream, bucket)
+                torch.distributed.all_reduce(self._buckets[bucket], group=self.pg)     # SUM; dloss carries 1/world
+                if last:
+                    if self.overlap_allreduce:      # early AdamW over the Regulation + head range, under the Pairwise + Embedding backward
+                        _lib.check(L.cf_adamw_step_part(m._handle, *hp, _lib.BUCKET_REG, side.cuda_stream), "cf_adamw_step_part")
+                    self._ev_join.record(side)
+
+        early = (((_lib.BUCKET_REG_HI, self._ev_fork, False), (_lib.BUCKET_REG_LO, self._ev_mid, True)) if self.halves
+                 else ((_lib.BUCKET_REG, self._ev_fork, True),))
+        if self.overlap_allreduce:      # (in halves: the upper half + head are on the wire while the lower half's backward runs)
+            early_allreduce(*early[0])
+        if self.halves:
             if self.use_graph:
-                self._launch(slot.graph["late"], st)
+                self._launch(slot.graph["mid"], st)
             else:
-                self._seq_late(slot, st)
-            if not self.overlap_allreduce:      # ... behind it (serialised schedule)
-                if self.halves:
-                    early_allreduce(_lib.BUCKET_REG_HI, self._ev_fork, last=False)
-                    early_allreduce(_lib.BUCKET_REG_LO, self._ev_mid, last=True)
-                else:
-                    early_allreduce()
-            if oig:
-                torch.distributed.all_reduce(self._buckets[_lib.BUCKET_PE], group=self.pg)
-                self._opt(_lib.BUCKET_PE, st)
-                self.stream.wait_event(self._ev_join)
-                if not self.overlap_opt:
-                    self._opt(_lib.BUCKET_REG, st)
-            elif early_opt:
-                # the Regulation + head range is stepped on the side stream (early_allreduce above): nothing is left for the main stream but the late
-                # bucket, so its all-reduce is issued from HERE -- main -> RCCL's stream -> main instead of main -> side -> RCCL -> side -> main: two
-                # cross-stream event hops less on the tail of every step (the transfers themselves queue behind the early ones on RCCL's stream)
-                torch.distributed.all_reduce(self._buckets[_lib.BUCKET_PE], group=self.pg)
-                self.stream.wait_event(self._ev_join)            # early buckets reduced and stepped
-                m._step += 1
-                hp = (self.lr, self.betas[0], self.betas[1], self.eps, self.wd, m._step)
-                _lib.check(L.cf_adamw_step_part(m._handle, *hp, _lib.BUCKET_PE, st), "cf_adamw_step_part")
-            else:
-                # the late bucket's all-reduce goes to the side stream as well (behind the early one) and the main stream
-                # steps the early bucket meanwhile: only the late bucket's 6 us of AdamW wait for the second all-reduce
-                ev_late, ev_done = self._ev_late, self._ev_done
-                ev_late.record(self.stream)
-                with torch.cuda.stream(self.side):
-                    self.side.wait_event(ev_late)
-                    torch.distributed.all_reduce(self._buckets[_lib.BUCKET_PE], group=self.pg)
-                    ev_done.record(self.side)
-                self.stream.wait_event(self._ev_join)            # early bucket reduced (dp_early_opt: and stepped)
-                m._step += 1
-                hp = (self.lr, self.betas[0], self.betas[1], self.eps, self.wd, m._step)
-                if not early_opt:
-                    _lib.check(L.cf_adamw_step_part(m._handle, *hp, _lib.BUCKET_REG, st), "cf_adamw_step_part")
-                self.stream.wait_event(ev_done)                  # late bucket reduced
-                _lib.check(L.cf_adamw_step_part(m._handle, *hp, _lib.BUCKET_PE, st), "cf_adamw_step_part")
-        if not oig and not self.dp and not self.merge_opt:
-            m.adamw_step(self.lr, self.betas, self.eps, self.wd)
-        self._last = slot
-        m._mark_grads(self.fuse_opt and not self.keep_grads)
-        return slot.logits, slot.loss
+                self._seq_mid(slot, st, reduce=not side_red)
+            if self.overlap_allreduce:
+                early_allreduce(*early[1])
+        if self.use_graph:
+            self._launch(slot.graph["late"], st)
+        else:
+            self._seq_late(slot, st)
+        if self.overlap_allreduce:
+            # the Regulation + head range is stepped on the side stream: nothing is left for the main stream but the late bucket, so its
+            # all-reduce is issued from HERE (main -> RCCL's stream -> main: two cross-stream event hops less than through the side stream)
+            torch.distributed.all_reduce(self._buckets[_lib.BUCKET_PE], group=self.pg)
+            self.stream.wait_event(self._ev_join)            # early buckets reduced and stepped
+            m._step += 1
+            _lib.check(L.cf_adamw_step_part(m._handle, *hp, _lib.BUCKET_PE, st), "cf_adamw_step_part")
+            return
+        # serialised: every all-reduce behind the whole backward pass; the late bucket's goes to the side stream as well (behind the early
+        # ones) and the main stream steps the early range meanwhile: only the late bucket's 6 us of AdamW wait for the last all-reduce
+        for b in early:
+            early_allreduce(*b)
+        self._ev_late.record(self.stream)
+        with torch.cuda.stream(side):
+            side.wait_event(self._ev_late)
+            torch.distributed.all_reduce(self._buckets[_lib.BUCKET_PE], group=self.pg)
+            self._ev_done.record(side)
+        self.stream.wait_event(self._ev_join)                # early buckets reduced
+        m._step += 1
+        _lib.check(L.cf_adamw_step_part(m._handle, *hp, _lib.BUCKET_REG, st), "cf_adamw_step_part")
+        self.stream.wait_event(self._ev_done)                # late bucket reduced
+        _lib.check(L.cf_adamw_step_part(m._handle, *hp, _lib.BUCKET_PE, st), "cf_adamw_step_part")
 
     def evaluate(self, slot):
         m = self.model

@@ -116,3 +116,19 @@ def test_no_gpu_means_loud_failure_not_fallback():
         assert "no CPU fallback" in str(e)
     else:
         raise AssertionError("expected a RuntimeError without a GPU")
+
+
+def test_trainer_offers_no_rejected_schedule():
+    """The step schedules that were measured and rejected stay gone: no Trainer keyword and no environment variable read by the
+    engine brings one back (the data-parallel serialised schedule keeps CF_DP_OVERLAP=0)."""
+    import inspect
+    from chromoformer_amd.engine import Trainer
+    params = set(inspect.signature(Trainer).parameters)
+    removed = {"opt_in_graph", "overlap_opt", "overlap_reduce", "fuse_one", "dp_halves", "dp_early_opt"}
+    assert not params & removed, params & removed
+    assert {"overlap_allreduce", "dp_side_reduce", "merge_opt", "fuse_opt", "rider_tiles", "keep_tiled", "keep_grads"} <= params
+    src = open(os.path.join(ROOT, "chromoformer_amd", "engine.py")).read()
+    for var in ("CF_OVERLAP_REDUCE", "CF_FUSE_OPT", "CF_FUSE_ONE", "CF_RIDER_TILES", "CF_KEEP_TILED", "CF_DP_HALVES", "CF_DP_EARLY_OPT",
+                "CF_DP_SIDE_REDUCE"):
+        assert var not in src, var
+    assert "CF_DP_OVERLAP" in src

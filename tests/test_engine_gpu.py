@@ -12,11 +12,13 @@ pytestmark = pytest.mark.gpu
 B = 8
 
 
-def _run(steps=3, **kw):
+def _run(steps=3, expect_halves=None, **kw):
     from chromoformer_amd import ChromoformerClassifier
     from chromoformer_amd.engine import Trainer
     model = ChromoformerClassifier(seed=42, max_batch=B).cuda(0)
     trainer = Trainer(model, lr=3e-5, **kw)
+    if expect_halves is not None:
+        assert trainer.halves is expect_halves, kw
     slots = [trainer.stage(orc.synthetic_batch(B, seed=7 + i, regime="realistic")) for i in range(2)]
     losses = []
     for i in range(steps):
@@ -31,27 +33,24 @@ def _run(steps=3, **kw):
     return sd, [float(x) for x in losses]
 
 
-def test_graph_replay_and_event_timing_are_bit_identical_to_the_eager_step():
+def test_graph_replay_and_event_timing_match_the_eager_step_bit_for_bit():
     ref, ref_loss = _run(use_graph=False)
-    for kw in (dict(use_graph=True), dict(use_graph=True, timed_kernel="k_reg_bwd"), dict(use_graph=False, timed_kernel="k_wgrad"),
-               dict(use_graph=True, opt_in_graph=True), dict(use_graph=True, opt_in_graph=True, overlap_opt=True),
-               dict(use_graph=False, opt_in_graph=True, overlap_opt=True)):
+    for kw in (dict(use_graph=True), dict(use_graph=True, timed_kernel="k_reg_bwd"), dict(use_graph=False, timed_kernel="k_wgrad")):
         got, loss = _run(**kw)
         assert loss == ref_loss, kw
         for k in ref:
             assert torch.equal(ref[k], got[k]), (kw, k)
 
 
-def test_round3_schedules_and_switches_are_bit_identical():
-    """The merged launch (one bucket's reduction beside the other bucket's AdamW), the reduction overlapped with the trunk backward on
-    the side stream, and the library switches that only move work between launches -- all the same arithmetic in the same order."""
+def test_single_gpu_schedules_and_library_switches_are_bit_identical():
+    """The merged launch (one bucket's reduction beside the other bucket's AdamW), the fused reduction + AdamW, and the library switches
+    that only move work between launches -- all the same arithmetic in the same order as the separate launches."""
     import os
     ref, ref_loss = _run(use_graph=False, merge_opt=False)
     for kw in (dict(use_graph=False, merge_opt=True, fuse_opt=False), dict(use_graph=True, merge_opt=True, fuse_opt=False),
-               dict(use_graph=True, merge_opt=True, overlap_reduce=True), dict(use_graph=False, merge_opt=True, overlap_reduce=True),
                # AdamW in the epilogue of the gradient reductions (the default single-GPU step), with and without the gradient stores
                dict(use_graph=False, fuse_opt=True), dict(use_graph=True, fuse_opt=True), dict(use_graph=True, fuse_opt=True, keep_grads=True),
-               dict(use_graph=True, fuse_opt=True, fuse_one=False), dict(use_graph=False, fuse_opt=True, fuse_one=False, keep_grads=True),
+               dict(use_graph=False, fuse_opt=True, keep_grads=True),
                # without / with riders in the trunk's backward launch (B = 8: 16 teams; 1,008 uniform tiles)
                dict(use_graph=True, fuse_opt=True, rider_tiles=0), dict(use_graph=True, fuse_opt=True, rider_tiles=100, keep_grads=True),
                dict(use_graph=False, fuse_opt=True, rider_tiles=5000)):
@@ -120,43 +119,50 @@ def test_grad_buckets_partition_the_active_range():
         assert (d["offset"] >= hi[0]) == upper, d["name"]
 
 
-def test_one_rank_rccl_all_reduce_in_the_step():
+def test_one_rank_rccl_schedules_are_bit_identical(monkeypatch):
     import torch.distributed as dist
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
     ref, ref_loss = _run(use_graph=True)
+    # the two-bucket schedule runs where the Regulation backward does not come in halves: the layer-by-layer Regulation kernels
+    # (CF_REG_FUSED=0, read when the model is constructed) -- compared with the single-GPU separate launches on the same kernels
+    with monkeypatch.context() as mp:
+        mp.setenv("CF_REG_FUSED", "0")
+        ref0, ref0_loss = _run(use_graph=False, merge_opt=False)
     dist.init_process_group("nccl", init_method="tcp://127.0.0.1:%d" % port, rank=0, world_size=1, device_id=torch.device("cuda", 0))
     try:
-        got, loss = _run(use_graph=True, world_size=1, process_group=dist.group.WORLD)
-        got2, loss2 = _run(use_graph=False, world_size=1, process_group=dist.group.WORLD, timed_kernel="k_reg_bwd")
-        got3, loss3 = _run(use_graph=True, world_size=1, process_group=dist.group.WORLD, opt_in_graph=True, overlap_opt=True)
+        dp = dict(world_size=1, process_group=dist.group.WORLD)
+        got, loss = _run(use_graph=True, expect_halves=True, **dp)
+        got2, loss2 = _run(use_graph=False, timed_kernel="k_reg_bwd", **dp)
         # serialised schedule: both all-reduces behind the whole backward pass (Trainer(overlap_allreduce=False) / CF_DP_OVERLAP=0)
-        got4, loss4 = _run(use_graph=True, world_size=1, process_group=dist.group.WORLD, overlap_allreduce=False)
-        got5, loss5 = _run(use_graph=False, world_size=1, process_group=dist.group.WORLD, overlap_allreduce=False, opt_in_graph=True)
-        # the schedules above send the Regulation + head bucket in two halves (round 5: the upper layers' gradients are on the wire while the
-        # lower half of the Regulation backward runs); the two-bucket schedule of rounds 2-4, overlapped and serialised, eager and replayed
-        more = [_run(use_graph=g, world_size=1, process_group=dist.group.WORLD, overlap_allreduce=o, dp_halves=False)
-                for g, o in ((True, True), (False, True), (True, False))]
-        more.append(_run(use_graph=False, world_size=1, process_group=dist.group.WORLD, overlap_allreduce=True))      # halves, eager
-        # (round 6: that one reduces the two Regulation halves' weight gradients on the side stream, beside the next backward launch; the round-5
-        #  form with every reduction on the main stream: dp_side_reduce=False / CF_DP_SIDE_REDUCE=0)
-        more.append(_run(use_graph=False, world_size=1, process_group=dist.group.WORLD, dp_side_reduce=False))
-        more.append(_run(use_graph=False, world_size=1, process_group=dist.group.WORLD, dp_side_reduce=True, dp_early_opt=False))
-        # (all of the above step the Regulation + head range on the side stream, straight behind its last all-reduce; the round-4 form, on the main
-        #  stream behind everything: dp_early_opt=False / CF_DP_EARLY_OPT=0)
-        more += [_run(use_graph=g, world_size=1, process_group=dist.group.WORLD, dp_early_opt=False, dp_halves=hv) for g, hv in ((True, True), (False, False))]
+        got4, loss4 = _run(use_graph=True, overlap_allreduce=False, **dp)
+        got5, loss5 = _run(use_graph=False, overlap_allreduce=False, **dp)
+        # the schedules above send the Regulation + head bucket in two halves (the upper layers' gradients are on the wire while the
+        # lower half of the Regulation backward runs)
+        more = [_run(use_graph=False, overlap_allreduce=True, expect_halves=True, **dp)]      # halves, eager
+        # (that one reduces the two Regulation halves' weight gradients on the side stream, beside the next backward launch; the form with every
+        #  reduction on the main stream: dp_side_reduce=False)
+        more.append(_run(use_graph=False, dp_side_reduce=False, **dp))
+        # the two-bucket schedule, overlapped and serialised, eager and replayed
+        with monkeypatch.context() as mp:
+            mp.setenv("CF_REG_FUSED", "0")
+            two = [_run(use_graph=g, overlap_allreduce=o, expect_halves=False, **dp) for g in (True, False) for o in (True, False)]
     finally:
         dist.destroy_process_group()
-    assert loss == ref_loss and loss2 == ref_loss and loss3 == ref_loss and loss4 == ref_loss and loss5 == ref_loss
+    assert loss == ref_loss and loss2 == ref_loss and loss4 == ref_loss and loss5 == ref_loss
     for k in ref:
-        assert torch.equal(ref[k], got[k]) and torch.equal(ref[k], got2[k]) and torch.equal(ref[k], got3[k]), k
+        assert torch.equal(ref[k], got[k]) and torch.equal(ref[k], got2[k]), k
         assert torch.equal(ref[k], got4[k]) and torch.equal(ref[k], got5[k]), k
     for sd, ls in more:
         assert ls == ref_loss
         for k in ref:
             assert torch.equal(ref[k], sd[k]), k
+    for sd, ls in two:
+        assert ls == ref0_loss
+        for k in ref0:
+            assert torch.equal(ref0[k], sd[k]), k
 
 
 def test_roofline_of_the_halved_regulation_backward_agrees_with_the_single_launch():

@@ -4,7 +4,7 @@ synchronisation, so that two runs can be compared step by step.  Round 5 used it
 run of ten (stale logits, every gradient of the step wrong) -- the head-ride arrival counters were zeroed by a workgroup at launch start and
 rewound by the last arriver; since then they are monotonic (csrc/cf_head_ride.h).
    python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 tools/dp_feed_determinism.py out.pt 7
-   (repeat, then compare the "sums" / "losses" of the saved files; DBG_EVAL=0, DBG_LAST=n, DP_GRAPH=0, CF_DP_HALVES=0 vary the run)"""
+   (repeat, then compare the "sums" / "losses" of the saved files; DBG_EVAL=0, DBG_LAST=n, DP_GRAPH=0, CF_REG_FUSED=0 vary the run)"""
 import os, sys, torch, torch.distributed as dist
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from chromoformer_amd import ChromoformerClassifier
