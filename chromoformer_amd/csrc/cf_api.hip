@@ -3,6 +3,7 @@
 // include/chromoformer_hip.h.  No torch, no allocation on the hot path.
 #include "../../include/chromoformer_hip.h"
 #include "cf_kernels.h"
+#include "cf_input_grad.h"
 
 #include <algorithm>
 #include <cmath>
@@ -328,6 +329,11 @@ struct cf_handle {
     std::vector<float*> Rx[kMaxRes], dRx[kMaxRes];
     std::vector<RegBuf> R[kMaxRes];
     float *hin, *h1, *logits, *dlogits, *dh1, *dhin, *loss, *loss_part, *tdbg;
+    // input gradients (cf_backward_from_inputs)
+    float* dfreq_part = nullptr;               // [n_res][max_batch][T * T]: d(interaction_freq) per resolution, summed by k_dfreq_sum
+    float* want_dfreq = nullptr;               // set for the duration of one cf_backward_from_inputs: the Regulation backward writes dfreq_part
+    bool reg_dfreq_ok = false;                 // k_reg8_bwd_dfreq got its LDS attribute
+    bool ig_smem_ok = false;                   // k_input_grad got its LDS attribute (first use)
     // deferred-gradient tile tables
     WgTile* wg_tiles = nullptr;
     int n_wg = 0;
@@ -496,6 +502,7 @@ static void plan_workspace(cf_handle* h) {
     h->head_cnt = reinterpret_cast<int*>(h->ws_get("H.cnt", MB + 1));      // arrivals per gene (cf_head_ride.h): monotonic, see ride_tick
     h->ride_reset_every = (unsigned long long)std::max(1, getenv_int("CF_RIDE_RESET_EVERY", 1 << 28));
     h->tdbg = h->ws_get("reg_tdbg", 2 * 16 * 64);      // shader-clock stamps (uint64) of the fused Regulation kernels
+    h->dfreq_part = h->ws_get("dR.freq", (size_t)c.n_res * MB * T * T);      // (last: the entries above keep their offsets)
 }
 
 // ------------------------------------------------------------------------------------
@@ -576,6 +583,7 @@ static const void* reg_kernel(bool bwd, int dff, bool save = true) {
     }
     return dff == 128 ? (const void*)k_reg8_bwd<128> : (const void*)k_reg8_bwd<256>;
 }
+static const void* reg_kernel_dfreq(int dff) { return dff == 128 ? (const void*)k_reg8_bwd<128, true> : (const void*)k_reg8_bwd<256, true>; }
 
 static int build_reg_table(cf_handle* h) {
     const cf_config& c = h->cfg;
@@ -951,6 +959,8 @@ extern "C" int cf_create(const cf_config* cfg, const float* const* pe_host, cf_h
             if (e1 == hipSuccess) e1 = hipFuncSetAttribute(reg_kernel(false, c.reg_dff, false), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sf);
             hipError_t e2 = hipFuncSetAttribute(reg_kernel(true, c.reg_dff), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sb);
             if (e1 != hipSuccess || e2 != hipSuccess) h->reg_fused = false;
+            // the interaction-frequency variant of the backward (cf_backward_from_inputs only): same LDS image
+            if (h->reg_fused) h->reg_dfreq_ok = hipFuncSetAttribute(reg_kernel_dfreq(c.reg_dff), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sb) == hipSuccess;
         }
         h->reg8 = h->reg_fused;
     }
@@ -1883,7 +1893,14 @@ static int backward_impl(cf_handle* h, const cf_batch* bt, hipStream_t st, int p
             h->head_loss_due = false;
         }
         ra.row0_last = h->reg_row0 ? 1 : 0;
-        if (launch_reg(h, "k_reg_bwd", reg_kernel(true, c.reg_dff), dim3(8 * ((B * nres + 7) / 8)), reg8_bwd_smem(c.reg_dff), ra, st)) return -1;
+        ra.dfreq = nullptr;
+        if (h->want_dfreq) {      // cf_backward_from_inputs: the variant that also leaves d(interaction_freq) per resolution
+            if (!h->reg_dfreq_ok) return fail("cf_backward_from_inputs: interaction_freq: the fused Regulation backward variant could not be configured");
+            ra.dfreq = h->want_dfreq;
+            void* kargs[] = {&ra};
+            HIP_TRY(hipLaunchKernel(reg_kernel_dfreq(c.reg_dff), dim3(8 * ((B * nres + 7) / 8)), dim3(512), kargs, reg8_bwd_smem(c.reg_dff), st));
+            LAUNCH_CHECK("k_reg_bwd_dfreq");
+        } else if (launch_reg(h, "k_reg_bwd", reg_kernel(true, c.reg_dff), dim3(8 * ((B * nres + 7) / 8)), reg8_bwd_smem(c.reg_dff), ra, st)) return -1;
     }
     for (int l = ((h->reg_fused || !(parts & 2)) ? -1 : c.reg_layers - 1); l >= 0; --l) {   // Regulation, unfused fallback
         PostBwdArgs pb;
@@ -1929,6 +1946,8 @@ static int backward_impl(cf_handle* h, const cf_batch* bt, hipStream_t st, int p
         at.T = T;
         at.H = c.reg_heads;
         at.DM = RDm;
+        at.dfreq = h->want_dfreq;
+        at.dfreq_add = l + 1 < c.reg_layers;      // (the top layer's launch comes first: it writes, the ones below add)
         dg.lddy = RW;
         dg.ldw = kD;
         dg.rmap = identity_map();
@@ -1946,7 +1965,8 @@ static int backward_impl(cf_handle* h, const cf_batch* bt, hipStream_t st, int p
         } else if (RDm == 128) launch_post_bwd<false, 128>(c.reg_dff, dim3(tiles_of(NR), nres), st, pb);
         else launch_post_bwd<false, 256>(c.reg_dff, dim3(tiles_of(NR), nres), st, pb);
         LAUNCH_CHECK("k_post_bwd<reg>");
-        hipLaunchKernelGGL((k_attr<true>), dim3(B, nres), dim3(256), attr_smem(T, at.H, RDm, true), st, at);
+        if (at.dfreq) hipLaunchKernelGGL((k_attr<true, true>), dim3(B, nres), dim3(256), attr_smem(T, at.H, RDm, true), st, at);
+        else hipLaunchKernelGGL((k_attr<true>), dim3(B, nres), dim3(256), attr_smem(T, at.H, RDm, true), st, at);
         LAUNCH_CHECK("k_attr<bwd>");
         if (RDm == 128) hipLaunchKernelGGL((k_dgrad<8>), dim3(tiles_of(NR), kD / 32, nres), dim3(256), 0, st, dg);
         else hipLaunchKernelGGL((k_dgrad<16>), dim3(tiles_of(NR), kD / 32, nres), dim3(256), 0, st, dg);
@@ -2278,6 +2298,89 @@ extern "C" int cf_backward_from(cf_handle* h, const cf_batch* bt, const float* d
     HIP_TRY(hipMemcpyAsync(h->dlogits, dlogits, (size_t)bt->B * h->cfg.n_out * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (backward_impl(h, bt, st)) return -1;
     return reduce_impl(h, bt->B, st);
+}
+
+// cf_backward_from + the gradients of the float inputs (cf_input_grad.h).  The parameter gradients come from the very launches of
+// cf_backward_from; the interaction_freq gradient from the Regulation backward's DFREQ variant, the feature gradients from the saved
+// attention operands, in front of the reductions.  Every requested output is overwritten in full.
+extern "C" int cf_backward_from_inputs(cf_handle* h, const cf_batch* bt, const float* dlogits, const cf_input_grads* want, void* stream) {
+    bool any_p = false, any_c = false;
+    if (want)
+        for (int r = 0; r < kMaxRes; ++r) {
+            any_p |= want->promoter_feats[r] != nullptr;
+            any_c |= want->pcre_feats[r] != nullptr;
+        }
+    const bool any_f = want && want->interaction_freq;
+    if (!any_p && !any_c && !any_f) return cf_backward_from(h, bt, dlogits, stream);
+    if (check_bwd(h, bt)) return -1;
+    if (!dlogits) return fail("cf_backward_from_inputs: dlogits is null");
+    const cf_config& c = h->cfg;
+    const int B = bt->B, S = c.i_max, T = S + 1, nres = c.n_res, F = c.n_feats, kD = c.d_emb;
+    for (int r = nres; r < kMaxRes; ++r)
+        if (want->promoter_feats[r] || want->pcre_feats[r]) return fail("cf_backward_from_inputs: promoter_feats / pcre_feats[%d]: the model has %d resolutions", r, nres);
+    if (any_p && h->embed_dense)
+        return fail("cf_backward_from_inputs: promoter_feats: input gradients are implemented for embed.n_layers = 1 (the centre-row Embedding); "
+                    "this model has embed.n_layers = %d (the all-rows path keeps no first-layer input-row gradient)", c.embed_layers);
+    if (any_f && h->reg_fused && !h->reg_dfreq_ok)
+        return fail("cf_backward_from_inputs: interaction_freq: the fused Regulation backward variant could not be configured");
+    size_t smem = 0;
+    for (int r = 0; r < nres; ++r) smem = std::max(smem, input_grad_smem(c.n_bins[r], F, kD));
+    if ((any_p || any_c) && !h->ig_smem_ok) {
+        if (hipFuncSetAttribute((const void*)k_input_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+            return fail("cf_backward_from_inputs: promoter_feats / pcre_feats: k_input_grad needs %zu bytes of LDS", smem);
+        h->ig_smem_ok = true;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(h->dlogits, dlogits, (size_t)B * c.n_out * sizeof(float), hipMemcpyDeviceToDevice, st));
+    h->want_dfreq = any_f ? h->dfreq_part : nullptr;
+    const int rc = backward_impl(h, bt, st);
+    h->want_dfreq = nullptr;
+    if (rc) return -1;
+    if (any_p || any_c) {
+        InGradArgs a;
+        memset(&a, 0, sizeof a);
+        for (int r = 0; r < nres; ++r) {
+            const int bs = c.binsizes[r];
+            a.feats_p[r] = bt->promoter_feats[r];
+            a.feats_c[r] = bt->pcre_feats[r];
+            a.mask_p[r] = static_cast<const uint8_t*>(bt->promoter_mask_row[r]);
+            a.mask_c[r] = static_cast<const uint8_t*>(bt->pcre_mask_row[r]);
+            a.mstride_p[r] = bt->promoter_mask_stride[r];
+            a.mstride_c[r] = bt->pcre_mask_stride[r];
+            a.pet[r] = h->pet[r];
+            a.w_p[r] = h->P_(fmt("embed.%d.lin_proj.weight", bs));
+            a.w_c[r] = h->P_(fmt("pairwise_interaction.%d.lin_proj_pcre.weight", bs));
+            a.edx0[r] = h->edx0[r];
+            a.ep[r] = h->E[r].p;
+            a.eqt[r] = h->E[r].qt;
+            a.edxbar[r] = h->E[r].dxbar;
+            for (int l = 0; l < c.pair_layers; ++l) {
+                a.pp[r][l] = h->P[r][l].p;
+                a.pqt[r][l] = h->P[r][l].qt;
+                a.pdxbar[r][l] = h->P[r][l].dxbar;
+            }
+            a.out_p[r] = want->promoter_feats[r];
+            a.out_c[r] = want->pcre_feats[r];
+            a.L[r] = c.n_bins[r];
+        }
+        a.B = B;
+        a.S = S;
+        a.F = F;
+        a.D = kD;
+        a.nh_e = c.embed_heads;
+        a.nh_p = c.pair_heads;
+        a.n_pl = c.pair_layers;
+        a.rs_e = 1.0f / sqrtf((float)(kD / c.embed_heads));
+        a.rs_p = 1.0f / sqrtf((float)(kD / c.pair_heads));
+        hipLaunchKernelGGL(k_input_grad, dim3(1 + S, B, nres), dim3(kIgThreads), smem, st, a);
+        LAUNCH_CHECK("k_input_grad");
+    }
+    if (any_f) {
+        const int n = B * T * T;
+        hipLaunchKernelGGL(k_dfreq_sum, dim3((n + 255) / 256), dim3(256), 0, st, h->dfreq_part, want->interaction_freq, n, nres);
+        LAUNCH_CHECK("k_dfreq_sum");
+    }
+    return reduce_impl(h, B, st);
 }
 
 // ------------------------------------------------------------------------------------

@@ -1610,9 +1610,11 @@ struct AttrArgs {
     float* dgam[kMaxRes];            // bwd out [B, H] per-gene partials
     int T;
     int H, DM;                       // heads, d_model (H * d_head)
+    float* dfreq;                    // bwd, DFREQ: [n_res][B][T * T] sum over heads of gamma_f dS, written by the first layer's launch,
+    int dfreq_add;                   //   added to by the later ones (stream order: no atomics)
 };
 
-template <bool BWD>
+template <bool BWD, bool DFREQ = false>
 __global__ __launch_bounds__(256) void k_attr(AttrArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int r = blockIdx.y, g = blockIdx.x, tid = threadIdx.x, T = a.T, TT = T * T;
@@ -1715,6 +1717,14 @@ __global__ __launch_bounds__(256) void k_attr(AttrArgs a) {
             float s = 0.f;
             for (int i = 0; i < T; ++i) s += red_s[tid * T + i];
             a.dgam[r][(size_t)g * H + tid] = s;
+        }
+        if constexpr (DFREQ) {
+            for (int ij = tid; ij < TT; ij += 256) {
+                float s = 0.f;
+                for (int h = 0; h < H; ++h) s = fmaf(a.gamma[r][h], ds_s[h * TT + ij], s);
+                float* o = a.dfreq + ((size_t)r * gridDim.x + g) * TT + ij;
+                *o = a.dfreq_add ? *o + s : s;
+            }
         }
         // dq, dk, dv
         for (int idx = tid; idx < T * DM; idx += 256) {

@@ -597,7 +597,9 @@ __global__ __launch_bounds__(512) void k_reg8_fwd(RegArgs a) {
 
 // Backward of the same stack.  LDS: ds = d(layer output) -> dy1 -> dt1 -> d(layer input); t2 = dt2; wide = dpre1;
 // dqk = d(q | k | v | gate) of the gene (A operand of the K = 1024 input-gradient product).
-template <int DFF>
+// DFREQ (cf_backward_from_inputs): also the gradient of interaction_freq -- sum over the layers of gamma_f[w] dS per lane in registers,
+// the 8 heads (waves) summed through LDS at the end, one [T, T] block per (resolution, gene) into a.dfreq [n_res][B][T * T]
+template <int DFF, bool DFREQ = false>
 __global__ __launch_bounds__(512) void k_reg8_bwd(RegArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const bool ride_loss = a.head.on && blockIdx.x == 0 && (threadIdx.x >> 6) == 7;      // (the head ran at the tail of the forward launch: cf_head_ride.h)
@@ -684,6 +686,7 @@ __global__ __launch_bounds__(512) void k_reg8_bwd(RegArgs a) {
     };
     request_ln2(load_layer(tab + a.l_top));
     __syncthreads();
+    float dfq[4] = {0.f, 0.f, 0.f, 0.f};      // DFREQ: lane (j = lr, lq): sum over layers of gamma_f[w] dS[4 lq + ii][j]
     auto layer = [&](auto r0_c, const int l) __attribute__((always_inline)) {
         constexpr bool r0 = decltype(r0_c)::value;      // the last layer: one live row above the attention (see b_run_row0)
         const RegLayerDev P = load_layer(tab + l);
@@ -839,6 +842,7 @@ __global__ __launch_bounds__(512) void k_reg8_bwd(RegArgs a) {
                 const float dot = group16_sum(pv[ii] * d);
                 const float sv = mkv[ii] ? 0.f : pv[ii] * (d - dot);
                 gsum = fmaf(sv, fqv[ii], gsum);
+                if constexpr (DFREQ) dfq[ii] = fmaf(ldg(P.gamma + w), sv, dfq[ii]);
                 dsv[ii] = sv / scale;
                 dss[oD20 + ii * 20] = dsv[ii];
             }
@@ -893,6 +897,18 @@ __global__ __launch_bounds__(512) void k_reg8_bwd(RegArgs a) {
     const bool top_row0 = a.row0_last && from_top;
     if (top_row0) layer(std::true_type{}, a.l_top);
     for (int l = a.l_top - (top_row0 ? 1 : 0); l >= a.l_bot; --l) layer(std::false_type{}, l);
+    if constexpr (DFREQ) {      // (the last layer ended on a barrier: the ds tile, 16 x LD >= 8 x 256 floats, is free)
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) smem[w * 256 + (lq * 4 + ii) * 16 + lr] = dfq[ii];
+        __syncthreads();
+        if (tid < TT) {
+            const int i = tid / T, j = tid - i * T;
+            float s = 0.f;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s += smem[k * 256 + i * 16 + j];
+            a.dfreq[((size_t)r * a.B + g) * TT + tid] = s;
+        }
+    }
     if (ride_loss) head_ride_loss(a.head, a.B, ride_l);
 }
 

@@ -23,6 +23,7 @@ struct RegArgs {
     int row0_last;                   // cf_reg8.h: only token 0 of the LAST layer's output is consumed (net.py:375): that layer computes row 0 only
     int l_top, l_bot;                // backward: the launch walks layers l_top down to l_bot (the whole stack: n_layers - 1 .. 0; the data-parallel step
                                      // runs the upper and the lower half as two launches, so that the upper half's gradients can be on the wire earlier)
+    float* dfreq;                    // backward, k_reg8_bwd<., true> only: d(interaction_freq) per resolution [n_res][B][T * T]
 };
 
 constexpr int kQkLd = kRW + 4;

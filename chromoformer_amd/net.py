@@ -66,11 +66,14 @@ def _init_kind(name, shape):
 
 
 class _BackwardHook(torch.autograd.Function):
-    """Lets ``loss.backward()`` of the caller drive cf_backward_from()."""
+    """Lets ``loss.backward()`` of the caller drive cf_backward_from(), or cf_backward_from_inputs() when one of the float inputs
+    (the device float32 copies _pack made of them: promoter_feats[b] per resolution, pcre_feats[b] per resolution, interaction_freq)
+    requires a gradient -- autograd carries it back through the .to() to the caller's tensor."""
 
     @staticmethod
-    def forward(ctx, anchor, model, batch_struct, keep):
+    def forward(ctx, anchor, model, batch_struct, keep, *inputs):
         ctx.model, ctx.batch_struct, ctx.keep = model, batch_struct, keep
+        ctx.shapes = [t.shape for t in inputs]
         return model._run_forward(batch_struct, save=True)
 
     @staticmethod
@@ -78,9 +81,28 @@ class _BackwardHook(torch.autograd.Function):
         m = ctx.model
         dl = dlogits.contiguous().float()
         st = torch.cuda.current_stream(m._device).cuda_stream
-        _lib.check(_lib.lib().cf_backward_from(m._handle, C.byref(ctx.batch_struct), dl.data_ptr(), st), "cf_backward_from")
+        needs = ctx.needs_input_grad[4:]
+        grads = [None] * len(needs)
+        if not any(needs):
+            _lib.check(_lib.lib().cf_backward_from(m._handle, C.byref(ctx.batch_struct), dl.data_ptr(), st), "cf_backward_from")
+        else:
+            nres = (len(needs) - 1) // 2
+            want = _lib.cf_input_grads()
+            for i, need in enumerate(needs):
+                if not need:
+                    continue
+                g = torch.empty(ctx.shapes[i], device=m._device, dtype=torch.float32)   # (written in full by the library)
+                grads[i] = g
+                if i < nres:
+                    want.promoter_feats[i] = g.data_ptr()
+                elif i < 2 * nres:
+                    want.pcre_feats[i - nres] = g.data_ptr()
+                else:
+                    want.interaction_freq = g.data_ptr()
+            _lib.check(_lib.lib().cf_backward_from_inputs(m._handle, C.byref(ctx.batch_struct), dl.data_ptr(), C.byref(want), st),
+                       "cf_backward_from_inputs")
         m._publish_grads()
-        return torch.zeros_like(m._anchor), None, None, None
+        return (torch.zeros_like(m._anchor), None, None, None, *grads)
 
 
 class ChromoformerBase(nn.Module):
@@ -214,13 +236,16 @@ class ChromoformerBase(nn.Module):
             return m, m.data_ptr(), L
         raise ValueError("unexpected pad-mask shape %s" % (tuple(mask.shape),))
 
-    def _pack(self, promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq):
+    def _pack(self, promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq, inputs=None):
+        """inputs: an optional list that receives the device float32 copies of the float inputs, in the order promoter_feats per
+        resolution, pcre_feats per resolution, interaction_freq (forward hands them to autograd)."""
         if self._handle is None:
             raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
         bs = _lib.cf_batch()
         keep = []
         S, T = self.i_max, self.i_max + 1
         B = None
+        pfs, cfs = [], []
 
         def dev_f32(t):
             t = t.to(self._device, torch.float32).contiguous()
@@ -234,6 +259,9 @@ class ChromoformerBase(nn.Module):
             if pf.numel() != B * L * self.n_feats or cf.numel() != B * S * L * self.n_feats:
                 raise ValueError("feature shapes do not match the configuration at binsize %d" % b)
             bs.promoter_feats[r], bs.pcre_feats[r] = pf.data_ptr(), cf.data_ptr()
+            if inputs is not None:
+                pfs.append(pf)
+                cfs.append(cf)
             m, ptr, stride = self._rows(promoter_pad_masks[b], L, B)
             keep.append(m)
             bs.promoter_mask_row[r], bs.promoter_mask_stride[r] = ptr, stride
@@ -252,6 +280,8 @@ class ChromoformerBase(nn.Module):
         bs.B = B
         if B > self._max_batch:
             raise ValueError("batch of %d genes exceeds max_batch=%d given at construction" % (B, self._max_batch))
+        if inputs is not None:
+            inputs.extend(pfs + cfs + [fr])
         return bs, keep
 
     def pack_batch(self, d):
@@ -299,10 +329,14 @@ class ChromoformerBase(nn.Module):
         return out
 
     def forward(self, promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq):
-        bs, keep = self._pack(promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq)
-        if torch.is_grad_enabled():
-            return _BackwardHook.apply(self._anchor, self, bs, keep)
-        return self._run_forward(bs, save=False)
+        if not torch.is_grad_enabled():
+            bs, keep = self._pack(promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq)
+            return self._run_forward(bs, save=False)
+        inputs = []
+        bs, keep = self._pack(promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq,
+                              inputs=inputs)
+        # the float inputs go in as arguments: a gradient requested for any of them is computed by the library (saliency maps)
+        return _BackwardHook.apply(self._anchor, self, bs, keep, *inputs)
 
     def embed_full(self, promoter_feats, promoter_pad_masks):
         """EmbeddingTransformer's first return value (net.py:57-59): {binsize: [B, 1, L, 128]}, the embedding of every

@@ -170,6 +170,18 @@ int cf_backward_part(cf_handle* h, const cf_batch* batch, const void* labels, fl
                      float* loss_out, int parts, void* stream);
 /* Same, but from a caller-supplied d(loss)/d(logits) [B, n_out]. */
 int cf_backward_from(cf_handle* h, const cf_batch* batch, const float* dlogits, void* stream);
+/* Gradients of the float inputs (saliency maps), device buffers; a NULL field is not wanted. */
+typedef struct cf_input_grads {
+    float* promoter_feats[CF_MAX_RES];   /* [B, n_bins[r], n_feats]        */
+    float* pcre_feats[CF_MAX_RES];       /* [B, i_max, n_bins[r], n_feats] */
+    float* interaction_freq;             /* [B, T, T], T = i_max + 1       */
+} cf_input_grads;
+/* cf_backward_from (same preconditions, bit-identical parameter gradients) that also OVERWRITES every requested input
+ * gradient in full: zeros for padded bins, dummy pCRE slots and masked interaction entries.  want == NULL or all
+ * fields NULL: exactly the launches of cf_backward_from.  Deterministic (no atomics).  promoter_feats needs
+ * embed.n_layers = 1; a configuration the kernels do not cover fails before anything is launched. */
+int cf_backward_from_inputs(cf_handle* h, const cf_batch* batch, const float* dlogits, const cf_input_grads* want,
+                            void* stream);
 /* torch.optim.AdamW.step (train.py:157, 196): decoupled weight decay, bias correction
  * from `step` (1-based), over [0, n_active). */
 int cf_adamw_step(cf_handle* h, float lr, float beta1, float beta2, float eps, float weight_decay,
