@@ -66,6 +66,11 @@ class cf_input_grads(C.Structure):
     _fields_ = [("promoter_feats", C.c_void_p * MAX_RES), ("pcre_feats", C.c_void_p * MAX_RES), ("interaction_freq", C.c_void_p)]
 
 
+class cf_attn_maps(C.Structure):
+    _fields_ = [("embed", C.c_void_p * MAX_RES), ("pairwise", C.c_void_p * MAX_RES), ("regulation", C.c_void_p * MAX_RES),
+                ("embedding", C.c_void_p)]
+
+
 class cf_store(C.Structure):
     _fields_ = [
         ("n_genes", C.c_longlong),
@@ -110,6 +115,7 @@ SYMBOLS = {
     "cf_wgrad_flops": (C.c_double, [C.c_void_p, C.c_int]),
     "cf_backward_from": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.c_void_p]),
     "cf_backward_from_inputs": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.POINTER(cf_input_grads), C.c_void_p]),
+    "cf_attention_maps": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.POINTER(cf_attn_maps), C.c_void_p]),
     "cf_adamw_step": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_longlong, C.c_void_p]),
     "cf_debug_copy": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p]),
     "cf_debug_names": (C.c_char_p, [C.c_void_p]),

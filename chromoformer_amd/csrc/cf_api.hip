@@ -4,6 +4,7 @@
 #include "../../include/chromoformer_hip.h"
 #include "cf_kernels.h"
 #include "cf_input_grad.h"
+#include "cf_attn_maps.h"
 
 #include <algorithm>
 #include <cmath>
@@ -2381,6 +2382,66 @@ extern "C" int cf_backward_from_inputs(cf_handle* h, const cf_batch* bt, const f
         LAUNCH_CHECK("k_dfreq_sum");
     }
     return reduce_impl(h, B, st);
+}
+
+// cf_forward(save = 1) + k_attn_maps (cf_attn_maps.h): the attention probabilities the forward kept for the backward pass and the
+// fc_head input, copied into the caller's dense layouts.  Nothing requested: exactly the launches of cf_forward(save = 1).
+extern "C" int cf_attention_maps(cf_handle* h, const cf_batch* bt, float* logits, const cf_attn_maps* want, void* stream) {
+    if (!h) return fail("null handle");
+    const cf_config& c = h->cfg;
+    const int nres = c.n_res;
+    bool any_e = false, any = false;
+    if (want) {
+        for (int r = 0; r < kMaxRes; ++r) {
+            if (r >= nres && (want->embed[r] || want->pairwise[r] || want->regulation[r]))
+                return fail("cf_attention_maps: embed / pairwise / regulation[%d]: the model has %d resolutions", r, nres);
+            any_e |= want->embed[r] != nullptr;
+            any |= want->embed[r] || want->pairwise[r] || want->regulation[r];
+        }
+        any |= want->embedding != nullptr;
+    }
+    if (any_e && h->embed_dense)
+        return fail("cf_attention_maps: embed: attention maps are implemented for embed.n_layers = 1 (the centre-row Embedding); "
+                    "this model has embed.n_layers = %d (the all-rows path keeps no probabilities)", c.embed_layers);
+    if (c.pair_layers > kMapPair || c.reg_layers > kMapReg)
+        return fail("cf_attention_maps: pairwise / regulation: at most %d / %d layers", kMapPair, kMapReg);
+    if (forward_impl(h, bt, logits, 1, stream, nullptr)) return -1;
+    if (!any) return 0;
+    const int B = bt->B;
+    AttnMapArgs a;
+    memset(&a, 0, sizeof a);
+    long long most = want->embedding ? (long long)B * nres * c.d_emb : 0;      // elements of the largest requested output
+    for (int r = 0; r < nres; ++r) {
+        const int L = c.n_bins[r];
+        a.ep[r] = h->E[r].p;
+        for (int l = 0; l < c.pair_layers; ++l) a.pp[r][l] = h->P[r][l].p;
+        for (int l = 0; l < c.reg_layers; ++l) a.rp[r][l] = h->reg_fused ? h->R[r][l].hq : h->R[r][l].p;
+        a.embed[r] = want->embed[r];
+        a.pair[r] = want->pairwise[r];
+        a.reg[r] = want->regulation[r];
+        a.L[r] = L;
+        if (a.embed[r]) most = std::max(most, (long long)B * c.embed_heads * L);
+        if (a.pair[r]) most = std::max(most, (long long)B * c.pair_layers * c.i_max * c.pair_heads * L);
+        if (a.reg[r]) most = std::max(most, (long long)B * c.reg_layers * c.reg_heads * (c.i_max + 1));
+    }
+    a.hin = h->hin;
+    a.emb = want->embedding;
+    a.B = B;
+    a.S = c.i_max;
+    a.T = c.i_max + 1;
+    a.nh_e = c.embed_heads;
+    a.nh_p = c.pair_heads;
+    a.n_pl = c.pair_layers;
+    a.H = c.reg_heads;
+    a.n_rl = c.reg_layers;
+    a.K = nres * c.d_emb;
+    a.reg_fused = h->reg_fused ? 1 : 0;
+    const int gx = (int)std::min<long long>((most + kMapThreads - 1) / kMapThreads, 1024);
+    hipLaunchKernelGGL(k_attn_maps, dim3(gx, kMapSegs), dim3(kMapThreads), 0, (hipStream_t)stream, a);
+    LAUNCH_CHECK("k_attn_maps");
+    ++h->n_fwd;
+    if (h->capturing) h->cap.n_fwd = h->n_fwd;
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------

@@ -74,11 +74,15 @@ class _BackwardHook(torch.autograd.Function):
     def forward(ctx, anchor, model, batch_struct, keep, *inputs):
         ctx.model, ctx.batch_struct, ctx.keep = model, batch_struct, keep
         ctx.shapes = [t.shape for t in inputs]
+        ctx.maps_gen = model._maps_gen
         return model._run_forward(batch_struct, save=True)
 
     @staticmethod
     def backward(ctx, dlogits):
         m = ctx.model
+        if ctx.maps_gen != m._maps_gen:
+            raise RuntimeError("loss.backward(): attention_maps() has run a forward pass since this output was computed and overwrote the "
+                               "activations its backward pass needs; call model(...) again before backward()")
         dl = dlogits.contiguous().float()
         st = torch.cuda.current_stream(m._device).cuda_stream
         needs = ctx.needs_input_grad[4:]
@@ -122,6 +126,7 @@ class ChromoformerBase(nn.Module):
         self.n_bins = [w_max // b for b in self.binsizes]
         self._kws = (embed, pair, reg)
         self._max_batch = max_batch
+        self._maps_gen = 0          # bumped by attention_maps(): a pending backward of an earlier forward refuses to run
         self._handle = None
         self._device = None
         self._cfg = _lib.make_config(n_feats, d_emb, d_head, self.n_out, self.binsizes, self.n_bins, i_max, embed, pair, reg,
@@ -337,6 +342,55 @@ class ChromoformerBase(nn.Module):
                               inputs=inputs)
         # the float inputs go in as arguments: a gradient requested for any of them is computed by the library (saliency maps)
         return _BackwardHook.apply(self._anchor, self, bs, keep, *inputs)
+
+    MAP_KEYS = ("embed", "pairwise_interaction", "regulation", "regulatory_embedding")
+
+    @torch.no_grad()
+    def attention_maps(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                       interaction_freq=None, which=MAP_KEYS):
+        """Logits and what a user of the reference reads off its attention modules (modules.py:73, 184) and fc_head input, from one
+        forward pass (cf_attention_maps) -> (logits [B, n_out], maps), tensors on the model's device.  Per binsize b, L = n_bins[b],
+        T = i_max + 1:
+
+          maps["embed"][b]                 [B, embed.n_heads, L]                       centre query's softmax row of the Embedding layer
+          maps["pairwise_interaction"][b]  [B, pw.n_layers, i_max, pw.n_heads, L]     promoter centre row over each pCRE's bins, per layer
+          maps["regulation"][b]            [B, reg.n_layers, reg.n_heads, T]           row 0 (promoter token) over [promoter, pCRE slots]
+          maps["regulatory_embedding"]     [B, 3 * d_emb]                              cat(x_out[b][:, 0]) + cat(x_in[b][:, 0])
+
+        Masked keys are 0, fully masked rows (dummy pCRE slots) uniform, as with the reference.  `which` selects the outputs (the others
+        are not copied).  The first argument may also be a packed batch (an engine.Slot or a pack_batch result), with nothing after it.
+        The pass overwrites the activations a grad-enabled model(...) keeps for its backward: such a pending backward() raises."""
+        if promoter_pad_masks is None:
+            bs = promoter_feats.struct if hasattr(promoter_feats, "struct") else promoter_feats[0]
+        else:
+            bs, _keep = self._pack(promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq)      # (alive until the call)
+        if self._handle is None:
+            raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
+        which = (which,) if isinstance(which, str) else tuple(which)
+        bad = [k for k in which if k not in self.MAP_KEYS]
+        if bad:
+            raise ValueError("attention_maps: unknown output(s) %s; choose from %s" % (bad, self.MAP_KEYS))
+        B, S, T, dev = bs.B, self.i_max, self.i_max + 1, self._device
+        embed, pair, reg = self._kws
+        want = _lib.cf_attn_maps()
+        maps = {k: {} for k in which if k != "regulatory_embedding"}
+        for r, b in enumerate(self.binsizes):
+            L = self.n_bins[r]
+            for key, field, shape in (("embed", "embed", (B, embed["n_heads"], L)),
+                                      ("pairwise_interaction", "pairwise", (B, pair["n_layers"], S, pair["n_heads"], L)),
+                                      ("regulation", "regulation", (B, reg["n_layers"], reg["n_heads"], T))):
+                if key in maps:
+                    t = maps[key][b] = torch.empty(shape, device=dev)      # (written in full by the library)
+                    getattr(want, field)[r] = t.data_ptr()
+        if "regulatory_embedding" in which:
+            maps["regulatory_embedding"] = t = torch.empty(B, len(self.binsizes) * self.d_emb, device=dev)
+            want.embedding = t.data_ptr()
+        logits = torch.empty(B, self.n_out, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        self._sync_tiled(st)
+        self._maps_gen += 1
+        _lib.check(_lib.lib().cf_attention_maps(self._handle, C.byref(bs), logits.data_ptr(), C.byref(want), st), "cf_attention_maps")
+        return logits, maps
 
     def embed_full(self, promoter_feats, promoter_pad_masks):
         """EmbeddingTransformer's first return value (net.py:57-59): {binsize: [B, 1, L, 128]}, the embedding of every

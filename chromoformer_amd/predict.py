@@ -46,9 +46,54 @@ def modernise_keys(state):
     return out
 
 
+def write_attention_maps(model, store, bsz, attention_dir=None, embeddings_out=None):
+    """Attention maps (`attention_dir`/{embed,pairwise_interaction,regulation}_{binsize}.npy) and / or the regulatory embedding
+    (`embeddings_out`, [n_genes, 3 * d_emb]) of every gene of a device-resident store, in store order.  Per batch: one device gather
+    into a Slot and one model.attention_maps; the rows go straight into .npy memory maps (nothing is gathered in host memory)."""
+    import ctypes as C
+    import os
+
+    from . import _lib
+    which = (("embed", "pairwise_interaction", "regulation") if attention_dir else ()) + (("regulatory_embedding",) if embeddings_out else ())
+    if not which:
+        return
+    n, dev, L = len(store), model._device, _lib.lib()
+    embed, pair, reg = model._kws
+    S, T = model.i_max, model.i_max + 1
+    outs = {}
+    if attention_dir:
+        os.makedirs(attention_dir, exist_ok=True)
+        for b, nb in zip(model.binsizes, model.n_bins):
+            for key, shape in (("embed", (embed["n_heads"], nb)), ("pairwise_interaction", (pair["n_layers"], S, pair["n_heads"], nb)),
+                               ("regulation", (reg["n_layers"], reg["n_heads"], T))):
+                outs[key, b] = np.lib.format.open_memmap(os.path.join(attention_dir, "%s_%d.npy" % (key, b)), mode="w+", dtype=np.float32,
+                                                         shape=(n,) + shape)
+    if embeddings_out:
+        outs["regulatory_embedding", None] = np.lib.format.open_memmap(embeddings_out, mode="w+", dtype=np.float32,
+                                                                       shape=(n, len(model.binsizes) * model.d_emb))
+    struct = store.struct()
+    order = torch.arange(n, dtype=torch.int32, device=dev)
+    slots = {}
+    st = torch.cuda.current_stream(dev).cuda_stream
+    for lo in range(0, n, bsz):
+        B = min(bsz, n - lo)
+        slot = slots.get(B) or slots.setdefault(B, Slot(model, B))
+        cursor = torch.tensor([0, 1, 0, 0], dtype=torch.int32).to(dev)
+        _lib.check(L.cf_gather_batch(model._handle, C.byref(struct), order[lo:].data_ptr(), cursor.data_ptr(), C.byref(slot.struct), None, st),
+                   "cf_gather_batch")
+        _, maps = model.attention_maps(slot, which=which)
+        if int(cursor[2].item()):
+            raise RuntimeError("write_attention_maps: the device-side gather reported errors at gene %d (store / order mismatch)" % lo)
+        for (key, b), mm in outs.items():
+            mm[lo:lo + B] = (maps[key] if b is None else maps[key][b]).cpu().numpy()
+    for mm in outs.values():
+        mm.flush()
+
+
 def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123, i_max=8, w_prom=40000, w_max=40000,
-            binsizes=(2000, 500, 100), progress=False, store_path=None):
-    """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file."""
+            binsizes=(2000, 500, 100), progress=False, store_path=None, attention_dir=None, embeddings_out=None):
+    """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file.  attention_dir / embeddings_out: also
+    write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps)."""
     seed_everything(seed)
     meta = pd.read_csv(meta_path)
     genes = meta.gene_id.tolist()
@@ -71,6 +116,7 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     trainer = Trainer(model, use_graph=False)
     out = trainer.evaluate_store(store, bsz).cpu()          # device gather + forward per batch, logits in store order
     preds = [out.numpy().reshape(-1) if regression else torch.sigmoid(out).numpy()[:, 1]]
+    write_attention_maps(model, store, bsz, attention_dir, embeddings_out)
     return meta, np.concatenate(preds).astype(np.float32)
 
 
@@ -82,8 +128,13 @@ def main(argv=None):
     ap.add_argument("-w", "--weights", default=None, help="Path to pretrained Chromoformer weights in .pt format.")
     ap.add_argument("--regression", action="store_true", help="ChromoformerRegressor (run_demo_regression.py)")
     ap.add_argument("--store", default=None, help="packed store of `python -m chromoformer_amd.pack` (default: <npy-dir>/chromoformer.cfstore if present)")
+    ap.add_argument("--attention-dir", default=None, help="also write DIR/{embed,pairwise_interaction,regulation}_{binsize}.npy: the "
+                    "attention maps of every gene, in metadata order (model.attention_maps)")
+    ap.add_argument("--embeddings-out", default=None, help="also write the regulatory embedding of every gene (the fc_head input, "
+                    "[n_genes, 3 * d_emb]) to this .npy file, in metadata order")
     args = ap.parse_args(argv)
-    meta, pred = predict(args.meta, args.npy_dir, args.weights, args.regression, progress=True, store_path=args.store)
+    meta, pred = predict(args.meta, args.npy_dir, args.weights, args.regression, progress=True, store_path=args.store,
+                         attention_dir=args.attention_dir, embeddings_out=args.embeddings_out)
     print("Predicting expressions for %d genes." % len(meta))
     meta["prediction"] = pred
     meta.to_csv(args.output, index=False)

@@ -182,6 +182,18 @@ typedef struct cf_input_grads {
  * embed.n_layers = 1; a configuration the kernels do not cover fails before anything is launched. */
 int cf_backward_from_inputs(cf_handle* h, const cf_batch* batch, const float* dlogits, const cf_input_grads* want,
                             void* stream);
+/* Attention maps and the regulatory embedding (interpretation), device buffers; a NULL field is not wanted.  T = i_max + 1. */
+typedef struct cf_attn_maps {
+    float* embed[CF_MAX_RES];       /* [B, embed.n_heads, n_bins[r]]: the centre query's row of the Embedding layer      */
+    float* pairwise[CF_MAX_RES];    /* [B, pw.n_layers, i_max, pw.n_heads, n_bins[r]]: the promoter centre row per pCRE  */
+    float* regulation[CF_MAX_RES];  /* [B, reg.n_layers, reg.n_heads, T]: row 0 (the promoter token) per layer           */
+    float* embedding;               /* [B, n_res * d_emb]: the fc_head input, cat(x_out[r][:, 0]) + cat(x_in[r][:, 0])   */
+} cf_attn_maps;
+/* cf_forward(save_for_backward = 1) (same launches, logits, saved activations) followed by ONE launch that OVERWRITES every
+ * requested output in full with the softmax probabilities the forward used (bit-equal: copies, no arithmetic; masked keys 0,
+ * fully masked rows uniform) and the fc_head input.  want == NULL or all fields NULL: exactly the launches of cf_forward(save = 1).
+ * Deterministic (no atomics).  embed needs embed.n_layers = 1; a resolution index >= n_res fails; both before anything is launched. */
+int cf_attention_maps(cf_handle* h, const cf_batch* batch, float* logits, const cf_attn_maps* want, void* stream);
 /* torch.optim.AdamW.step (train.py:157, 196): decoupled weight decay, bias correction
  * from `step` (1-based), over [0, n_active). */
 int cf_adamw_step(cf_handle* h, float lr, float beta1, float beta2, float eps, float weight_decay,

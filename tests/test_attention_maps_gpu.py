@@ -1,0 +1,260 @@
+"""Attention maps and the regulatory embedding (cf_attention_maps, ChromoformerBase.attention_maps): the softmax rows the model
+consumes and the fc_head input, as the reference computes them.
+
+  * the reference's own maps, embedding and logits on the default configuration (tests/golden/attention_maps.npz);
+  * the recording oracle (tests/attn_oracle.py) at bsz 64 in the realistic regime with padded promoters: exact zeros for masked keys,
+    uniform fully masked rows, rows summing to one;
+  * the stand-alone paths: d_emb = 64 with a 4 x 128 Regulation (layer-by-layer k_attr), i_max = 16 (T = 17); embed.n_layers = 2 refused
+    by name for `embed` only;
+  * the C ABI: every requested element written, nothing else, one launch more than cf_forward(save = 1), logits bit-equal to a
+    grad-enabled forward, run to run bit-identical;
+  * no side effects on training, and a pending backward of an earlier forward refused;
+  * `predict.py --attention-dir / --embeddings-out`."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import chromoformer_oracle as orc
+from tests.attn_oracle import oracle_maps
+from tests.helpers import GOLDEN, load_npz_batch
+
+pytestmark = pytest.mark.gpu
+BINS = (2000, 500, 100)
+MAP_TOL, EMB_TOL = 2e-5, 1e-4
+ARGS = ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq")
+
+
+def _args(batch):
+    return [batch[k] for k in ARGS]
+
+
+def _model(cfg=None, B=8, regression=False, seed=42):
+    from chromoformer_amd import ChromoformerClassifier, ChromoformerRegressor
+    c = orc._cfg(cfg)
+    Model = ChromoformerRegressor if regression else ChromoformerClassifier
+    return Model(c["n_feats"], c["d_emb"], c["d_head"], c["embed"], c["pairwise_interaction"], c["regulation"], binsizes=c["binsizes"],
+                 seed=seed, i_max=c["i_max"], w_max=c["w_max"], max_batch=B).cuda(0)
+
+
+def _padded(B, seed, cfg=None):
+    """Realistic regime plus promoter padding: the tail fifth of the bins of every other promoter is masked (centre bin kept)."""
+    b = orc.synthetic_batch(B, cfg=cfg, seed=seed, regime="realistic")
+    for m in b["promoter_pad_masks"].values():
+        L = m.shape[-1]
+        m[0::2, ..., L - max(1, L // 5):] = True
+    return b
+
+
+def _flat(maps, binsizes):
+    out = {"regulatory_embedding": maps["regulatory_embedding"].cpu()} if "regulatory_embedding" in maps else {}
+    for k in ("embed", "pairwise_interaction", "regulation"):
+        for b in binsizes:
+            if k in maps:
+                out["%s.%d" % (k, b)] = maps[k][b].cpu()
+    return out
+
+
+def _compare(got, ref, skip=()):
+    for k, r in ref.items():
+        if k.split(".")[0] in skip:
+            continue
+        g = got[k]
+        assert g.shape == r.shape, (k, g.shape, r.shape)
+        tol = EMB_TOL if k == "regulatory_embedding" else MAP_TOL
+        assert (g - r).abs().max().item() < tol, (k, (g - r).abs().max().item())
+
+
+@pytest.mark.parametrize("regression", [False, True], ids=["classifier", "regressor"])
+def test_default_config_matches_the_reference(regression):
+    z = np.load(os.path.join(GOLDEN, "attention_maps.npz"))
+    head = "reg" if regression else "clf"
+    model = _model(regression=regression)
+    for tag, batch in (("kat", load_npz_batch("kat.npz")[0]), ("real", orc.synthetic_batch(8, seed=31, regime="realistic"))):
+        genes = list(z["%s.genes" % tag])
+        logits, maps = model.attention_maps(*_args(batch))
+        got = _flat(maps, BINS)
+        for k, v in got.items():
+            ref = torch.from_numpy(z["%s.%s.%s" % (tag, head, k)])
+            v = v[genes] if k.startswith(("embed.", "pairwise_interaction.")) else v
+            assert v.shape == ref.shape, k
+            assert (v - ref).abs().max().item() < (EMB_TOL if k == "regulatory_embedding" else MAP_TOL), (tag, k)
+        assert (logits.cpu() - torch.from_numpy(z["%s.%s.logits" % (tag, head)])).abs().max().item() < EMB_TOL
+
+
+def test_bsz64_realistic_against_the_oracle():
+    batch = _padded(64, seed=77)
+    model = _model(B=64)
+    logits, maps = model.attention_maps(*_args(batch))
+    ref_logits, ref = oracle_maps(orc.init_params(None, 42, False), batch)
+    got = _flat(maps, BINS)
+    _compare(got, ref)
+    assert (logits.cpu() - ref_logits).abs().max().item() < EMB_TOL
+    for k, r in ref.items():
+        if k == "regulatory_embedding":
+            continue
+        g = got[k]
+        assert bool((g[r == 0] == 0).all()), k                                  # masked keys: exact zeros
+        assert (g.sum(-1) - 1).abs().max().item() < 1e-5, k                     # every row a distribution
+    for b in BINS:      # dummy pCRE slots: the whole centre row is masked -> uniform
+        L = batch["pcre_pad_masks"][b].shape[-1]
+        dummy = batch["pcre_pad_masks"][b][:, :, 0, L // 2].all(-1)             # [B, S]
+        assert bool(dummy.any())
+        rows = got["pairwise_interaction.%d" % b].permute(0, 2, 1, 3, 4)[dummy]  # [n_dummy, n_layers, nh, L]
+        assert (rows - 1.0 / L).abs().max().item() < 1e-6
+
+
+VARIANTS = {
+    "d_emb_64_reg_4x128": dict(d_emb=64, embed=dict(n_layers=1, n_heads=2, d_model=64, d_ff=128),
+                               pairwise_interaction=dict(n_layers=2, n_heads=2, d_model=64, d_ff=256),
+                               regulation=dict(n_layers=3, n_heads=4, d_model=128, d_ff=256)),
+    "i_max16": dict(i_max=16),
+}
+
+
+@pytest.mark.parametrize("name", sorted(VARIANTS))
+def test_stand_alone_paths_against_the_oracle(name):
+    cfg = orc._cfg(VARIANTS[name])
+    batch = _padded(5, seed=13, cfg=cfg)
+    P = orc.init_params(cfg, 3, False)
+    model = _model(cfg, B=5, seed=3)
+    model.load_state_dict(P)
+    logits, maps = model.attention_maps(*_args(batch))
+    ref_logits, ref = oracle_maps(P, batch, cfg)
+    _compare(_flat(maps, cfg["binsizes"]), ref)
+    assert (logits.cpu() - ref_logits).abs().max().item() < EMB_TOL
+
+
+def test_embed_with_two_layers_is_refused_by_name_the_rest_works():
+    cfg = orc._cfg(dict(embed=dict(n_layers=2, n_heads=2, d_model=128, d_ff=128)))
+    batch = _padded(4, seed=17, cfg=cfg)
+    P = orc.init_params(cfg, 3, False)
+    model = _model(cfg, B=4, seed=3)
+    model.load_state_dict(P)
+    with pytest.raises(RuntimeError, match=r"embed: .*embed\.n_layers = 1"):
+        model.attention_maps(*_args(batch), which=("embed",))
+    logits, maps = model.attention_maps(*_args(batch), which=("pairwise_interaction", "regulation", "regulatory_embedding"))
+    assert "embed" not in maps
+    ref_logits, ref = oracle_maps(P, batch, cfg)
+    _compare(_flat(maps, BINS), ref, skip=("embed",))
+    assert (logits.cpu() - ref_logits).abs().max().item() < EMB_TOL
+
+
+def test_launch_contract_at_the_c_abi():
+    from chromoformer_amd import _lib
+    B = 6
+    batch = orc.synthetic_batch(B, seed=23, regime="realistic")
+    model = _model(B=B)
+    packed = model.pack_batch(batch)
+    dev = model._device
+    L = _lib.lib()
+    shapes = {}
+    for r, (b, nb) in enumerate(zip(BINS, model.n_bins)):
+        shapes["embed", r] = (B, 2, nb)
+        shapes["pairwise", r] = (B, 2, 8, 2, nb)
+        shapes["regulation", r] = (B, 6, 8, 9)
+    shapes["embedding", None] = (B, 384)
+
+    def run(fields):
+        bufs = {k: torch.full(s, float("nan"), device=dev) for k, s in shapes.items()}
+        want = _lib.cf_attn_maps()
+        for (f, r), t in bufs.items():
+            if f in fields:
+                if r is None:
+                    want.embedding = t.data_ptr()
+                else:
+                    getattr(want, f)[r] = t.data_ptr()
+        logits = torch.full((B, 2), float("nan"), device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.cf_attention_maps(model._handle, C.byref(packed[0]), logits.data_ptr(), C.byref(want), st), "cf_attention_maps")
+        torch.cuda.synchronize()
+        return logits.cpu(), {k: v.cpu() for k, v in bufs.items()}, model.launch_counts()[0]
+
+    with torch.enable_grad():
+        ref_logits = model(*_args(batch)).detach().cpu()
+    n_fwd = model.launch_counts()[0]
+    everything = ("embed", "pairwise", "regulation", "embedding")
+    logits, bufs, n = run(everything)
+    assert n == n_fwd + 1
+    assert torch.equal(logits, ref_logits)
+    for k, t in bufs.items():
+        assert bool(torch.isfinite(t).all()), k
+    logits2, bufs2, _ = run(everything)
+    assert torch.equal(logits2, logits) and all(torch.equal(bufs2[k], bufs[k]) for k in bufs)
+    logits3, bufs3, n3 = run(("regulation",))
+    assert n3 == n_fwd + 1 and torch.equal(logits3, logits)
+    for (f, r), t in bufs3.items():
+        assert torch.equal(t, bufs[f, r]) if f == "regulation" else bool(torch.isnan(t).all()), (f, r)
+    _, bufs4, n4 = run(())
+    assert n4 == n_fwd and all(bool(torch.isnan(t).all()) for t in bufs4.values())
+    # the packed forms (pack_batch, engine.Slot) give the same result as the six tensors
+    from chromoformer_amd.engine import Slot
+    slot = Slot(model, B).fill(model, batch)
+    for p in (packed, slot):
+        lg, mp = model.attention_maps(p)
+        assert torch.equal(lg.cpu(), ref_logits)
+        assert torch.equal(mp["regulation"][100].cpu(), bufs["regulation", 2])
+
+
+def test_no_side_effects_on_training_and_a_stale_backward_is_refused():
+    from chromoformer_amd.engine import Trainer
+    batches = [orc.synthetic_batch(8, seed=41 + i, regime="realistic") for i in range(3)]
+
+    def run(interpose):
+        model = _model(B=8)
+        tr = Trainer(model, lr=1e-3)
+        slots = [tr.stage(b) for b in batches[:2]]
+        tr.step(slots[0])
+        if interpose:
+            torch.cuda.synchronize()
+            model.attention_maps(*_args(batches[2]))
+            torch.cuda.synchronize()
+        tr.step(slots[1])
+        torch.cuda.synchronize()
+        sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+        sd["<exp_avg>"], sd["<exp_avg_sq>"] = model._mflat.cpu().clone(), model._vflat.cpu().clone()
+        return sd
+
+    ref, got = run(False), run(True)
+    assert all(torch.equal(ref[k], got[k]) for k in ref)
+
+    model = _model(B=8)
+    b = batches[0]
+    with torch.enable_grad():
+        out = model(*_args(b))
+        model.attention_maps(*_args(batches[1]))
+        with pytest.raises(RuntimeError, match="attention_maps"):
+            out[:, 1].sum().backward()
+        model(*_args(b))[:, 1].sum().backward()      # a fresh forward trains as before
+    assert float(model._gflat.abs().sum()) > 0
+
+
+def test_predict_writes_maps_and_embeddings(tmp_path):
+    import pandas as pd
+
+    from chromoformer_amd import ChromoformerClassifier, predict
+    from chromoformer_amd.data import ChromoformerDataset
+    from tests.synth_data import make_dataset
+    meta = make_dataset(str(tmp_path / "npy"), n_genes=20, seed=11)
+    P = orc.init_params(seed=7)
+    ck = str(tmp_path / "w.pt")
+    torch.save({"net": P}, ck)
+    base = ["-m", meta, "-d", str(tmp_path / "npy"), "-w", ck]
+    assert predict.main(base + ["-o", str(tmp_path / "plain.csv")]) == 0
+    adir, emb = str(tmp_path / "maps"), str(tmp_path / "emb.npy")
+    assert predict.main(base + ["-o", str(tmp_path / "maps.csv"), "--attention-dir", adir, "--embeddings-out", emb]) == 0
+    p0 = pd.read_csv(str(tmp_path / "plain.csv"))["prediction"].to_numpy()
+    p1 = pd.read_csv(str(tmp_path / "maps.csv"))["prediction"].to_numpy()
+    assert np.abs(p0 - p1).max() <= 1e-6
+    ds = ChromoformerDataset(meta, str(tmp_path / "npy"), pd.read_csv(meta).gene_id.tolist())
+    batch = torch.utils.data.default_collate([ds[i] for i in range(len(ds))])
+    model = ChromoformerClassifier(seed=123, max_batch=32).cuda(0)
+    model.load_state_dict(P)
+    _, maps = model.attention_maps(*_args(batch))
+    got = {"regulatory_embedding": torch.from_numpy(np.load(emb))}
+    for k in ("embed", "pairwise_interaction", "regulation"):
+        for b in BINS:
+            got["%s.%d" % (k, b)] = torch.from_numpy(np.load(os.path.join(adir, "%s_%d.npy" % (k, b))))
+    _compare(got, _flat(maps, BINS))
