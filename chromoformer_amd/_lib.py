@@ -116,6 +116,7 @@ SYMBOLS = {
     "cf_backward_from": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.c_void_p]),
     "cf_backward_from_inputs": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.POINTER(cf_input_grads), C.c_void_p]),
     "cf_attention_maps": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.POINTER(cf_attn_maps), C.c_void_p]),
+    "cf_pcre_ablation": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.c_void_p]),
     "cf_adamw_step": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_longlong, C.c_void_p]),
     "cf_debug_copy": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p]),
     "cf_debug_names": (C.c_char_p, [C.c_void_p]),

@@ -5,6 +5,7 @@
 #include "cf_kernels.h"
 #include "cf_input_grad.h"
 #include "cf_attn_maps.h"
+#include "cf_ablate.h"
 
 #include <algorithm>
 #include <cmath>
@@ -335,6 +336,11 @@ struct cf_handle {
     float* want_dfreq = nullptr;               // set for the duration of one cf_backward_from_inputs: the Regulation backward writes dfreq_part
     bool reg_dfreq_ok = false;                 // k_reg8_bwd_dfreq got its LDS attribute
     bool ig_smem_ok = false;                   // k_input_grad got its LDS attribute (first use)
+    // in-silico pCRE deletion (cf_pcre_ablation): one allocation, made by the first call (ablate_alloc)
+    float* abl_stash[kMaxRes] = {};            // [max_batch, T, d_emb] per resolution: the trunk's output, Rx[r][0]
+    float* abl_freq = nullptr;                 // [max_batch, T, T]: interaction_freq of a chunk's gene-variants
+    uint8_t* abl_mask[kMaxRes] = {};           // [max_batch, T, T] per resolution: their interaction masks
+    void* abl_mem = nullptr;
     // deferred-gradient tile tables
     WgTile* wg_tiles = nullptr;
     int n_wg = 0;
@@ -1015,6 +1021,7 @@ extern "C" void cf_destroy(cf_handle* h) {
     for (hipEvent_t e : h->sync_ev) (void)hipEventDestroy(e);
     if (h->ride_ev) (void)hipEventDestroy(h->ride_ev);
     if (h->hyper) (void)hipFree(h->hyper);
+    if (h->abl_mem) (void)hipFree(h->abl_mem);
     delete h;
 }
 
@@ -1320,14 +1327,14 @@ static int retile_early(cf_handle* h, hipStream_t st) {
     h->tiled_pe_fresh = true;
     return 0;
 }
-static int forward_impl(cf_handle* h, const cf_batch* bt, float* logits, int save, void* stream, const HeadRide* ride) {
-    if (check_batch(h, bt)) return -1;
-    hipStream_t st = (hipStream_t)stream;
-    const long long launches0 = g_launches;
+// The forward pass in two parts: the trunk (prologue, Embedding + Pairwise stage) writes the Regulation input Rx[r][0]; the
+// Regulation stack and the head read it with the batch's interaction masks and frequencies (cf_pcre_ablation runs the second part
+// on gene-variant chunks of the first one's output).
+static int forward_trunk(cf_handle* h, const cf_batch* bt, int save, hipStream_t st) {
     const cf_config& c = h->cfg;
     const int kD = c.d_emb;      // (row width: shadows cf::kD in this function; 128, or 256 through the stand-alone kernels)
     const int B = bt->B, S = c.i_max, T = S + 1, nres = c.n_res, F = c.n_feats;
-    const int NE = B, NP = B * S, NR = B * T;
+    const int NE = B, NP = B * S;
     CentreParams ep[kMaxRes], pp[kMaxRes];
     for (int r = 0; r < nres; ++r) ep[r] = embed_params(h, r);
     const bool defer = h->defer_retile && !h->embed_dense && kPostWaves == 8 && c.embed_heads == 2 && c.d_emb == 128;      // (kD is shadowed in this function) Regulation + head units ride in the Embedding layer's chain launch
@@ -1617,6 +1624,12 @@ static int forward_impl(cf_handle* h, const cf_batch* bt, float* logits, int sav
                          l == 0, c.pair_heads, nullptr, nullptr, l > 0, last ? nullptr : npp, last ? nullptr : nbufs))
             return -1;
     }
+    return 0;
+}
+static int forward_reg_head(cf_handle* h, const cf_batch* bt, float* logits, int save, hipStream_t st, const HeadRide* ride) {
+    const cf_config& c = h->cfg;
+    const int kD = c.d_emb;      // (row width, as in forward_trunk)
+    const int B = bt->B, T = c.i_max + 1, nres = c.n_res, NR = B * T;
     if (h->reg_fused) {   // Regulation: all layers in one launch, one workgroup per (gene, resolution)
         RegArgs ra;
         ra.tab = h->reg_tab;
@@ -1721,7 +1734,14 @@ static int forward_impl(cf_handle* h, const cf_batch* bt, float* logits, int sav
         hipLaunchKernelGGL(k_head_fwd, dim3(tiles_of(B)), dim3(kHeadThreads), 0, st, a);
         LAUNCH_CHECK("k_head_fwd");
     }
-    h->last_fwd_B = save ? B : 0;
+    return 0;
+}
+static int forward_impl(cf_handle* h, const cf_batch* bt, float* logits, int save, void* stream, const HeadRide* ride) {
+    if (check_batch(h, bt)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    const long long launches0 = g_launches;
+    if (forward_trunk(h, bt, save, st) || forward_reg_head(h, bt, logits, save, st, ride)) return -1;
+    h->last_fwd_B = save ? bt->B : 0;
     h->n_fwd = (int)(g_launches - launches0);
     if (h->capturing) h->cap.n_fwd = h->n_fwd;
     return 0;
@@ -2440,6 +2460,76 @@ extern "C" int cf_attention_maps(cf_handle* h, const cf_batch* bt, float* logits
     hipLaunchKernelGGL(k_attn_maps, dim3(gx, kMapSegs), dim3(kMapThreads), 0, (hipStream_t)stream, a);
     LAUNCH_CHECK("k_attn_maps");
     ++h->n_fwd;
+    if (h->capturing) h->cap.n_fwd = h->n_fwd;
+    return 0;
+}
+
+// The buffers of cf_pcre_ablation, allocated by its first call (the model's other entry points never need them).
+static int ablate_alloc(cf_handle* h) {
+    if (h->abl_mem) return 0;
+    const cf_config& c = h->cfg;
+    const size_t T = c.i_max + 1, rows = (size_t)c.max_batch * T, x0 = rows * c.d_emb, tt = (size_t)c.max_batch * T * T;
+    const size_t freq_off = c.n_res * x0, mask_off = freq_off + tt;      // (floats; the masks follow as bytes)
+    void* q = nullptr;
+    if (hipMalloc(&q, mask_off * sizeof(float) + c.n_res * tt) != hipSuccess) return fail("cf_pcre_ablation: out of memory");
+    h->abl_mem = q;
+    float* f = (float*)q;
+    for (int r = 0; r < c.n_res; ++r) {
+        h->abl_stash[r] = f + r * x0;
+        h->abl_mask[r] = (uint8_t*)(f + mask_off) + r * tt;
+    }
+    h->abl_freq = f + freq_off;
+    return 0;
+}
+
+// The trunk once on the B genes, k_pcre_stash, then per chunk of at most max_batch of the B * V gene-variants (V = i_max + 2,
+// gene-major) k_pcre_expand and the Regulation + head launches of an inference forward on a batch of that chunk (cf_ablate.h).
+extern "C" int cf_pcre_ablation(cf_handle* h, const cf_batch* bt, float* logits, void* stream) {
+    if (!h) return fail("cf_pcre_ablation: null handle");
+    if (!bt) return fail("cf_pcre_ablation: null batch");
+    if (!logits) return fail("cf_pcre_ablation: null logits");
+    const cf_config& c = h->cfg;
+    if (bt->B > c.max_batch) return fail("cf_pcre_ablation: batch size %d exceeds max_batch=%d", bt->B, c.max_batch);
+    if (check_batch(h, bt)) return -1;
+    if (ablate_alloc(h)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    const long long launches0 = g_launches;
+    const int B = bt->B, S = c.i_max, T = S + 1, V = S + 2, nres = c.n_res, cap = c.max_batch;
+    const int row4 = T * c.d_emb / 4;
+    if (forward_trunk(h, bt, 0, st)) return -1;
+    AblateStashArgs sa;
+    memset(&sa, 0, sizeof sa);
+    for (int r = 0; r < nres; ++r) {
+        sa.src[r] = reinterpret_cast<const float4*>(h->Rx[r][0]);
+        sa.dst[r] = reinterpret_cast<float4*>(h->abl_stash[r]);
+    }
+    sa.n4 = (long long)B * row4;
+    hipLaunchKernelGGL(k_pcre_stash, dim3((int)std::min<long long>((sa.n4 + kAblThreads - 1) / kAblThreads, 256), nres), dim3(kAblThreads), 0, st, sa);
+    LAUNCH_CHECK("k_pcre_stash");
+    AblateExpandArgs ea;
+    memset(&ea, 0, sizeof ea);
+    cf_batch cb = *bt;      // the chunk's batch: only B, the masks and the frequencies are read past the trunk
+    for (int r = 0; r < nres; ++r) {
+        ea.stash[r] = reinterpret_cast<const float4*>(h->abl_stash[r]);
+        ea.x0[r] = reinterpret_cast<float4*>(h->Rx[r][0]);
+        ea.mask_in[r] = bt->interaction_mask[r];
+        ea.mask_out[r] = h->abl_mask[r];
+        cb.interaction_mask[r] = h->abl_mask[r];
+    }
+    ea.freq_in = bt->interaction_freq;
+    ea.freq_out = h->abl_freq;
+    cb.interaction_freq = h->abl_freq;
+    ea.V = V, ea.S = S, ea.T = T, ea.row4 = row4;
+    for (int g0 = 0; g0 < B * V; g0 += cap) {
+        const int n = std::min(cap, B * V - g0);
+        ea.g0 = g0;
+        hipLaunchKernelGGL(k_pcre_expand, dim3(n, nres), dim3(kAblThreads), 0, st, ea);
+        LAUNCH_CHECK("k_pcre_expand");
+        cb.B = n;
+        if (forward_reg_head(h, &cb, logits + (size_t)g0 * c.n_out, 0, st, nullptr)) return -1;
+    }
+    h->last_fwd_B = 0;
+    h->n_fwd = (int)(g_launches - launches0);
     if (h->capturing) h->cap.n_fwd = h->n_fwd;
     return 0;
 }

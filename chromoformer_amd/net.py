@@ -81,8 +81,8 @@ class _BackwardHook(torch.autograd.Function):
     def backward(ctx, dlogits):
         m = ctx.model
         if ctx.maps_gen != m._maps_gen:
-            raise RuntimeError("loss.backward(): attention_maps() has run a forward pass since this output was computed and overwrote the "
-                               "activations its backward pass needs; call model(...) again before backward()")
+            raise RuntimeError("loss.backward(): %s() has run a forward pass since this output was computed and overwrote the "
+                               "activations its backward pass needs; call model(...) again before backward()" % m._maps_by)
         dl = dlogits.contiguous().float()
         st = torch.cuda.current_stream(m._device).cuda_stream
         needs = ctx.needs_input_grad[4:]
@@ -126,7 +126,8 @@ class ChromoformerBase(nn.Module):
         self.n_bins = [w_max // b for b in self.binsizes]
         self._kws = (embed, pair, reg)
         self._max_batch = max_batch
-        self._maps_gen = 0          # bumped by attention_maps(): a pending backward of an earlier forward refuses to run
+        self._maps_gen = 0          # bumped by attention_maps() / pcre_ablation(): a pending backward of an earlier forward refuses to run
+        self._maps_by = None        # ... naming the last of them
         self._handle = None
         self._device = None
         self._cfg = _lib.make_config(n_feats, d_emb, d_head, self.n_out, self.binsizes, self.n_bins, i_max, embed, pair, reg,
@@ -389,8 +390,37 @@ class ChromoformerBase(nn.Module):
         st = torch.cuda.current_stream(dev).cuda_stream
         self._sync_tiled(st)
         self._maps_gen += 1
+        self._maps_by = "attention_maps"
         _lib.check(_lib.lib().cf_attention_maps(self._handle, C.byref(bs), logits.data_ptr(), C.byref(want), st), "cf_attention_maps")
         return logits, maps
+
+    @torch.no_grad()
+    def pcre_ablation(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                      interaction_freq=None):
+        """In-silico pCRE deletion (cf_pcre_ablation) -> logits [B, i_max + 2, n_out] on the model's device, no autograd graph:
+
+          [:, 0]          the prediction (model(...) under no_grad, bit-equal)
+          [:, 1 + j]      with pCRE slot j deleted: interaction_masks row and column j + 1 set at every resolution (= the slot made a
+                          dataset dummy, data.py); a slot that is already a dummy gives [:, 0]
+          [:, i_max + 1]  the promoter alone: rows and columns 1..i_max set
+
+        The Embedding + Pairwise stage runs once, the Regulation stack and the head on the B * (i_max + 2) gene-variants.  The first
+        argument may also be a packed batch (an engine.Slot or a pack_batch result), with nothing after it.  The pass overwrites the
+        activations a grad-enabled model(...) keeps for its backward: such a pending backward() raises."""
+        if promoter_pad_masks is None:
+            bs = promoter_feats.struct if hasattr(promoter_feats, "struct") else promoter_feats[0]
+        else:
+            bs, _keep = self._pack(promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq)      # (alive until the call)
+        if self._handle is None:
+            raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
+        dev = self._device
+        logits = torch.empty(bs.B, self.i_max + 2, self.n_out, device=dev)      # (written in full by the library)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        self._sync_tiled(st)
+        self._maps_gen += 1
+        self._maps_by = "pcre_ablation"
+        _lib.check(_lib.lib().cf_pcre_ablation(self._handle, C.byref(bs), logits.data_ptr(), st), "cf_pcre_ablation")
+        return logits
 
     def embed_full(self, promoter_feats, promoter_pad_masks):
         """EmbeddingTransformer's first return value (net.py:57-59): {binsize: [B, 1, L, 128]}, the embedding of every

@@ -90,10 +90,45 @@ def write_attention_maps(model, store, bsz, attention_dir=None, embeddings_out=N
         mm.flush()
 
 
+def write_pcre_ablation(model, store, bsz, path, regression=False):
+    """In-silico pCRE deletion of every gene of a device-resident store, in store order: `path`, a float32 .npy [n_genes, i_max + 2]
+    holding the prediction column's quantity (sigmoid(logits)[:, 1], or logits[:, 0] for the regressor) with nothing deleted
+    (column 0), pCRE slot j deleted (column 1 + j) and the promoter alone (last column).  Per batch: one device gather into a Slot
+    and one model.pcre_ablation.  The logits (8 bytes per gene and column) are kept on the host; each column goes through the
+    very sigmoid call predict() makes on the [n_genes, 2] logits, so column 0 is the prediction bit for bit."""
+    import ctypes as C
+
+    from . import _lib
+    n, dev, L = len(store), model._device, _lib.lib()
+    V = model.i_max + 2
+    logits = torch.empty(n, V, model.n_out)
+    struct = store.struct()
+    order = torch.arange(n, dtype=torch.int32, device=dev)
+    slots = {}
+    st = torch.cuda.current_stream(dev).cuda_stream
+    for lo in range(0, n, bsz):
+        B = min(bsz, n - lo)
+        slot = slots.get(B) or slots.setdefault(B, Slot(model, B))
+        cursor = torch.tensor([0, 1, 0, 0], dtype=torch.int32).to(dev)
+        _lib.check(L.cf_gather_batch(model._handle, C.byref(struct), order[lo:].data_ptr(), cursor.data_ptr(), C.byref(slot.struct), None, st),
+                   "cf_gather_batch")
+        out = model.pcre_ablation(slot)
+        if int(cursor[2].item()):
+            raise RuntimeError("write_pcre_ablation: the device-side gather reported errors at gene %d (store / order mismatch)" % lo)
+        logits[lo:lo + B] = out.cpu()
+    mm = np.lib.format.open_memmap(path, mode="w+", dtype=np.float32, shape=(n, V))
+    for v in range(V):
+        col = logits[:, v].contiguous()          # [n_genes, n_out], laid out as the logits predict() turns into its column
+        mm[:, v] = col.numpy().reshape(-1) if regression else torch.sigmoid(col).numpy()[:, 1]
+    mm.flush()
+
+
 def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123, i_max=8, w_prom=40000, w_max=40000,
-            binsizes=(2000, 500, 100), progress=False, store_path=None, attention_dir=None, embeddings_out=None):
+            binsizes=(2000, 500, 100), progress=False, store_path=None, attention_dir=None, embeddings_out=None,
+            pcre_ablation_out=None):
     """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file.  attention_dir / embeddings_out: also
-    write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps)."""
+    write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps); pcre_ablation_out:
+    the predictions with each pCRE deleted (write_pcre_ablation)."""
     seed_everything(seed)
     meta = pd.read_csv(meta_path)
     genes = meta.gene_id.tolist()
@@ -117,6 +152,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     out = trainer.evaluate_store(store, bsz).cpu()          # device gather + forward per batch, logits in store order
     preds = [out.numpy().reshape(-1) if regression else torch.sigmoid(out).numpy()[:, 1]]
     write_attention_maps(model, store, bsz, attention_dir, embeddings_out)
+    if pcre_ablation_out:
+        write_pcre_ablation(model, store, bsz, pcre_ablation_out, regression)
     return meta, np.concatenate(preds).astype(np.float32)
 
 
@@ -132,9 +169,12 @@ def main(argv=None):
                     "attention maps of every gene, in metadata order (model.attention_maps)")
     ap.add_argument("--embeddings-out", default=None, help="also write the regulatory embedding of every gene (the fc_head input, "
                     "[n_genes, 3 * d_emb]) to this .npy file, in metadata order")
+    ap.add_argument("--pcre-ablation-out", default=None, help="also write in-silico pCRE deletion to this .npy file: [n_genes, i_max + 2] "
+                    "predictions in metadata order, column 0 as --output, column 1 + j with pCRE j deleted, the last with the promoter "
+                    "alone (model.pcre_ablation)")
     args = ap.parse_args(argv)
     meta, pred = predict(args.meta, args.npy_dir, args.weights, args.regression, progress=True, store_path=args.store,
-                         attention_dir=args.attention_dir, embeddings_out=args.embeddings_out)
+                         attention_dir=args.attention_dir, embeddings_out=args.embeddings_out, pcre_ablation_out=args.pcre_ablation_out)
     print("Predicting expressions for %d genes." % len(meta))
     meta["prediction"] = pred
     meta.to_csv(args.output, index=False)

@@ -194,6 +194,21 @@ typedef struct cf_attn_maps {
  * fully masked rows uniform) and the fc_head input.  want == NULL or all fields NULL: exactly the launches of cf_forward(save = 1).
  * Deterministic (no atomics).  embed needs embed.n_layers = 1; a resolution index >= n_res fails; both before anything is launched. */
 int cf_attention_maps(cf_handle* h, const cf_batch* batch, float* logits, const cf_attn_maps* want, void* stream);
+/* In-silico pCRE deletion (interpretation).  logits: [B, V, n_out], V = i_max + 2, gene-major (b * V + v): the inference forward of
+ * gene b with its Regulation interaction mask (every resolution) replaced by
+ *   v = 0           the given mask (baseline: bit-equal to cf_forward(save = 0));
+ *   v = 1 + j       the given mask OR row j+1 OR column j+1 (pCRE slot j deleted; a slot that is already a dummy gives the baseline);
+ *   v = i_max + 1   the given mask OR rows and columns 1..i_max (promoter only).
+ * Features, pad masks and interaction_freq are gene b's.  Launches: the trunk part of cf_forward(save = 0) (prologue, Embedding +
+ * Pairwise) once, k_pcre_stash once (the Regulation input), then per chunk of at most max_batch gene-variants one k_pcre_expand and
+ * the Regulation + head launches of cf_forward(save = 0) on that chunk:
+ *   cf_launch_counts fwd = n_trunk + 1 + ceil(B * V / max_batch) * (1 + n_reg_head),
+ * where n_trunk + n_reg_head is what cf_forward(save = 0) issues (n_reg_head: 2 on the fused Regulation shapes -- k_reg_fwd, the
+ * head --, 3 * reg.n_layers + 1 layer by layer).  Overwrites the activations a cf_forward(save >= 1) kept: no cf_backward* may
+ * follow without a new saving forward.  Deterministic (no atomics).  The first call allocates the stash and chunk buffers (freed by
+ * cf_destroy; ~1 MB at max_batch 64); later calls allocate nothing.  A null handle / batch / logits or B > max_batch fails by name,
+ * before anything is launched. */
+int cf_pcre_ablation(cf_handle* h, const cf_batch* batch, float* logits, void* stream);
 /* torch.optim.AdamW.step (train.py:157, 196): decoupled weight decay, bias correction
  * from `step` (1-based), over [0, n_active). */
 int cf_adamw_step(cf_handle* h, float lr, float beta1, float beta2, float eps, float weight_decay,
