@@ -2,12 +2,17 @@
 all-reduce + AdamW), default config, bsz = 64 genes per GPU, synthetic 7-mark inputs resident
 in HBM (BASELINE.json: configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]      (N > 1: starts its own N ranks through torch.distributed.run)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]      (N > 1: starts its own N ranks through torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0 (see DESIGN.md section 6 for how `roofline` is defined).  `--dump-outputs DIR` also writes what the
 last timed step computed as DIR/<name>.npy (float32), from inputs and a model state fixed by the arguments alone: two builds run
 with the same arguments can be compared output for output.
+
+A plain run does what the headline figure needs and no more: it sets up, warms up, times the K steps, writes --dump-outputs and
+prints the line.  `--full` (one GPU) adds the legs that take runs of their own, after the timed steps and the dump: the step replayed
+as one hipGraph, the one-rank data-parallel path, the shipped training loop, the entrypoint's validation AUROC, the stress and
+binning records and the CPU baseline.
 """
 import argparse
 import json
@@ -412,22 +417,26 @@ def main():
     ap.add_argument("--graph", dest="graph", action="store_true", default=None,
                     help="replay the step as hipGraphs in the timed region (split around the event-bracketed roofline kernel: measured "
                          "+8..12 us per step).  Default: eager launches, on one GPU and under data parallelism (what chromoformer_amd.train runs there: "
-                         "replay with collectives between the graphs measured 4 %% slower on the one-rank proxy, `dp_path_ms_per_step`); on one GPU the "
-                         "one-graph replay time is reported beside it as `graph_replay_ms_per_step`; `config.hip_graph` says which was timed")
+                         "replay with collectives between the graphs measured 4 %% slower on the one-rank proxy, `dp_path_ms_per_step`); on one GPU with "
+                         "--full the one-graph replay time is reported beside it as `graph_replay_ms_per_step`; `config.hip_graph` says which was timed")
     ap.add_argument("--eager", "--no-graph", dest="graph", action="store_false", help="issue the launches of a step one by one")
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU: after the timed steps also run the legs below that take runs of their own (`graph_replay_ms_per_step`, "
+                         "`dp_path_ms_per_step`, `train_loop`, `val_auroc`, `stress`, `binning`, `cpu_baseline`; each can still be left out by its "
+                         "own option).  Default: only what the headline figure needs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--regime", default="dense", choices=["dense", "realistic"])
     ap.add_argument("--config", default="default", choices=["default", "stress"],
                     help="default = the headline benchmark (BASELINE configs[1]); stress = the 800-bin dense attention roofline run (configs[3])")
-    ap.add_argument("--train-loop-steps", type=int, default=2000, help="steps of the shipped training loop timed for the `train_loop` key (0 = skip)")
+    ap.add_argument("--train-loop-steps", type=int, default=2000, help="--full: steps of the shipped training loop timed for the `train_loop` key (0 = skip)")
     ap.add_argument("--train-loop-genes", type=int, default=16384, help="genes in the synthetic resident split of the `train_loop` leg")
     ap.add_argument("--dp-path", action="store_true", default=None, help="also time the data-parallel code path on a one-rank RCCL group "
-                    "(`dp_path_ms_per_step`; default: on for --gpus 1)")
+                    "(`dp_path_ms_per_step`; default: on for --gpus 1 --full)")
     ap.add_argument("--no-dp-path", dest="dp_path", action="store_false")
     ap.add_argument("--roofline-kernel", default="k_reg_bwd", help="kernel timed with HIP events: k_reg_bwd (dominant), k_reg_fwd (needs --no-graph), "
                     "k_trunk_fwd, k_trunk_bwd (the centre-row trunk; bwd includes its rider tiles' time, not their flops), k_wgrad, k_adamw")
     ap.add_argument("--val-auroc", dest="val_auroc", action="store_true", default=True,
-                    help="also run the entrypoint end to end on a small planted-signal cell line and report its validation AUROC (`val_auroc`; ~10 s)")
+                    help="--full: also run the entrypoint end to end on a small planted-signal cell line and report its validation AUROC (`val_auroc`; ~10 s)")
     ap.add_argument("--no-val-auroc", dest="val_auroc", action="store_false")
     ap.add_argument("--prewarm-s", type=float, default=0.5,
                     help="un-timed device pre-warm in front of the W warm-up steps: the same step, on a second model of the same construction, issued for "
@@ -435,7 +444,7 @@ def main():
                          "runs its first ~100 ms of kernels 5 %% slower: clock / power state); reported as `prewarm_s` / `prewarm_steps`; 0 = none.  "
                          "--steps / --warmup are honoured as given and what is timed does not change")
     ap.add_argument("--launch-timeout-s", type=int, default=1500, help="--gpus N > 1 started without torch.distributed.run: end the ranks this process started after so many seconds")
-    ap.add_argument("--no-extras", action="store_true", help="skip the `stress` and `binning` sub-records of the default line (~3 s)")
+    ap.add_argument("--no-extras", action="store_true", help="skip the `stress` and `binning` sub-records of a --full line (~3 s)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps write what the last one computed as DIR/<name>.npy, float32: rank 0's logits and loss and the "
                          "trainable parameters the step left (--config stress: a fixed sample of the attention outputs and gradients)")
@@ -504,7 +513,7 @@ def main():
     slot = trainer.stage(batch)            # inputs resident in HBM before the timed region
 
     # the same W + K steps on the box as it comes (no pre-warm): what this command timed up to round 4 -- reported beside the headline as
-    # `cold_ms_per_step`, never as `value`
+    # `cold_ms_per_step`, never as `value`.  Part of every run, plain or --full: the timed steps start from the state these steps leave
     for _ in range(args.warmup):
         trainer.step(slot)
     torch.cuda.synchronize()
@@ -606,7 +615,9 @@ def main():
             out["dp_self_check"] = checks
         if dumped is not None:
             out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
-        if world == 1 and not args.graph:      # the same step replayed as ONE hipGraph + AdamW (what train_epoch does), no events inside
+        # (--full: the legs below take runs of their own, after the timed steps and the dump; a plain run prints the line here)
+        full = world == 1 and args.full
+        if full and not args.graph:      # the same step replayed as ONE hipGraph + AdamW (what train_epoch does), no events inside
             tg = Trainer(model, lr=3e-5)
             sg = tg.stage(batch)
             for _ in range(max(args.warmup, 50)):      # (capture + the first replays of a new graph: un-timed, as the headline leg's pre-warm)
@@ -617,18 +628,18 @@ def main():
                 tg.step(sg)
             torch.cuda.synchronize()
             out["graph_replay_ms_per_step"] = round(1e3 * (time.perf_counter() - tg0) / args.steps, 4)
-        if world == 1 and args.dp_path is not False:
+        if full and args.dp_path is not False:
             out["dp_path_ms_per_step"] = dp_path_ms(model, batch, args.steps, args.warmup, dev)
-        if world == 1 and args.train_loop_steps > 0:
+        if full and args.train_loop_steps > 0:
             out["train_loop"] = train_loop_rate(model, 3e-5, args.train_loop_steps, args.train_loop_genes, args.regime, dev)
-        if world == 1 and args.val_auroc:
+        if full and args.val_auroc:
             out["val_auroc"] = val_auroc_run()
-        if world == 1 and not args.no_extras:
-            # BASELINE configs[3] and the HBM-bound kernel of the path in the SAME driver-run line (each about a second of GPU time)
+        if full and not args.no_extras:
+            # BASELINE configs[3] and the HBM-bound kernel of the path in the SAME --full line (each about a second of GPU time)
             sr = stress_record(10, 2)
             out["stress"] = dict(sr["roofline"], genes_per_s=sr["value"], ms_per_step=sr["ms_per_step"], workload=sr["config"]["workload"])
             out["binning"] = binning_record()
-        if world == 1 and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         json_out.write(json.dumps(out) + "\n")
         json_out.flush()

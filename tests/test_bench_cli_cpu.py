@@ -29,6 +29,11 @@ def test_world_size_mismatch_is_refused_by_name():
     assert r.returncode != 0 and "WORLD_SIZE=4" in (r.stdout + r.stderr)
 
 
+def test_full_is_an_option():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout
+
+
 def test_steps_below_one_is_refused_before_any_work():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "--steps must be at least 1" in r.stderr

@@ -13,7 +13,7 @@ for rnd in range(rounds):
             if kv and kv != "-":
                 k, v = kv.split("=")
                 env[k] = v
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "30", "--no-cpu-baseline", "--no-dp-path",
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", str(steps), "--warmup", "30", "--no-cpu-baseline", "--no-dp-path",
                             "--train-loop-steps", "0", "--no-val-auroc", "--no-extras"], env=env, capture_output=True, text=True)
         try:
             d = json.loads(r.stdout.strip().splitlines()[-1])

@@ -31,7 +31,7 @@ with open("$OUT/mfma_utilisation.csv", "w") as o:
 PY
 cd $R
 # the bench lines DESIGN.md quotes (un-profiled runs)
-timeout 400 python3 bench.py --steps 300 --warmup 30 > $OUT/bench.json 2> /dev/null
+timeout 400 python3 bench.py --full --steps 300 --warmup 30 > $OUT/bench.json 2> /dev/null
 timeout 200 python3 bench.py --steps 300 --warmup 30 --no-cpu-baseline --no-dp-path --train-loop-steps 0 --graph > $OUT/bench_graph.json 2> /dev/null
 timeout 200 python3 bench.py --steps 300 --warmup 30 --no-cpu-baseline --no-dp-path --train-loop-steps 0 --roofline-kernel k_reg_fwd > $OUT/bench_k_reg_fwd.json 2> /dev/null
 timeout 200 python3 bench.py --steps 300 --warmup 30 --no-cpu-baseline --no-dp-path --train-loop-steps 0 --roofline-kernel k_wgrad > $OUT/bench_k_wgrad.json 2> /dev/null
