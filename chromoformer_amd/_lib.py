@@ -71,6 +71,15 @@ class cf_attn_maps(C.Structure):
                 ("embedding", C.c_void_p)]
 
 
+class cf_ig_opts(C.Structure):
+    _fields_ = [("n_steps", C.c_int), ("target", C.c_int), ("interpolate", C.c_int), ("alphas", C.c_void_p), ("weights", C.c_void_p),
+                ("base_promoter_feats", C.c_void_p * MAX_RES), ("base_pcre_feats", C.c_void_p * MAX_RES),
+                ("base_interaction_freq", C.c_void_p), ("base_broadcast", C.c_int)]
+
+
+IG_PROMOTER, IG_PCRE, IG_FREQ = 1, 2, 4      # cf_ig_opts.interpolate
+
+
 class cf_store(C.Structure):
     _fields_ = [
         ("n_genes", C.c_longlong),
@@ -117,6 +126,8 @@ SYMBOLS = {
     "cf_backward_from_inputs": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.POINTER(cf_input_grads), C.c_void_p]),
     "cf_attention_maps": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.POINTER(cf_attn_maps), C.c_void_p]),
     "cf_pcre_ablation": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.c_void_p]),
+    "cf_integrated_gradients": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_ig_opts), C.POINTER(cf_input_grads), C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_adamw_step": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_longlong, C.c_void_p]),
     "cf_debug_copy": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p]),
     "cf_debug_names": (C.c_char_p, [C.c_void_p]),

@@ -6,6 +6,7 @@
 #include "cf_input_grad.h"
 #include "cf_attn_maps.h"
 #include "cf_ablate.h"
+#include "cf_ig.h"
 
 #include <algorithm>
 #include <cmath>
@@ -341,6 +342,22 @@ struct cf_handle {
     float* abl_freq = nullptr;                 // [max_batch, T, T]: interaction_freq of a chunk's gene-variants
     uint8_t* abl_mask[kMaxRes] = {};           // [max_batch, T, T] per resolution: their interaction masks
     void* abl_mem = nullptr;
+    // integrated gradients (cf_integrated_gradients): one allocation, made by the first call (intg_alloc); segments are
+    // promoter_feats[r], pcre_feats[r], interaction_freq (cf_ig.h)
+    float* intg_row[kIgSegs] = {};             // [max_batch, len]: a chunk's inputs
+    float* intg_grad[kIgSegs] = {};            // [max_batch, len]: their per-row gradients
+    uint8_t* intg_pm[kMaxRes] = {};            // [max_batch, L]: promoter pad-mask centre rows
+    uint8_t* intg_cm[kMaxRes] = {};            // [max_batch * i_max, L]: pCRE pad-mask centre rows
+    uint8_t* intg_im[kMaxRes] = {};            // [max_batch, T, T]: interaction masks
+    float* intg_stash[kMaxRes] = {};           // [max_batch, T, d_emb]: the trunk's output (frequency-only path)
+    float* intg_logits = nullptr;              // [max_batch, n_out]: a chunk's logits
+    void* intg_mem = nullptr;
+    float* intg_tab = nullptr;                 // [2, intg_cap]: nodes and weights
+    int intg_cap = 0;
+    float* intg_part = nullptr;                // [max_batch, kIgSlices]: per-slice sums of a gene's attributions (k_ig_delta)
+    bool intg_trunk_once = true;               // frequency-only IG runs the trunk once (CF_IG_TRUNK_ONCE=0 at cf_create: the general path, for A/B checks)
+    int ag_genes = 0;                          // set by cf_integrated_gradients: k_attc2 regions per workgroup chosen as for a batch of this many genes
+    bool skip_dense_embed_bwd = false;         // set by cf_integrated_gradients: the all-rows Embedding backward (it writes parameter gradients) is not run
     // deferred-gradient tile tables
     WgTile* wg_tiles = nullptr;
     int n_wg = 0;
@@ -992,6 +1009,7 @@ extern "C" int cf_create(const cf_config* cfg, const float* const* pe_host, cf_h
     if (const char* e = getenv("CF_XCD_MAP")) h->xcd_map = atoi(e) != 0;
     if (const char* e = getenv("CF_ATTC_CAP")) h->attc_cap = atoi(e);
     if (const char* e = getenv("CF_ATTC1")) h->attc1 = atoi(e) != 0;
+    h->intg_trunk_once = getenv_int("CF_IG_TRUNK_ONCE", 1) != 0;
     if (const char* e = getenv("CF_DEFER_RETILE")) h->defer_retile = atoi(e) != 0;
     if (const char* e = getenv("CF_HEAD_RIDE")) h->head_ride = atoi(e) != 0;
     if (const char* e = getenv("CF_XCD_REDUCE")) h->xcd_reduce = h->xcd_reduce_opt = atoi(e) != 0;
@@ -1022,6 +1040,8 @@ extern "C" void cf_destroy(cf_handle* h) {
     if (h->ride_ev) (void)hipEventDestroy(h->ride_ev);
     if (h->hyper) (void)hipFree(h->hyper);
     if (h->abl_mem) (void)hipFree(h->abl_mem);
+    if (h->intg_mem) (void)hipFree(h->intg_mem);
+    if (h->intg_tab) (void)hipFree(h->intg_tab);
     delete h;
 }
 
@@ -1505,7 +1525,7 @@ static int forward_trunk(cf_handle* h, const cf_batch* bt, int save, hipStream_t
             LAUNCH_CHECK("k_qchain_fwd");
         }
         if (h->attc2) {
-            const int ag = attc2_regions_per_wg(N, h->attc_cap);
+            const int ag = attc2_regions_per_wg(h->ag_genes ? N / B * h->ag_genes : N, h->attc_cap);
             Attc2Args a2;
             size_t sm2 = 0;
             for (int r = 0; r < nres; ++r) {
@@ -2098,7 +2118,7 @@ static int backward_impl(cf_handle* h, const cf_batch* bt, hipStream_t st, int p
         launch_post_bwd<true, 128>(dff, dim3(tiles_of(N), nres), st, pb);
         LAUNCH_CHECK("k_post_bwd<centre>");
         if (h->attc2) {
-            const int ag = attc2_regions_per_wg(N, h->attc_cap);
+            const int ag = attc2_regions_per_wg(h->ag_genes ? N / B * h->ag_genes : N, h->attc_cap);
             Attc2Args a2;
             size_t sm2 = 0;
             for (int r = 0; r < nres; ++r) {
@@ -2175,7 +2195,7 @@ static int backward_impl(cf_handle* h, const cf_batch* bt, hipStream_t st, int p
         LAUNCH_CHECK("k_join_dgrad");
     }
     if (h->embed_dense) {
-        if (embed_dense_backward(h, bt, st)) return -1;      // writes the Embedding gradients directly (no deferred tiles)
+        if (!h->skip_dense_embed_bwd && embed_dense_backward(h, bt, st)) return -1;      // writes the Embedding gradients directly (no deferred tiles)
     } else {   // Embedding
         CentreBuf* bufs[kMaxRes];
         const float* dout[kMaxRes];
@@ -2532,6 +2552,252 @@ extern "C" int cf_pcre_ablation(cf_handle* h, const cf_batch* bt, float* logits,
     h->n_fwd = (int)(g_launches - launches0);
     if (h->capturing) h->cap.n_fwd = h->n_fwd;
     return 0;
+}
+
+// The buffers of cf_integrated_gradients, allocated by its first call; the node / weight table grows with n_steps.
+static int intg_alloc(cf_handle* h, int n_steps) {
+    const cf_config& c = h->cfg;
+    const size_t M = c.max_batch, S = c.i_max, T = S + 1, F = c.n_feats;
+    if (!h->intg_mem) {
+        size_t nf = 0, nb = 0;      // floats, then bytes (every float segment a multiple of 4 floats: 16-byte aligned rows)
+        auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
+        for (int r = 0; r < c.n_res; ++r) nf += 2 * up4(M * c.n_bins[r] * F) + 2 * up4(M * S * c.n_bins[r] * F) + up4(M * T * c.d_emb);
+        nf += 2 * up4(M * T * T) + up4(M * c.n_out) + up4(M * kIgSlices);
+        for (int r = 0; r < c.n_res; ++r) nb += M * c.n_bins[r] + M * S * c.n_bins[r] + M * T * T;
+        void* q = nullptr;
+        if (hipMalloc(&q, nf * sizeof(float) + nb) != hipSuccess) return fail("cf_integrated_gradients: out of memory");
+        h->intg_mem = q;
+        float* f = (float*)q;
+        auto take = [&](size_t n) { float* p = f; f += up4(n); return p; };
+        for (int r = 0; r < c.n_res; ++r) {
+            const size_t L = c.n_bins[r];
+            h->intg_row[r] = take(M * L * F);
+            h->intg_grad[r] = take(M * L * F);
+            h->intg_row[kMaxRes + r] = take(M * S * L * F);
+            h->intg_grad[kMaxRes + r] = take(M * S * L * F);
+            h->intg_stash[r] = take(M * T * c.d_emb);
+        }
+        h->intg_row[2 * kMaxRes] = take(M * T * T);
+        h->intg_grad[2 * kMaxRes] = take(M * T * T);
+        h->intg_logits = take(M * c.n_out);
+        h->intg_part = take(M * kIgSlices);
+        uint8_t* u = (uint8_t*)f;
+        for (int r = 0; r < c.n_res; ++r) {
+            const size_t L = c.n_bins[r];
+            h->intg_pm[r] = u, u += M * L;
+            h->intg_cm[r] = u, u += M * S * L;
+            h->intg_im[r] = u, u += M * T * T;
+        }
+    }
+    if (n_steps > h->intg_cap) {
+        const int cap = std::max(n_steps, 64);
+        if (h->intg_tab) (void)hipFree(h->intg_tab);      // (synchronises: a call in flight may still read the old table)
+        h->intg_tab = nullptr;
+        h->intg_cap = 0;
+        if (hipMalloc(&h->intg_tab, 2 * (size_t)cap * sizeof(float)) != hipSuccess) return fail("cf_integrated_gradients: out of memory");
+        h->intg_cap = cap;
+    }
+    return 0;
+}
+
+// Integrated gradients (cf_ig.h).  General path, per chunk of at most max_batch of the B * V rows: k_ig_expand, the launches of
+// cf_forward(save = 1), backward_impl (head, Regulation, trunk), k_input_grad / k_dfreq_sum into the per-row scratch, k_ig_accumulate;
+// no reduce_impl; k_ig_delta once at the end.  k_attc2 takes as many regions per workgroup as for the caller's B genes (ag_genes),
+// so the chunks run the attention variant model(...) on the batch runs: the result does not depend on max_batch and equals the
+// hand-written loop of grad-enabled model(...) calls on the batch.  Frequency-only path: the trunk once (save = 1, the launches of cf_forward's first part) and its output stashed, then
+// per chunk k_ig_expand (stashed rows, masks, frequencies, dlogits), the Regulation + head forward, backward parts 1 and 2,
+// k_dfreq_sum, k_ig_accumulate.
+extern "C" int cf_integrated_gradients(cf_handle* h, const cf_batch* bt, const cf_ig_opts* o, const cf_input_grads* out,
+                                       float* logits_x, float* logits_base, float* delta, void* stream) {
+    if (!h) return fail("cf_integrated_gradients: null handle");
+    if (!bt) return fail("cf_integrated_gradients: null batch");
+    if (!o) return fail("cf_integrated_gradients: null opts");
+    if (!out) return fail("cf_integrated_gradients: null out");
+    if (!logits_x || !logits_base || !delta) return fail("cf_integrated_gradients: null logits_x / logits_base / delta");
+    const cf_config& c = h->cfg;
+    const int nres = c.n_res, S = c.i_max, T = S + 1, F = c.n_feats, kD = c.d_emb, cap = c.max_batch;
+    if (o->n_steps < 1) return fail("cf_integrated_gradients: n_steps = %d: at least 1 quadrature node", o->n_steps);
+    if (!o->alphas || !o->weights) return fail("cf_integrated_gradients: null alphas / weights");
+    if (o->target < 0 || o->target >= c.n_out) return fail("cf_integrated_gradients: target = %d outside [0, n_out = %d)", o->target, c.n_out);
+    if (o->interpolate & ~(CF_IG_PROMOTER | CF_IG_PCRE | CF_IG_FREQ) || !o->interpolate)
+        return fail("cf_integrated_gradients: interpolate = %d: a non-empty mask of CF_IG_PROMOTER | CF_IG_PCRE | CF_IG_FREQ", o->interpolate);
+    if (bt->B > cap) return fail("cf_integrated_gradients: batch size %d exceeds max_batch=%d", bt->B, cap);
+    const bool ip = o->interpolate & CF_IG_PROMOTER, ic = o->interpolate & CF_IG_PCRE, ifr = o->interpolate & CF_IG_FREQ;
+    for (int r = 0; r < kMaxRes; ++r) {
+        if (r >= nres && (out->promoter_feats[r] || out->pcre_feats[r] || o->base_promoter_feats[r] || o->base_pcre_feats[r]))
+            return fail("cf_integrated_gradients: promoter_feats / pcre_feats[%d]: the model has %d resolutions", r, nres);
+        if (r < nres && (out->promoter_feats[r] != nullptr) != ip)
+            return fail("cf_integrated_gradients: promoter_feats[%d]: the output must be given exactly when promoter_feats is interpolated", r);
+        if (r < nres && (out->pcre_feats[r] != nullptr) != ic)
+            return fail("cf_integrated_gradients: pcre_feats[%d]: the output must be given exactly when pcre_feats is interpolated", r);
+    }
+    if ((out->interaction_freq != nullptr) != ifr)
+        return fail("cf_integrated_gradients: interaction_freq: the output must be given exactly when interaction_freq is interpolated");
+    if (ip && h->embed_dense)
+        return fail("cf_integrated_gradients: promoter_feats: input gradients are implemented for embed.n_layers = 1 (the centre-row Embedding); "
+                    "this model has embed.n_layers = %d (the all-rows path keeps no first-layer input-row gradient)", c.embed_layers);
+    if (ifr && h->reg_fused && !h->reg_dfreq_ok)
+        return fail("cf_integrated_gradients: interaction_freq: the fused Regulation backward variant could not be configured");
+    if (!h->grads) return fail("cf_integrated_gradients: no gradient buffer bound (the backward workspace is set up by cf_bind; the buffer is not written)");
+    if (h->rider.armed || h->rider.done) return fail("cf_integrated_gradients: riders are armed for a training step (cf_rider_arm); finish the step first");
+    if (check_batch(h, bt)) return -1;
+    size_t smem = 0;
+    for (int r = 0; r < nres; ++r) smem = std::max(smem, input_grad_smem(c.n_bins[r], F, kD));
+    if ((ip || ic) && !h->ig_smem_ok) {
+        if (hipFuncSetAttribute((const void*)k_input_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+            return fail("cf_integrated_gradients: promoter_feats / pcre_feats: k_input_grad needs %zu bytes of LDS", smem);
+        h->ig_smem_ok = true;
+    }
+    if (intg_alloc(h, o->n_steps)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    const int B = bt->B, n = o->n_steps, V = n + 2, TT = T * T;
+    const bool freq_only = o->interpolate == CF_IG_FREQ && h->intg_trunk_once;
+    HIP_TRY(hipMemcpyAsync(h->intg_tab, o->alphas, n * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->intg_tab + h->intg_cap, o->weights, n * sizeof(float), hipMemcpyHostToDevice, st));
+    long long n_fwd = 0, n_bwd = 0;
+    IgExpandArgs ea;
+    IgAccArgs aa;
+    memset(&ea, 0, sizeof ea);
+    memset(&aa, 0, sizeof aa);
+    cf_batch cb;      // the chunk's batch: the rows' copies
+    memset(&cb, 0, sizeof cb);
+    for (int r = 0; r < nres; ++r) {
+        const int L = c.n_bins[r];
+        IgSeg* sp = &ea.seg[r];
+        IgSeg* sc = &ea.seg[kMaxRes + r];
+        *sp = IgSeg{bt->promoter_feats[r], o->base_promoter_feats[r], h->intg_row[r], h->intg_grad[r], out->promoter_feats[r], L * F};
+        *sc = IgSeg{bt->pcre_feats[r], o->base_pcre_feats[r], h->intg_row[kMaxRes + r], h->intg_grad[kMaxRes + r], out->pcre_feats[r], S * L * F};
+        ea.pm_in[r] = bt->promoter_mask_row[r];
+        ea.cm_in[r] = bt->pcre_mask_row[r];
+        ea.pm_stride[r] = bt->promoter_mask_stride[r];
+        ea.cm_stride[r] = bt->pcre_mask_stride[r];
+        ea.pm_out[r] = h->intg_pm[r];
+        ea.cm_out[r] = h->intg_cm[r];
+        ea.im_in[r] = bt->interaction_mask[r];
+        ea.im_out[r] = h->intg_im[r];
+        ea.stash[r] = reinterpret_cast<const float4*>(h->intg_stash[r]);
+        ea.x0[r] = reinterpret_cast<float4*>(h->Rx[r][0]);
+        ea.L[r] = L;
+        cb.promoter_feats[r] = h->intg_row[r];
+        cb.pcre_feats[r] = h->intg_row[kMaxRes + r];
+        cb.promoter_mask_row[r] = h->intg_pm[r];
+        cb.promoter_mask_stride[r] = L;
+        cb.pcre_mask_row[r] = h->intg_cm[r];
+        cb.pcre_mask_stride[r] = L;
+        cb.interaction_mask[r] = h->intg_im[r];
+    }
+    ea.seg[2 * kMaxRes] = IgSeg{bt->interaction_freq, o->base_interaction_freq, h->intg_row[2 * kMaxRes], h->intg_grad[2 * kMaxRes], out->interaction_freq, TT};
+    cb.interaction_freq = h->intg_row[2 * kMaxRes];
+    ea.alpha = h->intg_tab;
+    ea.weight = h->intg_tab + h->intg_cap;
+    ea.dlogits = h->dlogits;
+    ea.V = V, ea.S = S, ea.TT = TT, ea.n_out = c.n_out, ea.target = o->target, ea.nres = nres, ea.bcast = o->base_broadcast ? 1 : 0;
+    ea.freq_only = freq_only ? 1 : 0;
+    ea.row4 = T * kD / 4;
+    memcpy(aa.seg, ea.seg, sizeof aa.seg);
+    aa.logits = h->intg_logits;
+    aa.logits_x = logits_x;
+    aa.logits_b = logits_base;
+    aa.part = h->intg_part;
+    aa.V = V, aa.n_out = c.n_out, aa.bcast = ea.bcast;
+    auto run = [&]() -> int {
+        long long l0 = g_launches;
+        if (freq_only) {      // the trunk once on the B genes, its output (the Regulation input) stashed
+            if (forward_trunk(h, bt, 1, st)) return -1;
+            AblateStashArgs sa;
+            memset(&sa, 0, sizeof sa);
+            for (int r = 0; r < nres; ++r) {
+                sa.src[r] = reinterpret_cast<const float4*>(h->Rx[r][0]);
+                sa.dst[r] = reinterpret_cast<float4*>(h->intg_stash[r]);
+            }
+            sa.n4 = (long long)B * ea.row4;
+            hipLaunchKernelGGL(k_pcre_stash, dim3((int)std::min<long long>((sa.n4 + kAblThreads - 1) / kAblThreads, 256), nres), dim3(kAblThreads), 0, st, sa);
+            LAUNCH_CHECK("k_pcre_stash");
+        }
+        n_fwd += g_launches - l0;
+        for (int g0 = 0; g0 < B * V; g0 += cap) {
+            const int nr = std::min(cap, B * V - g0);
+            l0 = g_launches;
+            ea.g0 = g0;
+            hipLaunchKernelGGL(k_ig_expand, dim3(nr, nres), dim3(kIgxThreads), 0, st, ea);
+            LAUNCH_CHECK("k_ig_expand");
+            cb.B = nr;
+            if ((!freq_only && forward_trunk(h, &cb, 1, st)) || forward_reg_head(h, &cb, h->intg_logits, 1, st, nullptr)) return -1;
+            n_fwd += g_launches - l0;
+            l0 = g_launches;
+            h->want_dfreq = ifr ? h->dfreq_part : nullptr;
+            h->skip_dense_embed_bwd = true;
+            if (backward_impl(h, &cb, st, freq_only ? 3 : 7)) return -1;
+            h->want_dfreq = nullptr;
+            h->skip_dense_embed_bwd = false;
+            if (ip || ic) {
+                InGradArgs a;
+                memset(&a, 0, sizeof a);
+                for (int r = 0; r < nres; ++r) {
+                    const int bs = c.binsizes[r];
+                    a.feats_p[r] = cb.promoter_feats[r];
+                    a.feats_c[r] = cb.pcre_feats[r];
+                    a.mask_p[r] = cb.promoter_mask_row[r];
+                    a.mask_c[r] = cb.pcre_mask_row[r];
+                    a.mstride_p[r] = cb.promoter_mask_stride[r];
+                    a.mstride_c[r] = cb.pcre_mask_stride[r];
+                    a.pet[r] = h->pet[r];
+                    a.w_p[r] = h->P_(fmt("embed.%d.lin_proj.weight", bs));
+                    a.w_c[r] = h->P_(fmt("pairwise_interaction.%d.lin_proj_pcre.weight", bs));
+                    a.edx0[r] = h->edx0[r];
+                    a.ep[r] = h->E[r].p;
+                    a.eqt[r] = h->E[r].qt;
+                    a.edxbar[r] = h->E[r].dxbar;
+                    for (int l = 0; l < c.pair_layers; ++l) {
+                        a.pp[r][l] = h->P[r][l].p;
+                        a.pqt[r][l] = h->P[r][l].qt;
+                        a.pdxbar[r][l] = h->P[r][l].dxbar;
+                    }
+                    a.out_p[r] = ip ? h->intg_grad[r] : nullptr;
+                    a.out_c[r] = ic ? h->intg_grad[kMaxRes + r] : nullptr;
+                    a.L[r] = c.n_bins[r];
+                }
+                a.B = nr;
+                a.S = S;
+                a.F = F;
+                a.D = kD;
+                a.nh_e = c.embed_heads;
+                a.nh_p = c.pair_heads;
+                a.n_pl = c.pair_layers;
+                a.rs_e = 1.0f / sqrtf((float)(kD / c.embed_heads));
+                a.rs_p = 1.0f / sqrtf((float)(kD / c.pair_heads));
+                hipLaunchKernelGGL(k_input_grad, dim3(1 + S, nr, nres), dim3(kIgThreads), smem, st, a);
+                LAUNCH_CHECK("k_input_grad");
+            }
+            if (ifr) {
+                const int ne = nr * TT;
+                hipLaunchKernelGGL(k_dfreq_sum, dim3((ne + 255) / 256), dim3(256), 0, st, h->dfreq_part, h->intg_grad[2 * kMaxRes], ne, nres);
+                LAUNCH_CHECK("k_dfreq_sum");
+            }
+            aa.g0 = g0;
+            aa.n = nr;
+            hipLaunchKernelGGL(k_ig_accumulate, dim3((g0 + nr - 1) / V - g0 / V + 1, kIgSlices), dim3(kIgxThreads), 0, st, aa);
+            LAUNCH_CHECK("k_ig_accumulate");
+            n_bwd += g_launches - l0;
+        }
+        l0 = g_launches;
+        hipLaunchKernelGGL(k_ig_delta, dim3((B + 63) / 64), dim3(64), 0, st, h->intg_part, logits_x, logits_base, delta, B, c.n_out, o->target);
+        LAUNCH_CHECK("k_ig_delta");
+        n_bwd += g_launches - l0;
+        return 0;
+    };
+    const bool pend_record = h->pend_record;      // (a step record queued for the next training backward stays queued for it)
+    h->pend_record = false;
+    h->ag_genes = B;
+    const int rc = run();
+    h->ag_genes = 0;
+    h->want_dfreq = nullptr;
+    h->skip_dense_embed_bwd = false;
+    h->pend_record = pend_record;
+    h->last_fwd_B = 0;
+    h->n_fwd = (int)n_fwd;
+    h->n_bwd = (int)n_bwd;
+    return rc ? -1 : 0;
 }
 
 // ------------------------------------------------------------------------------------

@@ -126,7 +126,7 @@ class ChromoformerBase(nn.Module):
         self.n_bins = [w_max // b for b in self.binsizes]
         self._kws = (embed, pair, reg)
         self._max_batch = max_batch
-        self._maps_gen = 0          # bumped by attention_maps() / pcre_ablation(): a pending backward of an earlier forward refuses to run
+        self._maps_gen = 0          # bumped by attention_maps() / pcre_ablation() / integrated_gradients(): a pending backward of an earlier forward refuses to run
         self._maps_by = None        # ... naming the last of them
         self._handle = None
         self._device = None
@@ -421,6 +421,107 @@ class ChromoformerBase(nn.Module):
         self._maps_by = "pcre_ablation"
         _lib.check(_lib.lib().cf_pcre_ablation(self._handle, C.byref(bs), logits.data_ptr(), st), "cf_pcre_ablation")
         return logits
+
+    @torch.no_grad()
+    def integrated_gradients(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                             interaction_freq=None, target=None, n_steps=50, method="gausslegendre", baselines=None,
+                             inputs=("promoter_feats", "pcre_feats", "interaction_freq")):
+        """Integrated gradients of logit column `target` (default: 1 for the classifier, 0 for the regressor) with respect to the float
+        inputs named in `inputs` (cf_integrated_gradients) -> (attr, info), tensors on the model's device, no autograd graph:
+
+          attr["promoter_feats"][b], attr["pcre_feats"][b], attr["interaction_freq"]   the caller's shapes (inputs not named: absent)
+          info["logits"], info["baseline_logits"]   [B, n_out]: the forward of x and of the baseline
+          info["delta"]                             [B]: sum of a gene's attributions - (logits - baseline_logits)[:, target]
+
+        With nodes a_k and weights w_k of chromoformer_amd.attribution.ig_quadrature(method, n_steps): x_k = xb + a_k (x - xb),
+        g_k = d(w_k logits[:, target]) / d x_k, attr = (x - xb) * (g_0 + g_1 + ... + g_{n-1}) -- what a hand-written loop of
+        grad-enabled model(...) calls and backward()s gives, bit for bit.  `baselines`: None (zeros, the binned value of an empty
+        signal) or a dict with some of the three keys ({binsize: tensor} for the features), each with a leading dimension of B or 1.
+        Masks are never interpolated.  The first argument may also be a packed batch (an engine.Slot or a pack_batch result), with
+        nothing after it.  Parameter gradients and optimiser state are left as they are; the pass overwrites the activations a
+        grad-enabled model(...) keeps for its backward: such a pending backward() raises."""
+        from .attribution import INPUTS, ig_quadrature
+        shapes = None
+        if promoter_pad_masks is None:
+            bs = promoter_feats.struct if hasattr(promoter_feats, "struct") else promoter_feats[0]
+        else:
+            bs, _keep = self._pack(promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq)      # (alive until the call)
+            shapes = {"promoter_feats": {b: promoter_feats[b].shape for b in self.binsizes},
+                      "pcre_feats": {b: pcre_feats[b].shape for b in self.binsizes}, "interaction_freq": interaction_freq.shape}
+        if self._handle is None:
+            raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
+        inputs = (inputs,) if isinstance(inputs, str) else tuple(inputs)
+        bad = [k for k in inputs if k not in INPUTS]
+        if bad or not inputs:
+            raise ValueError("integrated_gradients: inputs %s; choose a non-empty subset of %s" % (bad or "()", INPUTS))
+        target = (1 if self.n_out == 2 else 0) if target is None else int(target)
+        alphas, weights = ig_quadrature(method, n_steps)
+        B, S, T, F, dev = bs.B, self.i_max, self.i_max + 1, self.n_feats, self._device
+        canon = {"promoter_feats": {b: (B, L, F) for b, L in zip(self.binsizes, self.n_bins)},
+                 "pcre_feats": {b: (B, S, L, F) for b, L in zip(self.binsizes, self.n_bins)}, "interaction_freq": (B, T, T)}
+        opts = _lib.cf_ig_opts()
+        opts.n_steps, opts.target = len(alphas), target
+        opts.interpolate = sum(bit for k, bit in zip(INPUTS, (_lib.IG_PROMOTER, _lib.IG_PCRE, _lib.IG_FREQ)) if k in inputs)
+        opts.alphas, opts.weights = alphas.ctypes.data, weights.ctypes.data
+        keep = []
+        baselines = baselines or {}
+        extra = [k for k in baselines if k not in INPUTS]
+        if extra:
+            raise ValueError("integrated_gradients: unknown baseline(s) %s; keys are %s" % (extra, INPUTS))
+        unused = [k for k in baselines if baselines[k] is not None and k not in inputs]
+        if unused:
+            raise ValueError("integrated_gradients: baseline(s) given for %s, which are not in inputs=%s" % (unused, inputs))
+        leads = set()
+        for k in inputs:
+            if baselines.get(k) is None:
+                continue
+            for t in (baselines[k].values() if isinstance(baselines[k], dict) else [baselines[k]]):
+                leads.add(t.shape[0])
+        if leads - {1, B}:
+            raise ValueError("integrated_gradients: baselines need a leading dimension of B = %d or 1, got %s" % (B, sorted(leads)))
+        bcast = leads == {1}
+
+        def base(t, shape):
+            n = 1 if bcast else B
+            t = t.to(dev, torch.float32)
+            if t.numel() != n * int(np.prod(shape[1:])):
+                t = t.expand(B, *t.shape[1:]) if t.shape[0] == 1 else t
+                if t.numel() != n * int(np.prod(shape[1:])):
+                    raise ValueError("integrated_gradients: a baseline of %d elements does not match the input's shape %s" % (t.numel(), tuple(shape)))
+            t = t.contiguous()
+            keep.append(t)
+            return t.data_ptr()
+
+        for r, b in enumerate(self.binsizes):
+            if "promoter_feats" in inputs and baselines.get("promoter_feats") is not None:
+                opts.base_promoter_feats[r] = base(baselines["promoter_feats"][b], canon["promoter_feats"][b])
+            if "pcre_feats" in inputs and baselines.get("pcre_feats") is not None:
+                opts.base_pcre_feats[r] = base(baselines["pcre_feats"][b], canon["pcre_feats"][b])
+        if "interaction_freq" in inputs and baselines.get("interaction_freq") is not None:
+            opts.base_interaction_freq = base(baselines["interaction_freq"], canon["interaction_freq"])
+        opts.base_broadcast = 1 if bcast else 0
+        out = _lib.cf_input_grads()
+        attr = {}
+        for r, b in enumerate(self.binsizes):
+            for k, field in (("promoter_feats", out.promoter_feats), ("pcre_feats", out.pcre_feats)):
+                if k in inputs:
+                    t = attr.setdefault(k, {})[b] = torch.empty(canon[k][b], device=dev)      # (written in full by the library)
+                    field[r] = t.data_ptr()
+        if "interaction_freq" in inputs:
+            t = attr["interaction_freq"] = torch.empty(canon["interaction_freq"], device=dev)
+            out.interaction_freq = t.data_ptr()
+        lx = torch.empty(B, self.n_out, device=dev)
+        lb = torch.empty(B, self.n_out, device=dev)
+        delta = torch.empty(B, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        self._sync_tiled(st)
+        self._maps_gen += 1
+        self._maps_by = "integrated_gradients"
+        _lib.check(_lib.lib().cf_integrated_gradients(self._handle, C.byref(bs), C.byref(opts), C.byref(out), lx.data_ptr(), lb.data_ptr(),
+                                                      delta.data_ptr(), st), "cf_integrated_gradients")
+        if shapes is not None:
+            attr = {k: ({b: t.view(shapes[k][b]) for b, t in v.items()} if isinstance(v, dict) else v.view(shapes[k])) for k, v in attr.items()}
+        return attr, {"logits": lx, "baseline_logits": lb, "delta": delta}
 
     def embed_full(self, promoter_feats, promoter_pad_masks):
         """EmbeddingTransformer's first return value (net.py:57-59): {binsize: [B, 1, L, 128]}, the embedding of every

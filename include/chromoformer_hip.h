@@ -209,6 +209,44 @@ int cf_attention_maps(cf_handle* h, const cf_batch* batch, float* logits, const 
  * cf_destroy; ~1 MB at max_batch 64); later calls allocate nothing.  A null handle / batch / logits or B > max_batch fails by name,
  * before anything is launched. */
 int cf_pcre_ablation(cf_handle* h, const cf_batch* batch, float* logits, void* stream);
+/* Integrated gradients (interpretation).  For the target logit column t, nodes a_k and weights w_k (k < n_steps) on [0, 1], per
+ * interpolated input x with baseline xb (T = i_max + 1):
+ *   x_k   = xb + a_k (x - xb)                         fp32, each operation rounded
+ *   g_k   = d(w_k logits[:, t]) / d x_k               (the backward from dlogits = w_k at column t, 0 elsewhere)
+ *   attr  = (x - xb) ((g_0 + g_1) + ... + g_{n-1})    fp32, in k order
+ *   delta = sum(attr over every interpolated element) - (F(x)[t] - F(xb)[t])        per gene
+ * `interpolate` selects the inputs: bit 0 promoter_feats, bit 1 pcre_feats, bit 2 interaction_freq (every resolution); the others and
+ * every mask stay at the given batch.  The outputs of `out` must be exactly those of the interpolated inputs (every resolution);
+ * each is OVERWRITTEN in full, in the layout of cf_input_grads: zeros for padded bins, dummy slots, masked interaction entries.
+ * logits_x / logits_base [B, n_out]: the forward of x / of xb; delta [B]. */
+#define CF_IG_PROMOTER 1
+#define CF_IG_PCRE 2
+#define CF_IG_FREQ 4
+typedef struct cf_ig_opts {
+    int n_steps, target, interpolate;
+    const float* alphas;             /* host [n_steps]: nodes a_k (read before the call returns)   */
+    const float* weights;            /* host [n_steps]: weights w_k                                */
+    const float* base_promoter_feats[CF_MAX_RES];   /* device baselines, layout of the inputs; NULL: zeros */
+    const float* base_pcre_feats[CF_MAX_RES];
+    const float* base_interaction_freq;
+    int base_broadcast;              /* 1: the baselines hold one gene, used for every gene                              */
+} cf_ig_opts;
+/* Rows are (gene, variant) pairs, gene-major, V = n_steps + 2 per gene (x, xb, then x_0 .. x_{n-1}), processed in chunks of at most
+ * max_batch rows.  Per chunk: k_ig_expand (the rows' inputs, masks and dlogits into buffers the first call allocates), the launches
+ * of cf_forward(save = 1) and of the backward chain with the input-gradient launches of cf_backward_from_inputs -- but no gradient
+ * reduction: the bound gradient buffer, the moments and the parameters are left as they were -- then k_ig_accumulate; k_ig_delta
+ * once at the end.  When only interaction_freq is interpolated the trunk runs once, its output is stashed, and the chunks run the
+ * Regulation + head forward and backward only (bit-equal to the general path, which CF_IG_TRUNK_ONCE=0 at cf_create selects).
+ * Deterministic (no atomics, fixed order).  Where the gene-batched attention kernel k_attc2 runs (configurations off the fused
+ * trunk: i_max > 8, embed.n_layers > 1, head counts other than 2), its regions per workgroup follow the number of sequences in the
+ * launch; the chunks take the count cf_forward would take for the B genes of the batch.  So the result does not depend on max_batch
+ * and equals cf_forward(save = 1) + cf_backward_from_inputs on the batch, per node, bit for bit.
+ * Overwrites the activations a cf_forward(save >= 1) kept: no cf_backward* may follow without a new saving forward.
+ * Refused by name, before anything is launched: a null argument, n_steps < 1, target outside [0, n_out), B > max_batch, an output
+ * that does not match `interpolate` or names a resolution >= n_res, promoter_feats with embed.n_layers > 1, no bound gradient
+ * buffer (its workspace), armed riders. */
+int cf_integrated_gradients(cf_handle* h, const cf_batch* batch, const cf_ig_opts* opts, const cf_input_grads* out,
+                            float* logits_x, float* logits_base, float* delta, void* stream);
 /* torch.optim.AdamW.step (train.py:157, 196): decoupled weight decay, bias correction
  * from `step` (1-based), over [0, n_active). */
 int cf_adamw_step(cf_handle* h, float lr, float beta1, float beta2, float eps, float weight_decay,
