@@ -346,7 +346,7 @@ struct cf_handle {
     // promoter_feats[r], pcre_feats[r], interaction_freq (cf_ig.h)
     float* intg_row[kIgSegs] = {};             // [max_batch, len]: a chunk's inputs
     float* intg_grad[kIgSegs] = {};            // [max_batch, len]: their per-row gradients
-    uint8_t* intg_pm[kMaxRes] = {};            // [max_batch, L]: promoter pad-mask centre rows
+    uint8_t* intg_pm[kMaxRes] = {};            // [max_batch, L]: promoter pad-mask centre rows ([max_batch, L, L] with the all-rows Embedding)
     uint8_t* intg_cm[kMaxRes] = {};            // [max_batch * i_max, L]: pCRE pad-mask centre rows
     uint8_t* intg_im[kMaxRes] = {};            // [max_batch, T, T]: interaction masks
     float* intg_stash[kMaxRes] = {};           // [max_batch, T, d_emb]: the trunk's output (frequency-only path)
@@ -2563,7 +2563,9 @@ static int intg_alloc(cf_handle* h, int n_steps) {
         auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
         for (int r = 0; r < c.n_res; ++r) nf += 2 * up4(M * c.n_bins[r] * F) + 2 * up4(M * S * c.n_bins[r] * F) + up4(M * T * c.d_emb);
         nf += 2 * up4(M * T * T) + up4(M * c.n_out) + up4(M * kIgSlices);
-        for (int r = 0; r < c.n_res; ++r) nb += M * c.n_bins[r] + M * S * c.n_bins[r] + M * T * T;
+        // (the all-rows Embedding reads every row of a full [B, L, L] promoter mask: its chunks keep L rows per chunk row)
+        auto pm_rows = [&](int r) { return h->embed_dense ? (size_t)c.n_bins[r] : (size_t)1; };
+        for (int r = 0; r < c.n_res; ++r) nb += M * pm_rows(r) * c.n_bins[r] + M * S * c.n_bins[r] + M * T * T;
         void* q = nullptr;
         if (hipMalloc(&q, nf * sizeof(float) + nb) != hipSuccess) return fail("cf_integrated_gradients: out of memory");
         h->intg_mem = q;
@@ -2584,7 +2586,7 @@ static int intg_alloc(cf_handle* h, int n_steps) {
         uint8_t* u = (uint8_t*)f;
         for (int r = 0; r < c.n_res; ++r) {
             const size_t L = c.n_bins[r];
-            h->intg_pm[r] = u, u += M * L;
+            h->intg_pm[r] = u, u += M * pm_rows(r) * L;
             h->intg_cm[r] = u, u += M * S * L;
             h->intg_im[r] = u, u += M * T * T;
         }
@@ -2667,7 +2669,11 @@ extern "C" int cf_integrated_gradients(cf_handle* h, const cf_batch* bt, const c
         IgSeg* sc = &ea.seg[kMaxRes + r];
         *sp = IgSeg{bt->promoter_feats[r], o->base_promoter_feats[r], h->intg_row[r], h->intg_grad[r], out->promoter_feats[r], L * F};
         *sc = IgSeg{bt->pcre_feats[r], o->base_pcre_feats[r], h->intg_row[kMaxRes + r], h->intg_grad[kMaxRes + r], out->pcre_feats[r], S * L * F};
-        ea.pm_in[r] = bt->promoter_mask_row[r];
+        // The all-rows Embedding (embed.n_layers > 1) honours a full [B, L, L] promoter mask entry by entry: the chunk rows carry
+        // all L rows of their gene's mask, not the centre row alone (from which only the dataset's not(valid x valid) form can be rebuilt).
+        const bool pm_full = h->embed_dense && bt->promoter_mask_stride[r] == (long long)L * L;
+        ea.pm_rows[r] = pm_full ? L : 1;
+        ea.pm_in[r] = static_cast<const uint8_t*>(bt->promoter_mask_row[r]) - (pm_full ? (size_t)(L / 2) * L : 0);
         ea.cm_in[r] = bt->pcre_mask_row[r];
         ea.pm_stride[r] = bt->promoter_mask_stride[r];
         ea.cm_stride[r] = bt->pcre_mask_stride[r];
@@ -2680,8 +2686,8 @@ extern "C" int cf_integrated_gradients(cf_handle* h, const cf_batch* bt, const c
         ea.L[r] = L;
         cb.promoter_feats[r] = h->intg_row[r];
         cb.pcre_feats[r] = h->intg_row[kMaxRes + r];
-        cb.promoter_mask_row[r] = h->intg_pm[r];
-        cb.promoter_mask_stride[r] = L;
+        cb.promoter_mask_row[r] = h->intg_pm[r] + (pm_full ? (size_t)(L / 2) * L : 0);
+        cb.promoter_mask_stride[r] = pm_full ? (long long)L * L : L;
         cb.pcre_mask_row[r] = h->intg_cm[r];
         cb.pcre_mask_stride[r] = L;
         cb.interaction_mask[r] = h->intg_im[r];

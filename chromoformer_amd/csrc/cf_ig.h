@@ -43,6 +43,8 @@ struct IgExpandArgs {
     long long pm_stride[kMaxRes], cm_stride[kMaxRes];
     uint8_t* pm_out[kMaxRes];          // the chunk's compact rows, stride L
     uint8_t* cm_out[kMaxRes];
+    int pm_rows[kMaxRes];              // 1; L where the all-rows Embedding reads the caller's full [B, L, L] promoter mask: pm_in is then
+                                       // row 0 of gene 0 and the chunk's copy keeps all L rows per chunk row (stride L * L)
     const uint8_t* im_in[kMaxRes];     // interaction masks [B, T, T]
     uint8_t* im_out[kMaxRes];
     const float4* stash[kMaxRes];      // frequency-only mode: the trunk output of the B genes, [B, T * D / 4]
@@ -97,7 +99,8 @@ __global__ __launch_bounds__(kIgxThreads) void k_ig_expand(IgExpandArgs a) {
         const int L = a.L[r], S = a.S;
         ig_row(a.seg[r], b, i, v, alpha, bc);
         ig_row(a.seg[kMaxRes + r], b, i, v, alpha, bc);
-        for (int k = tid; k < L; k += kIgxThreads) a.pm_out[r][(size_t)i * L + k] = a.pm_in[r][(size_t)b * a.pm_stride[r] + k];
+        const int PL = a.pm_rows[r] * L;
+        for (int k = tid; k < PL; k += kIgxThreads) a.pm_out[r][(size_t)i * PL + k] = a.pm_in[r][(size_t)b * a.pm_stride[r] + k];
         for (int k = tid; k < S * L; k += kIgxThreads) {
             const int s = k / L, j = k - s * L;
             a.cm_out[r][((size_t)i * S + s) * L + j] = a.cm_in[r][((size_t)b * S + s) * a.cm_stride[r] + j];

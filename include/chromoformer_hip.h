@@ -177,7 +177,9 @@ typedef struct cf_input_grads {
     float* interaction_freq;             /* [B, T, T], T = i_max + 1       */
 } cf_input_grads;
 /* cf_backward_from (same preconditions, bit-identical parameter gradients) that also OVERWRITES every requested input
- * gradient in full: zeros for padded bins, dummy pCRE slots and masked interaction entries.  want == NULL or all
+ * gradient in full, with zeros where the reference's autograd gives zeros: masked bins of a pad row that has a valid bin,
+ * interaction entries masked at every resolution, pCRE slots no unmasked interaction entry reaches (the dataset's dummy
+ * slots).  A fully padded slot whose token IS visible has a uniform softmax row and non-zero gradients.  want == NULL or all
  * fields NULL: exactly the launches of cf_backward_from.  Deterministic (no atomics).  promoter_feats needs
  * embed.n_layers = 1; a configuration the kernels do not cover fails before anything is launched. */
 int cf_backward_from_inputs(cf_handle* h, const cf_batch* batch, const float* dlogits, const cf_input_grads* want,

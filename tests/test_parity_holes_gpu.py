@@ -15,44 +15,15 @@ import os
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from oracle import chromoformer_oracle as orc
 from tests.helpers import GOLDEN
+from tests.helpers import perturbed_params as _perturbed
+from tests.helpers import referee_hip as _hip
+from tests.helpers import referee_oracle as _oracle
 
 pytestmark = pytest.mark.gpu
 B = 64
-
-
-def _hip(Model, batch, P):
-    model = Model(seed=42, max_batch=batch["interaction_freq"].shape[0]).cuda(0)
-    model.load_state_dict(P)
-    logits, loss = model.forward_backward(model.pack_batch(batch), batch["label"])
-    torch.cuda.synchronize()
-    model._publish_grads()
-    return logits.cpu().clone(), float(loss), {k: p.grad.detach().cpu().clone() for k, p in model.named_parameters() if p.grad is not None}
-
-
-def _oracle(P, batch, regression, dtype):
-    Pr = {k: v.detach().to(dtype).clone().requires_grad_(True) for k, v in P.items()}
-    b = {k: ({kk: (vv.to(dtype) if vv.is_floating_point() else vv) for kk, vv in v.items()} if isinstance(v, dict) else v) for k, v in batch.items()}
-    b["interaction_freq"] = batch["interaction_freq"].to(dtype)
-    logits = orc.forward(Pr, b)
-    if regression:
-        loss = F.mse_loss(logits, batch["label"].view(-1, 1).to(dtype))
-    else:
-        loss = F.cross_entropy(logits, batch["label"].long())
-    loss.backward()
-    return logits.detach(), float(loss), {k: v.grad for k, v in Pr.items() if v.grad is not None and not orc.never_trained(k)}
-
-
-def _perturbed(regression):
-    P = orc.init_params(None, 42, regression)
-    g = torch.Generator().manual_seed(5)
-    with torch.no_grad():
-        for v in P.values():
-            v.add_(0.02 * torch.randn(v.shape, generator=g))
-    return P
 
 
 @pytest.mark.parametrize("regression", [False, True], ids=["classifier", "regressor"])
