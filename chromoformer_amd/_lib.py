@@ -89,6 +89,11 @@ class cf_store(C.Structure):
     ]
 
 
+class cf_x0_store(C.Structure):
+    _fields_ = [("n_genes", C.c_longlong), ("x0", C.c_void_p * MAX_RES), ("interaction_mask", C.c_void_p * MAX_RES),
+                ("interaction_freq", C.c_void_p), ("labels", C.c_void_p)]
+
+
 #: every symbol include/chromoformer_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "cf_abi_version": (C.c_int, []),
@@ -157,6 +162,14 @@ SYMBOLS = {
                               + [C.POINTER(cf_dense_layer_grads)] + [C.c_void_p] * 3),
     "cf_op_attention_fwd": (C.c_int, [C.POINTER(cf_attn_shape)] + [C.c_void_p] * 9),
     "cf_op_attention_bwd": (C.c_int, [C.POINTER(cf_attn_shape)] + [C.c_void_p] * 14),
+    "cf_trunk_outputs": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(C.c_void_p), C.c_void_p]),
+    "cf_forward_train_x0": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                      C.c_void_p]),
+    "cf_x0_gather": (C.c_int, [C.c_void_p, C.POINTER(cf_x0_store), C.c_void_p, C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.c_void_p]),
+    "cf_x0_gather_fwd": (C.c_int, [C.c_void_p, C.POINTER(cf_x0_store), C.c_void_p, C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.c_void_p]),
+    "cf_reduce_opt_x0": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_longlong, C.c_int, C.c_void_p,
+                                   C.c_void_p]),
+    "cf_backward_from_top": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

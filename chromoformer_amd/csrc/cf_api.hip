@@ -7,6 +7,7 @@
 #include "cf_attn_maps.h"
 #include "cf_ablate.h"
 #include "cf_ig.h"
+#include "cf_x0_gather.h"
 
 #include <algorithm>
 #include <cmath>
@@ -284,6 +285,9 @@ struct cf_handle {
                                                // pass over ANOTHER batch (validation between two steps of a fed epoch) must not consume them
     GatherArgs pend_ga;
     int pend_ga_n = 0;
+    bool x0_fwd = false;                       // the last saving forward was cf_forward_train_x0: the trunk kept no activations, cf_backward_part(parts & 4) refuses
+    bool pend_x0 = false;                      // cf_x0_gather_fwd: the cache gather of the step shares a launch with the prologue of the next cf_forward_train_x0
+    X0GatherArgs pend_x0_ga;
     bool head_ride = true;                     // CF_HEAD_RIDE=0 (read at cf_create): the head stays a launch of its own (k_head_train)
     HeadRide ride;
     int* head_cnt = nullptr;
@@ -397,6 +401,7 @@ struct cf_handle {
         // launches it holds (-1: none), whether it starts a backward pass (head: the per-step counters restart), the backward launches it holds
         int n_fwd = -1, n_bwd = 0;
         bool starts_bwd = false;
+        bool x0_fwd = false;       // the forward it holds is cf_forward_train_x0
     };
     std::vector<Replay> replays;
     Replay cap;                    // under construction
@@ -1761,6 +1766,7 @@ static int forward_impl(cf_handle* h, const cf_batch* bt, float* logits, int sav
     hipStream_t st = (hipStream_t)stream;
     const long long launches0 = g_launches;
     if (forward_trunk(h, bt, save, st) || forward_reg_head(h, bt, logits, save, st, ride)) return -1;
+    h->x0_fwd = false;
     h->last_fwd_B = save ? bt->B : 0;
     h->n_fwd = (int)(g_launches - launches0);
     if (h->capturing) h->cap.n_fwd = h->n_fwd;
@@ -1821,14 +1827,9 @@ static int ride_tick(cf_handle* h, hipStream_t st) {
     }
     return 0;
 }
-extern "C" int cf_forward_train(cf_handle* h, const cf_batch* bt, float* logits, const void* labels, float loss_scale, float* loss_out,
-                                void* stream) {
-    if (!h) return fail("null handle");
-    if (!labels || !cf_head_rides(h)) return forward_impl(h, bt, logits, 2, stream, nullptr);
-    if (ride_tick(h, (hipStream_t)stream)) return -1;
-    if (!h->grads) return fail("cf_forward_train: no gradient buffer bound");
+// the head's ride at the tail of the Regulation forward launch (cf_forward_train, cf_forward_train_x0)
+static void head_ride_args(cf_handle* h, float* logits, const void* labels, float loss_scale, float* loss_out, HeadRide& hd) {
     const cf_config& c = h->cfg;
-    HeadRide hd;
     memset(&hd, 0, sizeof hd);
     hd.on = 1;
     hd.n_out = c.n_out;
@@ -1843,6 +1844,15 @@ extern "C" int cf_forward_train(cf_handle* h, const cf_batch* bt, float* logits,
     for (int r = 0; r < c.n_res; ++r) hd.dxl[r] = h->dRx[r][c.reg_layers];
     hd.loss = h->loss, hd.loss_part = h->loss_part, hd.loss_user = loss_out;
     hd.cnt = h->head_cnt;
+}
+extern "C" int cf_forward_train(cf_handle* h, const cf_batch* bt, float* logits, const void* labels, float loss_scale, float* loss_out,
+                                void* stream) {
+    if (!h) return fail("null handle");
+    if (!labels || !cf_head_rides(h)) return forward_impl(h, bt, logits, 2, stream, nullptr);
+    if (ride_tick(h, (hipStream_t)stream)) return -1;
+    if (!h->grads) return fail("cf_forward_train: no gradient buffer bound");
+    HeadRide hd;
+    head_ride_args(h, logits, labels, loss_scale, loss_out, hd);
     h->ride = hd;                 // (the backward launch finishes the mean loss)
     return forward_impl(h, bt, logits, 2, stream, &hd);
 }
@@ -2256,8 +2266,9 @@ static int reduce_impl(cf_handle* h, int B, hipStream_t st, int buckets = CF_BUC
 }
 
 // `first`: the call starts a backward pass (later pieces may follow a replayed graph, which bypasses the host-side record)
+static int check_batch_x0(const cf_handle* h, const cf_batch* b, const char* who);      // (with the frozen-trunk entry points below)
 static int check_bwd(cf_handle* h, const cf_batch* bt, bool first = true) {
-    if (check_batch(h, bt)) return -1;
+    if (h && h->x0_fwd ? check_batch_x0(h, bt, "cf_backward") : check_batch(h, bt)) return -1;
     if (!h->grads) return fail("cf_backward: no gradient buffer bound");
     if (first && h->last_fwd_B != bt->B) return fail("cf_backward must follow cf_forward(save_for_backward=1) on the same batch");
     return 0;
@@ -2265,6 +2276,9 @@ static int check_bwd(cf_handle* h, const cf_batch* bt, bool first = true) {
 
 extern "C" int cf_backward_part(cf_handle* h, const cf_batch* bt, const void* labels, float loss_scale, float* loss_out, int parts,
                                 void* stream) {
+    if (h && (parts & 4) && h->x0_fwd)
+        return fail("cf_backward_part: parts & 4 (the Pairwise + Embedding backward) cannot follow cf_forward_train_x0: that forward started at the "
+                    "Regulation input and the trunk kept no activations (frozen trunk: run parts 1 | 2 and reduce CF_BUCKET_REG only)");
     if (check_bwd(h, bt, (parts & 1) != 0)) return -1;
     hipStream_t st = (hipStream_t)stream;
     if ((parts & 1) && !labels && !h->head_done) return fail("cf_backward: labels is null");
@@ -2339,6 +2353,17 @@ extern "C" int cf_backward_from(cf_handle* h, const cf_batch* bt, const float* d
     HIP_TRY(hipMemcpyAsync(h->dlogits, dlogits, (size_t)bt->B * h->cfg.n_out * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (backward_impl(h, bt, st)) return -1;
     return reduce_impl(h, bt->B, st);
+}
+
+// cf_backward_from for a frozen trunk: head + Regulation backward and the Regulation + head bucket's reductions only (same launches as the
+// corresponding pieces of cf_backward_from: same bits in that range); the Embedding + Pairwise range of the gradient buffer is not written.
+extern "C" int cf_backward_from_top(cf_handle* h, const cf_batch* bt, const float* dlogits, void* stream) {
+    if (check_bwd(h, bt)) return -1;
+    if (!dlogits) return fail("cf_backward_from_top: dlogits is null");
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(h->dlogits, dlogits, (size_t)bt->B * h->cfg.n_out * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (backward_impl(h, bt, st, 3)) return -1;
+    return reduce_impl(h, bt->B, st, CF_BUCKET_REG);
 }
 
 // cf_backward_from + the gradients of the float inputs (cf_input_grad.h).  The parameter gradients come from the very launches of
@@ -2839,6 +2864,7 @@ extern "C" int cf_graph_launch(cf_handle* h, int graph_id, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (rp.n_fwd >= 0) {
         h->n_fwd = rp.n_fwd;
+        h->x0_fwd = rp.x0_fwd;
         h->adv_next = nullptr;      // (a replayed forward pass moves the cursor on by itself if it was captured that way)
         h->pend_key = nullptr;
     }
@@ -3136,6 +3162,166 @@ extern "C" int cf_retile_early(cf_handle* h, void* stream) {
 extern "C" int cf_adamw_step(cf_handle* h, float lr, float beta1, float beta2, float eps, float weight_decay, long long step,
                              void* stream) {
     return cf_adamw_step_part(h, lr, beta1, beta2, eps, weight_decay, step, CF_BUCKET_REG | CF_BUCKET_PE, stream);
+}
+
+// ------------------------------------------------------------------------------------
+// frozen trunk: trunk outputs, the training forward from the Regulation input, the cache gather (cf_x0_gather.h)
+// ------------------------------------------------------------------------------------
+static int check_batch_x0(const cf_handle* h, const cf_batch* b, const char* who) {
+    if (!h || !b) return fail("%s: null handle / batch", who);
+    if (!h->params) return fail("%s: cf_bind has not been called", who);
+    if (b->B < 1 || b->B > h->cfg.max_batch) return fail("%s: batch size %d outside 1..max_batch=%d", who, b->B, h->cfg.max_batch);
+    for (int r = 0; r < h->cfg.n_res; ++r)
+        if (!b->interaction_mask[r]) return fail("%s: interaction_mask of resolution %d is null", who, r);
+    if (!b->interaction_freq) return fail("%s: interaction_freq is null", who);
+    return 0;
+}
+static int x0_copy(cf_handle* h, int B, const float* const* src, float* const* dst, hipStream_t st) {
+    X0CopyArgs a;
+    memset(&a, 0, sizeof a);
+    for (int r = 0; r < h->cfg.n_res; ++r) {
+        a.src[r] = reinterpret_cast<const float4*>(src[r]);
+        a.dst[r] = reinterpret_cast<float4*>(dst[r]);
+    }
+    a.n4 = (long long)B * (h->cfg.i_max + 1) * h->cfg.d_emb / 4;      // (d_emb is a multiple of 4: check_config)
+    hipLaunchKernelGGL(k_x0_copy, dim3((int)std::min<long long>((a.n4 + kX0Threads - 1) / kX0Threads, 256), h->cfg.n_res), dim3(kX0Threads), 0, st, a);
+    LAUNCH_CHECK("k_x0_copy");
+    return 0;
+}
+extern "C" int cf_trunk_outputs(cf_handle* h, const cf_batch* bt, float* const* x0, void* stream) {
+    if (!h) return fail("cf_trunk_outputs: null handle");
+    if (!bt || !x0) return fail("cf_trunk_outputs: null batch / output table");
+    if (check_batch(h, bt)) return -1;
+    const float* src[kMaxRes] = {};
+    for (int r = 0; r < h->cfg.n_res; ++r) {
+        if (!x0[r]) return fail("cf_trunk_outputs: x0[%d] is null", r);
+        if ((uintptr_t)x0[r] & 15) return fail("cf_trunk_outputs: x0[%d] is not 16-byte aligned", r);
+        src[r] = h->Rx[r][0];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const long long launches0 = g_launches;
+    if (forward_trunk(h, bt, 0, st) || x0_copy(h, bt->B, src, x0, st)) return -1;
+    h->x0_fwd = false;
+    h->last_fwd_B = 0;      // (the activations a saving forward kept are overwritten)
+    h->n_fwd = (int)(g_launches - launches0);
+    if (h->capturing) h->cap.n_fwd = h->n_fwd;
+    return 0;
+}
+extern "C" int cf_forward_train_x0(cf_handle* h, const cf_batch* bt, const float* const* x0, float* logits, const void* labels, float loss_scale,
+                                   float* loss_out, void* stream) {
+    // a pending cf_x0_gather_fwd belongs to THIS call, which consumes it or fails: either way it is gone on return and cannot surface in a
+    // later, unrelated call
+    struct DropPending {
+        cf_handle* h;
+        ~DropPending() { if (h) h->pend_x0 = false; }
+    } drop{h};
+    if (check_batch_x0(h, bt, "cf_forward_train_x0")) return -1;
+    if (!h->grads) return fail("cf_forward_train_x0: no gradient buffer bound");
+    const cf_config& c = h->cfg;
+    hipStream_t st = (hipStream_t)stream;
+    const long long launches0 = g_launches;
+    const RetileUnit* units = (const RetileUnit*)h->retile_units + h->n_retile_early;      // the Regulation + head weights (the trunk's are not read)
+    const int n_units = h->n_retile - h->n_retile_early;
+    float* tT = h->reg8 ? h->tiledT : (float*)nullptr;
+    if (x0) {
+        float* dst[kMaxRes] = {};
+        for (int r = 0; r < c.n_res; ++r) {
+            if (!x0[r]) return fail("cf_forward_train_x0: x0[%d] is null", r);
+            if ((uintptr_t)x0[r] & 15) return fail("cf_forward_train_x0: x0[%d] is not 16-byte aligned", r);
+            dst[r] = h->Rx[r][0];
+        }
+        if (h->pend_x0) return fail("cf_forward_train_x0: a cf_x0_gather_fwd is pending; pass x0 = NULL to take its batch");
+        if (x0_copy(h, bt->B, x0, dst, st)) return -1;
+    }
+    if (h->pend_x0 && h->pend_x0_ga.B != bt->B) return fail("cf_forward_train_x0: the pending cf_x0_gather_fwd holds %d genes, the batch %d", h->pend_x0_ga.B, bt->B);
+    if (h->pend_x0) {      // the step's cache gather behind the re-tiling blocks: one launch
+        hipLaunchKernelGGL(k_x0_prologue, dim3(n_units + bt->B * h->pend_x0_ga.n_seg), dim3(kX0Threads), 0, st, (const float*)h->params, h->tiled, tT, units, n_units,
+                           h->pend_x0_ga);
+        LAUNCH_CHECK("k_x0_prologue");
+    } else if (n_units > 0) {
+        hipLaunchKernelGGL(k_retile, dim3(n_units), dim3(256), 0, st, (const float*)h->params, h->tiled, tT, units);
+        LAUNCH_CHECK("k_retile");
+    }
+    HeadRide hd;
+    const bool ride = labels && cf_head_rides(h);
+    if (ride) {
+        if (ride_tick(h, st)) return -1;
+        head_ride_args(h, logits, labels, loss_scale, loss_out, hd);
+        h->ride = hd;
+    }
+    if (forward_reg_head(h, bt, logits, 2, st, ride ? &hd : nullptr)) return -1;
+    h->x0_fwd = true;
+    h->last_fwd_B = bt->B;
+    h->n_fwd = (int)(g_launches - launches0);
+    if (h->capturing) h->cap.n_fwd = h->n_fwd, h->cap.x0_fwd = true;
+    return 0;
+}
+static int x0_gather_args(cf_handle* h, const cf_x0_store* cs, const int* order, int* cursor, const cf_batch* dst, void* labels_dst, X0GatherArgs& ga) {
+    if (!h || !cs || !order || !cursor || !dst) return fail("cf_x0_gather: null argument");
+    const cf_config& c = h->cfg;
+    const long long T = c.i_max + 1;
+    if (dst->B < 1 || dst->B > c.max_batch) return fail("cf_x0_gather: B = %d outside [1, max_batch = %d]", dst->B, c.max_batch);
+    memset(&ga, 0, sizeof ga);
+    int n = 0;
+    for (int r = 0; r < c.n_res; ++r) {
+        if (!cs->x0[r] || !cs->interaction_mask[r] || !dst->interaction_mask[r]) return fail("cf_x0_gather: null array at resolution %d", r);
+        ga.seg[n++] = X0Seg{(const char*)cs->x0[r], (char*)h->Rx[r][0], T * c.d_emb * 4};
+        ga.seg[n++] = X0Seg{(const char*)cs->interaction_mask[r], (char*)const_cast<uint8_t*>(dst->interaction_mask[r]), T * T};
+    }
+    if (!cs->interaction_freq || !dst->interaction_freq) return fail("cf_x0_gather: interaction_freq is null");
+    ga.seg[n++] = X0Seg{(const char*)cs->interaction_freq, (char*)const_cast<float*>(dst->interaction_freq), T * T * 4};
+    if (labels_dst) {
+        if (!cs->labels) return fail("cf_x0_gather: the cache holds no labels");
+        ga.seg[n++] = X0Seg{(const char*)cs->labels, (char*)labels_dst, c.n_out == 1 ? 4 : 8};
+    }
+    ga.n_seg = n;
+    ga.order = order;
+    ga.cursor = cursor;
+    ga.n_genes = cs->n_genes;
+    ga.B = dst->B;
+    return 0;
+}
+extern "C" int cf_x0_gather(cf_handle* h, const cf_x0_store* cs, const int* order, int* cursor, const cf_batch* dst, void* labels_dst, void* stream) {
+    X0GatherArgs ga;
+    if (x0_gather_args(h, cs, order, cursor, dst, labels_dst, ga)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_x0_gather, dim3(ga.B, ga.n_seg), dim3(kX0Threads), 0, st, ga);
+    LAUNCH_CHECK("k_x0_gather");
+    hipLaunchKernelGGL(k_gather_advance, dim3(1), dim3(1), 0, st, cursor);
+    LAUNCH_CHECK("k_gather_advance");
+    return 0;
+}
+extern "C" int cf_x0_gather_fwd(cf_handle* h, const cf_x0_store* cs, const int* order, int* cursor, const cf_batch* dst, void* labels_dst, void* stream) {
+    (void)stream;
+    if (x0_gather_args(h, cs, order, cursor, dst, labels_dst, h->pend_x0_ga)) return -1;
+    h->pend_x0 = true;
+    return 0;
+}
+extern "C" int cf_reduce_opt_x0(cf_handle* h, int B, float lr, float beta1, float beta2, float eps, float weight_decay, long long step, int keep_grads,
+                                int* cursor, void* stream) {
+    if (!h || !h->grads || !h->params || !h->m || !h->v) return fail("cf_reduce_opt_x0: params / grads / moments not bound");
+    if (B < 1 || B > h->cfg.max_batch) return fail("cf_reduce_opt_x0: bad batch size %d", B);
+    if (h->pend_gnext) return fail("cf_reduce_opt_x0: a cf_gather_batch_next is pending; this launch carries no batch gather (a frozen-trunk step gathers with "
+                                   "cf_gather_batch_fwd or cf_x0_gather_fwd in front of its forward)");
+    if (h->rider.done || h->rider.armed) return fail("cf_reduce_opt_x0: riders are armed (cf_rider_arm); a frozen-trunk step has no trunk backward launch for them");
+    AdamHyper hy;
+    if (adam_hyper(h, lr, beta1, beta2, eps, weight_decay, step, hy)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    // the Regulation + head bucket's tiles lead the tables; nothing of the Embedding + Pairwise range -- parameters, moments, gradients, tiled
+    // copies -- is read or written
+    const int wn = h->n_wg_r, cn = h->n_cs_r;
+    AdamFuse o{h->params, h->m, h->v, h->grads, hy.decay, hy.one_m_b1, hy.b2, hy.one_m_b2, hy.step_size, hy.bc2_sqrt, hy.eps, keep_grads ? 1 : 0, nullptr};
+    RecordArgs rec;
+    memset(&rec, 0, sizeof rec);
+    if (h->pend_record) {      // cf_record_step_bwd: the step log, written here (no trunk backward launch to carry it)
+        rec = h->pend_rec;
+        h->pend_record = false;
+    }
+    hipLaunchKernelGGL(k_reduce_opt_x0, dim3(xcd_grid(wn) + cn + 1), dim3(256), 0, st, (const WgTile*)h->wg_tiles, wn, (const CsTile*)h->cs_tiles, cn, B,
+                       h->xcd_reduce_opt, o, cursor, rec);
+    LAUNCH_CHECK("k_reduce_opt_x0");
+    h->n_bwd += 1;
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------

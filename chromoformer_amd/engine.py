@@ -110,9 +110,14 @@ class EpochFeed:
     appended to per-epoch logs (cf_record_step).  A training step is then four host calls -- graph replay, cf_rider_arm, the trunk's backward launch, reduction + AdamW --
     instead of the reference's DataLoader round trip plus per-tensor .cuda() copies (train.py:137-140, 171-177)."""
 
-    def __init__(self, model, store, bsz, max_batches=None):
+    def __init__(self, model, store, bsz, max_batches=None, cache=None):
         dev = model._device
         self.model, self.store, self.B = model, store, bsz
+        # cache: a TrunkCache of `store` -- a Trainer(freeze_trunk=True) then gathers the cached trunk outputs, interaction masks /
+        # frequencies and labels (cf_x0_gather_fwd) instead of the genes' features, and its steps do not run the trunk
+        if cache is not None and len(cache) != len(store):
+            raise ValueError("EpochFeed: the TrunkCache holds %d genes, the store %d" % (len(cache), len(store)))
+        self.cache = cache
         self.slot = Slot(model, bsz)
         self.slot.feed = self
         self.cap = max_batches or (len(store) // bsz + 1)
@@ -178,6 +183,72 @@ class EpochFeed:
                 self.loss_log[lo:hi].clone())
 
 
+class TrunkCache:
+    """The trunk's outputs for every gene of a device-resident GeneStore (cf_trunk_outputs over it in batches of max_batch): per
+    resolution [n, i_max + 1, d_emb], 13.8 KB per gene at the default shape against 126 KB of inputs.  With the Embedding + Pairwise
+    weights frozen they are constant over a run: a Trainer(freeze_trunk=True) fed by EpochFeed(..., cache=this) starts every step at the
+    Regulation stack.  The cache remembers the trunk parameters' version counters; a step after they were written through torch
+    refuses (rebuild the cache; an edit through `.data` or a raw pointer is not noticed: call model.params_changed() and rebuild)."""
+
+    def __init__(self, model, store, bsz=None):
+        if getattr(store, "device", None) is None:
+            raise ValueError("TrunkCache needs a device-resident GeneStore")
+        self.model, self.store = model, store
+        self.bsz = int(bsz or model._max_batch)
+        dev, T = model._device, model.i_max + 1
+        self.x0 = [torch.empty(len(store), T, model.d_emb, device=dev) for _ in model.binsizes]
+        self.rebuild()
+
+    def __len__(self):
+        return len(self.store)
+
+    def rebuild(self):
+        """(Re)compute every gene's trunk outputs with the model's current weights, on the current stream; waits for the result."""
+        m, L, store, n = self.model, _lib.lib(), self.store, len(self.store)
+        dev = m._device
+        torch.cuda.synchronize(dev)      # (the library's workspace is shared with whatever a Trainer's stream still has queued)
+        struct = store.struct()
+        st = torch.cuda.current_stream(dev).cuda_stream
+        order = torch.arange(n, dtype=torch.int32, device=dev)
+        n_full = n // self.bsz
+        cursors = []
+        for B, lo, nb in ((self.bsz, 0, n_full), (n - n_full * self.bsz, n_full * self.bsz, 1)):
+            if B == 0 or nb == 0:
+                continue
+            slot = Slot(m, B)
+            cursor = torch.tensor([0, nb, 0, 0], dtype=torch.int32).to(dev)
+            cursors.append(cursor)
+            for k in range(nb):
+                _lib.check(L.cf_gather_batch(m._handle, C.byref(struct), order[lo:].data_ptr(), cursor.data_ptr(), C.byref(slot.struct), None, st),
+                           "cf_gather_batch")
+                m._trunk_outputs(slot.struct, [x[lo + k * B: lo + (k + 1) * B] for x in self.x0])
+        torch.cuda.current_stream(dev).synchronize()
+        flags = [int(c[2].item()) for c in cursors]
+        if any(flags):
+            raise RuntimeError("TrunkCache: the device-side gather reported errors (flags %s)" % flags)
+        self.version = m.trunk_version()
+        self._struct = None
+        return self
+
+    def struct(self):
+        """cf_x0_store view (include/chromoformer_hip.h), for cf_x0_gather."""
+        if self._struct is None:
+            cs = _lib.cf_x0_store()
+            cs.n_genes = len(self.store)
+            for r, x in enumerate(self.x0):
+                cs.x0[r] = x.data_ptr()
+                cs.interaction_mask[r] = self.store.im.data_ptr()      # (the same at every resolution, data.py:200-203)
+            cs.interaction_freq, cs.labels = self.store.freq.data_ptr(), self.store.label.data_ptr()
+            self._struct = cs
+        return self._struct
+
+    def check(self):
+        if self.model.trunk_version() != self.version:
+            raise RuntimeError("TrunkCache is stale: Embedding / Pairwise parameters of the model have been written through torch since the cache "
+                               "was built (load_state_dict, an optimiser, an in-place op); call cache.rebuild() -- and model.params_changed() "
+                               "before it after an edit through .data or a raw pointer")
+
+
 class Trainer:
     """One optimisation step = forward, loss, backward, gradient reductions, [all-reduce], AdamW.
 
@@ -189,6 +260,9 @@ class Trainer:
       Regulation + head bucket's reduction] -> cf_reduce_adamw_part -> cf_adamw_step_part (`_step_merged`);
     - separate launches (`merge_opt=False`, and bench.py's k_wgrad / k_colsum / k_adamw timing): [graph: the whole backward pass with
       its reductions] -> model.adamw_step (`_step_separate`); the reference of the parity tests.
+    - frozen trunk (`freeze_trunk=True`): [graph: batch or cache gather, (trunk forward,) Regulation + head forward, loss, head + Regulation
+      backward] -> one reduction + AdamW launch over the Regulation + head bucket (cf_reduce_opt_x0; `_step_frozen`).  Embedding + Pairwise
+      parameters, moments and tiled copies are never written.  Fed by EpochFeed(..., cache=TrunkCache) the step starts at the Regulation stack.
     Data parallel (`_step_dp`): the Regulation + head bucket (in halves where cf_reg_halves offers them) is all-reduced on the side stream
     under the rest of the backward pass, then AdamW over its range runs there as well; `overlap_allreduce=False` issues the all-reduces
     behind the whole backward pass and steps both ranges on the main stream.
@@ -198,7 +272,13 @@ class Trainer:
 
     def __init__(self, model, lr=3e-5, gamma=0.87, world_size=1, process_group=None, use_graph=True,
                  betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, timed_kernel=None, overlap_allreduce=None, merge_opt=True,
-                 fuse_opt=True, keep_grads=False, rider_tiles=None, keep_tiled=True, dp_side_reduce=None):
+                 fuse_opt=True, keep_grads=False, rider_tiles=None, keep_tiled=True, dp_side_reduce=None, freeze_trunk=False):
+        self.freeze_trunk = bool(freeze_trunk)
+        if self.freeze_trunk and (world_size > 1 or process_group is not None):
+            raise ValueError("Trainer: freeze_trunk=True is not supported with data parallelism (world_size > 1 / a process group): the "
+                             "frozen-trunk step has no all-reduce schedule")
+        if self.freeze_trunk and timed_kernel in ("k_wgrad", "k_colsum", "k_adamw", "k_trunk_bwd"):
+            raise ValueError("Trainer: freeze_trunk=True does not launch %s on its own" % timed_kernel)
         self.model, self.lr, self.gamma = model, float(lr), gamma
         self.world, self.pg, self.use_graph = world_size, process_group, use_graph
         self.dp = world_size > 1 or process_group is not None
@@ -251,7 +331,7 @@ class Trainer:
         # in ONE launch behind the whole backward pass (the Embedding + Pairwise bucket's ~300 latency-bound tiles fill the gaps of the
         # Regulation bucket's 1,008).  The flat gradient buffer is only written with keep_grads=True.  Bit-identical parameters and
         # moments (tests/test_engine_gpu.py).
-        self.fuse_opt = bool(fuse_opt) and self.merge_opt and model._kws[0].get("n_layers", 1) == 1
+        self.fuse_opt = bool(fuse_opt) and self.merge_opt and model._kws[0].get("n_layers", 1) == 1 and not self.freeze_trunk
         self.fuse_one = True          # (one fused reduction launch per step; bench.py reads it)
         self.keep_grads = bool(keep_grads)
         # ... and part of the Regulation bucket's tiles as RIDERS of the trunk's backward launch (cf_rider_arm): the trunk's 192 workgroups
@@ -267,7 +347,9 @@ class Trainer:
         # ... and the fused optimiser keeps the tiled copies of the Embedding + Pairwise weights fresh (its epilogue writes every stepped
         # element in both layouts): no re-tiling launch in front of a step.  Data parallel: the separate AdamW launch over the Embedding +
         # Pairwise bucket writes them as well (k_adamw_tiled).  keep_tiled=False: every forward pass re-tiles (model.keep_tiled has the contract).
-        self.keep_tiled = model.keep_tiled(bool(keep_tiled) and (self.fuse_opt or self.dp))
+        # (frozen trunk: nobody writes the Embedding + Pairwise weights, their tiled copies stay fresh after the first pass; riders live on
+        # the trunk's backward launch, which does not run: rider_tiles is 0 above)
+        self.keep_tiled = model.keep_tiled(bool(keep_tiled) and (self.fuse_opt or self.dp or self.freeze_trunk))
         self._t_ms, self._t_n = 0.0, 0
         _lib.check(self._L.cf_timing_select(model._handle, timed_kernel.encode() if timed_kernel else None), "cf_timing_select")
 
@@ -370,6 +452,21 @@ class Trainer:
             gargs = None
             if feed is not None and self.fuse_opt:
                 gargs = (m._handle, C.byref(feed.struct), feed.order.data_ptr(), feed.cursor.data_ptr(), C.byref(slot.struct), slot.label.data_ptr(), st)
+            if self.freeze_trunk:
+                if feed is not None and feed.cache is not None:
+                    feed.cache.check()
+                if self.use_graph and slot.graph is None:
+                    self._seq_frozen(slot, st)             # one eager pass validates the arguments (no parameter is updated)
+                    if feed is not None:
+                        feed.rewind()
+                    torch.cuda.synchronize()
+                    slot.graph = {"first": self._capture(self._seq_frozen, slot, st)}
+                if feed is not None:
+                    feed.taken += 1
+                self._step_frozen(slot, st)
+                self._last = slot
+                m._mark_grads(not self.keep_grads, top=self._buckets[_lib.BUCKET_REG])
+                return slot.logits, slot.loss
             if self.use_graph and slot.graph is None:
                 self._capture_graphs(slot, st, gargs)
             if feed is not None:
@@ -429,6 +526,41 @@ class Trainer:
         elif not self.use_graph:
             self._part(slot, st, 4)
         _lib.check(L.cf_reduce_opt_part(m._handle, slot.B, _lib.BUCKET_REG | _lib.BUCKET_PE, *hp, kg, st), "cf_reduce_opt_part")
+
+    def _seq_frozen(self, slot, st):      # [cache or batch gather,] [trunk forward,] Regulation + head forward, loss, head + Regulation backward
+        m, L = self.model, self._L
+        feed = getattr(slot, "feed", None)
+        fargs = (slot.logits.data_ptr(), slot.label.data_ptr(), 1.0, slot.loss.data_ptr(), st)
+        if feed is not None and feed.cache is not None:
+            # (shares a launch with the re-tiling in front of the Regulation forward; the cursor moves on in the step's last launch)
+            _lib.check(L.cf_x0_gather_fwd(m._handle, C.byref(feed.cache.struct()), feed.order.data_ptr(), feed.cursor.data_ptr(),
+                                          C.byref(slot.struct), slot.label.data_ptr(), st), "cf_x0_gather_fwd")
+            _lib.check(L.cf_forward_train_x0(m._handle, C.byref(slot.struct), None, *fargs), "cf_forward_train_x0")
+        else:
+            if feed is not None:
+                _lib.check(L.cf_gather_batch_fwd(m._handle, C.byref(feed.struct), feed.order.data_ptr(), feed.cursor.data_ptr(),
+                                                 C.byref(slot.struct), slot.label.data_ptr(), st), "cf_gather_batch_fwd")
+            _lib.check(L.cf_forward_train(m._handle, C.byref(slot.struct), *fargs), "cf_forward_train")
+        self._part(slot, st, 3)
+
+    def _step_frozen(self, slot, st):
+        """[graph: gather, forward from the trunk or from its cached outputs, head + Regulation backward] -> one reduction + AdamW launch
+        over the Regulation + head bucket, which also moves a cached feed's cursor on and writes the step log."""
+        m, L, feed = self.model, self._L, getattr(slot, "feed", None)
+        if self.use_graph:
+            self._launch(slot.graph["first"], st)
+        else:
+            self._seq_frozen(slot, st)
+        cursor = None
+        if feed is not None:
+            _lib.check(L.cf_record_step_bwd(m._handle, feed.cursor.data_ptr(), slot.logits.data_ptr(), slot.label.data_ptr(),
+                                            slot.loss.data_ptr(), slot.B, feed.logits_log.data_ptr(), feed.labels_log.data_ptr(),
+                                            feed.loss_log.data_ptr(), st), "cf_record_step_bwd")
+            if feed.cache is not None:
+                cursor = feed.cursor.data_ptr()
+        hp = self._hp()
+        m._step += 1
+        _lib.check(L.cf_reduce_opt_x0(m._handle, slot.B, *hp, 1 if self.keep_grads else 0, cursor, st), "cf_reduce_opt_x0")
 
     def _step_merged(self, slot, st):
         """[graph: the backward pass up to the Pairwise + Embedding bucket] -> its reduction beside the Regulation + head AdamW -> its AdamW."""

@@ -65,6 +65,26 @@ def _init_kind(name, shape):
     return "bias", None  # fan_in resolved from the sibling weight
 
 
+TRUNK_PREFIXES = ("embed.", "pairwise_interaction.")
+FREEZE_GRANULARITY = ("freezing is supported for the whole trunk only -- every embed.* and pairwise_interaction.* tensor of every resolution "
+                      "(CF_BUCKET_PE) frozen, every regulation.* and fc_head.* tensor (CF_BUCKET_REG) trainable -- not for single resolutions, "
+                      "modules or layers")
+
+
+def is_trunk_name(name):
+    """Does a state_dict key (current naming) belong to the trunk, the Embedding + Pairwise modules?"""
+    return name.startswith(TRUNK_PREFIXES)
+
+
+def split_layout(table):
+    """The frozen / stepped partition of a parameter table under a frozen trunk -> (trunk, top, never): names of the trainable trunk
+    tensors (CF_BUCKET_PE), of the trainable Regulation + head tensors (CF_BUCKET_REG), and of the tensors no step ever writes."""
+    trunk = [e["name"] for e in table if e["trainable"] and is_trunk_name(e["name"])]
+    top = [e["name"] for e in table if e["trainable"] and not is_trunk_name(e["name"])]
+    never = [e["name"] for e in table if not e["trainable"]]
+    return trunk, top, never
+
+
 class _BackwardHook(torch.autograd.Function):
     """Lets ``loss.backward()`` of the caller drive cf_backward_from(), or cf_backward_from_inputs() when one of the float inputs
     (the device float32 copies _pack made of them: promoter_feats[b] per resolution, pcre_feats[b] per resolution, interaction_freq)
@@ -87,7 +107,11 @@ class _BackwardHook(torch.autograd.Function):
         st = torch.cuda.current_stream(m._device).cuda_stream
         needs = ctx.needs_input_grad[4:]
         grads = [None] * len(needs)
-        if not any(needs):
+        frozen = m._trunk_frozen()      # (raises for a freeze the library has no step for)
+        if frozen and not any(needs):
+            # every Embedding / Pairwise parameter has requires_grad == False: head + Regulation backward and their bucket's reductions only
+            _lib.check(_lib.lib().cf_backward_from_top(m._handle, C.byref(ctx.batch_struct), dl.data_ptr(), st), "cf_backward_from_top")
+        elif not any(needs):
             _lib.check(_lib.lib().cf_backward_from(m._handle, C.byref(ctx.batch_struct), dl.data_ptr(), st), "cf_backward_from")
         else:
             nres = (len(needs) - 1) // 2
@@ -105,7 +129,8 @@ class _BackwardHook(torch.autograd.Function):
                     want.interaction_freq = g.data_ptr()
             _lib.check(_lib.lib().cf_backward_from_inputs(m._handle, C.byref(ctx.batch_struct), dl.data_ptr(), C.byref(want), st),
                        "cf_backward_from_inputs")
-        m._publish_grads()
+        m._publish_grads(top_only=frozen)
+        m._grads_top = m._top_range() if frozen else None      # what active_grads() may hand out after this backward
         return (torch.zeros_like(m._anchor), None, None, None, *grads)
 
 
@@ -126,7 +151,7 @@ class ChromoformerBase(nn.Module):
         self.n_bins = [w_max // b for b in self.binsizes]
         self._kws = (embed, pair, reg)
         self._max_batch = max_batch
-        self._maps_gen = 0          # bumped by attention_maps() / pcre_ablation() / integrated_gradients(): a pending backward of an earlier forward refuses to run
+        self._maps_gen = 0          # bumped by attention_maps() / pcre_ablation() / integrated_gradients() / trunk_outputs(): a pending backward of an earlier forward refuses to run
         self._maps_by = None        # ... naming the last of them
         self._handle = None
         self._device = None
@@ -216,11 +241,44 @@ class ChromoformerBase(nn.Module):
         except Exception:
             pass
 
-    def _publish_grads(self):
+    def _publish_grads(self, top_only=False):
         named = self._named()
         for e in self._table:
-            if e["trainable"]:
+            if e["trainable"] and not (top_only and is_trunk_name(e["name"])):
                 named[e["name"]].grad = self._gflat[e["offset"]:e["offset"] + e["numel"]].view(e["shape"])
+
+    def _trunk_frozen(self):
+        """Have the trunk's parameters been frozen with requires_grad_(False)?  -> False (none frozen: the full backward) or True (EVERY
+        Embedding and Pairwise tensor frozen, every Regulation / fc_head tensor trainable).  Anything else raises: the library steps the
+        two ranges of the parameter layout whole.  (Runs in front of every loss.backward(): one pass over a cached list of the trainable
+        parameters; the names are only looked at once something is frozen.)"""
+        if getattr(self, "_freeze_list", None) is None:
+            named = self._named()
+            self._freeze_list = [(e["name"], named[e["name"]], is_trunk_name(e["name"])) for e in self._table if e["trainable"]]
+        if all(p.requires_grad for _, p, _ in self._freeze_list):
+            return False
+        off = [n for n, p, _ in self._freeze_list if not p.requires_grad]
+        top = [n for n, p, trunk in self._freeze_list if not trunk and not p.requires_grad]
+        if top:
+            raise RuntimeError("loss.backward(): parameter '%s' has requires_grad == False; %s" % (top[0], FREEZE_GRANULARITY))
+        on = [n for n, p, trunk in self._freeze_list if trunk and p.requires_grad]
+        if on:
+            raise RuntimeError("loss.backward(): parameter '%s' has requires_grad == True while '%s' is frozen; %s" % (on[0], off[0], FREEZE_GRANULARITY))
+        return True
+
+    def _top_range(self):
+        """The Regulation + head range (CF_BUCKET_REG) of the flat gradient buffer, from the parameter table."""
+        lo = min(e["offset"] for e in self._table if e["trainable"] and not is_trunk_name(e["name"]))
+        return self._gflat[lo: self._layout.n_active]
+
+    def freeze_trunk(self, frozen=True):
+        """requires_grad_(not frozen) on every Embedding and Pairwise parameter (the trunk); returns self."""
+        for n, p in self._named().items():
+            if is_trunk_name(n):
+                p.requires_grad_(not frozen)
+                if frozen:
+                    p.grad = None
+        return self
 
     def load_state_dict(self, state_dict, strict=True):
         out = super().load_state_dict(state_dict, strict=strict)   # copy_ into the flat-buffer views
@@ -523,6 +581,39 @@ class ChromoformerBase(nn.Module):
             attr = {k: ({b: t.view(shapes[k][b]) for b, t in v.items()} if isinstance(v, dict) else v.view(shapes[k])) for k, v in attr.items()}
         return attr, {"logits": lx, "baseline_logits": lb, "delta": delta}
 
+    @torch.no_grad()
+    def trunk_outputs(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                      interaction_freq=None):
+        """The trunk's output, the input of the Regulation stacks (cf_trunk_outputs) -> {binsize: [B, i_max + 1, d_emb]} on the model's
+        device, no autograd graph: row 0 the promoter's centre-bin embedding, row 1 + j that of the promoter attending pCRE slot j.  For
+        fixed Embedding + Pairwise weights it depends on the gene alone -- what engine.TrunkCache keeps for Trainer(freeze_trunk=True).
+        The first argument may also be a packed batch (an engine.Slot or a pack_batch result), with nothing after it.  The pass
+        overwrites the activations a grad-enabled model(...) keeps for its backward: such a pending backward() raises."""
+        if promoter_pad_masks is None:
+            bs = promoter_feats.struct if hasattr(promoter_feats, "struct") else promoter_feats[0]
+        else:
+            bs, _keep = self._pack(promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq)      # (alive until the call)
+        if self._handle is None:
+            raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
+        return dict(zip(self.binsizes, self._trunk_outputs(bs)))
+
+    def _trunk_outputs(self, bs, outs=None):
+        dev = self._device
+        if outs is None:
+            outs = [torch.empty(bs.B, self.i_max + 1, self.d_emb, device=dev) for _ in self.binsizes]      # (written in full by the library)
+        ptrs = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+        st = torch.cuda.current_stream(dev).cuda_stream
+        self._sync_tiled(st)
+        self._maps_gen += 1
+        self._maps_by = "trunk_outputs"
+        _lib.check(_lib.lib().cf_trunk_outputs(self._handle, C.byref(bs), ptrs, st), "cf_trunk_outputs")
+        return outs
+
+    def trunk_version(self):
+        """Sum of the torch version counters of the trunk's parameters (what _sync_tiled sums over all of them): changes whenever one
+        of them is written through torch."""
+        return sum(p._version for n, p in self.named_parameters() if is_trunk_name(n))
+
     def embed_full(self, promoter_feats, promoter_pad_masks):
         """EmbeddingTransformer's first return value (net.py:57-59): {binsize: [B, 1, L, 128]}, the embedding of every
         promoter bin (all rows of every Embedding layer through the dense transformer layer; forward only)."""
@@ -565,7 +656,7 @@ class ChromoformerBase(nn.Module):
                                                self._loss_buf.data_ptr(), st), "cf_forward_train")
         _lib.check(_lib.lib().cf_backward(self._handle, C.byref(bs), labels.data_ptr(), float(loss_scale),
                                           self._loss_buf.data_ptr(), st), "cf_backward")
-        self._grads_stale = False
+        self._grads_stale, self._grads_top = False, None      # (a full backward: every trainable gradient has just been written)
         return logits, self._loss_buf
 
     def adamw_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01):
@@ -581,14 +672,23 @@ class ChromoformerBase(nn.Module):
         if getattr(self, "_grads_stale", False):
             raise RuntimeError("the gradient buffer was not written by the last step (Trainer(fuse_opt=True, keep_grads=False) "
                                "updates parameters inside the gradient reductions); construct the Trainer with keep_grads=True")
+        top = getattr(self, "_grads_top", None)
+        if top is not None:      # the last step ran on a frozen trunk: the Regulation + head range is all it wrote
+            return top
         return self._gflat[: self._layout.n_active]
 
-    def _mark_grads(self, stale):
-        """Called by the Trainer after every step: `stale` = the step did not store its gradients."""
+    def _mark_grads(self, stale, top=None):
+        """Called by the Trainer after every step: `stale` = the step did not store its gradients; `top` = the step ran on a frozen
+        trunk and wrote (at most) this range of the flat gradient buffer, the Regulation + head bucket."""
         if stale and not getattr(self, "_grads_stale", False):
             for p in self._named().values():      # `.grad` views of the flat buffer (loss.backward() publishes them) would read old values
                 p.grad = None
+        elif top is not None and getattr(self, "_grads_top", None) is None:
+            for n, p in self._named().items():
+                if is_trunk_name(n):
+                    p.grad = None
         self._grads_stale = bool(stale)
+        self._grads_top = top
 
     def train_step(self, packed, labels, lr, process_group=None, world_size=1):
         """zero_grad -> forward -> loss -> backward -> [all-reduce] -> AdamW (train.py:182-196)."""

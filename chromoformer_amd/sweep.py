@@ -38,6 +38,10 @@ def command(eid, fold, ckpt, args):
         cmd += ["--binsizes"] + [str(b) for b in args.binsizes]
     if args.regression:
         cmd.append("--regression")
+    if getattr(args, "init_from", None):      # warm start, e.g. another cell line's checkpoint of the same fold
+        cmd += ["--init-from", args.init_from.format(eid=eid, fold=fold)]
+    if getattr(args, "freeze_trunk", False):
+        cmd.append("--freeze-trunk")
     return cmd
 
 
@@ -76,7 +80,7 @@ def run(jobs, args, launch=subprocess.Popen):
     return done
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--meta-template", required=True, help="metadata csv path with an {eid} placeholder")
     ap.add_argument("--npy-dir-template", required=True, help="signal directory with an {eid} placeholder")
@@ -91,7 +95,14 @@ def main(argv=None):
     ap.add_argument("--binsizes", nargs="+", default=None)
     ap.add_argument("--regression", action="store_true")
     ap.add_argument("--poll", type=float, default=1.0)
-    args = ap.parse_args(argv)
+    ap.add_argument("--init-from", default=None, metavar="CKPT",
+                    help="passed to every training: warm-start checkpoint path; {eid} and {fold} placeholders are filled per job")
+    ap.add_argument("--freeze-trunk", action="store_true", help="passed to every training: train Regulation + head on the frozen trunk")
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     done = run(plan(args.eids, args.folds, args.exp_id, args.conf, args.out_dir), args)
     bad = {k: v for k, v in done.items() if v != 0}
     print("[sweep] %d jobs, %d failed" % (len(done), len(bad)))

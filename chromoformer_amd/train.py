@@ -63,7 +63,42 @@ def epoch_permutation(n):
     return torch.randperm(n, generator=g).tolist()
 
 
-def optimizer_state_dict(model, lr, initial_lr=None, m_host=None, v_host=None):
+def load_init_weights(model, path):
+    """--init-from: a warm start, not a resume -- `ckpt["net"]` (or a bare state dict) goes into the model through
+    predict.modernise_keys (legacy `embed2000.` / `pw_int2000.` / `reg2000.` checkpoints work); a missing key, an unknown key and a
+    shape mismatch are fatal; the checkpoint's optimiser state, epoch and learning rate are not taken."""
+    from .predict import modernise_keys
+    ck = torch.load(path, map_location="cpu", weights_only=False)
+    sd = ck["net"] if isinstance(ck, dict) and "net" in ck and not torch.is_tensor(ck["net"]) else ck
+    if not isinstance(sd, dict) or not sd or not all(torch.is_tensor(v) for v in sd.values()):
+        raise ValueError("--init-from %s: neither a checkpoint with a `net` state dict nor a bare state dict" % path)
+    sd = modernise_keys(sd)
+    own = dict(model.named_parameters())
+    missing = [k for k in own if k not in sd]
+    if missing:
+        raise KeyError("--init-from %s: the checkpoint has no `%s` (%d of the model's %d tensors are missing)" % (path, missing[0], len(missing), len(own)))
+    extra = [k for k in sd if k not in own]
+    if extra:
+        raise KeyError("--init-from %s: the checkpoint's `%s` is not a tensor of this model (%d unknown keys)" % (path, extra[0], len(extra)))
+    for k, p in own.items():
+        if tuple(sd[k].shape) != tuple(p.shape):
+            raise ValueError("--init-from %s: shape mismatch at `%s`: checkpoint %s, model %s (configuration differs from the checkpoint's)"
+                             % (path, k, tuple(sd[k].shape), tuple(p.shape)))
+    with torch.no_grad():
+        for k, p in own.items():
+            p.copy_(sd[k])      # (through torch: the version counters tell the library that its tiled weight copies are stale)
+    return model
+
+
+def stepped_indices(table, freeze_trunk=False):
+    """Indices (positions in the parameter table = torch.optim.AdamW's parameter ids) of the tensors a run steps, i.e. those with an
+    entry in the optimiser state: every trainable tensor; with a frozen trunk the Regulation + head ones only (an AdamW that never
+    saw the Embedding / Pairwise gradients has no state for those parameters)."""
+    from .net import is_trunk_name
+    return [i for i, e in enumerate(table) if e["trainable"] and not (freeze_trunk and is_trunk_name(e["name"]))]
+
+
+def optimizer_state_dict(model, lr, initial_lr=None, m_host=None, v_host=None, freeze_trunk=False):
     """torch.optim.AdamW.state_dict() layout: entries only for parameters that ever had a gradient,
     `step` as a 0-dim float32 tensor (train.py:325, 336).  m_host / v_host: host copies of the flat moment buffers (one
     device-to-host copy each instead of one per tensor); default: copied here."""
@@ -78,9 +113,8 @@ def optimizer_state_dict(model, lr, initial_lr=None, m_host=None, v_host=None):
     if model._step > 0:
         if m_host is None:
             m_host, v_host = model._mflat.detach().cpu(), model._vflat.detach().cpu()
-        for i, e in enumerate(model._table):
-            if not e["trainable"]:
-                continue
+        for i in stepped_indices(model._table, freeze_trunk):
+            e = model._table[i]
             sl = slice(e["offset"], e["offset"] + e["numel"])
             state[i] = {"step": torch.tensor(float(model._step)),
                         "exp_avg": m_host[sl].view(e["shape"]).clone(),
@@ -100,7 +134,7 @@ class CheckpointWriter:
     keys and order are the reference's.)  One save is in flight at a time -- submit() waits for the previous one before it
     overwrites the buffers --, wait() re-raises a failed save, and the run writes its `.done` marker only behind the last wait()."""
 
-    def __init__(self, model):
+    def __init__(self, model, freeze_trunk=False):
         import threading
         self._threading = threading
         self.model = model
@@ -121,11 +155,11 @@ class CheckpointWriter:
         self._opt = torch.optim.AdamW([nn.Parameter(torch.zeros(1)) for _ in named], lr=1.0).state_dict()
         self._steps = []
         self._state = {}
-        for i, e in enumerate(model._table):
-            if e["trainable"]:
-                st = torch.zeros((), dtype=torch.float32)
-                self._steps.append(st)
-                self._state[i] = {"step": st, "exp_avg": view(m_h, e), "exp_avg_sq": view(v_h, e)}
+        for i in stepped_indices(model._table, freeze_trunk):
+            e = model._table[i]
+            st = torch.zeros((), dtype=torch.float32)
+            self._steps.append(st)
+            self._state[i] = {"step": st, "exp_avg": view(m_h, e), "exp_avg_sq": view(v_h, e)}
 
     def go(self):
         """The step loop has queued its epoch (train_epoch's `after_issue`): the pending save may start.  Until then the worker
@@ -204,7 +238,7 @@ def validation_metrics(val_out, val_lab, regression):
     return loss, score, {"acc": acc, "auc": auc, "ap": ap}
 
 
-def main(argv=None):
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("-o", "--output", required=True)
     parser.add_argument("-c", "--config", required=True)
@@ -224,7 +258,17 @@ def main(argv=None):
                         help="data-parallel runs: `static` = every rank owns (and loads) 1/world of the training genes and draws its "
                              "batches from them; `global` = every rank holds the whole split and takes its slice of each global batch "
                              "of the epoch permutation (reproduces the single-process batch composition exactly)")
-    args = parser.parse_args(argv)
+    parser.add_argument("--init-from", default=None, metavar="CKPT",
+                        help="warm start: load the weights of a checkpoint (`net`, or a bare state dict; legacy key names accepted) before "
+                             "epoch 1; its optimiser state is not taken")
+    parser.add_argument("--freeze-trunk", action="store_true", default=False,
+                        help="train the Regulation stacks and fc_head only: the Embedding + Pairwise modules keep their (--init-from) values, "
+                             "their outputs are computed once per gene and cached; single GPU")
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
 
     if args.use_wandb is False:
         os.environ["WANDB_MODE"] = "disabled"
@@ -314,17 +358,29 @@ def main(argv=None):
     model = Model(n_feats, d_emb, config["d_head"], config["embed"], config["pairwise_interaction"], config["regulation"],
                   binsizes=args.binsizes, seed=42, i_max=i_max, w_max=w_max, max_batch=bsz)
     model.cuda(local)
+    if args.init_from:
+        load_init_weights(model, args.init_from)
+        say("initial weights:", args.init_from)
+    if args.freeze_trunk and (world > 1 or pg is not None):
+        raise ValueError("--freeze-trunk is not supported with data parallelism (WORLD_SIZE > 1)")
     criterion = nn.MSELoss() if args.regression else nn.CrossEntropyLoss()
     # (single GPU: the step is a replayed graph + two eager launches; data parallel: three graphs with collectives between them replay 4 % SLOWER than the
     #  same launches issued eagerly -- 0.578 against 0.557 ms on a one-rank RCCL group, profiles/r05j_bench_dp.json --, so the ranks issue eagerly)
-    trainer = Trainer(model, lr=float(config["lr"]), gamma=gamma, world_size=world, process_group=pg, use_graph=(world == 1 and pg is None))
-    feed = EpochFeed(model, train_store, bsz)          # batches are gathered from the resident split inside the step graph
+    trainer = Trainer(model, lr=float(config["lr"]), gamma=gamma, world_size=world, process_group=pg, use_graph=(world == 1 and pg is None),
+                      freeze_trunk=args.freeze_trunk)
+    cache = None
+    if args.freeze_trunk:      # the trunk's outputs of every training gene, once (they do not change while the trunk is frozen)
+        from .engine import TrunkCache
+        mark("model, trainer")
+        cache = TrunkCache(model, train_store, bsz)
+        mark("trunk cache build (%d genes, %.1f MB)" % (len(cache), sum(x.numel() for x in cache.x0) * 4 / 1e6))
+    feed = EpochFeed(model, train_store, bsz, cache=cache)          # batches are gathered from the resident split inside the step graph
     if world > 1:                                      # one line per rank: what it loaded (stderr; stdout stays rank 0's, as in the reference)
         n_steps = (len(train_genes) // world // bsz) if static else (len(train_genes) // (world * bsz))
         print("[rank %d/%d] dp-shard %s: train store %d of %d genes, validation slice %d of %d genes, %d steps per epoch"
               % (rank, world, args.dp_shard, len(train_store), len(train_genes), len(val_store), n_val, n_steps), file=sys.stderr, flush=True)
 
-    writer = CheckpointWriter(model) if rank == 0 else None
+    writer = CheckpointWriter(model, freeze_trunk=args.freeze_trunk) if rank == 0 else None
     mark("model, trainer, feed")
     val_score = val_label = val_loss = None
     for epoch in range(1, num_epoch):

@@ -494,6 +494,53 @@ int cf_keep_tiled(cf_handle* h, int on);
 int cf_params_changed(cf_handle* h);
 int cf_retile_early(cf_handle* h, void* stream);
 
+/* ---- training on a frozen trunk ------------------------------------------------------------ */
+/* The trunk = every Embedding and Pairwise tensor (CF_BUCKET_PE); the top = the Regulation stacks and fc_head (CF_BUCKET_REG).  For fixed
+ * trunk weights the Regulation input of a gene -- per resolution [T, d_emb], T = i_max + 1 -- depends on the gene alone: it can be
+ * computed once (cf_trunk_outputs), kept, and a training step can start from it (cf_forward_train_x0).  No reference counterpart
+ * (train.py trains every parameter).
+ *
+ * cf_trunk_outputs: the trunk part of cf_forward(save = 0) -- every configuration cf_forward accepts -- then ONE launch that copies the
+ * Regulation input of the batch's genes to x0[r], [B, T, d_emb] (16-byte aligned; r < n_res).  Overwrites the activations a
+ * cf_forward(save >= 1) kept: no cf_backward* may follow without a new saving forward. */
+int cf_trunk_outputs(cf_handle* h, const cf_batch* batch, float* const* x0, void* stream);
+/* cf_forward_train from the Regulation input: reads B, interaction_mask[r] and interaction_freq of `batch` (its other fields may be
+ * null) and x0[r], [B, T, d_emb]; runs the Regulation + head forward with activations saved -- the head at the tail of the Regulation
+ * launch where cf_head_rides(h) -- and leaves the handle as cf_backward_part(parts = 1 | 2) expects (same batch; the bits of
+ * cf_forward_train on the batch whose trunk outputs x0 holds).  cf_backward_part(parts & 4) after it FAILS by name: the trunk kept no
+ * activations.  Launches: [k_x0_copy when x0 != NULL] -> the re-tiling of the Regulation + head weights (with the copy blocks of a pending
+ * cf_x0_gather_fwd behind them) -> the Regulation + head launches of cf_forward_train.  x0 == NULL: the Regulation input is what
+ * cf_x0_gather / cf_x0_gather_fwd put in place.  Capturable. */
+int cf_forward_train_x0(cf_handle* h, const cf_batch* batch, const float* const* x0, float* logits, const void* labels,
+                        float loss_scale, float* loss_out, void* stream);
+/* What a frozen-trunk step reads per gene, resident in HBM: the trunk outputs and the gene's interaction masks (one array may serve
+ * every resolution), frequencies and labels -- the corresponding arrays of cf_store can be passed as they are. */
+typedef struct cf_x0_store {
+    long long n_genes;
+    const float*   x0[CF_MAX_RES];                  /* [n,T,d_emb]  (16-byte aligned)     */
+    const uint8_t* interaction_mask[CF_MAX_RES];    /* [n,T,T]                            */
+    const float*   interaction_freq;                /* [n,T,T]                            */
+    const void*    labels;                          /* int64 [n] (n_out = 2) or float [n] */
+} cf_x0_store;
+/* cf_gather_batch for a frozen-trunk step (same order / cursor protocol, same error flags in cursor[2]): copies genes
+ * order[cursor[0] * B ... + B) of the cache into the library's Regulation input buffers, dst's interaction masks and frequencies and
+ * labels_dst (may be null), then advances the cursor (a second, one-thread launch).  Bytes only, no atomics; capturable. */
+int cf_x0_gather(cf_handle* h, const cf_x0_store* cache, const int* order, int* cursor, const cf_batch* dst, void* labels_dst,
+                 void* stream);
+/* The same without a launch of its own: the cf_forward_train_x0(x0 = NULL) that must follow on the same stream copies the genes in the
+ * launch that re-tiles the Regulation + head weights.  The cursor -- which that launch reads -- is advanced by the
+ * cf_reduce_opt_x0(cursor) that ends the step. */
+int cf_x0_gather_fwd(cf_handle* h, const cf_x0_store* cache, const int* order, int* cursor, const cf_batch* dst, void* labels_dst,
+                     void* stream);
+/* The last launch of a frozen-trunk step: cf_reduce_opt_part(CF_BUCKET_REG) -- the same tiles, the same arithmetic, the same bits;
+ * nothing of the Embedding + Pairwise range (parameters, moments, gradients, tiled copies) is read or written, no weight decay on it
+ * either -- with ONE more workgroup that advances `cursor` (null: nothing to advance) and writes a pending cf_record_step_bwd's log
+ * rows.  Also serves the all-rows Embedding (embed n_layers > 1): that path's gradients are the trunk's.  Not capturable. */
+int cf_reduce_opt_x0(cf_handle* h, int B, float lr, float beta1, float beta2, float eps, float weight_decay, long long step,
+                     int keep_grads, int* cursor, void* stream);
+/* cf_backward_from for a frozen trunk: head + Regulation backward and the reductions of CF_BUCKET_REG only. */
+int cf_backward_from_top(cf_handle* h, const cf_batch* batch, const float* dlogits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
