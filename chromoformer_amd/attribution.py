@@ -38,3 +38,148 @@ def ig_quadrature(method="gausslegendre", n_steps=50):
     """-> (alphas, weights), float32 [n_steps]: ig_quadrature64 cast to fp32 -- the table the library call uses."""
     a, w = ig_quadrature64(method, n_steps)
     return a.astype(np.float32), w.astype(np.float32)
+
+
+def raw_signal_gradients(model, dataset, genes=None, target=None, times_input=False, bsz=None):
+    """Raw-signal saliency: the gradient of logit column `target` (default: 1 for the classifier, 0 for the regressor) with respect to
+    the RAW histone signals of a ChromoformerDataset -- the fp16 [F, len] .npy regions, at their own resolution and in genomic
+    orientation -- by the exact chain rule on one backward pass.  A generator over `genes` (ids; default: the dataset's), working in
+    chunks of at most min(bsz, model.max_batch) genes; per chunk
+
+        raw regions -> HBM -> cf_bin_regions_multi -> model(...) with the binned features as leaves -> logits[:, target].sum().backward()
+        (cf_backward_from_inputs) -> cf_bin_regions_multi_backward with dfeat pointing into the .grad tensors
+
+    and per gene it yields a dict of host arrays:
+
+        gene_id    the id
+        logits     float32 [n_out]
+        promoter   float32 [F, window]: the window of the promoter file the dataset bins (w_prom-narrowed), genomic orientation (the mirror
+                   of a '-' strand promoter is undone)
+        pcres      list of float32 [F, len_s], one per pCRE, in the order of the metadata
+        regions    [(chrom, start, end)] of the promoter window and of every pCRE: sample s of a track is position start + s
+
+    times_input: gradient x input (each value multiplied by the raw sample).  Gradient and gradient x input only: integrated gradients
+    in raw space is a different path integral (log(1 + x) is not linear) and is not what this computes.  Parameters, their .grad and the
+    optimiser state are left as they are; the pass overwrites the activations a grad-enabled model(...) keeps for its backward."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    from .data import BIN_GRAD_JOB, BIN_JOB_MULTI, load_raw_regions, raw_window
+    ds = dataset
+    binsizes = [int(b) for b in ds.binsizes]
+    if len(binsizes) > 3 or len(set(binsizes)) != len(binsizes):
+        raise ValueError("raw_signal_gradients: binsizes %s: more than three or repeated bin sizes are binned by one cf_bin_regions launch "
+                         "per resolution, which has no backward; use at most three distinct bin sizes" % (binsizes,))
+    if model._handle is None:
+        raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
+    n_bins = [ds.w_max // b for b in binsizes]
+    if binsizes != list(model.binsizes) or n_bins != list(model.n_bins) or ds.i_max != model.i_max or ds.n_feats != model.n_feats:
+        raise ValueError("raw_signal_gradients: the dataset (binsizes %s, w_max %d, i_max %d, n_feats %d) does not match the model "
+                         "(binsizes %s, w_max %d, i_max %d, n_feats %d)" % (binsizes, ds.w_max, ds.i_max, ds.n_feats, list(model.binsizes),
+                                                                            model.w_max, model.i_max, model.n_feats))
+    target = (1 if model.n_out == 2 else 0) if target is None else int(target)
+    if not 0 <= target < model.n_out:
+        raise ValueError("raw_signal_gradients: target = %d outside [0, n_out = %d)" % (target, model.n_out))
+    genes = list(ds.target_genes if genes is None else genes)
+    missing = [g for g in genes if g not in ds.genes]
+    if missing:
+        raise KeyError("raw_signal_gradients: gene(s) %s are not in the dataset's metadata" % missing[:5])
+    chunk = model._max_batch if bsz is None else max(1, min(int(bsz), model._max_batch))
+    dev, L_ = model._device, _lib.lib()
+    S, T, F, nres = ds.i_max, ds.i_max + 1, ds.n_feats, len(binsizes)
+    order = sorted(range(nres), key=lambda r: -binsizes[r])      # coarsest first
+    cb = (C.c_int * nres)(*[binsizes[r] for r in order])
+    cl = (C.c_int * nres)(*[n_bins[r] for r in order])
+    for lo in range(0, len(genes), chunk):
+        ids = genes[lo:lo + chunk]
+        B = len(ids)
+        regs = []                                                # (gene row, slot, flip, raw array, col0, ncols, raw offset, draw offset, ld_out)
+        n_raw = n_out = max_cols = 0
+        for i, gene in enumerate(ids):
+            for s, flip, a in load_raw_regions(ds, gene):
+                c0, nc = raw_window(ds, s, a.shape[1])
+                for r, b in enumerate(binsizes):
+                    if -(-nc // b) > n_bins[r]:
+                        raise ValueError("region spans %d bins but w_max allows %d" % (-(-nc // b), n_bins[r]))
+                ld_out = -(-nc // 4) * 4
+                regs.append((i, s, flip, a, c0, nc, n_raw, n_out, ld_out))
+                n_raw += -(-a.size // 4) * 4                     # every region starts 8-byte aligned
+                n_out += F * ld_out
+                max_cols = max(max_cols, nc)
+        flat = np.zeros(n_raw, dtype=np.float16)
+        for _, _, _, a, _, _, off, _, _ in regs:
+            flat[off:off + a.size] = a.reshape(-1)
+        stream = torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev):
+            raw = torch.from_numpy(flat).to(dev)
+            draw = torch.empty(max(n_out, 1), dtype=torch.float32, device=dev)      # (every window sample is written by the library)
+            pf = [torch.zeros(B, 1, L, F, device=dev) for L in n_bins]
+            cf = [torch.zeros(B, S, L, F, device=dev) for L in n_bins]
+            pm = [torch.ones(B, L, dtype=torch.uint8, device=dev) for L in n_bins]
+            cm = [torch.ones(B, S, L, dtype=torch.uint8, device=dev) for L in n_bins]      # dummy slots stay fully masked
+            im = torch.ones(B, T, T, dtype=torch.uint8)
+            freq = torch.zeros(B, T, T)
+            for i, gene in enumerate(ids):
+                g = ds.genes[gene]
+                n_part = len(g["pcres"])
+                im[i, :n_part + 1, :n_part + 1] = 0
+                for s, sc in enumerate(g["scores"]):
+                    freq[i, 0, s + 1] = sc
+            im, freq = im.to(dev), freq.to(dev)
+            fj = np.zeros(len(regs), dtype=BIN_JOB_MULTI)
+            for k, (i, s, flip, a, c0, nc, off, _, _) in enumerate(regs):
+                fj[k]["raw"], fj[k]["ld"], fj[k]["col0"], fj[k]["ncols"], fj[k]["flip"] = raw.data_ptr() + 2 * off, a.shape[1], c0, nc, int(flip)
+                for r in range(nres):
+                    out = pf[r][i, 0] if s < 0 else cf[r][i, s]
+                    msk = pm[r][i] if s < 0 else cm[r][i, s]
+                    fj[k]["out"][order.index(r)], fj[k]["mask"][order.index(r)] = out.data_ptr(), msk.data_ptr()
+            tab = torch.from_numpy(fj.view(np.uint8)).to(dev)
+            _lib.check(L_.cf_bin_regions_multi(C.c_void_p(tab.data_ptr()), len(regs), F, nres, cb, cl, int(max_cols), stream.cuda_stream),
+                       "cf_bin_regions_multi")
+            # the backward of the model writes the flat gradient buffer and publishes it as the parameters' .grad: both are put back
+            named = model._named()
+            kept = {k: p.grad for k, p in named.items()}
+            kept_flat, kept_top = model._gflat.clone(), getattr(model, "_grads_top", None)
+            try:
+                for t in pf + cf:
+                    t.requires_grad_(True)
+                with torch.enable_grad():
+                    logits = model({b: pf[r] for r, b in enumerate(binsizes)}, {b: pm[r] for r, b in enumerate(binsizes)},
+                                   {b: cf[r] for r, b in enumerate(binsizes)}, {b: cm[r] for r, b in enumerate(binsizes)},
+                                   {b: im for b in binsizes}, freq)
+                    logits[:, target].sum().backward()
+            finally:
+                model._gflat.copy_(kept_flat)
+                for k, p in named.items():
+                    p.grad = kept[k]
+                model._grads_top = kept_top
+            dp, dc = [t.grad for t in pf], [t.grad for t in cf]
+            if any(t is None or not t.is_contiguous() for t in dp + dc):
+                raise RuntimeError("raw_signal_gradients: the backward pass left no gradient for a binned input")
+            bj = np.zeros(len(regs), dtype=BIN_GRAD_JOB)
+            for k, (i, s, flip, a, c0, nc, off, ooff, ld_out) in enumerate(regs):
+                for name in ("raw", "ld", "col0", "ncols", "flip"):
+                    bj[k][name] = fj[k][name]
+                for r in range(nres):
+                    bj[k]["dfeat"][order.index(r)] = (dp[r][i, 0] if s < 0 else dc[r][i, s]).data_ptr()
+                bj[k]["draw"], bj[k]["ld_out"] = draw.data_ptr() + 4 * ooff, ld_out
+            tab2 = torch.from_numpy(bj.view(np.uint8)).to(dev)
+            _lib.check(L_.cf_bin_regions_multi_backward(C.c_void_p(tab2.data_ptr()), len(regs), F, nres, cb, cl, int(max_cols),
+                                                        1 if times_input else 0, stream.cuda_stream), "cf_bin_regions_multi_backward")
+            host = draw.cpu().numpy()
+            lg = logits.detach().cpu().numpy()
+        per = [dict(gene_id=gene, logits=lg[i].copy(), promoter=None, pcres=[], regions=[]) for i, gene in enumerate(ids)]
+        for i, s, flip, a, c0, nc, off, ooff, ld_out in regs:
+            track = host[ooff:ooff + F * ld_out].reshape(F, ld_out)[:, :nc].copy()
+            g = ds.genes[ids[i]]
+            if s < 0:
+                chrom, tss, _ = g["tss"]
+                per[i]["promoter"] = track
+                per[i]["regions"].append((chrom, tss - 20000 + c0, tss - 20000 + c0 + nc))
+            else:
+                per[i]["pcres"].append(track)
+                per[i]["regions"].append(tuple(g["pcres"][s]))
+        for d in per:
+            yield d

@@ -3685,6 +3685,51 @@ extern "C" int cf_bin_regions_multi(const cf_bin_job_multi* jobs, int n_jobs, in
     return 0;
 }
 
+static_assert(sizeof(cf_bin_grad_job) == sizeof(BinGradJob) && sizeof(cf_bin_grad_job) == 72, "cf_bin_grad_job layout");
+extern "C" int cf_bin_regions_multi_backward(const cf_bin_grad_job* jobs, int n_jobs, int n_feats, int n_res, const int* bin_sizes,
+                                             const int* n_bins_out, int max_cols, int times_input, void* stream) {
+    if (!jobs || !bin_sizes || !n_bins_out) return fail("cf_bin_regions_multi_backward: null argument");
+    if (n_jobs < 0 || n_feats < 1 || n_feats > 64 || n_res < 1 || n_res > kBinMaxRes || max_cols < 0) return fail("cf_bin_regions_multi_backward: bad argument");
+    if (n_jobs == 0) return 0;
+    BinPlan pl;
+    memset(&pl, 0, sizeof pl);
+    pl.n_res = n_res;
+    pl.F = n_feats;
+    for (int r = 0; r < n_res; ++r) {
+        if (bin_sizes[r] < 1 || n_bins_out[r] < 1 || n_bins_out[r] > kBinMaxBins) return fail("cf_bin_regions_multi_backward: bad bin size / bin count at resolution %d", r);
+        if (r && bin_sizes[r] >= bin_sizes[r - 1]) return fail("cf_bin_regions_multi_backward: bin sizes must be listed coarsest first (%d after %d)", bin_sizes[r], bin_sizes[r - 1]);
+        pl.b[r] = bin_sizes[r];
+        pl.L[r] = n_bins_out[r];
+    }
+    {   // this call WRITES through the job table: rows shorter than the window would overlap.  The table is read back (72 bytes per region,
+        // stream-ordered, one synchronisation) -- an attribution call, not a step of a training loop
+        std::vector<cf_bin_grad_job> host((size_t)n_jobs);
+        if (hipMemcpyAsync(host.data(), jobs, sizeof(cf_bin_grad_job) * (size_t)n_jobs, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
+            hipStreamSynchronize((hipStream_t)stream) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail("cf_bin_regions_multi_backward: the job table could not be read back (it must be a device array of n_jobs records)");
+        }
+        for (int k = 0; k < n_jobs; ++k) {
+            if (host[k].ncols < 0 || host[k].ncols > max_cols) return fail("cf_bin_regions_multi_backward: ncols = %d of job %d outside [0, max_cols = %d]", host[k].ncols, k, max_cols);
+            if (host[k].ld_out < host[k].ncols) return fail("cf_bin_regions_multi_backward: ld_out = %lld < ncols = %d in job %d", host[k].ld_out, host[k].ncols, k);
+            if (host[k].ncols > 0 && (!host[k].raw || !host[k].draw)) return fail("cf_bin_regions_multi_backward: null raw / draw in job %d", k);
+        }
+    }
+    bool nested = n_res >= 2 && n_feats <= kBinMaxF && (pl.b[n_res - 1] & 3) == 0 && pl.b[0] <= kBinMaxLoads * 256 && pl.b[0] / pl.b[n_res - 1] <= 64;
+    for (int r = 0; r + 1 < n_res; ++r) nested = nested && pl.b[r] % pl.b[r + 1] == 0;
+    pl.nested = nested ? 1 : 0;
+    const int units = nested ? std::max(1, (max_cols + pl.b[0] - 1) / pl.b[0]) : 1;
+    const dim3 grid((units + 3) / 4, n_jobs);
+    const int nload = nested ? (pl.b[0] / 4 + 63) / 64 : 4;
+    const BinGradJob* jm = reinterpret_cast<const BinGradJob*>(jobs);
+    const int times = times_input ? 1 : 0;
+    if (nload <= 4) hipLaunchKernelGGL(k_bin_multi_bwd<4>, grid, dim3(256), 0, (hipStream_t)stream, jm, pl, times);
+    else if (nload <= 8) hipLaunchKernelGGL(k_bin_multi_bwd<8>, grid, dim3(256), 0, (hipStream_t)stream, jm, pl, times);
+    else hipLaunchKernelGGL(k_bin_multi_bwd<16>, grid, dim3(256), 0, (hipStream_t)stream, jm, pl, times);
+    LAUNCH_CHECK("k_bin_multi_bwd");
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------
 // dense (all rows) layer: projections -> attention core -> out-projection / LN / FFN / LN chain, and its backward
 // ------------------------------------------------------------------------------------

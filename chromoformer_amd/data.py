@@ -29,8 +29,9 @@ def _split_interval(s):
 
 def bin_log1p(x, bin_size):
     """[F, len] float32 -> [F, ceil(len/bin)]: per-bin mean (the last bin may be short, data.py:80-81)
-    followed by natural log(1 + x) (data.py:82)."""
-    x = torch.as_tensor(x, dtype=torch.float32)
+    followed by natural log(1 + x) (data.py:82).  A float64 tensor stays float64 (reference gradients in the tests)."""
+    if not (torch.is_tensor(x) and x.dtype == torch.float64):
+        x = torch.as_tensor(x, dtype=torch.float32)
     n_full, tail = divmod(x.shape[1], bin_size)
     parts = []
     if n_full:
@@ -48,7 +49,7 @@ def centred(binned, L, flip=False):
     if n > L:
         raise ValueError("region spans %d bins but w_max allows %d" % (n, L))
     left = math.ceil((L - n) / 2)
-    out = torch.zeros(binned.shape[0], L)
+    out = torch.zeros(binned.shape[0], L, dtype=binned.dtype)
     out[:, left:left + n] = binned
     if flip:
         return torch.flip(out, dims=[1]), (L - n) // 2, n
@@ -82,14 +83,15 @@ class ChromoformerDataset(torch.utils.data.Dataset):
     def _load(self, chrom, start, end):
         return np.load("%s/%s:%d-%d.npy" % (self.npy_dir, chrom, start, end))
 
-    def regions(self, gene):
+    def regions(self, gene, dtype=torch.float32):
         """Binned + centred regions of a gene for every resolution:
-        {binsize: (promoter [F,L], lo_p, n_p, [(pcre [F,L], lo, n), ...])}"""
+        {binsize: (promoter [F,L], lo_p, n_p, [(pcre [F,L], lo, n), ...])}
+        dtype: torch.float32 as the reference (data.py:104), or torch.float64 for reference gradients."""
         g = self.genes[gene]
         chrom, tss, strand = g["tss"]
-        raw_p = torch.as_tensor(self._load(chrom, tss - 20000, tss + 20000)).float()
+        raw_p = torch.as_tensor(self._load(chrom, tss - 20000, tss + 20000)).to(dtype)
         raw_p = raw_p[:, 20000 - self.w_prom // 2: 20000 + self.w_prom // 2]     # data.py:106-107
-        raws = [torch.as_tensor(self._load(*p)).float() for p in g["pcres"]]
+        raws = [torch.as_tensor(self._load(*p)).to(dtype) for p in g["pcres"]]
         out = {}
         for b in self.binsizes:
             L = self.w_max // b
@@ -140,6 +142,51 @@ BIN_JOB = np.dtype([("raw", "<u8"), ("ld", "<i8"), ("col0", "<i4"), ("ncols", "<
 #: layout of cf_bin_job_multi: out / mask per resolution, coarsest resolution first
 BIN_JOB_MULTI = np.dtype([("raw", "<u8"), ("ld", "<i8"), ("col0", "<i4"), ("ncols", "<i4"), ("flip", "<i4"), ("reserved", "<i4"),
                           ("out", "<u8", (3,)), ("mask", "<u8", (3,))])
+
+
+#: layout of cf_bin_grad_job: dfeat per resolution (coarsest first), the raw-signal gradient and its row pitch
+BIN_GRAD_JOB = np.dtype([("raw", "<u8"), ("ld", "<i8"), ("col0", "<i4"), ("ncols", "<i4"), ("flip", "<i4"), ("reserved", "<i4"),
+                         ("dfeat", "<u8", (3,)), ("draw", "<u8"), ("ld_out", "<i8")])
+
+
+def promoter_col0(ds):
+    """First sample of the promoter window inside its 40,000-sample file (data.py:106-107)."""
+    col0 = 20000 - ds.w_prom // 2
+    if col0 < 0:
+        raise ValueError("w_prom = %d exceeds the 40,000-sample promoter files" % ds.w_prom)
+    return col0
+
+
+def raw_window(ds, s, ld):
+    """(col0, ncols) of the samples of a raw region that are binned: the w_prom-narrowed window of the promoter (slot s < 0), the
+    whole file of a pCRE."""
+    if s >= 0:
+        return 0, ld
+    col0 = promoter_col0(ds)
+    return col0, max(0, min(col0 + ds.w_prom, ld) - col0)
+
+
+def load_raw_regions(ds, gene):
+    """The raw regions of a gene (its id) of a dataset as the device binning ships them: [(slot, flip, fp16 [F, len] contiguous)], the promoter
+    (slot -1, flip for a '-' strand) first, then the pCREs in order."""
+    g = ds.genes[gene]
+    chrom, tss, strand = g["tss"]
+    regions = [(-1, strand != "+", ds._load(chrom, tss - 20000, tss + 20000))] + [(s, False, ds._load(*p)) for s, p in enumerate(g["pcres"])]
+    out = []
+    for s, flip, a in regions:
+        if a.dtype != np.float16:
+            # the reference widens whatever dtype the file has (data.py:104); the device path ships fp16, which is
+            # what preprocessing writes (extract_signals.py:66-71) -- refuse a lossy narrowing instead of training on inf
+            h = a.astype(np.float16)
+            if not np.array_equal(h.astype(a.dtype), a):
+                raise ValueError("raw signal file is %s and does not fit float16 exactly: bin it on the host "
+                                 "(GeneStore(device=None)) or re-save it as float16" % a.dtype)
+            a = h
+        a = np.ascontiguousarray(a, dtype=np.float16)
+        if a.shape[0] != ds.n_feats:
+            raise ValueError("expected %d feature rows, file has %d" % (ds.n_feats, a.shape[0]))
+        out.append((s, flip, a))
+    return out
 
 
 class GeneStore:
@@ -207,9 +254,7 @@ class GeneStore:
         cf = [arena((G, S, L, F), torch.float32, 0, dev) for L in self.n_bins]
         pm = [arena((G, L), torch.uint8, 1, dev) for L in self.n_bins]
         cm = [arena((G, S, L), torch.uint8, 1, dev) for L in self.n_bins]       # dummy slots stay fully masked
-        col0 = 20000 - ds.w_prom // 2                                           # data.py:106-107
-        if col0 < 0:
-            raise ValueError("w_prom = %d exceeds the 40,000-sample promoter files" % ds.w_prom)
+        promoter_col0(ds)                                                       # (refuses a w_prom wider than the promoter files)
         stream = torch.cuda.current_stream(dev)
         it = range(G)
         if progress:
@@ -233,7 +278,7 @@ class GeneStore:
             max_cols = 0
             for k, (i, s, flip, a) in enumerate(pending):
                 ld = a.shape[1]
-                c0, nc = (col0, max(0, min(col0 + ds.w_prom, ld) - col0)) if s < 0 else (0, ld)
+                c0, nc = raw_window(ds, s, ld)
                 max_cols = max(max_cols, nc)
                 mjobs[k]["raw"], mjobs[k]["ld"], mjobs[k]["col0"], mjobs[k]["ncols"], mjobs[k]["flip"] = base + 2 * off, ld, c0, nc, int(flip)
                 for r, b in enumerate(self.binsizes):
@@ -263,21 +308,7 @@ class GeneStore:
             pending, pending_bytes = [], 0
 
         for i in it:
-            g = ds.genes[ds.target_genes[i]]
-            chrom, tss, strand = g["tss"]
-            regions = [(-1, strand != "+", ds._load(chrom, tss - 20000, tss + 20000))] + [(s, False, ds._load(*p)) for s, p in enumerate(g["pcres"])]
-            for s, flip, a in regions:
-                if a.dtype != np.float16:
-                    # the reference widens whatever dtype the file has (data.py:104); the device path ships fp16, which is
-                    # what preprocessing writes (extract_signals.py:66-71) -- refuse a lossy narrowing instead of training on inf
-                    h = a.astype(np.float16)
-                    if not np.array_equal(h.astype(a.dtype), a):
-                        raise ValueError("raw signal file is %s and does not fit float16 exactly: bin it on the host "
-                                         "(GeneStore(device=None)) or re-save it as float16" % a.dtype)
-                    a = h
-                a = np.ascontiguousarray(a, dtype=np.float16)
-                if a.shape[0] != F:
-                    raise ValueError("expected %d feature rows, file has %d" % (F, a.shape[0]))
+            for s, flip, a in load_raw_regions(ds, ds.target_genes[i]):
                 pending.append((i, s, flip, a))
                 pending_bytes += a.nbytes
             if pending_bytes >= chunk_bytes:

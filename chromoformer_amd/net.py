@@ -581,6 +581,13 @@ class ChromoformerBase(nn.Module):
             attr = {k: ({b: t.view(shapes[k][b]) for b, t in v.items()} if isinstance(v, dict) else v.view(shapes[k])) for k, v in attr.items()}
         return attr, {"logits": lx, "baseline_logits": lb, "delta": delta}
 
+    def raw_signal_gradients(self, dataset, genes=None, target=None, times_input=False, bsz=None):
+        """Raw-signal saliency of the genes of a ChromoformerDataset: the gradient (or gradient x input) of logit column `target` with
+        respect to the raw fp16 signals, per gene one track per histone mark for the promoter window and every pCRE, in genomic
+        orientation (chromoformer_amd.attribution.raw_signal_gradients, a generator of per-gene dicts)."""
+        from .attribution import raw_signal_gradients
+        return raw_signal_gradients(self, dataset, genes=genes, target=target, times_input=times_input, bsz=bsz)
+
     @torch.no_grad()
     def trunk_outputs(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
                       interaction_freq=None):

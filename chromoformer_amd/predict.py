@@ -165,16 +165,52 @@ def write_integrated_gradients(model, store, bsz, ig_dir, n_steps=50, method="ga
         m.flush()
 
 
+def require_raw_signals(dataset, genes=None):
+    """Raw-signal saliency reads the raw .npy regions themselves; a packed store holds binned features only.  Raises FileNotFoundError
+    naming the first region file of `genes` (default: the dataset's) that is missing."""
+    import os
+    ds = dataset
+    for gene in (ds.target_genes if genes is None else genes):
+        g = ds.genes[gene]
+        chrom, tss, _ = g["tss"]
+        for region in [(chrom, tss - 20000, tss + 20000)] + list(g["pcres"]):
+            path = "%s/%s:%d-%d.npy" % ((ds.npy_dir,) + tuple(region))
+            if not os.path.exists(path):
+                raise FileNotFoundError("raw-signal saliency: %s is missing (gene %s); raw signals are required -- a packed store holds the "
+                                        "binned features only, keep the .npy files next to it" % (path, gene))
+
+
+def write_raw_saliency(model, dataset, bsz, saliency_dir, target=None, times_input=False):
+    """Raw-signal saliency of every gene of a dataset (model.raw_signal_gradients) into `saliency_dir`/<gene_id>.npz: `promoter`
+    float32 [F, window] and `pcre_<s>` float32 [F, len_s] in genomic orientation, `regions` (a string array "chrom:start-end", the
+    promoter window first: sample s of a track is position start + s), `logits` [n_out]."""
+    import os
+    os.makedirs(saliency_dir, exist_ok=True)
+    require_raw_signals(dataset)
+    for d in model.raw_signal_gradients(dataset, target=target, times_input=times_input, bsz=bsz):
+        arrays = {"promoter": d["promoter"], "logits": d["logits"],
+                  "regions": np.array(["%s:%d-%d" % tuple(r) for r in d["regions"]])}
+        for s, t in enumerate(d["pcres"]):
+            arrays["pcre_%d" % s] = t
+        np.savez(os.path.join(saliency_dir, "%s.npz" % d["gene_id"]), **arrays)
+
+
 def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123, i_max=8, w_prom=40000, w_max=40000,
             binsizes=(2000, 500, 100), progress=False, store_path=None, attention_dir=None, embeddings_out=None,
-            pcre_ablation_out=None, ig_dir=None, ig_steps=50, ig_method="gausslegendre", ig_target=None):
+            pcre_ablation_out=None, ig_dir=None, ig_steps=50, ig_method="gausslegendre", ig_target=None, raw_saliency_dir=None,
+            raw_saliency_target=None, raw_saliency_times_input=False):
     """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file.  attention_dir / embeddings_out: also
     write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps); pcre_ablation_out:
     the predictions with each pCRE deleted (write_pcre_ablation); ig_dir: integrated gradients of every gene
-    (write_integrated_gradients)."""
+    (write_integrated_gradients); raw_saliency_dir: the gradient (or gradient x input) of the prediction with respect to the raw
+    signals, one .npz per gene (write_raw_saliency; needs the raw .npy files also when a packed store serves the predictions)."""
     seed_everything(seed)
     meta = pd.read_csv(meta_path)
     genes = meta.gene_id.tolist()
+    raw_ds = None
+    if raw_saliency_dir:
+        raw_ds = ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=regression)
+        require_raw_signals(raw_ds)      # (before anything is computed)
     from . import pack
     packed = pack.find(npy_dir, store_path, list(binsizes), i_max, w_prom, w_max, 7, genes, meta=meta)
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -199,10 +235,12 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         write_pcre_ablation(model, store, bsz, pcre_ablation_out, regression)
     if ig_dir:
         write_integrated_gradients(model, store, bsz, ig_dir, ig_steps, ig_method, ig_target)
+    if raw_saliency_dir:
+        write_raw_saliency(model, raw_ds, bsz, raw_saliency_dir, raw_saliency_target, raw_saliency_times_input)
     return meta, np.concatenate(preds).astype(np.float32)
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description="Chromoformer expression prediction on the MI355X path")
     ap.add_argument("-m", "--meta", required=True, help="Path to input metadata file.")
     ap.add_argument("-d", "--npy-dir", required=True, help="Path to directory containing histone signals in .npy files.")
@@ -225,7 +263,22 @@ def main(argv=None):
     ap.add_argument("--ig-steps", type=int, default=None, help="quadrature nodes of --ig-dir (default 50)")
     ap.add_argument("--ig-method", default=None, choices=METHODS, help="quadrature of --ig-dir (default gausslegendre)")
     ap.add_argument("--ig-target", type=int, default=None, help="logit column of --ig-dir (default 1 for the classifier, 0 with --regression)")
+    ap.add_argument("--raw-saliency-dir", default=None, help="also write raw-signal saliency: DIR/<gene_id>.npz with the gradient of the "
+                    "prediction's logit with respect to the raw .npy signals (promoter [7, window], pcre_<s> [7, len], genomic orientation, "
+                    "regions, logits; model.raw_signal_gradients).  Needs the raw .npy files, also next to a packed store")
+    ap.add_argument("--raw-saliency-target", type=int, default=None, help="logit column of --raw-saliency-dir (default 1 for the classifier, 0 "
+                    "with --regression)")
+    ap.add_argument("--raw-saliency-times-input", action="store_true", help="--raw-saliency-dir writes gradient x input")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
+    if not args.raw_saliency_dir and (args.raw_saliency_target is not None or args.raw_saliency_times_input):
+        ap.error("--raw-saliency-target / --raw-saliency-times-input need --raw-saliency-dir")
+    if args.raw_saliency_target is not None and not 0 <= args.raw_saliency_target < (1 if args.regression else 2):
+        ap.error("--raw-saliency-target must be in [0, %d)" % (1 if args.regression else 2))
     if not args.ig_dir and (args.ig_steps is not None or args.ig_method is not None or args.ig_target is not None):
         ap.error("--ig-steps / --ig-method / --ig-target need --ig-dir")
     if args.ig_steps is not None and args.ig_steps < (2 if args.ig_method == "riemann_trapezoid" else 1):
@@ -235,7 +288,8 @@ def main(argv=None):
     meta, pred = predict(args.meta, args.npy_dir, args.weights, args.regression, progress=True, store_path=args.store,
                          attention_dir=args.attention_dir, embeddings_out=args.embeddings_out, pcre_ablation_out=args.pcre_ablation_out,
                          ig_dir=args.ig_dir, ig_steps=50 if args.ig_steps is None else args.ig_steps,
-                         ig_method=args.ig_method or "gausslegendre", ig_target=args.ig_target)
+                         ig_method=args.ig_method or "gausslegendre", ig_target=args.ig_target, raw_saliency_dir=args.raw_saliency_dir,
+                         raw_saliency_target=args.raw_saliency_target, raw_saliency_times_input=args.raw_saliency_times_input)
     print("Predicting expressions for %d genes." % len(meta))
     meta["prediction"] = pred
     meta.to_csv(args.output, index=False)
