@@ -319,9 +319,6 @@ struct cf_handle {
     float *pe2[kMaxRes], *pet2[kMaxRes];      // padded layouts of the gene-batched attention kernel (cf_attc2.h)
     bool attc2 = false;
     bool attc1 = true;                        // one-region launches on the vector-ALU kernel (CF_ATTC1=0: k_attc2<., 1>)
-    AdamHyper* hyper = nullptr;               // step-dependent AdamW scalars for the graph-replayed optimiser launch
-    std::vector<hipEvent_t> sync_ev;          // cf_stream_wait
-    size_t sync_ev_used = 0;
     int attc_cap = 64;                        // most workgroups per resolution for which attc2 trades regions per workgroup for parallelism
     int xcd_map = 1;                          // XCD-aware placement of the Regulation workgroups (CF_XCD_MAP=0 turns it off)
     int n_wg_r = 0, n_cs_r = 0;               // leading entries of wg_tiles / cs_tiles that belong to the Regulation + head bucket
@@ -338,7 +335,6 @@ struct cf_handle {
     float *hin, *h1, *logits, *dlogits, *dh1, *dhin, *loss, *loss_part, *tdbg;
     // input gradients (cf_backward_from_inputs)
     float* dfreq_part = nullptr;               // [n_res][max_batch][T * T]: d(interaction_freq) per resolution, summed by k_dfreq_sum
-    float* want_dfreq = nullptr;               // set for the duration of one cf_backward_from_inputs: the Regulation backward writes dfreq_part
     bool reg_dfreq_ok = false;                 // k_reg8_bwd_dfreq got its LDS attribute
     bool ig_smem_ok = false;                   // k_input_grad got its LDS attribute (first use)
     // in-silico pCRE deletion (cf_pcre_ablation): one allocation, made by the first call (ablate_alloc)
@@ -360,8 +356,6 @@ struct cf_handle {
     int intg_cap = 0;
     float* intg_part = nullptr;                // [max_batch, kIgSlices]: per-slice sums of a gene's attributions (k_ig_delta)
     bool intg_trunk_once = true;               // frequency-only IG runs the trunk once (CF_IG_TRUNK_ONCE=0 at cf_create: the general path, for A/B checks)
-    int ag_genes = 0;                          // set by cf_integrated_gradients: k_attc2 regions per workgroup chosen as for a batch of this many genes
-    bool skip_dense_embed_bwd = false;         // set by cf_integrated_gradients: the all-rows Embedding backward (it writes parameter gradients) is not run
     // deferred-gradient tile tables
     WgTile* wg_tiles = nullptr;
     int n_wg = 0;
@@ -935,7 +929,7 @@ extern "C" int cf_create(const cf_config* cfg, const float* const* pe_host, cf_h
             if (late == 0) h->n_retile_early = (int)units.size();
         }
         h->n_retile = (int)units.size();
-        if (hipMalloc(&h->hyper, sizeof(AdamHyper)) != hipSuccess || hipMalloc(&h->tiled, h->lay.n_total * sizeof(float)) != hipSuccess ||
+        if (hipMalloc(&h->tiled, h->lay.n_total * sizeof(float)) != hipSuccess ||
             hipMalloc(&h->tiledT, h->lay.n_total * sizeof(float)) != hipSuccess ||
             hipMalloc(&h->retile_units, units.size() * sizeof(RetileUnit)) != hipSuccess ||
             hipMemcpy(h->retile_units, units.data(), units.size() * sizeof(RetileUnit), hipMemcpyHostToDevice) != hipSuccess) {
@@ -1041,9 +1035,7 @@ extern "C" void cf_destroy(cf_handle* h) {
         if (rp.second) (void)hipGraphExecDestroy(rp.second);
     }
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->sync_ev) (void)hipEventDestroy(e);
     if (h->ride_ev) (void)hipEventDestroy(h->ride_ev);
-    if (h->hyper) (void)hipFree(h->hyper);
     if (h->abl_mem) (void)hipFree(h->abl_mem);
     if (h->intg_mem) (void)hipFree(h->intg_mem);
     if (h->intg_tab) (void)hipFree(h->intg_tab);
@@ -1143,6 +1135,60 @@ static int centre_bwd_heads(hipStream_t st, int N, int nres, int dff, const Post
     LAUNCH_CHECK("k_attc<bwd>");
     hipLaunchKernelGGL((k_qchain_bwd<NWV, NH, D>), dim3(tiles_of(N), nres), dim3(NWV * 64), 0, st, qb);
     LAUNCH_CHECK("k_qchain_bwd");
+    return 0;
+}
+
+// Options of one pass that are not handle state: the attribution entry points (cf_api_attrib.h) set them, training passes the default.
+struct PassOpts {
+    float* dfreq = nullptr;                    // the Regulation backward also leaves d(interaction_freq) per resolution here (cf_handle::dfreq_part)
+    bool no_dense_embed_bwd = false;           // the all-rows Embedding backward (it writes parameter gradients) is not run
+    int ag_genes = 0;                          // k_attc2 regions per workgroup chosen as for a batch of this many genes (0: the batch's own)
+};
+// The centre-row attention launch of the default shape (two heads, 128): gene-batched (cf_attc2.h, one region per workgroup on cf_attc1.h)
+// where its LDS image fits, else k_attc.  Forward and backward pass take the same route.
+template <bool BWD>
+static int launch_attc(cf_handle* h, const AttcArgs& at, int N, int B, size_t smem, int ag_genes, hipStream_t st) {
+    const int nres = h->cfg.n_res;
+    if (h->attc2) {
+        const int ag = attc2_regions_per_wg(ag_genes ? N / B * ag_genes : N, h->attc_cap);
+        Attc2Args a2;
+        size_t sm2 = 0;
+        for (int r = 0; r < nres; ++r) {
+            a2.feats[r] = at.feats[r];
+            a2.mask[r] = at.mask[r];
+            a2.mstride[r] = at.mstride[r];
+            a2.pe[r] = h->pe2[r];
+            a2.pet[r] = h->pet2[r];
+            a2.wlp[r] = at.wlp[r];
+            a2.vin[r] = at.vin[r];
+            a2.p[r] = at.p[r];
+            a2.w[r] = at.w[r];
+            a2.vout[r] = at.vout[r];
+            a2.L[r] = at.L[r];
+            a2.Lpad[r] = attc2_lpad(at.L[r]);
+            a2.LT[r] = attc2_lt(at.L[r]);
+            sm2 = std::max(sm2, attc2_smem(at.L[r], at.F, ag));
+        }
+        a2.N = N;
+        a2.F = at.F;
+        a2.scale = at.scale;
+        a2.rscale = 1.0f / a2.scale;
+        a2.tdbg = (getenv("CF_STAMP_ATTC") && (!getenv("CF_STAMP_ATTC_AG") || atoi(getenv("CF_STAMP_ATTC_AG")) == ag))
+                      ? reinterpret_cast<unsigned long long*>(h->tdbg) + 256 : nullptr;
+        a2.tall = (getenv("CF_STAMP_ATTC_ALL") && atoi(getenv("CF_STAMP_ATTC_ALL")) == (BWD ? 1 : 0) && (!getenv("CF_STAMP_ATTC_AG") || atoi(getenv("CF_STAMP_ATTC_AG")) == ag))
+                      ? reinterpret_cast<unsigned long long*>(h->tdbg) + 256 : nullptr;
+        void* kargs2[] = {&a2};
+        if (ag == 1 && h->attc1) {      // one region per workgroup: the vector-ALU kernel (cf_attc1.h)
+            size_t sm1 = 0;
+            for (int r = 0; r < nres; ++r) sm1 = std::max(sm1, attc1_smem(at.L[r], at.F));
+            HIP_TRY(hipLaunchKernel((const void*)k_attc1<BWD>, dim3(N, nres), dim3(kAT), kargs2, sm1, st));
+        } else {
+            HIP_TRY(hipLaunchKernel(attc2_kernel<BWD>(ag), dim3((N + ag - 1) / ag, nres), dim3(kAT), kargs2, sm2, st));
+        }
+    } else {
+        hipLaunchKernelGGL((k_attc<BWD>), dim3(N, nres), dim3(256), smem, st, at);
+    }
+    LAUNCH_CHECK(BWD ? "k_attc<bwd>" : "k_attc<fwd>");
     return 0;
 }
 
@@ -1355,7 +1401,7 @@ static int retile_early(cf_handle* h, hipStream_t st) {
 // The forward pass in two parts: the trunk (prologue, Embedding + Pairwise stage) writes the Regulation input Rx[r][0]; the
 // Regulation stack and the head read it with the batch's interaction masks and frequencies (cf_pcre_ablation runs the second part
 // on gene-variant chunks of the first one's output).
-static int forward_trunk(cf_handle* h, const cf_batch* bt, int save, hipStream_t st) {
+static int forward_trunk(cf_handle* h, const cf_batch* bt, int save, hipStream_t st, int ag_genes = 0) {
     const cf_config& c = h->cfg;
     const int kD = c.d_emb;      // (row width: shadows cf::kD in this function; 128, or 256 through the stand-alone kernels)
     const int B = bt->B, S = c.i_max, T = S + 1, nres = c.n_res, F = c.n_feats;
@@ -1529,46 +1575,7 @@ static int forward_trunk(cf_handle* h, const cf_batch* bt, int save, hipStream_t
             hipLaunchKernelGGL((k_qchain_fwd<kPostWaves>), dim3(tiles_of(N), nres), dim3(kPostWaves * 64), 0, st, q);
             LAUNCH_CHECK("k_qchain_fwd");
         }
-        if (h->attc2) {
-            const int ag = attc2_regions_per_wg(h->ag_genes ? N / B * h->ag_genes : N, h->attc_cap);
-            Attc2Args a2;
-            size_t sm2 = 0;
-            for (int r = 0; r < nres; ++r) {
-                a2.feats[r] = at.feats[r];
-                a2.mask[r] = at.mask[r];
-                a2.mstride[r] = at.mstride[r];
-                a2.pe[r] = h->pe2[r];
-                a2.pet[r] = h->pet2[r];
-                a2.wlp[r] = at.wlp[r];
-                a2.vin[r] = at.vin[r];
-                a2.p[r] = at.p[r];
-                a2.w[r] = at.w[r];
-                a2.vout[r] = at.vout[r];
-                a2.L[r] = at.L[r];
-                a2.Lpad[r] = attc2_lpad(at.L[r]);
-                a2.LT[r] = attc2_lt(at.L[r]);
-                sm2 = std::max(sm2, attc2_smem(at.L[r], F, ag));
-            }
-            a2.N = N;
-            a2.F = F;
-            a2.scale = scale_c;
-            a2.rscale = 1.0f / a2.scale;
-            a2.tdbg = (getenv("CF_STAMP_ATTC") && (!getenv("CF_STAMP_ATTC_AG") || atoi(getenv("CF_STAMP_ATTC_AG")) == ag))
-                          ? reinterpret_cast<unsigned long long*>(h->tdbg) + 256 : nullptr;
-            a2.tall = (getenv("CF_STAMP_ATTC_ALL") && atoi(getenv("CF_STAMP_ATTC_ALL")) == 0 && (!getenv("CF_STAMP_ATTC_AG") || atoi(getenv("CF_STAMP_ATTC_AG")) == ag))
-                          ? reinterpret_cast<unsigned long long*>(h->tdbg) + 256 : nullptr;
-            void* kargs2[] = {&a2};
-            if (ag == 1 && h->attc1) {      // one region per workgroup: the vector-ALU kernel (cf_attc1.h)
-                size_t sm1 = 0;
-                for (int r = 0; r < nres; ++r) sm1 = std::max(sm1, attc1_smem(at.L[r], F));
-                HIP_TRY(hipLaunchKernel((const void*)k_attc1<false>, dim3(N, nres), dim3(kAT), kargs2, sm1, st));
-            } else {
-                HIP_TRY(hipLaunchKernel(attc2_kernel<false>(ag), dim3((N + ag - 1) / ag, nres), dim3(kAT), kargs2, sm2, st));
-            }
-        } else {
-            hipLaunchKernelGGL((k_attc<false>), dim3(N, nres), dim3(256), smem, st, at);
-        }
-        LAUNCH_CHECK("k_attc<fwd>");
+        if (launch_attc<false>(h, at, N, B, smem, ag_genes, st)) return -1;
         dim3 pgrid(tiles_of(N), nres);
         if (host_retile) {
             po.rt_units = h->retile_units + h->n_retile_early;
@@ -1860,7 +1867,7 @@ extern "C" int cf_forward_train(cf_handle* h, const cf_batch* bt, float* logits,
 // ------------------------------------------------------------------------------------
 // parts: 1 = head, 2 = Regulation stack, 4 = Pairwise + Embedding (the activation-gradient chain in order)
 static int backward_impl(cf_handle* h, const cf_batch* bt, hipStream_t st, int parts = 7, const void* labels = nullptr,
-                         float loss_scale = 1.f, float* loss_out = nullptr) {
+                         float loss_scale = 1.f, float* loss_out = nullptr, const PassOpts& opts = PassOpts()) {
     const cf_config& c = h->cfg;
     const int kD = c.d_emb;      // (row width: shadows cf::kD in this function)
     const int B = bt->B, S = c.i_max, T = S + 1, nres = c.n_res, F = c.n_feats;
@@ -1945,9 +1952,9 @@ static int backward_impl(cf_handle* h, const cf_batch* bt, hipStream_t st, int p
         }
         ra.row0_last = h->reg_row0 ? 1 : 0;
         ra.dfreq = nullptr;
-        if (h->want_dfreq) {      // cf_backward_from_inputs: the variant that also leaves d(interaction_freq) per resolution
+        if (opts.dfreq) {      // cf_backward_from_inputs: the variant that also leaves d(interaction_freq) per resolution
             if (!h->reg_dfreq_ok) return fail("cf_backward_from_inputs: interaction_freq: the fused Regulation backward variant could not be configured");
-            ra.dfreq = h->want_dfreq;
+            ra.dfreq = opts.dfreq;
             void* kargs[] = {&ra};
             HIP_TRY(hipLaunchKernel(reg_kernel_dfreq(c.reg_dff), dim3(8 * ((B * nres + 7) / 8)), dim3(512), kargs, reg8_bwd_smem(c.reg_dff), st));
             LAUNCH_CHECK("k_reg_bwd_dfreq");
@@ -1997,7 +2004,7 @@ static int backward_impl(cf_handle* h, const cf_batch* bt, hipStream_t st, int p
         at.T = T;
         at.H = c.reg_heads;
         at.DM = RDm;
-        at.dfreq = h->want_dfreq;
+        at.dfreq = opts.dfreq;
         at.dfreq_add = l + 1 < c.reg_layers;      // (the top layer's launch comes first: it writes, the ones below add)
         dg.lddy = RW;
         dg.ldw = kD;
@@ -2127,46 +2134,7 @@ static int backward_impl(cf_handle* h, const cf_batch* bt, hipStream_t st, int p
         if (nh == 4) return centre_bwd_heads<4>(st, N, nres, dff, pb, at, smem, qb);
         launch_post_bwd<true, 128>(dff, dim3(tiles_of(N), nres), st, pb);
         LAUNCH_CHECK("k_post_bwd<centre>");
-        if (h->attc2) {
-            const int ag = attc2_regions_per_wg(h->ag_genes ? N / B * h->ag_genes : N, h->attc_cap);
-            Attc2Args a2;
-            size_t sm2 = 0;
-            for (int r = 0; r < nres; ++r) {
-                a2.feats[r] = at.feats[r];
-                a2.mask[r] = at.mask[r];
-                a2.mstride[r] = at.mstride[r];
-                a2.pe[r] = h->pe2[r];
-                a2.pet[r] = h->pet2[r];
-                a2.wlp[r] = at.wlp[r];
-                a2.vin[r] = at.vin[r];
-                a2.p[r] = at.p[r];
-                a2.w[r] = at.w[r];
-                a2.vout[r] = at.vout[r];
-                a2.L[r] = at.L[r];
-                a2.Lpad[r] = attc2_lpad(at.L[r]);
-                a2.LT[r] = attc2_lt(at.L[r]);
-                sm2 = std::max(sm2, attc2_smem(at.L[r], F, ag));
-            }
-            a2.N = N;
-            a2.F = F;
-            a2.scale = scale_c;
-            a2.rscale = 1.0f / a2.scale;
-            a2.tdbg = (getenv("CF_STAMP_ATTC") && (!getenv("CF_STAMP_ATTC_AG") || atoi(getenv("CF_STAMP_ATTC_AG")) == ag))
-                          ? reinterpret_cast<unsigned long long*>(h->tdbg) + 256 : nullptr;
-            a2.tall = (getenv("CF_STAMP_ATTC_ALL") && atoi(getenv("CF_STAMP_ATTC_ALL")) == 1 && (!getenv("CF_STAMP_ATTC_AG") || atoi(getenv("CF_STAMP_ATTC_AG")) == ag))
-                          ? reinterpret_cast<unsigned long long*>(h->tdbg) + 256 : nullptr;
-            void* kargs2[] = {&a2};
-            if (ag == 1 && h->attc1) {
-                size_t sm1 = 0;
-                for (int r = 0; r < nres; ++r) sm1 = std::max(sm1, attc1_smem(at.L[r], F));
-                HIP_TRY(hipLaunchKernel((const void*)k_attc1<true>, dim3(N, nres), dim3(kAT), kargs2, sm1, st));
-            } else {
-                HIP_TRY(hipLaunchKernel(attc2_kernel<true>(ag), dim3((N + ag - 1) / ag, nres), dim3(kAT), kargs2, sm2, st));
-            }
-        } else {
-            hipLaunchKernelGGL((k_attc<true>), dim3(N, nres), dim3(256), smem, st, at);
-        }
-        LAUNCH_CHECK("k_attc<bwd>");
+        if (launch_attc<true>(h, at, N, B, smem, opts.ag_genes, st)) return -1;
         hipLaunchKernelGGL((k_qchain_bwd<kPostWaves>), dim3(tiles_of(N), nres), dim3(kPostWaves * 64), 0, st, qb);
         LAUNCH_CHECK("k_qchain_bwd");
         return 0;
@@ -2205,7 +2173,7 @@ static int backward_impl(cf_handle* h, const cf_batch* bt, hipStream_t st, int p
         LAUNCH_CHECK("k_join_dgrad");
     }
     if (h->embed_dense) {
-        if (!h->skip_dense_embed_bwd && embed_dense_backward(h, bt, st)) return -1;      // writes the Embedding gradients directly (no deferred tiles)
+        if (!opts.no_dense_embed_bwd && embed_dense_backward(h, bt, st)) return -1;      // writes the Embedding gradients directly (no deferred tiles)
     } else {   // Embedding
         CentreBuf* bufs[kMaxRes];
         const float* dout[kMaxRes];
@@ -2366,470 +2334,7 @@ extern "C" int cf_backward_from_top(cf_handle* h, const cf_batch* bt, const floa
     return reduce_impl(h, bt->B, st, CF_BUCKET_REG);
 }
 
-// cf_backward_from + the gradients of the float inputs (cf_input_grad.h).  The parameter gradients come from the very launches of
-// cf_backward_from; the interaction_freq gradient from the Regulation backward's DFREQ variant, the feature gradients from the saved
-// attention operands, in front of the reductions.  Every requested output is overwritten in full.
-extern "C" int cf_backward_from_inputs(cf_handle* h, const cf_batch* bt, const float* dlogits, const cf_input_grads* want, void* stream) {
-    bool any_p = false, any_c = false;
-    if (want)
-        for (int r = 0; r < kMaxRes; ++r) {
-            any_p |= want->promoter_feats[r] != nullptr;
-            any_c |= want->pcre_feats[r] != nullptr;
-        }
-    const bool any_f = want && want->interaction_freq;
-    if (!any_p && !any_c && !any_f) return cf_backward_from(h, bt, dlogits, stream);
-    if (check_bwd(h, bt)) return -1;
-    if (!dlogits) return fail("cf_backward_from_inputs: dlogits is null");
-    const cf_config& c = h->cfg;
-    const int B = bt->B, S = c.i_max, T = S + 1, nres = c.n_res, F = c.n_feats, kD = c.d_emb;
-    for (int r = nres; r < kMaxRes; ++r)
-        if (want->promoter_feats[r] || want->pcre_feats[r]) return fail("cf_backward_from_inputs: promoter_feats / pcre_feats[%d]: the model has %d resolutions", r, nres);
-    if (any_p && h->embed_dense)
-        return fail("cf_backward_from_inputs: promoter_feats: input gradients are implemented for embed.n_layers = 1 (the centre-row Embedding); "
-                    "this model has embed.n_layers = %d (the all-rows path keeps no first-layer input-row gradient)", c.embed_layers);
-    if (any_f && h->reg_fused && !h->reg_dfreq_ok)
-        return fail("cf_backward_from_inputs: interaction_freq: the fused Regulation backward variant could not be configured");
-    size_t smem = 0;
-    for (int r = 0; r < nres; ++r) smem = std::max(smem, input_grad_smem(c.n_bins[r], F, kD));
-    if ((any_p || any_c) && !h->ig_smem_ok) {
-        if (hipFuncSetAttribute((const void*)k_input_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return fail("cf_backward_from_inputs: promoter_feats / pcre_feats: k_input_grad needs %zu bytes of LDS", smem);
-        h->ig_smem_ok = true;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemcpyAsync(h->dlogits, dlogits, (size_t)B * c.n_out * sizeof(float), hipMemcpyDeviceToDevice, st));
-    h->want_dfreq = any_f ? h->dfreq_part : nullptr;
-    const int rc = backward_impl(h, bt, st);
-    h->want_dfreq = nullptr;
-    if (rc) return -1;
-    if (any_p || any_c) {
-        InGradArgs a;
-        memset(&a, 0, sizeof a);
-        for (int r = 0; r < nres; ++r) {
-            const int bs = c.binsizes[r];
-            a.feats_p[r] = bt->promoter_feats[r];
-            a.feats_c[r] = bt->pcre_feats[r];
-            a.mask_p[r] = static_cast<const uint8_t*>(bt->promoter_mask_row[r]);
-            a.mask_c[r] = static_cast<const uint8_t*>(bt->pcre_mask_row[r]);
-            a.mstride_p[r] = bt->promoter_mask_stride[r];
-            a.mstride_c[r] = bt->pcre_mask_stride[r];
-            a.pet[r] = h->pet[r];
-            a.w_p[r] = h->P_(fmt("embed.%d.lin_proj.weight", bs));
-            a.w_c[r] = h->P_(fmt("pairwise_interaction.%d.lin_proj_pcre.weight", bs));
-            a.edx0[r] = h->edx0[r];
-            a.ep[r] = h->E[r].p;
-            a.eqt[r] = h->E[r].qt;
-            a.edxbar[r] = h->E[r].dxbar;
-            for (int l = 0; l < c.pair_layers; ++l) {
-                a.pp[r][l] = h->P[r][l].p;
-                a.pqt[r][l] = h->P[r][l].qt;
-                a.pdxbar[r][l] = h->P[r][l].dxbar;
-            }
-            a.out_p[r] = want->promoter_feats[r];
-            a.out_c[r] = want->pcre_feats[r];
-            a.L[r] = c.n_bins[r];
-        }
-        a.B = B;
-        a.S = S;
-        a.F = F;
-        a.D = kD;
-        a.nh_e = c.embed_heads;
-        a.nh_p = c.pair_heads;
-        a.n_pl = c.pair_layers;
-        a.rs_e = 1.0f / sqrtf((float)(kD / c.embed_heads));
-        a.rs_p = 1.0f / sqrtf((float)(kD / c.pair_heads));
-        hipLaunchKernelGGL(k_input_grad, dim3(1 + S, B, nres), dim3(kIgThreads), smem, st, a);
-        LAUNCH_CHECK("k_input_grad");
-    }
-    if (any_f) {
-        const int n = B * T * T;
-        hipLaunchKernelGGL(k_dfreq_sum, dim3((n + 255) / 256), dim3(256), 0, st, h->dfreq_part, want->interaction_freq, n, nres);
-        LAUNCH_CHECK("k_dfreq_sum");
-    }
-    return reduce_impl(h, B, st);
-}
-
-// cf_forward(save = 1) + k_attn_maps (cf_attn_maps.h): the attention probabilities the forward kept for the backward pass and the
-// fc_head input, copied into the caller's dense layouts.  Nothing requested: exactly the launches of cf_forward(save = 1).
-extern "C" int cf_attention_maps(cf_handle* h, const cf_batch* bt, float* logits, const cf_attn_maps* want, void* stream) {
-    if (!h) return fail("null handle");
-    const cf_config& c = h->cfg;
-    const int nres = c.n_res;
-    bool any_e = false, any = false;
-    if (want) {
-        for (int r = 0; r < kMaxRes; ++r) {
-            if (r >= nres && (want->embed[r] || want->pairwise[r] || want->regulation[r]))
-                return fail("cf_attention_maps: embed / pairwise / regulation[%d]: the model has %d resolutions", r, nres);
-            any_e |= want->embed[r] != nullptr;
-            any |= want->embed[r] || want->pairwise[r] || want->regulation[r];
-        }
-        any |= want->embedding != nullptr;
-    }
-    if (any_e && h->embed_dense)
-        return fail("cf_attention_maps: embed: attention maps are implemented for embed.n_layers = 1 (the centre-row Embedding); "
-                    "this model has embed.n_layers = %d (the all-rows path keeps no probabilities)", c.embed_layers);
-    if (c.pair_layers > kMapPair || c.reg_layers > kMapReg)
-        return fail("cf_attention_maps: pairwise / regulation: at most %d / %d layers", kMapPair, kMapReg);
-    if (forward_impl(h, bt, logits, 1, stream, nullptr)) return -1;
-    if (!any) return 0;
-    const int B = bt->B;
-    AttnMapArgs a;
-    memset(&a, 0, sizeof a);
-    long long most = want->embedding ? (long long)B * nres * c.d_emb : 0;      // elements of the largest requested output
-    for (int r = 0; r < nres; ++r) {
-        const int L = c.n_bins[r];
-        a.ep[r] = h->E[r].p;
-        for (int l = 0; l < c.pair_layers; ++l) a.pp[r][l] = h->P[r][l].p;
-        for (int l = 0; l < c.reg_layers; ++l) a.rp[r][l] = h->reg_fused ? h->R[r][l].hq : h->R[r][l].p;
-        a.embed[r] = want->embed[r];
-        a.pair[r] = want->pairwise[r];
-        a.reg[r] = want->regulation[r];
-        a.L[r] = L;
-        if (a.embed[r]) most = std::max(most, (long long)B * c.embed_heads * L);
-        if (a.pair[r]) most = std::max(most, (long long)B * c.pair_layers * c.i_max * c.pair_heads * L);
-        if (a.reg[r]) most = std::max(most, (long long)B * c.reg_layers * c.reg_heads * (c.i_max + 1));
-    }
-    a.hin = h->hin;
-    a.emb = want->embedding;
-    a.B = B;
-    a.S = c.i_max;
-    a.T = c.i_max + 1;
-    a.nh_e = c.embed_heads;
-    a.nh_p = c.pair_heads;
-    a.n_pl = c.pair_layers;
-    a.H = c.reg_heads;
-    a.n_rl = c.reg_layers;
-    a.K = nres * c.d_emb;
-    a.reg_fused = h->reg_fused ? 1 : 0;
-    const int gx = (int)std::min<long long>((most + kMapThreads - 1) / kMapThreads, 1024);
-    hipLaunchKernelGGL(k_attn_maps, dim3(gx, kMapSegs), dim3(kMapThreads), 0, (hipStream_t)stream, a);
-    LAUNCH_CHECK("k_attn_maps");
-    ++h->n_fwd;
-    if (h->capturing) h->cap.n_fwd = h->n_fwd;
-    return 0;
-}
-
-// The buffers of cf_pcre_ablation, allocated by its first call (the model's other entry points never need them).
-static int ablate_alloc(cf_handle* h) {
-    if (h->abl_mem) return 0;
-    const cf_config& c = h->cfg;
-    const size_t T = c.i_max + 1, rows = (size_t)c.max_batch * T, x0 = rows * c.d_emb, tt = (size_t)c.max_batch * T * T;
-    const size_t freq_off = c.n_res * x0, mask_off = freq_off + tt;      // (floats; the masks follow as bytes)
-    void* q = nullptr;
-    if (hipMalloc(&q, mask_off * sizeof(float) + c.n_res * tt) != hipSuccess) return fail("cf_pcre_ablation: out of memory");
-    h->abl_mem = q;
-    float* f = (float*)q;
-    for (int r = 0; r < c.n_res; ++r) {
-        h->abl_stash[r] = f + r * x0;
-        h->abl_mask[r] = (uint8_t*)(f + mask_off) + r * tt;
-    }
-    h->abl_freq = f + freq_off;
-    return 0;
-}
-
-// The trunk once on the B genes, k_pcre_stash, then per chunk of at most max_batch of the B * V gene-variants (V = i_max + 2,
-// gene-major) k_pcre_expand and the Regulation + head launches of an inference forward on a batch of that chunk (cf_ablate.h).
-extern "C" int cf_pcre_ablation(cf_handle* h, const cf_batch* bt, float* logits, void* stream) {
-    if (!h) return fail("cf_pcre_ablation: null handle");
-    if (!bt) return fail("cf_pcre_ablation: null batch");
-    if (!logits) return fail("cf_pcre_ablation: null logits");
-    const cf_config& c = h->cfg;
-    if (bt->B > c.max_batch) return fail("cf_pcre_ablation: batch size %d exceeds max_batch=%d", bt->B, c.max_batch);
-    if (check_batch(h, bt)) return -1;
-    if (ablate_alloc(h)) return -1;
-    hipStream_t st = (hipStream_t)stream;
-    const long long launches0 = g_launches;
-    const int B = bt->B, S = c.i_max, T = S + 1, V = S + 2, nres = c.n_res, cap = c.max_batch;
-    const int row4 = T * c.d_emb / 4;
-    if (forward_trunk(h, bt, 0, st)) return -1;
-    AblateStashArgs sa;
-    memset(&sa, 0, sizeof sa);
-    for (int r = 0; r < nres; ++r) {
-        sa.src[r] = reinterpret_cast<const float4*>(h->Rx[r][0]);
-        sa.dst[r] = reinterpret_cast<float4*>(h->abl_stash[r]);
-    }
-    sa.n4 = (long long)B * row4;
-    hipLaunchKernelGGL(k_pcre_stash, dim3((int)std::min<long long>((sa.n4 + kAblThreads - 1) / kAblThreads, 256), nres), dim3(kAblThreads), 0, st, sa);
-    LAUNCH_CHECK("k_pcre_stash");
-    AblateExpandArgs ea;
-    memset(&ea, 0, sizeof ea);
-    cf_batch cb = *bt;      // the chunk's batch: only B, the masks and the frequencies are read past the trunk
-    for (int r = 0; r < nres; ++r) {
-        ea.stash[r] = reinterpret_cast<const float4*>(h->abl_stash[r]);
-        ea.x0[r] = reinterpret_cast<float4*>(h->Rx[r][0]);
-        ea.mask_in[r] = bt->interaction_mask[r];
-        ea.mask_out[r] = h->abl_mask[r];
-        cb.interaction_mask[r] = h->abl_mask[r];
-    }
-    ea.freq_in = bt->interaction_freq;
-    ea.freq_out = h->abl_freq;
-    cb.interaction_freq = h->abl_freq;
-    ea.V = V, ea.S = S, ea.T = T, ea.row4 = row4;
-    for (int g0 = 0; g0 < B * V; g0 += cap) {
-        const int n = std::min(cap, B * V - g0);
-        ea.g0 = g0;
-        hipLaunchKernelGGL(k_pcre_expand, dim3(n, nres), dim3(kAblThreads), 0, st, ea);
-        LAUNCH_CHECK("k_pcre_expand");
-        cb.B = n;
-        if (forward_reg_head(h, &cb, logits + (size_t)g0 * c.n_out, 0, st, nullptr)) return -1;
-    }
-    h->last_fwd_B = 0;
-    h->n_fwd = (int)(g_launches - launches0);
-    if (h->capturing) h->cap.n_fwd = h->n_fwd;
-    return 0;
-}
-
-// The buffers of cf_integrated_gradients, allocated by its first call; the node / weight table grows with n_steps.
-static int intg_alloc(cf_handle* h, int n_steps) {
-    const cf_config& c = h->cfg;
-    const size_t M = c.max_batch, S = c.i_max, T = S + 1, F = c.n_feats;
-    if (!h->intg_mem) {
-        size_t nf = 0, nb = 0;      // floats, then bytes (every float segment a multiple of 4 floats: 16-byte aligned rows)
-        auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
-        for (int r = 0; r < c.n_res; ++r) nf += 2 * up4(M * c.n_bins[r] * F) + 2 * up4(M * S * c.n_bins[r] * F) + up4(M * T * c.d_emb);
-        nf += 2 * up4(M * T * T) + up4(M * c.n_out) + up4(M * kIgSlices);
-        // (the all-rows Embedding reads every row of a full [B, L, L] promoter mask: its chunks keep L rows per chunk row)
-        auto pm_rows = [&](int r) { return h->embed_dense ? (size_t)c.n_bins[r] : (size_t)1; };
-        for (int r = 0; r < c.n_res; ++r) nb += M * pm_rows(r) * c.n_bins[r] + M * S * c.n_bins[r] + M * T * T;
-        void* q = nullptr;
-        if (hipMalloc(&q, nf * sizeof(float) + nb) != hipSuccess) return fail("cf_integrated_gradients: out of memory");
-        h->intg_mem = q;
-        float* f = (float*)q;
-        auto take = [&](size_t n) { float* p = f; f += up4(n); return p; };
-        for (int r = 0; r < c.n_res; ++r) {
-            const size_t L = c.n_bins[r];
-            h->intg_row[r] = take(M * L * F);
-            h->intg_grad[r] = take(M * L * F);
-            h->intg_row[kMaxRes + r] = take(M * S * L * F);
-            h->intg_grad[kMaxRes + r] = take(M * S * L * F);
-            h->intg_stash[r] = take(M * T * c.d_emb);
-        }
-        h->intg_row[2 * kMaxRes] = take(M * T * T);
-        h->intg_grad[2 * kMaxRes] = take(M * T * T);
-        h->intg_logits = take(M * c.n_out);
-        h->intg_part = take(M * kIgSlices);
-        uint8_t* u = (uint8_t*)f;
-        for (int r = 0; r < c.n_res; ++r) {
-            const size_t L = c.n_bins[r];
-            h->intg_pm[r] = u, u += M * pm_rows(r) * L;
-            h->intg_cm[r] = u, u += M * S * L;
-            h->intg_im[r] = u, u += M * T * T;
-        }
-    }
-    if (n_steps > h->intg_cap) {
-        const int cap = std::max(n_steps, 64);
-        if (h->intg_tab) (void)hipFree(h->intg_tab);      // (synchronises: a call in flight may still read the old table)
-        h->intg_tab = nullptr;
-        h->intg_cap = 0;
-        if (hipMalloc(&h->intg_tab, 2 * (size_t)cap * sizeof(float)) != hipSuccess) return fail("cf_integrated_gradients: out of memory");
-        h->intg_cap = cap;
-    }
-    return 0;
-}
-
-// Integrated gradients (cf_ig.h).  General path, per chunk of at most max_batch of the B * V rows: k_ig_expand, the launches of
-// cf_forward(save = 1), backward_impl (head, Regulation, trunk), k_input_grad / k_dfreq_sum into the per-row scratch, k_ig_accumulate;
-// no reduce_impl; k_ig_delta once at the end.  k_attc2 takes as many regions per workgroup as for the caller's B genes (ag_genes),
-// so the chunks run the attention variant model(...) on the batch runs: the result does not depend on max_batch and equals the
-// hand-written loop of grad-enabled model(...) calls on the batch.  Frequency-only path: the trunk once (save = 1, the launches of cf_forward's first part) and its output stashed, then
-// per chunk k_ig_expand (stashed rows, masks, frequencies, dlogits), the Regulation + head forward, backward parts 1 and 2,
-// k_dfreq_sum, k_ig_accumulate.
-extern "C" int cf_integrated_gradients(cf_handle* h, const cf_batch* bt, const cf_ig_opts* o, const cf_input_grads* out,
-                                       float* logits_x, float* logits_base, float* delta, void* stream) {
-    if (!h) return fail("cf_integrated_gradients: null handle");
-    if (!bt) return fail("cf_integrated_gradients: null batch");
-    if (!o) return fail("cf_integrated_gradients: null opts");
-    if (!out) return fail("cf_integrated_gradients: null out");
-    if (!logits_x || !logits_base || !delta) return fail("cf_integrated_gradients: null logits_x / logits_base / delta");
-    const cf_config& c = h->cfg;
-    const int nres = c.n_res, S = c.i_max, T = S + 1, F = c.n_feats, kD = c.d_emb, cap = c.max_batch;
-    if (o->n_steps < 1) return fail("cf_integrated_gradients: n_steps = %d: at least 1 quadrature node", o->n_steps);
-    if (!o->alphas || !o->weights) return fail("cf_integrated_gradients: null alphas / weights");
-    if (o->target < 0 || o->target >= c.n_out) return fail("cf_integrated_gradients: target = %d outside [0, n_out = %d)", o->target, c.n_out);
-    if (o->interpolate & ~(CF_IG_PROMOTER | CF_IG_PCRE | CF_IG_FREQ) || !o->interpolate)
-        return fail("cf_integrated_gradients: interpolate = %d: a non-empty mask of CF_IG_PROMOTER | CF_IG_PCRE | CF_IG_FREQ", o->interpolate);
-    if (bt->B > cap) return fail("cf_integrated_gradients: batch size %d exceeds max_batch=%d", bt->B, cap);
-    const bool ip = o->interpolate & CF_IG_PROMOTER, ic = o->interpolate & CF_IG_PCRE, ifr = o->interpolate & CF_IG_FREQ;
-    for (int r = 0; r < kMaxRes; ++r) {
-        if (r >= nres && (out->promoter_feats[r] || out->pcre_feats[r] || o->base_promoter_feats[r] || o->base_pcre_feats[r]))
-            return fail("cf_integrated_gradients: promoter_feats / pcre_feats[%d]: the model has %d resolutions", r, nres);
-        if (r < nres && (out->promoter_feats[r] != nullptr) != ip)
-            return fail("cf_integrated_gradients: promoter_feats[%d]: the output must be given exactly when promoter_feats is interpolated", r);
-        if (r < nres && (out->pcre_feats[r] != nullptr) != ic)
-            return fail("cf_integrated_gradients: pcre_feats[%d]: the output must be given exactly when pcre_feats is interpolated", r);
-    }
-    if ((out->interaction_freq != nullptr) != ifr)
-        return fail("cf_integrated_gradients: interaction_freq: the output must be given exactly when interaction_freq is interpolated");
-    if (ip && h->embed_dense)
-        return fail("cf_integrated_gradients: promoter_feats: input gradients are implemented for embed.n_layers = 1 (the centre-row Embedding); "
-                    "this model has embed.n_layers = %d (the all-rows path keeps no first-layer input-row gradient)", c.embed_layers);
-    if (ifr && h->reg_fused && !h->reg_dfreq_ok)
-        return fail("cf_integrated_gradients: interaction_freq: the fused Regulation backward variant could not be configured");
-    if (!h->grads) return fail("cf_integrated_gradients: no gradient buffer bound (the backward workspace is set up by cf_bind; the buffer is not written)");
-    if (h->rider.armed || h->rider.done) return fail("cf_integrated_gradients: riders are armed for a training step (cf_rider_arm); finish the step first");
-    if (check_batch(h, bt)) return -1;
-    size_t smem = 0;
-    for (int r = 0; r < nres; ++r) smem = std::max(smem, input_grad_smem(c.n_bins[r], F, kD));
-    if ((ip || ic) && !h->ig_smem_ok) {
-        if (hipFuncSetAttribute((const void*)k_input_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return fail("cf_integrated_gradients: promoter_feats / pcre_feats: k_input_grad needs %zu bytes of LDS", smem);
-        h->ig_smem_ok = true;
-    }
-    if (intg_alloc(h, o->n_steps)) return -1;
-    hipStream_t st = (hipStream_t)stream;
-    const int B = bt->B, n = o->n_steps, V = n + 2, TT = T * T;
-    const bool freq_only = o->interpolate == CF_IG_FREQ && h->intg_trunk_once;
-    HIP_TRY(hipMemcpyAsync(h->intg_tab, o->alphas, n * sizeof(float), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->intg_tab + h->intg_cap, o->weights, n * sizeof(float), hipMemcpyHostToDevice, st));
-    long long n_fwd = 0, n_bwd = 0;
-    IgExpandArgs ea;
-    IgAccArgs aa;
-    memset(&ea, 0, sizeof ea);
-    memset(&aa, 0, sizeof aa);
-    cf_batch cb;      // the chunk's batch: the rows' copies
-    memset(&cb, 0, sizeof cb);
-    for (int r = 0; r < nres; ++r) {
-        const int L = c.n_bins[r];
-        IgSeg* sp = &ea.seg[r];
-        IgSeg* sc = &ea.seg[kMaxRes + r];
-        *sp = IgSeg{bt->promoter_feats[r], o->base_promoter_feats[r], h->intg_row[r], h->intg_grad[r], out->promoter_feats[r], L * F};
-        *sc = IgSeg{bt->pcre_feats[r], o->base_pcre_feats[r], h->intg_row[kMaxRes + r], h->intg_grad[kMaxRes + r], out->pcre_feats[r], S * L * F};
-        // The all-rows Embedding (embed.n_layers > 1) honours a full [B, L, L] promoter mask entry by entry: the chunk rows carry
-        // all L rows of their gene's mask, not the centre row alone (from which only the dataset's not(valid x valid) form can be rebuilt).
-        const bool pm_full = h->embed_dense && bt->promoter_mask_stride[r] == (long long)L * L;
-        ea.pm_rows[r] = pm_full ? L : 1;
-        ea.pm_in[r] = static_cast<const uint8_t*>(bt->promoter_mask_row[r]) - (pm_full ? (size_t)(L / 2) * L : 0);
-        ea.cm_in[r] = bt->pcre_mask_row[r];
-        ea.pm_stride[r] = bt->promoter_mask_stride[r];
-        ea.cm_stride[r] = bt->pcre_mask_stride[r];
-        ea.pm_out[r] = h->intg_pm[r];
-        ea.cm_out[r] = h->intg_cm[r];
-        ea.im_in[r] = bt->interaction_mask[r];
-        ea.im_out[r] = h->intg_im[r];
-        ea.stash[r] = reinterpret_cast<const float4*>(h->intg_stash[r]);
-        ea.x0[r] = reinterpret_cast<float4*>(h->Rx[r][0]);
-        ea.L[r] = L;
-        cb.promoter_feats[r] = h->intg_row[r];
-        cb.pcre_feats[r] = h->intg_row[kMaxRes + r];
-        cb.promoter_mask_row[r] = h->intg_pm[r] + (pm_full ? (size_t)(L / 2) * L : 0);
-        cb.promoter_mask_stride[r] = pm_full ? (long long)L * L : L;
-        cb.pcre_mask_row[r] = h->intg_cm[r];
-        cb.pcre_mask_stride[r] = L;
-        cb.interaction_mask[r] = h->intg_im[r];
-    }
-    ea.seg[2 * kMaxRes] = IgSeg{bt->interaction_freq, o->base_interaction_freq, h->intg_row[2 * kMaxRes], h->intg_grad[2 * kMaxRes], out->interaction_freq, TT};
-    cb.interaction_freq = h->intg_row[2 * kMaxRes];
-    ea.alpha = h->intg_tab;
-    ea.weight = h->intg_tab + h->intg_cap;
-    ea.dlogits = h->dlogits;
-    ea.V = V, ea.S = S, ea.TT = TT, ea.n_out = c.n_out, ea.target = o->target, ea.nres = nres, ea.bcast = o->base_broadcast ? 1 : 0;
-    ea.freq_only = freq_only ? 1 : 0;
-    ea.row4 = T * kD / 4;
-    memcpy(aa.seg, ea.seg, sizeof aa.seg);
-    aa.logits = h->intg_logits;
-    aa.logits_x = logits_x;
-    aa.logits_b = logits_base;
-    aa.part = h->intg_part;
-    aa.V = V, aa.n_out = c.n_out, aa.bcast = ea.bcast;
-    auto run = [&]() -> int {
-        long long l0 = g_launches;
-        if (freq_only) {      // the trunk once on the B genes, its output (the Regulation input) stashed
-            if (forward_trunk(h, bt, 1, st)) return -1;
-            AblateStashArgs sa;
-            memset(&sa, 0, sizeof sa);
-            for (int r = 0; r < nres; ++r) {
-                sa.src[r] = reinterpret_cast<const float4*>(h->Rx[r][0]);
-                sa.dst[r] = reinterpret_cast<float4*>(h->intg_stash[r]);
-            }
-            sa.n4 = (long long)B * ea.row4;
-            hipLaunchKernelGGL(k_pcre_stash, dim3((int)std::min<long long>((sa.n4 + kAblThreads - 1) / kAblThreads, 256), nres), dim3(kAblThreads), 0, st, sa);
-            LAUNCH_CHECK("k_pcre_stash");
-        }
-        n_fwd += g_launches - l0;
-        for (int g0 = 0; g0 < B * V; g0 += cap) {
-            const int nr = std::min(cap, B * V - g0);
-            l0 = g_launches;
-            ea.g0 = g0;
-            hipLaunchKernelGGL(k_ig_expand, dim3(nr, nres), dim3(kIgxThreads), 0, st, ea);
-            LAUNCH_CHECK("k_ig_expand");
-            cb.B = nr;
-            if ((!freq_only && forward_trunk(h, &cb, 1, st)) || forward_reg_head(h, &cb, h->intg_logits, 1, st, nullptr)) return -1;
-            n_fwd += g_launches - l0;
-            l0 = g_launches;
-            h->want_dfreq = ifr ? h->dfreq_part : nullptr;
-            h->skip_dense_embed_bwd = true;
-            if (backward_impl(h, &cb, st, freq_only ? 3 : 7)) return -1;
-            h->want_dfreq = nullptr;
-            h->skip_dense_embed_bwd = false;
-            if (ip || ic) {
-                InGradArgs a;
-                memset(&a, 0, sizeof a);
-                for (int r = 0; r < nres; ++r) {
-                    const int bs = c.binsizes[r];
-                    a.feats_p[r] = cb.promoter_feats[r];
-                    a.feats_c[r] = cb.pcre_feats[r];
-                    a.mask_p[r] = cb.promoter_mask_row[r];
-                    a.mask_c[r] = cb.pcre_mask_row[r];
-                    a.mstride_p[r] = cb.promoter_mask_stride[r];
-                    a.mstride_c[r] = cb.pcre_mask_stride[r];
-                    a.pet[r] = h->pet[r];
-                    a.w_p[r] = h->P_(fmt("embed.%d.lin_proj.weight", bs));
-                    a.w_c[r] = h->P_(fmt("pairwise_interaction.%d.lin_proj_pcre.weight", bs));
-                    a.edx0[r] = h->edx0[r];
-                    a.ep[r] = h->E[r].p;
-                    a.eqt[r] = h->E[r].qt;
-                    a.edxbar[r] = h->E[r].dxbar;
-                    for (int l = 0; l < c.pair_layers; ++l) {
-                        a.pp[r][l] = h->P[r][l].p;
-                        a.pqt[r][l] = h->P[r][l].qt;
-                        a.pdxbar[r][l] = h->P[r][l].dxbar;
-                    }
-                    a.out_p[r] = ip ? h->intg_grad[r] : nullptr;
-                    a.out_c[r] = ic ? h->intg_grad[kMaxRes + r] : nullptr;
-                    a.L[r] = c.n_bins[r];
-                }
-                a.B = nr;
-                a.S = S;
-                a.F = F;
-                a.D = kD;
-                a.nh_e = c.embed_heads;
-                a.nh_p = c.pair_heads;
-                a.n_pl = c.pair_layers;
-                a.rs_e = 1.0f / sqrtf((float)(kD / c.embed_heads));
-                a.rs_p = 1.0f / sqrtf((float)(kD / c.pair_heads));
-                hipLaunchKernelGGL(k_input_grad, dim3(1 + S, nr, nres), dim3(kIgThreads), smem, st, a);
-                LAUNCH_CHECK("k_input_grad");
-            }
-            if (ifr) {
-                const int ne = nr * TT;
-                hipLaunchKernelGGL(k_dfreq_sum, dim3((ne + 255) / 256), dim3(256), 0, st, h->dfreq_part, h->intg_grad[2 * kMaxRes], ne, nres);
-                LAUNCH_CHECK("k_dfreq_sum");
-            }
-            aa.g0 = g0;
-            aa.n = nr;
-            hipLaunchKernelGGL(k_ig_accumulate, dim3((g0 + nr - 1) / V - g0 / V + 1, kIgSlices), dim3(kIgxThreads), 0, st, aa);
-            LAUNCH_CHECK("k_ig_accumulate");
-            n_bwd += g_launches - l0;
-        }
-        l0 = g_launches;
-        hipLaunchKernelGGL(k_ig_delta, dim3((B + 63) / 64), dim3(64), 0, st, h->intg_part, logits_x, logits_base, delta, B, c.n_out, o->target);
-        LAUNCH_CHECK("k_ig_delta");
-        n_bwd += g_launches - l0;
-        return 0;
-    };
-    const bool pend_record = h->pend_record;      // (a step record queued for the next training backward stays queued for it)
-    h->pend_record = false;
-    h->ag_genes = B;
-    const int rc = run();
-    h->ag_genes = 0;
-    h->want_dfreq = nullptr;
-    h->skip_dense_embed_bwd = false;
-    h->pend_record = pend_record;
-    h->last_fwd_B = 0;
-    h->n_fwd = (int)n_fwd;
-    h->n_bwd = (int)n_bwd;
-    return rc ? -1 : 0;
-}
+#include "cf_api_attrib.h"
 
 // ------------------------------------------------------------------------------------
 // hipGraph capture of launch sequences (the per-step sequence is static)
@@ -3094,45 +2599,6 @@ extern "C" int cf_rider_arm(cf_handle* h, float lr, float beta1, float beta2, fl
     h->rider.max_tiles = std::max(0, max_tiles);
     h->rider.step = step;
     h->rider.armed = max_tiles > 0;      // (max_tiles <= 0: disarms; the checks above tell a caller whether riders are available at all)
-    return 0;
-}
-// Split form for callers that replay the optimiser launch from a hipGraph: cf_adamw_set (eager, once per step, before the
-// replay) writes the step's scalars to device memory, cf_adamw_step_dev (capturable) reads them.
-extern "C" int cf_adamw_set(cf_handle* h, float lr, float beta1, float beta2, float eps, float weight_decay, long long step, void* stream) {
-    AdamHyper hy;
-    if (adam_hyper(h, lr, beta1, beta2, eps, weight_decay, step, hy)) return -1;
-    if (h->capturing) return fail("cf_adamw_set must not be captured: its arguments change every step");
-    hipLaunchKernelGGL(k_adamw_set, dim3(1), dim3(1), 0, (hipStream_t)stream, h->hyper, hy);
-    LAUNCH_CHECK("k_adamw_set");
-    return 0;
-}
-extern "C" int cf_adamw_step_dev(cf_handle* h, int buckets, void* stream) {
-    if (!h || !h->params || !h->grads || !h->m || !h->v) return fail("cf_adamw_step: params / grads / moments not bound");
-    long long lo, n4;
-    int grid;
-    if (adam_range(h, buckets, lo, n4, grid)) return -1;
-    if (buckets & CF_BUCKET_PE) h->tiled_pe_fresh = false;
-    h->time_mark("k_adamw", (hipStream_t)stream);
-    hipLaunchKernelGGL(k_adamw_dev, dim3(grid), dim3(256), 0, (hipStream_t)stream, h->params + lo, (const float*)h->grads + lo, h->m + lo,
-                       h->v + lo, n4, (const AdamHyper*)h->hyper);
-    h->time_mark("k_adamw", (hipStream_t)stream);
-    LAUNCH_CHECK("k_adamw_dev");
-    h->n_opt += 1;
-    return 0;
-}
-// `waiter` waits for everything enqueued on `signaller` so far (fork / join of a side stream; under capture this pulls
-// the other stream into the graph as a parallel branch).
-extern "C" int cf_stream_wait(cf_handle* h, void* waiter, void* signaller) {
-    if (!h) return fail("null handle");
-    const size_t slot = h->sync_ev_used++ % 64;           // a small ring: an event is re-recorded long after its waiters passed
-    if (slot >= h->sync_ev.size()) {
-        hipEvent_t ne;
-        HIP_TRY(hipEventCreateWithFlags(&ne, hipEventDisableTiming));
-        h->sync_ev.push_back(ne);
-    }
-    hipEvent_t e = h->sync_ev[slot];
-    HIP_TRY(hipEventRecord(e, (hipStream_t)signaller));
-    HIP_TRY(hipStreamWaitEvent((hipStream_t)waiter, e, 0));
     return 0;
 }
 // The fused optimiser (cf_reduce_opt_part over the Embedding + Pairwise bucket) can keep the tiled copies of that bucket's weights fresh: its
@@ -3461,579 +2927,7 @@ extern "C" int cf_record_step_bwd(cf_handle* h, const int* cursor, const float* 
     return 0;
 }
 
-// ------------------------------------------------------------------------------------
-// standalone operators
-// ------------------------------------------------------------------------------------
-extern "C" int cf_op_linear(const float* A, const float* W, const float* bias, float* C, int M, int N, int K, int relu, void* stream) {
-    if (K % 128 || N % 32) return fail("cf_op_linear: K %% 128 == 0 and N %% 32 == 0 required");
-    // standalone use: build the tiled copy of W on the fly (test / micro-benchmark helper, synchronous)
-    std::vector<RetileUnit> units;
-    for (int n0 = 0; n0 < N; n0 += 16) units.push_back(RetileUnit{(long long)n0 * K, 0, K, N, n0, 0});
-    float* Wt = nullptr;
-    RetileUnit* du = nullptr;
-    HIP_TRY(hipMalloc(&Wt, (size_t)N * K * sizeof(float)));
-    HIP_TRY(hipMalloc(&du, units.size() * sizeof(RetileUnit)));
-    HIP_TRY(hipMemcpy(du, units.data(), units.size() * sizeof(RetileUnit), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_retile, dim3((int)units.size()), dim3(256), 0, (hipStream_t)stream, W, Wt, (float*)nullptr, (const RetileUnit*)du);
-    LinArgs a;
-    memset(&a, 0, sizeof a);
-    a.x[0] = A;
-    a.w[0] = Wt;
-    a.b[0] = bias;
-    a.y[0] = C;
-    a.xmap = identity_map();
-    a.ldx = K;
-    a.ldy = N;
-    a.N = M;
-    a.K = K;
-    a.Nout = N;
-    a.relu = relu;
-    hipLaunchKernelGGL((k_linear_fwd<2>), dim3(tiles_of(M), (N + 127) / 128, 1), dim3(256), 0, (hipStream_t)stream, a);
-    LAUNCH_CHECK("cf_op_linear");
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    HIP_TRY(hipFree(Wt));
-    HIP_TRY(hipFree(du));
-    return 0;
-}
-extern "C" int cf_op_dgrad(const float* dY, const float* W, float* dX, int M, int N, int K, void* stream) {
-    if ((N != 128 && N != 256 && N != 1024) || K % 32) return fail("cf_op_dgrad: N in {128, 256, 1024} and K %% 32 == 0 required");
-    DgradArgs a;
-    memset(&a, 0, sizeof a);
-    a.dy[0] = dY;
-    a.lddy = N;
-    a.w[0] = W;
-    a.ldw = K;
-    a.rmap = identity_map();
-    a.dx[0] = dX;
-    a.lddx = K;
-    a.N = M;
-    a.K = N;
-    a.Ncols = K;
-    const dim3 grid(tiles_of(M), K / 32, 1);
-    if (N == 128) hipLaunchKernelGGL((k_dgrad<2>), grid, dim3(256), 0, (hipStream_t)stream, a);
-    else if (N == 256) hipLaunchKernelGGL((k_dgrad<4>), grid, dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((k_dgrad<16>), grid, dim3(256), 0, (hipStream_t)stream, a);
-    LAUNCH_CHECK("cf_op_dgrad");
-    return 0;
-}
-extern "C" int cf_op_wgrad(const float* dY, const float* X, float* dW, int M, int N, int K, void* stream) {
-    if (K % 4) return fail("cf_op_wgrad: K %% 4 == 0 required");
-    std::vector<WgTile> tiles;
-    push_wg(tiles, wg1(dY, N, X, K, M, dW, K, N, K));
-    WgTile* d = nullptr;
-    HIP_TRY(hipMalloc(&d, tiles.size() * sizeof(WgTile)));
-    HIP_TRY(hipMemcpy(d, tiles.data(), tiles.size() * sizeof(WgTile), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_wgrad, dim3(xcd_grid((int)tiles.size())), dim3(256), 0, (hipStream_t)stream, (const WgTile*)d, (int)tiles.size(), 1, 0);
-    LAUNCH_CHECK("cf_op_wgrad");
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    HIP_TRY(hipFree(d));
-    return 0;
-}
-
-static int attn_args(const cf_attn_shape* sh, AttnArgs& a) {
-    if (!sh) return fail("cf_op_attention: null shape");
-    if (sh->N < 1 || sh->H < 1 || sh->Lq < 1 || sh->Lk < 1) return fail("cf_op_attention: bad shape");
-    if (sh->N > 65535 || sh->H > 65535) return fail("cf_op_attention: N and H are grid dimensions (<= 65535)");
-    if ((sh->ldq | sh->ldk | sh->ldv | sh->ldo) & 3) return fail("cf_op_attention: row strides must be multiples of 4 floats");
-    if (sh->ldq < sh->H * kADh || sh->ldk < sh->H * kADh || sh->ldv < sh->H * kADh || sh->ldo < sh->H * kADh)
-        return fail("cf_op_attention: row stride smaller than H * 64");
-    memset(&a, 0, sizeof a);
-    a.N = sh->N;
-    a.H = sh->H;
-    a.Lq = sh->Lq;
-    a.Lk = sh->Lk;
-    a.ldq = sh->ldq;
-    a.ldk = sh->ldk;
-    a.ldv = sh->ldv;
-    a.ldo = sh->ldo;
-    a.rscale = 1.0f / sqrtf((float)kADh);
-    return 0;
-}
-// The dense attention forward: k_attn_fwd (round 5: transposed score tiles, 128 query rows per workgroup); CF_ATTN_FWD_V1=1 runs the round-1
-// kernel (64 rows per workgroup, P through a per-wave LDS patch) -- the cross-check of the tests.  Same results up to the order of the fp32
-// additions inside P V.
-static int attn_fwd_launch(const AttnArgs& a, hipStream_t st) {
-    if (getenv_int("CF_ATTN_FWD_V1", 0)) {
-        hipLaunchKernelGGL(k_attn_fwd_v1, dim3((a.Lq + kABq - 1) / kABq, a.H, a.N), dim3(256), 0, st, a);
-        LAUNCH_CHECK("k_attn_fwd_v1");
-        return 0;
-    }
-    const dim3 grid((a.Lq + kABq2 - 1) / kABq2, a.H, a.N);
-    if (a.mask) hipLaunchKernelGGL(k_attn_fwd<true>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_attn_fwd<false>, grid, dim3(256), 0, st, a);
-    LAUNCH_CHECK("k_attn_fwd");
-    return 0;
-}
-extern "C" int cf_op_attention_fwd(const cf_attn_shape* sh, const float* q, const float* k, const float* v, const unsigned char* qvalid,
-                                   const unsigned char* kvalid, const unsigned char* mask, float* o, float* stats, void* stream) {
-    AttnArgs a;
-    if (attn_args(sh, a)) return -1;
-    if (!q || !k || !v || !o) return fail("cf_op_attention_fwd: null tensor");
-    a.q = q;
-    a.k = k;
-    a.v = v;
-    a.qvalid = qvalid;
-    a.kvalid = kvalid;
-    a.mask = mask;
-    a.o = o;
-    a.stats = stats;
-    if (attn_fwd_launch(a, (hipStream_t)stream)) return -1;
-    return 0;
-}
-// dQ, dK, dV of the dense attention core (delta = rowsum(dO * O) is in a.delta already).  One fused pass per (sequence, head)
-// (k_attn_bwd: 5 tile products per key / query tile pair) when the launch has enough (sequence, head) workgroups to fill the chip;
-// otherwise the two kernels split by output owner (7 products per pair, but (Lk / 64 + Lq / 64) workgroups per sequence and head).
-// CF_ATTN_BWD_SPLIT=1 forces the split kernels, -1 the fused one (A/B runs, cross-checks in the tests; read at every call).  Same
-// results either way up to the order of the fp32 additions inside dQ.
-static int attn_bwd_launch(const AttnArgs& a, hipStream_t st) {
-    const int mode = getenv_int("CF_ATTN_BWD_SPLIT", 0);
-    const bool vec_ok = (a.ldq & 3) == 0 && (reinterpret_cast<uintptr_t>(a.dq) & 15) == 0;      // (the dQ update is 16 bytes per lane)
-    if (vec_ok && (mode < 0 || (mode == 0 && (long long)a.N * a.H >= 512))) {
-        // round 6: 128 keys per pass, eight waves, 141 KB of dynamic LDS (k_attn_bwd2); CF_ATTN_BWD_V1=1 runs the 64-key kernel of rounds 4-5 (the
-        // cross-check of the tests: same results up to the order of the fp32 additions inside dQ)
-        const bool v2_ok = ((reinterpret_cast<uintptr_t>(a.dk) | reinterpret_cast<uintptr_t>(a.dv)) & 15) == 0 && getenv_int("CF_ATTN_BWD_V1", 0) == 0;
-        if (v2_ok) {
-            static int ready = 0;      // 0: not tried, 1: attribute set, -1: refused by the runtime (fall through to the 64-key kernel)
-            if (ready == 0) {
-                hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_bwd2<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAB2Smem);
-                hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_bwd2<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAB2Smem);
-                ready = (e1 == hipSuccess && e2 == hipSuccess) ? 1 : -1;
-                if (ready < 0) (void)hipGetLastError();
-            }
-            if (ready > 0) {
-                if (a.mask) hipLaunchKernelGGL(k_attn_bwd2<true>, dim3(a.H, a.N), dim3(512), kAB2Smem, st, a);
-                else hipLaunchKernelGGL(k_attn_bwd2<false>, dim3(a.H, a.N), dim3(512), kAB2Smem, st, a);
-                LAUNCH_CHECK("k_attn_bwd2");
-                return 0;
-            }
-        }
-        hipLaunchKernelGGL(k_attn_bwd, dim3(a.H, a.N), dim3(256), 0, st, a);
-        LAUNCH_CHECK("k_attn_bwd");
-        return 0;
-    }
-    hipLaunchKernelGGL(k_attn_bwd_kv, dim3((a.Lk + kABk - 1) / kABk, a.H, a.N), dim3(256), 0, st, a);
-    LAUNCH_CHECK("k_attn_bwd_kv");
-    hipLaunchKernelGGL(k_attn_bwd_q, dim3((a.Lq + kABq - 1) / kABq, a.H, a.N), dim3(256), 0, st, a);
-    LAUNCH_CHECK("k_attn_bwd_q");
-    return 0;
-}
-extern "C" int cf_op_attention_bwd(const cf_attn_shape* sh, const float* q, const float* k, const float* v, const unsigned char* qvalid,
-                                   const unsigned char* kvalid, const unsigned char* mask, const float* o, const float* stats,
-                                   const float* d_o, float* dq, float* dk, float* dv, float* delta_ws, void* stream) {
-    AttnArgs a;
-    if (attn_args(sh, a)) return -1;
-    if (!q || !k || !v || !o || !stats || !d_o || !dq || !dk || !dv || !delta_ws) return fail("cf_op_attention_bwd: null tensor");
-    a.q = q;
-    a.k = k;
-    a.v = v;
-    a.qvalid = qvalid;
-    a.kvalid = kvalid;
-    a.mask = mask;
-    a.o = const_cast<float*>(o);
-    a.stats = const_cast<float*>(stats);
-    a.d_o = d_o;
-    a.dq = dq;
-    a.dk = dk;
-    a.dv = dv;
-    a.delta = delta_ws;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_attn_delta, dim3((a.Lq + 15) / 16, a.H, a.N), dim3(256), 0, st, a);
-    LAUNCH_CHECK("k_attn_delta");
-    if (attn_bwd_launch(a, st)) return -1;
-    return 0;
-}
-
-static_assert(sizeof(cf_bin_job) == sizeof(BinJob), "cf_bin_job layout");
-extern "C" int cf_bin_regions(const cf_bin_job* jobs, int n_jobs, int n_feats, int bin_size, int n_bins_out, void* stream) {
-    if (!jobs) return fail("cf_bin_regions: null job table");
-    if (n_jobs < 0 || n_feats < 1 || n_feats > 64 || bin_size < 1 || n_bins_out < 1) return fail("cf_bin_regions: bad argument");
-    if (n_jobs == 0) return 0;
-    hipLaunchKernelGGL(k_bin_regions, dim3(n_jobs), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const BinJob*>(jobs), n_feats,
-                       bin_size, n_bins_out);
-    LAUNCH_CHECK("k_bin_regions");
-    return 0;
-}
-
-static_assert(sizeof(cf_bin_job_multi) == sizeof(BinJobMulti), "cf_bin_job_multi layout");
-extern "C" int cf_bin_regions_multi(const cf_bin_job_multi* jobs, int n_jobs, int n_feats, int n_res, const int* bin_sizes, const int* n_bins_out,
-                                    int max_cols, void* stream) {
-    if (!jobs || !bin_sizes || !n_bins_out) return fail("cf_bin_regions_multi: null argument");
-    if (n_jobs < 0 || n_feats < 1 || n_feats > 64 || n_res < 1 || n_res > kBinMaxRes || max_cols < 0) return fail("cf_bin_regions_multi: bad argument");
-    if (n_jobs == 0) return 0;
-    BinPlan pl;
-    memset(&pl, 0, sizeof pl);
-    pl.n_res = n_res;
-    pl.F = n_feats;
-    for (int r = 0; r < n_res; ++r) {
-        if (bin_sizes[r] < 1 || n_bins_out[r] < 1 || n_bins_out[r] > kBinMaxBins) return fail("cf_bin_regions_multi: bad bin size / bin count at resolution %d", r);
-        if (r && bin_sizes[r] >= bin_sizes[r - 1]) return fail("cf_bin_regions_multi: bin sizes must be listed coarsest first (%d after %d)", bin_sizes[r], bin_sizes[r - 1]);
-        pl.b[r] = bin_sizes[r];
-        pl.L[r] = n_bins_out[r];
-    }
-    // one pass over the raw bytes when the bins nest and a unit (one coarsest bin) fits a wave's registers and lanes
-    bool nested = n_res >= 2 && n_feats <= kBinMaxF && (pl.b[n_res - 1] & 3) == 0 && pl.b[0] <= kBinMaxLoads * 256 && pl.b[0] / pl.b[n_res - 1] <= 64;
-    for (int r = 0; r + 1 < n_res; ++r) nested = nested && pl.b[r] % pl.b[r + 1] == 0;
-    pl.nested = nested ? 1 : 0;
-    const int units = nested ? std::max(1, (max_cols + pl.b[0] - 1) / pl.b[0]) : 1;
-    const dim3 grid((units + 3) / 4, n_jobs);
-    const int nload = nested ? (pl.b[0] / 4 + 63) / 64 : 4;
-    const BinJobMulti* jm = reinterpret_cast<const BinJobMulti*>(jobs);
-    if (nload <= 4) hipLaunchKernelGGL(k_bin_multi<4>, grid, dim3(256), 0, (hipStream_t)stream, jm, pl);
-    else if (nload <= 8) hipLaunchKernelGGL(k_bin_multi<8>, grid, dim3(256), 0, (hipStream_t)stream, jm, pl);
-    else hipLaunchKernelGGL(k_bin_multi<16>, grid, dim3(256), 0, (hipStream_t)stream, jm, pl);
-    LAUNCH_CHECK("k_bin_multi");
-    return 0;
-}
-
-static_assert(sizeof(cf_bin_grad_job) == sizeof(BinGradJob) && sizeof(cf_bin_grad_job) == 72, "cf_bin_grad_job layout");
-extern "C" int cf_bin_regions_multi_backward(const cf_bin_grad_job* jobs, int n_jobs, int n_feats, int n_res, const int* bin_sizes,
-                                             const int* n_bins_out, int max_cols, int times_input, void* stream) {
-    if (!jobs || !bin_sizes || !n_bins_out) return fail("cf_bin_regions_multi_backward: null argument");
-    if (n_jobs < 0 || n_feats < 1 || n_feats > 64 || n_res < 1 || n_res > kBinMaxRes || max_cols < 0) return fail("cf_bin_regions_multi_backward: bad argument");
-    if (n_jobs == 0) return 0;
-    BinPlan pl;
-    memset(&pl, 0, sizeof pl);
-    pl.n_res = n_res;
-    pl.F = n_feats;
-    for (int r = 0; r < n_res; ++r) {
-        if (bin_sizes[r] < 1 || n_bins_out[r] < 1 || n_bins_out[r] > kBinMaxBins) return fail("cf_bin_regions_multi_backward: bad bin size / bin count at resolution %d", r);
-        if (r && bin_sizes[r] >= bin_sizes[r - 1]) return fail("cf_bin_regions_multi_backward: bin sizes must be listed coarsest first (%d after %d)", bin_sizes[r], bin_sizes[r - 1]);
-        pl.b[r] = bin_sizes[r];
-        pl.L[r] = n_bins_out[r];
-    }
-    {   // this call WRITES through the job table: rows shorter than the window would overlap.  The table is read back (72 bytes per region,
-        // stream-ordered, one synchronisation) -- an attribution call, not a step of a training loop
-        std::vector<cf_bin_grad_job> host((size_t)n_jobs);
-        if (hipMemcpyAsync(host.data(), jobs, sizeof(cf_bin_grad_job) * (size_t)n_jobs, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
-            hipStreamSynchronize((hipStream_t)stream) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail("cf_bin_regions_multi_backward: the job table could not be read back (it must be a device array of n_jobs records)");
-        }
-        for (int k = 0; k < n_jobs; ++k) {
-            if (host[k].ncols < 0 || host[k].ncols > max_cols) return fail("cf_bin_regions_multi_backward: ncols = %d of job %d outside [0, max_cols = %d]", host[k].ncols, k, max_cols);
-            if (host[k].ld_out < host[k].ncols) return fail("cf_bin_regions_multi_backward: ld_out = %lld < ncols = %d in job %d", host[k].ld_out, host[k].ncols, k);
-            if (host[k].ncols > 0 && (!host[k].raw || !host[k].draw)) return fail("cf_bin_regions_multi_backward: null raw / draw in job %d", k);
-        }
-    }
-    bool nested = n_res >= 2 && n_feats <= kBinMaxF && (pl.b[n_res - 1] & 3) == 0 && pl.b[0] <= kBinMaxLoads * 256 && pl.b[0] / pl.b[n_res - 1] <= 64;
-    for (int r = 0; r + 1 < n_res; ++r) nested = nested && pl.b[r] % pl.b[r + 1] == 0;
-    pl.nested = nested ? 1 : 0;
-    const int units = nested ? std::max(1, (max_cols + pl.b[0] - 1) / pl.b[0]) : 1;
-    const dim3 grid((units + 3) / 4, n_jobs);
-    const int nload = nested ? (pl.b[0] / 4 + 63) / 64 : 4;
-    const BinGradJob* jm = reinterpret_cast<const BinGradJob*>(jobs);
-    const int times = times_input ? 1 : 0;
-    if (nload <= 4) hipLaunchKernelGGL(k_bin_multi_bwd<4>, grid, dim3(256), 0, (hipStream_t)stream, jm, pl, times);
-    else if (nload <= 8) hipLaunchKernelGGL(k_bin_multi_bwd<8>, grid, dim3(256), 0, (hipStream_t)stream, jm, pl, times);
-    else hipLaunchKernelGGL(k_bin_multi_bwd<16>, grid, dim3(256), 0, (hipStream_t)stream, jm, pl, times);
-    LAUNCH_CHECK("k_bin_multi_bwd");
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------
-// dense (all rows) layer: projections -> attention core -> out-projection / LN / FFN / LN chain, and its backward
-// ------------------------------------------------------------------------------------
-namespace {
-struct DenseWs {       // workspace layout in floats; `train` adds what the backward pass needs
-    long long wq_t, wkv_t, wo_t, w1_t, w2_t, q, kv, o, tab;                                  // forward
-    long long stats, xh1, rs1, y1, hdn, xh2, rs2;                                             // saved
-    long long dt2, dpre1, dt1, da, dq, dkv, delta, partial, wpart;                           // backward
-    long long total;
-    int splits;
-};
-constexpr int kDenseTab = 16384;        // floats reserved for the unit / tile tables
-constexpr int kDenseSplitRows = 4096;   // reduction rows per split-K chunk of the weight gradients
-DenseWs dense_ws(int N, int Lq, int Lk, int dff, bool train) {
-    const long long rq = (long long)N * Lq, rk = (long long)N * Lk;
-    DenseWs w;
-    long long o = 0;
-    auto take = [&](long long n) {
-        const long long at = o;
-        o += (n + 3) / 4 * 4;
-        return at;
-    };
-    w.wq_t = take(128 * 128);
-    w.wkv_t = take(256 * 128);
-    w.wo_t = take(128 * 128);
-    w.w1_t = take((long long)dff * 128);
-    w.w2_t = take((long long)128 * dff);
-    w.q = take(rq * 128);
-    w.kv = take(rk * 256);
-    w.o = take(rq * 128);
-    w.tab = take(kDenseTab);
-    w.splits = 0;
-    if (train) {
-        const long long tiles = (rq + kTile - 1) / kTile;
-        w.stats = take((long long)N * 2 * Lq * 2);
-        w.xh1 = take(rq * 128);
-        w.rs1 = take(rq);
-        w.y1 = take(rq * 128);
-        w.hdn = take(rq * dff);
-        w.xh2 = take(rq * 128);
-        w.rs2 = take(rq);
-        w.dt2 = take(rq * 128);
-        w.dpre1 = take(rq * dff);
-        w.dt1 = take(rq * 128);
-        w.da = take(rq * 128);
-        w.dq = take(rq * 128);
-        w.dkv = take(rk * 256);
-        w.delta = take((long long)N * 2 * Lq);
-        w.partial = take(tiles * post_partial_width(dff));
-        w.splits = (int)((std::max(rq, rk) + kDenseSplitRows - 1) / kDenseSplitRows);
-        w.wpart = take((long long)w.splits * 256 * 128);        // the largest weight is 256 x 128 (or 128 x 256)
-    }
-    w.total = o;
-    return w;
-}
-}  // namespace
-
-extern "C" long long cf_op_dense_layer_workspace(int N, int Lq, int Lk, int d_ff) { return dense_ws(N, Lq, Lk, d_ff, false).total; }
-extern "C" long long cf_op_dense_layer_train_workspace(int N, int Lq, int Lk, int d_ff) { return dense_ws(N, Lq, Lk, d_ff, true).total; }
-
-static int dense_layer_fwd(const cf_dense_layer* w, const float* x_q, const float* x_kv, const unsigned char* qvalid, const unsigned char* kvalid,
-                           const unsigned char* mask, int N, int Lq, int Lk, float* y, float* ws, bool train, hipStream_t st) {
-    if (!w || !x_q || !x_kv || !y || !ws) return fail("cf_op_dense_layer_fwd: null argument");
-    if (w->d_ff != 128 && w->d_ff != 256) return fail("cf_op_dense_layer_fwd: d_ff must be 128 or 256");
-    if (N < 1 || Lq < 1 || Lk < 1 || N > 65535) return fail("cf_op_dense_layer_fwd: bad shape");
-    const int dff = w->d_ff;
-    const long long rq = (long long)N * Lq, rk = (long long)N * Lk;
-    if (rq > 0x7fffffffLL / 256 || rk > 0x7fffffffLL / 256) return fail("cf_op_dense_layer_fwd: too many rows");
-    const DenseWs L = dense_ws(N, Lq, Lk, dff, train);
-    // tiled copies of the five weights (no table: workgroup b of a launch takes rows 16 b .. of its matrix)
-    struct Job { const float* src; float* dst; int rows, K; } jobs[5] = {{w->wq, ws + L.wq_t, 128, 128}, {w->wkv, ws + L.wkv_t, 256, 128},
-                                                                         {w->wo, ws + L.wo_t, 128, 128}, {w->w1, ws + L.w1_t, dff, 128},
-                                                                         {w->w2, ws + L.w2_t, 128, dff}};
-    for (int j = 0; j < 5; ++j) {
-        hipLaunchKernelGGL(k_retile_rows, dim3(jobs[j].rows / 16), dim3(256), 0, st, jobs[j].src, jobs[j].dst, jobs[j].K);
-        LAUNCH_CHECK("k_retile_rows<dense layer>");
-    }
-    auto linear = [&](const float* x, const float* wt, float* out, long long rows, int nout) {
-        LinArgs a;
-        memset(&a, 0, sizeof a);
-        a.x[0] = x;
-        a.w[0] = wt;
-        a.y[0] = out;
-        a.xmap = identity_map();
-        a.ldx = 128;
-        a.ldy = nout;
-        a.N = (int)rows;
-        a.K = 128;
-        a.Nout = nout;
-        hipLaunchKernelGGL((k_linear_fwd<2>), dim3(tiles_of((int)rows), (nout + 127) / 128, 1), dim3(256), 0, st, a);
-    };
-    linear(x_q, ws + L.wq_t, ws + L.q, rq, 128);
-    LAUNCH_CHECK("k_linear_fwd<q>");
-    linear(x_kv, ws + L.wkv_t, ws + L.kv, rk, 256);
-    LAUNCH_CHECK("k_linear_fwd<kv>");
-    {
-        AttnArgs a;
-        cf_attn_shape sh = {N, 2, Lq, Lk, 128, 256, 256, 128};
-        if (attn_args(&sh, a)) return -1;
-        a.q = ws + L.q;
-        a.k = ws + L.kv;
-        a.v = ws + L.kv + 128;
-        a.qvalid = qvalid;
-        a.kvalid = kvalid;
-        a.mask = mask;
-        a.o = ws + L.o;
-        a.stats = train ? ws + L.stats : nullptr;
-        if (attn_fwd_launch(a, st)) return -1;
-    }
-    {
-        PostArgs p;
-        memset(&p, 0, sizeof p);
-        p.x[0] = x_q;
-        p.xmap = identity_map();
-        p.ain[0] = ws + L.o;
-        p.wo[0] = ws + L.wo_t;
-        p.bo[0] = w->bo;
-        p.g1[0] = w->ln1_g;
-        p.be1[0] = w->ln1_b;
-        p.w1[0] = ws + L.w1_t;
-        p.b1[0] = w->b1;
-        p.w2[0] = ws + L.w2_t;
-        p.b2[0] = w->b2;
-        p.g2[0] = w->ln2_g;
-        p.be2[0] = w->ln2_b;
-        if (train) {
-            p.xh1[0] = ws + L.xh1;
-            p.rs1[0] = ws + L.rs1;
-            p.y1[0] = ws + L.y1;
-            p.hdn[0] = ws + L.hdn;
-            p.xh2[0] = ws + L.xh2;
-            p.rs2[0] = ws + L.rs2;
-        }
-        p.out[0] = y;
-        p.omap = identity_map();
-        p.N = (int)rq;
-        p.save = train ? 1 : 0;
-        launch_post_fwd<false, 128>(dff, dim3(tiles_of((int)rq), 1), st, p);
-        LAUNCH_CHECK("k_post_fwd<dense layer>");
-    }
-    return 0;
-}
-extern "C" int cf_op_dense_layer_fwd(const cf_dense_layer* w, const float* x_q, const float* x_kv, const unsigned char* qvalid,
-                                     const unsigned char* kvalid, const unsigned char* mask, int N, int Lq, int Lk, float* y, float* ws,
-                                     void* stream) {
-    return dense_layer_fwd(w, x_q, x_kv, qvalid, kvalid, mask, N, Lq, Lk, y, ws, false, (hipStream_t)stream);
-}
-extern "C" int cf_op_dense_layer_fwd_train(const cf_dense_layer* w, const float* x_q, const float* x_kv, const unsigned char* qvalid,
-                                           const unsigned char* kvalid, const unsigned char* mask, int N, int Lq, int Lk, float* y, float* ws,
-                                           void* stream) {
-    return dense_layer_fwd(w, x_q, x_kv, qvalid, kvalid, mask, N, Lq, Lk, y, ws, true, (hipStream_t)stream);
-}
-
-// dW[N_, K_] = dY^T X over `rows` rows: split-K over chunks of kDenseSplitRows rows (one k_wgrad tile per (n0, k0, chunk), partial
-// results in `part`), then a column sum over the chunks.  Fixed order: deterministic.
-static int dense_wgrad(const float* dY, int lddy, const float* X, int ldx, long long rows, float* dW, int N_, int K_, float* part,
-                       WgTile* tiles_d, CsTile* cs_d, hipStream_t st) {
-    const int splits = (int)((rows + kDenseSplitRows - 1) / kDenseSplitRows);
-    const int ntiles = ((N_ + 63) / 64) * ((K_ + kWgTk - 1) / kWgTk) * splits, ncs = (N_ * K_ + 63) / 64;
-    if ((size_t)ntiles * sizeof(WgTile) > (size_t)(kDenseTab / 2) * sizeof(float) * 64 || (size_t)ncs * sizeof(CsTile) > (size_t)(kDenseTab / 2) * sizeof(float) * 64)
-        return fail("cf_op_dense_layer_bwd: tile table overflow");
-    DenseWgTab tb{dY, X, part, dW, tiles_d, cs_d, rows, lddy, ldx, N_, K_, splits, kDenseSplitRows};
-    hipLaunchKernelGGL(k_dense_wg_tables, dim3(std::max(1, std::min(64, (ntiles + 255) / 256))), dim3(256), 0, st, tb);
-    LAUNCH_CHECK("k_dense_wg_tables");
-    hipLaunchKernelGGL(k_wgrad, dim3(xcd_grid(ntiles)), dim3(256), 0, st, (const WgTile*)tiles_d, ntiles, 1, 0);
-    LAUNCH_CHECK("k_wgrad<dense layer>");
-    hipLaunchKernelGGL(k_colsum, dim3(ncs), dim3(256), 0, st, (const CsTile*)cs_d, 1);
-    LAUNCH_CHECK("k_colsum<dense layer>");
-    return 0;
-}
-
-extern "C" int cf_op_dense_layer_bwd(const cf_dense_layer* w, const float* x_q, const float* x_kv, const unsigned char* qvalid,
-                                     const unsigned char* kvalid, const unsigned char* mask, int N, int Lq, int Lk, const float* dy,
-                                     float* dx_q, float* dx_kv, const cf_dense_layer_grads* g, float* ws, float* tables, void* stream) {
-    if (!w || !x_q || !x_kv || !dy || !dx_q || !dx_kv || !g || !ws || !tables) return fail("cf_op_dense_layer_bwd: null argument");
-    if (w->d_ff != 128 && w->d_ff != 256) return fail("cf_op_dense_layer_bwd: d_ff must be 128 or 256");
-    hipStream_t st = (hipStream_t)stream;
-    const int dff = w->d_ff;
-    const long long rq = (long long)N * Lq, rk = (long long)N * Lk;
-    const DenseWs L = dense_ws(N, Lq, Lk, dff, true);
-    const int tiles_q = tiles_of((int)rq);
-    {   // out-projection / LN / FFN / LN chain
-        PostBwdArgs p;
-        memset(&p, 0, sizeof p);
-        p.dout[0] = dy;
-        p.dmap = identity_map();
-        p.xh2[0] = ws + L.xh2;
-        p.rs2[0] = ws + L.rs2;
-        p.g2[0] = w->ln2_g;
-        p.hdn[0] = ws + L.hdn;
-        p.w2[0] = w->w2;
-        p.w1[0] = w->w1;
-        p.xh1[0] = ws + L.xh1;
-        p.rs1[0] = ws + L.rs1;
-        p.g1[0] = w->ln1_g;
-        p.wo[0] = w->wo;
-        p.dt2[0] = ws + L.dt2;
-        p.dpre1[0] = ws + L.dpre1;
-        p.dt1[0] = ws + L.dt1;
-        p.da[0] = ws + L.da;
-        p.partial[0] = ws + L.partial;
-        p.N = (int)rq;
-        launch_post_bwd<false, 128>(dff, dim3(tiles_q, 1), st, p);
-        LAUNCH_CHECK("k_post_bwd<dense layer>");
-    }
-    {   // attention core
-        AttnArgs a;
-        cf_attn_shape sh = {N, 2, Lq, Lk, 128, 256, 256, 128};
-        if (attn_args(&sh, a)) return -1;
-        a.q = ws + L.q;
-        a.k = ws + L.kv;
-        a.v = ws + L.kv + 128;
-        a.qvalid = qvalid;
-        a.kvalid = kvalid;
-        a.mask = mask;
-        a.o = ws + L.o;
-        a.stats = ws + L.stats;
-        a.d_o = ws + L.da;
-        a.dq = ws + L.dq;
-        a.dk = ws + L.dkv;
-        a.dv = ws + L.dkv + 128;
-        a.delta = ws + L.delta;
-        hipLaunchKernelGGL(k_attn_delta, dim3((Lq + 15) / 16, 2, N), dim3(256), 0, st, a);
-        LAUNCH_CHECK("k_attn_delta");
-        if (attn_bwd_launch(a, st)) return -1;
-    }
-    {   // input gradients: dx_q = dt1 (residual) + dq Wq;  dx_kv = dkv Wkv
-        DgradArgs d;
-        memset(&d, 0, sizeof d);
-        d.dy[0] = ws + L.dq;
-        d.lddy = 128;
-        d.w[0] = w->wq;
-        d.ldw = 128;
-        d.res[0] = ws + L.dt1;
-        d.rmap = identity_map();
-        d.ldres = 128;
-        d.dx[0] = dx_q;
-        d.lddx = 128;
-        d.N = (int)rq;
-        d.K = 128;
-        d.Ncols = 128;
-        hipLaunchKernelGGL((k_dgrad<2>), dim3(tiles_q, 128 / 32, 1), dim3(256), 0, st, d);
-        LAUNCH_CHECK("k_dgrad<q>");
-        memset(&d, 0, sizeof d);
-        d.dy[0] = ws + L.dkv;
-        d.lddy = 256;
-        d.w[0] = w->wkv;
-        d.ldw = 128;
-        d.rmap = identity_map();
-        d.dx[0] = dx_kv;
-        d.lddx = 128;
-        d.N = (int)rk;
-        d.K = 256;
-        d.Ncols = 128;
-        hipLaunchKernelGGL((k_dgrad<4>), dim3(tiles_of((int)rk), 128 / 32, 1), dim3(256), 0, st, d);
-        LAUNCH_CHECK("k_dgrad<kv>");
-    }
-    // weight gradients (split-K), bias / LayerNorm gradients (column sums of the per-tile partials)
-    WgTile* tiles_d = reinterpret_cast<WgTile*>(tables);
-    CsTile* cs_d = reinterpret_cast<CsTile*>(tables + (size_t)(kDenseTab / 2) * 64);
-    float* part = ws + L.wpart;
-    if (dense_wgrad(ws + L.dq, 128, x_q, 128, rq, g->wq, 128, 128, part, tiles_d, cs_d, st)) return -1;
-    if (dense_wgrad(ws + L.dkv, 256, x_kv, 128, rk, g->wkv, 256, 128, part, tiles_d, cs_d, st)) return -1;
-    if (dense_wgrad(ws + L.dt1, 128, ws + L.o, 128, rq, g->wo, 128, 128, part, tiles_d, cs_d, st)) return -1;
-    if (dense_wgrad(ws + L.dpre1, dff, ws + L.y1, 128, rq, g->w1, dff, 128, part, tiles_d, cs_d, st)) return -1;
-    if (dense_wgrad(ws + L.dt2, 128, ws + L.hdn, dff, rq, g->w2, 128, dff, part, tiles_d, cs_d, st)) return -1;
-    {
-        // two stages: the per-tile partial rows (one per 16 input rows: 100,000 of them at the stress shape) are first summed in
-        // chunks of 512 rows by many workgroups, then the chunk sums per quantity -- one workgroup walking 100,000 rows took 11 ms
-        const int pw = post_partial_width(dff);
-        const float* pp = ws + L.partial;
-        constexpr int kChunkRows = 512;
-        const int nchunks = (tiles_q + kChunkRows - 1) / kChunkRows;
-        float* part2 = ws + L.wpart;                 // free again: the weight gradients above are done with it
-        if ((long long)nchunks * pw > (long long)L.splits * 256 * 128) return fail("cf_op_dense_layer_bwd: chunk buffer too small");
-        const int per = (pw + 63) / 64, n1 = nchunks * per;
-        int n2 = 0;
-        DenseCsTab tb;
-        tb.partial = pp;
-        tb.part2 = part2;
-        tb.cs1 = reinterpret_cast<CsTile*>(tiles_d);
-        tb.cs2 = cs_d;
-        tb.tiles_q = tiles_q;
-        tb.chunk_rows = kChunkRows;
-        tb.nchunks = nchunks;
-        tb.pw = pw;
-        const int offs[7] = {0, 128, 256, 384, 384 + dff, 512 + dff, 640 + dff}, ncl[7] = {kD, kD, kD, dff, kD, kD, kD};
-        float* dsts[7] = {g->ln2_g, g->ln2_b, g->b2, g->b1, g->ln1_g, g->ln1_b, g->bo};
-        for (int k = 0; k < 7; ++k) {
-            tb.off[k] = offs[k];
-            tb.ncols[k] = ncl[k];
-            tb.dst[k] = dsts[k];
-            n2 += (ncl[k] + 63) / 64;
-        }
-        if ((size_t)n1 * sizeof(CsTile) > (size_t)(kDenseTab / 2) * sizeof(float) * 64) return fail("cf_op_dense_layer_bwd: tile table overflow");
-        hipLaunchKernelGGL(k_dense_cs_tables, dim3(std::max(1, std::min(64, (n1 + 255) / 256))), dim3(256), 0, st, tb);
-        LAUNCH_CHECK("k_dense_cs_tables");
-        hipLaunchKernelGGL(k_colsum, dim3(n1), dim3(256), 0, st, (const CsTile*)tb.cs1, 1);
-        LAUNCH_CHECK("k_colsum<dense layer bias, stage 1>");
-        hipLaunchKernelGGL(k_colsum, dim3(n2), dim3(256), 0, st, (const CsTile*)cs_d, 1);
-        LAUNCH_CHECK("k_colsum<dense layer bias>");
-    }
-    return 0;
-}
+#include "cf_api_ops.h"
 
 // ------------------------------------------------------------------------------------
 // Embedding over all promoter bins (embed.n_layers > 1, cf_embed_full): net.py:9-59 without the centre-row shortcut

@@ -1,0 +1,438 @@
+// cf_api_attrib.h -- host side of the attribution entry points (input gradients, attention maps, pCRE deletion, integrated
+// gradients).  Part of cf_api.hip's single translation unit: included there behind the backward pass, not on its own.
+#pragma once
+
+// k_input_grad's dynamic LDS size; the first call sets the kernel's attribute.  0: that failed (`who`: the entry point, for the error text).
+static size_t input_grad_prepare(cf_handle* h, const char* who) {
+    const cf_config& c = h->cfg;
+    size_t smem = 0;
+    for (int r = 0; r < c.n_res; ++r) smem = std::max(smem, input_grad_smem(c.n_bins[r], c.n_feats, c.d_emb));
+    if (!h->ig_smem_ok) {
+        if (hipFuncSetAttribute((const void*)k_input_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
+            fail("%s: promoter_feats / pcre_feats: k_input_grad needs %zu bytes of LDS", who, smem);
+            return 0;
+        }
+        h->ig_smem_ok = true;
+    }
+    return smem;
+}
+// The feature gradients of the B genes of `bt` from the attention operands its backward pass saved (cf_input_grad.h); a null output is skipped.
+static int launch_input_grad(cf_handle* h, const cf_batch& bt, int B, float* const out_p[], float* const out_c[], size_t smem, hipStream_t st) {
+    const cf_config& c = h->cfg;
+    const int S = c.i_max, nres = c.n_res, F = c.n_feats, kD = c.d_emb;
+    InGradArgs a;
+    memset(&a, 0, sizeof a);
+    for (int r = 0; r < nres; ++r) {
+        const int bs = c.binsizes[r];
+        a.feats_p[r] = bt.promoter_feats[r];
+        a.feats_c[r] = bt.pcre_feats[r];
+        a.mask_p[r] = static_cast<const uint8_t*>(bt.promoter_mask_row[r]);
+        a.mask_c[r] = static_cast<const uint8_t*>(bt.pcre_mask_row[r]);
+        a.mstride_p[r] = bt.promoter_mask_stride[r];
+        a.mstride_c[r] = bt.pcre_mask_stride[r];
+        a.pet[r] = h->pet[r];
+        a.w_p[r] = h->P_(fmt("embed.%d.lin_proj.weight", bs));
+        a.w_c[r] = h->P_(fmt("pairwise_interaction.%d.lin_proj_pcre.weight", bs));
+        a.edx0[r] = h->edx0[r];
+        a.ep[r] = h->E[r].p;
+        a.eqt[r] = h->E[r].qt;
+        a.edxbar[r] = h->E[r].dxbar;
+        for (int l = 0; l < c.pair_layers; ++l) {
+            a.pp[r][l] = h->P[r][l].p;
+            a.pqt[r][l] = h->P[r][l].qt;
+            a.pdxbar[r][l] = h->P[r][l].dxbar;
+        }
+        a.out_p[r] = out_p[r];
+        a.out_c[r] = out_c[r];
+        a.L[r] = c.n_bins[r];
+    }
+    a.B = B;
+    a.S = S;
+    a.F = F;
+    a.D = kD;
+    a.nh_e = c.embed_heads;
+    a.nh_p = c.pair_heads;
+    a.n_pl = c.pair_layers;
+    a.rs_e = 1.0f / sqrtf((float)(kD / c.embed_heads));
+    a.rs_p = 1.0f / sqrtf((float)(kD / c.pair_heads));
+    hipLaunchKernelGGL(k_input_grad, dim3(1 + S, B, nres), dim3(kIgThreads), smem, st, a);
+    LAUNCH_CHECK("k_input_grad");
+    return 0;
+}
+// The trunk's output (the Regulation input Rx[r][0]) of B genes, copied to dst[r]
+static int stash_trunk_output(cf_handle* h, int B, float* const dst[], hipStream_t st) {
+    const cf_config& c = h->cfg;
+    const int nres = c.n_res, row4 = (c.i_max + 1) * c.d_emb / 4;
+    AblateStashArgs sa;
+    memset(&sa, 0, sizeof sa);
+    for (int r = 0; r < nres; ++r) {
+        sa.src[r] = reinterpret_cast<const float4*>(h->Rx[r][0]);
+        sa.dst[r] = reinterpret_cast<float4*>(dst[r]);
+    }
+    sa.n4 = (long long)B * row4;
+    hipLaunchKernelGGL(k_pcre_stash, dim3((int)std::min<long long>((sa.n4 + kAblThreads - 1) / kAblThreads, 256), nres), dim3(kAblThreads), 0, st, sa);
+    LAUNCH_CHECK("k_pcre_stash");
+    return 0;
+}
+
+// cf_backward_from + the gradients of the float inputs (cf_input_grad.h).  The parameter gradients come from the very launches of
+// cf_backward_from; the interaction_freq gradient from the Regulation backward's DFREQ variant, the feature gradients from the saved
+// attention operands, in front of the reductions.  Every requested output is overwritten in full.
+extern "C" int cf_backward_from_inputs(cf_handle* h, const cf_batch* bt, const float* dlogits, const cf_input_grads* want, void* stream) {
+    bool any_p = false, any_c = false;
+    if (want)
+        for (int r = 0; r < kMaxRes; ++r) {
+            any_p |= want->promoter_feats[r] != nullptr;
+            any_c |= want->pcre_feats[r] != nullptr;
+        }
+    const bool any_f = want && want->interaction_freq;
+    if (!any_p && !any_c && !any_f) return cf_backward_from(h, bt, dlogits, stream);
+    if (check_bwd(h, bt)) return -1;
+    if (!dlogits) return fail("cf_backward_from_inputs: dlogits is null");
+    const cf_config& c = h->cfg;
+    const int B = bt->B, T = c.i_max + 1, nres = c.n_res;
+    for (int r = nres; r < kMaxRes; ++r)
+        if (want->promoter_feats[r] || want->pcre_feats[r]) return fail("cf_backward_from_inputs: promoter_feats / pcre_feats[%d]: the model has %d resolutions", r, nres);
+    if (any_p && h->embed_dense)
+        return fail("cf_backward_from_inputs: promoter_feats: input gradients are implemented for embed.n_layers = 1 (the centre-row Embedding); "
+                    "this model has embed.n_layers = %d (the all-rows path keeps no first-layer input-row gradient)", c.embed_layers);
+    if (any_f && h->reg_fused && !h->reg_dfreq_ok)
+        return fail("cf_backward_from_inputs: interaction_freq: the fused Regulation backward variant could not be configured");
+    const size_t smem = any_p || any_c ? input_grad_prepare(h, "cf_backward_from_inputs") : 0;
+    if ((any_p || any_c) && !smem) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(h->dlogits, dlogits, (size_t)B * c.n_out * sizeof(float), hipMemcpyDeviceToDevice, st));
+    PassOpts po;
+    po.dfreq = any_f ? h->dfreq_part : nullptr;
+    if (backward_impl(h, bt, st, 7, nullptr, 1.f, nullptr, po)) return -1;
+    if (any_p || any_c) {
+        if (launch_input_grad(h, *bt, B, want->promoter_feats, want->pcre_feats, smem, st)) return -1;
+    }
+    if (any_f) {
+        const int n = B * T * T;
+        hipLaunchKernelGGL(k_dfreq_sum, dim3((n + 255) / 256), dim3(256), 0, st, h->dfreq_part, want->interaction_freq, n, nres);
+        LAUNCH_CHECK("k_dfreq_sum");
+    }
+    return reduce_impl(h, B, st);
+}
+
+// cf_forward(save = 1) + k_attn_maps (cf_attn_maps.h): the attention probabilities the forward kept for the backward pass and the
+// fc_head input, copied into the caller's dense layouts.  Nothing requested: exactly the launches of cf_forward(save = 1).
+extern "C" int cf_attention_maps(cf_handle* h, const cf_batch* bt, float* logits, const cf_attn_maps* want, void* stream) {
+    if (!h) return fail("null handle");
+    const cf_config& c = h->cfg;
+    const int nres = c.n_res;
+    bool any_e = false, any = false;
+    if (want) {
+        for (int r = 0; r < kMaxRes; ++r) {
+            if (r >= nres && (want->embed[r] || want->pairwise[r] || want->regulation[r]))
+                return fail("cf_attention_maps: embed / pairwise / regulation[%d]: the model has %d resolutions", r, nres);
+            any_e |= want->embed[r] != nullptr;
+            any |= want->embed[r] || want->pairwise[r] || want->regulation[r];
+        }
+        any |= want->embedding != nullptr;
+    }
+    if (any_e && h->embed_dense)
+        return fail("cf_attention_maps: embed: attention maps are implemented for embed.n_layers = 1 (the centre-row Embedding); "
+                    "this model has embed.n_layers = %d (the all-rows path keeps no probabilities)", c.embed_layers);
+    if (c.pair_layers > kMapPair || c.reg_layers > kMapReg)
+        return fail("cf_attention_maps: pairwise / regulation: at most %d / %d layers", kMapPair, kMapReg);
+    if (forward_impl(h, bt, logits, 1, stream, nullptr)) return -1;
+    if (!any) return 0;
+    const int B = bt->B;
+    AttnMapArgs a;
+    memset(&a, 0, sizeof a);
+    long long most = want->embedding ? (long long)B * nres * c.d_emb : 0;      // elements of the largest requested output
+    for (int r = 0; r < nres; ++r) {
+        const int L = c.n_bins[r];
+        a.ep[r] = h->E[r].p;
+        for (int l = 0; l < c.pair_layers; ++l) a.pp[r][l] = h->P[r][l].p;
+        for (int l = 0; l < c.reg_layers; ++l) a.rp[r][l] = h->reg_fused ? h->R[r][l].hq : h->R[r][l].p;
+        a.embed[r] = want->embed[r];
+        a.pair[r] = want->pairwise[r];
+        a.reg[r] = want->regulation[r];
+        a.L[r] = L;
+        if (a.embed[r]) most = std::max(most, (long long)B * c.embed_heads * L);
+        if (a.pair[r]) most = std::max(most, (long long)B * c.pair_layers * c.i_max * c.pair_heads * L);
+        if (a.reg[r]) most = std::max(most, (long long)B * c.reg_layers * c.reg_heads * (c.i_max + 1));
+    }
+    a.hin = h->hin;
+    a.emb = want->embedding;
+    a.B = B;
+    a.S = c.i_max;
+    a.T = c.i_max + 1;
+    a.nh_e = c.embed_heads;
+    a.nh_p = c.pair_heads;
+    a.n_pl = c.pair_layers;
+    a.H = c.reg_heads;
+    a.n_rl = c.reg_layers;
+    a.K = nres * c.d_emb;
+    a.reg_fused = h->reg_fused ? 1 : 0;
+    const int gx = (int)std::min<long long>((most + kMapThreads - 1) / kMapThreads, 1024);
+    hipLaunchKernelGGL(k_attn_maps, dim3(gx, kMapSegs), dim3(kMapThreads), 0, (hipStream_t)stream, a);
+    LAUNCH_CHECK("k_attn_maps");
+    ++h->n_fwd;
+    if (h->capturing) h->cap.n_fwd = h->n_fwd;
+    return 0;
+}
+
+// The buffers of cf_pcre_ablation, allocated by its first call (the model's other entry points never need them).
+static int ablate_alloc(cf_handle* h) {
+    if (h->abl_mem) return 0;
+    const cf_config& c = h->cfg;
+    const size_t T = c.i_max + 1, rows = (size_t)c.max_batch * T, x0 = rows * c.d_emb, tt = (size_t)c.max_batch * T * T;
+    const size_t freq_off = c.n_res * x0, mask_off = freq_off + tt;      // (floats; the masks follow as bytes)
+    void* q = nullptr;
+    if (hipMalloc(&q, mask_off * sizeof(float) + c.n_res * tt) != hipSuccess) return fail("cf_pcre_ablation: out of memory");
+    h->abl_mem = q;
+    float* f = (float*)q;
+    for (int r = 0; r < c.n_res; ++r) {
+        h->abl_stash[r] = f + r * x0;
+        h->abl_mask[r] = (uint8_t*)(f + mask_off) + r * tt;
+    }
+    h->abl_freq = f + freq_off;
+    return 0;
+}
+
+// The trunk once on the B genes, k_pcre_stash, then per chunk of at most max_batch of the B * V gene-variants (V = i_max + 2,
+// gene-major) k_pcre_expand and the Regulation + head launches of an inference forward on a batch of that chunk (cf_ablate.h).
+extern "C" int cf_pcre_ablation(cf_handle* h, const cf_batch* bt, float* logits, void* stream) {
+    if (!h) return fail("cf_pcre_ablation: null handle");
+    if (!bt) return fail("cf_pcre_ablation: null batch");
+    if (!logits) return fail("cf_pcre_ablation: null logits");
+    const cf_config& c = h->cfg;
+    if (bt->B > c.max_batch) return fail("cf_pcre_ablation: batch size %d exceeds max_batch=%d", bt->B, c.max_batch);
+    if (check_batch(h, bt)) return -1;
+    if (ablate_alloc(h)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    const long long launches0 = g_launches;
+    const int B = bt->B, S = c.i_max, T = S + 1, V = S + 2, nres = c.n_res, cap = c.max_batch;
+    const int row4 = T * c.d_emb / 4;
+    if (forward_trunk(h, bt, 0, st) || stash_trunk_output(h, B, h->abl_stash, st)) return -1;
+    AblateExpandArgs ea;
+    memset(&ea, 0, sizeof ea);
+    cf_batch cb = *bt;      // the chunk's batch: only B, the masks and the frequencies are read past the trunk
+    for (int r = 0; r < nres; ++r) {
+        ea.stash[r] = reinterpret_cast<const float4*>(h->abl_stash[r]);
+        ea.x0[r] = reinterpret_cast<float4*>(h->Rx[r][0]);
+        ea.mask_in[r] = bt->interaction_mask[r];
+        ea.mask_out[r] = h->abl_mask[r];
+        cb.interaction_mask[r] = h->abl_mask[r];
+    }
+    ea.freq_in = bt->interaction_freq;
+    ea.freq_out = h->abl_freq;
+    cb.interaction_freq = h->abl_freq;
+    ea.V = V, ea.S = S, ea.T = T, ea.row4 = row4;
+    for (int g0 = 0; g0 < B * V; g0 += cap) {
+        const int n = std::min(cap, B * V - g0);
+        ea.g0 = g0;
+        hipLaunchKernelGGL(k_pcre_expand, dim3(n, nres), dim3(kAblThreads), 0, st, ea);
+        LAUNCH_CHECK("k_pcre_expand");
+        cb.B = n;
+        if (forward_reg_head(h, &cb, logits + (size_t)g0 * c.n_out, 0, st, nullptr)) return -1;
+    }
+    h->last_fwd_B = 0;
+    h->n_fwd = (int)(g_launches - launches0);
+    if (h->capturing) h->cap.n_fwd = h->n_fwd;
+    return 0;
+}
+
+// The buffers of cf_integrated_gradients, allocated by its first call; the node / weight table grows with n_steps.
+static int intg_alloc(cf_handle* h, int n_steps) {
+    const cf_config& c = h->cfg;
+    const size_t M = c.max_batch, S = c.i_max, T = S + 1, F = c.n_feats;
+    if (!h->intg_mem) {
+        size_t nf = 0, nb = 0;      // floats, then bytes (every float segment a multiple of 4 floats: 16-byte aligned rows)
+        auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
+        for (int r = 0; r < c.n_res; ++r) nf += 2 * up4(M * c.n_bins[r] * F) + 2 * up4(M * S * c.n_bins[r] * F) + up4(M * T * c.d_emb);
+        nf += 2 * up4(M * T * T) + up4(M * c.n_out) + up4(M * kIgSlices);
+        // (the all-rows Embedding reads every row of a full [B, L, L] promoter mask: its chunks keep L rows per chunk row)
+        auto pm_rows = [&](int r) { return h->embed_dense ? (size_t)c.n_bins[r] : (size_t)1; };
+        for (int r = 0; r < c.n_res; ++r) nb += M * pm_rows(r) * c.n_bins[r] + M * S * c.n_bins[r] + M * T * T;
+        void* q = nullptr;
+        if (hipMalloc(&q, nf * sizeof(float) + nb) != hipSuccess) return fail("cf_integrated_gradients: out of memory");
+        h->intg_mem = q;
+        float* f = (float*)q;
+        auto take = [&](size_t n) { float* p = f; f += up4(n); return p; };
+        for (int r = 0; r < c.n_res; ++r) {
+            const size_t L = c.n_bins[r];
+            h->intg_row[r] = take(M * L * F);
+            h->intg_grad[r] = take(M * L * F);
+            h->intg_row[kMaxRes + r] = take(M * S * L * F);
+            h->intg_grad[kMaxRes + r] = take(M * S * L * F);
+            h->intg_stash[r] = take(M * T * c.d_emb);
+        }
+        h->intg_row[2 * kMaxRes] = take(M * T * T);
+        h->intg_grad[2 * kMaxRes] = take(M * T * T);
+        h->intg_logits = take(M * c.n_out);
+        h->intg_part = take(M * kIgSlices);
+        uint8_t* u = (uint8_t*)f;
+        for (int r = 0; r < c.n_res; ++r) {
+            const size_t L = c.n_bins[r];
+            h->intg_pm[r] = u, u += M * pm_rows(r) * L;
+            h->intg_cm[r] = u, u += M * S * L;
+            h->intg_im[r] = u, u += M * T * T;
+        }
+    }
+    if (n_steps > h->intg_cap) {
+        const int cap = std::max(n_steps, 64);
+        if (h->intg_tab) (void)hipFree(h->intg_tab);      // (synchronises: a call in flight may still read the old table)
+        h->intg_tab = nullptr;
+        h->intg_cap = 0;
+        if (hipMalloc(&h->intg_tab, 2 * (size_t)cap * sizeof(float)) != hipSuccess) return fail("cf_integrated_gradients: out of memory");
+        h->intg_cap = cap;
+    }
+    return 0;
+}
+
+// Integrated gradients (cf_ig.h).  General path, per chunk of at most max_batch of the B * V rows: k_ig_expand, the launches of
+// cf_forward(save = 1), backward_impl (head, Regulation, trunk), k_input_grad / k_dfreq_sum into the per-row scratch, k_ig_accumulate;
+// no reduce_impl; k_ig_delta once at the end.  k_attc2 takes as many regions per workgroup as for the caller's B genes (ag_genes),
+// so the chunks run the attention variant model(...) on the batch runs: the result does not depend on max_batch and equals the
+// hand-written loop of grad-enabled model(...) calls on the batch.  Frequency-only path: the trunk once (save = 1, the launches of cf_forward's first part) and its output stashed, then
+// per chunk k_ig_expand (stashed rows, masks, frequencies, dlogits), the Regulation + head forward, backward parts 1 and 2,
+// k_dfreq_sum, k_ig_accumulate.
+extern "C" int cf_integrated_gradients(cf_handle* h, const cf_batch* bt, const cf_ig_opts* o, const cf_input_grads* out,
+                                       float* logits_x, float* logits_base, float* delta, void* stream) {
+    if (!h) return fail("cf_integrated_gradients: null handle");
+    if (!bt) return fail("cf_integrated_gradients: null batch");
+    if (!o) return fail("cf_integrated_gradients: null opts");
+    if (!out) return fail("cf_integrated_gradients: null out");
+    if (!logits_x || !logits_base || !delta) return fail("cf_integrated_gradients: null logits_x / logits_base / delta");
+    const cf_config& c = h->cfg;
+    const int nres = c.n_res, S = c.i_max, T = S + 1, F = c.n_feats, kD = c.d_emb, cap = c.max_batch;
+    if (o->n_steps < 1) return fail("cf_integrated_gradients: n_steps = %d: at least 1 quadrature node", o->n_steps);
+    if (!o->alphas || !o->weights) return fail("cf_integrated_gradients: null alphas / weights");
+    if (o->target < 0 || o->target >= c.n_out) return fail("cf_integrated_gradients: target = %d outside [0, n_out = %d)", o->target, c.n_out);
+    if (o->interpolate & ~(CF_IG_PROMOTER | CF_IG_PCRE | CF_IG_FREQ) || !o->interpolate)
+        return fail("cf_integrated_gradients: interpolate = %d: a non-empty mask of CF_IG_PROMOTER | CF_IG_PCRE | CF_IG_FREQ", o->interpolate);
+    if (bt->B > cap) return fail("cf_integrated_gradients: batch size %d exceeds max_batch=%d", bt->B, cap);
+    const bool ip = o->interpolate & CF_IG_PROMOTER, ic = o->interpolate & CF_IG_PCRE, ifr = o->interpolate & CF_IG_FREQ;
+    for (int r = 0; r < kMaxRes; ++r) {
+        if (r >= nres && (out->promoter_feats[r] || out->pcre_feats[r] || o->base_promoter_feats[r] || o->base_pcre_feats[r]))
+            return fail("cf_integrated_gradients: promoter_feats / pcre_feats[%d]: the model has %d resolutions", r, nres);
+        if (r < nres && (out->promoter_feats[r] != nullptr) != ip)
+            return fail("cf_integrated_gradients: promoter_feats[%d]: the output must be given exactly when promoter_feats is interpolated", r);
+        if (r < nres && (out->pcre_feats[r] != nullptr) != ic)
+            return fail("cf_integrated_gradients: pcre_feats[%d]: the output must be given exactly when pcre_feats is interpolated", r);
+    }
+    if ((out->interaction_freq != nullptr) != ifr)
+        return fail("cf_integrated_gradients: interaction_freq: the output must be given exactly when interaction_freq is interpolated");
+    if (ip && h->embed_dense)
+        return fail("cf_integrated_gradients: promoter_feats: input gradients are implemented for embed.n_layers = 1 (the centre-row Embedding); "
+                    "this model has embed.n_layers = %d (the all-rows path keeps no first-layer input-row gradient)", c.embed_layers);
+    if (ifr && h->reg_fused && !h->reg_dfreq_ok)
+        return fail("cf_integrated_gradients: interaction_freq: the fused Regulation backward variant could not be configured");
+    if (!h->grads) return fail("cf_integrated_gradients: no gradient buffer bound (the backward workspace is set up by cf_bind; the buffer is not written)");
+    if (h->rider.armed || h->rider.done) return fail("cf_integrated_gradients: riders are armed for a training step (cf_rider_arm); finish the step first");
+    if (check_batch(h, bt)) return -1;
+    const size_t smem = ip || ic ? input_grad_prepare(h, "cf_integrated_gradients") : 0;
+    if ((ip || ic) && !smem) return -1;
+    if (intg_alloc(h, o->n_steps)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    const int B = bt->B, n = o->n_steps, V = n + 2, TT = T * T;
+    const bool freq_only = o->interpolate == CF_IG_FREQ && h->intg_trunk_once;
+    HIP_TRY(hipMemcpyAsync(h->intg_tab, o->alphas, n * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->intg_tab + h->intg_cap, o->weights, n * sizeof(float), hipMemcpyHostToDevice, st));
+    long long n_fwd = 0, n_bwd = 0;
+    IgExpandArgs ea;
+    IgAccArgs aa;
+    memset(&ea, 0, sizeof ea);
+    memset(&aa, 0, sizeof aa);
+    cf_batch cb;      // the chunk's batch: the rows' copies
+    memset(&cb, 0, sizeof cb);
+    for (int r = 0; r < nres; ++r) {
+        const int L = c.n_bins[r];
+        IgSeg* sp = &ea.seg[r];
+        IgSeg* sc = &ea.seg[kMaxRes + r];
+        *sp = IgSeg{bt->promoter_feats[r], o->base_promoter_feats[r], h->intg_row[r], h->intg_grad[r], out->promoter_feats[r], L * F};
+        *sc = IgSeg{bt->pcre_feats[r], o->base_pcre_feats[r], h->intg_row[kMaxRes + r], h->intg_grad[kMaxRes + r], out->pcre_feats[r], S * L * F};
+        // The all-rows Embedding (embed.n_layers > 1) honours a full [B, L, L] promoter mask entry by entry: the chunk rows carry
+        // all L rows of their gene's mask, not the centre row alone (from which only the dataset's not(valid x valid) form can be rebuilt).
+        const bool pm_full = h->embed_dense && bt->promoter_mask_stride[r] == (long long)L * L;
+        ea.pm_rows[r] = pm_full ? L : 1;
+        ea.pm_in[r] = static_cast<const uint8_t*>(bt->promoter_mask_row[r]) - (pm_full ? (size_t)(L / 2) * L : 0);
+        ea.cm_in[r] = bt->pcre_mask_row[r];
+        ea.pm_stride[r] = bt->promoter_mask_stride[r];
+        ea.cm_stride[r] = bt->pcre_mask_stride[r];
+        ea.pm_out[r] = h->intg_pm[r];
+        ea.cm_out[r] = h->intg_cm[r];
+        ea.im_in[r] = bt->interaction_mask[r];
+        ea.im_out[r] = h->intg_im[r];
+        ea.stash[r] = reinterpret_cast<const float4*>(h->intg_stash[r]);
+        ea.x0[r] = reinterpret_cast<float4*>(h->Rx[r][0]);
+        ea.L[r] = L;
+        cb.promoter_feats[r] = h->intg_row[r];
+        cb.pcre_feats[r] = h->intg_row[kMaxRes + r];
+        cb.promoter_mask_row[r] = h->intg_pm[r] + (pm_full ? (size_t)(L / 2) * L : 0);
+        cb.promoter_mask_stride[r] = pm_full ? (long long)L * L : L;
+        cb.pcre_mask_row[r] = h->intg_cm[r];
+        cb.pcre_mask_stride[r] = L;
+        cb.interaction_mask[r] = h->intg_im[r];
+    }
+    ea.seg[2 * kMaxRes] = IgSeg{bt->interaction_freq, o->base_interaction_freq, h->intg_row[2 * kMaxRes], h->intg_grad[2 * kMaxRes], out->interaction_freq, TT};
+    cb.interaction_freq = h->intg_row[2 * kMaxRes];
+    ea.alpha = h->intg_tab;
+    ea.weight = h->intg_tab + h->intg_cap;
+    ea.dlogits = h->dlogits;
+    ea.V = V, ea.S = S, ea.TT = TT, ea.n_out = c.n_out, ea.target = o->target, ea.nres = nres, ea.bcast = o->base_broadcast ? 1 : 0;
+    ea.freq_only = freq_only ? 1 : 0;
+    ea.row4 = T * kD / 4;
+    memcpy(aa.seg, ea.seg, sizeof aa.seg);
+    aa.logits = h->intg_logits;
+    aa.logits_x = logits_x;
+    aa.logits_b = logits_base;
+    aa.part = h->intg_part;
+    aa.V = V, aa.n_out = c.n_out, aa.bcast = ea.bcast;
+    // k_attc2 takes as many regions per workgroup as for the caller's B genes; the all-rows Embedding backward writes parameter gradients: not run
+    PassOpts po;
+    po.dfreq = ifr ? h->dfreq_part : nullptr;
+    po.no_dense_embed_bwd = true;
+    po.ag_genes = B;
+    float* const no_grad[kMaxRes] = {};
+    auto run = [&]() -> int {
+        long long l0 = g_launches;
+        if (freq_only) {      // the trunk once on the B genes, its output (the Regulation input) stashed
+            if (forward_trunk(h, bt, 1, st, B) || stash_trunk_output(h, B, h->intg_stash, st)) return -1;
+        }
+        n_fwd += g_launches - l0;
+        for (int g0 = 0; g0 < B * V; g0 += cap) {
+            const int nr = std::min(cap, B * V - g0);
+            l0 = g_launches;
+            ea.g0 = g0;
+            hipLaunchKernelGGL(k_ig_expand, dim3(nr, nres), dim3(kIgxThreads), 0, st, ea);
+            LAUNCH_CHECK("k_ig_expand");
+            cb.B = nr;
+            if ((!freq_only && forward_trunk(h, &cb, 1, st, B)) || forward_reg_head(h, &cb, h->intg_logits, 1, st, nullptr)) return -1;
+            n_fwd += g_launches - l0;
+            l0 = g_launches;
+            if (backward_impl(h, &cb, st, freq_only ? 3 : 7, nullptr, 1.f, nullptr, po)) return -1;
+            if (ip || ic) {
+                if (launch_input_grad(h, cb, nr, ip ? h->intg_grad : no_grad, ic ? h->intg_grad + kMaxRes : no_grad, smem, st)) return -1;
+            }
+            if (ifr) {
+                const int ne = nr * TT;
+                hipLaunchKernelGGL(k_dfreq_sum, dim3((ne + 255) / 256), dim3(256), 0, st, h->dfreq_part, h->intg_grad[2 * kMaxRes], ne, nres);
+                LAUNCH_CHECK("k_dfreq_sum");
+            }
+            aa.g0 = g0;
+            aa.n = nr;
+            hipLaunchKernelGGL(k_ig_accumulate, dim3((g0 + nr - 1) / V - g0 / V + 1, kIgSlices), dim3(kIgxThreads), 0, st, aa);
+            LAUNCH_CHECK("k_ig_accumulate");
+            n_bwd += g_launches - l0;
+        }
+        l0 = g_launches;
+        hipLaunchKernelGGL(k_ig_delta, dim3((B + 63) / 64), dim3(64), 0, st, h->intg_part, logits_x, logits_base, delta, B, c.n_out, o->target);
+        LAUNCH_CHECK("k_ig_delta");
+        n_bwd += g_launches - l0;
+        return 0;
+    };
+    const bool pend_record = h->pend_record;      // (a step record queued for the next training backward stays queued for it)
+    h->pend_record = false;
+    const int rc = run();
+    h->pend_record = pend_record;
+    h->last_fwd_B = 0;
+    h->n_fwd = (int)n_fwd;
+    h->n_bwd = (int)n_bwd;
+    return rc ? -1 : 0;
+}

@@ -2414,18 +2414,10 @@ __global__ __launch_bounds__(256) void k_reduce_adamw(const WgTile* __restrict__
                     (long long)(blockIdx.x - n_red) * blockDim.x + threadIdx.x, nblk * blockDim.x);
     }
 }
-// The same update with the step-dependent scalars read from device memory, so that the launch can sit inside a
-// replayed hipGraph (kernel arguments are frozen at capture): k_adamw_set writes them each step, outside the graph.
+// the step-dependent AdamW scalars, computed on the host once per step (adam_hyper)
 struct AdamHyper {
     float decay, one_m_b1, b2, one_m_b2, step_size, bc2_sqrt, eps, pad;
 };
-__global__ void k_adamw_set(AdamHyper* dst, AdamHyper v) { *dst = v; }
-__global__ __launch_bounds__(256) void k_adamw_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, long long n4, const AdamHyper* __restrict__ hp) {
-    const AdamHyper h = *hp;
-    adamw_range(p, g, m, v, n4, h.decay, h.one_m_b1, h.b2, h.one_m_b2, h.step_size, h.bc2_sqrt, h.eps, (long long)blockIdx.x * blockDim.x + threadIdx.x,
-                (long long)gridDim.x * blockDim.x);
-}
 
 // =======================================================================================
 // Tiled copies of the Linear weights -- see FragNT.  One workgroup per 16-row unit of a tensor W[N][K] (retile_unit, above):
