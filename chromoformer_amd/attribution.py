@@ -6,6 +6,8 @@ and satisfies completeness: the attributions of one gene sum to F(x) - F(x') up 
 (IntegratedGradients(method=...)): Gauss-Legendre (default) and the four Riemann sums.  The trapezoid rule here is the composite one
 on n equally spaced nodes including both ends (step 1 / (n - 1), half weights at the ends), so that every method's weights sum to 1.
 """
+import ctypes as C
+
 import numpy as np
 
 METHODS = ("gausslegendre", "riemann_trapezoid", "riemann_middle", "riemann_left", "riemann_right")
@@ -40,6 +42,138 @@ def ig_quadrature(method="gausslegendre", n_steps=50):
     return a.astype(np.float32), w.astype(np.float32)
 
 
+def _raw_check(who, model, dataset, genes, target, bsz):
+    """The checks the raw-signal generators share -> (binsizes, n_bins, target, genes, chunk size)."""
+    ds = dataset
+    binsizes = [int(b) for b in ds.binsizes]
+    if len(binsizes) > 3 or len(set(binsizes)) != len(binsizes):
+        raise ValueError("%s: binsizes %s: more than three or repeated bin sizes are binned by one cf_bin_regions launch "
+                         "per resolution, which has no backward; use at most three distinct bin sizes" % (who, binsizes))
+    if model._handle is None:
+        raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
+    n_bins = [ds.w_max // b for b in binsizes]
+    if binsizes != list(model.binsizes) or n_bins != list(model.n_bins) or ds.i_max != model.i_max or ds.n_feats != model.n_feats:
+        raise ValueError("%s: the dataset (binsizes %s, w_max %d, i_max %d, n_feats %d) does not match the model "
+                         "(binsizes %s, w_max %d, i_max %d, n_feats %d)" % (who, binsizes, ds.w_max, ds.i_max, ds.n_feats, list(model.binsizes),
+                                                                            model.w_max, model.i_max, model.n_feats))
+    target = (1 if model.n_out == 2 else 0) if target is None else int(target)
+    if not 0 <= target < model.n_out:
+        raise ValueError("%s: target = %d outside [0, n_out = %d)" % (who, target, model.n_out))
+    genes = list(ds.target_genes if genes is None else genes)
+    missing = [g for g in genes if g not in ds.genes]
+    if missing:
+        raise KeyError("%s: gene(s) %s are not in the dataset's metadata" % (who, missing[:5]))
+    chunk = model._max_batch if bsz is None else max(1, min(int(bsz), model._max_batch))
+    return binsizes, n_bins, target, genes, chunk
+
+
+class _RawChunk:
+    """The raw regions of a chunk of genes on the device, binned by cf_bin_regions_multi into the model's inputs: what the raw-signal
+    generators share -- region loading, the job tables of the binning and of its backward, the scatter back into per-gene tracks."""
+
+    def __init__(self, model, ds, ids, binsizes, n_bins):
+        import torch
+
+        from . import _lib
+        from .data import BIN_JOB_MULTI, load_raw_regions, raw_window
+        self.ds, self.ids, self.binsizes, self.n_bins = ds, ids, binsizes, n_bins
+        self.dev, self.lib = model._device, _lib.lib()
+        dev = self.dev
+        B = len(ids)
+        S, T, F, nres = ds.i_max, ds.i_max + 1, ds.n_feats, len(binsizes)
+        self.F, self.nres = F, nres
+        self.order = order = sorted(range(nres), key=lambda r: -binsizes[r])      # coarsest first
+        self.cb = (C.c_int * nres)(*[binsizes[r] for r in order])
+        self.cl = (C.c_int * nres)(*[n_bins[r] for r in order])
+        self.regs = regs = []                                    # (gene row, slot, flip, raw array, col0, ncols, raw offset, draw offset, ld_out)
+        n_raw = n_out = max_cols = 0
+        for i, gene in enumerate(ids):
+            for s, flip, a in load_raw_regions(ds, gene):
+                c0, nc = raw_window(ds, s, a.shape[1])
+                for r, b in enumerate(binsizes):
+                    if -(-nc // b) > n_bins[r]:
+                        raise ValueError("region spans %d bins but w_max allows %d" % (-(-nc // b), n_bins[r]))
+                ld_out = -(-nc // 4) * 4
+                regs.append((i, s, flip, a, c0, nc, n_raw, n_out, ld_out))
+                n_raw += -(-a.size // 4) * 4                     # every region starts 8-byte aligned
+                n_out += F * ld_out
+                max_cols = max(max_cols, nc)
+        self.max_cols = max_cols
+        flat = np.zeros(n_raw, dtype=np.float16)
+        for _, _, _, a, _, _, off, _, _ in regs:
+            flat[off:off + a.size] = a.reshape(-1)
+        self.stream = torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev):
+            self.raw = raw = torch.from_numpy(flat).to(dev)
+            self.draw = torch.empty(max(n_out, 1), dtype=torch.float32, device=dev)      # (every window sample is written by the library)
+            self.pf = pf = [torch.zeros(B, 1, L, F, device=dev) for L in n_bins]
+            self.cf = cf = [torch.zeros(B, S, L, F, device=dev) for L in n_bins]
+            self.pm = pm = [torch.ones(B, L, dtype=torch.uint8, device=dev) for L in n_bins]
+            self.cm = cm = [torch.ones(B, S, L, dtype=torch.uint8, device=dev) for L in n_bins]      # dummy slots stay fully masked
+            im = torch.ones(B, T, T, dtype=torch.uint8)
+            freq = torch.zeros(B, T, T)
+            for i, gene in enumerate(ids):
+                g = ds.genes[gene]
+                n_part = len(g["pcres"])
+                im[i, :n_part + 1, :n_part + 1] = 0
+                for s, sc in enumerate(g["scores"]):
+                    freq[i, 0, s + 1] = sc
+            self.im, self.freq = im.to(dev), freq.to(dev)
+            self.fj = fj = np.zeros(len(regs), dtype=BIN_JOB_MULTI)
+            for k, (i, s, flip, a, c0, nc, off, _, _) in enumerate(regs):
+                fj[k]["raw"], fj[k]["ld"], fj[k]["col0"], fj[k]["ncols"], fj[k]["flip"] = raw.data_ptr() + 2 * off, a.shape[1], c0, nc, int(flip)
+                for r in range(nres):
+                    out = pf[r][i, 0] if s < 0 else cf[r][i, s]
+                    msk = pm[r][i] if s < 0 else cm[r][i, s]
+                    fj[k]["out"][order.index(r)], fj[k]["mask"][order.index(r)] = out.data_ptr(), msk.data_ptr()
+            tab = torch.from_numpy(fj.view(np.uint8)).to(dev)
+            _lib.check(self.lib.cf_bin_regions_multi(C.c_void_p(tab.data_ptr()), len(regs), F, nres, self.cb, self.cl, int(max_cols),
+                                                     self.stream.cuda_stream), "cf_bin_regions_multi")
+
+    def model_args(self):
+        """The six arguments of model(...) / model.integrated_gradients(...)."""
+        bs = self.binsizes
+        return ({b: self.pf[r] for r, b in enumerate(bs)}, {b: self.pm[r] for r, b in enumerate(bs)},
+                {b: self.cf[r] for r, b in enumerate(bs)}, {b: self.cm[r] for r, b in enumerate(bs)},
+                {b: self.im for b in bs}, self.freq)
+
+    def backward(self, dp, dc, times_input):
+        """cf_bin_regions_multi_backward with dfeat pointing into dp[r] [B, 1, L, F] / dc[r] [B, S, L, F] -> the tracks, host float32."""
+        import torch
+
+        from . import _lib
+        from .data import BIN_GRAD_JOB
+        regs, fj, order, draw = self.regs, self.fj, self.order, self.draw
+        with torch.cuda.device(self.dev):
+            bj = np.zeros(len(regs), dtype=BIN_GRAD_JOB)
+            for k, (i, s, flip, a, c0, nc, off, ooff, ld_out) in enumerate(regs):
+                for name in ("raw", "ld", "col0", "ncols", "flip"):
+                    bj[k][name] = fj[k][name]
+                for r in range(self.nres):
+                    bj[k]["dfeat"][order.index(r)] = (dp[r][i, 0] if s < 0 else dc[r][i, s]).data_ptr()
+                bj[k]["draw"], bj[k]["ld_out"] = draw.data_ptr() + 4 * ooff, ld_out
+            tab2 = torch.from_numpy(bj.view(np.uint8)).to(self.dev)
+            _lib.check(self.lib.cf_bin_regions_multi_backward(C.c_void_p(tab2.data_ptr()), len(regs), self.F, self.nres, self.cb, self.cl,
+                                                              int(self.max_cols), 1 if times_input else 0, self.stream.cuda_stream),
+                       "cf_bin_regions_multi_backward")
+            return draw.cpu().numpy()
+
+    def scatter(self, host, per):
+        """The tracks of `host` into the per-gene dicts `per` (promoter, pcres, regions), genomic coordinates."""
+        ds, ids, F = self.ds, self.ids, self.F
+        for i, s, flip, a, c0, nc, off, ooff, ld_out in self.regs:
+            track = host[ooff:ooff + F * ld_out].reshape(F, ld_out)[:, :nc].copy()
+            g = ds.genes[ids[i]]
+            if s < 0:
+                chrom, tss, _ = g["tss"]
+                per[i]["promoter"] = track
+                per[i]["regions"].append((chrom, tss - 20000 + c0, tss - 20000 + c0 + nc))
+            else:
+                per[i]["pcres"].append(track)
+                per[i]["regions"].append(tuple(g["pcres"][s]))
+        return per
+
+
 def raw_signal_gradients(model, dataset, genes=None, target=None, times_input=False, bsz=None):
     """Raw-signal saliency: the gradient of logit column `target` (default: 1 for the classifier, 0 for the regressor) with respect to
     the RAW histone signals of a ChromoformerDataset -- the fp16 [F, len] .npy regions, at their own resolution and in genomic
@@ -59,85 +193,17 @@ def raw_signal_gradients(model, dataset, genes=None, target=None, times_input=Fa
         regions    [(chrom, start, end)] of the promoter window and of every pCRE: sample s of a track is position start + s
 
     times_input: gradient x input (each value multiplied by the raw sample).  Gradient and gradient x input only: integrated gradients
-    in raw space is a different path integral (log(1 + x) is not linear) and is not what this computes.  Parameters, their .grad and the
-    optimiser state are left as they are; the pass overwrites the activations a grad-enabled model(...) keeps for its backward."""
-    import ctypes as C
-
+    in raw space is a different path integral (log(1 + x) is not linear) and is not what this computes -- raw_integrated_gradients
+    below does.  Parameters, their .grad and the optimiser state are left as they are; the pass overwrites the activations a
+    grad-enabled model(...) keeps for its backward."""
     import torch
-
-    from . import _lib
-    from .data import BIN_GRAD_JOB, BIN_JOB_MULTI, load_raw_regions, raw_window
     ds = dataset
-    binsizes = [int(b) for b in ds.binsizes]
-    if len(binsizes) > 3 or len(set(binsizes)) != len(binsizes):
-        raise ValueError("raw_signal_gradients: binsizes %s: more than three or repeated bin sizes are binned by one cf_bin_regions launch "
-                         "per resolution, which has no backward; use at most three distinct bin sizes" % (binsizes,))
-    if model._handle is None:
-        raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
-    n_bins = [ds.w_max // b for b in binsizes]
-    if binsizes != list(model.binsizes) or n_bins != list(model.n_bins) or ds.i_max != model.i_max or ds.n_feats != model.n_feats:
-        raise ValueError("raw_signal_gradients: the dataset (binsizes %s, w_max %d, i_max %d, n_feats %d) does not match the model "
-                         "(binsizes %s, w_max %d, i_max %d, n_feats %d)" % (binsizes, ds.w_max, ds.i_max, ds.n_feats, list(model.binsizes),
-                                                                            model.w_max, model.i_max, model.n_feats))
-    target = (1 if model.n_out == 2 else 0) if target is None else int(target)
-    if not 0 <= target < model.n_out:
-        raise ValueError("raw_signal_gradients: target = %d outside [0, n_out = %d)" % (target, model.n_out))
-    genes = list(ds.target_genes if genes is None else genes)
-    missing = [g for g in genes if g not in ds.genes]
-    if missing:
-        raise KeyError("raw_signal_gradients: gene(s) %s are not in the dataset's metadata" % missing[:5])
-    chunk = model._max_batch if bsz is None else max(1, min(int(bsz), model._max_batch))
-    dev, L_ = model._device, _lib.lib()
-    S, T, F, nres = ds.i_max, ds.i_max + 1, ds.n_feats, len(binsizes)
-    order = sorted(range(nres), key=lambda r: -binsizes[r])      # coarsest first
-    cb = (C.c_int * nres)(*[binsizes[r] for r in order])
-    cl = (C.c_int * nres)(*[n_bins[r] for r in order])
+    binsizes, n_bins, target, genes, chunk = _raw_check("raw_signal_gradients", model, ds, genes, target, bsz)
     for lo in range(0, len(genes), chunk):
         ids = genes[lo:lo + chunk]
-        B = len(ids)
-        regs = []                                                # (gene row, slot, flip, raw array, col0, ncols, raw offset, draw offset, ld_out)
-        n_raw = n_out = max_cols = 0
-        for i, gene in enumerate(ids):
-            for s, flip, a in load_raw_regions(ds, gene):
-                c0, nc = raw_window(ds, s, a.shape[1])
-                for r, b in enumerate(binsizes):
-                    if -(-nc // b) > n_bins[r]:
-                        raise ValueError("region spans %d bins but w_max allows %d" % (-(-nc // b), n_bins[r]))
-                ld_out = -(-nc // 4) * 4
-                regs.append((i, s, flip, a, c0, nc, n_raw, n_out, ld_out))
-                n_raw += -(-a.size // 4) * 4                     # every region starts 8-byte aligned
-                n_out += F * ld_out
-                max_cols = max(max_cols, nc)
-        flat = np.zeros(n_raw, dtype=np.float16)
-        for _, _, _, a, _, _, off, _, _ in regs:
-            flat[off:off + a.size] = a.reshape(-1)
-        stream = torch.cuda.current_stream(dev)
-        with torch.cuda.device(dev):
-            raw = torch.from_numpy(flat).to(dev)
-            draw = torch.empty(max(n_out, 1), dtype=torch.float32, device=dev)      # (every window sample is written by the library)
-            pf = [torch.zeros(B, 1, L, F, device=dev) for L in n_bins]
-            cf = [torch.zeros(B, S, L, F, device=dev) for L in n_bins]
-            pm = [torch.ones(B, L, dtype=torch.uint8, device=dev) for L in n_bins]
-            cm = [torch.ones(B, S, L, dtype=torch.uint8, device=dev) for L in n_bins]      # dummy slots stay fully masked
-            im = torch.ones(B, T, T, dtype=torch.uint8)
-            freq = torch.zeros(B, T, T)
-            for i, gene in enumerate(ids):
-                g = ds.genes[gene]
-                n_part = len(g["pcres"])
-                im[i, :n_part + 1, :n_part + 1] = 0
-                for s, sc in enumerate(g["scores"]):
-                    freq[i, 0, s + 1] = sc
-            im, freq = im.to(dev), freq.to(dev)
-            fj = np.zeros(len(regs), dtype=BIN_JOB_MULTI)
-            for k, (i, s, flip, a, c0, nc, off, _, _) in enumerate(regs):
-                fj[k]["raw"], fj[k]["ld"], fj[k]["col0"], fj[k]["ncols"], fj[k]["flip"] = raw.data_ptr() + 2 * off, a.shape[1], c0, nc, int(flip)
-                for r in range(nres):
-                    out = pf[r][i, 0] if s < 0 else cf[r][i, s]
-                    msk = pm[r][i] if s < 0 else cm[r][i, s]
-                    fj[k]["out"][order.index(r)], fj[k]["mask"][order.index(r)] = out.data_ptr(), msk.data_ptr()
-            tab = torch.from_numpy(fj.view(np.uint8)).to(dev)
-            _lib.check(L_.cf_bin_regions_multi(C.c_void_p(tab.data_ptr()), len(regs), F, nres, cb, cl, int(max_cols), stream.cuda_stream),
-                       "cf_bin_regions_multi")
+        ch = _RawChunk(model, ds, ids, binsizes, n_bins)
+        pf, cf = ch.pf, ch.cf
+        with torch.cuda.device(ch.dev):
             # the backward of the model writes the flat gradient buffer and publishes it as the parameters' .grad: both are put back
             named = model._named()
             kept = {k: p.grad for k, p in named.items()}
@@ -146,9 +212,7 @@ def raw_signal_gradients(model, dataset, genes=None, target=None, times_input=Fa
                 for t in pf + cf:
                     t.requires_grad_(True)
                 with torch.enable_grad():
-                    logits = model({b: pf[r] for r, b in enumerate(binsizes)}, {b: pm[r] for r, b in enumerate(binsizes)},
-                                   {b: cf[r] for r, b in enumerate(binsizes)}, {b: cm[r] for r, b in enumerate(binsizes)},
-                                   {b: im for b in binsizes}, freq)
+                    logits = model(*ch.model_args())
                     logits[:, target].sum().backward()
             finally:
                 model._gflat.copy_(kept_flat)
@@ -158,28 +222,50 @@ def raw_signal_gradients(model, dataset, genes=None, target=None, times_input=Fa
             dp, dc = [t.grad for t in pf], [t.grad for t in cf]
             if any(t is None or not t.is_contiguous() for t in dp + dc):
                 raise RuntimeError("raw_signal_gradients: the backward pass left no gradient for a binned input")
-            bj = np.zeros(len(regs), dtype=BIN_GRAD_JOB)
-            for k, (i, s, flip, a, c0, nc, off, ooff, ld_out) in enumerate(regs):
-                for name in ("raw", "ld", "col0", "ncols", "flip"):
-                    bj[k][name] = fj[k][name]
-                for r in range(nres):
-                    bj[k]["dfeat"][order.index(r)] = (dp[r][i, 0] if s < 0 else dc[r][i, s]).data_ptr()
-                bj[k]["draw"], bj[k]["ld_out"] = draw.data_ptr() + 4 * ooff, ld_out
-            tab2 = torch.from_numpy(bj.view(np.uint8)).to(dev)
-            _lib.check(L_.cf_bin_regions_multi_backward(C.c_void_p(tab2.data_ptr()), len(regs), F, nres, cb, cl, int(max_cols),
-                                                        1 if times_input else 0, stream.cuda_stream), "cf_bin_regions_multi_backward")
-            host = draw.cpu().numpy()
+            host = ch.backward(dp, dc, times_input)
             lg = logits.detach().cpu().numpy()
         per = [dict(gene_id=gene, logits=lg[i].copy(), promoter=None, pcres=[], regions=[]) for i, gene in enumerate(ids)]
-        for i, s, flip, a, c0, nc, off, ooff, ld_out in regs:
-            track = host[ooff:ooff + F * ld_out].reshape(F, ld_out)[:, :nc].copy()
-            g = ds.genes[ids[i]]
-            if s < 0:
-                chrom, tss, _ = g["tss"]
-                per[i]["promoter"] = track
-                per[i]["regions"].append((chrom, tss - 20000 + c0, tss - 20000 + c0 + nc))
-            else:
-                per[i]["pcres"].append(track)
-                per[i]["regions"].append(tuple(g["pcres"][s]))
-        for d in per:
+        for d in ch.scatter(host, per):
+            yield d
+
+
+def raw_integrated_gradients(model, dataset, genes=None, target=None, n_steps=50, method="gausslegendre", bsz=None):
+    """Integrated gradients in raw-signal space: the attribution of logit column `target` (default: 1 for the classifier, 0 for the
+    regressor) to every sample of the RAW histone signals of a ChromoformerDataset, along the path a * x from the zero signal, with the
+    nodes and weights of ig_quadrature(method, n_steps).  Binning is linear and followed by log(1 + .), so along the path a bin of
+    mean m has the feature log1p(a m), and with g_k the input gradient at node k and C = sum_k g_k / (1 + a_k m):
+
+        attr  = m * C                                             per bin: IG with respect to the bin mean (complete)
+        IG_raw[f, s] = x[f, s] * sum_r C_r[p_r(s), f] / cnt       per sample: each bin's attr spread over its samples in proportion to x
+
+    A generator over `genes` like raw_signal_gradients, in chunks of at most min(bsz, model.max_batch) genes; per chunk
+
+        raw regions -> HBM -> cf_bin_regions_multi -> cf_integrated_gradients_raw over the features (frequencies and masks held at the
+        gene's) -> cf_bin_regions_multi_backward(times_input = 1) with dfeat pointing at its `coeff` = (1 + m) * C
+
+    and per gene it yields the dict of raw_signal_gradients (gene_id, logits, promoter, pcres, regions; the tracks now hold IG_raw) plus
+
+        baseline_logits   float32 [n_out]: the prediction on the zero signal (same masks and frequencies)
+        delta             float32 scalar: sum of the per-bin attr - (logits - baseline_logits)[target], the quadrature error; the tracks
+                          sum to the same total up to fp32 rounding
+
+    Limits: the zero-signal baseline only; binned features below ~80 (expm1 in fp32; preprocessed signals are far below); a negative
+    signal with 1 + a m <= 0 gives inf / NaN as the forward's log does.  Parameters, their .grad, the flat gradient buffer and the
+    optimiser state are left as they are; the pass overwrites the activations a grad-enabled model(...) keeps for its backward."""
+    import torch
+    ds = dataset
+    binsizes, n_bins, target, genes, chunk = _raw_check("raw_integrated_gradients", model, ds, genes, target, bsz)
+    ig_quadrature(method, n_steps)      # (refuses an unknown method or node count before anything is loaded)
+    for lo in range(0, len(genes), chunk):
+        ids = genes[lo:lo + chunk]
+        ch = _RawChunk(model, ds, ids, binsizes, n_bins)
+        with torch.cuda.device(ch.dev):
+            attr, info = model.integrated_gradients(*ch.model_args(), target=target, n_steps=n_steps, method=method,
+                                                    inputs=("promoter_feats", "pcre_feats"), path="signal")
+            co = info["coeff"]
+            host = ch.backward([co["promoter_feats"][b] for b in binsizes], [co["pcre_feats"][b] for b in binsizes], True)
+            lg, lb, dl = (info[k].cpu().numpy() for k in ("logits", "baseline_logits", "delta"))
+        per = [dict(gene_id=gene, logits=lg[i].copy(), baseline_logits=lb[i].copy(), delta=dl[i].copy(), promoter=None, pcres=[], regions=[])
+               for i, gene in enumerate(ids)]
+        for d in ch.scatter(host, per):
             yield d

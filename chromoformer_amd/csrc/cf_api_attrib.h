@@ -292,46 +292,59 @@ static int intg_alloc(cf_handle* h, int n_steps) {
 // hand-written loop of grad-enabled model(...) calls on the batch.  Frequency-only path: the trunk once (save = 1, the launches of cf_forward's first part) and its output stashed, then
 // per chunk k_ig_expand (stashed rows, masks, frequencies, dlogits), the Regulation + head forward, backward parts 1 and 2,
 // k_dfreq_sum, k_ig_accumulate.
-extern "C" int cf_integrated_gradients(cf_handle* h, const cf_batch* bt, const cf_ig_opts* o, const cf_input_grads* out,
-                                       float* logits_x, float* logits_base, float* delta, void* stream) {
-    if (!h) return fail("cf_integrated_gradients: null handle");
-    if (!bt) return fail("cf_integrated_gradients: null batch");
-    if (!o) return fail("cf_integrated_gradients: null opts");
-    if (!out) return fail("cf_integrated_gradients: null out");
-    if (!logits_x || !logits_base || !delta) return fail("cf_integrated_gradients: null logits_x / logits_base / delta");
+//
+// raw: the signal path of the feature segments (cf_integrated_gradients_raw: k_ig_expand_raw, k_ig_accumulate_raw with the node table and
+// the optional second output `coeff`); everything else -- chunking, buffers, launches -- is shared.
+static int integrated_gradients_impl(cf_handle* h, const cf_batch* bt, const cf_ig_opts* o, const cf_input_grads* out, const cf_input_grads* coeff,
+                                     float* logits_x, float* logits_base, float* delta, void* stream, bool raw, const char* who) {
+    if (!h) return fail("%s: null handle", who);
+    if (!bt) return fail("%s: null batch", who);
+    if (!o) return fail("%s: null opts", who);
+    if (!out) return fail("%s: null out", who);
+    if (!logits_x || !logits_base || !delta) return fail("%s: null logits_x / logits_base / delta", who);
     const cf_config& c = h->cfg;
     const int nres = c.n_res, S = c.i_max, T = S + 1, F = c.n_feats, kD = c.d_emb, cap = c.max_batch;
-    if (o->n_steps < 1) return fail("cf_integrated_gradients: n_steps = %d: at least 1 quadrature node", o->n_steps);
-    if (!o->alphas || !o->weights) return fail("cf_integrated_gradients: null alphas / weights");
-    if (o->target < 0 || o->target >= c.n_out) return fail("cf_integrated_gradients: target = %d outside [0, n_out = %d)", o->target, c.n_out);
+    if (o->n_steps < 1) return fail("%s: n_steps = %d: at least 1 quadrature node", who, o->n_steps);
+    if (!o->alphas || !o->weights) return fail("%s: null alphas / weights", who);
+    if (o->target < 0 || o->target >= c.n_out) return fail("%s: target = %d outside [0, n_out = %d)", who, o->target, c.n_out);
     if (o->interpolate & ~(CF_IG_PROMOTER | CF_IG_PCRE | CF_IG_FREQ) || !o->interpolate)
-        return fail("cf_integrated_gradients: interpolate = %d: a non-empty mask of CF_IG_PROMOTER | CF_IG_PCRE | CF_IG_FREQ", o->interpolate);
-    if (bt->B > cap) return fail("cf_integrated_gradients: batch size %d exceeds max_batch=%d", bt->B, cap);
+        return fail("%s: interpolate = %d: a non-empty mask of CF_IG_PROMOTER | CF_IG_PCRE | CF_IG_FREQ", who, o->interpolate);
+    if (bt->B > cap) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, cap);
     const bool ip = o->interpolate & CF_IG_PROMOTER, ic = o->interpolate & CF_IG_PCRE, ifr = o->interpolate & CF_IG_FREQ;
+    if (raw) {
+        if (!ip && !ic) return fail("%s: interpolate = %d: the signal path needs CF_IG_PROMOTER or CF_IG_PCRE (frequencies alone: cf_integrated_gradients)", who, o->interpolate);
+        for (int r = 0; r < kMaxRes; ++r) {
+            if (o->base_promoter_feats[r] || o->base_pcre_feats[r])
+                return fail("%s: base_promoter_feats / base_pcre_feats[%d]: the signal path starts at the zero signal; a feature baseline is not accepted", who, r);
+            if (coeff && ((coeff->promoter_feats[r] && (!ip || r >= nres)) || (coeff->pcre_feats[r] && (!ic || r >= nres))))
+                return fail("%s: coeff promoter_feats / pcre_feats[%d]: given for an input that is not interpolated", who, r);
+        }
+        if (coeff && coeff->interaction_freq) return fail("%s: coeff interaction_freq: interaction_freq has no signal path, so no coefficient", who);
+    }
     for (int r = 0; r < kMaxRes; ++r) {
         if (r >= nres && (out->promoter_feats[r] || out->pcre_feats[r] || o->base_promoter_feats[r] || o->base_pcre_feats[r]))
-            return fail("cf_integrated_gradients: promoter_feats / pcre_feats[%d]: the model has %d resolutions", r, nres);
+            return fail("%s: promoter_feats / pcre_feats[%d]: the model has %d resolutions", who, r, nres);
         if (r < nres && (out->promoter_feats[r] != nullptr) != ip)
-            return fail("cf_integrated_gradients: promoter_feats[%d]: the output must be given exactly when promoter_feats is interpolated", r);
+            return fail("%s: promoter_feats[%d]: the output must be given exactly when promoter_feats is interpolated", who, r);
         if (r < nres && (out->pcre_feats[r] != nullptr) != ic)
-            return fail("cf_integrated_gradients: pcre_feats[%d]: the output must be given exactly when pcre_feats is interpolated", r);
+            return fail("%s: pcre_feats[%d]: the output must be given exactly when pcre_feats is interpolated", who, r);
     }
     if ((out->interaction_freq != nullptr) != ifr)
-        return fail("cf_integrated_gradients: interaction_freq: the output must be given exactly when interaction_freq is interpolated");
+        return fail("%s: interaction_freq: the output must be given exactly when interaction_freq is interpolated", who);
     if (ip && h->embed_dense)
-        return fail("cf_integrated_gradients: promoter_feats: input gradients are implemented for embed.n_layers = 1 (the centre-row Embedding); "
-                    "this model has embed.n_layers = %d (the all-rows path keeps no first-layer input-row gradient)", c.embed_layers);
+        return fail("%s: promoter_feats: input gradients are implemented for embed.n_layers = 1 (the centre-row Embedding); "
+                    "this model has embed.n_layers = %d (the all-rows path keeps no first-layer input-row gradient)", who, c.embed_layers);
     if (ifr && h->reg_fused && !h->reg_dfreq_ok)
-        return fail("cf_integrated_gradients: interaction_freq: the fused Regulation backward variant could not be configured");
-    if (!h->grads) return fail("cf_integrated_gradients: no gradient buffer bound (the backward workspace is set up by cf_bind; the buffer is not written)");
-    if (h->rider.armed || h->rider.done) return fail("cf_integrated_gradients: riders are armed for a training step (cf_rider_arm); finish the step first");
+        return fail("%s: interaction_freq: the fused Regulation backward variant could not be configured", who);
+    if (!h->grads) return fail("%s: no gradient buffer bound (the backward workspace is set up by cf_bind; the buffer is not written)", who);
+    if (h->rider.armed || h->rider.done) return fail("%s: riders are armed for a training step (cf_rider_arm); finish the step first", who);
     if (check_batch(h, bt)) return -1;
-    const size_t smem = ip || ic ? input_grad_prepare(h, "cf_integrated_gradients") : 0;
+    const size_t smem = ip || ic ? input_grad_prepare(h, who) : 0;
     if ((ip || ic) && !smem) return -1;
     if (intg_alloc(h, o->n_steps)) return -1;
     hipStream_t st = (hipStream_t)stream;
     const int B = bt->B, n = o->n_steps, V = n + 2, TT = T * T;
-    const bool freq_only = o->interpolate == CF_IG_FREQ && h->intg_trunk_once;
+    const bool freq_only = o->interpolate == CF_IG_FREQ && h->intg_trunk_once;      // (never on the signal path: a feature bit is set)
     HIP_TRY(hipMemcpyAsync(h->intg_tab, o->alphas, n * sizeof(float), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(h->intg_tab + h->intg_cap, o->weights, n * sizeof(float), hipMemcpyHostToDevice, st));
     long long n_fwd = 0, n_bwd = 0;
@@ -384,6 +397,11 @@ extern "C" int cf_integrated_gradients(cf_handle* h, const cf_batch* bt, const c
     aa.logits_b = logits_base;
     aa.part = h->intg_part;
     aa.V = V, aa.n_out = c.n_out, aa.bcast = ea.bcast;
+    IgAccRawArgs ra;
+    memset(&ra, 0, sizeof ra);
+    ra.alpha = h->intg_tab;
+    if (raw && coeff)
+        for (int r = 0; r < nres; ++r) ra.coeff[r] = coeff->promoter_feats[r], ra.coeff[kMaxRes + r] = coeff->pcre_feats[r];
     // k_attc2 takes as many regions per workgroup as for the caller's B genes; the all-rows Embedding backward writes parameter gradients: not run
     PassOpts po;
     po.dfreq = ifr ? h->dfreq_part : nullptr;
@@ -400,8 +418,13 @@ extern "C" int cf_integrated_gradients(cf_handle* h, const cf_batch* bt, const c
             const int nr = std::min(cap, B * V - g0);
             l0 = g_launches;
             ea.g0 = g0;
-            hipLaunchKernelGGL(k_ig_expand, dim3(nr, nres), dim3(kIgxThreads), 0, st, ea);
-            LAUNCH_CHECK("k_ig_expand");
+            if (raw) {
+                hipLaunchKernelGGL(k_ig_expand_raw, dim3(nr, nres), dim3(kIgxThreads), 0, st, ea);
+                LAUNCH_CHECK("k_ig_expand_raw");
+            } else {
+                hipLaunchKernelGGL(k_ig_expand, dim3(nr, nres), dim3(kIgxThreads), 0, st, ea);
+                LAUNCH_CHECK("k_ig_expand");
+            }
             cb.B = nr;
             if ((!freq_only && forward_trunk(h, &cb, 1, st, B)) || forward_reg_head(h, &cb, h->intg_logits, 1, st, nullptr)) return -1;
             n_fwd += g_launches - l0;
@@ -417,8 +440,15 @@ extern "C" int cf_integrated_gradients(cf_handle* h, const cf_batch* bt, const c
             }
             aa.g0 = g0;
             aa.n = nr;
-            hipLaunchKernelGGL(k_ig_accumulate, dim3((g0 + nr - 1) / V - g0 / V + 1, kIgSlices), dim3(kIgxThreads), 0, st, aa);
-            LAUNCH_CHECK("k_ig_accumulate");
+            const dim3 acc_grid((g0 + nr - 1) / V - g0 / V + 1, kIgSlices);
+            if (raw) {
+                ra.a = aa;
+                hipLaunchKernelGGL(k_ig_accumulate_raw, acc_grid, dim3(kIgxThreads), 0, st, ra);
+                LAUNCH_CHECK("k_ig_accumulate_raw");
+            } else {
+                hipLaunchKernelGGL(k_ig_accumulate, acc_grid, dim3(kIgxThreads), 0, st, aa);
+                LAUNCH_CHECK("k_ig_accumulate");
+            }
             n_bwd += g_launches - l0;
         }
         l0 = g_launches;
@@ -435,4 +465,16 @@ extern "C" int cf_integrated_gradients(cf_handle* h, const cf_batch* bt, const c
     h->n_fwd = (int)n_fwd;
     h->n_bwd = (int)n_bwd;
     return rc ? -1 : 0;
+}
+
+extern "C" int cf_integrated_gradients(cf_handle* h, const cf_batch* bt, const cf_ig_opts* o, const cf_input_grads* out,
+                                       float* logits_x, float* logits_base, float* delta, void* stream) {
+    return integrated_gradients_impl(h, bt, o, out, nullptr, logits_x, logits_base, delta, stream, false, "cf_integrated_gradients");
+}
+
+// Integrated gradients along the zero-signal path a m in bin-mean space (cf_ig.h, kIgSignal): the launches of cf_integrated_gradients
+// with k_ig_expand_raw / k_ig_accumulate_raw in place of k_ig_expand / k_ig_accumulate.
+extern "C" int cf_integrated_gradients_raw(cf_handle* h, const cf_batch* bt, const cf_ig_opts* o, const cf_input_grads* out,
+                                           const cf_input_grads* coeff, float* logits_x, float* logits_base, float* delta, void* stream) {
+    return integrated_gradients_impl(h, bt, o, out, coeff, logits_x, logits_base, delta, stream, true, "cf_integrated_gradients_raw");
 }

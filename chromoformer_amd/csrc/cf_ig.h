@@ -20,12 +20,25 @@
 //                    gene, each a fixed subset of the gene's elements.
 //   k_ig_delta       per gene, once per call: the slice sums in slice order, minus F(x)[t] - F(xb)[t].
 // The order of every sum depends on the gene's layout alone: the same bits whatever max_batch is.
+//
+// Signal path (cf_integrated_gradients_raw; template parameter kIgSignal, the kernels k_ig_expand_raw / k_ig_accumulate_raw).  The two
+// feature segments hold u = log(1 + m), m >= 0 the mean of a bin of the raw signal; the baseline is the empty signal and the path
+// is the straight line a m in MEAN space, which is curved in feature space:
+//     u_k   = log1p(a_k expm1(u))                               the row of node k (v = 0: u verbatim, v = 1: zeros)
+//     g_k   = d(w_k logits[:, t]) / d u_k                       the same backward
+//     C     = (g_0 / (1 + a_0 m) + g_1 / (1 + a_1 m)) + ...     fp32, k order, m = expm1f(u); no contraction
+//     attr  = m C                                               integrated gradients with respect to the bin mean: complete
+//     coeff = (1 + m) C                                         second output: dfeat of cf_bin_regions_multi_backward(times_input = 1),
+//                                                               which divides by cnt (1 + m) and multiplies by the raw sample
+// interaction_freq keeps the straight path and its baseline.  Between a gene's chunks `out` holds the running C; the last row turns it
+// into attr (and writes coeff).  The row helpers ig_row / ig_acc are templates on the path; the linear kernels' code is unchanged.
 #pragma once
 
 namespace cf {
 
 constexpr int kIgxThreads = 256;
 constexpr int kIgSegs = 2 * kMaxRes + 1;      // promoter_feats[r], pcre_feats[r], interaction_freq
+constexpr int kIgLinear = 0, kIgSignal = 1;   // path of a feature segment: xb + a (x - xb) | log1p(a expm1(x)) from the zero signal
 
 struct IgSeg {
     const float* x;           // the caller's input, [B, len]
@@ -56,12 +69,20 @@ struct IgExpandArgs {
     int g0, V, S, TT, n_out, target, nres, bcast, freq_only, row4;
 };
 
-// dst = x (v = 0), xb (v = 1), xb + a (x - xb) (interior) or x (not interpolated); float4 where the row allows
+// the signal path's interior value of one element
+__device__ __forceinline__ float ig_signal(float a, float x) {
+#pragma clang fp contract(off)
+    return log1pf(a * expm1f(x));
+}
+
+// dst = x (v = 0), xb (v = 1), xb + a (x - xb) (interior) or x (not interpolated); float4 where the row allows.  PATH = kIgSignal:
+// xb is the zero signal (s.xb is not read) and the interior is log1p(a expm1(x))
+template <int PATH>
 __device__ __forceinline__ void ig_row(const IgSeg& s, int b, int i, int v, float a, bool bcast) {
 #pragma clang fp contract(off)
     const int n = s.len;
     const float* __restrict__ x = s.x + (size_t)b * n;
-    const float* __restrict__ xb = s.xb ? s.xb + (bcast ? (size_t)0 : (size_t)b * n) : nullptr;
+    const float* __restrict__ xb = PATH == kIgLinear && s.xb ? s.xb + (bcast ? (size_t)0 : (size_t)b * n) : nullptr;
     float* __restrict__ d = s.row + (size_t)i * n;
     const int mode = !s.out || v == 0 ? 0 : v == 1 ? 1 : 2;
     const bool vec = (n & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(xb) | reinterpret_cast<uintptr_t>(d)) & 15) == 0;
@@ -75,18 +96,20 @@ __device__ __forceinline__ void ig_row(const IgSeg& s, int b, int i, int v, floa
             float4 o;
             if (mode == 0) o = xv;
             else if (mode == 1) o = bv;
+            else if (PATH == kIgSignal) o = make_float4(ig_signal(a, xv.x), ig_signal(a, xv.y), ig_signal(a, xv.z), ig_signal(a, xv.w));
             else o = make_float4(bv.x + a * (xv.x - bv.x), bv.y + a * (xv.y - bv.y), bv.z + a * (xv.z - bv.z), bv.w + a * (xv.w - bv.w));
             d4[e] = o;
         }
     } else {
         for (int e = threadIdx.x; e < n; e += kIgxThreads) {
             const float xv = x[e], bv = xb ? xb[e] : 0.f;
-            d[e] = mode == 0 ? xv : mode == 1 ? bv : bv + a * (xv - bv);
+            d[e] = mode == 0 ? xv : mode == 1 ? bv : PATH == kIgSignal ? ig_signal(a, xv) : bv + a * (xv - bv);
         }
     }
 }
 
-__global__ __launch_bounds__(kIgxThreads) void k_ig_expand(IgExpandArgs a) {
+template <int PATH>
+__device__ __forceinline__ void ig_expand(const IgExpandArgs a) {
     const int i = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
     const int gv = a.g0 + i, b = gv / a.V, v = gv - b * a.V;
     const float alpha = v >= 2 ? a.alpha[v - 2] : 0.f;
@@ -97,8 +120,8 @@ __global__ __launch_bounds__(kIgxThreads) void k_ig_expand(IgExpandArgs a) {
         for (int k = tid; k < a.row4; k += kIgxThreads) dst[k] = src[k];
     } else {
         const int L = a.L[r], S = a.S;
-        ig_row(a.seg[r], b, i, v, alpha, bc);
-        ig_row(a.seg[kMaxRes + r], b, i, v, alpha, bc);
+        ig_row<PATH>(a.seg[r], b, i, v, alpha, bc);
+        ig_row<PATH>(a.seg[kMaxRes + r], b, i, v, alpha, bc);
         const int PL = a.pm_rows[r] * L;
         for (int k = tid; k < PL; k += kIgxThreads) a.pm_out[r][(size_t)i * PL + k] = a.pm_in[r][(size_t)b * a.pm_stride[r] + k];
         for (int k = tid; k < S * L; k += kIgxThreads) {
@@ -108,10 +131,12 @@ __global__ __launch_bounds__(kIgxThreads) void k_ig_expand(IgExpandArgs a) {
     }
     for (int k = tid; k < a.TT; k += kIgxThreads) a.im_out[r][(size_t)i * a.TT + k] = a.im_in[r][(size_t)b * a.TT + k];
     if (r == 0) {
-        ig_row(a.seg[2 * kMaxRes], b, i, v, alpha, bc);
+        ig_row<kIgLinear>(a.seg[2 * kMaxRes], b, i, v, alpha, bc);
         for (int k = tid; k < a.n_out; k += kIgxThreads) a.dlogits[(size_t)i * a.n_out + k] = v >= 2 && k == a.target ? a.weight[v - 2] : 0.f;
     }
 }
+__global__ __launch_bounds__(kIgxThreads) void k_ig_expand(IgExpandArgs a) { ig_expand<kIgLinear>(a); }
+__global__ __launch_bounds__(kIgxThreads) void k_ig_expand_raw(IgExpandArgs a) { ig_expand<kIgSignal>(a); }
 
 constexpr int kIgSlices = 32;      // workgroups per gene in k_ig_accumulate (a gene's ~31.5 k elements: ~1 float4 per thread)
 
@@ -124,20 +149,69 @@ struct IgAccArgs {
     int g0, n, V, n_out, bcast;
 };
 
+struct IgAccRawArgs {                  // k_ig_accumulate_raw: the arguments above, the node table and the second output
+    IgAccArgs a;
+    const float* alpha;                // device [n_steps]
+    float* coeff[2 * kMaxRes];         // per feature segment [B, len]; nullptr: not wanted
+};
+
 // rows i0 .. i0 + nv - 1 of the chunk are variants v0 .. v0 + nv - 1 (all interior) of gene b; this workgroup takes the elements
 // (float4 or scalar) slice, slice + kIgSlices, ... of the segment in blocks of kIgxThreads.  Returns this thread's sum of attr when
-// the last of the rows is the gene's last row, else 0
-__device__ __forceinline__ float ig_acc(const IgSeg& s, int b, int i0, int v0, int nv, int V, bool bcast, int slice) {
+// the last of the rows is the gene's last row, else 0.  PATH = kIgSignal: row k adds g_k / (1 + alpha[v0 - 2 + k] m), m = expm1f(x),
+// the last row writes m acc (and (1 + m) acc into coeff)
+template <int PATH>
+__device__ __forceinline__ float ig_acc(const IgSeg& s, float* coeff, const float* alpha, int b, int i0, int v0, int nv, int V, bool bcast, int slice) {
 #pragma clang fp contract(off)
     if (!s.out || nv <= 0) return 0.f;
     const int n = s.len;
     const bool first = v0 == 2, last = v0 + nv == V;
     const float* __restrict__ x = s.x + (size_t)b * n;
-    const float* __restrict__ xb = s.xb ? s.xb + (bcast ? (size_t)0 : (size_t)b * n) : nullptr;
+    const float* __restrict__ xb = PATH == kIgLinear && s.xb ? s.xb + (bcast ? (size_t)0 : (size_t)b * n) : nullptr;
     const float* __restrict__ g = s.grad + (size_t)i0 * n;
     float* __restrict__ o = s.out + (size_t)b * n;
+    float* __restrict__ co = PATH == kIgSignal && coeff ? coeff + (size_t)b * n : nullptr;
     float part = 0.f;
     const int e0 = slice * kIgxThreads + threadIdx.x, step = kIgSlices * kIgxThreads;
+    if (PATH == kIgSignal) {
+        const bool vec = (n & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(o) |
+                                           reinterpret_cast<uintptr_t>(co)) & 15) == 0;
+        if (vec) {
+            const int n4 = n / 4;
+            for (int e = e0; e < n4; e += step) {
+                const float4 xv = reinterpret_cast<const float4*>(x)[e];
+                const float4 m = make_float4(expm1f(xv.x), expm1f(xv.y), expm1f(xv.z), expm1f(xv.w));
+                float4 acc = first ? make_float4(0.f, 0.f, 0.f, 0.f) : reinterpret_cast<const float4*>(o)[e];
+                for (int k = 0; k < nv; ++k) {
+                    const float4 gk = reinterpret_cast<const float4*>(g + (size_t)k * n)[e];
+                    const float ak = alpha[v0 - 2 + k];
+                    const float4 t = make_float4(gk.x / (1.0f + ak * m.x), gk.y / (1.0f + ak * m.y), gk.z / (1.0f + ak * m.z), gk.w / (1.0f + ak * m.w));
+                    acc = first && k == 0 ? t : make_float4(acc.x + t.x, acc.y + t.y, acc.z + t.z, acc.w + t.w);
+                }
+                if (last) {
+                    if (co) reinterpret_cast<float4*>(co)[e] = make_float4((1.0f + m.x) * acc.x, (1.0f + m.y) * acc.y, (1.0f + m.z) * acc.z, (1.0f + m.w) * acc.w);
+                    acc = make_float4(m.x * acc.x, m.y * acc.y, m.z * acc.z, m.w * acc.w);
+                    part += ((acc.x + acc.y) + acc.z) + acc.w;
+                }
+                reinterpret_cast<float4*>(o)[e] = acc;
+            }
+        } else {
+            for (int e = e0; e < n; e += step) {
+                const float m = expm1f(x[e]);
+                float acc = first ? 0.f : o[e];
+                for (int k = 0; k < nv; ++k) {
+                    const float t = g[(size_t)k * n + e] / (1.0f + alpha[v0 - 2 + k] * m);
+                    acc = first && k == 0 ? t : acc + t;
+                }
+                if (last) {
+                    if (co) co[e] = (1.0f + m) * acc;
+                    acc = m * acc;
+                    part += acc;
+                }
+                o[e] = acc;
+            }
+        }
+        return part;
+    }
     const bool vec = (n & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(xb) | reinterpret_cast<uintptr_t>(g) |
                                        reinterpret_cast<uintptr_t>(o)) & 15) == 0;
     if (vec) {
@@ -184,7 +258,39 @@ __global__ __launch_bounds__(kIgxThreads) void k_ig_accumulate(IgAccArgs a) {
         }
     const int v0 = max(vlo, 2), nv = vhi - v0;
     float part = 0.f;
-    for (int s = 0; s < kIgSegs; ++s) part += ig_acc(a.seg[s], b, irow + v0, v0, nv, a.V, bc, slice);
+    for (int s = 0; s < kIgSegs; ++s) part += ig_acc<kIgLinear>(a.seg[s], nullptr, nullptr, b, irow + v0, v0, nv, a.V, bc, slice);
+    if (vhi != a.V || nv <= 0) return;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) part += __shfl_xor(part, o, 64);
+    if ((tid & 63) == 0) red[tid >> 6] = part;
+    __syncthreads();
+    if (tid == 0) {
+        float sum = 0.f;
+        for (int k = 0; k < kIgxThreads / 64; ++k) sum += red[k];
+        a.part[(size_t)b * kIgSlices + slice] = sum;
+    }
+}
+
+// k_ig_accumulate for the signal path: the feature segments divide each row's gradient by 1 + a_k m (node table in the arguments) and
+// finish with attr = m acc, coeff = (1 + m) acc; interaction_freq as in k_ig_accumulate.  (A kernel of its own, not a second
+// instantiation of one body: k_ig_accumulate's code stays exactly what it was.)
+__global__ __launch_bounds__(kIgxThreads) void k_ig_accumulate_raw(IgAccRawArgs ra) {
+#pragma clang fp contract(off)
+    __shared__ float red[kIgxThreads / 64];
+    const IgAccArgs& a = ra.a;
+    const int b = a.g0 / a.V + blockIdx.x, slice = blockIdx.y, tid = threadIdx.x;
+    const int vlo = max(0, a.g0 - b * a.V), vhi = min(a.V, a.g0 + a.n - b * a.V);      // the gene's variants in this chunk: [vlo, vhi)
+    const int irow = b * a.V - a.g0;                                                     // chunk row of variant 0 (may be negative)
+    const bool bc = a.bcast != 0;
+    if (slice == 0)
+        for (int k = tid; k < a.n_out; k += kIgxThreads) {
+            if (vlo == 0) a.logits_x[(size_t)b * a.n_out + k] = a.logits[(size_t)irow * a.n_out + k];
+            if (vlo <= 1 && vhi > 1) a.logits_b[(size_t)b * a.n_out + k] = a.logits[(size_t)(irow + 1) * a.n_out + k];
+        }
+    const int v0 = max(vlo, 2), nv = vhi - v0;
+    float part = 0.f;
+    for (int s = 0; s < 2 * kMaxRes; ++s) part += ig_acc<kIgSignal>(a.seg[s], ra.coeff[s], ra.alpha, b, irow + v0, v0, nv, a.V, bc, slice);
+    part += ig_acc<kIgLinear>(a.seg[2 * kMaxRes], nullptr, nullptr, b, irow + v0, v0, nv, a.V, bc, slice);
     if (vhi != a.V || nv <= 0) return;
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) part += __shfl_xor(part, o, 64);

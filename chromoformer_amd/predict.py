@@ -195,20 +195,38 @@ def write_raw_saliency(model, dataset, bsz, saliency_dir, target=None, times_inp
         np.savez(os.path.join(saliency_dir, "%s.npz" % d["gene_id"]), **arrays)
 
 
+def write_raw_integrated_gradients(model, dataset, bsz, ig_dir, n_steps=50, method="gausslegendre", target=None):
+    """Integrated gradients in raw-signal space of every gene of a dataset (model.raw_integrated_gradients: zero-signal baseline, path
+    a * x) into `ig_dir`/<gene_id>.npz: the keys of write_raw_saliency (`promoter`, `pcre_<s>`, `regions`, `logits`; the tracks hold
+    the per-sample attributions) plus `baseline_logits` [n_out] and `delta` (the tracks' sum minus logits - baseline_logits at the
+    target: the quadrature error)."""
+    import os
+    os.makedirs(ig_dir, exist_ok=True)
+    require_raw_signals(dataset)
+    for d in model.raw_integrated_gradients(dataset, target=target, n_steps=n_steps, method=method, bsz=bsz):
+        arrays = {"promoter": d["promoter"], "logits": d["logits"], "baseline_logits": d["baseline_logits"], "delta": d["delta"],
+                  "regions": np.array(["%s:%d-%d" % tuple(r) for r in d["regions"]])}
+        for s, t in enumerate(d["pcres"]):
+            arrays["pcre_%d" % s] = t
+        np.savez(os.path.join(ig_dir, "%s.npz" % d["gene_id"]), **arrays)
+
+
 def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123, i_max=8, w_prom=40000, w_max=40000,
             binsizes=(2000, 500, 100), progress=False, store_path=None, attention_dir=None, embeddings_out=None,
             pcre_ablation_out=None, ig_dir=None, ig_steps=50, ig_method="gausslegendre", ig_target=None, raw_saliency_dir=None,
-            raw_saliency_target=None, raw_saliency_times_input=False):
+            raw_saliency_target=None, raw_saliency_times_input=False, raw_ig_dir=None):
     """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file.  attention_dir / embeddings_out: also
     write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps); pcre_ablation_out:
     the predictions with each pCRE deleted (write_pcre_ablation); ig_dir: integrated gradients of every gene
     (write_integrated_gradients); raw_saliency_dir: the gradient (or gradient x input) of the prediction with respect to the raw
-    signals, one .npz per gene (write_raw_saliency; needs the raw .npy files also when a packed store serves the predictions)."""
+    signals, one .npz per gene (write_raw_saliency; needs the raw .npy files also when a packed store serves the predictions);
+    raw_ig_dir: integrated gradients with respect to the raw signals, one .npz per gene (write_raw_integrated_gradients; ig_steps,
+    ig_method and ig_target apply; needs the raw .npy files too)."""
     seed_everything(seed)
     meta = pd.read_csv(meta_path)
     genes = meta.gene_id.tolist()
     raw_ds = None
-    if raw_saliency_dir:
+    if raw_saliency_dir or raw_ig_dir:
         raw_ds = ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=regression)
         require_raw_signals(raw_ds)      # (before anything is computed)
     from . import pack
@@ -237,6 +255,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         write_integrated_gradients(model, store, bsz, ig_dir, ig_steps, ig_method, ig_target)
     if raw_saliency_dir:
         write_raw_saliency(model, raw_ds, bsz, raw_saliency_dir, raw_saliency_target, raw_saliency_times_input)
+    if raw_ig_dir:
+        write_raw_integrated_gradients(model, raw_ds, bsz, raw_ig_dir, ig_steps, ig_method, ig_target)
     return meta, np.concatenate(preds).astype(np.float32)
 
 
@@ -263,6 +283,10 @@ def build_parser():
     ap.add_argument("--ig-steps", type=int, default=None, help="quadrature nodes of --ig-dir (default 50)")
     ap.add_argument("--ig-method", default=None, choices=METHODS, help="quadrature of --ig-dir (default gausslegendre)")
     ap.add_argument("--ig-target", type=int, default=None, help="logit column of --ig-dir (default 1 for the classifier, 0 with --regression)")
+    ap.add_argument("--raw-ig-dir", default=None, help="also write integrated gradients in raw-signal space (zero-signal baseline, path a * x): "
+                    "DIR/<gene_id>.npz with the keys of --raw-saliency-dir, the tracks holding the per-sample attributions, plus "
+                    "baseline_logits and delta (model.raw_integrated_gradients).  Takes --ig-steps, --ig-method and --ig-target; needs the "
+                    "raw .npy files, also next to a packed store")
     ap.add_argument("--raw-saliency-dir", default=None, help="also write raw-signal saliency: DIR/<gene_id>.npz with the gradient of the "
                     "prediction's logit with respect to the raw .npy signals (promoter [7, window], pcre_<s> [7, len], genomic orientation, "
                     "regions, logits; model.raw_signal_gradients).  Needs the raw .npy files, also next to a packed store")
@@ -279,8 +303,8 @@ def main(argv=None):
         ap.error("--raw-saliency-target / --raw-saliency-times-input need --raw-saliency-dir")
     if args.raw_saliency_target is not None and not 0 <= args.raw_saliency_target < (1 if args.regression else 2):
         ap.error("--raw-saliency-target must be in [0, %d)" % (1 if args.regression else 2))
-    if not args.ig_dir and (args.ig_steps is not None or args.ig_method is not None or args.ig_target is not None):
-        ap.error("--ig-steps / --ig-method / --ig-target need --ig-dir")
+    if not args.ig_dir and not args.raw_ig_dir and (args.ig_steps is not None or args.ig_method is not None or args.ig_target is not None):
+        ap.error("--ig-steps / --ig-method / --ig-target need --ig-dir or --raw-ig-dir")
     if args.ig_steps is not None and args.ig_steps < (2 if args.ig_method == "riemann_trapezoid" else 1):
         ap.error("--ig-steps must be at least %d" % (2 if args.ig_method == "riemann_trapezoid" else 1))
     if args.ig_target is not None and not 0 <= args.ig_target < (1 if args.regression else 2):
@@ -289,7 +313,8 @@ def main(argv=None):
                          attention_dir=args.attention_dir, embeddings_out=args.embeddings_out, pcre_ablation_out=args.pcre_ablation_out,
                          ig_dir=args.ig_dir, ig_steps=50 if args.ig_steps is None else args.ig_steps,
                          ig_method=args.ig_method or "gausslegendre", ig_target=args.ig_target, raw_saliency_dir=args.raw_saliency_dir,
-                         raw_saliency_target=args.raw_saliency_target, raw_saliency_times_input=args.raw_saliency_times_input)
+                         raw_saliency_target=args.raw_saliency_target, raw_saliency_times_input=args.raw_saliency_times_input,
+                         raw_ig_dir=args.raw_ig_dir)
     print("Predicting expressions for %d genes." % len(meta))
     meta["prediction"] = pred
     meta.to_csv(args.output, index=False)

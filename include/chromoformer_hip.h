@@ -249,6 +249,27 @@ typedef struct cf_ig_opts {
  * buffer (its workspace), armed riders. */
 int cf_integrated_gradients(cf_handle* h, const cf_batch* batch, const cf_ig_opts* opts, const cf_input_grads* out,
                             float* logits_x, float* logits_base, float* delta, void* stream);
+/* Integrated gradients in raw-signal space, zero-signal baseline (interpretation).  The feature inputs hold u = log(1 + m), m >= 0
+ * the mean of a bin of the raw signal x.  The path is x(a) = a x: linear in the bin means, curved in the features.  Same cf_ig_opts,
+ * rows, chunks, buffers and launches as cf_integrated_gradients, with k_ig_expand_raw / k_ig_accumulate_raw in place of k_ig_expand /
+ * k_ig_accumulate.  Per element of an interpolated feature input, with m = expm1f(u):
+ *   u_k   = log1pf(a_k m)                              the row of node k (fp32, each operation rounded); F(0) runs on zeros
+ *   g_k   = d(w_k logits[:, t]) / d u_k
+ *   C     = (g_0 / (1 + a_0 m) + g_1 / (1 + a_1 m)) + ...   fp32, in k order
+ *   attr  = m C           -> out:   integrated gradients with respect to the bin MEAN; complete: the attr of a gene (plus those of
+ *                                   interaction_freq, which keeps its straight path and baseline when its bit is set) sum to
+ *                                   F(x)[t] - F(0)[t] up to the quadrature error; delta is that sum minus the difference
+ *   coeff = (1 + m) C     -> coeff: dfeat for cf_bin_regions_multi_backward(times_input = 1), which divides by cnt (1 + m) and
+ *                                   multiplies by the sample: IG_raw[f, s] = x[f, s] sum_r C_r[p_r(s), f] / cnt, every bin's attr
+ *                                   spread over its samples in proportion to x
+ * `coeff` may be NULL, or have any of the feature fields of the interpolated inputs set (each OVERWRITTEN in full; exact zeros for
+ * padded bins and dummy slots, as in `out`).  Limits: the zero-signal baseline only; u < ~80 (expm1f overflows past 88); 1 + a m <= 0
+ * gives inf / NaN as the forward's log does.  Deterministic; the result does not depend on max_batch.
+ * Refused by name, before anything is launched: everything cf_integrated_gradients refuses; a non-NULL base_promoter_feats /
+ * base_pcre_feats; an `interpolate` without CF_IG_PROMOTER or CF_IG_PCRE; a coeff field set for an input that is not interpolated;
+ * a non-NULL coeff->interaction_freq. */
+int cf_integrated_gradients_raw(cf_handle* h, const cf_batch* batch, const cf_ig_opts* opts, const cf_input_grads* out,
+                                const cf_input_grads* coeff, float* logits_x, float* logits_base, float* delta, void* stream);
 /* torch.optim.AdamW.step (train.py:157, 196): decoupled weight decay, bias correction
  * from `step` (1-based), over [0, n_active). */
 int cf_adamw_step(cf_handle* h, float lr, float beta1, float beta2, float eps, float weight_decay,
