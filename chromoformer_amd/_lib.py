@@ -80,6 +80,11 @@ class cf_ig_opts(C.Structure):
 IG_PROMOTER, IG_PCRE, IG_FREQ = 1, 2, 4      # cf_ig_opts.interpolate
 
 
+class cf_scan_opts(C.Structure):
+    _fields_ = [("region", C.c_int), ("width", C.c_int), ("n_sets", C.c_int), ("mark_sets", C.c_void_p), ("scale", C.c_float),
+                ("flip", C.c_void_p), ("feats_out", C.c_void_p * MAX_RES)]
+
+
 class cf_store(C.Structure):
     _fields_ = [
         ("n_genes", C.c_longlong),
@@ -132,6 +137,7 @@ SYMBOLS = {
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_integrated_gradients_raw": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_ig_opts), C.POINTER(cf_input_grads),
                                               C.POINTER(cf_input_grads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cf_perturbation_scan": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_scan_opts), C.c_void_p, C.c_void_p]),
     "cf_adamw_step": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_longlong, C.c_void_p]),
     "cf_debug_copy": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p]),
     "cf_debug_names": (C.c_char_p, [C.c_void_p]),

@@ -269,3 +269,113 @@ def raw_integrated_gradients(model, dataset, genes=None, target=None, n_steps=50
                for i, gene in enumerate(ids)]
         for d in ch.scatter(host, per):
             yield d
+
+
+def scan_windows(start, end, binsize, width, n_win):
+    """Genomic [start, end) of windows 0 .. n_win - 1 of a region [start, end): window g begins at start + g * binsize and spans
+    `width` coarsest bins, its end clipped to the region -> int64 [n_win, 2]."""
+    g = np.arange(int(n_win), dtype=np.int64)
+    lo = int(start) + g * int(binsize)
+    return np.stack([lo, np.minimum(lo + int(width) * int(binsize), int(end))], axis=1).reshape(-1, 2)
+
+
+def perturbation_scan(model, dataset, genes=None, regions="promoter", scale=0.0, width=1, mark_sets=None, bsz=None, store=None):
+    """In-silico perturbation scan of the genes of a ChromoformerDataset (model.perturbation_scan per region, windows in genomic
+    coordinates): what the prediction becomes with the marks of a mark set scaled by `scale` in raw-signal space -- 0 erases, 2
+    doubles -- over each window of `width` coarsest bins of a region.  A generator over `genes` (ids; default: the dataset's) in
+    chunks of at most min(bsz, model.max_batch) genes; per gene it yields a dict of host arrays:
+
+        gene_id    the id
+        logits     float32 [n_out]: the unperturbed prediction
+        mark_sets  the sets, tuples of mark indices (default: each mark alone, then all together)
+        regions    [(chrom, start, end)] of the scanned regions the gene has: the promoter window (start = tss - 20000 +
+                   promoter_col0), then its pCREs
+        windows    per region int64 [n_win, 2]: genomic start and end of each REAL window, start + g * binsize_c, the end clipped to
+                   the region
+        scan       per region float32 [n_sets, n_win, n_out]: the logits with set k scaled over window g, genomic order
+
+    regions: "promoter", "all" (the promoter and every pCRE the gene has) or a list of region indices (0 the promoter, 1 + j pCRE
+    slot j; a slot the gene does not have is left out).  Strand and coordinates come from the dataset's metadata ('-' strand promoters
+    are stored mirrored: window 0 is still the genomic start).  The binned features come from `store` (a device-resident GeneStore
+    holding `genes` in order) if given, else from the packed store next to the raw files if one matches, else from the raw .npy
+    files binned on the device: the raw files are not required.  Parameters, gradients and optimiser state are left as they are; the
+    pass overwrites the activations a grad-enabled model(...) keeps for its backward."""
+    import copy
+
+    import torch
+
+    from . import pack
+    from .data import GeneStore, promoter_col0
+    ds = dataset
+    if model._handle is None:
+        raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
+    binsizes = [int(b) for b in ds.binsizes]
+    n_bins = [ds.w_max // b for b in binsizes]
+    if binsizes != list(model.binsizes) or n_bins != list(model.n_bins) or ds.i_max != model.i_max or ds.n_feats != model.n_feats:
+        raise ValueError("perturbation_scan: the dataset (binsizes %s, w_max %d, i_max %d, n_feats %d) does not match the model "
+                         "(binsizes %s, w_max %d, i_max %d, n_feats %d)" % (binsizes, ds.w_max, ds.i_max, ds.n_feats, list(model.binsizes),
+                                                                            model.w_max, model.i_max, model.n_feats))
+    genes = list(ds.target_genes if genes is None else genes)
+    missing = [g for g in genes if g not in ds.genes]
+    if missing:
+        raise KeyError("perturbation_scan: gene(s) %s are not in the dataset's metadata" % (missing[:5],))
+    S, F, dev = ds.i_max, ds.n_feats, model._device
+    if isinstance(regions, str):
+        if regions not in ("promoter", "all"):
+            raise ValueError("perturbation_scan: regions %r; choose 'promoter', 'all' or a list of region indices" % (regions,))
+        regions = [0] if regions == "promoter" else list(range(S + 1))
+    regions = [int(r) for r in regions]
+    if not regions or any(not 0 <= r <= S for r in regions):
+        raise ValueError("perturbation_scan: regions %s outside [0, i_max = %d]" % (regions, S))
+    if mark_sets is None:
+        mark_sets = [(f,) for f in range(F)] + [tuple(range(F))]
+    mark_sets = [tuple(int(f) for f in ms) for ms in mark_sets]
+    chunk = model._max_batch if bsz is None else max(1, min(int(bsz), model._max_batch))
+    rc = int(np.argmin(n_bins))
+    W, bc = n_bins[rc], binsizes[rc]
+    col0 = promoter_col0(ds)
+    if store is None:
+        packed = pack.find(ds.npy_dir, None, binsizes, S, ds.w_prom, ds.w_max, F, genes, meta=ds.meta)
+        if packed is not None:
+            store = packed.store(genes, device=dev, regression=False)
+        else:
+            sub = copy.copy(ds)
+            sub.target_genes = genes
+            store = GeneStore(sub, device=dev, resident=True)
+    if len(store) != len(genes):
+        raise ValueError("perturbation_scan: the store holds %d genes, the scan names %d" % (len(store), len(genes)))
+    for lo in range(0, len(genes), chunk):
+        ids = genes[lo:lo + chunk]
+        B = len(ids)
+        d = store.batch(list(range(lo, lo + B)))
+        args = tuple(d[k] for k in ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq"))
+        flip = [ds.genes[g]["tss"][2] != "+" for g in ids]
+        per = [dict(gene_id=g, logits=None, mark_sets=list(mark_sets), regions=[], windows=[], scan=[]) for g in ids]
+        for region in regions:
+            has = [region == 0 or region - 1 < len(ds.genes[g]["pcres"]) for g in ids]
+            if not any(has):
+                continue
+            out = model.perturbation_scan(*args, region=region, scale=scale, width=width, mark_sets=mark_sets,
+                                          flip=flip if region == 0 else None).cpu().numpy()
+            m = (d["promoter_pad_masks"][bc] if region == 0 else d["pcre_pad_masks"][bc][:, region - 1]).reshape(B, W).cpu().numpy() == 0
+            for i, g in enumerate(ids):
+                per[i]["logits"] = out[i, 0].copy()
+                if not has[i]:
+                    continue
+                real = np.flatnonzero(m[i])
+                n_win = int(real[-1] - real[0] + 1) if real.size else 0
+                if region == 0:
+                    chrom, tss, _ = ds.genes[g]["tss"]
+                    reg = (chrom, tss - 20000 + col0, tss - 20000 + col0 + min(ds.w_prom, 40000 - col0))
+                else:
+                    reg = tuple(ds.genes[g]["pcres"][region - 1])
+                per[i]["regions"].append(reg)
+                per[i]["windows"].append(scan_windows(reg[1], reg[2], bc, width, n_win))
+                per[i]["scan"].append(out[i, 1:].reshape(len(mark_sets), W, -1)[:, :n_win].copy())
+        if per[0]["logits"] is None:      # (no gene of the chunk has any of the regions: the prediction alone)
+            with torch.no_grad():
+                out = model(*args).cpu().numpy()
+            for i in range(B):
+                per[i]["logits"] = out[i].copy()
+        for p in per:
+            yield p

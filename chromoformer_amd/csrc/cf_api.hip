@@ -7,6 +7,7 @@
 #include "cf_attn_maps.h"
 #include "cf_ablate.h"
 #include "cf_ig.h"
+#include "cf_scan.h"
 #include "cf_x0_gather.h"
 
 #include <algorithm>

@@ -1,5 +1,5 @@
 // cf_api_attrib.h -- host side of the attribution entry points (input gradients, attention maps, pCRE deletion, integrated
-// gradients).  Part of cf_api.hip's single translation unit: included there behind the backward pass, not on its own.
+// gradients, perturbation scan).  Part of cf_api.hip's single translation unit: included there behind the backward pass, not on its own.
 #pragma once
 
 // k_input_grad's dynamic LDS size; the first call sets the kernel's attribute.  0: that failed (`who`: the entry point, for the error text).
@@ -477,4 +477,101 @@ extern "C" int cf_integrated_gradients(cf_handle* h, const cf_batch* bt, const c
 extern "C" int cf_integrated_gradients_raw(cf_handle* h, const cf_batch* bt, const cf_ig_opts* o, const cf_input_grads* out,
                                            const cf_input_grads* coeff, float* logits_x, float* logits_base, float* delta, void* stream) {
     return integrated_gradients_impl(h, bt, o, out, coeff, logits_x, logits_base, delta, stream, true, "cf_integrated_gradients_raw");
+}
+
+// In-silico perturbation scan (cf_scan.h).  Per chunk of at most max_batch of the B * V rows (V = 1 + n_sets * W, gene-major):
+// k_scan_expand into the chunk buffers of cf_integrated_gradients (whichever call comes first allocates them; the mark sets travel in
+// its node table), then the launches of cf_forward(save = 0) on the chunk, writing its slice of `logits`.  k_attc2 takes as many
+// regions per workgroup as for the caller's B genes (ag_genes): the result does not depend on max_batch and row (b, v) carries the
+// bits of cf_forward(save = 0) on the batch with the perturbed features substituted.
+extern "C" int cf_perturbation_scan(cf_handle* h, const cf_batch* bt, const cf_scan_opts* o, float* logits, void* stream) {
+    const char* who = "cf_perturbation_scan";
+    if (!h) return fail("%s: null handle", who);
+    if (!bt) return fail("%s: null batch", who);
+    if (!o) return fail("%s: null opts", who);
+    if (!logits) return fail("%s: null logits", who);
+    if (!o->mark_sets) return fail("%s: null mark_sets", who);
+    const cf_config& c = h->cfg;
+    const int nres = c.n_res, S = c.i_max, T = S + 1, F = c.n_feats, cap = c.max_batch;
+    if (bt->B > cap) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, cap);
+    if (o->region < 0 || o->region > S) return fail("%s: region = %d outside [0, i_max = %d]", who, o->region, S);
+    if (o->width < 1) return fail("%s: width = %d: at least 1 coarsest bin", who, o->width);
+    if (o->n_sets < 1) return fail("%s: n_sets = %d: at least 1 mark set", who, o->n_sets);
+    if (!(o->scale >= 0.f) || !std::isfinite(o->scale)) return fail("%s: scale = %g: a finite factor >= 0", who, (double)o->scale);
+    for (int k = 0; k < o->n_sets; ++k)
+        if (F < 32 && o->mark_sets[k] >> F) return fail("%s: mark_sets[%d] = 0x%x names a mark >= n_feats = %d", who, k, o->mark_sets[k], F);
+    int rc = 0;
+    for (int r = 1; r < nres; ++r)
+        if (c.n_bins[r] < c.n_bins[rc]) rc = r;
+    const int W = c.n_bins[rc];
+    for (int r = 0; r < nres; ++r)
+        if (c.n_bins[r] % W) return fail("%s: n_bins[%d] = %d is not a multiple of the coarsest resolution's %d bins", who, r, c.n_bins[r], W);
+    for (int r = nres; r < kMaxRes; ++r)
+        if (o->feats_out[r]) return fail("%s: feats_out[%d]: the model has %d resolutions", who, r, nres);
+    if (h->rider.armed || h->rider.done) return fail("%s: riders are armed for a training step (cf_rider_arm); finish the step first", who);
+    if (check_batch(h, bt)) return -1;
+    if (intg_alloc(h, o->n_sets)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    const int B = bt->B, V = 1 + o->n_sets * W, TT = T * T, slot = o->region - 1;
+    HIP_TRY(hipMemcpyAsync(h->intg_tab, o->mark_sets, o->n_sets * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    ScanExpandArgs ea;
+    memset(&ea, 0, sizeof ea);
+    cf_batch cb;      // the chunk's batch: the rows' copies
+    memset(&cb, 0, sizeof cb);
+    for (int r = 0; r < nres; ++r) {
+        const int L = c.n_bins[r];
+        ea.pf_in[r] = bt->promoter_feats[r];
+        ea.cf_in[r] = bt->pcre_feats[r];
+        ea.pf_out[r] = h->intg_row[r];
+        ea.cf_out[r] = h->intg_row[kMaxRes + r];
+        ea.feats_out[r] = o->feats_out[r];
+        // (the all-rows Embedding reads the caller's full [B, L, L] promoter mask: the chunk rows carry all L rows, as in cf_integrated_gradients)
+        const bool pm_full = h->embed_dense && bt->promoter_mask_stride[r] == (long long)L * L;
+        ea.pm_rows[r] = pm_full ? L : 1;
+        ea.pm_in[r] = static_cast<const uint8_t*>(bt->promoter_mask_row[r]) - (pm_full ? (size_t)(L / 2) * L : 0);
+        ea.cm_in[r] = bt->pcre_mask_row[r];
+        ea.pm_stride[r] = bt->promoter_mask_stride[r];
+        ea.cm_stride[r] = bt->pcre_mask_stride[r];
+        ea.pm_out[r] = h->intg_pm[r];
+        ea.cm_out[r] = h->intg_cm[r];
+        if (slot < 0) {
+            ea.rm_in[r] = bt->promoter_mask_row[r];
+            ea.rm_stride[r] = bt->promoter_mask_stride[r];
+        } else {
+            ea.rm_in[r] = bt->pcre_mask_row[r] + (long long)slot * bt->pcre_mask_stride[r];
+            ea.rm_stride[r] = (long long)S * bt->pcre_mask_stride[r];
+        }
+        ea.im_in[r] = bt->interaction_mask[r];
+        ea.im_out[r] = h->intg_im[r];
+        ea.L[r] = L;
+        cb.promoter_feats[r] = h->intg_row[r];
+        cb.pcre_feats[r] = h->intg_row[kMaxRes + r];
+        cb.promoter_mask_row[r] = h->intg_pm[r] + (pm_full ? (size_t)(L / 2) * L : 0);
+        cb.promoter_mask_stride[r] = pm_full ? (long long)L * L : L;
+        cb.pcre_mask_row[r] = h->intg_cm[r];
+        cb.pcre_mask_stride[r] = L;
+        cb.interaction_mask[r] = h->intg_im[r];
+    }
+    ea.freq_in = bt->interaction_freq;
+    ea.freq_out = h->intg_row[2 * kMaxRes];
+    cb.interaction_freq = h->intg_row[2 * kMaxRes];
+    ea.sets = reinterpret_cast<const unsigned*>(h->intg_tab);
+    ea.flip = o->flip;
+    ea.scale = o->scale;
+    ea.V = V, ea.S = S, ea.TT = TT, ea.F = F, ea.W = W, ea.width = o->width, ea.rc = rc, ea.region = o->region;
+    const long long launches0 = g_launches;
+    int rv = 0;
+    for (int g0 = 0; g0 < B * V && !rv; g0 += cap) {
+        const int nr = std::min(cap, B * V - g0);
+        ea.g0 = g0;
+        hipLaunchKernelGGL(k_scan_expand, dim3(nr, nres), dim3(kIgxThreads), 0, st, ea);
+        LAUNCH_CHECK("k_scan_expand");
+        cb.B = nr;
+        rv = forward_trunk(h, &cb, 0, st, B) || forward_reg_head(h, &cb, logits + (size_t)g0 * c.n_out, 0, st, nullptr);
+    }
+    h->x0_fwd = false;
+    h->last_fwd_B = 0;
+    h->n_fwd = (int)(g_launches - launches0);
+    if (h->capturing) h->cap.n_fwd = h->n_fwd;
+    return rv ? -1 : 0;
 }

@@ -1,0 +1,146 @@
+// cf_scan.h -- in-silico perturbation scan (cf_perturbation_scan; included by cf_api.hip behind cf_ig.h).
+//
+// One region of every gene -- the promoter or one pCRE slot -- is scanned: the histone marks of a mark set are scaled by s >= 0 in
+// RAW-SIGNAL space over a window of the region, and the gene is run forward.  Binning is linear, so scaling the samples of a bin by
+// s scales the bin's mean by s, and the feature u = log(1 + m) of a covered bin becomes
+//     u' = log1pf(s expm1f(u))                                  fp32, each operation rounded (no contraction): ig_signal of cf_ig.h
+// exactly the feature the binning would produce from the scaled signal.
+//
+// Geometry.  c = the coarsest resolution (fewest bins), W = n_bins[c], R_r = n_bins[r] / W.  At resolution r the region's centre
+// pad-mask row gives q_r / e_r, the first / last unmasked row, n_r = e_r - q_r + 1 (0: all masked; holes inside count).  Genomic
+// bin j sits in row q_r + j, or in row q_r + n_r - 1 - j where the region is stored mirrored (flip[b]).  Window g of width w covers
+// the coarse genomic bins [g, min(g + w, n_c)) and at resolution r the genomic bins [g R_r, min(min(g + w, n_c) R_r, n_r)): bin
+// sizes nest, so every finer bin lies in one coarse bin (short last bins included).
+//
+// Rows are (gene, variant) pairs, gene-major (gv = b * V + v, V = 1 + n_sets * W):
+//   v = 0               gene b verbatim
+//   v = 1 + k * W + g   mark set k scaled over window g (g >= n_c, or an empty set: gene b verbatim)
+// in chunks of at most max_batch rows.  One kernel, no atomics, no LDS beyond the two row-extent reductions:
+//   k_scan_expand   per (chunk row, resolution): the row's features of every region, its compact pad-mask rows and interaction
+//                   mask, resolution 0 also its interaction_freq -- float4 where the row allows; the covered rows of the scanned region
+//                   are rewritten on the way (every element is written once), and the scanned region's rows also go to feats_out.
+#pragma once
+
+namespace cf {
+
+struct ScanExpandArgs {
+    const float* pf_in[kMaxRes];       // the caller's promoter_feats [B, L, F]
+    const float* cf_in[kMaxRes];       // pcre_feats [B, S, L, F]
+    float* pf_out[kMaxRes];            // the chunk's copies, [max_batch, L, F] / [max_batch, S, L, F]
+    float* cf_out[kMaxRes];
+    float* feats_out[kMaxRes];         // [B, V, L, F]: the scanned region as row (b, v) reads it; nullptr: not wanted
+    const uint8_t* pm_in[kMaxRes];     // as IgExpandArgs: the rows copied into the chunk
+    const uint8_t* cm_in[kMaxRes];
+    long long pm_stride[kMaxRes], cm_stride[kMaxRes];
+    uint8_t* pm_out[kMaxRes];
+    uint8_t* cm_out[kMaxRes];
+    int pm_rows[kMaxRes];
+    const uint8_t* rm_in[kMaxRes];     // the scanned region's centre pad-mask row of gene b: rm_in[r] + b * rm_stride[r]
+    long long rm_stride[kMaxRes];
+    const uint8_t* im_in[kMaxRes];     // interaction masks [B, T, T]
+    uint8_t* im_out[kMaxRes];
+    const float* freq_in;              // [B, T, T]
+    float* freq_out;
+    const unsigned* sets;              // device [n_sets]: bit f set: mark f is scaled
+    const uint8_t* flip;               // device [B] or nullptr
+    float scale;
+    int L[kMaxRes];
+    int g0, V, S, TT, F, W, width, rc, region;
+};
+
+// first unmasked row and one past the last of a mask row of L bytes (lo = L, hi = 0: all masked); every thread gets the result
+__device__ __forceinline__ void scan_extent(const uint8_t* __restrict__ m, int L, int* red, int& lo, int& hi) {
+    int a = L, b = 0;
+    for (int k = threadIdx.x; k < L; k += kIgxThreads)
+        if (!m[k]) a = min(a, k), b = max(b, k + 1);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) a = min(a, __shfl_xor(a, o, 64)), b = max(b, __shfl_xor(b, o, 64));
+    __syncthreads();      // (red may still be read from the previous call)
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a, red[kIgxThreads / 64 + (threadIdx.x >> 6)] = b;
+    __syncthreads();
+    lo = L, hi = 0;
+#pragma unroll
+    for (int k = 0; k < kIgxThreads / 64; ++k) lo = min(lo, red[k]), hi = max(hi, red[kIgxThreads / 64 + k]);
+}
+
+// one element of the scanned segment: e in [c0, c1) (the covered rows, in elements of the segment) with its mark in `bits` is scaled
+__device__ __forceinline__ float scan_elem(float x, int e, int off, int c0, int c1, unsigned bits, int F, float s) {
+    if (e < c0 || e >= c1) return x;
+    const int f = (e - off) % F;
+    return (bits >> f) & 1u ? ig_signal(s, x) : x;
+}
+
+// dst[0, n) = src[0, n); elements [c0, c1) pass through scan_elem; elements [off, off + len) also go to fo (nullptr: not wanted)
+__device__ __forceinline__ void scan_copy(const float* __restrict__ src, float* __restrict__ dst, int n, int off, int len, int c0, int c1,
+                                          unsigned bits, int F, float s, float* __restrict__ fo) {
+    const bool vec = (n & 3) == 0 && ((off | len) & 3) == 0 &&
+                     ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(fo)) & 15) == 0;
+    if (vec) {
+        const float4* s4 = reinterpret_cast<const float4*>(src);
+        float4* d4 = reinterpret_cast<float4*>(dst);
+        float4* f4 = reinterpret_cast<float4*>(fo);
+        for (int k = threadIdx.x; k < n / 4; k += kIgxThreads) {
+            float4 x = s4[k];
+            const int e = 4 * k;
+            if (e + 4 > c0 && e < c1) {
+                x.x = scan_elem(x.x, e, off, c0, c1, bits, F, s);
+                x.y = scan_elem(x.y, e + 1, off, c0, c1, bits, F, s);
+                x.z = scan_elem(x.z, e + 2, off, c0, c1, bits, F, s);
+                x.w = scan_elem(x.w, e + 3, off, c0, c1, bits, F, s);
+            }
+            d4[k] = x;
+            if (fo && e >= off && e < off + len) f4[(e - off) / 4] = x;
+        }
+    } else {
+        for (int e = threadIdx.x; e < n; e += kIgxThreads) {
+            const float x = scan_elem(src[e], e, off, c0, c1, bits, F, s);
+            dst[e] = x;
+            if (fo && e >= off && e < off + len) fo[e - off] = x;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kIgxThreads) void k_scan_expand(ScanExpandArgs a) {
+    __shared__ int red[2 * (kIgxThreads / 64)];
+    const int i = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
+    const int gv = a.g0 + i, b = gv / a.V, v = gv - b * a.V;
+    const int L = a.L[r], S = a.S, F = a.F, LF = L * F;
+    // the covered rows [p0, p1) of the scanned region at this resolution (block-uniform)
+    int p0 = 0, p1 = 0;
+    unsigned bits = 0;
+    if (v > 0) {
+        const int k = (v - 1) / a.W, g = (v - 1) - k * a.W;
+        bits = a.sets[k];
+        int lo, hi;
+        scan_extent(a.rm_in[a.rc] + (size_t)b * a.rm_stride[a.rc], a.L[a.rc], red, lo, hi);
+        const int nc = hi > lo ? hi - lo : 0;
+        if (bits && g < nc) {
+            if (r != a.rc) scan_extent(a.rm_in[r] + (size_t)b * a.rm_stride[r], L, red, lo, hi);
+            const int nr = hi > lo ? hi - lo : 0, R = L / a.W;
+            const int j0 = g * R, j1 = min(min(g + a.width, nc) * R, nr);
+            if (j0 < j1) {
+                const bool fl = a.flip && a.flip[b];
+                p0 = fl ? lo + nr - j1 : lo + j0;
+                p1 = fl ? lo + nr - j0 : lo + j1;
+            }
+        }
+    }
+    float* fo = a.feats_out[r] ? a.feats_out[r] + (size_t)gv * LF : nullptr;
+    const bool prom = a.region == 0;
+    const int off = prom ? 0 : (a.region - 1) * LF;
+    scan_copy(a.pf_in[r] + (size_t)b * LF, a.pf_out[r] + (size_t)i * LF, LF, 0, LF, prom ? p0 * F : 0, prom ? p1 * F : 0, bits, F, a.scale,
+              prom ? fo : nullptr);
+    scan_copy(a.cf_in[r] + (size_t)b * S * LF, a.cf_out[r] + (size_t)i * S * LF, S * LF, off, LF, prom ? 0 : off + p0 * F,
+              prom ? 0 : off + p1 * F, bits, F, a.scale, prom ? nullptr : fo);
+    const int PL = a.pm_rows[r] * L;
+    for (int k = tid; k < PL; k += kIgxThreads) a.pm_out[r][(size_t)i * PL + k] = a.pm_in[r][(size_t)b * a.pm_stride[r] + k];
+    for (int k = tid; k < S * L; k += kIgxThreads) {
+        const int s = k / L, j = k - s * L;
+        a.cm_out[r][((size_t)i * S + s) * L + j] = a.cm_in[r][((size_t)b * S + s) * a.cm_stride[r] + j];
+    }
+    for (int k = tid; k < a.TT; k += kIgxThreads) a.im_out[r][(size_t)i * a.TT + k] = a.im_in[r][(size_t)b * a.TT + k];
+    if (r == 0)
+        for (int k = tid; k < a.TT; k += kIgxThreads) a.freq_out[(size_t)i * a.TT + k] = a.freq_in[(size_t)b * a.TT + k];
+}
+
+}  // namespace cf

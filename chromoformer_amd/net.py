@@ -613,6 +613,70 @@ class ChromoformerBase(nn.Module):
                 info["coeff"] = {k: {b: t.view(shapes[k][b]) for b, t in v.items()} for k, v in info["coeff"].items()}
         return attr, info
 
+    @torch.no_grad()
+    def perturbation_scan(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                          interaction_freq=None, region=0, scale=0.0, width=1, mark_sets=None, flip=None, return_feats=False):
+        """In-silico perturbation scan (cf_perturbation_scan): the prediction with the histone marks of a mark set scaled by `scale`
+        (0 erases, 2 doubles) in RAW-SIGNAL space over a window of one region -- the promoter (region 0) or pCRE slot j (region
+        1 + j) -- for every window and every mark set, from one call -> logits [B, V, n_out] on the model's device, no autograd graph.
+        With W = min(n_bins), the bins of the coarsest resolution, V = 1 + n_sets * W:
+
+          [:, 0]                the prediction (model(...) under no_grad, bit-equal)
+          [:, 1 + k * W + g]    mark set k over window g: the coarse genomic bins [g, g + width) of the region and the finer bins inside
+                                them; a covered feature u = log(1 + mean) becomes log1p(scale * expm1(u)), exactly what binning the
+                                scaled signal gives.  Windows past the region's real bins (a short pCRE, a dummy slot, a narrowed
+                                promoter) and empty mark sets give [:, 0], bit for bit.
+
+        mark_sets: iterables of mark indices; default each mark alone, then all marks together (n_feats + 1 sets).  flip: [B] bools,
+        True where the region is stored mirrored (the dataset mirrors '-' strand promoters, never pCREs): window g then counts from
+        the genomic start.  return_feats: also {binsize: [B, V, n_bins, n_feats]}, the features of the scanned region that row (b, v)
+        read.  Features must stay below ~80 (expm1 in fp32).  The first argument may also be a packed batch (an engine.Slot or a
+        pack_batch result), with nothing after it.  The pass overwrites the activations a grad-enabled model(...) keeps for its
+        backward: such a pending backward() raises."""
+        if promoter_pad_masks is None:
+            bs = promoter_feats.struct if hasattr(promoter_feats, "struct") else promoter_feats[0]
+        else:
+            bs, _keep = self._pack(promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq)      # (alive until the call)
+        if self._handle is None:
+            raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
+        F, dev, B = self.n_feats, self._device, bs.B
+        if mark_sets is None:
+            mark_sets = [(f,) for f in range(F)] + [tuple(range(F))]
+        mark_sets = [tuple(int(f) for f in ms) for ms in mark_sets]
+        bad = [ms for ms in mark_sets if any(not 0 <= f < min(F, 32) for f in ms)]
+        if bad or not mark_sets:
+            raise ValueError("perturbation_scan: mark_sets %s: a non-empty list of sets of mark indices in [0, n_feats = %d)" % (bad or "()", F))
+        bits = np.array([sum(1 << f for f in set(ms)) for ms in mark_sets], dtype=np.uint32)
+        W = min(self.n_bins)
+        V = 1 + len(mark_sets) * W
+        opts = _lib.cf_scan_opts()
+        opts.region, opts.width, opts.n_sets, opts.scale = int(region), int(width), len(mark_sets), float(scale)
+        opts.mark_sets = bits.ctypes.data
+        if flip is not None:
+            flip = torch.as_tensor(flip).to(dev).ne(0).to(torch.uint8).contiguous()
+            if flip.numel() != B:
+                raise ValueError("perturbation_scan: flip has %d entries for a batch of %d genes" % (flip.numel(), B))
+            opts.flip = flip.data_ptr()
+        feats = None
+        if return_feats:
+            feats = {}
+            for r, b in enumerate(self.binsizes):
+                t = feats[b] = torch.empty(B, V, self.n_bins[r], F, device=dev)      # (written in full by the library)
+                opts.feats_out[r] = t.data_ptr()
+        logits = torch.empty(B, V, self.n_out, device=dev)      # (written in full by the library)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        self._sync_tiled(st)
+        self._maps_gen += 1
+        self._maps_by = "perturbation_scan"
+        _lib.check(_lib.lib().cf_perturbation_scan(self._handle, C.byref(bs), C.byref(opts), logits.data_ptr(), st), "cf_perturbation_scan")
+        return (logits, feats) if return_feats else logits
+
+    def perturbation_scan_dataset(self, dataset, genes=None, regions="promoter", scale=0.0, width=1, mark_sets=None, bsz=None, store=None):
+        """perturbation_scan over the genes of a ChromoformerDataset with windows in genomic coordinates
+        (chromoformer_amd.attribution.perturbation_scan, a generator of per-gene dicts)."""
+        from .attribution import perturbation_scan
+        return perturbation_scan(self, dataset, genes=genes, regions=regions, scale=scale, width=width, mark_sets=mark_sets, bsz=bsz, store=store)
+
     def raw_signal_gradients(self, dataset, genes=None, target=None, times_input=False, bsz=None):
         """Raw-signal saliency of the genes of a ChromoformerDataset: the gradient (or gradient x input) of logit column `target` with
         respect to the raw fp16 signals, per gene one track per histone mark for the promoter window and every pCRE, in genomic

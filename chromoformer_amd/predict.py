@@ -165,6 +165,79 @@ def write_integrated_gradients(model, store, bsz, ig_dir, n_steps=50, method="ga
         m.flush()
 
 
+def write_perturbation_scan(model, store, bsz, path, gene_ids, strands, regression=False, scale=0.0, width=1, regions="promoter",
+                            mark_sets=None):
+    """In-silico perturbation scan of every gene of a device-resident store, in store order (model.perturbation_scan: the marks of a
+    mark set scaled by `scale` in raw-signal space over each window of `width` coarsest bins) into `path`, an .npz holding
+
+        gene_ids     [n]
+        mark_sets    [n_sets, n_feats] bool: the marks of each set (default: each mark alone, then all together)
+        prediction   float32 [n]: the prediction column's quantity (sigmoid(logits)[:, 1], or logits[:, 0] for the regressor) of the
+                     unperturbed gene, through the very sigmoid call predict() makes: the CSV column bit for bit
+        promoter     float32 [n, n_sets, W], W = the coarsest resolution's bins: the same quantity with set k scaled over window g of
+                     the promoter (genomic order: `strands` undoes the mirror of '-' strand promoters); NaN where the window holds no
+                     real bin
+        pcres        float32 [n, i_max, n_sets, W], with regions="all": the same per pCRE slot (NaN for dummy slots)
+
+    Per batch: one device gather into a Slot and one model.perturbation_scan per scanned region."""
+    import ctypes as C
+
+    from . import _lib
+    n, dev, L = len(store), model._device, _lib.lib()
+    S, F = model.i_max, model.n_feats
+    if mark_sets is None:
+        mark_sets = [(f,) for f in range(F)] + [tuple(range(F))]
+    mark_sets = [tuple(int(f) for f in ms) for ms in mark_sets]
+    K = len(mark_sets)
+    rc = int(np.argmin(model.n_bins))
+    W = model.n_bins[rc]
+    V = 1 + K * W
+    scanned = [0] + (list(range(1, S + 1)) if regions == "all" else [])
+    logits = torch.empty(len(scanned), n, V, model.n_out)
+    live = torch.zeros(len(scanned), n, W, dtype=torch.bool)      # window g of the region holds a real bin
+    struct = store.struct()
+    order = torch.arange(n, dtype=torch.int32, device=dev)
+    flip = torch.tensor([s != "+" for s in strands], dtype=torch.uint8, device=dev)
+    slots = {}
+    st = torch.cuda.current_stream(dev).cuda_stream
+    for lo in range(0, n, bsz):
+        B = min(bsz, n - lo)
+        slot = slots.get(B) or slots.setdefault(B, Slot(model, B))
+        cursor = torch.tensor([0, 1, 0, 0], dtype=torch.int32).to(dev)
+        _lib.check(L.cf_gather_batch(model._handle, C.byref(struct), order[lo:].data_ptr(), cursor.data_ptr(), C.byref(slot.struct), None, st),
+                   "cf_gather_batch")
+        for k, region in enumerate(scanned):
+            out = model.perturbation_scan(slot, region=region, scale=scale, width=width, mark_sets=mark_sets,
+                                          flip=flip[lo:lo + B] if region == 0 else None)
+            logits[k, lo:lo + B] = out.cpu()
+            m = (store.pm[rc][lo:lo + B] if region == 0 else store.cm[rc][lo:lo + B, region - 1]).reshape(B, W).cpu() == 0
+            pos = torch.arange(W)
+            first = torch.where(m, pos, W).amin(1)
+            last = torch.where(m, pos, -1).amax(1)
+            live[k, lo:lo + B] = pos[None, :] < (last - first + 1).clamp(min=0)[:, None]
+        if int(cursor[2].item()):
+            raise RuntimeError("write_perturbation_scan: the device-side gather reported errors at gene %d (store / order mismatch)" % lo)
+
+    def column(lg):          # [n, n_out], laid out as the logits predict() turns into its column
+        lg = lg.contiguous()
+        return lg.numpy().reshape(-1) if regression else torch.sigmoid(lg).numpy()[:, 1]
+
+    vals = np.empty((len(scanned), n, V), dtype=np.float32)
+    for k in range(len(scanned)):
+        for v in range(V):
+            vals[k, :, v] = column(logits[k, :, v])
+    scan = vals[:, :, 1:].reshape(len(scanned), n, K, W)
+    scan[~np.broadcast_to(live.numpy()[:, :, None, :], scan.shape)] = np.nan
+    sets = np.zeros((K, F), dtype=bool)
+    for k, ms in enumerate(mark_sets):
+        sets[k, list(ms)] = True
+    arrays = dict(gene_ids=np.array(list(gene_ids)), mark_sets=sets, prediction=vals[0, :, 0].copy(), promoter=scan[0])
+    if regions == "all":
+        arrays["pcres"] = np.ascontiguousarray(scan[1:].transpose(1, 0, 2, 3))
+    with open(path, "wb") as f:
+        np.savez(f, **arrays)
+
+
 def require_raw_signals(dataset, genes=None):
     """Raw-signal saliency reads the raw .npy regions themselves; a packed store holds binned features only.  Raises FileNotFoundError
     naming the first region file of `genes` (default: the dataset's) that is missing."""
@@ -214,14 +287,16 @@ def write_raw_integrated_gradients(model, dataset, bsz, ig_dir, n_steps=50, meth
 def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123, i_max=8, w_prom=40000, w_max=40000,
             binsizes=(2000, 500, 100), progress=False, store_path=None, attention_dir=None, embeddings_out=None,
             pcre_ablation_out=None, ig_dir=None, ig_steps=50, ig_method="gausslegendre", ig_target=None, raw_saliency_dir=None,
-            raw_saliency_target=None, raw_saliency_times_input=False, raw_ig_dir=None):
+            raw_saliency_target=None, raw_saliency_times_input=False, raw_ig_dir=None, scan_out=None, scan_scale=0.0, scan_width=1,
+            scan_regions="promoter"):
     """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file.  attention_dir / embeddings_out: also
     write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps); pcre_ablation_out:
     the predictions with each pCRE deleted (write_pcre_ablation); ig_dir: integrated gradients of every gene
     (write_integrated_gradients); raw_saliency_dir: the gradient (or gradient x input) of the prediction with respect to the raw
     signals, one .npz per gene (write_raw_saliency; needs the raw .npy files also when a packed store serves the predictions);
     raw_ig_dir: integrated gradients with respect to the raw signals, one .npz per gene (write_raw_integrated_gradients; ig_steps,
-    ig_method and ig_target apply; needs the raw .npy files too)."""
+    ig_method and ig_target apply; needs the raw .npy files too); scan_out: the in-silico perturbation scan of every gene, one .npz
+    (write_perturbation_scan; scan_scale, scan_width and scan_regions apply; served by a packed store as well)."""
     seed_everything(seed)
     meta = pd.read_csv(meta_path)
     genes = meta.gene_id.tolist()
@@ -253,6 +328,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         write_pcre_ablation(model, store, bsz, pcre_ablation_out, regression)
     if ig_dir:
         write_integrated_gradients(model, store, bsz, ig_dir, ig_steps, ig_method, ig_target)
+    if scan_out:
+        write_perturbation_scan(model, store, bsz, scan_out, genes, meta.strand.tolist(), regression, scan_scale, scan_width, scan_regions)
     if raw_saliency_dir:
         write_raw_saliency(model, raw_ds, bsz, raw_saliency_dir, raw_saliency_target, raw_saliency_times_input)
     if raw_ig_dir:
@@ -293,6 +370,14 @@ def build_parser():
     ap.add_argument("--raw-saliency-target", type=int, default=None, help="logit column of --raw-saliency-dir (default 1 for the classifier, 0 "
                     "with --regression)")
     ap.add_argument("--raw-saliency-times-input", action="store_true", help="--raw-saliency-dir writes gradient x input")
+    ap.add_argument("--scan-out", default=None, help="also write the in-silico perturbation scan to this .npz file: gene_ids, mark_sets "
+                    "[n_sets, 7], prediction [n] (as --output) and promoter [n, n_sets, W]: the prediction with each mark alone, then all "
+                    "marks, scaled by --scan-scale in raw-signal space over each window of the promoter, genomic order, NaN where a window "
+                    "holds no real bin (model.perturbation_scan)")
+    ap.add_argument("--scan-scale", type=float, default=None, help="scale factor of --scan-out: 0 erases the marks (default), 2 doubles them")
+    ap.add_argument("--scan-width", type=int, default=None, help="window width of --scan-out in coarsest bins (default 1)")
+    ap.add_argument("--scan-regions", default=None, choices=("promoter", "all"), help="--scan-out scans the promoter (default) or also every "
+                    "pCRE slot: pcres [n, i_max, n_sets, W]")
     return ap
 
 
@@ -309,12 +394,19 @@ def main(argv=None):
         ap.error("--ig-steps must be at least %d" % (2 if args.ig_method == "riemann_trapezoid" else 1))
     if args.ig_target is not None and not 0 <= args.ig_target < (1 if args.regression else 2):
         ap.error("--ig-target must be in [0, %d)" % (1 if args.regression else 2))
+    if not args.scan_out and (args.scan_scale is not None or args.scan_width is not None or args.scan_regions is not None):
+        ap.error("--scan-scale / --scan-width / --scan-regions need --scan-out")
+    if args.scan_scale is not None and not (args.scan_scale >= 0 and np.isfinite(args.scan_scale)):
+        ap.error("--scan-scale must be a finite factor >= 0")
+    if args.scan_width is not None and args.scan_width < 1:
+        ap.error("--scan-width must be at least 1")
     meta, pred = predict(args.meta, args.npy_dir, args.weights, args.regression, progress=True, store_path=args.store,
                          attention_dir=args.attention_dir, embeddings_out=args.embeddings_out, pcre_ablation_out=args.pcre_ablation_out,
                          ig_dir=args.ig_dir, ig_steps=50 if args.ig_steps is None else args.ig_steps,
                          ig_method=args.ig_method or "gausslegendre", ig_target=args.ig_target, raw_saliency_dir=args.raw_saliency_dir,
                          raw_saliency_target=args.raw_saliency_target, raw_saliency_times_input=args.raw_saliency_times_input,
-                         raw_ig_dir=args.raw_ig_dir)
+                         raw_ig_dir=args.raw_ig_dir, scan_out=args.scan_out, scan_scale=0.0 if args.scan_scale is None else args.scan_scale,
+                         scan_width=1 if args.scan_width is None else args.scan_width, scan_regions=args.scan_regions or "promoter")
     print("Predicting expressions for %d genes." % len(meta))
     meta["prediction"] = pred
     meta.to_csv(args.output, index=False)

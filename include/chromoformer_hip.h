@@ -270,6 +270,45 @@ int cf_integrated_gradients(cf_handle* h, const cf_batch* batch, const cf_ig_opt
  * a non-NULL coeff->interaction_freq. */
 int cf_integrated_gradients_raw(cf_handle* h, const cf_batch* batch, const cf_ig_opts* opts, const cf_input_grads* out,
                                 const cf_input_grads* coeff, float* logits_x, float* logits_base, float* delta, void* stream);
+/* In-silico perturbation scan (interpretation): what would the prediction be if the marks of a mark set were scaled by s -- erased
+ * (s = 0), doubled (s = 2) -- over a window of the promoter or of one pCRE?  The perturbation is defined in RAW-SIGNAL space and is
+ * exact there: binning is linear, so scaling the window's samples by s scales the means of its bins by s, and a covered feature
+ * u = log(1 + m) becomes
+ *   u' = log1pf(s expm1f(u))                          fp32, each operation rounded (no contraction)
+ * which is the feature the binning produces from the scaled signal.  Every other element of every input, and every mask, is the gene's own.
+ * Geometry: c = the coarsest resolution (fewest bins), W = n_bins[c], R_r = n_bins[r] / W (20 / 80 / 400 bins: 1, 4, 20).  At
+ * resolution r the centre pad-mask row of the region gives q_r / e_r, its first / last unmasked row, and n_r = e_r - q_r + 1 (0: all
+ * masked; holes inside count as real rows).  Genomic bin j is row q_r + j, or row q_r + n_r - 1 - j where the region is stored
+ * mirrored (flip[b] != 0: the dataset mirrors '-' strand promoters, never pCREs).  Window g of width w covers the coarse genomic bins
+ * [g, min(g + w, n_c)) and at resolution r the genomic bins [g R_r, min(min(g + w, n_c) R_r, n_r)): bin sizes nest, every finer bin
+ * lies wholly inside one coarse bin (short last bins included), no sample counts are needed. */
+typedef struct cf_scan_opts {
+    int region;                 /* 0 promoter, 1 + j pCRE slot j                                  */
+    int width;                  /* window width in coarsest bins, >= 1                            */
+    int n_sets;                 /* >= 1                                                           */
+    const unsigned* mark_sets;  /* host [n_sets]; bit f set: mark f is scaled; 0 = nothing (read before the call returns) */
+    float scale;                /* s >= 0, finite                                                 */
+    const uint8_t* flip;        /* device [B], non-zero: the region is stored mirrored; NULL: none */
+    float* feats_out[CF_MAX_RES]; /* optional, device, [B, V, n_bins[r], n_feats]                  */
+} cf_scan_opts;
+/* logits: [B, V, n_out], V = 1 + n_sets * W, gene-major (b * V + v):
+ *   v = 0               the unperturbed gene (bit-equal to cf_forward(save = 0));
+ *   v = 1 + k * W + g   mark set k applied to window g; a window with g >= n_c (a dummy slot, a narrowed promoter, a short pCRE) or
+ *                       an empty set changes nothing: the baseline's logits, bit for bit.
+ * feats_out[r] (optional): the features of the scanned region that the forward of row (b, v) read, OVERWRITTEN in full.
+ * Rows run in chunks of at most max_batch.  Per chunk one k_scan_expand writes the rows' inputs -- features of every region and
+ * resolution with the covered rows of the scanned region rewritten, compact pad-mask rows (all L rows of a full promoter mask with
+ * embed.n_layers > 1), interaction masks, frequencies -- into the chunk buffers of cf_integrated_gradients (whichever call comes
+ * first allocates them; cf_destroy frees them), then the launches of cf_forward(save = 0) run on the chunk and write its slice of
+ * `logits`:   cf_launch_counts fwd = ceil(B * V / max_batch) * (1 + n_fwd),  n_fwd = what cf_forward(save = 0) issues.
+ * Deterministic (no atomics).  Off the fused trunk k_attc2's regions per workgroup are chosen as for the caller's B genes, so the
+ * result does not depend on max_batch and row (b, v) equals cf_forward(save = 0) on the batch with feats_out[:, v] substituted, bit
+ * for bit.  Overwrites the activations a cf_forward(save >= 1) kept: no cf_backward* may follow without a new saving forward.
+ * Limits: u < ~80 (expm1f overflows past 88); a negative feature with 1 + s m <= 0 gives NaN, as the forward's log does.
+ * Refused by name, before anything is launched: a null handle / batch / opts / logits / mark_sets, B > max_batch, region outside
+ * [0, i_max], width < 1, n_sets < 1, a negative or non-finite scale, a mark bit >= n_feats, an n_bins[r] that is no multiple of the
+ * smallest, a feats_out index >= n_res, armed riders. */
+int cf_perturbation_scan(cf_handle* h, const cf_batch* batch, const cf_scan_opts* opts, float* logits, void* stream);
 /* torch.optim.AdamW.step (train.py:157, 196): decoupled weight decay, bias correction
  * from `step` (1-based), over [0, n_active). */
 int cf_adamw_step(cf_handle* h, float lr, float beta1, float beta2, float eps, float weight_decay,
