@@ -133,6 +133,9 @@ SYMBOLS = {
     "cf_backward_from_inputs": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.POINTER(cf_input_grads), C.c_void_p]),
     "cf_attention_maps": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.POINTER(cf_attn_maps), C.c_void_p]),
     "cf_pcre_ablation": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.c_void_p]),
+    "cf_pcre_coalitions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "cf_pcre_shapley": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cf_pcre_epistasis": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_integrated_gradients": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_ig_opts), C.POINTER(cf_input_grads), C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_integrated_gradients_raw": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_ig_opts), C.POINTER(cf_input_grads),

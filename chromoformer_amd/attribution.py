@@ -42,6 +42,43 @@ def ig_quadrature(method="gausslegendre", n_steps=50):
     return a.astype(np.float32), w.astype(np.float32)
 
 
+def coalition_table(kind, i_max):
+    """The pCRE coalition words (bit j set: slot j kept) of ChromoformerBase.pcre_shapley / pcre_epistasis -> uint32 array.
+    "all": every word 0 .. 2^i_max - 1 in ascending order (word m at position m).  "pairs", with N = 2^i_max - 1: N; N without i for
+    i = 0 .. i_max - 1; then N without i and j for the pairs i < j in lexicographic order (1 + S + S (S - 1) / 2 words)."""
+    S = int(i_max)
+    if S != i_max or not 1 <= S <= 31:
+        raise ValueError("coalition_table: i_max = %r; an integer in 1..31" % (i_max,))
+    if kind == "all":
+        return np.arange(1 << S, dtype=np.uint32)
+    if kind == "pairs":
+        N = (1 << S) - 1
+        words = [N] + [N & ~(1 << i) for i in range(S)] + [N & ~(1 << i) & ~(1 << j) for i in range(S) for j in range(i + 1, S)]
+        return np.array(words, dtype=np.uint32)
+    raise ValueError("coalition_table: kind %r; choose 'all' or 'pairs'" % (kind,))
+
+
+def coalition_words(keep, i_max, who="pcre_coalitions"):
+    """`keep` as the uint32 words the library reads: a sequence / array of ints (bit j set: slot j kept), or a bool array
+    [n_coal, i_max] (column j: slot j kept).  Empty input, a negative word or a bit >= i_max raise ValueError naming `who`."""
+    S = int(i_max)
+    a = np.asarray(keep.cpu() if hasattr(keep, "cpu") else keep)
+    if a.size < 1:
+        raise ValueError("%s: keep is empty: at least 1 coalition" % who)
+    if a.dtype == np.bool_:
+        if a.ndim != 2 or a.shape[1] != S:
+            raise ValueError("%s: a bool keep must be [n_coal, i_max = %d], got %s" % (who, S, tuple(a.shape)))
+        a = (a.astype(np.int64) << np.arange(S, dtype=np.int64)).sum(1)
+    elif a.ndim != 1 or a.dtype.kind not in "iu":
+        raise ValueError("%s: keep must be a sequence of ints or a bool array [n_coal, i_max], got dtype %s with shape %s"
+                         % (who, a.dtype, tuple(a.shape)))
+    a = a.astype(np.int64) if a.dtype != np.uint64 else a
+    bad = [int(m) for m in a if int(m) < 0 or int(m) >> S]
+    if bad:
+        raise ValueError("%s: keep word(s) %s name a pCRE slot >= i_max = %d (or are negative)" % (who, [hex(m) for m in bad[:4]], S))
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
 def _raw_check(who, model, dataset, genes, target, bsz):
     """The checks the raw-signal generators share -> (binsizes, n_bins, target, genes, chunk size)."""
     ds = dataset

@@ -6,6 +6,7 @@
 #include "cf_input_grad.h"
 #include "cf_attn_maps.h"
 #include "cf_ablate.h"
+#include "cf_coalition.h"
 #include "cf_ig.h"
 #include "cf_scan.h"
 #include "cf_x0_gather.h"
@@ -343,6 +344,11 @@ struct cf_handle {
     float* abl_freq = nullptr;                 // [max_batch, T, T]: interaction_freq of a chunk's gene-variants
     uint8_t* abl_mask[kMaxRes] = {};           // [max_batch, T, T] per resolution: their interaction masks
     void* abl_mem = nullptr;
+    // pCRE coalitions (cf_pcre_coalitions / cf_pcre_shapley / cf_pcre_epistasis; cf_coalition.h): the chunk buffers are the ablation's
+    unsigned* coal_tab = nullptr;              // [coal_cap]: the coalition words of a call; grows on demand
+    long long coal_cap = 0;
+    float* coal_rows = nullptr;                // [max_batch, coal_rows_per, n_out]: the rows of a Shapley / epistasis call without a caller's buffer
+    long long coal_rows_per = 0;
     // integrated gradients (cf_integrated_gradients): one allocation, made by the first call (intg_alloc); segments are
     // promoter_feats[r], pcre_feats[r], interaction_freq (cf_ig.h)
     float* intg_row[kIgSegs] = {};             // [max_batch, len]: a chunk's inputs
@@ -1038,6 +1044,8 @@ extern "C" void cf_destroy(cf_handle* h) {
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     if (h->ride_ev) (void)hipEventDestroy(h->ride_ev);
     if (h->abl_mem) (void)hipFree(h->abl_mem);
+    if (h->coal_tab) (void)hipFree(h->coal_tab);
+    if (h->coal_rows) (void)hipFree(h->coal_rows);
     if (h->intg_mem) (void)hipFree(h->intg_mem);
     if (h->intg_tab) (void)hipFree(h->intg_tab);
     delete h;

@@ -1,4 +1,4 @@
-// cf_api_attrib.h -- host side of the attribution entry points (input gradients, attention maps, pCRE deletion, integrated
+// cf_api_attrib.h -- host side of the attribution entry points (input gradients, attention maps, pCRE deletion, pCRE coalitions, integrated
 // gradients, perturbation scan).  Part of cf_api.hip's single translation unit: included there behind the backward pass, not on its own.
 #pragma once
 
@@ -176,14 +176,15 @@ extern "C" int cf_attention_maps(cf_handle* h, const cf_batch* bt, float* logits
     return 0;
 }
 
-// The buffers of cf_pcre_ablation, allocated by its first call (the model's other entry points never need them).
-static int ablate_alloc(cf_handle* h) {
+// The buffers of cf_pcre_ablation and of the coalition entry points, allocated by the first call of any of them (the model's other
+// entry points never need them).
+static int ablate_alloc(cf_handle* h, const char* who = "cf_pcre_ablation") {
     if (h->abl_mem) return 0;
     const cf_config& c = h->cfg;
     const size_t T = c.i_max + 1, rows = (size_t)c.max_batch * T, x0 = rows * c.d_emb, tt = (size_t)c.max_batch * T * T;
     const size_t freq_off = c.n_res * x0, mask_off = freq_off + tt;      // (floats; the masks follow as bytes)
     void* q = nullptr;
-    if (hipMalloc(&q, mask_off * sizeof(float) + c.n_res * tt) != hipSuccess) return fail("cf_pcre_ablation: out of memory");
+    if (hipMalloc(&q, mask_off * sizeof(float) + c.n_res * tt) != hipSuccess) return fail("%s: out of memory", who);
     h->abl_mem = q;
     float* f = (float*)q;
     for (int r = 0; r < c.n_res; ++r) {
@@ -234,6 +235,145 @@ extern "C" int cf_pcre_ablation(cf_handle* h, const cf_batch* bt, float* logits,
     h->last_fwd_B = 0;
     h->n_fwd = (int)(g_launches - launches0);
     if (h->capturing) h->cap.n_fwd = h->n_fwd;
+    return 0;
+}
+
+// The shared host routine of the coalition entry points (cf_coalition.h): the trunk once on the B genes, k_pcre_stash, the words into
+// the handle's device table, then per chunk of at most max_batch of the B * n_coal rows (gene-major) one k_coalition_expand and the
+// Regulation + head launches of an inference forward on that chunk, writing the chunk's contiguous slice of `logits`.  The callers
+// have checked h, bt and logits.
+static int coalition_rows(cf_handle* h, const cf_batch* bt, const uint32_t* keep, int n_coal, float* logits, hipStream_t st, const char* who) {
+    const cf_config& c = h->cfg;
+    if (bt->B > c.max_batch) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, c.max_batch);
+    if (n_coal < 1) return fail("%s: n_coal = %d: at least 1 coalition", who, n_coal);
+    if (!keep) return fail("%s: null keep", who);
+    const int B = bt->B, S = c.i_max, T = S + 1, nres = c.n_res, cap = c.max_batch;
+    for (int k = 0; k < n_coal; ++k)
+        if (keep[k] >> S) return fail("%s: keep[%d] = 0x%x names a pCRE slot >= i_max = %d", who, k, keep[k], S);
+    if (check_batch(h, bt)) return -1;
+    if (ablate_alloc(h, who)) return -1;
+    if (n_coal > h->coal_cap) {
+        const long long want = std::max<long long>(n_coal, 256);
+        if (h->coal_tab) (void)hipFree(h->coal_tab);      // (synchronises: a call in flight may still read the old table)
+        h->coal_tab = nullptr;
+        h->coal_cap = 0;
+        if (hipMalloc(&h->coal_tab, (size_t)want * sizeof(unsigned)) != hipSuccess) return fail("%s: out of memory", who);
+        h->coal_cap = want;
+    }
+    const long long launches0 = g_launches;
+    HIP_TRY(hipMemcpyAsync(h->coal_tab, keep, (size_t)n_coal * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    if (forward_trunk(h, bt, 0, st) || stash_trunk_output(h, B, h->abl_stash, st)) return -1;
+    CoalExpandArgs ea;
+    memset(&ea, 0, sizeof ea);
+    cf_batch cb = *bt;      // the chunk's batch: only B, the masks and the frequencies are read past the trunk
+    for (int r = 0; r < nres; ++r) {
+        ea.stash[r] = reinterpret_cast<const float4*>(h->abl_stash[r]);
+        ea.x0[r] = reinterpret_cast<float4*>(h->Rx[r][0]);
+        ea.mask_in[r] = bt->interaction_mask[r];
+        ea.mask_out[r] = h->abl_mask[r];
+        cb.interaction_mask[r] = h->abl_mask[r];
+    }
+    ea.freq_in = bt->interaction_freq;
+    ea.freq_out = h->abl_freq;
+    cb.interaction_freq = h->abl_freq;
+    ea.keep = h->coal_tab;
+    ea.n_coal = n_coal, ea.T = T, ea.row4 = T * c.d_emb / 4;
+    const long long rows = (long long)B * n_coal;
+    for (long long g0 = 0; g0 < rows; g0 += cap) {
+        const int n = (int)std::min<long long>(cap, rows - g0);
+        ea.g0 = g0;
+        hipLaunchKernelGGL(k_coalition_expand, dim3(n, nres), dim3(kAblThreads), 0, st, ea);
+        LAUNCH_CHECK("k_coalition_expand");
+        cb.B = n;
+        if (forward_reg_head(h, &cb, logits + (size_t)g0 * c.n_out, 0, st, nullptr)) return -1;
+    }
+    h->last_fwd_B = 0;
+    h->n_fwd = (int)(g_launches - launches0);
+    if (h->capturing) h->cap.n_fwd = h->n_fwd;
+    return 0;
+}
+
+extern "C" int cf_pcre_coalitions(cf_handle* h, const cf_batch* bt, const uint32_t* keep, int n_coal, float* logits, void* stream) {
+    const char* who = "cf_pcre_coalitions";
+    if (!h) return fail("%s: null handle", who);
+    if (!bt) return fail("%s: null batch", who);
+    if (!logits) return fail("%s: null logits", who);
+    return coalition_rows(h, bt, keep, n_coal, logits, (hipStream_t)stream, who);
+}
+
+// The rows of a Shapley / epistasis call whose caller gave no buffer: [max_batch, per, n_out], allocated by the first such call.
+static float* coalition_own_rows(cf_handle* h, long long per, const char* who) {
+    if (per > h->coal_rows_per) {
+        if (h->coal_rows) (void)hipFree(h->coal_rows);      // (synchronises)
+        h->coal_rows = nullptr;
+        h->coal_rows_per = 0;
+        if (hipMalloc(&h->coal_rows, (size_t)h->cfg.max_batch * per * h->cfg.n_out * sizeof(float)) != hipSuccess) {
+            fail("%s: out of memory", who);
+            return nullptr;
+        }
+        h->coal_rows_per = per;
+    }
+    return h->coal_rows;
+}
+// One more launch (the reducer) on the account of the forward
+static void coalition_count_reducer(cf_handle* h) {
+    ++h->n_fwd;
+    if (h->capturing) h->cap.n_fwd = h->n_fwd;
+}
+
+// All 2^i_max coalitions through coalition_rows (word m at column m), then k_shapley.
+extern "C" int cf_pcre_shapley(cf_handle* h, const cf_batch* bt, float* phi, float* logits_all, void* stream) {
+    const char* who = "cf_pcre_shapley";
+    if (!h) return fail("%s: null handle", who);
+    if (!bt) return fail("%s: null batch", who);
+    if (!phi) return fail("%s: null phi", who);
+    const cf_config& c = h->cfg;
+    if (bt->B > c.max_batch) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, c.max_batch);
+    const int S = c.i_max, n = 1 << S;
+    float* rows = logits_all ? logits_all : coalition_own_rows(h, n, who);
+    if (!rows) return -1;
+    std::vector<uint32_t> keep(n);
+    for (int m = 0; m < n; ++m) keep[m] = (uint32_t)m;
+    hipStream_t st = (hipStream_t)stream;
+    if (coalition_rows(h, bt, keep.data(), n, rows, st, who)) return -1;
+    ShapleyArgs sa;
+    memset(&sa, 0, sizeof sa);
+    sa.v = rows, sa.phi = phi, sa.S = S, sa.n_out = c.n_out;
+    double fact[kCoalMaxS + 1] = {1.0};
+    for (int k = 1; k <= S; ++k) fact[k] = fact[k - 1] * k;
+    for (int k = 0; k < S; ++k) sa.w[k] = (float)(fact[k] * fact[S - k - 1] / fact[S]);
+    hipLaunchKernelGGL(k_shapley, dim3(bt->B, S), dim3(kShapThreads), 0, st, sa);
+    LAUNCH_CHECK("k_shapley");
+    coalition_count_reducer(h);
+    return 0;
+}
+
+// The 1 + S + S (S - 1) / 2 pair-deletion coalitions through coalition_rows, then k_epistasis.
+extern "C" int cf_pcre_epistasis(cf_handle* h, const cf_batch* bt, float* eps, float* logits_pairs, void* stream) {
+    const char* who = "cf_pcre_epistasis";
+    if (!h) return fail("%s: null handle", who);
+    if (!bt) return fail("%s: null batch", who);
+    if (!eps) return fail("%s: null eps", who);
+    const cf_config& c = h->cfg;
+    if (bt->B > c.max_batch) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, c.max_batch);
+    const int S = c.i_max;
+    const uint32_t N = (1u << S) - 1u;
+    std::vector<uint32_t> keep;
+    keep.push_back(N);
+    for (int i = 0; i < S; ++i) keep.push_back(N & ~(1u << i));
+    for (int i = 0; i < S; ++i)
+        for (int j = i + 1; j < S; ++j) keep.push_back(N & ~(1u << i) & ~(1u << j));
+    const int R = (int)keep.size();
+    float* rows = logits_pairs ? logits_pairs : coalition_own_rows(h, R, who);
+    if (!rows) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    if (coalition_rows(h, bt, keep.data(), R, rows, st, who)) return -1;
+    EpistasisArgs ea;
+    ea.v = rows, ea.eps = eps, ea.B = bt->B, ea.S = S, ea.n_out = c.n_out;
+    const long long n = (long long)bt->B * S * S * c.n_out;
+    hipLaunchKernelGGL(k_epistasis, dim3((int)std::min<long long>((n + kShapThreads - 1) / kShapThreads, 1024)), dim3(kShapThreads), 0, st, ea);
+    LAUNCH_CHECK("k_epistasis");
+    coalition_count_reducer(h);
     return 0;
 }
 

@@ -1,0 +1,121 @@
+// cf_coalition.h -- pCRE coalition forwards, exact Shapley values and pair epistasis (cf_pcre_coalitions, cf_pcre_shapley,
+// cf_pcre_epistasis; included by cf_api.hip behind cf_ablate.h, whose stash kernel and buffers it shares).
+//
+// A coalition is a 32-bit word m, bit j set = pCRE slot j kept.  Row (b, m) is the inference forward of gene b with its interaction
+// mask (every resolution) OR-ed with row j+1 and column j+1 for every clear bit j < S: the generalisation of cf_ablate.h's variants
+// (m = 2^S - 1: variant 0; one clear bit j: variant 1 + j; m = 0: variant S + 1).  The trunk runs once, its output is stashed
+// (k_pcre_stash), and the Regulation stack + head run on the B * n_coal rows, gene-major (row = b * n_coal + c), in chunks of at most
+// max_batch rows.
+//   k_coalition_expand  per (chunk row, resolution): the stashed rows of its gene -> Rx[r][0], the OR-ed mask from the row's word (read
+//                       from a device table) -> the chunk's mask[r]; resolution 0 also copies the gene's interaction_freq.  Bytes
+//                       and bit tests only.
+//   k_shapley           per (gene, slot j): phi[b, j, o] = sum over m with bit j clear of w(|m|) (v[b, m | 1 << j, o] - v[b, m, o]),
+//                       w(k) = k! (S - k - 1)! / S! (computed by the host in double, rounded to fp32, passed by value).  Every
+//                       operation rounded to fp32 (no contraction); thread t sums the words of rank t, t + 256, ... in ascending
+//                       order, then a fixed-order LDS tree: deterministic, no atomics.  All S slots are players: a dummy slot's
+//                       differences are exact zeros, so its phi is exactly 0 and the live slots' values are those of the game
+//                       among the live slots alone.
+//   k_epistasis         per (gene, pair i <= j) from the pair-deletion rows (N = 2^S - 1; row 0: N, row 1 + i: N \ i, then N \ {i, j}
+//                       for i < j in lexicographic order): eps[b, i, j, o] = ((v_N - v_{N\i}) - v_{N\j}) + v_{N\ij}, each operation
+//                       rounded to fp32, written to [i, j] and [j, i]; the diagonal is v_N - v_{N\i}.
+#pragma once
+
+namespace cf {
+
+constexpr int kCoalMaxS = 16;                // cf_create accepts i_max in 1..16
+constexpr int kShapThreads = 256;
+
+struct CoalExpandArgs {
+    const float4* stash[kMaxRes];            // [B, T * D / 4] per resolution
+    float4* x0[kMaxRes];                     // Rx[r][0], rows of the chunk
+    const uint8_t* mask_in[kMaxRes];         // the caller's interaction_mask[r]   [B, T, T]
+    uint8_t* mask_out[kMaxRes];              // the chunk's                        [n, T, T]
+    const float* freq_in;                    // the caller's interaction_freq      [B, T, T]
+    float* freq_out;                         // the chunk's                        [n, T, T]
+    const unsigned* keep;                    // [n_coal] coalition words (device)
+    long long g0;                            // first row of the chunk
+    int n_coal, T;
+    int row4;                                // T * D / 4
+};
+
+__global__ __launch_bounds__(kAblThreads) void k_coalition_expand(CoalExpandArgs a) {
+    const int i = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
+    const long long g = a.g0 + i;
+    const int b = (int)(g / a.n_coal), T = a.T, TT = T * T;
+    // bit 0 of `gone` is the promoter token (never deleted), bit j + 1 pCRE slot j
+    const unsigned gone = ~(a.keep[g - (long long)b * a.n_coal] << 1) & ((1u << T) - 2u);
+    const float4* __restrict__ src = a.stash[r] + (size_t)b * a.row4;
+    float4* __restrict__ dst = a.x0[r] + (size_t)i * a.row4;
+    for (int k = tid; k < a.row4; k += kAblThreads) dst[k] = src[k];
+    const uint8_t* __restrict__ min = a.mask_in[r] + (size_t)b * TT;
+    uint8_t* __restrict__ mout = a.mask_out[r] + (size_t)i * TT;
+    for (int k = tid; k < TT; k += kAblThreads) {
+        const int row = k / T, col = k - row * T;
+        mout[k] = (gone >> row | gone >> col) & 1u ? (uint8_t)1 : min[k];
+    }
+    if (r == 0)
+        for (int k = tid; k < TT; k += kAblThreads) a.freq_out[(size_t)i * TT + k] = a.freq_in[(size_t)b * TT + k];
+}
+
+struct ShapleyArgs {
+    const float* v;                          // [B, 2^S, n_out]: the logits of every coalition, indexed by the word
+    float* phi;                              // [B, S, n_out]
+    float w[kCoalMaxS];                      // w[k], k = |m| < S
+    int S, n_out;
+};
+
+__global__ __launch_bounds__(kShapThreads) void k_shapley(ShapleyArgs a) {
+    __shared__ float sw[kCoalMaxS];
+    __shared__ float red[kShapThreads];
+    const int b = blockIdx.x, j = blockIdx.y, tid = threadIdx.x, S = a.S, n_out = a.n_out;
+#pragma unroll
+    for (int k = 0; k < kCoalMaxS; ++k)      // (constant indices into the kernel arguments: scalar loads, no private copy)
+        if (tid == k) sw[k] = a.w[k];
+    __syncthreads();
+    const unsigned half = 1u << (S - 1), low = (1u << j) - 1u, bit = 1u << j;
+    const float* __restrict__ v = a.v + ((size_t)b << S) * n_out;
+    for (int o = 0; o < n_out; ++o) {
+        float acc = 0.f;
+        for (unsigned q = tid; q < half; q += kShapThreads) {
+            const unsigned m = (q & ~low) << 1 | (q & low);      // the q-th word with bit j clear
+            const float d = __fsub_rn(v[(size_t)(m | bit) * n_out + o], v[(size_t)m * n_out + o]);
+            acc = __fadd_rn(acc, __fmul_rn(sw[__popc(m)], d));
+        }
+        red[tid] = acc;
+        __syncthreads();
+        for (int s = kShapThreads / 2; s > 0; s >>= 1) {
+            if (tid < s) red[tid] = __fadd_rn(red[tid], red[tid + s]);
+            __syncthreads();
+        }
+        if (tid == 0) a.phi[((size_t)b * S + j) * n_out + o] = red[0];
+        __syncthreads();
+    }
+}
+
+struct EpistasisArgs {
+    const float* v;                          // [B, 1 + S + S (S - 1) / 2, n_out]: the pair-deletion rows
+    float* eps;                              // [B, S, S, n_out]
+    int B, S, n_out;
+};
+
+__global__ __launch_bounds__(kShapThreads) void k_epistasis(EpistasisArgs a) {
+    const int S = a.S, n_out = a.n_out, R = 1 + S + S * (S - 1) / 2;
+    const long long n = (long long)a.B * S * S * n_out;
+    for (long long e = (long long)blockIdx.x * kShapThreads + threadIdx.x; e < n; e += (long long)gridDim.x * kShapThreads) {
+        const int o = (int)(e % n_out);
+        long long t = e / n_out;
+        const int c = (int)(t % S);
+        t /= S;
+        const int r = (int)(t % S), b = (int)(t / S);
+        const int i = r < c ? r : c, j = r < c ? c : r;      // [j, i] carries the bits of [i, j]
+        const float* __restrict__ v = a.v + (size_t)b * R * n_out + o;
+        float x = __fsub_rn(v[0], v[(size_t)(1 + i) * n_out]);
+        if (i < j) {
+            const int p = 1 + S + i * S - i * (i + 1) / 2 + (j - i - 1);      // pairs before row i: i S - i (i + 1) / 2
+            x = __fadd_rn(__fsub_rn(x, v[(size_t)(1 + j) * n_out]), v[(size_t)p * n_out]);
+        }
+        a.eps[e] = x;
+    }
+}
+
+}  // namespace cf

@@ -151,7 +151,7 @@ class ChromoformerBase(nn.Module):
         self.n_bins = [w_max // b for b in self.binsizes]
         self._kws = (embed, pair, reg)
         self._max_batch = max_batch
-        self._maps_gen = 0          # bumped by attention_maps() / pcre_ablation() / integrated_gradients() / trunk_outputs(): a pending backward of an earlier forward refuses to run
+        self._maps_gen = 0          # bumped by attention_maps() / pcre_ablation() / pcre_coalitions() / pcre_shapley() / pcre_epistasis() / integrated_gradients() / trunk_outputs(): a pending backward of an earlier forward refuses to run
         self._maps_by = None        # ... naming the last of them
         self._handle = None
         self._device = None
@@ -479,6 +479,91 @@ class ChromoformerBase(nn.Module):
         self._maps_by = "pcre_ablation"
         _lib.check(_lib.lib().cf_pcre_ablation(self._handle, C.byref(bs), logits.data_ptr(), st), "cf_pcre_ablation")
         return logits
+
+    def _coalition_call(self, who, args):
+        """What the coalition methods share -> (batch struct, keep-alive, stream): the packed batch, the pending-backward bookkeeping."""
+        if args[1] is None:
+            bs, keep = (args[0].struct if hasattr(args[0], "struct") else args[0][0]), args[0]
+        else:
+            bs, keep = self._pack(*args)
+        if self._handle is None:
+            raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
+        st = torch.cuda.current_stream(self._device).cuda_stream
+        self._sync_tiled(st)
+        self._maps_gen += 1
+        self._maps_by = who
+        return bs, keep, st
+
+    @torch.no_grad()
+    def pcre_coalitions(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                        interaction_freq=None, keep=None):
+        """The prediction under pCRE coalitions (cf_pcre_coalitions) -> logits [B, n_coal, n_out] on the model's device, no autograd
+        graph.  `keep`: a sequence / array of ints, bit j set = pCRE slot j kept, or a bool array [n_coal, i_max].  Column c is the
+        inference forward with interaction_masks row and column j + 1 set, at every resolution, for every slot j that keep[c] drops
+        (model(...) under no_grad on those masks, bit-equal): 2^i_max - 1 is the prediction, 0 the promoter alone; a bit of a slot
+        that is already a dummy changes nothing; a bit >= i_max raises ValueError.  The Embedding + Pairwise stage runs once, the
+        Regulation stack and the head on the B * n_coal rows.  The first argument may also be a packed batch (an engine.Slot or a
+        pack_batch result), with nothing after it.  The pass overwrites the activations a grad-enabled model(...) keeps for its
+        backward: such a pending backward() raises."""
+        from .attribution import coalition_words
+        if keep is None:
+            raise ValueError("pcre_coalitions: keep is required: the coalition words (bit j set: pCRE slot j kept)")
+        words = coalition_words(keep, self.i_max, "pcre_coalitions")
+        bs, _keep, st = self._coalition_call("pcre_coalitions", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks,
+                                                                 interaction_masks, interaction_freq))
+        logits = torch.empty(bs.B, len(words), self.n_out, device=self._device)      # (written in full by the library)
+        _lib.check(_lib.lib().cf_pcre_coalitions(self._handle, C.byref(bs), words.ctypes.data, len(words), logits.data_ptr(), st),
+                   "cf_pcre_coalitions")
+        return logits
+
+    @torch.no_grad()
+    def pcre_shapley(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                     interaction_freq=None, return_coalitions=False):
+        """Exact Shapley values of the pCRE slots (cf_pcre_shapley) -> (phi, info), tensors on the model's device, no autograd graph:
+
+          phi                    [B, i_max, n_out]: slot j's average marginal contribution to each logit over all orders of adding
+                                 the pCREs to the promoter; exactly 0 for a dummy slot
+          info["logits"]         [B, n_out]: the prediction (all pCREs kept; model(...) under no_grad, bit-equal)
+          info["promoter_only"]  [B, n_out]: the promoter alone
+          info["delta"]          [B, n_out]: phi.sum(1) - (logits - promoter_only), the efficiency gap (rounding only)
+          info["coalitions"]     [B, 2^i_max, n_out], with return_coalitions: the logits of every coalition, word m at column m
+
+        All 2^i_max coalitions run from one trunk pass (pcre_coalitions); the values are in logit space, where efficiency holds.
+        The first argument may also be a packed batch (an engine.Slot or a pack_batch result), with nothing after it.  The pass
+        overwrites the activations a grad-enabled model(...) keeps for its backward: such a pending backward() raises."""
+        bs, _keep, st = self._coalition_call("pcre_shapley", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks,
+                                                              interaction_masks, interaction_freq))
+        n = 1 << self.i_max
+        rows = torch.empty(bs.B, n, self.n_out, device=self._device)      # (both written in full by the library)
+        phi = torch.empty(bs.B, self.i_max, self.n_out, device=self._device)
+        _lib.check(_lib.lib().cf_pcre_shapley(self._handle, C.byref(bs), phi.data_ptr(), rows.data_ptr(), st), "cf_pcre_shapley")
+        info = {"logits": rows[:, n - 1].clone(), "promoter_only": rows[:, 0].clone()}
+        info["delta"] = phi.sum(1) - (info["logits"] - info["promoter_only"])
+        if return_coalitions:
+            info["coalitions"] = rows
+        return phi, info
+
+    @torch.no_grad()
+    def pcre_epistasis(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                       interaction_freq=None):
+        """Pair-deletion epistasis of the pCRE slots (cf_pcre_epistasis) -> (eps, info), tensors on the model's device, no autograd graph.
+        With v(...) the logits after deleting the named slots from the full gene:
+
+          eps[:, i, j]    [B, i_max, i_max, n_out]: ((v() - v(i)) - v(j)) + v(i, j) for i != j, exactly symmetric: 0 when the two
+                          deletions add up, non-zero when the pCREs are redundant or cooperate; eps[:, i, i] = v() - v(i), the
+                          leave-one-out effect; rows and columns of dummy slots are exactly 0
+          info["logits"]  [B, n_out]: v(), the prediction;  info["single"]  [B, i_max, n_out]: v(i)
+
+        The 1 + i_max + i_max (i_max - 1) / 2 rows (attribution.coalition_table("pairs", i_max)) run from one trunk pass.  The first
+        argument may also be a packed batch (an engine.Slot or a pack_batch result), with nothing after it.  The pass overwrites the
+        activations a grad-enabled model(...) keeps for its backward: such a pending backward() raises."""
+        bs, _keep, st = self._coalition_call("pcre_epistasis", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks,
+                                                                interaction_masks, interaction_freq))
+        S = self.i_max
+        rows = torch.empty(bs.B, 1 + S + S * (S - 1) // 2, self.n_out, device=self._device)      # (both written in full by the library)
+        eps = torch.empty(bs.B, S, S, self.n_out, device=self._device)
+        _lib.check(_lib.lib().cf_pcre_epistasis(self._handle, C.byref(bs), eps.data_ptr(), rows.data_ptr(), st), "cf_pcre_epistasis")
+        return eps, {"logits": rows[:, 0].clone(), "single": rows[:, 1:1 + S].clone()}
 
     @torch.no_grad()
     def integrated_gradients(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,

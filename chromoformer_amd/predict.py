@@ -123,6 +123,48 @@ def write_pcre_ablation(model, store, bsz, path, regression=False):
     mm.flush()
 
 
+def write_pcre_coalition_values(model, store, bsz, shapley_out=None, epistasis_out=None, regression=False):
+    """Exact Shapley values and / or pair-deletion epistasis of the pCREs of every gene of a device-resident store, in store order,
+    in LOGIT space of the prediction's column (1 for the classifier, 0 for the regressor: the efficiency identity
+    phi.sum(1) = logits - promoter_only holds there, not after the sigmoid).  shapley_out: an .npz with phi [n_genes, i_max],
+    logits [n_genes], promoter_only [n_genes] and n_pcres [n_genes] (the slots that are no dummies); epistasis_out: a float32 .npy
+    [n_genes, i_max, i_max].  Per batch: one device gather into a Slot, one model.pcre_shapley and / or one model.pcre_epistasis."""
+    import ctypes as C
+
+    from . import _lib
+    n, dev, L = len(store), model._device, _lib.lib()
+    S, t = model.i_max, 0 if regression else 1
+    phi, logits, alone = torch.empty(n, S), torch.empty(n), torch.empty(n)
+    n_pcres = torch.empty(n, dtype=torch.int32)
+    eps = np.lib.format.open_memmap(epistasis_out, mode="w+", dtype=np.float32, shape=(n, S, S)) if epistasis_out else None
+    struct = store.struct()
+    order = torch.arange(n, dtype=torch.int32, device=dev)
+    slots = {}
+    st = torch.cuda.current_stream(dev).cuda_stream
+    for lo in range(0, n, bsz):
+        B = min(bsz, n - lo)
+        slot = slots.get(B) or slots.setdefault(B, Slot(model, B))
+        cursor = torch.tensor([0, 1, 0, 0], dtype=torch.int32).to(dev)
+        _lib.check(L.cf_gather_batch(model._handle, C.byref(struct), order[lo:].data_ptr(), cursor.data_ptr(), C.byref(slot.struct), None, st),
+                   "cf_gather_batch")
+        if shapley_out:
+            p, info = model.pcre_shapley(slot)
+            phi[lo:lo + B] = p[..., t].cpu()
+            logits[lo:lo + B] = info["logits"][:, t].cpu()
+            alone[lo:lo + B] = info["promoter_only"][:, t].cpu()
+            dummy = torch.stack([m[:, 0, 1:] != 0 for m in slot.im]).all(0)      # a dummy slot: its key masked for the promoter row, every resolution
+            n_pcres[lo:lo + B] = (~dummy).sum(1).to(torch.int32).cpu()
+        if eps is not None:
+            eps[lo:lo + B] = model.pcre_epistasis(slot)[0][..., t].cpu().numpy()
+        if int(cursor[2].item()):
+            raise RuntimeError("write_pcre_coalition_values: the device-side gather reported errors at gene %d (store / order mismatch)" % lo)
+    if shapley_out:
+        with open(shapley_out, "wb") as f:      # (a file object: np.savez would append .npz to a name without it)
+            np.savez(f, phi=phi.numpy(), logits=logits.numpy(), promoter_only=alone.numpy(), n_pcres=n_pcres.numpy())
+    if eps is not None:
+        eps.flush()
+
+
 def write_integrated_gradients(model, store, bsz, ig_dir, n_steps=50, method="gausslegendre", target=None):
     """Integrated gradients of every gene of a device-resident store, in store order, into `ig_dir`: promoter_feats_{b}.npy
     [n, L, F], pcre_feats_{b}.npy [n, i_max, L, F], interaction_freq.npy [n, T, T] and delta.npy [n] (float32 .npy memory maps;
@@ -288,7 +330,7 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
             binsizes=(2000, 500, 100), progress=False, store_path=None, attention_dir=None, embeddings_out=None,
             pcre_ablation_out=None, ig_dir=None, ig_steps=50, ig_method="gausslegendre", ig_target=None, raw_saliency_dir=None,
             raw_saliency_target=None, raw_saliency_times_input=False, raw_ig_dir=None, scan_out=None, scan_scale=0.0, scan_width=1,
-            scan_regions="promoter"):
+            scan_regions="promoter", pcre_shapley_out=None, pcre_epistasis_out=None):
     """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file.  attention_dir / embeddings_out: also
     write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps); pcre_ablation_out:
     the predictions with each pCRE deleted (write_pcre_ablation); ig_dir: integrated gradients of every gene
@@ -296,7 +338,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     signals, one .npz per gene (write_raw_saliency; needs the raw .npy files also when a packed store serves the predictions);
     raw_ig_dir: integrated gradients with respect to the raw signals, one .npz per gene (write_raw_integrated_gradients; ig_steps,
     ig_method and ig_target apply; needs the raw .npy files too); scan_out: the in-silico perturbation scan of every gene, one .npz
-    (write_perturbation_scan; scan_scale, scan_width and scan_regions apply; served by a packed store as well)."""
+    (write_perturbation_scan; scan_scale, scan_width and scan_regions apply; served by a packed store as well); pcre_shapley_out /
+    pcre_epistasis_out: exact Shapley values / pair-deletion epistasis of the pCREs, in logit space (write_pcre_coalition_values)."""
     seed_everything(seed)
     meta = pd.read_csv(meta_path)
     genes = meta.gene_id.tolist()
@@ -326,6 +369,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     write_attention_maps(model, store, bsz, attention_dir, embeddings_out)
     if pcre_ablation_out:
         write_pcre_ablation(model, store, bsz, pcre_ablation_out, regression)
+    if pcre_shapley_out or pcre_epistasis_out:
+        write_pcre_coalition_values(model, store, bsz, pcre_shapley_out, pcre_epistasis_out, regression)
     if ig_dir:
         write_integrated_gradients(model, store, bsz, ig_dir, ig_steps, ig_method, ig_target)
     if scan_out:
@@ -352,6 +397,11 @@ def build_parser():
     ap.add_argument("--pcre-ablation-out", default=None, help="also write in-silico pCRE deletion to this .npy file: [n_genes, i_max + 2] "
                     "predictions in metadata order, column 0 as --output, column 1 + j with pCRE j deleted, the last with the promoter "
                     "alone (model.pcre_ablation)")
+    ap.add_argument("--pcre-shapley-out", default=None, help="also write the exact Shapley values of the pCREs to this .npz file, in metadata "
+                    "order and in LOGIT space of the prediction's column (efficiency holds there, not after the sigmoid): phi [n_genes, i_max] "
+                    "(0 for dummy slots), logits, promoter_only (phi sums to their difference) and n_pcres (model.pcre_shapley)")
+    ap.add_argument("--pcre-epistasis-out", default=None, help="also write the pair-deletion epistasis of the pCREs to this .npy file: "
+                    "[n_genes, i_max, i_max] in logit space, symmetric, the leave-one-out effects on the diagonal (model.pcre_epistasis)")
     from .attribution import METHODS
     ap.add_argument("--ig-dir", default=None, help="also write integrated gradients (zero baseline, every float input) of every gene, in "
                     "metadata order, as DIR/promoter_feats_{binsize}.npy [n, L, F], DIR/pcre_feats_{binsize}.npy [n, i_max, L, F], "
@@ -406,7 +456,8 @@ def main(argv=None):
                          ig_method=args.ig_method or "gausslegendre", ig_target=args.ig_target, raw_saliency_dir=args.raw_saliency_dir,
                          raw_saliency_target=args.raw_saliency_target, raw_saliency_times_input=args.raw_saliency_times_input,
                          raw_ig_dir=args.raw_ig_dir, scan_out=args.scan_out, scan_scale=0.0 if args.scan_scale is None else args.scan_scale,
-                         scan_width=1 if args.scan_width is None else args.scan_width, scan_regions=args.scan_regions or "promoter")
+                         scan_width=1 if args.scan_width is None else args.scan_width, scan_regions=args.scan_regions or "promoter",
+                         pcre_shapley_out=args.pcre_shapley_out, pcre_epistasis_out=args.pcre_epistasis_out)
     print("Predicting expressions for %d genes." % len(meta))
     meta["prediction"] = pred
     meta.to_csv(args.output, index=False)

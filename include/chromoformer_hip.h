@@ -211,6 +211,37 @@ int cf_attention_maps(cf_handle* h, const cf_batch* batch, float* logits, const 
  * cf_destroy; ~1 MB at max_batch 64); later calls allocate nothing.  A null handle / batch / logits or B > max_batch fails by name,
  * before anything is launched. */
 int cf_pcre_ablation(cf_handle* h, const cf_batch* batch, float* logits, void* stream);
+/* pCRE coalition forwards, exact Shapley values and pair epistasis (interpretation).  S = i_max.  A coalition is a 32-bit word m: bit
+ * j set = pCRE slot j kept.  Row (b, m) is the inference forward of gene b with its Regulation interaction mask (every resolution)
+ * replaced by the given mask OR row j+1 OR column j+1 for every j < S whose bit is clear; features, pad masks and interaction_freq
+ * are gene b's.  So m = 2^S - 1 is variant 0 of cf_pcre_ablation (the prediction), one clear bit j its variant 1 + j, m = 0 its
+ * variant S + 1 (the promoter alone), bit for bit; a bit of a slot that is already a dummy changes nothing.
+ * cf_pcre_coalitions: keep is a HOST array of n_coal words (read before the call returns); logits [B, n_coal, n_out], gene-major
+ * (b * n_coal + c).  Launches: the trunk part of cf_forward(save = 0) once, k_pcre_stash once, then per chunk of at most max_batch
+ * rows one k_coalition_expand and the Regulation + head launches of cf_forward(save = 0) on that chunk:
+ *   cf_launch_counts fwd = n_trunk + 1 + ceil(B * n_coal / max_batch) * (1 + n_reg_head)      (n_trunk, n_reg_head: see cf_pcre_ablation)
+ * The words travel in a device table the handle owns (grown on demand); the stash and chunk buffers are those of cf_pcre_ablation
+ * (whichever call comes first allocates them; cf_destroy frees them).  Overwrites the activations a cf_forward(save >= 1) kept: no
+ * cf_backward* may follow without a new saving forward.  Parameters, gradients and moments are untouched.  Deterministic (no
+ * atomics); the result does not depend on max_batch.  Refused by name, before anything is launched: a null handle / batch / logits,
+ * B > max_batch, n_coal < 1, a null keep, a word with a bit >= i_max set. */
+int cf_pcre_coalitions(cf_handle* h, const cf_batch* batch, const uint32_t* keep, int n_coal, float* logits, void* stream);
+/* Exact Shapley values of the pCRE slots: all 2^S coalitions through the routine above (word m at column m), then one k_shapley:
+ *   phi[b, j, o] = sum over m with bit j clear of w(|m|) (v[b, m | 1 << j, o] - v[b, m, o]),   w(k) = k! (S - k - 1)! / S!
+ * with the S weights computed on the host in double and rounded to fp32, every device operation rounded to fp32, in a fixed order
+ * (per thread an ascending stride of the words, then a fixed tree).  phi [B, S, n_out].  All S slots are players; a dummy slot is a
+ * null player (phi exactly 0), which leaves the live slots' values those of the game among the live slots.  Efficiency:
+ * sum_j phi[b, j] = v[b, 2^S - 1] - v[b, 0] up to rounding.  logits_all: [B, 2^S, n_out], or NULL: the rows go to a buffer the handle
+ * owns (allocated by the first such call for max_batch genes, freed by cf_destroy).  fwd = that of cf_pcre_coalitions with
+ * n_coal = 2^S, plus 1.  Accepted for every i_max (65,536 rows per gene at 16).  Refusals as above (null phi). */
+int cf_pcre_shapley(cf_handle* h, const cf_batch* batch, float* phi, float* logits_all, void* stream);
+/* Pair-deletion epistasis.  With N = 2^S - 1 the rows are: 0: N; 1 + i: N without i; then N without i and j for the pairs i < j in
+ * lexicographic order (1 + S + S (S - 1) / 2 rows), through the routine above, then one k_epistasis:
+ *   eps[b, i, j, o] = ((v_N - v_{N\i}) - v_{N\j}) + v_{N\{i,j}}   for i < j, every operation rounded to fp32 (no contraction);
+ *   eps[b, j, i] carries the bits of eps[b, i, j];  eps[b, i, i] = v_N - v_{N\i}.
+ * eps [B, S, S, n_out]; rows and columns of dummy slots are exactly 0.  logits_pairs: [B, 1 + S + S (S - 1) / 2, n_out], or NULL (a
+ * handle-owned buffer, as above).  fwd = that of cf_pcre_coalitions with that n_coal, plus 1.  Refusals as above (null eps). */
+int cf_pcre_epistasis(cf_handle* h, const cf_batch* batch, float* eps, float* logits_pairs, void* stream);
 /* Integrated gradients (interpretation).  For the target logit column t, nodes a_k and weights w_k (k < n_steps) on [0, 1], per
  * interpolated input x with baseline xb (T = i_max + 1):
  *   x_k   = xb + a_k (x - xb)                         fp32, each operation rounded
