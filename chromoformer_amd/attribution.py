@@ -79,13 +79,9 @@ def coalition_words(keep, i_max, who="pcre_coalitions"):
     return np.ascontiguousarray(a, dtype=np.uint32)
 
 
-def _raw_check(who, model, dataset, genes, target, bsz):
-    """The checks the raw-signal generators share -> (binsizes, n_bins, target, genes, chunk size)."""
+def _geometry_check(who, model, dataset, binsizes):
+    """The model is on the device and the dataset has its geometry -> n_bins."""
     ds = dataset
-    binsizes = [int(b) for b in ds.binsizes]
-    if len(binsizes) > 3 or len(set(binsizes)) != len(binsizes):
-        raise ValueError("%s: binsizes %s: more than three or repeated bin sizes are binned by one cf_bin_regions launch "
-                         "per resolution, which has no backward; use at most three distinct bin sizes" % (who, binsizes))
     if model._handle is None:
         raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
     n_bins = [ds.w_max // b for b in binsizes]
@@ -93,14 +89,29 @@ def _raw_check(who, model, dataset, genes, target, bsz):
         raise ValueError("%s: the dataset (binsizes %s, w_max %d, i_max %d, n_feats %d) does not match the model "
                          "(binsizes %s, w_max %d, i_max %d, n_feats %d)" % (who, binsizes, ds.w_max, ds.i_max, ds.n_feats, list(model.binsizes),
                                                                             model.w_max, model.i_max, model.n_feats))
+    return n_bins
+
+
+def _genes_check(who, model, dataset, genes, bsz):
+    """-> (the genes, all in the dataset's metadata; chunk size)."""
+    genes = list(dataset.target_genes if genes is None else genes)
+    missing = [g for g in genes if g not in dataset.genes]
+    if missing:
+        raise KeyError("%s: gene(s) %s are not in the dataset's metadata" % (who, missing[:5]))
+    return genes, model._max_batch if bsz is None else max(1, min(int(bsz), model._max_batch))
+
+
+def _raw_check(who, model, dataset, genes, target, bsz):
+    """The checks the raw-signal generators share -> (binsizes, n_bins, target, genes, chunk size)."""
+    binsizes = [int(b) for b in dataset.binsizes]
+    if len(binsizes) > 3 or len(set(binsizes)) != len(binsizes):
+        raise ValueError("%s: binsizes %s: more than three or repeated bin sizes are binned by one cf_bin_regions launch "
+                         "per resolution, which has no backward; use at most three distinct bin sizes" % (who, binsizes))
+    n_bins = _geometry_check(who, model, dataset, binsizes)
     target = (1 if model.n_out == 2 else 0) if target is None else int(target)
     if not 0 <= target < model.n_out:
         raise ValueError("%s: target = %d outside [0, n_out = %d)" % (who, target, model.n_out))
-    genes = list(ds.target_genes if genes is None else genes)
-    missing = [g for g in genes if g not in ds.genes]
-    if missing:
-        raise KeyError("%s: gene(s) %s are not in the dataset's metadata" % (who, missing[:5]))
-    chunk = model._max_batch if bsz is None else max(1, min(int(bsz), model._max_batch))
+    genes, chunk = _genes_check(who, model, dataset, genes, bsz)
     return binsizes, n_bins, target, genes, chunk
 
 
@@ -344,18 +355,9 @@ def perturbation_scan(model, dataset, genes=None, regions="promoter", scale=0.0,
     from . import pack
     from .data import GeneStore, promoter_col0
     ds = dataset
-    if model._handle is None:
-        raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
     binsizes = [int(b) for b in ds.binsizes]
-    n_bins = [ds.w_max // b for b in binsizes]
-    if binsizes != list(model.binsizes) or n_bins != list(model.n_bins) or ds.i_max != model.i_max or ds.n_feats != model.n_feats:
-        raise ValueError("perturbation_scan: the dataset (binsizes %s, w_max %d, i_max %d, n_feats %d) does not match the model "
-                         "(binsizes %s, w_max %d, i_max %d, n_feats %d)" % (binsizes, ds.w_max, ds.i_max, ds.n_feats, list(model.binsizes),
-                                                                            model.w_max, model.i_max, model.n_feats))
-    genes = list(ds.target_genes if genes is None else genes)
-    missing = [g for g in genes if g not in ds.genes]
-    if missing:
-        raise KeyError("perturbation_scan: gene(s) %s are not in the dataset's metadata" % (missing[:5],))
+    n_bins = _geometry_check("perturbation_scan", model, ds, binsizes)
+    genes, chunk = _genes_check("perturbation_scan", model, ds, genes, bsz)
     S, F, dev = ds.i_max, ds.n_feats, model._device
     if isinstance(regions, str):
         if regions not in ("promoter", "all"):
@@ -367,7 +369,6 @@ def perturbation_scan(model, dataset, genes=None, regions="promoter", scale=0.0,
     if mark_sets is None:
         mark_sets = [(f,) for f in range(F)] + [tuple(range(F))]
     mark_sets = [tuple(int(f) for f in ms) for ms in mark_sets]
-    chunk = model._max_batch if bsz is None else max(1, min(int(bsz), model._max_batch))
     rc = int(np.argmin(n_bins))
     W, bc = n_bins[rc], binsizes[rc]
     col0 = promoter_col0(ds)

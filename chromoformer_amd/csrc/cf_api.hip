@@ -5,7 +5,7 @@
 #include "cf_kernels.h"
 #include "cf_input_grad.h"
 #include "cf_attn_maps.h"
-#include "cf_ablate.h"
+#include "cf_rows.h"
 #include "cf_coalition.h"
 #include "cf_ig.h"
 #include "cf_scan.h"
@@ -339,12 +339,12 @@ struct cf_handle {
     float* dfreq_part = nullptr;               // [n_res][max_batch][T * T]: d(interaction_freq) per resolution, summed by k_dfreq_sum
     bool reg_dfreq_ok = false;                 // k_reg8_bwd_dfreq got its LDS attribute
     bool ig_smem_ok = false;                   // k_input_grad got its LDS attribute (first use)
-    // in-silico pCRE deletion (cf_pcre_ablation): one allocation, made by the first call (ablate_alloc)
+    // in-silico pCRE deletion and coalitions (cf_coalition.h): one allocation, made by the first call (ablate_alloc)
     float* abl_stash[kMaxRes] = {};            // [max_batch, T, d_emb] per resolution: the trunk's output, Rx[r][0]
     float* abl_freq = nullptr;                 // [max_batch, T, T]: interaction_freq of a chunk's gene-variants
     uint8_t* abl_mask[kMaxRes] = {};           // [max_batch, T, T] per resolution: their interaction masks
+    const unsigned* abl_tab = nullptr;         // [i_max + 2]: the coalition words of cf_pcre_ablation's variants, written once
     void* abl_mem = nullptr;
-    // pCRE coalitions (cf_pcre_coalitions / cf_pcre_shapley / cf_pcre_epistasis; cf_coalition.h): the chunk buffers are the ablation's
     unsigned* coal_tab = nullptr;              // [coal_cap]: the coalition words of a call; grows on demand
     long long coal_cap = 0;
     float* coal_rows = nullptr;                // [max_batch, coal_rows_per, n_out]: the rows of a Shapley / epistasis call without a caller's buffer
@@ -2677,9 +2677,7 @@ extern "C" int cf_trunk_outputs(cf_handle* h, const cf_batch* bt, float* const* 
     const long long launches0 = g_launches;
     if (forward_trunk(h, bt, 0, st) || x0_copy(h, bt->B, src, x0, st)) return -1;
     h->x0_fwd = false;
-    h->last_fwd_B = 0;      // (the activations a saving forward kept are overwritten)
-    h->n_fwd = (int)(g_launches - launches0);
-    if (h->capturing) h->cap.n_fwd = h->n_fwd;
+    forward_counted(h, launches0);
     return 0;
 }
 extern "C" int cf_forward_train_x0(cf_handle* h, const cf_batch* bt, const float* const* x0, float* logits, const void* labels, float loss_scale,

@@ -116,6 +116,19 @@ extern "C" int cf_backward_from_inputs(cf_handle* h, const cf_batch* bt, const f
     return reduce_impl(h, B, st);
 }
 
+// The epilogue of the forward-only entry points: the activations a saving forward kept are gone (a later cf_backward* is refused),
+// the launches since `launches0` are the forward's count (mirrored into a capture).
+static void forward_counted(cf_handle* h, long long launches0) {
+    h->last_fwd_B = 0;
+    h->n_fwd = (int)(g_launches - launches0);
+    if (h->capturing) h->cap.n_fwd = h->n_fwd;
+}
+// One more launch (a copy-out or a reducer) on the account of the forward
+static void forward_one_more(cf_handle* h) {
+    ++h->n_fwd;
+    if (h->capturing) h->cap.n_fwd = h->n_fwd;
+}
+
 // cf_forward(save = 1) + k_attn_maps (cf_attn_maps.h): the attention probabilities the forward kept for the backward pass and the
 // fc_head input, copied into the caller's dense layouts.  Nothing requested: exactly the launches of cf_forward(save = 1).
 extern "C" int cf_attention_maps(cf_handle* h, const cf_batch* bt, float* logits, const cf_attn_maps* want, void* stream) {
@@ -171,97 +184,46 @@ extern "C" int cf_attention_maps(cf_handle* h, const cf_batch* bt, float* logits
     const int gx = (int)std::min<long long>((most + kMapThreads - 1) / kMapThreads, 1024);
     hipLaunchKernelGGL(k_attn_maps, dim3(gx, kMapSegs), dim3(kMapThreads), 0, (hipStream_t)stream, a);
     LAUNCH_CHECK("k_attn_maps");
-    ++h->n_fwd;
-    if (h->capturing) h->cap.n_fwd = h->n_fwd;
+    forward_one_more(h);
     return 0;
 }
 
 // The buffers of cf_pcre_ablation and of the coalition entry points, allocated by the first call of any of them (the model's other
-// entry points never need them).
-static int ablate_alloc(cf_handle* h, const char* who = "cf_pcre_ablation") {
+// entry points never need them); the ablation's i_max + 2 coalition words (cf_coalition.h) are written here, once.
+static int ablate_alloc(cf_handle* h, const char* who) {
     if (h->abl_mem) return 0;
     const cf_config& c = h->cfg;
     const size_t T = c.i_max + 1, rows = (size_t)c.max_batch * T, x0 = rows * c.d_emb, tt = (size_t)c.max_batch * T * T;
-    const size_t freq_off = c.n_res * x0, mask_off = freq_off + tt;      // (floats; the masks follow as bytes)
+    const size_t freq_off = c.n_res * x0, tab_off = freq_off + tt, mask_off = tab_off + T + 1;      // (floats; the masks follow as bytes)
     void* q = nullptr;
     if (hipMalloc(&q, mask_off * sizeof(float) + c.n_res * tt) != hipSuccess) return fail("%s: out of memory", who);
-    h->abl_mem = q;
     float* f = (float*)q;
+    const unsigned N = (1u << c.i_max) - 1u;
+    std::vector<unsigned> words(T + 1, N);
+    for (int j = 0; j < c.i_max; ++j) words[1 + j] = N & ~(1u << j);
+    words[T] = 0;
+    if (hipMemcpy(f + tab_off, words.data(), (T + 1) * sizeof(unsigned), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(q);
+        return fail("%s: writing the deletion table failed", who);
+    }
+    h->abl_mem = q;
     for (int r = 0; r < c.n_res; ++r) {
         h->abl_stash[r] = f + r * x0;
         h->abl_mask[r] = (uint8_t*)(f + mask_off) + r * tt;
     }
     h->abl_freq = f + freq_off;
+    h->abl_tab = (const unsigned*)(f + tab_off);
     return 0;
 }
 
-// The trunk once on the B genes, k_pcre_stash, then per chunk of at most max_batch of the B * V gene-variants (V = i_max + 2,
-// gene-major) k_pcre_expand and the Regulation + head launches of an inference forward on a batch of that chunk (cf_ablate.h).
-extern "C" int cf_pcre_ablation(cf_handle* h, const cf_batch* bt, float* logits, void* stream) {
-    if (!h) return fail("cf_pcre_ablation: null handle");
-    if (!bt) return fail("cf_pcre_ablation: null batch");
-    if (!logits) return fail("cf_pcre_ablation: null logits");
+// The shared host routine of cf_pcre_ablation and the coalition entry points (cf_coalition.h): the trunk once on the B genes,
+// k_pcre_stash, then per chunk of at most max_batch of the B * n_coal rows (gene-major; row (b, k) is word tab[k], a device table) one
+// k_coalition_expand and the Regulation + head launches of an inference forward on that chunk, writing the chunk's contiguous slice of
+// `logits`.  The callers have checked the batch and called ablate_alloc.
+static int coalition_rows(cf_handle* h, const cf_batch* bt, const unsigned* tab, int n_coal, float* logits, hipStream_t st) {
     const cf_config& c = h->cfg;
-    if (bt->B > c.max_batch) return fail("cf_pcre_ablation: batch size %d exceeds max_batch=%d", bt->B, c.max_batch);
-    if (check_batch(h, bt)) return -1;
-    if (ablate_alloc(h)) return -1;
-    hipStream_t st = (hipStream_t)stream;
+    const int B = bt->B, T = c.i_max + 1, nres = c.n_res, cap = c.max_batch;
     const long long launches0 = g_launches;
-    const int B = bt->B, S = c.i_max, T = S + 1, V = S + 2, nres = c.n_res, cap = c.max_batch;
-    const int row4 = T * c.d_emb / 4;
-    if (forward_trunk(h, bt, 0, st) || stash_trunk_output(h, B, h->abl_stash, st)) return -1;
-    AblateExpandArgs ea;
-    memset(&ea, 0, sizeof ea);
-    cf_batch cb = *bt;      // the chunk's batch: only B, the masks and the frequencies are read past the trunk
-    for (int r = 0; r < nres; ++r) {
-        ea.stash[r] = reinterpret_cast<const float4*>(h->abl_stash[r]);
-        ea.x0[r] = reinterpret_cast<float4*>(h->Rx[r][0]);
-        ea.mask_in[r] = bt->interaction_mask[r];
-        ea.mask_out[r] = h->abl_mask[r];
-        cb.interaction_mask[r] = h->abl_mask[r];
-    }
-    ea.freq_in = bt->interaction_freq;
-    ea.freq_out = h->abl_freq;
-    cb.interaction_freq = h->abl_freq;
-    ea.V = V, ea.S = S, ea.T = T, ea.row4 = row4;
-    for (int g0 = 0; g0 < B * V; g0 += cap) {
-        const int n = std::min(cap, B * V - g0);
-        ea.g0 = g0;
-        hipLaunchKernelGGL(k_pcre_expand, dim3(n, nres), dim3(kAblThreads), 0, st, ea);
-        LAUNCH_CHECK("k_pcre_expand");
-        cb.B = n;
-        if (forward_reg_head(h, &cb, logits + (size_t)g0 * c.n_out, 0, st, nullptr)) return -1;
-    }
-    h->last_fwd_B = 0;
-    h->n_fwd = (int)(g_launches - launches0);
-    if (h->capturing) h->cap.n_fwd = h->n_fwd;
-    return 0;
-}
-
-// The shared host routine of the coalition entry points (cf_coalition.h): the trunk once on the B genes, k_pcre_stash, the words into
-// the handle's device table, then per chunk of at most max_batch of the B * n_coal rows (gene-major) one k_coalition_expand and the
-// Regulation + head launches of an inference forward on that chunk, writing the chunk's contiguous slice of `logits`.  The callers
-// have checked h, bt and logits.
-static int coalition_rows(cf_handle* h, const cf_batch* bt, const uint32_t* keep, int n_coal, float* logits, hipStream_t st, const char* who) {
-    const cf_config& c = h->cfg;
-    if (bt->B > c.max_batch) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, c.max_batch);
-    if (n_coal < 1) return fail("%s: n_coal = %d: at least 1 coalition", who, n_coal);
-    if (!keep) return fail("%s: null keep", who);
-    const int B = bt->B, S = c.i_max, T = S + 1, nres = c.n_res, cap = c.max_batch;
-    for (int k = 0; k < n_coal; ++k)
-        if (keep[k] >> S) return fail("%s: keep[%d] = 0x%x names a pCRE slot >= i_max = %d", who, k, keep[k], S);
-    if (check_batch(h, bt)) return -1;
-    if (ablate_alloc(h, who)) return -1;
-    if (n_coal > h->coal_cap) {
-        const long long want = std::max<long long>(n_coal, 256);
-        if (h->coal_tab) (void)hipFree(h->coal_tab);      // (synchronises: a call in flight may still read the old table)
-        h->coal_tab = nullptr;
-        h->coal_cap = 0;
-        if (hipMalloc(&h->coal_tab, (size_t)want * sizeof(unsigned)) != hipSuccess) return fail("%s: out of memory", who);
-        h->coal_cap = want;
-    }
-    const long long launches0 = g_launches;
-    HIP_TRY(hipMemcpyAsync(h->coal_tab, keep, (size_t)n_coal * sizeof(unsigned), hipMemcpyHostToDevice, st));
     if (forward_trunk(h, bt, 0, st) || stash_trunk_output(h, B, h->abl_stash, st)) return -1;
     CoalExpandArgs ea;
     memset(&ea, 0, sizeof ea);
@@ -276,7 +238,7 @@ static int coalition_rows(cf_handle* h, const cf_batch* bt, const uint32_t* keep
     ea.freq_in = bt->interaction_freq;
     ea.freq_out = h->abl_freq;
     cb.interaction_freq = h->abl_freq;
-    ea.keep = h->coal_tab;
+    ea.keep = tab;
     ea.n_coal = n_coal, ea.T = T, ea.row4 = T * c.d_emb / 4;
     const long long rows = (long long)B * n_coal;
     for (long long g0 = 0; g0 < rows; g0 += cap) {
@@ -287,9 +249,39 @@ static int coalition_rows(cf_handle* h, const cf_batch* bt, const uint32_t* keep
         cb.B = n;
         if (forward_reg_head(h, &cb, logits + (size_t)g0 * c.n_out, 0, st, nullptr)) return -1;
     }
-    h->last_fwd_B = 0;
-    h->n_fwd = (int)(g_launches - launches0);
-    if (h->capturing) h->cap.n_fwd = h->n_fwd;
+    forward_counted(h, launches0);
+    return 0;
+}
+
+// The fixed table of ablate_alloc through coalition_rows: variant v of gene b is row (b, v).
+extern "C" int cf_pcre_ablation(cf_handle* h, const cf_batch* bt, float* logits, void* stream) {
+    const char* who = "cf_pcre_ablation";
+    if (!h) return fail("%s: null handle", who);
+    if (!bt) return fail("%s: null batch", who);
+    if (!logits) return fail("%s: null logits", who);
+    if (bt->B > h->cfg.max_batch) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, h->cfg.max_batch);
+    if (check_batch(h, bt) || ablate_alloc(h, who)) return -1;
+    return coalition_rows(h, bt, h->abl_tab, h->cfg.i_max + 2, logits, (hipStream_t)stream);
+}
+
+// A host `keep` array validated and uploaded into the handle's device table (in front of coalition_rows); checks the batch.
+static int coalition_upload(cf_handle* h, const cf_batch* bt, const uint32_t* keep, int n_coal, hipStream_t st, const char* who) {
+    const cf_config& c = h->cfg;
+    if (bt->B > c.max_batch) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, c.max_batch);
+    if (n_coal < 1) return fail("%s: n_coal = %d: at least 1 coalition", who, n_coal);
+    if (!keep) return fail("%s: null keep", who);
+    for (int k = 0; k < n_coal; ++k)
+        if (keep[k] >> c.i_max) return fail("%s: keep[%d] = 0x%x names a pCRE slot >= i_max = %d", who, k, keep[k], c.i_max);
+    if (check_batch(h, bt) || ablate_alloc(h, who)) return -1;
+    if (n_coal > h->coal_cap) {
+        const long long want = std::max<long long>(n_coal, 256);
+        if (h->coal_tab) (void)hipFree(h->coal_tab);      // (synchronises: a call in flight may still read the old table)
+        h->coal_tab = nullptr;
+        h->coal_cap = 0;
+        if (hipMalloc(&h->coal_tab, (size_t)want * sizeof(unsigned)) != hipSuccess) return fail("%s: out of memory", who);
+        h->coal_cap = want;
+    }
+    HIP_TRY(hipMemcpyAsync(h->coal_tab, keep, (size_t)n_coal * sizeof(unsigned), hipMemcpyHostToDevice, st));
     return 0;
 }
 
@@ -298,7 +290,9 @@ extern "C" int cf_pcre_coalitions(cf_handle* h, const cf_batch* bt, const uint32
     if (!h) return fail("%s: null handle", who);
     if (!bt) return fail("%s: null batch", who);
     if (!logits) return fail("%s: null logits", who);
-    return coalition_rows(h, bt, keep, n_coal, logits, (hipStream_t)stream, who);
+    hipStream_t st = (hipStream_t)stream;
+    if (coalition_upload(h, bt, keep, n_coal, st, who)) return -1;
+    return coalition_rows(h, bt, h->coal_tab, n_coal, logits, st);
 }
 
 // The rows of a Shapley / epistasis call whose caller gave no buffer: [max_batch, per, n_out], allocated by the first such call.
@@ -315,13 +309,8 @@ static float* coalition_own_rows(cf_handle* h, long long per, const char* who) {
     }
     return h->coal_rows;
 }
-// One more launch (the reducer) on the account of the forward
-static void coalition_count_reducer(cf_handle* h) {
-    ++h->n_fwd;
-    if (h->capturing) h->cap.n_fwd = h->n_fwd;
-}
 
-// All 2^i_max coalitions through coalition_rows (word m at column m), then k_shapley.
+// All 2^i_max coalitions through coalition_upload + coalition_rows (word m at column m), then k_shapley.
 extern "C" int cf_pcre_shapley(cf_handle* h, const cf_batch* bt, float* phi, float* logits_all, void* stream) {
     const char* who = "cf_pcre_shapley";
     if (!h) return fail("%s: null handle", who);
@@ -335,7 +324,7 @@ extern "C" int cf_pcre_shapley(cf_handle* h, const cf_batch* bt, float* phi, flo
     std::vector<uint32_t> keep(n);
     for (int m = 0; m < n; ++m) keep[m] = (uint32_t)m;
     hipStream_t st = (hipStream_t)stream;
-    if (coalition_rows(h, bt, keep.data(), n, rows, st, who)) return -1;
+    if (coalition_upload(h, bt, keep.data(), n, st, who) || coalition_rows(h, bt, h->coal_tab, n, rows, st)) return -1;
     ShapleyArgs sa;
     memset(&sa, 0, sizeof sa);
     sa.v = rows, sa.phi = phi, sa.S = S, sa.n_out = c.n_out;
@@ -344,11 +333,11 @@ extern "C" int cf_pcre_shapley(cf_handle* h, const cf_batch* bt, float* phi, flo
     for (int k = 0; k < S; ++k) sa.w[k] = (float)(fact[k] * fact[S - k - 1] / fact[S]);
     hipLaunchKernelGGL(k_shapley, dim3(bt->B, S), dim3(kShapThreads), 0, st, sa);
     LAUNCH_CHECK("k_shapley");
-    coalition_count_reducer(h);
+    forward_one_more(h);
     return 0;
 }
 
-// The 1 + S + S (S - 1) / 2 pair-deletion coalitions through coalition_rows, then k_epistasis.
+// The 1 + S + S (S - 1) / 2 pair-deletion coalitions through coalition_upload + coalition_rows, then k_epistasis.
 extern "C" int cf_pcre_epistasis(cf_handle* h, const cf_batch* bt, float* eps, float* logits_pairs, void* stream) {
     const char* who = "cf_pcre_epistasis";
     if (!h) return fail("%s: null handle", who);
@@ -367,13 +356,13 @@ extern "C" int cf_pcre_epistasis(cf_handle* h, const cf_batch* bt, float* eps, f
     float* rows = logits_pairs ? logits_pairs : coalition_own_rows(h, R, who);
     if (!rows) return -1;
     hipStream_t st = (hipStream_t)stream;
-    if (coalition_rows(h, bt, keep.data(), R, rows, st, who)) return -1;
+    if (coalition_upload(h, bt, keep.data(), R, st, who) || coalition_rows(h, bt, h->coal_tab, R, rows, st)) return -1;
     EpistasisArgs ea;
     ea.v = rows, ea.eps = eps, ea.B = bt->B, ea.S = S, ea.n_out = c.n_out;
     const long long n = (long long)bt->B * S * S * c.n_out;
     hipLaunchKernelGGL(k_epistasis, dim3((int)std::min<long long>((n + kShapThreads - 1) / kShapThreads, 1024)), dim3(kShapThreads), 0, st, ea);
     LAUNCH_CHECK("k_epistasis");
-    coalition_count_reducer(h);
+    forward_one_more(h);
     return 0;
 }
 
@@ -423,6 +412,40 @@ static int intg_alloc(cf_handle* h, int n_steps) {
         h->intg_cap = cap;
     }
     return 0;
+}
+
+// A chunk of rows in the intg_* buffers (cf_integrated_gradients, cf_perturbation_scan): the chunk's batch `cb` (all but B) and the
+// description `ra` of the mask rows its expand kernel copies from the caller's batch (cf_rows.h).
+static void intg_chunk_rows(cf_handle* h, const cf_batch* bt, RowCopyArgs* ra, cf_batch* cb) {
+    const cf_config& c = h->cfg;
+    memset(ra, 0, sizeof *ra);
+    memset(cb, 0, sizeof *cb);
+    for (int r = 0; r < c.n_res; ++r) {
+        const int L = c.n_bins[r];
+        // The all-rows Embedding (embed.n_layers > 1) honours a full [B, L, L] promoter mask entry by entry: the chunk rows carry
+        // all L rows of their gene's mask, not the centre row alone (from which only the dataset's not(valid x valid) form can be rebuilt).
+        const bool pm_full = h->embed_dense && bt->promoter_mask_stride[r] == (long long)L * L;
+        ra->pm_rows[r] = pm_full ? L : 1;
+        ra->pm_in[r] = static_cast<const uint8_t*>(bt->promoter_mask_row[r]) - (pm_full ? (size_t)(L / 2) * L : 0);
+        ra->cm_in[r] = bt->pcre_mask_row[r];
+        ra->pm_stride[r] = bt->promoter_mask_stride[r];
+        ra->cm_stride[r] = bt->pcre_mask_stride[r];
+        ra->pm_out[r] = h->intg_pm[r];
+        ra->cm_out[r] = h->intg_cm[r];
+        ra->im_in[r] = bt->interaction_mask[r];
+        ra->im_out[r] = h->intg_im[r];
+        ra->L[r] = L;
+        cb->promoter_feats[r] = h->intg_row[r];
+        cb->pcre_feats[r] = h->intg_row[kMaxRes + r];
+        cb->promoter_mask_row[r] = h->intg_pm[r] + (pm_full ? (size_t)(L / 2) * L : 0);
+        cb->promoter_mask_stride[r] = pm_full ? (long long)L * L : L;
+        cb->pcre_mask_row[r] = h->intg_cm[r];
+        cb->pcre_mask_stride[r] = L;
+        cb->interaction_mask[r] = h->intg_im[r];
+    }
+    cb->interaction_freq = h->intg_row[2 * kMaxRes];
+    ra->S = c.i_max;
+    ra->TT = (c.i_max + 1) * (c.i_max + 1);
 }
 
 // Integrated gradients (cf_ig.h).  General path, per chunk of at most max_batch of the B * V rows: k_ig_expand, the launches of
@@ -493,42 +516,21 @@ static int integrated_gradients_impl(cf_handle* h, const cf_batch* bt, const cf_
     memset(&ea, 0, sizeof ea);
     memset(&aa, 0, sizeof aa);
     cf_batch cb;      // the chunk's batch: the rows' copies
-    memset(&cb, 0, sizeof cb);
+    intg_chunk_rows(h, bt, &ea.rows, &cb);
     for (int r = 0; r < nres; ++r) {
         const int L = c.n_bins[r];
         IgSeg* sp = &ea.seg[r];
         IgSeg* sc = &ea.seg[kMaxRes + r];
         *sp = IgSeg{bt->promoter_feats[r], o->base_promoter_feats[r], h->intg_row[r], h->intg_grad[r], out->promoter_feats[r], L * F};
         *sc = IgSeg{bt->pcre_feats[r], o->base_pcre_feats[r], h->intg_row[kMaxRes + r], h->intg_grad[kMaxRes + r], out->pcre_feats[r], S * L * F};
-        // The all-rows Embedding (embed.n_layers > 1) honours a full [B, L, L] promoter mask entry by entry: the chunk rows carry
-        // all L rows of their gene's mask, not the centre row alone (from which only the dataset's not(valid x valid) form can be rebuilt).
-        const bool pm_full = h->embed_dense && bt->promoter_mask_stride[r] == (long long)L * L;
-        ea.pm_rows[r] = pm_full ? L : 1;
-        ea.pm_in[r] = static_cast<const uint8_t*>(bt->promoter_mask_row[r]) - (pm_full ? (size_t)(L / 2) * L : 0);
-        ea.cm_in[r] = bt->pcre_mask_row[r];
-        ea.pm_stride[r] = bt->promoter_mask_stride[r];
-        ea.cm_stride[r] = bt->pcre_mask_stride[r];
-        ea.pm_out[r] = h->intg_pm[r];
-        ea.cm_out[r] = h->intg_cm[r];
-        ea.im_in[r] = bt->interaction_mask[r];
-        ea.im_out[r] = h->intg_im[r];
         ea.stash[r] = reinterpret_cast<const float4*>(h->intg_stash[r]);
         ea.x0[r] = reinterpret_cast<float4*>(h->Rx[r][0]);
-        ea.L[r] = L;
-        cb.promoter_feats[r] = h->intg_row[r];
-        cb.pcre_feats[r] = h->intg_row[kMaxRes + r];
-        cb.promoter_mask_row[r] = h->intg_pm[r] + (pm_full ? (size_t)(L / 2) * L : 0);
-        cb.promoter_mask_stride[r] = pm_full ? (long long)L * L : L;
-        cb.pcre_mask_row[r] = h->intg_cm[r];
-        cb.pcre_mask_stride[r] = L;
-        cb.interaction_mask[r] = h->intg_im[r];
     }
     ea.seg[2 * kMaxRes] = IgSeg{bt->interaction_freq, o->base_interaction_freq, h->intg_row[2 * kMaxRes], h->intg_grad[2 * kMaxRes], out->interaction_freq, TT};
-    cb.interaction_freq = h->intg_row[2 * kMaxRes];
     ea.alpha = h->intg_tab;
     ea.weight = h->intg_tab + h->intg_cap;
     ea.dlogits = h->dlogits;
-    ea.V = V, ea.S = S, ea.TT = TT, ea.n_out = c.n_out, ea.target = o->target, ea.nres = nres, ea.bcast = o->base_broadcast ? 1 : 0;
+    ea.V = V, ea.n_out = c.n_out, ea.target = o->target, ea.nres = nres, ea.bcast = o->base_broadcast ? 1 : 0;
     ea.freq_only = freq_only ? 1 : 0;
     ea.row4 = T * kD / 4;
     memcpy(aa.seg, ea.seg, sizeof aa.seg);
@@ -632,7 +634,7 @@ extern "C" int cf_perturbation_scan(cf_handle* h, const cf_batch* bt, const cf_s
     if (!logits) return fail("%s: null logits", who);
     if (!o->mark_sets) return fail("%s: null mark_sets", who);
     const cf_config& c = h->cfg;
-    const int nres = c.n_res, S = c.i_max, T = S + 1, F = c.n_feats, cap = c.max_batch;
+    const int nres = c.n_res, S = c.i_max, F = c.n_feats, cap = c.max_batch;
     if (bt->B > cap) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, cap);
     if (o->region < 0 || o->region > S) return fail("%s: region = %d outside [0, i_max = %d]", who, o->region, S);
     if (o->width < 1) return fail("%s: width = %d: at least 1 coarsest bin", who, o->width);
@@ -652,28 +654,18 @@ extern "C" int cf_perturbation_scan(cf_handle* h, const cf_batch* bt, const cf_s
     if (check_batch(h, bt)) return -1;
     if (intg_alloc(h, o->n_sets)) return -1;
     hipStream_t st = (hipStream_t)stream;
-    const int B = bt->B, V = 1 + o->n_sets * W, TT = T * T, slot = o->region - 1;
+    const int B = bt->B, V = 1 + o->n_sets * W, slot = o->region - 1;
     HIP_TRY(hipMemcpyAsync(h->intg_tab, o->mark_sets, o->n_sets * sizeof(unsigned), hipMemcpyHostToDevice, st));
     ScanExpandArgs ea;
     memset(&ea, 0, sizeof ea);
     cf_batch cb;      // the chunk's batch: the rows' copies
-    memset(&cb, 0, sizeof cb);
+    intg_chunk_rows(h, bt, &ea.rows, &cb);
     for (int r = 0; r < nres; ++r) {
-        const int L = c.n_bins[r];
         ea.pf_in[r] = bt->promoter_feats[r];
         ea.cf_in[r] = bt->pcre_feats[r];
         ea.pf_out[r] = h->intg_row[r];
         ea.cf_out[r] = h->intg_row[kMaxRes + r];
         ea.feats_out[r] = o->feats_out[r];
-        // (the all-rows Embedding reads the caller's full [B, L, L] promoter mask: the chunk rows carry all L rows, as in cf_integrated_gradients)
-        const bool pm_full = h->embed_dense && bt->promoter_mask_stride[r] == (long long)L * L;
-        ea.pm_rows[r] = pm_full ? L : 1;
-        ea.pm_in[r] = static_cast<const uint8_t*>(bt->promoter_mask_row[r]) - (pm_full ? (size_t)(L / 2) * L : 0);
-        ea.cm_in[r] = bt->pcre_mask_row[r];
-        ea.pm_stride[r] = bt->promoter_mask_stride[r];
-        ea.cm_stride[r] = bt->pcre_mask_stride[r];
-        ea.pm_out[r] = h->intg_pm[r];
-        ea.cm_out[r] = h->intg_cm[r];
         if (slot < 0) {
             ea.rm_in[r] = bt->promoter_mask_row[r];
             ea.rm_stride[r] = bt->promoter_mask_stride[r];
@@ -681,24 +673,13 @@ extern "C" int cf_perturbation_scan(cf_handle* h, const cf_batch* bt, const cf_s
             ea.rm_in[r] = bt->pcre_mask_row[r] + (long long)slot * bt->pcre_mask_stride[r];
             ea.rm_stride[r] = (long long)S * bt->pcre_mask_stride[r];
         }
-        ea.im_in[r] = bt->interaction_mask[r];
-        ea.im_out[r] = h->intg_im[r];
-        ea.L[r] = L;
-        cb.promoter_feats[r] = h->intg_row[r];
-        cb.pcre_feats[r] = h->intg_row[kMaxRes + r];
-        cb.promoter_mask_row[r] = h->intg_pm[r] + (pm_full ? (size_t)(L / 2) * L : 0);
-        cb.promoter_mask_stride[r] = pm_full ? (long long)L * L : L;
-        cb.pcre_mask_row[r] = h->intg_cm[r];
-        cb.pcre_mask_stride[r] = L;
-        cb.interaction_mask[r] = h->intg_im[r];
     }
     ea.freq_in = bt->interaction_freq;
     ea.freq_out = h->intg_row[2 * kMaxRes];
-    cb.interaction_freq = h->intg_row[2 * kMaxRes];
     ea.sets = reinterpret_cast<const unsigned*>(h->intg_tab);
     ea.flip = o->flip;
     ea.scale = o->scale;
-    ea.V = V, ea.S = S, ea.TT = TT, ea.F = F, ea.W = W, ea.width = o->width, ea.rc = rc, ea.region = o->region;
+    ea.V = V, ea.F = F, ea.W = W, ea.width = o->width, ea.rc = rc, ea.region = o->region;
     const long long launches0 = g_launches;
     int rv = 0;
     for (int g0 = 0; g0 < B * V && !rv; g0 += cap) {
@@ -710,8 +691,6 @@ extern "C" int cf_perturbation_scan(cf_handle* h, const cf_batch* bt, const cf_s
         rv = forward_trunk(h, &cb, 0, st, B) || forward_reg_head(h, &cb, logits + (size_t)g0 * c.n_out, 0, st, nullptr);
     }
     h->x0_fwd = false;
-    h->last_fwd_B = 0;
-    h->n_fwd = (int)(g_launches - launches0);
-    if (h->capturing) h->cap.n_fwd = h->n_fwd;
+    forward_counted(h, launches0);
     return rv ? -1 : 0;
 }

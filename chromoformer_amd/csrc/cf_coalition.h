@@ -1,11 +1,18 @@
-// cf_coalition.h -- pCRE coalition forwards, exact Shapley values and pair epistasis (cf_pcre_coalitions, cf_pcre_shapley,
-// cf_pcre_epistasis; included by cf_api.hip behind cf_ablate.h, whose stash kernel and buffers it shares).
+// cf_coalition.h -- in-silico pCRE deletion, pCRE coalition forwards, exact Shapley values and pair epistasis (cf_pcre_ablation,
+// cf_pcre_coalitions, cf_pcre_shapley, cf_pcre_epistasis; included by cf_api.hip behind cf_rows.h).
 //
+// Deleting pCRE slot j of gene b is exactly the reference forward on the same tensors with interaction_masks[b, 0, j+1, :] and
+// interaction_masks[b, 0, :, j+1] set (data.py: a dummy slot is a masked row and column): the Embedding +
+// Pairwise output of every slot depends on the promoter and that slot alone, and the Regulation stack has no positional encoding.
 // A coalition is a 32-bit word m, bit j set = pCRE slot j kept.  Row (b, m) is the inference forward of gene b with its interaction
-// mask (every resolution) OR-ed with row j+1 and column j+1 for every clear bit j < S: the generalisation of cf_ablate.h's variants
-// (m = 2^S - 1: variant 0; one clear bit j: variant 1 + j; m = 0: variant S + 1).  The trunk runs once, its output is stashed
-// (k_pcre_stash), and the Regulation stack + head run on the B * n_coal rows, gene-major (row = b * n_coal + c), in chunks of at most
-// max_batch rows.
+// mask (every resolution) OR-ed with row j+1 and column j+1 for every clear bit j < S.  The trunk runs once, its output (the
+// Regulation input Rx[r][0], [B, T, d_emb] per resolution) is stashed, and the Regulation stack + head run on the B * n_coal rows,
+// gene-major (row = b * n_coal + c), in chunks of at most max_batch rows.  cf_pcre_ablation is the fixed table of i_max + 2 words
+//   v = 0            2^S - 1               the given mask (baseline)
+//   v = 1 + j        2^S - 1 without bit j (slot j deleted)
+//   v = i_max + 1    0                     rows and columns 1..i_max (promoter only)
+// Kernels:
+//   k_pcre_stash        Rx[r][0] -> stash[r], float4 per thread, blockIdx.y = resolution.  Bytes only.
 //   k_coalition_expand  per (chunk row, resolution): the stashed rows of its gene -> Rx[r][0], the OR-ed mask from the row's word (read
 //                       from a device table) -> the chunk's mask[r]; resolution 0 also copies the gene's interaction_freq.  Bytes
 //                       and bit tests only.
@@ -24,6 +31,20 @@ namespace cf {
 
 constexpr int kCoalMaxS = 16;                // cf_create accepts i_max in 1..16
 constexpr int kShapThreads = 256;
+constexpr int kAblThreads = kRowThreads;
+
+struct AblateStashArgs {
+    const float4* src[kMaxRes];              // Rx[r][0]           [B * T * D / 4]
+    float4* dst[kMaxRes];                    // stash of resolution r
+    long long n4;                            // B * T * D / 4
+};
+
+__global__ __launch_bounds__(kAblThreads) void k_pcre_stash(AblateStashArgs a) {
+    const int r = blockIdx.y;
+    const float4* __restrict__ src = a.src[r];
+    float4* __restrict__ dst = a.dst[r];
+    for (long long i = (long long)blockIdx.x * kAblThreads + threadIdx.x; i < a.n4; i += (long long)gridDim.x * kAblThreads) dst[i] = src[i];
+}
 
 struct CoalExpandArgs {
     const float4* stash[kMaxRes];            // [B, T * D / 4] per resolution
@@ -44,17 +65,14 @@ __global__ __launch_bounds__(kAblThreads) void k_coalition_expand(CoalExpandArgs
     const int b = (int)(g / a.n_coal), T = a.T, TT = T * T;
     // bit 0 of `gone` is the promoter token (never deleted), bit j + 1 pCRE slot j
     const unsigned gone = ~(a.keep[g - (long long)b * a.n_coal] << 1) & ((1u << T) - 2u);
-    const float4* __restrict__ src = a.stash[r] + (size_t)b * a.row4;
-    float4* __restrict__ dst = a.x0[r] + (size_t)i * a.row4;
-    for (int k = tid; k < a.row4; k += kAblThreads) dst[k] = src[k];
+    rows_copy_x0(a.stash[r], a.x0[r], b, i, a.row4);
     const uint8_t* __restrict__ min = a.mask_in[r] + (size_t)b * TT;
     uint8_t* __restrict__ mout = a.mask_out[r] + (size_t)i * TT;
     for (int k = tid; k < TT; k += kAblThreads) {
         const int row = k / T, col = k - row * T;
         mout[k] = (gone >> row | gone >> col) & 1u ? (uint8_t)1 : min[k];
     }
-    if (r == 0)
-        for (int k = tid; k < TT; k += kAblThreads) a.freq_out[(size_t)i * TT + k] = a.freq_in[(size_t)b * TT + k];
+    if (r == 0) rows_copy_tt(a.freq_in, a.freq_out, b, i, TT);
 }
 
 struct ShapleyArgs {

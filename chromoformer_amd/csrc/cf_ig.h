@@ -36,7 +36,7 @@
 
 namespace cf {
 
-constexpr int kIgxThreads = 256;
+constexpr int kIgxThreads = kRowThreads;
 constexpr int kIgSegs = 2 * kMaxRes + 1;      // promoter_feats[r], pcre_feats[r], interaction_freq
 constexpr int kIgLinear = 0, kIgSignal = 1;   // path of a feature segment: xb + a (x - xb) | log1p(a expm1(x)) from the zero signal
 
@@ -51,22 +51,13 @@ struct IgSeg {
 
 struct IgExpandArgs {
     IgSeg seg[kIgSegs];
-    const uint8_t* pm_in[kMaxRes];     // the caller's pad-mask centre rows (promoter: row = gene; pCRE: row = gene * S + slot)
-    const uint8_t* cm_in[kMaxRes];
-    long long pm_stride[kMaxRes], cm_stride[kMaxRes];
-    uint8_t* pm_out[kMaxRes];          // the chunk's compact rows, stride L
-    uint8_t* cm_out[kMaxRes];
-    int pm_rows[kMaxRes];              // 1; L where the all-rows Embedding reads the caller's full [B, L, L] promoter mask: pm_in is then
-                                       // row 0 of gene 0 and the chunk's copy keeps all L rows per chunk row (stride L * L)
-    const uint8_t* im_in[kMaxRes];     // interaction masks [B, T, T]
-    uint8_t* im_out[kMaxRes];
+    RowCopyArgs rows;                  // the masks of the chunk's rows (cf_rows.h)
     const float4* stash[kMaxRes];      // frequency-only mode: the trunk output of the B genes, [B, T * D / 4]
     float4* x0[kMaxRes];               // ... copied into Rx[r][0], [n, T * D / 4]
     const float* alpha;                // device [n_steps]
     const float* weight;               // device [n_steps]
     float* dlogits;                    // [n, n_out]
-    int L[kMaxRes];
-    int g0, V, S, TT, n_out, target, nres, bcast, freq_only, row4;
+    int g0, V, n_out, target, nres, bcast, freq_only, row4;
 };
 
 // the signal path's interior value of one element
@@ -115,21 +106,13 @@ __device__ __forceinline__ void ig_expand(const IgExpandArgs a) {
     const float alpha = v >= 2 ? a.alpha[v - 2] : 0.f;
     const bool bc = a.bcast != 0;
     if (a.freq_only) {
-        const float4* __restrict__ src = a.stash[r] + (size_t)b * a.row4;
-        float4* __restrict__ dst = a.x0[r] + (size_t)i * a.row4;
-        for (int k = tid; k < a.row4; k += kIgxThreads) dst[k] = src[k];
+        rows_copy_x0(a.stash[r], a.x0[r], b, i, a.row4);
     } else {
-        const int L = a.L[r], S = a.S;
         ig_row<PATH>(a.seg[r], b, i, v, alpha, bc);
         ig_row<PATH>(a.seg[kMaxRes + r], b, i, v, alpha, bc);
-        const int PL = a.pm_rows[r] * L;
-        for (int k = tid; k < PL; k += kIgxThreads) a.pm_out[r][(size_t)i * PL + k] = a.pm_in[r][(size_t)b * a.pm_stride[r] + k];
-        for (int k = tid; k < S * L; k += kIgxThreads) {
-            const int s = k / L, j = k - s * L;
-            a.cm_out[r][((size_t)i * S + s) * L + j] = a.cm_in[r][((size_t)b * S + s) * a.cm_stride[r] + j];
-        }
+        rows_pad_masks(a.rows, r, b, i);
     }
-    for (int k = tid; k < a.TT; k += kIgxThreads) a.im_out[r][(size_t)i * a.TT + k] = a.im_in[r][(size_t)b * a.TT + k];
+    rows_interaction_mask(a.rows, r, b, i);
     if (r == 0) {
         ig_row<kIgLinear>(a.seg[2 * kMaxRes], b, i, v, alpha, bc);
         for (int k = tid; k < a.n_out; k += kIgxThreads) a.dlogits[(size_t)i * a.n_out + k] = v >= 2 && k == a.target ? a.weight[v - 2] : 0.f;

@@ -29,23 +29,15 @@ struct ScanExpandArgs {
     float* pf_out[kMaxRes];            // the chunk's copies, [max_batch, L, F] / [max_batch, S, L, F]
     float* cf_out[kMaxRes];
     float* feats_out[kMaxRes];         // [B, V, L, F]: the scanned region as row (b, v) reads it; nullptr: not wanted
-    const uint8_t* pm_in[kMaxRes];     // as IgExpandArgs: the rows copied into the chunk
-    const uint8_t* cm_in[kMaxRes];
-    long long pm_stride[kMaxRes], cm_stride[kMaxRes];
-    uint8_t* pm_out[kMaxRes];
-    uint8_t* cm_out[kMaxRes];
-    int pm_rows[kMaxRes];
+    RowCopyArgs rows;                  // the masks of the chunk's rows (cf_rows.h)
     const uint8_t* rm_in[kMaxRes];     // the scanned region's centre pad-mask row of gene b: rm_in[r] + b * rm_stride[r]
     long long rm_stride[kMaxRes];
-    const uint8_t* im_in[kMaxRes];     // interaction masks [B, T, T]
-    uint8_t* im_out[kMaxRes];
     const float* freq_in;              // [B, T, T]
     float* freq_out;
     const unsigned* sets;              // device [n_sets]: bit f set: mark f is scaled
     const uint8_t* flip;               // device [B] or nullptr
     float scale;
-    int L[kMaxRes];
-    int g0, V, S, TT, F, W, width, rc, region;
+    int g0, V, F, W, width, rc, region;
 };
 
 // first unmasked row and one past the last of a mask row of L bytes (lo = L, hi = 0: all masked); every thread gets the result
@@ -102,9 +94,9 @@ __device__ __forceinline__ void scan_copy(const float* __restrict__ src, float* 
 
 __global__ __launch_bounds__(kIgxThreads) void k_scan_expand(ScanExpandArgs a) {
     __shared__ int red[2 * (kIgxThreads / 64)];
-    const int i = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
+    const int i = blockIdx.x, r = blockIdx.y;
     const int gv = a.g0 + i, b = gv / a.V, v = gv - b * a.V;
-    const int L = a.L[r], S = a.S, F = a.F, LF = L * F;
+    const int L = a.rows.L[r], S = a.rows.S, F = a.F, LF = L * F;
     // the covered rows [p0, p1) of the scanned region at this resolution (block-uniform)
     int p0 = 0, p1 = 0;
     unsigned bits = 0;
@@ -112,7 +104,7 @@ __global__ __launch_bounds__(kIgxThreads) void k_scan_expand(ScanExpandArgs a) {
         const int k = (v - 1) / a.W, g = (v - 1) - k * a.W;
         bits = a.sets[k];
         int lo, hi;
-        scan_extent(a.rm_in[a.rc] + (size_t)b * a.rm_stride[a.rc], a.L[a.rc], red, lo, hi);
+        scan_extent(a.rm_in[a.rc] + (size_t)b * a.rm_stride[a.rc], a.rows.L[a.rc], red, lo, hi);
         const int nc = hi > lo ? hi - lo : 0;
         if (bits && g < nc) {
             if (r != a.rc) scan_extent(a.rm_in[r] + (size_t)b * a.rm_stride[r], L, red, lo, hi);
@@ -132,15 +124,9 @@ __global__ __launch_bounds__(kIgxThreads) void k_scan_expand(ScanExpandArgs a) {
               prom ? fo : nullptr);
     scan_copy(a.cf_in[r] + (size_t)b * S * LF, a.cf_out[r] + (size_t)i * S * LF, S * LF, off, LF, prom ? 0 : off + p0 * F,
               prom ? 0 : off + p1 * F, bits, F, a.scale, prom ? nullptr : fo);
-    const int PL = a.pm_rows[r] * L;
-    for (int k = tid; k < PL; k += kIgxThreads) a.pm_out[r][(size_t)i * PL + k] = a.pm_in[r][(size_t)b * a.pm_stride[r] + k];
-    for (int k = tid; k < S * L; k += kIgxThreads) {
-        const int s = k / L, j = k - s * L;
-        a.cm_out[r][((size_t)i * S + s) * L + j] = a.cm_in[r][((size_t)b * S + s) * a.cm_stride[r] + j];
-    }
-    for (int k = tid; k < a.TT; k += kIgxThreads) a.im_out[r][(size_t)i * a.TT + k] = a.im_in[r][(size_t)b * a.TT + k];
-    if (r == 0)
-        for (int k = tid; k < a.TT; k += kIgxThreads) a.freq_out[(size_t)i * a.TT + k] = a.freq_in[(size_t)b * a.TT + k];
+    rows_pad_masks(a.rows, r, b, i);
+    rows_interaction_mask(a.rows, r, b, i);
+    if (r == 0) rows_copy_tt(a.freq_in, a.freq_out, b, i, a.rows.TT);
 }
 
 }  // namespace cf

@@ -2,7 +2,7 @@
 // cf_reduce_opt_x0; included by cf_api.hip).
 //
 // With the Embedding + Pairwise weights fixed, the Regulation input Rx[r][0] ([T, d_emb] per gene and resolution) depends on the gene
-// alone (cf_ablate.h): it is computed once per gene, kept in a device-resident cache store beside the gene's interaction mask,
+// alone (cf_coalition.h): it is computed once per gene, kept in a device-resident cache store beside the gene's interaction mask,
 // interaction frequencies and label, and a training step starts at the Regulation stack.  The kernels here move bytes only (no
 // arithmetic on them, no atomics):
 //   k_x0_copy            [B, T, d_emb] rows between Rx[r][0] and a caller's buffers, float4 per thread, blockIdx.y = resolution;

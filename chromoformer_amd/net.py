@@ -404,6 +404,28 @@ class ChromoformerBase(nn.Module):
 
     MAP_KEYS = ("embed", "pairwise_interaction", "regulation", "regulatory_embedding")
 
+    def _attrib_call(self, who, args):
+        """What the attribution methods share -> (batch struct, keep-alive, book).  `args`: the six tensors of forward(), or a packed
+        batch (an engine.Slot, a pack_batch result or a batch struct) with None after it.  book() -> stream, called directly in front
+        of the library call, once the arguments are accepted: it brings the tiled weights up to date on the stream and books the call
+        as `who` (a pending backward of an earlier forward then refuses to run)."""
+        if args[1] is None:
+            p = args[0]
+            bs, keep = (p if isinstance(p, _lib.cf_batch) else p.struct if hasattr(p, "struct") else p[0]), p
+        else:
+            bs, keep = self._pack(*args)
+        if self._handle is None:
+            raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
+
+        def book():
+            st = torch.cuda.current_stream(self._device).cuda_stream
+            self._sync_tiled(st)
+            self._maps_gen += 1
+            self._maps_by = who
+            return st
+
+        return bs, keep, book
+
     @torch.no_grad()
     def attention_maps(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
                        interaction_freq=None, which=MAP_KEYS):
@@ -419,12 +441,7 @@ class ChromoformerBase(nn.Module):
         Masked keys are 0, fully masked rows (dummy pCRE slots) uniform, as with the reference.  `which` selects the outputs (the others
         are not copied).  The first argument may also be a packed batch (an engine.Slot or a pack_batch result), with nothing after it.
         The pass overwrites the activations a grad-enabled model(...) keeps for its backward: such a pending backward() raises."""
-        if promoter_pad_masks is None:
-            bs = promoter_feats.struct if hasattr(promoter_feats, "struct") else promoter_feats[0]
-        else:
-            bs, _keep = self._pack(promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq)      # (alive until the call)
-        if self._handle is None:
-            raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
+        bs, _keep, book = self._attrib_call("attention_maps", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
         which = (which,) if isinstance(which, str) else tuple(which)
         bad = [k for k in which if k not in self.MAP_KEYS]
         if bad:
@@ -445,10 +462,7 @@ class ChromoformerBase(nn.Module):
             maps["regulatory_embedding"] = t = torch.empty(B, len(self.binsizes) * self.d_emb, device=dev)
             want.embedding = t.data_ptr()
         logits = torch.empty(B, self.n_out, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        self._sync_tiled(st)
-        self._maps_gen += 1
-        self._maps_by = "attention_maps"
+        st = book()
         _lib.check(_lib.lib().cf_attention_maps(self._handle, C.byref(bs), logits.data_ptr(), C.byref(want), st), "cf_attention_maps")
         return logits, maps
 
@@ -465,34 +479,11 @@ class ChromoformerBase(nn.Module):
         The Embedding + Pairwise stage runs once, the Regulation stack and the head on the B * (i_max + 2) gene-variants.  The first
         argument may also be a packed batch (an engine.Slot or a pack_batch result), with nothing after it.  The pass overwrites the
         activations a grad-enabled model(...) keeps for its backward: such a pending backward() raises."""
-        if promoter_pad_masks is None:
-            bs = promoter_feats.struct if hasattr(promoter_feats, "struct") else promoter_feats[0]
-        else:
-            bs, _keep = self._pack(promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq)      # (alive until the call)
-        if self._handle is None:
-            raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
-        dev = self._device
-        logits = torch.empty(bs.B, self.i_max + 2, self.n_out, device=dev)      # (written in full by the library)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        self._sync_tiled(st)
-        self._maps_gen += 1
-        self._maps_by = "pcre_ablation"
+        bs, _keep, book = self._attrib_call("pcre_ablation", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        logits = torch.empty(bs.B, self.i_max + 2, self.n_out, device=self._device)      # (written in full by the library)
+        st = book()
         _lib.check(_lib.lib().cf_pcre_ablation(self._handle, C.byref(bs), logits.data_ptr(), st), "cf_pcre_ablation")
         return logits
-
-    def _coalition_call(self, who, args):
-        """What the coalition methods share -> (batch struct, keep-alive, stream): the packed batch, the pending-backward bookkeeping."""
-        if args[1] is None:
-            bs, keep = (args[0].struct if hasattr(args[0], "struct") else args[0][0]), args[0]
-        else:
-            bs, keep = self._pack(*args)
-        if self._handle is None:
-            raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
-        st = torch.cuda.current_stream(self._device).cuda_stream
-        self._sync_tiled(st)
-        self._maps_gen += 1
-        self._maps_by = who
-        return bs, keep, st
 
     @torch.no_grad()
     def pcre_coalitions(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
@@ -509,9 +500,9 @@ class ChromoformerBase(nn.Module):
         if keep is None:
             raise ValueError("pcre_coalitions: keep is required: the coalition words (bit j set: pCRE slot j kept)")
         words = coalition_words(keep, self.i_max, "pcre_coalitions")
-        bs, _keep, st = self._coalition_call("pcre_coalitions", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks,
-                                                                 interaction_masks, interaction_freq))
+        bs, _keep, book = self._attrib_call("pcre_coalitions", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
         logits = torch.empty(bs.B, len(words), self.n_out, device=self._device)      # (written in full by the library)
+        st = book()
         _lib.check(_lib.lib().cf_pcre_coalitions(self._handle, C.byref(bs), words.ctypes.data, len(words), logits.data_ptr(), st),
                    "cf_pcre_coalitions")
         return logits
@@ -531,11 +522,11 @@ class ChromoformerBase(nn.Module):
         All 2^i_max coalitions run from one trunk pass (pcre_coalitions); the values are in logit space, where efficiency holds.
         The first argument may also be a packed batch (an engine.Slot or a pack_batch result), with nothing after it.  The pass
         overwrites the activations a grad-enabled model(...) keeps for its backward: such a pending backward() raises."""
-        bs, _keep, st = self._coalition_call("pcre_shapley", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks,
-                                                              interaction_masks, interaction_freq))
+        bs, _keep, book = self._attrib_call("pcre_shapley", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
         n = 1 << self.i_max
         rows = torch.empty(bs.B, n, self.n_out, device=self._device)      # (both written in full by the library)
         phi = torch.empty(bs.B, self.i_max, self.n_out, device=self._device)
+        st = book()
         _lib.check(_lib.lib().cf_pcre_shapley(self._handle, C.byref(bs), phi.data_ptr(), rows.data_ptr(), st), "cf_pcre_shapley")
         info = {"logits": rows[:, n - 1].clone(), "promoter_only": rows[:, 0].clone()}
         info["delta"] = phi.sum(1) - (info["logits"] - info["promoter_only"])
@@ -557,11 +548,11 @@ class ChromoformerBase(nn.Module):
         The 1 + i_max + i_max (i_max - 1) / 2 rows (attribution.coalition_table("pairs", i_max)) run from one trunk pass.  The first
         argument may also be a packed batch (an engine.Slot or a pack_batch result), with nothing after it.  The pass overwrites the
         activations a grad-enabled model(...) keeps for its backward: such a pending backward() raises."""
-        bs, _keep, st = self._coalition_call("pcre_epistasis", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks,
-                                                                interaction_masks, interaction_freq))
+        bs, _keep, book = self._attrib_call("pcre_epistasis", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
         S = self.i_max
         rows = torch.empty(bs.B, 1 + S + S * (S - 1) // 2, self.n_out, device=self._device)      # (both written in full by the library)
         eps = torch.empty(bs.B, S, S, self.n_out, device=self._device)
+        st = book()
         _lib.check(_lib.lib().cf_pcre_epistasis(self._handle, C.byref(bs), eps.data_ptr(), rows.data_ptr(), st), "cf_pcre_epistasis")
         return eps, {"logits": rows[:, 0].clone(), "single": rows[:, 1:1 + S].clone()}
 
@@ -602,15 +593,11 @@ class ChromoformerBase(nn.Module):
                 raise ValueError("integrated_gradients: path='signal' starts at the zero signal; a baseline for %s is not accepted" % given)
             if not set(named) & {"promoter_feats", "pcre_feats"}:
                 raise ValueError("integrated_gradients: path='signal' needs promoter_feats or pcre_feats in inputs, got %s" % (named,))
+        bs, _keep, book = self._attrib_call("integrated_gradients", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
         shapes = None
-        if promoter_pad_masks is None:
-            bs = promoter_feats.struct if hasattr(promoter_feats, "struct") else promoter_feats[0]
-        else:
-            bs, _keep = self._pack(promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq)      # (alive until the call)
+        if promoter_pad_masks is not None:      # (given tensors: the attributions come back in the callers' shapes)
             shapes = {"promoter_feats": {b: promoter_feats[b].shape for b in self.binsizes},
                       "pcre_feats": {b: pcre_feats[b].shape for b in self.binsizes}, "interaction_freq": interaction_freq.shape}
-        if self._handle is None:
-            raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
         inputs = (inputs,) if isinstance(inputs, str) else tuple(inputs)
         bad = [k for k in inputs if k not in INPUTS]
         if bad or not inputs:
@@ -674,10 +661,7 @@ class ChromoformerBase(nn.Module):
         lx = torch.empty(B, self.n_out, device=dev)
         lb = torch.empty(B, self.n_out, device=dev)
         delta = torch.empty(B, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        self._sync_tiled(st)
-        self._maps_gen += 1
-        self._maps_by = "integrated_gradients"
+        st = book()
         info = {"logits": lx, "baseline_logits": lb, "delta": delta}
         if signal:
             co = _lib.cf_input_grads()
@@ -718,12 +702,7 @@ class ChromoformerBase(nn.Module):
         read.  Features must stay below ~80 (expm1 in fp32).  The first argument may also be a packed batch (an engine.Slot or a
         pack_batch result), with nothing after it.  The pass overwrites the activations a grad-enabled model(...) keeps for its
         backward: such a pending backward() raises."""
-        if promoter_pad_masks is None:
-            bs = promoter_feats.struct if hasattr(promoter_feats, "struct") else promoter_feats[0]
-        else:
-            bs, _keep = self._pack(promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq)      # (alive until the call)
-        if self._handle is None:
-            raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
+        bs, _keep, book = self._attrib_call("perturbation_scan", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
         F, dev, B = self.n_feats, self._device, bs.B
         if mark_sets is None:
             mark_sets = [(f,) for f in range(F)] + [tuple(range(F))]
@@ -749,10 +728,7 @@ class ChromoformerBase(nn.Module):
                 t = feats[b] = torch.empty(B, V, self.n_bins[r], F, device=dev)      # (written in full by the library)
                 opts.feats_out[r] = t.data_ptr()
         logits = torch.empty(B, V, self.n_out, device=dev)      # (written in full by the library)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        self._sync_tiled(st)
-        self._maps_gen += 1
-        self._maps_by = "perturbation_scan"
+        st = book()
         _lib.check(_lib.lib().cf_perturbation_scan(self._handle, C.byref(bs), C.byref(opts), logits.data_ptr(), st), "cf_perturbation_scan")
         return (logits, feats) if return_feats else logits
 
@@ -785,23 +761,15 @@ class ChromoformerBase(nn.Module):
         fixed Embedding + Pairwise weights it depends on the gene alone -- what engine.TrunkCache keeps for Trainer(freeze_trunk=True).
         The first argument may also be a packed batch (an engine.Slot or a pack_batch result), with nothing after it.  The pass
         overwrites the activations a grad-enabled model(...) keeps for its backward: such a pending backward() raises."""
-        if promoter_pad_masks is None:
-            bs = promoter_feats.struct if hasattr(promoter_feats, "struct") else promoter_feats[0]
-        else:
-            bs, _keep = self._pack(promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq)      # (alive until the call)
-        if self._handle is None:
-            raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
-        return dict(zip(self.binsizes, self._trunk_outputs(bs)))
+        return dict(zip(self.binsizes, self._trunk_outputs((promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))))
 
-    def _trunk_outputs(self, bs, outs=None):
-        dev = self._device
+    def _trunk_outputs(self, batch, outs=None):
+        """batch: the six arguments of trunk_outputs, or a batch struct."""
+        bs, _keep, book = self._attrib_call("trunk_outputs", (batch, None) if isinstance(batch, _lib.cf_batch) else batch)
         if outs is None:
-            outs = [torch.empty(bs.B, self.i_max + 1, self.d_emb, device=dev) for _ in self.binsizes]      # (written in full by the library)
+            outs = [torch.empty(bs.B, self.i_max + 1, self.d_emb, device=self._device) for _ in self.binsizes]      # (written in full by the library)
         ptrs = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
-        st = torch.cuda.current_stream(dev).cuda_stream
-        self._sync_tiled(st)
-        self._maps_gen += 1
-        self._maps_by = "trunk_outputs"
+        st = book()
         _lib.check(_lib.lib().cf_trunk_outputs(self._handle, C.byref(bs), ptrs, st), "cf_trunk_outputs")
         return outs
 

@@ -202,13 +202,15 @@ int cf_attention_maps(cf_handle* h, const cf_batch* batch, float* logits, const 
  *   v = 1 + j       the given mask OR row j+1 OR column j+1 (pCRE slot j deleted; a slot that is already a dummy gives the baseline);
  *   v = i_max + 1   the given mask OR rows and columns 1..i_max (promoter only).
  * Features, pad masks and interaction_freq are gene b's.  Launches: the trunk part of cf_forward(save = 0) (prologue, Embedding +
- * Pairwise) once, k_pcre_stash once (the Regulation input), then per chunk of at most max_batch gene-variants one k_pcre_expand and
- * the Regulation + head launches of cf_forward(save = 0) on that chunk:
+ * Pairwise) once, k_pcre_stash once (the Regulation input), then per chunk of at most max_batch gene-variants one k_coalition_expand
+ * (the variants are the coalition words 2^i_max - 1, that word without bit j, 0 of cf_pcre_coalitions below, in a device table written
+ * when the buffers are allocated: no copy per call) and the Regulation + head launches of cf_forward(save = 0) on that chunk:
  *   cf_launch_counts fwd = n_trunk + 1 + ceil(B * V / max_batch) * (1 + n_reg_head),
  * where n_trunk + n_reg_head is what cf_forward(save = 0) issues (n_reg_head: 2 on the fused Regulation shapes -- k_reg_fwd, the
  * head --, 3 * reg.n_layers + 1 layer by layer).  Overwrites the activations a cf_forward(save >= 1) kept: no cf_backward* may
  * follow without a new saving forward.  Deterministic (no atomics).  The first call allocates the stash and chunk buffers (freed by
- * cf_destroy; ~1 MB at max_batch 64); later calls allocate nothing.  A null handle / batch / logits or B > max_batch fails by name,
+ * cf_destroy; ~1 MB at max_batch 64) and writes the table with a blocking copy: it synchronises, whichever of cf_pcre_ablation and
+ * the coalition entry points comes first; later calls allocate nothing.  A null handle / batch / logits or B > max_batch fails by name,
  * before anything is launched. */
 int cf_pcre_ablation(cf_handle* h, const cf_batch* batch, float* logits, void* stream);
 /* pCRE coalition forwards, exact Shapley values and pair epistasis (interpretation).  S = i_max.  A coalition is a 32-bit word m: bit

@@ -231,6 +231,32 @@ def test_no_side_effects_on_training_and_a_stale_backward_is_refused():
     assert float(model._gflat.abs().sum()) > 0
 
 
+def test_a_call_refused_for_its_arguments_leaves_a_pending_backward_usable():
+    """A method that raises on its own arguments has run nothing: the activations of an earlier grad-enabled forward are intact and
+    its backward() still runs, with the gradients of an undisturbed forward + backward."""
+    batch = orc.synthetic_batch(4, seed=43, regime="realistic")
+    model = _model(B=4)
+    with torch.enable_grad():
+        model(*_args(batch))[:, 1].sum().backward()
+    ref = model._gflat.clone()
+    model._gflat.zero_()
+    with torch.enable_grad():
+        out = model(*_args(batch))
+    with pytest.raises(ValueError, match="attention_maps"):
+        model.attention_maps(*_args(batch), which="no_such_map")
+    with pytest.raises(ValueError, match="integrated_gradients"):
+        model.integrated_gradients(*_args(batch), inputs=("no_such_input",))
+    with pytest.raises(ValueError, match="integrated_gradients"):
+        model.integrated_gradients(*_args(batch), baselines={"interaction_freq": torch.zeros(3, 9, 9)})      # (leading dimension not 1 or B)
+    with pytest.raises(ValueError, match="perturbation_scan"):
+        model.perturbation_scan(*_args(batch), mark_sets=[(99,)])
+    with pytest.raises(ValueError, match="pcre_coalitions"):
+        model.pcre_coalitions(*_args(batch), keep=[1 << model.i_max])
+    with torch.enable_grad():
+        out[:, 1].sum().backward()
+    assert torch.equal(model._gflat, ref)
+
+
 def test_predict_writes_maps_and_embeddings(tmp_path):
     import pandas as pd
 

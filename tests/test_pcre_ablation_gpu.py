@@ -89,6 +89,33 @@ def test_bsz64_realistic_against_the_oracle_and_chunking_invariant():
     assert one.shape == (1, 10, 2) and torch.equal(one[0], runs[64][5])      # B = 1
 
 
+def test_variants_straddling_chunks_equal_the_forward_on_hand_set_masks():
+    """The smallest shape at which a gene's variants straddle chunks: i_max = 2 (V = 4), B = 2, max_batch = 3 -- chunks of 3, 3 and
+    2 rows, gene 0 ending and gene 1 beginning inside the second.  Every column is model(...) on the batch with the variant's rows
+    and columns of interaction_masks set here, by hand, bit for bit; and one chunk (max_batch = 8) gives the same bits."""
+    cfg = orc._cfg(dict(i_max=2))
+    batch = orc.synthetic_batch(2, cfg=cfg, seed=13, regime="realistic")
+    P = orc.init_params(cfg, 3, False)
+    runs = {}
+    for cap in (3, 8):
+        model = _model(cfg, B=cap, seed=3)
+        model.load_state_dict(P)
+        runs[cap] = model.pcre_ablation(*_args(batch))
+        assert runs[cap].shape == (2, 4, 2)
+        gone = {0: [], 1: [1], 2: [2], 3: [1, 2]}      # variant -> the interaction-mask rows and columns it sets
+        with torch.no_grad():
+            for v, tokens in gone.items():
+                masks = {r: m.clone() for r, m in batch["interaction_masks"].items()}
+                for m in masks.values():
+                    for t in tokens:
+                        m[:, 0, t, :] = True
+                        m[:, 0, :, t] = True
+                ref = model(*_args(dict(batch, interaction_masks=masks)))
+                assert torch.equal(runs[cap][:, v], ref), (cap, v)
+    assert not torch.equal(runs[3][:, 0], runs[3][:, 3])      # (the promoter alone is another prediction: the masks are read)
+    assert torch.equal(runs[3], runs[8])
+
+
 REG_4x128 = dict(n_layers=6, n_heads=4, d_model=128, d_ff=256)
 SHAPES = {
     "reg_4x128": (dict(regulation=REG_4x128), False),
