@@ -1,5 +1,5 @@
 // cf_api_attrib.h -- host side of the attribution entry points (input gradients, attention maps, pCRE deletion, pCRE coalitions, integrated
-// gradients, perturbation scan).  Part of cf_api.hip's single translation unit: included there behind the backward pass, not on its own.
+// gradients, perturbation scan).  Part of cf_api.hip's single translation unit: included there behind cf_api_bwd.h, not on its own.
 #pragma once
 
 // k_input_grad's dynamic LDS size; the first call sets the kernel's attribute.  0: that failed (`who`: the entry point, for the error text).
@@ -23,7 +23,6 @@ static int launch_input_grad(cf_handle* h, const cf_batch& bt, int B, float* con
     InGradArgs a;
     memset(&a, 0, sizeof a);
     for (int r = 0; r < nres; ++r) {
-        const int bs = c.binsizes[r];
         a.feats_p[r] = bt.promoter_feats[r];
         a.feats_c[r] = bt.pcre_feats[r];
         a.mask_p[r] = static_cast<const uint8_t*>(bt.promoter_mask_row[r]);
@@ -31,8 +30,8 @@ static int launch_input_grad(cf_handle* h, const cf_batch& bt, int B, float* con
         a.mstride_p[r] = bt.promoter_mask_stride[r];
         a.mstride_c[r] = bt.pcre_mask_stride[r];
         a.pet[r] = h->pet[r];
-        a.w_p[r] = h->P_(fmt("embed.%d.lin_proj.weight", bs));
-        a.w_c[r] = h->P_(fmt("pairwise_interaction.%d.lin_proj_pcre.weight", bs));
+        a.w_p[r] = h->refs.lin_proj[r];
+        a.w_c[r] = h->refs.P[r][0].wlp;
         a.edx0[r] = h->edx0[r];
         a.ep[r] = h->E[r].p;
         a.eqt[r] = h->E[r].qt;

@@ -1,5 +1,6 @@
-// cf_api_ops.h -- the stand-alone operators, the binning entry points and the dense transformer layer: nothing here touches a
-// cf_handle.  Part of cf_api.hip's single translation unit: included there, not on its own.
+// cf_api_ops.h -- the stand-alone operators, the binning entry points and the dense transformer layer (nothing of these touches a
+// cf_handle), and behind them the all-rows Embedding path of the model, which runs on the dense layer.
+// Part of cf_api.hip's single translation unit: included there behind cf_api_launch.h, not on its own.
 #pragma once
 
 // ------------------------------------------------------------------------------------
@@ -572,6 +573,116 @@ extern "C" int cf_op_dense_layer_bwd(const cf_dense_layer* w, const float* x_q, 
         LAUNCH_CHECK("k_colsum<dense layer bias, stage 1>");
         hipLaunchKernelGGL(k_colsum, dim3(n2), dim3(256), 0, st, (const CsTile*)cs_d, 1);
         LAUNCH_CHECK("k_colsum<dense layer bias>");
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// Embedding over all promoter bins (embed.n_layers > 1, cf_embed_full): net.py:9-59 without the centre-row shortcut
+// ------------------------------------------------------------------------------------
+static int embed_dense_alloc(cf_handle* h) {
+    cf_handle::EmbedDense& e = h->ed;
+    if (e.ready) return 0;
+    const cf_config& c = h->cfg;
+    const int B = c.max_batch, E = c.embed_layers;
+    auto get = [&](size_t floats) -> float* {
+        void* q = nullptr;
+        if (hipMalloc(&q, floats * sizeof(float)) != hipSuccess) return nullptr;
+        (void)hipMemset(q, 0, floats * sizeof(float));
+        h->ed.owned.push_back(q);
+        return (float*)q;
+    };
+    for (int r = 0; r < c.n_res; ++r) {
+        const int L = c.n_bins[r];
+        const size_t rows = (size_t)B * L;
+        for (int l = 0; l <= E; ++l)
+            if (!(e.x[r][l] = get(rows * kD))) return fail("embed_dense_alloc: out of memory");
+        for (int l = 0; l < E; ++l)
+            if (!(e.ws[r][l] = get((size_t)dense_ws(B, L, L, c.embed_dff, true).total))) return fail("embed_dense_alloc: out of memory");
+        for (int k = 0; k < 3; ++k)
+            if (!(e.dy[r][k] = get(rows * kD))) return fail("embed_dense_alloc: out of memory");
+        if (!(e.lp_partial[r] = get(((rows + kEmbWgRows - 1) / kEmbWgRows) * kD * 8))) return fail("embed_dense_alloc: out of memory");
+        if (!(e.valid[r] = reinterpret_cast<uint8_t*>(get((rows + 3) / 4 + 4)))) return fail("embed_dense_alloc: out of memory");
+    }
+    if (!(e.tables = get((size_t)1 << 20))) return fail("embed_dense_alloc: out of memory");
+    e.B = B;
+    e.ready = true;
+    return 0;
+}
+// Pad mask of the promoters as the dense layer wants it: the full [B, L, L] byte mask when the caller passed the reference's
+// tensor (row stride L * L: the centre-row pointer is L/2 rows into it), else validity bytes from the compact centre row
+// -- exact for the dataset's structured masks  not(valid x valid)  with a real centre bin (data.py:156-161).
+static void embed_dense_mask(cf_handle* h, const cf_batch* bt, int r, const uint8_t** full, const uint8_t** valid, hipStream_t st) {
+    const int L = h->cfg.n_bins[r];
+    if (bt->promoter_mask_stride[r] == (long long)L * L) {
+        *full = bt->promoter_mask_row[r] - (size_t)(L / 2) * L;
+        *valid = nullptr;
+    } else {
+        hipLaunchKernelGGL(k_mask_to_valid, dim3(bt->B), dim3(256), 0, st, bt->promoter_mask_row[r], bt->promoter_mask_stride[r], L, h->ed.valid[r]);
+        *full = nullptr;
+        *valid = h->ed.valid[r];
+    }
+}
+static int embed_dense_forward(cf_handle* h, const cf_batch* bt, bool train, hipStream_t st) {
+    if (embed_dense_alloc(h)) return -1;
+    const cf_config& c = h->cfg;
+    const int B = bt->B, E = c.embed_layers, T = c.i_max + 1;
+    for (int r = 0; r < c.n_res; ++r) {
+        const int L = c.n_bins[r];
+        EmbTokArgs ta{bt->promoter_feats[r], h->pe[r], h->refs.lin_proj[r], h->ed.x[r][0], B, L, c.n_feats};
+        hipLaunchKernelGGL(k_embed_tokens, dim3(std::min<long long>((long long)B * L, 4096)), dim3(128), 0, st, ta);
+        LAUNCH_CHECK("k_embed_tokens");
+        const uint8_t *full, *valid;
+        embed_dense_mask(h, bt, r, &full, &valid, st);
+        for (int l = 0; l < E; ++l) {
+            const cf_dense_layer& w = h->refs.ED[r][l];
+            if (dense_layer_fwd(&w, h->ed.x[r][l], h->ed.x[r][l], valid, valid, full, B, L, L, h->ed.x[r][l + 1], h->ed.ws[r][l], train, st)) return -1;
+        }
+        hipLaunchKernelGGL(k_rows_gather, dim3(B), dim3(128), 0, st, (const float*)h->ed.x[r][E], L, L / 2, h->Rx[r][0], T * kD);
+        LAUNCH_CHECK("k_rows_gather");
+    }
+    return 0;
+}
+static int embed_dense_backward(cf_handle* h, const cf_batch* bt, hipStream_t st) {
+    const cf_config& c = h->cfg;
+    const int B = bt->B, E = c.embed_layers;
+    for (int r = 0; r < c.n_res; ++r) {
+        const int L = c.n_bins[r];
+        const long long n = (long long)B * L * kD;
+        float *dy = h->ed.dy[r][0], *da = h->ed.dy[r][1], *db = h->ed.dy[r][2];
+        hipLaunchKernelGGL(k_rows_scatter, dim3(B * L), dim3(128), 0, st, (const float*)h->edout[r], L, L / 2, dy);      // only the centre row is consumed (net.py:59)
+        LAUNCH_CHECK("k_rows_scatter");
+        const uint8_t *full, *valid;
+        embed_dense_mask(h, bt, r, &full, &valid, st);
+        for (int l = E - 1; l >= 0; --l) {
+            const cf_dense_layer& w = h->refs.ED[r][l];
+            cf_dense_layer_grads g{h->grad_of(w.wq), h->grad_of(w.wkv), h->grad_of(w.wo), h->grad_of(w.bo), h->grad_of(w.ln1_g), h->grad_of(w.ln1_b),
+                                   h->grad_of(w.w1), h->grad_of(w.b1), h->grad_of(w.w2), h->grad_of(w.b2), h->grad_of(w.ln2_g), h->grad_of(w.ln2_b)};
+            if (cf_op_dense_layer_bwd(&w, h->ed.x[r][l], h->ed.x[r][l], valid, valid, full, B, L, L, dy, da, db, &g, h->ed.ws[r][l], h->ed.tables, st)) return -1;
+            hipLaunchKernelGGL(k_add_inplace, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, da, (const float*)db, n);      // self-attention: x is query and key/value input
+            LAUNCH_CHECK("k_add_inplace");
+            std::swap(dy, da);
+        }
+        const long long rows = (long long)B * L;
+        const int chunks = (int)((rows + kEmbWgRows - 1) / kEmbWgRows);
+        EmbTokWgArgs wa{dy, bt->promoter_feats[r], h->ed.lp_partial[r], rows, c.n_feats};
+        hipLaunchKernelGGL(k_embed_tokens_wgrad, dim3(chunks), dim3(128), 0, st, wa);
+        hipLaunchKernelGGL(k_embed_tokens_wgrad2, dim3(1), dim3(128), 0, st, (const float*)h->ed.lp_partial[r], chunks, c.n_feats,
+                           h->grad_of(h->refs.lin_proj[r]));
+        LAUNCH_CHECK("k_embed_tokens_wgrad");
+    }
+    return 0;
+}
+
+// EmbeddingTransformer.forward's FIRST return value (net.py:57-59): the embeddings of every promoter bin, [B, 1, L, 128] per
+// resolution, for consumers that want more than the centre row.  Forward only; not capturable.
+extern "C" int cf_embed_full(cf_handle* h, const cf_batch* bt, float* const* out, void* stream) {
+    if (check_batch(h, bt) || !out) return fail("cf_embed_full: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    if (embed_dense_forward(h, bt, false, st)) return -1;
+    for (int r = 0; r < h->cfg.n_res; ++r) {
+        if (!out[r]) continue;
+        HIP_TRY(hipMemcpyAsync(out[r], h->ed.x[r][h->cfg.embed_layers], (size_t)bt->B * h->cfg.n_bins[r] * kD * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     return 0;
 }
