@@ -327,9 +327,45 @@ def scan_windows(start, end, binsize, width, n_win):
     return np.stack([lo, np.minimum(lo + int(width) * int(binsize), int(end))], axis=1).reshape(-1, 2)
 
 
+def scan_regions_expand(regions, i_max, who="perturbation_scan"):
+    """The scanned regions as a sorted list of region indices (0 the promoter, 1 + j pCRE slot j): "promoter" -> [0], "all" ->
+    [0 .. i_max], "pcres" -> [1 .. i_max], or an iterable of indices (duplicates dropped).  Raises ValueError on anything else."""
+    S = int(i_max)
+    if isinstance(regions, str):
+        named = {"promoter": [0], "all": list(range(S + 1)), "pcres": list(range(1, S + 1))}
+        if regions not in named:
+            raise ValueError("%s: regions %r; choose 'promoter', 'all', 'pcres' or a list of region indices" % (who, regions))
+        return named[regions]
+    regions = sorted({int(r) for r in regions})
+    if not regions or regions[0] < 0 or regions[-1] > S:
+        raise ValueError("%s: regions %s outside [0, i_max = %d]" % (who, regions, S))
+    return regions
+
+
+def scan_row(q, k, g, n_sets, W):
+    """Row of (block q of the scanned regions, mark set k, window g) in the flattened [n_reg * V] rows of a scan, V = 1 + n_sets * W;
+    k = None: the block's unperturbed row."""
+    V = 1 + int(n_sets) * int(W)
+    if k is None:
+        return int(q) * V
+    if not (0 <= k < n_sets and 0 <= g < W):
+        raise ValueError("scan_row: set %d / window %d outside [0, %d) x [0, %d)" % (k, g, n_sets, W))
+    return int(q) * V + 1 + int(k) * int(W) + int(g)
+
+
+def scan_row_inverse(row, n_sets, W):
+    """The inverse of scan_row: row -> (q, k, g), or (q, None, None) for a block's unperturbed row."""
+    V = 1 + int(n_sets) * int(W)
+    q, v = divmod(int(row), V)
+    if v == 0:
+        return q, None, None
+    k, g = divmod(v - 1, int(W))
+    return q, k, g
+
+
 def perturbation_scan(model, dataset, genes=None, regions="promoter", scale=0.0, width=1, mark_sets=None, bsz=None, store=None):
-    """In-silico perturbation scan of the genes of a ChromoformerDataset (model.perturbation_scan per region, windows in genomic
-    coordinates): what the prediction becomes with the marks of a mark set scaled by `scale` in raw-signal space -- 0 erases, 2
+    """In-silico perturbation scan of the genes of a ChromoformerDataset (one model.perturbation_scan_regions per batch, windows in
+    genomic coordinates): what the prediction becomes with the marks of a mark set scaled by `scale` in raw-signal space -- 0 erases, 2
     doubles -- over each window of `width` coarsest bins of a region.  A generator over `genes` (ids; default: the dataset's) in
     chunks of at most min(bsz, model.max_batch) genes; per gene it yields a dict of host arrays:
 
@@ -342,7 +378,7 @@ def perturbation_scan(model, dataset, genes=None, regions="promoter", scale=0.0,
                    the region
         scan       per region float32 [n_sets, n_win, n_out]: the logits with set k scaled over window g, genomic order
 
-    regions: "promoter", "all" (the promoter and every pCRE the gene has) or a list of region indices (0 the promoter, 1 + j pCRE
+    regions: "promoter", "all" (the promoter and every pCRE the gene has), "pcres" or a list of region indices (0 the promoter, 1 + j pCRE
     slot j; a slot the gene does not have is left out).  Strand and coordinates come from the dataset's metadata ('-' strand promoters
     are stored mirrored: window 0 is still the genomic start).  The binned features come from `store` (a device-resident GeneStore
     holding `genes` in order) if given, else from the packed store next to the raw files if one matches, else from the raw .npy
@@ -359,13 +395,8 @@ def perturbation_scan(model, dataset, genes=None, regions="promoter", scale=0.0,
     n_bins = _geometry_check("perturbation_scan", model, ds, binsizes)
     genes, chunk = _genes_check("perturbation_scan", model, ds, genes, bsz)
     S, F, dev = ds.i_max, ds.n_feats, model._device
-    if isinstance(regions, str):
-        if regions not in ("promoter", "all"):
-            raise ValueError("perturbation_scan: regions %r; choose 'promoter', 'all' or a list of region indices" % (regions,))
-        regions = [0] if regions == "promoter" else list(range(S + 1))
-    regions = [int(r) for r in regions]
-    if not regions or any(not 0 <= r <= S for r in regions):
-        raise ValueError("perturbation_scan: regions %s outside [0, i_max = %d]" % (regions, S))
+    order = scan_regions_expand(regions, S) if isinstance(regions, str) else [int(r) for r in regions]      # (the caller's order is kept)
+    regions = scan_regions_expand(order, S)
     if mark_sets is None:
         mark_sets = [(f,) for f in range(F)] + [tuple(range(F))]
     mark_sets = [tuple(int(f) for f in ms) for ms in mark_sets]
@@ -389,15 +420,18 @@ def perturbation_scan(model, dataset, genes=None, regions="promoter", scale=0.0,
         args = tuple(d[k] for k in ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq"))
         flip = [ds.genes[g]["tss"][2] != "+" for g in ids]
         per = [dict(gene_id=g, logits=None, mark_sets=list(mark_sets), regions=[], windows=[], scan=[]) for g in ids]
-        for region in regions:
-            has = [region == 0 or region - 1 < len(ds.genes[g]["pcres"]) for g in ids]
-            if not any(has):
-                continue
-            out = model.perturbation_scan(*args, region=region, scale=scale, width=width, mark_sets=mark_sets,
-                                          flip=flip if region == 0 else None).cpu().numpy()
+        has_of = {region: [region == 0 or region - 1 < len(ds.genes[g]["pcres"]) for g in ids] for region in regions}
+        live = [region for region in regions if any(has_of[region])]      # (a slot no gene of the chunk has is not scanned)
+        blocks = None
+        if live:
+            blocks, _ = model.perturbation_scan_regions(*args, regions=live, scale=scale, width=width, mark_sets=mark_sets, flip=flip)
+            blocks = blocks.cpu().numpy()
+        K = len(mark_sets)
+        for region in (r for r in order if r in live):
+            has, out = has_of[region], blocks[live.index(region)]
             m = (d["promoter_pad_masks"][bc] if region == 0 else d["pcre_pad_masks"][bc][:, region - 1]).reshape(B, W).cpu().numpy() == 0
             for i, g in enumerate(ids):
-                per[i]["logits"] = out[i, 0].copy()
+                per[i]["logits"] = out[i, scan_row(0, None, None, K, W)].copy()
                 if not has[i]:
                     continue
                 real = np.flatnonzero(m[i])
@@ -409,7 +443,7 @@ def perturbation_scan(model, dataset, genes=None, regions="promoter", scale=0.0,
                     reg = tuple(ds.genes[g]["pcres"][region - 1])
                 per[i]["regions"].append(reg)
                 per[i]["windows"].append(scan_windows(reg[1], reg[2], bc, width, n_win))
-                per[i]["scan"].append(out[i, 1:].reshape(len(mark_sets), W, -1)[:, :n_win].copy())
+                per[i]["scan"].append(out[i, scan_row(0, 0, 0, K, W):].reshape(K, W, -1)[:, :n_win].copy())
         if per[0]["logits"] is None:      # (no gene of the chunk has any of the regions: the prediction alone)
             with torch.no_grad():
                 out = model(*args).cpu().numpy()

@@ -195,6 +195,7 @@ extern "C" int cf_create(const cf_config* cfg, const float* const* pe_host, cf_h
     if (const char* e = getenv("CF_ATTC_CAP")) h->attc_cap = atoi(e);
     if (const char* e = getenv("CF_ATTC1")) h->attc1 = atoi(e) != 0;
     h->intg_trunk_once = getenv_int("CF_IG_TRUNK_ONCE", 1) != 0;
+    h->scan_pack = getenv_int("CF_SCAN_PACK", 1) != 0;
     if (const char* e = getenv("CF_DEFER_RETILE")) h->defer_retile = atoi(e) != 0;
     if (const char* e = getenv("CF_HEAD_RIDE")) h->head_ride = atoi(e) != 0;
     if (const char* e = getenv("CF_XCD_REDUCE")) h->xcd_reduce = h->xcd_reduce_opt = atoi(e) != 0;
@@ -227,6 +228,7 @@ extern "C" void cf_destroy(cf_handle* h) {
     if (h->coal_rows) (void)hipFree(h->coal_rows);
     if (h->intg_mem) (void)hipFree(h->intg_mem);
     if (h->intg_tab) (void)hipFree(h->intg_tab);
+    if (h->scan_xv) (void)hipFree(h->scan_xv);
     delete h;
 }
 

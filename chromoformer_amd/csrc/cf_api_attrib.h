@@ -620,41 +620,40 @@ extern "C" int cf_integrated_gradients_raw(cf_handle* h, const cf_batch* bt, con
     return integrated_gradients_impl(h, bt, o, out, coeff, logits_x, logits_base, delta, stream, true, "cf_integrated_gradients_raw");
 }
 
-// In-silico perturbation scan (cf_scan.h).  Per chunk of at most max_batch of the B * V rows (V = 1 + n_sets * W, gene-major):
-// k_scan_expand into the chunk buffers of cf_integrated_gradients (whichever call comes first allocates them; the mark sets travel in
-// its node table), then the launches of cf_forward(save = 0) on the chunk, writing its slice of `logits`.  k_attc2 takes as many
-// regions per workgroup as for the caller's B genes (ag_genes): the result does not depend on max_batch and row (b, v) carries the
-// bits of cf_forward(save = 0) on the batch with the perturbed features substituted.
-extern "C" int cf_perturbation_scan(cf_handle* h, const cf_batch* bt, const cf_scan_opts* o, float* logits, void* stream) {
-    const char* who = "cf_perturbation_scan";
-    if (!h) return fail("%s: null handle", who);
-    if (!bt) return fail("%s: null batch", who);
-    if (!o) return fail("%s: null opts", who);
-    if (!logits) return fail("%s: null logits", who);
-    if (!o->mark_sets) return fail("%s: null mark_sets", who);
+// What the two scan entry points check alike, in front of anything launched.  scan_check: the window, the mark sets, the scale, nested
+// bin counts (*rc_out: the coarsest resolution); scan_check_state: riders, the batch, and the chunk buffers are allocated.
+static int scan_check(cf_handle* h, int width, int n_sets, const unsigned* mark_sets, float scale, const char* who, int* rc_out) {
     const cf_config& c = h->cfg;
-    const int nres = c.n_res, S = c.i_max, F = c.n_feats, cap = c.max_batch;
-    if (bt->B > cap) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, cap);
-    if (o->region < 0 || o->region > S) return fail("%s: region = %d outside [0, i_max = %d]", who, o->region, S);
-    if (o->width < 1) return fail("%s: width = %d: at least 1 coarsest bin", who, o->width);
-    if (o->n_sets < 1) return fail("%s: n_sets = %d: at least 1 mark set", who, o->n_sets);
-    if (!(o->scale >= 0.f) || !std::isfinite(o->scale)) return fail("%s: scale = %g: a finite factor >= 0", who, (double)o->scale);
-    for (int k = 0; k < o->n_sets; ++k)
-        if (F < 32 && o->mark_sets[k] >> F) return fail("%s: mark_sets[%d] = 0x%x names a mark >= n_feats = %d", who, k, o->mark_sets[k], F);
+    const int nres = c.n_res, F = c.n_feats;
+    if (width < 1) return fail("%s: width = %d: at least 1 coarsest bin", who, width);
+    if (n_sets < 1) return fail("%s: n_sets = %d: at least 1 mark set", who, n_sets);
+    if (!(scale >= 0.f) || !std::isfinite(scale)) return fail("%s: scale = %g: a finite factor >= 0", who, (double)scale);
+    for (int k = 0; k < n_sets; ++k)
+        if (F < 32 && mark_sets[k] >> F) return fail("%s: mark_sets[%d] = 0x%x names a mark >= n_feats = %d", who, k, mark_sets[k], F);
     int rc = 0;
     for (int r = 1; r < nres; ++r)
         if (c.n_bins[r] < c.n_bins[rc]) rc = r;
     const int W = c.n_bins[rc];
     for (int r = 0; r < nres; ++r)
         if (c.n_bins[r] % W) return fail("%s: n_bins[%d] = %d is not a multiple of the coarsest resolution's %d bins", who, r, c.n_bins[r], W);
-    for (int r = nres; r < kMaxRes; ++r)
-        if (o->feats_out[r]) return fail("%s: feats_out[%d]: the model has %d resolutions", who, r, nres);
+    *rc_out = rc;
+    return 0;
+}
+static int scan_check_state(cf_handle* h, const cf_batch* bt, int n_sets, const char* who) {
     if (h->rider.armed || h->rider.done) return fail("%s: riders are armed for a training step (cf_rider_arm); finish the step first", who);
     if (check_batch(h, bt)) return -1;
-    if (intg_alloc(h, o->n_sets)) return -1;
-    hipStream_t st = (hipStream_t)stream;
+    return intg_alloc(h, n_sets);
+}
+
+// One region of a scan, every row through the whole forward.  Per chunk of at most max_batch of the B * V rows (V = 1 + n_sets * W,
+// gene-major): k_scan_expand into the chunk buffers of cf_integrated_gradients (whichever call comes first allocates them; the mark
+// sets travel in its node table, uploaded by the caller), then the launches of cf_forward(save = 0) on the chunk, writing its slice of
+// `logits`.  k_attc2 takes as many regions per workgroup as for the caller's B genes (ag_genes): the result does not depend on
+// max_batch and row (b, v) carries the bits of cf_forward(save = 0) on the batch with the perturbed features substituted.
+static int scan_region_rows(cf_handle* h, const cf_batch* bt, const cf_scan_opts* o, int rc, float* logits, hipStream_t st) {
+    const cf_config& c = h->cfg;
+    const int nres = c.n_res, S = c.i_max, F = c.n_feats, cap = c.max_batch, W = c.n_bins[rc];
     const int B = bt->B, V = 1 + o->n_sets * W, slot = o->region - 1;
-    HIP_TRY(hipMemcpyAsync(h->intg_tab, o->mark_sets, o->n_sets * sizeof(unsigned), hipMemcpyHostToDevice, st));
     ScanExpandArgs ea;
     memset(&ea, 0, sizeof ea);
     cf_batch cb;      // the chunk's batch: the rows' copies
@@ -679,15 +678,143 @@ extern "C" int cf_perturbation_scan(cf_handle* h, const cf_batch* bt, const cf_s
     ea.flip = o->flip;
     ea.scale = o->scale;
     ea.V = V, ea.F = F, ea.W = W, ea.width = o->width, ea.rc = rc, ea.region = o->region;
-    const long long launches0 = g_launches;
-    int rv = 0;
-    for (int g0 = 0; g0 < B * V && !rv; g0 += cap) {
+    for (int g0 = 0; g0 < B * V; g0 += cap) {
         const int nr = std::min(cap, B * V - g0);
         ea.g0 = g0;
         hipLaunchKernelGGL(k_scan_expand, dim3(nr, nres), dim3(kIgxThreads), 0, st, ea);
         LAUNCH_CHECK("k_scan_expand");
         cb.B = nr;
-        rv = forward_trunk(h, &cb, 0, st, B) || forward_reg_head(h, &cb, logits + (size_t)g0 * c.n_out, 0, st, nullptr);
+        if (forward_trunk(h, &cb, 0, st, B) || forward_reg_head(h, &cb, logits + (size_t)g0 * c.n_out, 0, st, nullptr)) return -1;
+    }
+    return 0;
+}
+
+// In-silico perturbation scan of one region (cf_scan.h): scan_region_rows.
+extern "C" int cf_perturbation_scan(cf_handle* h, const cf_batch* bt, const cf_scan_opts* o, float* logits, void* stream) {
+    const char* who = "cf_perturbation_scan";
+    if (!h) return fail("%s: null handle", who);
+    if (!bt) return fail("%s: null batch", who);
+    if (!o) return fail("%s: null opts", who);
+    if (!logits) return fail("%s: null logits", who);
+    if (!o->mark_sets) return fail("%s: null mark_sets", who);
+    const cf_config& c = h->cfg;
+    if (bt->B > c.max_batch) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, c.max_batch);
+    if (o->region < 0 || o->region > c.i_max) return fail("%s: region = %d outside [0, i_max = %d]", who, o->region, c.i_max);
+    int rc = 0;
+    if (scan_check(h, o->width, o->n_sets, o->mark_sets, o->scale, who, &rc)) return -1;
+    for (int r = c.n_res; r < kMaxRes; ++r)
+        if (o->feats_out[r]) return fail("%s: feats_out[%d]: the model has %d resolutions", who, r, c.n_res);
+    if (scan_check_state(h, bt, o->n_sets, who)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(h->intg_tab, o->mark_sets, o->n_sets * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    const long long launches0 = g_launches;
+    const int rv = scan_region_rows(h, bt, o, rc, logits, st);
+    h->x0_fwd = false;
+    forward_counted(h, launches0);
+    return rv ? -1 : 0;
+}
+
+// The variants of pCRE slot `slot`, slot-packed (cf_scan.h), into `logits` [B, V, n_out].  The caller has stashed the B genes' trunk
+// output in abl_stash and uploaded the mark sets.  Pack phase, per chunk of at most max_batch of the B * U pseudo rows: k_scan_pack,
+// the trunk (k_attc2's regions per workgroup as for the caller's B genes, as scan_region_rows), k_scan_unpack into scan_xv.  Row phase,
+// per chunk of at most max_batch of the B * V rows: k_scan_rows, the Regulation + head launches of an inference forward.
+static int scan_slot_packed(cf_handle* h, const cf_batch* bt, const cf_scan_regions_opts* o, int slot, int rc, float* logits, hipStream_t st) {
+    const cf_config& c = h->cfg;
+    const int nres = c.n_res, S = c.i_max, T = S + 1, cap = c.max_batch, W = c.n_bins[rc], d4 = c.d_emb / 4;
+    const int B = bt->B, V = 1 + o->n_sets * W, U = (V - 1 + S - 1) / S;
+    ScanPackArgs pa;
+    ScanUnpackArgs ua;
+    ScanRowsArgs ra;
+    memset(&pa, 0, sizeof pa);
+    memset(&ua, 0, sizeof ua);
+    memset(&ra, 0, sizeof ra);
+    cf_batch cb;      // the chunk's batch: pseudo-genes for the trunk, then rows (masks and frequencies) for Regulation + head
+    intg_chunk_rows(h, bt, &pa.rows, &cb);
+    ra.rows = pa.rows;
+    const size_t xv_res = (size_t)B * (V - 1) * c.d_emb;
+    for (int r = 0; r < nres; ++r) {
+        pa.pf_in[r] = bt->promoter_feats[r];
+        pa.cf_in[r] = bt->pcre_feats[r];
+        pa.pf_out[r] = h->intg_row[r];
+        pa.cf_out[r] = h->intg_row[kMaxRes + r];
+        ua.x0[r] = reinterpret_cast<const float4*>(h->Rx[r][0]);
+        ua.xv[r] = reinterpret_cast<float4*>(h->scan_xv + r * xv_res);
+        ra.stash[r] = reinterpret_cast<const float4*>(h->abl_stash[r]);
+        ra.xv[r] = ua.xv[r];
+        ra.x0[r] = reinterpret_cast<float4*>(h->Rx[r][0]);
+    }
+    pa.sets = reinterpret_cast<const unsigned*>(h->intg_tab);
+    pa.scale = o->scale;
+    pa.U = U, pa.V = V, pa.F = c.n_feats, pa.W = W, pa.width = o->width, pa.rc = rc, pa.slot = slot;
+    ua.U = U, ua.V = V, ua.S = S, ua.T = T, ua.d4 = d4;
+    ra.freq_in = bt->interaction_freq;
+    ra.freq_out = h->intg_row[2 * kMaxRes];
+    ra.V = V, ra.row4 = T * d4, ra.d4 = d4, ra.slot = slot;
+    for (int g0 = 0; g0 < B * U; g0 += cap) {
+        const int n = std::min(cap, B * U - g0);
+        pa.g0 = ua.g0 = g0;
+        hipLaunchKernelGGL(k_scan_pack, dim3(n, nres), dim3(kIgxThreads), 0, st, pa);
+        LAUNCH_CHECK("k_scan_pack");
+        cb.B = n;
+        if (forward_trunk(h, &cb, 0, st, B)) return -1;
+        hipLaunchKernelGGL(k_scan_unpack, dim3(n, nres), dim3(kRowThreads), 0, st, ua);
+        LAUNCH_CHECK("k_scan_unpack");
+    }
+    for (int g0 = 0; g0 < B * V; g0 += cap) {
+        const int n = std::min(cap, B * V - g0);
+        ra.g0 = g0;
+        hipLaunchKernelGGL(k_scan_rows, dim3(n, nres), dim3(kRowThreads), 0, st, ra);
+        LAUNCH_CHECK("k_scan_rows");
+        cb.B = n;
+        if (forward_reg_head(h, &cb, logits + (size_t)g0 * c.n_out, 0, st, nullptr)) return -1;
+    }
+    return 0;
+}
+
+// The scan of several regions of every gene from one call: the promoter block through scan_region_rows, the pCRE blocks slot-packed
+// (scan_slot_packed; CF_SCAN_PACK=0 at cf_create: through scan_region_rows as well, the cross-check).
+extern "C" int cf_perturbation_scan_regions(cf_handle* h, const cf_batch* bt, const cf_scan_regions_opts* o, float* logits, void* stream) {
+    const char* who = "cf_perturbation_scan_regions";
+    if (!h) return fail("%s: null handle", who);
+    if (!bt) return fail("%s: null batch", who);
+    if (!o) return fail("%s: null opts", who);
+    if (!logits) return fail("%s: null logits", who);
+    if (!o->mark_sets) return fail("%s: null mark_sets", who);
+    const cf_config& c = h->cfg;
+    const int S = c.i_max;
+    if (bt->B > c.max_batch) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, c.max_batch);
+    if (!o->regions) return fail("%s: regions = 0: at least one region bit (bit 0 the promoter, bit 1 + j pCRE slot j)", who);
+    if (o->regions >> S >> 1) return fail("%s: regions = 0x%x names a region above i_max = %d", who, o->regions, S);
+    int rc = 0;
+    if (scan_check(h, o->width, o->n_sets, o->mark_sets, o->scale, who, &rc) || scan_check_state(h, bt, o->n_sets, who)) return -1;
+    const bool packed = h->scan_pack && (o->regions >> 1);
+    const int B = bt->B, V = 1 + o->n_sets * c.n_bins[rc];
+    if (packed) {
+        if (ablate_alloc(h, who)) return -1;
+        const size_t need = (size_t)c.n_res * B * (V - 1) * c.d_emb;
+        if (need > h->scan_xv_floats) {
+            if (h->scan_xv) (void)hipFree(h->scan_xv);      // (synchronises: a call in flight may still read the old buffer)
+            h->scan_xv = nullptr;
+            h->scan_xv_floats = 0;
+            if (hipMalloc(&h->scan_xv, need * sizeof(float)) != hipSuccess) return fail("%s: out of memory", who);
+            h->scan_xv_floats = need;
+        }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(h->intg_tab, o->mark_sets, o->n_sets * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    const long long launches0 = g_launches;
+    const size_t block = (size_t)B * V * c.n_out;
+    cf_scan_opts so;
+    memset(&so, 0, sizeof so);
+    so.width = o->width, so.n_sets = o->n_sets, so.mark_sets = o->mark_sets, so.scale = o->scale;
+    int rv = 0, q = 0;
+    if (packed) rv = forward_trunk(h, bt, 0, st) || stash_trunk_output(h, B, h->abl_stash, st);
+    for (int region = 0; region <= S && !rv; ++region) {
+        if (!(o->regions >> region & 1u)) continue;
+        float* out = logits + q++ * block;
+        so.region = region;
+        so.flip = region == 0 ? o->flip : nullptr;      // (pCREs are never stored mirrored)
+        rv = region == 0 || !packed ? scan_region_rows(h, bt, &so, rc, out, st) : scan_slot_packed(h, bt, o, region - 1, rc, out, st);
     }
     h->x0_fwd = false;
     forward_counted(h, launches0);

@@ -368,6 +368,10 @@ struct cf_handle {
     int intg_cap = 0;
     float* intg_part = nullptr;                // [max_batch, kIgSlices]: per-slice sums of a gene's attributions (k_ig_delta)
     bool intg_trunk_once = true;               // frequency-only IG runs the trunk once (CF_IG_TRUNK_ONCE=0 at cf_create: the general path, for A/B checks)
+    // perturbation scan of several regions (cf_perturbation_scan_regions): the changed Regulation input row of every variant of one pCRE slot
+    float* scan_xv = nullptr;                  // [n_res][B * (V - 1), d_emb]; grows on demand
+    size_t scan_xv_floats = 0;
+    bool scan_pack = true;                     // pCRE variants run slot-packed (CF_SCAN_PACK=0 at cf_create: the per-region path, for A/B checks)
     // deferred-gradient tile tables
     WgTile* wg_tiles = nullptr;
     int n_wg = 0;

@@ -1,4 +1,4 @@
-// cf_scan.h -- in-silico perturbation scan (cf_perturbation_scan; included by cf_api.hip behind cf_ig.h).
+// cf_scan.h -- in-silico perturbation scan (cf_perturbation_scan, cf_perturbation_scan_regions; included by cf_api.hip behind cf_ig.h).
 //
 // One region of every gene -- the promoter or one pCRE slot -- is scanned: the histone marks of a mark set are scaled by s >= 0 in
 // RAW-SIGNAL space over a window of the region, and the gene is run forward.  Binning is linear, so scaling the samples of a bin by
@@ -125,6 +125,95 @@ __global__ __launch_bounds__(kIgxThreads) void k_scan_expand(ScanExpandArgs a) {
     scan_copy(a.cf_in[r] + (size_t)b * S * LF, a.cf_out[r] + (size_t)i * S * LF, S * LF, off, LF, prom ? 0 : off + p0 * F,
               prom ? 0 : off + p1 * F, bits, F, a.scale, prom ? nullptr : fo);
     rows_pad_masks(a.rows, r, b, i);
+    rows_interaction_mask(a.rows, r, b, i);
+    if (r == 0) rows_copy_tt(a.freq_in, a.freq_out, b, i, a.rows.TT);
+}
+
+// Several regions per call (cf_perturbation_scan_regions): the variants of ONE pCRE slot j, slot-packed.  The Pairwise output of a slot
+// depends on the promoter and on that slot alone, and the S slots of a gene are S independent rows of one tile: a pseudo-gene with gene
+// b's promoter and S differently perturbed copies of its slot j as slots yields, in one trunk pass, the changed Regulation input row of
+// S variants.  Pseudo rows are (gene, u) pairs, gene-major (gp = b * U + u, U = ceil((V - 1) / S)); slot s of pseudo row (b, u) is
+// variant v = 1 + u * S + s (v >= V: slot j verbatim).  Byte movers plus the window rule above, no atomics:
+//   k_scan_pack     per (pseudo row, resolution): the promoter's features and pad-mask rows verbatim, slot j's features under each of
+//                   the S variants, slot j's pad-mask row into every slot
+//   k_scan_unpack   per (pseudo row, resolution): rows 1..S of the pseudo-gene's trunk output -> xv[(b, v - 1)], one d_emb row per variant
+//   k_scan_rows     per (row (b, v), resolution): the stashed trunk output of gene b -> Rx[r][0] with row j + 1 from xv (v >= 1), the
+//                   gene's interaction mask, resolution 0 also its interaction_freq
+struct ScanPackArgs {
+    const float* pf_in[kMaxRes];       // as ScanExpandArgs
+    const float* cf_in[kMaxRes];
+    float* pf_out[kMaxRes];
+    float* cf_out[kMaxRes];
+    RowCopyArgs rows;                  // the pad masks (the interaction masks are not read by the trunk: not copied)
+    const unsigned* sets;
+    float scale;
+    int g0, U, V, F, W, width, rc, slot;
+};
+
+__global__ __launch_bounds__(kIgxThreads) void k_scan_pack(ScanPackArgs a) {
+    __shared__ int red[2 * (kIgxThreads / 64)];
+    const int i = blockIdx.x, r = blockIdx.y;
+    const int gp = a.g0 + i, b = gp / a.U, u = gp - b * a.U;
+    const int L = a.rows.L[r], S = a.rows.S, F = a.F, LF = L * F, PL = a.rows.pm_rows[r] * L;
+    // slot j's extent at the coarsest resolution and at this one (block-uniform; k_scan_expand's geometry, never mirrored)
+    const uint8_t* cm = a.rows.cm_in[r] + ((size_t)b * S + a.slot) * a.rows.cm_stride[r];
+    int clo, chi, lo, hi;
+    scan_extent(a.rows.cm_in[a.rc] + ((size_t)b * S + a.slot) * a.rows.cm_stride[a.rc], a.rows.L[a.rc], red, clo, chi);
+    scan_extent(cm, L, red, lo, hi);
+    const int nc = chi > clo ? chi - clo : 0, nr = hi > lo ? hi - lo : 0, R = L / a.W;
+    scan_copy(a.pf_in[r] + (size_t)b * LF, a.pf_out[r] + (size_t)i * LF, LF, 0, LF, 0, 0, 0u, F, a.scale, nullptr);
+    const float* src = a.cf_in[r] + ((size_t)b * S + a.slot) * LF;
+    for (int s = 0; s < S; ++s) {
+        const int v = 1 + u * S + s;
+        int p0 = 0, p1 = 0;
+        unsigned bits = 0;
+        if (v < a.V) {
+            const int k = (v - 1) / a.W, g = (v - 1) - k * a.W;
+            bits = a.sets[k];
+            if (bits && g < nc) {
+                const int j0 = g * R, j1 = min(min(g + a.width, nc) * R, nr);
+                if (j0 < j1) p0 = lo + j0, p1 = lo + j1;
+            }
+        }
+        scan_copy(src, a.cf_out[r] + ((size_t)i * S + s) * LF, LF, 0, LF, p0 * F, p1 * F, bits, F, a.scale, nullptr);
+    }
+    for (int k = threadIdx.x; k < PL; k += kIgxThreads) a.rows.pm_out[r][(size_t)i * PL + k] = a.rows.pm_in[r][(size_t)b * a.rows.pm_stride[r] + k];
+    for (int k = threadIdx.x; k < S * L; k += kIgxThreads) a.rows.cm_out[r][(size_t)i * S * L + k] = cm[k % L];
+}
+
+struct ScanUnpackArgs {
+    const float4* x0[kMaxRes];         // Rx[r][0] of the chunk's pseudo-genes, [n, T, D / 4]
+    float4* xv[kMaxRes];               // [B * (V - 1), D / 4]
+    int g0, U, V, S, T, d4;
+};
+
+__global__ __launch_bounds__(kRowThreads) void k_scan_unpack(ScanUnpackArgs a) {
+    const int i = blockIdx.x, r = blockIdx.y;
+    const int gp = a.g0 + i, b = gp / a.U, u = gp - b * a.U;
+    const int n = min(a.S, a.V - 1 - u * a.S) * a.d4;      // rows 1..S are adjacent, and so are their variants
+    const float4* __restrict__ src = a.x0[r] + ((size_t)i * a.T + 1) * a.d4;
+    float4* __restrict__ dst = a.xv[r] + ((size_t)b * (a.V - 1) + (size_t)u * a.S) * a.d4;
+    for (int k = threadIdx.x; k < n; k += kRowThreads) dst[k] = src[k];
+}
+
+struct ScanRowsArgs {
+    const float4* stash[kMaxRes];      // [B, T * D / 4]: the genes' own trunk output
+    const float4* xv[kMaxRes];
+    float4* x0[kMaxRes];               // Rx[r][0], rows of the chunk
+    RowCopyArgs rows;                  // the interaction masks
+    const float* freq_in;              // [B, T, T]
+    float* freq_out;
+    int g0, V, row4, d4, slot;
+};
+
+__global__ __launch_bounds__(kRowThreads) void k_scan_rows(ScanRowsArgs a) {
+    const int i = blockIdx.x, r = blockIdx.y;
+    const int gv = a.g0 + i, b = gv / a.V, v = gv - b * a.V;
+    const float4* __restrict__ src = a.stash[r] + (size_t)b * a.row4;
+    const float4* __restrict__ var = a.xv[r] + ((size_t)b * (a.V - 1) + (v > 0 ? v - 1 : 0)) * a.d4;
+    float4* __restrict__ dst = a.x0[r] + (size_t)i * a.row4;
+    const int k0 = v > 0 ? (a.slot + 1) * a.d4 : a.row4;      // (v = 0: no row is replaced)
+    for (int k = threadIdx.x; k < a.row4; k += kRowThreads) dst[k] = k >= k0 && k < k0 + a.d4 ? var[k - k0] : src[k];
     rows_interaction_mask(a.rows, r, b, i);
     if (r == 0) rows_copy_tt(a.freq_in, a.freq_out, b, i, a.rows.TT);
 }

@@ -151,7 +151,7 @@ class ChromoformerBase(nn.Module):
         self.n_bins = [w_max // b for b in self.binsizes]
         self._kws = (embed, pair, reg)
         self._max_batch = max_batch
-        self._maps_gen = 0          # bumped by attention_maps() / pcre_ablation() / pcre_coalitions() / pcre_shapley() / pcre_epistasis() / integrated_gradients() / trunk_outputs(): a pending backward of an earlier forward refuses to run
+        self._maps_gen = 0          # bumped by attention_maps() / pcre_ablation() / pcre_coalitions() / pcre_shapley() / pcre_epistasis() / integrated_gradients() / perturbation_scan() / perturbation_scan_regions() / trunk_outputs(): a pending backward of an earlier forward refuses to run
         self._maps_by = None        # ... naming the last of them
         self._handle = None
         self._device = None
@@ -731,6 +731,44 @@ class ChromoformerBase(nn.Module):
         st = book()
         _lib.check(_lib.lib().cf_perturbation_scan(self._handle, C.byref(bs), C.byref(opts), logits.data_ptr(), st), "cf_perturbation_scan")
         return (logits, feats) if return_feats else logits
+
+    @torch.no_grad()
+    def perturbation_scan_regions(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                                  interaction_freq=None, regions="all", scale=0.0, width=1, mark_sets=None, flip=None):
+        """perturbation_scan of several regions from one call (cf_perturbation_scan_regions) -> (logits [n_reg, B, V, n_out] on the
+        model's device, the list of scanned regions in block order).  regions: "all" (0 .. i_max), "pcres" (1 .. i_max) or an iterable
+        of region indices (0 the promoter, 1 + j pCRE slot j; sorted, duplicates dropped).  Block q carries the bits of
+        perturbation_scan(region=regions[q]) with the same scale, width and mark_sets -- `flip` applies to the promoter block alone
+        (pCREs are never stored mirrored).  The promoter block costs what perturbation_scan costs; the variants of a pCRE slot run
+        slot-packed: i_max variants share one pass of the Embedding + Pairwise stage, and only the Regulation stack and the head run
+        per variant.  mark_sets, the packed forms of the first argument and the effect on a pending backward() are those of
+        perturbation_scan; there is no return_feats."""
+        from .attribution import scan_regions_expand
+        bs, _keep, book = self._attrib_call("perturbation_scan_regions", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        F, dev, B = self.n_feats, self._device, bs.B
+        regions = scan_regions_expand(regions, self.i_max, "perturbation_scan_regions")
+        if mark_sets is None:
+            mark_sets = [(f,) for f in range(F)] + [tuple(range(F))]
+        mark_sets = [tuple(int(f) for f in ms) for ms in mark_sets]
+        bad = [ms for ms in mark_sets if any(not 0 <= f < min(F, 32) for f in ms)]
+        if bad or not mark_sets:
+            raise ValueError("perturbation_scan_regions: mark_sets %s: a non-empty list of sets of mark indices in [0, n_feats = %d)" % (bad or "()", F))
+        bits = np.array([sum(1 << f for f in set(ms)) for ms in mark_sets], dtype=np.uint32)
+        V = 1 + len(mark_sets) * min(self.n_bins)
+        opts = _lib.cf_scan_regions_opts()
+        opts.regions = sum(1 << r for r in regions)
+        opts.width, opts.n_sets, opts.scale = int(width), len(mark_sets), float(scale)
+        opts.mark_sets = bits.ctypes.data
+        if flip is not None:
+            flip = torch.as_tensor(flip).to(dev).ne(0).to(torch.uint8).contiguous()
+            if flip.numel() != B:
+                raise ValueError("perturbation_scan_regions: flip has %d entries for a batch of %d genes" % (flip.numel(), B))
+            opts.flip = flip.data_ptr()
+        logits = torch.empty(len(regions), B, V, self.n_out, device=dev)      # (written in full by the library)
+        st = book()
+        _lib.check(_lib.lib().cf_perturbation_scan_regions(self._handle, C.byref(bs), C.byref(opts), logits.data_ptr(), st),
+                   "cf_perturbation_scan_regions")
+        return logits, regions
 
     def perturbation_scan_dataset(self, dataset, genes=None, regions="promoter", scale=0.0, width=1, mark_sets=None, bsz=None, store=None):
         """perturbation_scan over the genes of a ChromoformerDataset with windows in genomic coordinates

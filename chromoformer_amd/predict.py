@@ -221,10 +221,11 @@ def write_perturbation_scan(model, store, bsz, path, gene_ids, strands, regressi
                      real bin
         pcres        float32 [n, i_max, n_sets, W], with regions="all": the same per pCRE slot (NaN for dummy slots)
 
-    Per batch: one device gather into a Slot and one model.perturbation_scan per scanned region."""
+    Per batch: one device gather into a Slot and one model.perturbation_scan_regions over the scanned regions."""
     import ctypes as C
 
     from . import _lib
+    from .attribution import scan_regions_expand, scan_row
     n, dev, L = len(store), model._device, _lib.lib()
     S, F = model.i_max, model.n_feats
     if mark_sets is None:
@@ -234,7 +235,7 @@ def write_perturbation_scan(model, store, bsz, path, gene_ids, strands, regressi
     rc = int(np.argmin(model.n_bins))
     W = model.n_bins[rc]
     V = 1 + K * W
-    scanned = [0] + (list(range(1, S + 1)) if regions == "all" else [])
+    scanned = scan_regions_expand("all" if regions == "all" else "promoter", S, "write_perturbation_scan")
     logits = torch.empty(len(scanned), n, V, model.n_out)
     live = torch.zeros(len(scanned), n, W, dtype=torch.bool)      # window g of the region holds a real bin
     struct = store.struct()
@@ -248,10 +249,9 @@ def write_perturbation_scan(model, store, bsz, path, gene_ids, strands, regressi
         cursor = torch.tensor([0, 1, 0, 0], dtype=torch.int32).to(dev)
         _lib.check(L.cf_gather_batch(model._handle, C.byref(struct), order[lo:].data_ptr(), cursor.data_ptr(), C.byref(slot.struct), None, st),
                    "cf_gather_batch")
+        out, _ = model.perturbation_scan_regions(slot, regions=scanned, scale=scale, width=width, mark_sets=mark_sets, flip=flip[lo:lo + B])
+        logits[:, lo:lo + B] = out.cpu()
         for k, region in enumerate(scanned):
-            out = model.perturbation_scan(slot, region=region, scale=scale, width=width, mark_sets=mark_sets,
-                                          flip=flip[lo:lo + B] if region == 0 else None)
-            logits[k, lo:lo + B] = out.cpu()
             m = (store.pm[rc][lo:lo + B] if region == 0 else store.cm[rc][lo:lo + B, region - 1]).reshape(B, W).cpu() == 0
             pos = torch.arange(W)
             first = torch.where(m, pos, W).amin(1)
@@ -268,12 +268,12 @@ def write_perturbation_scan(model, store, bsz, path, gene_ids, strands, regressi
     for k in range(len(scanned)):
         for v in range(V):
             vals[k, :, v] = column(logits[k, :, v])
-    scan = vals[:, :, 1:].reshape(len(scanned), n, K, W)
+    scan = vals[:, :, scan_row(0, 0, 0, K, W):].reshape(len(scanned), n, K, W)
     scan[~np.broadcast_to(live.numpy()[:, :, None, :], scan.shape)] = np.nan
     sets = np.zeros((K, F), dtype=bool)
     for k, ms in enumerate(mark_sets):
         sets[k, list(ms)] = True
-    arrays = dict(gene_ids=np.array(list(gene_ids)), mark_sets=sets, prediction=vals[0, :, 0].copy(), promoter=scan[0])
+    arrays = dict(gene_ids=np.array(list(gene_ids)), mark_sets=sets, prediction=vals[0, :, scan_row(0, None, None, K, W)].copy(), promoter=scan[0])
     if regions == "all":
         arrays["pcres"] = np.ascontiguousarray(scan[1:].transpose(1, 0, 2, 3))
     with open(path, "wb") as f:

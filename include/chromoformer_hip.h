@@ -342,6 +342,41 @@ typedef struct cf_scan_opts {
  * [0, i_max], width < 1, n_sets < 1, a negative or non-finite scale, a mark bit >= n_feats, an n_bins[r] that is no multiple of the
  * smallest, a feats_out index >= n_res, armed riders. */
 int cf_perturbation_scan(cf_handle* h, const cf_batch* batch, const cf_scan_opts* opts, float* logits, void* stream);
+/* The scan of several regions of every gene from one call, the pCRE variants slot-packed. */
+typedef struct cf_scan_regions_opts {
+    unsigned regions;           /* bit 0: the promoter; bit 1 + j: pCRE slot j.  At least one bit; no bit above i_max */
+    int width, n_sets;
+    const unsigned* mark_sets;  /* host [n_sets], as in cf_scan_opts */
+    float scale;
+    const uint8_t* flip;        /* device [B] or NULL: applies to the promoter block only (pCREs are never stored mirrored) */
+} cf_scan_regions_opts;
+/* logits: [n_reg, B, V, n_out], n_reg = the set bits of `regions`, the regions in ascending bit order, V = 1 + n_sets * W as above.
+ * Block q carries, bit for bit, what cf_perturbation_scan writes for that region with the same width, mark_sets and scale -- with
+ * flip = opts->flip for the promoter block, flip = NULL for a pCRE block.  So row v = 0 of every block is the unperturbed gene, and
+ * dead windows, empty sets and dummy slots give the baseline's bits.  There is no feats_out (cf_perturbation_scan serves that).
+ * The promoter block runs the launches of cf_perturbation_scan.  A pCRE slot j does not: its Pairwise output depends on the promoter
+ * and on slot j alone, so only row j + 1 of the Regulation input [B, T, d_emb] differs between the gene and a variant, and the S slots
+ * of a (gene, resolution) workgroup are S independent (promoter, pCRE) pairs that pass through the same operations in the same order.
+ * With any pCRE bit the trunk runs once on the B genes and its output is stashed (k_pcre_stash, the buffers of cf_pcre_ablation).
+ * Then per pCRE slot j, with U = ceil((V - 1) / S), S = i_max:
+ *   pack phase   pseudo rows (b, u), gene-major, in chunks of at most max_batch: k_scan_pack writes gene b's promoter and, into slot s,
+ *                its slot j under variant v = 1 + u * S + s (v >= V: verbatim) with slot j's pad-mask row in every slot, into the chunk
+ *                buffers of cf_integrated_gradients; the trunk part of cf_forward(save = 0) runs on the chunk (k_attc2's regions per
+ *                workgroup as for the caller's B genes); k_scan_unpack copies rows 1..S of each pseudo-gene's output to a handle-owned
+ *                buffer [n_res][B * (V - 1), d_emb] (grown on demand, freed by cf_destroy; 15.7 MB at B = 64, V = 161);
+ *   row phase    rows (b, v) in output order, in chunks of at most max_batch: k_scan_rows writes the stash back with row j + 1 taken
+ *                from that buffer for v >= 1, and the gene's interaction masks and frequencies; the Regulation + head launches of
+ *                cf_forward(save = 0) write the chunk's slice of the block.
+ * With np / nc the promoter / pCRE bits set, C = ceil(B * V / max_batch), P = ceil(B * U / max_batch):
+ *   cf_launch_counts fwd = np * C * (1 + n_fwd) + [nc > 0] * (n_trunk + 1) + nc * (P * (n_trunk + 2) + C * (1 + n_reg_head))
+ * (n_fwd = n_trunk + n_reg_head: see cf_pcre_ablation): a pCRE region issues P trunk passes, not C.  CF_SCAN_PACK=0 at cf_create runs
+ * the pCRE blocks through the launches of cf_perturbation_scan as well (the cross-check: the same bits; fwd = n_reg * C * (1 + n_fwd)).
+ * Deterministic (no atomics); the result does not depend on max_batch.  Overwrites the activations a cf_forward(save >= 1) kept: no
+ * cf_backward* may follow without a new saving forward.  Parameters, gradients and moments are untouched.
+ * Refused by name, before anything is launched: everything cf_perturbation_scan refuses (a null handle / batch / opts / logits /
+ * mark_sets, B > max_batch, width < 1, n_sets < 1, a negative or non-finite scale, a mark bit >= n_feats, non-nested n_bins, armed
+ * riders), regions == 0, a region bit above i_max. */
+int cf_perturbation_scan_regions(cf_handle* h, const cf_batch* batch, const cf_scan_regions_opts* opts, float* logits, void* stream);
 /* torch.optim.AdamW.step (train.py:157, 196): decoupled weight decay, bias correction
  * from `step` (1-based), over [0, n_active). */
 int cf_adamw_step(cf_handle* h, float lr, float beta1, float beta2, float eps, float weight_decay,
