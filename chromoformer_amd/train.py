@@ -98,14 +98,22 @@ def stepped_indices(table, freeze_trunk=False):
     return [i for i, e in enumerate(table) if e["trainable"] and not (freeze_trunk and is_trunk_name(e["name"]))]
 
 
-def optimizer_state_dict(model, lr, initial_lr=None, m_host=None, v_host=None, freeze_trunk=False):
+def optimizer_state_dict(model, lr, initial_lr=None, m_host=None, v_host=None, freeze_trunk=False, betas=None, eps=None, weight_decay=None):
     """torch.optim.AdamW.state_dict() layout: entries only for parameters that ever had a gradient,
     `step` as a 0-dim float32 tensor (train.py:325, 336).  m_host / v_host: host copies of the flat moment buffers (one
-    device-to-host copy each instead of one per tensor); default: copied here."""
+    device-to-host copy each instead of one per tensor); default: copied here.  betas / eps / weight_decay: what the run stepped with
+    where it left torch.optim.AdamW's defaults (Trainer(betas=, eps=, weight_decay=)) -- torch's load_state_dict takes the
+    hyper-parameters of the loaded param_groups, not those the receiving optimiser was built with."""
     named = list(model.named_parameters())
     ref = torch.optim.AdamW([nn.Parameter(torch.zeros(1)) for _ in named], lr=float(lr))
     sd = ref.state_dict()
     sd["param_groups"][0]["lr"] = float(lr)
+    if betas is not None:
+        sd["param_groups"][0]["betas"] = (float(betas[0]), float(betas[1]))
+    if eps is not None:
+        sd["param_groups"][0]["eps"] = float(eps)
+    if weight_decay is not None:
+        sd["param_groups"][0]["weight_decay"] = float(weight_decay)
     # the reference's optimizer has a StepLR attached (train.py:157-158), which adds this key to the group: a consumer that
     # loads the state and rebuilds the scheduler with last_epoch >= 0 needs it
     sd["param_groups"][0]["initial_lr"] = float(initial_lr if initial_lr is not None else lr)

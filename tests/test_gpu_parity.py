@@ -214,7 +214,8 @@ def test_g4_train_step_golden(reg):
     orc.train_step(P, opt, b, regression=reg)
     # the first AdamW update is u = lr * g / (|g| + eps) with du/dg = lr * eps / (|g| + eps)^2: where |g| is far
     # above eps = 1e-8 the update is insensitive to rounding noise in g (checked to 2e-7); where |g| ~ eps the
-    # noise of g (~1e-9, in the oracle as well) is amplified up to a fraction of lr = 3e-5 (bounded by 2e-5)
+    # noise of g (~1e-9, in the oracle as well) is amplified up to a fraction of lr = 3e-5 (bounded by 2e-5).  (One step from zero moments
+    # cannot see beta1, beta2 or the decay; the exact check of the update lives in tests/test_adamw_gpu.py.)
     sd = model.state_dict()
     for k in P:
         d = (sd[k].cpu() - P[k].detach()).abs()
@@ -240,7 +241,9 @@ def test_three_adamw_steps_track_oracle():
         assert abs(loss.item() - ref_loss.item()) < 2e-4
     sd = model.state_dict()
     worst = max((sd[k].cpu() - P[k].detach()).abs().max().item() for k in P)
-    assert worst < 2e-4, worst     # lr 1e-3 * 3 steps = 3e-3 of movement; sign-level agreement of the updates
+    # lr 1e-3 * 3 steps = 3e-3 of movement: this bounds how far the noise of the oracle's gradients (~1e-3 relative) carries the parameters, not
+    # the optimiser's arithmetic -- that is checked per element, to a few units of fp32 rounding, in tests/test_adamw_gpu.py
+    assert worst < 2e-4, worst
 
 
 # ------------------------------------------------------------------ full-size properties (B = 64)
