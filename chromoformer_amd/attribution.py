@@ -327,6 +327,13 @@ def scan_windows(start, end, binsize, width, n_win):
     return np.stack([lo, np.minimum(lo + int(width) * int(binsize), int(end))], axis=1).reshape(-1, 2)
 
 
+def scan_mark_sets(mark_sets, n_feats):
+    """The mark sets of a scan as a list of tuples of mark indices; None: each mark alone, then all marks together (n_feats + 1 sets)."""
+    if mark_sets is None:
+        mark_sets = [(f,) for f in range(n_feats)] + [tuple(range(n_feats))]
+    return [tuple(int(f) for f in ms) for ms in mark_sets]
+
+
 def scan_regions_expand(regions, i_max, who="perturbation_scan"):
     """The scanned regions as a sorted list of region indices (0 the promoter, 1 + j pCRE slot j): "promoter" -> [0], "all" ->
     [0 .. i_max], "pcres" -> [1 .. i_max], or an iterable of indices (duplicates dropped).  Raises ValueError on anything else."""
@@ -397,9 +404,7 @@ def perturbation_scan(model, dataset, genes=None, regions="promoter", scale=0.0,
     S, F, dev = ds.i_max, ds.n_feats, model._device
     order = scan_regions_expand(regions, S) if isinstance(regions, str) else [int(r) for r in regions]      # (the caller's order is kept)
     regions = scan_regions_expand(order, S)
-    if mark_sets is None:
-        mark_sets = [(f,) for f in range(F)] + [tuple(range(F))]
-    mark_sets = [tuple(int(f) for f in ms) for ms in mark_sets]
+    mark_sets = scan_mark_sets(mark_sets, F)
     rc = int(np.argmin(n_bins))
     W, bc = n_bins[rc], binsizes[rc]
     col0 = promoter_col0(ds)

@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -68,17 +69,15 @@ extern "C" int cf_create(const cf_config* cfg, const float* const* pe_host, cf_h
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail("cf_create: no HIP device visible -- libchromoformer_hip has no CPU fallback");
-    cf_handle* h = new cf_handle();
+    std::unique_ptr<cf_handle> owner(new cf_handle());      // (every error return below drops the handle and, through its members, the device memory)
+    cf_handle* h = owner.get();
     h->cfg = *cfg;
     {   // compute units of the current device: sizes the rows of rider workgroups that share a launch with one-per-CU workgroups
         int dev = 0, ncu = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0)
             h->n_cu = ncu;
     }
-    if (build_layout(h->cfg, h->table, h->lay)) {
-        delete h;
-        return -1;
-    }
+    if (build_layout(h->cfg, h->table, h->lay)) return -1;
     for (size_t i = 0; i < h->table.size(); ++i) h->index[h->table[i].name] = (int)i;
     {   // bucket boundary: trainable tensors are laid out in state_dict order (embed | pairwise | regulation | fc_head)
         long long split = -1, pe_end = 0;
@@ -88,10 +87,7 @@ extern "C" int cf_create(const cf_config* cfg, const float* const* pe_host, cf_h
             if (late && split < 0) split = p.offset;
             if (!late) pe_end = std::max(pe_end, p.offset + (p.numel + 3) / 4 * 4);
         }
-        if (split < 0 || pe_end > split) {
-            delete h;
-            return fail("cf_create: parameter layout does not split into [embed, pairwise | regulation, head] ranges");
-        }
+        if (split < 0 || pe_end > split) return fail("cf_create: parameter layout does not split into [embed, pairwise | regulation, head] ranges");
         h->bucket_split = split;
         h->bucket_split_hi = h->lay.n_active;
         for (const PDesc& p : h->table) {
@@ -115,23 +111,14 @@ extern "C" int cf_create(const cf_config* cfg, const float* const* pe_host, cf_h
             if (late == 0) h->n_retile_early = (int)units.size();
         }
         h->n_retile = (int)units.size();
-        if (hipMalloc(&h->tiled, h->lay.n_total * sizeof(float)) != hipSuccess ||
-            hipMalloc(&h->tiledT, h->lay.n_total * sizeof(float)) != hipSuccess ||
-            hipMalloc(&h->retile_units, units.size() * sizeof(RetileUnit)) != hipSuccess ||
-            hipMemcpy(h->retile_units, units.data(), units.size() * sizeof(RetileUnit), hipMemcpyHostToDevice) != hipSuccess) {
-            delete h;
-            return fail("cf_create: allocation of the tiled weight copy failed");
-        }
+        const char* who = "cf_create: the tiled weight copies";
+        if (h->tiled.alloc(h->lay.n_total, who) || h->tiledT.alloc(h->lay.n_total, who) || h->retile_units.upload(units, who)) return -1;
     }
     h->embed_dense = h->cfg.embed_layers > 1;
     h->planning = true;
     plan_workspace(h);
-    hipError_t e = hipMalloc(&h->arena, h->arena_floats * sizeof(float));
-    if (e != hipSuccess) {
-        delete h;
-        return fail("cf_create: hipMalloc(%zu bytes) failed: %s", h->arena_floats * sizeof(float), hipGetErrorString(e));
-    }
-    e = hipMemset(h->arena, 0, h->arena_floats * sizeof(float));
+    if (h->arena.alloc(h->arena_floats, fmt("cf_create: the workspace of %zu bytes", h->arena_floats * sizeof(float)).c_str())) return -1;
+    HIP_TRY(hipMemset(h->arena, 0, h->arena_floats * sizeof(float)));
     h->planning = false;
     plan_workspace(h);
     for (const auto& en : h->ws) h->ws_names += en.name + "\n";
@@ -148,11 +135,8 @@ extern "C" int cf_create(const cf_config* cfg, const float* const* pe_host, cf_h
         if (hipMemcpy(h->pe2[r], pe_host[r], (size_t)L * kD * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||       // rows >= L stay zero
             hipMemcpy(h->pet2[r], t2.data(), t2.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(h->pe[r], pe_host[r], (size_t)L * kD * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(h->pet[r], t.data(), (size_t)L * kD * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(h->arena);
-            delete h;
+            hipMemcpy(h->pet[r], t.data(), (size_t)L * kD * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
             return fail("cf_create: positional table upload failed");
-        }
     }
     const cf_config& c = h->cfg;
     {   // the fused Regulation kernels need up to ~150 KB of dynamic LDS
@@ -187,50 +171,21 @@ extern "C" int cf_create(const cf_config* cfg, const float* const* pe_host, cf_h
             }
         }
     }
-    if (h->embed_dense && embed_dense_alloc(h)) {      // the training path needs the all-rows buffers: allocate them now, not on the hot path
-        cf_destroy(h);
-        return -1;
-    }
+    if (h->embed_dense && embed_dense_alloc(h)) return -1;      // the training path needs the all-rows buffers: allocate them now, not on the hot path
     if (const char* e = getenv("CF_XCD_MAP")) h->xcd_map = atoi(e) != 0;
     if (const char* e = getenv("CF_ATTC_CAP")) h->attc_cap = atoi(e);
     if (const char* e = getenv("CF_ATTC1")) h->attc1 = atoi(e) != 0;
-    h->intg_trunk_once = getenv_int("CF_IG_TRUNK_ONCE", 1) != 0;
+    h->ig_trunk_once = getenv_int("CF_IG_TRUNK_ONCE", 1) != 0;
     h->scan_pack = getenv_int("CF_SCAN_PACK", 1) != 0;
     if (const char* e = getenv("CF_DEFER_RETILE")) h->defer_retile = atoi(e) != 0;
     if (const char* e = getenv("CF_HEAD_RIDE")) h->head_ride = atoi(e) != 0;
     if (const char* e = getenv("CF_XCD_REDUCE")) h->xcd_reduce = h->xcd_reduce_opt = atoi(e) != 0;
     h->n_fwd = h->n_bwd = h->n_opt = 0;      // counted at the launch sites by the first calls (cf_launch_counts)
-    *out = h;
+    *out = owner.release();
     return 0;
 }
 
-extern "C" void cf_destroy(cf_handle* h) {
-    if (!h) return;
-    if (h->arena) (void)hipFree(h->arena);
-    if (h->wg_tiles) (void)hipFree(h->wg_tiles);
-    if (h->tiled_map) (void)hipFree(h->tiled_map);
-    if (h->cs_tiles) (void)hipFree(h->cs_tiles);
-    if (h->lp_jobs) (void)hipFree(h->lp_jobs);
-    if (h->reg_tab) (void)hipFree(h->reg_tab);
-    if (h->trunk_tab) (void)hipFree(h->trunk_tab);
-    if (h->tiled) (void)hipFree(h->tiled);
-    if (h->tiledT) (void)hipFree(h->tiledT);
-    for (void* q : h->ed.owned) (void)hipFree(q);
-    if (h->retile_units) (void)hipFree(h->retile_units);
-    for (cf_handle::Replay& rp : h->replays) {
-        if (rp.first) (void)hipGraphExecDestroy(rp.first);
-        if (rp.second) (void)hipGraphExecDestroy(rp.second);
-    }
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    if (h->ride_ev) (void)hipEventDestroy(h->ride_ev);
-    if (h->abl_mem) (void)hipFree(h->abl_mem);
-    if (h->coal_tab) (void)hipFree(h->coal_tab);
-    if (h->coal_rows) (void)hipFree(h->coal_rows);
-    if (h->intg_mem) (void)hipFree(h->intg_mem);
-    if (h->intg_tab) (void)hipFree(h->intg_tab);
-    if (h->scan_xv) (void)hipFree(h->scan_xv);
-    delete h;
-}
+extern "C" void cf_destroy(cf_handle* h) { delete h; }
 
 extern "C" int cf_bind(cf_handle* h, float* params, float* grads, float* exp_avg, float* exp_avg_sq) {
     if (!h || !params) return fail("cf_bind: null handle / params");
@@ -239,12 +194,11 @@ extern "C" int cf_bind(cf_handle* h, float* params, float* grads, float* exp_avg
     h->grads = grads;
     h->m = exp_avg;
     h->v = exp_avg_sq;
-    if (resolve_refs(h)) {      // (no forward pass on half-filled references: the handle is unbound again)
+    // (no forward pass on half-filled references or tables: on failure the handle is unbound again, safe to destroy and to bind again)
+    if (resolve_refs(h) || build_reg_table(h) || build_trunk_table(h) || (grads && build_tables(h))) {
         h->params = h->grads = h->m = h->v = nullptr;
         return -1;
     }
-    if (build_reg_table(h) || build_trunk_table(h)) return -1;
-    if (grads) return build_tables(h);
     return 0;
 }
 

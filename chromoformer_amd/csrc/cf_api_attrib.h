@@ -187,56 +187,88 @@ extern "C" int cf_attention_maps(cf_handle* h, const cf_batch* bt, float* logits
     return 0;
 }
 
-// The buffers of cf_pcre_ablation and of the coalition entry points, allocated by the first call of any of them (the model's other
-// entry points never need them); the ablation's i_max + 2 coalition words (cf_coalition.h) are written here, once.
-static int ablate_alloc(cf_handle* h, const char* who) {
-    if (h->abl_mem) return 0;
+// What the chunked attribution entry points check alike, first: the handle, the batch, its size, riders where the call runs a backward
+// pass or leaves the launch sequence of a step (`no_riders`), the batch's pointers.
+static int attrib_open(cf_handle* h, const cf_batch* bt, bool no_riders, const char* who) {
+    if (!h) return fail("%s: null handle", who);
+    if (!bt) return fail("%s: null batch", who);
+    if (bt->B > h->cfg.max_batch) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, h->cfg.max_batch);
+    if (no_riders && (h->rider.armed || h->rider.done)) return fail("%s: riders are armed for a training step (cf_rider_arm); finish the step first", who);
+    return check_batch(h, bt);
+}
+
+// The chunk workspace (cf_handle::AttribWs), allocated by the first attribution call that needs chunk buffers (the model's other entry
+// points never do): the chunk's rows and per-row gradients, the three mask sets, one stash, the chunk logits, the per-slice sums and the
+// i_max + 2 coalition words of cf_pcre_ablation (cf_coalition.h), written here, once -- a call copies nothing from the host.
+static int attrib_ws(cf_handle* h, const char* who) {
+    cf_handle::AttribWs& w = h->aw;
+    if (w.mem) return 0;
     const cf_config& c = h->cfg;
-    const size_t T = c.i_max + 1, rows = (size_t)c.max_batch * T, x0 = rows * c.d_emb, tt = (size_t)c.max_batch * T * T;
-    const size_t freq_off = c.n_res * x0, tab_off = freq_off + tt, mask_off = tab_off + T + 1;      // (floats; the masks follow as bytes)
-    void* q = nullptr;
-    if (hipMalloc(&q, mask_off * sizeof(float) + c.n_res * tt) != hipSuccess) return fail("%s: out of memory", who);
-    float* f = (float*)q;
+    const size_t M = c.max_batch, S = c.i_max, T = S + 1, F = c.n_feats;
+    size_t nf = 0, nb = 0;      // floats, then bytes (every float segment a multiple of 4 floats: 16-byte aligned rows)
+    auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
+    for (int r = 0; r < c.n_res; ++r) nf += 2 * up4(M * c.n_bins[r] * F) + 2 * up4(M * S * c.n_bins[r] * F) + up4(M * T * c.d_emb);
+    nf += 2 * up4(M * T * T) + up4(M * c.n_out) + up4(M * kIgSlices) + up4(T + 1);
+    // (the all-rows Embedding reads every row of a full [B, L, L] promoter mask: its chunks keep L rows per chunk row)
+    auto pm_rows = [&](int r) { return h->embed_dense ? (size_t)c.n_bins[r] : (size_t)1; };
+    for (int r = 0; r < c.n_res; ++r) nb += M * pm_rows(r) * c.n_bins[r] + M * S * c.n_bins[r] + M * T * T;
+    DevBuf<float> mem;
+    if (mem.alloc(nf + (nb + 3) / 4, who)) return -1;
+    float* f = mem;
+    auto take = [&](size_t n) { float* p = f; f += up4(n); return p; };
+    for (int r = 0; r < c.n_res; ++r) {
+        const size_t L = c.n_bins[r];
+        w.row[r] = take(M * L * F);
+        w.grad[r] = take(M * L * F);
+        w.row[kMaxRes + r] = take(M * S * L * F);
+        w.grad[kMaxRes + r] = take(M * S * L * F);
+        w.stash[r] = take(M * T * c.d_emb);
+    }
+    w.row[2 * kMaxRes] = take(M * T * T);
+    w.grad[2 * kMaxRes] = take(M * T * T);
+    w.logits = take(M * c.n_out);
+    w.slice_sums = take(M * kIgSlices);
+    float* words_at = take(T + 1);
+    uint8_t* u = (uint8_t*)f;
+    for (int r = 0; r < c.n_res; ++r) {
+        const size_t L = c.n_bins[r];
+        w.pmask[r] = u, u += M * pm_rows(r) * L;
+        w.cmask[r] = u, u += M * S * L;
+        w.imask[r] = u, u += M * T * T;
+    }
     const unsigned N = (1u << c.i_max) - 1u;
-    std::vector<unsigned> words(T + 1, N);
+    std::vector<unsigned> words(T + 1, N);      // everything kept | slot j deleted | nothing kept
     for (int j = 0; j < c.i_max; ++j) words[1 + j] = N & ~(1u << j);
     words[T] = 0;
-    if (hipMemcpy(f + tab_off, words.data(), (T + 1) * sizeof(unsigned), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(q);
-        return fail("%s: writing the deletion table failed", who);
-    }
-    h->abl_mem = q;
-    for (int r = 0; r < c.n_res; ++r) {
-        h->abl_stash[r] = f + r * x0;
-        h->abl_mask[r] = (uint8_t*)(f + mask_off) + r * tt;
-    }
-    h->abl_freq = f + freq_off;
-    h->abl_tab = (const unsigned*)(f + tab_off);
+    if (hipMemcpy(words_at, words.data(), (T + 1) * sizeof(unsigned), hipMemcpyHostToDevice) != hipSuccess)
+        return fail("%s: writing the deletion table failed", who);      // (`mem` frees itself; the workspace stays unallocated)
+    w.deletion_words = (const unsigned*)words_at;
+    w.mem = std::move(mem);
     return 0;
 }
 
 // The shared host routine of cf_pcre_ablation and the coalition entry points (cf_coalition.h): the trunk once on the B genes,
 // k_pcre_stash, then per chunk of at most max_batch of the B * n_coal rows (gene-major; row (b, k) is word tab[k], a device table) one
 // k_coalition_expand and the Regulation + head launches of an inference forward on that chunk, writing the chunk's contiguous slice of
-// `logits`.  The callers have checked the batch and called ablate_alloc.
+// `logits`.  The callers have checked the batch and called attrib_ws.
 static int coalition_rows(cf_handle* h, const cf_batch* bt, const unsigned* tab, int n_coal, float* logits, hipStream_t st) {
     const cf_config& c = h->cfg;
     const int B = bt->B, T = c.i_max + 1, nres = c.n_res, cap = c.max_batch;
     const long long launches0 = g_launches;
-    if (forward_trunk(h, bt, 0, st) || stash_trunk_output(h, B, h->abl_stash, st)) return -1;
+    if (forward_trunk(h, bt, 0, st) || stash_trunk_output(h, B, h->aw.stash, st)) return -1;
     CoalExpandArgs ea;
     memset(&ea, 0, sizeof ea);
     cf_batch cb = *bt;      // the chunk's batch: only B, the masks and the frequencies are read past the trunk
     for (int r = 0; r < nres; ++r) {
-        ea.stash[r] = reinterpret_cast<const float4*>(h->abl_stash[r]);
+        ea.stash[r] = reinterpret_cast<const float4*>(h->aw.stash[r]);
         ea.x0[r] = reinterpret_cast<float4*>(h->Rx[r][0]);
         ea.mask_in[r] = bt->interaction_mask[r];
-        ea.mask_out[r] = h->abl_mask[r];
-        cb.interaction_mask[r] = h->abl_mask[r];
+        ea.mask_out[r] = h->aw.imask[r];
+        cb.interaction_mask[r] = h->aw.imask[r];
     }
     ea.freq_in = bt->interaction_freq;
-    ea.freq_out = h->abl_freq;
-    cb.interaction_freq = h->abl_freq;
+    ea.freq_out = h->aw.row[2 * kMaxRes];
+    cb.interaction_freq = h->aw.row[2 * kMaxRes];
     ea.keep = tab;
     ea.n_coal = n_coal, ea.T = T, ea.row4 = T * c.d_emb / 4;
     const long long rows = (long long)B * n_coal;
@@ -252,78 +284,55 @@ static int coalition_rows(cf_handle* h, const cf_batch* bt, const unsigned* tab,
     return 0;
 }
 
-// The fixed table of ablate_alloc through coalition_rows: variant v of gene b is row (b, v).
+// The fixed table of attrib_ws through coalition_rows: variant v of gene b is row (b, v).
 extern "C" int cf_pcre_ablation(cf_handle* h, const cf_batch* bt, float* logits, void* stream) {
     const char* who = "cf_pcre_ablation";
-    if (!h) return fail("%s: null handle", who);
-    if (!bt) return fail("%s: null batch", who);
+    if (attrib_open(h, bt, false, who)) return -1;
     if (!logits) return fail("%s: null logits", who);
-    if (bt->B > h->cfg.max_batch) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, h->cfg.max_batch);
-    if (check_batch(h, bt) || ablate_alloc(h, who)) return -1;
-    return coalition_rows(h, bt, h->abl_tab, h->cfg.i_max + 2, logits, (hipStream_t)stream);
+    if (attrib_ws(h, who)) return -1;
+    return coalition_rows(h, bt, h->aw.deletion_words, h->cfg.i_max + 2, logits, (hipStream_t)stream);
 }
 
-// A host `keep` array validated and uploaded into the handle's device table (in front of coalition_rows); checks the batch.
-static int coalition_upload(cf_handle* h, const cf_batch* bt, const uint32_t* keep, int n_coal, hipStream_t st, const char* who) {
+// A host `keep` array validated and uploaded into the handle's word table (in front of coalition_rows).
+static int coalition_upload(cf_handle* h, const uint32_t* keep, int n_coal, hipStream_t st, const char* who) {
     const cf_config& c = h->cfg;
-    if (bt->B > c.max_batch) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, c.max_batch);
     if (n_coal < 1) return fail("%s: n_coal = %d: at least 1 coalition", who, n_coal);
     if (!keep) return fail("%s: null keep", who);
     for (int k = 0; k < n_coal; ++k)
         if (keep[k] >> c.i_max) return fail("%s: keep[%d] = 0x%x names a pCRE slot >= i_max = %d", who, k, keep[k], c.i_max);
-    if (check_batch(h, bt) || ablate_alloc(h, who)) return -1;
-    if (n_coal > h->coal_cap) {
-        const long long want = std::max<long long>(n_coal, 256);
-        if (h->coal_tab) (void)hipFree(h->coal_tab);      // (synchronises: a call in flight may still read the old table)
-        h->coal_tab = nullptr;
-        h->coal_cap = 0;
-        if (hipMalloc(&h->coal_tab, (size_t)want * sizeof(unsigned)) != hipSuccess) return fail("%s: out of memory", who);
-        h->coal_cap = want;
-    }
-    HIP_TRY(hipMemcpyAsync(h->coal_tab, keep, (size_t)n_coal * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    if (attrib_ws(h, who) || h->aw.words.need(n_coal, 256, who)) return -1;
+    HIP_TRY(hipMemcpyAsync(h->aw.words, keep, (size_t)n_coal * sizeof(unsigned), hipMemcpyHostToDevice, st));
     return 0;
 }
 
 extern "C" int cf_pcre_coalitions(cf_handle* h, const cf_batch* bt, const uint32_t* keep, int n_coal, float* logits, void* stream) {
     const char* who = "cf_pcre_coalitions";
-    if (!h) return fail("%s: null handle", who);
-    if (!bt) return fail("%s: null batch", who);
+    if (attrib_open(h, bt, false, who)) return -1;
     if (!logits) return fail("%s: null logits", who);
     hipStream_t st = (hipStream_t)stream;
-    if (coalition_upload(h, bt, keep, n_coal, st, who)) return -1;
-    return coalition_rows(h, bt, h->coal_tab, n_coal, logits, st);
+    if (coalition_upload(h, keep, n_coal, st, who)) return -1;
+    return coalition_rows(h, bt, h->aw.words, n_coal, logits, st);
 }
 
-// The rows of a Shapley / epistasis call whose caller gave no buffer: [max_batch, per, n_out], allocated by the first such call.
-static float* coalition_own_rows(cf_handle* h, long long per, const char* who) {
-    if (per > h->coal_rows_per) {
-        if (h->coal_rows) (void)hipFree(h->coal_rows);      // (synchronises)
-        h->coal_rows = nullptr;
-        h->coal_rows_per = 0;
-        if (hipMalloc(&h->coal_rows, (size_t)h->cfg.max_batch * per * h->cfg.n_out * sizeof(float)) != hipSuccess) {
-            fail("%s: out of memory", who);
-            return nullptr;
-        }
-        h->coal_rows_per = per;
-    }
-    return h->coal_rows;
+// The rows of a Shapley / epistasis call: the caller's buffer, else the handle's own [max_batch, per, n_out] (null: out of memory)
+static float* coalition_out_rows(cf_handle* h, float* callers, long long per, const char* who) {
+    if (callers) return callers;
+    return h->aw.own_rows.need((size_t)h->cfg.max_batch * per * h->cfg.n_out, 0, who) ? nullptr : (float*)h->aw.own_rows;
 }
 
 // All 2^i_max coalitions through coalition_upload + coalition_rows (word m at column m), then k_shapley.
 extern "C" int cf_pcre_shapley(cf_handle* h, const cf_batch* bt, float* phi, float* logits_all, void* stream) {
     const char* who = "cf_pcre_shapley";
-    if (!h) return fail("%s: null handle", who);
-    if (!bt) return fail("%s: null batch", who);
+    if (attrib_open(h, bt, false, who)) return -1;
     if (!phi) return fail("%s: null phi", who);
     const cf_config& c = h->cfg;
-    if (bt->B > c.max_batch) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, c.max_batch);
     const int S = c.i_max, n = 1 << S;
-    float* rows = logits_all ? logits_all : coalition_own_rows(h, n, who);
+    float* rows = coalition_out_rows(h, logits_all, n, who);
     if (!rows) return -1;
     std::vector<uint32_t> keep(n);
     for (int m = 0; m < n; ++m) keep[m] = (uint32_t)m;
     hipStream_t st = (hipStream_t)stream;
-    if (coalition_upload(h, bt, keep.data(), n, st, who) || coalition_rows(h, bt, h->coal_tab, n, rows, st)) return -1;
+    if (coalition_upload(h, keep.data(), n, st, who) || coalition_rows(h, bt, h->aw.words, n, rows, st)) return -1;
     ShapleyArgs sa;
     memset(&sa, 0, sizeof sa);
     sa.v = rows, sa.phi = phi, sa.S = S, sa.n_out = c.n_out;
@@ -339,11 +348,9 @@ extern "C" int cf_pcre_shapley(cf_handle* h, const cf_batch* bt, float* phi, flo
 // The 1 + S + S (S - 1) / 2 pair-deletion coalitions through coalition_upload + coalition_rows, then k_epistasis.
 extern "C" int cf_pcre_epistasis(cf_handle* h, const cf_batch* bt, float* eps, float* logits_pairs, void* stream) {
     const char* who = "cf_pcre_epistasis";
-    if (!h) return fail("%s: null handle", who);
-    if (!bt) return fail("%s: null batch", who);
+    if (attrib_open(h, bt, false, who)) return -1;
     if (!eps) return fail("%s: null eps", who);
     const cf_config& c = h->cfg;
-    if (bt->B > c.max_batch) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, c.max_batch);
     const int S = c.i_max;
     const uint32_t N = (1u << S) - 1u;
     std::vector<uint32_t> keep;
@@ -352,10 +359,10 @@ extern "C" int cf_pcre_epistasis(cf_handle* h, const cf_batch* bt, float* eps, f
     for (int i = 0; i < S; ++i)
         for (int j = i + 1; j < S; ++j) keep.push_back(N & ~(1u << i) & ~(1u << j));
     const int R = (int)keep.size();
-    float* rows = logits_pairs ? logits_pairs : coalition_own_rows(h, R, who);
+    float* rows = coalition_out_rows(h, logits_pairs, R, who);
     if (!rows) return -1;
     hipStream_t st = (hipStream_t)stream;
-    if (coalition_upload(h, bt, keep.data(), R, st, who) || coalition_rows(h, bt, h->coal_tab, R, rows, st)) return -1;
+    if (coalition_upload(h, keep.data(), R, st, who) || coalition_rows(h, bt, h->aw.words, R, rows, st)) return -1;
     EpistasisArgs ea;
     ea.v = rows, ea.eps = eps, ea.B = bt->B, ea.S = S, ea.n_out = c.n_out;
     const long long n = (long long)bt->B * S * S * c.n_out;
@@ -365,57 +372,9 @@ extern "C" int cf_pcre_epistasis(cf_handle* h, const cf_batch* bt, float* eps, f
     return 0;
 }
 
-// The buffers of cf_integrated_gradients, allocated by its first call; the node / weight table grows with n_steps.
-static int intg_alloc(cf_handle* h, int n_steps) {
-    const cf_config& c = h->cfg;
-    const size_t M = c.max_batch, S = c.i_max, T = S + 1, F = c.n_feats;
-    if (!h->intg_mem) {
-        size_t nf = 0, nb = 0;      // floats, then bytes (every float segment a multiple of 4 floats: 16-byte aligned rows)
-        auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
-        for (int r = 0; r < c.n_res; ++r) nf += 2 * up4(M * c.n_bins[r] * F) + 2 * up4(M * S * c.n_bins[r] * F) + up4(M * T * c.d_emb);
-        nf += 2 * up4(M * T * T) + up4(M * c.n_out) + up4(M * kIgSlices);
-        // (the all-rows Embedding reads every row of a full [B, L, L] promoter mask: its chunks keep L rows per chunk row)
-        auto pm_rows = [&](int r) { return h->embed_dense ? (size_t)c.n_bins[r] : (size_t)1; };
-        for (int r = 0; r < c.n_res; ++r) nb += M * pm_rows(r) * c.n_bins[r] + M * S * c.n_bins[r] + M * T * T;
-        void* q = nullptr;
-        if (hipMalloc(&q, nf * sizeof(float) + nb) != hipSuccess) return fail("cf_integrated_gradients: out of memory");
-        h->intg_mem = q;
-        float* f = (float*)q;
-        auto take = [&](size_t n) { float* p = f; f += up4(n); return p; };
-        for (int r = 0; r < c.n_res; ++r) {
-            const size_t L = c.n_bins[r];
-            h->intg_row[r] = take(M * L * F);
-            h->intg_grad[r] = take(M * L * F);
-            h->intg_row[kMaxRes + r] = take(M * S * L * F);
-            h->intg_grad[kMaxRes + r] = take(M * S * L * F);
-            h->intg_stash[r] = take(M * T * c.d_emb);
-        }
-        h->intg_row[2 * kMaxRes] = take(M * T * T);
-        h->intg_grad[2 * kMaxRes] = take(M * T * T);
-        h->intg_logits = take(M * c.n_out);
-        h->intg_part = take(M * kIgSlices);
-        uint8_t* u = (uint8_t*)f;
-        for (int r = 0; r < c.n_res; ++r) {
-            const size_t L = c.n_bins[r];
-            h->intg_pm[r] = u, u += M * pm_rows(r) * L;
-            h->intg_cm[r] = u, u += M * S * L;
-            h->intg_im[r] = u, u += M * T * T;
-        }
-    }
-    if (n_steps > h->intg_cap) {
-        const int cap = std::max(n_steps, 64);
-        if (h->intg_tab) (void)hipFree(h->intg_tab);      // (synchronises: a call in flight may still read the old table)
-        h->intg_tab = nullptr;
-        h->intg_cap = 0;
-        if (hipMalloc(&h->intg_tab, 2 * (size_t)cap * sizeof(float)) != hipSuccess) return fail("cf_integrated_gradients: out of memory");
-        h->intg_cap = cap;
-    }
-    return 0;
-}
-
-// A chunk of rows in the intg_* buffers (cf_integrated_gradients, cf_perturbation_scan): the chunk's batch `cb` (all but B) and the
+// A chunk of rows in the workspace (cf_integrated_gradients, the scans): the chunk's batch `cb` (all but B) and the
 // description `ra` of the mask rows its expand kernel copies from the caller's batch (cf_rows.h).
-static void intg_chunk_rows(cf_handle* h, const cf_batch* bt, RowCopyArgs* ra, cf_batch* cb) {
+static void chunk_rows(cf_handle* h, const cf_batch* bt, RowCopyArgs* ra, cf_batch* cb) {
     const cf_config& c = h->cfg;
     memset(ra, 0, sizeof *ra);
     memset(cb, 0, sizeof *cb);
@@ -429,20 +388,20 @@ static void intg_chunk_rows(cf_handle* h, const cf_batch* bt, RowCopyArgs* ra, c
         ra->cm_in[r] = bt->pcre_mask_row[r];
         ra->pm_stride[r] = bt->promoter_mask_stride[r];
         ra->cm_stride[r] = bt->pcre_mask_stride[r];
-        ra->pm_out[r] = h->intg_pm[r];
-        ra->cm_out[r] = h->intg_cm[r];
+        ra->pm_out[r] = h->aw.pmask[r];
+        ra->cm_out[r] = h->aw.cmask[r];
         ra->im_in[r] = bt->interaction_mask[r];
-        ra->im_out[r] = h->intg_im[r];
+        ra->im_out[r] = h->aw.imask[r];
         ra->L[r] = L;
-        cb->promoter_feats[r] = h->intg_row[r];
-        cb->pcre_feats[r] = h->intg_row[kMaxRes + r];
-        cb->promoter_mask_row[r] = h->intg_pm[r] + (pm_full ? (size_t)(L / 2) * L : 0);
+        cb->promoter_feats[r] = h->aw.row[r];
+        cb->pcre_feats[r] = h->aw.row[kMaxRes + r];
+        cb->promoter_mask_row[r] = h->aw.pmask[r] + (pm_full ? (size_t)(L / 2) * L : 0);
         cb->promoter_mask_stride[r] = pm_full ? (long long)L * L : L;
-        cb->pcre_mask_row[r] = h->intg_cm[r];
+        cb->pcre_mask_row[r] = h->aw.cmask[r];
         cb->pcre_mask_stride[r] = L;
-        cb->interaction_mask[r] = h->intg_im[r];
+        cb->interaction_mask[r] = h->aw.imask[r];
     }
-    cb->interaction_freq = h->intg_row[2 * kMaxRes];
+    cb->interaction_freq = h->aw.row[2 * kMaxRes];
     ra->S = c.i_max;
     ra->TT = (c.i_max + 1) * (c.i_max + 1);
 }
@@ -459,8 +418,7 @@ static void intg_chunk_rows(cf_handle* h, const cf_batch* bt, RowCopyArgs* ra, c
 // the optional second output `coeff`); everything else -- chunking, buffers, launches -- is shared.
 static int integrated_gradients_impl(cf_handle* h, const cf_batch* bt, const cf_ig_opts* o, const cf_input_grads* out, const cf_input_grads* coeff,
                                      float* logits_x, float* logits_base, float* delta, void* stream, bool raw, const char* who) {
-    if (!h) return fail("%s: null handle", who);
-    if (!bt) return fail("%s: null batch", who);
+    if (attrib_open(h, bt, true, who)) return -1;
     if (!o) return fail("%s: null opts", who);
     if (!out) return fail("%s: null out", who);
     if (!logits_x || !logits_base || !delta) return fail("%s: null logits_x / logits_base / delta", who);
@@ -471,7 +429,6 @@ static int integrated_gradients_impl(cf_handle* h, const cf_batch* bt, const cf_
     if (o->target < 0 || o->target >= c.n_out) return fail("%s: target = %d outside [0, n_out = %d)", who, o->target, c.n_out);
     if (o->interpolate & ~(CF_IG_PROMOTER | CF_IG_PCRE | CF_IG_FREQ) || !o->interpolate)
         return fail("%s: interpolate = %d: a non-empty mask of CF_IG_PROMOTER | CF_IG_PCRE | CF_IG_FREQ", who, o->interpolate);
-    if (bt->B > cap) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, cap);
     const bool ip = o->interpolate & CF_IG_PROMOTER, ic = o->interpolate & CF_IG_PCRE, ifr = o->interpolate & CF_IG_FREQ;
     if (raw) {
         if (!ip && !ic) return fail("%s: interpolate = %d: the signal path needs CF_IG_PROMOTER or CF_IG_PCRE (frequencies alone: cf_integrated_gradients)", who, o->interpolate);
@@ -499,48 +456,48 @@ static int integrated_gradients_impl(cf_handle* h, const cf_batch* bt, const cf_
     if (ifr && h->reg_fused && !h->reg_dfreq_ok)
         return fail("%s: interaction_freq: the fused Regulation backward variant could not be configured", who);
     if (!h->grads) return fail("%s: no gradient buffer bound (the backward workspace is set up by cf_bind; the buffer is not written)", who);
-    if (h->rider.armed || h->rider.done) return fail("%s: riders are armed for a training step (cf_rider_arm); finish the step first", who);
-    if (check_batch(h, bt)) return -1;
     const size_t smem = ip || ic ? input_grad_prepare(h, who) : 0;
     if ((ip || ic) && !smem) return -1;
-    if (intg_alloc(h, o->n_steps)) return -1;
-    hipStream_t st = (hipStream_t)stream;
     const int B = bt->B, n = o->n_steps, V = n + 2, TT = T * T;
-    const bool freq_only = o->interpolate == CF_IG_FREQ && h->intg_trunk_once;      // (never on the signal path: a feature bit is set)
-    HIP_TRY(hipMemcpyAsync(h->intg_tab, o->alphas, n * sizeof(float), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->intg_tab + h->intg_cap, o->weights, n * sizeof(float), hipMemcpyHostToDevice, st));
+    if (attrib_ws(h, who) || h->aw.words.need(2 * (size_t)n, 128, who)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    float* const alpha = reinterpret_cast<float*>((unsigned*)h->aw.words);      // the word table as [nodes | weights]
+    float* const weight = alpha + n;
+    const bool freq_only = o->interpolate == CF_IG_FREQ && h->ig_trunk_once;      // (never on the signal path: a feature bit is set)
+    HIP_TRY(hipMemcpyAsync(alpha, o->alphas, n * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(weight, o->weights, n * sizeof(float), hipMemcpyHostToDevice, st));
     long long n_fwd = 0, n_bwd = 0;
     IgExpandArgs ea;
     IgAccArgs aa;
     memset(&ea, 0, sizeof ea);
     memset(&aa, 0, sizeof aa);
     cf_batch cb;      // the chunk's batch: the rows' copies
-    intg_chunk_rows(h, bt, &ea.rows, &cb);
+    chunk_rows(h, bt, &ea.rows, &cb);
     for (int r = 0; r < nres; ++r) {
         const int L = c.n_bins[r];
         IgSeg* sp = &ea.seg[r];
         IgSeg* sc = &ea.seg[kMaxRes + r];
-        *sp = IgSeg{bt->promoter_feats[r], o->base_promoter_feats[r], h->intg_row[r], h->intg_grad[r], out->promoter_feats[r], L * F};
-        *sc = IgSeg{bt->pcre_feats[r], o->base_pcre_feats[r], h->intg_row[kMaxRes + r], h->intg_grad[kMaxRes + r], out->pcre_feats[r], S * L * F};
-        ea.stash[r] = reinterpret_cast<const float4*>(h->intg_stash[r]);
+        *sp = IgSeg{bt->promoter_feats[r], o->base_promoter_feats[r], h->aw.row[r], h->aw.grad[r], out->promoter_feats[r], L * F};
+        *sc = IgSeg{bt->pcre_feats[r], o->base_pcre_feats[r], h->aw.row[kMaxRes + r], h->aw.grad[kMaxRes + r], out->pcre_feats[r], S * L * F};
+        ea.stash[r] = reinterpret_cast<const float4*>(h->aw.stash[r]);
         ea.x0[r] = reinterpret_cast<float4*>(h->Rx[r][0]);
     }
-    ea.seg[2 * kMaxRes] = IgSeg{bt->interaction_freq, o->base_interaction_freq, h->intg_row[2 * kMaxRes], h->intg_grad[2 * kMaxRes], out->interaction_freq, TT};
-    ea.alpha = h->intg_tab;
-    ea.weight = h->intg_tab + h->intg_cap;
+    ea.seg[2 * kMaxRes] = IgSeg{bt->interaction_freq, o->base_interaction_freq, h->aw.row[2 * kMaxRes], h->aw.grad[2 * kMaxRes], out->interaction_freq, TT};
+    ea.alpha = alpha;
+    ea.weight = weight;
     ea.dlogits = h->dlogits;
     ea.V = V, ea.n_out = c.n_out, ea.target = o->target, ea.nres = nres, ea.bcast = o->base_broadcast ? 1 : 0;
     ea.freq_only = freq_only ? 1 : 0;
     ea.row4 = T * kD / 4;
     memcpy(aa.seg, ea.seg, sizeof aa.seg);
-    aa.logits = h->intg_logits;
+    aa.logits = h->aw.logits;
     aa.logits_x = logits_x;
     aa.logits_b = logits_base;
-    aa.part = h->intg_part;
+    aa.part = h->aw.slice_sums;
     aa.V = V, aa.n_out = c.n_out, aa.bcast = ea.bcast;
     IgAccRawArgs ra;
     memset(&ra, 0, sizeof ra);
-    ra.alpha = h->intg_tab;
+    ra.alpha = alpha;
     if (raw && coeff)
         for (int r = 0; r < nres; ++r) ra.coeff[r] = coeff->promoter_feats[r], ra.coeff[kMaxRes + r] = coeff->pcre_feats[r];
     // k_attc2 takes as many regions per workgroup as for the caller's B genes; the all-rows Embedding backward writes parameter gradients: not run
@@ -552,7 +509,7 @@ static int integrated_gradients_impl(cf_handle* h, const cf_batch* bt, const cf_
     auto run = [&]() -> int {
         long long l0 = g_launches;
         if (freq_only) {      // the trunk once on the B genes, its output (the Regulation input) stashed
-            if (forward_trunk(h, bt, 1, st, B) || stash_trunk_output(h, B, h->intg_stash, st)) return -1;
+            if (forward_trunk(h, bt, 1, st, B) || stash_trunk_output(h, B, h->aw.stash, st)) return -1;
         }
         n_fwd += g_launches - l0;
         for (int g0 = 0; g0 < B * V; g0 += cap) {
@@ -567,16 +524,16 @@ static int integrated_gradients_impl(cf_handle* h, const cf_batch* bt, const cf_
                 LAUNCH_CHECK("k_ig_expand");
             }
             cb.B = nr;
-            if ((!freq_only && forward_trunk(h, &cb, 1, st, B)) || forward_reg_head(h, &cb, h->intg_logits, 1, st, nullptr)) return -1;
+            if ((!freq_only && forward_trunk(h, &cb, 1, st, B)) || forward_reg_head(h, &cb, h->aw.logits, 1, st, nullptr)) return -1;
             n_fwd += g_launches - l0;
             l0 = g_launches;
             if (backward_impl(h, &cb, st, freq_only ? 3 : 7, nullptr, 1.f, nullptr, po)) return -1;
             if (ip || ic) {
-                if (launch_input_grad(h, cb, nr, ip ? h->intg_grad : no_grad, ic ? h->intg_grad + kMaxRes : no_grad, smem, st)) return -1;
+                if (launch_input_grad(h, cb, nr, ip ? h->aw.grad : no_grad, ic ? h->aw.grad + kMaxRes : no_grad, smem, st)) return -1;
             }
             if (ifr) {
                 const int ne = nr * TT;
-                hipLaunchKernelGGL(k_dfreq_sum, dim3((ne + 255) / 256), dim3(256), 0, st, h->dfreq_part, h->intg_grad[2 * kMaxRes], ne, nres);
+                hipLaunchKernelGGL(k_dfreq_sum, dim3((ne + 255) / 256), dim3(256), 0, st, h->dfreq_part, h->aw.grad[2 * kMaxRes], ne, nres);
                 LAUNCH_CHECK("k_dfreq_sum");
             }
             aa.g0 = g0;
@@ -593,7 +550,7 @@ static int integrated_gradients_impl(cf_handle* h, const cf_batch* bt, const cf_
             n_bwd += g_launches - l0;
         }
         l0 = g_launches;
-        hipLaunchKernelGGL(k_ig_delta, dim3((B + 63) / 64), dim3(64), 0, st, h->intg_part, logits_x, logits_base, delta, B, c.n_out, o->target);
+        hipLaunchKernelGGL(k_ig_delta, dim3((B + 63) / 64), dim3(64), 0, st, h->aw.slice_sums, logits_x, logits_base, delta, B, c.n_out, o->target);
         LAUNCH_CHECK("k_ig_delta");
         n_bwd += g_launches - l0;
         return 0;
@@ -621,7 +578,7 @@ extern "C" int cf_integrated_gradients_raw(cf_handle* h, const cf_batch* bt, con
 }
 
 // What the two scan entry points check alike, in front of anything launched.  scan_check: the window, the mark sets, the scale, nested
-// bin counts (*rc_out: the coarsest resolution); scan_check_state: riders, the batch, and the chunk buffers are allocated.
+// bin counts (*rc_out: the coarsest resolution); scan_upload_sets: the workspace is allocated and holds the mark sets.
 static int scan_check(cf_handle* h, int width, int n_sets, const unsigned* mark_sets, float scale, const char* who, int* rc_out) {
     const cf_config& c = h->cfg;
     const int nres = c.n_res, F = c.n_feats;
@@ -639,16 +596,15 @@ static int scan_check(cf_handle* h, int width, int n_sets, const unsigned* mark_
     *rc_out = rc;
     return 0;
 }
-static int scan_check_state(cf_handle* h, const cf_batch* bt, int n_sets, const char* who) {
-    if (h->rider.armed || h->rider.done) return fail("%s: riders are armed for a training step (cf_rider_arm); finish the step first", who);
-    if (check_batch(h, bt)) return -1;
-    return intg_alloc(h, n_sets);
+static int scan_upload_sets(cf_handle* h, const unsigned* mark_sets, int n_sets, hipStream_t st, const char* who) {
+    if (attrib_ws(h, who) || h->aw.words.need(n_sets, 128, who)) return -1;
+    HIP_TRY(hipMemcpyAsync(h->aw.words, mark_sets, n_sets * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    return 0;
 }
 
 // One region of a scan, every row through the whole forward.  Per chunk of at most max_batch of the B * V rows (V = 1 + n_sets * W,
-// gene-major): k_scan_expand into the chunk buffers of cf_integrated_gradients (whichever call comes first allocates them; the mark
-// sets travel in its node table, uploaded by the caller), then the launches of cf_forward(save = 0) on the chunk, writing its slice of
-// `logits`.  k_attc2 takes as many regions per workgroup as for the caller's B genes (ag_genes): the result does not depend on
+// gene-major): k_scan_expand into the chunk workspace (the mark sets are in its word table, uploaded by the caller), then the launches
+// of cf_forward(save = 0) on the chunk, writing its slice of `logits`.  k_attc2 takes as many regions per workgroup as for the caller's B genes (ag_genes): the result does not depend on
 // max_batch and row (b, v) carries the bits of cf_forward(save = 0) on the batch with the perturbed features substituted.
 static int scan_region_rows(cf_handle* h, const cf_batch* bt, const cf_scan_opts* o, int rc, float* logits, hipStream_t st) {
     const cf_config& c = h->cfg;
@@ -657,12 +613,12 @@ static int scan_region_rows(cf_handle* h, const cf_batch* bt, const cf_scan_opts
     ScanExpandArgs ea;
     memset(&ea, 0, sizeof ea);
     cf_batch cb;      // the chunk's batch: the rows' copies
-    intg_chunk_rows(h, bt, &ea.rows, &cb);
+    chunk_rows(h, bt, &ea.rows, &cb);
     for (int r = 0; r < nres; ++r) {
         ea.pf_in[r] = bt->promoter_feats[r];
         ea.cf_in[r] = bt->pcre_feats[r];
-        ea.pf_out[r] = h->intg_row[r];
-        ea.cf_out[r] = h->intg_row[kMaxRes + r];
+        ea.pf_out[r] = h->aw.row[r];
+        ea.cf_out[r] = h->aw.row[kMaxRes + r];
         ea.feats_out[r] = o->feats_out[r];
         if (slot < 0) {
             ea.rm_in[r] = bt->promoter_mask_row[r];
@@ -673,8 +629,8 @@ static int scan_region_rows(cf_handle* h, const cf_batch* bt, const cf_scan_opts
         }
     }
     ea.freq_in = bt->interaction_freq;
-    ea.freq_out = h->intg_row[2 * kMaxRes];
-    ea.sets = reinterpret_cast<const unsigned*>(h->intg_tab);
+    ea.freq_out = h->aw.row[2 * kMaxRes];
+    ea.sets = h->aw.words;
     ea.flip = o->flip;
     ea.scale = o->scale;
     ea.V = V, ea.F = F, ea.W = W, ea.width = o->width, ea.rc = rc, ea.region = o->region;
@@ -692,21 +648,18 @@ static int scan_region_rows(cf_handle* h, const cf_batch* bt, const cf_scan_opts
 // In-silico perturbation scan of one region (cf_scan.h): scan_region_rows.
 extern "C" int cf_perturbation_scan(cf_handle* h, const cf_batch* bt, const cf_scan_opts* o, float* logits, void* stream) {
     const char* who = "cf_perturbation_scan";
-    if (!h) return fail("%s: null handle", who);
-    if (!bt) return fail("%s: null batch", who);
+    if (attrib_open(h, bt, true, who)) return -1;
     if (!o) return fail("%s: null opts", who);
     if (!logits) return fail("%s: null logits", who);
     if (!o->mark_sets) return fail("%s: null mark_sets", who);
     const cf_config& c = h->cfg;
-    if (bt->B > c.max_batch) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, c.max_batch);
     if (o->region < 0 || o->region > c.i_max) return fail("%s: region = %d outside [0, i_max = %d]", who, o->region, c.i_max);
     int rc = 0;
     if (scan_check(h, o->width, o->n_sets, o->mark_sets, o->scale, who, &rc)) return -1;
     for (int r = c.n_res; r < kMaxRes; ++r)
         if (o->feats_out[r]) return fail("%s: feats_out[%d]: the model has %d resolutions", who, r, c.n_res);
-    if (scan_check_state(h, bt, o->n_sets, who)) return -1;
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemcpyAsync(h->intg_tab, o->mark_sets, o->n_sets * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    if (scan_upload_sets(h, o->mark_sets, o->n_sets, st, who)) return -1;
     const long long launches0 = g_launches;
     const int rv = scan_region_rows(h, bt, o, rc, logits, st);
     h->x0_fwd = false;
@@ -715,8 +668,8 @@ extern "C" int cf_perturbation_scan(cf_handle* h, const cf_batch* bt, const cf_s
 }
 
 // The variants of pCRE slot `slot`, slot-packed (cf_scan.h), into `logits` [B, V, n_out].  The caller has stashed the B genes' trunk
-// output in abl_stash and uploaded the mark sets.  Pack phase, per chunk of at most max_batch of the B * U pseudo rows: k_scan_pack,
-// the trunk (k_attc2's regions per workgroup as for the caller's B genes, as scan_region_rows), k_scan_unpack into scan_xv.  Row phase,
+// output in the workspace's stash and uploaded the mark sets.  Pack phase, per chunk of at most max_batch of the B * U pseudo rows: k_scan_pack,
+// the trunk (k_attc2's regions per workgroup as for the caller's B genes, as scan_region_rows), k_scan_unpack into slot_rows.  Row phase,
 // per chunk of at most max_batch of the B * V rows: k_scan_rows, the Regulation + head launches of an inference forward.
 static int scan_slot_packed(cf_handle* h, const cf_batch* bt, const cf_scan_regions_opts* o, int slot, int rc, float* logits, hipStream_t st) {
     const cf_config& c = h->cfg;
@@ -729,26 +682,26 @@ static int scan_slot_packed(cf_handle* h, const cf_batch* bt, const cf_scan_regi
     memset(&ua, 0, sizeof ua);
     memset(&ra, 0, sizeof ra);
     cf_batch cb;      // the chunk's batch: pseudo-genes for the trunk, then rows (masks and frequencies) for Regulation + head
-    intg_chunk_rows(h, bt, &pa.rows, &cb);
+    chunk_rows(h, bt, &pa.rows, &cb);
     ra.rows = pa.rows;
     const size_t xv_res = (size_t)B * (V - 1) * c.d_emb;
     for (int r = 0; r < nres; ++r) {
         pa.pf_in[r] = bt->promoter_feats[r];
         pa.cf_in[r] = bt->pcre_feats[r];
-        pa.pf_out[r] = h->intg_row[r];
-        pa.cf_out[r] = h->intg_row[kMaxRes + r];
+        pa.pf_out[r] = h->aw.row[r];
+        pa.cf_out[r] = h->aw.row[kMaxRes + r];
         ua.x0[r] = reinterpret_cast<const float4*>(h->Rx[r][0]);
-        ua.xv[r] = reinterpret_cast<float4*>(h->scan_xv + r * xv_res);
-        ra.stash[r] = reinterpret_cast<const float4*>(h->abl_stash[r]);
+        ua.xv[r] = reinterpret_cast<float4*>(h->aw.slot_rows + r * xv_res);
+        ra.stash[r] = reinterpret_cast<const float4*>(h->aw.stash[r]);
         ra.xv[r] = ua.xv[r];
         ra.x0[r] = reinterpret_cast<float4*>(h->Rx[r][0]);
     }
-    pa.sets = reinterpret_cast<const unsigned*>(h->intg_tab);
+    pa.sets = h->aw.words;
     pa.scale = o->scale;
     pa.U = U, pa.V = V, pa.F = c.n_feats, pa.W = W, pa.width = o->width, pa.rc = rc, pa.slot = slot;
     ua.U = U, ua.V = V, ua.S = S, ua.T = T, ua.d4 = d4;
     ra.freq_in = bt->interaction_freq;
-    ra.freq_out = h->intg_row[2 * kMaxRes];
+    ra.freq_out = h->aw.row[2 * kMaxRes];
     ra.V = V, ra.row4 = T * d4, ra.d4 = d4, ra.slot = slot;
     for (int g0 = 0; g0 < B * U; g0 += cap) {
         const int n = std::min(cap, B * U - g0);
@@ -775,40 +728,28 @@ static int scan_slot_packed(cf_handle* h, const cf_batch* bt, const cf_scan_regi
 // (scan_slot_packed; CF_SCAN_PACK=0 at cf_create: through scan_region_rows as well, the cross-check).
 extern "C" int cf_perturbation_scan_regions(cf_handle* h, const cf_batch* bt, const cf_scan_regions_opts* o, float* logits, void* stream) {
     const char* who = "cf_perturbation_scan_regions";
-    if (!h) return fail("%s: null handle", who);
-    if (!bt) return fail("%s: null batch", who);
+    if (attrib_open(h, bt, true, who)) return -1;
     if (!o) return fail("%s: null opts", who);
     if (!logits) return fail("%s: null logits", who);
     if (!o->mark_sets) return fail("%s: null mark_sets", who);
     const cf_config& c = h->cfg;
     const int S = c.i_max;
-    if (bt->B > c.max_batch) return fail("%s: batch size %d exceeds max_batch=%d", who, bt->B, c.max_batch);
     if (!o->regions) return fail("%s: regions = 0: at least one region bit (bit 0 the promoter, bit 1 + j pCRE slot j)", who);
     if (o->regions >> S >> 1) return fail("%s: regions = 0x%x names a region above i_max = %d", who, o->regions, S);
     int rc = 0;
-    if (scan_check(h, o->width, o->n_sets, o->mark_sets, o->scale, who, &rc) || scan_check_state(h, bt, o->n_sets, who)) return -1;
+    if (scan_check(h, o->width, o->n_sets, o->mark_sets, o->scale, who, &rc)) return -1;
     const bool packed = h->scan_pack && (o->regions >> 1);
     const int B = bt->B, V = 1 + o->n_sets * c.n_bins[rc];
-    if (packed) {
-        if (ablate_alloc(h, who)) return -1;
-        const size_t need = (size_t)c.n_res * B * (V - 1) * c.d_emb;
-        if (need > h->scan_xv_floats) {
-            if (h->scan_xv) (void)hipFree(h->scan_xv);      // (synchronises: a call in flight may still read the old buffer)
-            h->scan_xv = nullptr;
-            h->scan_xv_floats = 0;
-            if (hipMalloc(&h->scan_xv, need * sizeof(float)) != hipSuccess) return fail("%s: out of memory", who);
-            h->scan_xv_floats = need;
-        }
-    }
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemcpyAsync(h->intg_tab, o->mark_sets, o->n_sets * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    if (scan_upload_sets(h, o->mark_sets, o->n_sets, st, who)) return -1;
+    if (packed && h->aw.slot_rows.need((size_t)c.n_res * B * (V - 1) * c.d_emb, 0, who)) return -1;
     const long long launches0 = g_launches;
     const size_t block = (size_t)B * V * c.n_out;
     cf_scan_opts so;
     memset(&so, 0, sizeof so);
     so.width = o->width, so.n_sets = o->n_sets, so.mark_sets = o->mark_sets, so.scale = o->scale;
     int rv = 0, q = 0;
-    if (packed) rv = forward_trunk(h, bt, 0, st) || stash_trunk_output(h, B, h->abl_stash, st);
+    if (packed) rv = forward_trunk(h, bt, 0, st) || stash_trunk_output(h, B, h->aw.stash, st);
     for (int region = 0; region <= S && !rv; ++region) {
         if (!(o->regions >> region & 1u)) continue;
         float* out = logits + q++ * block;

@@ -28,6 +28,7 @@ static thread_local long long g_launches = 0;
         hipError_t e_ = hipGetLastError();                                                     \
         if (e_ != hipSuccess) return fail("launch %s failed: %s", name, hipGetErrorString(e_)); \
     } while (0)
+#include "cf_devbuf.h"      // DevBuf<T>, the owner of every device allocation below (it reports through fail)
 
 // ------------------------------------------------------------------------------------
 // parameter layout (host only)
@@ -251,13 +252,13 @@ struct cf_handle {
     cf_layout lay;
     float *params = nullptr, *grads = nullptr, *m = nullptr, *v = nullptr;
     ModelRefs refs;                      // where every tensor of the model lies in `params` (cf_bind)
-    float* tiled = nullptr;              // tiled copy of the Linear weights (forward products), same offsets
-    float* tiledT = nullptr;             // tiled copy of the transposed Regulation weights (backward products), same offsets
+    DevBuf<float> tiled;                 // tiled copy of the Linear weights (forward products), same offsets
+    DevBuf<float> tiledT;                // tiled copy of the transposed Regulation weights (backward products), same offsets
     bool reg8 = false;                   // Regulation stack on the 512-thread kernels of cf_reg8.h
     bool reg_row0 = true;                // ... whose last layer computes only what token 0 of its output needs (CF_REG_ROW0=0: all rows, the cross-check)
     bool keep_tiled_ok = false;          // (build_tables: the reduction tiles cover every tensor of that group)
     bool keep_tiled = false;             // cf_keep_tiled: the fused optimiser keeps the Embedding + Pairwise tiled copies fresh, forward passes do not re-tile them
-    int* tiled_map = nullptr;            // [bucket_split / 4]: where each flat float4 of the Embedding + Pairwise range lies in the tiled buffer (k_adamw_tiled)
+    DevBuf<int> tiled_map;               // [bucket_split / 4]: where each flat float4 of the Embedding + Pairwise range lies in the tiled buffer (k_adamw_tiled)
     bool tiled_pe_fresh = false;         // ... and they ARE fresh (cleared by whatever else writes parameters: cf_bind, cf_params_changed, the separate AdamW launches)
     // Embedding stack over ALL promoter bins (cf_embed_full.h + the dense transformer layer): used by the model path when
     // embed.n_layers > 1 and by cf_embed_full; device buffers outside the arena, allocated on first need
@@ -270,12 +271,12 @@ struct cf_handle {
         float* lp_partial[kMaxRes] = {};
         uint8_t* valid[kMaxRes] = {};
         float* tables = nullptr;                           // 4 MiB of tile tables for the backward pass
-        std::vector<void*> owned;
+        std::vector<DevBuf<float>> owned;                  // the allocations the pointers above point into, one each
     } ed;
     bool embed_dense = false;            // the training path goes through it (embed.n_layers > 1)
-    RetileUnit* retile_units = nullptr;
+    DevBuf<RetileUnit> retile_units;
     int n_retile = 0, n_retile_early = 0;      // all units | the leading ones a forward pass needs at once (Embedding + Pairwise)
-    TrunkResDev* trunk_tab = nullptr;          // fused centre-row trunk (cf_trunk.h): device table, one entry per resolution
+    DevBuf<TrunkResDev> trunk_tab;             // fused centre-row trunk (cf_trunk.h): device table, one entry per resolution
     bool trunk = false;                        // the Embedding + Pairwise stage runs as k_trunk_fwd / k_trunk_bwd (CF_TRUNK=0: the stand-alone kernels)
     size_t trunk_smem_bytes = 0;
     bool head_deferred = false;                // cf_forward(save = 2) left the head to cf_backward_part (k_head_train)
@@ -315,7 +316,7 @@ struct cf_handle {
                                                // cached accesses) the table order wins: 0.5012 -> 0.4892 ms (profiles/r06n_env_ab.txt); CF_XCD_REDUCE=1 forces it on
     int defer_retile = 1;                      // Regulation + head units ride in the Embedding layer's chain launch (CF_DEFER_RETILE=0: all in the prologue)
     // workspace
-    float* arena = nullptr;
+    DevBuf<float> arena;
     size_t arena_floats = 0;
     std::vector<WsEntry> ws;
     std::map<std::string, int> ws_index;
@@ -344,42 +345,34 @@ struct cf_handle {
     float* dfreq_part = nullptr;               // [n_res][max_batch][T * T]: d(interaction_freq) per resolution, summed by k_dfreq_sum
     bool reg_dfreq_ok = false;                 // k_reg8_bwd_dfreq got its LDS attribute
     bool ig_smem_ok = false;                   // k_input_grad got its LDS attribute (first use)
-    // in-silico pCRE deletion and coalitions (cf_coalition.h): one allocation, made by the first call (ablate_alloc)
-    float* abl_stash[kMaxRes] = {};            // [max_batch, T, d_emb] per resolution: the trunk's output, Rx[r][0]
-    float* abl_freq = nullptr;                 // [max_batch, T, T]: interaction_freq of a chunk's gene-variants
-    uint8_t* abl_mask[kMaxRes] = {};           // [max_batch, T, T] per resolution: their interaction masks
-    const unsigned* abl_tab = nullptr;         // [i_max + 2]: the coalition words of cf_pcre_ablation's variants, written once
-    void* abl_mem = nullptr;
-    unsigned* coal_tab = nullptr;              // [coal_cap]: the coalition words of a call; grows on demand
-    long long coal_cap = 0;
-    float* coal_rows = nullptr;                // [max_batch, coal_rows_per, n_out]: the rows of a Shapley / epistasis call without a caller's buffer
-    long long coal_rows_per = 0;
-    // integrated gradients (cf_integrated_gradients): one allocation, made by the first call (intg_alloc); segments are
-    // promoter_feats[r], pcre_feats[r], interaction_freq (cf_ig.h)
-    float* intg_row[kIgSegs] = {};             // [max_batch, len]: a chunk's inputs
-    float* intg_grad[kIgSegs] = {};            // [max_batch, len]: their per-row gradients
-    uint8_t* intg_pm[kMaxRes] = {};            // [max_batch, L]: promoter pad-mask centre rows ([max_batch, L, L] with the all-rows Embedding)
-    uint8_t* intg_cm[kMaxRes] = {};            // [max_batch * i_max, L]: pCRE pad-mask centre rows
-    uint8_t* intg_im[kMaxRes] = {};            // [max_batch, T, T]: interaction masks
-    float* intg_stash[kMaxRes] = {};           // [max_batch, T, d_emb]: the trunk's output (frequency-only path)
-    float* intg_logits = nullptr;              // [max_batch, n_out]: a chunk's logits
-    void* intg_mem = nullptr;
-    float* intg_tab = nullptr;                 // [2, intg_cap]: nodes and weights
-    int intg_cap = 0;
-    float* intg_part = nullptr;                // [max_batch, kIgSlices]: per-slice sums of a gene's attributions (k_ig_delta)
-    bool intg_trunk_once = true;               // frequency-only IG runs the trunk once (CF_IG_TRUNK_ONCE=0 at cf_create: the general path, for A/B checks)
-    // perturbation scan of several regions (cf_perturbation_scan_regions): the changed Regulation input row of every variant of one pCRE slot
-    float* scan_xv = nullptr;                  // [n_res][B * (V - 1), d_emb]; grows on demand
-    size_t scan_xv_floats = 0;
+    // The chunk workspace of the attribution entry points (attrib_ws, cf_api_attrib.h), allocated by the first call that needs it: a
+    // chunk is at most max_batch rows (gene-variants) that run through the model as one batch.  One allocation, `mem`; float
+    // segments are promoter_feats[r], pcre_feats[r], interaction_freq (cf_ig.h).
+    struct AttribWs {
+        DevBuf<float> mem;
+        float* row[kIgSegs] = {};              // [max_batch, len]: the chunk's float inputs
+        float* grad[kIgSegs] = {};             // [max_batch, len]: their per-row gradients
+        uint8_t* pmask[kMaxRes] = {};          // [max_batch, L]: promoter pad-mask centre rows ([max_batch, L, L] with the all-rows Embedding)
+        uint8_t* cmask[kMaxRes] = {};          // [max_batch * i_max, L]: pCRE pad-mask centre rows
+        uint8_t* imask[kMaxRes] = {};          // [max_batch, T, T]: interaction masks
+        float* stash[kMaxRes] = {};            // [max_batch, T, d_emb]: the trunk's output Rx[r][0] of the call's genes
+        float* logits = nullptr;               // [max_batch, n_out]: the chunk's logits
+        float* slice_sums = nullptr;           // [max_batch, kIgSlices]: per-slice sums of a gene's attributions (k_ig_delta)
+        const unsigned* deletion_words = nullptr;      // [i_max + 2]: the coalition words of cf_pcre_ablation's variants, written once
+        DevBuf<unsigned> words;                // the 32-bit table of a call: coalition words | quadrature nodes, then weights | mark sets; grows on demand
+        DevBuf<float> own_rows;                // [max_batch, per, n_out]: the rows of a Shapley / epistasis call without a caller's buffer; grows on demand
+        DevBuf<float> slot_rows;               // [n_res][B * (V - 1), d_emb]: the changed Regulation input row of every variant of one pCRE slot (scan); grows on demand
+    } aw;
+    bool ig_trunk_once = true;                 // frequency-only IG runs the trunk once (CF_IG_TRUNK_ONCE=0 at cf_create: the general path, for A/B checks)
     bool scan_pack = true;                     // pCRE variants run slot-packed (CF_SCAN_PACK=0 at cf_create: the per-region path, for A/B checks)
     // deferred-gradient tile tables
-    WgTile* wg_tiles = nullptr;
+    DevBuf<WgTile> wg_tiles;
     int n_wg = 0;
-    CsTile* cs_tiles = nullptr;
+    DevBuf<CsTile> cs_tiles;
     int n_cs = 0;
-    LpJob* lp_jobs = nullptr;
+    DevBuf<LpJob> lp_jobs;
     int n_lp = 0;
-    RegLayerDev* reg_tab = nullptr;      // fused Regulation stack (one workgroup per gene), when it fits in LDS
+    DevBuf<RegLayerDev> reg_tab;         // fused Regulation stack (one workgroup per gene), when it fits in LDS
     bool reg_fused = false;
     float *lp_part_e[kMaxRes], *lp_part_p[kMaxRes];
     int last_fwd_B = 0;
@@ -415,6 +408,18 @@ struct cf_handle {
     };
     std::vector<Replay> replays;
     Replay cap;                    // under construction
+
+    cf_handle() = default;
+    cf_handle(const cf_handle&) = delete;
+    cf_handle& operator=(const cf_handle&) = delete;
+    ~cf_handle() {      // (the DevBuf members free the device memory)
+        for (Replay& rp : replays) {
+            if (rp.first) (void)hipGraphExecDestroy(rp.first);
+            if (rp.second) (void)hipGraphExecDestroy(rp.second);
+        }
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        if (ride_ev) (void)hipEventDestroy(ride_ev);
+    }
 
     void time_mark(const char* name, hipStream_t st) {
         if (timed.empty() || capturing || timed != name) return;

@@ -11,12 +11,10 @@ extern "C" int cf_op_linear(const float* A, const float* W, const float* bias, f
     // standalone use: build the tiled copy of W on the fly (test / micro-benchmark helper, synchronous)
     std::vector<RetileUnit> units;
     for (int n0 = 0; n0 < N; n0 += 16) units.push_back(RetileUnit{(long long)n0 * K, 0, K, N, n0, 0});
-    float* Wt = nullptr;
-    RetileUnit* du = nullptr;
-    HIP_TRY(hipMalloc(&Wt, (size_t)N * K * sizeof(float)));
-    HIP_TRY(hipMalloc(&du, units.size() * sizeof(RetileUnit)));
-    HIP_TRY(hipMemcpy(du, units.data(), units.size() * sizeof(RetileUnit), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_retile, dim3((int)units.size()), dim3(256), 0, (hipStream_t)stream, W, Wt, (float*)nullptr, (const RetileUnit*)du);
+    DevBuf<float> Wt;      // (freed on every return; the synchronisation below keeps them alive while the kernels run)
+    DevBuf<RetileUnit> du;
+    if (Wt.alloc((size_t)N * K, "cf_op_linear") || du.upload(units, "cf_op_linear")) return -1;
+    hipLaunchKernelGGL(k_retile, dim3((int)units.size()), dim3(256), 0, (hipStream_t)stream, W, (float*)Wt, (float*)nullptr, (const RetileUnit*)du);
     LinArgs a;
     memset(&a, 0, sizeof a);
     a.x[0] = A;
@@ -33,8 +31,6 @@ extern "C" int cf_op_linear(const float* A, const float* W, const float* bias, f
     hipLaunchKernelGGL((k_linear_fwd<2>), dim3(tiles_of(M), (N + 127) / 128, 1), dim3(256), 0, (hipStream_t)stream, a);
     LAUNCH_CHECK("cf_op_linear");
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    HIP_TRY(hipFree(Wt));
-    HIP_TRY(hipFree(du));
     return 0;
 }
 extern "C" int cf_op_dgrad(const float* dY, const float* W, float* dX, int M, int N, int K, void* stream) {
@@ -62,13 +58,11 @@ extern "C" int cf_op_wgrad(const float* dY, const float* X, float* dW, int M, in
     if (K % 4) return fail("cf_op_wgrad: K %% 4 == 0 required");
     std::vector<WgTile> tiles;
     push_wg(tiles, wg1(dY, N, X, K, M, dW, K, N, K));
-    WgTile* d = nullptr;
-    HIP_TRY(hipMalloc(&d, tiles.size() * sizeof(WgTile)));
-    HIP_TRY(hipMemcpy(d, tiles.data(), tiles.size() * sizeof(WgTile), hipMemcpyHostToDevice));
+    DevBuf<WgTile> d;
+    if (d.upload(tiles, "cf_op_wgrad")) return -1;
     hipLaunchKernelGGL(k_wgrad, dim3(xcd_grid((int)tiles.size())), dim3(256), 0, (hipStream_t)stream, (const WgTile*)d, (int)tiles.size(), 1, 0);
     LAUNCH_CHECK("cf_op_wgrad");
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    HIP_TRY(hipFree(d));
     return 0;
 }
 
@@ -585,12 +579,14 @@ static int embed_dense_alloc(cf_handle* h) {
     if (e.ready) return 0;
     const cf_config& c = h->cfg;
     const int B = c.max_batch, E = c.embed_layers;
-    auto get = [&](size_t floats) -> float* {
-        void* q = nullptr;
-        if (hipMalloc(&q, floats * sizeof(float)) != hipSuccess) return nullptr;
-        (void)hipMemset(q, 0, floats * sizeof(float));
-        h->ed.owned.push_back(q);
-        return (float*)q;
+    auto get = [&](size_t floats) -> float* {      // (separate allocations: the all-rows path keeps the addresses and alignment it has)
+        DevBuf<float> q;
+        if (q.alloc(floats, "embed_dense_alloc") || hipMemset(q, 0, floats * sizeof(float)) != hipSuccess) {
+            e.owned.clear();      // nothing half-made stays behind: the next call starts from an empty list
+            return nullptr;
+        }
+        e.owned.push_back(std::move(q));
+        return e.owned.back();
     };
     for (int r = 0; r < c.n_res; ++r) {
         const int L = c.n_bins[r];

@@ -101,9 +101,7 @@ static int build_reg_table(cf_handle* h) {
                 d.hq = b.hq, d.dy1 = b.dy1;
                 rt.push_back(d);
             }
-        if (h->reg_tab) (void)hipFree(h->reg_tab);
-        HIP_TRY(hipMalloc(&h->reg_tab, rt.size() * sizeof(RegLayerDev)));
-        HIP_TRY(hipMemcpy(h->reg_tab, rt.data(), rt.size() * sizeof(RegLayerDev), hipMemcpyHostToDevice));
+        if (h->reg_tab.upload(rt, "cf_bind: the Regulation layer table")) return -1;
     }
     return 0;
 }
@@ -208,10 +206,8 @@ static int build_tables(cf_handle* h) {
     push_cs(csHi, h->dh1, c.d_head, c.d_head, 1, 1, h->grad_of(m.head.b1));
     push_cs(csHi, h->dlogits, c.n_out, c.n_out, 1, 1, h->grad_of(m.head.b2));
 
-    if (h->lp_jobs) (void)hipFree(h->lp_jobs);
+    if (h->lp_jobs.upload(lpj, "cf_bind: the lin_proj gradient jobs")) return -1;
     h->n_lp = (int)lpj.size();
-    HIP_TRY(hipMalloc(&h->lp_jobs, lpj.size() * sizeof(LpJob)));
-    HIP_TRY(hipMemcpy(h->lp_jobs, lpj.data(), lpj.size() * sizeof(LpJob), hipMemcpyHostToDevice));
     // Embedding + Pairwise tiles whose tensor has a tiled copy: where the tensor starts in the flat buffers and which of its rows the tile's row 0 is
     // (AdamFuse::tiled: the optimiser epilogue writes the stepped elements into the tiled copy as well)
     for (WgTile& t : wg) {
@@ -250,9 +246,7 @@ static int build_tables(cf_handle* h) {
                     map[(size_t)(flat / 4)] = (int)(til / 4);
                 }
         }
-        if (h->tiled_map) (void)hipFree(h->tiled_map);
-        HIP_TRY(hipMalloc(&h->tiled_map, map.size() * sizeof(int)));
-        HIP_TRY(hipMemcpy(h->tiled_map, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
+        if (h->tiled_map.upload(map, "cf_bind: the flat-to-tiled map")) return -1;
     }
     h->n_wg_hi = (int)wgHi.size();
     h->n_cs_hi = (int)csHi.size();
@@ -267,14 +261,9 @@ static int build_tables(cf_handle* h) {
         if (t.n0 || t.k0) continue;      // count each job once
         for (int sgi = 0; sgi < t.nseg; ++sgi) h->wg_flops_per_gene += 2.0 * t.seg[sgi].rows_per_gene * (double)t.Nn * t.Kk;
     }
-    if (h->wg_tiles) (void)hipFree(h->wg_tiles);
-    if (h->cs_tiles) (void)hipFree(h->cs_tiles);
+    if (h->wg_tiles.upload(wg, "cf_bind: the weight-gradient tiles") || h->cs_tiles.upload(cs, "cf_bind: the column-sum tiles")) return -1;
     h->n_wg = (int)wg.size();
     h->n_cs = (int)cs.size();
-    HIP_TRY(hipMalloc(&h->wg_tiles, wg.size() * sizeof(WgTile)));
-    HIP_TRY(hipMalloc(&h->cs_tiles, cs.size() * sizeof(CsTile)));
-    HIP_TRY(hipMemcpy(h->wg_tiles, wg.data(), wg.size() * sizeof(WgTile), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->cs_tiles, cs.data(), cs.size() * sizeof(CsTile), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -324,9 +313,7 @@ static int build_trunk_table(cf_handle* h) {
         t.lp_part_e = h->lp_part_e[r], t.lp_part_p = h->lp_part_p[r];
         t.L = c.n_bins[r], t.Lpad = attc2_lpad(c.n_bins[r]), t.LT = attc2_lt(c.n_bins[r]);
     }
-    if (h->trunk_tab) (void)hipFree(h->trunk_tab);
-    HIP_TRY(hipMalloc(&h->trunk_tab, tab.size() * sizeof(TrunkResDev)));
-    HIP_TRY(hipMemcpy(h->trunk_tab, tab.data(), tab.size() * sizeof(TrunkResDev), hipMemcpyHostToDevice));
+    if (h->trunk_tab.upload(tab, "cf_bind: the trunk table")) return -1;
     h->trunk_smem_bytes = need;
     h->trunk = true;
     return 0;

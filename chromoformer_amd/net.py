@@ -682,6 +682,25 @@ class ChromoformerBase(nn.Module):
                 info["coeff"] = {k: {b: t.view(shapes[k][b]) for b, t in v.items()} for k, v in info["coeff"].items()}
         return attr, info
 
+    def _scan_mark_bits(self, who, mark_sets):
+        """mark_sets (None: attribution.scan_mark_sets' default) validated -> uint32 [n_sets], bit f of word k set where set k holds mark f."""
+        from .attribution import scan_mark_sets
+        F = self.n_feats
+        mark_sets = scan_mark_sets(mark_sets, F)
+        bad = [ms for ms in mark_sets if any(not 0 <= f < min(F, 32) for f in ms)]
+        if bad or not mark_sets:
+            raise ValueError("%s: mark_sets %s: a non-empty list of sets of mark indices in [0, n_feats = %d)" % (who, bad or "()", F))
+        return np.array([sum(1 << f for f in set(ms)) for ms in mark_sets], dtype=np.uint32)
+
+    def _scan_flip(self, who, flip, B):
+        """flip ([B] bools, or None) -> a uint8 tensor of B entries on the model's device, or None."""
+        if flip is None:
+            return None
+        flip = torch.as_tensor(flip).to(self._device).ne(0).to(torch.uint8).contiguous()
+        if flip.numel() != B:
+            raise ValueError("%s: flip has %d entries for a batch of %d genes" % (who, flip.numel(), B))
+        return flip
+
     @torch.no_grad()
     def perturbation_scan(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
                           interaction_freq=None, region=0, scale=0.0, width=1, mark_sets=None, flip=None, return_feats=False):
@@ -704,22 +723,14 @@ class ChromoformerBase(nn.Module):
         backward: such a pending backward() raises."""
         bs, _keep, book = self._attrib_call("perturbation_scan", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
         F, dev, B = self.n_feats, self._device, bs.B
-        if mark_sets is None:
-            mark_sets = [(f,) for f in range(F)] + [tuple(range(F))]
-        mark_sets = [tuple(int(f) for f in ms) for ms in mark_sets]
-        bad = [ms for ms in mark_sets if any(not 0 <= f < min(F, 32) for f in ms)]
-        if bad or not mark_sets:
-            raise ValueError("perturbation_scan: mark_sets %s: a non-empty list of sets of mark indices in [0, n_feats = %d)" % (bad or "()", F))
-        bits = np.array([sum(1 << f for f in set(ms)) for ms in mark_sets], dtype=np.uint32)
+        bits = self._scan_mark_bits("perturbation_scan", mark_sets)
         W = min(self.n_bins)
-        V = 1 + len(mark_sets) * W
+        V = 1 + len(bits) * W
         opts = _lib.cf_scan_opts()
-        opts.region, opts.width, opts.n_sets, opts.scale = int(region), int(width), len(mark_sets), float(scale)
+        opts.region, opts.width, opts.n_sets, opts.scale = int(region), int(width), len(bits), float(scale)
         opts.mark_sets = bits.ctypes.data
+        flip = self._scan_flip("perturbation_scan", flip, B)      # (kept alive until the call below has been issued)
         if flip is not None:
-            flip = torch.as_tensor(flip).to(dev).ne(0).to(torch.uint8).contiguous()
-            if flip.numel() != B:
-                raise ValueError("perturbation_scan: flip has %d entries for a batch of %d genes" % (flip.numel(), B))
             opts.flip = flip.data_ptr()
         feats = None
         if return_feats:
@@ -745,24 +756,16 @@ class ChromoformerBase(nn.Module):
         perturbation_scan; there is no return_feats."""
         from .attribution import scan_regions_expand
         bs, _keep, book = self._attrib_call("perturbation_scan_regions", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
-        F, dev, B = self.n_feats, self._device, bs.B
+        dev, B = self._device, bs.B
         regions = scan_regions_expand(regions, self.i_max, "perturbation_scan_regions")
-        if mark_sets is None:
-            mark_sets = [(f,) for f in range(F)] + [tuple(range(F))]
-        mark_sets = [tuple(int(f) for f in ms) for ms in mark_sets]
-        bad = [ms for ms in mark_sets if any(not 0 <= f < min(F, 32) for f in ms)]
-        if bad or not mark_sets:
-            raise ValueError("perturbation_scan_regions: mark_sets %s: a non-empty list of sets of mark indices in [0, n_feats = %d)" % (bad or "()", F))
-        bits = np.array([sum(1 << f for f in set(ms)) for ms in mark_sets], dtype=np.uint32)
-        V = 1 + len(mark_sets) * min(self.n_bins)
+        bits = self._scan_mark_bits("perturbation_scan_regions", mark_sets)
+        V = 1 + len(bits) * min(self.n_bins)
         opts = _lib.cf_scan_regions_opts()
         opts.regions = sum(1 << r for r in regions)
-        opts.width, opts.n_sets, opts.scale = int(width), len(mark_sets), float(scale)
+        opts.width, opts.n_sets, opts.scale = int(width), len(bits), float(scale)
         opts.mark_sets = bits.ctypes.data
+        flip = self._scan_flip("perturbation_scan_regions", flip, B)      # (kept alive until the call below has been issued)
         if flip is not None:
-            flip = torch.as_tensor(flip).to(dev).ne(0).to(torch.uint8).contiguous()
-            if flip.numel() != B:
-                raise ValueError("perturbation_scan_regions: flip has %d entries for a batch of %d genes" % (flip.numel(), B))
             opts.flip = flip.data_ptr()
         logits = torch.empty(len(regions), B, V, self.n_out, device=dev)      # (written in full by the library)
         st = book()

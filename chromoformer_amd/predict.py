@@ -225,12 +225,10 @@ def write_perturbation_scan(model, store, bsz, path, gene_ids, strands, regressi
     import ctypes as C
 
     from . import _lib
-    from .attribution import scan_regions_expand, scan_row
+    from .attribution import scan_mark_sets, scan_regions_expand, scan_row
     n, dev, L = len(store), model._device, _lib.lib()
     S, F = model.i_max, model.n_feats
-    if mark_sets is None:
-        mark_sets = [(f,) for f in range(F)] + [tuple(range(F))]
-    mark_sets = [tuple(int(f) for f in ms) for ms in mark_sets]
+    mark_sets = scan_mark_sets(mark_sets, F)
     K = len(mark_sets)
     rc = int(np.argmin(model.n_bins))
     W = model.n_bins[rc]
