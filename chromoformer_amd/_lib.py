@@ -90,6 +90,10 @@ class cf_scan_regions_opts(C.Structure):
                 ("flip", C.c_void_p)]
 
 
+class cf_mark_opts(C.Structure):
+    _fields_ = [("n_players", C.c_int), ("player_marks", C.c_void_p), ("player_regions", C.c_void_p), ("scale", C.c_float)]
+
+
 class cf_store(C.Structure):
     _fields_ = [
         ("n_genes", C.c_longlong),
@@ -147,6 +151,9 @@ SYMBOLS = {
                                               C.POINTER(cf_input_grads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_perturbation_scan": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_scan_opts), C.c_void_p, C.c_void_p]),
     "cf_perturbation_scan_regions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_scan_regions_opts), C.c_void_p, C.c_void_p]),
+    "cf_mark_coalitions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_opts), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "cf_mark_shapley": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_opts), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cf_mark_epistasis": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_opts), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_adamw_step": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_longlong, C.c_void_p]),
     "cf_debug_copy": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p]),
     "cf_debug_names": (C.c_char_p, [C.c_void_p]),

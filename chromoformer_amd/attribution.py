@@ -58,25 +58,81 @@ def coalition_table(kind, i_max):
     raise ValueError("coalition_table: kind %r; choose 'all' or 'pairs'" % (kind,))
 
 
-def coalition_words(keep, i_max, who="pcre_coalitions"):
+def coalition_words(keep, i_max, who="pcre_coalitions", item="pCRE slot", limit="i_max"):
     """`keep` as the uint32 words the library reads: a sequence / array of ints (bit j set: slot j kept), or a bool array
-    [n_coal, i_max] (column j: slot j kept).  Empty input, a negative word or a bit >= i_max raise ValueError naming `who`."""
+    [n_coal, i_max] (column j: slot j kept).  Empty input, a negative word or a bit >= i_max raise ValueError naming `who`.
+    (`item` / `limit`: what a bit and its bound are called in the messages; mark_coalition_words passes the players'.)"""
     S = int(i_max)
     a = np.asarray(keep.cpu() if hasattr(keep, "cpu") else keep)
     if a.size < 1:
         raise ValueError("%s: keep is empty: at least 1 coalition" % who)
     if a.dtype == np.bool_:
         if a.ndim != 2 or a.shape[1] != S:
-            raise ValueError("%s: a bool keep must be [n_coal, i_max = %d], got %s" % (who, S, tuple(a.shape)))
+            raise ValueError("%s: a bool keep must be [n_coal, %s = %d], got %s" % (who, limit, S, tuple(a.shape)))
         a = (a.astype(np.int64) << np.arange(S, dtype=np.int64)).sum(1)
     elif a.ndim != 1 or a.dtype.kind not in "iu":
-        raise ValueError("%s: keep must be a sequence of ints or a bool array [n_coal, i_max], got dtype %s with shape %s"
-                         % (who, a.dtype, tuple(a.shape)))
+        raise ValueError("%s: keep must be a sequence of ints or a bool array [n_coal, %s], got dtype %s with shape %s"
+                         % (who, limit, a.dtype, tuple(a.shape)))
     a = a.astype(np.int64) if a.dtype != np.uint64 else a
     bad = [int(m) for m in a if int(m) < 0 or int(m) >> S]
     if bad:
-        raise ValueError("%s: keep word(s) %s name a pCRE slot >= i_max = %d (or are negative)" % (who, [hex(m) for m in bad[:4]], S))
+        raise ValueError("%s: keep word(s) %s name a %s >= %s = %d (or are negative)" % (who, [hex(m) for m in bad[:4]], item, limit, S))
     return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+MARK_PLAYER_SPECS = ("marks", "compartments", "regions")
+
+
+def mark_players(spec, n_feats, i_max):
+    """The players of the histone-mark game (ChromoformerBase.mark_coalitions / mark_shapley / mark_epistasis) ->
+    (marks uint32 [P], regions uint32 [P], names): bit f of marks[p] set = player p holds mark f; bit 0 of regions[p] = in the
+    promoter, bit 1 + j = in pCRE slot j.  spec:
+
+      "marks"          P = n_feats: player f is mark f in every region ("mark0", ...)
+      "compartments"   P = 2 n_feats: mark f in the promoter ("mark0@promoter", ...), then mark f in all pCRE slots ("mark0@pcres", ...)
+      "regions"        P = i_max + 1: all marks in region rho ("promoter", "pcre0", ...)
+      a list of (marks, regions) pairs of index iterables (regions: 0 the promoter, 1 + j pCRE slot j); players may overlap
+
+    More than 16 players, an empty player or an index out of range raise ValueError naming mark_players."""
+    F, S = int(n_feats), int(i_max)
+    every_mark, every_region = list(range(F)), list(range(S + 1))
+    if isinstance(spec, str):
+        if spec == "marks":
+            pairs = [([f], every_region) for f in every_mark]
+            names = ["mark%d" % f for f in every_mark]
+        elif spec == "compartments":
+            pairs = [([f], [0]) for f in every_mark] + [([f], every_region[1:]) for f in every_mark]
+            names = ["mark%d@promoter" % f for f in every_mark] + ["mark%d@pcres" % f for f in every_mark]
+        elif spec == "regions":
+            pairs = [(every_mark, [rho]) for rho in every_region]
+            names = ["promoter"] + ["pcre%d" % j for j in range(S)]
+        else:
+            raise ValueError("mark_players: players %r; choose from %s or give a list of (marks, regions) pairs" % (spec, MARK_PLAYER_SPECS))
+    else:
+        try:
+            pairs = [(sorted({int(f) for f in ms}), sorted({int(r) for r in rs})) for ms, rs in spec]
+        except (TypeError, ValueError):
+            raise ValueError("mark_players: players must be one of %s or a list of (marks, regions) pairs of index iterables, got %r"
+                             % (MARK_PLAYER_SPECS, spec)) from None
+        names = ["marks(%s)@regions(%s)" % (",".join(map(str, ms)), ",".join(map(str, rs))) for ms, rs in pairs]
+    if not 1 <= len(pairs) <= 16:
+        raise ValueError("mark_players: %d players; the exact game takes 1..16" % len(pairs))
+    for p, (ms, rs) in enumerate(pairs):
+        if not ms or not rs:
+            raise ValueError("mark_players: player %d is empty: at least one mark and one region" % p)
+        if ms[0] < 0 or ms[-1] >= min(F, 32):
+            raise ValueError("mark_players: player %d names mark(s) %s outside [0, n_feats = %d)" % (p, ms, F))
+        if rs[0] < 0 or rs[-1] > S:
+            raise ValueError("mark_players: player %d names region(s) %s outside [0, i_max = %d]" % (p, rs, S))
+    marks = np.array([sum(1 << f for f in ms) for ms, _ in pairs], dtype=np.uint32)
+    regions = np.array([sum(1 << r for r in rs) for _, rs in pairs], dtype=np.uint32)
+    return marks, regions, names
+
+
+def mark_coalition_words(keep, n_players, who="mark_coalitions"):
+    """`keep` as the uint32 words the library reads: a sequence / array of ints (bit p set: player p present), or a bool array
+    [n_coal, P].  Empty input, a negative word or a bit >= P raise ValueError naming `who`."""
+    return coalition_words(keep, n_players, who, item="player", limit="n_players")
 
 
 def _geometry_check(who, model, dataset, binsizes):
@@ -370,6 +426,26 @@ def scan_row_inverse(row, n_sets, W):
     return q, k, g
 
 
+def _resident_store(who, ds, genes, binsizes, dev, store=None):
+    """The binned features of `genes` on the device: `store` (a device-resident GeneStore holding `genes` in order) if given, else the
+    packed store next to the raw files if one matches, else the raw .npy files binned on the device."""
+    import copy
+
+    from . import pack
+    from .data import GeneStore
+    if store is None:
+        packed = pack.find(ds.npy_dir, None, binsizes, ds.i_max, ds.w_prom, ds.w_max, ds.n_feats, genes, meta=ds.meta)
+        if packed is not None:
+            store = packed.store(genes, device=dev, regression=False)
+        else:
+            sub = copy.copy(ds)
+            sub.target_genes = genes
+            store = GeneStore(sub, device=dev, resident=True)
+    if len(store) != len(genes):
+        raise ValueError("%s: the store holds %d genes, `genes` names %d" % (who, len(store), len(genes)))
+    return store
+
+
 def perturbation_scan(model, dataset, genes=None, regions="promoter", scale=0.0, width=1, mark_sets=None, bsz=None, store=None):
     """In-silico perturbation scan of the genes of a ChromoformerDataset (one model.perturbation_scan_regions per batch, windows in
     genomic coordinates): what the prediction becomes with the marks of a mark set scaled by `scale` in raw-signal space -- 0 erases, 2
@@ -391,12 +467,9 @@ def perturbation_scan(model, dataset, genes=None, regions="promoter", scale=0.0,
     holding `genes` in order) if given, else from the packed store next to the raw files if one matches, else from the raw .npy
     files binned on the device: the raw files are not required.  Parameters, gradients and optimiser state are left as they are; the
     pass overwrites the activations a grad-enabled model(...) keeps for its backward."""
-    import copy
-
     import torch
 
-    from . import pack
-    from .data import GeneStore, promoter_col0
+    from .data import promoter_col0
     ds = dataset
     binsizes = [int(b) for b in ds.binsizes]
     n_bins = _geometry_check("perturbation_scan", model, ds, binsizes)
@@ -408,16 +481,7 @@ def perturbation_scan(model, dataset, genes=None, regions="promoter", scale=0.0,
     rc = int(np.argmin(n_bins))
     W, bc = n_bins[rc], binsizes[rc]
     col0 = promoter_col0(ds)
-    if store is None:
-        packed = pack.find(ds.npy_dir, None, binsizes, S, ds.w_prom, ds.w_max, F, genes, meta=ds.meta)
-        if packed is not None:
-            store = packed.store(genes, device=dev, regression=False)
-        else:
-            sub = copy.copy(ds)
-            sub.target_genes = genes
-            store = GeneStore(sub, device=dev, resident=True)
-    if len(store) != len(genes):
-        raise ValueError("perturbation_scan: the store holds %d genes, the scan names %d" % (len(store), len(genes)))
+    store = _resident_store("perturbation_scan", ds, genes, binsizes, dev, store)
     for lo in range(0, len(genes), chunk):
         ids = genes[lo:lo + chunk]
         B = len(ids)
@@ -456,3 +520,41 @@ def perturbation_scan(model, dataset, genes=None, regions="promoter", scale=0.0,
                 per[i]["logits"] = out[i].copy()
         for p in per:
             yield p
+
+
+def mark_shapley(model, dataset, genes=None, players="marks", scale=0.0, epistasis=False, bsz=None, store=None):
+    """Exact Shapley values of the histone marks for the genes of a ChromoformerDataset (one model.mark_shapley per batch, with
+    epistasis=True also one model.mark_epistasis): which marks carry the prediction when an absent mark's raw signal is scaled by
+    `scale` (0 erases it) over the regions of its player.  A generator over `genes` (ids; default: the dataset's) in chunks of at most
+    min(bsz, model.max_batch) genes; per gene it yields a dict of host arrays:
+
+        gene_id   the id
+        phi       float32 [P, n_out]: the players' Shapley values, in logit space; phi.sum(0) = logits - erased up to rounding
+        logits    float32 [n_out]: the prediction (every player present)
+        erased    float32 [n_out]: every player absent
+        players   the players' names (mark_players)
+        eps       float32 [P, P, n_out], with epistasis=True: the pair epistasis, the leave-one-out effects on the diagonal
+
+    players: "marks", "compartments", "regions" or a list of (marks, regions) pairs (mark_players).  The binned features come from
+    `store` (a device-resident GeneStore holding `genes` in order) if given, else from the packed store next to the raw files if one
+    matches, else from the raw .npy files binned on the device.  Parameters, gradients and optimiser state are left as they are; the
+    pass overwrites the activations a grad-enabled model(...) keeps for its backward."""
+    ds = dataset
+    binsizes = [int(b) for b in ds.binsizes]
+    _geometry_check("mark_shapley", model, ds, binsizes)
+    genes, chunk = _genes_check("mark_shapley", model, ds, genes, bsz)
+    spec = players if isinstance(players, str) else list(players)
+    names = mark_players(spec, ds.n_feats, ds.i_max)[2]      # (refusals before anything is loaded)
+    store = _resident_store("mark_shapley", ds, genes, binsizes, model._device, store)
+    for lo in range(0, len(genes), chunk):
+        ids = genes[lo:lo + chunk]
+        d = store.batch(list(range(lo, lo + len(ids))))
+        args = tuple(d[k] for k in ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq"))
+        phi, info = model.mark_shapley(*args, players=spec, scale=scale)
+        phi, logits, erased = phi.cpu().numpy(), info["logits"].cpu().numpy(), info["erased"].cpu().numpy()
+        eps = model.mark_epistasis(*args, players=spec, scale=scale)[0].cpu().numpy() if epistasis else None
+        for i, g in enumerate(ids):
+            out = dict(gene_id=g, phi=phi[i].copy(), logits=logits[i].copy(), erased=erased[i].copy(), players=list(names))
+            if epistasis:
+                out["eps"] = eps[i].copy()
+            yield out

@@ -1,5 +1,5 @@
 // cf_api_attrib.h -- host side of the attribution entry points (input gradients, attention maps, pCRE deletion, pCRE coalitions, integrated
-// gradients, perturbation scan).  Part of cf_api.hip's single translation unit: included there behind cf_api_bwd.h, not on its own.
+// gradients, perturbation scan, histone-mark coalitions).  Part of cf_api.hip's single translation unit: included there behind cf_api_bwd.h, not on its own.
 #pragma once
 
 // k_input_grad's dynamic LDS size; the first call sets the kernel's attribute.  0: that failed (`who`: the entry point, for the error text).
@@ -760,4 +760,143 @@ extern "C" int cf_perturbation_scan_regions(cf_handle* h, const cf_batch* bt, co
     h->x0_fwd = false;
     forward_counted(h, launches0);
     return rv ? -1 : 0;
+}
+
+// Histone-mark coalitions (cf_marks.h).  mark_check: what the three entry points check alike, in front of anything launched -- the
+// handle, the batch, riders, the options: the player count, the player words, the scale.
+static int mark_check(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, const char* who) {
+    if (attrib_open(h, bt, true, who)) return -1;
+    if (!o) return fail("%s: null opts", who);
+    const cf_config& c = h->cfg;
+    const int S = c.i_max, F = c.n_feats;
+    if (o->n_players < 1 || o->n_players > kCoalMaxS) return fail("%s: n_players = %d outside 1..%d", who, o->n_players, kCoalMaxS);
+    if (!o->player_marks || !o->player_regions) return fail("%s: null player_marks / player_regions", who);
+    for (int p = 0; p < o->n_players; ++p) {
+        const unsigned pm = o->player_marks[p], pr = o->player_regions[p];
+        if (!pm) return fail("%s: player_marks[%d] = 0: a player names at least one mark", who, p);
+        if (!pr) return fail("%s: player_regions[%d] = 0: a player names at least one region (bit 0 the promoter, bit 1 + j pCRE slot j)", who, p);
+        if (F < 32 && pm >> F) return fail("%s: player_marks[%d] = 0x%x names a mark >= n_feats = %d", who, p, pm, F);
+        if (pr >> S >> 1) return fail("%s: player_regions[%d] = 0x%x names a region above i_max = %d", who, p, pr, S);
+    }
+    if (!(o->scale >= 0.f) || !std::isfinite(o->scale)) return fail("%s: scale = %g: a finite factor >= 0", who, (double)o->scale);
+    return 0;
+}
+
+// The coalition words (validated) and the 2 P player words into the workspace's word table: [words | marks_p | regions_p].
+static int mark_upload(cf_handle* h, const cf_mark_opts* o, const uint32_t* keep, int n_coal, hipStream_t st, const char* who) {
+    const int P = o->n_players;
+    if (n_coal < 1) return fail("%s: n_coal = %d: at least 1 coalition", who, n_coal);
+    if (!keep) return fail("%s: null keep", who);
+    for (int k = 0; k < n_coal; ++k)
+        if (P < 32 && keep[k] >> P) return fail("%s: keep[%d] = 0x%x names a player >= n_players = %d", who, k, keep[k], P);
+    if (attrib_ws(h, who) || h->aw.words.need((size_t)n_coal + 2 * P, 256, who)) return -1;
+    unsigned* tab = h->aw.words;
+    HIP_TRY(hipMemcpyAsync(tab, keep, (size_t)n_coal * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(tab + n_coal, o->player_marks, P * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(tab + n_coal + P, o->player_regions, P * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+// The B * n_coal rows of a mark-coalition call (gene-major; row (b, k) is word k of the table mark_upload wrote), every row through
+// the whole forward.  Per chunk of at most max_batch rows: k_mark_expand into the chunk workspace, then the launches of
+// cf_forward(save = 0) on the chunk, writing its slice of `logits`.  k_attc2 takes as many regions per workgroup as for the caller's B
+// genes (ag_genes), as scan_region_rows: the result does not depend on max_batch.
+static int mark_rows(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, int n_coal, float* logits, hipStream_t st) {
+    const cf_config& c = h->cfg;
+    const int nres = c.n_res, cap = c.max_batch, B = bt->B, P = o->n_players;
+    MarkExpandArgs ea;
+    memset(&ea, 0, sizeof ea);
+    cf_batch cb;      // the chunk's batch: the rows' copies
+    chunk_rows(h, bt, &ea.rows, &cb);
+    for (int r = 0; r < nres; ++r) {
+        ea.pf_in[r] = bt->promoter_feats[r];
+        ea.cf_in[r] = bt->pcre_feats[r];
+        ea.pf_out[r] = h->aw.row[r];
+        ea.cf_out[r] = h->aw.row[kMaxRes + r];
+    }
+    ea.freq_in = bt->interaction_freq;
+    ea.freq_out = h->aw.row[2 * kMaxRes];
+    ea.words = h->aw.words;
+    ea.players = h->aw.words + n_coal;
+    ea.scale = o->scale;
+    ea.n_coal = n_coal, ea.P = P, ea.F = c.n_feats;
+    const long long launches0 = g_launches, rows = (long long)B * n_coal;
+    auto run = [&]() -> int {
+        for (long long g0 = 0; g0 < rows; g0 += cap) {
+            const int n = (int)std::min<long long>(cap, rows - g0);
+            ea.g0 = g0;
+            hipLaunchKernelGGL(k_mark_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, ea);
+            LAUNCH_CHECK("k_mark_expand");
+            cb.B = n;
+            if (forward_trunk(h, &cb, 0, st, B) || forward_reg_head(h, &cb, logits + (size_t)g0 * c.n_out, 0, st, nullptr)) return -1;
+        }
+        return 0;
+    };
+    const int rv = run();
+    h->x0_fwd = false;
+    forward_counted(h, launches0);
+    return rv ? -1 : 0;
+}
+
+extern "C" int cf_mark_coalitions(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, const uint32_t* keep, int n_coal, float* logits,
+                                  void* stream) {
+    const char* who = "cf_mark_coalitions";
+    if (mark_check(h, bt, o, who)) return -1;
+    if (!logits) return fail("%s: null logits", who);
+    hipStream_t st = (hipStream_t)stream;
+    if (mark_upload(h, o, keep, n_coal, st, who)) return -1;
+    return mark_rows(h, bt, o, n_coal, logits, st);
+}
+
+// All 2^P coalitions through mark_upload + mark_rows (word m at column m), then k_shapley with S = P.
+extern "C" int cf_mark_shapley(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, float* phi, float* logits_all, void* stream) {
+    const char* who = "cf_mark_shapley";
+    if (mark_check(h, bt, o, who)) return -1;
+    if (!phi) return fail("%s: null phi", who);
+    const cf_config& c = h->cfg;
+    const int P = o->n_players, n = 1 << P;
+    float* rows = coalition_out_rows(h, logits_all, n, who);
+    if (!rows) return -1;
+    std::vector<uint32_t> keep(n);
+    for (int m = 0; m < n; ++m) keep[m] = (uint32_t)m;
+    hipStream_t st = (hipStream_t)stream;
+    if (mark_upload(h, o, keep.data(), n, st, who) || mark_rows(h, bt, o, n, rows, st)) return -1;
+    ShapleyArgs sa;
+    memset(&sa, 0, sizeof sa);
+    sa.v = rows, sa.phi = phi, sa.S = P, sa.n_out = c.n_out;
+    double fact[kCoalMaxS + 1] = {1.0};
+    for (int k = 1; k <= P; ++k) fact[k] = fact[k - 1] * k;
+    for (int k = 0; k < P; ++k) sa.w[k] = (float)(fact[k] * fact[P - k - 1] / fact[P]);
+    hipLaunchKernelGGL(k_shapley, dim3(bt->B, P), dim3(kShapThreads), 0, st, sa);
+    LAUNCH_CHECK("k_shapley");
+    forward_one_more(h);
+    return 0;
+}
+
+// The 1 + P + P (P - 1) / 2 pair-deletion coalitions (N = 2^P - 1; N without i; N without i and j, i < j) through mark_upload +
+// mark_rows, then k_epistasis with S = P.
+extern "C" int cf_mark_epistasis(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, float* eps, float* logits_pairs, void* stream) {
+    const char* who = "cf_mark_epistasis";
+    if (mark_check(h, bt, o, who)) return -1;
+    if (!eps) return fail("%s: null eps", who);
+    const cf_config& c = h->cfg;
+    const int P = o->n_players;
+    const uint32_t N = (1u << P) - 1u;
+    std::vector<uint32_t> keep;
+    keep.push_back(N);
+    for (int i = 0; i < P; ++i) keep.push_back(N & ~(1u << i));
+    for (int i = 0; i < P; ++i)
+        for (int j = i + 1; j < P; ++j) keep.push_back(N & ~(1u << i) & ~(1u << j));
+    const int R = (int)keep.size();
+    float* rows = coalition_out_rows(h, logits_pairs, R, who);
+    if (!rows) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    if (mark_upload(h, o, keep.data(), R, st, who) || mark_rows(h, bt, o, R, rows, st)) return -1;
+    EpistasisArgs ea;
+    ea.v = rows, ea.eps = eps, ea.B = bt->B, ea.S = P, ea.n_out = c.n_out;
+    const long long n = (long long)bt->B * P * P * c.n_out;
+    hipLaunchKernelGGL(k_epistasis, dim3((int)std::min<long long>((n + kShapThreads - 1) / kShapThreads, 1024)), dim3(kShapThreads), 0, st, ea);
+    LAUNCH_CHECK("k_epistasis");
+    forward_one_more(h);
+    return 0;
 }

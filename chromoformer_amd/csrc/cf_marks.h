@@ -1,0 +1,102 @@
+// cf_marks.h -- histone-mark coalitions (cf_mark_coalitions, cf_mark_shapley, cf_mark_epistasis; included by cf_api.hip behind cf_scan.h).
+//
+// The players of the game are MARKS, each optionally restricted to a set of regions.  Player p is a pair of words: marks_p (bit f:
+// mark f) and regions_p (bit 0: the promoter, bit 1 + j: pCRE slot j), both non-zero.  A coalition is a 32-bit word m, bit p set =
+// player p PRESENT.  Row (b, m) is the inference forward of gene b with these inputs: for every region rho,
+//     gone(rho) = OR of marks_p over the absent players p whose regions_p has bit rho
+// and every element of region rho, at every resolution and in every row, whose mark f has its bit in gone(rho) becomes
+//     u' = log1pf(s expm1f(u))                                  fp32, each operation rounded (no contraction): ig_signal of cf_ig.h
+// Every other element keeps its bits; all masks and interaction_freq are the gene's own.
+//   * Binning is linear: this is exactly the feature the binning produces when the raw samples of those marks are scaled by s over the
+//     whole region (the rule of cf_scan.h with a window that covers the region).
+//   * s = 0 (the default of the Python layer) erases the mark: a non-negative finite feature becomes exactly +0.
+//   * Padded rows hold zeros and keep their bits (log1pf(s expm1f(0)) = 0), so no row extents are needed: every row is treated alike.
+//   * Players may overlap: an element is scaled ONCE if any player that covers it is absent.
+//   * Limits are the scan's: u < ~80 (expm1f overflows past 88); a negative feature with 1 + s m <= 0 gives NaN.
+//
+// Rows are (gene, coalition) pairs, gene-major (gv = b * n_coal + k, word k of a device table), in chunks of at most max_batch rows.
+// One kernel, no atomics, no scratch, 68 bytes of LDS:
+//   k_mark_expand   per (chunk row, resolution, slice): the T = i_max + 1 words gone(rho) once per workgroup from the row's coalition
+//                   word and the 2 P player words; then its slice of the row's promoter and pCRE features (every element written once,
+//                   float4 where the row allows; the mark of element e is e % F; a region with gone = 0 is a plain copy); slice 0 also
+//                   the row's compact pad-mask rows and interaction mask, at resolution 0 its interaction_freq.  kMarkSlices
+//                   workgroups share a (row, resolution): one workgroup per pair leaves the finest resolution's 25,200 floats to 256
+//                   threads, ~25 dependent load / store rounds, and the launch latency-bound.
+// The reducers are k_shapley and k_epistasis of cf_coalition.h with S = P.
+#pragma once
+
+namespace cf {
+
+constexpr int kMarkSlices = 8;         // workgroups per (chunk row, resolution): blockIdx.z
+
+struct MarkExpandArgs {
+    const float* pf_in[kMaxRes];       // the caller's promoter_feats [B, L, F]
+    const float* cf_in[kMaxRes];       // pcre_feats [B, S, L, F]
+    float* pf_out[kMaxRes];            // the chunk's copies, [max_batch, L, F] / [max_batch, S, L, F]
+    float* cf_out[kMaxRes];
+    RowCopyArgs rows;                  // the masks of the chunk's rows (cf_rows.h)
+    const float* freq_in;              // [B, T, T]
+    float* freq_out;
+    const unsigned* words;             // device [n_coal]: bit p set: player p present
+    const unsigned* players;           // device [2 P]: marks_p, then regions_p
+    long long g0;                      // first row of the chunk
+    float scale;
+    int n_coal, P, F;
+};
+
+__device__ __forceinline__ float mark_elem(float x, unsigned gone, int f, float s) { return (gone >> f) & 1u ? ig_signal(s, x) : x; }
+
+// dst[0, n) = src[0, n), n = a whole number of regions of LF elements each: element e lies in region e / LF (its word: gone[e / LF])
+// and carries mark e % F (LF is a multiple of F).  The workgroup takes the blocks blockIdx.z, blockIdx.z + kMarkSlices, ... of
+// kIgxThreads float4s (or floats).
+__device__ __forceinline__ void mark_copy(const float* __restrict__ src, float* __restrict__ dst, int n, int LF, int F, const unsigned* gone, float s) {
+    const int first = blockIdx.z * kIgxThreads + threadIdx.x, step = kMarkSlices * kIgxThreads;
+    const bool vec = (n & 3) == 0 && LF >= 4 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+    if (vec) {
+        const float4* s4 = reinterpret_cast<const float4*>(src);
+        float4* d4 = reinterpret_cast<float4*>(dst);
+        for (int k = first; k < n / 4; k += step) {
+            float4 x = s4[k];
+            const int e = 4 * k, rho = e / LF, rem = e - rho * LF;
+            const int over = LF - rem;                               // elements over .. 3 of the float4 lie in region rho + 1 (LF % 4 != 0)
+            const unsigned ga = gone[rho], gb = over < 4 ? gone[rho + 1] : ga;
+            if (ga | gb) {
+                const int f0 = rem % F, f1 = f0 + 1 == F ? 0 : f0 + 1, f2 = f1 + 1 == F ? 0 : f1 + 1, f3 = f2 + 1 == F ? 0 : f2 + 1;
+                x.x = mark_elem(x.x, ga, f0, s);
+                x.y = mark_elem(x.y, over > 1 ? ga : gb, f1, s);
+                x.z = mark_elem(x.z, over > 2 ? ga : gb, f2, s);
+                x.w = mark_elem(x.w, over > 3 ? ga : gb, f3, s);
+            }
+            d4[k] = x;
+        }
+    } else {
+        for (int e = first; e < n; e += step) {
+            const int rho = e / LF;
+            dst[e] = mark_elem(src[e], gone[rho], (e - rho * LF) % F, s);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kIgxThreads) void k_mark_expand(MarkExpandArgs a) {
+    __shared__ unsigned gone[kCoalMaxS + 1];      // gone(rho), rho = 0 .. i_max: 68 bytes
+    const int i = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
+    const long long gv = a.g0 + i;
+    const int b = (int)(gv / a.n_coal);
+    const int L = a.rows.L[r], S = a.rows.S, F = a.F, LF = L * F, P = a.P;
+    if (tid <= S) {
+        const unsigned m = a.words[gv - (long long)b * a.n_coal];
+        unsigned g = 0;
+        for (int p = 0; p < P; ++p)
+            if (!((m >> p) & 1u) && ((a.players[P + p] >> tid) & 1u)) g |= a.players[p];
+        gone[tid] = g;
+    }
+    __syncthreads();
+    mark_copy(a.pf_in[r] + (size_t)b * LF, a.pf_out[r] + (size_t)i * LF, LF, LF, F, gone, a.scale);
+    mark_copy(a.cf_in[r] + (size_t)b * S * LF, a.cf_out[r] + (size_t)i * S * LF, S * LF, LF, F, gone + 1, a.scale);
+    if (blockIdx.z) return;
+    rows_pad_masks(a.rows, r, b, i);
+    rows_interaction_mask(a.rows, r, b, i);
+    if (r == 0) rows_copy_tt(a.freq_in, a.freq_out, b, i, a.rows.TT);
+}
+
+}  // namespace cf

@@ -779,6 +779,95 @@ class ChromoformerBase(nn.Module):
         from .attribution import perturbation_scan
         return perturbation_scan(self, dataset, genes=genes, regions=regions, scale=scale, width=width, mark_sets=mark_sets, bsz=bsz, store=store)
 
+    def _mark_opts(self, players, scale):
+        """players (a mark_players spec) and scale -> (cf_mark_opts, the arrays it points to, names)."""
+        from .attribution import mark_players
+        marks, regions, names = mark_players(players, self.n_feats, self.i_max)
+        opts = _lib.cf_mark_opts()
+        opts.n_players, opts.scale = len(marks), float(scale)
+        opts.player_marks, opts.player_regions = marks.ctypes.data, regions.ctypes.data
+        return opts, (marks, regions), names
+
+    @torch.no_grad()
+    def mark_coalitions(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                        interaction_freq=None, keep=None, players="marks", scale=0.0):
+        """The prediction under histone-mark coalitions (cf_mark_coalitions) -> logits [B, n_coal, n_out] on the model's device, no
+        autograd graph.  The players are marks, each optionally restricted to regions (attribution.mark_players: "marks",
+        "compartments", "regions" or a list of (marks, regions) pairs).  `keep`: a sequence / array of ints, bit p set = player p
+        present, or a bool array [n_coal, P].  Column c is the inference forward with the raw signal of every ABSENT player's marks
+        scaled by `scale` (0 erases, the default) over the player's regions: a feature u = log(1 + mean) becomes
+        log1p(scale * expm1(u)), exactly what binning the scaled signal gives; an element covered by several absent players is scaled
+        once.  The full word 2^P - 1 is the prediction (model(...) under no_grad, bit-equal).  Features must stay below ~80 (expm1 in
+        fp32).  The first argument may also be a packed batch (an engine.Slot or a pack_batch result), with nothing after it.  The
+        pass overwrites the activations a grad-enabled model(...) keeps for its backward: such a pending backward() raises."""
+        from .attribution import mark_coalition_words
+        if keep is None:
+            raise ValueError("mark_coalitions: keep is required: the coalition words (bit p set: player p present)")
+        opts, _alive, _names = self._mark_opts(players, scale)
+        words = mark_coalition_words(keep, opts.n_players, "mark_coalitions")
+        bs, _keep, book = self._attrib_call("mark_coalitions", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        logits = torch.empty(bs.B, len(words), self.n_out, device=self._device)      # (written in full by the library)
+        st = book()
+        _lib.check(_lib.lib().cf_mark_coalitions(self._handle, C.byref(bs), C.byref(opts), words.ctypes.data, len(words), logits.data_ptr(), st),
+                   "cf_mark_coalitions")
+        return logits
+
+    @torch.no_grad()
+    def mark_shapley(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                     interaction_freq=None, players="marks", scale=0.0, return_coalitions=False):
+        """Exact Shapley values of the histone marks (cf_mark_shapley) -> (phi, info), tensors on the model's device, no autograd graph:
+
+          phi                 [B, P, n_out]: player p's average marginal contribution to each logit over all orders of adding the
+                              players to the gene with every player absent; exactly 0 for a player whose elements are all zeros
+          info["logits"]      [B, n_out]: the prediction (every player present; model(...) under no_grad, bit-equal)
+          info["erased"]      [B, n_out]: every player absent
+          info["delta"]       [B, n_out]: phi.sum(1) - (logits - erased), the efficiency gap (rounding only)
+          info["players"]     the players' names
+          info["coalitions"]  [B, 2^P, n_out], with return_coalitions: the logits of every coalition, word m at column m
+
+        players and scale as in mark_coalitions; all 2^P coalitions (128 for the seven marks) run from one call, in logit space, where
+        efficiency holds.  The packed forms of the first argument and the effect on a pending backward() are those of mark_coalitions."""
+        opts, _alive, names = self._mark_opts(players, scale)
+        bs, _keep, book = self._attrib_call("mark_shapley", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        P = opts.n_players
+        n = 1 << P
+        rows = torch.empty(bs.B, n, self.n_out, device=self._device)      # (both written in full by the library)
+        phi = torch.empty(bs.B, P, self.n_out, device=self._device)
+        st = book()
+        _lib.check(_lib.lib().cf_mark_shapley(self._handle, C.byref(bs), C.byref(opts), phi.data_ptr(), rows.data_ptr(), st), "cf_mark_shapley")
+        info = {"logits": rows[:, n - 1].clone(), "erased": rows[:, 0].clone(), "players": names}
+        info["delta"] = phi.sum(1) - (info["logits"] - info["erased"])
+        if return_coalitions:
+            info["coalitions"] = rows
+        return phi, info
+
+    @torch.no_grad()
+    def mark_epistasis(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                       interaction_freq=None, players="marks", scale=0.0):
+        """Pair epistasis of the histone-mark players (cf_mark_epistasis) -> (eps, info), tensors on the model's device, no autograd
+        graph.  With v(...) the logits with the named players absent:
+
+          eps[:, i, j]    [B, P, P, n_out]: ((v() - v(i)) - v(j)) + v(i, j) for i != j, exactly symmetric: 0 when the two marks add
+                          up, non-zero when they are redundant or cooperate; eps[:, i, i] = v() - v(i), the leave-one-out effect
+          info["logits"]  [B, n_out]: v(), the prediction;  info["single"]  [B, P, n_out]: v(i);  info["players"]  the names
+
+        The 1 + P + P (P - 1) / 2 rows (attribution.coalition_table("pairs", P)) run from one call.  players, scale, the packed forms
+        of the first argument and the effect on a pending backward() are those of mark_coalitions."""
+        opts, _alive, names = self._mark_opts(players, scale)
+        bs, _keep, book = self._attrib_call("mark_epistasis", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        P = opts.n_players
+        rows = torch.empty(bs.B, 1 + P + P * (P - 1) // 2, self.n_out, device=self._device)      # (both written in full by the library)
+        eps = torch.empty(bs.B, P, P, self.n_out, device=self._device)
+        st = book()
+        _lib.check(_lib.lib().cf_mark_epistasis(self._handle, C.byref(bs), C.byref(opts), eps.data_ptr(), rows.data_ptr(), st), "cf_mark_epistasis")
+        return eps, {"logits": rows[:, 0].clone(), "single": rows[:, 1:1 + P].clone(), "players": names}
+
+    def mark_shapley_dataset(self, dataset, genes=None, players="marks", scale=0.0, epistasis=False, bsz=None, store=None):
+        """mark_shapley (and optionally mark_epistasis) over the genes of a ChromoformerDataset
+        (chromoformer_amd.attribution.mark_shapley, a generator of per-gene dicts)."""
+        from .attribution import mark_shapley
+        return mark_shapley(self, dataset, genes=genes, players=players, scale=scale, epistasis=epistasis, bsz=bsz, store=store)
+
     def raw_signal_gradients(self, dataset, genes=None, target=None, times_input=False, bsz=None):
         """Raw-signal saliency of the genes of a ChromoformerDataset: the gradient (or gradient x input) of logit column `target` with
         respect to the raw fp16 signals, per gene one track per histone mark for the promoter window and every pCRE, in genomic

@@ -165,6 +165,47 @@ def write_pcre_coalition_values(model, store, bsz, shapley_out=None, epistasis_o
         eps.flush()
 
 
+def write_mark_values(model, store, bsz, gene_ids, shapley_out=None, epistasis_out=None, regression=False, players="marks", scale=0.0):
+    """Exact Shapley values and / or pair epistasis of the histone marks of every gene of a device-resident store, in store order, in
+    LOGIT space of the prediction's column (1 for the classifier, 0 for the regressor: efficiency holds there, not after the
+    sigmoid).  shapley_out: an .npz with gene_ids [n], players [P] (names), phi [n, P], logits [n] and erased [n] (phi sums to
+    their difference); epistasis_out: a float32 .npy [n, P, P].  Per batch: one device gather into a Slot, one model.mark_shapley
+    and / or one model.mark_epistasis."""
+    import ctypes as C
+
+    from . import _lib
+    from .attribution import mark_players
+    n, dev, L = len(store), model._device, _lib.lib()
+    names = mark_players(players, model.n_feats, model.i_max)[2]
+    P, t = len(names), 0 if regression else 1
+    phi, logits, erased = torch.empty(n, P), torch.empty(n), torch.empty(n)
+    eps = np.lib.format.open_memmap(epistasis_out, mode="w+", dtype=np.float32, shape=(n, P, P)) if epistasis_out else None
+    struct = store.struct()
+    order = torch.arange(n, dtype=torch.int32, device=dev)
+    slots = {}
+    st = torch.cuda.current_stream(dev).cuda_stream
+    for lo in range(0, n, bsz):
+        B = min(bsz, n - lo)
+        slot = slots.get(B) or slots.setdefault(B, Slot(model, B))
+        cursor = torch.tensor([0, 1, 0, 0], dtype=torch.int32).to(dev)
+        _lib.check(L.cf_gather_batch(model._handle, C.byref(struct), order[lo:].data_ptr(), cursor.data_ptr(), C.byref(slot.struct), None, st),
+                   "cf_gather_batch")
+        if shapley_out:
+            p, info = model.mark_shapley(slot, players=players, scale=scale)
+            phi[lo:lo + B] = p[..., t].cpu()
+            logits[lo:lo + B] = info["logits"][:, t].cpu()
+            erased[lo:lo + B] = info["erased"][:, t].cpu()
+        if eps is not None:
+            eps[lo:lo + B] = model.mark_epistasis(slot, players=players, scale=scale)[0][..., t].cpu().numpy()
+        if int(cursor[2].item()):
+            raise RuntimeError("write_mark_values: the device-side gather reported errors at gene %d (store / order mismatch)" % lo)
+    if shapley_out:
+        with open(shapley_out, "wb") as f:      # (a file object: np.savez would append .npz to a name without it)
+            np.savez(f, gene_ids=np.array(list(gene_ids)), players=np.array(names), phi=phi.numpy(), logits=logits.numpy(), erased=erased.numpy())
+    if eps is not None:
+        eps.flush()
+
+
 def write_integrated_gradients(model, store, bsz, ig_dir, n_steps=50, method="gausslegendre", target=None):
     """Integrated gradients of every gene of a device-resident store, in store order, into `ig_dir`: promoter_feats_{b}.npy
     [n, L, F], pcre_feats_{b}.npy [n, i_max, L, F], interaction_freq.npy [n, T, T] and delta.npy [n] (float32 .npy memory maps;
@@ -328,7 +369,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
             binsizes=(2000, 500, 100), progress=False, store_path=None, attention_dir=None, embeddings_out=None,
             pcre_ablation_out=None, ig_dir=None, ig_steps=50, ig_method="gausslegendre", ig_target=None, raw_saliency_dir=None,
             raw_saliency_target=None, raw_saliency_times_input=False, raw_ig_dir=None, scan_out=None, scan_scale=0.0, scan_width=1,
-            scan_regions="promoter", pcre_shapley_out=None, pcre_epistasis_out=None):
+            scan_regions="promoter", pcre_shapley_out=None, pcre_epistasis_out=None, mark_shapley_out=None, mark_epistasis_out=None,
+            mark_players="marks", mark_scale=0.0):
     """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file.  attention_dir / embeddings_out: also
     write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps); pcre_ablation_out:
     the predictions with each pCRE deleted (write_pcre_ablation); ig_dir: integrated gradients of every gene
@@ -337,7 +379,9 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     raw_ig_dir: integrated gradients with respect to the raw signals, one .npz per gene (write_raw_integrated_gradients; ig_steps,
     ig_method and ig_target apply; needs the raw .npy files too); scan_out: the in-silico perturbation scan of every gene, one .npz
     (write_perturbation_scan; scan_scale, scan_width and scan_regions apply; served by a packed store as well); pcre_shapley_out /
-    pcre_epistasis_out: exact Shapley values / pair-deletion epistasis of the pCREs, in logit space (write_pcre_coalition_values)."""
+    pcre_epistasis_out: exact Shapley values / pair-deletion epistasis of the pCREs, in logit space (write_pcre_coalition_values);
+    mark_shapley_out / mark_epistasis_out: exact Shapley values / pair epistasis of the histone marks, in logit space
+    (write_mark_values; mark_players and mark_scale apply)."""
     seed_everything(seed)
     meta = pd.read_csv(meta_path)
     genes = meta.gene_id.tolist()
@@ -369,6 +413,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         write_pcre_ablation(model, store, bsz, pcre_ablation_out, regression)
     if pcre_shapley_out or pcre_epistasis_out:
         write_pcre_coalition_values(model, store, bsz, pcre_shapley_out, pcre_epistasis_out, regression)
+    if mark_shapley_out or mark_epistasis_out:
+        write_mark_values(model, store, bsz, genes, mark_shapley_out, mark_epistasis_out, regression, mark_players, mark_scale)
     if ig_dir:
         write_integrated_gradients(model, store, bsz, ig_dir, ig_steps, ig_method, ig_target)
     if scan_out:
@@ -426,6 +472,16 @@ def build_parser():
     ap.add_argument("--scan-width", type=int, default=None, help="window width of --scan-out in coarsest bins (default 1)")
     ap.add_argument("--scan-regions", default=None, choices=("promoter", "all"), help="--scan-out scans the promoter (default) or also every "
                     "pCRE slot: pcres [n, i_max, n_sets, W]")
+    from .attribution import MARK_PLAYER_SPECS
+    ap.add_argument("--mark-shapley-out", default=None, help="also write the exact Shapley values of the histone marks to this .npz file, in "
+                    "metadata order and in LOGIT space of the prediction's column: gene_ids, players (names), phi [n_genes, P], logits and "
+                    "erased (every player absent; phi sums to their difference) (model.mark_shapley)")
+    ap.add_argument("--mark-epistasis-out", default=None, help="also write the pair epistasis of the histone marks to this .npy file: "
+                    "[n_genes, P, P] in logit space, symmetric, the leave-one-out effects on the diagonal (model.mark_epistasis)")
+    ap.add_argument("--mark-players", default=None, choices=MARK_PLAYER_SPECS, help="the players of --mark-shapley-out / --mark-epistasis-out: "
+                    "each mark in every region (marks, the default), each mark in the promoter and in the pCREs (compartments), or all marks "
+                    "per region (regions)")
+    ap.add_argument("--mark-scale", type=float, default=None, help="what an absent mark's raw signal is scaled by: 0 erases it (default)")
     return ap
 
 
@@ -448,6 +504,10 @@ def main(argv=None):
         ap.error("--scan-scale must be a finite factor >= 0")
     if args.scan_width is not None and args.scan_width < 1:
         ap.error("--scan-width must be at least 1")
+    if not args.mark_shapley_out and not args.mark_epistasis_out and (args.mark_players is not None or args.mark_scale is not None):
+        ap.error("--mark-players / --mark-scale need --mark-shapley-out or --mark-epistasis-out")
+    if args.mark_scale is not None and not (args.mark_scale >= 0 and np.isfinite(args.mark_scale)):
+        ap.error("--mark-scale must be a finite factor >= 0")
     meta, pred = predict(args.meta, args.npy_dir, args.weights, args.regression, progress=True, store_path=args.store,
                          attention_dir=args.attention_dir, embeddings_out=args.embeddings_out, pcre_ablation_out=args.pcre_ablation_out,
                          ig_dir=args.ig_dir, ig_steps=50 if args.ig_steps is None else args.ig_steps,
@@ -455,7 +515,9 @@ def main(argv=None):
                          raw_saliency_target=args.raw_saliency_target, raw_saliency_times_input=args.raw_saliency_times_input,
                          raw_ig_dir=args.raw_ig_dir, scan_out=args.scan_out, scan_scale=0.0 if args.scan_scale is None else args.scan_scale,
                          scan_width=1 if args.scan_width is None else args.scan_width, scan_regions=args.scan_regions or "promoter",
-                         pcre_shapley_out=args.pcre_shapley_out, pcre_epistasis_out=args.pcre_epistasis_out)
+                         pcre_shapley_out=args.pcre_shapley_out, pcre_epistasis_out=args.pcre_epistasis_out,
+                         mark_shapley_out=args.mark_shapley_out, mark_epistasis_out=args.mark_epistasis_out,
+                         mark_players=args.mark_players or "marks", mark_scale=0.0 if args.mark_scale is None else args.mark_scale)
     print("Predicting expressions for %d genes." % len(meta))
     meta["prediction"] = pred
     meta.to_csv(args.output, index=False)

@@ -377,6 +377,55 @@ typedef struct cf_scan_regions_opts {
  * mark_sets, B > max_batch, width < 1, n_sets < 1, a negative or non-finite scale, a mark bit >= n_feats, non-nested n_bins, armed
  * riders), regions == 0, a region bit above i_max. */
 int cf_perturbation_scan_regions(cf_handle* h, const cf_batch* batch, const cf_scan_regions_opts* opts, float* logits, void* stream);
+/* Histone-mark coalitions, exact Shapley values of the marks and their pair epistasis (interpretation): which marks carry the
+ * prediction, and do they act alone or together?  The players of the game are MARKS, each optionally restricted to a set of regions.
+ * Player p is a pair of words: player_marks[p] (bit f: mark f; non-zero, no bit >= n_feats) and player_regions[p] (bit 0: the promoter,
+ * bit 1 + j: pCRE slot j; non-zero, no bit above i_max).  A coalition is a 32-bit word m, bit p set = player p PRESENT.  Row (b, m) is
+ * the inference forward of gene b with these inputs: for every region rho,
+ *   gone(rho) = OR of player_marks[p] over the absent players p whose player_regions[p] has bit rho
+ * and every element of region rho (every row, every resolution) whose mark f has its bit in gone(rho) becomes
+ *   u' = log1pf(s expm1f(u))                          fp32, each operation rounded (no contraction): the rule of the perturbation scan
+ * Every other element keeps its bits; all masks and interaction_freq are gene b's.  Binning is linear, so this is exactly the feature
+ * the binning produces when the raw samples of those marks are scaled by s over the whole region.  s = 0 erases the mark: a
+ * non-negative finite feature becomes exactly +0.  Padded rows hold zeros and keep their bits.  Players may overlap: an element is
+ * scaled once if any player that covers it is absent.  Limits: those of the scan (u < ~80; a negative feature with 1 + s m <= 0 gives
+ * NaN). */
+typedef struct cf_mark_opts {
+    int n_players;                   /* 1..16 */
+    const unsigned* player_marks;    /* host [n_players], read before the call returns */
+    const unsigned* player_regions;  /* host [n_players] */
+    float scale;                     /* s >= 0, finite: what an ABSENT player's elements are scaled by; 0 erases */
+} cf_mark_opts;                      /* 32 bytes */
+/* cf_mark_coalitions: keep is a HOST array of n_coal words (read before the call returns); logits [B, n_coal, n_out], gene-major
+ * (b * n_coal + c).  The full word 2^P - 1 is cf_forward(save = 0), bit for bit.  Rows run in chunks of at most max_batch; per chunk
+ * one k_mark_expand writes the rows' inputs -- features of every region and resolution, each element once, compact pad-mask rows (all L
+ * rows of a full promoter mask with embed.n_layers > 1), interaction masks, frequencies -- into the chunk buffers of
+ * cf_integrated_gradients (whichever call comes first allocates them; cf_destroy frees them), then the launches of
+ * cf_forward(save = 0) run on the chunk and write its slice of `logits`:
+ *   cf_launch_counts fwd = ceil(B * n_coal / max_batch) * (1 + n_fwd),  n_fwd = what cf_forward(save = 0) issues.
+ * The coalition words and the player words travel in the device table the handle owns (grown on demand).  Deterministic (no atomics).
+ * Off the fused trunk k_attc2's regions per workgroup are chosen as for the caller's B genes, so the result does not depend on
+ * max_batch.  Overwrites the activations a cf_forward(save >= 1) kept: no cf_backward* may follow without a new saving forward.
+ * Parameters, gradients and moments are untouched.
+ * Refused by name, before anything is launched: a null handle / batch / opts / keep / logits, B > max_batch, n_players outside 1..16,
+ * a null or zero player word, a mark bit >= n_feats, a region bit above i_max, n_coal < 1, a keep bit >= n_players, a negative or
+ * non-finite scale, armed riders. */
+int cf_mark_coalitions(cf_handle* h, const cf_batch* batch, const cf_mark_opts* opts, const uint32_t* keep, int n_coal, float* logits,
+                       void* stream);
+/* Exact Shapley values of the P players: all 2^P coalitions through the routine above (word m at column m), then one k_shapley with
+ * the P weights w(k) = k! (P - k - 1)! / P! computed on the host in double and rounded to fp32 (see cf_pcre_shapley: the same kernel, a
+ * fixed order, every operation rounded to fp32).  phi [B, P, n_out]; efficiency: sum_p phi[b, p] = v[b, 2^P - 1] - v[b, 0] up to
+ * rounding; a player whose elements are all zeros (a dummy slot) is a null player, phi exactly 0.  logits_all: [B, 2^P, n_out], or
+ * NULL: the rows go to the handle-owned buffer of cf_pcre_shapley.  fwd = that of cf_mark_coalitions with n_coal = 2^P, plus 1.
+ * Refusals as above (null phi). */
+int cf_mark_shapley(cf_handle* h, const cf_batch* batch, const cf_mark_opts* opts, float* phi, float* logits_all, void* stream);
+/* Pair epistasis of the players.  With N = 2^P - 1 the rows are: 0: N; 1 + i: N without i; then N without i and j for the pairs i < j
+ * in lexicographic order (1 + P + P (P - 1) / 2 rows), through the routine above, then one k_epistasis (see cf_pcre_epistasis):
+ *   eps[b, i, j] = ((v_N - v_{N\i}) - v_{N\j}) + v_{N\{i,j}} for i < j, fp32, each operation rounded; eps[b, j, i] carries its bits;
+ *   eps[b, i, i] = v_N - v_{N\i}.
+ * eps [B, P, P, n_out].  logits_pairs: [B, 1 + P + P (P - 1) / 2, n_out], or NULL (the handle-owned buffer).  fwd = that of
+ * cf_mark_coalitions with that n_coal, plus 1.  Refusals as above (null eps). */
+int cf_mark_epistasis(cf_handle* h, const cf_batch* batch, const cf_mark_opts* opts, float* eps, float* logits_pairs, void* stream);
 /* torch.optim.AdamW.step (train.py:157, 196): decoupled weight decay, bias correction
  * from `step` (1-based), over [0, n_active). */
 int cf_adamw_step(cf_handle* h, float lr, float beta1, float beta2, float eps, float weight_decay,
