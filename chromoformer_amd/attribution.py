@@ -558,3 +558,83 @@ def mark_shapley(model, dataset, genes=None, players="marks", scale=0.0, epistas
             if epistasis:
                 out["eps"] = eps[i].copy()
             yield out
+
+
+def same_regions(dataset, donor_dataset, genes=None):
+    """The donor rule replaces a mark's signal over a region by the other cell type's signal over the SAME region: both datasets must
+    read the genes' promoters and pCREs at the same coordinates with the same geometry.  A pure host check (no device): raises
+    ValueError naming the geometry fields that differ (binsizes, w_max, w_prom, i_max, n_feats), genes the donor's metadata does not
+    hold, or up to five genes whose TSS, strand or pCRE list differ.  -> the genes checked (default: the dataset's)."""
+    ds, dn = dataset, donor_dataset
+    diff = []
+    for field in ("binsizes", "w_max", "w_prom", "i_max", "n_feats"):
+        a, b = getattr(ds, field), getattr(dn, field)
+        a, b = ([int(x) for x in a], [int(x) for x in b]) if field == "binsizes" else (int(a), int(b))
+        if a != b:
+            diff.append("%s %s != %s" % (field, a, b))
+    if diff:
+        raise ValueError("same_regions: the datasets differ in geometry: %s" % ", ".join(diff))
+    genes = list(ds.target_genes if genes is None else genes)
+    missing = [g for g in genes if g not in ds.genes or g not in dn.genes]
+    if missing:
+        raise ValueError("same_regions: gene(s) %s are not in both datasets' metadata (%d in all)" % (missing[:5], len(missing)))
+    bad = []
+    for g in genes:
+        a, b = ds.genes[g], dn.genes[g]
+        what = [name for name, same in (("tss", a["tss"][:2] == b["tss"][:2]), ("strand", a["tss"][2] == b["tss"][2]),
+                                        ("pcres", [tuple(p) for p in a["pcres"]] == [tuple(p) for p in b["pcres"]])) if not same]
+        if what:
+            bad.append("%s (%s)" % (g, ", ".join(what)))
+    if bad:
+        raise ValueError("same_regions: %d gene(s) do not have the same regions in the two datasets: %s%s"
+                         % (len(bad), "; ".join(bad[:5]), " ..." if len(bad) > 5 else ""))
+    return genes
+
+
+def mark_donor_shapley(model, dataset, donor_dataset, genes=None, players="marks", epistasis=False, bsz=None, store=None, donor_store=None):
+    """Exact Shapley values of the histone marks against a donor cell type, for the genes of two ChromoformerDatasets over the same
+    regions (same_regions): one model.mark_donor_shapley per batch, with epistasis=True also one model.mark_donor_epistasis -- which
+    mark changes account for the difference between the prediction in `dataset` and in `donor_dataset`?  A generator over `genes`
+    (ids; default: the dataset's) in chunks of at most min(bsz, model.max_batch) genes; per gene it yields a dict of host arrays:
+
+        gene_id            the id
+        phi                float32 [P, n_out]: the players' Shapley values, in logit space; phi.sum(0) = logits - donor up to rounding
+        logits             float32 [n_out]: the prediction (every player present)
+        donor              float32 [n_out]: every player's marks from the donor, under the gene's masks and frequencies
+        donor_prediction   float32 [n_out]: the plain forward of the donor's own batch, with its own frequencies: donor_prediction -
+                           donor is what the marks of the players do not explain
+        players            the players' names (mark_players)
+        eps                float32 [P, P, n_out], with epistasis=True: the pair epistasis, the leave-one-out effects on the diagonal
+
+    players as in mark_shapley.  The binned features come from `store` / `donor_store` (device-resident GeneStores holding `genes` in
+    order) if given, else from the packed store next to each dataset's raw files if one matches, else from the raw .npy files binned
+    on the device.  Parameters, gradients and optimiser state are left as they are; the pass overwrites the activations a
+    grad-enabled model(...) keeps for its backward."""
+    import torch
+    ds, dn = dataset, donor_dataset
+    binsizes = [int(b) for b in ds.binsizes]
+    _geometry_check("mark_donor_shapley", model, ds, binsizes)
+    genes, chunk = _genes_check("mark_donor_shapley", model, ds, genes, bsz)
+    same_regions(ds, dn, genes)
+    spec = players if isinstance(players, str) else list(players)
+    names = mark_players(spec, ds.n_feats, ds.i_max)[2]      # (refusals before anything is loaded)
+    store = _resident_store("mark_donor_shapley", ds, genes, binsizes, model._device, store)
+    donor_store = _resident_store("mark_donor_shapley", dn, genes, binsizes, model._device, donor_store)
+    keys = ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq")
+    for lo in range(0, len(genes), chunk):
+        ids = genes[lo:lo + chunk]
+        idx = list(range(lo, lo + len(ids)))
+        d, dd = store.batch(idx), donor_store.batch(idx)
+        args = tuple(d[k] for k in keys)
+        donor = ({b: t.contiguous() for b, t in dd["promoter_feats"].items()}, {b: t.contiguous() for b, t in dd["pcre_feats"].items()})
+        phi, info = model.mark_donor_shapley(*args, donor=donor, players=spec)
+        phi, logits, don = phi.cpu().numpy(), info["logits"].cpu().numpy(), info["donor"].cpu().numpy()
+        eps = model.mark_donor_epistasis(*args, donor=donor, players=spec)[0].cpu().numpy() if epistasis else None
+        with torch.no_grad():
+            pred = model(*(dd[k] for k in keys)).cpu().numpy()
+        for i, g in enumerate(ids):
+            out = dict(gene_id=g, phi=phi[i].copy(), logits=logits[i].copy(), donor=don[i].copy(), donor_prediction=pred[i].copy(),
+                       players=list(names))
+            if epistasis:
+                out["eps"] = eps[i].copy()
+            yield out

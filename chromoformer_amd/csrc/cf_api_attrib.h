@@ -1,5 +1,5 @@
 // cf_api_attrib.h -- host side of the attribution entry points (input gradients, attention maps, pCRE deletion, pCRE coalitions, integrated
-// gradients, perturbation scan, histone-mark coalitions).  Part of cf_api.hip's single translation unit: included there behind cf_api_bwd.h, not on its own.
+// gradients, perturbation scan, histone-mark coalitions and their donor form).  Part of cf_api.hip's single translation unit: included there behind cf_api_bwd.h, not on its own.
 #pragma once
 
 // k_input_grad's dynamic LDS size; the first call sets the kernel's attribute.  0: that failed (`who`: the entry point, for the error text).
@@ -762,29 +762,55 @@ extern "C" int cf_perturbation_scan_regions(cf_handle* h, const cf_batch* bt, co
     return rv ? -1 : 0;
 }
 
-// Histone-mark coalitions (cf_marks.h).  mark_check: what the three entry points check alike, in front of anything launched -- the
-// handle, the batch, riders, the options: the player count, the player words, the scale.
-static int mark_check(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, const char* who) {
+// Histone-mark coalitions (cf_marks.h).  The two families -- cf_mark_* (an absent mark is the gene's own signal scaled) and
+// cf_mark_donor_* (an absent mark is the donor's) -- share everything but the options struct and the expand kernel: MarkGame is what
+// either struct says, checked.
+struct MarkGame {
+    int P;
+    const unsigned* marks;                // host [P]
+    const unsigned* regions;              // host [P]
+    float scale;                          // the scale rule (donor == nullptr)
+    const cf_mark_donor_opts* donor;      // the donor rule
+};
+
+// mark_check: what the entry points check alike, in front of anything launched -- the handle, the batch, riders, the options: the
+// player count, the player words.  `o`: whether the caller's opts pointer is non-null.
+static int mark_check(cf_handle* h, const cf_batch* bt, bool o, const MarkGame& g, const char* who) {
     if (attrib_open(h, bt, true, who)) return -1;
     if (!o) return fail("%s: null opts", who);
     const cf_config& c = h->cfg;
     const int S = c.i_max, F = c.n_feats;
-    if (o->n_players < 1 || o->n_players > kCoalMaxS) return fail("%s: n_players = %d outside 1..%d", who, o->n_players, kCoalMaxS);
-    if (!o->player_marks || !o->player_regions) return fail("%s: null player_marks / player_regions", who);
-    for (int p = 0; p < o->n_players; ++p) {
-        const unsigned pm = o->player_marks[p], pr = o->player_regions[p];
+    if (g.P < 1 || g.P > kCoalMaxS) return fail("%s: n_players = %d outside 1..%d", who, g.P, kCoalMaxS);
+    if (!g.marks || !g.regions) return fail("%s: null player_marks / player_regions", who);
+    for (int p = 0; p < g.P; ++p) {
+        const unsigned pm = g.marks[p], pr = g.regions[p];
         if (!pm) return fail("%s: player_marks[%d] = 0: a player names at least one mark", who, p);
         if (!pr) return fail("%s: player_regions[%d] = 0: a player names at least one region (bit 0 the promoter, bit 1 + j pCRE slot j)", who, p);
         if (F < 32 && pm >> F) return fail("%s: player_marks[%d] = 0x%x names a mark >= n_feats = %d", who, p, pm, F);
         if (pr >> S >> 1) return fail("%s: player_regions[%d] = 0x%x names a region above i_max = %d", who, p, pr, S);
     }
+    return 0;
+}
+// ... then the scale of the scale rule,
+static int mark_game(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, MarkGame* g, const char* who) {
+    *g = o ? MarkGame{o->n_players, o->player_marks, o->player_regions, o->scale, nullptr} : MarkGame{};
+    if (mark_check(h, bt, o != nullptr, *g, who)) return -1;
     if (!(o->scale >= 0.f) || !std::isfinite(o->scale)) return fail("%s: scale = %g: a finite factor >= 0", who, (double)o->scale);
+    return 0;
+}
+// ... or the donor's feature pointers of the donor rule.
+static int mark_donor_game(cf_handle* h, const cf_batch* bt, const cf_mark_donor_opts* o, MarkGame* g, const char* who) {
+    *g = o ? MarkGame{o->n_players, o->player_marks, o->player_regions, 0.f, o} : MarkGame{};
+    if (mark_check(h, bt, o != nullptr, *g, who)) return -1;
+    for (int r = 0; r < h->cfg.n_res; ++r)
+        if (!o->donor_promoter_feats[r] || !o->donor_pcre_feats[r])
+            return fail("%s: null donor_promoter_feats / donor_pcre_feats[%d]: the donor's features at every one of the model's %d resolutions", who, r, h->cfg.n_res);
     return 0;
 }
 
 // The coalition words (validated) and the 2 P player words into the workspace's word table: [words | marks_p | regions_p].
-static int mark_upload(cf_handle* h, const cf_mark_opts* o, const uint32_t* keep, int n_coal, hipStream_t st, const char* who) {
-    const int P = o->n_players;
+static int mark_upload(cf_handle* h, const MarkGame& g, const uint32_t* keep, int n_coal, hipStream_t st, const char* who) {
+    const int P = g.P;
     if (n_coal < 1) return fail("%s: n_coal = %d: at least 1 coalition", who, n_coal);
     if (!keep) return fail("%s: null keep", who);
     for (int k = 0; k < n_coal; ++k)
@@ -792,20 +818,21 @@ static int mark_upload(cf_handle* h, const cf_mark_opts* o, const uint32_t* keep
     if (attrib_ws(h, who) || h->aw.words.need((size_t)n_coal + 2 * P, 256, who)) return -1;
     unsigned* tab = h->aw.words;
     HIP_TRY(hipMemcpyAsync(tab, keep, (size_t)n_coal * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(tab + n_coal, o->player_marks, P * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(tab + n_coal + P, o->player_regions, P * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(tab + n_coal, g.marks, P * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(tab + n_coal + P, g.regions, P * sizeof(unsigned), hipMemcpyHostToDevice, st));
     return 0;
 }
 
 // The B * n_coal rows of a mark-coalition call (gene-major; row (b, k) is word k of the table mark_upload wrote), every row through
-// the whole forward.  Per chunk of at most max_batch rows: k_mark_expand into the chunk workspace, then the launches of
-// cf_forward(save = 0) on the chunk, writing its slice of `logits`.  k_attc2 takes as many regions per workgroup as for the caller's B
-// genes (ag_genes), as scan_region_rows: the result does not depend on max_batch.
-static int mark_rows(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, int n_coal, float* logits, hipStream_t st) {
+// the whole forward.  Per chunk of at most max_batch rows: k_mark_expand (the donor rule: k_mark_donor_expand) into the chunk workspace,
+// then the launches of cf_forward(save = 0) on the chunk, writing its slice of `logits`.  k_attc2 takes as many regions per workgroup
+// as for the caller's B genes (ag_genes), as scan_region_rows: the result does not depend on max_batch.
+static int mark_rows(cf_handle* h, const cf_batch* bt, const MarkGame& g, int n_coal, float* logits, hipStream_t st) {
     const cf_config& c = h->cfg;
-    const int nres = c.n_res, cap = c.max_batch, B = bt->B, P = o->n_players;
-    MarkExpandArgs ea;
-    memset(&ea, 0, sizeof ea);
+    const int nres = c.n_res, cap = c.max_batch, B = bt->B, P = g.P;
+    MarkDonorArgs da;
+    memset(&da, 0, sizeof da);
+    MarkExpandArgs& ea = da.m;
     cf_batch cb;      // the chunk's batch: the rows' copies
     chunk_rows(h, bt, &ea.rows, &cb);
     for (int r = 0; r < nres; ++r) {
@@ -813,20 +840,29 @@ static int mark_rows(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, in
         ea.cf_in[r] = bt->pcre_feats[r];
         ea.pf_out[r] = h->aw.row[r];
         ea.cf_out[r] = h->aw.row[kMaxRes + r];
+        if (g.donor) {
+            da.pf_don[r] = g.donor->donor_promoter_feats[r];
+            da.cf_don[r] = g.donor->donor_pcre_feats[r];
+        }
     }
     ea.freq_in = bt->interaction_freq;
     ea.freq_out = h->aw.row[2 * kMaxRes];
     ea.words = h->aw.words;
     ea.players = h->aw.words + n_coal;
-    ea.scale = o->scale;
+    ea.scale = g.scale;
     ea.n_coal = n_coal, ea.P = P, ea.F = c.n_feats;
     const long long launches0 = g_launches, rows = (long long)B * n_coal;
     auto run = [&]() -> int {
         for (long long g0 = 0; g0 < rows; g0 += cap) {
             const int n = (int)std::min<long long>(cap, rows - g0);
             ea.g0 = g0;
-            hipLaunchKernelGGL(k_mark_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, ea);
-            LAUNCH_CHECK("k_mark_expand");
+            if (g.donor) {
+                hipLaunchKernelGGL(k_mark_donor_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, da);
+                LAUNCH_CHECK("k_mark_donor_expand");
+            } else {
+                hipLaunchKernelGGL(k_mark_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, ea);
+                LAUNCH_CHECK("k_mark_expand");
+            }
             cb.B = n;
             if (forward_trunk(h, &cb, 0, st, B) || forward_reg_head(h, &cb, logits + (size_t)g0 * c.n_out, 0, st, nullptr)) return -1;
         }
@@ -838,29 +874,25 @@ static int mark_rows(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, in
     return rv ? -1 : 0;
 }
 
-extern "C" int cf_mark_coalitions(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, const uint32_t* keep, int n_coal, float* logits,
-                                  void* stream) {
-    const char* who = "cf_mark_coalitions";
-    if (mark_check(h, bt, o, who)) return -1;
+// The three calls on a checked game: the given coalitions;
+static int mark_coalitions_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g, const uint32_t* keep, int n_coal, float* logits, void* stream,
+                                const char* who) {
     if (!logits) return fail("%s: null logits", who);
     hipStream_t st = (hipStream_t)stream;
-    if (mark_upload(h, o, keep, n_coal, st, who)) return -1;
-    return mark_rows(h, bt, o, n_coal, logits, st);
+    if (mark_upload(h, g, keep, n_coal, st, who)) return -1;
+    return mark_rows(h, bt, g, n_coal, logits, st);
 }
-
-// All 2^P coalitions through mark_upload + mark_rows (word m at column m), then k_shapley with S = P.
-extern "C" int cf_mark_shapley(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, float* phi, float* logits_all, void* stream) {
-    const char* who = "cf_mark_shapley";
-    if (mark_check(h, bt, o, who)) return -1;
+// all 2^P coalitions through mark_upload + mark_rows (word m at column m), then k_shapley with S = P;
+static int mark_shapley_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g, float* phi, float* logits_all, void* stream, const char* who) {
     if (!phi) return fail("%s: null phi", who);
     const cf_config& c = h->cfg;
-    const int P = o->n_players, n = 1 << P;
+    const int P = g.P, n = 1 << P;
     float* rows = coalition_out_rows(h, logits_all, n, who);
     if (!rows) return -1;
     std::vector<uint32_t> keep(n);
     for (int m = 0; m < n; ++m) keep[m] = (uint32_t)m;
     hipStream_t st = (hipStream_t)stream;
-    if (mark_upload(h, o, keep.data(), n, st, who) || mark_rows(h, bt, o, n, rows, st)) return -1;
+    if (mark_upload(h, g, keep.data(), n, st, who) || mark_rows(h, bt, g, n, rows, st)) return -1;
     ShapleyArgs sa;
     memset(&sa, 0, sizeof sa);
     sa.v = rows, sa.phi = phi, sa.S = P, sa.n_out = c.n_out;
@@ -872,15 +904,12 @@ extern "C" int cf_mark_shapley(cf_handle* h, const cf_batch* bt, const cf_mark_o
     forward_one_more(h);
     return 0;
 }
-
-// The 1 + P + P (P - 1) / 2 pair-deletion coalitions (N = 2^P - 1; N without i; N without i and j, i < j) through mark_upload +
+// the 1 + P + P (P - 1) / 2 pair-deletion coalitions (N = 2^P - 1; N without i; N without i and j, i < j) through mark_upload +
 // mark_rows, then k_epistasis with S = P.
-extern "C" int cf_mark_epistasis(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, float* eps, float* logits_pairs, void* stream) {
-    const char* who = "cf_mark_epistasis";
-    if (mark_check(h, bt, o, who)) return -1;
+static int mark_epistasis_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g, float* eps, float* logits_pairs, void* stream, const char* who) {
     if (!eps) return fail("%s: null eps", who);
     const cf_config& c = h->cfg;
-    const int P = o->n_players;
+    const int P = g.P;
     const uint32_t N = (1u << P) - 1u;
     std::vector<uint32_t> keep;
     keep.push_back(N);
@@ -891,7 +920,7 @@ extern "C" int cf_mark_epistasis(cf_handle* h, const cf_batch* bt, const cf_mark
     float* rows = coalition_out_rows(h, logits_pairs, R, who);
     if (!rows) return -1;
     hipStream_t st = (hipStream_t)stream;
-    if (mark_upload(h, o, keep.data(), R, st, who) || mark_rows(h, bt, o, R, rows, st)) return -1;
+    if (mark_upload(h, g, keep.data(), R, st, who) || mark_rows(h, bt, g, R, rows, st)) return -1;
     EpistasisArgs ea;
     ea.v = rows, ea.eps = eps, ea.B = bt->B, ea.S = P, ea.n_out = c.n_out;
     const long long n = (long long)bt->B * P * P * c.n_out;
@@ -899,4 +928,39 @@ extern "C" int cf_mark_epistasis(cf_handle* h, const cf_batch* bt, const cf_mark
     LAUNCH_CHECK("k_epistasis");
     forward_one_more(h);
     return 0;
+}
+
+extern "C" int cf_mark_coalitions(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, const uint32_t* keep, int n_coal, float* logits,
+                                  void* stream) {
+    const char* who = "cf_mark_coalitions";
+    MarkGame g;
+    return mark_game(h, bt, o, &g, who) ? -1 : mark_coalitions_impl(h, bt, g, keep, n_coal, logits, stream, who);
+}
+extern "C" int cf_mark_shapley(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, float* phi, float* logits_all, void* stream) {
+    const char* who = "cf_mark_shapley";
+    MarkGame g;
+    return mark_game(h, bt, o, &g, who) ? -1 : mark_shapley_impl(h, bt, g, phi, logits_all, stream, who);
+}
+extern "C" int cf_mark_epistasis(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, float* eps, float* logits_pairs, void* stream) {
+    const char* who = "cf_mark_epistasis";
+    MarkGame g;
+    return mark_game(h, bt, o, &g, who) ? -1 : mark_epistasis_impl(h, bt, g, eps, logits_pairs, stream, who);
+}
+
+// The donor family: an absent mark takes the donor's bits (k_mark_donor_expand); everything else as above.
+extern "C" int cf_mark_donor_coalitions(cf_handle* h, const cf_batch* bt, const cf_mark_donor_opts* o, const uint32_t* keep, int n_coal,
+                                        float* logits, void* stream) {
+    const char* who = "cf_mark_donor_coalitions";
+    MarkGame g;
+    return mark_donor_game(h, bt, o, &g, who) ? -1 : mark_coalitions_impl(h, bt, g, keep, n_coal, logits, stream, who);
+}
+extern "C" int cf_mark_donor_shapley(cf_handle* h, const cf_batch* bt, const cf_mark_donor_opts* o, float* phi, float* logits_all, void* stream) {
+    const char* who = "cf_mark_donor_shapley";
+    MarkGame g;
+    return mark_donor_game(h, bt, o, &g, who) ? -1 : mark_shapley_impl(h, bt, g, phi, logits_all, stream, who);
+}
+extern "C" int cf_mark_donor_epistasis(cf_handle* h, const cf_batch* bt, const cf_mark_donor_opts* o, float* eps, float* logits_pairs, void* stream) {
+    const char* who = "cf_mark_donor_epistasis";
+    MarkGame g;
+    return mark_donor_game(h, bt, o, &g, who) ? -1 : mark_epistasis_impl(h, bt, g, eps, logits_pairs, stream, who);
 }

@@ -1,4 +1,5 @@
-// cf_marks.h -- histone-mark coalitions (cf_mark_coalitions, cf_mark_shapley, cf_mark_epistasis; included by cf_api.hip behind cf_scan.h).
+// cf_marks.h -- histone-mark coalitions (cf_mark_coalitions, cf_mark_shapley, cf_mark_epistasis and their cf_mark_donor_* siblings;
+// included by cf_api.hip behind cf_scan.h).
 //
 // The players of the game are MARKS, each optionally restricted to a set of regions.  Player p is a pair of words: marks_p (bit f:
 // mark f) and regions_p (bit 0: the promoter, bit 1 + j: pCRE slot j), both non-zero.  A coalition is a 32-bit word m, bit p set =
@@ -23,6 +24,15 @@
 //                   workgroups share a (row, resolution): one workgroup per pair leaves the finest resolution's 25,200 floats to 256
 //                   threads, ~25 dependent load / store rounds, and the launch latency-bound.
 // The reducers are k_shapley and k_epistasis of cf_coalition.h with S = P.
+//
+// The donor family (cf_mark_donor_coalitions, cf_mark_donor_shapley, cf_mark_donor_epistasis): the same players, words and gone(rho), but
+// an element whose mark is in gone(rho) takes the BITS of a second feature set's element at the same (gene, region, row, resolution,
+// mark) -- the same gene's signal in another cell type -- instead of the scaled value.  A select, no arithmetic: NaN payloads, -0 and
+// inf pass through.  Binning works per mark, so this is exactly the feature the binning produces when those marks' rows of the raw
+// region are replaced by the donor's.
+//   k_mark_donor_expand   the grid, the gone(rho) words and the element order of k_mark_expand; the donor's float4 (or float) is loaded
+//                         only where the element's region has gone != 0, together with the gene's own (both loads in flight before
+//                         either is used), and selected per lane by the mark bit.
 #pragma once
 
 namespace cf {
@@ -93,6 +103,76 @@ __global__ __launch_bounds__(kIgxThreads) void k_mark_expand(MarkExpandArgs a) {
     __syncthreads();
     mark_copy(a.pf_in[r] + (size_t)b * LF, a.pf_out[r] + (size_t)i * LF, LF, LF, F, gone, a.scale);
     mark_copy(a.cf_in[r] + (size_t)b * S * LF, a.cf_out[r] + (size_t)i * S * LF, S * LF, LF, F, gone + 1, a.scale);
+    if (blockIdx.z) return;
+    rows_pad_masks(a.rows, r, b, i);
+    rows_interaction_mask(a.rows, r, b, i);
+    if (r == 0) rows_copy_tt(a.freq_in, a.freq_out, b, i, a.rows.TT);
+}
+
+struct MarkDonorArgs {
+    MarkExpandArgs m;                  // as for k_mark_expand (scale is not read)
+    const float* pf_don[kMaxRes];      // the donor's promoter_feats [B, L, F]
+    const float* cf_don[kMaxRes];      // pcre_feats [B, S, L, F]
+};
+
+// The donor's bits where the mark is gone, else the gene's (an integer select: no canonicalisation of NaNs, -0 stays -0)
+__device__ __forceinline__ float donor_elem(float x, float d, unsigned gone, int f) {
+    return __uint_as_float((gone >> f) & 1u ? __float_as_uint(d) : __float_as_uint(x));
+}
+
+// mark_copy with the donor's element in place of the scaled one: don[0, n) is laid out as src[0, n) and read only in regions with gone != 0
+__device__ __forceinline__ void mark_donor_copy(const float* __restrict__ src, const float* __restrict__ don, float* __restrict__ dst, int n, int LF, int F,
+                                                const unsigned* gone) {
+    const int first = blockIdx.z * kIgxThreads + threadIdx.x, step = kMarkSlices * kIgxThreads;
+    const bool vec = (n & 3) == 0 && LF >= 4 &&
+                     ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(don) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+    if (vec) {
+        const float4* s4 = reinterpret_cast<const float4*>(src);
+        const float4* n4 = reinterpret_cast<const float4*>(don);
+        float4* d4 = reinterpret_cast<float4*>(dst);
+        for (int k = first; k < n / 4; k += step) {
+            const int e = 4 * k, rho = e / LF, rem = e - rho * LF;
+            const int over = LF - rem;                               // elements over .. 3 of the float4 lie in region rho + 1 (LF % 4 != 0)
+            const unsigned ga = gone[rho], gb = over < 4 ? gone[rho + 1] : ga;
+            float4 x = s4[k];
+            if (ga | gb) {
+                const float4 d = n4[k];
+                const int f0 = rem % F, f1 = f0 + 1 == F ? 0 : f0 + 1, f2 = f1 + 1 == F ? 0 : f1 + 1, f3 = f2 + 1 == F ? 0 : f2 + 1;
+                x.x = donor_elem(x.x, d.x, ga, f0);
+                x.y = donor_elem(x.y, d.y, over > 1 ? ga : gb, f1);
+                x.z = donor_elem(x.z, d.z, over > 2 ? ga : gb, f2);
+                x.w = donor_elem(x.w, d.w, over > 3 ? ga : gb, f3);
+            }
+            d4[k] = x;
+        }
+    } else {
+        for (int e = first; e < n; e += step) {
+            const int rho = e / LF;
+            const unsigned g = gone[rho];
+            float x = src[e];
+            if (g) x = donor_elem(x, don[e], g, (e - rho * LF) % F);
+            dst[e] = x;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kIgxThreads) void k_mark_donor_expand(MarkDonorArgs da) {
+    __shared__ unsigned gone[kCoalMaxS + 1];      // gone(rho), rho = 0 .. i_max: 68 bytes
+    const MarkExpandArgs& a = da.m;
+    const int i = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
+    const long long gv = a.g0 + i;
+    const int b = (int)(gv / a.n_coal);
+    const int L = a.rows.L[r], S = a.rows.S, F = a.F, LF = L * F, P = a.P;
+    if (tid <= S) {      // (as k_mark_expand)
+        const unsigned m = a.words[gv - (long long)b * a.n_coal];
+        unsigned g = 0;
+        for (int p = 0; p < P; ++p)
+            if (!((m >> p) & 1u) && ((a.players[P + p] >> tid) & 1u)) g |= a.players[p];
+        gone[tid] = g;
+    }
+    __syncthreads();
+    mark_donor_copy(a.pf_in[r] + (size_t)b * LF, da.pf_don[r] + (size_t)b * LF, a.pf_out[r] + (size_t)i * LF, LF, LF, F, gone);
+    mark_donor_copy(a.cf_in[r] + (size_t)b * S * LF, da.cf_don[r] + (size_t)b * S * LF, a.cf_out[r] + (size_t)i * S * LF, S * LF, LF, F, gone + 1);
     if (blockIdx.z) return;
     rows_pad_masks(a.rows, r, b, i);
     rows_interaction_mask(a.rows, r, b, i);

@@ -868,6 +868,135 @@ class ChromoformerBase(nn.Module):
         from .attribution import mark_shapley
         return mark_shapley(self, dataset, genes=genes, players=players, scale=scale, epistasis=epistasis, bsz=bsz, store=store)
 
+    def _mark_donor_opts(self, who, donor, players, B):
+        """players (a mark_players spec) and the donor of a batch of B genes -> (cf_mark_donor_opts, what it points to, names).  donor:
+        a (promoter_feats, pcre_feats) pair of dicts by bin size (or lists in binsizes order) of contiguous float32 tensors on the
+        model's device, [B, 1, L, F] and [B, i_max, L, F]; or a packed batch (an engine.Slot, a pack_batch result or a batch struct),
+        whose features are used and the rest ignored.  Anything else raises ValueError naming `who`."""
+        from .attribution import mark_players
+        marks, regions, names = mark_players(players, self.n_feats, self.i_max)
+        opts = _lib.cf_mark_donor_opts()
+        opts.n_players = len(marks)
+        opts.player_marks, opts.player_regions = marks.ctypes.data, regions.ctypes.data
+        if donor is None:
+            raise ValueError("%s: donor is required: the same genes' features in the other cell type, a (promoter_feats, pcre_feats) "
+                             "pair or a packed batch" % who)
+        S, F = self.i_max, self.n_feats
+        packed = donor if isinstance(donor, _lib.cf_batch) else getattr(donor, "struct", None)
+        if packed is None and isinstance(donor, (tuple, list)) and len(donor) == 2 and isinstance(donor[0], _lib.cf_batch):
+            packed = donor[0]
+        if packed is not None:
+            if packed.B != B:
+                raise ValueError("%s: the donor holds %d genes, the batch %d" % (who, packed.B, B))
+            for r in range(len(self.binsizes)):
+                opts.donor_promoter_feats[r], opts.donor_pcre_feats[r] = packed.promoter_feats[r], packed.pcre_feats[r]
+            return opts, (marks, regions, donor), names
+        try:
+            pfs, cfs = donor
+            pfs = [pfs[b] for b in self.binsizes] if isinstance(pfs, dict) else list(pfs)
+            cfs = [cfs[b] for b in self.binsizes] if isinstance(cfs, dict) else list(cfs)
+        except (TypeError, ValueError, KeyError):
+            raise ValueError("%s: donor must be a (promoter_feats, pcre_feats) pair of dicts by bin size %s (or lists in that order) or a "
+                             "packed batch" % (who, list(self.binsizes))) from None
+        if len(pfs) != len(self.binsizes) or len(cfs) != len(self.binsizes):
+            raise ValueError("%s: donor has %d / %d feature tensors, the model %d resolutions" % (who, len(pfs), len(cfs), len(self.binsizes)))
+        for r, b in enumerate(self.binsizes):
+            L = self.n_bins[r]
+            for name, t, lead in (("promoter_feats", pfs[r], 1), ("pcre_feats", cfs[r], S)):
+                what = "%s: donor %s[%d]" % (who, name, b)
+                if not torch.is_tensor(t):
+                    raise ValueError("%s is not a tensor" % what)
+                if t.dtype != torch.float32:
+                    raise ValueError("%s is %s; the donor's bits are selected as they are: float32 is required" % (what, t.dtype))
+                if t.device != self._device:
+                    raise ValueError("%s is on %s, the model on %s" % (what, t.device, self._device))
+                if t.numel() != B * lead * L * F or t.dim() < 3 or t.shape[0] != B or tuple(t.shape[-2:]) != (L, F):
+                    raise ValueError("%s has shape %s; expected %s" % (what, tuple(t.shape), (B, lead, L, F)))
+                if not t.is_contiguous():
+                    raise ValueError("%s is not contiguous" % what)
+            opts.donor_promoter_feats[r], opts.donor_pcre_feats[r] = pfs[r].data_ptr(), cfs[r].data_ptr()
+        return opts, (marks, regions, pfs, cfs), names
+
+    @torch.no_grad()
+    def mark_donor_coalitions(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                              interaction_freq=None, donor=None, keep=None, players="marks"):
+        """The prediction under histone-mark coalitions against a donor cell type (cf_mark_donor_coalitions) -> logits
+        [B, n_coal, n_out] on the model's device, no autograd graph.  Players and `keep` as in mark_coalitions.  `donor`: the same B
+        genes' features in the other cell type -- a (promoter_feats, pcre_feats) pair of dicts by bin size (or lists in binsizes
+        order) of contiguous float32 tensors on the model's device, or a packed batch (an engine.Slot or a pack_batch result), whose
+        features are used and the rest ignored.  Column c is the inference forward with every ABSENT player's marks taken from the
+        donor over the player's regions, bit for bit, at every resolution and in every row; masks and interaction_freq stay the
+        gene's own.  Where the two cell types share a region's coordinates this is exactly what binning the raw region with those
+        marks' rows replaced gives.  The full word 2^P - 1 is the prediction (model(...) under no_grad, bit-equal).  The first
+        argument may also be a packed batch, with nothing after it.  The pass overwrites the activations a grad-enabled model(...)
+        keeps for its backward: such a pending backward() raises."""
+        from .attribution import mark_coalition_words
+        who = "mark_donor_coalitions"
+        if keep is None:
+            raise ValueError("mark_donor_coalitions: keep is required: the coalition words (bit p set: player p present)")
+        bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        opts, _alive, _names = self._mark_donor_opts(who, donor, players, bs.B)
+        words = mark_coalition_words(keep, opts.n_players, who)
+        logits = torch.empty(bs.B, len(words), self.n_out, device=self._device)      # (written in full by the library)
+        st = book()
+        _lib.check(_lib.lib().cf_mark_donor_coalitions(self._handle, C.byref(bs), C.byref(opts), words.ctypes.data, len(words), logits.data_ptr(), st),
+                   "cf_mark_donor_coalitions")
+        return logits
+
+    @torch.no_grad()
+    def mark_donor_shapley(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                           interaction_freq=None, donor=None, players="marks", return_coalitions=False):
+        """Exact Shapley values of the histone marks against a donor cell type (cf_mark_donor_shapley) -> (phi, info), tensors on the
+        model's device, no autograd graph: which mark changes account for the difference between the two predictions?
+
+          phi                 [B, P, n_out]: player p's average marginal contribution to each logit over all orders of switching the
+                              players from the donor's signal to the gene's; exactly 0 for a player whose elements are the same in both
+          info["logits"]      [B, n_out]: the prediction (every player present; model(...) under no_grad, bit-equal)
+          info["donor"]       [B, n_out]: every player absent: the donor's marks under the gene's masks and frequencies
+          info["delta"]       [B, n_out]: phi.sum(1) - (logits - donor), the efficiency gap (rounding only)
+          info["players"]     the players' names
+          info["coalitions"]  [B, 2^P, n_out], with return_coalitions: the logits of every coalition, word m at column m
+
+        donor and players as in mark_donor_coalitions; all 2^P coalitions run from one call.  The packed forms of the first argument
+        and the effect on a pending backward() are those of mark_coalitions."""
+        who = "mark_donor_shapley"
+        bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        opts, _alive, names = self._mark_donor_opts(who, donor, players, bs.B)
+        P = opts.n_players
+        n = 1 << P
+        rows = torch.empty(bs.B, n, self.n_out, device=self._device)      # (both written in full by the library)
+        phi = torch.empty(bs.B, P, self.n_out, device=self._device)
+        st = book()
+        _lib.check(_lib.lib().cf_mark_donor_shapley(self._handle, C.byref(bs), C.byref(opts), phi.data_ptr(), rows.data_ptr(), st), "cf_mark_donor_shapley")
+        info = {"logits": rows[:, n - 1].clone(), "donor": rows[:, 0].clone(), "players": names}
+        info["delta"] = phi.sum(1) - (info["logits"] - info["donor"])
+        if return_coalitions:
+            info["coalitions"] = rows
+        return phi, info
+
+    @torch.no_grad()
+    def mark_donor_epistasis(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                             interaction_freq=None, donor=None, players="marks"):
+        """Pair epistasis of the histone-mark players against a donor cell type (cf_mark_donor_epistasis) -> (eps, info) as
+        mark_epistasis returns them, with v(...) the logits with the named players' marks taken from the donor.  donor and players as
+        in mark_donor_coalitions."""
+        who = "mark_donor_epistasis"
+        bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        opts, _alive, names = self._mark_donor_opts(who, donor, players, bs.B)
+        P = opts.n_players
+        rows = torch.empty(bs.B, 1 + P + P * (P - 1) // 2, self.n_out, device=self._device)      # (both written in full by the library)
+        eps = torch.empty(bs.B, P, P, self.n_out, device=self._device)
+        st = book()
+        _lib.check(_lib.lib().cf_mark_donor_epistasis(self._handle, C.byref(bs), C.byref(opts), eps.data_ptr(), rows.data_ptr(), st), "cf_mark_donor_epistasis")
+        return eps, {"logits": rows[:, 0].clone(), "single": rows[:, 1:1 + P].clone(), "players": names}
+
+    def mark_donor_shapley_dataset(self, dataset, donor_dataset, genes=None, players="marks", epistasis=False, bsz=None, store=None, donor_store=None):
+        """mark_donor_shapley (and optionally mark_donor_epistasis) over the genes of two ChromoformerDatasets, the gene's cell type
+        and the donor's (chromoformer_amd.attribution.mark_donor_shapley, a generator of per-gene dicts)."""
+        from .attribution import mark_donor_shapley
+        return mark_donor_shapley(self, dataset, donor_dataset, genes=genes, players=players, epistasis=epistasis, bsz=bsz, store=store,
+                                  donor_store=donor_store)
+
     def raw_signal_gradients(self, dataset, genes=None, target=None, times_input=False, bsz=None):
         """Raw-signal saliency of the genes of a ChromoformerDataset: the gradient (or gradient x input) of logit column `target` with
         respect to the raw fp16 signals, per gene one track per histone mark for the promoter window and every pCRE, in genomic

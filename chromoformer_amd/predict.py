@@ -206,6 +206,45 @@ def write_mark_values(model, store, bsz, gene_ids, shapley_out=None, epistasis_o
         eps.flush()
 
 
+def write_mark_donor_values(model, store, donor_store, bsz, gene_ids, shapley_out=None, epistasis_out=None, regression=False, players="marks"):
+    """Exact Shapley values and / or pair epistasis of the histone marks against a donor cell type, for every gene of two
+    device-resident stores that hold the same genes in the same order, in LOGIT space of the prediction's column.  shapley_out: an .npz
+    with gene_ids [n], players [P] (names), phi [n, P], logits [n], donor [n] (every player's marks from the donor, under the gene's
+    masks and frequencies; phi sums to logits - donor) and donor_prediction [n] (the plain forward of the donor's own batch);
+    epistasis_out: a float32 .npy [n, P, P].  Per batch: one gather per store, one model.mark_donor_shapley and / or one
+    model.mark_donor_epistasis, one plain forward of the donor's batch."""
+    from .attribution import mark_players
+    n = len(store)
+    if len(donor_store) != n:
+        raise ValueError("write_mark_donor_values: the donor store holds %d genes, the store %d" % (len(donor_store), n))
+    names = mark_players(players, model.n_feats, model.i_max)[2]
+    P, t = len(names), 0 if regression else 1
+    phi, logits, donor, pred = torch.empty(n, P), torch.empty(n), torch.empty(n), torch.empty(n)
+    eps = np.lib.format.open_memmap(epistasis_out, mode="w+", dtype=np.float32, shape=(n, P, P)) if epistasis_out else None
+    keys = ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq")
+    for lo in range(0, n, bsz):
+        B = min(bsz, n - lo)
+        idx = list(range(lo, lo + B))
+        d, dd = store.batch(idx), donor_store.batch(idx)
+        args = tuple(d[k] for k in keys)
+        feats = ({b: x.contiguous() for b, x in dd["promoter_feats"].items()}, {b: x.contiguous() for b, x in dd["pcre_feats"].items()})
+        if shapley_out:
+            p, info = model.mark_donor_shapley(*args, donor=feats, players=players)
+            phi[lo:lo + B] = p[..., t].cpu()
+            logits[lo:lo + B] = info["logits"][:, t].cpu()
+            donor[lo:lo + B] = info["donor"][:, t].cpu()
+            with torch.no_grad():
+                pred[lo:lo + B] = model(*(dd[k] for k in keys))[:, t].cpu()
+        if eps is not None:
+            eps[lo:lo + B] = model.mark_donor_epistasis(*args, donor=feats, players=players)[0][..., t].cpu().numpy()
+    if shapley_out:
+        with open(shapley_out, "wb") as f:      # (a file object: np.savez would append .npz to a name without it)
+            np.savez(f, gene_ids=np.array(list(gene_ids)), players=np.array(names), phi=phi.numpy(), logits=logits.numpy(), donor=donor.numpy(),
+                     donor_prediction=pred.numpy())
+    if eps is not None:
+        eps.flush()
+
+
 def write_integrated_gradients(model, store, bsz, ig_dir, n_steps=50, method="gausslegendre", target=None):
     """Integrated gradients of every gene of a device-resident store, in store order, into `ig_dir`: promoter_feats_{b}.npy
     [n, L, F], pcre_feats_{b}.npy [n, i_max, L, F], interaction_freq.npy [n, T, T] and delta.npy [n] (float32 .npy memory maps;
@@ -370,7 +409,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
             pcre_ablation_out=None, ig_dir=None, ig_steps=50, ig_method="gausslegendre", ig_target=None, raw_saliency_dir=None,
             raw_saliency_target=None, raw_saliency_times_input=False, raw_ig_dir=None, scan_out=None, scan_scale=0.0, scan_width=1,
             scan_regions="promoter", pcre_shapley_out=None, pcre_epistasis_out=None, mark_shapley_out=None, mark_epistasis_out=None,
-            mark_players="marks", mark_scale=0.0):
+            mark_players="marks", mark_scale=0.0, donor_npy_dir=None, donor_meta=None, donor_store_path=None, mark_donor_shapley_out=None,
+            mark_donor_epistasis_out=None):
     """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file.  attention_dir / embeddings_out: also
     write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps); pcre_ablation_out:
     the predictions with each pCRE deleted (write_pcre_ablation); ig_dir: integrated gradients of every gene
@@ -381,7 +421,10 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     (write_perturbation_scan; scan_scale, scan_width and scan_regions apply; served by a packed store as well); pcre_shapley_out /
     pcre_epistasis_out: exact Shapley values / pair-deletion epistasis of the pCREs, in logit space (write_pcre_coalition_values);
     mark_shapley_out / mark_epistasis_out: exact Shapley values / pair epistasis of the histone marks, in logit space
-    (write_mark_values; mark_players and mark_scale apply)."""
+    (write_mark_values; mark_players and mark_scale apply); mark_donor_shapley_out / mark_donor_epistasis_out: the same against a donor
+    cell type (write_mark_donor_values; mark_players applies), whose signals are read from donor_npy_dir with the metadata donor_meta
+    (default: meta_path) or the packed store donor_store_path -- both cell types must hold the genes' regions at the same coordinates
+    (attribution.same_regions)."""
     seed_everything(seed)
     meta = pd.read_csv(meta_path)
     genes = meta.gene_id.tolist()
@@ -390,6 +433,13 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         raw_ds = ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=regression)
         require_raw_signals(raw_ds)      # (before anything is computed)
     from . import pack
+    donor_out = mark_donor_shapley_out or mark_donor_epistasis_out
+    if donor_out:      # (before anything is computed)
+        from .attribution import same_regions
+        if not donor_npy_dir:
+            raise ValueError("predict: mark_donor_shapley_out / mark_donor_epistasis_out need donor_npy_dir")
+        donor_ds = ChromoformerDataset(donor_meta or meta_path, donor_npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False)
+        same_regions(ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False), donor_ds)
     packed = pack.find(npy_dir, store_path, list(binsizes), i_max, w_prom, w_max, 7, genes, meta=meta)
     dev = torch.device("cuda", torch.cuda.current_device())
     if packed is not None:
@@ -415,6 +465,12 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         write_pcre_coalition_values(model, store, bsz, pcre_shapley_out, pcre_epistasis_out, regression)
     if mark_shapley_out or mark_epistasis_out:
         write_mark_values(model, store, bsz, genes, mark_shapley_out, mark_epistasis_out, regression, mark_players, mark_scale)
+    if donor_out:
+        donor_packed = pack.find(donor_npy_dir, donor_store_path, list(binsizes), i_max, w_prom, w_max, 7, genes, meta=donor_ds.meta)
+        donor_store = (donor_packed.store(genes, device=dev, regression=False) if donor_packed is not None
+                       else GeneStore(donor_ds, progress=progress, device=dev, resident=True))
+        write_mark_donor_values(model, store, donor_store, bsz, genes, mark_donor_shapley_out, mark_donor_epistasis_out, regression, mark_players)
+        del donor_store
     if ig_dir:
         write_integrated_gradients(model, store, bsz, ig_dir, ig_steps, ig_method, ig_target)
     if scan_out:
@@ -482,6 +538,18 @@ def build_parser():
                     "each mark in every region (marks, the default), each mark in the promoter and in the pCREs (compartments), or all marks "
                     "per region (regions)")
     ap.add_argument("--mark-scale", type=float, default=None, help="what an absent mark's raw signal is scaled by: 0 erases it (default)")
+    ap.add_argument("--donor-npy-dir", default=None, help="directory of the .npy histone signals of a DONOR cell type over the same regions: "
+                    "what an absent mark becomes in --mark-donor-shapley-out / --mark-donor-epistasis-out")
+    ap.add_argument("--donor-meta", default=None, help="metadata file of the donor cell type (default: --meta); TSS, strand and pCREs of every "
+                    "gene must equal those of --meta")
+    ap.add_argument("--donor-store", default=None, help="packed store of the donor cell type (default: <donor-npy-dir>/chromoformer.cfstore if present)")
+    ap.add_argument("--mark-donor-shapley-out", default=None, help="also write the exact Shapley values of the histone marks against the donor "
+                    "cell type to this .npz file, in metadata order and in LOGIT space of the prediction's column: gene_ids, players (names), "
+                    "phi [n_genes, P], logits, donor (every player's marks from the donor, the gene's masks and frequencies; phi sums to logits "
+                    "- donor) and donor_prediction (the donor's own prediction) (model.mark_donor_shapley).  --mark-players applies")
+    ap.add_argument("--mark-donor-epistasis-out", default=None, help="also write the pair epistasis of the histone marks against the donor cell "
+                    "type to this .npy file: [n_genes, P, P] in logit space, symmetric, the leave-one-out effects on the diagonal "
+                    "(model.mark_donor_epistasis).  --mark-players applies")
     return ap
 
 
@@ -504,8 +572,14 @@ def main(argv=None):
         ap.error("--scan-scale must be a finite factor >= 0")
     if args.scan_width is not None and args.scan_width < 1:
         ap.error("--scan-width must be at least 1")
-    if not args.mark_shapley_out and not args.mark_epistasis_out and (args.mark_players is not None or args.mark_scale is not None):
-        ap.error("--mark-players / --mark-scale need --mark-shapley-out or --mark-epistasis-out")
+    donor_out = args.mark_donor_shapley_out or args.mark_donor_epistasis_out
+    if donor_out and not args.donor_npy_dir:
+        ap.error("--mark-donor-shapley-out / --mark-donor-epistasis-out need --donor-npy-dir")
+    if not donor_out and (args.donor_npy_dir or args.donor_meta or args.donor_store):
+        ap.error("--donor-npy-dir / --donor-meta / --donor-store need --mark-donor-shapley-out or --mark-donor-epistasis-out")
+    if not args.mark_shapley_out and not args.mark_epistasis_out and (args.mark_scale is not None or (args.mark_players is not None and not donor_out)):
+        ap.error("--mark-players / --mark-scale need --mark-shapley-out or --mark-epistasis-out"
+                 " (--mark-players also applies to --mark-donor-shapley-out / --mark-donor-epistasis-out)")
     if args.mark_scale is not None and not (args.mark_scale >= 0 and np.isfinite(args.mark_scale)):
         ap.error("--mark-scale must be a finite factor >= 0")
     meta, pred = predict(args.meta, args.npy_dir, args.weights, args.regression, progress=True, store_path=args.store,
@@ -517,7 +591,9 @@ def main(argv=None):
                          scan_width=1 if args.scan_width is None else args.scan_width, scan_regions=args.scan_regions or "promoter",
                          pcre_shapley_out=args.pcre_shapley_out, pcre_epistasis_out=args.pcre_epistasis_out,
                          mark_shapley_out=args.mark_shapley_out, mark_epistasis_out=args.mark_epistasis_out,
-                         mark_players=args.mark_players or "marks", mark_scale=0.0 if args.mark_scale is None else args.mark_scale)
+                         mark_players=args.mark_players or "marks", mark_scale=0.0 if args.mark_scale is None else args.mark_scale,
+                         donor_npy_dir=args.donor_npy_dir, donor_meta=args.donor_meta, donor_store_path=args.donor_store,
+                         mark_donor_shapley_out=args.mark_donor_shapley_out, mark_donor_epistasis_out=args.mark_donor_epistasis_out)
     print("Predicting expressions for %d genes." % len(meta))
     meta["prediction"] = pred
     meta.to_csv(args.output, index=False)

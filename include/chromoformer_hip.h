@@ -426,6 +426,37 @@ int cf_mark_shapley(cf_handle* h, const cf_batch* batch, const cf_mark_opts* opt
  * eps [B, P, P, n_out].  logits_pairs: [B, 1 + P + P (P - 1) / 2, n_out], or NULL (the handle-owned buffer).  fwd = that of
  * cf_mark_coalitions with that n_coal, plus 1.  Refusals as above (null eps). */
 int cf_mark_epistasis(cf_handle* h, const cf_batch* batch, const cf_mark_opts* opts, float* eps, float* logits_pairs, void* stream);
+/* The same game against a DONOR (interpretation): gene G is predicted on in one cell type and off in another -- which mark changes
+ * account for the difference?  Players, coalition words and gone(rho) are those of cf_mark_coalitions; the caller passes, beside the
+ * batch, the same B genes' features in the other cell type, and every element of region rho (every row, every resolution, padded rows
+ * included) whose mark f has its bit in gone(rho) takes the BITS of the donor's element at the same (gene, region, row, resolution,
+ * mark).  A select, not arithmetic: NaN payloads, -0 and inf pass through unchanged.  Every other element keeps the gene's bits; all
+ * masks and interaction_freq are gene b's.  Players may overlap: an element is the donor's if any player that covers it is absent.
+ * Binning works per mark, so where the two cell types share a region's coordinates this is exactly the feature the binning produces
+ * when those marks' rows of the raw region are replaced by the donor's.  The donor may alias the batch's own feature pointers (every
+ * row is then the plain forward). */
+typedef struct cf_mark_donor_opts {
+    int n_players;                                   /* 1..16 */
+    const unsigned* player_marks;                    /* host [n_players], read before the call returns */
+    const unsigned* player_regions;                  /* host [n_players] */
+    const float* donor_promoter_feats[CF_MAX_RES];   /* device, layout of cf_batch.promoter_feats: what an ABSENT player's elements become */
+    const float* donor_pcre_feats[CF_MAX_RES];       /* device, layout of cf_batch.pcre_feats */
+} cf_mark_donor_opts;                                /* 72 bytes */
+/* cf_mark_donor_coalitions: keep, logits, the chunking, the launch count, the effect on saved activations and on parameters are those
+ * of cf_mark_coalitions, with k_mark_donor_expand in place of k_mark_expand: it reads the donor's bytes only in regions with
+ * gone(rho) != 0.  The full word 2^P - 1 is cf_forward(save = 0) on the batch, bit for bit; with every element covered by some player,
+ * word 0 is the donor's features under the gene's masks and frequencies.  Only the workspace of cf_mark_coalitions is used: no device
+ * buffer is added.
+ * Refused by name, before anything is launched: what cf_mark_coalitions refuses (there is no scale), and a null
+ * donor_promoter_feats[r] or donor_pcre_feats[r] for an r below the model's resolution count. */
+int cf_mark_donor_coalitions(cf_handle* h, const cf_batch* batch, const cf_mark_donor_opts* opts, const uint32_t* keep, int n_coal,
+                             float* logits, void* stream);
+/* cf_mark_shapley with the donor rule: phi [B, P, n_out], sum_p phi[b, p] = v[b, 2^P - 1] - v[b, 0] up to rounding -- the prediction
+ * minus the prediction on the donor's marks; a player whose elements carry the same bits in both feature sets (a slot that is a dummy
+ * in both) is a null player, phi exactly 0.  logits_all and fwd as there.  Refusals as above (null phi). */
+int cf_mark_donor_shapley(cf_handle* h, const cf_batch* batch, const cf_mark_donor_opts* opts, float* phi, float* logits_all, void* stream);
+/* cf_mark_epistasis with the donor rule: eps [B, P, P, n_out], rows, logits_pairs and fwd as there.  Refusals as above (null eps). */
+int cf_mark_donor_epistasis(cf_handle* h, const cf_batch* batch, const cf_mark_donor_opts* opts, float* eps, float* logits_pairs, void* stream);
 /* torch.optim.AdamW.step (train.py:157, 196): decoupled weight decay, bias correction
  * from `step` (1-based), over [0, n_active). */
 int cf_adamw_step(cf_handle* h, float lr, float beta1, float beta2, float eps, float weight_decay,
