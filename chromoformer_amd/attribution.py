@@ -94,6 +94,11 @@ def mark_players(spec, n_feats, i_max):
       a list of (marks, regions) pairs of index iterables (regions: 0 the promoter, 1 + j pCRE slot j); players may overlap
 
     More than 16 players, an empty player or an index out of range raise ValueError naming mark_players."""
+    return _mark_players(spec, n_feats, i_max, "mark_players", MARK_PLAYER_SPECS, 16, "the exact game takes 1..16")
+
+
+def _mark_players(spec, n_feats, i_max, who, specs, limit, limit_text):
+    """mark_players / mark_players_wide: `specs` the named specs offered, `limit` the most players, `who` the name in the messages."""
     F, S = int(n_feats), int(i_max)
     every_mark, every_region = list(range(F)), list(range(S + 1))
     if isinstance(spec, str):
@@ -106,24 +111,27 @@ def mark_players(spec, n_feats, i_max):
         elif spec == "regions":
             pairs = [(every_mark, [rho]) for rho in every_region]
             names = ["promoter"] + ["pcre%d" % j for j in range(S)]
+        elif spec == "cells" and spec in specs:
+            pairs = [([f], [rho]) for rho in every_region for f in every_mark]
+            names = ["mark%d@%s" % (f, "promoter" if rho == 0 else "pcre%d" % (rho - 1)) for rho in every_region for f in every_mark]
         else:
-            raise ValueError("mark_players: players %r; choose from %s or give a list of (marks, regions) pairs" % (spec, MARK_PLAYER_SPECS))
+            raise ValueError("%s: players %r; choose from %s or give a list of (marks, regions) pairs" % (who, spec, specs))
     else:
         try:
             pairs = [(sorted({int(f) for f in ms}), sorted({int(r) for r in rs})) for ms, rs in spec]
         except (TypeError, ValueError):
-            raise ValueError("mark_players: players must be one of %s or a list of (marks, regions) pairs of index iterables, got %r"
-                             % (MARK_PLAYER_SPECS, spec)) from None
+            raise ValueError("%s: players must be one of %s or a list of (marks, regions) pairs of index iterables, got %r"
+                             % (who, specs, spec)) from None
         names = ["marks(%s)@regions(%s)" % (",".join(map(str, ms)), ",".join(map(str, rs))) for ms, rs in pairs]
-    if not 1 <= len(pairs) <= 16:
-        raise ValueError("mark_players: %d players; the exact game takes 1..16" % len(pairs))
+    if not 1 <= len(pairs) <= limit:
+        raise ValueError("%s: %d players; %s" % (who, len(pairs), limit_text))
     for p, (ms, rs) in enumerate(pairs):
         if not ms or not rs:
-            raise ValueError("mark_players: player %d is empty: at least one mark and one region" % p)
+            raise ValueError("%s: player %d is empty: at least one mark and one region" % (who, p))
         if ms[0] < 0 or ms[-1] >= min(F, 32):
-            raise ValueError("mark_players: player %d names mark(s) %s outside [0, n_feats = %d)" % (p, ms, F))
+            raise ValueError("%s: player %d names mark(s) %s outside [0, n_feats = %d)" % (who, p, ms, F))
         if rs[0] < 0 or rs[-1] > S:
-            raise ValueError("mark_players: player %d names region(s) %s outside [0, i_max = %d]" % (p, rs, S))
+            raise ValueError("%s: player %d names region(s) %s outside [0, i_max = %d]" % (who, p, rs, S))
     marks = np.array([sum(1 << f for f in ms) for ms, _ in pairs], dtype=np.uint32)
     regions = np.array([sum(1 << r for r in rs) for _, rs in pairs], dtype=np.uint32)
     return marks, regions, names
@@ -133,6 +141,58 @@ def mark_coalition_words(keep, n_players, who="mark_coalitions"):
     """`keep` as the uint32 words the library reads: a sequence / array of ints (bit p set: player p present), or a bool array
     [n_coal, P].  Empty input, a negative word or a bit >= P raise ValueError naming `who`."""
     return coalition_words(keep, n_players, who, item="player", limit="n_players")
+
+
+MARK_WIDE_PLAYER_SPECS = MARK_PLAYER_SPECS + ("cells",)
+MARK_WIDE_MAX_PLAYERS = 128
+
+
+def mark_players_wide(spec, n_feats, i_max):
+    """The players of the wide histone-mark game (ChromoformerBase.mark_coalitions_wide / mark_shapley_sampled) -> (marks, regions,
+    names) as mark_players returns them, for up to 128 players.  spec: what mark_players takes, or
+
+      "cells"   P = n_feats (i_max + 1): player rho * n_feats + f is mark f in region rho alone ("mark0@promoter", ...,
+                "mark0@pcre0", ...); a [B, P, n_out] result reshapes to [B, i_max + 1, n_feats, n_out]
+
+    More than 128 players, an empty player or an index out of range raise ValueError naming mark_players_wide."""
+    return _mark_players(spec, n_feats, i_max, "mark_players_wide", MARK_WIDE_PLAYER_SPECS, MARK_WIDE_MAX_PLAYERS,
+                         "the sampled game takes 1..%d" % MARK_WIDE_MAX_PLAYERS)
+
+
+def mark_wide_words(keep, P, who="mark_coalitions_wide"):
+    """`keep` as the uint32 words [n_coal, kw], kw = ceil(P / 32), the wide game reads (bit p % 32 of word p / 32 set: player p
+    present): a bool array [n_coal, P], or a sequence of Python ints of any width (bit p set: player p present).  Empty input, a
+    negative int or a bit >= P raise ValueError naming `who`."""
+    P = int(P)
+    kw = (P + 31) // 32
+    a = keep.cpu().numpy() if hasattr(keep, "cpu") else keep
+    if isinstance(a, np.ndarray) and a.dtype == np.bool_:
+        if a.ndim != 2 or a.shape[1] != P or a.shape[0] < 1:
+            raise ValueError("%s: a bool keep must be [n_coal >= 1, n_players = %d], got %s" % (who, P, tuple(a.shape)))
+        bits = np.zeros((a.shape[0], kw * 32), dtype=np.uint64)
+        bits[:, :P] = a
+        return np.ascontiguousarray((bits.reshape(a.shape[0], kw, 32) << np.arange(32, dtype=np.uint64)).sum(2).astype(np.uint32))
+    try:
+        ints = [int(m) for m in a]
+        exact = all(m == x for m, x in zip(ints, a))
+    except (TypeError, ValueError):
+        ints, exact = [], False
+    if not ints or not exact:
+        raise ValueError("%s: keep must be a non-empty sequence of ints or a bool array [n_coal, n_players = %d]" % (who, P))
+    bad = [m for m in ints if m < 0 or m >> P]
+    if bad:
+        raise ValueError("%s: keep word(s) %s name a player >= n_players = %d (or are negative)" % (who, [hex(m) for m in bad[:4]], P))
+    return np.array([[(m >> (32 * w)) & 0xFFFFFFFF for w in range(kw)] for m in ints], dtype=np.uint32).reshape(len(ints), kw)
+
+
+def shapley_permutations(P, n_perm, seed=0):
+    """n_perm independent uniform orders of P players -> uint8 [n_perm, P], each row a permutation of 0..P-1, from
+    numpy.random.Generator(PCG64(seed)): the same seed gives the same orders."""
+    P, n_perm = int(P), int(n_perm)
+    if not 1 <= P <= MARK_WIDE_MAX_PLAYERS or n_perm < 1:
+        raise ValueError("shapley_permutations: P = %d in 1..%d and n_perm = %d >= 1 are required" % (P, MARK_WIDE_MAX_PLAYERS, n_perm))
+    rng = np.random.Generator(np.random.PCG64(int(seed)))
+    return np.stack([rng.permutation(P) for _ in range(n_perm)]).astype(np.uint8)
 
 
 def _geometry_check(who, model, dataset, binsizes):
@@ -638,3 +698,51 @@ def mark_donor_shapley(model, dataset, donor_dataset, genes=None, players="marks
             if epistasis:
                 out["eps"] = eps[i].copy()
             yield out
+
+
+def mark_shapley_sampled(model, dataset, donor_dataset=None, genes=None, players="cells", n_perm=64, seed=0, scale=0.0, bsz=None, store=None,
+                         donor_store=None):
+    """Permutation-sampled Shapley values of up to 128 histone-mark players for the genes of a ChromoformerDataset (one
+    model.mark_shapley_sampled per batch): which mark matters at which region?  Without `donor_dataset` an absent player's raw signal
+    is scaled by `scale` (0 erases it); with one -- the same genes over the same regions in another cell type (same_regions runs
+    first) -- it takes the donor's signal.  A generator over `genes` (ids; default: the dataset's) in chunks of at most
+    min(bsz, model.max_batch) genes; per gene it yields a dict of host arrays:
+
+        gene_id        the id
+        phi            float32 [P, n_out]: the estimates, in logit space; phi.sum(0) = logits - absent up to rounding
+        stderr         float32 [P, n_out]: the standard error of phi over the sampled orders -- the sampling error is reported here
+                       and not bounded anywhere
+        logits         float32 [n_out]: the prediction (every player present)
+        absent         float32 [n_out]: every player absent
+        players        the players' names (mark_players_wide); "cells": phi.reshape(i_max + 1, n_feats, n_out)
+        permutations   uint8 [n_perm, P]: the orders, shapley_permutations(P, n_perm, seed), the same for every gene
+
+    The binned features come from `store` / `donor_store` as in mark_donor_shapley.  Parameters, gradients and optimiser state are left
+    as they are; the pass overwrites the activations a grad-enabled model(...) keeps for its backward."""
+    ds, dn = dataset, donor_dataset
+    who = "mark_shapley_sampled"
+    binsizes = [int(b) for b in ds.binsizes]
+    _geometry_check(who, model, ds, binsizes)
+    genes, chunk = _genes_check(who, model, ds, genes, bsz)
+    if dn is not None:
+        same_regions(ds, dn, genes)
+    spec = players if isinstance(players, str) else list(players)
+    names = mark_players_wide(spec, ds.n_feats, ds.i_max)[2]      # (refusals before anything is loaded)
+    perms = shapley_permutations(len(names), n_perm, seed)
+    store = _resident_store(who, ds, genes, binsizes, model._device, store)
+    if dn is not None:
+        donor_store = _resident_store(who, dn, genes, binsizes, model._device, donor_store)
+    keys = ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq")
+    for lo in range(0, len(genes), chunk):
+        ids = genes[lo:lo + chunk]
+        idx = list(range(lo, lo + len(ids)))
+        d = store.batch(idx)
+        donor = None
+        if dn is not None:
+            dd = donor_store.batch(idx)
+            donor = ({b: t.contiguous() for b, t in dd["promoter_feats"].items()}, {b: t.contiguous() for b, t in dd["pcre_feats"].items()})
+        phi, info = model.mark_shapley_sampled(*(d[k] for k in keys), players=spec, permutations=perms, scale=scale, donor=donor)
+        phi, se, logits, absent = phi.cpu().numpy(), info["stderr"].cpu().numpy(), info["logits"].cpu().numpy(), info["absent"].cpu().numpy()
+        for i, g in enumerate(ids):
+            yield dict(gene_id=g, phi=phi[i].copy(), stderr=se[i].copy(), logits=logits[i].copy(), absent=absent[i].copy(), players=list(names),
+                       permutations=perms.copy())

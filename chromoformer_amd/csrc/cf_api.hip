@@ -10,6 +10,7 @@
 #include "cf_ig.h"
 #include "cf_scan.h"
 #include "cf_marks.h"
+#include "cf_marks_wide.h"
 #include "cf_x0_gather.h"
 
 #include <algorithm>

@@ -1,5 +1,5 @@
 // cf_api_attrib.h -- host side of the attribution entry points (input gradients, attention maps, pCRE deletion, pCRE coalitions, integrated
-// gradients, perturbation scan, histone-mark coalitions and their donor form).  Part of cf_api.hip's single translation unit: included there behind cf_api_bwd.h, not on its own.
+// gradients, perturbation scan, histone-mark coalitions, their donor form, the wide game and its sampled Shapley values).  Part of cf_api.hip's single translation unit: included there behind cf_api_bwd.h, not on its own.
 #pragma once
 
 // k_input_grad's dynamic LDS size; the first call sets the kernel's attribute.  0: that failed (`who`: the entry point, for the error text).
@@ -771,16 +771,17 @@ struct MarkGame {
     const unsigned* regions;              // host [P]
     float scale;                          // the scale rule (donor == nullptr)
     const cf_mark_donor_opts* donor;      // the donor rule
+    int kw = 0;                           // words per coalition of the wide game (cf_marks_wide.h); 0: the one-word kernels
 };
 
 // mark_check: what the entry points check alike, in front of anything launched -- the handle, the batch, riders, the options: the
-// player count, the player words.  `o`: whether the caller's opts pointer is non-null.
-static int mark_check(cf_handle* h, const cf_batch* bt, bool o, const MarkGame& g, const char* who) {
+// player count (at most `limit`), the player words.  `o`: whether the caller's opts pointer is non-null.
+static int mark_check(cf_handle* h, const cf_batch* bt, bool o, const MarkGame& g, const char* who, int limit = kCoalMaxS) {
     if (attrib_open(h, bt, true, who)) return -1;
     if (!o) return fail("%s: null opts", who);
     const cf_config& c = h->cfg;
     const int S = c.i_max, F = c.n_feats;
-    if (g.P < 1 || g.P > kCoalMaxS) return fail("%s: n_players = %d outside 1..%d", who, g.P, kCoalMaxS);
+    if (g.P < 1 || g.P > limit) return fail("%s: n_players = %d outside 1..%d", who, g.P, limit);
     if (!g.marks || !g.regions) return fail("%s: null player_marks / player_regions", who);
     for (int p = 0; p < g.P; ++p) {
         const unsigned pm = g.marks[p], pr = g.regions[p];
@@ -824,7 +825,8 @@ static int mark_upload(cf_handle* h, const MarkGame& g, const uint32_t* keep, in
 }
 
 // The B * n_coal rows of a mark-coalition call (gene-major; row (b, k) is word k of the table mark_upload wrote), every row through
-// the whole forward.  Per chunk of at most max_batch rows: k_mark_expand (the donor rule: k_mark_donor_expand) into the chunk workspace,
+// the whole forward.  Per chunk of at most max_batch rows: k_mark_expand (the donor rule: k_mark_donor_expand; the wide game, whose rows
+// are g.kw words each: k_mark_wide_expand / k_mark_wide_donor_expand) into the chunk workspace,
 // then the launches of cf_forward(save = 0) on the chunk, writing its slice of `logits`.  k_attc2 takes as many regions per workgroup
 // as for the caller's B genes (ag_genes), as scan_region_rows: the result does not depend on max_batch.
 static int mark_rows(cf_handle* h, const cf_batch* bt, const MarkGame& g, int n_coal, float* logits, hipStream_t st) {
@@ -848,7 +850,7 @@ static int mark_rows(cf_handle* h, const cf_batch* bt, const MarkGame& g, int n_
     ea.freq_in = bt->interaction_freq;
     ea.freq_out = h->aw.row[2 * kMaxRes];
     ea.words = h->aw.words;
-    ea.players = h->aw.words + n_coal;
+    ea.players = h->aw.words + (size_t)n_coal * (g.kw ? g.kw : 1);
     ea.scale = g.scale;
     ea.n_coal = n_coal, ea.P = P, ea.F = c.n_feats;
     const long long launches0 = g_launches, rows = (long long)B * n_coal;
@@ -856,7 +858,13 @@ static int mark_rows(cf_handle* h, const cf_batch* bt, const MarkGame& g, int n_
         for (long long g0 = 0; g0 < rows; g0 += cap) {
             const int n = (int)std::min<long long>(cap, rows - g0);
             ea.g0 = g0;
-            if (g.donor) {
+            if (g.kw && g.donor) {
+                hipLaunchKernelGGL(k_mark_wide_donor_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, da);
+                LAUNCH_CHECK("k_mark_wide_donor_expand");
+            } else if (g.kw) {
+                hipLaunchKernelGGL(k_mark_wide_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, ea);
+                LAUNCH_CHECK("k_mark_wide_expand");
+            } else if (g.donor) {
                 hipLaunchKernelGGL(k_mark_donor_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, da);
                 LAUNCH_CHECK("k_mark_donor_expand");
             } else {
@@ -963,4 +971,110 @@ extern "C" int cf_mark_donor_epistasis(cf_handle* h, const cf_batch* bt, const c
     const char* who = "cf_mark_donor_epistasis";
     MarkGame g;
     return mark_donor_game(h, bt, o, &g, who) ? -1 : mark_epistasis_impl(h, bt, g, eps, logits_pairs, stream, who);
+}
+
+// The wide game (cf_marks_wide.h): up to kMarkWideMaxP players, kw words per coalition, one options struct for both rules.  `d`: the
+// donor's pointers in the struct mark_rows reads them from (the caller's storage).
+static int mark_wide_game(cf_handle* h, const cf_batch* bt, const cf_mark_wide_opts* o, MarkGame* g, cf_mark_donor_opts* d, const char* who) {
+    *g = o ? MarkGame{o->n_players, o->player_marks, o->player_regions, o->scale, nullptr} : MarkGame{};
+    if (mark_check(h, bt, o != nullptr, *g, who, kMarkWideMaxP)) return -1;
+    g->kw = (g->P + 31) / 32;
+    int given = 0;
+    for (int r = 0; r < h->cfg.n_res; ++r) given += (o->donor_promoter_feats[r] != nullptr) + (o->donor_pcre_feats[r] != nullptr);
+    if (given && given != 2 * h->cfg.n_res)
+        return fail("%s: %d of the %d donor_promoter_feats / donor_pcre_feats pointers below the model's %d resolutions are null: all of them "
+                    "(the scale rule) or none (the donor rule)", who, 2 * h->cfg.n_res - given, 2 * h->cfg.n_res, h->cfg.n_res);
+    if (given) {
+        memset(d, 0, sizeof *d);
+        for (int r = 0; r < h->cfg.n_res; ++r) d->donor_promoter_feats[r] = o->donor_promoter_feats[r], d->donor_pcre_feats[r] = o->donor_pcre_feats[r];
+        g->donor = d;
+        g->scale = 0.f;
+    } else if (!(o->scale >= 0.f) || !std::isfinite(o->scale)) {
+        return fail("%s: scale = %g: a finite factor >= 0", who, (double)o->scale);
+    }
+    return 0;
+}
+
+// The n_coal * kw coalition words (validated) and the 2 P player words into the workspace's word table, with room for `extra` words
+// behind them: [words | marks_p | regions_p | extra].
+static int mark_wide_upload(cf_handle* h, const MarkGame& g, const uint32_t* keep, int n_coal, size_t extra, hipStream_t st, const char* who) {
+    const int P = g.P, kw = g.kw;
+    if (n_coal < 1) return fail("%s: n_coal = %d: at least 1 coalition", who, n_coal);
+    if (!keep) return fail("%s: null keep", who);
+    if (P & 31)
+        for (int k = 0; k < n_coal; ++k) {
+            const uint32_t last = keep[(size_t)k * kw + kw - 1];
+            if (last >> (P & 31)) return fail("%s: keep[%d] (word %d = 0x%x) names a player >= n_players = %d", who, k, kw - 1, last, P);
+        }
+    const size_t nw = (size_t)n_coal * kw;
+    if (attrib_ws(h, who) || h->aw.words.need(nw + 2 * P + extra, 256, who)) return -1;
+    unsigned* tab = h->aw.words;
+    HIP_TRY(hipMemcpyAsync(tab, keep, nw * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(tab + nw, g.marks, P * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(tab + nw + P, g.regions, P * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+extern "C" int cf_mark_coalitions_wide(cf_handle* h, const cf_batch* bt, const cf_mark_wide_opts* o, const uint32_t* keep, int n_coal, float* logits,
+                                       void* stream) {
+    const char* who = "cf_mark_coalitions_wide";
+    MarkGame g;
+    cf_mark_donor_opts d;
+    if (mark_wide_game(h, bt, o, &g, &d, who)) return -1;
+    if (!logits) return fail("%s: null logits", who);
+    hipStream_t st = (hipStream_t)stream;
+    if (mark_wide_upload(h, g, keep, n_coal, 0, st, who)) return -1;
+    return mark_rows(h, bt, g, n_coal, logits, st);
+}
+
+// The prefix rows of n_perm permutations through mark_wide_upload + mark_rows (column 0 nobody, column 1 everybody, column
+// 2 + q (P - 1) + (k - 1) the first k players of permutation q), then k_perm_shapley on the inverse permutations, which travel as bytes
+// behind the player words.
+extern "C" int cf_mark_shapley_sampled(cf_handle* h, const cf_batch* bt, const cf_mark_wide_opts* o, const uint8_t* perms, int n_perm, float* phi,
+                                       float* se, float* logits_rows, void* stream) {
+    const char* who = "cf_mark_shapley_sampled";
+    MarkGame g;
+    cf_mark_donor_opts d;
+    if (mark_wide_game(h, bt, o, &g, &d, who)) return -1;
+    if (!phi) return fail("%s: null phi", who);
+    if (!perms) return fail("%s: null perms", who);
+    if (n_perm < 1) return fail("%s: n_perm = %d: at least 1 permutation", who, n_perm);
+    const cf_config& c = h->cfg;
+    const int P = g.P, kw = g.kw;
+    const long long R64 = 2 + (long long)n_perm * (P - 1);
+    if (R64 * kw > (1ll << 30)) return fail("%s: n_perm = %d: %lld rows per gene; at most 2^30 coalition words", who, n_perm, R64);
+    const int R = (int)R64;
+    std::vector<uint8_t> rank((size_t)n_perm * P);
+    std::vector<uint32_t> keep((size_t)R * kw, 0u), cur(kw);
+    for (int p = 0; p < P; ++p) keep[kw + (p >> 5)] |= 1u << (p & 31);      // column 1: everybody
+    for (int q = 0; q < n_perm; ++q) {
+        const uint8_t* pi = perms + (size_t)q * P;
+        uint8_t* rk = rank.data() + (size_t)q * P;
+        memset(rk, 0xFF, P);
+        for (int k = 0; k < P; ++k) {
+            if (pi[k] >= P || rk[pi[k]] != 0xFF) return fail("%s: perms[%d] is not a permutation of 0..%d (position %d holds %d)", who, q, P - 1, k, (int)pi[k]);
+            rk[pi[k]] = (uint8_t)k;
+        }
+        std::fill(cur.begin(), cur.end(), 0u);
+        for (int k = 1; k < P; ++k) {
+            cur[pi[k - 1] >> 5] |= 1u << (pi[k - 1] & 31);
+            memcpy(&keep[(2 + (size_t)q * (P - 1) + (k - 1)) * kw], cur.data(), kw * sizeof(uint32_t));
+        }
+    }
+    float* rows = coalition_out_rows(h, logits_rows, R, who);
+    if (!rows) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    if (mark_wide_upload(h, g, keep.data(), R, (rank.size() + 3) / 4, st, who)) return -1;
+    uint8_t* rank_at = reinterpret_cast<uint8_t*>((unsigned*)h->aw.words + (size_t)R * kw + 2 * P);
+    HIP_TRY(hipMemcpyAsync(rank_at, rank.data(), rank.size(), hipMemcpyHostToDevice, st));
+    if (mark_rows(h, bt, g, R, rows, st)) return -1;
+    PermShapleyArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.v = rows, pa.rank = rank_at, pa.phi = phi, pa.se = se;
+    pa.n = (float)n_perm, pa.nn1 = (float)((double)n_perm * (n_perm - 1));
+    pa.P = P, pa.n_perm = n_perm, pa.n_out = c.n_out;
+    hipLaunchKernelGGL(k_perm_shapley, dim3(bt->B, P), dim3(kShapThreads), 0, st, pa);
+    LAUNCH_CHECK("k_perm_shapley");
+    forward_one_more(h);
+    return 0;
 }

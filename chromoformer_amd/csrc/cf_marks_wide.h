@@ -1,0 +1,124 @@
+// cf_marks_wide.h -- histone-mark coalitions over up to 128 players and their permutation-sampled Shapley values
+// (cf_mark_coalitions_wide, cf_mark_shapley_sampled; included by cf_api.hip behind cf_marks.h).
+//
+// The game is that of cf_marks.h -- the same (marks_p, regions_p) player words, the same gone(rho), the same scale rule and donor rule,
+// element by element -- with more players than one word holds: "mark f in region rho" is n_feats (i_max + 1) players, 63 on the default
+// model, 119 at i_max = 16.  A coalition over P <= kMarkWideMaxP players is kw = ceil(P / 32) consecutive 32-bit words, bit p % 32 of
+// word p / 32 set = player p PRESENT; row (b, k) reads words [k kw, (k + 1) kw) of the device table.
+//   k_mark_wide_expand         k_mark_expand with gone(rho) formed from the row's kw words: the grid (chunk row x resolution x
+//   k_mark_wide_donor_expand   kMarkSlices), the 68 bytes of LDS, mark_copy / mark_donor_copy and the slice-0 mask and frequency copies
+//                              are the sibling's.  The few gone lines are repeated here, not shared: the shipped kernels keep their code.
+// 2^P coalitions cannot be enumerated, so the Shapley values are ESTIMATED from n_perm orders of adding the players (permutations):
+//   rows of gene b   column 0 nobody present, column 1 everybody (both shared by all permutations), column 2 + q (P - 1) + (k - 1) the
+//                    first k players of permutation q, k = 1 .. P - 1: R = 2 + n_perm (P - 1) rows
+//   k_perm_shapley   per (gene, player p), rank_q[p] = r the position of p in permutation q (bytes, the inverse permutations):
+//                        d_q = v[col(q, r + 1)] - v[col(q, r)]                              one fp32 subtraction
+//                        phi = (sum_q d_q) / n_perm
+//                        se  = sqrt(sum_q (d_q - phi)^2 / (n_perm (n_perm - 1)))            0 for n_perm = 1
+//                    each operation rounded to fp32, a fixed order: thread t sums q = t, t + kShapThreads, ..., then the LDS tree of
+//                    k_shapley.  No atomics.  A player whose two adjacent rows carry the same bits in every permutation has d_q = 0
+//                    throughout: phi and se exactly 0.  Efficiency telescopes within every permutation: sum_p phi = v_N - v_0 up to
+//                    rounding.  The SAMPLING error is what se reports; nothing in the code bounds it.
+#pragma once
+
+namespace cf {
+
+constexpr int kMarkWideMaxP = 128;     // players of the wide game: four words
+
+// (both kernels take the argument structs of their siblings; kw follows from P)
+__global__ __launch_bounds__(kIgxThreads) void k_mark_wide_expand(MarkExpandArgs a) {
+    __shared__ unsigned gone[kCoalMaxS + 1];      // gone(rho), rho = 0 .. i_max: 68 bytes
+    const int i = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
+    const long long gv = a.g0 + i;
+    const int b = (int)(gv / a.n_coal);
+    const int L = a.rows.L[r], S = a.rows.S, F = a.F, LF = L * F, P = a.P;
+    if (tid <= S) {
+        const unsigned* __restrict__ m = a.words + (gv - (long long)b * a.n_coal) * ((P + 31) >> 5);
+        unsigned g = 0;
+        for (int p = 0; p < P; ++p)
+            if (!((m[p >> 5] >> (p & 31)) & 1u) && ((a.players[P + p] >> tid) & 1u)) g |= a.players[p];
+        gone[tid] = g;
+    }
+    __syncthreads();
+    mark_copy(a.pf_in[r] + (size_t)b * LF, a.pf_out[r] + (size_t)i * LF, LF, LF, F, gone, a.scale);
+    mark_copy(a.cf_in[r] + (size_t)b * S * LF, a.cf_out[r] + (size_t)i * S * LF, S * LF, LF, F, gone + 1, a.scale);
+    if (blockIdx.z) return;
+    rows_pad_masks(a.rows, r, b, i);
+    rows_interaction_mask(a.rows, r, b, i);
+    if (r == 0) rows_copy_tt(a.freq_in, a.freq_out, b, i, a.rows.TT);
+}
+
+__global__ __launch_bounds__(kIgxThreads) void k_mark_wide_donor_expand(MarkDonorArgs da) {
+    __shared__ unsigned gone[kCoalMaxS + 1];      // gone(rho), rho = 0 .. i_max: 68 bytes
+    const MarkExpandArgs& a = da.m;
+    const int i = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
+    const long long gv = a.g0 + i;
+    const int b = (int)(gv / a.n_coal);
+    const int L = a.rows.L[r], S = a.rows.S, F = a.F, LF = L * F, P = a.P;
+    if (tid <= S) {      // (as k_mark_wide_expand)
+        const unsigned* __restrict__ m = a.words + (gv - (long long)b * a.n_coal) * ((P + 31) >> 5);
+        unsigned g = 0;
+        for (int p = 0; p < P; ++p)
+            if (!((m[p >> 5] >> (p & 31)) & 1u) && ((a.players[P + p] >> tid) & 1u)) g |= a.players[p];
+        gone[tid] = g;
+    }
+    __syncthreads();
+    mark_donor_copy(a.pf_in[r] + (size_t)b * LF, da.pf_don[r] + (size_t)b * LF, a.pf_out[r] + (size_t)i * LF, LF, LF, F, gone);
+    mark_donor_copy(a.cf_in[r] + (size_t)b * S * LF, da.cf_don[r] + (size_t)b * S * LF, a.cf_out[r] + (size_t)i * S * LF, S * LF, LF, F, gone + 1);
+    if (blockIdx.z) return;
+    rows_pad_masks(a.rows, r, b, i);
+    rows_interaction_mask(a.rows, r, b, i);
+    if (r == 0) rows_copy_tt(a.freq_in, a.freq_out, b, i, a.rows.TT);
+}
+
+struct PermShapleyArgs {
+    const float* v;                          // [B, R, n_out], R = 2 + n_perm (P - 1): the prefix rows
+    const uint8_t* rank;                     // [n_perm, P]: rank[q, p] = the position of player p in permutation q
+    float* phi;                              // [B, P, n_out]
+    float* se;                               // [B, P, n_out], or null
+    float n, nn1;                            // n_perm and n_perm (n_perm - 1) as floats (the host rounds them once)
+    int P, n_perm, n_out;
+};
+
+__global__ __launch_bounds__(kShapThreads) void k_perm_shapley(PermShapleyArgs a) {
+    __shared__ float red[kShapThreads];
+    const int b = blockIdx.x, p = blockIdx.y, tid = threadIdx.x, P = a.P, n_perm = a.n_perm, n_out = a.n_out;
+    const size_t R = 2 + (size_t)n_perm * (P - 1);
+    const float* __restrict__ v = a.v + (size_t)b * R * n_out;
+    // the column of the first k players of permutation q: nobody, everybody, else the permutation's own row
+    auto col = [&](int q, int k) -> size_t { return k == 0 ? 0 : k == P ? 1 : 2 + (size_t)q * (P - 1) + (k - 1); };
+    for (int o = 0; o < n_out; ++o) {
+        float acc = 0.f;
+        for (int q = tid; q < n_perm; q += kShapThreads) {
+            const int r = a.rank[(size_t)q * P + p];
+            acc = __fadd_rn(acc, __fsub_rn(v[col(q, r + 1) * n_out + o], v[col(q, r) * n_out + o]));
+        }
+        red[tid] = acc;
+        __syncthreads();
+        for (int s = kShapThreads / 2; s > 0; s >>= 1) {
+            if (tid < s) red[tid] = __fadd_rn(red[tid], red[tid + s]);
+            __syncthreads();
+        }
+        const float phi = __fdiv_rn(red[0], a.n);
+        __syncthreads();
+        const size_t at = ((size_t)b * P + p) * n_out + o;
+        if (tid == 0) a.phi[at] = phi;
+        if (!a.se) continue;
+        acc = 0.f;
+        for (int q = tid; q < n_perm; q += kShapThreads) {
+            const int r = a.rank[(size_t)q * P + p];
+            const float e = __fsub_rn(__fsub_rn(v[col(q, r + 1) * n_out + o], v[col(q, r) * n_out + o]), phi);
+            acc = __fadd_rn(acc, __fmul_rn(e, e));
+        }
+        red[tid] = acc;
+        __syncthreads();
+        for (int s = kShapThreads / 2; s > 0; s >>= 1) {
+            if (tid < s) red[tid] = __fadd_rn(red[tid], red[tid + s]);
+            __syncthreads();
+        }
+        if (tid == 0) a.se[at] = n_perm > 1 ? __fsqrt_rn(__fdiv_rn(red[0], a.nn1)) : 0.f;
+        __syncthreads();
+    }
+}
+
+}  // namespace cf

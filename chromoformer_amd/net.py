@@ -878,6 +878,11 @@ class ChromoformerBase(nn.Module):
         opts = _lib.cf_mark_donor_opts()
         opts.n_players = len(marks)
         opts.player_marks, opts.player_regions = marks.ctypes.data, regions.ctypes.data
+        return opts, (marks, regions) + self._donor_feats(who, donor, B, opts), names
+
+    def _donor_feats(self, who, donor, B, opts):
+        """The donor of a batch of B genes (the forms of _mark_donor_opts) checked, its feature pointers written into
+        opts.donor_promoter_feats / donor_pcre_feats -> what they point to."""
         if donor is None:
             raise ValueError("%s: donor is required: the same genes' features in the other cell type, a (promoter_feats, pcre_feats) "
                              "pair or a packed batch" % who)
@@ -890,7 +895,7 @@ class ChromoformerBase(nn.Module):
                 raise ValueError("%s: the donor holds %d genes, the batch %d" % (who, packed.B, B))
             for r in range(len(self.binsizes)):
                 opts.donor_promoter_feats[r], opts.donor_pcre_feats[r] = packed.promoter_feats[r], packed.pcre_feats[r]
-            return opts, (marks, regions, donor), names
+            return (donor,)
         try:
             pfs, cfs = donor
             pfs = [pfs[b] for b in self.binsizes] if isinstance(pfs, dict) else list(pfs)
@@ -915,7 +920,7 @@ class ChromoformerBase(nn.Module):
                 if not t.is_contiguous():
                     raise ValueError("%s is not contiguous" % what)
             opts.donor_promoter_feats[r], opts.donor_pcre_feats[r] = pfs[r].data_ptr(), cfs[r].data_ptr()
-        return opts, (marks, regions, pfs, cfs), names
+        return (pfs, cfs)
 
     @torch.no_grad()
     def mark_donor_coalitions(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
@@ -996,6 +1001,97 @@ class ChromoformerBase(nn.Module):
         from .attribution import mark_donor_shapley
         return mark_donor_shapley(self, dataset, donor_dataset, genes=genes, players=players, epistasis=epistasis, bsz=bsz, store=store,
                                   donor_store=donor_store)
+
+    def _mark_wide_opts(self, who, players, scale, donor, B):
+        """players (a mark_players_wide spec), scale and donor (None: the scale rule; else the forms of _mark_donor_opts) for a batch of
+        B genes -> (cf_mark_wide_opts, what it points to, names)."""
+        from .attribution import mark_players_wide
+        marks, regions, names = mark_players_wide(players, self.n_feats, self.i_max)
+        opts = _lib.cf_mark_wide_opts()
+        opts.n_players, opts.scale = len(marks), float(scale)
+        opts.player_marks, opts.player_regions = marks.ctypes.data, regions.ctypes.data
+        alive = (marks, regions) + (self._donor_feats(who, donor, B, opts) if donor is not None else ())
+        return opts, alive, names
+
+    @torch.no_grad()
+    def mark_coalitions_wide(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                             interaction_freq=None, keep=None, players="cells", scale=0.0, donor=None):
+        """The prediction under histone-mark coalitions of up to 128 players (cf_mark_coalitions_wide) -> logits [B, n_coal, n_out] on
+        the model's device, no autograd graph.  players: attribution.mark_players_wide -- what mark_coalitions takes, or "cells", one
+        player per (mark, region) pair: n_feats (i_max + 1) of them.  `keep`: a bool array [n_coal, P], or a sequence of Python ints
+        (bit p set = player p present; attribution.mark_wide_words).  donor None: an ABSENT player's raw signal is scaled by `scale`
+        (0 erases) as in mark_coalitions; a donor (the forms of mark_donor_coalitions): its elements take the donor's bits and `scale`
+        is not read.  With at most 16 players the rows carry the bits of mark_coalitions / mark_donor_coalitions.  The packed forms
+        of the first argument and the effect on a pending backward() are those of mark_coalitions."""
+        from .attribution import mark_wide_words
+        who = "mark_coalitions_wide"
+        if keep is None:
+            raise ValueError("mark_coalitions_wide: keep is required: the coalitions (bit p set: player p present)")
+        bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        opts, _alive, _names = self._mark_wide_opts(who, players, scale, donor, bs.B)
+        words = mark_wide_words(keep, opts.n_players, who)
+        logits = torch.empty(bs.B, len(words), self.n_out, device=self._device)      # (written in full by the library)
+        st = book()
+        _lib.check(_lib.lib().cf_mark_coalitions_wide(self._handle, C.byref(bs), C.byref(opts), words.ctypes.data, len(words), logits.data_ptr(), st),
+                   "cf_mark_coalitions_wide")
+        return logits
+
+    @torch.no_grad()
+    def mark_shapley_sampled(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                             interaction_freq=None, players="cells", n_perm=64, seed=0, permutations=None, scale=0.0, donor=None,
+                             return_rows=False):
+        """Permutation-sampled Shapley values of up to 128 histone-mark players (cf_mark_shapley_sampled) -> (phi, info), tensors on the
+        model's device, no autograd graph: which mark matters at which region?
+
+          phi                   [B, P, n_out]: the mean, over the sampled orders of adding the players, of player p's marginal
+                                contribution to each logit; exactly 0 for a player whose elements are the same present and absent.
+                                With players="cells", phi.view(B, i_max + 1, n_feats, n_out)[:, rho, f] is mark f in region rho
+          info["stderr"]        [B, P, n_out]: the standard error of that mean over the orders (0 with one order).  phi is an
+                                ESTIMATE: this is the only statement about its sampling error, nothing bounds it
+          info["logits"]        [B, n_out]: the prediction (every player present; model(...) under no_grad, bit-equal)
+          info["absent"]        [B, n_out]: every player absent (erased, scaled, or the donor's marks)
+          info["delta"]         [B, n_out]: phi.sum(1) - (logits - absent), the efficiency gap (rounding only: every order telescopes)
+          info["names"]         the players' names
+          info["permutations"]  uint8 [n_perm, P]: the orders used
+          info["rows"]          [B, 2 + n_perm (P - 1), n_out], with return_rows: nobody, everybody, then per order q its first
+                                k = 1 .. P - 1 players at column 2 + q (P - 1) + (k - 1)
+
+        The orders are attribution.shapley_permutations(P, n_perm, seed), or `permutations` (an integer array [n_perm, P], each row a
+        permutation; stderr then still assumes independent orders).  players, scale and donor as in mark_coalitions_wide.  The packed
+        forms of the first argument and the effect on a pending backward() are those of mark_coalitions."""
+        from .attribution import shapley_permutations
+        who = "mark_shapley_sampled"
+        bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        opts, _alive, names = self._mark_wide_opts(who, players, scale, donor, bs.B)
+        P = opts.n_players
+        if permutations is None:
+            perms = shapley_permutations(P, n_perm, seed)
+        else:
+            given = np.asarray(permutations.cpu() if hasattr(permutations, "cpu") else permutations)
+            if given.ndim != 2 or given.shape[0] < 1 or given.shape[1] != P or given.dtype.kind not in "iu" or given.min() < 0 or given.max() >= P:
+                raise ValueError("%s: permutations must be an integer array [n_perm >= 1, P = %d] with entries in [0, P)" % (who, P))
+            perms = np.ascontiguousarray(given, dtype=np.uint8)
+        n = len(perms)
+        R = 2 + n * (P - 1)
+        rows = torch.empty(bs.B, R, self.n_out, device=self._device)      # (all three written in full by the library)
+        phi = torch.empty(bs.B, P, self.n_out, device=self._device)
+        se = torch.empty(bs.B, P, self.n_out, device=self._device)
+        st = book()
+        _lib.check(_lib.lib().cf_mark_shapley_sampled(self._handle, C.byref(bs), C.byref(opts), perms.ctypes.data, n, phi.data_ptr(), se.data_ptr(),
+                                                      rows.data_ptr(), st), "cf_mark_shapley_sampled")
+        info = {"logits": rows[:, 1].clone(), "absent": rows[:, 0].clone(), "stderr": se, "names": names, "permutations": perms}
+        info["delta"] = phi.sum(1) - (info["logits"] - info["absent"])
+        if return_rows:
+            info["rows"] = rows
+        return phi, info
+
+    def mark_shapley_sampled_dataset(self, dataset, donor_dataset=None, genes=None, players="cells", n_perm=64, seed=0, scale=0.0, bsz=None,
+                                     store=None, donor_store=None):
+        """mark_shapley_sampled over the genes of a ChromoformerDataset, against a donor cell type's dataset if one is given
+        (chromoformer_amd.attribution.mark_shapley_sampled, a generator of per-gene dicts)."""
+        from .attribution import mark_shapley_sampled
+        return mark_shapley_sampled(self, dataset, donor_dataset, genes=genes, players=players, n_perm=n_perm, seed=seed, scale=scale, bsz=bsz,
+                                    store=store, donor_store=donor_store)
 
     def raw_signal_gradients(self, dataset, genes=None, target=None, times_input=False, bsz=None):
         """Raw-signal saliency of the genes of a ChromoformerDataset: the gradient (or gradient x input) of logit column `target` with

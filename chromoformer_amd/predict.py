@@ -245,6 +245,40 @@ def write_mark_donor_values(model, store, donor_store, bsz, gene_ids, shapley_ou
         eps.flush()
 
 
+def write_mark_sampled_values(model, store, donor_store, bsz, gene_ids, path, regression=False, players="cells", n_perm=64, seed=0, scale=0.0):
+    """Permutation-sampled Shapley values of up to 128 histone-mark players (model.mark_shapley_sampled) of every gene of a
+    device-resident store, in store order, in LOGIT space of the prediction's column, into `path`, an .npz with gene_ids [n], players
+    [P] (names), permutations uint8 [n_perm, P] (the orders, the same for every gene), phi [n, P], stderr [n, P] (the standard error of
+    phi over the orders: the sampling error is reported, not bounded), logits [n] and absent [n] (every player absent; phi sums to
+    their difference).  donor_store None: an absent player's raw signal is scaled by `scale`; else a store of the same genes in the
+    same order in the donor cell type, whose signal it takes.  Per batch: one gather per store and one model.mark_shapley_sampled."""
+    from .attribution import mark_players_wide, shapley_permutations
+    n = len(store)
+    if donor_store is not None and len(donor_store) != n:
+        raise ValueError("write_mark_sampled_values: the donor store holds %d genes, the store %d" % (len(donor_store), n))
+    names = mark_players_wide(players, model.n_feats, model.i_max)[2]
+    P, t = len(names), 0 if regression else 1
+    perms = shapley_permutations(P, n_perm, seed)
+    phi, se, logits, absent = torch.empty(n, P), torch.empty(n, P), torch.empty(n), torch.empty(n)
+    keys = ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq")
+    for lo in range(0, n, bsz):
+        B = min(bsz, n - lo)
+        idx = list(range(lo, lo + B))
+        d = store.batch(idx)
+        feats = None
+        if donor_store is not None:
+            dd = donor_store.batch(idx)
+            feats = ({b: x.contiguous() for b, x in dd["promoter_feats"].items()}, {b: x.contiguous() for b, x in dd["pcre_feats"].items()})
+        p, info = model.mark_shapley_sampled(*(d[k] for k in keys), players=players, permutations=perms, scale=scale, donor=feats)
+        phi[lo:lo + B] = p[..., t].cpu()
+        se[lo:lo + B] = info["stderr"][..., t].cpu()
+        logits[lo:lo + B] = info["logits"][:, t].cpu()
+        absent[lo:lo + B] = info["absent"][:, t].cpu()
+    with open(path, "wb") as f:      # (a file object: np.savez would append .npz to a name without it)
+        np.savez(f, gene_ids=np.array(list(gene_ids)), players=np.array(names), permutations=perms, phi=phi.numpy(), stderr=se.numpy(),
+                 logits=logits.numpy(), absent=absent.numpy())
+
+
 def write_integrated_gradients(model, store, bsz, ig_dir, n_steps=50, method="gausslegendre", target=None):
     """Integrated gradients of every gene of a device-resident store, in store order, into `ig_dir`: promoter_feats_{b}.npy
     [n, L, F], pcre_feats_{b}.npy [n, i_max, L, F], interaction_freq.npy [n, T, T] and delta.npy [n] (float32 .npy memory maps;
@@ -410,7 +444,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
             raw_saliency_target=None, raw_saliency_times_input=False, raw_ig_dir=None, scan_out=None, scan_scale=0.0, scan_width=1,
             scan_regions="promoter", pcre_shapley_out=None, pcre_epistasis_out=None, mark_shapley_out=None, mark_epistasis_out=None,
             mark_players="marks", mark_scale=0.0, donor_npy_dir=None, donor_meta=None, donor_store_path=None, mark_donor_shapley_out=None,
-            mark_donor_epistasis_out=None):
+            mark_donor_epistasis_out=None, mark_sampled_shapley_out=None, mark_donor_sampled_shapley_out=None, mark_sampled_players="cells",
+            mark_perms=64, mark_seed=0):
     """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file.  attention_dir / embeddings_out: also
     write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps); pcre_ablation_out:
     the predictions with each pCRE deleted (write_pcre_ablation); ig_dir: integrated gradients of every gene
@@ -424,7 +459,9 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     (write_mark_values; mark_players and mark_scale apply); mark_donor_shapley_out / mark_donor_epistasis_out: the same against a donor
     cell type (write_mark_donor_values; mark_players applies), whose signals are read from donor_npy_dir with the metadata donor_meta
     (default: meta_path) or the packed store donor_store_path -- both cell types must hold the genes' regions at the same coordinates
-    (attribution.same_regions)."""
+    (attribution.same_regions); mark_sampled_shapley_out / mark_donor_sampled_shapley_out: permutation-sampled Shapley values of up
+    to 128 mark players, by default one per (mark, region) pair, under the scale rule (mark_scale applies) / against the donor
+    (write_mark_sampled_values; mark_sampled_players, mark_perms and mark_seed apply)."""
     seed_everything(seed)
     meta = pd.read_csv(meta_path)
     genes = meta.gene_id.tolist()
@@ -433,11 +470,11 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         raw_ds = ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=regression)
         require_raw_signals(raw_ds)      # (before anything is computed)
     from . import pack
-    donor_out = mark_donor_shapley_out or mark_donor_epistasis_out
+    donor_out = mark_donor_shapley_out or mark_donor_epistasis_out or mark_donor_sampled_shapley_out
     if donor_out:      # (before anything is computed)
         from .attribution import same_regions
         if not donor_npy_dir:
-            raise ValueError("predict: mark_donor_shapley_out / mark_donor_epistasis_out need donor_npy_dir")
+            raise ValueError("predict: mark_donor_shapley_out / mark_donor_epistasis_out / mark_donor_sampled_shapley_out need donor_npy_dir")
         donor_ds = ChromoformerDataset(donor_meta or meta_path, donor_npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False)
         same_regions(ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False), donor_ds)
     packed = pack.find(npy_dir, store_path, list(binsizes), i_max, w_prom, w_max, 7, genes, meta=meta)
@@ -469,8 +506,15 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         donor_packed = pack.find(donor_npy_dir, donor_store_path, list(binsizes), i_max, w_prom, w_max, 7, genes, meta=donor_ds.meta)
         donor_store = (donor_packed.store(genes, device=dev, regression=False) if donor_packed is not None
                        else GeneStore(donor_ds, progress=progress, device=dev, resident=True))
-        write_mark_donor_values(model, store, donor_store, bsz, genes, mark_donor_shapley_out, mark_donor_epistasis_out, regression, mark_players)
+        if mark_donor_shapley_out or mark_donor_epistasis_out:
+            write_mark_donor_values(model, store, donor_store, bsz, genes, mark_donor_shapley_out, mark_donor_epistasis_out, regression, mark_players)
+        if mark_donor_sampled_shapley_out:
+            write_mark_sampled_values(model, store, donor_store, bsz, genes, mark_donor_sampled_shapley_out, regression, mark_sampled_players,
+                                      mark_perms, mark_seed)
         del donor_store
+    if mark_sampled_shapley_out:
+        write_mark_sampled_values(model, store, None, bsz, genes, mark_sampled_shapley_out, regression, mark_sampled_players, mark_perms, mark_seed,
+                                  mark_scale)
     if ig_dir:
         write_integrated_gradients(model, store, bsz, ig_dir, ig_steps, ig_method, ig_target)
     if scan_out:
@@ -550,6 +594,19 @@ def build_parser():
     ap.add_argument("--mark-donor-epistasis-out", default=None, help="also write the pair epistasis of the histone marks against the donor cell "
                     "type to this .npy file: [n_genes, P, P] in logit space, symmetric, the leave-one-out effects on the diagonal "
                     "(model.mark_donor_epistasis).  --mark-players applies")
+    from .attribution import MARK_WIDE_PLAYER_SPECS
+    ap.add_argument("--mark-sampled-shapley-out", default=None, help="also write permutation-SAMPLED Shapley values of up to 128 histone-mark "
+                    "players to this .npz file, in metadata order and in LOGIT space of the prediction's column: gene_ids, players (names), "
+                    "permutations [n_perm, P], phi [n_genes, P], stderr [n_genes, P] (the standard error over the sampled orders: the sampling "
+                    "error is reported, not bounded), logits and absent (every player absent; phi sums to their difference) "
+                    "(model.mark_shapley_sampled).  --mark-scale applies")
+    ap.add_argument("--mark-donor-sampled-shapley-out", default=None, help="the same against the donor cell type of --donor-npy-dir: an absent "
+                    "player takes the donor's signal")
+    ap.add_argument("--mark-sampled-players", default=None, choices=MARK_WIDE_PLAYER_SPECS, help="the players of --mark-sampled-shapley-out / "
+                    "--mark-donor-sampled-shapley-out: one per (mark, region) pair (cells, the default: 63 players, phi reshapes to "
+                    "[n_genes, i_max + 1, 7]), or the specs of --mark-players")
+    ap.add_argument("--mark-perms", type=int, default=None, help="sampled orders of adding the players (default 64); each costs P - 1 forwards per gene")
+    ap.add_argument("--mark-seed", type=int, default=None, help="seed of the sampled orders (default 0)")
     return ap
 
 
@@ -572,14 +629,23 @@ def main(argv=None):
         ap.error("--scan-scale must be a finite factor >= 0")
     if args.scan_width is not None and args.scan_width < 1:
         ap.error("--scan-width must be at least 1")
-    donor_out = args.mark_donor_shapley_out or args.mark_donor_epistasis_out
+    donor_exact = args.mark_donor_shapley_out or args.mark_donor_epistasis_out
+    donor_out = donor_exact or args.mark_donor_sampled_shapley_out
+    sampled_out = args.mark_sampled_shapley_out or args.mark_donor_sampled_shapley_out
     if donor_out and not args.donor_npy_dir:
-        ap.error("--mark-donor-shapley-out / --mark-donor-epistasis-out need --donor-npy-dir")
+        ap.error("--mark-donor-shapley-out / --mark-donor-epistasis-out / --mark-donor-sampled-shapley-out need --donor-npy-dir")
     if not donor_out and (args.donor_npy_dir or args.donor_meta or args.donor_store):
-        ap.error("--donor-npy-dir / --donor-meta / --donor-store need --mark-donor-shapley-out or --mark-donor-epistasis-out")
-    if not args.mark_shapley_out and not args.mark_epistasis_out and (args.mark_scale is not None or (args.mark_players is not None and not donor_out)):
+        ap.error("--donor-npy-dir / --donor-meta / --donor-store need --mark-donor-shapley-out, --mark-donor-epistasis-out or "
+                 "--mark-donor-sampled-shapley-out")
+    if not sampled_out and (args.mark_sampled_players is not None or args.mark_perms is not None or args.mark_seed is not None):
+        ap.error("--mark-sampled-players / --mark-perms / --mark-seed need --mark-sampled-shapley-out or --mark-donor-sampled-shapley-out")
+    if args.mark_perms is not None and args.mark_perms < 1:
+        ap.error("--mark-perms must be at least 1")
+    if not args.mark_shapley_out and not args.mark_epistasis_out and ((args.mark_scale is not None and not args.mark_sampled_shapley_out)
+                                                                      or (args.mark_players is not None and not donor_exact)):
         ap.error("--mark-players / --mark-scale need --mark-shapley-out or --mark-epistasis-out"
-                 " (--mark-players also applies to --mark-donor-shapley-out / --mark-donor-epistasis-out)")
+                 " (--mark-players also applies to --mark-donor-shapley-out / --mark-donor-epistasis-out, --mark-scale to"
+                 " --mark-sampled-shapley-out)")
     if args.mark_scale is not None and not (args.mark_scale >= 0 and np.isfinite(args.mark_scale)):
         ap.error("--mark-scale must be a finite factor >= 0")
     meta, pred = predict(args.meta, args.npy_dir, args.weights, args.regression, progress=True, store_path=args.store,
@@ -593,7 +659,10 @@ def main(argv=None):
                          mark_shapley_out=args.mark_shapley_out, mark_epistasis_out=args.mark_epistasis_out,
                          mark_players=args.mark_players or "marks", mark_scale=0.0 if args.mark_scale is None else args.mark_scale,
                          donor_npy_dir=args.donor_npy_dir, donor_meta=args.donor_meta, donor_store_path=args.donor_store,
-                         mark_donor_shapley_out=args.mark_donor_shapley_out, mark_donor_epistasis_out=args.mark_donor_epistasis_out)
+                         mark_donor_shapley_out=args.mark_donor_shapley_out, mark_donor_epistasis_out=args.mark_donor_epistasis_out,
+                         mark_sampled_shapley_out=args.mark_sampled_shapley_out, mark_donor_sampled_shapley_out=args.mark_donor_sampled_shapley_out,
+                         mark_sampled_players=args.mark_sampled_players or "cells", mark_perms=64 if args.mark_perms is None else args.mark_perms,
+                         mark_seed=0 if args.mark_seed is None else args.mark_seed)
     print("Predicting expressions for %d genes." % len(meta))
     meta["prediction"] = pred
     meta.to_csv(args.output, index=False)

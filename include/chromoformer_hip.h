@@ -457,6 +457,54 @@ int cf_mark_donor_coalitions(cf_handle* h, const cf_batch* batch, const cf_mark_
 int cf_mark_donor_shapley(cf_handle* h, const cf_batch* batch, const cf_mark_donor_opts* opts, float* phi, float* logits_all, void* stream);
 /* cf_mark_epistasis with the donor rule: eps [B, P, P, n_out], rows, logits_pairs and fwd as there.  Refusals as above (null eps). */
 int cf_mark_donor_epistasis(cf_handle* h, const cf_batch* batch, const cf_mark_donor_opts* opts, float* eps, float* logits_pairs, void* stream);
+/* The same game over up to 128 players (interpretation): which mark matters at which region?  "Mark f in region rho" is
+ * n_feats * (i_max + 1) players -- 63 on the default model, 119 at i_max = 16 -- more than one word holds and far more than 2^P rows
+ * can enumerate.  Players, gone(rho), the scale rule and the donor rule are exactly those above; a coalition is kw = ceil(P / 32)
+ * consecutive 32-bit words, bit p % 32 of word p / 32 set = player p PRESENT.  One struct serves both rules. */
+typedef struct cf_mark_wide_opts {
+    int n_players;                                   /* 1..128 */
+    const unsigned* player_marks;                    /* host [n_players], read before the call returns */
+    const unsigned* player_regions;                  /* host [n_players] */
+    float scale;                                     /* the scale rule: used when every donor pointer is NULL */
+    const float* donor_promoter_feats[CF_MAX_RES];   /* all NULL: scale rule; all non-NULL below n_res: donor rule; mixed: refused */
+    const float* donor_pcre_feats[CF_MAX_RES];
+} cf_mark_wide_opts;                                 /* 80 bytes */
+/* cf_mark_coalitions_wide: keep is a HOST array of n_coal * kw words, coalition k at [k kw, (k + 1) kw) (read before the call returns);
+ * logits [B, n_coal, n_out], gene-major.  The full word is cf_forward(save = 0), bit for bit; with P <= 16 the rows carry the bits of
+ * cf_mark_coalitions / cf_mark_donor_coalitions on the same words.  Rows run in chunks of at most max_batch in the chunk buffers of
+ * cf_mark_coalitions; per chunk one k_mark_wide_expand (the donor rule: k_mark_wide_donor_expand), then the launches of
+ * cf_forward(save = 0) on the chunk:
+ *   cf_launch_counts fwd = ceil(B * n_coal / max_batch) * (1 + n_fwd),  n_fwd = what cf_forward(save = 0) issues.
+ * The words and the 2 P player words travel in the device table the handle owns (grown on demand); no other device buffer is added.
+ * Deterministic (no atomics); k_attc2's regions per workgroup are chosen as for the caller's B genes, so the result does not depend on
+ * max_batch.  Overwrites the activations a cf_forward(save >= 1) kept.  Parameters, gradients and moments are untouched.
+ * Refused by name, before anything is launched: what cf_mark_coalitions refuses, with n_players in 1..128; a keep bit >= n_players in
+ * any word (the coalition's index is named); donor pointers of which some but not all below the model's resolution count are NULL;
+ * under the scale rule a negative or non-finite scale. */
+int cf_mark_coalitions_wide(cf_handle* h, const cf_batch* batch, const cf_mark_wide_opts* opts, const uint32_t* keep, int n_coal, float* logits,
+                            void* stream);
+/* Permutation-SAMPLED Shapley values of the P players.  perms: HOST bytes [n_perm, P], each row a permutation of 0..P-1: an order of
+ * adding the players (read before the call returns).  Per gene R = 2 + n_perm * (P - 1) rows run through the routine above:
+ *   column 0                          nobody present
+ *   column 1                          everybody present: cf_forward(save = 0), bit for bit
+ *   column 2 + q * (P - 1) + (k - 1)  the first k players of permutation q, k = 1 .. P - 1
+ * (the two end rows are shared by all permutations), then one k_perm_shapley per (gene, player).  With r the position of player p
+ * in permutation q and col(q, 0) = 0, col(q, P) = 1:
+ *   d_q = v[col(q, r + 1)] - v[col(q, r)]                          one fp32 subtraction
+ *   phi[b, p] = (sum_q d_q) / n_perm
+ *   se[b, p]  = sqrt(sum_q (d_q - phi)^2 / (n_perm (n_perm - 1)))  0 for n_perm = 1
+ * every operation rounded to fp32, a fixed summation order (a strided partial sum per thread, then a fixed tree), no atomics: the
+ * result does not depend on max_batch.  phi [B, P, n_out]; se [B, P, n_out] or NULL; logits_rows [B, R, n_out] or NULL (the
+ * handle-owned buffer of cf_pcre_shapley).  The inverse permutations travel as bytes in the word table.
+ * Efficiency: sum_p phi[b, p] = v[b, 1] - v[b, 0] up to rounding (it telescopes in every permutation).  A player whose elements carry
+ * the same bits present and absent (a dummy slot; identical donor bits) has phi and se exactly 0.  With all P! permutations phi is the
+ * exact Shapley value.  Otherwise phi is an ESTIMATE: its sampling error is what se reports (the standard error of the mean, assuming
+ * independent uniform permutations) and is not bounded by the library.
+ * fwd = that of cf_mark_coalitions_wide with n_coal = R, plus 1.
+ * Refused by name, before anything is launched: what cf_mark_coalitions_wide refuses (null phi), null perms, n_perm < 1, a row of
+ * perms that is not a permutation (its index q is named). */
+int cf_mark_shapley_sampled(cf_handle* h, const cf_batch* batch, const cf_mark_wide_opts* opts, const uint8_t* perms, int n_perm, float* phi,
+                            float* se, float* logits_rows, void* stream);
 /* torch.optim.AdamW.step (train.py:157, 196): decoupled weight decay, bias correction
  * from `step` (1-based), over [0, n_active). */
 int cf_adamw_step(cf_handle* h, float lr, float beta1, float beta2, float eps, float weight_decay,
