@@ -104,6 +104,12 @@ class cf_mark_wide_opts(C.Structure):
                 ("donor_promoter_feats", C.c_void_p * MAX_RES), ("donor_pcre_feats", C.c_void_p * MAX_RES)]
 
 
+class cf_mark_window_opts(C.Structure):
+    _fields_ = [("n_players", C.c_int), ("player_marks", C.c_void_p), ("player_regions", C.c_void_p), ("player_lo", C.c_void_p),
+                ("player_hi", C.c_void_p), ("flip", C.c_void_p), ("scale", C.c_float),
+                ("donor_promoter_feats", C.c_void_p * MAX_RES), ("donor_pcre_feats", C.c_void_p * MAX_RES)]
+
+
 class cf_store(C.Structure):
     _fields_ = [
         ("n_genes", C.c_longlong),
@@ -170,7 +176,12 @@ SYMBOLS = {
     "cf_mark_coalitions_wide": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_wide_opts), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "cf_mark_shapley_sampled": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_wide_opts), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
-    "cf_adamw_step": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_longlong, C.c_void_p]),
+    "cf_mark_window_coalitions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_window_opts), C.c_void_p, C.c_int, C.c_void_p,
+                                            C.c_void_p]),
+    "cf_mark_window_shapley": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_window_opts), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cf_mark_window_shapley_sampled": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_window_opts), C.c_void_p, C.c_int, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cf_adamw_step":(C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_longlong, C.c_void_p]),
     "cf_debug_copy": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p]),
     "cf_debug_names": (C.c_char_p, [C.c_void_p]),
     "cf_reduce_adamw_part": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_longlong, C.c_int,

@@ -195,6 +195,77 @@ def shapley_permutations(P, n_perm, seed=0):
     return np.stack([rng.permutation(P) for _ in range(n_perm)]).astype(np.uint8)
 
 
+WINDOW_PLAYER_SPECS = ("promoter", "promoter_cells", "regions")
+
+
+def window_players(spec, n_feats, i_max, W, width=1):
+    """The players of the window game (ChromoformerBase.mark_window_coalitions / mark_window_shapley / mark_window_shapley_sampled) ->
+    (marks, regions, lo, hi, names): uint32 [P] mark and region words as mark_players returns them, int32 [P] windows [lo, hi) in
+    bins of the coarsest resolution (W of them per region: the windows of the perturbation scan), and a name per player.  With
+    n_win = ceil(W / width) windows [g width, min((g + 1) width, W)):
+
+      "promoter"         P = n_win: all marks over window g of the promoter ("promoter[4:6]")
+      "promoter_cells"   P = n_feats n_win: player g * n_feats + f is mark f over window g of the promoter ("mark3@promoter[4:6]"); a
+                         [B, P, n_out] result reshapes to [B, n_win, n_feats, n_out]
+      "regions"          P = (i_max + 1) n_win: player rho * n_win + g is all marks over window g of region rho ("promoter[0:2]", ...,
+                         "pcre1[0:2]", ...)
+      a list of (marks, regions, (lo, hi)) triples: index iterables as in mark_players and a window; players may overlap
+
+    More than 128 players (the count is named: choose a larger width), an empty player, an index out of range or a window outside
+    0 <= lo < hi <= W raise ValueError naming window_players."""
+    who = "window_players"
+    F, S, W = int(n_feats), int(i_max), int(W)
+    if W < 1:
+        raise ValueError("%s: W = %d: the coarsest resolution has at least one bin" % (who, W))
+    every_mark = list(range(F))
+
+    def region_name(rho):
+        return "promoter" if rho == 0 else "pcre%d" % (rho - 1)
+
+    if isinstance(spec, str):
+        if spec not in WINDOW_PLAYER_SPECS:
+            raise ValueError("%s: players %r; choose from %s or give a list of (marks, regions, (lo, hi)) triples" % (who, spec, WINDOW_PLAYER_SPECS))
+        width = int(width)
+        if width < 1:
+            raise ValueError("%s: width = %d: at least 1 coarsest bin" % (who, width))
+        wins = [(g, min(g + width, W)) for g in range(0, W, width)]
+        if spec == "promoter":
+            triples = [(every_mark, [0], w) for w in wins]
+            names = ["promoter[%d:%d]" % w for w in wins]
+        elif spec == "promoter_cells":
+            triples = [([f], [0], w) for w in wins for f in every_mark]
+            names = ["mark%d@promoter[%d:%d]" % ((f,) + w) for w in wins for f in every_mark]
+        else:
+            triples = [(every_mark, [rho], w) for rho in range(S + 1) for w in wins]
+            names = ["%s[%d:%d]" % ((region_name(rho),) + w) for rho in range(S + 1) for w in wins]
+        if len(triples) > MARK_WIDE_MAX_PLAYERS:
+            raise ValueError("%s: %r at width = %d gives %d players; the game takes 1..%d: choose a larger width"
+                             % (who, spec, width, len(triples), MARK_WIDE_MAX_PLAYERS))
+    else:
+        try:
+            triples = [(sorted({int(f) for f in ms}), sorted({int(r) for r in rs}), (int(w[0]), int(w[1]))) for ms, rs, w in spec]
+        except (TypeError, ValueError, IndexError):
+            raise ValueError("%s: players must be one of %s or a list of (marks, regions, (lo, hi)) triples, got %r"
+                             % (who, WINDOW_PLAYER_SPECS, spec)) from None
+        names = ["marks(%s)@regions(%s)[%d:%d]" % (",".join(map(str, ms)), ",".join(map(str, rs)), w[0], w[1]) for ms, rs, w in triples]
+        if not 1 <= len(triples) <= MARK_WIDE_MAX_PLAYERS:
+            raise ValueError("%s: %d players; the game takes 1..%d: choose a larger width" % (who, len(triples), MARK_WIDE_MAX_PLAYERS))
+    for p, (ms, rs, (lo, hi)) in enumerate(triples):
+        if not ms or not rs:
+            raise ValueError("%s: player %d is empty: at least one mark and one region" % (who, p))
+        if ms[0] < 0 or ms[-1] >= min(F, 32):
+            raise ValueError("%s: player %d names mark(s) %s outside [0, n_feats = %d)" % (who, p, ms, F))
+        if rs[0] < 0 or rs[-1] > S:
+            raise ValueError("%s: player %d names region(s) %s outside [0, i_max = %d]" % (who, p, rs, S))
+        if lo < 0 or hi > W or lo >= hi:
+            raise ValueError("%s: player %d has the window [%d, %d): 0 <= lo < hi <= W = %d is required" % (who, p, lo, hi, W))
+    marks = np.array([sum(1 << f for f in ms) for ms, _, _ in triples], dtype=np.uint32)
+    regions = np.array([sum(1 << r for r in rs) for _, rs, _ in triples], dtype=np.uint32)
+    lo = np.array([w[0] for _, _, w in triples], dtype=np.int32)
+    hi = np.array([w[1] for _, _, w in triples], dtype=np.int32)
+    return marks, regions, lo, hi, names
+
+
 def _geometry_check(who, model, dataset, binsizes):
     """The model is on the device and the dataset has its geometry -> n_bins."""
     ds = dataset
@@ -746,3 +817,103 @@ def mark_shapley_sampled(model, dataset, donor_dataset=None, genes=None, players
         for i, g in enumerate(ids):
             yield dict(gene_id=g, phi=phi[i].copy(), stderr=se[i].copy(), logits=logits[i].copy(), absent=absent[i].copy(), players=list(names),
                        permutations=perms.copy())
+
+
+def window_player_coordinates(marks_regions_windows, regions, n_real, binsize):
+    """Genomic coordinates of window players for one gene.  marks_regions_windows: window_players' (marks, regions, lo, hi, ...);
+    regions: {region index: (chrom, start, end)} of the regions the gene has; n_real: {region index: real bins at the coarsest
+    resolution}; binsize: the coarsest bin size -> (windows, null): per player the list of (region index, chrom, start, end) of its REAL
+    windows -- start + lo * binsize, the end clipped to the region, the windows of the perturbation scan -- and a bool [P], True where
+    the player has none (a null player for this gene: its phi is exactly 0)."""
+    _, pr, lo, hi = marks_regions_windows[:4]
+    windows = []
+    for p in range(len(pr)):
+        real = []
+        for rho, (chrom, start, end) in sorted(regions.items()):
+            if (int(pr[p]) >> rho) & 1 and int(lo[p]) < n_real[rho]:
+                real.append((rho, chrom, int(start) + int(lo[p]) * int(binsize), min(int(start) + int(hi[p]) * int(binsize), int(end))))
+        windows.append(real)
+    return windows, np.array([not w for w in windows], dtype=bool)
+
+
+def mark_window_shapley(model, dataset, donor_dataset=None, genes=None, players="promoter", width=1, n_perm=64, seed=0, scale=0.0, bsz=None,
+                        store=None, donor_store=None):
+    """Shapley values of WINDOW players for the genes of a ChromoformerDataset: where inside a region does the signal lie?  With at most
+    16 players one model.mark_window_shapley per batch (exact), else one model.mark_window_shapley_sampled (n_perm orders from `seed`).
+    Without `donor_dataset` an absent player's raw signal inside its window is scaled by `scale` (0 erases it); with one -- the same
+    genes over the same regions in another cell type (same_regions runs first) -- it takes the donor's signal.  A generator over
+    `genes` (ids; default: the dataset's) in chunks of at most min(bsz, model.max_batch) genes; per gene it yields a dict of host arrays:
+
+        gene_id        the id
+        estimator      "exact" or "sampled"
+        phi            float32 [P, n_out]: the values, in logit space; phi.sum(0) = logits - absent up to rounding
+        stderr         float32 [P, n_out]: the standard error of phi over the sampled orders; zeros from the exact call
+        logits         float32 [n_out]: the prediction (every player present)
+        absent         float32 [n_out]: every player absent
+        players        the players' names (window_players)
+        windows        per player the list of (region index, chrom, start, end) of its real windows in this gene, genomic coordinates as
+                       perturbation_scan reports them ('-' strand promoters are stored mirrored: window 0 is still the genomic start)
+        null           bool [P]: the player has no real window in this gene (a dummy slot, a short pCRE, a narrowed promoter): phi = 0
+        permutations   uint8 [n_perm, P], sampled only: the orders, the same for every gene
+
+    Strand and coordinates come from the dataset's metadata.  The binned features come from `store` / `donor_store` as in
+    mark_donor_shapley.  Parameters, gradients and optimiser state are left as they are; the pass overwrites the activations a
+    grad-enabled model(...) keeps for its backward."""
+    from .data import promoter_col0
+    ds, dn = dataset, donor_dataset
+    who = "mark_window_shapley"
+    binsizes = [int(b) for b in ds.binsizes]
+    n_bins = _geometry_check(who, model, ds, binsizes)
+    genes, chunk = _genes_check(who, model, ds, genes, bsz)
+    if dn is not None:
+        same_regions(ds, dn, genes)
+    spec = players if isinstance(players, str) else list(players)
+    rc = int(np.argmin(n_bins))
+    W, bc = n_bins[rc], binsizes[rc]
+    game = window_players(spec, ds.n_feats, ds.i_max, W, width)      # (refusals before anything is loaded)
+    names = game[4]
+    P = len(names)
+    exact = P <= 16
+    perms = None if exact else shapley_permutations(P, n_perm, seed)
+    col0 = promoter_col0(ds)
+    store = _resident_store(who, ds, genes, binsizes, model._device, store)
+    if dn is not None:
+        donor_store = _resident_store(who, dn, genes, binsizes, model._device, donor_store)
+    keys = ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq")
+    for lo in range(0, len(genes), chunk):
+        ids = genes[lo:lo + chunk]
+        B = len(ids)
+        idx = list(range(lo, lo + B))
+        d = store.batch(idx)
+        donor = None
+        if dn is not None:
+            dd = donor_store.batch(idx)
+            donor = ({b: t.contiguous() for b, t in dd["promoter_feats"].items()}, {b: t.contiguous() for b, t in dd["pcre_feats"].items()})
+        flip = [ds.genes[g]["tss"][2] != "+" for g in ids]
+        args = tuple(d[k] for k in keys)
+        if exact:
+            phi, info = model.mark_window_shapley(*args, players=spec, width=width, scale=scale, donor=donor, flip=flip)
+            absent = info["erased" if donor is None else "donor"].cpu().numpy()
+            se = np.zeros(tuple(phi.shape), dtype=np.float32)
+        else:
+            phi, info = model.mark_window_shapley_sampled(*args, players=spec, width=width, permutations=perms, scale=scale, donor=donor, flip=flip)
+            absent, se = info["absent"].cpu().numpy(), info["stderr"].cpu().numpy()
+        phi, logits = phi.cpu().numpy(), info["logits"].cpu().numpy()
+        pm = d["promoter_pad_masks"][bc].reshape(B, -1, W)
+        pm = pm[:, pm.shape[1] // 2].cpu().numpy() == 0                       # the centre row of a full [L, L] mask, or the compact row
+        cm = d["pcre_pad_masks"][bc].reshape(B, ds.i_max, -1, W)
+        cm = cm[:, :, cm.shape[2] // 2].cpu().numpy() == 0
+        for i, g in enumerate(ids):
+            chrom, tss, _ = ds.genes[g]["tss"]
+            regions = {0: (chrom, tss - 20000 + col0, tss - 20000 + col0 + min(ds.w_prom, 40000 - col0))}
+            regions.update({1 + j: tuple(p) for j, p in enumerate(ds.genes[g]["pcres"][:ds.i_max])})
+            n_real = {}
+            for rho in regions:
+                real = np.flatnonzero(pm[i] if rho == 0 else cm[i, rho - 1])
+                n_real[rho] = int(real[-1] - real[0] + 1) if real.size else 0
+            windows, null = window_player_coordinates(game, regions, n_real, bc)
+            out = dict(gene_id=g, estimator="exact" if exact else "sampled", phi=phi[i].copy(), stderr=se[i].copy(), logits=logits[i].copy(),
+                       absent=absent[i].copy(), players=list(names), windows=windows, null=null)
+            if not exact:
+                out["permutations"] = perms.copy()
+            yield out

@@ -11,6 +11,7 @@
 #include "cf_scan.h"
 #include "cf_marks.h"
 #include "cf_marks_wide.h"
+#include "cf_mark_windows.h"
 #include "cf_x0_gather.h"
 
 #include <algorithm>

@@ -1,5 +1,5 @@
 // cf_api_attrib.h -- host side of the attribution entry points (input gradients, attention maps, pCRE deletion, pCRE coalitions, integrated
-// gradients, perturbation scan, histone-mark coalitions, their donor form, the wide game and its sampled Shapley values).  Part of cf_api.hip's single translation unit: included there behind cf_api_bwd.h, not on its own.
+// gradients, perturbation scan, histone-mark coalitions, their donor form, the wide game and its sampled Shapley values, the window game).  Part of cf_api.hip's single translation unit: included there behind cf_api_bwd.h, not on its own.
 #pragma once
 
 // k_input_grad's dynamic LDS size; the first call sets the kernel's attribute.  0: that failed (`who`: the entry point, for the error text).
@@ -772,6 +772,10 @@ struct MarkGame {
     float scale;                          // the scale rule (donor == nullptr)
     const cf_mark_donor_opts* donor;      // the donor rule
     int kw = 0;                           // words per coalition of the wide game (cf_marks_wide.h); 0: the one-word kernels
+    const int* lo = nullptr;              // host [P]: the window game (cf_mark_windows.h): player p's coarse bins [lo, hi); null: whole regions
+    const int* hi = nullptr;
+    const uint8_t* flip = nullptr;        // device [B] or null: the promoter is stored mirrored (the window game)
+    int W = 0, rc = 0;                    // the coarsest resolution's bin count and index (the window game)
 };
 
 // mark_check: what the entry points check alike, in front of anything launched -- the handle, the batch, riders, the options: the
@@ -826,7 +830,8 @@ static int mark_upload(cf_handle* h, const MarkGame& g, const uint32_t* keep, in
 
 // The B * n_coal rows of a mark-coalition call (gene-major; row (b, k) is word k of the table mark_upload wrote), every row through
 // the whole forward.  Per chunk of at most max_batch rows: k_mark_expand (the donor rule: k_mark_donor_expand; the wide game, whose rows
-// are g.kw words each: k_mark_wide_expand / k_mark_wide_donor_expand) into the chunk workspace,
+// are g.kw words each: k_mark_wide_expand / k_mark_wide_donor_expand; the window game, g.lo set: k_mark_window_expand /
+// k_mark_window_donor_expand) into the chunk workspace,
 // then the launches of cf_forward(save = 0) on the chunk, writing its slice of `logits`.  k_attc2 takes as many regions per workgroup
 // as for the caller's B genes (ag_genes), as scan_region_rows: the result does not depend on max_batch.
 static int mark_rows(cf_handle* h, const cf_batch* bt, const MarkGame& g, int n_coal, float* logits, hipStream_t st) {
@@ -853,12 +858,32 @@ static int mark_rows(cf_handle* h, const cf_batch* bt, const MarkGame& g, int n_
     ea.players = h->aw.words + (size_t)n_coal * (g.kw ? g.kw : 1);
     ea.scale = g.scale;
     ea.n_coal = n_coal, ea.P = P, ea.F = c.n_feats;
+    MarkWindowDonorArgs wd;      // the window game: ea with the promoter's centre mask rows, flip and the coarsest resolution
+    memset(&wd, 0, sizeof wd);
+    if (g.lo) {
+        for (int r = 0; r < nres; ++r) {
+            wd.w.pmc[r] = static_cast<const uint8_t*>(bt->promoter_mask_row[r]);
+            wd.pf_don[r] = da.pf_don[r];
+            wd.cf_don[r] = da.cf_don[r];
+        }
+        wd.w.flip = g.flip;
+        wd.w.W = g.W, wd.w.rc = g.rc;
+    }
     const long long launches0 = g_launches, rows = (long long)B * n_coal;
     auto run = [&]() -> int {
         for (long long g0 = 0; g0 < rows; g0 += cap) {
             const int n = (int)std::min<long long>(cap, rows - g0);
             ea.g0 = g0;
-            if (g.kw && g.donor) {
+            if (g.lo) {
+                wd.w.m = ea;
+                if (g.donor) {
+                    hipLaunchKernelGGL(k_mark_window_donor_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, wd);
+                    LAUNCH_CHECK("k_mark_window_donor_expand");
+                } else {
+                    hipLaunchKernelGGL(k_mark_window_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, wd.w);
+                    LAUNCH_CHECK("k_mark_window_expand");
+                }
+            } else if (g.kw && g.donor) {
                 hipLaunchKernelGGL(k_mark_wide_donor_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, da);
                 LAUNCH_CHECK("k_mark_wide_donor_expand");
             } else if (g.kw) {
@@ -890,7 +915,9 @@ static int mark_coalitions_impl(cf_handle* h, const cf_batch* bt, const MarkGame
     if (mark_upload(h, g, keep, n_coal, st, who)) return -1;
     return mark_rows(h, bt, g, n_coal, logits, st);
 }
-// all 2^P coalitions through mark_upload + mark_rows (word m at column m), then k_shapley with S = P;
+static int mark_wide_upload(cf_handle* h, const MarkGame& g, const uint32_t* keep, int n_coal, size_t extra, hipStream_t st, const char* who);
+// all 2^P coalitions through mark_upload (a game of g.kw = 1 word: mark_wide_upload) + mark_rows (word m at column m), then k_shapley
+// with S = P;
 static int mark_shapley_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g, float* phi, float* logits_all, void* stream, const char* who) {
     if (!phi) return fail("%s: null phi", who);
     const cf_config& c = h->cfg;
@@ -900,7 +927,7 @@ static int mark_shapley_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g
     std::vector<uint32_t> keep(n);
     for (int m = 0; m < n; ++m) keep[m] = (uint32_t)m;
     hipStream_t st = (hipStream_t)stream;
-    if (mark_upload(h, g, keep.data(), n, st, who) || mark_rows(h, bt, g, n, rows, st)) return -1;
+    if ((g.kw ? mark_wide_upload(h, g, keep.data(), n, 0, st, who) : mark_upload(h, g, keep.data(), n, st, who)) || mark_rows(h, bt, g, n, rows, st)) return -1;
     ShapleyArgs sa;
     memset(&sa, 0, sizeof sa);
     sa.v = rows, sa.phi = phi, sa.S = P, sa.n_out = c.n_out;
@@ -975,28 +1002,34 @@ extern "C" int cf_mark_donor_epistasis(cf_handle* h, const cf_batch* bt, const c
 
 // The wide game (cf_marks_wide.h): up to kMarkWideMaxP players, kw words per coalition, one options struct for both rules.  `d`: the
 // donor's pointers in the struct mark_rows reads them from (the caller's storage).
-static int mark_wide_game(cf_handle* h, const cf_batch* bt, const cf_mark_wide_opts* o, MarkGame* g, cf_mark_donor_opts* d, const char* who) {
-    *g = o ? MarkGame{o->n_players, o->player_marks, o->player_regions, o->scale, nullptr} : MarkGame{};
-    if (mark_check(h, bt, o != nullptr, *g, who, kMarkWideMaxP)) return -1;
-    g->kw = (g->P + 31) / 32;
+// mark_rule: which rule a one-struct game asks for -- all donor pointers null: the scale rule (g->scale, checked); all set: the donor
+// rule (g->donor = d, filled); mixed: refused.
+static int mark_rule(cf_handle* h, MarkGame* g, cf_mark_donor_opts* d, const float* const* don_p, const float* const* don_c, const char* who) {
     int given = 0;
-    for (int r = 0; r < h->cfg.n_res; ++r) given += (o->donor_promoter_feats[r] != nullptr) + (o->donor_pcre_feats[r] != nullptr);
+    for (int r = 0; r < h->cfg.n_res; ++r) given += (don_p[r] != nullptr) + (don_c[r] != nullptr);
     if (given && given != 2 * h->cfg.n_res)
         return fail("%s: %d of the %d donor_promoter_feats / donor_pcre_feats pointers below the model's %d resolutions are null: all of them "
                     "(the scale rule) or none (the donor rule)", who, 2 * h->cfg.n_res - given, 2 * h->cfg.n_res, h->cfg.n_res);
     if (given) {
         memset(d, 0, sizeof *d);
-        for (int r = 0; r < h->cfg.n_res; ++r) d->donor_promoter_feats[r] = o->donor_promoter_feats[r], d->donor_pcre_feats[r] = o->donor_pcre_feats[r];
+        for (int r = 0; r < h->cfg.n_res; ++r) d->donor_promoter_feats[r] = don_p[r], d->donor_pcre_feats[r] = don_c[r];
         g->donor = d;
         g->scale = 0.f;
-    } else if (!(o->scale >= 0.f) || !std::isfinite(o->scale)) {
-        return fail("%s: scale = %g: a finite factor >= 0", who, (double)o->scale);
+    } else if (!(g->scale >= 0.f) || !std::isfinite(g->scale)) {
+        return fail("%s: scale = %g: a finite factor >= 0", who, (double)g->scale);
     }
     return 0;
 }
+static int mark_wide_game(cf_handle* h, const cf_batch* bt, const cf_mark_wide_opts* o, MarkGame* g, cf_mark_donor_opts* d, const char* who) {
+    *g = o ? MarkGame{o->n_players, o->player_marks, o->player_regions, o->scale, nullptr} : MarkGame{};
+    if (mark_check(h, bt, o != nullptr, *g, who, kMarkWideMaxP)) return -1;
+    g->kw = (g->P + 31) / 32;
+    return mark_rule(h, g, d, o->donor_promoter_feats, o->donor_pcre_feats, who);
+}
 
 // The n_coal * kw coalition words (validated) and the 2 P player words into the workspace's word table, with room for `extra` words
-// behind them: [words | marks_p | regions_p | extra].
+// behind them: [words | marks_p | regions_p | extra]; the window game: [words | marks_p | regions_p | lo_p | hi_p | extra].
+static int mark_player_words(const MarkGame& g) { return (g.lo ? 4 : 2) * g.P; }
 static int mark_wide_upload(cf_handle* h, const MarkGame& g, const uint32_t* keep, int n_coal, size_t extra, hipStream_t st, const char* who) {
     const int P = g.P, kw = g.kw;
     if (n_coal < 1) return fail("%s: n_coal = %d: at least 1 coalition", who, n_coal);
@@ -1007,11 +1040,15 @@ static int mark_wide_upload(cf_handle* h, const MarkGame& g, const uint32_t* kee
             if (last >> (P & 31)) return fail("%s: keep[%d] (word %d = 0x%x) names a player >= n_players = %d", who, k, kw - 1, last, P);
         }
     const size_t nw = (size_t)n_coal * kw;
-    if (attrib_ws(h, who) || h->aw.words.need(nw + 2 * P + extra, 256, who)) return -1;
+    if (attrib_ws(h, who) || h->aw.words.need(nw + mark_player_words(g) + extra, 256, who)) return -1;
     unsigned* tab = h->aw.words;
     HIP_TRY(hipMemcpyAsync(tab, keep, nw * sizeof(unsigned), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(tab + nw, g.marks, P * sizeof(unsigned), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(tab + nw + P, g.regions, P * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    if (g.lo) {
+        HIP_TRY(hipMemcpyAsync(tab + nw + 2 * P, g.lo, P * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(tab + nw + 3 * P, g.hi, P * sizeof(int), hipMemcpyHostToDevice, st));
+    }
     return 0;
 }
 
@@ -1029,13 +1066,9 @@ extern "C" int cf_mark_coalitions_wide(cf_handle* h, const cf_batch* bt, const c
 
 // The prefix rows of n_perm permutations through mark_wide_upload + mark_rows (column 0 nobody, column 1 everybody, column
 // 2 + q (P - 1) + (k - 1) the first k players of permutation q), then k_perm_shapley on the inverse permutations, which travel as bytes
-// behind the player words.
-extern "C" int cf_mark_shapley_sampled(cf_handle* h, const cf_batch* bt, const cf_mark_wide_opts* o, const uint8_t* perms, int n_perm, float* phi,
-                                       float* se, float* logits_rows, void* stream) {
-    const char* who = "cf_mark_shapley_sampled";
-    MarkGame g;
-    cf_mark_donor_opts d;
-    if (mark_wide_game(h, bt, o, &g, &d, who)) return -1;
+// behind the player words.  `g`: a checked wide game, with or without windows.
+static int mark_sampled_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g, const uint8_t* perms, int n_perm, float* phi, float* se,
+                             float* logits_rows, void* stream, const char* who) {
     if (!phi) return fail("%s: null phi", who);
     if (!perms) return fail("%s: null perms", who);
     if (n_perm < 1) return fail("%s: n_perm = %d: at least 1 permutation", who, n_perm);
@@ -1065,7 +1098,7 @@ extern "C" int cf_mark_shapley_sampled(cf_handle* h, const cf_batch* bt, const c
     if (!rows) return -1;
     hipStream_t st = (hipStream_t)stream;
     if (mark_wide_upload(h, g, keep.data(), R, (rank.size() + 3) / 4, st, who)) return -1;
-    uint8_t* rank_at = reinterpret_cast<uint8_t*>((unsigned*)h->aw.words + (size_t)R * kw + 2 * P);
+    uint8_t* rank_at = reinterpret_cast<uint8_t*>((unsigned*)h->aw.words + (size_t)R * kw + mark_player_words(g));
     HIP_TRY(hipMemcpyAsync(rank_at, rank.data(), rank.size(), hipMemcpyHostToDevice, st));
     if (mark_rows(h, bt, g, R, rows, st)) return -1;
     PermShapleyArgs pa;
@@ -1077,4 +1110,61 @@ extern "C" int cf_mark_shapley_sampled(cf_handle* h, const cf_batch* bt, const c
     LAUNCH_CHECK("k_perm_shapley");
     forward_one_more(h);
     return 0;
+}
+extern "C" int cf_mark_shapley_sampled(cf_handle* h, const cf_batch* bt, const cf_mark_wide_opts* o, const uint8_t* perms, int n_perm, float* phi,
+                                       float* se, float* logits_rows, void* stream) {
+    const char* who = "cf_mark_shapley_sampled";
+    MarkGame g;
+    cf_mark_donor_opts d;
+    return mark_wide_game(h, bt, o, &g, &d, who) ? -1 : mark_sampled_impl(h, bt, g, perms, n_perm, phi, se, logits_rows, stream, who);
+}
+
+// The window game (cf_mark_windows.h): the wide game's checks, then the windows against the coarsest resolution's W bins (nested bin
+// counts in the scan's wording, W within the kernels' table) and the rule.  `limit`: the most players (the exact call: kCoalMaxS).
+static int mark_window_game(cf_handle* h, const cf_batch* bt, const cf_mark_window_opts* o, MarkGame* g, cf_mark_donor_opts* d, const char* who,
+                            int limit = kMarkWideMaxP) {
+    *g = o ? MarkGame{o->n_players, o->player_marks, o->player_regions, o->scale, nullptr} : MarkGame{};
+    if (mark_check(h, bt, o != nullptr, *g, who, limit)) return -1;
+    g->kw = (g->P + 31) / 32;
+    const cf_config& c = h->cfg;
+    int rc = 0;
+    for (int r = 1; r < c.n_res; ++r)
+        if (c.n_bins[r] < c.n_bins[rc]) rc = r;
+    const int W = c.n_bins[rc];
+    for (int r = 0; r < c.n_res; ++r)
+        if (c.n_bins[r] % W) return fail("%s: n_bins[%d] = %d is not a multiple of the coarsest resolution's %d bins", who, r, c.n_bins[r], W);
+    if (W > kWinMaxW) return fail("%s: the coarsest resolution has W = %d bins; the window table holds at most %d", who, W, kWinMaxW);
+    if (!o->player_lo || !o->player_hi) return fail("%s: null player_lo / player_hi", who);
+    for (int p = 0; p < g->P; ++p) {
+        const int lo = o->player_lo[p], hi = o->player_hi[p];
+        if (lo < 0 || hi > W || lo >= hi)
+            return fail("%s: player %d has the window [%d, %d): 0 <= lo < hi <= W = %d coarsest bins is required", who, p, lo, hi, W);
+    }
+    g->lo = o->player_lo, g->hi = o->player_hi, g->flip = o->flip, g->W = W, g->rc = rc;
+    return mark_rule(h, g, d, o->donor_promoter_feats, o->donor_pcre_feats, who);
+}
+
+extern "C" int cf_mark_window_coalitions(cf_handle* h, const cf_batch* bt, const cf_mark_window_opts* o, const uint32_t* keep, int n_coal,
+                                         float* logits, void* stream) {
+    const char* who = "cf_mark_window_coalitions";
+    MarkGame g;
+    cf_mark_donor_opts d;
+    if (mark_window_game(h, bt, o, &g, &d, who)) return -1;
+    if (!logits) return fail("%s: null logits", who);
+    hipStream_t st = (hipStream_t)stream;
+    if (mark_wide_upload(h, g, keep, n_coal, 0, st, who)) return -1;
+    return mark_rows(h, bt, g, n_coal, logits, st);
+}
+extern "C" int cf_mark_window_shapley(cf_handle* h, const cf_batch* bt, const cf_mark_window_opts* o, float* phi, float* logits_all, void* stream) {
+    const char* who = "cf_mark_window_shapley";
+    MarkGame g;
+    cf_mark_donor_opts d;
+    return mark_window_game(h, bt, o, &g, &d, who, kCoalMaxS) ? -1 : mark_shapley_impl(h, bt, g, phi, logits_all, stream, who);
+}
+extern "C" int cf_mark_window_shapley_sampled(cf_handle* h, const cf_batch* bt, const cf_mark_window_opts* o, const uint8_t* perms, int n_perm,
+                                              float* phi, float* se, float* logits_rows, void* stream) {
+    const char* who = "cf_mark_window_shapley_sampled";
+    MarkGame g;
+    cf_mark_donor_opts d;
+    return mark_window_game(h, bt, o, &g, &d, who) ? -1 : mark_sampled_impl(h, bt, g, perms, n_perm, phi, se, logits_rows, stream, who);
 }

@@ -1093,6 +1093,123 @@ class ChromoformerBase(nn.Module):
         return mark_shapley_sampled(self, dataset, donor_dataset, genes=genes, players=players, n_perm=n_perm, seed=seed, scale=scale, bsz=bsz,
                                     store=store, donor_store=donor_store)
 
+    def _mark_window_opts(self, who, players, width, scale, donor, flip, B):
+        """players (a window_players spec) at `width`, scale, donor (None: the scale rule; else the forms of _mark_donor_opts) and flip
+        ([B] bools or None: the promoter is stored mirrored) for a batch of B genes -> (cf_mark_window_opts, what it points to, names)."""
+        from .attribution import window_players
+        marks, regions, lo, hi, names = window_players(players, self.n_feats, self.i_max, min(self.n_bins), width)
+        opts = _lib.cf_mark_window_opts()
+        opts.n_players, opts.scale = len(marks), float(scale)
+        opts.player_marks, opts.player_regions = marks.ctypes.data, regions.ctypes.data
+        opts.player_lo, opts.player_hi = lo.ctypes.data, hi.ctypes.data
+        flip = self._scan_flip(who, flip, B)
+        if flip is not None:
+            opts.flip = flip.data_ptr()
+        alive = (marks, regions, lo, hi, flip) + (self._donor_feats(who, donor, B, opts) if donor is not None else ())
+        return opts, alive, names
+
+    @torch.no_grad()
+    def mark_window_coalitions(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                               interaction_freq=None, keep=None, players="promoter", width=1, scale=0.0, donor=None, flip=None):
+        """The prediction under coalitions of WINDOW players (cf_mark_window_coalitions) -> logits [B, n_coal, n_out] on the model's
+        device, no autograd graph.  A player is a set of marks in a set of regions over a window of bins of the coarsest resolution
+        (attribution.window_players: "promoter", "promoter_cells", "regions" at `width` bins per window, or (marks, regions, (lo, hi))
+        triples; at most 128).  `keep` as in mark_coalitions_wide.  Column c is the inference forward with the marks of every ABSENT
+        player, inside its window of its regions, scaled by `scale` in raw-signal space (0 erases; donor None) or taken from the donor
+        (the forms of mark_donor_coalitions), at every resolution; an element covered by several absent players changes once.  flip:
+        [B] bools, True where the promoter is stored mirrored ('-' strand): windows count from the genomic start, as in
+        perturbation_scan.  One absent single-region player gives the row of perturbation_scan(width=hi - lo) at window lo, bit for bit; a
+        window past a region's real bins changes nothing.  The packed forms of the first argument and the effect on a pending
+        backward() are those of mark_coalitions."""
+        from .attribution import mark_wide_words
+        who = "mark_window_coalitions"
+        if keep is None:
+            raise ValueError("mark_window_coalitions: keep is required: the coalitions (bit p set: player p present)")
+        bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        opts, _alive, _names = self._mark_window_opts(who, players, width, scale, donor, flip, bs.B)
+        words = mark_wide_words(keep, opts.n_players, who)
+        logits = torch.empty(bs.B, len(words), self.n_out, device=self._device)      # (written in full by the library)
+        st = book()
+        _lib.check(_lib.lib().cf_mark_window_coalitions(self._handle, C.byref(bs), C.byref(opts), words.ctypes.data, len(words), logits.data_ptr(), st),
+                   "cf_mark_window_coalitions")
+        return logits
+
+    @torch.no_grad()
+    def mark_window_shapley(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                            interaction_freq=None, players="promoter", width=1, scale=0.0, donor=None, flip=None, return_coalitions=False):
+        """Exact Shapley values of at most 16 window players (cf_mark_window_shapley) -> (phi, info), tensors on the model's device, no
+        autograd graph: which stretch of the region carries the prediction?  Two redundant stretches share the credit here, where a
+        leave-one-out scan scores both near zero.
+
+          phi                 [B, P, n_out]: player p's average marginal contribution over all orders; exactly 0 for a null player
+                              (a window past the region's real bins, a dummy slot)
+          info["logits"]      [B, n_out]: the prediction (every player present; model(...) under no_grad, bit-equal)
+          info["erased"]      [B, n_out]: every player absent (donor None); info["donor"] with a donor
+          info["delta"]       [B, n_out]: phi.sum(1) - (logits - erased), the efficiency gap (rounding only)
+          info["players"]     the players' names
+          info["coalitions"]  [B, 2^P, n_out], with return_coalitions: the logits of every coalition, word m at column m
+
+        players, width, scale, donor and flip as in mark_window_coalitions."""
+        who = "mark_window_shapley"
+        bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        opts, _alive, names = self._mark_window_opts(who, players, width, scale, donor, flip, bs.B)
+        P = opts.n_players
+        if P > 16:
+            raise ValueError("%s: %d players; the exact game takes 1..16: choose a larger width or mark_window_shapley_sampled" % (who, P))
+        n = 1 << P
+        rows = torch.empty(bs.B, n, self.n_out, device=self._device)      # (both written in full by the library)
+        phi = torch.empty(bs.B, P, self.n_out, device=self._device)
+        st = book()
+        _lib.check(_lib.lib().cf_mark_window_shapley(self._handle, C.byref(bs), C.byref(opts), phi.data_ptr(), rows.data_ptr(), st), "cf_mark_window_shapley")
+        absent = "erased" if donor is None else "donor"
+        info = {"logits": rows[:, n - 1].clone(), absent: rows[:, 0].clone(), "players": names}
+        info["delta"] = phi.sum(1) - (info["logits"] - info[absent])
+        if return_coalitions:
+            info["coalitions"] = rows
+        return phi, info
+
+    @torch.no_grad()
+    def mark_window_shapley_sampled(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                                    interaction_freq=None, players="promoter", width=1, n_perm=64, seed=0, permutations=None, scale=0.0,
+                                    donor=None, flip=None, return_rows=False):
+        """Permutation-sampled Shapley values of up to 128 window players (cf_mark_window_shapley_sampled) -> (phi, info) with the keys,
+        the row layout and the estimator of mark_shapley_sampled: which mark in which stretch?  players, width, scale, donor and flip
+        as in mark_window_coalitions; n_perm, seed and permutations as in mark_shapley_sampled.  A null player (a window past the
+        region's real bins, a dummy slot) has phi and stderr exactly 0."""
+        from .attribution import shapley_permutations
+        who = "mark_window_shapley_sampled"
+        bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        opts, _alive, names = self._mark_window_opts(who, players, width, scale, donor, flip, bs.B)
+        P = opts.n_players
+        if permutations is None:
+            perms = shapley_permutations(P, n_perm, seed)
+        else:
+            given = np.asarray(permutations.cpu() if hasattr(permutations, "cpu") else permutations)
+            if given.ndim != 2 or given.shape[0] < 1 or given.shape[1] != P or given.dtype.kind not in "iu" or given.min() < 0 or given.max() >= P:
+                raise ValueError("%s: permutations must be an integer array [n_perm >= 1, P = %d] with entries in [0, P)" % (who, P))
+            perms = np.ascontiguousarray(given, dtype=np.uint8)
+        n = len(perms)
+        R = 2 + n * (P - 1)
+        rows = torch.empty(bs.B, R, self.n_out, device=self._device)      # (all three written in full by the library)
+        phi = torch.empty(bs.B, P, self.n_out, device=self._device)
+        se = torch.empty(bs.B, P, self.n_out, device=self._device)
+        st = book()
+        _lib.check(_lib.lib().cf_mark_window_shapley_sampled(self._handle, C.byref(bs), C.byref(opts), perms.ctypes.data, n, phi.data_ptr(),
+                                                             se.data_ptr(), rows.data_ptr(), st), "cf_mark_window_shapley_sampled")
+        info = {"logits": rows[:, 1].clone(), "absent": rows[:, 0].clone(), "stderr": se, "names": names, "permutations": perms}
+        info["delta"] = phi.sum(1) - (info["logits"] - info["absent"])
+        if return_rows:
+            info["rows"] = rows
+        return phi, info
+
+    def mark_window_shapley_dataset(self, dataset, donor_dataset=None, genes=None, players="promoter", width=1, n_perm=64, seed=0, scale=0.0,
+                                    bsz=None, store=None, donor_store=None):
+        """Shapley values of window players over the genes of a ChromoformerDataset, against a donor cell type's dataset if one is
+        given, windows in genomic coordinates (chromoformer_amd.attribution.mark_window_shapley, a generator of per-gene dicts)."""
+        from .attribution import mark_window_shapley
+        return mark_window_shapley(self, dataset, donor_dataset, genes=genes, players=players, width=width, n_perm=n_perm, seed=seed,
+                                   scale=scale, bsz=bsz, store=store, donor_store=donor_store)
+
     def raw_signal_gradients(self, dataset, genes=None, target=None, times_input=False, bsz=None):
         """Raw-signal saliency of the genes of a ChromoformerDataset: the gradient (or gradient x input) of logit column `target` with
         respect to the raw fp16 signals, per gene one track per histone mark for the promoter window and every pCRE, in genomic

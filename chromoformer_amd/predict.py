@@ -279,6 +279,34 @@ def write_mark_sampled_values(model, store, donor_store, bsz, gene_ids, path, re
                  logits=logits.numpy(), absent=absent.numpy())
 
 
+def write_mark_window_values(model, ds, donor_ds, store, donor_store, bsz, gene_ids, path, regression=False, players="promoter", width=1, n_perm=64,
+                             seed=0, scale=0.0):
+    """Shapley values of window players (model.mark_window_shapley_dataset: exact with at most 16 players, else sampled) of every gene
+    of a device-resident store, in store order, in LOGIT space of the prediction's column, into `path`, an .npz with gene_ids [n],
+    players [P] (names), estimator ("exact" or "sampled": which one ran), phi [n, P], stderr [n, P] (zeros from the exact call), logits
+    [n], absent [n] (every player absent; phi sums to their difference), null bool [n, P] (the player's window holds no real bin of
+    the gene: phi = 0), chroms [n, P] and windows int64 [n, P, 2] (the genomic start and end of the player's window in its region; ""
+    and -1 where null) and, sampled, permutations uint8 [n_perm, P].  ds / donor_ds: the datasets the stores were built from (strand
+    and coordinates); donor_ds None: the scale rule."""
+    n, t = len(gene_ids), 0 if regression else 1
+    rows = list(model.mark_window_shapley_dataset(ds, donor_ds, genes=list(gene_ids), players=players, width=width, n_perm=n_perm, seed=seed,
+                                                  scale=scale, bsz=bsz, store=store, donor_store=donor_store))
+    P = len(rows[0]["players"])
+    chroms, windows = np.full((n, P), "", dtype=object), np.full((n, P, 2), -1, dtype=np.int64)
+    for i, r in enumerate(rows):
+        for p, real in enumerate(r["windows"]):
+            if real:      # (the named specs give every player one region)
+                chroms[i, p], windows[i, p] = real[0][1], real[0][2:]
+    out = dict(gene_ids=np.array(list(gene_ids)), players=np.array(rows[0]["players"]), estimator=np.array(rows[0]["estimator"]),
+               phi=np.stack([r["phi"][:, t] for r in rows]), stderr=np.stack([r["stderr"][:, t] for r in rows]),
+               logits=np.array([r["logits"][t] for r in rows], dtype=np.float32), absent=np.array([r["absent"][t] for r in rows], dtype=np.float32),
+               null=np.stack([r["null"] for r in rows]), chroms=chroms.astype(str), windows=windows)
+    if "permutations" in rows[0]:
+        out["permutations"] = rows[0]["permutations"]
+    with open(path, "wb") as f:      # (a file object: np.savez would append .npz to a name without it)
+        np.savez(f, **out)
+
+
 def write_integrated_gradients(model, store, bsz, ig_dir, n_steps=50, method="gausslegendre", target=None):
     """Integrated gradients of every gene of a device-resident store, in store order, into `ig_dir`: promoter_feats_{b}.npy
     [n, L, F], pcre_feats_{b}.npy [n, i_max, L, F], interaction_freq.npy [n, T, T] and delta.npy [n] (float32 .npy memory maps;
@@ -445,7 +473,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
             scan_regions="promoter", pcre_shapley_out=None, pcre_epistasis_out=None, mark_shapley_out=None, mark_epistasis_out=None,
             mark_players="marks", mark_scale=0.0, donor_npy_dir=None, donor_meta=None, donor_store_path=None, mark_donor_shapley_out=None,
             mark_donor_epistasis_out=None, mark_sampled_shapley_out=None, mark_donor_sampled_shapley_out=None, mark_sampled_players="cells",
-            mark_perms=64, mark_seed=0):
+            mark_perms=64, mark_seed=0, window_shapley_out=None, window_donor_shapley_out=None, window_players="promoter", window_width=1,
+            window_perms=64, window_seed=0, window_scale=0.0):
     """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file.  attention_dir / embeddings_out: also
     write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps); pcre_ablation_out:
     the predictions with each pCRE deleted (write_pcre_ablation); ig_dir: integrated gradients of every gene
@@ -461,7 +490,10 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     (default: meta_path) or the packed store donor_store_path -- both cell types must hold the genes' regions at the same coordinates
     (attribution.same_regions); mark_sampled_shapley_out / mark_donor_sampled_shapley_out: permutation-sampled Shapley values of up
     to 128 mark players, by default one per (mark, region) pair, under the scale rule (mark_scale applies) / against the donor
-    (write_mark_sampled_values; mark_sampled_players, mark_perms and mark_seed apply)."""
+    (write_mark_sampled_values; mark_sampled_players, mark_perms and mark_seed apply); window_shapley_out /
+    window_donor_shapley_out: Shapley values of window players -- stretches of the promoter or of every region -- under the scale
+    rule (window_scale applies) / against the donor, exact with at most 16 players and sampled otherwise (write_mark_window_values;
+    window_players, window_width, window_perms and window_seed apply)."""
     seed_everything(seed)
     meta = pd.read_csv(meta_path)
     genes = meta.gene_id.tolist()
@@ -470,11 +502,17 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         raw_ds = ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=regression)
         require_raw_signals(raw_ds)      # (before anything is computed)
     from . import pack
-    donor_out = mark_donor_shapley_out or mark_donor_epistasis_out or mark_donor_sampled_shapley_out
+    donor_out = mark_donor_shapley_out or mark_donor_epistasis_out or mark_donor_sampled_shapley_out or window_donor_shapley_out
+    window_ds = None
+    if window_shapley_out or window_donor_shapley_out:      # (strand and coordinates; refusals before anything is computed)
+        from .attribution import window_players as window_game
+        window_game(window_players, 7, i_max, w_max // max(binsizes), window_width)
+        window_ds = ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False)
     if donor_out:      # (before anything is computed)
         from .attribution import same_regions
         if not donor_npy_dir:
-            raise ValueError("predict: mark_donor_shapley_out / mark_donor_epistasis_out / mark_donor_sampled_shapley_out need donor_npy_dir")
+            raise ValueError("predict: mark_donor_shapley_out / mark_donor_epistasis_out / mark_donor_sampled_shapley_out / "
+                             "window_donor_shapley_out need donor_npy_dir")
         donor_ds = ChromoformerDataset(donor_meta or meta_path, donor_npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False)
         same_regions(ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False), donor_ds)
     packed = pack.find(npy_dir, store_path, list(binsizes), i_max, w_prom, w_max, 7, genes, meta=meta)
@@ -511,10 +549,16 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         if mark_donor_sampled_shapley_out:
             write_mark_sampled_values(model, store, donor_store, bsz, genes, mark_donor_sampled_shapley_out, regression, mark_sampled_players,
                                       mark_perms, mark_seed)
+        if window_donor_shapley_out:
+            write_mark_window_values(model, window_ds, donor_ds, store, donor_store, bsz, genes, window_donor_shapley_out, regression, window_players,
+                                     window_width, window_perms, window_seed)
         del donor_store
     if mark_sampled_shapley_out:
         write_mark_sampled_values(model, store, None, bsz, genes, mark_sampled_shapley_out, regression, mark_sampled_players, mark_perms, mark_seed,
                                   mark_scale)
+    if window_shapley_out:
+        write_mark_window_values(model, window_ds, None, store, None, bsz, genes, window_shapley_out, regression, window_players, window_width,
+                                 window_perms, window_seed, window_scale)
     if ig_dir:
         write_integrated_gradients(model, store, bsz, ig_dir, ig_steps, ig_method, ig_target)
     if scan_out:
@@ -607,6 +651,22 @@ def build_parser():
                     "[n_genes, i_max + 1, 7]), or the specs of --mark-players")
     ap.add_argument("--mark-perms", type=int, default=None, help="sampled orders of adding the players (default 64); each costs P - 1 forwards per gene")
     ap.add_argument("--mark-seed", type=int, default=None, help="seed of the sampled orders (default 0)")
+    from .attribution import WINDOW_PLAYER_SPECS
+    ap.add_argument("--window-shapley-out", default=None, help="also write the Shapley values of WINDOW players -- stretches of a region, in "
+                    "coarsest bins -- to this .npz file, in metadata order and in LOGIT space of the prediction's column: gene_ids, players "
+                    "(names), estimator (exact with at most 16 players, else sampled), phi [n_genes, P], stderr, logits, absent (every player "
+                    "absent; phi sums to their difference), null (the window holds no real bin of the gene), chroms and windows [n_genes, P, 2] "
+                    "(genomic start and end) and, sampled, permutations (model.mark_window_shapley / mark_window_shapley_sampled)")
+    ap.add_argument("--window-donor-shapley-out", default=None, help="the same against the donor cell type of --donor-npy-dir: an absent "
+                    "player's window takes the donor's signal")
+    ap.add_argument("--window-players", default=None, choices=WINDOW_PLAYER_SPECS, help="the players of --window-shapley-out / "
+                    "--window-donor-shapley-out: all marks per promoter window (promoter, the default), each mark per promoter window "
+                    "(promoter_cells) or all marks per window of every region (regions); at most 128: widen the windows")
+    ap.add_argument("--window-width", type=int, default=None, help="window width in coarsest bins (default 1)")
+    ap.add_argument("--window-perms", type=int, default=None, help="sampled orders when there are more than 16 players (default 64)")
+    ap.add_argument("--window-seed", type=int, default=None, help="seed of the sampled orders (default 0)")
+    ap.add_argument("--window-scale", type=float, default=None, help="what an absent player's raw signal is scaled by inside its window: 0 "
+                    "erases it (default); --window-shapley-out only")
     return ap
 
 
@@ -630,13 +690,14 @@ def main(argv=None):
     if args.scan_width is not None and args.scan_width < 1:
         ap.error("--scan-width must be at least 1")
     donor_exact = args.mark_donor_shapley_out or args.mark_donor_epistasis_out
-    donor_out = donor_exact or args.mark_donor_sampled_shapley_out
+    donor_out = donor_exact or args.mark_donor_sampled_shapley_out or args.window_donor_shapley_out
     sampled_out = args.mark_sampled_shapley_out or args.mark_donor_sampled_shapley_out
     if donor_out and not args.donor_npy_dir:
-        ap.error("--mark-donor-shapley-out / --mark-donor-epistasis-out / --mark-donor-sampled-shapley-out need --donor-npy-dir")
+        ap.error("--mark-donor-shapley-out / --mark-donor-epistasis-out / --mark-donor-sampled-shapley-out / --window-donor-shapley-out need "
+                 "--donor-npy-dir")
     if not donor_out and (args.donor_npy_dir or args.donor_meta or args.donor_store):
         ap.error("--donor-npy-dir / --donor-meta / --donor-store need --mark-donor-shapley-out, --mark-donor-epistasis-out or "
-                 "--mark-donor-sampled-shapley-out")
+                 "--mark-donor-sampled-shapley-out (or --window-donor-shapley-out)")
     if not sampled_out and (args.mark_sampled_players is not None or args.mark_perms is not None or args.mark_seed is not None):
         ap.error("--mark-sampled-players / --mark-perms / --mark-seed need --mark-sampled-shapley-out or --mark-donor-sampled-shapley-out")
     if args.mark_perms is not None and args.mark_perms < 1:
@@ -648,6 +709,24 @@ def main(argv=None):
                  " --mark-sampled-shapley-out)")
     if args.mark_scale is not None and not (args.mark_scale >= 0 and np.isfinite(args.mark_scale)):
         ap.error("--mark-scale must be a finite factor >= 0")
+    window_out = args.window_shapley_out or args.window_donor_shapley_out
+    if not window_out and (args.window_players is not None or args.window_width is not None or args.window_perms is not None
+                           or args.window_seed is not None):
+        ap.error("--window-players / --window-width / --window-perms / --window-seed need --window-shapley-out or --window-donor-shapley-out")
+    if args.window_scale is not None and not args.window_shapley_out:
+        ap.error("--window-scale needs --window-shapley-out (the donor rule has no scale)")
+    if args.window_scale is not None and not (args.window_scale >= 0 and np.isfinite(args.window_scale)):
+        ap.error("--window-scale must be a finite factor >= 0")
+    if args.window_width is not None and args.window_width < 1:
+        ap.error("--window-width must be at least 1")
+    if args.window_perms is not None and args.window_perms < 1:
+        ap.error("--window-perms must be at least 1")
+    if window_out:
+        from .attribution import window_players
+        try:
+            window_players(args.window_players or "promoter", 7, 8, 20, 1 if args.window_width is None else args.window_width)
+        except ValueError as e:
+            ap.error(str(e))
     meta, pred = predict(args.meta, args.npy_dir, args.weights, args.regression, progress=True, store_path=args.store,
                          attention_dir=args.attention_dir, embeddings_out=args.embeddings_out, pcre_ablation_out=args.pcre_ablation_out,
                          ig_dir=args.ig_dir, ig_steps=50 if args.ig_steps is None else args.ig_steps,
@@ -662,7 +741,12 @@ def main(argv=None):
                          mark_donor_shapley_out=args.mark_donor_shapley_out, mark_donor_epistasis_out=args.mark_donor_epistasis_out,
                          mark_sampled_shapley_out=args.mark_sampled_shapley_out, mark_donor_sampled_shapley_out=args.mark_donor_sampled_shapley_out,
                          mark_sampled_players=args.mark_sampled_players or "cells", mark_perms=64 if args.mark_perms is None else args.mark_perms,
-                         mark_seed=0 if args.mark_seed is None else args.mark_seed)
+                         mark_seed=0 if args.mark_seed is None else args.mark_seed, window_shapley_out=args.window_shapley_out,
+                         window_donor_shapley_out=args.window_donor_shapley_out, window_players=args.window_players or "promoter",
+                         window_width=1 if args.window_width is None else args.window_width,
+                         window_perms=64 if args.window_perms is None else args.window_perms,
+                         window_seed=0 if args.window_seed is None else args.window_seed,
+                         window_scale=0.0 if args.window_scale is None else args.window_scale)
     print("Predicting expressions for %d genes." % len(meta))
     meta["prediction"] = pred
     meta.to_csv(args.output, index=False)

@@ -505,6 +505,53 @@ int cf_mark_coalitions_wide(cf_handle* h, const cf_batch* batch, const cf_mark_w
  * perms that is not a permutation (its index q is named). */
 int cf_mark_shapley_sampled(cf_handle* h, const cf_batch* batch, const cf_mark_wide_opts* opts, const uint8_t* perms, int n_perm, float* phi,
                             float* se, float* logits_rows, void* stream);
+/* The same game with WINDOWS as players (interpretation): where inside a region does the signal lie?  c = the coarsest resolution,
+ * W = n_bins[c], R_r = n_bins[r] / W.  Player p is (player_marks[p], player_regions[p], [player_lo[p], player_hi[p])): those marks in
+ * those regions over the coarse genomic bins lo .. hi - 1, the windows of cf_perturbation_scan; 0 <= lo < hi <= W.  Coalitions are
+ * the kw = ceil(P / 32) words of cf_mark_coalitions_wide.  Row (b, k) is the inference forward of gene b with, for every region rho
+ * and coarse genomic bin g,
+ *   gone(rho, g) = OR of player_marks[p] over the absent players p with bit rho in player_regions[p] and lo_p <= g < hi_p
+ * Region rho's real rows at resolution r are [q_r, q_r + n_r) and n_c is its real bin count at c, from the centre pad-mask rows of
+ * the batch as cf_perturbation_scan reads them.  Genomic bin j is row q_r + j, or row q_r + n_r - 1 - j where flip[b] is set (the
+ * promoter only: a pCRE is never stored mirrored).  The element of a real row with genomic bin j and mark f, g = j / R_r, g < n_c and
+ * bit f in gone(rho, g) changes -- the scale rule: log1pf(s expm1f(u)), once however many absent players cover it; the donor rule:
+ * the bits of the donor's element at the same position -- and every other element keeps its bits; masks and interaction_freq are
+ * gene b's.  Bin sizes nest and binning is linear per mark: this is exactly the feature the binning produces when the raw samples
+ * of those marks inside the windows are scaled by s, or replaced by the donor's.  A window with lo_p >= n_c (a dummy slot, a short
+ * pCRE, a narrowed promoter) changes nothing: a null player.  One absent player with one region bit gives the row of
+ * cf_perturbation_scan(region, width = hi - lo) at window lo, bit for bit; with every window [0, W) and zeros in the padded rows (the
+ * donor rule: a donor that agrees with the gene outside the real rows) the rows are those of cf_mark_coalitions_wide. */
+typedef struct cf_mark_window_opts {
+    int n_players;                                   /* 1..128 (cf_mark_window_shapley: 1..16) */
+    const unsigned* player_marks;                    /* host [n_players], read before the call returns */
+    const unsigned* player_regions;                  /* host [n_players] */
+    const int* player_lo;                            /* host [n_players]: the first coarse genomic bin of the player's window */
+    const int* player_hi;                            /* host [n_players]: one past the last */
+    const uint8_t* flip;                             /* device [B] or NULL: gene b's promoter is stored mirrored (the '-' strand) */
+    float scale;                                     /* the scale rule: used when every donor pointer is NULL */
+    const float* donor_promoter_feats[CF_MAX_RES];   /* all NULL: scale rule; all non-NULL below n_res: donor rule; mixed: refused */
+    const float* donor_pcre_feats[CF_MAX_RES];
+} cf_mark_window_opts;                               /* 104 bytes */
+/* cf_mark_window_coalitions: keep (HOST, n_coal * kw words), logits [B, n_coal, n_out], the chunking and the chunk buffers are those of
+ * cf_mark_coalitions_wide; per chunk one k_mark_window_expand (the donor rule: k_mark_window_donor_expand), then the launches of
+ * cf_forward(save = 0) on the chunk:
+ *   cf_launch_counts fwd = ceil(B * n_coal / max_batch) * (1 + n_fwd),  n_fwd = what cf_forward(save = 0) issues.
+ * The words and the 4 P player words (marks, regions, lo, hi) travel in the device table the handle owns; no device buffer is added.
+ * Deterministic (no atomics); the result does not depend on max_batch.  Overwrites the activations a cf_forward(save >= 1) kept.
+ * Parameters, gradients and moments are untouched.
+ * Refused by name, before anything is launched: what cf_mark_coalitions_wide refuses; a null player_lo or player_hi; a window with
+ * lo < 0, hi > W or lo >= hi (the player's index is named); an n_bins[r] that is no multiple of W; W > 64. */
+int cf_mark_window_coalitions(cf_handle* h, const cf_batch* batch, const cf_mark_window_opts* opts, const uint32_t* keep, int n_coal,
+                              float* logits, void* stream);
+/* Exact Shapley values of P <= 16 window players: all 2^P words through the routine above (word m at column m), then the k_shapley
+ * of cf_mark_shapley.  phi [B, P, n_out]; logits_all [B, 2^P, n_out] or NULL (the handle-owned buffer).  A null player's phi is
+ * exactly 0.  fwd = that of cf_mark_window_coalitions with n_coal = 2^P, plus 1.  Refusals as above (null phi, n_players > 16). */
+int cf_mark_window_shapley(cf_handle* h, const cf_batch* batch, const cf_mark_window_opts* opts, float* phi, float* logits_all, void* stream);
+/* Permutation-sampled Shapley values of the window players: perms, the R = 2 + n_perm * (P - 1) rows per gene, k_perm_shapley, phi, the
+ * optional se and logits_rows and the launch count are those of cf_mark_shapley_sampled; a null player's phi and se are exactly 0.
+ * Refusals as above and as there. */
+int cf_mark_window_shapley_sampled(cf_handle* h, const cf_batch* batch, const cf_mark_window_opts* opts, const uint8_t* perms, int n_perm,
+                                   float* phi, float* se, float* logits_rows, void* stream);
 /* torch.optim.AdamW.step (train.py:157, 196): decoupled weight decay, bias correction
  * from `step` (1-based), over [0, n_active). */
 int cf_adamw_step(cf_handle* h, float lr, float beta1, float beta2, float eps, float weight_decay,
