@@ -145,6 +145,7 @@ SYMBOLS = {
     "cf_head_rides": (C.c_int, [C.c_void_p]),
     "cf_kernel_flops": (C.c_double, [C.c_void_p, C.c_char_p, C.c_int]),
     "cf_cu_count": (C.c_int, [C.c_void_p]),
+    "cf_attc_regions": (C.c_int, [C.c_void_p, C.c_int]),
     "cf_keep_tiled": (C.c_int, [C.c_void_p, C.c_int]),
     "cf_params_changed": (C.c_int, [C.c_void_p]),
     "cf_retile_early": (C.c_int, [C.c_void_p, C.c_void_p]),

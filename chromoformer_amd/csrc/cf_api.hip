@@ -445,6 +445,11 @@ extern "C" double cf_kernel_flops(cf_handle* h, const char* kernel, int B) {
     return 0.0;
 }
 extern "C" int cf_cu_count(cf_handle* h) { return h ? h->n_cu : 0; }
+// What launch_attc (cf_api_launch.h) takes for a launch of n_sequences; h == NULL: the rule with the default cap (host only).
+extern "C" int cf_attc_regions(cf_handle* h, int n_sequences) {
+    if (!h) return attc2_regions_per_wg(n_sequences, kAttcCapDefault);
+    return h->attc2 ? attc2_regions_per_wg(n_sequences, h->attc_cap) : 0;
+}
 
 // ------------------------------------------------------------------------------------
 // optimiser

@@ -245,6 +245,8 @@ struct ModelRefs {
     HeadParams head;
 };
 
+constexpr int kAttcCapDefault = 64;      // cf_handle::attc_cap unless CF_ATTC_CAP says otherwise; cf_attc_regions(NULL, .) applies it
+
 struct cf_handle {
     cf_config cfg;
     std::vector<PDesc> table;
@@ -327,7 +329,7 @@ struct cf_handle {
     float *pe2[kMaxRes], *pet2[kMaxRes];      // padded layouts of the gene-batched attention kernel (cf_attc2.h)
     bool attc2 = false;
     bool attc1 = true;                        // one-region launches on the vector-ALU kernel (CF_ATTC1=0: k_attc2<., 1>)
-    int attc_cap = 64;                        // most workgroups per resolution for which attc2 trades regions per workgroup for parallelism
+    int attc_cap = kAttcCapDefault;           // most workgroups per resolution for which attc2 trades regions per workgroup for parallelism
     int xcd_map = 1;                          // XCD-aware placement of the Regulation workgroups (CF_XCD_MAP=0 turns it off)
     int n_wg_r = 0, n_cs_r = 0;               // leading entries of wg_tiles / cs_tiles that belong to the Regulation + head bucket
     long long bucket_split = 0;               // flat offset of the first Regulation parameter (bucket boundary)

@@ -597,6 +597,13 @@ double cf_kernel_flops(cf_handle* h, const char* kernel, int B);
 /* Compute units of the device the handle lives on (hipDeviceAttributeMultiprocessorCount): callers that add rider workgroups to
  * a launch of one-per-CU workgroups (cf_rider_arm) size them with it. */
 int cf_cu_count(cf_handle* h);
+/* Regions per workgroup (1, 2, 4 or 8) that the stand-alone centre-row attention launch takes for n_sequences sequences, forward
+ * and backward alike: n_sequences = B for the Embedding launch, B * i_max for every Pairwise launch.  1 is the one-region kernel
+ * (k_attc1), the others are k_attc2<., 2 / 4 / 8>; a launch whose n_sequences is no multiple of the answer ends in a workgroup with
+ * fewer regions.  0 where the handle does not use the gene-batched kernel (other head counts or row widths, rows too long for its
+ * LDS image).  h == NULL: the rule with the default cap, no device needed.  Read-only; the fused trunk does not go through this
+ * launch.  Tests use it to assert which kernel a batch size reaches. */
+int cf_attc_regions(cf_handle* h, int n_sequences);
 /* Copies a named workspace buffer (e.g. "E0.qt", "dP2.1.xbar") to dst (device);
  * *n_floats receives its size; dst may be NULL to query. */
 int cf_debug_copy(cf_handle* h, const char* name, float* dst, long long* n_floats, void* stream);

@@ -3,7 +3,8 @@ kernel implementations of the library against each other at that size.
 
 Small-batch tests run the centre-row attention with one region per workgroup (k_attc1) in both stages and leave most CUs
 idle; at bsz 64 the Pairwise launches take the eight-regions-per-workgroup MFMA kernel (k_attc2<., 8>), the Regulation kernels
-run 192 workgroups and the weight-gradient tables are fully populated.  The oracle's forward + autograd of one 64-gene batch
+run 192 workgroups and the weight-gradient tables are fully populated (the batch sizes in between -- two and four regions per
+workgroup, a ragged last workgroup, reductions with a partial last stage -- are in test_batch_dispatch_gpu.py).  The oracle's forward + autograd of one 64-gene batch
 takes a few seconds on the host.  Switches (environment, read when a model is constructed): CF_ATTC1=0 puts the one-region
 launches back on the MFMA kernel, CF_REG_FUSED=0 runs the Regulation stack layer by layer on the stand-alone kernels instead of the fused 512-thread ones, CF_HEAD_RIDE=0 the prediction head as a launch of its own (matrix cores, 16 genes per
 workgroup) instead of at the tail of the Regulation forward launch (vector ALUs, one gene per workgroup), CF_REG_ROW0=0 the last Regulation
