@@ -80,6 +80,12 @@ class cf_ig_opts(C.Structure):
 IG_PROMOTER, IG_PCRE, IG_FREQ = 1, 2, 4      # cf_ig_opts.interpolate
 
 
+class cf_bin_spread_job(C.Structure):         # one region of cf_bin_spread_difference (88 bytes; data.BIN_SPREAD_JOB is its numpy twin)
+    _fields_ = [("raw", C.c_void_p), ("ld", C.c_longlong), ("raw_donor", C.c_void_p), ("ld_donor", C.c_longlong), ("col0", C.c_int),
+                ("ncols", C.c_int), ("flip", C.c_int), ("reserved", C.c_int), ("cmean", C.c_void_p * 3), ("draw", C.c_void_p),
+                ("ld_out", C.c_longlong)]
+
+
 class cf_scan_opts(C.Structure):
     _fields_ = [("region", C.c_int), ("width", C.c_int), ("n_sets", C.c_int), ("mark_sets", C.c_void_p), ("scale", C.c_float),
                 ("flip", C.c_void_p), ("feats_out", C.c_void_p * MAX_RES)]
@@ -166,6 +172,8 @@ SYMBOLS = {
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_integrated_gradients_raw": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_ig_opts), C.POINTER(cf_input_grads),
                                               C.POINTER(cf_input_grads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cf_integrated_gradients_raw_donor": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_ig_opts), C.POINTER(cf_input_grads),
+                                                    C.POINTER(cf_input_grads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_perturbation_scan": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_scan_opts), C.c_void_p, C.c_void_p]),
     "cf_perturbation_scan_regions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_scan_regions_opts), C.c_void_p, C.c_void_p]),
     "cf_mark_coalitions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_opts), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
@@ -198,6 +206,7 @@ SYMBOLS = {
     "cf_bin_regions_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p]),
     "cf_bin_regions_multi_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int,
                                                 C.c_void_p]),
+    "cf_bin_spread_difference": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p]),
     "cf_embed_full": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(C.c_void_p), C.c_void_p]),
     "cf_gather_batch": (C.c_int, [C.c_void_p, C.POINTER(cf_store), C.c_void_p, C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.c_void_p]),
     "cf_gather_batch_fwd": (C.c_int, [C.c_void_p, C.POINTER(cf_store), C.c_void_p, C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.c_void_p]),

@@ -393,6 +393,30 @@ class _RawChunk:
                        "cf_bin_regions_multi_backward")
             return draw.cpu().numpy()
 
+    def spread(self, donor, mp, mc):
+        """cf_bin_spread_difference between this chunk's raw regions and those of `donor` (a _RawChunk of the same genes in another
+        dataset over the same regions), cmean pointing into mp[r] [B, 1, L, F] / mc[r] [B, S, L, F] -> the tracks, host float32."""
+        import torch
+
+        from . import _lib
+        from .data import BIN_SPREAD_JOB
+        regs, fj, order, draw = self.regs, self.fj, self.order, self.draw
+        if len(donor.regs) != len(regs) or any((a[0], a[1], a[4], a[5]) != (b[0], b[1], b[4], b[5]) for a, b in zip(regs, donor.regs)):
+            raise ValueError("the donor's raw regions do not cover the same windows as the dataset's")
+        with torch.cuda.device(self.dev):
+            sj = np.zeros(len(regs), dtype=BIN_SPREAD_JOB)
+            for k, (i, s, flip, a, c0, nc, off, ooff, ld_out) in enumerate(regs):
+                for name in ("raw", "ld", "col0", "ncols", "flip"):
+                    sj[k][name] = fj[k][name]
+                sj[k]["raw_donor"], sj[k]["ld_donor"] = donor.fj[k]["raw"], donor.fj[k]["ld"]
+                for r in range(self.nres):
+                    sj[k]["cmean"][order.index(r)] = (mp[r][i, 0] if s < 0 else mc[r][i, s]).data_ptr()
+                sj[k]["draw"], sj[k]["ld_out"] = draw.data_ptr() + 4 * ooff, ld_out
+            tab = torch.from_numpy(sj.view(np.uint8)).to(self.dev)
+            _lib.check(self.lib.cf_bin_spread_difference(C.c_void_p(tab.data_ptr()), len(regs), self.F, self.nres, self.cb, self.cl,
+                                                         int(self.max_cols), self.stream.cuda_stream), "cf_bin_spread_difference")
+            return draw.cpu().numpy()
+
     def scatter(self, host, per):
         """The tracks of `host` into the per-gene dicts `per` (promoter, pcres, regions), genomic coordinates."""
         ds, ids, F = self.ds, self.ids, self.F
@@ -464,7 +488,7 @@ def raw_signal_gradients(model, dataset, genes=None, target=None, times_input=Fa
             yield d
 
 
-def raw_integrated_gradients(model, dataset, genes=None, target=None, n_steps=50, method="gausslegendre", bsz=None):
+def raw_integrated_gradients(model, dataset, genes=None, target=None, n_steps=50, method="gausslegendre", bsz=None, donor_dataset=None):
     """Integrated gradients in raw-signal space: the attribution of logit column `target` (default: 1 for the classifier, 0 for the
     regressor) to every sample of the RAW histone signals of a ChromoformerDataset, along the path a * x from the zero signal, with the
     nodes and weights of ig_quadrature(method, n_steps).  Binning is linear and followed by log(1 + .), so along the path a bin of
@@ -484,16 +508,49 @@ def raw_integrated_gradients(model, dataset, genes=None, target=None, n_steps=50
         delta             float32 scalar: sum of the per-bin attr - (logits - baseline_logits)[target], the quadrature error; the tracks
                           sum to the same total up to fp32 rounding
 
-    Limits: the zero-signal baseline only; binned features below ~80 (expm1 in fp32; preprocessed signals are far below); a negative
-    signal with 1 + a m <= 0 gives inf / NaN as the forward's log does.  Parameters, their .grad, the flat gradient buffer and the
-    optimiser state are left as they are; the pass overwrites the activations a grad-enabled model(...) keeps for its backward."""
+    donor_dataset: a ChromoformerDataset of another cell type over the same regions (same_regions runs first).  The baseline is then
+    that cell type's signal xd and the path xd + a (x - xd): a bin with means m, md has the feature log1p(md + a (m - md)), and with
+    C = sum_k g_k / (1 + md + a_k (m - md))
+
+        attr  = (m - md) * C                                      per bin (complete: sums to F(x) - F(xd))
+        IG_raw[f, s] = (x[f, s] - xd[f, s]) * sum_r C_r[p_r(s), f] / cnt      per sample, coarsest resolution first
+
+    by cf_integrated_gradients_raw_donor and cf_bin_spread_difference on both chunks' raw buffers.  baseline_logits is then the donor's
+    signal under the gene's masks and frequencies, and each dict gains
+
+        donor_prediction  float32 [n_out]: the donor dataset's own plain forward of the gene (its masks, its frequencies)
+
+    A sample where the two signals agree gets exactly 0.
+
+    Limits: without a donor the zero-signal baseline; binned features below ~80 (expm1 in fp32; preprocessed signals are far below); a
+    negative signal with 1 + a m <= 0 gives inf / NaN as the forward's log does.  Parameters, their .grad, the flat gradient buffer and
+    the optimiser state are left as they are; the pass overwrites the activations a grad-enabled model(...) keeps for its backward."""
     import torch
     ds = dataset
     binsizes, n_bins, target, genes, chunk = _raw_check("raw_integrated_gradients", model, ds, genes, target, bsz)
     ig_quadrature(method, n_steps)      # (refuses an unknown method or node count before anything is loaded)
+    if donor_dataset is not None:
+        same_regions(ds, donor_dataset, genes)
     for lo in range(0, len(genes), chunk):
         ids = genes[lo:lo + chunk]
         ch = _RawChunk(model, ds, ids, binsizes, n_bins)
+        if donor_dataset is not None:
+            dch = _RawChunk(model, donor_dataset, ids, binsizes, n_bins)
+            with torch.cuda.device(ch.dev):
+                with torch.no_grad():
+                    dp = model(*dch.model_args()).cpu().numpy()
+                attr, info = model.integrated_gradients(*ch.model_args(), target=target, n_steps=n_steps, method=method,
+                                                        inputs=("promoter_feats", "pcre_feats"), path="signal",
+                                                        donor=({b: dch.pf[r] for r, b in enumerate(binsizes)},
+                                                               {b: dch.cf[r] for r, b in enumerate(binsizes)}))
+                cm = info["cmean"]
+                host = ch.spread(dch, [cm["promoter_feats"][b] for b in binsizes], [cm["pcre_feats"][b] for b in binsizes])
+                lg, lb, dl = (info[k].cpu().numpy() for k in ("logits", "baseline_logits", "delta"))
+            per = [dict(gene_id=gene, logits=lg[i].copy(), baseline_logits=lb[i].copy(), delta=dl[i].copy(), donor_prediction=dp[i].copy(),
+                        promoter=None, pcres=[], regions=[]) for i, gene in enumerate(ids)]
+            for d in ch.scatter(host, per):
+                yield d
+            continue
         with torch.cuda.device(ch.dev):
             attr, info = model.integrated_gradients(*ch.model_args(), target=target, n_steps=n_steps, method=method,
                                                     inputs=("promoter_feats", "pcre_feats"), path="signal")

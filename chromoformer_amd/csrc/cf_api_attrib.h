@@ -415,9 +415,13 @@ static void chunk_rows(cf_handle* h, const cf_batch* bt, RowCopyArgs* ra, cf_bat
 // k_dfreq_sum, k_ig_accumulate.
 //
 // raw: the signal path of the feature segments (cf_integrated_gradients_raw: k_ig_expand_raw, k_ig_accumulate_raw with the node table and
-// the optional second output `coeff`); everything else -- chunking, buffers, launches -- is shared.
+// the optional second output `coeff`); everything else -- chunking, buffers, launches -- is shared.  path = kIgSignalDonor
+// (cf_integrated_gradients_raw_donor): the feature baselines are the donor's features, `coeff` receives cmean, and k_ig_expand_raw_donor /
+// k_ig_accumulate_raw_donor take the two places; nothing else differs.
 static int integrated_gradients_impl(cf_handle* h, const cf_batch* bt, const cf_ig_opts* o, const cf_input_grads* out, const cf_input_grads* coeff,
-                                     float* logits_x, float* logits_base, float* delta, void* stream, bool raw, const char* who) {
+                                     float* logits_x, float* logits_base, float* delta, void* stream, int path, const char* who) {
+    const bool donor = path == kIgSignalDonor, raw = path != kIgLinear;
+    const char* const second = donor ? "cmean" : "coeff";
     if (attrib_open(h, bt, true, who)) return -1;
     if (!o) return fail("%s: null opts", who);
     if (!out) return fail("%s: null out", who);
@@ -433,12 +437,15 @@ static int integrated_gradients_impl(cf_handle* h, const cf_batch* bt, const cf_
     if (raw) {
         if (!ip && !ic) return fail("%s: interpolate = %d: the signal path needs CF_IG_PROMOTER or CF_IG_PCRE (frequencies alone: cf_integrated_gradients)", who, o->interpolate);
         for (int r = 0; r < kMaxRes; ++r) {
-            if (o->base_promoter_feats[r] || o->base_pcre_feats[r])
+            if (!donor && (o->base_promoter_feats[r] || o->base_pcre_feats[r]))
                 return fail("%s: base_promoter_feats / base_pcre_feats[%d]: the signal path starts at the zero signal; a feature baseline is not accepted", who, r);
             if (coeff && ((coeff->promoter_feats[r] && (!ip || r >= nres)) || (coeff->pcre_feats[r] && (!ic || r >= nres))))
-                return fail("%s: coeff promoter_feats / pcre_feats[%d]: given for an input that is not interpolated", who, r);
+                return fail("%s: %s promoter_feats / pcre_feats[%d]: given for an input that is not interpolated", who, second, r);
+            if (donor && r < nres && ((ip && !o->base_promoter_feats[r]) || (ic && !o->base_pcre_feats[r])))
+                return fail("%s: base_promoter_feats / base_pcre_feats[%d]: the donor's features are required for every interpolated feature input", who, r);
         }
-        if (coeff && coeff->interaction_freq) return fail("%s: coeff interaction_freq: interaction_freq has no signal path, so no coefficient", who);
+        if (coeff && coeff->interaction_freq) return fail("%s: %s interaction_freq: interaction_freq has no signal path, so no coefficient", who, second);
+        if (donor && o->base_broadcast) return fail("%s: base_broadcast = %d: the donor holds the same genes as the batch, one row each", who, o->base_broadcast);
     }
     for (int r = 0; r < kMaxRes; ++r) {
         if (r >= nres && (out->promoter_feats[r] || out->pcre_feats[r] || o->base_promoter_feats[r] || o->base_pcre_feats[r]))
@@ -516,7 +523,10 @@ static int integrated_gradients_impl(cf_handle* h, const cf_batch* bt, const cf_
             const int nr = std::min(cap, B * V - g0);
             l0 = g_launches;
             ea.g0 = g0;
-            if (raw) {
+            if (donor) {
+                hipLaunchKernelGGL(k_ig_expand_raw_donor, dim3(nr, nres), dim3(kIgxThreads), 0, st, ea);
+                LAUNCH_CHECK("k_ig_expand_raw_donor");
+            } else if (raw) {
                 hipLaunchKernelGGL(k_ig_expand_raw, dim3(nr, nres), dim3(kIgxThreads), 0, st, ea);
                 LAUNCH_CHECK("k_ig_expand_raw");
             } else {
@@ -539,7 +549,11 @@ static int integrated_gradients_impl(cf_handle* h, const cf_batch* bt, const cf_
             aa.g0 = g0;
             aa.n = nr;
             const dim3 acc_grid((g0 + nr - 1) / V - g0 / V + 1, kIgSlices);
-            if (raw) {
+            if (donor) {
+                ra.a = aa;
+                hipLaunchKernelGGL(k_ig_accumulate_raw_donor, acc_grid, dim3(kIgxThreads), 0, st, ra);
+                LAUNCH_CHECK("k_ig_accumulate_raw_donor");
+            } else if (raw) {
                 ra.a = aa;
                 hipLaunchKernelGGL(k_ig_accumulate_raw, acc_grid, dim3(kIgxThreads), 0, st, ra);
                 LAUNCH_CHECK("k_ig_accumulate_raw");
@@ -567,14 +581,22 @@ static int integrated_gradients_impl(cf_handle* h, const cf_batch* bt, const cf_
 
 extern "C" int cf_integrated_gradients(cf_handle* h, const cf_batch* bt, const cf_ig_opts* o, const cf_input_grads* out,
                                        float* logits_x, float* logits_base, float* delta, void* stream) {
-    return integrated_gradients_impl(h, bt, o, out, nullptr, logits_x, logits_base, delta, stream, false, "cf_integrated_gradients");
+    return integrated_gradients_impl(h, bt, o, out, nullptr, logits_x, logits_base, delta, stream, kIgLinear, "cf_integrated_gradients");
 }
 
 // Integrated gradients along the zero-signal path a m in bin-mean space (cf_ig.h, kIgSignal): the launches of cf_integrated_gradients
 // with k_ig_expand_raw / k_ig_accumulate_raw in place of k_ig_expand / k_ig_accumulate.
 extern "C" int cf_integrated_gradients_raw(cf_handle* h, const cf_batch* bt, const cf_ig_opts* o, const cf_input_grads* out,
                                            const cf_input_grads* coeff, float* logits_x, float* logits_base, float* delta, void* stream) {
-    return integrated_gradients_impl(h, bt, o, out, coeff, logits_x, logits_base, delta, stream, true, "cf_integrated_gradients_raw");
+    return integrated_gradients_impl(h, bt, o, out, coeff, logits_x, logits_base, delta, stream, kIgSignal, "cf_integrated_gradients_raw");
+}
+
+// Integrated gradients along x(a) = xd + a (x - xd) between two raw signals, in bin-mean space (cf_ig.h, kIgSignalDonor): the launches of
+// cf_integrated_gradients_raw with k_ig_expand_raw_donor / k_ig_accumulate_raw_donor; the donor's features travel in opts->base_promoter_feats /
+// base_pcre_feats.
+extern "C" int cf_integrated_gradients_raw_donor(cf_handle* h, const cf_batch* bt, const cf_ig_opts* o, const cf_input_grads* out,
+                                                 const cf_input_grads* cmean, float* logits_x, float* logits_base, float* delta, void* stream) {
+    return integrated_gradients_impl(h, bt, o, out, cmean, logits_x, logits_base, delta, stream, kIgSignalDonor, "cf_integrated_gradients_raw_donor");
 }
 
 // What the two scan entry points check alike, in front of anything launched.  scan_check: the window, the mark sets, the scale, nested

@@ -266,6 +266,51 @@ extern "C" int cf_bin_regions_multi_backward(const cf_bin_grad_job* jobs, int n_
     return 0;
 }
 
+static_assert(sizeof(cf_bin_spread_job) == sizeof(BinSpreadJob) && sizeof(cf_bin_spread_job) == 88, "cf_bin_spread_job layout");
+extern "C" int cf_bin_spread_difference(const cf_bin_spread_job* jobs, int n_jobs, int n_feats, int n_res, const int* bin_sizes,
+                                        const int* n_bins_out, int max_cols, void* stream) {
+    if (!jobs || !bin_sizes || !n_bins_out) return fail("cf_bin_spread_difference: null argument");
+    if (n_jobs < 0 || n_jobs > 65535 || n_feats < 1 || n_feats > 64 || n_res < 1 || n_res > kBinMaxRes || max_cols < 0)
+        return fail("cf_bin_spread_difference: bad argument");
+    if (n_jobs == 0) return 0;
+    BinPlan pl;
+    memset(&pl, 0, sizeof pl);
+    pl.n_res = n_res;
+    pl.F = n_feats;
+    for (int r = 0; r < n_res; ++r) {
+        if (bin_sizes[r] < 1 || n_bins_out[r] < 1 || n_bins_out[r] > kBinMaxBins) return fail("cf_bin_spread_difference: bad bin size / bin count at resolution %d", r);
+        if (r && bin_sizes[r] >= bin_sizes[r - 1]) return fail("cf_bin_spread_difference: bin sizes must be listed coarsest first (%d after %d)", bin_sizes[r], bin_sizes[r - 1]);
+        pl.b[r] = bin_sizes[r];
+        pl.L[r] = n_bins_out[r];
+    }
+    {   // this call WRITES through the job table, as cf_bin_regions_multi_backward does: the table is read back and checked first
+        std::vector<cf_bin_spread_job> host((size_t)n_jobs);
+        if (hipMemcpyAsync(host.data(), jobs, sizeof(cf_bin_spread_job) * (size_t)n_jobs, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
+            hipStreamSynchronize((hipStream_t)stream) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail("cf_bin_spread_difference: the job table could not be read back (it must be a device array of n_jobs records)");
+        }
+        for (int k = 0; k < n_jobs; ++k) {
+            const cf_bin_spread_job& j = host[k];
+            if (j.ncols < 0 || j.ncols > max_cols) return fail("cf_bin_spread_difference: ncols = %d of job %d outside [0, max_cols = %d]", j.ncols, k, max_cols);
+            if (j.ld_out < j.ncols) return fail("cf_bin_spread_difference: ld_out = %lld < ncols = %d in job %d", j.ld_out, j.ncols, k);
+            if (j.ncols > 0 && (!j.raw || !j.draw)) return fail("cf_bin_spread_difference: null raw / draw in job %d", k);
+            if (j.ncols > 0 && (j.col0 < 0 || j.ld < (long long)j.col0 + j.ncols || (j.raw_donor && j.ld_donor < (long long)j.col0 + j.ncols)))
+                return fail("cf_bin_spread_difference: the window [%d, %d + %d) of job %d does not fit its rows (ld = %lld, ld_donor = %lld)", j.col0, j.col0,
+                            j.ncols, k, j.ld, j.ld_donor);
+        }
+    }
+    // a chunk of 4 samples lies in one bin of every resolution when the bin sizes nest and the finest is a multiple of 4
+    bool nested = (pl.b[n_res - 1] & 3) == 0;
+    for (int r = 0; r + 1 < n_res; ++r) nested = nested && pl.b[r] % pl.b[r + 1] == 0;
+    pl.nested = nested ? 1 : 0;
+    const int chunks = std::max(1, (max_cols + 3) / 4);
+    hipLaunchKernelGGL(k_bin_spread_diff, dim3((chunks + 255) / 256, n_jobs), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const BinSpreadJob*>(jobs), pl);
+    LAUNCH_CHECK("k_bin_spread_diff");
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------
 // dense (all rows) layer: projections -> attention core -> out-projection / LN / FFN / LN chain, and its backward
 // ------------------------------------------------------------------------------------

@@ -32,6 +32,19 @@
 //                                                               which divides by cnt (1 + m) and multiplies by the raw sample
 // interaction_freq keeps the straight path and its baseline.  Between a gene's chunks `out` holds the running C; the last row turns it
 // into attr (and writes coeff).  The row helpers ig_row / ig_acc are templates on the path; the linear kernels' code is unchanged.
+//
+// Donor path (cf_integrated_gradients_raw_donor; kIgSignalDonor, the kernels k_ig_expand_raw_donor / k_ig_accumulate_raw_donor).  The
+// baseline of the two feature segments is a second signal over the same regions, binned the same way: IgSeg::xb holds ud = log(1 + md).
+// The path is the straight line md + a (m - md) in MEAN space, which is the binned x(a) = xd + a (x - xd) because binning is linear:
+//     m = expm1f(u), md = expm1f(ud), d = m - md, mk = md + a_k d
+//     u_k   = log1pf(mk)                                        the row of node k (v = 0: u verbatim, v = 1: ud verbatim)
+//     C     = (g_0 / (1 + mk_0) + g_1 / (1 + mk_1)) + ...       fp32, k order; no contraction
+//     attr  = d C                                               complete: sums to F(x)[t] - F(xd)[t] up to the quadrature error
+//     cmean = C                                                 second output: what k_bin_spread_diff (cf_bin_spread.h) spreads over
+//                                                               the difference of the two raw signals
+// An element with the same bits in both has d = 0 and gets exactly 0.  With ud = 0: md = 0, d = m and mk = 0 + a m carries the bits
+// of a m, so rows, attr, logits and delta are those of the signal path.  The bodies ig_row_donor / ig_acc_donor are functions of
+// their own: no instruction of the kernels above moves.
 #pragma once
 
 namespace cf {
@@ -39,6 +52,7 @@ namespace cf {
 constexpr int kIgxThreads = kRowThreads;
 constexpr int kIgSegs = 2 * kMaxRes + 1;      // promoter_feats[r], pcre_feats[r], interaction_freq
 constexpr int kIgLinear = 0, kIgSignal = 1;   // path of a feature segment: xb + a (x - xb) | log1p(a expm1(x)) from the zero signal
+constexpr int kIgSignalDonor = 2;             // ... | log1p(md + a (m - md)), m = expm1(x), md = expm1(xb): from a donor signal
 
 struct IgSeg {
     const float* x;           // the caller's input, [B, len]
@@ -120,6 +134,63 @@ __device__ __forceinline__ void ig_expand(const IgExpandArgs a) {
 }
 __global__ __launch_bounds__(kIgxThreads) void k_ig_expand(IgExpandArgs a) { ig_expand<kIgLinear>(a); }
 __global__ __launch_bounds__(kIgxThreads) void k_ig_expand_raw(IgExpandArgs a) { ig_expand<kIgSignal>(a); }
+
+// the donor path's interior value of one element
+__device__ __forceinline__ float ig_signal_donor(float a, float x, float xd) {
+#pragma clang fp contract(off)
+    const float md = expm1f(xd);
+    const float d = expm1f(x) - md;
+    return log1pf(md + a * d);
+}
+
+// ig_row for kIgSignalDonor: dst = x (v = 0 or not interpolated), xb (v = 1: the donor's features verbatim) or log1p(md + a (m - md));
+// xb is per gene ([B, len], never broadcast) and is read only where the segment is interpolated
+__device__ __forceinline__ void ig_row_donor(const IgSeg& s, int b, int i, int v, float a) {
+#pragma clang fp contract(off)
+    const int n = s.len;
+    const float* __restrict__ x = s.x + (size_t)b * n;
+    const float* __restrict__ xb = s.out ? s.xb + (size_t)b * n : nullptr;
+    float* __restrict__ d = s.row + (size_t)i * n;
+    const int mode = !s.out || v == 0 ? 0 : v == 1 ? 1 : 2;
+    const bool vec = (n & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(xb) | reinterpret_cast<uintptr_t>(d)) & 15) == 0;
+    if (vec) {
+        const float4* x4 = reinterpret_cast<const float4*>(x);
+        const float4* b4 = reinterpret_cast<const float4*>(xb);
+        float4* d4 = reinterpret_cast<float4*>(d);
+        for (int e = threadIdx.x; e < n / 4; e += kIgxThreads) {
+            const float4 xv = x4[e];
+            float4 o = xv;
+            if (mode != 0) {
+                const float4 bv = b4[e];
+                o = mode == 1 ? bv
+                              : make_float4(ig_signal_donor(a, xv.x, bv.x), ig_signal_donor(a, xv.y, bv.y), ig_signal_donor(a, xv.z, bv.z),
+                                            ig_signal_donor(a, xv.w, bv.w));
+            }
+            d4[e] = o;
+        }
+    } else {
+        for (int e = threadIdx.x; e < n; e += kIgxThreads) {
+            const float xv = x[e];
+            d[e] = mode == 0 ? xv : mode == 1 ? xb[e] : ig_signal_donor(a, xv, xb[e]);
+        }
+    }
+}
+
+// k_ig_expand for the donor path: the feature segments by ig_row_donor, everything else as ig_expand (never frequency-only: a feature
+// bit is set)
+__global__ __launch_bounds__(kIgxThreads) void k_ig_expand_raw_donor(IgExpandArgs a) {
+    const int i = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
+    const int gv = a.g0 + i, b = gv / a.V, v = gv - b * a.V;
+    const float alpha = v >= 2 ? a.alpha[v - 2] : 0.f;
+    ig_row_donor(a.seg[r], b, i, v, alpha);
+    ig_row_donor(a.seg[kMaxRes + r], b, i, v, alpha);
+    rows_pad_masks(a.rows, r, b, i);
+    rows_interaction_mask(a.rows, r, b, i);
+    if (r == 0) {
+        ig_row<kIgLinear>(a.seg[2 * kMaxRes], b, i, v, alpha, a.bcast != 0);
+        for (int k = tid; k < a.n_out; k += kIgxThreads) a.dlogits[(size_t)i * a.n_out + k] = v >= 2 && k == a.target ? a.weight[v - 2] : 0.f;
+    }
+}
 
 constexpr int kIgSlices = 32;      // workgroups per gene in k_ig_accumulate (a gene's ~31.5 k elements: ~1 float4 per thread)
 
@@ -273,6 +344,95 @@ __global__ __launch_bounds__(kIgxThreads) void k_ig_accumulate_raw(IgAccRawArgs 
     const int v0 = max(vlo, 2), nv = vhi - v0;
     float part = 0.f;
     for (int s = 0; s < 2 * kMaxRes; ++s) part += ig_acc<kIgSignal>(a.seg[s], ra.coeff[s], ra.alpha, b, irow + v0, v0, nv, a.V, bc, slice);
+    part += ig_acc<kIgLinear>(a.seg[2 * kMaxRes], nullptr, nullptr, b, irow + v0, v0, nv, a.V, bc, slice);
+    if (vhi != a.V || nv <= 0) return;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) part += __shfl_xor(part, o, 64);
+    if ((tid & 63) == 0) red[tid >> 6] = part;
+    __syncthreads();
+    if (tid == 0) {
+        float sum = 0.f;
+        for (int k = 0; k < kIgxThreads / 64; ++k) sum += red[k];
+        a.part[(size_t)b * kIgSlices + slice] = sum;
+    }
+}
+
+// ig_acc for kIgSignalDonor: row k adds g_k / (1 + mk), mk = md + alpha[v0 - 2 + k] d; between a gene's chunks `out` holds the running
+// C; the last row writes C into cmean (where given) and d C into out
+__device__ __forceinline__ float ig_acc_donor(const IgSeg& s, float* cmean, const float* alpha, int b, int i0, int v0, int nv, int V, int slice) {
+#pragma clang fp contract(off)
+    if (!s.out || nv <= 0) return 0.f;
+    const int n = s.len;
+    const bool first = v0 == 2, last = v0 + nv == V;
+    const float* __restrict__ x = s.x + (size_t)b * n;
+    const float* __restrict__ xb = s.xb + (size_t)b * n;
+    const float* __restrict__ g = s.grad + (size_t)i0 * n;
+    float* __restrict__ o = s.out + (size_t)b * n;
+    float* __restrict__ co = cmean ? cmean + (size_t)b * n : nullptr;
+    float part = 0.f;
+    const int e0 = slice * kIgxThreads + threadIdx.x, step = kIgSlices * kIgxThreads;
+    const bool vec = (n & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(xb) | reinterpret_cast<uintptr_t>(g) |
+                                       reinterpret_cast<uintptr_t>(o) | reinterpret_cast<uintptr_t>(co)) & 15) == 0;
+    if (vec) {
+        const int n4 = n / 4;
+        for (int e = e0; e < n4; e += step) {
+            const float4 xv = reinterpret_cast<const float4*>(x)[e];
+            const float4 bv = reinterpret_cast<const float4*>(xb)[e];
+            const float4 md = make_float4(expm1f(bv.x), expm1f(bv.y), expm1f(bv.z), expm1f(bv.w));
+            const float4 d = make_float4(expm1f(xv.x) - md.x, expm1f(xv.y) - md.y, expm1f(xv.z) - md.z, expm1f(xv.w) - md.w);
+            float4 acc = first ? make_float4(0.f, 0.f, 0.f, 0.f) : reinterpret_cast<const float4*>(o)[e];
+            for (int k = 0; k < nv; ++k) {
+                const float4 gk = reinterpret_cast<const float4*>(g + (size_t)k * n)[e];
+                const float ak = alpha[v0 - 2 + k];
+                const float4 t = make_float4(gk.x / (1.0f + (md.x + ak * d.x)), gk.y / (1.0f + (md.y + ak * d.y)), gk.z / (1.0f + (md.z + ak * d.z)),
+                                             gk.w / (1.0f + (md.w + ak * d.w)));
+                acc = first && k == 0 ? t : make_float4(acc.x + t.x, acc.y + t.y, acc.z + t.z, acc.w + t.w);
+            }
+            if (last) {
+                if (co) reinterpret_cast<float4*>(co)[e] = acc;
+                acc = make_float4(d.x * acc.x, d.y * acc.y, d.z * acc.z, d.w * acc.w);
+                part += ((acc.x + acc.y) + acc.z) + acc.w;
+            }
+            reinterpret_cast<float4*>(o)[e] = acc;
+        }
+    } else {
+        for (int e = e0; e < n; e += step) {
+            const float md = expm1f(xb[e]);
+            const float d = expm1f(x[e]) - md;
+            float acc = first ? 0.f : o[e];
+            for (int k = 0; k < nv; ++k) {
+                const float t = g[(size_t)k * n + e] / (1.0f + (md + alpha[v0 - 2 + k] * d));
+                acc = first && k == 0 ? t : acc + t;
+            }
+            if (last) {
+                if (co) co[e] = acc;
+                acc = d * acc;
+                part += acc;
+            }
+            o[e] = acc;
+        }
+    }
+    return part;
+}
+
+// k_ig_accumulate for the donor path: the arguments of k_ig_accumulate_raw, `coeff` holding the cmean outputs; the feature segments by
+// ig_acc_donor, interaction_freq as in k_ig_accumulate
+__global__ __launch_bounds__(kIgxThreads) void k_ig_accumulate_raw_donor(IgAccRawArgs ra) {
+#pragma clang fp contract(off)
+    __shared__ float red[kIgxThreads / 64];
+    const IgAccArgs& a = ra.a;
+    const int b = a.g0 / a.V + blockIdx.x, slice = blockIdx.y, tid = threadIdx.x;
+    const int vlo = max(0, a.g0 - b * a.V), vhi = min(a.V, a.g0 + a.n - b * a.V);      // the gene's variants in this chunk: [vlo, vhi)
+    const int irow = b * a.V - a.g0;                                                     // chunk row of variant 0 (may be negative)
+    const bool bc = a.bcast != 0;
+    if (slice == 0)
+        for (int k = tid; k < a.n_out; k += kIgxThreads) {
+            if (vlo == 0) a.logits_x[(size_t)b * a.n_out + k] = a.logits[(size_t)irow * a.n_out + k];
+            if (vlo <= 1 && vhi > 1) a.logits_b[(size_t)b * a.n_out + k] = a.logits[(size_t)(irow + 1) * a.n_out + k];
+        }
+    const int v0 = max(vlo, 2), nv = vhi - v0;
+    float part = 0.f;
+    for (int s = 0; s < 2 * kMaxRes; ++s) part += ig_acc_donor(a.seg[s], ra.coeff[s], ra.alpha, b, irow + v0, v0, nv, a.V, slice);
     part += ig_acc<kIgLinear>(a.seg[2 * kMaxRes], nullptr, nullptr, b, irow + v0, v0, nv, a.V, bc, slice);
     if (vhi != a.V || nv <= 0) return;
 #pragma unroll

@@ -2523,6 +2523,7 @@ __global__ __launch_bounds__(256) void k_dense_cs_tables(DenseCsTab a) {
 #include "cf_attn.h"
 #include "cf_bin.h"
 #include "cf_bin_grad.h"
+#include "cf_bin_spread.h"
 #include "cf_embed_full.h"
 #if CF_TID_OPAQUE
 #undef threadIdx      // the opaque thread index is a property of the kernels above, not of whatever includes this header

@@ -149,6 +149,11 @@ BIN_GRAD_JOB = np.dtype([("raw", "<u8"), ("ld", "<i8"), ("col0", "<i4"), ("ncols
                          ("dfeat", "<u8", (3,)), ("draw", "<u8"), ("ld_out", "<i8")])
 
 
+#: layout of cf_bin_spread_job: the gene's and the donor's raw rows, cmean per resolution (coarsest first), the tracks and their row pitch
+BIN_SPREAD_JOB = np.dtype([("raw", "<u8"), ("ld", "<i8"), ("raw_donor", "<u8"), ("ld_donor", "<i8"), ("col0", "<i4"), ("ncols", "<i4"),
+                           ("flip", "<i4"), ("reserved", "<i4"), ("cmean", "<u8", (3,)), ("draw", "<u8"), ("ld_out", "<i8")])
+
+
 def promoter_col0(ds):
     """First sample of the promoter window inside its 40,000-sample file (data.py:106-107)."""
     col0 = 20000 - ds.w_prom // 2

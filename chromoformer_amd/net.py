@@ -559,7 +559,7 @@ class ChromoformerBase(nn.Module):
     @torch.no_grad()
     def integrated_gradients(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
                              interaction_freq=None, target=None, n_steps=50, method="gausslegendre", baselines=None,
-                             inputs=("promoter_feats", "pcre_feats", "interaction_freq"), path="linear"):
+                             inputs=("promoter_feats", "pcre_feats", "interaction_freq"), path="linear", donor=None):
         """Integrated gradients of logit column `target` (default: 1 for the classifier, 0 for the regressor) with respect to the float
         inputs named in `inputs` (cf_integrated_gradients) -> (attr, info), tensors on the model's device, no autograd graph:
 
@@ -581,12 +581,30 @@ class ChromoformerBase(nn.Module):
         complete: delta as above), and info gains "coeff": {"promoter_feats": {b: ...}, "pcre_feats": {b: ...}} = (1 + m) * C, the dfeat
         that cf_bin_regions_multi_backward(times_input = 1) turns into per-sample attributions (attribution.raw_integrated_gradients).
         interaction_freq, if named, keeps its straight path and baseline.  `inputs` must name a feature input; a feature baseline
-        raises ValueError (zero signal only); features must stay below ~80 (expm1 in fp32)."""
+        raises ValueError (zero signal only); features must stay below ~80 (expm1 in fp32).
+
+        path="signal" with donor=(donor_promoter_feats, donor_pcre_feats) (cf_integrated_gradients_raw_donor): the baseline is the same
+        genes' binned signal in another cell type, in any form mark_donor_shapley's `donor` takes, and the path is the straight line
+        xd + a (x - xd) between the two RAW signals: with m, md the bin means of the two, u_k = log1p(md + a_k (m - md)),
+        C = sum_k g_k / (1 + md + a_k (m - md)), attr = (m - md) * C.  info["baseline_logits"] is the donor's features under the gene's
+        masks and frequencies, info["cmean"] (in place of "coeff") = C per bin, which cf_bin_spread_difference spreads over the
+        difference of the two raw signals.  An element with the same bits in both gets exactly 0; a donor of zeros gives the bits of
+        the call without donor.  donor= with path="linear", or together with a feature baseline, raises ValueError."""
         from .attribution import INPUTS, ig_quadrature
         if path not in ("linear", "signal"):
             raise ValueError("integrated_gradients: path %r; choose 'linear' or 'signal'" % (path,))
         signal = path == "signal"
-        if signal:      # (before anything touches the device)
+        if donor is not None:      # (before anything touches the device)
+            if not signal:
+                raise ValueError("integrated_gradients: donor= is the baseline of path='signal' (a path between two raw signals); "
+                                 "path='linear' takes feature baselines in baselines=")
+            given = [k for k in ("promoter_feats", "pcre_feats") if (baselines or {}).get(k) is not None]
+            if given:
+                raise ValueError("integrated_gradients: donor= and a baseline for %s: the donor is the feature baseline" % given)
+            named = (inputs,) if isinstance(inputs, str) else tuple(inputs)
+            if not set(named) & {"promoter_feats", "pcre_feats"}:
+                raise ValueError("integrated_gradients: path='signal' needs promoter_feats or pcre_feats in inputs, got %s" % (named,))
+        elif signal:
             named = (inputs,) if isinstance(inputs, str) else tuple(inputs)
             given = [k for k in ("promoter_feats", "pcre_feats") if (baselines or {}).get(k) is not None]
             if given:
@@ -648,6 +666,16 @@ class ChromoformerBase(nn.Module):
         if "interaction_freq" in inputs and baselines.get("interaction_freq") is not None:
             opts.base_interaction_freq = base(baselines["interaction_freq"], canon["interaction_freq"])
         opts.base_broadcast = 1 if bcast else 0
+        if donor is not None:
+            if bcast:
+                raise ValueError("integrated_gradients: donor= holds one row per gene; a broadcast baseline (leading dimension 1) cannot go with it")
+            dn = _lib.cf_mark_donor_opts()
+            keep.append(self._donor_feats("integrated_gradients", donor, B, dn))
+            for r in range(len(self.binsizes)):
+                if "promoter_feats" in inputs:
+                    opts.base_promoter_feats[r] = dn.donor_promoter_feats[r]
+                if "pcre_feats" in inputs:
+                    opts.base_pcre_feats[r] = dn.donor_pcre_feats[r]
         out = _lib.cf_input_grads()
         attr = {}
         for r, b in enumerate(self.binsizes):
@@ -665,21 +693,27 @@ class ChromoformerBase(nn.Module):
         info = {"logits": lx, "baseline_logits": lb, "delta": delta}
         if signal:
             co = _lib.cf_input_grads()
-            coeff = info["coeff"] = {}
+            second = "cmean" if donor is not None else "coeff"
+            coeff = info[second] = {}
             for r, b in enumerate(self.binsizes):
                 for k, field in (("promoter_feats", co.promoter_feats), ("pcre_feats", co.pcre_feats)):
                     if k in inputs:
                         t = coeff.setdefault(k, {})[b] = torch.empty(canon[k][b], device=dev)      # (written in full by the library)
                         field[r] = t.data_ptr()
-            _lib.check(_lib.lib().cf_integrated_gradients_raw(self._handle, C.byref(bs), C.byref(opts), C.byref(out), C.byref(co), lx.data_ptr(),
-                                                              lb.data_ptr(), delta.data_ptr(), st), "cf_integrated_gradients_raw")
+            if donor is not None:
+                _lib.check(_lib.lib().cf_integrated_gradients_raw_donor(self._handle, C.byref(bs), C.byref(opts), C.byref(out), C.byref(co),
+                                                                        lx.data_ptr(), lb.data_ptr(), delta.data_ptr(), st),
+                           "cf_integrated_gradients_raw_donor")
+            else:
+                _lib.check(_lib.lib().cf_integrated_gradients_raw(self._handle, C.byref(bs), C.byref(opts), C.byref(out), C.byref(co), lx.data_ptr(),
+                                                                  lb.data_ptr(), delta.data_ptr(), st), "cf_integrated_gradients_raw")
         else:
             _lib.check(_lib.lib().cf_integrated_gradients(self._handle, C.byref(bs), C.byref(opts), C.byref(out), lx.data_ptr(), lb.data_ptr(),
                                                           delta.data_ptr(), st), "cf_integrated_gradients")
         if shapes is not None:
             attr = {k: ({b: t.view(shapes[k][b]) for b, t in v.items()} if isinstance(v, dict) else v.view(shapes[k])) for k, v in attr.items()}
             if signal:
-                info["coeff"] = {k: {b: t.view(shapes[k][b]) for b, t in v.items()} for k, v in info["coeff"].items()}
+                info[second] = {k: {b: t.view(shapes[k][b]) for b, t in v.items()} for k, v in info[second].items()}
         return attr, info
 
     def _scan_mark_bits(self, who, mark_sets):
@@ -1217,13 +1251,15 @@ class ChromoformerBase(nn.Module):
         from .attribution import raw_signal_gradients
         return raw_signal_gradients(self, dataset, genes=genes, target=target, times_input=times_input, bsz=bsz)
 
-    def raw_integrated_gradients(self, dataset, genes=None, target=None, n_steps=50, method="gausslegendre", bsz=None):
+    def raw_integrated_gradients(self, dataset, genes=None, target=None, n_steps=50, method="gausslegendre", bsz=None, donor_dataset=None):
         """Integrated gradients of logit column `target` with respect to the raw fp16 signals of the genes of a ChromoformerDataset, from
         the zero signal along a * x: per gene one track per histone mark for the promoter window and every pCRE, in genomic
-        orientation, summing to logits - baseline_logits up to the quadrature error
+        orientation, summing to logits - baseline_logits up to the quadrature error.  donor_dataset: another cell type's dataset over
+        the same regions; the baseline is then its signal xd and the path xd + a * (x - xd)
         (chromoformer_amd.attribution.raw_integrated_gradients, a generator of per-gene dicts)."""
         from .attribution import raw_integrated_gradients
-        return raw_integrated_gradients(self, dataset, genes=genes, target=target, n_steps=n_steps, method=method, bsz=bsz)
+        return raw_integrated_gradients(self, dataset, genes=genes, target=target, n_steps=n_steps, method=method, bsz=bsz,
+                                        donor_dataset=donor_dataset)
 
     @torch.no_grad()
     def trunk_outputs(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,

@@ -450,17 +450,22 @@ def write_raw_saliency(model, dataset, bsz, saliency_dir, target=None, times_inp
         np.savez(os.path.join(saliency_dir, "%s.npz" % d["gene_id"]), **arrays)
 
 
-def write_raw_integrated_gradients(model, dataset, bsz, ig_dir, n_steps=50, method="gausslegendre", target=None):
+def write_raw_integrated_gradients(model, dataset, bsz, ig_dir, n_steps=50, method="gausslegendre", target=None, donor_dataset=None):
     """Integrated gradients in raw-signal space of every gene of a dataset (model.raw_integrated_gradients: zero-signal baseline, path
     a * x) into `ig_dir`/<gene_id>.npz: the keys of write_raw_saliency (`promoter`, `pcre_<s>`, `regions`, `logits`; the tracks hold
     the per-sample attributions) plus `baseline_logits` [n_out] and `delta` (the tracks' sum minus logits - baseline_logits at the
-    target: the quadrature error)."""
+    target: the quadrature error).  With donor_dataset the baseline is that cell type's signal over the same regions (path
+    xd + a (x - xd)) and every file also holds `donor_prediction` [n_out], the donor dataset's own forward of the gene."""
     import os
     os.makedirs(ig_dir, exist_ok=True)
     require_raw_signals(dataset)
-    for d in model.raw_integrated_gradients(dataset, target=target, n_steps=n_steps, method=method, bsz=bsz):
+    if donor_dataset is not None:
+        require_raw_signals(donor_dataset)
+    for d in model.raw_integrated_gradients(dataset, target=target, n_steps=n_steps, method=method, bsz=bsz, donor_dataset=donor_dataset):
         arrays = {"promoter": d["promoter"], "logits": d["logits"], "baseline_logits": d["baseline_logits"], "delta": d["delta"],
                   "regions": np.array(["%s:%d-%d" % tuple(r) for r in d["regions"]])}
+        if donor_dataset is not None:
+            arrays["donor_prediction"] = d["donor_prediction"]
         for s, t in enumerate(d["pcres"]):
             arrays["pcre_%d" % s] = t
         np.savez(os.path.join(ig_dir, "%s.npz" % d["gene_id"]), **arrays)
@@ -474,7 +479,7 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
             mark_players="marks", mark_scale=0.0, donor_npy_dir=None, donor_meta=None, donor_store_path=None, mark_donor_shapley_out=None,
             mark_donor_epistasis_out=None, mark_sampled_shapley_out=None, mark_donor_sampled_shapley_out=None, mark_sampled_players="cells",
             mark_perms=64, mark_seed=0, window_shapley_out=None, window_donor_shapley_out=None, window_players="promoter", window_width=1,
-            window_perms=64, window_seed=0, window_scale=0.0):
+            window_perms=64, window_seed=0, window_scale=0.0, raw_donor_ig_dir=None):
     """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file.  attention_dir / embeddings_out: also
     write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps); pcre_ablation_out:
     the predictions with each pCRE deleted (write_pcre_ablation); ig_dir: integrated gradients of every gene
@@ -493,16 +498,26 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     (write_mark_sampled_values; mark_sampled_players, mark_perms and mark_seed apply); window_shapley_out /
     window_donor_shapley_out: Shapley values of window players -- stretches of the promoter or of every region -- under the scale
     rule (window_scale applies) / against the donor, exact with at most 16 players and sampled otherwise (write_mark_window_values;
-    window_players, window_width, window_perms and window_seed apply)."""
+    window_players, window_width, window_perms and window_seed apply); raw_donor_ig_dir: integrated gradients with respect to the raw
+    signals against the donor cell type's signals of donor_npy_dir, one .npz per gene (write_raw_integrated_gradients with the donor's
+    dataset; ig_steps, ig_method and ig_target apply; needs the raw .npy files of both cell types)."""
     seed_everything(seed)
     meta = pd.read_csv(meta_path)
     genes = meta.gene_id.tolist()
     raw_ds = None
-    if raw_saliency_dir or raw_ig_dir:
+    if raw_saliency_dir or raw_ig_dir or raw_donor_ig_dir:
         raw_ds = ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=regression)
         require_raw_signals(raw_ds)      # (before anything is computed)
     from . import pack
     donor_out = mark_donor_shapley_out or mark_donor_epistasis_out or mark_donor_sampled_shapley_out or window_donor_shapley_out
+    raw_donor_ds = None
+    if raw_donor_ig_dir:      # (before anything is computed)
+        from .attribution import same_regions
+        if not donor_npy_dir:
+            raise ValueError("predict: raw_donor_ig_dir needs donor_npy_dir")
+        raw_donor_ds = ChromoformerDataset(donor_meta or meta_path, donor_npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=regression)
+        require_raw_signals(raw_donor_ds)
+        same_regions(raw_ds, raw_donor_ds)
     window_ds = None
     if window_shapley_out or window_donor_shapley_out:      # (strand and coordinates; refusals before anything is computed)
         from .attribution import window_players as window_game
@@ -567,6 +582,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         write_raw_saliency(model, raw_ds, bsz, raw_saliency_dir, raw_saliency_target, raw_saliency_times_input)
     if raw_ig_dir:
         write_raw_integrated_gradients(model, raw_ds, bsz, raw_ig_dir, ig_steps, ig_method, ig_target)
+    if raw_donor_ig_dir:
+        write_raw_integrated_gradients(model, raw_ds, bsz, raw_donor_ig_dir, ig_steps, ig_method, ig_target, donor_dataset=raw_donor_ds)
     return meta, np.concatenate(preds).astype(np.float32)
 
 
@@ -626,6 +643,11 @@ def build_parser():
                     "each mark in every region (marks, the default), each mark in the promoter and in the pCREs (compartments), or all marks "
                     "per region (regions)")
     ap.add_argument("--mark-scale", type=float, default=None, help="what an absent mark's raw signal is scaled by: 0 erases it (default)")
+    ap.add_argument("--raw-donor-ig-dir", default=None, help="also write integrated gradients in raw-signal space against the DONOR cell type of "
+                    "--donor-npy-dir (path xd + a * (x - xd) between the two raw signals): DIR/<gene_id>.npz with the keys of --raw-ig-dir plus "
+                    "donor_prediction; baseline_logits is the donor's signal under the gene's masks and frequencies "
+                    "(model.raw_integrated_gradients(donor_dataset=...)).  Takes --ig-steps, --ig-method and --ig-target; needs the raw .npy "
+                    "files of both cell types")
     ap.add_argument("--donor-npy-dir", default=None, help="directory of the .npy histone signals of a DONOR cell type over the same regions: "
                     "what an absent mark becomes in --mark-donor-shapley-out / --mark-donor-epistasis-out")
     ap.add_argument("--donor-meta", default=None, help="metadata file of the donor cell type (default: --meta); TSS, strand and pCREs of every "
@@ -677,8 +699,9 @@ def main(argv=None):
         ap.error("--raw-saliency-target / --raw-saliency-times-input need --raw-saliency-dir")
     if args.raw_saliency_target is not None and not 0 <= args.raw_saliency_target < (1 if args.regression else 2):
         ap.error("--raw-saliency-target must be in [0, %d)" % (1 if args.regression else 2))
-    if not args.ig_dir and not args.raw_ig_dir and (args.ig_steps is not None or args.ig_method is not None or args.ig_target is not None):
-        ap.error("--ig-steps / --ig-method / --ig-target need --ig-dir or --raw-ig-dir")
+    if not args.ig_dir and not args.raw_ig_dir and not args.raw_donor_ig_dir and (args.ig_steps is not None or args.ig_method is not None
+                                                                                  or args.ig_target is not None):
+        ap.error("--ig-steps / --ig-method / --ig-target need --ig-dir or --raw-ig-dir (or --raw-donor-ig-dir)")
     if args.ig_steps is not None and args.ig_steps < (2 if args.ig_method == "riemann_trapezoid" else 1):
         ap.error("--ig-steps must be at least %d" % (2 if args.ig_method == "riemann_trapezoid" else 1))
     if args.ig_target is not None and not 0 <= args.ig_target < (1 if args.regression else 2):
@@ -691,11 +714,15 @@ def main(argv=None):
         ap.error("--scan-width must be at least 1")
     donor_exact = args.mark_donor_shapley_out or args.mark_donor_epistasis_out
     donor_out = donor_exact or args.mark_donor_sampled_shapley_out or args.window_donor_shapley_out
+    if args.raw_donor_ig_dir and not args.donor_npy_dir:
+        ap.error("--raw-donor-ig-dir needs --donor-npy-dir")
+    if args.raw_donor_ig_dir and args.donor_store:
+        ap.error("--raw-donor-ig-dir reads the donor's raw .npy signals; --donor-store does not serve it")
     sampled_out = args.mark_sampled_shapley_out or args.mark_donor_sampled_shapley_out
     if donor_out and not args.donor_npy_dir:
         ap.error("--mark-donor-shapley-out / --mark-donor-epistasis-out / --mark-donor-sampled-shapley-out / --window-donor-shapley-out need "
                  "--donor-npy-dir")
-    if not donor_out and (args.donor_npy_dir or args.donor_meta or args.donor_store):
+    if not donor_out and not args.raw_donor_ig_dir and (args.donor_npy_dir or args.donor_meta or args.donor_store):
         ap.error("--donor-npy-dir / --donor-meta / --donor-store need --mark-donor-shapley-out, --mark-donor-epistasis-out or "
                  "--mark-donor-sampled-shapley-out (or --window-donor-shapley-out)")
     if not sampled_out and (args.mark_sampled_players is not None or args.mark_perms is not None or args.mark_seed is not None):
@@ -746,7 +773,7 @@ def main(argv=None):
                          window_width=1 if args.window_width is None else args.window_width,
                          window_perms=64 if args.window_perms is None else args.window_perms,
                          window_seed=0 if args.window_seed is None else args.window_seed,
-                         window_scale=0.0 if args.window_scale is None else args.window_scale)
+                         window_scale=0.0 if args.window_scale is None else args.window_scale, raw_donor_ig_dir=args.raw_donor_ig_dir)
     print("Predicting expressions for %d genes." % len(meta))
     meta["prediction"] = pred
     meta.to_csv(args.output, index=False)

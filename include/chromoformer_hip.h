@@ -296,13 +296,35 @@ int cf_integrated_gradients(cf_handle* h, const cf_batch* batch, const cf_ig_opt
  *                                   multiplies by the sample: IG_raw[f, s] = x[f, s] sum_r C_r[p_r(s), f] / cnt, every bin's attr
  *                                   spread over its samples in proportion to x
  * `coeff` may be NULL, or have any of the feature fields of the interpolated inputs set (each OVERWRITTEN in full; exact zeros for
- * padded bins and dummy slots, as in `out`).  Limits: the zero-signal baseline only; u < ~80 (expm1f overflows past 88); 1 + a m <= 0
+ * padded bins and dummy slots, as in `out`).  Limits: the zero-signal baseline only (a donor cell type's signal as the baseline:
+ * cf_integrated_gradients_raw_donor below); u < ~80 (expm1f overflows past 88); 1 + a m <= 0
  * gives inf / NaN as the forward's log does.  Deterministic; the result does not depend on max_batch.
  * Refused by name, before anything is launched: everything cf_integrated_gradients refuses; a non-NULL base_promoter_feats /
  * base_pcre_feats; an `interpolate` without CF_IG_PROMOTER or CF_IG_PCRE; a coeff field set for an input that is not interpolated;
  * a non-NULL coeff->interaction_freq. */
 int cf_integrated_gradients_raw(cf_handle* h, const cf_batch* batch, const cf_ig_opts* opts, const cf_input_grads* out,
                                 const cf_input_grads* coeff, float* logits_x, float* logits_base, float* delta, void* stream);
+/* Integrated gradients in raw-signal space against a donor cell type (interpretation).  The path is x(a) = xd + a (x - xd) between two
+ * raw signals over the same regions; binning is linear, so a bin with means m (gene) and md (donor) has the mean md + a (m - md) along
+ * it.  The donor's binned features ud = log(1 + md) travel in opts->base_promoter_feats / base_pcre_feats ([B, ...], the layout of
+ * the inputs, one row per gene).  Rows, chunks, buffers and launches of cf_integrated_gradients_raw, with k_ig_expand_raw_donor /
+ * k_ig_accumulate_raw_donor.  Per element of an interpolated feature input, fp32, each operation rounded:
+ *   m = expm1f(u)   md = expm1f(ud)   d = m - md   mk = md + a_k d
+ *   u_k   = log1pf(mk)                                 the row of node k; F(x) runs on u verbatim, F(xd) on ud verbatim
+ *   g_k   = d(w_k logits[:, t]) / d u_k
+ *   C     = (g_0 / (1 + mk_0) + g_1 / (1 + mk_1)) + ...     in k order
+ *   attr  = d C           -> out:   complete: the attr of a gene (plus those of interaction_freq, which keeps its straight path and
+ *                                   baseline) sum to F(x)[t] - F(xd)[t] up to the quadrature error; delta is that sum minus the difference
+ *   cmean = C             -> cmean: per bin, what cf_bin_spread_difference spreads over the difference of the two raw signals
+ * logits_base is the donor's features under the batch's masks and frequencies.  An element with the same bits in both cell types
+ * (a padded row, a dummy slot, an unchanged mark) gets exactly 0; a donor of zeros gives the bits of cf_integrated_gradients_raw
+ * in out, logits_x, logits_base and delta.  `cmean` as `coeff` above.  Limits: u, ud < ~80; 1 + mk <= 0 gives inf / NaN.
+ * Deterministic; the result does not depend on max_batch.
+ * Refused by name, before anything is launched: everything cf_integrated_gradients_raw refuses except the feature baseline; a NULL
+ * base_promoter_feats / base_pcre_feats[r] of an interpolated feature input; base_broadcast != 0; a cmean field set for an input that
+ * is not interpolated; a non-NULL cmean->interaction_freq. */
+int cf_integrated_gradients_raw_donor(cf_handle* h, const cf_batch* batch, const cf_ig_opts* opts, const cf_input_grads* out,
+                                      const cf_input_grads* cmean, float* logits_x, float* logits_base, float* delta, void* stream);
 /* In-silico perturbation scan (interpretation): what would the prediction be if the marks of a mark set were scaled by s -- erased
  * (s = 0), doubled (s = 2) -- over a window of the promoter or of one pCRE?  The perturbation is defined in RAW-SIGNAL space and is
  * exact there: binning is linear, so scaling the window's samples by s scales the means of its bins by s, and a covered feature
@@ -738,6 +760,26 @@ typedef struct cf_bin_grad_job {
 } cf_bin_grad_job;                  /* 72 bytes */
 int cf_bin_regions_multi_backward(const cf_bin_grad_job* jobs, int n_jobs, int n_feats, int n_res, const int* bin_sizes,
                                   const int* n_bins_out, int max_cols, int times_input, void* stream);
+/* Per-bin integrated gradients spread over the difference of two raw signals (k_bin_spread_diff).  With cmean[r][p, f] = C of
+ * cf_integrated_gradients_raw_donor in the layout of out[r] of the forward job, g_r(s) = s / b_r, p_r the centred (mirrored if `flip`)
+ * row of bin g_r and cnt_r = min((g_r + 1) b_r, ncols) - g_r b_r its sample count,
+ *     draw[f, s] = (x[f, col0 + s] - xd[f, col0 + s]) * ((C_0[p_0(s), f] / cnt_0 + C_1[p_1(s), f] / cnt_1) + C_2[p_2(s), f] / cnt_2)
+ * coarsest resolution first, fp32, every operation rounded; the shares of a bin's samples sum to its attr.  Raw (genomic)
+ * orientation, window-relative.  A sample past the last real bin of a resolution gets nothing from it.  Exactly the elements
+ * draw[f * ld_out + s], s < ncols, are written, each once: no atomics, bit-reproducible.  Nested bin sizes (the finest a multiple of
+ * 4) with 8-byte aligned rows of both signals, a 16-byte aligned draw and ld_out % 4 == 0 move 4 bytes in and 4 bytes out per
+ * sample with 16-byte stores; anything else takes a per-sample walk inside the same launch.  `jobs` is a DEVICE array; the other
+ * arguments as the backward's.  Refused: ld_out < ncols, ncols > max_cols, a window that does not fit its rows, null raw / draw (the
+ * job table is read back for that: the call synchronises `stream`). */
+typedef struct cf_bin_spread_job {
+    const void* raw;        long long ld;          /* gene's fp16 [n_feats, ld]                                 */
+    const void* raw_donor;  long long ld_donor;    /* donor's, same col0 / ncols; NULL: the zero signal         */
+    int col0, ncols, flip, reserved;
+    const float* cmean[3];                         /* [n_bins_out[r], n_feats], coarsest first; NULL counts as 0 */
+    float* draw;            long long ld_out;
+} cf_bin_spread_job;                               /* 88 bytes */
+int cf_bin_spread_difference(const cf_bin_spread_job* jobs, int n_jobs, int n_feats, int n_res, const int* bin_sizes,
+                             const int* n_bins_out, int max_cols, void* stream);
 
 /* ---- resident split, batch gather inside the step graph --------------------------------- */
 /* The binned genes of a split, resident in HBM (what chromoformer_amd.data.GeneStore builds with cf_bin_regions):
