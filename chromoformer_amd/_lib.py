@@ -96,6 +96,12 @@ class cf_scan_regions_opts(C.Structure):
                 ("flip", C.c_void_p)]
 
 
+class cf_scan_fine_opts(C.Structure):
+    _fields_ = [("region", C.c_int), ("n_sets", C.c_int), ("mark_sets", C.c_void_p), ("scale", C.c_float), ("flip", C.c_void_p),
+                ("width", C.c_int), ("stride", C.c_int), ("n_windows", C.c_int), ("start", C.c_void_p), ("lengths", C.c_void_p),
+                ("feats_out", C.c_void_p * MAX_RES)]
+
+
 class cf_mark_opts(C.Structure):
     _fields_ = [("n_players", C.c_int), ("player_marks", C.c_void_p), ("player_regions", C.c_void_p), ("scale", C.c_float)]
 
@@ -176,6 +182,7 @@ SYMBOLS = {
                                                     C.POINTER(cf_input_grads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_perturbation_scan": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_scan_opts), C.c_void_p, C.c_void_p]),
     "cf_perturbation_scan_regions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_scan_regions_opts), C.c_void_p, C.c_void_p]),
+    "cf_perturbation_scan_fine": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_scan_fine_opts), C.c_void_p, C.c_void_p]),
     "cf_mark_coalitions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_opts), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "cf_mark_shapley": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_opts), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_mark_epistasis": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_opts), C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -710,6 +710,122 @@ def perturbation_scan(model, dataset, genes=None, regions="promoter", scale=0.0,
             yield p
 
 
+def fine_scan_windows(chrom, start, end, binsize, first, width, stride, n_win):
+    """Genomic windows of a fine scan of the region [start, end): window g begins at start + (first + g * stride) * binsize and spans
+    `width` finest bins, its end clipped to the region; only windows that begin inside the region -> [(chrom, start, end)]."""
+    out = []
+    for g in range(int(n_win)):
+        lo = int(start) + (int(first) + g * int(stride)) * int(binsize)
+        if lo >= end:
+            break
+        out.append((chrom, lo, min(lo + int(width) * int(binsize), int(end))))
+    return out
+
+
+def perturbation_scan_fine(model, dataset, genes=None, region="promoter", zoom=None, scale=0.0, width=1, stride=None, mark_sets=None,
+                           target=None, bsz=None, store=None):
+    """Fine-resolution perturbation scan of the genes of a ChromoformerDataset (model.perturbation_scan_fine per batch, windows in
+    genomic coordinates): what the prediction becomes with the marks of a mark set scaled by `scale` in raw-signal space over each
+    window of `width` FINEST bins of one region, windows `stride` (default: width) finest bins apart.  A generator over `genes` (ids;
+    default: the dataset's) in chunks of at most min(bsz, model.max_batch) genes; per gene it yields a dict:
+
+        gene_id    the id
+        logits     float32 [n_out]: the unperturbed prediction
+        mark_sets  the sets, tuples of mark indices (default: each mark alone, then all together)
+        region     (chrom, start, end) of the scanned region, None if the gene does not have it (windows and scan are then empty)
+        windows    [(chrom, start, end)]: each window in genomic coordinates, the end clipped to the region
+        scan       float32 [n_sets, n_win, n_out]: the logits with set k scaled over window g, in the order of `windows`
+
+    region: "promoter" or a pCRE slot j (an int).  zoom = None scans the whole region.  zoom = k first runs the coarse scan
+    (model.perturbation_scan, width 1) and fine-scans, per gene, the k coarse windows in which some mark set moves logit `target`
+    (default: the last) the most -- one model.perturbation_scan_fine per rank, each gene at its own start; `windows` / `scan` then hold the
+    fine windows of rank 0, then of rank 1, ..., and the dict also carries
+
+        zoom           int64 [k']: the chosen coarse windows, most important first (k' = min(k, the region's real coarse windows))
+        coarse_windows [(chrom, start, end)] and coarse_scan float32 [n_sets, n_cwin, n_out]: the coarse scan
+
+    Strand and the region's length come from the dataset's metadata: '-' strand promoters are stored mirrored (window 0 is still the
+    genomic start), and the short last bin of a pCRE is weighted by the samples it holds.  Features, parameters and the effect on a
+    pending backward: as perturbation_scan."""
+    from .data import promoter_col0
+    who = "perturbation_scan_fine"
+    ds = dataset
+    binsizes = [int(b) for b in ds.binsizes]
+    n_bins = _geometry_check(who, model, ds, binsizes)
+    genes, chunk = _genes_check(who, model, ds, genes, bsz)
+    S, F, dev = ds.i_max, ds.n_feats, model._device
+    if region == "promoter":
+        region = 0
+    elif isinstance(region, str) or not 0 <= int(region) < S:
+        raise ValueError("%s: region %r; choose 'promoter' or a pCRE slot in [0, i_max = %d)" % (who, region, S))
+    else:
+        region = 1 + int(region)
+    mark_sets = scan_mark_sets(mark_sets, F)
+    K = len(mark_sets)
+    width = int(width)
+    stride = width if stride is None else int(stride)
+    if width < 1 or stride < 1:
+        raise ValueError("%s: width = %d, stride = %d: at least 1 finest bin each" % (who, width, stride))
+    if zoom is not None and int(zoom) < 1:
+        raise ValueError("%s: zoom = %r: at least 1 coarse window, or None" % (who, zoom))
+    rf, rc = int(np.argmin(binsizes)), int(np.argmin(n_bins))
+    Lf, bf, W, bc = n_bins[rf], binsizes[rf], n_bins[rc], binsizes[rc]
+    Rc = Lf // W
+    target = model.n_out - 1 if target is None else int(target)
+    col0 = promoter_col0(ds)
+    store = _resident_store(who, ds, genes, binsizes, dev, store)
+    for lo in range(0, len(genes), chunk):
+        ids = genes[lo:lo + chunk]
+        B = len(ids)
+        d = store.batch(list(range(lo, lo + B)))
+        args = tuple(d[k] for k in ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq"))
+        flip = [region == 0 and ds.genes[g]["tss"][2] != "+" for g in ids]
+        regs = []
+        for g in ids:
+            if region == 0:
+                chrom, tss, _ = ds.genes[g]["tss"]
+                regs.append((chrom, tss - 20000 + col0, tss - 20000 + col0 + min(ds.w_prom, 40000 - col0)))
+            else:
+                pc = ds.genes[g]["pcres"]
+                regs.append(tuple(pc[region - 1]) if region - 1 < len(pc) else None)
+        lengths = [r[2] - r[1] if r else 0 for r in regs]
+        kw = dict(region=region, scale=scale, width=width, stride=stride, mark_sets=mark_sets, lengths=lengths, flip=flip)
+        per = [dict(gene_id=g, logits=None, mark_sets=list(mark_sets), region=regs[i], windows=[], scan=np.zeros((K, 0, model.n_out), np.float32))
+               for i, g in enumerate(ids)]
+        if zoom is None:
+            n_win = -(-Lf // stride)
+            out = model.perturbation_scan_fine(*args, n_windows=n_win, **kw).cpu().numpy()
+            for i, r in enumerate(regs):
+                per[i]["logits"] = out[i, 0].copy()
+                if r:
+                    per[i]["windows"] = fine_scan_windows(r[0], r[1], r[2], bf, 0, width, stride, n_win)
+                    per[i]["scan"] = out[i, 1:].reshape(K, n_win, -1)[:, :len(per[i]["windows"])].copy()
+        else:
+            coarse = model.perturbation_scan(*args, region=region, scale=scale, width=1, mark_sets=mark_sets, flip=flip).cpu().numpy()
+            ranks = []
+            for i, r in enumerate(regs):
+                per[i]["logits"] = coarse[i, 0].copy()
+                n_cw = -(-(r[2] - r[1]) // bc) if r else 0
+                cs = coarse[i, 1:].reshape(K, W, -1)[:, :n_cw]
+                moved = np.abs(cs[..., target] - coarse[i, 0, target]).max(axis=0) if n_cw else np.zeros(0)
+                ranks.append(np.argsort(-moved, kind="stable")[:int(zoom)].astype(np.int64))
+                per[i]["zoom"] = ranks[i]
+                per[i]["coarse_windows"] = [(r[0], int(a), int(b)) for a, b in scan_windows(r[1], r[2], bc, 1, n_cw)] if r else []
+                per[i]["coarse_scan"] = cs.copy()
+            n_win = -(-Rc // stride)
+            for rank in range(max([len(z) for z in ranks] + [0])):
+                # a gene with fewer real coarse windows than ranks starts past its region: the baseline's rows, left out below
+                start = [int(z[rank]) * Rc if rank < len(z) else Lf for z in ranks]
+                out = model.perturbation_scan_fine(*args, start=start, n_windows=n_win, **kw).cpu().numpy()
+                for i, r in enumerate(regs):
+                    if rank < len(ranks[i]):
+                        wins = fine_scan_windows(r[0], r[1], r[2], bf, start[i], width, stride, n_win)
+                        per[i]["windows"] += wins
+                        per[i]["scan"] = np.concatenate([per[i]["scan"], out[i, 1:].reshape(K, n_win, -1)[:, :len(wins)]], axis=1)
+        for p in per:
+            yield p
+
+
 def mark_shapley(model, dataset, genes=None, players="marks", scale=0.0, epistasis=False, bsz=None, store=None):
     """Exact Shapley values of the histone marks for the genes of a ChromoformerDataset (one model.mark_shapley per batch, with
     epistasis=True also one model.mark_epistasis): which marks carry the prediction when an absent mark's raw signal is scaled by

@@ -9,6 +9,7 @@
 #include "cf_coalition.h"
 #include "cf_ig.h"
 #include "cf_scan.h"
+#include "cf_scan_fine.h"
 #include "cf_marks.h"
 #include "cf_marks_wide.h"
 #include "cf_mark_windows.h"

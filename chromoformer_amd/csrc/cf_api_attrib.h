@@ -1,5 +1,5 @@
 // cf_api_attrib.h -- host side of the attribution entry points (input gradients, attention maps, pCRE deletion, pCRE coalitions, integrated
-// gradients, perturbation scan, histone-mark coalitions, their donor form, the wide game and its sampled Shapley values, the window game).  Part of cf_api.hip's single translation unit: included there behind cf_api_bwd.h, not on its own.
+// gradients, perturbation scan and its fine-resolution form, histone-mark coalitions, their donor form, the wide game and its sampled Shapley values, the window game).  Part of cf_api.hip's single translation unit: included there behind cf_api_bwd.h, not on its own.
 #pragma once
 
 // k_input_grad's dynamic LDS size; the first call sets the kernel's attribute.  0: that failed (`who`: the entry point, for the error text).
@@ -778,6 +778,103 @@ extern "C" int cf_perturbation_scan_regions(cf_handle* h, const cf_batch* bt, co
         so.region = region;
         so.flip = region == 0 ? o->flip : nullptr;      // (pCREs are never stored mirrored)
         rv = region == 0 || !packed ? scan_region_rows(h, bt, &so, rc, out, st) : scan_slot_packed(h, bt, o, region - 1, rc, out, st);
+    }
+    h->x0_fwd = false;
+    forward_counted(h, launches0);
+    return rv ? -1 : 0;
+}
+
+// Fine-resolution perturbation scan (cf_scan_fine.h): scan_region_rows with k_scan_fine_expand in the place of k_scan_expand.  The word
+// table of the workspace holds [mark sets | start | samples of the last real finest bin], uploaded here: no device buffer of its own.
+// With `lengths` the finest centre pad-mask rows of the scanned region are read back once (a copy, no launch) to check each length
+// against its gene's real bins.
+extern "C" int cf_perturbation_scan_fine(cf_handle* h, const cf_batch* bt, const cf_scan_fine_opts* o, float* logits, void* stream) {
+    const char* who = "cf_perturbation_scan_fine";
+    if (attrib_open(h, bt, true, who)) return -1;
+    if (!o) return fail("%s: null opts", who);
+    if (!logits) return fail("%s: null logits", who);
+    if (!o->mark_sets) return fail("%s: null mark_sets", who);
+    const cf_config& c = h->cfg;
+    const int nres = c.n_res, S = c.i_max, F = c.n_feats, cap = c.max_batch, B = bt->B, slot = o->region - 1;
+    if (o->region < 0 || o->region > S) return fail("%s: region = %d outside [0, i_max = %d]", who, o->region, S);
+    if (o->width < 1) return fail("%s: width = %d: at least 1 finest bin", who, o->width);
+    if (o->stride < 1) return fail("%s: stride = %d: at least 1 finest bin", who, o->stride);
+    if (o->n_windows < 1) return fail("%s: n_windows = %d: at least 1 window", who, o->n_windows);
+    int rc = 0;
+    if (scan_check(h, 1, o->n_sets, o->mark_sets, o->scale, who, &rc)) return -1;
+    int rf = 0;
+    for (int r = 1; r < nres; ++r)
+        if (c.binsizes[r] < c.binsizes[rf]) rf = r;
+    const int Lf = c.n_bins[rf], bf = c.binsizes[rf];
+    for (int r = 0; r < nres; ++r)
+        if (Lf % c.n_bins[r])
+            return fail("%s: n_bins[%d] = %d of the finest resolution is not a multiple of n_bins[%d] = %d", who, rf, Lf, r, c.n_bins[r]);
+    for (int r = nres; r < kMaxRes; ++r)
+        if (o->feats_out[r]) return fail("%s: feats_out[%d]: the model has %d resolutions", who, r, nres);
+    for (int b = 0; o->start && b < B; ++b)
+        if (o->start[b] < 0) return fail("%s: start[%d] = %d: a finest genomic bin >= 0", who, b, o->start[b]);
+    const long long rows = (long long)B * (1 + (long long)o->n_sets * o->n_windows);
+    if (rows > 0x7fffffffLL) return fail("%s: B * (1 + n_sets * n_windows) = %lld rows do not fit an int", who, rows);
+    hipStream_t st = (hipStream_t)stream;
+    const uint8_t* rm = slot < 0 ? bt->promoter_mask_row[rf] : bt->pcre_mask_row[rf] + (long long)slot * bt->pcre_mask_stride[rf];
+    const long long rm_stride = slot < 0 ? bt->promoter_mask_stride[rf] : (long long)S * bt->pcre_mask_stride[rf];
+    std::vector<unsigned> words(o->n_sets + 2 * (size_t)B);
+    memcpy(words.data(), o->mark_sets, o->n_sets * sizeof(unsigned));
+    for (int b = 0; b < B; ++b) words[o->n_sets + b] = o->start ? (unsigned)o->start[b] : 0u, words[o->n_sets + B + b] = (unsigned)bf;
+    if (o->lengths && B > 0) {
+        std::vector<uint8_t> m((size_t)B * Lf);
+        HIP_TRY(hipMemcpy2DAsync(m.data(), Lf, rm, (size_t)rm_stride, Lf, B, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (int b = 0; b < B; ++b) {
+            int lo = Lf, hi = 0;
+            for (int k = 0; k < Lf; ++k)
+                if (!m[(size_t)b * Lf + k]) lo = std::min(lo, k), hi = k + 1;
+            const long long nf = hi > lo ? hi - lo : 0, len = o->lengths[b];
+            if (!nf) continue;      // a dummy slot: nothing is scanned, the length is not read
+            if (len <= (nf - 1) * bf || len > nf * bf)
+                return fail("%s: lengths[%d] = %lld outside ((n_f - 1) b_f, n_f b_f] = (%lld, %lld]: the region has n_f = %lld real bins of b_f = %d samples",
+                            who, b, len, (nf - 1) * bf, nf * bf, nf, bf);
+            words[o->n_sets + B + b] = (unsigned)(len - (nf - 1) * bf);
+        }
+    }
+    if (attrib_ws(h, who) || h->aw.words.need(words.size(), 128, who)) return -1;
+    HIP_TRY(hipMemcpyAsync(h->aw.words, words.data(), words.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    const int V = (int)(rows / std::max(B, 1));
+    ScanFineExpandArgs ea;
+    memset(&ea, 0, sizeof ea);
+    cf_batch cb;      // the chunk's batch: the rows' copies
+    chunk_rows(h, bt, &ea.rows, &cb);
+    for (int r = 0; r < nres; ++r) {
+        ea.pf_in[r] = bt->promoter_feats[r];
+        ea.cf_in[r] = bt->pcre_feats[r];
+        ea.pf_out[r] = h->aw.row[r];
+        ea.cf_out[r] = h->aw.row[kMaxRes + r];
+        ea.feats_out[r] = o->feats_out[r];
+        if (slot < 0) {
+            ea.rm_in[r] = bt->promoter_mask_row[r];
+            ea.rm_stride[r] = bt->promoter_mask_stride[r];
+        } else {
+            ea.rm_in[r] = bt->pcre_mask_row[r] + (long long)slot * bt->pcre_mask_stride[r];
+            ea.rm_stride[r] = (long long)S * bt->pcre_mask_stride[r];
+        }
+    }
+    ea.freq_in = bt->interaction_freq;
+    ea.freq_out = h->aw.row[2 * kMaxRes];
+    ea.sets = h->aw.words;
+    ea.start = reinterpret_cast<const int*>((unsigned*)h->aw.words) + o->n_sets;
+    ea.cnt_last = ea.start + B;
+    ea.flip = o->flip;
+    ea.scale = o->scale;
+    ea.V = V, ea.F = F, ea.NW = o->n_windows, ea.width = o->width, ea.stride = o->stride, ea.rf = rf, ea.bf = bf, ea.region = o->region;
+    const long long launches0 = g_launches;
+    int rv = 0;
+    for (int g0 = 0; g0 < B * V && !rv; g0 += cap) {
+        const int nr = std::min(cap, B * V - g0);
+        ea.g0 = g0;
+        hipLaunchKernelGGL(k_scan_fine_expand, dim3(nr, nres), dim3(kIgxThreads), 0, st, ea);
+        LAUNCH_CHECK("k_scan_fine_expand");
+        cb.B = nr;
+        rv = forward_trunk(h, &cb, 0, st, B) || forward_reg_head(h, &cb, logits + (size_t)g0 * c.n_out, 0, st, nullptr);
     }
     h->x0_fwd = false;
     forward_counted(h, launches0);

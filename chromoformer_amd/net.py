@@ -151,7 +151,7 @@ class ChromoformerBase(nn.Module):
         self.n_bins = [w_max // b for b in self.binsizes]
         self._kws = (embed, pair, reg)
         self._max_batch = max_batch
-        self._maps_gen = 0          # bumped by attention_maps() / pcre_ablation() / pcre_coalitions() / pcre_shapley() / pcre_epistasis() / integrated_gradients() / perturbation_scan() / perturbation_scan_regions() / trunk_outputs(): a pending backward of an earlier forward refuses to run
+        self._maps_gen = 0          # bumped by attention_maps() / pcre_ablation() / pcre_coalitions() / pcre_shapley() / pcre_epistasis() / integrated_gradients() / perturbation_scan() / perturbation_scan_regions() / perturbation_scan_fine() / trunk_outputs(): a pending backward of an earlier forward refuses to run
         self._maps_by = None        # ... naming the last of them
         self._handle = None
         self._device = None
@@ -806,6 +806,79 @@ class ChromoformerBase(nn.Module):
         _lib.check(_lib.lib().cf_perturbation_scan_regions(self._handle, C.byref(bs), C.byref(opts), logits.data_ptr(), st),
                    "cf_perturbation_scan_regions")
         return logits, regions
+
+    @torch.no_grad()
+    def perturbation_scan_fine(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                               interaction_freq=None, region=0, scale=0.0, width=1, stride=None, start=0, n_windows=None, mark_sets=None,
+                               lengths=None, flip=None, return_feats=False):
+        """perturbation_scan with windows in bins of the FINEST resolution (cf_perturbation_scan_fine) -> logits [B, V, n_out] on the
+        model's device, no autograd graph; V = 1 + n_sets * n_windows:
+
+          [:, 0]                        the prediction (model(...) under no_grad, bit-equal)
+          [:, 1 + k * n_windows + g]    mark set k over the finest genomic bins [start[b] + g * stride, start[b] + g * stride + width) of
+                                        the region.  A coarser bin the window covers wholly follows perturbation_scan's rule; one it
+                                        covers in part is recomputed from its finest children, weighted by their sample counts -- what
+                                        binning the scaled signal gives, up to the rounding of the stored features.  Windows past the
+                                        region's real bins and empty mark sets give [:, 0], bit for bit.
+
+        width, stride (default: width) in finest bins; start: an int or B ints, the first finest genomic bin per gene (zoom into a
+        different coarse window per gene); n_windows: default the windows that reach the end of the region from the smallest start.
+        lengths: B ints, the scanned region's length in samples, so that the short last bin of a region is weighted by what it holds
+        (None: every real finest bin is full -- exact for promoters and whenever the length is a multiple of the finest bin size;
+        giving it costs one read-back of the pad-mask rows and a stream synchronisation).  mark_sets, flip, return_feats, the packed
+        forms of the first argument and the effect on a pending backward() are those of perturbation_scan."""
+        who = "perturbation_scan_fine"
+        bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        F, dev, B = self.n_feats, self._device, bs.B
+        bits = self._scan_mark_bits(who, mark_sets)
+        Lf = self.n_bins[min(range(len(self.binsizes)), key=lambda r: self.binsizes[r])]
+        width = int(width)
+        stride = width if stride is None else int(stride)
+        start = np.asarray(start, dtype=np.int64).reshape(-1)
+        if start.size == 1:
+            start = np.repeat(start, B)
+        if start.size != B:
+            raise ValueError("%s: start has %d entries for a batch of %d genes" % (who, start.size, B))
+        if start.size and (start.min() < -2 ** 31 or start.max() >= 2 ** 31):
+            raise ValueError("%s: start does not fit an int" % who)
+        start = start.astype(np.int32)
+        if n_windows is None:
+            first = max(int(start.min()), 0) if B else 0
+            n_windows = max(-(-(Lf - first) // max(stride, 1)), 1)
+        n_windows = int(n_windows)
+        V = 1 + len(bits) * max(n_windows, 0)
+        opts = _lib.cf_scan_fine_opts()
+        opts.region, opts.n_sets, opts.scale = int(region), len(bits), float(scale)
+        opts.width, opts.stride, opts.n_windows = width, stride, n_windows
+        opts.mark_sets = bits.ctypes.data
+        opts.start = start.ctypes.data
+        if lengths is not None:
+            lengths = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+            if lengths.size != B:
+                raise ValueError("%s: lengths has %d entries for a batch of %d genes" % (who, lengths.size, B))
+            lengths = np.clip(lengths, -1, 2 ** 31 - 1).astype(np.int32)      # (out of range either way: refused by the library)
+            opts.lengths = lengths.ctypes.data
+        flip = self._scan_flip(who, flip, B)      # (kept alive until the call below has been issued)
+        if flip is not None:
+            opts.flip = flip.data_ptr()
+        feats = None
+        if return_feats:
+            feats = {}
+            for r, b in enumerate(self.binsizes):
+                t = feats[b] = torch.empty(B, V, self.n_bins[r], F, device=dev)      # (written in full by the library)
+                opts.feats_out[r] = t.data_ptr()
+        logits = torch.empty(B, V, self.n_out, device=dev)      # (written in full by the library)
+        st = book()
+        _lib.check(_lib.lib().cf_perturbation_scan_fine(self._handle, C.byref(bs), C.byref(opts), logits.data_ptr(), st), "cf_perturbation_scan_fine")
+        return (logits, feats) if return_feats else logits
+
+    def perturbation_scan_fine_dataset(self, dataset, genes=None, region="promoter", zoom=None, scale=0.0, width=1, stride=None, mark_sets=None,
+                                       target=None, bsz=None, store=None):
+        """perturbation_scan_fine over the genes of a ChromoformerDataset with windows in genomic coordinates
+        (chromoformer_amd.attribution.perturbation_scan_fine, a generator of per-gene dicts)."""
+        from .attribution import perturbation_scan_fine
+        return perturbation_scan_fine(self, dataset, genes=genes, region=region, zoom=zoom, scale=scale, width=width, stride=stride,
+                                      mark_sets=mark_sets, target=target, bsz=bsz, store=store)
 
     def perturbation_scan_dataset(self, dataset, genes=None, regions="promoter", scale=0.0, width=1, mark_sets=None, bsz=None, store=None):
         """perturbation_scan over the genes of a ChromoformerDataset with windows in genomic coordinates

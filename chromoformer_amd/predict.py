@@ -420,6 +420,50 @@ def write_perturbation_scan(model, store, bsz, path, gene_ids, strands, regressi
         np.savez(f, **arrays)
 
 
+def write_perturbation_scan_fine(model, dataset, store, bsz, path, gene_ids, regression=False, region="promoter", width=1, stride=None, zoom=None,
+                                 scale=0.0, mark_sets=None):
+    """Fine-resolution perturbation scan of every gene of `dataset` (attribution.perturbation_scan_fine on the device-resident `store`,
+    which holds `gene_ids` in order: windows of `width` finest bins, `stride` apart, of the promoter or of one pCRE slot) into `path`, an
+    .npz holding
+
+        gene_ids     [n]
+        mark_sets    [n_sets, n_feats] bool: the marks of each set (default: each mark alone, then all together)
+        prediction   float32 [n]: the prediction column's quantity (sigmoid(logits)[:, 1], or logits[:, 0] for the regressor)
+        chroms       [n] and windows int64 [n, n_win, 2]: genomic start and end of each window (-1 where the gene has fewer windows)
+        scan         float32 [n, n_sets, n_win]: the same quantity with set k scaled by `scale` over window g; NaN where windows is -1
+        zoom         int64 [n, k], coarse_windows int64 [n, W, 2] and coarse float32 [n, n_sets, W], with zoom = k: the k coarse windows
+                     that were fine-scanned, most important first, and the coarse scan they were chosen from (-1 / NaN padding)"""
+    from .attribution import perturbation_scan_fine
+    col = (lambda lg: lg[..., 0]) if regression else (lambda lg: torch.sigmoid(torch.from_numpy(np.ascontiguousarray(lg))).numpy()[..., 1])
+    res = list(perturbation_scan_fine(model, dataset, genes=list(gene_ids), region=region, zoom=zoom, scale=scale, width=width, stride=stride,
+                                      mark_sets=mark_sets, bsz=bsz, store=store))
+    n, K, F = len(res), len(res[0]["mark_sets"]) if res else 0, model.n_feats
+    n_win = max([len(d["windows"]) for d in res] + [0])
+    windows = np.full((n, n_win, 2), -1, dtype=np.int64)
+    scan = np.full((n, K, n_win), np.nan, dtype=np.float32)
+    for i, d in enumerate(res):
+        m = len(d["windows"])
+        windows[i, :m] = np.array([w[1:] for w in d["windows"]], dtype=np.int64).reshape(m, 2)
+        scan[i, :, :m] = col(d["scan"])
+    sets = np.zeros((K, F), dtype=bool)
+    for k, ms in enumerate(res[0]["mark_sets"] if res else []):
+        sets[k, list(ms)] = True
+    arrays = dict(gene_ids=np.array(list(gene_ids)), mark_sets=sets, prediction=np.array([col(d["logits"]) for d in res], dtype=np.float32),
+                  chroms=np.array([d["region"][0] if d["region"] else "" for d in res]), windows=windows, scan=scan)
+    if zoom is not None:
+        W = max([len(d["coarse_windows"]) for d in res] + [0])
+        arrays["zoom"] = np.full((n, int(zoom)), -1, dtype=np.int64)
+        arrays["coarse_windows"] = np.full((n, W, 2), -1, dtype=np.int64)
+        arrays["coarse"] = np.full((n, K, W), np.nan, dtype=np.float32)
+        for i, d in enumerate(res):
+            m = len(d["coarse_windows"])
+            arrays["zoom"][i, :len(d["zoom"])] = d["zoom"]
+            arrays["coarse_windows"][i, :m] = np.array([w[1:] for w in d["coarse_windows"]], dtype=np.int64).reshape(m, 2)
+            arrays["coarse"][i, :, :m] = col(d["coarse_scan"])
+    with open(path, "wb") as f:
+        np.savez(f, **arrays)
+
+
 def require_raw_signals(dataset, genes=None):
     """Raw-signal saliency reads the raw .npy regions themselves; a packed store holds binned features only.  Raises FileNotFoundError
     naming the first region file of `genes` (default: the dataset's) that is missing."""
@@ -479,7 +523,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
             mark_players="marks", mark_scale=0.0, donor_npy_dir=None, donor_meta=None, donor_store_path=None, mark_donor_shapley_out=None,
             mark_donor_epistasis_out=None, mark_sampled_shapley_out=None, mark_donor_sampled_shapley_out=None, mark_sampled_players="cells",
             mark_perms=64, mark_seed=0, window_shapley_out=None, window_donor_shapley_out=None, window_players="promoter", window_width=1,
-            window_perms=64, window_seed=0, window_scale=0.0, raw_donor_ig_dir=None):
+            window_perms=64, window_seed=0, window_scale=0.0, raw_donor_ig_dir=None, fine_scan_out=None, fine_scan_region="promoter",
+            fine_scan_width=1, fine_scan_stride=None, fine_scan_zoom=None, fine_scan_scale=0.0):
     """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file.  attention_dir / embeddings_out: also
     write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps); pcre_ablation_out:
     the predictions with each pCRE deleted (write_pcre_ablation); ig_dir: integrated gradients of every gene
@@ -500,7 +545,9 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     rule (window_scale applies) / against the donor, exact with at most 16 players and sampled otherwise (write_mark_window_values;
     window_players, window_width, window_perms and window_seed apply); raw_donor_ig_dir: integrated gradients with respect to the raw
     signals against the donor cell type's signals of donor_npy_dir, one .npz per gene (write_raw_integrated_gradients with the donor's
-    dataset; ig_steps, ig_method and ig_target apply; needs the raw .npy files of both cell types)."""
+    dataset; ig_steps, ig_method and ig_target apply; needs the raw .npy files of both cell types); fine_scan_out: the fine-resolution
+    perturbation scan of every gene, one .npz (write_perturbation_scan_fine; fine_scan_region -- "promoter" or a pCRE slot --,
+    fine_scan_width, fine_scan_stride, fine_scan_zoom and fine_scan_scale apply; served by a packed store as well)."""
     seed_everything(seed)
     meta = pd.read_csv(meta_path)
     genes = meta.gene_id.tolist()
@@ -576,6 +623,10 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
                                  window_perms, window_seed, window_scale)
     if ig_dir:
         write_integrated_gradients(model, store, bsz, ig_dir, ig_steps, ig_method, ig_target)
+    if fine_scan_out:      # (strand, coordinates and region lengths come from the metadata)
+        fine_ds = ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False)
+        write_perturbation_scan_fine(model, fine_ds, store, bsz, fine_scan_out, genes, regression, fine_scan_region, fine_scan_width, fine_scan_stride,
+                                     fine_scan_zoom, fine_scan_scale)
     if scan_out:
         write_perturbation_scan(model, store, bsz, scan_out, genes, meta.strand.tolist(), regression, scan_scale, scan_width, scan_regions)
     if raw_saliency_dir:
@@ -633,6 +684,16 @@ def build_parser():
     ap.add_argument("--scan-width", type=int, default=None, help="window width of --scan-out in coarsest bins (default 1)")
     ap.add_argument("--scan-regions", default=None, choices=("promoter", "all"), help="--scan-out scans the promoter (default) or also every "
                     "pCRE slot: pcres [n, i_max, n_sets, W]")
+    ap.add_argument("--fine-scan-out", default=None, help="also write the FINE-resolution perturbation scan to this .npz file: gene_ids, "
+                    "mark_sets [n_sets, 7], prediction [n] (as --output), chroms [n], windows [n, n_win, 2] (genomic start and end, -1 padding) and "
+                    "scan [n, n_sets, n_win]: the prediction with each mark alone, then all marks, scaled by --fine-scan-scale in raw-signal space "
+                    "over windows of --fine-scan-width finest bins (100 bp), NaN padding (model.perturbation_scan_fine)")
+    ap.add_argument("--fine-scan-region", default=None, help="the region --fine-scan-out scans: promoter (default) or a pCRE slot 0 .. 7")
+    ap.add_argument("--fine-scan-width", type=int, default=None, help="window width of --fine-scan-out in finest bins (default 1)")
+    ap.add_argument("--fine-scan-stride", type=int, default=None, help="distance between windows of --fine-scan-out in finest bins (default: the width)")
+    ap.add_argument("--fine-scan-zoom", type=int, default=None, help="--fine-scan-out first runs the coarse scan and fine-scans, per gene, the K "
+                    "coarse windows that move the prediction's logit most; also writes zoom [n, K], coarse_windows and coarse (default: the whole region)")
+    ap.add_argument("--fine-scan-scale", type=float, default=None, help="scale factor of --fine-scan-out: 0 erases the marks (default), 2 doubles them")
     from .attribution import MARK_PLAYER_SPECS
     ap.add_argument("--mark-shapley-out", default=None, help="also write the exact Shapley values of the histone marks to this .npz file, in "
                     "metadata order and in LOGIT space of the prediction's column: gene_ids, players (names), phi [n_genes, P], logits and "
@@ -712,6 +773,19 @@ def main(argv=None):
         ap.error("--scan-scale must be a finite factor >= 0")
     if args.scan_width is not None and args.scan_width < 1:
         ap.error("--scan-width must be at least 1")
+    fine_opts = (args.fine_scan_region, args.fine_scan_width, args.fine_scan_stride, args.fine_scan_zoom, args.fine_scan_scale)
+    if not args.fine_scan_out and any(v is not None for v in fine_opts):
+        ap.error("--fine-scan-region / --fine-scan-width / --fine-scan-stride / --fine-scan-zoom / --fine-scan-scale need --fine-scan-out")
+    fine_region = "promoter"
+    if args.fine_scan_region not in (None, "promoter"):
+        if not args.fine_scan_region.isdigit() or int(args.fine_scan_region) >= 8:
+            ap.error("--fine-scan-region must be promoter or a pCRE slot in [0, 8)")
+        fine_region = int(args.fine_scan_region)
+    if args.fine_scan_scale is not None and not (args.fine_scan_scale >= 0 and np.isfinite(args.fine_scan_scale)):
+        ap.error("--fine-scan-scale must be a finite factor >= 0")
+    for name, v in (("width", args.fine_scan_width), ("stride", args.fine_scan_stride), ("zoom", args.fine_scan_zoom)):
+        if v is not None and v < 1:
+            ap.error("--fine-scan-%s must be at least 1" % name)
     donor_exact = args.mark_donor_shapley_out or args.mark_donor_epistasis_out
     donor_out = donor_exact or args.mark_donor_sampled_shapley_out or args.window_donor_shapley_out
     if args.raw_donor_ig_dir and not args.donor_npy_dir:
@@ -773,7 +847,10 @@ def main(argv=None):
                          window_width=1 if args.window_width is None else args.window_width,
                          window_perms=64 if args.window_perms is None else args.window_perms,
                          window_seed=0 if args.window_seed is None else args.window_seed,
-                         window_scale=0.0 if args.window_scale is None else args.window_scale, raw_donor_ig_dir=args.raw_donor_ig_dir)
+                         window_scale=0.0 if args.window_scale is None else args.window_scale, raw_donor_ig_dir=args.raw_donor_ig_dir,
+                         fine_scan_out=args.fine_scan_out, fine_scan_region=fine_region,
+                         fine_scan_width=1 if args.fine_scan_width is None else args.fine_scan_width, fine_scan_stride=args.fine_scan_stride,
+                         fine_scan_zoom=args.fine_scan_zoom, fine_scan_scale=0.0 if args.fine_scan_scale is None else args.fine_scan_scale)
     print("Predicting expressions for %d genes." % len(meta))
     meta["prediction"] = pred
     meta.to_csv(args.output, index=False)

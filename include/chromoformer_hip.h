@@ -399,6 +399,51 @@ typedef struct cf_scan_regions_opts {
  * mark_sets, B > max_batch, width < 1, n_sets < 1, a negative or non-finite scale, a mark bit >= n_feats, non-nested n_bins, armed
  * riders), regions == 0, a region bit above i_max. */
 int cf_perturbation_scan_regions(cf_handle* h, const cf_batch* batch, const cf_scan_regions_opts* opts, float* logits, void* stream);
+/* Fine-resolution perturbation scan (interpretation): the scan above with windows given in bins of the FINEST resolution -- "where
+ * inside this coarse bin?".  The perturbation is the scan's (the window's raw samples of a mark set scaled by s); a fine window covers
+ * a coarser bin only in part, and such a bin is recomputed from its finest children, weighted by sample counts.
+ * The rule.  f = the resolution with the smallest bin size, b_r the bin sizes, R_r = n_bins[f] / n_bins[r] (an n_bins[f] that is not a
+ * multiple of every n_bins[r] is refused).  The real rows [q_r, q_r + n_r) of the region come from the centre pad-mask rows as above;
+ * genomic bin j is row q_r + j, or q_r + n_r - 1 - j under flip[b].
+ * Sample counts: finest bin k holds cnt_k = b_f samples, except the last real one, which with `lengths` given holds
+ * len - (n_f - 1) b_f samples (1 <= cnt <= b_f, else refused).  Bin j at resolution r has the children K_j = [j R_r, min((j + 1) R_r, n_f))
+ * and cnt_j = sum of cnt_k over K_j.  lengths = NULL: every real finest bin is full -- exact whenever the region's length is a multiple
+ * of b_f (the promoter's always is).
+ * A window [lo, hi) is given in finest genomic bins.  With C = K_j n [lo, hi), for a mark of the set:
+ *   C empty, or lo >= n_f    the element keeps its bits;
+ *   C = K_j                  u' = log1pf(s expm1f(u)), the scan's function: a fine window that is a union of whole coarse bins
+ *                            reproduces the scan bit for bit; the finest resolution always falls under this case;
+ *   otherwise                S  = sum over k in C of (double)cnt_k (double)expm1f(u_k), in ascending genomic k,
+ *                            m' = (float)((double)expm1f(u_j) + ((double)s - 1.0) S / (double)cnt_j),
+ *                            u' = log1pf(m'); no contraction, no clamp; u_k are the source gene's finest-resolution elements of the
+ *                            same region and mark.
+ * Binning is linear per mark, so this is the feature that binning produces when the raw samples inside the window are scaled by s, up
+ * to the rounding of the stored fp32 features.  Limits: those of the scan (u < ~80; 1 + m' <= 0 gives NaN as log does); and a partly
+ * covered bin that is nearly emptied carries an absolute error of order eps (1 + m_j) / (1 + m'). */
+typedef struct cf_scan_fine_opts {
+    int region;                 /* 0 promoter, 1 + j pCRE slot j                                  */
+    int n_sets;                 /* >= 1                                                           */
+    const unsigned* mark_sets;  /* host [n_sets], as in cf_scan_opts                              */
+    float scale;                /* s >= 0, finite                                                 */
+    const uint8_t* flip;        /* device [B] or NULL, as in cf_scan_opts                         */
+    int width, stride, n_windows; /* each >= 1; width and stride in finest bins                   */
+    const int* start;           /* host [B] or NULL (all 0): the gene's first finest genomic bin  */
+    const int* lengths;         /* host [B] or NULL: the scanned region's length in samples       */
+    float* feats_out[CF_MAX_RES]; /* optional, device, [B, V, n_bins[r], n_feats]                  */
+} cf_scan_fine_opts;
+/* Window g of gene b covers the finest genomic bins [start[b] + g stride, start[b] + g stride + width), clipped to n_bins[f].
+ * logits: [B, V, n_out], V = 1 + n_sets * n_windows, gene-major; v = 0 the unperturbed gene, v = 1 + k * n_windows + g mark set k over
+ * window g.  Windows past the real bins, empty sets and dummy slots give the baseline's bits.  feats_out as in cf_scan_opts.
+ * Rows run in chunks of at most max_batch in the chunk buffers of cf_integrated_gradients; start and the tail counts travel in the
+ * workspace's word table behind the mark sets (no device buffer of its own).  Per chunk one k_scan_fine_expand, then the launches of
+ * cf_forward(save = 0):   cf_launch_counts fwd = ceil(B * V / max_batch) * (1 + n_fwd).
+ * Deterministic (no atomics); k_attc2's regions per workgroup are chosen as for the caller's B genes, so the result does not depend on
+ * max_batch and row (b, v) equals cf_forward(save = 0) on the batch with feats_out[:, v] substituted, bit for bit.  Overwrites the
+ * activations a cf_forward(save >= 1) kept.  Parameters, gradients and moments are untouched.
+ * Refused by name, before anything is launched: everything cf_perturbation_scan refuses; width, stride or n_windows < 1; a negative
+ * start; a lengths[b] outside ((n_f - 1) b_f, n_f b_f] for that gene's real n_f (read back from the finest pad-mask rows, a copy and a
+ * stream synchronisation; a dummy slot is exempt: it is ignored); an n_bins[f] that is no multiple of every n_bins[r]. */
+int cf_perturbation_scan_fine(cf_handle* h, const cf_batch* batch, const cf_scan_fine_opts* opts, float* logits, void* stream);
 /* Histone-mark coalitions, exact Shapley values of the marks and their pair epistasis (interpretation): which marks carry the
  * prediction, and do they act alone or together?  The players of the game are MARKS, each optionally restricted to a set of regions.
  * Player p is a pair of words: player_marks[p] (bit f: mark f; non-zero, no bit >= n_feats) and player_regions[p] (bit 0: the promoter,
