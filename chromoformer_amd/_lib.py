@@ -122,6 +122,12 @@ class cf_mark_window_opts(C.Structure):
                 ("donor_promoter_feats", C.c_void_p * MAX_RES), ("donor_pcre_feats", C.c_void_p * MAX_RES)]
 
 
+class cf_mark_fine_opts(C.Structure):
+    _fields_ = [("region", C.c_int), ("n_players", C.c_int), ("player_marks", C.c_void_p), ("player_lo", C.c_void_p), ("player_hi", C.c_void_p),
+                ("start", C.c_void_p), ("lengths", C.c_void_p), ("flip", C.c_void_p), ("scale", C.c_float),
+                ("donor_promoter_feats", C.c_void_p * MAX_RES), ("donor_pcre_feats", C.c_void_p * MAX_RES), ("feats_out", C.c_void_p * MAX_RES)]
+
+
 class cf_store(C.Structure):
     _fields_ = [
         ("n_genes", C.c_longlong),
@@ -197,6 +203,10 @@ SYMBOLS = {
     "cf_mark_window_shapley": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_window_opts), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_mark_window_shapley_sampled": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_window_opts), C.c_void_p, C.c_int, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cf_mark_fine_coalitions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_fine_opts), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "cf_mark_fine_shapley": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_fine_opts), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cf_mark_fine_shapley_sampled": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_fine_opts), C.c_void_p, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_adamw_step":(C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_longlong, C.c_void_p]),
     "cf_debug_copy": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p]),
     "cf_debug_names": (C.c_char_p, [C.c_void_p]),

@@ -266,6 +266,65 @@ def window_players(spec, n_feats, i_max, W, width=1):
     return marks, regions, lo, hi, names
 
 
+FINE_WINDOW_PLAYER_SPECS = ("windows", "cells")
+
+
+def fine_window_players(spec, n_feats, width=1, n_windows=1):
+    """The players of the fine window game (ChromoformerBase.mark_fine_window_coalitions / mark_fine_window_shapley /
+    mark_fine_window_shapley_sampled) -> (marks, lo, hi, names): uint32 [P] mark words as mark_players returns them, int32 [P] windows
+    [lo, hi) in bins of the FINEST resolution relative to each gene's start, and a name per player.  With window g = [g width,
+    (g + 1) width), g < n_windows:
+
+      "windows"   P = n_windows: all marks over window g ("fine[4:6]")
+      "cells"     P = n_feats n_windows: player g * n_feats + f is mark f over window g ("mark3@fine[4:6]"); a [B, P, n_out] result
+                  reshapes to [B, n_windows, n_feats, n_out]
+      a list of (marks, (lo, hi)) pairs: index iterables as in mark_players and a window; players may overlap
+
+    More than 128 players (the count is named: choose a larger width), an empty player, a mark out of range or a window without
+    0 <= lo < hi raise ValueError naming fine_window_players."""
+    who = "fine_window_players"
+    F = int(n_feats)
+    every_mark = list(range(F))
+    if isinstance(spec, str):
+        if spec not in FINE_WINDOW_PLAYER_SPECS:
+            raise ValueError("%s: players %r; choose from %s or give a list of (marks, (lo, hi)) pairs" % (who, spec, FINE_WINDOW_PLAYER_SPECS))
+        width, n_windows = int(width), int(n_windows)
+        if width < 1:
+            raise ValueError("%s: width = %d: at least 1 finest bin" % (who, width))
+        if n_windows < 1:
+            raise ValueError("%s: n_windows = %d: at least 1 window" % (who, n_windows))
+        count = n_windows * (F if spec == "cells" else 1)
+        if count > MARK_WIDE_MAX_PLAYERS:
+            raise ValueError("%s: %r at width = %d over %d windows gives %d players; the game takes 1..%d: choose a larger width"
+                             % (who, spec, width, n_windows, count, MARK_WIDE_MAX_PLAYERS))
+        wins = [(g * width, (g + 1) * width) for g in range(n_windows)]
+        if spec == "windows":
+            pairs = [(every_mark, w) for w in wins]
+            names = ["fine[%d:%d]" % w for w in wins]
+        else:
+            pairs = [([f], w) for w in wins for f in every_mark]
+            names = ["mark%d@fine[%d:%d]" % ((f,) + w) for w in wins for f in every_mark]
+    else:
+        try:
+            pairs = [(sorted({int(f) for f in ms}), (int(w[0]), int(w[1]))) for ms, w in spec]
+        except (TypeError, ValueError, IndexError):
+            raise ValueError("%s: players must be one of %s or a list of (marks, (lo, hi)) pairs, got %r" % (who, FINE_WINDOW_PLAYER_SPECS, spec)) from None
+        names = ["marks(%s)@fine[%d:%d]" % (",".join(map(str, ms)), w[0], w[1]) for ms, w in pairs]
+        if not 1 <= len(pairs) <= MARK_WIDE_MAX_PLAYERS:
+            raise ValueError("%s: %d players; the game takes 1..%d: choose a larger width" % (who, len(pairs), MARK_WIDE_MAX_PLAYERS))
+    for p, (ms, (lo, hi)) in enumerate(pairs):
+        if not ms:
+            raise ValueError("%s: player %d is empty: at least one mark" % (who, p))
+        if ms[0] < 0 or ms[-1] >= min(F, 32):
+            raise ValueError("%s: player %d names mark(s) %s outside [0, n_feats = %d)" % (who, p, ms, F))
+        if lo < 0 or lo >= hi or hi >= 2 ** 31:
+            raise ValueError("%s: player %d has the window [%d, %d): 0 <= lo < hi finest bins is required" % (who, p, lo, hi))
+    marks = np.array([sum(1 << f for f in ms) for ms, _ in pairs], dtype=np.uint32)
+    lo = np.array([w[0] for _, w in pairs], dtype=np.int32)
+    hi = np.array([w[1] for _, w in pairs], dtype=np.int32)
+    return marks, lo, hi, names
+
+
 def _geometry_check(who, model, dataset, binsizes):
     """The model is on the device and the dataset has its geometry -> n_bins."""
     ds = dataset
@@ -1090,3 +1149,133 @@ def mark_window_shapley(model, dataset, donor_dataset=None, genes=None, players=
             if not exact:
                 out["permutations"] = perms.copy()
             yield out
+
+
+def mark_fine_window_shapley(model, dataset, donor_dataset=None, genes=None, region="promoter", zoom=1, coarse_width=1, width=2, players="windows",
+                             n_perm=64, seed=0, scale=0.0, target=None, bsz=None, store=None, donor_store=None):
+    """Shapley values of FINE window players for the genes of a ChromoformerDataset: which 200 bp of this peak?  Per batch the coarse
+    window game runs first (model.mark_window_shapley over `region` at `coarse_width` coarsest bins per player, exact with at most 16
+    players, else sampled); per gene the `zoom` coarse windows with the largest |phi| at logit `target` (default: the last) are chosen,
+    and inside each the fine game is played: players = fine_window_players(players, n_feats, width, ...) tiling the coarse window, each
+    gene at its own start (model.mark_fine_window_shapley, or _sampled above 16 players with n_perm orders from `seed`).  Without
+    `donor_dataset` an absent player's raw signal inside its window is scaled by `scale` (0 erases it); with one -- the same genes over
+    the same regions in another cell type (same_regions runs first) -- it takes the donor's signal, in both games.  A generator over
+    `genes` in chunks of at most min(bsz, model.max_batch) genes; per gene it yields a dict:
+
+        gene_id         the id
+        region          (chrom, start, end) of the region, None if the gene does not have it (everything below is then empty)
+        coarse_phi      float32 [n_cwin, n_out]: the coarse game's values of the region's real coarse windows
+        coarse_windows  [(chrom, start, end)]: those windows
+        zoom            int64 [k']: the chosen coarse windows, most important first (k' = min(zoom, n_cwin))
+        players         the names of the fine players with a real window, rank 0's first, then rank 1's, ...
+        windows         [(chrom, start, end)]: each such player's window in genomic coordinates, the end clipped to the region
+        rank, index     int64 [n] each: the rank of the coarse window the player lies in and its index among the fine game's players
+        phi             float32 [n, n_out]: their values, in logit space; per rank they sum to logits - absent[rank] up to rounding
+        stderr          float32 [n, n_out], or None when the fine game was exact
+        logits          float32 [n_out]: the prediction
+        absent          float32 [k', n_out]: per rank, every fine player absent
+        exact           whether the fine game was exact
+
+    Strand, coordinates and the region's length come from the dataset's metadata: '-' strand promoters are stored mirrored (window 0 is
+    still the genomic start) and the short last bin of a pCRE is weighted by the samples it holds.  Features, stores, parameters and
+    the effect on a pending backward: as mark_window_shapley."""
+    from .data import promoter_col0
+    ds, dn = dataset, donor_dataset
+    who = "mark_fine_window_shapley"
+    binsizes = [int(b) for b in ds.binsizes]
+    n_bins = _geometry_check(who, model, ds, binsizes)
+    genes, chunk = _genes_check(who, model, ds, genes, bsz)
+    if dn is not None:
+        same_regions(ds, dn, genes)
+    S, F = ds.i_max, ds.n_feats
+    if region == "promoter":
+        region = 0
+    elif isinstance(region, str) or not 0 <= int(region) < S:
+        raise ValueError("%s: region %r; choose 'promoter' or a pCRE slot in [0, i_max = %d)" % (who, region, S))
+    else:
+        region = 1 + int(region)
+    zoom, coarse_width, width = int(zoom), int(coarse_width), int(width)
+    if zoom < 1:
+        raise ValueError("%s: zoom = %d: at least 1 coarse window" % (who, zoom))
+    if coarse_width < 1 or width < 1:
+        raise ValueError("%s: coarse_width = %d, width = %d: at least 1 bin each" % (who, coarse_width, width))
+    rf, rc = int(np.argmin(binsizes)), int(np.argmin(n_bins))
+    Lf, bf, W, bc = n_bins[rf], binsizes[rf], n_bins[rc], binsizes[rc]
+    Rc = Lf // W
+    spec = players if isinstance(players, str) else list(players)
+    n_fw = -(-(coarse_width * Rc) // width)
+    game = fine_window_players(spec, F, width, n_fw)      # (refusals before anything is loaded)
+    names = game[3]
+    P = len(names)
+    exact = P <= 16
+    perms = None if exact else shapley_permutations(P, n_perm, seed)
+    coarse = [(list(range(F)), [region], (g, min(g + coarse_width, W))) for g in range(0, W, coarse_width)]
+    Pc = len(coarse)
+    cperms = None if Pc <= 16 else shapley_permutations(Pc, n_perm, seed)
+    target = model.n_out - 1 if target is None else int(target)
+    col0 = promoter_col0(ds)
+    store = _resident_store(who, ds, genes, binsizes, model._device, store)
+    if dn is not None:
+        donor_store = _resident_store(who, dn, genes, binsizes, model._device, donor_store)
+    keys = ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq")
+    for lo in range(0, len(genes), chunk):
+        ids = genes[lo:lo + chunk]
+        B = len(ids)
+        idx = list(range(lo, lo + B))
+        d = store.batch(idx)
+        donor = None
+        if dn is not None:
+            dd = donor_store.batch(idx)
+            donor = ({b: t.contiguous() for b, t in dd["promoter_feats"].items()}, {b: t.contiguous() for b, t in dd["pcre_feats"].items()})
+        args = tuple(d[k] for k in keys)
+        flip = [region == 0 and ds.genes[g]["tss"][2] != "+" for g in ids]
+        regs = []
+        for g in ids:
+            if region == 0:
+                chrom, tss, _ = ds.genes[g]["tss"]
+                regs.append((chrom, tss - 20000 + col0, tss - 20000 + col0 + min(ds.w_prom, 40000 - col0)))
+            else:
+                pc = ds.genes[g]["pcres"]
+                regs.append(tuple(pc[region - 1]) if region - 1 < len(pc) else None)
+        lengths = [r[2] - r[1] if r else 0 for r in regs]
+        if cperms is None:
+            cphi, info = model.mark_window_shapley(*args, players=coarse, scale=scale, donor=donor, flip=flip)
+        else:
+            cphi, info = model.mark_window_shapley_sampled(*args, players=coarse, permutations=cperms, scale=scale, donor=donor, flip=flip)
+        cphi, logits = cphi.cpu().numpy(), info["logits"].cpu().numpy()
+        per, ranks = [], []
+        for i, r in enumerate(regs):
+            n_cw = min(-(-(-(-(r[2] - r[1]) // bc)) // coarse_width), Pc) if r else 0
+            z = np.argsort(-np.abs(cphi[i, :n_cw, target]), kind="stable")[:zoom].astype(np.int64)
+            ranks.append(z)
+            cwins = [(r[0], r[1] + g * coarse_width * bc, min(r[1] + (g + 1) * coarse_width * bc, r[2])) for g in range(n_cw)] if r else []
+            per.append(dict(gene_id=ids[i], region=r, coarse_phi=cphi[i, :n_cw].copy(), coarse_windows=cwins, zoom=z, players=[], windows=[], rank=np.zeros(0, np.int64),
+                            index=np.zeros(0, np.int64),
+                            phi=np.zeros((0, model.n_out), np.float32), stderr=None if exact else np.zeros((0, model.n_out), np.float32),
+                            logits=logits[i].copy(), absent=np.zeros((0, model.n_out), np.float32), exact=exact))
+        for rank in range(max([len(z) for z in ranks] + [0])):
+            # a gene with fewer real coarse windows than ranks starts past its region: null players, left out below
+            start = [int(z[rank]) * coarse_width * Rc if rank < len(z) else Lf for z in ranks]
+            kw = dict(region=region, players=spec, width=width, n_windows=n_fw, start=start, lengths=lengths, scale=scale, donor=donor, flip=flip)
+            if exact:
+                phi, info = model.mark_fine_window_shapley(*args, **kw)
+                absent, se = info["erased" if donor is None else "donor"].cpu().numpy(), None
+            else:
+                phi, info = model.mark_fine_window_shapley_sampled(*args, permutations=perms, **kw)
+                absent, se = info["absent"].cpu().numpy(), info["stderr"].cpu().numpy()
+            phi = phi.cpu().numpy()
+            for i, r in enumerate(regs):
+                if rank >= len(ranks[i]):
+                    continue
+                first = r[1] + start[i] * bf
+                real = [p for p in range(P) if first + int(game[1][p]) * bf < r[2]]
+                per[i]["players"] += [names[p] for p in real]
+                per[i]["windows"] += [(r[0], first + int(game[1][p]) * bf, min(first + int(game[2][p]) * bf, r[2])) for p in real]
+                per[i]["rank"] = np.concatenate([per[i]["rank"], np.full(len(real), rank, np.int64)])
+                per[i]["index"] = np.concatenate([per[i]["index"], np.array(real, np.int64)])
+                per[i]["phi"] = np.concatenate([per[i]["phi"], phi[i, real]])
+                if not exact:
+                    per[i]["stderr"] = np.concatenate([per[i]["stderr"], se[i, real]])
+                per[i]["absent"] = np.concatenate([per[i]["absent"], absent[i][None]])
+        for p in per:
+            yield p

@@ -13,6 +13,7 @@
 #include "cf_marks.h"
 #include "cf_marks_wide.h"
 #include "cf_mark_windows.h"
+#include "cf_mark_fine.h"
 #include "cf_x0_gather.h"
 
 #include <algorithm>

@@ -895,6 +895,9 @@ struct MarkGame {
     const int* hi = nullptr;
     const uint8_t* flip = nullptr;        // device [B] or null: the promoter is stored mirrored (the window game)
     int W = 0, rc = 0;                    // the coarsest resolution's bin count and index (the window game)
+    const cf_mark_fine_opts* fine = nullptr;      // the fine window game (cf_mark_fine.h): lo / hi in finest bins, one region, no regions words
+    int rf = 0, bf = 0;                           // ... the finest resolution's index and bin size
+    std::vector<unsigned> fine_words;             // ... [start[B] | cnt_last[B]], behind the player words in the word table
 };
 
 // mark_check: what the entry points check alike, in front of anything launched -- the handle, the batch, riders, the options: the
@@ -950,7 +953,7 @@ static int mark_upload(cf_handle* h, const MarkGame& g, const uint32_t* keep, in
 // The B * n_coal rows of a mark-coalition call (gene-major; row (b, k) is word k of the table mark_upload wrote), every row through
 // the whole forward.  Per chunk of at most max_batch rows: k_mark_expand (the donor rule: k_mark_donor_expand; the wide game, whose rows
 // are g.kw words each: k_mark_wide_expand / k_mark_wide_donor_expand; the window game, g.lo set: k_mark_window_expand /
-// k_mark_window_donor_expand) into the chunk workspace,
+// k_mark_window_donor_expand; the fine window game, g.fine set: k_mark_fine_expand / k_mark_fine_donor_expand) into the chunk workspace,
 // then the launches of cf_forward(save = 0) on the chunk, writing its slice of `logits`.  k_attc2 takes as many regions per workgroup
 // as for the caller's B genes (ag_genes), as scan_region_rows: the result does not depend on max_batch.
 static int mark_rows(cf_handle* h, const cf_batch* bt, const MarkGame& g, int n_coal, float* logits, hipStream_t st) {
@@ -979,7 +982,27 @@ static int mark_rows(cf_handle* h, const cf_batch* bt, const MarkGame& g, int n_
     ea.n_coal = n_coal, ea.P = P, ea.F = c.n_feats;
     MarkWindowDonorArgs wd;      // the window game: ea with the promoter's centre mask rows, flip and the coarsest resolution
     memset(&wd, 0, sizeof wd);
-    if (g.lo) {
+    MarkFineDonorArgs fd;        // the fine window game: ea with the region's centre mask rows, start, the tail counts and feats_out
+    memset(&fd, 0, sizeof fd);
+    if (g.fine) {
+        const int slot = g.fine->region - 1, S = c.i_max;
+        for (int r = 0; r < nres; ++r) {
+            if (slot < 0) {
+                fd.w.rm_in[r] = bt->promoter_mask_row[r];
+                fd.w.rm_stride[r] = bt->promoter_mask_stride[r];
+            } else {
+                fd.w.rm_in[r] = bt->pcre_mask_row[r] + (long long)slot * bt->pcre_mask_stride[r];
+                fd.w.rm_stride[r] = (long long)S * bt->pcre_mask_stride[r];
+            }
+            fd.w.feats_out[r] = g.fine->feats_out[r];
+            fd.pf_don[r] = da.pf_don[r];
+            fd.cf_don[r] = da.cf_don[r];
+        }
+        fd.w.start = reinterpret_cast<const int*>(ea.players) + 3 * P;
+        fd.w.cnt_last = fd.w.start + B;
+        fd.w.flip = g.flip;
+        fd.w.rf = g.rf, fd.w.bf = g.bf, fd.w.region = g.fine->region;
+    } else if (g.lo) {
         for (int r = 0; r < nres; ++r) {
             wd.w.pmc[r] = static_cast<const uint8_t*>(bt->promoter_mask_row[r]);
             wd.pf_don[r] = da.pf_don[r];
@@ -993,7 +1016,16 @@ static int mark_rows(cf_handle* h, const cf_batch* bt, const MarkGame& g, int n_
         for (long long g0 = 0; g0 < rows; g0 += cap) {
             const int n = (int)std::min<long long>(cap, rows - g0);
             ea.g0 = g0;
-            if (g.lo) {
+            if (g.fine) {
+                fd.w.m = ea;
+                if (g.donor) {
+                    hipLaunchKernelGGL(k_mark_fine_donor_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, fd);
+                    LAUNCH_CHECK("k_mark_fine_donor_expand");
+                } else {
+                    hipLaunchKernelGGL(k_mark_fine_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, fd.w);
+                    LAUNCH_CHECK("k_mark_fine_expand");
+                }
+            } else if (g.lo) {
                 wd.w.m = ea;
                 if (g.donor) {
                     hipLaunchKernelGGL(k_mark_window_donor_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, wd);
@@ -1147,8 +1179,9 @@ static int mark_wide_game(cf_handle* h, const cf_batch* bt, const cf_mark_wide_o
 }
 
 // The n_coal * kw coalition words (validated) and the 2 P player words into the workspace's word table, with room for `extra` words
-// behind them: [words | marks_p | regions_p | extra]; the window game: [words | marks_p | regions_p | lo_p | hi_p | extra].
-static int mark_player_words(const MarkGame& g) { return (g.lo ? 4 : 2) * g.P; }
+// behind them: [words | marks_p | regions_p | extra]; the window game: [words | marks_p | regions_p | lo_p | hi_p | extra]; the fine
+// window game: [words | marks_p | lo_p | hi_p | start[B] | cnt_last[B] | extra].
+static int mark_player_words(const MarkGame& g) { return g.fine ? 3 * g.P + (int)g.fine_words.size() : (g.lo ? 4 : 2) * g.P; }
 static int mark_wide_upload(cf_handle* h, const MarkGame& g, const uint32_t* keep, int n_coal, size_t extra, hipStream_t st, const char* who) {
     const int P = g.P, kw = g.kw;
     if (n_coal < 1) return fail("%s: n_coal = %d: at least 1 coalition", who, n_coal);
@@ -1163,6 +1196,13 @@ static int mark_wide_upload(cf_handle* h, const MarkGame& g, const uint32_t* kee
     unsigned* tab = h->aw.words;
     HIP_TRY(hipMemcpyAsync(tab, keep, nw * sizeof(unsigned), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(tab + nw, g.marks, P * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    if (g.fine) {
+        HIP_TRY(hipMemcpyAsync(tab + nw + P, g.lo, P * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(tab + nw + 2 * P, g.hi, P * sizeof(int), hipMemcpyHostToDevice, st));
+        if (!g.fine_words.empty())
+            HIP_TRY(hipMemcpyAsync(tab + nw + 3 * P, g.fine_words.data(), g.fine_words.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
+        return 0;
+    }
     HIP_TRY(hipMemcpyAsync(tab + nw + P, g.regions, P * sizeof(unsigned), hipMemcpyHostToDevice, st));
     if (g.lo) {
         HIP_TRY(hipMemcpyAsync(tab + nw + 2 * P, g.lo, P * sizeof(int), hipMemcpyHostToDevice, st));
@@ -1286,4 +1326,94 @@ extern "C" int cf_mark_window_shapley_sampled(cf_handle* h, const cf_batch* bt, 
     MarkGame g;
     cf_mark_donor_opts d;
     return mark_window_game(h, bt, o, &g, &d, who) ? -1 : mark_sampled_impl(h, bt, g, perms, n_perm, phi, se, logits_rows, stream, who);
+}
+
+// The fine window game (cf_mark_fine.h): the wide game's checks on the players, the fine scan's on the region, the nesting, start and
+// lengths, then the windows and the rule.  `regions`: storage for the one region word every player carries (mark_check reads it; the
+// kernels do not).  With `lengths` the finest centre pad-mask rows of the region are read back once, as cf_perturbation_scan_fine does.
+static int mark_fine_game(cf_handle* h, const cf_batch* bt, const cf_mark_fine_opts* o, MarkGame* g, cf_mark_donor_opts* d, std::vector<unsigned>* regions,
+                          hipStream_t st, const char* who, int limit = kMarkWideMaxP) {
+    if (o) regions->assign((size_t)std::min(std::max(o->n_players, 1), kMarkWideMaxP), 1u);
+    *g = o ? MarkGame{o->n_players, o->player_marks, regions->data(), o->scale, nullptr} : MarkGame{};
+    if (mark_check(h, bt, o != nullptr, *g, who, limit)) return -1;
+    g->kw = (g->P + 31) / 32;
+    const cf_config& c = h->cfg;
+    const int nres = c.n_res, S = c.i_max, B = bt->B, slot = o->region - 1;
+    if (o->region < 0 || o->region > S) return fail("%s: region = %d outside [0, i_max = %d]", who, o->region, S);
+    int rf = 0;
+    for (int r = 1; r < nres; ++r)
+        if (c.binsizes[r] < c.binsizes[rf]) rf = r;
+    const int Lf = c.n_bins[rf], bf = c.binsizes[rf];
+    int rc = 0;
+    for (int r = 1; r < nres; ++r)
+        if (c.n_bins[r] < c.n_bins[rc]) rc = r;
+    for (int r = 0; r < nres; ++r) {      // (nested bin counts, in the scan's wording: the zoom starts from coarse windows)
+        if (c.n_bins[r] % c.n_bins[rc])
+            return fail("%s: n_bins[%d] = %d is not a multiple of the coarsest resolution's %d bins", who, r, c.n_bins[r], c.n_bins[rc]);
+        if (Lf % c.n_bins[r])
+            return fail("%s: n_bins[%d] = %d of the finest resolution is not a multiple of n_bins[%d] = %d", who, rf, Lf, r, c.n_bins[r]);
+    }
+    if (Lf > kFineMaxL) return fail("%s: the finest resolution has n_bins[%d] = %d bins; the window table holds at most %d", who, rf, Lf, kFineMaxL);
+    for (int r = nres; r < kMaxRes; ++r)
+        if (o->feats_out[r]) return fail("%s: feats_out[%d]: the model has %d resolutions", who, r, nres);
+    if (!o->player_lo || !o->player_hi) return fail("%s: null player_lo / player_hi", who);
+    for (int p = 0; p < g->P; ++p) {
+        const int lo = o->player_lo[p], hi = o->player_hi[p];
+        if (lo < 0 || lo >= hi) return fail("%s: player %d has the window [%d, %d): 0 <= lo < hi finest bins is required", who, p, lo, hi);
+    }
+    for (int b = 0; o->start && b < B; ++b)
+        if (o->start[b] < 0) return fail("%s: start[%d] = %d: a finest genomic bin >= 0", who, b, o->start[b]);
+    g->lo = o->player_lo, g->hi = o->player_hi, g->flip = o->flip, g->fine = o, g->rf = rf, g->bf = bf;
+    if (mark_rule(h, g, d, o->donor_promoter_feats, o->donor_pcre_feats, who)) return -1;
+    g->fine_words.assign(2 * (size_t)B, (unsigned)bf);
+    for (int b = 0; b < B; ++b) g->fine_words[b] = o->start ? (unsigned)o->start[b] : 0u;
+    if (o->lengths && B > 0) {
+        const uint8_t* rm = slot < 0 ? bt->promoter_mask_row[rf] : bt->pcre_mask_row[rf] + (long long)slot * bt->pcre_mask_stride[rf];
+        const long long rm_stride = slot < 0 ? bt->promoter_mask_stride[rf] : (long long)S * bt->pcre_mask_stride[rf];
+        std::vector<uint8_t> m((size_t)B * Lf);
+        HIP_TRY(hipMemcpy2DAsync(m.data(), Lf, rm, (size_t)rm_stride, Lf, B, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (int b = 0; b < B; ++b) {
+            int lo = Lf, hi = 0;
+            for (int k = 0; k < Lf; ++k)
+                if (!m[(size_t)b * Lf + k]) lo = std::min(lo, k), hi = k + 1;
+            const long long nf = hi > lo ? hi - lo : 0, len = o->lengths[b];
+            if (!nf) continue;      // a dummy slot: every player is a null player there, the length is not read
+            if (len <= (nf - 1) * bf || len > nf * bf)
+                return fail("%s: lengths[%d] = %lld outside ((n_f - 1) b_f, n_f b_f] = (%lld, %lld]: the region has n_f = %lld real bins of b_f = %d samples",
+                            who, b, len, (nf - 1) * bf, nf * bf, nf, bf);
+            g->fine_words[B + b] = (unsigned)(len - (nf - 1) * bf);
+        }
+    }
+    return 0;
+}
+
+extern "C" int cf_mark_fine_coalitions(cf_handle* h, const cf_batch* bt, const cf_mark_fine_opts* o, const uint32_t* keep, int n_coal, float* logits,
+                                       void* stream) {
+    const char* who = "cf_mark_fine_coalitions";
+    MarkGame g;
+    cf_mark_donor_opts d;
+    std::vector<unsigned> regions;
+    hipStream_t st = (hipStream_t)stream;
+    if (mark_fine_game(h, bt, o, &g, &d, &regions, st, who)) return -1;
+    if (!logits) return fail("%s: null logits", who);
+    if (mark_wide_upload(h, g, keep, n_coal, 0, st, who)) return -1;
+    return mark_rows(h, bt, g, n_coal, logits, st);
+}
+extern "C" int cf_mark_fine_shapley(cf_handle* h, const cf_batch* bt, const cf_mark_fine_opts* o, float* phi, float* logits_all, void* stream) {
+    const char* who = "cf_mark_fine_shapley";
+    MarkGame g;
+    cf_mark_donor_opts d;
+    std::vector<unsigned> regions;
+    if (mark_fine_game(h, bt, o, &g, &d, &regions, (hipStream_t)stream, who, kCoalMaxS)) return -1;
+    return mark_shapley_impl(h, bt, g, phi, logits_all, stream, who);
+}
+extern "C" int cf_mark_fine_shapley_sampled(cf_handle* h, const cf_batch* bt, const cf_mark_fine_opts* o, const uint8_t* perms, int n_perm, float* phi,
+                                            float* se, float* logits_rows, void* stream) {
+    const char* who = "cf_mark_fine_shapley_sampled";
+    MarkGame g;
+    cf_mark_donor_opts d;
+    std::vector<unsigned> regions;
+    if (mark_fine_game(h, bt, o, &g, &d, &regions, (hipStream_t)stream, who)) return -1;
+    return mark_sampled_impl(h, bt, g, perms, n_perm, phi, se, logits_rows, stream, who);
 }

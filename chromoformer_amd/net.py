@@ -1317,6 +1317,172 @@ class ChromoformerBase(nn.Module):
         return mark_window_shapley(self, dataset, donor_dataset, genes=genes, players=players, width=width, n_perm=n_perm, seed=seed,
                                    scale=scale, bsz=bsz, store=store, donor_store=donor_store)
 
+    def _mark_fine_opts(self, who, B, n_coal, region, players, width, n_windows, start, lengths, scale, donor, flip, return_feats):
+        """The options of the fine window game for a batch of B genes and n_coal(P) rows per gene -> (cf_mark_fine_opts, what it points
+        to, names, feats or None)."""
+        from .attribution import fine_window_players
+        Lf = self.n_bins[min(range(len(self.binsizes)), key=lambda r: self.binsizes[r])]
+        start = np.asarray(start, dtype=np.int64).reshape(-1)
+        if start.size == 1:
+            start = np.repeat(start, B)
+        if start.size != B:
+            raise ValueError("%s: start has %d entries for a batch of %d genes" % (who, start.size, B))
+        if start.size and (start.min() < -2 ** 31 or start.max() >= 2 ** 31):
+            raise ValueError("%s: start does not fit an int" % who)
+        start = start.astype(np.int32)
+        width = int(width)
+        if n_windows is None:
+            first = max(int(start.min()), 0) if B else 0
+            n_windows = max(-(-(Lf - first) // max(width, 1)), 1)
+        marks, lo, hi, names = fine_window_players(players, self.n_feats, width, n_windows)
+        opts = _lib.cf_mark_fine_opts()
+        opts.region, opts.n_players, opts.scale = int(region), len(marks), float(scale)
+        opts.player_marks, opts.player_lo, opts.player_hi = marks.ctypes.data, lo.ctypes.data, hi.ctypes.data
+        opts.start = start.ctypes.data
+        if lengths is not None:
+            lengths = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+            if lengths.size != B:
+                raise ValueError("%s: lengths has %d entries for a batch of %d genes" % (who, lengths.size, B))
+            lengths = np.clip(lengths, -1, 2 ** 31 - 1).astype(np.int32)      # (out of range either way: refused by the library)
+            opts.lengths = lengths.ctypes.data
+        flip = self._scan_flip(who, flip, B)
+        if flip is not None:
+            opts.flip = flip.data_ptr()
+        feats = None
+        if return_feats:
+            feats = {}
+            for r, b in enumerate(self.binsizes):
+                t = feats[b] = torch.empty(B, n_coal(len(marks)), self.n_bins[r], self.n_feats, device=self._device)      # (written in full by the library)
+                opts.feats_out[r] = t.data_ptr()
+        alive = (marks, lo, hi, start, lengths, flip) + (self._donor_feats(who, donor, B, opts) if donor is not None else ())
+        return opts, alive, names, feats
+
+    @torch.no_grad()
+    def mark_fine_window_coalitions(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                                    interaction_freq=None, keep=None, region=0, players="windows", width=1, n_windows=None, start=0,
+                                    lengths=None, scale=0.0, donor=None, flip=None, return_feats=False):
+        """The prediction under coalitions of FINE window players (cf_mark_fine_coalitions) -> logits [B, n_coal, n_out] on the model's
+        device, no autograd graph.  The game plays in one region (0 the promoter, 1 + j pCRE slot j); a player is a set of marks over a
+        window of bins of the FINEST resolution, relative to the gene's `start` (attribution.fine_window_players: "windows", "cells" at
+        `width` bins per window and `n_windows` windows, or (marks, (lo, hi)) pairs; at most 128).  `keep` as in mark_coalitions_wide.
+        Column c is the inference forward with the marks of every ABSENT player, inside its window, scaled by `scale` in raw-signal
+        space (0 erases; donor None) or taken from the donor (the forms of mark_donor_coalitions), at every resolution: a coarser bin
+        the absent windows cover wholly follows mark_window_coalitions' rule, one they cover in part is recomputed from its finest
+        children, weighted by their sample counts, as in perturbation_scan_fine; an element covered by several absent players changes
+        once.  start: an int or B ints, the first finest genomic bin per gene; n_windows: default the windows that reach the end of
+        the region from the smallest start; lengths, flip, return_feats ({binsize: [B, n_coal, n_bins, n_feats]}, the region's
+        features that row (b, c) read; returned as (logits, feats)): as in perturbation_scan_fine.  One absent player gives the row of
+        perturbation_scan_fine at that window, bit for bit; a window past the region's real bins changes nothing.  The packed forms of
+        the first argument and the effect on a pending backward() are those of mark_coalitions."""
+        from .attribution import mark_wide_words
+        who = "mark_fine_window_coalitions"
+        if keep is None:
+            raise ValueError("mark_fine_window_coalitions: keep is required: the coalitions (bit p set: player p present)")
+        bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        words = []
+
+        def n_coal(P):
+            words.append(mark_wide_words(keep, P, who))
+            return len(words[0])
+
+        opts, _alive, _names, feats = self._mark_fine_opts(who, bs.B, n_coal, region, players, width, n_windows, start, lengths, scale, donor, flip,
+                                                           return_feats)
+        words = words[0] if words else mark_wide_words(keep, opts.n_players, who)
+        logits = torch.empty(bs.B, len(words), self.n_out, device=self._device)      # (written in full by the library)
+        st = book()
+        _lib.check(_lib.lib().cf_mark_fine_coalitions(self._handle, C.byref(bs), C.byref(opts), words.ctypes.data, len(words), logits.data_ptr(), st),
+                   "cf_mark_fine_coalitions")
+        return (logits, feats) if return_feats else logits
+
+    @torch.no_grad()
+    def mark_fine_window_shapley(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                                 interaction_freq=None, region=0, players="windows", width=1, n_windows=None, start=0, lengths=None, scale=0.0,
+                                 donor=None, flip=None, return_coalitions=False, return_feats=False):
+        """Exact Shapley values of at most 16 fine window players (cf_mark_fine_shapley) -> (phi, info) with the keys of
+        mark_window_shapley (info["feats"] with return_feats): which 200 bp of the peak carries the prediction?  Neighbouring fine windows
+        share the credit here, where the leave-one-out perturbation_scan_fine scores redundant ones near zero.  Everything else as in
+        mark_fine_window_coalitions; a null player (a window past the region's real bins, a dummy slot, a donor that agrees with the gene
+        inside the window) has phi exactly 0."""
+        who = "mark_fine_window_shapley"
+        bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+
+        def n_coal(P):
+            if P > 16:
+                raise ValueError("%s: %d players; the exact game takes 1..16: choose a larger width or mark_fine_window_shapley_sampled" % (who, P))
+            return 1 << P
+
+        opts, _alive, names, feats = self._mark_fine_opts(who, bs.B, n_coal, region, players, width, n_windows, start, lengths, scale, donor, flip,
+                                                          return_feats)
+        P = opts.n_players
+        n = n_coal(P)
+        rows = torch.empty(bs.B, n, self.n_out, device=self._device)      # (both written in full by the library)
+        phi = torch.empty(bs.B, P, self.n_out, device=self._device)
+        st = book()
+        _lib.check(_lib.lib().cf_mark_fine_shapley(self._handle, C.byref(bs), C.byref(opts), phi.data_ptr(), rows.data_ptr(), st), "cf_mark_fine_shapley")
+        absent = "erased" if donor is None else "donor"
+        info = {"logits": rows[:, n - 1].clone(), absent: rows[:, 0].clone(), "players": names}
+        info["delta"] = phi.sum(1) - (info["logits"] - info[absent])
+        if return_coalitions:
+            info["coalitions"] = rows
+        if return_feats:
+            info["feats"] = feats
+        return phi, info
+
+    @torch.no_grad()
+    def mark_fine_window_shapley_sampled(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                                         interaction_freq=None, region=0, players="windows", width=1, n_windows=None, start=0, lengths=None,
+                                         n_perm=64, seed=0, permutations=None, scale=0.0, donor=None, flip=None, return_rows=False,
+                                         return_feats=False):
+        """Permutation-sampled Shapley values of up to 128 fine window players (cf_mark_fine_shapley_sampled) -> (phi, info) with the
+        keys, the row layout and the estimator of mark_shapley_sampled (info["feats"] with return_feats): which mark in which 200 bp?
+        region, players, width, n_windows, start, lengths, scale, donor and flip as in mark_fine_window_coalitions; n_perm, seed and
+        permutations as in mark_shapley_sampled.  A null player has phi and stderr exactly 0."""
+        from .attribution import shapley_permutations
+        who = "mark_fine_window_shapley_sampled"
+        bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        got = {}
+
+        def n_coal(P):
+            if "perms" not in got:
+                if permutations is None:
+                    got["perms"] = shapley_permutations(P, n_perm, seed)
+                else:
+                    given = np.asarray(permutations.cpu() if hasattr(permutations, "cpu") else permutations)
+                    if given.ndim != 2 or given.shape[0] < 1 or given.shape[1] != P or given.dtype.kind not in "iu" or given.min() < 0 or given.max() >= P:
+                        raise ValueError("%s: permutations must be an integer array [n_perm >= 1, P = %d] with entries in [0, P)" % (who, P))
+                    got["perms"] = np.ascontiguousarray(given, dtype=np.uint8)
+            return 2 + len(got["perms"]) * (P - 1)
+
+        opts, _alive, names, feats = self._mark_fine_opts(who, bs.B, n_coal, region, players, width, n_windows, start, lengths, scale, donor, flip,
+                                                          return_feats)
+        P = opts.n_players
+        R = n_coal(P)
+        perms = got["perms"]
+        n = len(perms)
+        rows = torch.empty(bs.B, R, self.n_out, device=self._device)      # (all three written in full by the library)
+        phi = torch.empty(bs.B, P, self.n_out, device=self._device)
+        se = torch.empty(bs.B, P, self.n_out, device=self._device)
+        st = book()
+        _lib.check(_lib.lib().cf_mark_fine_shapley_sampled(self._handle, C.byref(bs), C.byref(opts), perms.ctypes.data, n, phi.data_ptr(),
+                                                           se.data_ptr(), rows.data_ptr(), st), "cf_mark_fine_shapley_sampled")
+        info = {"logits": rows[:, 1].clone(), "absent": rows[:, 0].clone(), "stderr": se, "names": names, "permutations": perms}
+        info["delta"] = phi.sum(1) - (info["logits"] - info["absent"])
+        if return_rows:
+            info["rows"] = rows
+        if return_feats:
+            info["feats"] = feats
+        return phi, info
+
+    def mark_fine_window_shapley_dataset(self, dataset, donor_dataset=None, genes=None, region="promoter", zoom=1, coarse_width=1, width=2,
+                                         players="windows", n_perm=64, seed=0, scale=0.0, target=None, bsz=None, store=None, donor_store=None):
+        """Shapley values of fine window players over the genes of a ChromoformerDataset, zooming from the coarse window game, against a
+        donor cell type's dataset if one is given, windows in genomic coordinates (chromoformer_amd.attribution.mark_fine_window_shapley,
+        a generator of per-gene dicts)."""
+        from .attribution import mark_fine_window_shapley
+        return mark_fine_window_shapley(self, dataset, donor_dataset, genes=genes, region=region, zoom=zoom, coarse_width=coarse_width, width=width,
+                                        players=players, n_perm=n_perm, seed=seed, scale=scale, target=target, bsz=bsz, store=store,
+                                        donor_store=donor_store)
+
     def raw_signal_gradients(self, dataset, genes=None, target=None, times_input=False, bsz=None):
         """Raw-signal saliency of the genes of a ChromoformerDataset: the gradient (or gradient x input) of logit column `target` with
         respect to the raw fp16 signals, per gene one track per histone mark for the promoter window and every pCRE, in genomic

@@ -307,6 +307,44 @@ def write_mark_window_values(model, ds, donor_ds, store, donor_store, bsz, gene_
         np.savez(f, **out)
 
 
+def write_mark_fine_window_values(model, ds, donor_ds, store, donor_store, bsz, gene_ids, path, regression=False, region="promoter", width=2,
+                                  players="windows", zoom=1, n_perm=64, seed=0, scale=0.0):
+    """Shapley values of FINE window players (model.mark_fine_window_shapley_dataset: the coarse window game first, then the fine game
+    inside each gene's `zoom` most important coarse windows) of every gene of a device-resident store, in store order, in LOGIT space
+    of the prediction's column, into `path`, an .npz with gene_ids [n], players [P] (the fine game's names, windows relative to the
+    zoomed coarse window), exact (whether the fine game was exact), zoom int64 [n, k] (the chosen coarse windows, most important first;
+    -1 where the gene has fewer), coarse_phi [n, n_cwin] (the coarse game's values; NaN past the region's real coarse windows), phi and
+    stderr [n, k, P] (stderr zeros when exact), logits [n], absent [n, k] (every fine player absent; phi[:, r] sums to logits - absent[:, r];
+    NaN where zoom is -1), null bool [n, k, P] (the player has no real window in the gene: phi = 0), chroms [n] (the region's
+    chromosome; "" without the region) and windows int64 [n, k, P, 2] (genomic start and end; -1 where null).  ds / donor_ds: the
+    datasets the stores were built from (strand, coordinates, lengths); donor_ds None: the scale rule."""
+    n, t = len(gene_ids), 0 if regression else 1
+    rows = list(model.mark_fine_window_shapley_dataset(ds, donor_ds, genes=list(gene_ids), region=region, zoom=zoom, width=width, players=players,
+                                                       n_perm=n_perm, seed=seed, scale=scale, bsz=bsz, store=store, donor_store=donor_store))
+    from .attribution import fine_window_players
+    rf, rc = int(np.argmin(model.binsizes)), int(np.argmin(model.n_bins))
+    names = fine_window_players(players, model.n_feats, width, -(-(model.n_bins[rf] // model.n_bins[rc]) // width))[3]
+    P, k, Pc = len(names), int(zoom), model.n_bins[rc]
+    out = dict(gene_ids=np.array(list(gene_ids)), players=np.array(names), exact=np.array(bool(rows[0]["exact"])),
+               zoom=np.full((n, k), -1, dtype=np.int64), coarse_phi=np.full((n, Pc), np.nan, dtype=np.float32),
+               phi=np.zeros((n, k, P), dtype=np.float32), stderr=np.zeros((n, k, P), dtype=np.float32),
+               logits=np.array([r["logits"][t] for r in rows], dtype=np.float32), absent=np.full((n, k), np.nan, dtype=np.float32),
+               null=np.ones((n, k, P), dtype=bool), chroms=np.array([r["region"][0] if r["region"] else "" for r in rows]),
+               windows=np.full((n, k, P, 2), -1, dtype=np.int64))
+    for i, r in enumerate(rows):
+        out["zoom"][i, :len(r["zoom"])] = r["zoom"]
+        out["coarse_phi"][i, :len(r["coarse_phi"])] = r["coarse_phi"][:, t]
+        out["absent"][i, :len(r["absent"])] = r["absent"][:, t]
+        at = (i, r["rank"], r["index"])
+        out["phi"][at], out["null"][at] = r["phi"][:, t], False
+        if r["stderr"] is not None:
+            out["stderr"][at] = r["stderr"][:, t]
+        if len(r["windows"]):
+            out["windows"][at] = np.array([w[1:] for w in r["windows"]], dtype=np.int64)
+    with open(path, "wb") as f:      # (a file object: np.savez would append .npz to a name without it)
+        np.savez(f, **out)
+
+
 def write_integrated_gradients(model, store, bsz, ig_dir, n_steps=50, method="gausslegendre", target=None):
     """Integrated gradients of every gene of a device-resident store, in store order, into `ig_dir`: promoter_feats_{b}.npy
     [n, L, F], pcre_feats_{b}.npy [n, i_max, L, F], interaction_freq.npy [n, T, T] and delta.npy [n] (float32 .npy memory maps;
@@ -524,7 +562,9 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
             mark_donor_epistasis_out=None, mark_sampled_shapley_out=None, mark_donor_sampled_shapley_out=None, mark_sampled_players="cells",
             mark_perms=64, mark_seed=0, window_shapley_out=None, window_donor_shapley_out=None, window_players="promoter", window_width=1,
             window_perms=64, window_seed=0, window_scale=0.0, raw_donor_ig_dir=None, fine_scan_out=None, fine_scan_region="promoter",
-            fine_scan_width=1, fine_scan_stride=None, fine_scan_zoom=None, fine_scan_scale=0.0):
+            fine_scan_width=1, fine_scan_stride=None, fine_scan_zoom=None, fine_scan_scale=0.0, fine_window_shapley_out=None,
+            fine_window_donor_shapley_out=None, fine_window_region="promoter", fine_window_width=2, fine_window_players="windows",
+            fine_window_zoom=1, fine_window_perms=64, fine_window_seed=0, fine_window_scale=0.0):
     """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file.  attention_dir / embeddings_out: also
     write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps); pcre_ablation_out:
     the predictions with each pCRE deleted (write_pcre_ablation); ig_dir: integrated gradients of every gene
@@ -547,7 +587,10 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     signals against the donor cell type's signals of donor_npy_dir, one .npz per gene (write_raw_integrated_gradients with the donor's
     dataset; ig_steps, ig_method and ig_target apply; needs the raw .npy files of both cell types); fine_scan_out: the fine-resolution
     perturbation scan of every gene, one .npz (write_perturbation_scan_fine; fine_scan_region -- "promoter" or a pCRE slot --,
-    fine_scan_width, fine_scan_stride, fine_scan_zoom and fine_scan_scale apply; served by a packed store as well)."""
+    fine_scan_width, fine_scan_stride, fine_scan_zoom and fine_scan_scale apply; served by a packed store as well);
+    fine_window_shapley_out / fine_window_donor_shapley_out: Shapley values of fine window players inside each gene's most important
+    coarse windows, under the scale rule (fine_window_scale applies) / against the donor (write_mark_fine_window_values;
+    fine_window_region, fine_window_width, fine_window_players, fine_window_zoom, fine_window_perms and fine_window_seed apply)."""
     seed_everything(seed)
     meta = pd.read_csv(meta_path)
     genes = meta.gene_id.tolist()
@@ -556,7 +599,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         raw_ds = ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=regression)
         require_raw_signals(raw_ds)      # (before anything is computed)
     from . import pack
-    donor_out = mark_donor_shapley_out or mark_donor_epistasis_out or mark_donor_sampled_shapley_out or window_donor_shapley_out
+    donor_out = (mark_donor_shapley_out or mark_donor_epistasis_out or mark_donor_sampled_shapley_out or window_donor_shapley_out
+                 or fine_window_donor_shapley_out)
     raw_donor_ds = None
     if raw_donor_ig_dir:      # (before anything is computed)
         from .attribution import same_regions
@@ -570,11 +614,16 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         from .attribution import window_players as window_game
         window_game(window_players, 7, i_max, w_max // max(binsizes), window_width)
         window_ds = ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False)
+    fine_window_ds = None
+    if fine_window_shapley_out or fine_window_donor_shapley_out:      # (strand, coordinates, lengths; refusals before anything is computed)
+        from .attribution import fine_window_players as fine_window_game
+        fine_window_game(fine_window_players, 7, fine_window_width, -(-(max(binsizes) // min(binsizes)) // max(int(fine_window_width), 1)))
+        fine_window_ds = ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False)
     if donor_out:      # (before anything is computed)
         from .attribution import same_regions
         if not donor_npy_dir:
             raise ValueError("predict: mark_donor_shapley_out / mark_donor_epistasis_out / mark_donor_sampled_shapley_out / "
-                             "window_donor_shapley_out need donor_npy_dir")
+                             "window_donor_shapley_out / fine_window_donor_shapley_out need donor_npy_dir")
         donor_ds = ChromoformerDataset(donor_meta or meta_path, donor_npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False)
         same_regions(ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False), donor_ds)
     packed = pack.find(npy_dir, store_path, list(binsizes), i_max, w_prom, w_max, 7, genes, meta=meta)
@@ -614,6 +663,10 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         if window_donor_shapley_out:
             write_mark_window_values(model, window_ds, donor_ds, store, donor_store, bsz, genes, window_donor_shapley_out, regression, window_players,
                                      window_width, window_perms, window_seed)
+        if fine_window_donor_shapley_out:
+            write_mark_fine_window_values(model, fine_window_ds, donor_ds, store, donor_store, bsz, genes, fine_window_donor_shapley_out, regression,
+                                          fine_window_region, fine_window_width, fine_window_players, fine_window_zoom, fine_window_perms,
+                                          fine_window_seed)
         del donor_store
     if mark_sampled_shapley_out:
         write_mark_sampled_values(model, store, None, bsz, genes, mark_sampled_shapley_out, regression, mark_sampled_players, mark_perms, mark_seed,
@@ -621,6 +674,9 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     if window_shapley_out:
         write_mark_window_values(model, window_ds, None, store, None, bsz, genes, window_shapley_out, regression, window_players, window_width,
                                  window_perms, window_seed, window_scale)
+    if fine_window_shapley_out:
+        write_mark_fine_window_values(model, fine_window_ds, None, store, None, bsz, genes, fine_window_shapley_out, regression, fine_window_region,
+                                      fine_window_width, fine_window_players, fine_window_zoom, fine_window_perms, fine_window_seed, fine_window_scale)
     if ig_dir:
         write_integrated_gradients(model, store, bsz, ig_dir, ig_steps, ig_method, ig_target)
     if fine_scan_out:      # (strand, coordinates and region lengths come from the metadata)
@@ -750,6 +806,23 @@ def build_parser():
     ap.add_argument("--window-seed", type=int, default=None, help="seed of the sampled orders (default 0)")
     ap.add_argument("--window-scale", type=float, default=None, help="what an absent player's raw signal is scaled by inside its window: 0 "
                     "erases it (default); --window-shapley-out only")
+    from .attribution import FINE_WINDOW_PLAYER_SPECS
+    ap.add_argument("--fine-window-shapley-out", default=None, help="also write the Shapley values of FINE window players -- stretches of "
+                    "finest bins inside each gene's most important coarse windows (the coarse window game runs first) -- to this .npz file, in "
+                    "metadata order and in LOGIT space of the prediction's column: gene_ids, players (names), exact, zoom [n_genes, k] (the "
+                    "chosen coarse windows), coarse_phi, phi and stderr [n_genes, k, P], logits, absent [n_genes, k], null, chroms and "
+                    "windows [n_genes, k, P, 2] (genomic start and end) (model.mark_fine_window_shapley_dataset)")
+    ap.add_argument("--fine-window-donor-shapley-out", default=None, help="the same against the donor cell type of --donor-npy-dir: an absent "
+                    "player's window takes the donor's signal, in the coarse and in the fine game")
+    ap.add_argument("--fine-window-region", default=None, help="the region the game plays in: promoter (default) or a pCRE slot 0..7")
+    ap.add_argument("--fine-window-width", type=int, default=None, help="window width in finest bins (default 2)")
+    ap.add_argument("--fine-window-players", default=None, choices=FINE_WINDOW_PLAYER_SPECS, help="all marks per fine window (windows, the "
+                    "default) or each mark per fine window (cells); at most 128: widen the windows")
+    ap.add_argument("--fine-window-zoom", type=int, default=None, help="coarse windows to zoom into per gene (default 1)")
+    ap.add_argument("--fine-window-perms", type=int, default=None, help="sampled orders when a game has more than 16 players (default 64)")
+    ap.add_argument("--fine-window-seed", type=int, default=None, help="seed of the sampled orders (default 0)")
+    ap.add_argument("--fine-window-scale", type=float, default=None, help="what an absent player's raw signal is scaled by inside its window: 0 "
+                    "erases it (default); --fine-window-shapley-out only")
     return ap
 
 
@@ -787,18 +860,18 @@ def main(argv=None):
         if v is not None and v < 1:
             ap.error("--fine-scan-%s must be at least 1" % name)
     donor_exact = args.mark_donor_shapley_out or args.mark_donor_epistasis_out
-    donor_out = donor_exact or args.mark_donor_sampled_shapley_out or args.window_donor_shapley_out
+    donor_out = donor_exact or args.mark_donor_sampled_shapley_out or args.window_donor_shapley_out or args.fine_window_donor_shapley_out
     if args.raw_donor_ig_dir and not args.donor_npy_dir:
         ap.error("--raw-donor-ig-dir needs --donor-npy-dir")
     if args.raw_donor_ig_dir and args.donor_store:
         ap.error("--raw-donor-ig-dir reads the donor's raw .npy signals; --donor-store does not serve it")
     sampled_out = args.mark_sampled_shapley_out or args.mark_donor_sampled_shapley_out
     if donor_out and not args.donor_npy_dir:
-        ap.error("--mark-donor-shapley-out / --mark-donor-epistasis-out / --mark-donor-sampled-shapley-out / --window-donor-shapley-out need "
-                 "--donor-npy-dir")
+        ap.error("--mark-donor-shapley-out / --mark-donor-epistasis-out / --mark-donor-sampled-shapley-out / --window-donor-shapley-out / "
+                 "--fine-window-donor-shapley-out need --donor-npy-dir")
     if not donor_out and not args.raw_donor_ig_dir and (args.donor_npy_dir or args.donor_meta or args.donor_store):
         ap.error("--donor-npy-dir / --donor-meta / --donor-store need --mark-donor-shapley-out, --mark-donor-epistasis-out or "
-                 "--mark-donor-sampled-shapley-out (or --window-donor-shapley-out)")
+                 "--mark-donor-sampled-shapley-out (or --window-donor-shapley-out, --fine-window-donor-shapley-out)")
     if not sampled_out and (args.mark_sampled_players is not None or args.mark_perms is not None or args.mark_seed is not None):
         ap.error("--mark-sampled-players / --mark-perms / --mark-seed need --mark-sampled-shapley-out or --mark-donor-sampled-shapley-out")
     if args.mark_perms is not None and args.mark_perms < 1:
@@ -828,6 +901,30 @@ def main(argv=None):
             window_players(args.window_players or "promoter", 7, 8, 20, 1 if args.window_width is None else args.window_width)
         except ValueError as e:
             ap.error(str(e))
+    fine_window_out = args.fine_window_shapley_out or args.fine_window_donor_shapley_out
+    if not fine_window_out and any(v is not None for v in (args.fine_window_region, args.fine_window_width, args.fine_window_players,
+                                                           args.fine_window_zoom, args.fine_window_perms, args.fine_window_seed)):
+        ap.error("--fine-window-region / --fine-window-width / --fine-window-players / --fine-window-zoom / --fine-window-perms / "
+                 "--fine-window-seed need --fine-window-shapley-out or --fine-window-donor-shapley-out")
+    if args.fine_window_scale is not None and not args.fine_window_shapley_out:
+        ap.error("--fine-window-scale needs --fine-window-shapley-out (the donor rule has no scale)")
+    if args.fine_window_scale is not None and not (args.fine_window_scale >= 0 and np.isfinite(args.fine_window_scale)):
+        ap.error("--fine-window-scale must be a finite factor >= 0")
+    fine_window_region = "promoter"
+    if args.fine_window_region not in (None, "promoter"):
+        if not args.fine_window_region.isdigit() or int(args.fine_window_region) >= 8:
+            ap.error("--fine-window-region must be promoter or a pCRE slot in [0, 8)")
+        fine_window_region = int(args.fine_window_region)
+    for name, v in (("width", args.fine_window_width), ("zoom", args.fine_window_zoom), ("perms", args.fine_window_perms)):
+        if v is not None and v < 1:
+            ap.error("--fine-window-%s must be at least 1" % name)
+    if fine_window_out:
+        from .attribution import fine_window_players
+        try:
+            width = 2 if args.fine_window_width is None else args.fine_window_width
+            fine_window_players(args.fine_window_players or "windows", 7, width, -(-20 // width))
+        except ValueError as e:
+            ap.error(str(e))
     meta, pred = predict(args.meta, args.npy_dir, args.weights, args.regression, progress=True, store_path=args.store,
                          attention_dir=args.attention_dir, embeddings_out=args.embeddings_out, pcre_ablation_out=args.pcre_ablation_out,
                          ig_dir=args.ig_dir, ig_steps=50 if args.ig_steps is None else args.ig_steps,
@@ -850,7 +947,14 @@ def main(argv=None):
                          window_scale=0.0 if args.window_scale is None else args.window_scale, raw_donor_ig_dir=args.raw_donor_ig_dir,
                          fine_scan_out=args.fine_scan_out, fine_scan_region=fine_region,
                          fine_scan_width=1 if args.fine_scan_width is None else args.fine_scan_width, fine_scan_stride=args.fine_scan_stride,
-                         fine_scan_zoom=args.fine_scan_zoom, fine_scan_scale=0.0 if args.fine_scan_scale is None else args.fine_scan_scale)
+                         fine_scan_zoom=args.fine_scan_zoom, fine_scan_scale=0.0 if args.fine_scan_scale is None else args.fine_scan_scale,
+                         fine_window_shapley_out=args.fine_window_shapley_out, fine_window_donor_shapley_out=args.fine_window_donor_shapley_out,
+                         fine_window_region=fine_window_region, fine_window_width=2 if args.fine_window_width is None else args.fine_window_width,
+                         fine_window_players=args.fine_window_players or "windows",
+                         fine_window_zoom=1 if args.fine_window_zoom is None else args.fine_window_zoom,
+                         fine_window_perms=64 if args.fine_window_perms is None else args.fine_window_perms,
+                         fine_window_seed=0 if args.fine_window_seed is None else args.fine_window_seed,
+                         fine_window_scale=0.0 if args.fine_window_scale is None else args.fine_window_scale)
     print("Predicting expressions for %d genes." % len(meta))
     meta["prediction"] = pred
     meta.to_csv(args.output, index=False)

@@ -619,6 +619,70 @@ int cf_mark_window_shapley(cf_handle* h, const cf_batch* batch, const cf_mark_wi
  * Refusals as above and as there. */
 int cf_mark_window_shapley_sampled(cf_handle* h, const cf_batch* batch, const cf_mark_window_opts* opts, const uint8_t* perms, int n_perm,
                                    float* phi, float* se, float* logits_rows, void* stream);
+/* The window game at the FINEST resolution (interpretation): which 200 bp of this peak?  Neighbouring fine windows of one peak are
+ * redundant almost by construction, which is where the leave-one-out map of cf_perturbation_scan_fine misleads most.  Notation is
+ * that of cf_perturbation_scan_fine: f = the finest resolution, R_r = n_bins[f] / n_bins[r], K_j = [j R_r, min((j + 1) R_r, n_f)) the
+ * finest children of bin j at resolution r, cnt_k = b_f except the last real finest bin (lengths[b] - (n_f - 1) b_f samples), cnt_j =
+ * the sum of cnt_k over K_j.
+ * The game plays in ONE region per call (region: 0 the promoter, 1 + j pCRE slot j).  Player p is (player_marks[p], [player_lo[p],
+ * player_hi[p])), 0 <= lo < hi, in finest genomic bins RELATIVE to start[b]: for gene b its window is [start[b] + lo, start[b] + hi),
+ * clipped to the region's real n_f.  Geometry (the extent from the centre pad-mask rows, flip for a mirrored promoter) is the
+ * scan's.  Coalitions are the kw = ceil(P / 32) words of cf_mark_coalitions_wide, bit set = PRESENT.  For a coalition
+ *   gone_f(k) = OR of player_marks[p] over the absent players whose clipped window holds finest bin k
+ * and for bin j of resolution r and mark m, C = {k in K_j : bit m in gone_f(k)}.  The element becomes
+ *   C empty        its own bits;
+ *   C = K_j        (always so at r = f) the scale rule: log1pf(s expm1f(u)), once however many absent players cover it; the donor
+ *                  rule: the bits of the donor's element at the same position;
+ *   otherwise      the scale rule:  S  = sum over k in C, ascending genomic k, of (double)cnt_k (double)expm1f(u_k),
+ *                                   m' = (float)((double)expm1f(u_j) + ((double)s - 1.0) S / (double)cnt_j),  u' = log1pf(m')
+ *                                   -- the partial rule of cf_perturbation_scan_fine operation for operation, no contraction, no clamp;
+ *                  the donor rule:  d_k bit-equal to u_k for every k in C: its own bits; else
+ *                                   D  = sum over k in C, ascending, of (double)cnt_k ((double)expm1f(d_k) - (double)expm1f(u_k)),
+ *                                   m' = (float)((double)expm1f(u_j) + D / (double)cnt_j),  u' = log1pf(m'),
+ *                                   d_k the donor's finest element of the same region, mark and position.
+ * C may differ from mark to mark in one bin, and any number of bins may be partly covered.  Masks and interaction_freq are the
+ * gene's own; every other region is copied verbatim.  Binning is linear per mark and bin sizes nest: this is the feature that binning
+ * the edited raw region gives, up to the rounding of the stored fp32 features, and exactly where a bin is wholly covered or untouched.
+ * One absent player gives the row and feats_out of cf_perturbation_scan_fine at that window, mark set and start, bit for bit; players
+ * whose windows are unions of whole coarse bins give the rows of cf_mark_window_coalitions restricted to the region. */
+typedef struct cf_mark_fine_opts {
+    int region;                                      /* 0 promoter, 1 + j pCRE slot j */
+    int n_players;                                   /* 1..128 (cf_mark_fine_shapley: 1..16) */
+    const unsigned* player_marks;                    /* host [n_players], read before the call returns */
+    const int* player_lo;                            /* host [n_players]: the window's first finest bin, relative to start[b] */
+    const int* player_hi;                            /* host [n_players]: one past the last */
+    const int* start;                                /* host [B] or NULL (all 0): gene b's first finest genomic bin */
+    const int* lengths;                              /* host [B] or NULL: the region's length in samples, as in cf_scan_fine_opts */
+    const uint8_t* flip;                             /* device [B] or NULL: the region of gene b is stored mirrored, as in cf_scan_fine_opts */
+    float scale;                                     /* the scale rule: used when every donor pointer is NULL */
+    const float* donor_promoter_feats[CF_MAX_RES];   /* all NULL: scale rule; all non-NULL below n_res: donor rule; mixed: refused */
+    const float* donor_pcre_feats[CF_MAX_RES];
+    float* feats_out[CF_MAX_RES];                    /* optional, device, [B, n_coal, n_bins[r], n_feats]: the edited region */
+} cf_mark_fine_opts;
+/* cf_mark_fine_coalitions: keep (HOST, n_coal * kw words), logits [B, n_coal, n_out], the chunking and the chunk buffers are those of
+ * cf_mark_window_coalitions; per chunk one k_mark_fine_expand (the donor rule: k_mark_fine_donor_expand), then the launches of
+ * cf_forward(save = 0) on the chunk:
+ *   cf_launch_counts fwd = ceil(B * n_coal / max_batch) * (1 + n_fwd).
+ * The words, the 3 P player words (marks, lo, hi), start and the tail counts travel in the device table the handle owns; no device
+ * buffer is added.  Deterministic (no atomics); the result does not depend on max_batch and row (b, c) equals cf_forward(save = 0) on
+ * the batch with feats_out[:, c] substituted, bit for bit.  Overwrites the activations a cf_forward(save >= 1) kept.  Parameters,
+ * gradients and moments are untouched.  A window past the real bins, a player in a dummy slot and a donor-rule player whose touched
+ * elements agree in both cell types are null players.
+ * Refused by name, before anything is launched: what cf_mark_coalitions_wide and cf_perturbation_scan_fine refuse (a region outside
+ * [0, i_max], a negative start, a lengths[b] outside ((n_f - 1) b_f, n_f b_f], non-nested n_bins, a feats_out above n_res); a null
+ * player_lo or player_hi; a window with lo < 0 or lo >= hi (the player's index is named); n_bins[f] > 512; mixed donor pointers. */
+int cf_mark_fine_coalitions(cf_handle* h, const cf_batch* batch, const cf_mark_fine_opts* opts, const uint32_t* keep, int n_coal, float* logits,
+                            void* stream);
+/* Exact Shapley values of P <= 16 fine window players: all 2^P words through the routine above (word m at column m; feats_out, if
+ * given, [B, 2^P, ...]), then the k_shapley of cf_mark_shapley.  phi [B, P, n_out]; logits_all [B, 2^P, n_out] or NULL (the
+ * handle-owned buffer).  A null player's phi is exactly 0.  fwd = that of cf_mark_fine_coalitions with n_coal = 2^P, plus 1.
+ * Refusals as above (null phi, n_players > 16). */
+int cf_mark_fine_shapley(cf_handle* h, const cf_batch* batch, const cf_mark_fine_opts* opts, float* phi, float* logits_all, void* stream);
+/* Permutation-sampled Shapley values of the fine window players: perms, the R = 2 + n_perm * (P - 1) rows per gene, k_perm_shapley,
+ * phi, the optional se and logits_rows and the launch count are those of cf_mark_shapley_sampled; a null player's phi and se are
+ * exactly 0.  Refusals as above and as there. */
+int cf_mark_fine_shapley_sampled(cf_handle* h, const cf_batch* batch, const cf_mark_fine_opts* opts, const uint8_t* perms, int n_perm, float* phi,
+                                 float* se, float* logits_rows, void* stream);
 /* torch.optim.AdamW.step (train.py:157, 196): decoupled weight decay, bias correction
  * from `step` (1-based), over [0, n_active). */
 int cf_adamw_step(cf_handle* h, float lr, float beta1, float beta2, float eps, float weight_decay,
