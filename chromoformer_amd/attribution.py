@@ -325,6 +325,33 @@ def fine_window_players(spec, n_feats, width=1, n_windows=1):
     return marks, lo, hi, names
 
 
+_BATCH_KEYS = ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq")      # forward()'s arguments, in order
+
+
+def _donor_pair(dd):
+    """The donor of a batch, from the donor store's batch dict -> (promoter_feats, pcre_feats), contiguous, by bin size."""
+    return ({b: t.contiguous() for b, t in dd["promoter_feats"].items()}, {b: t.contiguous() for b, t in dd["pcre_feats"].items()})
+
+
+def _region_index(who, region, S):
+    """"promoter" or a pCRE slot j -> the region index (0 the promoter, 1 + j pCRE slot j)."""
+    if region == "promoter":
+        return 0
+    if isinstance(region, str) or not 0 <= int(region) < S:
+        raise ValueError("%s: region %r; choose 'promoter' or a pCRE slot in [0, i_max = %d)" % (who, region, S))
+    return 1 + int(region)
+
+
+def _gene_region(ds, g, region, col0):
+    """Region `region` of gene g -> (chrom, start, end): the promoter window from its first stored column col0 on, or the pCRE; None
+    for a pCRE slot the gene does not have."""
+    if region == 0:
+        chrom, tss, _ = ds.genes[g]["tss"]
+        return (chrom, tss - 20000 + col0, tss - 20000 + col0 + min(ds.w_prom, 40000 - col0))
+    pc = ds.genes[g]["pcres"]
+    return tuple(pc[region - 1]) if region - 1 < len(pc) else None
+
+
 def _geometry_check(who, model, dataset, binsizes):
     """The model is on the device and the dataset has its geometry -> n_bins."""
     ds = dataset
@@ -733,7 +760,7 @@ def perturbation_scan(model, dataset, genes=None, regions="promoter", scale=0.0,
         ids = genes[lo:lo + chunk]
         B = len(ids)
         d = store.batch(list(range(lo, lo + B)))
-        args = tuple(d[k] for k in ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq"))
+        args = tuple(d[k] for k in _BATCH_KEYS)
         flip = [ds.genes[g]["tss"][2] != "+" for g in ids]
         per = [dict(gene_id=g, logits=None, mark_sets=list(mark_sets), regions=[], windows=[], scan=[]) for g in ids]
         has_of = {region: [region == 0 or region - 1 < len(ds.genes[g]["pcres"]) for g in ids] for region in regions}
@@ -752,11 +779,7 @@ def perturbation_scan(model, dataset, genes=None, regions="promoter", scale=0.0,
                     continue
                 real = np.flatnonzero(m[i])
                 n_win = int(real[-1] - real[0] + 1) if real.size else 0
-                if region == 0:
-                    chrom, tss, _ = ds.genes[g]["tss"]
-                    reg = (chrom, tss - 20000 + col0, tss - 20000 + col0 + min(ds.w_prom, 40000 - col0))
-                else:
-                    reg = tuple(ds.genes[g]["pcres"][region - 1])
+                reg = _gene_region(ds, g, region, col0)
                 per[i]["regions"].append(reg)
                 per[i]["windows"].append(scan_windows(reg[1], reg[2], bc, width, n_win))
                 per[i]["scan"].append(out[i, scan_row(0, 0, 0, K, W):].reshape(K, W, -1)[:, :n_win].copy())
@@ -813,12 +836,7 @@ def perturbation_scan_fine(model, dataset, genes=None, region="promoter", zoom=N
     n_bins = _geometry_check(who, model, ds, binsizes)
     genes, chunk = _genes_check(who, model, ds, genes, bsz)
     S, F, dev = ds.i_max, ds.n_feats, model._device
-    if region == "promoter":
-        region = 0
-    elif isinstance(region, str) or not 0 <= int(region) < S:
-        raise ValueError("%s: region %r; choose 'promoter' or a pCRE slot in [0, i_max = %d)" % (who, region, S))
-    else:
-        region = 1 + int(region)
+    region = _region_index(who, region, S)
     mark_sets = scan_mark_sets(mark_sets, F)
     K = len(mark_sets)
     width = int(width)
@@ -837,16 +855,9 @@ def perturbation_scan_fine(model, dataset, genes=None, region="promoter", zoom=N
         ids = genes[lo:lo + chunk]
         B = len(ids)
         d = store.batch(list(range(lo, lo + B)))
-        args = tuple(d[k] for k in ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq"))
+        args = tuple(d[k] for k in _BATCH_KEYS)
         flip = [region == 0 and ds.genes[g]["tss"][2] != "+" for g in ids]
-        regs = []
-        for g in ids:
-            if region == 0:
-                chrom, tss, _ = ds.genes[g]["tss"]
-                regs.append((chrom, tss - 20000 + col0, tss - 20000 + col0 + min(ds.w_prom, 40000 - col0)))
-            else:
-                pc = ds.genes[g]["pcres"]
-                regs.append(tuple(pc[region - 1]) if region - 1 < len(pc) else None)
+        regs = [_gene_region(ds, g, region, col0) for g in ids]
         lengths = [r[2] - r[1] if r else 0 for r in regs]
         kw = dict(region=region, scale=scale, width=width, stride=stride, mark_sets=mark_sets, lengths=lengths, flip=flip)
         per = [dict(gene_id=g, logits=None, mark_sets=list(mark_sets), region=regs[i], windows=[], scan=np.zeros((K, 0, model.n_out), np.float32))
@@ -912,7 +923,7 @@ def mark_shapley(model, dataset, genes=None, players="marks", scale=0.0, epistas
     for lo in range(0, len(genes), chunk):
         ids = genes[lo:lo + chunk]
         d = store.batch(list(range(lo, lo + len(ids))))
-        args = tuple(d[k] for k in ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq"))
+        args = tuple(d[k] for k in _BATCH_KEYS)
         phi, info = model.mark_shapley(*args, players=spec, scale=scale)
         phi, logits, erased = phi.cpu().numpy(), info["logits"].cpu().numpy(), info["erased"].cpu().numpy()
         eps = model.mark_epistasis(*args, players=spec, scale=scale)[0].cpu().numpy() if epistasis else None
@@ -983,18 +994,17 @@ def mark_donor_shapley(model, dataset, donor_dataset, genes=None, players="marks
     names = mark_players(spec, ds.n_feats, ds.i_max)[2]      # (refusals before anything is loaded)
     store = _resident_store("mark_donor_shapley", ds, genes, binsizes, model._device, store)
     donor_store = _resident_store("mark_donor_shapley", dn, genes, binsizes, model._device, donor_store)
-    keys = ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq")
     for lo in range(0, len(genes), chunk):
         ids = genes[lo:lo + chunk]
         idx = list(range(lo, lo + len(ids)))
         d, dd = store.batch(idx), donor_store.batch(idx)
-        args = tuple(d[k] for k in keys)
-        donor = ({b: t.contiguous() for b, t in dd["promoter_feats"].items()}, {b: t.contiguous() for b, t in dd["pcre_feats"].items()})
+        args = tuple(d[k] for k in _BATCH_KEYS)
+        donor = _donor_pair(dd)
         phi, info = model.mark_donor_shapley(*args, donor=donor, players=spec)
         phi, logits, don = phi.cpu().numpy(), info["logits"].cpu().numpy(), info["donor"].cpu().numpy()
         eps = model.mark_donor_epistasis(*args, donor=donor, players=spec)[0].cpu().numpy() if epistasis else None
         with torch.no_grad():
-            pred = model(*(dd[k] for k in keys)).cpu().numpy()
+            pred = model(*(dd[k] for k in _BATCH_KEYS)).cpu().numpy()
         for i, g in enumerate(ids):
             out = dict(gene_id=g, phi=phi[i].copy(), logits=logits[i].copy(), donor=don[i].copy(), donor_prediction=pred[i].copy(),
                        players=list(names))
@@ -1035,7 +1045,6 @@ def mark_shapley_sampled(model, dataset, donor_dataset=None, genes=None, players
     store = _resident_store(who, ds, genes, binsizes, model._device, store)
     if dn is not None:
         donor_store = _resident_store(who, dn, genes, binsizes, model._device, donor_store)
-    keys = ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq")
     for lo in range(0, len(genes), chunk):
         ids = genes[lo:lo + chunk]
         idx = list(range(lo, lo + len(ids)))
@@ -1043,8 +1052,8 @@ def mark_shapley_sampled(model, dataset, donor_dataset=None, genes=None, players
         donor = None
         if dn is not None:
             dd = donor_store.batch(idx)
-            donor = ({b: t.contiguous() for b, t in dd["promoter_feats"].items()}, {b: t.contiguous() for b, t in dd["pcre_feats"].items()})
-        phi, info = model.mark_shapley_sampled(*(d[k] for k in keys), players=spec, permutations=perms, scale=scale, donor=donor)
+            donor = _donor_pair(dd)
+        phi, info = model.mark_shapley_sampled(*(d[k] for k in _BATCH_KEYS), players=spec, permutations=perms, scale=scale, donor=donor)
         phi, se, logits, absent = phi.cpu().numpy(), info["stderr"].cpu().numpy(), info["logits"].cpu().numpy(), info["absent"].cpu().numpy()
         for i, g in enumerate(ids):
             yield dict(gene_id=g, phi=phi[i].copy(), stderr=se[i].copy(), logits=logits[i].copy(), absent=absent[i].copy(), players=list(names),
@@ -1111,7 +1120,6 @@ def mark_window_shapley(model, dataset, donor_dataset=None, genes=None, players=
     store = _resident_store(who, ds, genes, binsizes, model._device, store)
     if dn is not None:
         donor_store = _resident_store(who, dn, genes, binsizes, model._device, donor_store)
-    keys = ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq")
     for lo in range(0, len(genes), chunk):
         ids = genes[lo:lo + chunk]
         B = len(ids)
@@ -1120,9 +1128,9 @@ def mark_window_shapley(model, dataset, donor_dataset=None, genes=None, players=
         donor = None
         if dn is not None:
             dd = donor_store.batch(idx)
-            donor = ({b: t.contiguous() for b, t in dd["promoter_feats"].items()}, {b: t.contiguous() for b, t in dd["pcre_feats"].items()})
+            donor = _donor_pair(dd)
         flip = [ds.genes[g]["tss"][2] != "+" for g in ids]
-        args = tuple(d[k] for k in keys)
+        args = tuple(d[k] for k in _BATCH_KEYS)
         if exact:
             phi, info = model.mark_window_shapley(*args, players=spec, width=width, scale=scale, donor=donor, flip=flip)
             absent = info["erased" if donor is None else "donor"].cpu().numpy()
@@ -1136,8 +1144,7 @@ def mark_window_shapley(model, dataset, donor_dataset=None, genes=None, players=
         cm = d["pcre_pad_masks"][bc].reshape(B, ds.i_max, -1, W)
         cm = cm[:, :, cm.shape[2] // 2].cpu().numpy() == 0
         for i, g in enumerate(ids):
-            chrom, tss, _ = ds.genes[g]["tss"]
-            regions = {0: (chrom, tss - 20000 + col0, tss - 20000 + col0 + min(ds.w_prom, 40000 - col0))}
+            regions = {0: _gene_region(ds, g, 0, col0)}
             regions.update({1 + j: tuple(p) for j, p in enumerate(ds.genes[g]["pcres"][:ds.i_max])})
             n_real = {}
             for rho in regions:
@@ -1188,12 +1195,7 @@ def mark_fine_window_shapley(model, dataset, donor_dataset=None, genes=None, reg
     if dn is not None:
         same_regions(ds, dn, genes)
     S, F = ds.i_max, ds.n_feats
-    if region == "promoter":
-        region = 0
-    elif isinstance(region, str) or not 0 <= int(region) < S:
-        raise ValueError("%s: region %r; choose 'promoter' or a pCRE slot in [0, i_max = %d)" % (who, region, S))
-    else:
-        region = 1 + int(region)
+    region = _region_index(who, region, S)
     zoom, coarse_width, width = int(zoom), int(coarse_width), int(width)
     if zoom < 1:
         raise ValueError("%s: zoom = %d: at least 1 coarse window" % (who, zoom))
@@ -1217,7 +1219,6 @@ def mark_fine_window_shapley(model, dataset, donor_dataset=None, genes=None, reg
     store = _resident_store(who, ds, genes, binsizes, model._device, store)
     if dn is not None:
         donor_store = _resident_store(who, dn, genes, binsizes, model._device, donor_store)
-    keys = ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq")
     for lo in range(0, len(genes), chunk):
         ids = genes[lo:lo + chunk]
         B = len(ids)
@@ -1226,17 +1227,10 @@ def mark_fine_window_shapley(model, dataset, donor_dataset=None, genes=None, reg
         donor = None
         if dn is not None:
             dd = donor_store.batch(idx)
-            donor = ({b: t.contiguous() for b, t in dd["promoter_feats"].items()}, {b: t.contiguous() for b, t in dd["pcre_feats"].items()})
-        args = tuple(d[k] for k in keys)
+            donor = _donor_pair(dd)
+        args = tuple(d[k] for k in _BATCH_KEYS)
         flip = [region == 0 and ds.genes[g]["tss"][2] != "+" for g in ids]
-        regs = []
-        for g in ids:
-            if region == 0:
-                chrom, tss, _ = ds.genes[g]["tss"]
-                regs.append((chrom, tss - 20000 + col0, tss - 20000 + col0 + min(ds.w_prom, 40000 - col0)))
-            else:
-                pc = ds.genes[g]["pcres"]
-                regs.append(tuple(pc[region - 1]) if region - 1 < len(pc) else None)
+        regs = [_gene_region(ds, g, region, col0) for g in ids]
         lengths = [r[2] - r[1] if r else 0 for r in regs]
         if cperms is None:
             cphi, info = model.mark_window_shapley(*args, players=coarse, scale=scale, donor=donor, flip=flip)

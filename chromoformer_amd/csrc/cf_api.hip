@@ -38,6 +38,7 @@ using namespace cf;
 #include "cf_api_fwd.h"
 #include "cf_api_bwd.h"
 #include "cf_api_attrib.h"
+#include "cf_api_marks.h"
 
 // ------------------------------------------------------------------------------------
 // C ABI: host-only part

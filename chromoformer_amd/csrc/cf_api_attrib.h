@@ -1,5 +1,7 @@
 // cf_api_attrib.h -- host side of the attribution entry points (input gradients, attention maps, pCRE deletion, pCRE coalitions, integrated
-// gradients, perturbation scan and its fine-resolution form, histone-mark coalitions, their donor form, the wide game and its sampled Shapley values, the window game).  Part of cf_api.hip's single translation unit: included there behind cf_api_bwd.h, not on its own.
+// gradients, perturbation scan and its fine-resolution form) and what the row-expanding ones share with the histone-mark games of
+// cf_api_marks.h: the chunk workspace and loop, the region geometry, the exact games' words and reducers.  Part of cf_api.hip's single
+// translation unit: included there behind cf_api_bwd.h, not on its own.
 #pragma once
 
 // k_input_grad's dynamic LDS size; the first call sets the kernel's attribute.  0: that failed (`who`: the entry point, for the error text).
@@ -247,13 +249,37 @@ static int attrib_ws(cf_handle* h, const char* who) {
     return 0;
 }
 
+// One launch of an expand kernel (kIgxThreads / kAblThreads / kRowThreads threads, no LDS) with its argument struct, counted.
+template <class Args>
+static int launch_expand(void (*kernel)(Args), const char* name, dim3 grid, int threads, const Args& a, hipStream_t st) {
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, st, a);
+    LAUNCH_CHECK(name);
+    return 0;
+}
+
+// The chunk loop of the row-expanding entry points.  Per chunk of at most max_batch of the `rows` rows: expand(g0, n) launches the
+// kernel that writes rows g0 .. g0 + n - 1 into the chunk workspace, then an inference forward on the chunk's batch `cb` writes the
+// chunk's contiguous slice of `logits` -- the launches of cf_forward(save = 0) when `trunk` (k_attc2 takes as many regions per
+// workgroup as for the caller's `genes` genes, ag_genes), else Regulation + head alone, on rows the kernel has put in place.
+template <class Expand>
+static int chunk_forward(cf_handle* h, cf_batch* cb, long long rows, float* logits, bool trunk, int genes, hipStream_t st, Expand expand) {
+    const int cap = h->cfg.max_batch, n_out = h->cfg.n_out;
+    for (long long g0 = 0; g0 < rows; g0 += cap) {
+        const int n = (int)std::min<long long>(cap, rows - g0);
+        if (expand(g0, n)) return -1;
+        cb->B = n;
+        if ((trunk && forward_trunk(h, cb, 0, st, genes)) || forward_reg_head(h, cb, logits + (size_t)g0 * n_out, 0, st, nullptr)) return -1;
+    }
+    return 0;
+}
+
 // The shared host routine of cf_pcre_ablation and the coalition entry points (cf_coalition.h): the trunk once on the B genes,
 // k_pcre_stash, then per chunk of at most max_batch of the B * n_coal rows (gene-major; row (b, k) is word tab[k], a device table) one
 // k_coalition_expand and the Regulation + head launches of an inference forward on that chunk, writing the chunk's contiguous slice of
 // `logits`.  The callers have checked the batch and called attrib_ws.
 static int coalition_rows(cf_handle* h, const cf_batch* bt, const unsigned* tab, int n_coal, float* logits, hipStream_t st) {
     const cf_config& c = h->cfg;
-    const int B = bt->B, T = c.i_max + 1, nres = c.n_res, cap = c.max_batch;
+    const int B = bt->B, T = c.i_max + 1, nres = c.n_res;
     const long long launches0 = g_launches;
     if (forward_trunk(h, bt, 0, st) || stash_trunk_output(h, B, h->aw.stash, st)) return -1;
     CoalExpandArgs ea;
@@ -271,15 +297,11 @@ static int coalition_rows(cf_handle* h, const cf_batch* bt, const unsigned* tab,
     cb.interaction_freq = h->aw.row[2 * kMaxRes];
     ea.keep = tab;
     ea.n_coal = n_coal, ea.T = T, ea.row4 = T * c.d_emb / 4;
-    const long long rows = (long long)B * n_coal;
-    for (long long g0 = 0; g0 < rows; g0 += cap) {
-        const int n = (int)std::min<long long>(cap, rows - g0);
-        ea.g0 = g0;
-        hipLaunchKernelGGL(k_coalition_expand, dim3(n, nres), dim3(kAblThreads), 0, st, ea);
-        LAUNCH_CHECK("k_coalition_expand");
-        cb.B = n;
-        if (forward_reg_head(h, &cb, logits + (size_t)g0 * c.n_out, 0, st, nullptr)) return -1;
-    }
+    if (chunk_forward(h, &cb, (long long)B * n_coal, logits, false, B, st, [&](long long g0, int n) {
+            ea.g0 = g0;
+            return launch_expand(k_coalition_expand, "k_coalition_expand", dim3(n, nres), kAblThreads, ea, st);
+        }))
+        return -1;
     forward_counted(h, launches0);
     return 0;
 }
@@ -320,56 +342,72 @@ static float* coalition_out_rows(cf_handle* h, float* callers, long long per, co
     return h->aw.own_rows.need((size_t)h->cfg.max_batch * per * h->cfg.n_out, 0, who) ? nullptr : (float*)h->aw.own_rows;
 }
 
-// All 2^i_max coalitions through coalition_upload + coalition_rows (word m at column m), then k_shapley.
-extern "C" int cf_pcre_shapley(cf_handle* h, const cf_batch* bt, float* phi, float* logits_all, void* stream) {
-    const char* who = "cf_pcre_shapley";
-    if (attrib_open(h, bt, false, who)) return -1;
-    if (!phi) return fail("%s: null phi", who);
-    const cf_config& c = h->cfg;
-    const int S = c.i_max, n = 1 << S;
-    float* rows = coalition_out_rows(h, logits_all, n, who);
-    if (!rows) return -1;
-    std::vector<uint32_t> keep(n);
-    for (int m = 0; m < n; ++m) keep[m] = (uint32_t)m;
-    hipStream_t st = (hipStream_t)stream;
-    if (coalition_upload(h, keep.data(), n, st, who) || coalition_rows(h, bt, h->aw.words, n, rows, st)) return -1;
+// The two exact games on P players (the pCRE slots, or the players of a mark game), their coalition words and their reducers.
+// all_words: every coalition, word m at column m; launch_shapley: k_shapley on the [B, 2^P, n_out] rows.
+static std::vector<uint32_t> all_words(int P) {
+    std::vector<uint32_t> keep((size_t)1 << P);
+    for (size_t m = 0; m < keep.size(); ++m) keep[m] = (uint32_t)m;
+    return keep;
+}
+static int launch_shapley(cf_handle* h, int B, int P, const float* rows, float* phi, hipStream_t st) {
     ShapleyArgs sa;
     memset(&sa, 0, sizeof sa);
-    sa.v = rows, sa.phi = phi, sa.S = S, sa.n_out = c.n_out;
+    sa.v = rows, sa.phi = phi, sa.S = P, sa.n_out = h->cfg.n_out;
     double fact[kCoalMaxS + 1] = {1.0};
-    for (int k = 1; k <= S; ++k) fact[k] = fact[k - 1] * k;
-    for (int k = 0; k < S; ++k) sa.w[k] = (float)(fact[k] * fact[S - k - 1] / fact[S]);
-    hipLaunchKernelGGL(k_shapley, dim3(bt->B, S), dim3(kShapThreads), 0, st, sa);
+    for (int k = 1; k <= P; ++k) fact[k] = fact[k - 1] * k;
+    for (int k = 0; k < P; ++k) sa.w[k] = (float)(fact[k] * fact[P - k - 1] / fact[P]);
+    hipLaunchKernelGGL(k_shapley, dim3(B, P), dim3(kShapThreads), 0, st, sa);
     LAUNCH_CHECK("k_shapley");
     forward_one_more(h);
     return 0;
 }
+// pair_words: the 1 + P + P (P - 1) / 2 pair-deletion coalitions (N = 2^P - 1; N without i; N without i and j, i < j);
+// launch_epistasis: k_epistasis on those rows.
+static std::vector<uint32_t> pair_words(int P) {
+    const uint32_t N = (1u << P) - 1u;
+    std::vector<uint32_t> keep;
+    keep.push_back(N);
+    for (int i = 0; i < P; ++i) keep.push_back(N & ~(1u << i));
+    for (int i = 0; i < P; ++i)
+        for (int j = i + 1; j < P; ++j) keep.push_back(N & ~(1u << i) & ~(1u << j));
+    return keep;
+}
+static int launch_epistasis(cf_handle* h, int B, int P, const float* rows, float* eps, hipStream_t st) {
+    EpistasisArgs ea;
+    ea.v = rows, ea.eps = eps, ea.B = B, ea.S = P, ea.n_out = h->cfg.n_out;
+    const long long n = (long long)B * P * P * h->cfg.n_out;
+    hipLaunchKernelGGL(k_epistasis, dim3((int)std::min<long long>((n + kShapThreads - 1) / kShapThreads, 1024)), dim3(kShapThreads), 0, st, ea);
+    LAUNCH_CHECK("k_epistasis");
+    forward_one_more(h);
+    return 0;
+}
 
-// The 1 + S + S (S - 1) / 2 pair-deletion coalitions through coalition_upload + coalition_rows, then k_epistasis.
+// All 2^i_max coalitions through coalition_upload + coalition_rows, then k_shapley.
+extern "C" int cf_pcre_shapley(cf_handle* h, const cf_batch* bt, float* phi, float* logits_all, void* stream) {
+    const char* who = "cf_pcre_shapley";
+    if (attrib_open(h, bt, false, who)) return -1;
+    if (!phi) return fail("%s: null phi", who);
+    const int S = h->cfg.i_max, n = 1 << S;
+    float* rows = coalition_out_rows(h, logits_all, n, who);
+    if (!rows) return -1;
+    const std::vector<uint32_t> keep = all_words(S);
+    hipStream_t st = (hipStream_t)stream;
+    if (coalition_upload(h, keep.data(), n, st, who) || coalition_rows(h, bt, h->aw.words, n, rows, st)) return -1;
+    return launch_shapley(h, bt->B, S, rows, phi, st);
+}
+
+// The pair-deletion coalitions through coalition_upload + coalition_rows, then k_epistasis.
 extern "C" int cf_pcre_epistasis(cf_handle* h, const cf_batch* bt, float* eps, float* logits_pairs, void* stream) {
     const char* who = "cf_pcre_epistasis";
     if (attrib_open(h, bt, false, who)) return -1;
     if (!eps) return fail("%s: null eps", who);
-    const cf_config& c = h->cfg;
-    const int S = c.i_max;
-    const uint32_t N = (1u << S) - 1u;
-    std::vector<uint32_t> keep;
-    keep.push_back(N);
-    for (int i = 0; i < S; ++i) keep.push_back(N & ~(1u << i));
-    for (int i = 0; i < S; ++i)
-        for (int j = i + 1; j < S; ++j) keep.push_back(N & ~(1u << i) & ~(1u << j));
+    const std::vector<uint32_t> keep = pair_words(h->cfg.i_max);
     const int R = (int)keep.size();
     float* rows = coalition_out_rows(h, logits_pairs, R, who);
     if (!rows) return -1;
     hipStream_t st = (hipStream_t)stream;
     if (coalition_upload(h, keep.data(), R, st, who) || coalition_rows(h, bt, h->aw.words, R, rows, st)) return -1;
-    EpistasisArgs ea;
-    ea.v = rows, ea.eps = eps, ea.B = bt->B, ea.S = S, ea.n_out = c.n_out;
-    const long long n = (long long)bt->B * S * S * c.n_out;
-    hipLaunchKernelGGL(k_epistasis, dim3((int)std::min<long long>((n + kShapThreads - 1) / kShapThreads, 1024)), dim3(kShapThreads), 0, st, ea);
-    LAUNCH_CHECK("k_epistasis");
-    forward_one_more(h);
-    return 0;
+    return launch_epistasis(h, bt->B, h->cfg.i_max, rows, eps, st);
 }
 
 // A chunk of rows in the workspace (cf_integrated_gradients, the scans): the chunk's batch `cb` (all but B) and the
@@ -599,24 +637,85 @@ extern "C" int cf_integrated_gradients_raw_donor(cf_handle* h, const cf_batch* b
     return integrated_gradients_impl(h, bt, o, out, cmean, logits_x, logits_base, delta, stream, kIgSignalDonor, "cf_integrated_gradients_raw_donor");
 }
 
-// What the two scan entry points check alike, in front of anything launched.  scan_check: the window, the mark sets, the scale, nested
+// The geometry the scans and the window games stand on.  coarsest: the resolution with the fewest bins (*rc), every n_bins a multiple of
+// its W; finest: the resolution with the smallest bins (*rf), its L_f a multiple of every n_bins.
+static int coarsest(cf_handle* h, const char* who, int* rc) {
+    const cf_config& c = h->cfg;
+    *rc = 0;
+    for (int r = 1; r < c.n_res; ++r)
+        if (c.n_bins[r] < c.n_bins[*rc]) *rc = r;
+    const int W = c.n_bins[*rc];
+    for (int r = 0; r < c.n_res; ++r)
+        if (c.n_bins[r] % W) return fail("%s: n_bins[%d] = %d is not a multiple of the coarsest resolution's %d bins", who, r, c.n_bins[r], W);
+    return 0;
+}
+static int finest(cf_handle* h, const char* who, int* rf) {
+    const cf_config& c = h->cfg;
+    *rf = 0;
+    for (int r = 1; r < c.n_res; ++r)
+        if (c.binsizes[r] < c.binsizes[*rf]) *rf = r;
+    const int Lf = c.n_bins[*rf];
+    for (int r = 0; r < c.n_res; ++r)
+        if (Lf % c.n_bins[r])
+            return fail("%s: n_bins[%d] = %d of the finest resolution is not a multiple of n_bins[%d] = %d", who, *rf, Lf, r, c.n_bins[r]);
+    return 0;
+}
+// The centre pad-mask row of region `region` (0 the promoter, 1 + j pCRE slot j) of gene b at resolution r: *row + b * *stride.
+static void region_mask_row(const cf_batch* bt, int region, int r, int S, const uint8_t** row, long long* stride) {
+    if (region == 0) {
+        *row = bt->promoter_mask_row[r];
+        *stride = bt->promoter_mask_stride[r];
+    } else {
+        *row = bt->pcre_mask_row[r] + (long long)(region - 1) * bt->pcre_mask_stride[r];
+        *stride = (long long)S * bt->pcre_mask_stride[r];
+    }
+}
+
+// The samples of the last real finest bin of each gene, cnt_last[b], from the region's finest centre pad-mask rows m [B, Lf] (a host
+// copy) and its lengths: gene b has n_f real bins (first to last unmasked byte), lengths[b] must lie in ((n_f - 1) b_f, n_f b_f].  A
+// gene without a real bin (a dummy slot: nothing is edited there) keeps its count and its length is not read.  Host arithmetic only.
+static int fine_tail_counts(const uint8_t* m, int B, int Lf, int bf, const int* lengths, unsigned* cnt_last, const char* who) {
+    for (int b = 0; b < B; ++b) {
+        int lo = Lf, hi = 0;
+        for (int k = 0; k < Lf; ++k)
+            if (!m[(size_t)b * Lf + k]) lo = std::min(lo, k), hi = k + 1;
+        const long long nf = hi > lo ? hi - lo : 0, len = lengths[b];
+        if (!nf) continue;
+        if (len <= (nf - 1) * bf || len > nf * bf)
+            return fail("%s: lengths[%d] = %lld outside ((n_f - 1) b_f, n_f b_f] = (%lld, %lld]: the region has n_f = %lld real bins of b_f = %d samples",
+                        who, b, len, (nf - 1) * bf, nf * bf, nf, bf);
+        cnt_last[b] = (unsigned)(len - (nf - 1) * bf);
+    }
+    return 0;
+}
+// out[0, 2 B) = [start[B] | cnt_last[B]], the words the fine kernels read behind their tables: start (null: all 0) and the samples of
+// the last real finest bin (b_f; with `lengths`: fine_tail_counts on the finest centre pad-mask rows of the region, read back once -- a
+// copy, no launch).
+static int fine_tail_words(cf_handle* h, const cf_batch* bt, int region, int rf, const int* start, const int* lengths, hipStream_t st, const char* who,
+                           unsigned* out) {
+    const int B = bt->B, Lf = h->cfg.n_bins[rf], bf = h->cfg.binsizes[rf];
+    for (int b = 0; b < B; ++b) out[b] = start ? (unsigned)start[b] : 0u, out[B + b] = (unsigned)bf;
+    if (!lengths || B <= 0) return 0;
+    const uint8_t* rm;
+    long long rm_stride;
+    region_mask_row(bt, region, rf, h->cfg.i_max, &rm, &rm_stride);
+    std::vector<uint8_t> m((size_t)B * Lf);
+    HIP_TRY(hipMemcpy2DAsync(m.data(), Lf, rm, (size_t)rm_stride, Lf, B, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return fine_tail_counts(m.data(), B, Lf, bf, lengths, out + B, who);
+}
+
+// What the scan entry points check alike, in front of anything launched.  scan_check: the window, the mark sets, the scale, nested
 // bin counts (*rc_out: the coarsest resolution); scan_upload_sets: the workspace is allocated and holds the mark sets.
 static int scan_check(cf_handle* h, int width, int n_sets, const unsigned* mark_sets, float scale, const char* who, int* rc_out) {
     const cf_config& c = h->cfg;
-    const int nres = c.n_res, F = c.n_feats;
+    const int F = c.n_feats;
     if (width < 1) return fail("%s: width = %d: at least 1 coarsest bin", who, width);
     if (n_sets < 1) return fail("%s: n_sets = %d: at least 1 mark set", who, n_sets);
     if (!(scale >= 0.f) || !std::isfinite(scale)) return fail("%s: scale = %g: a finite factor >= 0", who, (double)scale);
     for (int k = 0; k < n_sets; ++k)
         if (F < 32 && mark_sets[k] >> F) return fail("%s: mark_sets[%d] = 0x%x names a mark >= n_feats = %d", who, k, mark_sets[k], F);
-    int rc = 0;
-    for (int r = 1; r < nres; ++r)
-        if (c.n_bins[r] < c.n_bins[rc]) rc = r;
-    const int W = c.n_bins[rc];
-    for (int r = 0; r < nres; ++r)
-        if (c.n_bins[r] % W) return fail("%s: n_bins[%d] = %d is not a multiple of the coarsest resolution's %d bins", who, r, c.n_bins[r], W);
-    *rc_out = rc;
-    return 0;
+    return coarsest(h, who, rc_out);
 }
 static int scan_upload_sets(cf_handle* h, const unsigned* mark_sets, int n_sets, hipStream_t st, const char* who) {
     if (attrib_ws(h, who) || h->aw.words.need(n_sets, 128, who)) return -1;
@@ -624,16 +723,17 @@ static int scan_upload_sets(cf_handle* h, const unsigned* mark_sets, int n_sets,
     return 0;
 }
 
-// One region of a scan, every row through the whole forward.  Per chunk of at most max_batch of the B * V rows (V = 1 + n_sets * W,
-// gene-major): k_scan_expand into the chunk workspace (the mark sets are in its word table, uploaded by the caller), then the launches
-// of cf_forward(save = 0) on the chunk, writing its slice of `logits`.  k_attc2 takes as many regions per workgroup as for the caller's B genes (ag_genes): the result does not depend on
-// max_batch and row (b, v) carries the bits of cf_forward(save = 0) on the batch with the perturbed features substituted.
-static int scan_region_rows(cf_handle* h, const cf_batch* bt, const cf_scan_opts* o, int rc, float* logits, hipStream_t st) {
+// One region of a scan, every row through the whole forward (chunk_forward).  Per chunk of at most max_batch of the B * V rows
+// (gene-major; V = 1 + n_sets * W): the scan's expand kernel into the chunk workspace (the mark sets are in its word table, uploaded by
+// the caller), then the launches of cf_forward(save = 0) on the chunk.  The result does not depend on max_batch and row (b, v) carries
+// the bits of cf_forward(save = 0) on the batch with the perturbed features substituted.
+// `ea`: ScanExpandArgs or ScanFineExpandArgs (cf_scan_fine.h) with the fields of its kernel alone set by the caller; what the two share
+// is filled in here.
+template <class Args>
+static int scan_rows(cf_handle* h, const cf_batch* bt, void (*kernel)(Args), const char* name, Args& ea, int region, float* const feats_out[], int V,
+                     float* logits, hipStream_t st) {
     const cf_config& c = h->cfg;
-    const int nres = c.n_res, S = c.i_max, F = c.n_feats, cap = c.max_batch, W = c.n_bins[rc];
-    const int B = bt->B, V = 1 + o->n_sets * W, slot = o->region - 1;
-    ScanExpandArgs ea;
-    memset(&ea, 0, sizeof ea);
+    const int nres = c.n_res;
     cf_batch cb;      // the chunk's batch: the rows' copies
     chunk_rows(h, bt, &ea.rows, &cb);
     for (int r = 0; r < nres; ++r) {
@@ -641,30 +741,26 @@ static int scan_region_rows(cf_handle* h, const cf_batch* bt, const cf_scan_opts
         ea.cf_in[r] = bt->pcre_feats[r];
         ea.pf_out[r] = h->aw.row[r];
         ea.cf_out[r] = h->aw.row[kMaxRes + r];
-        ea.feats_out[r] = o->feats_out[r];
-        if (slot < 0) {
-            ea.rm_in[r] = bt->promoter_mask_row[r];
-            ea.rm_stride[r] = bt->promoter_mask_stride[r];
-        } else {
-            ea.rm_in[r] = bt->pcre_mask_row[r] + (long long)slot * bt->pcre_mask_stride[r];
-            ea.rm_stride[r] = (long long)S * bt->pcre_mask_stride[r];
-        }
+        ea.feats_out[r] = feats_out[r];
+        region_mask_row(bt, region, r, c.i_max, &ea.rm_in[r], &ea.rm_stride[r]);
     }
     ea.freq_in = bt->interaction_freq;
     ea.freq_out = h->aw.row[2 * kMaxRes];
     ea.sets = h->aw.words;
+    ea.V = V, ea.F = c.n_feats, ea.region = region;
+    return chunk_forward(h, &cb, (long long)bt->B * V, logits, true, bt->B, st, [&](long long g0, int n) {
+        ea.g0 = (int)g0;
+        return launch_expand(kernel, name, dim3(n, nres), kIgxThreads, ea, st);
+    });
+}
+static int scan_region_rows(cf_handle* h, const cf_batch* bt, const cf_scan_opts* o, int rc, float* logits, hipStream_t st) {
+    const int W = h->cfg.n_bins[rc];
+    ScanExpandArgs ea;
+    memset(&ea, 0, sizeof ea);
     ea.flip = o->flip;
     ea.scale = o->scale;
-    ea.V = V, ea.F = F, ea.W = W, ea.width = o->width, ea.rc = rc, ea.region = o->region;
-    for (int g0 = 0; g0 < B * V; g0 += cap) {
-        const int nr = std::min(cap, B * V - g0);
-        ea.g0 = g0;
-        hipLaunchKernelGGL(k_scan_expand, dim3(nr, nres), dim3(kIgxThreads), 0, st, ea);
-        LAUNCH_CHECK("k_scan_expand");
-        cb.B = nr;
-        if (forward_trunk(h, &cb, 0, st, B) || forward_reg_head(h, &cb, logits + (size_t)g0 * c.n_out, 0, st, nullptr)) return -1;
-    }
-    return 0;
+    ea.W = W, ea.width = o->width, ea.rc = rc;
+    return scan_rows(h, bt, k_scan_expand, "k_scan_expand", ea, o->region, o->feats_out, 1 + o->n_sets * W, logits, st);
 }
 
 // In-silico perturbation scan of one region (cf_scan.h): scan_region_rows.
@@ -735,15 +831,10 @@ static int scan_slot_packed(cf_handle* h, const cf_batch* bt, const cf_scan_regi
         hipLaunchKernelGGL(k_scan_unpack, dim3(n, nres), dim3(kRowThreads), 0, st, ua);
         LAUNCH_CHECK("k_scan_unpack");
     }
-    for (int g0 = 0; g0 < B * V; g0 += cap) {
-        const int n = std::min(cap, B * V - g0);
-        ra.g0 = g0;
-        hipLaunchKernelGGL(k_scan_rows, dim3(n, nres), dim3(kRowThreads), 0, st, ra);
-        LAUNCH_CHECK("k_scan_rows");
-        cb.B = n;
-        if (forward_reg_head(h, &cb, logits + (size_t)g0 * c.n_out, 0, st, nullptr)) return -1;
-    }
-    return 0;
+    return chunk_forward(h, &cb, (long long)B * V, logits, false, B, st, [&](long long g0, int n) {
+        ra.g0 = (int)g0;
+        return launch_expand(k_scan_rows, "k_scan_rows", dim3(n, nres), kRowThreads, ra, st);
+    });
 }
 
 // The scan of several regions of every gene from one call: the promoter block through scan_region_rows, the pCRE blocks slot-packed
@@ -784,10 +875,9 @@ extern "C" int cf_perturbation_scan_regions(cf_handle* h, const cf_batch* bt, co
     return rv ? -1 : 0;
 }
 
-// Fine-resolution perturbation scan (cf_scan_fine.h): scan_region_rows with k_scan_fine_expand in the place of k_scan_expand.  The word
-// table of the workspace holds [mark sets | start | samples of the last real finest bin], uploaded here: no device buffer of its own.
-// With `lengths` the finest centre pad-mask rows of the scanned region are read back once (a copy, no launch) to check each length
-// against its gene's real bins.
+// Fine-resolution perturbation scan (cf_scan_fine.h): scan_rows with k_scan_fine_expand where scan_region_rows hands it k_scan_expand.
+// The word table of the workspace holds [mark sets | start | samples of the last real finest bin] (fine_tail_words), uploaded here: no
+// device buffer of its own.
 extern "C" int cf_perturbation_scan_fine(cf_handle* h, const cf_batch* bt, const cf_scan_fine_opts* o, float* logits, void* stream) {
     const char* who = "cf_perturbation_scan_fine";
     if (attrib_open(h, bt, true, who)) return -1;
@@ -795,20 +885,13 @@ extern "C" int cf_perturbation_scan_fine(cf_handle* h, const cf_batch* bt, const
     if (!logits) return fail("%s: null logits", who);
     if (!o->mark_sets) return fail("%s: null mark_sets", who);
     const cf_config& c = h->cfg;
-    const int nres = c.n_res, S = c.i_max, F = c.n_feats, cap = c.max_batch, B = bt->B, slot = o->region - 1;
+    const int nres = c.n_res, S = c.i_max, B = bt->B;
     if (o->region < 0 || o->region > S) return fail("%s: region = %d outside [0, i_max = %d]", who, o->region, S);
     if (o->width < 1) return fail("%s: width = %d: at least 1 finest bin", who, o->width);
     if (o->stride < 1) return fail("%s: stride = %d: at least 1 finest bin", who, o->stride);
     if (o->n_windows < 1) return fail("%s: n_windows = %d: at least 1 window", who, o->n_windows);
-    int rc = 0;
-    if (scan_check(h, 1, o->n_sets, o->mark_sets, o->scale, who, &rc)) return -1;
-    int rf = 0;
-    for (int r = 1; r < nres; ++r)
-        if (c.binsizes[r] < c.binsizes[rf]) rf = r;
-    const int Lf = c.n_bins[rf], bf = c.binsizes[rf];
-    for (int r = 0; r < nres; ++r)
-        if (Lf % c.n_bins[r])
-            return fail("%s: n_bins[%d] = %d of the finest resolution is not a multiple of n_bins[%d] = %d", who, rf, Lf, r, c.n_bins[r]);
+    int rc = 0, rf = 0;
+    if (scan_check(h, 1, o->n_sets, o->mark_sets, o->scale, who, &rc) || finest(h, who, &rf)) return -1;
     for (int r = nres; r < kMaxRes; ++r)
         if (o->feats_out[r]) return fail("%s: feats_out[%d]: the model has %d resolutions", who, r, nres);
     for (int b = 0; o->start && b < B; ++b)
@@ -816,604 +899,21 @@ extern "C" int cf_perturbation_scan_fine(cf_handle* h, const cf_batch* bt, const
     const long long rows = (long long)B * (1 + (long long)o->n_sets * o->n_windows);
     if (rows > 0x7fffffffLL) return fail("%s: B * (1 + n_sets * n_windows) = %lld rows do not fit an int", who, rows);
     hipStream_t st = (hipStream_t)stream;
-    const uint8_t* rm = slot < 0 ? bt->promoter_mask_row[rf] : bt->pcre_mask_row[rf] + (long long)slot * bt->pcre_mask_stride[rf];
-    const long long rm_stride = slot < 0 ? bt->promoter_mask_stride[rf] : (long long)S * bt->pcre_mask_stride[rf];
     std::vector<unsigned> words(o->n_sets + 2 * (size_t)B);
     memcpy(words.data(), o->mark_sets, o->n_sets * sizeof(unsigned));
-    for (int b = 0; b < B; ++b) words[o->n_sets + b] = o->start ? (unsigned)o->start[b] : 0u, words[o->n_sets + B + b] = (unsigned)bf;
-    if (o->lengths && B > 0) {
-        std::vector<uint8_t> m((size_t)B * Lf);
-        HIP_TRY(hipMemcpy2DAsync(m.data(), Lf, rm, (size_t)rm_stride, Lf, B, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (int b = 0; b < B; ++b) {
-            int lo = Lf, hi = 0;
-            for (int k = 0; k < Lf; ++k)
-                if (!m[(size_t)b * Lf + k]) lo = std::min(lo, k), hi = k + 1;
-            const long long nf = hi > lo ? hi - lo : 0, len = o->lengths[b];
-            if (!nf) continue;      // a dummy slot: nothing is scanned, the length is not read
-            if (len <= (nf - 1) * bf || len > nf * bf)
-                return fail("%s: lengths[%d] = %lld outside ((n_f - 1) b_f, n_f b_f] = (%lld, %lld]: the region has n_f = %lld real bins of b_f = %d samples",
-                            who, b, len, (nf - 1) * bf, nf * bf, nf, bf);
-            words[o->n_sets + B + b] = (unsigned)(len - (nf - 1) * bf);
-        }
-    }
+    if (fine_tail_words(h, bt, o->region, rf, o->start, o->lengths, st, who, words.data() + o->n_sets)) return -1;
     if (attrib_ws(h, who) || h->aw.words.need(words.size(), 128, who)) return -1;
     HIP_TRY(hipMemcpyAsync(h->aw.words, words.data(), words.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    const int V = (int)(rows / std::max(B, 1));
     ScanFineExpandArgs ea;
     memset(&ea, 0, sizeof ea);
-    cf_batch cb;      // the chunk's batch: the rows' copies
-    chunk_rows(h, bt, &ea.rows, &cb);
-    for (int r = 0; r < nres; ++r) {
-        ea.pf_in[r] = bt->promoter_feats[r];
-        ea.cf_in[r] = bt->pcre_feats[r];
-        ea.pf_out[r] = h->aw.row[r];
-        ea.cf_out[r] = h->aw.row[kMaxRes + r];
-        ea.feats_out[r] = o->feats_out[r];
-        if (slot < 0) {
-            ea.rm_in[r] = bt->promoter_mask_row[r];
-            ea.rm_stride[r] = bt->promoter_mask_stride[r];
-        } else {
-            ea.rm_in[r] = bt->pcre_mask_row[r] + (long long)slot * bt->pcre_mask_stride[r];
-            ea.rm_stride[r] = (long long)S * bt->pcre_mask_stride[r];
-        }
-    }
-    ea.freq_in = bt->interaction_freq;
-    ea.freq_out = h->aw.row[2 * kMaxRes];
-    ea.sets = h->aw.words;
     ea.start = reinterpret_cast<const int*>((unsigned*)h->aw.words) + o->n_sets;
     ea.cnt_last = ea.start + B;
     ea.flip = o->flip;
     ea.scale = o->scale;
-    ea.V = V, ea.F = F, ea.NW = o->n_windows, ea.width = o->width, ea.stride = o->stride, ea.rf = rf, ea.bf = bf, ea.region = o->region;
+    ea.NW = o->n_windows, ea.width = o->width, ea.stride = o->stride, ea.rf = rf, ea.bf = c.binsizes[rf];
     const long long launches0 = g_launches;
-    int rv = 0;
-    for (int g0 = 0; g0 < B * V && !rv; g0 += cap) {
-        const int nr = std::min(cap, B * V - g0);
-        ea.g0 = g0;
-        hipLaunchKernelGGL(k_scan_fine_expand, dim3(nr, nres), dim3(kIgxThreads), 0, st, ea);
-        LAUNCH_CHECK("k_scan_fine_expand");
-        cb.B = nr;
-        rv = forward_trunk(h, &cb, 0, st, B) || forward_reg_head(h, &cb, logits + (size_t)g0 * c.n_out, 0, st, nullptr);
-    }
+    const int rv = scan_rows(h, bt, k_scan_fine_expand, "k_scan_fine_expand", ea, o->region, o->feats_out, (int)(rows / std::max(B, 1)), logits, st);
     h->x0_fwd = false;
     forward_counted(h, launches0);
     return rv ? -1 : 0;
-}
-
-// Histone-mark coalitions (cf_marks.h).  The two families -- cf_mark_* (an absent mark is the gene's own signal scaled) and
-// cf_mark_donor_* (an absent mark is the donor's) -- share everything but the options struct and the expand kernel: MarkGame is what
-// either struct says, checked.
-struct MarkGame {
-    int P;
-    const unsigned* marks;                // host [P]
-    const unsigned* regions;              // host [P]
-    float scale;                          // the scale rule (donor == nullptr)
-    const cf_mark_donor_opts* donor;      // the donor rule
-    int kw = 0;                           // words per coalition of the wide game (cf_marks_wide.h); 0: the one-word kernels
-    const int* lo = nullptr;              // host [P]: the window game (cf_mark_windows.h): player p's coarse bins [lo, hi); null: whole regions
-    const int* hi = nullptr;
-    const uint8_t* flip = nullptr;        // device [B] or null: the promoter is stored mirrored (the window game)
-    int W = 0, rc = 0;                    // the coarsest resolution's bin count and index (the window game)
-    const cf_mark_fine_opts* fine = nullptr;      // the fine window game (cf_mark_fine.h): lo / hi in finest bins, one region, no regions words
-    int rf = 0, bf = 0;                           // ... the finest resolution's index and bin size
-    std::vector<unsigned> fine_words;             // ... [start[B] | cnt_last[B]], behind the player words in the word table
-};
-
-// mark_check: what the entry points check alike, in front of anything launched -- the handle, the batch, riders, the options: the
-// player count (at most `limit`), the player words.  `o`: whether the caller's opts pointer is non-null.
-static int mark_check(cf_handle* h, const cf_batch* bt, bool o, const MarkGame& g, const char* who, int limit = kCoalMaxS) {
-    if (attrib_open(h, bt, true, who)) return -1;
-    if (!o) return fail("%s: null opts", who);
-    const cf_config& c = h->cfg;
-    const int S = c.i_max, F = c.n_feats;
-    if (g.P < 1 || g.P > limit) return fail("%s: n_players = %d outside 1..%d", who, g.P, limit);
-    if (!g.marks || !g.regions) return fail("%s: null player_marks / player_regions", who);
-    for (int p = 0; p < g.P; ++p) {
-        const unsigned pm = g.marks[p], pr = g.regions[p];
-        if (!pm) return fail("%s: player_marks[%d] = 0: a player names at least one mark", who, p);
-        if (!pr) return fail("%s: player_regions[%d] = 0: a player names at least one region (bit 0 the promoter, bit 1 + j pCRE slot j)", who, p);
-        if (F < 32 && pm >> F) return fail("%s: player_marks[%d] = 0x%x names a mark >= n_feats = %d", who, p, pm, F);
-        if (pr >> S >> 1) return fail("%s: player_regions[%d] = 0x%x names a region above i_max = %d", who, p, pr, S);
-    }
-    return 0;
-}
-// ... then the scale of the scale rule,
-static int mark_game(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, MarkGame* g, const char* who) {
-    *g = o ? MarkGame{o->n_players, o->player_marks, o->player_regions, o->scale, nullptr} : MarkGame{};
-    if (mark_check(h, bt, o != nullptr, *g, who)) return -1;
-    if (!(o->scale >= 0.f) || !std::isfinite(o->scale)) return fail("%s: scale = %g: a finite factor >= 0", who, (double)o->scale);
-    return 0;
-}
-// ... or the donor's feature pointers of the donor rule.
-static int mark_donor_game(cf_handle* h, const cf_batch* bt, const cf_mark_donor_opts* o, MarkGame* g, const char* who) {
-    *g = o ? MarkGame{o->n_players, o->player_marks, o->player_regions, 0.f, o} : MarkGame{};
-    if (mark_check(h, bt, o != nullptr, *g, who)) return -1;
-    for (int r = 0; r < h->cfg.n_res; ++r)
-        if (!o->donor_promoter_feats[r] || !o->donor_pcre_feats[r])
-            return fail("%s: null donor_promoter_feats / donor_pcre_feats[%d]: the donor's features at every one of the model's %d resolutions", who, r, h->cfg.n_res);
-    return 0;
-}
-
-// The coalition words (validated) and the 2 P player words into the workspace's word table: [words | marks_p | regions_p].
-static int mark_upload(cf_handle* h, const MarkGame& g, const uint32_t* keep, int n_coal, hipStream_t st, const char* who) {
-    const int P = g.P;
-    if (n_coal < 1) return fail("%s: n_coal = %d: at least 1 coalition", who, n_coal);
-    if (!keep) return fail("%s: null keep", who);
-    for (int k = 0; k < n_coal; ++k)
-        if (P < 32 && keep[k] >> P) return fail("%s: keep[%d] = 0x%x names a player >= n_players = %d", who, k, keep[k], P);
-    if (attrib_ws(h, who) || h->aw.words.need((size_t)n_coal + 2 * P, 256, who)) return -1;
-    unsigned* tab = h->aw.words;
-    HIP_TRY(hipMemcpyAsync(tab, keep, (size_t)n_coal * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(tab + n_coal, g.marks, P * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(tab + n_coal + P, g.regions, P * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    return 0;
-}
-
-// The B * n_coal rows of a mark-coalition call (gene-major; row (b, k) is word k of the table mark_upload wrote), every row through
-// the whole forward.  Per chunk of at most max_batch rows: k_mark_expand (the donor rule: k_mark_donor_expand; the wide game, whose rows
-// are g.kw words each: k_mark_wide_expand / k_mark_wide_donor_expand; the window game, g.lo set: k_mark_window_expand /
-// k_mark_window_donor_expand; the fine window game, g.fine set: k_mark_fine_expand / k_mark_fine_donor_expand) into the chunk workspace,
-// then the launches of cf_forward(save = 0) on the chunk, writing its slice of `logits`.  k_attc2 takes as many regions per workgroup
-// as for the caller's B genes (ag_genes), as scan_region_rows: the result does not depend on max_batch.
-static int mark_rows(cf_handle* h, const cf_batch* bt, const MarkGame& g, int n_coal, float* logits, hipStream_t st) {
-    const cf_config& c = h->cfg;
-    const int nres = c.n_res, cap = c.max_batch, B = bt->B, P = g.P;
-    MarkDonorArgs da;
-    memset(&da, 0, sizeof da);
-    MarkExpandArgs& ea = da.m;
-    cf_batch cb;      // the chunk's batch: the rows' copies
-    chunk_rows(h, bt, &ea.rows, &cb);
-    for (int r = 0; r < nres; ++r) {
-        ea.pf_in[r] = bt->promoter_feats[r];
-        ea.cf_in[r] = bt->pcre_feats[r];
-        ea.pf_out[r] = h->aw.row[r];
-        ea.cf_out[r] = h->aw.row[kMaxRes + r];
-        if (g.donor) {
-            da.pf_don[r] = g.donor->donor_promoter_feats[r];
-            da.cf_don[r] = g.donor->donor_pcre_feats[r];
-        }
-    }
-    ea.freq_in = bt->interaction_freq;
-    ea.freq_out = h->aw.row[2 * kMaxRes];
-    ea.words = h->aw.words;
-    ea.players = h->aw.words + (size_t)n_coal * (g.kw ? g.kw : 1);
-    ea.scale = g.scale;
-    ea.n_coal = n_coal, ea.P = P, ea.F = c.n_feats;
-    MarkWindowDonorArgs wd;      // the window game: ea with the promoter's centre mask rows, flip and the coarsest resolution
-    memset(&wd, 0, sizeof wd);
-    MarkFineDonorArgs fd;        // the fine window game: ea with the region's centre mask rows, start, the tail counts and feats_out
-    memset(&fd, 0, sizeof fd);
-    if (g.fine) {
-        const int slot = g.fine->region - 1, S = c.i_max;
-        for (int r = 0; r < nres; ++r) {
-            if (slot < 0) {
-                fd.w.rm_in[r] = bt->promoter_mask_row[r];
-                fd.w.rm_stride[r] = bt->promoter_mask_stride[r];
-            } else {
-                fd.w.rm_in[r] = bt->pcre_mask_row[r] + (long long)slot * bt->pcre_mask_stride[r];
-                fd.w.rm_stride[r] = (long long)S * bt->pcre_mask_stride[r];
-            }
-            fd.w.feats_out[r] = g.fine->feats_out[r];
-            fd.pf_don[r] = da.pf_don[r];
-            fd.cf_don[r] = da.cf_don[r];
-        }
-        fd.w.start = reinterpret_cast<const int*>(ea.players) + 3 * P;
-        fd.w.cnt_last = fd.w.start + B;
-        fd.w.flip = g.flip;
-        fd.w.rf = g.rf, fd.w.bf = g.bf, fd.w.region = g.fine->region;
-    } else if (g.lo) {
-        for (int r = 0; r < nres; ++r) {
-            wd.w.pmc[r] = static_cast<const uint8_t*>(bt->promoter_mask_row[r]);
-            wd.pf_don[r] = da.pf_don[r];
-            wd.cf_don[r] = da.cf_don[r];
-        }
-        wd.w.flip = g.flip;
-        wd.w.W = g.W, wd.w.rc = g.rc;
-    }
-    const long long launches0 = g_launches, rows = (long long)B * n_coal;
-    auto run = [&]() -> int {
-        for (long long g0 = 0; g0 < rows; g0 += cap) {
-            const int n = (int)std::min<long long>(cap, rows - g0);
-            ea.g0 = g0;
-            if (g.fine) {
-                fd.w.m = ea;
-                if (g.donor) {
-                    hipLaunchKernelGGL(k_mark_fine_donor_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, fd);
-                    LAUNCH_CHECK("k_mark_fine_donor_expand");
-                } else {
-                    hipLaunchKernelGGL(k_mark_fine_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, fd.w);
-                    LAUNCH_CHECK("k_mark_fine_expand");
-                }
-            } else if (g.lo) {
-                wd.w.m = ea;
-                if (g.donor) {
-                    hipLaunchKernelGGL(k_mark_window_donor_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, wd);
-                    LAUNCH_CHECK("k_mark_window_donor_expand");
-                } else {
-                    hipLaunchKernelGGL(k_mark_window_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, wd.w);
-                    LAUNCH_CHECK("k_mark_window_expand");
-                }
-            } else if (g.kw && g.donor) {
-                hipLaunchKernelGGL(k_mark_wide_donor_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, da);
-                LAUNCH_CHECK("k_mark_wide_donor_expand");
-            } else if (g.kw) {
-                hipLaunchKernelGGL(k_mark_wide_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, ea);
-                LAUNCH_CHECK("k_mark_wide_expand");
-            } else if (g.donor) {
-                hipLaunchKernelGGL(k_mark_donor_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, da);
-                LAUNCH_CHECK("k_mark_donor_expand");
-            } else {
-                hipLaunchKernelGGL(k_mark_expand, dim3(n, nres, kMarkSlices), dim3(kIgxThreads), 0, st, ea);
-                LAUNCH_CHECK("k_mark_expand");
-            }
-            cb.B = n;
-            if (forward_trunk(h, &cb, 0, st, B) || forward_reg_head(h, &cb, logits + (size_t)g0 * c.n_out, 0, st, nullptr)) return -1;
-        }
-        return 0;
-    };
-    const int rv = run();
-    h->x0_fwd = false;
-    forward_counted(h, launches0);
-    return rv ? -1 : 0;
-}
-
-// The three calls on a checked game: the given coalitions;
-static int mark_coalitions_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g, const uint32_t* keep, int n_coal, float* logits, void* stream,
-                                const char* who) {
-    if (!logits) return fail("%s: null logits", who);
-    hipStream_t st = (hipStream_t)stream;
-    if (mark_upload(h, g, keep, n_coal, st, who)) return -1;
-    return mark_rows(h, bt, g, n_coal, logits, st);
-}
-static int mark_wide_upload(cf_handle* h, const MarkGame& g, const uint32_t* keep, int n_coal, size_t extra, hipStream_t st, const char* who);
-// all 2^P coalitions through mark_upload (a game of g.kw = 1 word: mark_wide_upload) + mark_rows (word m at column m), then k_shapley
-// with S = P;
-static int mark_shapley_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g, float* phi, float* logits_all, void* stream, const char* who) {
-    if (!phi) return fail("%s: null phi", who);
-    const cf_config& c = h->cfg;
-    const int P = g.P, n = 1 << P;
-    float* rows = coalition_out_rows(h, logits_all, n, who);
-    if (!rows) return -1;
-    std::vector<uint32_t> keep(n);
-    for (int m = 0; m < n; ++m) keep[m] = (uint32_t)m;
-    hipStream_t st = (hipStream_t)stream;
-    if ((g.kw ? mark_wide_upload(h, g, keep.data(), n, 0, st, who) : mark_upload(h, g, keep.data(), n, st, who)) || mark_rows(h, bt, g, n, rows, st)) return -1;
-    ShapleyArgs sa;
-    memset(&sa, 0, sizeof sa);
-    sa.v = rows, sa.phi = phi, sa.S = P, sa.n_out = c.n_out;
-    double fact[kCoalMaxS + 1] = {1.0};
-    for (int k = 1; k <= P; ++k) fact[k] = fact[k - 1] * k;
-    for (int k = 0; k < P; ++k) sa.w[k] = (float)(fact[k] * fact[P - k - 1] / fact[P]);
-    hipLaunchKernelGGL(k_shapley, dim3(bt->B, P), dim3(kShapThreads), 0, st, sa);
-    LAUNCH_CHECK("k_shapley");
-    forward_one_more(h);
-    return 0;
-}
-// the 1 + P + P (P - 1) / 2 pair-deletion coalitions (N = 2^P - 1; N without i; N without i and j, i < j) through mark_upload +
-// mark_rows, then k_epistasis with S = P.
-static int mark_epistasis_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g, float* eps, float* logits_pairs, void* stream, const char* who) {
-    if (!eps) return fail("%s: null eps", who);
-    const cf_config& c = h->cfg;
-    const int P = g.P;
-    const uint32_t N = (1u << P) - 1u;
-    std::vector<uint32_t> keep;
-    keep.push_back(N);
-    for (int i = 0; i < P; ++i) keep.push_back(N & ~(1u << i));
-    for (int i = 0; i < P; ++i)
-        for (int j = i + 1; j < P; ++j) keep.push_back(N & ~(1u << i) & ~(1u << j));
-    const int R = (int)keep.size();
-    float* rows = coalition_out_rows(h, logits_pairs, R, who);
-    if (!rows) return -1;
-    hipStream_t st = (hipStream_t)stream;
-    if (mark_upload(h, g, keep.data(), R, st, who) || mark_rows(h, bt, g, R, rows, st)) return -1;
-    EpistasisArgs ea;
-    ea.v = rows, ea.eps = eps, ea.B = bt->B, ea.S = P, ea.n_out = c.n_out;
-    const long long n = (long long)bt->B * P * P * c.n_out;
-    hipLaunchKernelGGL(k_epistasis, dim3((int)std::min<long long>((n + kShapThreads - 1) / kShapThreads, 1024)), dim3(kShapThreads), 0, st, ea);
-    LAUNCH_CHECK("k_epistasis");
-    forward_one_more(h);
-    return 0;
-}
-
-extern "C" int cf_mark_coalitions(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, const uint32_t* keep, int n_coal, float* logits,
-                                  void* stream) {
-    const char* who = "cf_mark_coalitions";
-    MarkGame g;
-    return mark_game(h, bt, o, &g, who) ? -1 : mark_coalitions_impl(h, bt, g, keep, n_coal, logits, stream, who);
-}
-extern "C" int cf_mark_shapley(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, float* phi, float* logits_all, void* stream) {
-    const char* who = "cf_mark_shapley";
-    MarkGame g;
-    return mark_game(h, bt, o, &g, who) ? -1 : mark_shapley_impl(h, bt, g, phi, logits_all, stream, who);
-}
-extern "C" int cf_mark_epistasis(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, float* eps, float* logits_pairs, void* stream) {
-    const char* who = "cf_mark_epistasis";
-    MarkGame g;
-    return mark_game(h, bt, o, &g, who) ? -1 : mark_epistasis_impl(h, bt, g, eps, logits_pairs, stream, who);
-}
-
-// The donor family: an absent mark takes the donor's bits (k_mark_donor_expand); everything else as above.
-extern "C" int cf_mark_donor_coalitions(cf_handle* h, const cf_batch* bt, const cf_mark_donor_opts* o, const uint32_t* keep, int n_coal,
-                                        float* logits, void* stream) {
-    const char* who = "cf_mark_donor_coalitions";
-    MarkGame g;
-    return mark_donor_game(h, bt, o, &g, who) ? -1 : mark_coalitions_impl(h, bt, g, keep, n_coal, logits, stream, who);
-}
-extern "C" int cf_mark_donor_shapley(cf_handle* h, const cf_batch* bt, const cf_mark_donor_opts* o, float* phi, float* logits_all, void* stream) {
-    const char* who = "cf_mark_donor_shapley";
-    MarkGame g;
-    return mark_donor_game(h, bt, o, &g, who) ? -1 : mark_shapley_impl(h, bt, g, phi, logits_all, stream, who);
-}
-extern "C" int cf_mark_donor_epistasis(cf_handle* h, const cf_batch* bt, const cf_mark_donor_opts* o, float* eps, float* logits_pairs, void* stream) {
-    const char* who = "cf_mark_donor_epistasis";
-    MarkGame g;
-    return mark_donor_game(h, bt, o, &g, who) ? -1 : mark_epistasis_impl(h, bt, g, eps, logits_pairs, stream, who);
-}
-
-// The wide game (cf_marks_wide.h): up to kMarkWideMaxP players, kw words per coalition, one options struct for both rules.  `d`: the
-// donor's pointers in the struct mark_rows reads them from (the caller's storage).
-// mark_rule: which rule a one-struct game asks for -- all donor pointers null: the scale rule (g->scale, checked); all set: the donor
-// rule (g->donor = d, filled); mixed: refused.
-static int mark_rule(cf_handle* h, MarkGame* g, cf_mark_donor_opts* d, const float* const* don_p, const float* const* don_c, const char* who) {
-    int given = 0;
-    for (int r = 0; r < h->cfg.n_res; ++r) given += (don_p[r] != nullptr) + (don_c[r] != nullptr);
-    if (given && given != 2 * h->cfg.n_res)
-        return fail("%s: %d of the %d donor_promoter_feats / donor_pcre_feats pointers below the model's %d resolutions are null: all of them "
-                    "(the scale rule) or none (the donor rule)", who, 2 * h->cfg.n_res - given, 2 * h->cfg.n_res, h->cfg.n_res);
-    if (given) {
-        memset(d, 0, sizeof *d);
-        for (int r = 0; r < h->cfg.n_res; ++r) d->donor_promoter_feats[r] = don_p[r], d->donor_pcre_feats[r] = don_c[r];
-        g->donor = d;
-        g->scale = 0.f;
-    } else if (!(g->scale >= 0.f) || !std::isfinite(g->scale)) {
-        return fail("%s: scale = %g: a finite factor >= 0", who, (double)g->scale);
-    }
-    return 0;
-}
-static int mark_wide_game(cf_handle* h, const cf_batch* bt, const cf_mark_wide_opts* o, MarkGame* g, cf_mark_donor_opts* d, const char* who) {
-    *g = o ? MarkGame{o->n_players, o->player_marks, o->player_regions, o->scale, nullptr} : MarkGame{};
-    if (mark_check(h, bt, o != nullptr, *g, who, kMarkWideMaxP)) return -1;
-    g->kw = (g->P + 31) / 32;
-    return mark_rule(h, g, d, o->donor_promoter_feats, o->donor_pcre_feats, who);
-}
-
-// The n_coal * kw coalition words (validated) and the 2 P player words into the workspace's word table, with room for `extra` words
-// behind them: [words | marks_p | regions_p | extra]; the window game: [words | marks_p | regions_p | lo_p | hi_p | extra]; the fine
-// window game: [words | marks_p | lo_p | hi_p | start[B] | cnt_last[B] | extra].
-static int mark_player_words(const MarkGame& g) { return g.fine ? 3 * g.P + (int)g.fine_words.size() : (g.lo ? 4 : 2) * g.P; }
-static int mark_wide_upload(cf_handle* h, const MarkGame& g, const uint32_t* keep, int n_coal, size_t extra, hipStream_t st, const char* who) {
-    const int P = g.P, kw = g.kw;
-    if (n_coal < 1) return fail("%s: n_coal = %d: at least 1 coalition", who, n_coal);
-    if (!keep) return fail("%s: null keep", who);
-    if (P & 31)
-        for (int k = 0; k < n_coal; ++k) {
-            const uint32_t last = keep[(size_t)k * kw + kw - 1];
-            if (last >> (P & 31)) return fail("%s: keep[%d] (word %d = 0x%x) names a player >= n_players = %d", who, k, kw - 1, last, P);
-        }
-    const size_t nw = (size_t)n_coal * kw;
-    if (attrib_ws(h, who) || h->aw.words.need(nw + mark_player_words(g) + extra, 256, who)) return -1;
-    unsigned* tab = h->aw.words;
-    HIP_TRY(hipMemcpyAsync(tab, keep, nw * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(tab + nw, g.marks, P * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    if (g.fine) {
-        HIP_TRY(hipMemcpyAsync(tab + nw + P, g.lo, P * sizeof(int), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(tab + nw + 2 * P, g.hi, P * sizeof(int), hipMemcpyHostToDevice, st));
-        if (!g.fine_words.empty())
-            HIP_TRY(hipMemcpyAsync(tab + nw + 3 * P, g.fine_words.data(), g.fine_words.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
-        return 0;
-    }
-    HIP_TRY(hipMemcpyAsync(tab + nw + P, g.regions, P * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    if (g.lo) {
-        HIP_TRY(hipMemcpyAsync(tab + nw + 2 * P, g.lo, P * sizeof(int), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(tab + nw + 3 * P, g.hi, P * sizeof(int), hipMemcpyHostToDevice, st));
-    }
-    return 0;
-}
-
-extern "C" int cf_mark_coalitions_wide(cf_handle* h, const cf_batch* bt, const cf_mark_wide_opts* o, const uint32_t* keep, int n_coal, float* logits,
-                                       void* stream) {
-    const char* who = "cf_mark_coalitions_wide";
-    MarkGame g;
-    cf_mark_donor_opts d;
-    if (mark_wide_game(h, bt, o, &g, &d, who)) return -1;
-    if (!logits) return fail("%s: null logits", who);
-    hipStream_t st = (hipStream_t)stream;
-    if (mark_wide_upload(h, g, keep, n_coal, 0, st, who)) return -1;
-    return mark_rows(h, bt, g, n_coal, logits, st);
-}
-
-// The prefix rows of n_perm permutations through mark_wide_upload + mark_rows (column 0 nobody, column 1 everybody, column
-// 2 + q (P - 1) + (k - 1) the first k players of permutation q), then k_perm_shapley on the inverse permutations, which travel as bytes
-// behind the player words.  `g`: a checked wide game, with or without windows.
-static int mark_sampled_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g, const uint8_t* perms, int n_perm, float* phi, float* se,
-                             float* logits_rows, void* stream, const char* who) {
-    if (!phi) return fail("%s: null phi", who);
-    if (!perms) return fail("%s: null perms", who);
-    if (n_perm < 1) return fail("%s: n_perm = %d: at least 1 permutation", who, n_perm);
-    const cf_config& c = h->cfg;
-    const int P = g.P, kw = g.kw;
-    const long long R64 = 2 + (long long)n_perm * (P - 1);
-    if (R64 * kw > (1ll << 30)) return fail("%s: n_perm = %d: %lld rows per gene; at most 2^30 coalition words", who, n_perm, R64);
-    const int R = (int)R64;
-    std::vector<uint8_t> rank((size_t)n_perm * P);
-    std::vector<uint32_t> keep((size_t)R * kw, 0u), cur(kw);
-    for (int p = 0; p < P; ++p) keep[kw + (p >> 5)] |= 1u << (p & 31);      // column 1: everybody
-    for (int q = 0; q < n_perm; ++q) {
-        const uint8_t* pi = perms + (size_t)q * P;
-        uint8_t* rk = rank.data() + (size_t)q * P;
-        memset(rk, 0xFF, P);
-        for (int k = 0; k < P; ++k) {
-            if (pi[k] >= P || rk[pi[k]] != 0xFF) return fail("%s: perms[%d] is not a permutation of 0..%d (position %d holds %d)", who, q, P - 1, k, (int)pi[k]);
-            rk[pi[k]] = (uint8_t)k;
-        }
-        std::fill(cur.begin(), cur.end(), 0u);
-        for (int k = 1; k < P; ++k) {
-            cur[pi[k - 1] >> 5] |= 1u << (pi[k - 1] & 31);
-            memcpy(&keep[(2 + (size_t)q * (P - 1) + (k - 1)) * kw], cur.data(), kw * sizeof(uint32_t));
-        }
-    }
-    float* rows = coalition_out_rows(h, logits_rows, R, who);
-    if (!rows) return -1;
-    hipStream_t st = (hipStream_t)stream;
-    if (mark_wide_upload(h, g, keep.data(), R, (rank.size() + 3) / 4, st, who)) return -1;
-    uint8_t* rank_at = reinterpret_cast<uint8_t*>((unsigned*)h->aw.words + (size_t)R * kw + mark_player_words(g));
-    HIP_TRY(hipMemcpyAsync(rank_at, rank.data(), rank.size(), hipMemcpyHostToDevice, st));
-    if (mark_rows(h, bt, g, R, rows, st)) return -1;
-    PermShapleyArgs pa;
-    memset(&pa, 0, sizeof pa);
-    pa.v = rows, pa.rank = rank_at, pa.phi = phi, pa.se = se;
-    pa.n = (float)n_perm, pa.nn1 = (float)((double)n_perm * (n_perm - 1));
-    pa.P = P, pa.n_perm = n_perm, pa.n_out = c.n_out;
-    hipLaunchKernelGGL(k_perm_shapley, dim3(bt->B, P), dim3(kShapThreads), 0, st, pa);
-    LAUNCH_CHECK("k_perm_shapley");
-    forward_one_more(h);
-    return 0;
-}
-extern "C" int cf_mark_shapley_sampled(cf_handle* h, const cf_batch* bt, const cf_mark_wide_opts* o, const uint8_t* perms, int n_perm, float* phi,
-                                       float* se, float* logits_rows, void* stream) {
-    const char* who = "cf_mark_shapley_sampled";
-    MarkGame g;
-    cf_mark_donor_opts d;
-    return mark_wide_game(h, bt, o, &g, &d, who) ? -1 : mark_sampled_impl(h, bt, g, perms, n_perm, phi, se, logits_rows, stream, who);
-}
-
-// The window game (cf_mark_windows.h): the wide game's checks, then the windows against the coarsest resolution's W bins (nested bin
-// counts in the scan's wording, W within the kernels' table) and the rule.  `limit`: the most players (the exact call: kCoalMaxS).
-static int mark_window_game(cf_handle* h, const cf_batch* bt, const cf_mark_window_opts* o, MarkGame* g, cf_mark_donor_opts* d, const char* who,
-                            int limit = kMarkWideMaxP) {
-    *g = o ? MarkGame{o->n_players, o->player_marks, o->player_regions, o->scale, nullptr} : MarkGame{};
-    if (mark_check(h, bt, o != nullptr, *g, who, limit)) return -1;
-    g->kw = (g->P + 31) / 32;
-    const cf_config& c = h->cfg;
-    int rc = 0;
-    for (int r = 1; r < c.n_res; ++r)
-        if (c.n_bins[r] < c.n_bins[rc]) rc = r;
-    const int W = c.n_bins[rc];
-    for (int r = 0; r < c.n_res; ++r)
-        if (c.n_bins[r] % W) return fail("%s: n_bins[%d] = %d is not a multiple of the coarsest resolution's %d bins", who, r, c.n_bins[r], W);
-    if (W > kWinMaxW) return fail("%s: the coarsest resolution has W = %d bins; the window table holds at most %d", who, W, kWinMaxW);
-    if (!o->player_lo || !o->player_hi) return fail("%s: null player_lo / player_hi", who);
-    for (int p = 0; p < g->P; ++p) {
-        const int lo = o->player_lo[p], hi = o->player_hi[p];
-        if (lo < 0 || hi > W || lo >= hi)
-            return fail("%s: player %d has the window [%d, %d): 0 <= lo < hi <= W = %d coarsest bins is required", who, p, lo, hi, W);
-    }
-    g->lo = o->player_lo, g->hi = o->player_hi, g->flip = o->flip, g->W = W, g->rc = rc;
-    return mark_rule(h, g, d, o->donor_promoter_feats, o->donor_pcre_feats, who);
-}
-
-extern "C" int cf_mark_window_coalitions(cf_handle* h, const cf_batch* bt, const cf_mark_window_opts* o, const uint32_t* keep, int n_coal,
-                                         float* logits, void* stream) {
-    const char* who = "cf_mark_window_coalitions";
-    MarkGame g;
-    cf_mark_donor_opts d;
-    if (mark_window_game(h, bt, o, &g, &d, who)) return -1;
-    if (!logits) return fail("%s: null logits", who);
-    hipStream_t st = (hipStream_t)stream;
-    if (mark_wide_upload(h, g, keep, n_coal, 0, st, who)) return -1;
-    return mark_rows(h, bt, g, n_coal, logits, st);
-}
-extern "C" int cf_mark_window_shapley(cf_handle* h, const cf_batch* bt, const cf_mark_window_opts* o, float* phi, float* logits_all, void* stream) {
-    const char* who = "cf_mark_window_shapley";
-    MarkGame g;
-    cf_mark_donor_opts d;
-    return mark_window_game(h, bt, o, &g, &d, who, kCoalMaxS) ? -1 : mark_shapley_impl(h, bt, g, phi, logits_all, stream, who);
-}
-extern "C" int cf_mark_window_shapley_sampled(cf_handle* h, const cf_batch* bt, const cf_mark_window_opts* o, const uint8_t* perms, int n_perm,
-                                              float* phi, float* se, float* logits_rows, void* stream) {
-    const char* who = "cf_mark_window_shapley_sampled";
-    MarkGame g;
-    cf_mark_donor_opts d;
-    return mark_window_game(h, bt, o, &g, &d, who) ? -1 : mark_sampled_impl(h, bt, g, perms, n_perm, phi, se, logits_rows, stream, who);
-}
-
-// The fine window game (cf_mark_fine.h): the wide game's checks on the players, the fine scan's on the region, the nesting, start and
-// lengths, then the windows and the rule.  `regions`: storage for the one region word every player carries (mark_check reads it; the
-// kernels do not).  With `lengths` the finest centre pad-mask rows of the region are read back once, as cf_perturbation_scan_fine does.
-static int mark_fine_game(cf_handle* h, const cf_batch* bt, const cf_mark_fine_opts* o, MarkGame* g, cf_mark_donor_opts* d, std::vector<unsigned>* regions,
-                          hipStream_t st, const char* who, int limit = kMarkWideMaxP) {
-    if (o) regions->assign((size_t)std::min(std::max(o->n_players, 1), kMarkWideMaxP), 1u);
-    *g = o ? MarkGame{o->n_players, o->player_marks, regions->data(), o->scale, nullptr} : MarkGame{};
-    if (mark_check(h, bt, o != nullptr, *g, who, limit)) return -1;
-    g->kw = (g->P + 31) / 32;
-    const cf_config& c = h->cfg;
-    const int nres = c.n_res, S = c.i_max, B = bt->B, slot = o->region - 1;
-    if (o->region < 0 || o->region > S) return fail("%s: region = %d outside [0, i_max = %d]", who, o->region, S);
-    int rf = 0;
-    for (int r = 1; r < nres; ++r)
-        if (c.binsizes[r] < c.binsizes[rf]) rf = r;
-    const int Lf = c.n_bins[rf], bf = c.binsizes[rf];
-    int rc = 0;
-    for (int r = 1; r < nres; ++r)
-        if (c.n_bins[r] < c.n_bins[rc]) rc = r;
-    for (int r = 0; r < nres; ++r) {      // (nested bin counts, in the scan's wording: the zoom starts from coarse windows)
-        if (c.n_bins[r] % c.n_bins[rc])
-            return fail("%s: n_bins[%d] = %d is not a multiple of the coarsest resolution's %d bins", who, r, c.n_bins[r], c.n_bins[rc]);
-        if (Lf % c.n_bins[r])
-            return fail("%s: n_bins[%d] = %d of the finest resolution is not a multiple of n_bins[%d] = %d", who, rf, Lf, r, c.n_bins[r]);
-    }
-    if (Lf > kFineMaxL) return fail("%s: the finest resolution has n_bins[%d] = %d bins; the window table holds at most %d", who, rf, Lf, kFineMaxL);
-    for (int r = nres; r < kMaxRes; ++r)
-        if (o->feats_out[r]) return fail("%s: feats_out[%d]: the model has %d resolutions", who, r, nres);
-    if (!o->player_lo || !o->player_hi) return fail("%s: null player_lo / player_hi", who);
-    for (int p = 0; p < g->P; ++p) {
-        const int lo = o->player_lo[p], hi = o->player_hi[p];
-        if (lo < 0 || lo >= hi) return fail("%s: player %d has the window [%d, %d): 0 <= lo < hi finest bins is required", who, p, lo, hi);
-    }
-    for (int b = 0; o->start && b < B; ++b)
-        if (o->start[b] < 0) return fail("%s: start[%d] = %d: a finest genomic bin >= 0", who, b, o->start[b]);
-    g->lo = o->player_lo, g->hi = o->player_hi, g->flip = o->flip, g->fine = o, g->rf = rf, g->bf = bf;
-    if (mark_rule(h, g, d, o->donor_promoter_feats, o->donor_pcre_feats, who)) return -1;
-    g->fine_words.assign(2 * (size_t)B, (unsigned)bf);
-    for (int b = 0; b < B; ++b) g->fine_words[b] = o->start ? (unsigned)o->start[b] : 0u;
-    if (o->lengths && B > 0) {
-        const uint8_t* rm = slot < 0 ? bt->promoter_mask_row[rf] : bt->pcre_mask_row[rf] + (long long)slot * bt->pcre_mask_stride[rf];
-        const long long rm_stride = slot < 0 ? bt->promoter_mask_stride[rf] : (long long)S * bt->pcre_mask_stride[rf];
-        std::vector<uint8_t> m((size_t)B * Lf);
-        HIP_TRY(hipMemcpy2DAsync(m.data(), Lf, rm, (size_t)rm_stride, Lf, B, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (int b = 0; b < B; ++b) {
-            int lo = Lf, hi = 0;
-            for (int k = 0; k < Lf; ++k)
-                if (!m[(size_t)b * Lf + k]) lo = std::min(lo, k), hi = k + 1;
-            const long long nf = hi > lo ? hi - lo : 0, len = o->lengths[b];
-            if (!nf) continue;      // a dummy slot: every player is a null player there, the length is not read
-            if (len <= (nf - 1) * bf || len > nf * bf)
-                return fail("%s: lengths[%d] = %lld outside ((n_f - 1) b_f, n_f b_f] = (%lld, %lld]: the region has n_f = %lld real bins of b_f = %d samples",
-                            who, b, len, (nf - 1) * bf, nf * bf, nf, bf);
-            g->fine_words[B + b] = (unsigned)(len - (nf - 1) * bf);
-        }
-    }
-    return 0;
-}
-
-extern "C" int cf_mark_fine_coalitions(cf_handle* h, const cf_batch* bt, const cf_mark_fine_opts* o, const uint32_t* keep, int n_coal, float* logits,
-                                       void* stream) {
-    const char* who = "cf_mark_fine_coalitions";
-    MarkGame g;
-    cf_mark_donor_opts d;
-    std::vector<unsigned> regions;
-    hipStream_t st = (hipStream_t)stream;
-    if (mark_fine_game(h, bt, o, &g, &d, &regions, st, who)) return -1;
-    if (!logits) return fail("%s: null logits", who);
-    if (mark_wide_upload(h, g, keep, n_coal, 0, st, who)) return -1;
-    return mark_rows(h, bt, g, n_coal, logits, st);
-}
-extern "C" int cf_mark_fine_shapley(cf_handle* h, const cf_batch* bt, const cf_mark_fine_opts* o, float* phi, float* logits_all, void* stream) {
-    const char* who = "cf_mark_fine_shapley";
-    MarkGame g;
-    cf_mark_donor_opts d;
-    std::vector<unsigned> regions;
-    if (mark_fine_game(h, bt, o, &g, &d, &regions, (hipStream_t)stream, who, kCoalMaxS)) return -1;
-    return mark_shapley_impl(h, bt, g, phi, logits_all, stream, who);
-}
-extern "C" int cf_mark_fine_shapley_sampled(cf_handle* h, const cf_batch* bt, const cf_mark_fine_opts* o, const uint8_t* perms, int n_perm, float* phi,
-                                            float* se, float* logits_rows, void* stream) {
-    const char* who = "cf_mark_fine_shapley_sampled";
-    MarkGame g;
-    cf_mark_donor_opts d;
-    std::vector<unsigned> regions;
-    if (mark_fine_game(h, bt, o, &g, &d, &regions, (hipStream_t)stream, who)) return -1;
-    return mark_sampled_impl(h, bt, g, perms, n_perm, phi, se, logits_rows, stream, who);
 }

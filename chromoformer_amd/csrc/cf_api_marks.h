@@ -1,0 +1,403 @@
+// cf_api_marks.h -- host side of the histone-mark games: mark coalitions, exact Shapley values and pair epistasis under the scale rule
+// (cf_mark_*) and the donor rule (cf_mark_donor_*), the wide game and its sampled Shapley values, the window game, the fine window game.
+// One MarkGame per call, built and checked by the constructor of its kind, then one of three calls on it: the given coalitions, an exact
+// game (Shapley / epistasis), sampled permutations.  Part of cf_api.hip's single translation unit: included there behind
+// cf_api_attrib.h, whose chunk loop, geometry helpers and exact-game reducers it uses; not on its own.
+#pragma once
+
+// Histone-mark coalitions (cf_marks.h).  The families share everything but the options struct and the expand kernel: MarkGame is what
+// the options struct says, checked.  `kind` names the table layout and, with `donor`, the kernel:
+//   narrow  [words | marks_p | regions_p], one word per coalition                 k_mark_expand / k_mark_donor_expand
+//   wide    [n_coal * kw words | marks_p | regions_p | extra]                       k_mark_wide_expand / k_mark_wide_donor_expand
+//   window  [words | marks_p | regions_p | lo_p | hi_p | extra]                     k_mark_window_expand / k_mark_window_donor_expand
+//   fine    [words | marks_p | lo_p | hi_p | start[B] | cnt_last[B] | extra]        k_mark_fine_expand / k_mark_fine_donor_expand
+enum MarkKind { kMarkNarrow, kMarkWide, kMarkWindow, kMarkFine };
+struct MarkGame {
+    MarkKind kind = kMarkNarrow;
+    int P = 0, kw = 1;                    // players; words per coalition
+    const unsigned* marks = nullptr;      // host [P]
+    const unsigned* regions = nullptr;    // host [P]
+    float scale = 0.f;                    // the scale rule (donor == nullptr)
+    const cf_mark_donor_opts* donor = nullptr;      // the donor rule
+    const int* lo = nullptr;              // host [P]: player p's bins [lo, hi) -- coarsest bins (window), finest bins (fine)
+    const int* hi = nullptr;
+    const uint8_t* flip = nullptr;        // device [B] or null: the promoter is stored mirrored (window, fine)
+    int W = 0, rc = 0;                    // the coarsest resolution's bin count and index (window)
+    const cf_mark_fine_opts* fine = nullptr;      // the fine game's region and feats_out
+    int rf = 0, bf = 0;                           // ... the finest resolution's index and bin size
+    std::vector<unsigned> fine_words;             // ... [start[B] | cnt_last[B]]
+    cf_mark_donor_opts rule_donor;                // storage: the donor's pointers of a one-struct game (mark_rule points `donor` here)
+    std::vector<unsigned> fine_regions;           // storage: the one region word every player of a fine game carries (mark_check reads it)
+    MarkGame() = default;
+    MarkGame(const MarkGame&) = delete;      // (`donor` and `regions` may point into the game)
+    void players(MarkKind k, int n, const unsigned* m, const unsigned* rg, float s) { kind = k, P = n, kw = (n + 31) / 32, marks = m, regions = rg, scale = s; }
+};
+
+// mark_check: what the entry points check alike, in front of anything launched -- the handle, the batch, riders, the options: the
+// player count (at most `limit`), the player words.  `o`: whether the caller's opts pointer is non-null.
+static int mark_check(cf_handle* h, const cf_batch* bt, bool o, const MarkGame& g, const char* who, int limit = kCoalMaxS) {
+    if (attrib_open(h, bt, true, who)) return -1;
+    if (!o) return fail("%s: null opts", who);
+    const cf_config& c = h->cfg;
+    const int S = c.i_max, F = c.n_feats;
+    if (g.P < 1 || g.P > limit) return fail("%s: n_players = %d outside 1..%d", who, g.P, limit);
+    if (!g.marks || !g.regions) return fail("%s: null player_marks / player_regions", who);
+    for (int p = 0; p < g.P; ++p) {
+        const unsigned pm = g.marks[p], pr = g.regions[p];
+        if (!pm) return fail("%s: player_marks[%d] = 0: a player names at least one mark", who, p);
+        if (!pr) return fail("%s: player_regions[%d] = 0: a player names at least one region (bit 0 the promoter, bit 1 + j pCRE slot j)", who, p);
+        if (F < 32 && pm >> F) return fail("%s: player_marks[%d] = 0x%x names a mark >= n_feats = %d", who, p, pm, F);
+        if (pr >> S >> 1) return fail("%s: player_regions[%d] = 0x%x names a region above i_max = %d", who, p, pr, S);
+    }
+    return 0;
+}
+// ... then the scale of the scale rule,
+static int mark_game(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, MarkGame* g, const char* who) {
+    if (o) g->players(kMarkNarrow, o->n_players, o->player_marks, o->player_regions, o->scale);
+    if (mark_check(h, bt, o != nullptr, *g, who)) return -1;
+    if (!(o->scale >= 0.f) || !std::isfinite(o->scale)) return fail("%s: scale = %g: a finite factor >= 0", who, (double)o->scale);
+    return 0;
+}
+// ... or the donor's feature pointers of the donor rule.
+static int mark_donor_game(cf_handle* h, const cf_batch* bt, const cf_mark_donor_opts* o, MarkGame* g, const char* who) {
+    if (o) g->players(kMarkNarrow, o->n_players, o->player_marks, o->player_regions, 0.f), g->donor = o;
+    if (mark_check(h, bt, o != nullptr, *g, who)) return -1;
+    for (int r = 0; r < h->cfg.n_res; ++r)
+        if (!o->donor_promoter_feats[r] || !o->donor_pcre_feats[r])
+            return fail("%s: null donor_promoter_feats / donor_pcre_feats[%d]: the donor's features at every one of the model's %d resolutions", who, r, h->cfg.n_res);
+    return 0;
+}
+
+// The wide game (cf_marks_wide.h): up to kMarkWideMaxP players, kw words per coalition, one options struct for both rules.
+// mark_rule: which rule a one-struct game asks for -- all donor pointers null: the scale rule (g->scale, checked); all set: the donor
+// rule (g->donor, filled); mixed: refused.
+static int mark_rule(cf_handle* h, MarkGame* g, const float* const* don_p, const float* const* don_c, const char* who) {
+    int given = 0;
+    for (int r = 0; r < h->cfg.n_res; ++r) given += (don_p[r] != nullptr) + (don_c[r] != nullptr);
+    if (given && given != 2 * h->cfg.n_res)
+        return fail("%s: %d of the %d donor_promoter_feats / donor_pcre_feats pointers below the model's %d resolutions are null: all of them "
+                    "(the scale rule) or none (the donor rule)", who, 2 * h->cfg.n_res - given, 2 * h->cfg.n_res, h->cfg.n_res);
+    if (given) {
+        cf_mark_donor_opts* d = &g->rule_donor;
+        memset(d, 0, sizeof *d);
+        for (int r = 0; r < h->cfg.n_res; ++r) d->donor_promoter_feats[r] = don_p[r], d->donor_pcre_feats[r] = don_c[r];
+        g->donor = d;
+        g->scale = 0.f;
+    } else if (!(g->scale >= 0.f) || !std::isfinite(g->scale)) {
+        return fail("%s: scale = %g: a finite factor >= 0", who, (double)g->scale);
+    }
+    return 0;
+}
+static int mark_wide_game(cf_handle* h, const cf_batch* bt, const cf_mark_wide_opts* o, MarkGame* g, const char* who) {
+    if (o) g->players(kMarkWide, o->n_players, o->player_marks, o->player_regions, o->scale);
+    if (mark_check(h, bt, o != nullptr, *g, who, kMarkWideMaxP)) return -1;
+    return mark_rule(h, g, o->donor_promoter_feats, o->donor_pcre_feats, who);
+}
+
+// The window game (cf_mark_windows.h): the wide game's checks, then the windows against the coarsest resolution's W bins (nested bin
+// counts in the scan's wording, W within the kernels' table) and the rule.  `limit`: the most players (the exact call: kCoalMaxS).
+static int mark_window_game(cf_handle* h, const cf_batch* bt, const cf_mark_window_opts* o, MarkGame* g, const char* who, int limit = kMarkWideMaxP) {
+    if (o) g->players(kMarkWindow, o->n_players, o->player_marks, o->player_regions, o->scale);
+    if (mark_check(h, bt, o != nullptr, *g, who, limit) || coarsest(h, who, &g->rc)) return -1;
+    const int W = g->W = h->cfg.n_bins[g->rc];
+    if (W > kWinMaxW) return fail("%s: the coarsest resolution has W = %d bins; the window table holds at most %d", who, W, kWinMaxW);
+    if (!o->player_lo || !o->player_hi) return fail("%s: null player_lo / player_hi", who);
+    for (int p = 0; p < g->P; ++p) {
+        const int lo = o->player_lo[p], hi = o->player_hi[p];
+        if (lo < 0 || hi > W || lo >= hi)
+            return fail("%s: player %d has the window [%d, %d): 0 <= lo < hi <= W = %d coarsest bins is required", who, p, lo, hi, W);
+    }
+    g->lo = o->player_lo, g->hi = o->player_hi, g->flip = o->flip;
+    return mark_rule(h, g, o->donor_promoter_feats, o->donor_pcre_feats, who);
+}
+
+// The fine window game (cf_mark_fine.h): the wide game's checks on the players, the fine scan's on the region, the nesting, start and
+// lengths (fine_tail_words, as cf_perturbation_scan_fine), then the windows and the rule.
+static int mark_fine_game(cf_handle* h, const cf_batch* bt, const cf_mark_fine_opts* o, MarkGame* g, hipStream_t st, const char* who,
+                          int limit = kMarkWideMaxP) {
+    if (o) {
+        g->fine_regions.assign((size_t)std::min(std::max(o->n_players, 1), kMarkWideMaxP), 1u);
+        g->players(kMarkFine, o->n_players, o->player_marks, g->fine_regions.data(), o->scale);
+    }
+    if (mark_check(h, bt, o != nullptr, *g, who, limit)) return -1;
+    const cf_config& c = h->cfg;
+    const int nres = c.n_res, S = c.i_max, B = bt->B;
+    if (o->region < 0 || o->region > S) return fail("%s: region = %d outside [0, i_max = %d]", who, o->region, S);
+    int rc = 0;      // (nested bin counts, in the scan's wording: the zoom starts from coarse windows)
+    if (coarsest(h, who, &rc) || finest(h, who, &g->rf)) return -1;
+    const int rf = g->rf, Lf = c.n_bins[rf];
+    if (Lf > kFineMaxL) return fail("%s: the finest resolution has n_bins[%d] = %d bins; the window table holds at most %d", who, rf, Lf, kFineMaxL);
+    for (int r = nres; r < kMaxRes; ++r)
+        if (o->feats_out[r]) return fail("%s: feats_out[%d]: the model has %d resolutions", who, r, nres);
+    if (!o->player_lo || !o->player_hi) return fail("%s: null player_lo / player_hi", who);
+    for (int p = 0; p < g->P; ++p) {
+        const int lo = o->player_lo[p], hi = o->player_hi[p];
+        if (lo < 0 || lo >= hi) return fail("%s: player %d has the window [%d, %d): 0 <= lo < hi finest bins is required", who, p, lo, hi);
+    }
+    for (int b = 0; o->start && b < B; ++b)
+        if (o->start[b] < 0) return fail("%s: start[%d] = %d: a finest genomic bin >= 0", who, b, o->start[b]);
+    g->lo = o->player_lo, g->hi = o->player_hi, g->flip = o->flip, g->fine = o, g->bf = c.binsizes[rf];
+    if (mark_rule(h, g, o->donor_promoter_feats, o->donor_pcre_feats, who)) return -1;
+    g->fine_words.resize(2 * (size_t)B);
+    return fine_tail_words(h, bt, o->region, rf, o->start, o->lengths, st, who, g->fine_words.data());
+}
+
+// The n_coal * kw coalition words (validated) and the player words into the workspace's word table, in the layout of the game's kind
+// (above), with room for `extra` words behind them.
+static int mark_player_words(const MarkGame& g) { return g.kind == kMarkFine ? 3 * g.P + (int)g.fine_words.size() : (g.kind == kMarkWindow ? 4 : 2) * g.P; }
+static int mark_upload(cf_handle* h, const MarkGame& g, const uint32_t* keep, int n_coal, size_t extra, hipStream_t st, const char* who) {
+    const int P = g.P, kw = g.kw;
+    if (n_coal < 1) return fail("%s: n_coal = %d: at least 1 coalition", who, n_coal);
+    if (!keep) return fail("%s: null keep", who);
+    if (P & 31)
+        for (int k = 0; k < n_coal; ++k) {
+            const uint32_t last = keep[(size_t)k * kw + kw - 1];
+            if (!(last >> (P & 31))) continue;
+            if (g.kind == kMarkNarrow) return fail("%s: keep[%d] = 0x%x names a player >= n_players = %d", who, k, last, P);
+            return fail("%s: keep[%d] (word %d = 0x%x) names a player >= n_players = %d", who, k, kw - 1, last, P);
+        }
+    const size_t nw = (size_t)n_coal * kw;
+    if (attrib_ws(h, who) || h->aw.words.need(nw + mark_player_words(g) + extra, 256, who)) return -1;
+    unsigned* tab = h->aw.words;
+    HIP_TRY(hipMemcpyAsync(tab, keep, nw * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(tab + nw, g.marks, P * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    unsigned* at = tab + nw + P;
+    if (g.kind != kMarkFine) {
+        HIP_TRY(hipMemcpyAsync(at, g.regions, P * sizeof(unsigned), hipMemcpyHostToDevice, st));
+        at += P;
+    }
+    if (g.lo) {
+        HIP_TRY(hipMemcpyAsync(at, g.lo, P * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(at + P, g.hi, P * sizeof(int), hipMemcpyHostToDevice, st));
+        at += 2 * P;
+    }
+    if (!g.fine_words.empty()) HIP_TRY(hipMemcpyAsync(at, g.fine_words.data(), g.fine_words.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+// The B * n_coal rows of a mark-coalition call (gene-major; row (b, k) is coalition k of the table mark_upload wrote), every row
+// through the whole forward: chunk_forward with the expand kernel of the game's kind and rule, on the argument struct of that kind.
+// k_attc2 takes as many regions per workgroup as for the caller's B genes (ag_genes), as scan_region_rows: the result does not depend
+// on max_batch.
+static int mark_rows(cf_handle* h, const cf_batch* bt, const MarkGame& g, int n_coal, float* logits, hipStream_t st) {
+    const cf_config& c = h->cfg;
+    const int nres = c.n_res, B = bt->B, P = g.P;
+    MarkExpandArgs ea;      // what every kind reads
+    memset(&ea, 0, sizeof ea);
+    cf_batch cb;            // the chunk's batch: the rows' copies
+    chunk_rows(h, bt, &ea.rows, &cb);
+    for (int r = 0; r < nres; ++r) {
+        ea.pf_in[r] = bt->promoter_feats[r];
+        ea.cf_in[r] = bt->pcre_feats[r];
+        ea.pf_out[r] = h->aw.row[r];
+        ea.cf_out[r] = h->aw.row[kMaxRes + r];
+    }
+    ea.freq_in = bt->interaction_freq;
+    ea.freq_out = h->aw.row[2 * kMaxRes];
+    ea.words = h->aw.words;
+    ea.players = h->aw.words + (size_t)n_coal * g.kw;
+    ea.scale = g.scale;
+    ea.n_coal = n_coal, ea.P = P, ea.F = c.n_feats;
+    auto donor_feats = [&](const float** pf, const float** cf) {
+        for (int r = 0; g.donor && r < nres; ++r) pf[r] = g.donor->donor_promoter_feats[r], cf[r] = g.donor->donor_pcre_feats[r];
+    };
+    // the chunk loop on `d` (the donor rule's struct, its first member `a` the scale rule's, whose first member is `m`): kernel kd or k
+    const long long launches0 = g_launches;
+    auto run = [&](auto kd, const char* nd, auto k, const char* nk, auto& d, auto& a, MarkExpandArgs& m) {
+        const int rv = chunk_forward(h, &cb, (long long)B * n_coal, logits, true, B, st, [&](long long g0, int n) {
+            m.g0 = g0;
+            const dim3 grid(n, nres, kMarkSlices);
+            return g.donor ? launch_expand(kd, nd, grid, kIgxThreads, d, st) : launch_expand(k, nk, grid, kIgxThreads, a, st);
+        });
+        h->x0_fwd = false;
+        forward_counted(h, launches0);
+        return rv ? -1 : 0;
+    };
+    if (g.kind == kMarkFine) {      // ea with the region's centre mask rows, start, the tail counts and feats_out
+        MarkFineDonorArgs fd;
+        memset(&fd, 0, sizeof fd);
+        fd.w.m = ea;
+        donor_feats(fd.pf_don, fd.cf_don);
+        for (int r = 0; r < nres; ++r) {
+            region_mask_row(bt, g.fine->region, r, c.i_max, &fd.w.rm_in[r], &fd.w.rm_stride[r]);
+            fd.w.feats_out[r] = g.fine->feats_out[r];
+        }
+        fd.w.start = reinterpret_cast<const int*>(ea.players) + 3 * P;
+        fd.w.cnt_last = fd.w.start + B;
+        fd.w.flip = g.flip;
+        fd.w.rf = g.rf, fd.w.bf = g.bf, fd.w.region = g.fine->region;
+        return run(k_mark_fine_donor_expand, "k_mark_fine_donor_expand", k_mark_fine_expand, "k_mark_fine_expand", fd, fd.w, fd.w.m);
+    }
+    if (g.kind == kMarkWindow) {      // ea with the promoter's centre mask rows, flip and the coarsest resolution
+        MarkWindowDonorArgs wd;
+        memset(&wd, 0, sizeof wd);
+        wd.w.m = ea;
+        donor_feats(wd.pf_don, wd.cf_don);
+        for (int r = 0; r < nres; ++r) wd.w.pmc[r] = bt->promoter_mask_row[r];
+        wd.w.flip = g.flip;
+        wd.w.W = g.W, wd.w.rc = g.rc;
+        return run(k_mark_window_donor_expand, "k_mark_window_donor_expand", k_mark_window_expand, "k_mark_window_expand", wd, wd.w, wd.w.m);
+    }
+    MarkDonorArgs da;
+    memset(&da, 0, sizeof da);
+    da.m = ea;
+    donor_feats(da.pf_don, da.cf_don);
+    if (g.kind == kMarkWide) return run(k_mark_wide_donor_expand, "k_mark_wide_donor_expand", k_mark_wide_expand, "k_mark_wide_expand", da, da.m, da.m);
+    return run(k_mark_donor_expand, "k_mark_donor_expand", k_mark_expand, "k_mark_expand", da, da.m, da.m);
+}
+
+// The three calls on a checked game: the given coalitions;
+static int mark_coalitions_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g, const uint32_t* keep, int n_coal, float* logits, void* stream,
+                                const char* who) {
+    if (!logits) return fail("%s: null logits", who);
+    hipStream_t st = (hipStream_t)stream;
+    if (mark_upload(h, g, keep, n_coal, 0, st, who)) return -1;
+    return mark_rows(h, bt, g, n_coal, logits, st);
+}
+// an exact game -- all 2^P coalitions and k_shapley, or the pair-deletion coalitions and k_epistasis, with S = P (all_words /
+// launch_shapley, pair_words / launch_epistasis: cf_api_attrib.h) -- through mark_upload + mark_rows;
+static int mark_exact_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g, bool pairs, float* out, float* logits_rows, void* stream, const char* who) {
+    if (!out) return fail(pairs ? "%s: null eps" : "%s: null phi", who);
+    const std::vector<uint32_t> keep = pairs ? pair_words(g.P) : all_words(g.P);
+    const int R = (int)keep.size();
+    float* rows = coalition_out_rows(h, logits_rows, R, who);
+    if (!rows) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    if (mark_upload(h, g, keep.data(), R, 0, st, who) || mark_rows(h, bt, g, R, rows, st)) return -1;
+    return pairs ? launch_epistasis(h, bt->B, g.P, rows, out, st) : launch_shapley(h, bt->B, g.P, rows, out, st);
+}
+// the prefix rows of n_perm permutations through mark_upload + mark_rows (column 0 nobody, column 1 everybody, column
+// 2 + q (P - 1) + (k - 1) the first k players of permutation q), then k_perm_shapley on the inverse permutations, which travel as bytes
+// behind the player words.  `g`: a checked game of a kind with kw words per coalition (wide, window, fine).
+static int mark_sampled_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g, const uint8_t* perms, int n_perm, float* phi, float* se,
+                             float* logits_rows, void* stream, const char* who) {
+    if (!phi) return fail("%s: null phi", who);
+    if (!perms) return fail("%s: null perms", who);
+    if (n_perm < 1) return fail("%s: n_perm = %d: at least 1 permutation", who, n_perm);
+    const cf_config& c = h->cfg;
+    const int P = g.P, kw = g.kw;
+    const long long R64 = 2 + (long long)n_perm * (P - 1);
+    if (R64 * kw > (1ll << 30)) return fail("%s: n_perm = %d: %lld rows per gene; at most 2^30 coalition words", who, n_perm, R64);
+    const int R = (int)R64;
+    std::vector<uint8_t> rank((size_t)n_perm * P);
+    std::vector<uint32_t> keep((size_t)R * kw, 0u), cur(kw);
+    for (int p = 0; p < P; ++p) keep[kw + (p >> 5)] |= 1u << (p & 31);      // column 1: everybody
+    for (int q = 0; q < n_perm; ++q) {
+        const uint8_t* pi = perms + (size_t)q * P;
+        uint8_t* rk = rank.data() + (size_t)q * P;
+        memset(rk, 0xFF, P);
+        for (int k = 0; k < P; ++k) {
+            if (pi[k] >= P || rk[pi[k]] != 0xFF) return fail("%s: perms[%d] is not a permutation of 0..%d (position %d holds %d)", who, q, P - 1, k, (int)pi[k]);
+            rk[pi[k]] = (uint8_t)k;
+        }
+        std::fill(cur.begin(), cur.end(), 0u);
+        for (int k = 1; k < P; ++k) {
+            cur[pi[k - 1] >> 5] |= 1u << (pi[k - 1] & 31);
+            memcpy(&keep[(2 + (size_t)q * (P - 1) + (k - 1)) * kw], cur.data(), kw * sizeof(uint32_t));
+        }
+    }
+    float* rows = coalition_out_rows(h, logits_rows, R, who);
+    if (!rows) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    if (mark_upload(h, g, keep.data(), R, (rank.size() + 3) / 4, st, who)) return -1;
+    uint8_t* rank_at = reinterpret_cast<uint8_t*>((unsigned*)h->aw.words + (size_t)R * kw + mark_player_words(g));
+    HIP_TRY(hipMemcpyAsync(rank_at, rank.data(), rank.size(), hipMemcpyHostToDevice, st));
+    if (mark_rows(h, bt, g, R, rows, st)) return -1;
+    PermShapleyArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.v = rows, pa.rank = rank_at, pa.phi = phi, pa.se = se;
+    pa.n = (float)n_perm, pa.nn1 = (float)((double)n_perm * (n_perm - 1));
+    pa.P = P, pa.n_perm = n_perm, pa.n_out = c.n_out;
+    hipLaunchKernelGGL(k_perm_shapley, dim3(bt->B, P), dim3(kShapThreads), 0, st, pa);
+    LAUNCH_CHECK("k_perm_shapley");
+    forward_one_more(h);
+    return 0;
+}
+
+// The entry points: the game of the family, then its call.  The scale rule's one-word game;
+extern "C" int cf_mark_coalitions(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, const uint32_t* keep, int n_coal, float* logits,
+                                  void* stream) {
+    const char* who = "cf_mark_coalitions";
+    MarkGame g;
+    return mark_game(h, bt, o, &g, who) ? -1 : mark_coalitions_impl(h, bt, g, keep, n_coal, logits, stream, who);
+}
+extern "C" int cf_mark_shapley(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, float* phi, float* logits_all, void* stream) {
+    const char* who = "cf_mark_shapley";
+    MarkGame g;
+    return mark_game(h, bt, o, &g, who) ? -1 : mark_exact_impl(h, bt, g, false, phi, logits_all, stream, who);
+}
+extern "C" int cf_mark_epistasis(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, float* eps, float* logits_pairs, void* stream) {
+    const char* who = "cf_mark_epistasis";
+    MarkGame g;
+    return mark_game(h, bt, o, &g, who) ? -1 : mark_exact_impl(h, bt, g, true, eps, logits_pairs, stream, who);
+}
+
+// the donor family: an absent mark takes the donor's bits (k_mark_donor_expand); everything else as above;
+extern "C" int cf_mark_donor_coalitions(cf_handle* h, const cf_batch* bt, const cf_mark_donor_opts* o, const uint32_t* keep, int n_coal,
+                                        float* logits, void* stream) {
+    const char* who = "cf_mark_donor_coalitions";
+    MarkGame g;
+    return mark_donor_game(h, bt, o, &g, who) ? -1 : mark_coalitions_impl(h, bt, g, keep, n_coal, logits, stream, who);
+}
+extern "C" int cf_mark_donor_shapley(cf_handle* h, const cf_batch* bt, const cf_mark_donor_opts* o, float* phi, float* logits_all, void* stream) {
+    const char* who = "cf_mark_donor_shapley";
+    MarkGame g;
+    return mark_donor_game(h, bt, o, &g, who) ? -1 : mark_exact_impl(h, bt, g, false, phi, logits_all, stream, who);
+}
+extern "C" int cf_mark_donor_epistasis(cf_handle* h, const cf_batch* bt, const cf_mark_donor_opts* o, float* eps, float* logits_pairs, void* stream) {
+    const char* who = "cf_mark_donor_epistasis";
+    MarkGame g;
+    return mark_donor_game(h, bt, o, &g, who) ? -1 : mark_exact_impl(h, bt, g, true, eps, logits_pairs, stream, who);
+}
+
+// the wide game;
+extern "C" int cf_mark_coalitions_wide(cf_handle* h, const cf_batch* bt, const cf_mark_wide_opts* o, const uint32_t* keep, int n_coal, float* logits,
+                                       void* stream) {
+    const char* who = "cf_mark_coalitions_wide";
+    MarkGame g;
+    return mark_wide_game(h, bt, o, &g, who) ? -1 : mark_coalitions_impl(h, bt, g, keep, n_coal, logits, stream, who);
+}
+extern "C" int cf_mark_shapley_sampled(cf_handle* h, const cf_batch* bt, const cf_mark_wide_opts* o, const uint8_t* perms, int n_perm, float* phi,
+                                       float* se, float* logits_rows, void* stream) {
+    const char* who = "cf_mark_shapley_sampled";
+    MarkGame g;
+    return mark_wide_game(h, bt, o, &g, who) ? -1 : mark_sampled_impl(h, bt, g, perms, n_perm, phi, se, logits_rows, stream, who);
+}
+
+// the window game;
+extern "C" int cf_mark_window_coalitions(cf_handle* h, const cf_batch* bt, const cf_mark_window_opts* o, const uint32_t* keep, int n_coal,
+                                         float* logits, void* stream) {
+    const char* who = "cf_mark_window_coalitions";
+    MarkGame g;
+    return mark_window_game(h, bt, o, &g, who) ? -1 : mark_coalitions_impl(h, bt, g, keep, n_coal, logits, stream, who);
+}
+extern "C" int cf_mark_window_shapley(cf_handle* h, const cf_batch* bt, const cf_mark_window_opts* o, float* phi, float* logits_all, void* stream) {
+    const char* who = "cf_mark_window_shapley";
+    MarkGame g;
+    return mark_window_game(h, bt, o, &g, who, kCoalMaxS) ? -1 : mark_exact_impl(h, bt, g, false, phi, logits_all, stream, who);
+}
+extern "C" int cf_mark_window_shapley_sampled(cf_handle* h, const cf_batch* bt, const cf_mark_window_opts* o, const uint8_t* perms, int n_perm,
+                                              float* phi, float* se, float* logits_rows, void* stream) {
+    const char* who = "cf_mark_window_shapley_sampled";
+    MarkGame g;
+    return mark_window_game(h, bt, o, &g, who) ? -1 : mark_sampled_impl(h, bt, g, perms, n_perm, phi, se, logits_rows, stream, who);
+}
+
+// the fine window game.
+extern "C" int cf_mark_fine_coalitions(cf_handle* h, const cf_batch* bt, const cf_mark_fine_opts* o, const uint32_t* keep, int n_coal, float* logits,
+                                       void* stream) {
+    const char* who = "cf_mark_fine_coalitions";
+    MarkGame g;
+    return mark_fine_game(h, bt, o, &g, (hipStream_t)stream, who) ? -1 : mark_coalitions_impl(h, bt, g, keep, n_coal, logits, stream, who);
+}
+extern "C" int cf_mark_fine_shapley(cf_handle* h, const cf_batch* bt, const cf_mark_fine_opts* o, float* phi, float* logits_all, void* stream) {
+    const char* who = "cf_mark_fine_shapley";
+    MarkGame g;
+    return mark_fine_game(h, bt, o, &g, (hipStream_t)stream, who, kCoalMaxS) ? -1 : mark_exact_impl(h, bt, g, false, phi, logits_all, stream, who);
+}
+extern "C" int cf_mark_fine_shapley_sampled(cf_handle* h, const cf_batch* bt, const cf_mark_fine_opts* o, const uint8_t* perms, int n_perm, float* phi,
+                                            float* se, float* logits_rows, void* stream) {
+    const char* who = "cf_mark_fine_shapley_sampled";
+    MarkGame g;
+    return mark_fine_game(h, bt, o, &g, (hipStream_t)stream, who) ? -1 : mark_sampled_impl(h, bt, g, perms, n_perm, phi, se, logits_rows, stream, who);
+}

@@ -895,6 +895,59 @@ class ChromoformerBase(nn.Module):
         opts.player_marks, opts.player_regions = marks.ctypes.data, regions.ctypes.data
         return opts, (marks, regions), names
 
+    # The four calls every mark game offers, on a checked options struct of its family (`cfn`: the library's entry point): the runners
+    # allocate the outputs, book the call, run it and build `info`.
+    def _mark_run_coalitions(self, cfn, bs, opts, words, book):
+        logits = torch.empty(bs.B, len(words), self.n_out, device=self._device)      # (written in full by the library)
+        st = book()
+        _lib.check(getattr(_lib.lib(), cfn)(self._handle, C.byref(bs), C.byref(opts), words.ctypes.data, len(words), logits.data_ptr(), st), cfn)
+        return logits
+
+    def _mark_run_shapley(self, cfn, bs, opts, names, absent_key, book, return_coalitions):
+        P = opts.n_players
+        n = 1 << P
+        rows = torch.empty(bs.B, n, self.n_out, device=self._device)      # (both written in full by the library)
+        phi = torch.empty(bs.B, P, self.n_out, device=self._device)
+        st = book()
+        _lib.check(getattr(_lib.lib(), cfn)(self._handle, C.byref(bs), C.byref(opts), phi.data_ptr(), rows.data_ptr(), st), cfn)
+        info = {"logits": rows[:, n - 1].clone(), absent_key: rows[:, 0].clone(), "players": names}
+        info["delta"] = phi.sum(1) - (info["logits"] - info[absent_key])
+        if return_coalitions:
+            info["coalitions"] = rows
+        return phi, info
+
+    def _mark_run_epistasis(self, cfn, bs, opts, names, book):
+        P = opts.n_players
+        rows = torch.empty(bs.B, 1 + P + P * (P - 1) // 2, self.n_out, device=self._device)      # (both written in full by the library)
+        eps = torch.empty(bs.B, P, P, self.n_out, device=self._device)
+        st = book()
+        _lib.check(getattr(_lib.lib(), cfn)(self._handle, C.byref(bs), C.byref(opts), eps.data_ptr(), rows.data_ptr(), st), cfn)
+        return eps, {"logits": rows[:, 0].clone(), "single": rows[:, 1:1 + P].clone(), "players": names}
+
+    def _permutations(self, who, P, n_perm, seed, permutations):
+        """The orders of a sampled game of P players -> uint8 [n_perm, P]: shapley_permutations, or `permutations` checked."""
+        from .attribution import shapley_permutations
+        if permutations is None:
+            return shapley_permutations(P, n_perm, seed)
+        given = np.asarray(permutations.cpu() if hasattr(permutations, "cpu") else permutations)
+        if given.ndim != 2 or given.shape[0] < 1 or given.shape[1] != P or given.dtype.kind not in "iu" or given.min() < 0 or given.max() >= P:
+            raise ValueError("%s: permutations must be an integer array [n_perm >= 1, P = %d] with entries in [0, P)" % (who, P))
+        return np.ascontiguousarray(given, dtype=np.uint8)
+
+    def _mark_run_sampled(self, cfn, bs, opts, names, perms, book, return_rows):
+        P, n = opts.n_players, len(perms)
+        rows = torch.empty(bs.B, 2 + n * (P - 1), self.n_out, device=self._device)      # (all three written in full by the library)
+        phi = torch.empty(bs.B, P, self.n_out, device=self._device)
+        se = torch.empty(bs.B, P, self.n_out, device=self._device)
+        st = book()
+        _lib.check(getattr(_lib.lib(), cfn)(self._handle, C.byref(bs), C.byref(opts), perms.ctypes.data, n, phi.data_ptr(), se.data_ptr(),
+                                            rows.data_ptr(), st), cfn)
+        info = {"logits": rows[:, 1].clone(), "absent": rows[:, 0].clone(), "stderr": se, "names": names, "permutations": perms}
+        info["delta"] = phi.sum(1) - (info["logits"] - info["absent"])
+        if return_rows:
+            info["rows"] = rows
+        return phi, info
+
     @torch.no_grad()
     def mark_coalitions(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
                         interaction_freq=None, keep=None, players="marks", scale=0.0):
@@ -913,11 +966,7 @@ class ChromoformerBase(nn.Module):
         opts, _alive, _names = self._mark_opts(players, scale)
         words = mark_coalition_words(keep, opts.n_players, "mark_coalitions")
         bs, _keep, book = self._attrib_call("mark_coalitions", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
-        logits = torch.empty(bs.B, len(words), self.n_out, device=self._device)      # (written in full by the library)
-        st = book()
-        _lib.check(_lib.lib().cf_mark_coalitions(self._handle, C.byref(bs), C.byref(opts), words.ctypes.data, len(words), logits.data_ptr(), st),
-                   "cf_mark_coalitions")
-        return logits
+        return self._mark_run_coalitions("cf_mark_coalitions", bs, opts, words, book)
 
     @torch.no_grad()
     def mark_shapley(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
@@ -936,17 +985,7 @@ class ChromoformerBase(nn.Module):
         efficiency holds.  The packed forms of the first argument and the effect on a pending backward() are those of mark_coalitions."""
         opts, _alive, names = self._mark_opts(players, scale)
         bs, _keep, book = self._attrib_call("mark_shapley", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
-        P = opts.n_players
-        n = 1 << P
-        rows = torch.empty(bs.B, n, self.n_out, device=self._device)      # (both written in full by the library)
-        phi = torch.empty(bs.B, P, self.n_out, device=self._device)
-        st = book()
-        _lib.check(_lib.lib().cf_mark_shapley(self._handle, C.byref(bs), C.byref(opts), phi.data_ptr(), rows.data_ptr(), st), "cf_mark_shapley")
-        info = {"logits": rows[:, n - 1].clone(), "erased": rows[:, 0].clone(), "players": names}
-        info["delta"] = phi.sum(1) - (info["logits"] - info["erased"])
-        if return_coalitions:
-            info["coalitions"] = rows
-        return phi, info
+        return self._mark_run_shapley("cf_mark_shapley", bs, opts, names, "erased", book, return_coalitions)
 
     @torch.no_grad()
     def mark_epistasis(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
@@ -962,12 +1001,7 @@ class ChromoformerBase(nn.Module):
         of the first argument and the effect on a pending backward() are those of mark_coalitions."""
         opts, _alive, names = self._mark_opts(players, scale)
         bs, _keep, book = self._attrib_call("mark_epistasis", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
-        P = opts.n_players
-        rows = torch.empty(bs.B, 1 + P + P * (P - 1) // 2, self.n_out, device=self._device)      # (both written in full by the library)
-        eps = torch.empty(bs.B, P, P, self.n_out, device=self._device)
-        st = book()
-        _lib.check(_lib.lib().cf_mark_epistasis(self._handle, C.byref(bs), C.byref(opts), eps.data_ptr(), rows.data_ptr(), st), "cf_mark_epistasis")
-        return eps, {"logits": rows[:, 0].clone(), "single": rows[:, 1:1 + P].clone(), "players": names}
+        return self._mark_run_epistasis("cf_mark_epistasis", bs, opts, names, book)
 
     def mark_shapley_dataset(self, dataset, genes=None, players="marks", scale=0.0, epistasis=False, bsz=None, store=None):
         """mark_shapley (and optionally mark_epistasis) over the genes of a ChromoformerDataset
@@ -1048,12 +1082,7 @@ class ChromoformerBase(nn.Module):
             raise ValueError("mark_donor_coalitions: keep is required: the coalition words (bit p set: player p present)")
         bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
         opts, _alive, _names = self._mark_donor_opts(who, donor, players, bs.B)
-        words = mark_coalition_words(keep, opts.n_players, who)
-        logits = torch.empty(bs.B, len(words), self.n_out, device=self._device)      # (written in full by the library)
-        st = book()
-        _lib.check(_lib.lib().cf_mark_donor_coalitions(self._handle, C.byref(bs), C.byref(opts), words.ctypes.data, len(words), logits.data_ptr(), st),
-                   "cf_mark_donor_coalitions")
-        return logits
+        return self._mark_run_coalitions("cf_mark_donor_coalitions", bs, opts, mark_coalition_words(keep, opts.n_players, who), book)
 
     @torch.no_grad()
     def mark_donor_shapley(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
@@ -1074,17 +1103,7 @@ class ChromoformerBase(nn.Module):
         who = "mark_donor_shapley"
         bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
         opts, _alive, names = self._mark_donor_opts(who, donor, players, bs.B)
-        P = opts.n_players
-        n = 1 << P
-        rows = torch.empty(bs.B, n, self.n_out, device=self._device)      # (both written in full by the library)
-        phi = torch.empty(bs.B, P, self.n_out, device=self._device)
-        st = book()
-        _lib.check(_lib.lib().cf_mark_donor_shapley(self._handle, C.byref(bs), C.byref(opts), phi.data_ptr(), rows.data_ptr(), st), "cf_mark_donor_shapley")
-        info = {"logits": rows[:, n - 1].clone(), "donor": rows[:, 0].clone(), "players": names}
-        info["delta"] = phi.sum(1) - (info["logits"] - info["donor"])
-        if return_coalitions:
-            info["coalitions"] = rows
-        return phi, info
+        return self._mark_run_shapley("cf_mark_donor_shapley", bs, opts, names, "donor", book, return_coalitions)
 
     @torch.no_grad()
     def mark_donor_epistasis(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
@@ -1095,12 +1114,7 @@ class ChromoformerBase(nn.Module):
         who = "mark_donor_epistasis"
         bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
         opts, _alive, names = self._mark_donor_opts(who, donor, players, bs.B)
-        P = opts.n_players
-        rows = torch.empty(bs.B, 1 + P + P * (P - 1) // 2, self.n_out, device=self._device)      # (both written in full by the library)
-        eps = torch.empty(bs.B, P, P, self.n_out, device=self._device)
-        st = book()
-        _lib.check(_lib.lib().cf_mark_donor_epistasis(self._handle, C.byref(bs), C.byref(opts), eps.data_ptr(), rows.data_ptr(), st), "cf_mark_donor_epistasis")
-        return eps, {"logits": rows[:, 0].clone(), "single": rows[:, 1:1 + P].clone(), "players": names}
+        return self._mark_run_epistasis("cf_mark_donor_epistasis", bs, opts, names, book)
 
     def mark_donor_shapley_dataset(self, dataset, donor_dataset, genes=None, players="marks", epistasis=False, bsz=None, store=None, donor_store=None):
         """mark_donor_shapley (and optionally mark_donor_epistasis) over the genes of two ChromoformerDatasets, the gene's cell type
@@ -1136,12 +1150,7 @@ class ChromoformerBase(nn.Module):
             raise ValueError("mark_coalitions_wide: keep is required: the coalitions (bit p set: player p present)")
         bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
         opts, _alive, _names = self._mark_wide_opts(who, players, scale, donor, bs.B)
-        words = mark_wide_words(keep, opts.n_players, who)
-        logits = torch.empty(bs.B, len(words), self.n_out, device=self._device)      # (written in full by the library)
-        st = book()
-        _lib.check(_lib.lib().cf_mark_coalitions_wide(self._handle, C.byref(bs), C.byref(opts), words.ctypes.data, len(words), logits.data_ptr(), st),
-                   "cf_mark_coalitions_wide")
-        return logits
+        return self._mark_run_coalitions("cf_mark_coalitions_wide", bs, opts, mark_wide_words(keep, opts.n_players, who), book)
 
     @torch.no_grad()
     def mark_shapley_sampled(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
@@ -1166,31 +1175,11 @@ class ChromoformerBase(nn.Module):
         The orders are attribution.shapley_permutations(P, n_perm, seed), or `permutations` (an integer array [n_perm, P], each row a
         permutation; stderr then still assumes independent orders).  players, scale and donor as in mark_coalitions_wide.  The packed
         forms of the first argument and the effect on a pending backward() are those of mark_coalitions."""
-        from .attribution import shapley_permutations
         who = "mark_shapley_sampled"
         bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
         opts, _alive, names = self._mark_wide_opts(who, players, scale, donor, bs.B)
-        P = opts.n_players
-        if permutations is None:
-            perms = shapley_permutations(P, n_perm, seed)
-        else:
-            given = np.asarray(permutations.cpu() if hasattr(permutations, "cpu") else permutations)
-            if given.ndim != 2 or given.shape[0] < 1 or given.shape[1] != P or given.dtype.kind not in "iu" or given.min() < 0 or given.max() >= P:
-                raise ValueError("%s: permutations must be an integer array [n_perm >= 1, P = %d] with entries in [0, P)" % (who, P))
-            perms = np.ascontiguousarray(given, dtype=np.uint8)
-        n = len(perms)
-        R = 2 + n * (P - 1)
-        rows = torch.empty(bs.B, R, self.n_out, device=self._device)      # (all three written in full by the library)
-        phi = torch.empty(bs.B, P, self.n_out, device=self._device)
-        se = torch.empty(bs.B, P, self.n_out, device=self._device)
-        st = book()
-        _lib.check(_lib.lib().cf_mark_shapley_sampled(self._handle, C.byref(bs), C.byref(opts), perms.ctypes.data, n, phi.data_ptr(), se.data_ptr(),
-                                                      rows.data_ptr(), st), "cf_mark_shapley_sampled")
-        info = {"logits": rows[:, 1].clone(), "absent": rows[:, 0].clone(), "stderr": se, "names": names, "permutations": perms}
-        info["delta"] = phi.sum(1) - (info["logits"] - info["absent"])
-        if return_rows:
-            info["rows"] = rows
-        return phi, info
+        perms = self._permutations(who, opts.n_players, n_perm, seed, permutations)
+        return self._mark_run_sampled("cf_mark_shapley_sampled", bs, opts, names, perms, book, return_rows)
 
     def mark_shapley_sampled_dataset(self, dataset, donor_dataset=None, genes=None, players="cells", n_perm=64, seed=0, scale=0.0, bsz=None,
                                      store=None, donor_store=None):
@@ -1234,12 +1223,7 @@ class ChromoformerBase(nn.Module):
             raise ValueError("mark_window_coalitions: keep is required: the coalitions (bit p set: player p present)")
         bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
         opts, _alive, _names = self._mark_window_opts(who, players, width, scale, donor, flip, bs.B)
-        words = mark_wide_words(keep, opts.n_players, who)
-        logits = torch.empty(bs.B, len(words), self.n_out, device=self._device)      # (written in full by the library)
-        st = book()
-        _lib.check(_lib.lib().cf_mark_window_coalitions(self._handle, C.byref(bs), C.byref(opts), words.ctypes.data, len(words), logits.data_ptr(), st),
-                   "cf_mark_window_coalitions")
-        return logits
+        return self._mark_run_coalitions("cf_mark_window_coalitions", bs, opts, mark_wide_words(keep, opts.n_players, who), book)
 
     @torch.no_grad()
     def mark_window_shapley(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
@@ -1263,17 +1247,7 @@ class ChromoformerBase(nn.Module):
         P = opts.n_players
         if P > 16:
             raise ValueError("%s: %d players; the exact game takes 1..16: choose a larger width or mark_window_shapley_sampled" % (who, P))
-        n = 1 << P
-        rows = torch.empty(bs.B, n, self.n_out, device=self._device)      # (both written in full by the library)
-        phi = torch.empty(bs.B, P, self.n_out, device=self._device)
-        st = book()
-        _lib.check(_lib.lib().cf_mark_window_shapley(self._handle, C.byref(bs), C.byref(opts), phi.data_ptr(), rows.data_ptr(), st), "cf_mark_window_shapley")
-        absent = "erased" if donor is None else "donor"
-        info = {"logits": rows[:, n - 1].clone(), absent: rows[:, 0].clone(), "players": names}
-        info["delta"] = phi.sum(1) - (info["logits"] - info[absent])
-        if return_coalitions:
-            info["coalitions"] = rows
-        return phi, info
+        return self._mark_run_shapley("cf_mark_window_shapley", bs, opts, names, "erased" if donor is None else "donor", book, return_coalitions)
 
     @torch.no_grad()
     def mark_window_shapley_sampled(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
@@ -1283,31 +1257,11 @@ class ChromoformerBase(nn.Module):
         the row layout and the estimator of mark_shapley_sampled: which mark in which stretch?  players, width, scale, donor and flip
         as in mark_window_coalitions; n_perm, seed and permutations as in mark_shapley_sampled.  A null player (a window past the
         region's real bins, a dummy slot) has phi and stderr exactly 0."""
-        from .attribution import shapley_permutations
         who = "mark_window_shapley_sampled"
         bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
         opts, _alive, names = self._mark_window_opts(who, players, width, scale, donor, flip, bs.B)
-        P = opts.n_players
-        if permutations is None:
-            perms = shapley_permutations(P, n_perm, seed)
-        else:
-            given = np.asarray(permutations.cpu() if hasattr(permutations, "cpu") else permutations)
-            if given.ndim != 2 or given.shape[0] < 1 or given.shape[1] != P or given.dtype.kind not in "iu" or given.min() < 0 or given.max() >= P:
-                raise ValueError("%s: permutations must be an integer array [n_perm >= 1, P = %d] with entries in [0, P)" % (who, P))
-            perms = np.ascontiguousarray(given, dtype=np.uint8)
-        n = len(perms)
-        R = 2 + n * (P - 1)
-        rows = torch.empty(bs.B, R, self.n_out, device=self._device)      # (all three written in full by the library)
-        phi = torch.empty(bs.B, P, self.n_out, device=self._device)
-        se = torch.empty(bs.B, P, self.n_out, device=self._device)
-        st = book()
-        _lib.check(_lib.lib().cf_mark_window_shapley_sampled(self._handle, C.byref(bs), C.byref(opts), perms.ctypes.data, n, phi.data_ptr(),
-                                                             se.data_ptr(), rows.data_ptr(), st), "cf_mark_window_shapley_sampled")
-        info = {"logits": rows[:, 1].clone(), "absent": rows[:, 0].clone(), "stderr": se, "names": names, "permutations": perms}
-        info["delta"] = phi.sum(1) - (info["logits"] - info["absent"])
-        if return_rows:
-            info["rows"] = rows
-        return phi, info
+        perms = self._permutations(who, opts.n_players, n_perm, seed, permutations)
+        return self._mark_run_sampled("cf_mark_window_shapley_sampled", bs, opts, names, perms, book, return_rows)
 
     def mark_window_shapley_dataset(self, dataset, donor_dataset=None, genes=None, players="promoter", width=1, n_perm=64, seed=0, scale=0.0,
                                     bsz=None, store=None, donor_store=None):
@@ -1317,9 +1271,8 @@ class ChromoformerBase(nn.Module):
         return mark_window_shapley(self, dataset, donor_dataset, genes=genes, players=players, width=width, n_perm=n_perm, seed=seed,
                                    scale=scale, bsz=bsz, store=store, donor_store=donor_store)
 
-    def _mark_fine_opts(self, who, B, n_coal, region, players, width, n_windows, start, lengths, scale, donor, flip, return_feats):
-        """The options of the fine window game for a batch of B genes and n_coal(P) rows per gene -> (cf_mark_fine_opts, what it points
-        to, names, feats or None)."""
+    def _mark_fine_opts(self, who, B, region, players, width, n_windows, start, lengths, scale, donor, flip):
+        """The options of the fine window game for a batch of B genes -> (P, cf_mark_fine_opts, what it points to, names)."""
         from .attribution import fine_window_players
         Lf = self.n_bins[min(range(len(self.binsizes)), key=lambda r: self.binsizes[r])]
         start = np.asarray(start, dtype=np.int64).reshape(-1)
@@ -1348,14 +1301,16 @@ class ChromoformerBase(nn.Module):
         flip = self._scan_flip(who, flip, B)
         if flip is not None:
             opts.flip = flip.data_ptr()
-        feats = None
-        if return_feats:
-            feats = {}
-            for r, b in enumerate(self.binsizes):
-                t = feats[b] = torch.empty(B, n_coal(len(marks)), self.n_bins[r], self.n_feats, device=self._device)      # (written in full by the library)
-                opts.feats_out[r] = t.data_ptr()
         alive = (marks, lo, hi, start, lengths, flip) + (self._donor_feats(who, donor, B, opts) if donor is not None else ())
-        return opts, alive, names, feats
+        return len(marks), opts, alive, names
+
+    def _fine_feats(self, opts, B, rows):
+        """feats_out of a fine game of `rows` rows per gene, attached to its options -> {binsize: [B, rows, n_bins, n_feats]}."""
+        feats = {}
+        for r, b in enumerate(self.binsizes):
+            t = feats[b] = torch.empty(B, rows, self.n_bins[r], self.n_feats, device=self._device)      # (written in full by the library)
+            opts.feats_out[r] = t.data_ptr()
+        return feats
 
     @torch.no_grad()
     def mark_fine_window_coalitions(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
@@ -1379,19 +1334,10 @@ class ChromoformerBase(nn.Module):
         if keep is None:
             raise ValueError("mark_fine_window_coalitions: keep is required: the coalitions (bit p set: player p present)")
         bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
-        words = []
-
-        def n_coal(P):
-            words.append(mark_wide_words(keep, P, who))
-            return len(words[0])
-
-        opts, _alive, _names, feats = self._mark_fine_opts(who, bs.B, n_coal, region, players, width, n_windows, start, lengths, scale, donor, flip,
-                                                           return_feats)
-        words = words[0] if words else mark_wide_words(keep, opts.n_players, who)
-        logits = torch.empty(bs.B, len(words), self.n_out, device=self._device)      # (written in full by the library)
-        st = book()
-        _lib.check(_lib.lib().cf_mark_fine_coalitions(self._handle, C.byref(bs), C.byref(opts), words.ctypes.data, len(words), logits.data_ptr(), st),
-                   "cf_mark_fine_coalitions")
+        P, opts, _alive, _names = self._mark_fine_opts(who, bs.B, region, players, width, n_windows, start, lengths, scale, donor, flip)
+        words = mark_wide_words(keep, P, who)
+        feats = self._fine_feats(opts, bs.B, len(words)) if return_feats else None
+        logits = self._mark_run_coalitions("cf_mark_fine_coalitions", bs, opts, words, book)
         return (logits, feats) if return_feats else logits
 
     @torch.no_grad()
@@ -1405,25 +1351,11 @@ class ChromoformerBase(nn.Module):
         inside the window) has phi exactly 0."""
         who = "mark_fine_window_shapley"
         bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
-
-        def n_coal(P):
-            if P > 16:
-                raise ValueError("%s: %d players; the exact game takes 1..16: choose a larger width or mark_fine_window_shapley_sampled" % (who, P))
-            return 1 << P
-
-        opts, _alive, names, feats = self._mark_fine_opts(who, bs.B, n_coal, region, players, width, n_windows, start, lengths, scale, donor, flip,
-                                                          return_feats)
-        P = opts.n_players
-        n = n_coal(P)
-        rows = torch.empty(bs.B, n, self.n_out, device=self._device)      # (both written in full by the library)
-        phi = torch.empty(bs.B, P, self.n_out, device=self._device)
-        st = book()
-        _lib.check(_lib.lib().cf_mark_fine_shapley(self._handle, C.byref(bs), C.byref(opts), phi.data_ptr(), rows.data_ptr(), st), "cf_mark_fine_shapley")
-        absent = "erased" if donor is None else "donor"
-        info = {"logits": rows[:, n - 1].clone(), absent: rows[:, 0].clone(), "players": names}
-        info["delta"] = phi.sum(1) - (info["logits"] - info[absent])
-        if return_coalitions:
-            info["coalitions"] = rows
+        P, opts, _alive, names = self._mark_fine_opts(who, bs.B, region, players, width, n_windows, start, lengths, scale, donor, flip)
+        if P > 16:
+            raise ValueError("%s: %d players; the exact game takes 1..16: choose a larger width or mark_fine_window_shapley_sampled" % (who, P))
+        feats = self._fine_feats(opts, bs.B, 1 << P) if return_feats else None
+        phi, info = self._mark_run_shapley("cf_mark_fine_shapley", bs, opts, names, "erased" if donor is None else "donor", book, return_coalitions)
         if return_feats:
             info["feats"] = feats
         return phi, info
@@ -1437,38 +1369,12 @@ class ChromoformerBase(nn.Module):
         keys, the row layout and the estimator of mark_shapley_sampled (info["feats"] with return_feats): which mark in which 200 bp?
         region, players, width, n_windows, start, lengths, scale, donor and flip as in mark_fine_window_coalitions; n_perm, seed and
         permutations as in mark_shapley_sampled.  A null player has phi and stderr exactly 0."""
-        from .attribution import shapley_permutations
         who = "mark_fine_window_shapley_sampled"
         bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
-        got = {}
-
-        def n_coal(P):
-            if "perms" not in got:
-                if permutations is None:
-                    got["perms"] = shapley_permutations(P, n_perm, seed)
-                else:
-                    given = np.asarray(permutations.cpu() if hasattr(permutations, "cpu") else permutations)
-                    if given.ndim != 2 or given.shape[0] < 1 or given.shape[1] != P or given.dtype.kind not in "iu" or given.min() < 0 or given.max() >= P:
-                        raise ValueError("%s: permutations must be an integer array [n_perm >= 1, P = %d] with entries in [0, P)" % (who, P))
-                    got["perms"] = np.ascontiguousarray(given, dtype=np.uint8)
-            return 2 + len(got["perms"]) * (P - 1)
-
-        opts, _alive, names, feats = self._mark_fine_opts(who, bs.B, n_coal, region, players, width, n_windows, start, lengths, scale, donor, flip,
-                                                          return_feats)
-        P = opts.n_players
-        R = n_coal(P)
-        perms = got["perms"]
-        n = len(perms)
-        rows = torch.empty(bs.B, R, self.n_out, device=self._device)      # (all three written in full by the library)
-        phi = torch.empty(bs.B, P, self.n_out, device=self._device)
-        se = torch.empty(bs.B, P, self.n_out, device=self._device)
-        st = book()
-        _lib.check(_lib.lib().cf_mark_fine_shapley_sampled(self._handle, C.byref(bs), C.byref(opts), perms.ctypes.data, n, phi.data_ptr(),
-                                                           se.data_ptr(), rows.data_ptr(), st), "cf_mark_fine_shapley_sampled")
-        info = {"logits": rows[:, 1].clone(), "absent": rows[:, 0].clone(), "stderr": se, "names": names, "permutations": perms}
-        info["delta"] = phi.sum(1) - (info["logits"] - info["absent"])
-        if return_rows:
-            info["rows"] = rows
+        P, opts, _alive, names = self._mark_fine_opts(who, bs.B, region, players, width, n_windows, start, lengths, scale, donor, flip)
+        perms = self._permutations(who, P, n_perm, seed, permutations)
+        feats = self._fine_feats(opts, bs.B, 2 + len(perms) * (P - 1)) if return_feats else None
+        phi, info = self._mark_run_sampled("cf_mark_fine_shapley_sampled", bs, opts, names, perms, book, return_rows)
         if return_feats:
             info["feats"] = feats
         return phi, info

@@ -213,7 +213,7 @@ def write_mark_donor_values(model, store, donor_store, bsz, gene_ids, shapley_ou
     masks and frequencies; phi sums to logits - donor) and donor_prediction [n] (the plain forward of the donor's own batch);
     epistasis_out: a float32 .npy [n, P, P].  Per batch: one gather per store, one model.mark_donor_shapley and / or one
     model.mark_donor_epistasis, one plain forward of the donor's batch."""
-    from .attribution import mark_players
+    from .attribution import _BATCH_KEYS, _donor_pair, mark_players
     n = len(store)
     if len(donor_store) != n:
         raise ValueError("write_mark_donor_values: the donor store holds %d genes, the store %d" % (len(donor_store), n))
@@ -221,20 +221,19 @@ def write_mark_donor_values(model, store, donor_store, bsz, gene_ids, shapley_ou
     P, t = len(names), 0 if regression else 1
     phi, logits, donor, pred = torch.empty(n, P), torch.empty(n), torch.empty(n), torch.empty(n)
     eps = np.lib.format.open_memmap(epistasis_out, mode="w+", dtype=np.float32, shape=(n, P, P)) if epistasis_out else None
-    keys = ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq")
     for lo in range(0, n, bsz):
         B = min(bsz, n - lo)
         idx = list(range(lo, lo + B))
         d, dd = store.batch(idx), donor_store.batch(idx)
-        args = tuple(d[k] for k in keys)
-        feats = ({b: x.contiguous() for b, x in dd["promoter_feats"].items()}, {b: x.contiguous() for b, x in dd["pcre_feats"].items()})
+        args = tuple(d[k] for k in _BATCH_KEYS)
+        feats = _donor_pair(dd)
         if shapley_out:
             p, info = model.mark_donor_shapley(*args, donor=feats, players=players)
             phi[lo:lo + B] = p[..., t].cpu()
             logits[lo:lo + B] = info["logits"][:, t].cpu()
             donor[lo:lo + B] = info["donor"][:, t].cpu()
             with torch.no_grad():
-                pred[lo:lo + B] = model(*(dd[k] for k in keys))[:, t].cpu()
+                pred[lo:lo + B] = model(*(dd[k] for k in _BATCH_KEYS))[:, t].cpu()
         if eps is not None:
             eps[lo:lo + B] = model.mark_donor_epistasis(*args, donor=feats, players=players)[0][..., t].cpu().numpy()
     if shapley_out:
@@ -252,7 +251,7 @@ def write_mark_sampled_values(model, store, donor_store, bsz, gene_ids, path, re
     phi over the orders: the sampling error is reported, not bounded), logits [n] and absent [n] (every player absent; phi sums to
     their difference).  donor_store None: an absent player's raw signal is scaled by `scale`; else a store of the same genes in the
     same order in the donor cell type, whose signal it takes.  Per batch: one gather per store and one model.mark_shapley_sampled."""
-    from .attribution import mark_players_wide, shapley_permutations
+    from .attribution import _BATCH_KEYS, _donor_pair, mark_players_wide, shapley_permutations
     n = len(store)
     if donor_store is not None and len(donor_store) != n:
         raise ValueError("write_mark_sampled_values: the donor store holds %d genes, the store %d" % (len(donor_store), n))
@@ -260,7 +259,6 @@ def write_mark_sampled_values(model, store, donor_store, bsz, gene_ids, path, re
     P, t = len(names), 0 if regression else 1
     perms = shapley_permutations(P, n_perm, seed)
     phi, se, logits, absent = torch.empty(n, P), torch.empty(n, P), torch.empty(n), torch.empty(n)
-    keys = ("promoter_feats", "promoter_pad_masks", "pcre_feats", "pcre_pad_masks", "interaction_masks", "interaction_freq")
     for lo in range(0, n, bsz):
         B = min(bsz, n - lo)
         idx = list(range(lo, lo + B))
@@ -268,8 +266,8 @@ def write_mark_sampled_values(model, store, donor_store, bsz, gene_ids, path, re
         feats = None
         if donor_store is not None:
             dd = donor_store.batch(idx)
-            feats = ({b: x.contiguous() for b, x in dd["promoter_feats"].items()}, {b: x.contiguous() for b, x in dd["pcre_feats"].items()})
-        p, info = model.mark_shapley_sampled(*(d[k] for k in keys), players=players, permutations=perms, scale=scale, donor=feats)
+            feats = _donor_pair(dd)
+        p, info = model.mark_shapley_sampled(*(d[k] for k in _BATCH_KEYS), players=players, permutations=perms, scale=scale, donor=feats)
         phi[lo:lo + B] = p[..., t].cpu()
         se[lo:lo + B] = info["stderr"][..., t].cpu()
         logits[lo:lo + B] = info["logits"][:, t].cpu()
