@@ -9,8 +9,8 @@
 #include "cf_coalition.h"
 #include "cf_ig.h"
 #include "cf_scan.h"
-#include "cf_scan_fine.h"
 #include "cf_marks.h"
+#include "cf_scan_fine.h"
 #include "cf_marks_wide.h"
 #include "cf_mark_windows.h"
 #include "cf_mark_fine.h"

@@ -8,7 +8,7 @@
 // Histone-mark coalitions (cf_marks.h).  The families share everything but the options struct and the expand kernel: MarkGame is what
 // the options struct says, checked.  `kind` names the table layout and, with `donor`, the kernel:
 //   narrow  [words | marks_p | regions_p], one word per coalition                 k_mark_expand / k_mark_donor_expand
-//   wide    [n_coal * kw words | marks_p | regions_p | extra]                       k_mark_wide_expand / k_mark_wide_donor_expand
+//   wide    [n_coal * kw words | marks_p | regions_p | extra]                       the same pair: narrow is the case kw = 1
 //   window  [words | marks_p | regions_p | lo_p | hi_p | extra]                     k_mark_window_expand / k_mark_window_donor_expand
 //   fine    [words | marks_p | lo_p | hi_p | start[B] | cnt_last[B] | extra]        k_mark_fine_expand / k_mark_fine_donor_expand
 enum MarkKind { kMarkNarrow, kMarkWide, kMarkWindow, kMarkFine };
@@ -242,7 +242,6 @@ static int mark_rows(cf_handle* h, const cf_batch* bt, const MarkGame& g, int n_
     memset(&da, 0, sizeof da);
     da.m = ea;
     donor_feats(da.pf_don, da.cf_don);
-    if (g.kind == kMarkWide) return run(k_mark_wide_donor_expand, "k_mark_wide_donor_expand", k_mark_wide_expand, "k_mark_wide_expand", da, da.m, da.m);
     return run(k_mark_donor_expand, "k_mark_donor_expand", k_mark_expand, "k_mark_expand", da, da.m, da.m);
 }
 

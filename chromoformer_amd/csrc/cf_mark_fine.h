@@ -31,8 +31,8 @@
 //                  (the thread walks the <= R_r children: gone_f from LDS, the finest features from global memory), else its bits.
 //                  The optional feats_out[r] ([B, n_coal, n_bins[r], F], the region only) is written in the same pass.
 // No atomics, no scratch, deterministic.  5,668 bytes of LDS (gone_f 2,048, some / all 2,048, staged words 1,552, extents and flag
-// 20); 50 / 55 VGPRs (scale / donor rule), no spills (tools/kernel_resources.sh k_mark_fine).  The extent reduction and the float4 walk are repeated here, not shared with
-// cf_mark_windows.h or cf_scan_fine.h: the shipped kernels keep their code.
+// 20); 50 / 55 VGPRs (scale / donor rule), no spills (tools/kernel_resources.sh k_mark_fine).  The extent reduction is win_extent of
+// cf_rows.h; the end of the partial rule is partial_tail of cf_marks.h, the very text scan_fine_partial runs.
 #pragma once
 
 namespace cf {
@@ -40,7 +40,7 @@ namespace cf {
 constexpr int kFineMaxL = 512;         // finest bins per region the gone_f table holds
 
 struct MarkFineArgs {
-    MarkExpandArgs m;                  // as for k_mark_wide_expand; m.players: device [3 P + 2 B]: marks_p, lo_p, hi_p, start[B], cnt_last[B]
+    MarkExpandArgs m;                  // as for k_mark_expand; m.players: device [3 P + 2 B]: marks_p, lo_p, hi_p, start[B], cnt_last[B]
     const uint8_t* rm_in[kMaxRes];     // the region's centre pad-mask rows: rm_in[r] + b * rm_stride[r]
     long long rm_stride[kMaxRes];
     float* feats_out[kMaxRes];         // optional [B, n_coal, L, F]: the edited region
@@ -77,37 +77,17 @@ struct FineGeom {
     float s;
 };
 
-// first unmasked byte and one past the last of a mask row of L bytes, by one wave (lo = L, hi = 0: all masked); every lane gets the result
-__device__ __forceinline__ void fine_extent(const uint8_t* __restrict__ m, int L, int lane, int& lo, int& hi) {
-    int a = L, b = 0;
-    if ((L & 3) == 0 && (reinterpret_cast<uintptr_t>(m) & 3) == 0) {
-        const unsigned* __restrict__ m4 = reinterpret_cast<const unsigned*>(m);
-        for (int k = lane; k < L / 4; k += 64) {
-            const unsigned w = m4[k];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (!((w >> (8 * j)) & 0xFFu)) a = min(a, 4 * k + j), b = max(b, 4 * k + j + 1);
-        }
-    } else {
-        for (int k = lane; k < L; k += 64)
-            if (!m[k]) a = min(a, k), b = max(b, k + 1);
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) a = min(a, __shfl_xor(a, o, 64)), b = max(b, __shfl_xor(b, o, 64));
-    lo = a, hi = b;
-}
-
 // phases 1 to 3: t filled for chunk row gv = (gene b, coalition gv - b n_coal) at resolution r; ends with a barrier
 __device__ __forceinline__ void fine_table(const MarkFineArgs& fa, FineTable& t, int r, int b, long long gv) {
     const MarkExpandArgs& a = fa.m;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, P = a.P, rf = fa.rf, L = a.rows.L[r], Lf = a.rows.L[rf];
     if (wave == 0) {
         int lo, hi;
-        fine_extent(fa.rm_in[rf] + (size_t)b * fa.rm_stride[rf], Lf, lane, lo, hi);
+        win_extent(fa.rm_in[rf] + (size_t)b * fa.rm_stride[rf], Lf, lane, lo, hi);
         if (lane == 0) t.ext[2] = lo, t.ext[3] = hi > lo ? hi - lo : 0, t.any = 0u;
     } else if (wave == 1) {
         int lo, hi;
-        fine_extent(fa.rm_in[r] + (size_t)b * fa.rm_stride[r], L, lane, lo, hi);
+        win_extent(fa.rm_in[r] + (size_t)b * fa.rm_stride[r], L, lane, lo, hi);
         if (lane == 0) t.ext[0] = lo, t.ext[1] = hi > lo ? hi - lo : 0;
     }
     const int kw = (P + 31) >> 5;
@@ -158,10 +138,7 @@ __device__ __forceinline__ float fine_partial(float uj, const FineTable& t, cons
         }
     }
     if (DONOR && same) return uj;
-    const double cj = (double)((K1 - K0) * g.bf - (K1 == g.nf ? g.bf - g.cl : 0));
-    const double tt = DONOR ? S : ((double)g.s - 1.0) * S;
-    const float m = (float)((double)expm1f(uj) + tt / cj);
-    return log1pf(m);
+    return partial_tail(uj, DONOR ? S : ((double)g.s - 1.0) * S, K0, K1, g.nf, g.bf, g.cl);
 }
 
 // element e of the region ([L, F], e = row * F + f): x its value, d the donor's (donor rule)
@@ -236,6 +213,8 @@ __device__ __forceinline__ void fine_copy(const float* __restrict__ src, const f
 template <bool DONOR>
 __device__ __forceinline__ void fine_expand(const MarkFineArgs& fa, const float* const* pf_don, const float* const* cf_don, FineTable& t) {
     const MarkExpandArgs& a = fa.m;
+    // (the row and the closing lines are written out, not mark_row / rows_masks_freq: with the helpers this kernel measured 0.5 us of its
+    // 39.8 us slower, profiles/r22_mark_kernels_shared.txt)
     const int i = blockIdx.x, r = blockIdx.y, rf = fa.rf;
     const long long gv = a.g0 + i;
     const int b = (int)(gv / a.n_coal);

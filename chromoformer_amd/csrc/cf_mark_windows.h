@@ -16,7 +16,7 @@
 // holds whole finer bins, and binning is linear per mark: either rule is exact in raw-signal space, as in cf_scan.h.  A window with
 // lo_p >= n_c changes nothing (a dummy slot, a short pCRE, a narrowed promoter): such a player is a null player.
 //   k_mark_window_expand         the grid (chunk row x resolution x kMarkSlices), the 256 threads and the slice-0 mask and frequency
-//   k_mark_window_donor_expand   copies of k_mark_wide_expand, in three phases:
+//   k_mark_window_donor_expand   copies of k_mark_expand (one body, win_expand<DONOR>), in three phases:
 //     1  extents   (q_r, n_r, n_c) of every region into LDS: wave w takes regions w, w + 4, ..., each with two shuffle reductions
 //                  over mask rows read four bytes per load -- no block-wide barrier per region; the 4 P player words and the row's
 //                  kw coalition words are staged in LDS on the way
@@ -26,9 +26,9 @@
 //                  float4 copy (the donor is not loaded); in a touched region every element takes the word of ITS row -- a float4
 //                  spans up to two rows and two regions when F is no multiple of 4.  A segment whose length is no multiple of 4
 //                  floats (or F < 4) goes element by element.
-// No atomics, no scratch, 6,688 bytes of LDS (extents 204, table 4,352, flags 68, staged words 2,064); 48 / 36 VGPRs (scale / donor
-// rule), 8 waves per SIMD.  The gone lines and the float4 walk are repeated here, not shared with cf_marks.h: the
-// shipped kernels keep their code.
+// No atomics, no scratch, 6,688 bytes of LDS (extents 204, table 4,352, flags 68, staged words 2,064); 46 / 36 VGPRs (scale / donor
+// rule), 8 waves per SIMD.  The float4 walk is its own, not mark_copy's: an element's word comes from a table
+// lookup per row here, from one word per region there.
 #pragma once
 
 namespace cf {
@@ -37,7 +37,7 @@ constexpr int kWinMaxW = 64;           // coarse bins per region the gone table 
 constexpr int kWinMaxT = kCoalMaxS + 1;
 
 struct MarkWindowArgs {
-    MarkExpandArgs m;                  // as for k_mark_wide_expand; m.players: device [4 P]: marks_p, regions_p, lo_p, hi_p
+    MarkExpandArgs m;                  // as for k_mark_expand; m.players: device [4 P]: marks_p, regions_p, lo_p, hi_p
     const uint8_t* pmc[kMaxRes];       // the promoter's centre pad-mask rows: pmc[r] + b * m.rows.pm_stride[r]
     const uint8_t* flip;               // device [B] or nullptr: the promoter of gene b is stored mirrored
     int W, rc;                         // n_bins of the coarsest resolution, its index
@@ -56,26 +56,6 @@ struct WinTable {
     unsigned pl[4 * kMarkWideMaxP];        // the 4 P player words and
     unsigned kept[kMarkWideMaxP / 32];     // the row's coalition words: staged once, walked by T W threads
 };
-
-// first unmasked byte and one past the last of a mask row of L bytes, by one wave (lo = L, hi = 0: all masked); every lane gets the result
-__device__ __forceinline__ void win_extent(const uint8_t* __restrict__ m, int L, int lane, int& lo, int& hi) {
-    int a = L, b = 0;
-    if ((L & 3) == 0 && (reinterpret_cast<uintptr_t>(m) & 3) == 0) {      // four mask bytes per load: L = 400 in two rounds, not seven
-        const unsigned* __restrict__ m4 = reinterpret_cast<const unsigned*>(m);
-        for (int k = lane; k < L / 4; k += 64) {
-            const unsigned w = m4[k];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (!((w >> (8 * j)) & 0xFFu)) a = min(a, 4 * k + j), b = max(b, 4 * k + j + 1);
-        }
-    } else {
-        for (int k = lane; k < L; k += 64)
-            if (!m[k]) a = min(a, k), b = max(b, k + 1);
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) a = min(a, __shfl_xor(a, o, 64)), b = max(b, __shfl_xor(b, o, 64));
-    lo = a, hi = b;
-}
 
 // phases 1 and 2: t filled for chunk row gv = (gene b, coalition gv - b n_coal) at resolution r; ends with a barrier
 __device__ __forceinline__ void win_table(const MarkWindowArgs& wa, WinTable& t, int r, int b, long long gv) {
@@ -175,39 +155,28 @@ __device__ __forceinline__ void win_copy(const float* __restrict__ src, const fl
     }
 }
 
+template <bool DONOR>
+__device__ __forceinline__ void win_expand(const MarkWindowArgs& wa, const float* const* pf_don, const float* const* cf_don, WinTable& t) {
+    const MarkExpandArgs& a = wa.m;
+    const MarkRow w = mark_row(a);
+    const int r = w.r, b = w.b, i = w.i, L = a.rows.L[r], S = a.rows.S, F = a.F, LF = L * F;
+    win_table(wa, t, r, b, w.gv);
+    const bool fl = wa.flip && wa.flip[b];
+    win_copy<DONOR>(a.pf_in[r] + (size_t)b * LF, DONOR ? pf_don[r] + (size_t)b * LF : nullptr, a.pf_out[r] + (size_t)i * LF, LF, L, F, 0, t, wa.W, fl,
+                    a.scale);
+    win_copy<DONOR>(a.cf_in[r] + (size_t)b * S * LF, DONOR ? cf_don[r] + (size_t)b * S * LF : nullptr, a.cf_out[r] + (size_t)i * S * LF, S * LF, L, F, 1,
+                    t, wa.W, fl, a.scale);
+    if (blockIdx.z == 0) rows_masks_freq(a.rows, a.freq_in, a.freq_out, r, b, i);
+}
+
 __global__ __launch_bounds__(kIgxThreads) void k_mark_window_expand(MarkWindowArgs wa) {
     __shared__ WinTable t;
-    const MarkExpandArgs& a = wa.m;
-    const int i = blockIdx.x, r = blockIdx.y;
-    const long long gv = a.g0 + i;
-    const int b = (int)(gv / a.n_coal);
-    const int L = a.rows.L[r], S = a.rows.S, F = a.F, LF = L * F;
-    win_table(wa, t, r, b, gv);
-    const bool fl = wa.flip && wa.flip[b];
-    win_copy<false>(a.pf_in[r] + (size_t)b * LF, nullptr, a.pf_out[r] + (size_t)i * LF, LF, L, F, 0, t, wa.W, fl, a.scale);
-    win_copy<false>(a.cf_in[r] + (size_t)b * S * LF, nullptr, a.cf_out[r] + (size_t)i * S * LF, S * LF, L, F, 1, t, wa.W, fl, a.scale);
-    if (blockIdx.z) return;
-    rows_pad_masks(a.rows, r, b, i);
-    rows_interaction_mask(a.rows, r, b, i);
-    if (r == 0) rows_copy_tt(a.freq_in, a.freq_out, b, i, a.rows.TT);
+    win_expand<false>(wa, nullptr, nullptr, t);
 }
 
 __global__ __launch_bounds__(kIgxThreads) void k_mark_window_donor_expand(MarkWindowDonorArgs da) {
     __shared__ WinTable t;
-    const MarkWindowArgs& wa = da.w;
-    const MarkExpandArgs& a = wa.m;
-    const int i = blockIdx.x, r = blockIdx.y;
-    const long long gv = a.g0 + i;
-    const int b = (int)(gv / a.n_coal);
-    const int L = a.rows.L[r], S = a.rows.S, F = a.F, LF = L * F;
-    win_table(wa, t, r, b, gv);
-    const bool fl = wa.flip && wa.flip[b];
-    win_copy<true>(a.pf_in[r] + (size_t)b * LF, da.pf_don[r] + (size_t)b * LF, a.pf_out[r] + (size_t)i * LF, LF, L, F, 0, t, wa.W, fl, 0.f);
-    win_copy<true>(a.cf_in[r] + (size_t)b * S * LF, da.cf_don[r] + (size_t)b * S * LF, a.cf_out[r] + (size_t)i * S * LF, S * LF, L, F, 1, t, wa.W, fl, 0.f);
-    if (blockIdx.z) return;
-    rows_pad_masks(a.rows, r, b, i);
-    rows_interaction_mask(a.rows, r, b, i);
-    if (r == 0) rows_copy_tt(a.freq_in, a.freq_out, b, i, a.rows.TT);
+    win_expand<true>(da.w, da.pf_don, da.cf_don, t);
 }
 
 }  // namespace cf

@@ -5,9 +5,8 @@
 // element by element -- with more players than one word holds: "mark f in region rho" is n_feats (i_max + 1) players, 63 on the default
 // model, 119 at i_max = 16.  A coalition over P <= kMarkWideMaxP players is kw = ceil(P / 32) consecutive 32-bit words, bit p % 32 of
 // word p / 32 set = player p PRESENT; row (b, k) reads words [k kw, (k + 1) kw) of the device table.
-//   k_mark_wide_expand         k_mark_expand with gone(rho) formed from the row's kw words: the grid (chunk row x resolution x
-//   k_mark_wide_donor_expand   kMarkSlices), the 68 bytes of LDS, mark_copy / mark_donor_copy and the slice-0 mask and frequency copies
-//                              are the sibling's.  The few gone lines are repeated here, not shared: the shipped kernels keep their code.
+// The rows are built by k_mark_expand / k_mark_donor_expand of cf_marks.h themselves: mark_gone reads the row's kw words, and the narrow
+// game is the case kw = 1.
 // 2^P coalitions cannot be enumerated, so the Shapley values are ESTIMATED from n_perm orders of adding the players (permutations):
 //   rows of gene b   column 0 nobody present, column 1 everybody (both shared by all permutations), column 2 + q (P - 1) + (k - 1) the
 //                    first k players of permutation q, k = 1 .. P - 1: R = 2 + n_perm (P - 1) rows
@@ -24,52 +23,6 @@
 namespace cf {
 
 constexpr int kMarkWideMaxP = 128;     // players of the wide game: four words
-
-// (both kernels take the argument structs of their siblings; kw follows from P)
-__global__ __launch_bounds__(kIgxThreads) void k_mark_wide_expand(MarkExpandArgs a) {
-    __shared__ unsigned gone[kCoalMaxS + 1];      // gone(rho), rho = 0 .. i_max: 68 bytes
-    const int i = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
-    const long long gv = a.g0 + i;
-    const int b = (int)(gv / a.n_coal);
-    const int L = a.rows.L[r], S = a.rows.S, F = a.F, LF = L * F, P = a.P;
-    if (tid <= S) {
-        const unsigned* __restrict__ m = a.words + (gv - (long long)b * a.n_coal) * ((P + 31) >> 5);
-        unsigned g = 0;
-        for (int p = 0; p < P; ++p)
-            if (!((m[p >> 5] >> (p & 31)) & 1u) && ((a.players[P + p] >> tid) & 1u)) g |= a.players[p];
-        gone[tid] = g;
-    }
-    __syncthreads();
-    mark_copy(a.pf_in[r] + (size_t)b * LF, a.pf_out[r] + (size_t)i * LF, LF, LF, F, gone, a.scale);
-    mark_copy(a.cf_in[r] + (size_t)b * S * LF, a.cf_out[r] + (size_t)i * S * LF, S * LF, LF, F, gone + 1, a.scale);
-    if (blockIdx.z) return;
-    rows_pad_masks(a.rows, r, b, i);
-    rows_interaction_mask(a.rows, r, b, i);
-    if (r == 0) rows_copy_tt(a.freq_in, a.freq_out, b, i, a.rows.TT);
-}
-
-__global__ __launch_bounds__(kIgxThreads) void k_mark_wide_donor_expand(MarkDonorArgs da) {
-    __shared__ unsigned gone[kCoalMaxS + 1];      // gone(rho), rho = 0 .. i_max: 68 bytes
-    const MarkExpandArgs& a = da.m;
-    const int i = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
-    const long long gv = a.g0 + i;
-    const int b = (int)(gv / a.n_coal);
-    const int L = a.rows.L[r], S = a.rows.S, F = a.F, LF = L * F, P = a.P;
-    if (tid <= S) {      // (as k_mark_wide_expand)
-        const unsigned* __restrict__ m = a.words + (gv - (long long)b * a.n_coal) * ((P + 31) >> 5);
-        unsigned g = 0;
-        for (int p = 0; p < P; ++p)
-            if (!((m[p >> 5] >> (p & 31)) & 1u) && ((a.players[P + p] >> tid) & 1u)) g |= a.players[p];
-        gone[tid] = g;
-    }
-    __syncthreads();
-    mark_donor_copy(a.pf_in[r] + (size_t)b * LF, da.pf_don[r] + (size_t)b * LF, a.pf_out[r] + (size_t)i * LF, LF, LF, F, gone);
-    mark_donor_copy(a.cf_in[r] + (size_t)b * S * LF, da.cf_don[r] + (size_t)b * S * LF, a.cf_out[r] + (size_t)i * S * LF, S * LF, LF, F, gone + 1);
-    if (blockIdx.z) return;
-    rows_pad_masks(a.rows, r, b, i);
-    rows_interaction_mask(a.rows, r, b, i);
-    if (r == 0) rows_copy_tt(a.freq_in, a.freq_out, b, i, a.rows.TT);
-}
 
 struct PermShapleyArgs {
     const float* v;                          // [B, R, n_out], R = 2 + n_perm (P - 1): the prefix rows

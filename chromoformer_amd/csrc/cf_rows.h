@@ -1,6 +1,8 @@
 // cf_rows.h -- a chunk of rows copied from the caller's batch: what the expand kernels of the attribution entry points share
-// (cf_coalition.h, cf_ig.h, cf_scan.h; included by cf_api.hip in front of them).  Chunk row i is a copy of gene b; blockIdx.y is the
-// resolution r.  Bytes only, kRowThreads threads per workgroup.
+// (cf_coalition.h, cf_ig.h, cf_scan.h, cf_scan_fine.h and the mark games cf_marks.h, cf_mark_windows.h, cf_mark_fine.h; included by
+// cf_api.hip in front of them).  Chunk row i is a copy of gene b; blockIdx.y is the resolution r.  Bytes only, kRowThreads threads per
+// workgroup.  Also here: rows_masks_freq, the three copies that close the mark and scan expand kernels, and win_extent, the real rows of
+// a pad-mask row by one wave (the window and fine games).
 #pragma once
 
 namespace cf {
@@ -38,6 +40,33 @@ __device__ __forceinline__ void rows_interaction_mask(const RowCopyArgs& a, int 
 // out[i] = in[b], [T, T] floats (interaction_freq)
 __device__ __forceinline__ void rows_copy_tt(const float* in, float* out, int b, int i, int TT) {
     for (int k = threadIdx.x; k < TT; k += kRowThreads) out[(size_t)i * TT + k] = in[(size_t)b * TT + k];
+}
+
+// what closes an expand kernel: chunk row i's compact pad-mask rows and interaction mask, at resolution 0 its interaction_freq
+__device__ __forceinline__ void rows_masks_freq(const RowCopyArgs& a, const float* freq_in, float* freq_out, int r, int b, int i) {
+    rows_pad_masks(a, r, b, i);
+    rows_interaction_mask(a, r, b, i);
+    if (r == 0) rows_copy_tt(freq_in, freq_out, b, i, a.TT);
+}
+
+// first unmasked byte and one past the last of a mask row of L bytes, by one wave (lo = L, hi = 0: all masked); every lane gets the result
+__device__ __forceinline__ void win_extent(const uint8_t* __restrict__ m, int L, int lane, int& lo, int& hi) {
+    int a = L, b = 0;
+    if ((L & 3) == 0 && (reinterpret_cast<uintptr_t>(m) & 3) == 0) {      // four mask bytes per load: L = 400 in two rounds, not seven
+        const unsigned* __restrict__ m4 = reinterpret_cast<const unsigned*>(m);
+        for (int k = lane; k < L / 4; k += 64) {
+            const unsigned w = m4[k];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (!((w >> (8 * j)) & 0xFFu)) a = min(a, 4 * k + j), b = max(b, 4 * k + j + 1);
+        }
+    } else {
+        for (int k = lane; k < L; k += 64)
+            if (!m[k]) a = min(a, k), b = max(b, k + 1);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) a = min(a, __shfl_xor(a, o, 64)), b = max(b, __shfl_xor(b, o, 64));
+    lo = a, hi = b;
 }
 
 // x0[i] = stash[b]: the stashed trunk output of gene b into the Regulation input Rx[r][0] of chunk row i, row4 = T * D / 4

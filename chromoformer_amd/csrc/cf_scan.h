@@ -124,9 +124,7 @@ __global__ __launch_bounds__(kIgxThreads) void k_scan_expand(ScanExpandArgs a) {
               prom ? fo : nullptr);
     scan_copy(a.cf_in[r] + (size_t)b * S * LF, a.cf_out[r] + (size_t)i * S * LF, S * LF, off, LF, prom ? 0 : off + p0 * F,
               prom ? 0 : off + p1 * F, bits, F, a.scale, prom ? nullptr : fo);
-    rows_pad_masks(a.rows, r, b, i);
-    rows_interaction_mask(a.rows, r, b, i);
-    if (r == 0) rows_copy_tt(a.freq_in, a.freq_out, b, i, a.rows.TT);
+    rows_masks_freq(a.rows, a.freq_in, a.freq_out, r, b, i);
 }
 
 // Several regions per call (cf_perturbation_scan_regions): the variants of ONE pCRE slot j, slot-packed.  The Pairwise output of a slot

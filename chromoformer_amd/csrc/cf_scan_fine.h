@@ -1,4 +1,5 @@
-// cf_scan_fine.h -- fine-resolution perturbation scan (cf_perturbation_scan_fine; included by cf_api.hip behind cf_scan.h).
+// cf_scan_fine.h -- fine-resolution perturbation scan (cf_perturbation_scan_fine; included by cf_api.hip behind cf_scan.h and cf_marks.h,
+// whose partial_tail ends the third case of the rule below).
 //
 // The scan of cf_scan.h with windows given in bins of the FINEST resolution f (the smallest bin size), so a window may cover a coarser
 // bin only in part.  The perturbation is the scan's: the window's raw samples of a mark set are scaled by s >= 0.  With R_r =
@@ -99,10 +100,7 @@ __device__ __forceinline__ float scan_fine_partial(float uj, const float* __rest
         const double cnt = (double)(k == nf - 1 ? cl : bf);
         S += cnt * (double)expm1f(uf[(size_t)row * F + f]);
     }
-    const double cj = (double)((K1 - K0) * bf - (K1 == nf ? bf - cl : 0));
-    const double t = ((double)s - 1.0) * S;
-    const float m = (float)((double)expm1f(uj) + t / cj);
-    return log1pf(m);
+    return partial_tail(uj, ((double)s - 1.0) * S, K0, K1, nf, bf, cl);
 }
 
 __global__ __launch_bounds__(kIgxThreads) void k_scan_fine_expand(ScanFineExpandArgs a) {
@@ -159,9 +157,7 @@ __global__ __launch_bounds__(kIgxThreads) void k_scan_fine_expand(ScanFineExpand
     // what is not scanned first: the waves without a partly covered value to compute do not wait for those that have one
     if (prom) scan_fine_copy(a.cf_in[r] + (size_t)b * S * LF, a.cf_out[r] + (size_t)i * S * LF, S * LF, 0, 0, 0, 0, 0u, F, a.scale, -1, -1, pv, nullptr);
     else scan_fine_copy(a.pf_in[r] + (size_t)b * LF, a.pf_out[r] + (size_t)i * LF, LF, 0, 0, 0, 0, 0u, F, a.scale, -1, -1, pv, nullptr);
-    rows_pad_masks(a.rows, r, b, i);
-    rows_interaction_mask(a.rows, r, b, i);
-    if (r == 0) rows_copy_tt(a.freq_in, a.freq_out, b, i, a.rows.TT);
+    rows_masks_freq(a.rows, a.freq_in, a.freq_out, r, b, i);
     __syncthreads();      // pv
     if (prom) scan_fine_copy(a.pf_in[r] + (size_t)b * LF, a.pf_out[r] + (size_t)i * LF, LF, 0, LF, p0 * F, p1 * F, bits, F, a.scale, pr0, pr1, pv, fo);
     else scan_fine_copy(a.cf_in[r] + (size_t)b * S * LF, a.cf_out[r] + (size_t)i * S * LF, S * LF, off, LF, off + p0 * F, off + p1 * F, bits, F, a.scale,

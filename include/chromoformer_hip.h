@@ -539,7 +539,7 @@ typedef struct cf_mark_wide_opts {
 /* cf_mark_coalitions_wide: keep is a HOST array of n_coal * kw words, coalition k at [k kw, (k + 1) kw) (read before the call returns);
  * logits [B, n_coal, n_out], gene-major.  The full word is cf_forward(save = 0), bit for bit; with P <= 16 the rows carry the bits of
  * cf_mark_coalitions / cf_mark_donor_coalitions on the same words.  Rows run in chunks of at most max_batch in the chunk buffers of
- * cf_mark_coalitions; per chunk one k_mark_wide_expand (the donor rule: k_mark_wide_donor_expand), then the launches of
+ * cf_mark_coalitions; per chunk one k_mark_expand (the donor rule: k_mark_donor_expand) reading kw words per row, then the launches of
  * cf_forward(save = 0) on the chunk:
  *   cf_launch_counts fwd = ceil(B * n_coal / max_batch) * (1 + n_fwd),  n_fwd = what cf_forward(save = 0) issues.
  * The words and the 2 P player words travel in the device table the handle owns (grown on demand); no other device buffer is added.

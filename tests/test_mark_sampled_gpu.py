@@ -153,6 +153,36 @@ def test_cells_rows_are_the_plain_forward_bit_for_bit(data, small, rule):
 
 
 @pytest.mark.parametrize("rule", ["scale", "donor"])
+def test_rows_at_the_ends_of_a_coalition_word(data, small, rule):
+    """One kernel pair builds the rows of the one-word and of the wide entry points from kw = ceil(P / 32) words: the player counts at
+    which kw or the word index of the last player changes.  The players are the first P of "cells" (31: mark 3 in pCRE slot 3, 32: mark 4
+    there); 1 and 16 players through the one-word calls, 32 and 33 through the wide one."""
+    batch = data[0]
+    donor = data[1] if rule == "donor" else None
+    cells = [((f,), (rho,)) for rho in range(9) for f in range(7)]
+    base = _plain(small, batch)
+    for P, absent in ((1, [(0,)]), (16, [(15,), tuple(range(15)), (0, 5, 9)]), (32, [(31,), tuple(range(31)), (0,)]),
+                      (33, [(32,), (31,), tuple(range(32)), (31, 32)])):
+        spec = cells[:P]
+        players = mark_players_wide(spec, 7, 8)
+        full = (1 << P) - 1
+        words = [full, 0] + [full & ~sum(1 << p for p in gone) for gone in absent]
+        if P > 16:
+            got = small.mark_coalitions_wide(*_args(batch), keep=words, players=spec, **(dict(donor=_feats(donor)) if donor is not None else {}))
+        elif donor is None:
+            got = small.mark_coalitions(*_args(batch), keep=words, players=spec)
+        else:
+            got = small.mark_donor_coalitions(*_args(batch), keep=words, players=spec, donor=_feats(donor))
+        got = got.cpu()
+        assert got.shape == (3, len(words), 2) and torch.equal(got[:, 0], base), (rule, P)
+        for c, m in enumerate(words):
+            assert torch.equal(got[:, c], _reference(small, batch, donor, players, m)), (rule, P, c, hex(m))
+        assert not torch.equal(got[:, 2], base), (rule, P)      # the last player alone absent changes a row
+        if P == 33:      # ... and is not taken for its neighbour across the word boundary
+            assert not torch.equal(got[:, 3], base) and not torch.equal(got[:, 2], got[:, 3]), rule
+
+
+@pytest.mark.parametrize("rule", ["scale", "donor"])
 def test_119_players_in_four_words(rule):
     cfg = orc._cfg(SHAPES["i_max16"][0])
     batch = _dev(orc.synthetic_batch(2, cfg=cfg, seed=13, regime="realistic"))

@@ -3,14 +3,14 @@ python tools/mark_sampled_bench.py [--out profiles/r16_mark_sampled.json]
 
 Shape: B = 64 genes (realistic regime), the default model, players "cells" (P = 63), n_perm = 16, s = 0: R = 2 + 16 * 62 = 994 rows per
 gene, 63,616 forwards.
-  call   one model.mark_shapley_sampled call (cf_mark_shapley_sampled: rows built by k_mark_wide_expand, 994 chunks of 64, then
+  call   one model.mark_shapley_sampled call (cf_mark_shapley_sampled: rows built by k_mark_expand, 994 chunks of 64, then
          k_perm_shapley);
   loop   public calls only: per 64 rows the prefix coalitions' inputs built with torch on the device (the same rule on the absent
          players' columns), model(...) under no_grad, then the estimator (mean and standard error over the orders) with torch.
 The two legs are interleaved in one process; HIP events around each; median of --rounds rounds with min and max, two warm-up rounds.
 The row logits of the two legs are compared for bit-equality in the same run (they must agree within 1e-4 before a time is reported).
 
-k_mark_wide_expand's bytes per second need the kernel's own time: run the call leg alone under the profiler and pass its statistics in,
+k_mark_expand's bytes per second need the kernel's own time: run the call leg alone under the profiler and pass its statistics in,
     rocprofv3 --kernel-trace --stats -d OUT -o run --output-format csv -- python tools/mark_sampled_bench.py --call-only
     python tools/mark_sampled_bench.py --kernel-stats OUT/<host>/run_kernel_stats.csv --out profiles/r16_mark_sampled.json
 Algorithmic bytes of one launch as in tools/mark_shapley_bench.py: every feature element read and written once, the masks and
@@ -26,7 +26,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=11)
 ap.add_argument("--perms", type=int, default=16)
 ap.add_argument("--call-only", action="store_true", help="two mark_shapley_sampled calls and nothing else (for a profiler run)")
-ap.add_argument("--kernel-stats", default=None, help="rocprofv3 --stats CSV of a --call-only run: adds k_mark_wide_expand's time and bytes per second")
+ap.add_argument("--kernel-stats", default=None, help="rocprofv3 --stats CSV of a --call-only run: adds k_mark_expand's time and bytes per second")
 ap.add_argument("--out", default=None, help="also write the result line to this file")
 a = ap.parse_args()
 dev = torch.device("cuda", 0)
@@ -118,9 +118,9 @@ row_bytes = sum(8 * (1 + S) * L * F + 2 * (1 + S) * L + 2 * T * T for L in NB) +
 expand = {"bytes_per_chunk_of_64": 64 * row_bytes, "launches_per_call": B * R // B}
 if a.kernel_stats:
     with open(a.kernel_stats) as f:
-        hit = [r for r in csv.DictReader(f) if "k_mark_wide_expand" in r["Name"]]
+        hit = [r for r in csv.DictReader(f) if "k_mark_expand" in r["Name"]]
     if not hit:
-        raise SystemExit("mark_sampled_bench: no k_mark_wide_expand row in %s" % a.kernel_stats)
+        raise SystemExit("mark_sampled_bench: no k_mark_expand row in %s" % a.kernel_stats)
     us = float(hit[0]["AverageNs"]) / 1e3
     expand.update({"us_average": round(us, 2), "calls_in_profile": int(hit[0]["Calls"]), "TB/s": round(64 * row_bytes / us / 1e6, 3),
                    "frac_of_8TBs": round(64 * row_bytes / us / 1e6 / 8, 3), "source": "rocprofv3 --kernel-trace --stats, a run of its own"})
@@ -129,7 +129,7 @@ else:
 line = json.dumps({"workload": "B = 64, one player per (mark, region) pair (P = %d), n_perm = %d, s = 0: %d forwards" % (P, NP, B * R),
                    "row_logits_bit_equal": same, "row_logits_max_abs_diff": worst, "phi_max_abs_diff": worst_phi, "stderr_max_abs_diff": worst_se,
                    "stderr_max": float(info["stderr"].max()), "phi_abs_max": float(phi_c.abs().max()),
-                   "timing": "HIP events around one call per leg, legs interleaved, two warm-up rounds", "call": res, "k_mark_wide_expand": expand})
+                   "timing": "HIP events around one call per leg, legs interleaved, two warm-up rounds", "call": res, "k_mark_expand": expand})
 print(line)
 if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

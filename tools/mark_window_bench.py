@@ -11,7 +11,7 @@ R = 2 + 16 * 69 = 1,106 rows per gene, 70,784 forwards.
 The two legs are interleaved in one process; HIP events around each; median of --rounds rounds with min and max, two warm-up rounds.
 The row logits of the two legs are compared for bit-equality in the same run (they must agree within 1e-4 before a time is reported).
 
-The per-chunk time of k_mark_window_expand beside k_mark_wide_expand's (what the extent and table phases cost) needs the kernels' own
+The per-chunk time of k_mark_window_expand beside k_mark_expand's (what the extent and table phases cost) needs the kernels' own
 times: run the call legs of both games alone under the profiler and pass the statistics in,
     rocprofv3 --kernel-trace --stats -d OUT -o run --output-format csv -- python tools/mark_window_bench.py --call-only
     python tools/mark_window_bench.py --kernel-stats OUT/<host>/run_kernel_stats.csv --out profiles/r17_mark_window.json
@@ -140,7 +140,7 @@ expand = {"bytes_per_chunk_of_64": 64 * row_bytes, "launches_per_call": B * R //
 if a.kernel_stats:
     with open(a.kernel_stats) as f:
         rows = list(csv.DictReader(f))
-    for name in ("k_mark_window_expand", "k_mark_wide_expand"):
+    for name in ("k_mark_window_expand", "k_mark_expand"):
         hit = [r for r in rows if name in r["Name"]]
         if not hit:
             expand[name] = "not measured"
@@ -149,7 +149,7 @@ if a.kernel_stats:
         expand[name] = {"us_average": round(us, 2), "calls_in_profile": int(hit[0]["Calls"]), "TB/s": round(64 * row_bytes / us / 1e6, 3)}
     expand["source"] = "rocprofv3 --kernel-trace --stats, one run of its own for both kernels (chunks of 64 rows, n_perm = %d)" % NP
 else:
-    expand["k_mark_window_expand"] = expand["k_mark_wide_expand"] = "not measured"
+    expand["k_mark_window_expand"] = expand["k_mark_expand"] = "not measured"
 line = json.dumps({"workload": "B = 64, one player per (mark, promoter window of 2 coarse bins) (P = %d), n_perm = %d, s = 0: %d forwards" % (P, NP, B * R),
                    "row_logits_bit_equal": same, "row_logits_max_abs_diff": worst, "phi_max_abs_diff": worst_phi, "stderr_max_abs_diff": worst_se,
                    "stderr_max": float(info["stderr"].max()), "phi_abs_max": float(phi_c.abs().max()),
