@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("CF_LIB_PATH") or os.path.join(_HERE, "libchromoformer
 FLAGS_PATH = LIB_PATH + ".flags"       # the CF_HIPCC_FLAGS the library was built with (part of the reuse check of build())
 CSRC = os.path.join(_HERE, "csrc")
 MAX_RES = 3
+INTERACTION_INDEX = {"sii": 0, "sti": 1}      # CF_INTERACTION_SII / CF_INTERACTION_STI
 BUCKET_REG, BUCKET_PE = 1, 2
 BUCKET_REG_HI, BUCKET_REG_LO = 4, 8      # the Regulation bucket in halves (cf_reg_halves): upper layers + head, lower layers
 PART_REG_HI, PART_REG_LO = 8, 16        # cf_backward_part: the Regulation backward as two launches
@@ -180,6 +181,8 @@ SYMBOLS = {
     "cf_pcre_coalitions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "cf_pcre_shapley": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_pcre_epistasis": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cf_shapley_interactions_from_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cf_pcre_shapley_interactions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_integrated_gradients": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_ig_opts), C.POINTER(cf_input_grads), C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_integrated_gradients_raw": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_ig_opts), C.POINTER(cf_input_grads),
@@ -192,19 +195,27 @@ SYMBOLS = {
     "cf_mark_coalitions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_opts), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "cf_mark_shapley": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_opts), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_mark_epistasis": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_opts), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cf_mark_shapley_interactions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_opts), C.c_int, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]),
     "cf_mark_donor_coalitions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_donor_opts), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "cf_mark_donor_shapley": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_donor_opts), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_mark_donor_epistasis": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_donor_opts), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cf_mark_donor_shapley_interactions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_donor_opts), C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
     "cf_mark_coalitions_wide": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_wide_opts), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "cf_mark_shapley_sampled": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_wide_opts), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
     "cf_mark_window_coalitions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_window_opts), C.c_void_p, C.c_int, C.c_void_p,
                                             C.c_void_p]),
     "cf_mark_window_shapley": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_window_opts), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cf_mark_window_shapley_interactions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_window_opts), C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
     "cf_mark_window_shapley_sampled": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_window_opts), C.c_void_p, C.c_int, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_mark_fine_coalitions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_fine_opts), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "cf_mark_fine_shapley": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_fine_opts), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cf_mark_fine_shapley_interactions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_fine_opts), C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
     "cf_mark_fine_shapley_sampled": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_fine_opts), C.c_void_p, C.c_int, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_adamw_step":(C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_longlong, C.c_void_p]),

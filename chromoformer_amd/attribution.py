@@ -185,6 +185,32 @@ def mark_wide_words(keep, P, who="mark_coalitions_wide"):
     return np.array([[(m >> (32 * w)) & 0xFFFFFFFF for w in range(kw)] for m in ints], dtype=np.uint32).reshape(len(ints), kw)
 
 
+INTERACTION_INDICES = ("sii", "sti")
+
+
+def interaction_index(index, who="interaction_index"):
+    """The library's constant of an interaction index name ("sii": the Shapley interaction index, "sti": Shapley-Taylor of order 2);
+    anything else raises ValueError listing the two."""
+    from . import _lib
+    if not isinstance(index, str) or index not in _lib.INTERACTION_INDEX:
+        raise ValueError("%s: unknown interaction index %r; choose from %s" % (who, index, list(INTERACTION_INDICES)))
+    return _lib.INTERACTION_INDEX[index]
+
+
+def interaction_weights(P, index="sii"):
+    """The weight table of the pairwise interaction index of a game of P >= 2 players -> float64 [P - 1]: w[s] for a coalition of s
+    players that holds neither of the pair.  "sii": s! (P - s - 2)! / (P - 1)!, which sums to 1 over all such coalitions; "sti":
+    (2 / P) / C(P - 1, s).  The library computes the same table in double and rounds it to fp32."""
+    from math import comb, factorial
+    interaction_index(index, "interaction_weights")
+    P = int(P)
+    if P < 2:
+        raise ValueError("interaction_weights: P = %d: a pair needs at least 2 players" % P)
+    if index == "sii":
+        return np.array([factorial(s) * factorial(P - s - 2) / factorial(P - 1) for s in range(P - 1)], dtype=np.float64)
+    return np.array([(2.0 / P) / comb(P - 1, s) for s in range(P - 1)], dtype=np.float64)
+
+
 def shapley_permutations(P, n_perm, seed=0):
     """n_perm independent uniform orders of P players -> uint8 [n_perm, P], each row a permutation of 0..P-1, from
     numpy.random.Generator(PCG64(seed)): the same seed gives the same orders."""
@@ -896,7 +922,7 @@ def perturbation_scan_fine(model, dataset, genes=None, region="promoter", zoom=N
             yield p
 
 
-def mark_shapley(model, dataset, genes=None, players="marks", scale=0.0, epistasis=False, bsz=None, store=None):
+def mark_shapley(model, dataset, genes=None, players="marks", scale=0.0, epistasis=False, bsz=None, store=None, interactions=None):
     """Exact Shapley values of the histone marks for the genes of a ChromoformerDataset (one model.mark_shapley per batch, with
     epistasis=True also one model.mark_epistasis): which marks carry the prediction when an absent mark's raw signal is scaled by
     `scale` (0 erases it) over the regions of its player.  A generator over `genes` (ids; default: the dataset's) in chunks of at most
@@ -908,6 +934,8 @@ def mark_shapley(model, dataset, genes=None, players="marks", scale=0.0, epistas
         erased    float32 [n_out]: every player absent
         players   the players' names (mark_players)
         eps       float32 [P, P, n_out], with epistasis=True: the pair epistasis, the leave-one-out effects on the diagonal
+        interactions  float32 [P, P, n_out], with interactions="sii" / "sti": the pairwise Shapley interaction index; the batch then makes
+                  one model.mark_shapley_interactions call in place of model.mark_shapley (the 2^P forwards run once; phi keeps its bits)
 
     players: "marks", "compartments", "regions" or a list of (marks, regions) pairs (mark_players).  The binned features come from
     `store` (a device-resident GeneStore holding `genes` in order) if given, else from the packed store next to the raw files if one
@@ -919,18 +947,27 @@ def mark_shapley(model, dataset, genes=None, players="marks", scale=0.0, epistas
     genes, chunk = _genes_check("mark_shapley", model, ds, genes, bsz)
     spec = players if isinstance(players, str) else list(players)
     names = mark_players(spec, ds.n_feats, ds.i_max)[2]      # (refusals before anything is loaded)
+    if interactions is not None:
+        interaction_index(interactions, "mark_shapley")
     store = _resident_store("mark_shapley", ds, genes, binsizes, model._device, store)
     for lo in range(0, len(genes), chunk):
         ids = genes[lo:lo + chunk]
         d = store.batch(list(range(lo, lo + len(ids))))
         args = tuple(d[k] for k in _BATCH_KEYS)
-        phi, info = model.mark_shapley(*args, players=spec, scale=scale)
+        inter = None
+        if interactions is None:
+            phi, info = model.mark_shapley(*args, players=spec, scale=scale)
+        else:
+            inter, info = model.mark_shapley_interactions(*args, players=spec, scale=scale, index=interactions)
+            phi, inter = info["phi"], inter.cpu().numpy()
         phi, logits, erased = phi.cpu().numpy(), info["logits"].cpu().numpy(), info["erased"].cpu().numpy()
         eps = model.mark_epistasis(*args, players=spec, scale=scale)[0].cpu().numpy() if epistasis else None
         for i, g in enumerate(ids):
             out = dict(gene_id=g, phi=phi[i].copy(), logits=logits[i].copy(), erased=erased[i].copy(), players=list(names))
             if epistasis:
                 out["eps"] = eps[i].copy()
+            if inter is not None:
+                out["interactions"] = inter[i].copy()
             yield out
 
 
@@ -965,7 +1002,8 @@ def same_regions(dataset, donor_dataset, genes=None):
     return genes
 
 
-def mark_donor_shapley(model, dataset, donor_dataset, genes=None, players="marks", epistasis=False, bsz=None, store=None, donor_store=None):
+def mark_donor_shapley(model, dataset, donor_dataset, genes=None, players="marks", epistasis=False, bsz=None, store=None, donor_store=None,
+                       interactions=None):
     """Exact Shapley values of the histone marks against a donor cell type, for the genes of two ChromoformerDatasets over the same
     regions (same_regions): one model.mark_donor_shapley per batch, with epistasis=True also one model.mark_donor_epistasis -- which
     mark changes account for the difference between the prediction in `dataset` and in `donor_dataset`?  A generator over `genes`
@@ -979,6 +1017,8 @@ def mark_donor_shapley(model, dataset, donor_dataset, genes=None, players="marks
                            donor is what the marks of the players do not explain
         players            the players' names (mark_players)
         eps                float32 [P, P, n_out], with epistasis=True: the pair epistasis, the leave-one-out effects on the diagonal
+        interactions       float32 [P, P, n_out], with interactions="sii" / "sti": the pairwise Shapley interaction index; the batch then
+                           makes one model.mark_donor_shapley_interactions call in place of model.mark_donor_shapley
 
     players as in mark_shapley.  The binned features come from `store` / `donor_store` (device-resident GeneStores holding `genes` in
     order) if given, else from the packed store next to each dataset's raw files if one matches, else from the raw .npy files binned
@@ -992,6 +1032,8 @@ def mark_donor_shapley(model, dataset, donor_dataset, genes=None, players="marks
     same_regions(ds, dn, genes)
     spec = players if isinstance(players, str) else list(players)
     names = mark_players(spec, ds.n_feats, ds.i_max)[2]      # (refusals before anything is loaded)
+    if interactions is not None:
+        interaction_index(interactions, "mark_donor_shapley")
     store = _resident_store("mark_donor_shapley", ds, genes, binsizes, model._device, store)
     donor_store = _resident_store("mark_donor_shapley", dn, genes, binsizes, model._device, donor_store)
     for lo in range(0, len(genes), chunk):
@@ -1000,7 +1042,12 @@ def mark_donor_shapley(model, dataset, donor_dataset, genes=None, players="marks
         d, dd = store.batch(idx), donor_store.batch(idx)
         args = tuple(d[k] for k in _BATCH_KEYS)
         donor = _donor_pair(dd)
-        phi, info = model.mark_donor_shapley(*args, donor=donor, players=spec)
+        inter = None
+        if interactions is None:
+            phi, info = model.mark_donor_shapley(*args, donor=donor, players=spec)
+        else:
+            inter, info = model.mark_donor_shapley_interactions(*args, donor=donor, players=spec, index=interactions)
+            phi, inter = info["phi"], inter.cpu().numpy()
         phi, logits, don = phi.cpu().numpy(), info["logits"].cpu().numpy(), info["donor"].cpu().numpy()
         eps = model.mark_donor_epistasis(*args, donor=donor, players=spec)[0].cpu().numpy() if epistasis else None
         with torch.no_grad():
@@ -1010,6 +1057,8 @@ def mark_donor_shapley(model, dataset, donor_dataset, genes=None, players="marks
                        players=list(names))
             if epistasis:
                 out["eps"] = eps[i].copy()
+            if inter is not None:
+                out["interactions"] = inter[i].copy()
             yield out
 
 
@@ -1078,7 +1127,7 @@ def window_player_coordinates(marks_regions_windows, regions, n_real, binsize):
 
 
 def mark_window_shapley(model, dataset, donor_dataset=None, genes=None, players="promoter", width=1, n_perm=64, seed=0, scale=0.0, bsz=None,
-                        store=None, donor_store=None):
+                        store=None, donor_store=None, interactions=None):
     """Shapley values of WINDOW players for the genes of a ChromoformerDataset: where inside a region does the signal lie?  With at most
     16 players one model.mark_window_shapley per batch (exact), else one model.mark_window_shapley_sampled (n_perm orders from `seed`).
     Without `donor_dataset` an absent player's raw signal inside its window is scaled by `scale` (0 erases it); with one -- the same
@@ -1096,6 +1145,9 @@ def mark_window_shapley(model, dataset, donor_dataset=None, genes=None, players=
                        perturbation_scan reports them ('-' strand promoters are stored mirrored: window 0 is still the genomic start)
         null           bool [P]: the player has no real window in this gene (a dummy slot, a short pCRE, a narrowed promoter): phi = 0
         permutations   uint8 [n_perm, P], sampled only: the orders, the same for every gene
+        interactions   float32 [P, P, n_out], with interactions="sii" / "sti": the pairwise Shapley interaction index of the players (a
+                       null player's row and column are 0); the batch then makes one model.mark_window_shapley_interactions call in
+                       place of model.mark_window_shapley.  The index has no sampled estimator: more than 16 players raise ValueError
 
     Strand and coordinates come from the dataset's metadata.  The binned features come from `store` / `donor_store` as in
     mark_donor_shapley.  Parameters, gradients and optimiser state are left as they are; the pass overwrites the activations a
@@ -1115,6 +1167,11 @@ def mark_window_shapley(model, dataset, donor_dataset=None, genes=None, players=
     names = game[4]
     P = len(names)
     exact = P <= 16
+    if interactions is not None:
+        interaction_index(interactions, who)
+        if not exact:
+            raise ValueError("%s: interactions: %d players; the index is computed by the exact game of at most 16 players: choose a "
+                             "larger width" % (who, P))
     perms = None if exact else shapley_permutations(P, n_perm, seed)
     col0 = promoter_col0(ds)
     store = _resident_store(who, ds, genes, binsizes, model._device, store)
@@ -1131,8 +1188,14 @@ def mark_window_shapley(model, dataset, donor_dataset=None, genes=None, players=
             donor = _donor_pair(dd)
         flip = [ds.genes[g]["tss"][2] != "+" for g in ids]
         args = tuple(d[k] for k in _BATCH_KEYS)
+        inter = None
         if exact:
-            phi, info = model.mark_window_shapley(*args, players=spec, width=width, scale=scale, donor=donor, flip=flip)
+            if interactions is None:
+                phi, info = model.mark_window_shapley(*args, players=spec, width=width, scale=scale, donor=donor, flip=flip)
+            else:
+                inter, info = model.mark_window_shapley_interactions(*args, players=spec, width=width, scale=scale, donor=donor, flip=flip,
+                                                                     index=interactions)
+                phi, inter = info["phi"], inter.cpu().numpy()
             absent = info["erased" if donor is None else "donor"].cpu().numpy()
             se = np.zeros(tuple(phi.shape), dtype=np.float32)
         else:
@@ -1155,11 +1218,13 @@ def mark_window_shapley(model, dataset, donor_dataset=None, genes=None, players=
                        absent=absent[i].copy(), players=list(names), windows=windows, null=null)
             if not exact:
                 out["permutations"] = perms.copy()
+            if inter is not None:
+                out["interactions"] = inter[i].copy()
             yield out
 
 
 def mark_fine_window_shapley(model, dataset, donor_dataset=None, genes=None, region="promoter", zoom=1, coarse_width=1, width=2, players="windows",
-                             n_perm=64, seed=0, scale=0.0, target=None, bsz=None, store=None, donor_store=None):
+                             n_perm=64, seed=0, scale=0.0, target=None, bsz=None, store=None, donor_store=None, interactions=None):
     """Shapley values of FINE window players for the genes of a ChromoformerDataset: which 200 bp of this peak?  Per batch the coarse
     window game runs first (model.mark_window_shapley over `region` at `coarse_width` coarsest bins per player, exact with at most 16
     players, else sampled); per gene the `zoom` coarse windows with the largest |phi| at logit `target` (default: the last) are chosen,
@@ -1182,6 +1247,10 @@ def mark_fine_window_shapley(model, dataset, donor_dataset=None, genes=None, reg
         logits          float32 [n_out]: the prediction
         absent          float32 [k', n_out]: per rank, every fine player absent
         exact           whether the fine game was exact
+        interactions    with interactions="sii" / "sti": per rank a float32 [n_r, n_r, n_out], the pairwise Shapley interaction index of
+                        that rank's fine players with a real window, in their order above; the fine game then makes one
+                        model.mark_fine_window_shapley_interactions call in place of model.mark_fine_window_shapley (the coarse game is
+                        unchanged).  The index has no sampled estimator: more than 16 fine players raise ValueError
 
     Strand, coordinates and the region's length come from the dataset's metadata: '-' strand promoters are stored mirrored (window 0 is
     still the genomic start) and the short last bin of a pCRE is weighted by the samples it holds.  Features, stores, parameters and
@@ -1210,6 +1279,11 @@ def mark_fine_window_shapley(model, dataset, donor_dataset=None, genes=None, reg
     names = game[3]
     P = len(names)
     exact = P <= 16
+    if interactions is not None:
+        interaction_index(interactions, who)
+        if not exact:
+            raise ValueError("%s: interactions: %d fine players; the index is computed by the exact game of at most 16 players: choose a "
+                             "larger width or a smaller coarse_width" % (who, P))
     perms = None if exact else shapley_permutations(P, n_perm, seed)
     coarse = [(list(range(F)), [region], (g, min(g + coarse_width, W))) for g in range(0, W, coarse_width)]
     Pc = len(coarse)
@@ -1247,12 +1321,19 @@ def mark_fine_window_shapley(model, dataset, donor_dataset=None, genes=None, reg
                             index=np.zeros(0, np.int64),
                             phi=np.zeros((0, model.n_out), np.float32), stderr=None if exact else np.zeros((0, model.n_out), np.float32),
                             logits=logits[i].copy(), absent=np.zeros((0, model.n_out), np.float32), exact=exact))
+            if interactions is not None:
+                per[-1]["interactions"] = []
         for rank in range(max([len(z) for z in ranks] + [0])):
             # a gene with fewer real coarse windows than ranks starts past its region: null players, left out below
             start = [int(z[rank]) * coarse_width * Rc if rank < len(z) else Lf for z in ranks]
             kw = dict(region=region, players=spec, width=width, n_windows=n_fw, start=start, lengths=lengths, scale=scale, donor=donor, flip=flip)
+            inter = None
             if exact:
-                phi, info = model.mark_fine_window_shapley(*args, **kw)
+                if interactions is None:
+                    phi, info = model.mark_fine_window_shapley(*args, **kw)
+                else:
+                    inter, info = model.mark_fine_window_shapley_interactions(*args, index=interactions, **kw)
+                    phi, inter = info["phi"], inter.cpu().numpy()
                 absent, se = info["erased" if donor is None else "donor"].cpu().numpy(), None
             else:
                 phi, info = model.mark_fine_window_shapley_sampled(*args, permutations=perms, **kw)
@@ -1271,5 +1352,7 @@ def mark_fine_window_shapley(model, dataset, donor_dataset=None, genes=None, reg
                 if not exact:
                     per[i]["stderr"] = np.concatenate([per[i]["stderr"], se[i, real]])
                 per[i]["absent"] = np.concatenate([per[i]["absent"], absent[i][None]])
+                if inter is not None:
+                    per[i]["interactions"].append(inter[i][np.ix_(real, real)].copy())
         for p in per:
             yield p

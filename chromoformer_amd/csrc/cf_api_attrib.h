@@ -349,17 +349,60 @@ static std::vector<uint32_t> all_words(int P) {
     for (size_t m = 0; m < keep.size(); ++m) keep[m] = (uint32_t)m;
     return keep;
 }
+static void shapley_weights(int P, float* w) {      // w(k) = k! (P - k - 1)! / P!, in double, rounded to fp32
+    double fact[kCoalMaxS + 1] = {1.0};
+    for (int k = 1; k <= P; ++k) fact[k] = fact[k - 1] * k;
+    for (int k = 0; k < P; ++k) w[k] = (float)(fact[k] * fact[P - k - 1] / fact[P]);
+}
 static int launch_shapley(cf_handle* h, int B, int P, const float* rows, float* phi, hipStream_t st) {
     ShapleyArgs sa;
     memset(&sa, 0, sizeof sa);
     sa.v = rows, sa.phi = phi, sa.S = P, sa.n_out = h->cfg.n_out;
-    double fact[kCoalMaxS + 1] = {1.0};
-    for (int k = 1; k <= P; ++k) fact[k] = fact[k - 1] * k;
-    for (int k = 0; k < P; ++k) sa.w[k] = (float)(fact[k] * fact[P - k - 1] / fact[P]);
+    shapley_weights(P, sa.w);
     hipLaunchKernelGGL(k_shapley, dim3(B, P), dim3(kShapThreads), 0, st, sa);
     LAUNCH_CHECK("k_shapley");
     forward_one_more(h);
     return 0;
+}
+// The pairwise interaction index of the P >= 2 players on the same rows: what the interactions entry points check beside their
+// sibling's checks, and k_shapley_pairs with the weight table of `index` (cf_coalition.h), in double, rounded to fp32:
+//   sii  w2(s) = s! (P - s - 2)! / (P - 1)!        sti  w2(s) = (2 / P) / C(P - 1, s),   s = |S| <= P - 2.
+static int interactions_check(int index, int P, const float* inter, const char* who) {
+    if (!inter) return fail("%s: null inter", who);
+    if (index != CF_INTERACTION_SII && index != CF_INTERACTION_STI)
+        return fail("%s: index = %d: CF_INTERACTION_SII (%d) or CF_INTERACTION_STI (%d)", who, index, CF_INTERACTION_SII, CF_INTERACTION_STI);
+    if (P < 2) return fail("%s: %d player%s: a pair needs at least 2", who, P, P == 1 ? "" : "s");
+    return 0;
+}
+static int launch_shapley_pairs(cf_handle* h, int B, int P, int index, const float* rows, float* inter, hipStream_t st) {
+    ShapleyPairsArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.v = rows, pa.inter = inter, pa.P = P, pa.n_out = h->cfg.n_out, pa.sti = index == CF_INTERACTION_STI;
+    shapley_weights(P, pa.w1);
+    double fact[kCoalMaxS + 1] = {1.0};
+    for (int k = 1; k <= P; ++k) fact[k] = fact[k - 1] * k;
+    for (int s = 0; s <= P - 2; ++s)
+        pa.w2[s] = pa.sti ? (float)((2.0 / P) / (fact[P - 1] / (fact[s] * fact[P - 1 - s]))) : (float)(fact[s] * fact[P - s - 2] / fact[P - 1]);
+    hipLaunchKernelGGL(k_shapley_pairs, dim3(B, P * (P + 1) / 2), dim3(kShapThreads), 0, st, pa);
+    LAUNCH_CHECK("k_shapley_pairs");
+    forward_one_more(h);
+    return 0;
+}
+// The reducers of an interactions call on its 2^P rows: k_shapley_pairs, and k_shapley too if the caller wants phi.
+static int launch_interactions(cf_handle* h, int B, int P, int index, const float* rows, float* inter, float* phi, hipStream_t st) {
+    if (launch_shapley_pairs(h, B, P, index, rows, inter, st)) return -1;
+    return phi ? launch_shapley(h, B, P, rows, phi, st) : 0;
+}
+// The operator on a caller's table: no batch, no workspace, nothing of the handle but n_out is read and no activation is written.
+extern "C" int cf_shapley_interactions_from_rows(cf_handle* h, const float* rows, int B, int P, int index, float* inter, void* stream) {
+    const char* who = "cf_shapley_interactions_from_rows";
+    if (!h) return fail("%s: null handle", who);
+    if (!rows) return fail("%s: null rows", who);
+    if (B < 1) return fail("%s: B = %d: at least 1 gene", who, B);
+    if (P < 2 || P > kCoalMaxS) return fail("%s: P = %d outside 2..%d", who, P, kCoalMaxS);
+    if (interactions_check(index, P, inter, who)) return -1;
+    h->n_fwd = 0;
+    return launch_shapley_pairs(h, B, P, index, rows, inter, (hipStream_t)stream);
 }
 // pair_words: the 1 + P + P (P - 1) / 2 pair-deletion coalitions (N = 2^P - 1; N without i; N without i and j, i < j);
 // launch_epistasis: k_epistasis on those rows.
@@ -394,6 +437,20 @@ extern "C" int cf_pcre_shapley(cf_handle* h, const cf_batch* bt, float* phi, flo
     hipStream_t st = (hipStream_t)stream;
     if (coalition_upload(h, keep.data(), n, st, who) || coalition_rows(h, bt, h->aw.words, n, rows, st)) return -1;
     return launch_shapley(h, bt->B, S, rows, phi, st);
+}
+
+// cf_pcre_shapley's rows, then k_shapley_pairs (and k_shapley if phi is wanted).
+extern "C" int cf_pcre_shapley_interactions(cf_handle* h, const cf_batch* bt, int index, float* inter, float* phi, float* logits_all, void* stream) {
+    const char* who = "cf_pcre_shapley_interactions";
+    if (attrib_open(h, bt, false, who)) return -1;
+    const int S = h->cfg.i_max, n = 1 << S;
+    if (interactions_check(index, S, inter, who)) return -1;
+    float* rows = coalition_out_rows(h, logits_all, n, who);
+    if (!rows) return -1;
+    const std::vector<uint32_t> keep = all_words(S);
+    hipStream_t st = (hipStream_t)stream;
+    if (coalition_upload(h, keep.data(), n, st, who) || coalition_rows(h, bt, h->aw.words, n, rows, st)) return -1;
+    return launch_interactions(h, bt->B, S, index, rows, inter, phi, st);
 }
 
 // The pair-deletion coalitions through coalition_upload + coalition_rows, then k_epistasis.

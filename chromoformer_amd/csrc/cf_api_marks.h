@@ -253,17 +253,25 @@ static int mark_coalitions_impl(cf_handle* h, const cf_batch* bt, const MarkGame
     if (mark_upload(h, g, keep, n_coal, 0, st, who)) return -1;
     return mark_rows(h, bt, g, n_coal, logits, st);
 }
-// an exact game -- all 2^P coalitions and k_shapley, or the pair-deletion coalitions and k_epistasis, with S = P (all_words /
-// launch_shapley, pair_words / launch_epistasis: cf_api_attrib.h) -- through mark_upload + mark_rows;
-static int mark_exact_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g, bool pairs, float* out, float* logits_rows, void* stream, const char* who) {
-    if (!out) return fail(pairs ? "%s: null eps" : "%s: null phi", who);
-    const std::vector<uint32_t> keep = pairs ? pair_words(g.P) : all_words(g.P);
+// an exact game -- all 2^P coalitions and k_shapley, the pair-deletion coalitions and k_epistasis, or all 2^P coalitions and
+// k_shapley_pairs (with k_shapley if `phi` is given), with S = P (all_words / launch_shapley, pair_words / launch_epistasis,
+// launch_interactions: cf_api_attrib.h) -- through mark_upload + mark_rows;
+enum MarkExact { kExactShapley, kExactEpistasis, kExactInteractions };
+static int mark_exact_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g, MarkExact what, float* out, float* logits_rows, void* stream,
+                           const char* who, int index = 0, float* phi = nullptr) {
+    if (what == kExactInteractions) {
+        if (interactions_check(index, g.P, out, who)) return -1;
+    } else if (!out) {
+        return fail(what == kExactEpistasis ? "%s: null eps" : "%s: null phi", who);
+    }
+    const std::vector<uint32_t> keep = what == kExactEpistasis ? pair_words(g.P) : all_words(g.P);
     const int R = (int)keep.size();
     float* rows = coalition_out_rows(h, logits_rows, R, who);
     if (!rows) return -1;
     hipStream_t st = (hipStream_t)stream;
     if (mark_upload(h, g, keep.data(), R, 0, st, who) || mark_rows(h, bt, g, R, rows, st)) return -1;
-    return pairs ? launch_epistasis(h, bt->B, g.P, rows, out, st) : launch_shapley(h, bt->B, g.P, rows, out, st);
+    if (what == kExactInteractions) return launch_interactions(h, bt->B, g.P, index, rows, out, phi, st);
+    return what == kExactEpistasis ? launch_epistasis(h, bt->B, g.P, rows, out, st) : launch_shapley(h, bt->B, g.P, rows, out, st);
 }
 // the prefix rows of n_perm permutations through mark_upload + mark_rows (column 0 nobody, column 1 everybody, column
 // 2 + q (P - 1) + (k - 1) the first k players of permutation q), then k_perm_shapley on the inverse permutations, which travel as bytes
@@ -323,12 +331,18 @@ extern "C" int cf_mark_coalitions(cf_handle* h, const cf_batch* bt, const cf_mar
 extern "C" int cf_mark_shapley(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, float* phi, float* logits_all, void* stream) {
     const char* who = "cf_mark_shapley";
     MarkGame g;
-    return mark_game(h, bt, o, &g, who) ? -1 : mark_exact_impl(h, bt, g, false, phi, logits_all, stream, who);
+    return mark_game(h, bt, o, &g, who) ? -1 : mark_exact_impl(h, bt, g, kExactShapley, phi, logits_all, stream, who);
 }
 extern "C" int cf_mark_epistasis(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, float* eps, float* logits_pairs, void* stream) {
     const char* who = "cf_mark_epistasis";
     MarkGame g;
-    return mark_game(h, bt, o, &g, who) ? -1 : mark_exact_impl(h, bt, g, true, eps, logits_pairs, stream, who);
+    return mark_game(h, bt, o, &g, who) ? -1 : mark_exact_impl(h, bt, g, kExactEpistasis, eps, logits_pairs, stream, who);
+}
+extern "C" int cf_mark_shapley_interactions(cf_handle* h, const cf_batch* bt, const cf_mark_opts* o, int index, float* inter, float* phi,
+                                            float* logits_all, void* stream) {
+    const char* who = "cf_mark_shapley_interactions";
+    MarkGame g;
+    return mark_game(h, bt, o, &g, who) ? -1 : mark_exact_impl(h, bt, g, kExactInteractions, inter, logits_all, stream, who, index, phi);
 }
 
 // the donor family: an absent mark takes the donor's bits (k_mark_donor_expand); everything else as above;
@@ -341,12 +355,18 @@ extern "C" int cf_mark_donor_coalitions(cf_handle* h, const cf_batch* bt, const 
 extern "C" int cf_mark_donor_shapley(cf_handle* h, const cf_batch* bt, const cf_mark_donor_opts* o, float* phi, float* logits_all, void* stream) {
     const char* who = "cf_mark_donor_shapley";
     MarkGame g;
-    return mark_donor_game(h, bt, o, &g, who) ? -1 : mark_exact_impl(h, bt, g, false, phi, logits_all, stream, who);
+    return mark_donor_game(h, bt, o, &g, who) ? -1 : mark_exact_impl(h, bt, g, kExactShapley, phi, logits_all, stream, who);
 }
 extern "C" int cf_mark_donor_epistasis(cf_handle* h, const cf_batch* bt, const cf_mark_donor_opts* o, float* eps, float* logits_pairs, void* stream) {
     const char* who = "cf_mark_donor_epistasis";
     MarkGame g;
-    return mark_donor_game(h, bt, o, &g, who) ? -1 : mark_exact_impl(h, bt, g, true, eps, logits_pairs, stream, who);
+    return mark_donor_game(h, bt, o, &g, who) ? -1 : mark_exact_impl(h, bt, g, kExactEpistasis, eps, logits_pairs, stream, who);
+}
+extern "C" int cf_mark_donor_shapley_interactions(cf_handle* h, const cf_batch* bt, const cf_mark_donor_opts* o, int index, float* inter, float* phi,
+                                                  float* logits_all, void* stream) {
+    const char* who = "cf_mark_donor_shapley_interactions";
+    MarkGame g;
+    return mark_donor_game(h, bt, o, &g, who) ? -1 : mark_exact_impl(h, bt, g, kExactInteractions, inter, logits_all, stream, who, index, phi);
 }
 
 // the wide game;
@@ -373,7 +393,14 @@ extern "C" int cf_mark_window_coalitions(cf_handle* h, const cf_batch* bt, const
 extern "C" int cf_mark_window_shapley(cf_handle* h, const cf_batch* bt, const cf_mark_window_opts* o, float* phi, float* logits_all, void* stream) {
     const char* who = "cf_mark_window_shapley";
     MarkGame g;
-    return mark_window_game(h, bt, o, &g, who, kCoalMaxS) ? -1 : mark_exact_impl(h, bt, g, false, phi, logits_all, stream, who);
+    return mark_window_game(h, bt, o, &g, who, kCoalMaxS) ? -1 : mark_exact_impl(h, bt, g, kExactShapley, phi, logits_all, stream, who);
+}
+extern "C" int cf_mark_window_shapley_interactions(cf_handle* h, const cf_batch* bt, const cf_mark_window_opts* o, int index, float* inter, float* phi,
+                                                   float* logits_all, void* stream) {
+    const char* who = "cf_mark_window_shapley_interactions";
+    MarkGame g;
+    return mark_window_game(h, bt, o, &g, who, kCoalMaxS) ? -1
+                                                          : mark_exact_impl(h, bt, g, kExactInteractions, inter, logits_all, stream, who, index, phi);
 }
 extern "C" int cf_mark_window_shapley_sampled(cf_handle* h, const cf_batch* bt, const cf_mark_window_opts* o, const uint8_t* perms, int n_perm,
                                               float* phi, float* se, float* logits_rows, void* stream) {
@@ -392,7 +419,15 @@ extern "C" int cf_mark_fine_coalitions(cf_handle* h, const cf_batch* bt, const c
 extern "C" int cf_mark_fine_shapley(cf_handle* h, const cf_batch* bt, const cf_mark_fine_opts* o, float* phi, float* logits_all, void* stream) {
     const char* who = "cf_mark_fine_shapley";
     MarkGame g;
-    return mark_fine_game(h, bt, o, &g, (hipStream_t)stream, who, kCoalMaxS) ? -1 : mark_exact_impl(h, bt, g, false, phi, logits_all, stream, who);
+    return mark_fine_game(h, bt, o, &g, (hipStream_t)stream, who, kCoalMaxS) ? -1 : mark_exact_impl(h, bt, g, kExactShapley, phi, logits_all, stream, who);
+}
+extern "C" int cf_mark_fine_shapley_interactions(cf_handle* h, const cf_batch* bt, const cf_mark_fine_opts* o, int index, float* inter, float* phi,
+                                                 float* logits_all, void* stream) {
+    const char* who = "cf_mark_fine_shapley_interactions";
+    MarkGame g;
+    return mark_fine_game(h, bt, o, &g, (hipStream_t)stream, who, kCoalMaxS)
+               ? -1
+               : mark_exact_impl(h, bt, g, kExactInteractions, inter, logits_all, stream, who, index, phi);
 }
 extern "C" int cf_mark_fine_shapley_sampled(cf_handle* h, const cf_batch* bt, const cf_mark_fine_opts* o, const uint8_t* perms, int n_perm, float* phi,
                                             float* se, float* logits_rows, void* stream) {

@@ -151,7 +151,7 @@ class ChromoformerBase(nn.Module):
         self.n_bins = [w_max // b for b in self.binsizes]
         self._kws = (embed, pair, reg)
         self._max_batch = max_batch
-        self._maps_gen = 0          # bumped by attention_maps() / pcre_ablation() / pcre_coalitions() / pcre_shapley() / pcre_epistasis() / integrated_gradients() / perturbation_scan() / perturbation_scan_regions() / perturbation_scan_fine() / trunk_outputs(): a pending backward of an earlier forward refuses to run
+        self._maps_gen = 0          # bumped by attention_maps() / pcre_ablation() / pcre_coalitions() / pcre_shapley() / pcre_shapley_interactions() / pcre_epistasis() / integrated_gradients() / perturbation_scan() / perturbation_scan_regions() / perturbation_scan_fine() / trunk_outputs(): a pending backward of an earlier forward refuses to run
         self._maps_by = None        # ... naming the last of them
         self._handle = None
         self._device = None
@@ -535,6 +535,64 @@ class ChromoformerBase(nn.Module):
         return phi, info
 
     @torch.no_grad()
+    def pcre_shapley_interactions(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                                  interaction_freq=None, index="sii", return_coalitions=False):
+        """Pairwise Shapley interaction indices of the pCRE slots (cf_pcre_shapley_interactions) -> (inter, info), tensors on the
+        model's device, no autograd graph.  P = i_max (at least 2); the 2^i_max coalitions run once, as in pcre_shapley:
+
+          inter               [B, P, P, n_out], exactly symmetric.  Off the diagonal, with S over the coalitions that hold neither player,
+                              I_ij = sum_S w(|S|) ((v(S + i + j) - v(S + j)) - (v(S + i) - v(S))): how much i's marginal contribution
+                              changes with j present, averaged over every context -- negative for redundant players, positive for
+                              cooperating ones, also where a third player hides the effect from the full-coalition *_epistasis.  index "sii"
+                              (Shapley interaction index): w(s) = s! (P - s - 2)! / (P - 1)!, the diagonal is phi.  index "sti"
+                              (Shapley-Taylor, order 2): w(s) = (2 / P) / C(P - 1, s), the diagonal is v({i}) - v(nobody), and the
+                              diagonal plus the upper triangle sums to logits - promoter_only.  A null player's row and column are exactly 0
+          info["phi"]         [B, P, n_out]: the Shapley values of pcre_shapley on the same rows, bit for bit
+          info["logits"]      [B, n_out]: the prediction;  info["promoter_only"]  [B, n_out]: every player absent
+          info["index"]       the index name;  info["delta"]  [B, n_out], "sti" only: the efficiency gap (rounding only)
+          info["coalitions"]  [B, 2^P, n_out], with return_coalitions: the logits of every coalition, word m at column m
+
+        SHAP's interaction values follow from the sii result: Phi_ij = I_ij / 2 off the diagonal and Phi_ii = phi_i - sum_{j != i} I_ij / 2.
+        The packed forms of the first argument and the effect on a pending backward() are those of pcre_shapley."""
+        from .attribution import interaction_index
+        code = interaction_index(index, "pcre_shapley_interactions")
+        bs, _keep, book = self._attrib_call("pcre_shapley_interactions", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        S = self.i_max
+        rows = torch.empty(bs.B, 1 << S, self.n_out, device=self._device)      # (all three written in full by the library)
+        inter = torch.empty(bs.B, S, S, self.n_out, device=self._device)
+        phi = torch.empty(bs.B, S, self.n_out, device=self._device)
+        st = book()
+        _lib.check(_lib.lib().cf_pcre_shapley_interactions(self._handle, C.byref(bs), code, inter.data_ptr(), phi.data_ptr(), rows.data_ptr(), st),
+                   "cf_pcre_shapley_interactions")
+        return inter, self._interactions_info(inter, phi, rows, index, "promoter_only", None, return_coalitions)
+
+    @torch.no_grad()
+    def shapley_interactions(self, coalitions, index="sii"):
+        """Pairwise Shapley interaction indices from a kept coalition table (cf_shapley_interactions_from_rows) -> inter
+        [B, P, P, n_out] on the model's device: `coalitions` is info["coalitions"] of any exact *_shapley call, [B, 2^P, n_out] with
+        word m at column m, 2 <= P <= 16 (a float32 tensor; moved to the model's device and made contiguous if it is not).  The bits
+        are those of the *_shapley_interactions call on the same table (index as there); no forward runs and a pending backward() is
+        left alone.
+        SHAP's interaction values follow from the sii result: Phi_ij = I_ij / 2 off the diagonal and Phi_ii = phi_i - sum_{j != i} I_ij / 2."""
+        from .attribution import interaction_index
+        code = interaction_index(index, "shapley_interactions")
+        if not torch.is_tensor(coalitions) or coalitions.dim() != 3 or coalitions.dtype != torch.float32:
+            raise ValueError("shapley_interactions: coalitions must be a float32 tensor [B, 2^P, n_out]")
+        B, n, n_out = coalitions.shape
+        P = n.bit_length() - 1
+        if B < 1 or n != 1 << P or not 2 <= P <= 16 or n_out != self.n_out:
+            raise ValueError("shapley_interactions: coalitions has shape %s; expected [B >= 1, 2^P with P in 2..16, n_out = %d]"
+                             % (tuple(coalitions.shape), self.n_out))
+        if self._handle is None:
+            raise RuntimeError("shapley_interactions: the model is not on a GPU (model.cuda() first); there is no CPU fallback")
+        rows = coalitions.to(self._device).contiguous()
+        inter = torch.empty(B, P, P, n_out, device=self._device)      # (written in full by the library)
+        st = torch.cuda.current_stream(self._device).cuda_stream
+        _lib.check(_lib.lib().cf_shapley_interactions_from_rows(self._handle, rows.data_ptr(), B, P, code, inter.data_ptr(), st),
+                   "cf_shapley_interactions_from_rows")
+        return inter
+
+    @torch.no_grad()
     def pcre_epistasis(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
                        interaction_freq=None):
         """Pair-deletion epistasis of the pCRE slots (cf_pcre_epistasis) -> (eps, info), tensors on the model's device, no autograd graph.
@@ -916,6 +974,32 @@ class ChromoformerBase(nn.Module):
             info["coalitions"] = rows
         return phi, info
 
+    def _interactions_info(self, inter, phi, rows, index, absent_key, names, return_coalitions):
+        """`info` of an interactions call from its outputs; rows [B, 2^P, n_out], word m at column m."""
+        n = rows.shape[1]
+        info = {"phi": phi, "logits": rows[:, n - 1].clone(), absent_key: rows[:, 0].clone(), "index": index}
+        if names is not None:
+            info["players"] = names
+        if index == "sti":      # efficiency: the diagonal plus the upper triangle sums to v(N) - v(0)
+            P = inter.shape[1]
+            upper = torch.triu(torch.ones(P, P, dtype=torch.bool, device=inter.device))
+            info["delta"] = inter[:, upper].sum(1) - (info["logits"] - info[absent_key])
+        if return_coalitions:
+            info["coalitions"] = rows
+        return info
+
+    def _mark_run_interactions(self, cfn, bs, opts, names, absent_key, book, index, return_coalitions):
+        from .attribution import interaction_index
+        code = interaction_index(index, cfn[3:])
+        P = opts.n_players
+        n = 1 << P
+        rows = torch.empty(bs.B, n, self.n_out, device=self._device)      # (all three written in full by the library)
+        inter = torch.empty(bs.B, P, P, self.n_out, device=self._device)
+        phi = torch.empty(bs.B, P, self.n_out, device=self._device)
+        st = book()
+        _lib.check(getattr(_lib.lib(), cfn)(self._handle, C.byref(bs), C.byref(opts), code, inter.data_ptr(), phi.data_ptr(), rows.data_ptr(), st), cfn)
+        return inter, self._interactions_info(inter, phi, rows, index, absent_key, names, return_coalitions)
+
     def _mark_run_epistasis(self, cfn, bs, opts, names, book):
         P = opts.n_players
         rows = torch.empty(bs.B, 1 + P + P * (P - 1) // 2, self.n_out, device=self._device)      # (both written in full by the library)
@@ -1003,11 +1087,38 @@ class ChromoformerBase(nn.Module):
         bs, _keep, book = self._attrib_call("mark_epistasis", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
         return self._mark_run_epistasis("cf_mark_epistasis", bs, opts, names, book)
 
-    def mark_shapley_dataset(self, dataset, genes=None, players="marks", scale=0.0, epistasis=False, bsz=None, store=None):
-        """mark_shapley (and optionally mark_epistasis) over the genes of a ChromoformerDataset
+    @torch.no_grad()
+    def mark_shapley_interactions(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                                  interaction_freq=None, players="marks", scale=0.0, index="sii", return_coalitions=False):
+        """Pairwise Shapley interaction indices of the histone-mark players (cf_mark_shapley_interactions) -> (inter, info), tensors on
+        the model's device, no autograd graph.  At least 2 players; the 2^P coalitions run once, as in mark_shapley:
+
+          inter               [B, P, P, n_out], exactly symmetric.  Off the diagonal, with S over the coalitions that hold neither player,
+                              I_ij = sum_S w(|S|) ((v(S + i + j) - v(S + j)) - (v(S + i) - v(S))): how much i's marginal contribution
+                              changes with j present, averaged over every context -- negative for redundant players, positive for
+                              cooperating ones, also where a third player hides the effect from the full-coalition *_epistasis.  index "sii"
+                              (Shapley interaction index): w(s) = s! (P - s - 2)! / (P - 1)!, the diagonal is phi.  index "sti"
+                              (Shapley-Taylor, order 2): w(s) = (2 / P) / C(P - 1, s), the diagonal is v({i}) - v(nobody), and the
+                              diagonal plus the upper triangle sums to logits - erased.  A null player's row and column are exactly 0
+          info["phi"]         [B, P, n_out]: the Shapley values of mark_shapley on the same rows, bit for bit
+          info["logits"]      [B, n_out]: the prediction;  info["erased"]  [B, n_out]: every player absent
+          info["index"]       the index name;  info["delta"]  [B, n_out], "sti" only: the efficiency gap (rounding only)
+          info["players"]     the players' names
+          info["coalitions"]  [B, 2^P, n_out], with return_coalitions: the logits of every coalition, word m at column m
+
+        SHAP's interaction values follow from the sii result: Phi_ij = I_ij / 2 off the diagonal and Phi_ii = phi_i - sum_{j != i} I_ij / 2.
+        players and scale as in mark_coalitions.  The packed forms of the first argument and the effect on a pending backward() are
+        those of mark_coalitions."""
+        opts, _alive, names = self._mark_opts(players, scale)
+        bs, _keep, book = self._attrib_call("mark_shapley_interactions", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        return self._mark_run_interactions("cf_mark_shapley_interactions", bs, opts, names, "erased", book, index, return_coalitions)
+
+    def mark_shapley_dataset(self, dataset, genes=None, players="marks", scale=0.0, epistasis=False, bsz=None, store=None, interactions=None):
+        """mark_shapley (and optionally mark_epistasis, or mark_shapley_interactions in its place) over the genes of a ChromoformerDataset
         (chromoformer_amd.attribution.mark_shapley, a generator of per-gene dicts)."""
         from .attribution import mark_shapley
-        return mark_shapley(self, dataset, genes=genes, players=players, scale=scale, epistasis=epistasis, bsz=bsz, store=store)
+        return mark_shapley(self, dataset, genes=genes, players=players, scale=scale, epistasis=epistasis, bsz=bsz, store=store,
+                            interactions=interactions)
 
     def _mark_donor_opts(self, who, donor, players, B):
         """players (a mark_players spec) and the donor of a batch of B genes -> (cf_mark_donor_opts, what it points to, names).  donor:
@@ -1116,12 +1227,40 @@ class ChromoformerBase(nn.Module):
         opts, _alive, names = self._mark_donor_opts(who, donor, players, bs.B)
         return self._mark_run_epistasis("cf_mark_donor_epistasis", bs, opts, names, book)
 
-    def mark_donor_shapley_dataset(self, dataset, donor_dataset, genes=None, players="marks", epistasis=False, bsz=None, store=None, donor_store=None):
+    @torch.no_grad()
+    def mark_donor_shapley_interactions(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                                        interaction_freq=None, donor=None, players="marks", index="sii", return_coalitions=False):
+        """Pairwise Shapley interaction indices of the histone-mark players against a donor cell type
+        (cf_mark_donor_shapley_interactions) -> (inter, info), tensors on the model's device, no autograd graph.  At least 2 players;
+        the 2^P coalitions run once, as in mark_donor_shapley:
+
+          inter               [B, P, P, n_out], exactly symmetric.  Off the diagonal, with S over the coalitions that hold neither player,
+                              I_ij = sum_S w(|S|) ((v(S + i + j) - v(S + j)) - (v(S + i) - v(S))): how much i's marginal contribution
+                              changes with j present, averaged over every context -- negative for redundant players, positive for
+                              cooperating ones, also where a third player hides the effect from the full-coalition *_epistasis.  index "sii"
+                              (Shapley interaction index): w(s) = s! (P - s - 2)! / (P - 1)!, the diagonal is phi.  index "sti"
+                              (Shapley-Taylor, order 2): w(s) = (2 / P) / C(P - 1, s), the diagonal is v({i}) - v(nobody), and the
+                              diagonal plus the upper triangle sums to logits - donor.  A null player's row and column are exactly 0
+          info["phi"]         [B, P, n_out]: the Shapley values of mark_donor_shapley on the same rows, bit for bit
+          info["logits"]      [B, n_out]: the prediction;  info["donor"]  [B, n_out]: every player absent
+          info["index"]       the index name;  info["delta"]  [B, n_out], "sti" only: the efficiency gap (rounding only)
+          info["players"]     the players' names
+          info["coalitions"]  [B, 2^P, n_out], with return_coalitions: the logits of every coalition, word m at column m
+
+        SHAP's interaction values follow from the sii result: Phi_ij = I_ij / 2 off the diagonal and Phi_ii = phi_i - sum_{j != i} I_ij / 2.
+        donor and players as in mark_donor_coalitions; a player whose elements are the same in both cell types is a null player."""
+        who = "mark_donor_shapley_interactions"
+        bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        opts, _alive, names = self._mark_donor_opts(who, donor, players, bs.B)
+        return self._mark_run_interactions("cf_mark_donor_shapley_interactions", bs, opts, names, "donor", book, index, return_coalitions)
+
+    def mark_donor_shapley_dataset(self, dataset, donor_dataset, genes=None, players="marks", epistasis=False, bsz=None, store=None, donor_store=None,
+                                   interactions=None):
         """mark_donor_shapley (and optionally mark_donor_epistasis) over the genes of two ChromoformerDatasets, the gene's cell type
         and the donor's (chromoformer_amd.attribution.mark_donor_shapley, a generator of per-gene dicts)."""
         from .attribution import mark_donor_shapley
         return mark_donor_shapley(self, dataset, donor_dataset, genes=genes, players=players, epistasis=epistasis, bsz=bsz, store=store,
-                                  donor_store=donor_store)
+                                  donor_store=donor_store, interactions=interactions)
 
     def _mark_wide_opts(self, who, players, scale, donor, B):
         """players (a mark_players_wide spec), scale and donor (None: the scale rule; else the forms of _mark_donor_opts) for a batch of
@@ -1250,6 +1389,39 @@ class ChromoformerBase(nn.Module):
         return self._mark_run_shapley("cf_mark_window_shapley", bs, opts, names, "erased" if donor is None else "donor", book, return_coalitions)
 
     @torch.no_grad()
+    def mark_window_shapley_interactions(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
+                                         interaction_freq=None, players="promoter", width=1, scale=0.0, donor=None, flip=None, index="sii",
+                                         return_coalitions=False):
+        """Pairwise Shapley interaction indices of 2..16 window players (cf_mark_window_shapley_interactions) -> (inter, info),
+        tensors on the model's device, no autograd graph: which stretches are redundant, which cooperate?  The 2^P coalitions run once,
+        as in mark_window_shapley:
+
+          inter               [B, P, P, n_out], exactly symmetric.  Off the diagonal, with S over the coalitions that hold neither player,
+                              I_ij = sum_S w(|S|) ((v(S + i + j) - v(S + j)) - (v(S + i) - v(S))): how much i's marginal contribution
+                              changes with j present, averaged over every context -- negative for redundant players, positive for
+                              cooperating ones, also where a third player hides the effect from the full-coalition *_epistasis.  index "sii"
+                              (Shapley interaction index): w(s) = s! (P - s - 2)! / (P - 1)!, the diagonal is phi.  index "sti"
+                              (Shapley-Taylor, order 2): w(s) = (2 / P) / C(P - 1, s), the diagonal is v({i}) - v(nobody), and the
+                              diagonal plus the upper triangle sums to logits - erased.  A null player's row and column are exactly 0
+          info["phi"]         [B, P, n_out]: the Shapley values of mark_window_shapley on the same rows, bit for bit
+          info["logits"]      [B, n_out]: the prediction;  info["erased"]  [B, n_out]: every player absent
+          info["index"]       the index name;  info["delta"]  [B, n_out], "sti" only: the efficiency gap (rounding only)
+          info["players"]     the players' names
+          info["coalitions"]  [B, 2^P, n_out], with return_coalitions: the logits of every coalition, word m at column m
+
+        SHAP's interaction values follow from the sii result: Phi_ij = I_ij / 2 off the diagonal and Phi_ii = phi_i - sum_{j != i} I_ij / 2.
+        info["donor"] takes the place of info["erased"] with a donor.  players, width, scale, donor and flip as in
+        mark_window_coalitions; a window past the region's real bins and a player in a dummy slot are null players."""
+        who = "mark_window_shapley_interactions"
+        bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        opts, _alive, names = self._mark_window_opts(who, players, width, scale, donor, flip, bs.B)
+        P = opts.n_players
+        if P > 16:
+            raise ValueError("%s: %d players; the exact game takes 2..16 and the index has no sampled estimator: choose a larger width" % (who, P))
+        return self._mark_run_interactions("cf_mark_window_shapley_interactions", bs, opts, names, "erased" if donor is None else "donor", book,
+                                           index, return_coalitions)
+
+    @torch.no_grad()
     def mark_window_shapley_sampled(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
                                     interaction_freq=None, players="promoter", width=1, n_perm=64, seed=0, permutations=None, scale=0.0,
                                     donor=None, flip=None, return_rows=False):
@@ -1264,12 +1436,12 @@ class ChromoformerBase(nn.Module):
         return self._mark_run_sampled("cf_mark_window_shapley_sampled", bs, opts, names, perms, book, return_rows)
 
     def mark_window_shapley_dataset(self, dataset, donor_dataset=None, genes=None, players="promoter", width=1, n_perm=64, seed=0, scale=0.0,
-                                    bsz=None, store=None, donor_store=None):
+                                    bsz=None, store=None, donor_store=None, interactions=None):
         """Shapley values of window players over the genes of a ChromoformerDataset, against a donor cell type's dataset if one is
         given, windows in genomic coordinates (chromoformer_amd.attribution.mark_window_shapley, a generator of per-gene dicts)."""
         from .attribution import mark_window_shapley
         return mark_window_shapley(self, dataset, donor_dataset, genes=genes, players=players, width=width, n_perm=n_perm, seed=seed,
-                                   scale=scale, bsz=bsz, store=store, donor_store=donor_store)
+                                   scale=scale, bsz=bsz, store=store, donor_store=donor_store, interactions=interactions)
 
     def _mark_fine_opts(self, who, B, region, players, width, n_windows, start, lengths, scale, donor, flip):
         """The options of the fine window game for a batch of B genes -> (P, cf_mark_fine_opts, what it points to, names)."""
@@ -1361,6 +1533,44 @@ class ChromoformerBase(nn.Module):
         return phi, info
 
     @torch.no_grad()
+    def mark_fine_window_shapley_interactions(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None,
+                                              interaction_masks=None, interaction_freq=None, region=0, players="windows", width=1, n_windows=None,
+                                              start=0, lengths=None, scale=0.0, donor=None, flip=None, index="sii", return_coalitions=False,
+                                              return_feats=False):
+        """Pairwise Shapley interaction indices of 2..16 fine window players (cf_mark_fine_shapley_interactions) -> (inter, info),
+        tensors on the model's device, no autograd graph: which 200 bp stretches of the peak are redundant, which cooperate?  The 2^P
+        coalitions run once, as in mark_fine_window_shapley:
+
+          inter               [B, P, P, n_out], exactly symmetric.  Off the diagonal, with S over the coalitions that hold neither player,
+                              I_ij = sum_S w(|S|) ((v(S + i + j) - v(S + j)) - (v(S + i) - v(S))): how much i's marginal contribution
+                              changes with j present, averaged over every context -- negative for redundant players, positive for
+                              cooperating ones, also where a third player hides the effect from the full-coalition *_epistasis.  index "sii"
+                              (Shapley interaction index): w(s) = s! (P - s - 2)! / (P - 1)!, the diagonal is phi.  index "sti"
+                              (Shapley-Taylor, order 2): w(s) = (2 / P) / C(P - 1, s), the diagonal is v({i}) - v(nobody), and the
+                              diagonal plus the upper triangle sums to logits - erased.  A null player's row and column are exactly 0
+          info["phi"]         [B, P, n_out]: the Shapley values of mark_fine_window_shapley on the same rows, bit for bit
+          info["logits"]      [B, n_out]: the prediction;  info["erased"]  [B, n_out]: every player absent
+          info["index"]       the index name;  info["delta"]  [B, n_out], "sti" only: the efficiency gap (rounding only)
+          info["players"]     the players' names
+          info["coalitions"]  [B, 2^P, n_out], with return_coalitions: the logits of every coalition, word m at column m
+
+        SHAP's interaction values follow from the sii result: Phi_ij = I_ij / 2 off the diagonal and Phi_ii = phi_i - sum_{j != i} I_ij / 2.
+        info["donor"] takes the place of info["erased"] with a donor; info["feats"] with return_feats.  Everything else as in
+        mark_fine_window_shapley; a null player (a window past the region's real bins, a dummy slot, a donor that agrees with the gene
+        inside the window) has its row and column exactly 0."""
+        who = "mark_fine_window_shapley_interactions"
+        bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        P, opts, _alive, names = self._mark_fine_opts(who, bs.B, region, players, width, n_windows, start, lengths, scale, donor, flip)
+        if P > 16:
+            raise ValueError("%s: %d players; the exact game takes 2..16 and the index has no sampled estimator: choose a larger width" % (who, P))
+        feats = self._fine_feats(opts, bs.B, 1 << P) if return_feats else None
+        inter, info = self._mark_run_interactions("cf_mark_fine_shapley_interactions", bs, opts, names, "erased" if donor is None else "donor", book,
+                                                  index, return_coalitions)
+        if return_feats:
+            info["feats"] = feats
+        return inter, info
+
+    @torch.no_grad()
     def mark_fine_window_shapley_sampled(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
                                          interaction_freq=None, region=0, players="windows", width=1, n_windows=None, start=0, lengths=None,
                                          n_perm=64, seed=0, permutations=None, scale=0.0, donor=None, flip=None, return_rows=False,
@@ -1380,14 +1590,15 @@ class ChromoformerBase(nn.Module):
         return phi, info
 
     def mark_fine_window_shapley_dataset(self, dataset, donor_dataset=None, genes=None, region="promoter", zoom=1, coarse_width=1, width=2,
-                                         players="windows", n_perm=64, seed=0, scale=0.0, target=None, bsz=None, store=None, donor_store=None):
+                                         players="windows", n_perm=64, seed=0, scale=0.0, target=None, bsz=None, store=None, donor_store=None,
+                                         interactions=None):
         """Shapley values of fine window players over the genes of a ChromoformerDataset, zooming from the coarse window game, against a
         donor cell type's dataset if one is given, windows in genomic coordinates (chromoformer_amd.attribution.mark_fine_window_shapley,
         a generator of per-gene dicts)."""
         from .attribution import mark_fine_window_shapley
         return mark_fine_window_shapley(self, dataset, donor_dataset, genes=genes, region=region, zoom=zoom, coarse_width=coarse_width, width=width,
                                         players=players, n_perm=n_perm, seed=seed, scale=scale, target=target, bsz=bsz, store=store,
-                                        donor_store=donor_store)
+                                        donor_store=donor_store, interactions=interactions)
 
     def raw_signal_gradients(self, dataset, genes=None, target=None, times_input=False, bsz=None):
         """Raw-signal saliency of the genes of a ChromoformerDataset: the gradient (or gradient x input) of logit column `target` with

@@ -123,12 +123,14 @@ def write_pcre_ablation(model, store, bsz, path, regression=False):
     mm.flush()
 
 
-def write_pcre_coalition_values(model, store, bsz, shapley_out=None, epistasis_out=None, regression=False):
+def write_pcre_coalition_values(model, store, bsz, shapley_out=None, epistasis_out=None, regression=False, interactions_out=None, index="sii"):
     """Exact Shapley values and / or pair-deletion epistasis of the pCREs of every gene of a device-resident store, in store order,
     in LOGIT space of the prediction's column (1 for the classifier, 0 for the regressor: the efficiency identity
     phi.sum(1) = logits - promoter_only holds there, not after the sigmoid).  shapley_out: an .npz with phi [n_genes, i_max],
     logits [n_genes], promoter_only [n_genes] and n_pcres [n_genes] (the slots that are no dummies); epistasis_out: a float32 .npy
-    [n_genes, i_max, i_max].  Per batch: one device gather into a Slot, one model.pcre_shapley and / or one model.pcre_epistasis."""
+    [n_genes, i_max, i_max]; interactions_out: a float32 .npy [n_genes, i_max, i_max], the pairwise Shapley interaction index `index`
+    ("sii" / "sti").  Per batch: one device gather into a Slot, one model.pcre_shapley and / or one model.pcre_epistasis; with
+    interactions_out one model.pcre_shapley_interactions, which serves shapley_out too (the 2^i_max forwards run once)."""
     import ctypes as C
 
     from . import _lib
@@ -137,6 +139,7 @@ def write_pcre_coalition_values(model, store, bsz, shapley_out=None, epistasis_o
     phi, logits, alone = torch.empty(n, S), torch.empty(n), torch.empty(n)
     n_pcres = torch.empty(n, dtype=torch.int32)
     eps = np.lib.format.open_memmap(epistasis_out, mode="w+", dtype=np.float32, shape=(n, S, S)) if epistasis_out else None
+    inter = np.lib.format.open_memmap(interactions_out, mode="w+", dtype=np.float32, shape=(n, S, S)) if interactions_out else None
     struct = store.struct()
     order = torch.arange(n, dtype=torch.int32, device=dev)
     slots = {}
@@ -147,8 +150,13 @@ def write_pcre_coalition_values(model, store, bsz, shapley_out=None, epistasis_o
         cursor = torch.tensor([0, 1, 0, 0], dtype=torch.int32).to(dev)
         _lib.check(L.cf_gather_batch(model._handle, C.byref(struct), order[lo:].data_ptr(), cursor.data_ptr(), C.byref(slot.struct), None, st),
                    "cf_gather_batch")
-        if shapley_out:
+        if inter is not None:
+            x, info = model.pcre_shapley_interactions(slot, index=index)
+            inter[lo:lo + B] = x[..., t].cpu().numpy()
+            p = info["phi"]
+        elif shapley_out:
             p, info = model.pcre_shapley(slot)
+        if shapley_out:
             phi[lo:lo + B] = p[..., t].cpu()
             logits[lo:lo + B] = info["logits"][:, t].cpu()
             alone[lo:lo + B] = info["promoter_only"][:, t].cpu()
@@ -163,14 +171,18 @@ def write_pcre_coalition_values(model, store, bsz, shapley_out=None, epistasis_o
             np.savez(f, phi=phi.numpy(), logits=logits.numpy(), promoter_only=alone.numpy(), n_pcres=n_pcres.numpy())
     if eps is not None:
         eps.flush()
+    if inter is not None:
+        inter.flush()
 
 
-def write_mark_values(model, store, bsz, gene_ids, shapley_out=None, epistasis_out=None, regression=False, players="marks", scale=0.0):
+def write_mark_values(model, store, bsz, gene_ids, shapley_out=None, epistasis_out=None, regression=False, players="marks", scale=0.0,
+                      interactions_out=None, index="sii"):
     """Exact Shapley values and / or pair epistasis of the histone marks of every gene of a device-resident store, in store order, in
     LOGIT space of the prediction's column (1 for the classifier, 0 for the regressor: efficiency holds there, not after the
     sigmoid).  shapley_out: an .npz with gene_ids [n], players [P] (names), phi [n, P], logits [n] and erased [n] (phi sums to
-    their difference); epistasis_out: a float32 .npy [n, P, P].  Per batch: one device gather into a Slot, one model.mark_shapley
-    and / or one model.mark_epistasis."""
+    their difference); epistasis_out: a float32 .npy [n, P, P]; interactions_out: a float32 .npy [n, P, P], the pairwise Shapley
+    interaction index `index` ("sii" / "sti").  Per batch: one device gather into a Slot, one model.mark_shapley and / or one
+    model.mark_epistasis; with interactions_out one model.mark_shapley_interactions, which serves shapley_out too."""
     import ctypes as C
 
     from . import _lib
@@ -180,6 +192,7 @@ def write_mark_values(model, store, bsz, gene_ids, shapley_out=None, epistasis_o
     P, t = len(names), 0 if regression else 1
     phi, logits, erased = torch.empty(n, P), torch.empty(n), torch.empty(n)
     eps = np.lib.format.open_memmap(epistasis_out, mode="w+", dtype=np.float32, shape=(n, P, P)) if epistasis_out else None
+    inter = np.lib.format.open_memmap(interactions_out, mode="w+", dtype=np.float32, shape=(n, P, P)) if interactions_out else None
     struct = store.struct()
     order = torch.arange(n, dtype=torch.int32, device=dev)
     slots = {}
@@ -190,8 +203,13 @@ def write_mark_values(model, store, bsz, gene_ids, shapley_out=None, epistasis_o
         cursor = torch.tensor([0, 1, 0, 0], dtype=torch.int32).to(dev)
         _lib.check(L.cf_gather_batch(model._handle, C.byref(struct), order[lo:].data_ptr(), cursor.data_ptr(), C.byref(slot.struct), None, st),
                    "cf_gather_batch")
-        if shapley_out:
+        if inter is not None:
+            x, info = model.mark_shapley_interactions(slot, players=players, scale=scale, index=index)
+            inter[lo:lo + B] = x[..., t].cpu().numpy()
+            p = info["phi"]
+        elif shapley_out:
             p, info = model.mark_shapley(slot, players=players, scale=scale)
+        if shapley_out:
             phi[lo:lo + B] = p[..., t].cpu()
             logits[lo:lo + B] = info["logits"][:, t].cpu()
             erased[lo:lo + B] = info["erased"][:, t].cpu()
@@ -204,15 +222,20 @@ def write_mark_values(model, store, bsz, gene_ids, shapley_out=None, epistasis_o
             np.savez(f, gene_ids=np.array(list(gene_ids)), players=np.array(names), phi=phi.numpy(), logits=logits.numpy(), erased=erased.numpy())
     if eps is not None:
         eps.flush()
+    if inter is not None:
+        inter.flush()
 
 
-def write_mark_donor_values(model, store, donor_store, bsz, gene_ids, shapley_out=None, epistasis_out=None, regression=False, players="marks"):
+def write_mark_donor_values(model, store, donor_store, bsz, gene_ids, shapley_out=None, epistasis_out=None, regression=False, players="marks",
+                            interactions_out=None, index="sii"):
     """Exact Shapley values and / or pair epistasis of the histone marks against a donor cell type, for every gene of two
     device-resident stores that hold the same genes in the same order, in LOGIT space of the prediction's column.  shapley_out: an .npz
     with gene_ids [n], players [P] (names), phi [n, P], logits [n], donor [n] (every player's marks from the donor, under the gene's
     masks and frequencies; phi sums to logits - donor) and donor_prediction [n] (the plain forward of the donor's own batch);
-    epistasis_out: a float32 .npy [n, P, P].  Per batch: one gather per store, one model.mark_donor_shapley and / or one
-    model.mark_donor_epistasis, one plain forward of the donor's batch."""
+    epistasis_out: a float32 .npy [n, P, P]; interactions_out: a float32 .npy [n, P, P], the pairwise Shapley interaction index
+    `index` ("sii" / "sti").  Per batch: one gather per store, one model.mark_donor_shapley and / or one model.mark_donor_epistasis,
+    one plain forward of the donor's batch; with interactions_out one model.mark_donor_shapley_interactions, which serves shapley_out
+    too."""
     from .attribution import _BATCH_KEYS, _donor_pair, mark_players
     n = len(store)
     if len(donor_store) != n:
@@ -221,14 +244,20 @@ def write_mark_donor_values(model, store, donor_store, bsz, gene_ids, shapley_ou
     P, t = len(names), 0 if regression else 1
     phi, logits, donor, pred = torch.empty(n, P), torch.empty(n), torch.empty(n), torch.empty(n)
     eps = np.lib.format.open_memmap(epistasis_out, mode="w+", dtype=np.float32, shape=(n, P, P)) if epistasis_out else None
+    inter = np.lib.format.open_memmap(interactions_out, mode="w+", dtype=np.float32, shape=(n, P, P)) if interactions_out else None
     for lo in range(0, n, bsz):
         B = min(bsz, n - lo)
         idx = list(range(lo, lo + B))
         d, dd = store.batch(idx), donor_store.batch(idx)
         args = tuple(d[k] for k in _BATCH_KEYS)
         feats = _donor_pair(dd)
-        if shapley_out:
+        if inter is not None:
+            x, info = model.mark_donor_shapley_interactions(*args, donor=feats, players=players, index=index)
+            inter[lo:lo + B] = x[..., t].cpu().numpy()
+            p = info["phi"]
+        elif shapley_out:
             p, info = model.mark_donor_shapley(*args, donor=feats, players=players)
+        if shapley_out:
             phi[lo:lo + B] = p[..., t].cpu()
             logits[lo:lo + B] = info["logits"][:, t].cpu()
             donor[lo:lo + B] = info["donor"][:, t].cpu()
@@ -242,6 +271,8 @@ def write_mark_donor_values(model, store, donor_store, bsz, gene_ids, shapley_ou
                      donor_prediction=pred.numpy())
     if eps is not None:
         eps.flush()
+    if inter is not None:
+        inter.flush()
 
 
 def write_mark_sampled_values(model, store, donor_store, bsz, gene_ids, path, regression=False, players="cells", n_perm=64, seed=0, scale=0.0):
@@ -562,7 +593,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
             window_perms=64, window_seed=0, window_scale=0.0, raw_donor_ig_dir=None, fine_scan_out=None, fine_scan_region="promoter",
             fine_scan_width=1, fine_scan_stride=None, fine_scan_zoom=None, fine_scan_scale=0.0, fine_window_shapley_out=None,
             fine_window_donor_shapley_out=None, fine_window_region="promoter", fine_window_width=2, fine_window_players="windows",
-            fine_window_zoom=1, fine_window_perms=64, fine_window_seed=0, fine_window_scale=0.0):
+            fine_window_zoom=1, fine_window_perms=64, fine_window_seed=0, fine_window_scale=0.0, pcre_interactions_out=None,
+            mark_interactions_out=None, mark_donor_interactions_out=None, interaction_index="sii"):
     """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file.  attention_dir / embeddings_out: also
     write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps); pcre_ablation_out:
     the predictions with each pCRE deleted (write_pcre_ablation); ig_dir: integrated gradients of every gene
@@ -588,7 +620,12 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     fine_scan_width, fine_scan_stride, fine_scan_zoom and fine_scan_scale apply; served by a packed store as well);
     fine_window_shapley_out / fine_window_donor_shapley_out: Shapley values of fine window players inside each gene's most important
     coarse windows, under the scale rule (fine_window_scale applies) / against the donor (write_mark_fine_window_values;
-    fine_window_region, fine_window_width, fine_window_players, fine_window_zoom, fine_window_perms and fine_window_seed apply)."""
+    fine_window_region, fine_window_width, fine_window_players, fine_window_zoom, fine_window_perms and fine_window_seed apply);
+    pcre_interactions_out / mark_interactions_out / mark_donor_interactions_out: the pairwise Shapley interaction index
+    interaction_index ("sii" / "sti") of the pCREs / the histone marks / the marks against the donor, a float32 .npy [n_genes, P, P] in
+    logit space, by the writers of the Shapley values of the same game (one interactions call serves both outputs)."""
+    from .attribution import interaction_index as _index_check
+    _index_check(interaction_index, "predict")      # (before anything is computed)
     seed_everything(seed)
     meta = pd.read_csv(meta_path)
     genes = meta.gene_id.tolist()
@@ -598,7 +635,7 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         require_raw_signals(raw_ds)      # (before anything is computed)
     from . import pack
     donor_out = (mark_donor_shapley_out or mark_donor_epistasis_out or mark_donor_sampled_shapley_out or window_donor_shapley_out
-                 or fine_window_donor_shapley_out)
+                 or fine_window_donor_shapley_out or mark_donor_interactions_out)
     raw_donor_ds = None
     if raw_donor_ig_dir:      # (before anything is computed)
         from .attribution import same_regions
@@ -621,7 +658,7 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         from .attribution import same_regions
         if not donor_npy_dir:
             raise ValueError("predict: mark_donor_shapley_out / mark_donor_epistasis_out / mark_donor_sampled_shapley_out / "
-                             "window_donor_shapley_out / fine_window_donor_shapley_out need donor_npy_dir")
+                             "window_donor_shapley_out / fine_window_donor_shapley_out / mark_donor_interactions_out need donor_npy_dir")
         donor_ds = ChromoformerDataset(donor_meta or meta_path, donor_npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False)
         same_regions(ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False), donor_ds)
     packed = pack.find(npy_dir, store_path, list(binsizes), i_max, w_prom, w_max, 7, genes, meta=meta)
@@ -645,16 +682,18 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     write_attention_maps(model, store, bsz, attention_dir, embeddings_out)
     if pcre_ablation_out:
         write_pcre_ablation(model, store, bsz, pcre_ablation_out, regression)
-    if pcre_shapley_out or pcre_epistasis_out:
-        write_pcre_coalition_values(model, store, bsz, pcre_shapley_out, pcre_epistasis_out, regression)
-    if mark_shapley_out or mark_epistasis_out:
-        write_mark_values(model, store, bsz, genes, mark_shapley_out, mark_epistasis_out, regression, mark_players, mark_scale)
+    if pcre_shapley_out or pcre_epistasis_out or pcre_interactions_out:
+        write_pcre_coalition_values(model, store, bsz, pcre_shapley_out, pcre_epistasis_out, regression, pcre_interactions_out, interaction_index)
+    if mark_shapley_out or mark_epistasis_out or mark_interactions_out:
+        write_mark_values(model, store, bsz, genes, mark_shapley_out, mark_epistasis_out, regression, mark_players, mark_scale,
+                          mark_interactions_out, interaction_index)
     if donor_out:
         donor_packed = pack.find(donor_npy_dir, donor_store_path, list(binsizes), i_max, w_prom, w_max, 7, genes, meta=donor_ds.meta)
         donor_store = (donor_packed.store(genes, device=dev, regression=False) if donor_packed is not None
                        else GeneStore(donor_ds, progress=progress, device=dev, resident=True))
-        if mark_donor_shapley_out or mark_donor_epistasis_out:
-            write_mark_donor_values(model, store, donor_store, bsz, genes, mark_donor_shapley_out, mark_donor_epistasis_out, regression, mark_players)
+        if mark_donor_shapley_out or mark_donor_epistasis_out or mark_donor_interactions_out:
+            write_mark_donor_values(model, store, donor_store, bsz, genes, mark_donor_shapley_out, mark_donor_epistasis_out, regression, mark_players,
+                                    mark_donor_interactions_out, interaction_index)
         if mark_donor_sampled_shapley_out:
             write_mark_sampled_values(model, store, donor_store, bsz, genes, mark_donor_sampled_shapley_out, regression, mark_sampled_players,
                                       mark_perms, mark_seed)
@@ -712,6 +751,15 @@ def build_parser():
                     "(0 for dummy slots), logits, promoter_only (phi sums to their difference) and n_pcres (model.pcre_shapley)")
     ap.add_argument("--pcre-epistasis-out", default=None, help="also write the pair-deletion epistasis of the pCREs to this .npy file: "
                     "[n_genes, i_max, i_max] in logit space, symmetric, the leave-one-out effects on the diagonal (model.pcre_epistasis)")
+    from .attribution import INTERACTION_INDICES
+    ap.add_argument("--pcre-interactions-out", default=None, help="also write the pairwise Shapley interaction index of the pCREs to this .npy "
+                    "file: [n_genes, i_max, i_max] in logit space, symmetric, how much one pCRE's marginal contribution changes with the other "
+                    "present, averaged over every coalition of the rest (negative: redundant, positive: cooperating); the diagonal as "
+                    "--interaction-index says (model.pcre_shapley_interactions)")
+    ap.add_argument("--interaction-index", default=None, choices=INTERACTION_INDICES, help="the index of --pcre-interactions-out / "
+                    "--mark-interactions-out / --mark-donor-interactions-out: sii, the Shapley interaction index, the Shapley values on the "
+                    "diagonal (default), or sti, Shapley-Taylor of order 2, v({i}) - v(nobody) on the diagonal (diagonal and upper triangle then "
+                    "sum to the prediction's logit minus every player absent)")
     from .attribution import METHODS
     ap.add_argument("--ig-dir", default=None, help="also write integrated gradients (zero baseline, every float input) of every gene, in "
                     "metadata order, as DIR/promoter_feats_{binsize}.npy [n, L, F], DIR/pcre_feats_{binsize}.npy [n, i_max, L, F], "
@@ -754,6 +802,9 @@ def build_parser():
                     "erased (every player absent; phi sums to their difference) (model.mark_shapley)")
     ap.add_argument("--mark-epistasis-out", default=None, help="also write the pair epistasis of the histone marks to this .npy file: "
                     "[n_genes, P, P] in logit space, symmetric, the leave-one-out effects on the diagonal (model.mark_epistasis)")
+    ap.add_argument("--mark-interactions-out", default=None, help="also write the pairwise Shapley interaction index of the histone marks to "
+                    "this .npy file: [n_genes, P, P] in logit space, symmetric (model.mark_shapley_interactions).  --mark-players, --mark-scale "
+                    "and --interaction-index apply")
     ap.add_argument("--mark-players", default=None, choices=MARK_PLAYER_SPECS, help="the players of --mark-shapley-out / --mark-epistasis-out: "
                     "each mark in every region (marks, the default), each mark in the promoter and in the pCREs (compartments), or all marks "
                     "per region (regions)")
@@ -775,6 +826,9 @@ def build_parser():
     ap.add_argument("--mark-donor-epistasis-out", default=None, help="also write the pair epistasis of the histone marks against the donor cell "
                     "type to this .npy file: [n_genes, P, P] in logit space, symmetric, the leave-one-out effects on the diagonal "
                     "(model.mark_donor_epistasis).  --mark-players applies")
+    ap.add_argument("--mark-donor-interactions-out", default=None, help="also write the pairwise Shapley interaction index of the histone marks "
+                    "against the donor cell type to this .npy file: [n_genes, P, P] in logit space, symmetric "
+                    "(model.mark_donor_shapley_interactions).  --mark-players and --interaction-index apply")
     from .attribution import MARK_WIDE_PLAYER_SPECS
     ap.add_argument("--mark-sampled-shapley-out", default=None, help="also write permutation-SAMPLED Shapley values of up to 128 histone-mark "
                     "players to this .npz file, in metadata order and in LOGIT space of the prediction's column: gene_ids, players (names), "
@@ -857,7 +911,9 @@ def main(argv=None):
     for name, v in (("width", args.fine_scan_width), ("stride", args.fine_scan_stride), ("zoom", args.fine_scan_zoom)):
         if v is not None and v < 1:
             ap.error("--fine-scan-%s must be at least 1" % name)
-    donor_exact = args.mark_donor_shapley_out or args.mark_donor_epistasis_out
+    donor_exact = args.mark_donor_shapley_out or args.mark_donor_epistasis_out or args.mark_donor_interactions_out
+    if args.interaction_index is not None and not (args.pcre_interactions_out or args.mark_interactions_out or args.mark_donor_interactions_out):
+        ap.error("--interaction-index needs --pcre-interactions-out, --mark-interactions-out or --mark-donor-interactions-out")
     donor_out = donor_exact or args.mark_donor_sampled_shapley_out or args.window_donor_shapley_out or args.fine_window_donor_shapley_out
     if args.raw_donor_ig_dir and not args.donor_npy_dir:
         ap.error("--raw-donor-ig-dir needs --donor-npy-dir")
@@ -866,7 +922,7 @@ def main(argv=None):
     sampled_out = args.mark_sampled_shapley_out or args.mark_donor_sampled_shapley_out
     if donor_out and not args.donor_npy_dir:
         ap.error("--mark-donor-shapley-out / --mark-donor-epistasis-out / --mark-donor-sampled-shapley-out / --window-donor-shapley-out / "
-                 "--fine-window-donor-shapley-out need --donor-npy-dir")
+                 "--fine-window-donor-shapley-out / --mark-donor-interactions-out need --donor-npy-dir")
     if not donor_out and not args.raw_donor_ig_dir and (args.donor_npy_dir or args.donor_meta or args.donor_store):
         ap.error("--donor-npy-dir / --donor-meta / --donor-store need --mark-donor-shapley-out, --mark-donor-epistasis-out or "
                  "--mark-donor-sampled-shapley-out (or --window-donor-shapley-out, --fine-window-donor-shapley-out)")
@@ -874,9 +930,9 @@ def main(argv=None):
         ap.error("--mark-sampled-players / --mark-perms / --mark-seed need --mark-sampled-shapley-out or --mark-donor-sampled-shapley-out")
     if args.mark_perms is not None and args.mark_perms < 1:
         ap.error("--mark-perms must be at least 1")
-    if not args.mark_shapley_out and not args.mark_epistasis_out and ((args.mark_scale is not None and not args.mark_sampled_shapley_out)
-                                                                      or (args.mark_players is not None and not donor_exact)):
-        ap.error("--mark-players / --mark-scale need --mark-shapley-out or --mark-epistasis-out"
+    if not args.mark_shapley_out and not args.mark_epistasis_out and not args.mark_interactions_out and ((args.mark_scale is not None and not args.mark_sampled_shapley_out)
+                                                                                                         or (args.mark_players is not None and not donor_exact)):
+        ap.error("--mark-players / --mark-scale need --mark-shapley-out, --mark-epistasis-out or --mark-interactions-out"
                  " (--mark-players also applies to --mark-donor-shapley-out / --mark-donor-epistasis-out, --mark-scale to"
                  " --mark-sampled-shapley-out)")
     if args.mark_scale is not None and not (args.mark_scale >= 0 and np.isfinite(args.mark_scale)):
@@ -952,7 +1008,9 @@ def main(argv=None):
                          fine_window_zoom=1 if args.fine_window_zoom is None else args.fine_window_zoom,
                          fine_window_perms=64 if args.fine_window_perms is None else args.fine_window_perms,
                          fine_window_seed=0 if args.fine_window_seed is None else args.fine_window_seed,
-                         fine_window_scale=0.0 if args.fine_window_scale is None else args.fine_window_scale)
+                         fine_window_scale=0.0 if args.fine_window_scale is None else args.fine_window_scale,
+                         pcre_interactions_out=args.pcre_interactions_out, mark_interactions_out=args.mark_interactions_out,
+                         mark_donor_interactions_out=args.mark_donor_interactions_out, interaction_index=args.interaction_index or "sii")
     print("Predicting expressions for %d genes." % len(meta))
     meta["prediction"] = pred
     meta.to_csv(args.output, index=False)

@@ -244,6 +244,31 @@ int cf_pcre_shapley(cf_handle* h, const cf_batch* batch, float* phi, float* logi
  * eps [B, S, S, n_out]; rows and columns of dummy slots are exactly 0.  logits_pairs: [B, 1 + S + S (S - 1) / 2, n_out], or NULL (a
  * handle-owned buffer, as above).  fwd = that of cf_pcre_coalitions with that n_coal, plus 1.  Refusals as above (null eps). */
 int cf_pcre_epistasis(cf_handle* h, const cf_batch* batch, float* eps, float* logits_pairs, void* stream);
+/* Pairwise Shapley interaction indices of the players of an exact game (interpretation): a second reduction of the [B, 2^P, n_out]
+ * table the Shapley entry points reduce with k_shapley (word m at column m).  For players i != j, S running over the coalitions that
+ * hold neither, per output column:
+ *   delta_ij(S)    = (v(S + i + j) - v(S + j)) - (v(S + i) - v(S))      i's marginal contribution with j present, minus that with j absent
+ *   inter[b, i, j] = sum_S w(|S|) delta_ij(S)
+ * `index` selects the weight table alone (computed on the host in double, rounded to fp32, passed by value):
+ *   CF_INTERACTION_SII  w(s) = s! (P - s - 2)! / (P - 1)!    the Shapley interaction index; inter[b, i, i] = phi[b, i], the bits of k_shapley
+ *   CF_INTERACTION_STI  w(s) = (2 / P) / C(P - 1, s)         Shapley-Taylor, order 2; inter[b, i, i] = v({i}) - v(0), one fp32 subtraction,
+ *                                                            and sum_i inter[i, i] + sum_{i<j} inter[i, j] = v(N) - v(0) up to rounding
+ * One k_shapley_pairs: a workgroup per (gene, pair i <= j), every operation rounded to fp32 (no contraction) in the grouping written
+ * above, a thread's subsets in ascending stride, then a fixed tree: deterministic, no atomics; inter[b, j, i] carries the bits of
+ * inter[b, i, j].  The grouping is part of the definition: delta is exactly 0 when either player is null (its rows bit-equal present
+ * and absent), so a null player's row and column are exact zeros; at P = 2 the off-diagonal entry agrees with *_epistasis within
+ * rounding, not bit for bit (k_epistasis groups differently).  inter [B, P, P, n_out].
+ * cf_shapley_interactions_from_rows: the operator on a caller's device table rows [B, 2^P, n_out] (for instance a kept logits_all): no
+ * batch, no workspace, no activation is touched; n_out is the handle's.  cf_launch_counts fwd = 1.  Refused by name, before anything is
+ * launched: a null handle / rows / inter, B < 1, P outside 2..16, an index other than the two constants. */
+#define CF_INTERACTION_SII 0
+#define CF_INTERACTION_STI 1
+int cf_shapley_interactions_from_rows(cf_handle* h, const float* rows, int B, int P, int index, float* inter, void* stream);
+/* cf_pcre_shapley's rows (S = i_max players, all 2^S coalitions through the same routine, logits_all as there), then k_shapley_pairs;
+ * phi [B, S, n_out] is optional: if given, k_shapley runs on the same rows too.  fwd = that of cf_pcre_coalitions with n_coal = 2^S, plus
+ * 1 per reducer launched (1, or 2 with phi).  Refused by name, before anything is launched: what cf_pcre_shapley refuses (phi may be
+ * null), a null inter, an index other than the two constants, i_max < 2. */
+int cf_pcre_shapley_interactions(cf_handle* h, const cf_batch* batch, int index, float* inter, float* phi, float* logits_all, void* stream);
 /* Integrated gradients (interpretation).  For the target logit column t, nodes a_k and weights w_k (k < n_steps) on [0, 1], per
  * interpolated input x with baseline xb (T = i_max + 1):
  *   x_k   = xb + a_k (x - xb)                         fp32, each operation rounded
@@ -493,6 +518,13 @@ int cf_mark_shapley(cf_handle* h, const cf_batch* batch, const cf_mark_opts* opt
  * eps [B, P, P, n_out].  logits_pairs: [B, 1 + P + P (P - 1) / 2, n_out], or NULL (the handle-owned buffer).  fwd = that of
  * cf_mark_coalitions with that n_coal, plus 1.  Refusals as above (null eps). */
 int cf_mark_epistasis(cf_handle* h, const cf_batch* batch, const cf_mark_opts* opts, float* eps, float* logits_pairs, void* stream);
+/* Pairwise Shapley interaction indices of the P players (see cf_shapley_interactions_from_rows): cf_mark_shapley's rows (all 2^P
+ * coalitions, logits_all as there), then k_shapley_pairs; phi [B, P, n_out] is optional: if given, k_shapley runs on the same rows too.
+ * inter [B, P, P, n_out].  fwd = that of cf_mark_coalitions with n_coal = 2^P, plus 1 per reducer launched (1, or 2 with phi).
+ * Refused by name, before anything is launched: what cf_mark_shapley refuses (phi may be null), a null inter, an index other than the
+ * two constants, n_players < 2. */
+int cf_mark_shapley_interactions(cf_handle* h, const cf_batch* batch, const cf_mark_opts* opts, int index, float* inter, float* phi,
+                                 float* logits_all, void* stream);
 /* The same game against a DONOR (interpretation): gene G is predicted on in one cell type and off in another -- which mark changes
  * account for the difference?  Players, coalition words and gone(rho) are those of cf_mark_coalitions; the caller passes, beside the
  * batch, the same B genes' features in the other cell type, and every element of region rho (every row, every resolution, padded rows
@@ -524,6 +556,11 @@ int cf_mark_donor_coalitions(cf_handle* h, const cf_batch* batch, const cf_mark_
 int cf_mark_donor_shapley(cf_handle* h, const cf_batch* batch, const cf_mark_donor_opts* opts, float* phi, float* logits_all, void* stream);
 /* cf_mark_epistasis with the donor rule: eps [B, P, P, n_out], rows, logits_pairs and fwd as there.  Refusals as above (null eps). */
 int cf_mark_donor_epistasis(cf_handle* h, const cf_batch* batch, const cf_mark_donor_opts* opts, float* eps, float* logits_pairs, void* stream);
+/* cf_mark_shapley_interactions with the donor rule: cf_mark_donor_shapley's rows, then k_shapley_pairs (and k_shapley with phi); a
+ * player whose elements carry the same bits in both feature sets is a null player: its row and column of inter are exactly 0.  fwd
+ * and refusals as there, with cf_mark_donor_shapley's in place of cf_mark_shapley's. */
+int cf_mark_donor_shapley_interactions(cf_handle* h, const cf_batch* batch, const cf_mark_donor_opts* opts, int index, float* inter, float* phi,
+                                       float* logits_all, void* stream);
 /* The same game over up to 128 players (interpretation): which mark matters at which region?  "Mark f in region rho" is
  * n_feats * (i_max + 1) players -- 63 on the default model, 119 at i_max = 16 -- more than one word holds and far more than 2^P rows
  * can enumerate.  Players, gone(rho), the scale rule and the donor rule are exactly those above; a coalition is kw = ceil(P / 32)
@@ -614,6 +651,13 @@ int cf_mark_window_coalitions(cf_handle* h, const cf_batch* batch, const cf_mark
  * of cf_mark_shapley.  phi [B, P, n_out]; logits_all [B, 2^P, n_out] or NULL (the handle-owned buffer).  A null player's phi is
  * exactly 0.  fwd = that of cf_mark_window_coalitions with n_coal = 2^P, plus 1.  Refusals as above (null phi, n_players > 16). */
 int cf_mark_window_shapley(cf_handle* h, const cf_batch* batch, const cf_mark_window_opts* opts, float* phi, float* logits_all, void* stream);
+/* Pairwise Shapley interaction indices of P <= 16 window players (see cf_shapley_interactions_from_rows): cf_mark_window_shapley's
+ * rows, then k_shapley_pairs (and k_shapley with the optional phi).  inter [B, P, P, n_out]; a null player's row and column are exactly
+ * 0.  fwd = that of cf_mark_window_coalitions with n_coal = 2^P, plus 1 per reducer launched (1, or 2 with phi).  Refused by name,
+ * before anything is launched: what cf_mark_window_shapley refuses (phi may be null), a null inter, an index other than the two
+ * constants, n_players < 2. */
+int cf_mark_window_shapley_interactions(cf_handle* h, const cf_batch* batch, const cf_mark_window_opts* opts, int index, float* inter, float* phi,
+                                        float* logits_all, void* stream);
 /* Permutation-sampled Shapley values of the window players: perms, the R = 2 + n_perm * (P - 1) rows per gene, k_perm_shapley, phi, the
  * optional se and logits_rows and the launch count are those of cf_mark_shapley_sampled; a null player's phi and se are exactly 0.
  * Refusals as above and as there. */
@@ -678,6 +722,13 @@ int cf_mark_fine_coalitions(cf_handle* h, const cf_batch* batch, const cf_mark_f
  * handle-owned buffer).  A null player's phi is exactly 0.  fwd = that of cf_mark_fine_coalitions with n_coal = 2^P, plus 1.
  * Refusals as above (null phi, n_players > 16). */
 int cf_mark_fine_shapley(cf_handle* h, const cf_batch* batch, const cf_mark_fine_opts* opts, float* phi, float* logits_all, void* stream);
+/* Pairwise Shapley interaction indices of P <= 16 fine window players (see cf_shapley_interactions_from_rows): cf_mark_fine_shapley's
+ * rows (feats_out, if given, [B, 2^P, ...]), then k_shapley_pairs (and k_shapley with the optional phi).  inter [B, P, P, n_out]; a null
+ * player's row and column are exactly 0.  fwd = that of cf_mark_fine_coalitions with n_coal = 2^P, plus 1 per reducer launched (1, or 2
+ * with phi).  Refused by name, before anything is launched: what cf_mark_fine_shapley refuses (phi may be null), a null inter, an index
+ * other than the two constants, n_players < 2. */
+int cf_mark_fine_shapley_interactions(cf_handle* h, const cf_batch* batch, const cf_mark_fine_opts* opts, int index, float* inter, float* phi,
+                                      float* logits_all, void* stream);
 /* Permutation-sampled Shapley values of the fine window players: perms, the R = 2 + n_perm * (P - 1) rows per gene, k_perm_shapley,
  * phi, the optional se and logits_rows and the launch count are those of cf_mark_shapley_sampled; a null player's phi and se are
  * exactly 0.  Refusals as above and as there. */
