@@ -218,6 +218,14 @@ SYMBOLS = {
                                       C.c_void_p, C.c_void_p]),
     "cf_mark_fine_shapley_sampled": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_fine_opts), C.c_void_p, C.c_int, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cf_mark_shapley_interactions_sampled": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_wide_opts), C.c_void_p, C.c_int, C.c_void_p,
+                                                       C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "cf_mark_window_shapley_interactions_sampled": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_window_opts), C.c_void_p, C.c_int,
+                                                              C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "cf_mark_fine_shapley_interactions_sampled": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_fine_opts), C.c_void_p, C.c_int,
+                                                            C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "cf_perm_interactions_from_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
+                                       + [C.c_void_p] * 5),
     "cf_adamw_step":(C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_longlong, C.c_void_p]),
     "cf_debug_copy": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p]),
     "cf_debug_names": (C.c_char_p, [C.c_void_p]),

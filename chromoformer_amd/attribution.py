@@ -221,6 +221,103 @@ def shapley_permutations(P, n_perm, seed=0):
     return np.stack([rng.permutation(P) for _ in range(n_perm)]).astype(np.uint8)
 
 
+def focal_players(focal, names, P):
+    """The focal players of a sampled interactions call -> int32 [n_focal]: `focal` is a sequence of player indices or of player names
+    (entries of `names`), or one of either.  An empty sequence, an unknown name, an index outside 0..P-1 or a repeated player raise
+    ValueError naming focal_players."""
+    P = int(P)
+    if isinstance(focal, (str, int, np.integer)):
+        focal = [focal]
+    try:
+        given = list(focal.tolist() if hasattr(focal, "tolist") else focal)
+    except TypeError:
+        given = []
+    if not given:
+        raise ValueError("focal_players: focal must name at least one player (indices or names)")
+    out = []
+    for at, x in enumerate(given):
+        if isinstance(x, str):
+            if names is None or x not in names:
+                raise ValueError("focal_players: focal[%d] = %r is not a player name" % (at, x))
+            x = list(names).index(x)
+        elif isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+            raise ValueError("focal_players: focal[%d] = %r is neither a player index nor a player name" % (at, x))
+        x = int(x)
+        if not 0 <= x < P:
+            raise ValueError("focal_players: focal[%d] = %d outside 0..%d" % (at, x, P - 1))
+        if x in out:
+            raise ValueError("focal_players: focal[%d] = %d repeats focal[%d]" % (at, x, out.index(x)))
+        out.append(x)
+    return np.array(out, dtype=np.int32)
+
+
+def focal_row_count(perms, focal):
+    """The rows per gene of focal_words(perms, focal) without building them: 2 + n_perm (P - 1) shared with mark_shapley_sampled, then
+    per focal player 2 + sum over the orders of P - 2 (the player first or last in the order) or P - 3 (elsewhere)."""
+    perms = np.asarray(perms)
+    n_perm, P = perms.shape
+    R = 2 + n_perm * (P - 1)
+    for i in focal:
+        r = np.argmax(perms == int(i), axis=1)
+        ends = int(((r == 0) | (r == P - 1)).sum())
+        R += 2 + ends * (P - 2) + (n_perm - ends) * (P - 3)
+    return int(R)
+
+
+def focal_words(perms, focal):
+    """The rows of a sampled interactions call (ChromoformerBase.mark_shapley_interactions_sampled) -> (words, col).  perms: integer
+    [n_perm, P], each row an order of the P >= 2 players; focal: distinct player indices.  words: the R coalitions as Python ints (bit p
+    set: player p present) in row order -- nobody, everybody, per order q its first k = 1 .. P - 1 players (mark_shapley_sampled's
+    table), then per focal player i: {i} alone, everybody but i, and per order, with o the order without i, T_k its first k players and
+    r the position of i in the order, the rows T_k + i for k = 1 .. r - 1, then the rows T_k for k = r + 1 .. P - 2 (the others are
+    prefixes of the order itself).  col: uint32 [n_focal, n_perm, P, 2], col[f, q, k, 0] the row of T_k and col[f, q, k, 1] that of
+    T_k + i, k = 0 .. P - 1: what the library's reducer reads.  Where a set is a prefix of the order, col names that leading row ({i}
+    alone for an order that starts with i, everybody but i for one that ends with it, too).  Focal player f's own rows start at row
+    focal_row_count(perms, focal[:f])."""
+    perms = np.asarray(perms)
+    if perms.ndim != 2 or perms.shape[1] < 2 or perms.dtype.kind not in "iu":
+        raise ValueError("focal_words: perms must be an integer array [n_perm, P >= 2]")
+    n_perm, P = perms.shape
+    for q in range(n_perm):
+        if sorted(int(x) for x in perms[q]) != list(range(P)):
+            raise ValueError("focal_words: perms[%d] is not a permutation of 0..%d" % (q, P - 1))
+    focal = focal_players(focal, None, P)
+    full = (1 << P) - 1
+    words = [0, full]
+    for q in range(n_perm):
+        m = 0
+        for k in range(1, P):
+            m |= 1 << int(perms[q, k - 1])
+            words.append(m)
+    col = np.zeros((len(focal), n_perm, P, 2), dtype=np.uint32)
+    for f, i in enumerate(int(x) for x in focal):
+        alone, without = len(words), len(words) + 1
+        words += [1 << i, full & ~(1 << i)]
+        for q in range(n_perm):
+            pi = [int(x) for x in perms[q]]
+            r = pi.index(i)
+            prefix = lambda k: 2 + q * (P - 1) + (k - 1)      # noqa: E731 (the first k of pi, 1 <= k <= P - 1)
+            col[f, q, 0] = (0, prefix(1) if r == 0 else alone)      # (a prefix of the order where there is one)
+            col[f, q, P - 1] = (prefix(P - 1) if r == P - 1 else without, 1)
+            m = 1 << i
+            for k in range(1, P - 1):      # T_k + i
+                if k < r:
+                    m |= 1 << pi[k - 1]
+                    col[f, q, k, 1] = len(words)
+                    words.append(m)
+                else:
+                    col[f, q, k, 1] = prefix(k + 1)
+            m = sum(1 << p for p in pi[:r])
+            for k in range(1, P - 1):      # T_k
+                if k > r:
+                    m |= 1 << pi[k]
+                    col[f, q, k, 0] = len(words)
+                    words.append(m)
+                else:
+                    col[f, q, k, 0] = prefix(k)
+    return words, col
+
+
 WINDOW_PLAYER_SPECS = ("promoter", "promoter_cells", "regions")
 
 
@@ -1107,6 +1204,73 @@ def mark_shapley_sampled(model, dataset, donor_dataset=None, genes=None, players
         for i, g in enumerate(ids):
             yield dict(gene_id=g, phi=phi[i].copy(), stderr=se[i].copy(), logits=logits[i].copy(), absent=absent[i].copy(), players=list(names),
                        permutations=perms.copy())
+
+
+def mark_shapley_interactions_sampled(model, dataset, donor_dataset=None, genes=None, players="cells", top=4, focal=None, index="sii", n_perm=64,
+                                      seed=0, scale=0.0, bsz=None, store=None, donor_store=None):
+    """Sampled pairwise Shapley interaction indices of each gene's leading histone-mark players, for the genes of a
+    ChromoformerDataset: for the cells that carry the prediction, which other cells are redundant with them, which cooperate?  Per
+    batch one model.mark_shapley_sampled call finds every gene's `top` players by |phi| at the last output column (ties: the lower
+    index); per gene one model.mark_shapley_interactions_sampled call on that gene alone, with the same orders, takes them as its focal
+    players (the rows run in chunks of max_batch either way).  `focal` (indices or names, attribution.focal_players) fixes the focal
+    players for every gene instead, and the per-batch call is skipped.  With `donor_dataset` an absent player takes the donor's signal
+    (same_regions runs first), else its raw signal is scaled by `scale`.  A generator over `genes` (ids; default: the dataset's); per
+    gene it yields a dict of host arrays:
+
+        gene_id        the id
+        interactions   float32 [n_focal, P, n_out]: row f estimates the index of focal player focal[f] with every player; the
+                       diagonal entry as in model.mark_shapley_interactions_sampled.  Not symmetric between two focal players
+        stderr         float32 [n_focal, P, n_out]: the standard error over the orders -- the sampling error is reported here and
+                       not bounded anywhere
+        phi, phi_stderr   float32 [P, n_out]: the sampled Shapley values from the same forwards
+        focal          int32 [n_focal]: the focal players, strongest first;  focal_names: their names
+        logits, absent    float32 [n_out]: every player present (the prediction), every player absent
+        players        the players' names (mark_players_wide)
+        index          the index name
+        permutations   uint8 [n_perm, P]: the orders, shapley_permutations(P, n_perm, seed), the same for every gene
+
+    The binned features come from `store` / `donor_store` as in mark_donor_shapley.  Parameters, gradients and optimiser state are left
+    as they are; the pass overwrites the activations a grad-enabled model(...) keeps for its backward."""
+    ds, dn = dataset, donor_dataset
+    who = "mark_shapley_interactions_sampled"
+    binsizes = [int(b) for b in ds.binsizes]
+    _geometry_check(who, model, ds, binsizes)
+    genes, chunk = _genes_check(who, model, ds, genes, bsz)
+    if dn is not None:
+        same_regions(ds, dn, genes)
+    spec = players if isinstance(players, str) else list(players)
+    names = mark_players_wide(spec, ds.n_feats, ds.i_max)[2]      # (refusals before anything is loaded)
+    P = len(names)
+    interaction_index(index, who)
+    if P < 2:
+        raise ValueError("%s: %d player; a pair needs at least 2" % (who, P))
+    if focal is not None:
+        focal = focal_players(focal, names, P)
+    elif not 1 <= int(top) <= P:
+        raise ValueError("%s: top = %r outside 1..%d" % (who, top, P))
+    perms = shapley_permutations(P, n_perm, seed)
+    store = _resident_store(who, ds, genes, binsizes, model._device, store)
+    if dn is not None:
+        donor_store = _resident_store(who, dn, genes, binsizes, model._device, donor_store)
+    for lo in range(0, len(genes), chunk):
+        ids = genes[lo:lo + chunk]
+        idx = list(range(lo, lo + len(ids)))
+        lead = None
+        if focal is None:
+            d = store.batch(idx)
+            donor = _donor_pair(donor_store.batch(idx)) if dn is not None else None
+            phi = model.mark_shapley_sampled(*(d[k] for k in _BATCH_KEYS), players=spec, permutations=perms, scale=scale, donor=donor)[0]
+            lead = np.argsort(-np.abs(phi[..., -1].cpu().numpy()), axis=1, kind="stable")[:, :int(top)]
+        for i, g in enumerate(ids):
+            d = store.batch([lo + i])
+            donor = _donor_pair(donor_store.batch([lo + i])) if dn is not None else None
+            mine = focal if focal is not None else lead[i].astype(np.int32)
+            inter, info = model.mark_shapley_interactions_sampled(*(d[k] for k in _BATCH_KEYS), players=spec, focal=mine, index=index,
+                                                                  permutations=perms, scale=scale, donor=donor)
+            host = lambda t: t[0].cpu().numpy().copy()      # noqa: E731
+            yield dict(gene_id=g, interactions=host(inter), stderr=host(info["stderr"]), phi=host(info["phi"]), phi_stderr=host(info["phi_stderr"]),
+                       focal=np.array(mine, dtype=np.int32), focal_names=[names[int(p)] for p in mine], logits=host(info["logits"]),
+                       absent=host(info["absent"]), players=list(names), index=index, permutations=perms.copy())
 
 
 def window_player_coordinates(marks_regions_windows, regions, n_real, binsize):

@@ -12,6 +12,7 @@
 #include "cf_marks.h"
 #include "cf_scan_fine.h"
 #include "cf_marks_wide.h"
+#include "cf_mark_pairs.h"
 #include "cf_mark_windows.h"
 #include "cf_mark_fine.h"
 #include "cf_x0_gather.h"

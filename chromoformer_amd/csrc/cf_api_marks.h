@@ -1,7 +1,7 @@
 // cf_api_marks.h -- host side of the histone-mark games: mark coalitions, exact Shapley values and pair epistasis under the scale rule
 // (cf_mark_*) and the donor rule (cf_mark_donor_*), the wide game and its sampled Shapley values, the window game, the fine window game.
-// One MarkGame per call, built and checked by the constructor of its kind, then one of three calls on it: the given coalitions, an exact
-// game (Shapley / epistasis), sampled permutations.  Part of cf_api.hip's single translation unit: included there behind
+// One MarkGame per call, built and checked by the constructor of its kind, then one of four calls on it: the given coalitions, an exact
+// game (Shapley / epistasis), sampled permutations, sampled interaction indices of focal players.  Part of cf_api.hip's single translation unit: included there behind
 // cf_api_attrib.h, whose chunk loop, geometry helpers and exact-game reducers it uses; not on its own.
 #pragma once
 
@@ -276,33 +276,56 @@ static int mark_exact_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g, 
 // the prefix rows of n_perm permutations through mark_upload + mark_rows (column 0 nobody, column 1 everybody, column
 // 2 + q (P - 1) + (k - 1) the first k players of permutation q), then k_perm_shapley on the inverse permutations, which travel as bytes
 // behind the player words.  `g`: a checked game of a kind with kw words per coalition (wide, window, fine).
-static int mark_sampled_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g, const uint8_t* perms, int n_perm, float* phi, float* se,
-                             float* logits_rows, void* stream, const char* who) {
-    if (!phi) return fail("%s: null phi", who);
-    if (!perms) return fail("%s: null perms", who);
-    if (n_perm < 1) return fail("%s: n_perm = %d: at least 1 permutation", who, n_perm);
-    const cf_config& c = h->cfg;
-    const int P = g.P, kw = g.kw;
-    const long long R64 = 2 + (long long)n_perm * (P - 1);
-    if (R64 * kw > (1ll << 30)) return fail("%s: n_perm = %d: %lld rows per gene; at most 2^30 coalition words", who, n_perm, R64);
-    const int R = (int)R64;
-    std::vector<uint8_t> rank((size_t)n_perm * P);
-    std::vector<uint32_t> keep((size_t)R * kw, 0u), cur(kw);
-    for (int p = 0; p < P; ++p) keep[kw + (p >> 5)] |= 1u << (p & 31);      // column 1: everybody
+static int perm_ranks(const uint8_t* perms, int n_perm, int P, std::vector<uint8_t>* rank, const char* who) {      // the inverses, checked
+    rank->assign((size_t)n_perm * P, 0xFF);
     for (int q = 0; q < n_perm; ++q) {
         const uint8_t* pi = perms + (size_t)q * P;
-        uint8_t* rk = rank.data() + (size_t)q * P;
-        memset(rk, 0xFF, P);
+        uint8_t* rk = rank->data() + (size_t)q * P;
         for (int k = 0; k < P; ++k) {
             if (pi[k] >= P || rk[pi[k]] != 0xFF) return fail("%s: perms[%d] is not a permutation of 0..%d (position %d holds %d)", who, q, P - 1, k, (int)pi[k]);
             rk[pi[k]] = (uint8_t)k;
         }
+    }
+    return 0;
+}
+static void prefix_words(const uint8_t* perms, int n_perm, int P, int kw, uint32_t* keep) {      // the 2 + n_perm (P - 1) leading rows, zeroed
+    std::vector<uint32_t> cur(kw);
+    for (int p = 0; p < P; ++p) keep[kw + (p >> 5)] |= 1u << (p & 31);      // column 1: everybody
+    for (int q = 0; q < n_perm; ++q) {
+        const uint8_t* pi = perms + (size_t)q * P;
         std::fill(cur.begin(), cur.end(), 0u);
         for (int k = 1; k < P; ++k) {
             cur[pi[k - 1] >> 5] |= 1u << (pi[k - 1] & 31);
             memcpy(&keep[(2 + (size_t)q * (P - 1) + (k - 1)) * kw], cur.data(), kw * sizeof(uint32_t));
         }
     }
+}
+// k_perm_shapley on the prefix rows that lead a table of `stride` rows per gene (0: the prefix rows are the table)
+static int launch_perm_shapley(cf_handle* h, int B, int P, int n_out, int n_perm, const float* rows, size_t stride, const uint8_t* rank_at, float* phi, float* se,
+                               hipStream_t st) {
+    PermShapleyArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.v = rows, pa.rank = rank_at, pa.phi = phi, pa.se = se;
+    pa.n = (float)n_perm, pa.nn1 = (float)((double)n_perm * (n_perm - 1));
+    pa.P = P, pa.n_perm = n_perm, pa.n_out = n_out, pa.stride = stride;
+    hipLaunchKernelGGL(k_perm_shapley, dim3(B, P), dim3(kShapThreads), 0, st, pa);
+    LAUNCH_CHECK("k_perm_shapley");
+    forward_one_more(h);
+    return 0;
+}
+static int mark_sampled_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g, const uint8_t* perms, int n_perm, float* phi, float* se,
+                             float* logits_rows, void* stream, const char* who) {
+    if (!phi) return fail("%s: null phi", who);
+    if (!perms) return fail("%s: null perms", who);
+    if (n_perm < 1) return fail("%s: n_perm = %d: at least 1 permutation", who, n_perm);
+    const int P = g.P, kw = g.kw;
+    const long long R64 = 2 + (long long)n_perm * (P - 1);
+    if (R64 * kw > (1ll << 30)) return fail("%s: n_perm = %d: %lld rows per gene; at most 2^30 coalition words", who, n_perm, R64);
+    const int R = (int)R64;
+    std::vector<uint8_t> rank;
+    if (perm_ranks(perms, n_perm, P, &rank, who)) return -1;
+    std::vector<uint32_t> keep((size_t)R * kw, 0u);
+    prefix_words(perms, n_perm, P, kw, keep.data());
     float* rows = coalition_out_rows(h, logits_rows, R, who);
     if (!rows) return -1;
     hipStream_t st = (hipStream_t)stream;
@@ -310,15 +333,147 @@ static int mark_sampled_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g
     uint8_t* rank_at = reinterpret_cast<uint8_t*>((unsigned*)h->aw.words + (size_t)R * kw + mark_player_words(g));
     HIP_TRY(hipMemcpyAsync(rank_at, rank.data(), rank.size(), hipMemcpyHostToDevice, st));
     if (mark_rows(h, bt, g, R, rows, st)) return -1;
-    PermShapleyArgs pa;
-    memset(&pa, 0, sizeof pa);
-    pa.v = rows, pa.rank = rank_at, pa.phi = phi, pa.se = se;
-    pa.n = (float)n_perm, pa.nn1 = (float)((double)n_perm * (n_perm - 1));
-    pa.P = P, pa.n_perm = n_perm, pa.n_out = c.n_out;
-    hipLaunchKernelGGL(k_perm_shapley, dim3(bt->B, P), dim3(kShapThreads), 0, st, pa);
-    LAUNCH_CHECK("k_perm_shapley");
-    forward_one_more(h);
+    return launch_perm_shapley(h, bt->B, P, h->cfg.n_out, n_perm, rows, 0, rank_at, phi, se, st);
+}
+
+// Sampled pairwise interaction indices of focal players (cf_mark_pairs.h).  FocalTable: what the host builds from the orders and the
+// focal players -- the inverse permutations, the R coalitions (kw words each: the prefix rows of mark_sampled_impl, then per focal player
+// {i}, everybody but i, and per order the rows T_k + i, k = 1 .. r - 1, and T_k, k = r + 1 .. P - 2), and col[f, q, k, {without, with}].
+struct FocalTable {
+    std::vector<uint8_t> rank;
+    std::vector<uint32_t> keep, col;
+    long long R = 0;
+};
+// What the sampled-interactions calls check beside their game, then the table.  Refused by name: null inter / perms / focal, n_perm < 1,
+// n_focal outside 1..P, index, P < 2, a focal index outside 0..P-1 or repeated (its position is named), a row of perms that is no
+// permutation, more than 2^30 coalition words.
+static int focal_table(int P, const uint8_t* perms, int n_perm, const int* focal, int n_focal, int index, const float* inter, const float* phi,
+                       const float* phi_se, FocalTable* t, const char* who) {
+    if (interactions_check(index, P, inter, who)) return -1;
+    if (phi_se && !phi) return fail("%s: phi_se without phi", who);
+    if (!perms) return fail("%s: null perms", who);
+    if (n_perm < 1) return fail("%s: n_perm = %d: at least 1 permutation", who, n_perm);
+    if (!focal) return fail("%s: null focal", who);
+    if (n_focal < 1 || n_focal > P) return fail("%s: n_focal = %d outside 1..%d", who, n_focal, P);
+    for (int f = 0; f < n_focal; ++f) {
+        if (focal[f] < 0 || focal[f] >= P) return fail("%s: focal[%d] = %d outside 0..%d", who, f, focal[f], P - 1);
+        for (int e = 0; e < f; ++e)
+            if (focal[e] == focal[f]) return fail("%s: focal[%d] = %d repeats focal[%d]", who, f, focal[f], e);
+    }
+    if (perm_ranks(perms, n_perm, P, &t->rank, who)) return -1;
+    const int kw = (P + 31) / 32;
+    auto extra = [&](int r) { return r == 0 || r == P - 1 ? P - 2 : P - 3; };      // the rows of one (focal, order) that are no prefix
+    long long R = 2 + (long long)n_perm * (P - 1);
+    for (int f = 0; f < n_focal; ++f) {
+        R += 2;
+        for (int q = 0; q < n_perm; ++q) R += extra(t->rank[(size_t)q * P + focal[f]]);
+    }
+    if (R * kw > (1ll << 30)) return fail("%s: n_perm = %d, n_focal = %d: %lld rows per gene; at most 2^30 coalition words", who, n_perm, n_focal, R);
+    t->R = R;
+    t->keep.assign((size_t)R * kw, 0u);
+    t->col.assign((size_t)n_focal * n_perm * P * 2, 0u);
+    prefix_words(perms, n_perm, P, kw, t->keep.data());
+    std::vector<uint32_t> cur(kw);
+    auto put = [&](std::vector<uint32_t>& w, int p) { w[p >> 5] |= 1u << (p & 31); };
+    size_t row = 2 + (size_t)n_perm * (P - 1);
+    auto emit = [&]() {      // (a row past the count is not written: the count is checked below)
+        if (row < (size_t)R) memcpy(&t->keep[row * kw], cur.data(), kw * sizeof(uint32_t));
+        return (uint32_t)row++;
+    };
+    for (int f = 0; f < n_focal; ++f) {
+        const int i = focal[f];
+        std::fill(cur.begin(), cur.end(), 0u);
+        put(cur, i);
+        const uint32_t alone = emit();
+        memcpy(cur.data(), &t->keep[kw], kw * sizeof(uint32_t));
+        cur[i >> 5] &= ~(1u << (i & 31));
+        const uint32_t without = emit();
+        for (int q = 0; q < n_perm; ++q) {
+            const uint8_t* pi = perms + (size_t)q * P;
+            const int r = t->rank[(size_t)q * P + i];
+            uint32_t* c = &t->col[((size_t)f * n_perm + q) * P * 2];
+            auto prefix = [&](int k) { return (uint32_t)(2 + (size_t)q * (P - 1) + (k - 1)); };      // the first k of pi, 1 <= k <= P - 1
+            // (a prefix of pi where there is one: the diagonal then reads the very rows k_perm_shapley reads, on any table)
+            c[0] = 0, c[1] = r == 0 ? prefix(1) : alone;
+            c[2 * (P - 1)] = r == P - 1 ? prefix(P - 1) : without, c[2 * (P - 1) + 1] = 1;
+            std::fill(cur.begin(), cur.end(), 0u);
+            put(cur, i);
+            for (int k = 1; k <= P - 2; ++k) {      // T_k + i: an own row in front of i's position, the prefix pi[:k + 1] from there on
+                if (k < r) put(cur, pi[k - 1]);
+                c[2 * k + 1] = k < r ? emit() : prefix(k + 1);
+            }
+            std::fill(cur.begin(), cur.end(), 0u);
+            for (int k = 0; k <= r && k < P; ++k)
+                if (k != r) put(cur, pi[k]);
+            for (int k = 1; k <= P - 2; ++k) {      // T_k: the prefix pi[:k] up to i's position, an own row behind it (pi[:k + 1] less i)
+                if (k > r) put(cur, pi[k]);
+                c[2 * k] = k > r ? emit() : prefix(k);
+            }
+        }
+    }
+    if ((long long)row != R) return fail("%s: internal: %zu rows built, %lld counted", who, row, R);
     return 0;
+}
+// k_perm_pairs on a table in FocalTable's layout, rank and col on the device, and k_perm_shapley on its leading rows if phi is given.
+static int launch_perm_pairs(cf_handle* h, int B, int P, int n_out, int n_perm, const int* focal, int n_focal, int index, const float* rows, size_t R,
+                             const uint8_t* rank_at, const unsigned* col_at, float* inter, float* se, float* phi, float* phi_se, hipStream_t st) {
+    PermPairsArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.v = rows, pa.rank = rank_at, pa.col = col_at, pa.inter = inter, pa.se = se, pa.R = R;
+    pa.n = (float)n_perm, pa.nn1 = (float)((double)n_perm * (n_perm - 1));
+    pa.P = P, pa.n_perm = n_perm, pa.n_out = n_out, pa.n_focal = n_focal, pa.sti = index == CF_INTERACTION_STI;
+    for (int f = 0; f < n_focal; ++f) pa.focal[f] = (uint8_t)focal[f];
+    for (int a = 0; a < P - 1; ++a) pa.w[a] = (float)(2.0 * (P - 1 - a) / P);
+    hipLaunchKernelGGL(k_perm_pairs, dim3(B, n_focal * P), dim3(kShapThreads), 0, st, pa);
+    LAUNCH_CHECK("k_perm_pairs");
+    forward_one_more(h);
+    return phi ? launch_perm_shapley(h, B, P, n_out, n_perm, rows, R, rank_at, phi, phi_se, st) : 0;
+}
+// rank (bytes) and col behind `at` words of the word table, which has room for them
+static int focal_upload(cf_handle* h, const FocalTable& t, size_t at, const uint8_t** rank_at, const unsigned** col_at, hipStream_t st) {
+    unsigned* tab = (unsigned*)h->aw.words + at;
+    HIP_TRY(hipMemcpyAsync(tab, t.rank.data(), t.rank.size(), hipMemcpyHostToDevice, st));
+    unsigned* c = tab + (t.rank.size() + 3) / 4;
+    HIP_TRY(hipMemcpyAsync(c, t.col.data(), t.col.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    *rank_at = reinterpret_cast<const uint8_t*>(tab), *col_at = c;
+    return 0;
+}
+// The call on a checked game of a kind with kw words per coalition (wide, window, fine): the R rows through mark_upload + mark_rows,
+// then the reducers.
+static int mark_pairs_sampled_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g, const uint8_t* perms, int n_perm, const int* focal,
+                                   int n_focal, int index, float* inter, float* se, float* phi, float* phi_se, float* logits_rows, void* stream,
+                                   const char* who) {
+    FocalTable t;
+    if (focal_table(g.P, perms, n_perm, focal, n_focal, index, inter, phi, phi_se, &t, who)) return -1;
+    const int R = (int)t.R;
+    float* rows = coalition_out_rows(h, logits_rows, R, who);
+    if (!rows) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    if (mark_upload(h, g, t.keep.data(), R, (t.rank.size() + 3) / 4 + t.col.size(), st, who)) return -1;
+    const uint8_t* rank_at;
+    const unsigned* col_at;
+    if (focal_upload(h, t, (size_t)R * g.kw + mark_player_words(g), &rank_at, &col_at, st) || mark_rows(h, bt, g, R, rows, st)) return -1;
+    return launch_perm_pairs(h, bt->B, g.P, h->cfg.n_out, n_perm, focal, n_focal, index, rows, (size_t)R, rank_at, col_at, inter, se, phi, phi_se, st);
+}
+// The operator on a caller's table in that layout: no batch, no chunk workspace, nothing of the handle but the word table.
+extern "C" int cf_perm_interactions_from_rows(cf_handle* h, const float* rows, int B, int P, int n_out, const uint8_t* perms, int n_perm,
+                                              const int* focal, int n_focal, int index, float* inter, float* se, float* phi, float* phi_se,
+                                              void* stream) {
+    const char* who = "cf_perm_interactions_from_rows";
+    if (!h) return fail("%s: null handle", who);
+    if (!rows) return fail("%s: null rows", who);
+    if (B < 1) return fail("%s: B = %d: at least 1 gene", who, B);
+    if (P > kMarkWideMaxP) return fail("%s: P = %d outside 2..%d", who, P, kMarkWideMaxP);
+    if (n_out < 1) return fail("%s: n_out = %d: at least 1 output", who, n_out);
+    FocalTable t;
+    if (focal_table(P, perms, n_perm, focal, n_focal, index, inter, phi, phi_se, &t, who)) return -1;
+    if (h->aw.words.need((t.rank.size() + 3) / 4 + t.col.size(), 256, who)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    const uint8_t* rank_at;
+    const unsigned* col_at;
+    if (focal_upload(h, t, 0, &rank_at, &col_at, st)) return -1;
+    h->n_fwd = 0;
+    return launch_perm_pairs(h, B, P, n_out, n_perm, focal, n_focal, index, rows, (size_t)t.R, rank_at, col_at, inter, se, phi, phi_se, st);
 }
 
 // The entry points: the game of the family, then its call.  The scale rule's one-word game;
@@ -434,4 +589,33 @@ extern "C" int cf_mark_fine_shapley_sampled(cf_handle* h, const cf_batch* bt, co
     const char* who = "cf_mark_fine_shapley_sampled";
     MarkGame g;
     return mark_fine_game(h, bt, o, &g, (hipStream_t)stream, who) ? -1 : mark_sampled_impl(h, bt, g, perms, n_perm, phi, se, logits_rows, stream, who);
+}
+
+// Sampled interaction indices of focal players, one entry point per wide kind.
+extern "C" int cf_mark_shapley_interactions_sampled(cf_handle* h, const cf_batch* bt, const cf_mark_wide_opts* o, const uint8_t* perms, int n_perm,
+                                                    const int* focal, int n_focal, int index, float* inter, float* se, float* phi, float* phi_se,
+                                                    float* logits_rows, void* stream) {
+    const char* who = "cf_mark_shapley_interactions_sampled";
+    MarkGame g;
+    return mark_wide_game(h, bt, o, &g, who)
+               ? -1
+               : mark_pairs_sampled_impl(h, bt, g, perms, n_perm, focal, n_focal, index, inter, se, phi, phi_se, logits_rows, stream, who);
+}
+extern "C" int cf_mark_window_shapley_interactions_sampled(cf_handle* h, const cf_batch* bt, const cf_mark_window_opts* o, const uint8_t* perms,
+                                                           int n_perm, const int* focal, int n_focal, int index, float* inter, float* se, float* phi,
+                                                           float* phi_se, float* logits_rows, void* stream) {
+    const char* who = "cf_mark_window_shapley_interactions_sampled";
+    MarkGame g;
+    return mark_window_game(h, bt, o, &g, who)
+               ? -1
+               : mark_pairs_sampled_impl(h, bt, g, perms, n_perm, focal, n_focal, index, inter, se, phi, phi_se, logits_rows, stream, who);
+}
+extern "C" int cf_mark_fine_shapley_interactions_sampled(cf_handle* h, const cf_batch* bt, const cf_mark_fine_opts* o, const uint8_t* perms,
+                                                         int n_perm, const int* focal, int n_focal, int index, float* inter, float* se, float* phi,
+                                                         float* phi_se, float* logits_rows, void* stream) {
+    const char* who = "cf_mark_fine_shapley_interactions_sampled";
+    MarkGame g;
+    return mark_fine_game(h, bt, o, &g, (hipStream_t)stream, who)
+               ? -1
+               : mark_pairs_sampled_impl(h, bt, g, perms, n_perm, focal, n_focal, index, inter, se, phi, phi_se, logits_rows, stream, who);
 }

@@ -31,46 +31,59 @@ struct PermShapleyArgs {
     float* se;                               // [B, P, n_out], or null
     float n, nn1;                            // n_perm and n_perm (n_perm - 1) as floats (the host rounds them once)
     int P, n_perm, n_out;
+    size_t stride;                           // rows per gene of `v`; 0: R (a longer table leads with the prefix rows: cf_mark_pairs.h)
 };
+
+// The estimator of one (gene, player, output) by one workgroup: d(q) is the sample of order q (one fp32 subtraction), `red` kShapThreads
+// floats of LDS.  Writes the mean, and the standard error if se_at is not null.  k_perm_shapley and the "sii" diagonal of k_perm_pairs
+// (cf_mark_pairs.h) both call it, so the two carry the same bits.  The square e e is fused into the sum of squares with an explicit
+// fmaf: what the compiler made of the separate __fmul_rn / __fadd_rn (plain operators here) before this function existed, written
+// down so that it no longer depends on the compiler; the root is __fsqrt_rn (the hardware's approximate v_sqrt_f32 in this toolchain).
+template <class Sample>
+__device__ __forceinline__ void perm_mean_se(int n_perm, float n, float nn1, float* red, Sample d, float* mean_at, float* se_at) {
+    const int tid = threadIdx.x;
+    float acc = 0.f;
+    for (int q = tid; q < n_perm; q += kShapThreads) acc = __fadd_rn(acc, d(q));
+    red[tid] = acc;
+    __syncthreads();
+    for (int s = kShapThreads / 2; s > 0; s >>= 1) {
+        if (tid < s) red[tid] = __fadd_rn(red[tid], red[tid + s]);
+        __syncthreads();
+    }
+    const float phi = __fdiv_rn(red[0], n);
+    __syncthreads();
+    if (tid == 0) *mean_at = phi;
+    if (!se_at) return;
+    acc = 0.f;
+    for (int q = tid; q < n_perm; q += kShapThreads) {
+        const float e = __fsub_rn(d(q), phi);
+        acc = fmaf(e, e, acc);
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (int s = kShapThreads / 2; s > 0; s >>= 1) {
+        if (tid < s) red[tid] = __fadd_rn(red[tid], red[tid + s]);
+        __syncthreads();
+    }
+    if (tid == 0) *se_at = n_perm > 1 ? __fsqrt_rn(__fdiv_rn(red[0], nn1)) : 0.f;
+    __syncthreads();
+}
 
 __global__ __launch_bounds__(kShapThreads) void k_perm_shapley(PermShapleyArgs a) {
     __shared__ float red[kShapThreads];
-    const int b = blockIdx.x, p = blockIdx.y, tid = threadIdx.x, P = a.P, n_perm = a.n_perm, n_out = a.n_out;
-    const size_t R = 2 + (size_t)n_perm * (P - 1);
+    const int b = blockIdx.x, p = blockIdx.y, P = a.P, n_perm = a.n_perm, n_out = a.n_out;
+    const size_t R = a.stride ? a.stride : 2 + (size_t)n_perm * (P - 1);
     const float* __restrict__ v = a.v + (size_t)b * R * n_out;
     // the column of the first k players of permutation q: nobody, everybody, else the permutation's own row
     auto col = [&](int q, int k) -> size_t { return k == 0 ? 0 : k == P ? 1 : 2 + (size_t)q * (P - 1) + (k - 1); };
     for (int o = 0; o < n_out; ++o) {
-        float acc = 0.f;
-        for (int q = tid; q < n_perm; q += kShapThreads) {
-            const int r = a.rank[(size_t)q * P + p];
-            acc = __fadd_rn(acc, __fsub_rn(v[col(q, r + 1) * n_out + o], v[col(q, r) * n_out + o]));
-        }
-        red[tid] = acc;
-        __syncthreads();
-        for (int s = kShapThreads / 2; s > 0; s >>= 1) {
-            if (tid < s) red[tid] = __fadd_rn(red[tid], red[tid + s]);
-            __syncthreads();
-        }
-        const float phi = __fdiv_rn(red[0], a.n);
-        __syncthreads();
         const size_t at = ((size_t)b * P + p) * n_out + o;
-        if (tid == 0) a.phi[at] = phi;
-        if (!a.se) continue;
-        acc = 0.f;
-        for (int q = tid; q < n_perm; q += kShapThreads) {
-            const int r = a.rank[(size_t)q * P + p];
-            const float e = __fsub_rn(__fsub_rn(v[col(q, r + 1) * n_out + o], v[col(q, r) * n_out + o]), phi);
-            acc = __fadd_rn(acc, __fmul_rn(e, e));
-        }
-        red[tid] = acc;
-        __syncthreads();
-        for (int s = kShapThreads / 2; s > 0; s >>= 1) {
-            if (tid < s) red[tid] = __fadd_rn(red[tid], red[tid + s]);
-            __syncthreads();
-        }
-        if (tid == 0) a.se[at] = n_perm > 1 ? __fsqrt_rn(__fdiv_rn(red[0], a.nn1)) : 0.f;
-        __syncthreads();
+        perm_mean_se(n_perm, a.n, a.nn1, red,
+                     [&](int q) {
+                         const int r = a.rank[(size_t)q * P + p];
+                         return __fsub_rn(v[col(q, r + 1) * n_out + o], v[col(q, r) * n_out + o]);
+                     },
+                     a.phi + at, a.se ? a.se + at : nullptr);
     }
 }
 

@@ -1032,6 +1032,67 @@ class ChromoformerBase(nn.Module):
             info["rows"] = rows
         return phi, info
 
+    def _mark_run_pairs_sampled(self, cfn, bs, opts, names, perms, focal, index, book, return_rows):
+        """The sampled interactions call of a wide game (`cfn`) -> (inter, info): see mark_shapley_interactions_sampled."""
+        from .attribution import focal_players, focal_row_count, focal_words, interaction_index
+        code = interaction_index(index, cfn[3:])
+        P, n = opts.n_players, len(perms)
+        if P < 2:
+            raise ValueError("%s: %d player; a pair needs at least 2" % (cfn[3:], P))
+        if focal is None:
+            raise ValueError("%s: focal is required: the players whose interactions are asked for (indices or names)" % cfn[3:])
+        focal = focal_players(focal, names, P)
+        words, col = focal_words(perms, focal)
+        F, R, dev = len(focal), len(words), self._device
+        rows = torch.empty(bs.B, R, self.n_out, device=dev)      # (all five written in full by the library)
+        inter, se = torch.empty(bs.B, F, P, self.n_out, device=dev), torch.empty(bs.B, F, P, self.n_out, device=dev)
+        phi, phi_se = torch.empty(bs.B, P, self.n_out, device=dev), torch.empty(bs.B, P, self.n_out, device=dev)
+        st = book()
+        _lib.check(getattr(_lib.lib(), cfn)(self._handle, C.byref(bs), C.byref(opts), perms.ctypes.data, n, focal.ctypes.data, F, code,
+                                            inter.data_ptr(), se.data_ptr(), phi.data_ptr(), phi_se.data_ptr(), rows.data_ptr(), st), cfn)
+        at = torch.as_tensor([focal_row_count(perms, focal[:f]) for f in range(F)], device=dev)      # {i} alone; everybody but i follows it
+        info = {"stderr": se, "phi": phi, "phi_stderr": phi_se, "logits": rows[:, 1].clone(), "absent": rows[:, 0].clone(),
+                "alone": rows[:, at].clone(), "without": rows[:, at + 1].clone(), "index": index, "names": names,
+                "focal": focal, "permutations": perms, "col": col, "delta": None}
+        if index == "sii":      # every order telescopes: sum_{j != i} d(j) = (v(N) - v(N - i)) - (v({i}) - v(0))
+            off = torch.ones(F, P, dtype=torch.bool, device=dev)
+            off[torch.arange(F, device=dev), torch.as_tensor(focal.astype(np.int64), device=dev)] = False
+            total = (inter * off[None, :, :, None]).sum(2)
+            info["delta"] = total - ((info["logits"][:, None] - info["without"]) - (info["alone"] - info["absent"][:, None]))
+        if return_rows:
+            info["rows"] = rows
+        return inter, info
+
+    @torch.no_grad()
+    def perm_interactions_from_rows(self, rows, permutations, focal, index="sii"):
+        """The reducers of the sampled interactions calls on a table (cf_perm_interactions_from_rows) -> (inter, stderr, phi,
+        phi_stderr).  rows: a float32 tensor [B, R, n] on the model's device in the layout of attribution.focal_words(permutations,
+        focal) (any n >= 1); permutations: integer [n_perm, P], 2 <= P <= 128; focal: distinct player indices.  inter, stderr
+        [B, n_focal, P, n]; phi, phi_stderr [B, P, n].  No forward runs and no activation is written."""
+        from .attribution import focal_players, focal_row_count, interaction_index
+        who = "perm_interactions_from_rows"
+        code = interaction_index(index, who)
+        if self._handle is None:
+            raise RuntimeError("call .cuda() first: the Chromoformer HIP path needs device buffers")
+        perms = np.ascontiguousarray(np.asarray(permutations.cpu() if hasattr(permutations, "cpu") else permutations))
+        if perms.ndim != 2 or perms.dtype.kind not in "iu" or not 2 <= perms.shape[1] <= 128 or perms.min() < 0 or perms.max() >= perms.shape[1]:
+            raise ValueError("%s: permutations must be an integer array [n_perm >= 1, 2 <= P <= 128] with entries in [0, P)" % who)
+        perms = np.ascontiguousarray(perms, dtype=np.uint8)
+        n, P = perms.shape
+        focal = focal_players(focal, None, P)
+        R = focal_row_count(perms, focal)
+        if not torch.is_tensor(rows) or rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[1] != R or rows.device != self._device:
+            raise ValueError("%s: rows must be a float32 tensor [B, R = %d, n] on %s" % (who, R, self._device))
+        rows = rows.contiguous()
+        B, n_out, F, dev = rows.shape[0], rows.shape[2], len(focal), self._device
+        inter, se = torch.empty(B, F, P, n_out, device=dev), torch.empty(B, F, P, n_out, device=dev)
+        phi, phi_se = torch.empty(B, P, n_out, device=dev), torch.empty(B, P, n_out, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.lib().cf_perm_interactions_from_rows(self._handle, rows.data_ptr(), B, P, n_out, perms.ctypes.data, n, focal.ctypes.data, F,
+                                                             code, inter.data_ptr(), se.data_ptr(), phi.data_ptr(), phi_se.data_ptr(), st),
+                   "cf_perm_interactions_from_rows")
+        return inter, se, phi, phi_se
+
     @torch.no_grad()
     def mark_coalitions(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
                         interaction_freq=None, keep=None, players="marks", scale=0.0):
@@ -1328,6 +1389,53 @@ class ChromoformerBase(nn.Module):
         return mark_shapley_sampled(self, dataset, donor_dataset, genes=genes, players=players, n_perm=n_perm, seed=seed, scale=scale, bsz=bsz,
                                     store=store, donor_store=donor_store)
 
+    @torch.no_grad()
+    def mark_shapley_interactions_sampled(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None,
+                                          interaction_masks=None, interaction_freq=None, players="cells", focal=None, index="sii", n_perm=64,
+                                          seed=0, permutations=None, scale=0.0, donor=None, return_rows=False):
+        """Permutation-sampled pairwise Shapley interaction indices of a few FOCAL players of up to 128 histone-mark players
+        (cf_mark_shapley_interactions_sampled) -> (inter, info), tensors on the model's device, no autograd graph: for the cells that
+        carry the prediction (mark_shapley_sampled finds them), which other cells are redundant with them, which cooperate?
+
+          inter                 [B, n_focal, P, n_out]: inter[b, f, j] estimates the interaction index of focal player i = focal[f] with
+                                player j -- how much i's marginal contribution changes with j present: per order, with the players
+                                that precede j among the others as context, (i's marginal with j) - (i's marginal without j); the mean
+                                over the orders.  index "sii": unbiased for the Shapley interaction index; the diagonal j = i is
+                                info["phi"][b, i], bit for bit.  index "sti": each sample weighted by 2 (P - 1 - a) / P, a the size of
+                                the context: unbiased for Shapley-Taylor of order 2; the diagonal is v({i}) - v(nobody).  Exactly 0
+                                where i or j is a null player.  NOT symmetric: inter[b, f, j] from focal i and the entry of focal j at
+                                player i are different samples of the same quantity
+          info["stderr"]        [B, n_focal, P, n_out]: the standard error of that mean over the orders (0 with one order; 0 on the
+                                "sti" diagonal).  inter is an ESTIMATE: this is the only statement about its sampling error
+          info["phi"], info["phi_stderr"]   [B, P, n_out]: mark_shapley_sampled's estimate of every player on the same orders, from the
+                                same forwards, bit for bit
+          info["logits"], info["absent"]    [B, n_out]: everybody present (the prediction), nobody present
+          info["alone"], info["without"]    [B, n_focal, n_out]: the focal player alone present; everybody but the focal player
+          info["delta"]         [B, n_focal, n_out], "sii": sum_{j != i} inter - ((logits - without) - (alone - absent)), rounding only
+                                (every order telescopes); None for "sti"
+          info["names"], info["focal"], info["index"], info["permutations"]   the players' names, the focal indices (int32), the index
+                                name, the orders (uint8 [n_perm, P])
+          info["col"]           uint32 [n_focal, n_perm, P, 2]: the rows the reducer reads (attribution.focal_words)
+          info["rows"]          [B, R, n_out], with return_rows: mark_shapley_sampled's table, then the focal players' own rows
+                                (attribution.focal_words) -- about as many forwards again as the Shapley estimate per focal player
+
+        focal: player indices or names (attribution.focal_players), distinct.  players, n_perm, seed, permutations, scale and donor as
+        in mark_shapley_sampled.  The packed forms of the first argument and the effect on a pending backward() are those of
+        mark_coalitions."""
+        who = "mark_shapley_interactions_sampled"
+        bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        opts, _alive, names = self._mark_wide_opts(who, players, scale, donor, bs.B)
+        perms = self._permutations(who, opts.n_players, n_perm, seed, permutations)
+        return self._mark_run_pairs_sampled("cf_mark_shapley_interactions_sampled", bs, opts, names, perms, focal, index, book, return_rows)
+
+    def mark_shapley_interactions_sampled_dataset(self, dataset, donor_dataset=None, genes=None, players="cells", top=4, focal=None, index="sii",
+                                                  n_perm=64, seed=0, scale=0.0, bsz=None, store=None, donor_store=None):
+        """mark_shapley_interactions_sampled over the genes of a ChromoformerDataset, the focal players chosen per gene
+        (chromoformer_amd.attribution.mark_shapley_interactions_sampled, a generator of per-gene dicts)."""
+        from .attribution import mark_shapley_interactions_sampled
+        return mark_shapley_interactions_sampled(self, dataset, donor_dataset, genes=genes, players=players, top=top, focal=focal, index=index,
+                                                 n_perm=n_perm, seed=seed, scale=scale, bsz=bsz, store=store, donor_store=donor_store)
+
     def _mark_window_opts(self, who, players, width, scale, donor, flip, B):
         """players (a window_players spec) at `width`, scale, donor (None: the scale rule; else the forms of _mark_donor_opts) and flip
         ([B] bools or None: the promoter is stored mirrored) for a batch of B genes -> (cf_mark_window_opts, what it points to, names)."""
@@ -1434,6 +1542,23 @@ class ChromoformerBase(nn.Module):
         opts, _alive, names = self._mark_window_opts(who, players, width, scale, donor, flip, bs.B)
         perms = self._permutations(who, opts.n_players, n_perm, seed, permutations)
         return self._mark_run_sampled("cf_mark_window_shapley_sampled", bs, opts, names, perms, book, return_rows)
+
+    @torch.no_grad()
+    def mark_window_shapley_interactions_sampled(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None,
+                                                 interaction_masks=None, interaction_freq=None, players="promoter", width=1, focal=None,
+                                                 index="sii", n_perm=64, seed=0, permutations=None, scale=0.0, donor=None, flip=None,
+                                                 return_rows=False):
+        """Permutation-sampled pairwise Shapley interaction indices of focal players among up to 128 window players
+        (cf_mark_window_shapley_interactions_sampled) -> (inter, info) with the keys, the row layout and the estimator of
+        mark_shapley_interactions_sampled: which stretches are redundant with the ones that carry the prediction?  players, width,
+        scale, donor and flip as in mark_window_coalitions; focal, index, n_perm, seed and permutations as in
+        mark_shapley_interactions_sampled.  The estimate is not symmetric; a null player (a window past the region's real bins, a
+        dummy slot) has its row and column exactly 0."""
+        who = "mark_window_shapley_interactions_sampled"
+        bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        opts, _alive, names = self._mark_window_opts(who, players, width, scale, donor, flip, bs.B)
+        perms = self._permutations(who, opts.n_players, n_perm, seed, permutations)
+        return self._mark_run_pairs_sampled("cf_mark_window_shapley_interactions_sampled", bs, opts, names, perms, focal, index, book, return_rows)
 
     def mark_window_shapley_dataset(self, dataset, donor_dataset=None, genes=None, players="promoter", width=1, n_perm=64, seed=0, scale=0.0,
                                     bsz=None, store=None, donor_store=None, interactions=None):
@@ -1588,6 +1713,23 @@ class ChromoformerBase(nn.Module):
         if return_feats:
             info["feats"] = feats
         return phi, info
+
+    @torch.no_grad()
+    def mark_fine_window_shapley_interactions_sampled(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None,
+                                                      interaction_masks=None, interaction_freq=None, region=0, players="windows", width=1,
+                                                      n_windows=None, start=0, lengths=None, focal=None, index="sii", n_perm=64, seed=0,
+                                                      permutations=None, scale=0.0, donor=None, flip=None, return_rows=False):
+        """Permutation-sampled pairwise Shapley interaction indices of focal players among up to 128 fine window players
+        (cf_mark_fine_shapley_interactions_sampled) -> (inter, info) with the keys, the row layout and the estimator of
+        mark_shapley_interactions_sampled: which 200 bp stretches are redundant with the ones that carry the prediction?  region,
+        players, width, n_windows, start, lengths, scale, donor and flip as in mark_fine_window_coalitions; focal, index, n_perm, seed
+        and permutations as in mark_shapley_interactions_sampled.  The estimate is not symmetric; a null player has its row and column
+        exactly 0."""
+        who = "mark_fine_window_shapley_interactions_sampled"
+        bs, _keep, book = self._attrib_call(who, (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
+        P, opts, _alive, names = self._mark_fine_opts(who, bs.B, region, players, width, n_windows, start, lengths, scale, donor, flip)
+        perms = self._permutations(who, P, n_perm, seed, permutations)
+        return self._mark_run_pairs_sampled("cf_mark_fine_shapley_interactions_sampled", bs, opts, names, perms, focal, index, book, return_rows)
 
     def mark_fine_window_shapley_dataset(self, dataset, donor_dataset=None, genes=None, region="promoter", zoom=1, coarse_width=1, width=2,
                                          players="windows", n_perm=64, seed=0, scale=0.0, target=None, bsz=None, store=None, donor_store=None,

@@ -308,6 +308,27 @@ def write_mark_sampled_values(model, store, donor_store, bsz, gene_ids, path, re
                  logits=logits.numpy(), absent=absent.numpy())
 
 
+def write_mark_sampled_interactions(model, ds, donor_ds, store, donor_store, bsz, gene_ids, path, regression=False, players="cells", top=4, focal=None,
+                                    index="sii", n_perm=64, seed=0, scale=0.0):
+    """Sampled pairwise Shapley interaction indices of each gene's focal mark players (attribution.mark_shapley_interactions_sampled:
+    the gene's `top` players by |phi|, or `focal` for every gene) of every gene of a device-resident store, in store order, in LOGIT
+    space of the prediction's column, into `path`, an .npz with gene_ids [n], players [P] (names), index, permutations uint8
+    [n_perm, P], focal int32 [n, n_focal] (the focal players of each gene), interactions [n, n_focal, P] (row f: focal player f with
+    every player; not symmetric between focal players), stderr [n, n_focal, P] (the standard error over the orders: the sampling error
+    is reported, not bounded), phi and phi_stderr [n, P] (the sampled Shapley values from the same forwards), logits [n] and absent [n].
+    ds / donor_ds: the datasets the stores were built from; donor_ds None: the scale rule."""
+    from .attribution import mark_shapley_interactions_sampled
+    t = 0 if regression else 1
+    res = list(mark_shapley_interactions_sampled(model, ds, donor_ds, genes=list(gene_ids), players=players, top=top, focal=focal, index=index,
+                                                 n_perm=n_perm, seed=seed, scale=scale, bsz=bsz, store=store, donor_store=donor_store))
+    with open(path, "wb") as f:      # (a file object: np.savez would append .npz to a name without it)
+        np.savez(f, gene_ids=np.array(list(gene_ids)), players=np.array(res[0]["players"]), index=np.array(index), permutations=res[0]["permutations"],
+                 focal=np.stack([r["focal"] for r in res]), interactions=np.stack([r["interactions"][..., t] for r in res]),
+                 stderr=np.stack([r["stderr"][..., t] for r in res]), phi=np.stack([r["phi"][..., t] for r in res]),
+                 phi_stderr=np.stack([r["phi_stderr"][..., t] for r in res]), logits=np.array([r["logits"][t] for r in res], dtype=np.float32),
+                 absent=np.array([r["absent"][t] for r in res], dtype=np.float32))
+
+
 def write_mark_window_values(model, ds, donor_ds, store, donor_store, bsz, gene_ids, path, regression=False, players="promoter", width=1, n_perm=64,
                              seed=0, scale=0.0):
     """Shapley values of window players (model.mark_window_shapley_dataset: exact with at most 16 players, else sampled) of every gene
@@ -594,7 +615,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
             fine_scan_width=1, fine_scan_stride=None, fine_scan_zoom=None, fine_scan_scale=0.0, fine_window_shapley_out=None,
             fine_window_donor_shapley_out=None, fine_window_region="promoter", fine_window_width=2, fine_window_players="windows",
             fine_window_zoom=1, fine_window_perms=64, fine_window_seed=0, fine_window_scale=0.0, pcre_interactions_out=None,
-            mark_interactions_out=None, mark_donor_interactions_out=None, interaction_index="sii"):
+            mark_interactions_out=None, mark_donor_interactions_out=None, interaction_index="sii", mark_sampled_interactions_out=None,
+            mark_donor_sampled_interactions_out=None, mark_focal=4):
     """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file.  attention_dir / embeddings_out: also
     write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps); pcre_ablation_out:
     the predictions with each pCRE deleted (write_pcre_ablation); ig_dir: integrated gradients of every gene
@@ -623,9 +645,24 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     fine_window_region, fine_window_width, fine_window_players, fine_window_zoom, fine_window_perms and fine_window_seed apply);
     pcre_interactions_out / mark_interactions_out / mark_donor_interactions_out: the pairwise Shapley interaction index
     interaction_index ("sii" / "sti") of the pCREs / the histone marks / the marks against the donor, a float32 .npy [n_genes, P, P] in
-    logit space, by the writers of the Shapley values of the same game (one interactions call serves both outputs)."""
+    logit space, by the writers of the Shapley values of the same game (one interactions call serves both outputs);
+    mark_sampled_interactions_out / mark_donor_sampled_interactions_out: the SAMPLED interaction index of each gene's focal players
+    among up to 128 mark players, one .npz, under the scale rule (mark_scale applies) / against the donor
+    (write_mark_sampled_interactions; mark_focal -- an int: each gene's strongest players by |phi|; a list of names or indices: those
+    for every gene --, mark_sampled_players, mark_perms, mark_seed and interaction_index apply)."""
     from .attribution import interaction_index as _index_check
     _index_check(interaction_index, "predict")      # (before anything is computed)
+    pairs_ds, pairs_kw = None, {}
+    if mark_sampled_interactions_out or mark_donor_sampled_interactions_out:      # (refusals before anything is computed)
+        from .attribution import focal_players, mark_players_wide
+        pair_names = mark_players_wide(mark_sampled_players, 7, i_max)[2]
+        if isinstance(mark_focal, (int, np.integer)) and not isinstance(mark_focal, bool):
+            if not 1 <= mark_focal <= len(pair_names):
+                raise ValueError("predict: mark_focal = %d outside 1..%d" % (mark_focal, len(pair_names)))
+            pairs_kw = dict(top=int(mark_focal))
+        else:
+            pairs_kw = dict(focal=focal_players(mark_focal, pair_names, len(pair_names)))
+        pairs_kw.update(players=mark_sampled_players, index=interaction_index, n_perm=mark_perms, seed=mark_seed)
     seed_everything(seed)
     meta = pd.read_csv(meta_path)
     genes = meta.gene_id.tolist()
@@ -635,7 +672,9 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         require_raw_signals(raw_ds)      # (before anything is computed)
     from . import pack
     donor_out = (mark_donor_shapley_out or mark_donor_epistasis_out or mark_donor_sampled_shapley_out or window_donor_shapley_out
-                 or fine_window_donor_shapley_out or mark_donor_interactions_out)
+                 or fine_window_donor_shapley_out or mark_donor_interactions_out or mark_donor_sampled_interactions_out)
+    if pairs_kw:      # (the geometry the generator checks the model against)
+        pairs_ds = ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False)
     raw_donor_ds = None
     if raw_donor_ig_dir:      # (before anything is computed)
         from .attribution import same_regions
@@ -658,7 +697,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         from .attribution import same_regions
         if not donor_npy_dir:
             raise ValueError("predict: mark_donor_shapley_out / mark_donor_epistasis_out / mark_donor_sampled_shapley_out / "
-                             "window_donor_shapley_out / fine_window_donor_shapley_out / mark_donor_interactions_out need donor_npy_dir")
+                             "window_donor_shapley_out / fine_window_donor_shapley_out / mark_donor_interactions_out / "
+                             "mark_donor_sampled_interactions_out need donor_npy_dir")
         donor_ds = ChromoformerDataset(donor_meta or meta_path, donor_npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False)
         same_regions(ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False), donor_ds)
     packed = pack.find(npy_dir, store_path, list(binsizes), i_max, w_prom, w_max, 7, genes, meta=meta)
@@ -697,6 +737,9 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         if mark_donor_sampled_shapley_out:
             write_mark_sampled_values(model, store, donor_store, bsz, genes, mark_donor_sampled_shapley_out, regression, mark_sampled_players,
                                       mark_perms, mark_seed)
+        if mark_donor_sampled_interactions_out:
+            write_mark_sampled_interactions(model, pairs_ds, donor_ds, store, donor_store, bsz, genes, mark_donor_sampled_interactions_out, regression,
+                                            **pairs_kw)
         if window_donor_shapley_out:
             write_mark_window_values(model, window_ds, donor_ds, store, donor_store, bsz, genes, window_donor_shapley_out, regression, window_players,
                                      window_width, window_perms, window_seed)
@@ -708,6 +751,9 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     if mark_sampled_shapley_out:
         write_mark_sampled_values(model, store, None, bsz, genes, mark_sampled_shapley_out, regression, mark_sampled_players, mark_perms, mark_seed,
                                   mark_scale)
+    if mark_sampled_interactions_out:
+        write_mark_sampled_interactions(model, pairs_ds, None, store, None, bsz, genes, mark_sampled_interactions_out, regression, scale=mark_scale,
+                                        **pairs_kw)
     if window_shapley_out:
         write_mark_window_values(model, window_ds, None, store, None, bsz, genes, window_shapley_out, regression, window_players, window_width,
                                  window_perms, window_seed, window_scale)
@@ -842,6 +888,17 @@ def build_parser():
                     "[n_genes, i_max + 1, 7]), or the specs of --mark-players")
     ap.add_argument("--mark-perms", type=int, default=None, help="sampled orders of adding the players (default 64); each costs P - 1 forwards per gene")
     ap.add_argument("--mark-seed", type=int, default=None, help="seed of the sampled orders (default 0)")
+    ap.add_argument("--mark-sampled-interactions-out", default=None, help="also write the SAMPLED pairwise Shapley interaction index of each gene's "
+                    "focal mark players with every player to this .npz file, in metadata order and in LOGIT space of the prediction's column: "
+                    "gene_ids, players (names), index, permutations, focal [n_genes, n_focal], interactions and stderr [n_genes, n_focal, P] (the "
+                    "standard error over the sampled orders: the sampling error is reported, not bounded), phi and phi_stderr [n_genes, P], "
+                    "logits and absent (model.mark_shapley_interactions_sampled).  --mark-focal, --mark-sampled-players, --mark-perms, "
+                    "--mark-seed, --mark-scale and --interaction-index apply")
+    ap.add_argument("--mark-donor-sampled-interactions-out", default=None, help="the same against the donor cell type of --donor-npy-dir: an "
+                    "absent player takes the donor's signal")
+    ap.add_argument("--mark-focal", default=None, help="the focal players of --mark-sampled-interactions-out / "
+                    "--mark-donor-sampled-interactions-out: a number K (default 4): each gene's K strongest players by |phi| of a sampled Shapley "
+                    "estimate on the same orders; or player names separated by commas (mark3@pcre0,mark0@promoter): those for every gene")
     from .attribution import WINDOW_PLAYER_SPECS
     ap.add_argument("--window-shapley-out", default=None, help="also write the Shapley values of WINDOW players -- stretches of a region, in "
                     "coarsest bins -- to this .npz file, in metadata order and in LOGIT space of the prediction's column: gene_ids, players "
@@ -912,9 +969,34 @@ def main(argv=None):
         if v is not None and v < 1:
             ap.error("--fine-scan-%s must be at least 1" % name)
     donor_exact = args.mark_donor_shapley_out or args.mark_donor_epistasis_out or args.mark_donor_interactions_out
-    if args.interaction_index is not None and not (args.pcre_interactions_out or args.mark_interactions_out or args.mark_donor_interactions_out):
-        ap.error("--interaction-index needs --pcre-interactions-out, --mark-interactions-out or --mark-donor-interactions-out")
-    donor_out = donor_exact or args.mark_donor_sampled_shapley_out or args.window_donor_shapley_out or args.fine_window_donor_shapley_out
+    pairs_out = args.mark_sampled_interactions_out or args.mark_donor_sampled_interactions_out
+    if args.interaction_index is not None and not (args.pcre_interactions_out or args.mark_interactions_out or args.mark_donor_interactions_out
+                                                   or pairs_out):
+        ap.error("--interaction-index needs --pcre-interactions-out, --mark-interactions-out or --mark-donor-interactions-out"
+                 " (or --mark-sampled-interactions-out, --mark-donor-sampled-interactions-out)")
+    mark_focal = 4
+    if args.mark_focal is not None:
+        if not pairs_out:
+            ap.error("--mark-focal needs --mark-sampled-interactions-out or --mark-donor-sampled-interactions-out")
+        if args.mark_focal.strip().lstrip("+-").isdigit():
+            mark_focal = int(args.mark_focal)
+            if mark_focal < 1:
+                ap.error("--mark-focal must be at least 1 player (or a list of player names)")
+        else:
+            mark_focal = [s.strip() for s in args.mark_focal.split(",")]
+    if pairs_out:      # (the players' names: a bad count or name is a usage error)
+        from .attribution import focal_players, mark_players_wide
+        pair_names = mark_players_wide(args.mark_sampled_players or "cells", 7, 8)[2]      # (predict()'s n_feats and default i_max)
+        try:
+            if isinstance(mark_focal, int):
+                if mark_focal > len(pair_names):
+                    raise ValueError("K = %d exceeds the %d players" % (mark_focal, len(pair_names)))
+            else:
+                focal_players(mark_focal, pair_names, len(pair_names))
+        except ValueError as e:
+            ap.error("--mark-focal: %s" % e)
+    donor_out = (donor_exact or args.mark_donor_sampled_shapley_out or args.window_donor_shapley_out or args.fine_window_donor_shapley_out
+                 or args.mark_donor_sampled_interactions_out)
     if args.raw_donor_ig_dir and not args.donor_npy_dir:
         ap.error("--raw-donor-ig-dir needs --donor-npy-dir")
     if args.raw_donor_ig_dir and args.donor_store:
@@ -922,15 +1004,18 @@ def main(argv=None):
     sampled_out = args.mark_sampled_shapley_out or args.mark_donor_sampled_shapley_out
     if donor_out and not args.donor_npy_dir:
         ap.error("--mark-donor-shapley-out / --mark-donor-epistasis-out / --mark-donor-sampled-shapley-out / --window-donor-shapley-out / "
-                 "--fine-window-donor-shapley-out / --mark-donor-interactions-out need --donor-npy-dir")
+                 "--fine-window-donor-shapley-out / --mark-donor-interactions-out / --mark-donor-sampled-interactions-out need --donor-npy-dir")
     if not donor_out and not args.raw_donor_ig_dir and (args.donor_npy_dir or args.donor_meta or args.donor_store):
         ap.error("--donor-npy-dir / --donor-meta / --donor-store need --mark-donor-shapley-out, --mark-donor-epistasis-out or "
-                 "--mark-donor-sampled-shapley-out (or --window-donor-shapley-out, --fine-window-donor-shapley-out)")
-    if not sampled_out and (args.mark_sampled_players is not None or args.mark_perms is not None or args.mark_seed is not None):
-        ap.error("--mark-sampled-players / --mark-perms / --mark-seed need --mark-sampled-shapley-out or --mark-donor-sampled-shapley-out")
+                 "--mark-donor-sampled-shapley-out (or --window-donor-shapley-out, --fine-window-donor-shapley-out, "
+                 "--mark-donor-interactions-out, --mark-donor-sampled-interactions-out)")
+    if not sampled_out and not pairs_out and (args.mark_sampled_players is not None or args.mark_perms is not None or args.mark_seed is not None):
+        ap.error("--mark-sampled-players / --mark-perms / --mark-seed need --mark-sampled-shapley-out or --mark-donor-sampled-shapley-out"
+                 " (or --mark-sampled-interactions-out, --mark-donor-sampled-interactions-out)")
     if args.mark_perms is not None and args.mark_perms < 1:
         ap.error("--mark-perms must be at least 1")
-    if not args.mark_shapley_out and not args.mark_epistasis_out and not args.mark_interactions_out and ((args.mark_scale is not None and not args.mark_sampled_shapley_out)
+    if not args.mark_shapley_out and not args.mark_epistasis_out and not args.mark_interactions_out and ((args.mark_scale is not None and not args.mark_sampled_shapley_out
+                                                                                                          and not args.mark_sampled_interactions_out)
                                                                                                          or (args.mark_players is not None and not donor_exact)):
         ap.error("--mark-players / --mark-scale need --mark-shapley-out, --mark-epistasis-out or --mark-interactions-out"
                  " (--mark-players also applies to --mark-donor-shapley-out / --mark-donor-epistasis-out, --mark-scale to"
@@ -1010,7 +1095,9 @@ def main(argv=None):
                          fine_window_seed=0 if args.fine_window_seed is None else args.fine_window_seed,
                          fine_window_scale=0.0 if args.fine_window_scale is None else args.fine_window_scale,
                          pcre_interactions_out=args.pcre_interactions_out, mark_interactions_out=args.mark_interactions_out,
-                         mark_donor_interactions_out=args.mark_donor_interactions_out, interaction_index=args.interaction_index or "sii")
+                         mark_donor_interactions_out=args.mark_donor_interactions_out, interaction_index=args.interaction_index or "sii",
+                         mark_sampled_interactions_out=args.mark_sampled_interactions_out,
+                         mark_donor_sampled_interactions_out=args.mark_donor_sampled_interactions_out, mark_focal=mark_focal)
     print("Predicting expressions for %d genes." % len(meta))
     meta["prediction"] = pred
     meta.to_csv(args.output, index=False)

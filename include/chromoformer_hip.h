@@ -734,6 +734,46 @@ int cf_mark_fine_shapley_interactions(cf_handle* h, const cf_batch* batch, const
  * exactly 0.  Refusals as above and as there. */
 int cf_mark_fine_shapley_sampled(cf_handle* h, const cf_batch* batch, const cf_mark_fine_opts* opts, const uint8_t* perms, int n_perm, float* phi,
                                  float* se, float* logits_rows, void* stream);
+/* Permutation-SAMPLED pairwise Shapley interaction indices of a few FOCAL players of a wide game (up to 128 players): for the players
+ * that carry the prediction, which other players do they interact with?  perms as in cf_mark_shapley_sampled; focal: HOST ints
+ * [n_focal], distinct players.  For focal player i and order pi, o = pi with i removed, T_k the first k players of o, r the position of
+ * i in pi.  For j = o[a]:
+ *   d(j) = (v(T_{a+1} + i) - v(T_{a+1})) - (v(T_a + i) - v(T_a))         three fp32 subtractions, in this grouping
+ *   CF_INTERACTION_SII  s_q = d(j)             (T_a has the law a! (P - 2 - a)! / (P - 1)! over uniform orders: unbiased)
+ *   CF_INTERACTION_STI  s_q = w_a d(j),  w_a = 2 (P - 1 - a) / P in double, rounded to fp32; one rounded product
+ *   inter[b, f, j] = (sum_q s_q) / n_perm,   se[b, f, j] = sqrt(sum_q (s_q - inter)^2 / (n_perm (n_perm - 1)))    0 for n_perm = 1
+ * in the summation order of k_perm_shapley, no atomics: the result does not depend on max_batch.  The diagonal j = focal[f]: SII the
+ * bits of cf_mark_shapley_sampled's phi and se on the same orders; STI v({i}) - v(nobody), se 0.  If i or j is a null player d(j) = 0
+ * bit for bit: inter and se are exactly 0.  The estimate is NOT symmetric: inter[i, j] from focal i and inter[j, i] from focal j are
+ * different samples.  Its sampling error is what se reports; the library does not bound it.
+ * Rows per gene (R of them, through the routine of cf_mark_coalitions_wide):
+ *   the R0 = 2 + n_perm (P - 1) rows of cf_mark_shapley_sampled, unchanged, then per focal player f in the order given:
+ *   {i} alone;  everybody but i;  then per order q the rows T_k + i, k = 1 .. r - 1, then the rows T_k, k = r + 1 .. P - 2
+ * (T_k = pi[:k] for k <= r and T_k + i = pi[:k + 1] for k >= r are rows of the leading block): P - 3 rows per (f, q) for
+ * 1 <= r <= P - 2, P - 2 for r = 0 or P - 1.  The host builds the words and a column table col[f, q, k, {without, with}] (uint32) that
+ * travels in the word table behind the inverse permutations; k_perm_pairs reads columns through it.
+ * inter, se [B, n_focal, P, n_out]; se NULL: not computed.  phi, phi_se [B, P, n_out] or NULL: the sampled Shapley values of every
+ * player from the leading rows (k_perm_shapley; the bits of cf_mark_shapley_sampled).  logits_rows [B, R, n_out] or NULL.
+ * fwd = that of cf_mark_coalitions_wide with n_coal = R, plus 1, plus 1 if phi is given.
+ * Refused by name, before anything is launched: what cf_mark_shapley_sampled refuses (phi may be null), null inter, null focal,
+ * n_focal outside 1..P, a focal index outside 0..P-1 or repeated (its position is named), index outside {SII, STI}, P < 2, phi_se
+ * without phi, more than 2^30 coalition words. */
+int cf_mark_shapley_interactions_sampled(cf_handle* h, const cf_batch* batch, const cf_mark_wide_opts* opts, const uint8_t* perms, int n_perm,
+                                         const int* focal, int n_focal, int index, float* inter, float* se, float* phi, float* phi_se,
+                                         float* logits_rows, void* stream);
+/* The same for window players (cf_mark_window_coalitions' game) and fine window players (cf_mark_fine_coalitions' game; feats_out
+ * then holds R rows per gene). */
+int cf_mark_window_shapley_interactions_sampled(cf_handle* h, const cf_batch* batch, const cf_mark_window_opts* opts, const uint8_t* perms,
+                                                int n_perm, const int* focal, int n_focal, int index, float* inter, float* se, float* phi,
+                                                float* phi_se, float* logits_rows, void* stream);
+int cf_mark_fine_shapley_interactions_sampled(cf_handle* h, const cf_batch* batch, const cf_mark_fine_opts* opts, const uint8_t* perms,
+                                              int n_perm, const int* focal, int n_focal, int index, float* inter, float* se, float* phi,
+                                              float* phi_se, float* logits_rows, void* stream);
+/* The operator on a caller's device table rows [B, R, n_out] in the layout above (for instance a kept logits_rows), 2 <= P <= 128: no
+ * batch, no chunk workspace; of the handle only the word table is used (the inverse permutations and col).  fwd = 1, plus 1 if phi is
+ * given.  Refusals: null handle / rows, B < 1, n_out < 1, P > 128 and those above. */
+int cf_perm_interactions_from_rows(cf_handle* h, const float* rows, int B, int P, int n_out, const uint8_t* perms, int n_perm, const int* focal,
+                                   int n_focal, int index, float* inter, float* se, float* phi, float* phi_se, void* stream);
 /* torch.optim.AdamW.step (train.py:157, 196): decoupled weight decay, bias correction
  * from `step` (1-based), over [0, n_active). */
 int cf_adamw_step(cf_handle* h, float lr, float beta1, float beta2, float eps, float weight_decay,
