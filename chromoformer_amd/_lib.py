@@ -182,6 +182,9 @@ SYMBOLS = {
     "cf_pcre_shapley": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_pcre_epistasis": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_shapley_interactions_from_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cf_dividends_from_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cf_set_interactions_from_dividends": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                     C.c_void_p]),
     "cf_pcre_shapley_interactions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_integrated_gradients": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_ig_opts), C.POINTER(cf_input_grads), C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),

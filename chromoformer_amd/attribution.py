@@ -211,6 +211,101 @@ def interaction_weights(P, index="sii"):
     return np.array([(2.0 / P) / comb(P - 1, s) for s in range(P - 1)], dtype=np.float64)
 
 
+def _popcount(words):
+    """The number of players in each uint32 word -> int64, the shape of `words`."""
+    words = np.asarray(words, dtype=np.uint32)
+    n = np.zeros(words.shape, dtype=np.int64)
+    for k in range(32):
+        n += (words >> np.uint32(k)) & np.uint32(1)
+    return n
+
+
+def _order_check(who, P, order):
+    P, order = int(P), int(order)
+    if not 1 <= P <= 16:
+        raise ValueError("%s: P = %d outside 1..16" % (who, P))
+    if not 1 <= order <= P:
+        raise ValueError("%s: order = %d outside 1..P = %d" % (who, order, P))
+    return P, order
+
+
+def interaction_sets(P, order):
+    """The words of every set of 1..order of P players -> uint32 [n]: bit p set = player p in the set, ordered by size and then by
+    ascending word (P = 16, order = 3: 16 + 120 + 560 = 696 sets).  1 <= order <= P <= 16."""
+    P, order = _order_check("interaction_sets", P, order)
+    words = np.arange(1, 1 << P, dtype=np.uint32)
+    size = _popcount(words)
+    words, size = words[size <= order], size[size <= order]
+    return np.ascontiguousarray(words[np.argsort(size, kind="stable")])
+
+
+def set_interaction_weights(P, index="sii", order=2):
+    """The weights that turn Harsanyi dividends into an interaction index of top order `order` -> float64 [order + 1, P + 1]:
+    index(S) = sum over U >= S of w[|S|, |U|] dividend(U); entries with |U| < |S| and row 0 are 0.  "sii": 1 / (|U| - |S| + 1) -- the
+    Shapley value at |S| = 1, the pairwise Shapley interaction index at |S| = 2.  "sti" (Shapley-Taylor of order k = `order`): a set
+    below the top order gets its own dividend (w = 1 at U = S alone), a set of size k gets 1 / C(|U|, k); the index then sums to
+    v(everybody) - v(nobody) over all sets of size 1..k.  The library computes the same table in double and rounds it to fp32."""
+    from math import comb
+    interaction_index(index, "set_interaction_weights")
+    P, order = _order_check("set_interaction_weights", P, order)
+    w = np.zeros((order + 1, P + 1), dtype=np.float64)
+    for s in range(1, order + 1):
+        for u in range(s, P + 1):
+            if index == "sii":
+                w[s, u] = 1.0 / (u - s + 1)
+            elif s == order:
+                w[s, u] = 1.0 / comb(u, order)
+            else:
+                w[s, u] = 1.0 if u == s else 0.0
+    return w
+
+
+def set_names(words, names):
+    """The names of sets of players given as words -> a list of strings: the players' names in ascending bit order joined by "*"
+    ("mark0*mark3"); the empty set is "" .  A word with a bit >= len(names) raises ValueError."""
+    names = list(names)
+    out = []
+    for k, w in enumerate(np.asarray(words).reshape(-1).tolist()):
+        w = int(w)
+        if w < 0 or w >> len(names):
+            raise ValueError("set_names: words[%d] = 0x%x names a player >= %d" % (k, w, len(names)))
+        out.append("*".join(names[p] for p in range(len(names)) if w >> p & 1))
+    return out
+
+
+def dividend_bound(mass, P):
+    """The rounding bound of the fp32 dividends -> an array of the shape of `mass` ([..., 2^P, n_out], numpy or anything np.asarray
+    takes), float64: |dividend(S) - exact| <= ((1 + 2^-24)^|S| - 1) mass(S), since the element passes through |S| subtractions, each
+    with a relative error of at most 2^-24, of quantities whose magnitudes sum to at most mass(S) = sum over T <= S of |v(T)|.  The
+    fp32 `mass` itself is |S| rounded additions of non-negative numbers, so it may fall short of the exact sum by a factor
+    (1 - 2^-24)^|S|: the bound is widened by (1 - 2^-24)^-|S|.  A dividend smaller than its bound is rounding noise."""
+    P = int(P)
+    m = np.asarray(mass, dtype=np.float64)
+    if m.ndim < 2 or m.shape[-2] != 1 << P:
+        raise ValueError("dividend_bound: mass has shape %s; expected [..., 2^P = %d, n_out]" % (m.shape, 1 << P))
+    size = _popcount(np.arange(1 << P, dtype=np.uint32)).astype(np.float64)
+    u = 2.0 ** -24
+    factor = ((1.0 + u) ** size - 1.0) * (1.0 - u) ** -size
+    return m * factor[:, None]
+
+
+def top_dividends(div, names, k=10, min_order=1):
+    """The k largest dividends of one gene by magnitude among the sets of at least min_order players -> a list of (set name, word,
+    value) with value float32 [n_out], sorted by falling max |value| over the outputs.  div: [2^P, n_out] (numpy or a tensor's
+    .cpu().numpy()), names: the P players' names."""
+    d = np.asarray(div)
+    P = len(names)
+    if d.ndim != 2 or d.shape[0] != 1 << P:
+        raise ValueError("top_dividends: div has shape %s; expected [2^P = %d, n_out] for %d names" % (d.shape, 1 << P, P))
+    if int(k) < 1 or int(min_order) < 0:
+        raise ValueError("top_dividends: k >= 1 and min_order >= 0")
+    words = np.arange(1 << P, dtype=np.uint32)
+    words = words[_popcount(words) >= int(min_order)]
+    mag = np.abs(d[words]).max(axis=1)
+    pick = words[np.argsort(-mag, kind="stable")[:int(k)]]
+    return [(nm, int(w), d[w].copy()) for nm, w in zip(set_names(pick, names), pick)]
+
+
 def shapley_permutations(P, n_perm, seed=0):
     """n_perm independent uniform orders of P players -> uint8 [n_perm, P], each row a permutation of 0..P-1, from
     numpy.random.Generator(PCG64(seed)): the same seed gives the same orders."""
@@ -1019,7 +1114,8 @@ def perturbation_scan_fine(model, dataset, genes=None, region="promoter", zoom=N
             yield p
 
 
-def mark_shapley(model, dataset, genes=None, players="marks", scale=0.0, epistasis=False, bsz=None, store=None, interactions=None):
+def mark_shapley(model, dataset, genes=None, players="marks", scale=0.0, epistasis=False, bsz=None, store=None, interactions=None,
+                 dividends=False):
     """Exact Shapley values of the histone marks for the genes of a ChromoformerDataset (one model.mark_shapley per batch, with
     epistasis=True also one model.mark_epistasis): which marks carry the prediction when an absent mark's raw signal is scaled by
     `scale` (0 erases it) over the regions of its player.  A generator over `genes` (ids; default: the dataset's) in chunks of at most
@@ -1033,6 +1129,9 @@ def mark_shapley(model, dataset, genes=None, players="marks", scale=0.0, epistas
         eps       float32 [P, P, n_out], with epistasis=True: the pair epistasis, the leave-one-out effects on the diagonal
         interactions  float32 [P, P, n_out], with interactions="sii" / "sti": the pairwise Shapley interaction index; the batch then makes
                   one model.mark_shapley_interactions call in place of model.mark_shapley (the 2^P forwards run once; phi keeps its bits)
+        dividends, mass  float32 [2^P, n_out] each, with dividends=True: the Harsanyi dividend of every set of players, word m at row m
+                  (set_names names them), and the scale of its rounding error (dividend_bound); model.shapley_dividends on the table of
+                  the batch's one Shapley call: no forward is added
 
     players: "marks", "compartments", "regions" or a list of (marks, regions) pairs (mark_players).  The binned features come from
     `store` (a device-resident GeneStore holding `genes` in order) if given, else from the packed store next to the raw files if one
@@ -1053,10 +1152,11 @@ def mark_shapley(model, dataset, genes=None, players="marks", scale=0.0, epistas
         args = tuple(d[k] for k in _BATCH_KEYS)
         inter = None
         if interactions is None:
-            phi, info = model.mark_shapley(*args, players=spec, scale=scale)
+            phi, info = model.mark_shapley(*args, players=spec, scale=scale, return_coalitions=bool(dividends))
         else:
-            inter, info = model.mark_shapley_interactions(*args, players=spec, scale=scale, index=interactions)
+            inter, info = model.mark_shapley_interactions(*args, players=spec, scale=scale, index=interactions, return_coalitions=bool(dividends))
             phi, inter = info["phi"], inter.cpu().numpy()
+        div, mass = _batch_dividends(model, info, dividends)
         phi, logits, erased = phi.cpu().numpy(), info["logits"].cpu().numpy(), info["erased"].cpu().numpy()
         eps = model.mark_epistasis(*args, players=spec, scale=scale)[0].cpu().numpy() if epistasis else None
         for i, g in enumerate(ids):
@@ -1065,7 +1165,17 @@ def mark_shapley(model, dataset, genes=None, players="marks", scale=0.0, epistas
                 out["eps"] = eps[i].copy()
             if inter is not None:
                 out["interactions"] = inter[i].copy()
+            if div is not None:
+                out["dividends"], out["mass"] = div[i].copy(), mass[i].copy()
             yield out
+
+
+def _batch_dividends(model, info, dividends):
+    """(dividends, mass) of a batch as host arrays [B, 2^P, n_out] from the coalition table its exact Shapley call kept, or (None, None)."""
+    if not dividends:
+        return None, None
+    div, mass = model.shapley_dividends(info["coalitions"], return_mass=True)
+    return div.cpu().numpy(), mass.cpu().numpy()
 
 
 def same_regions(dataset, donor_dataset, genes=None):
@@ -1100,7 +1210,7 @@ def same_regions(dataset, donor_dataset, genes=None):
 
 
 def mark_donor_shapley(model, dataset, donor_dataset, genes=None, players="marks", epistasis=False, bsz=None, store=None, donor_store=None,
-                       interactions=None):
+                       interactions=None, dividends=False):
     """Exact Shapley values of the histone marks against a donor cell type, for the genes of two ChromoformerDatasets over the same
     regions (same_regions): one model.mark_donor_shapley per batch, with epistasis=True also one model.mark_donor_epistasis -- which
     mark changes account for the difference between the prediction in `dataset` and in `donor_dataset`?  A generator over `genes`
@@ -1116,6 +1226,7 @@ def mark_donor_shapley(model, dataset, donor_dataset, genes=None, players="marks
         eps                float32 [P, P, n_out], with epistasis=True: the pair epistasis, the leave-one-out effects on the diagonal
         interactions       float32 [P, P, n_out], with interactions="sii" / "sti": the pairwise Shapley interaction index; the batch then
                            makes one model.mark_donor_shapley_interactions call in place of model.mark_donor_shapley
+        dividends, mass    float32 [2^P, n_out] each, with dividends=True: as in mark_shapley
 
     players as in mark_shapley.  The binned features come from `store` / `donor_store` (device-resident GeneStores holding `genes` in
     order) if given, else from the packed store next to each dataset's raw files if one matches, else from the raw .npy files binned
@@ -1141,10 +1252,11 @@ def mark_donor_shapley(model, dataset, donor_dataset, genes=None, players="marks
         donor = _donor_pair(dd)
         inter = None
         if interactions is None:
-            phi, info = model.mark_donor_shapley(*args, donor=donor, players=spec)
+            phi, info = model.mark_donor_shapley(*args, donor=donor, players=spec, return_coalitions=bool(dividends))
         else:
-            inter, info = model.mark_donor_shapley_interactions(*args, donor=donor, players=spec, index=interactions)
+            inter, info = model.mark_donor_shapley_interactions(*args, donor=donor, players=spec, index=interactions, return_coalitions=bool(dividends))
             phi, inter = info["phi"], inter.cpu().numpy()
+        div, mass = _batch_dividends(model, info, dividends)
         phi, logits, don = phi.cpu().numpy(), info["logits"].cpu().numpy(), info["donor"].cpu().numpy()
         eps = model.mark_donor_epistasis(*args, donor=donor, players=spec)[0].cpu().numpy() if epistasis else None
         with torch.no_grad():
@@ -1156,6 +1268,8 @@ def mark_donor_shapley(model, dataset, donor_dataset, genes=None, players="marks
                 out["eps"] = eps[i].copy()
             if inter is not None:
                 out["interactions"] = inter[i].copy()
+            if div is not None:
+                out["dividends"], out["mass"] = div[i].copy(), mass[i].copy()
             yield out
 
 
@@ -1291,7 +1405,7 @@ def window_player_coordinates(marks_regions_windows, regions, n_real, binsize):
 
 
 def mark_window_shapley(model, dataset, donor_dataset=None, genes=None, players="promoter", width=1, n_perm=64, seed=0, scale=0.0, bsz=None,
-                        store=None, donor_store=None, interactions=None):
+                        store=None, donor_store=None, interactions=None, dividends=False):
     """Shapley values of WINDOW players for the genes of a ChromoformerDataset: where inside a region does the signal lie?  With at most
     16 players one model.mark_window_shapley per batch (exact), else one model.mark_window_shapley_sampled (n_perm orders from `seed`).
     Without `donor_dataset` an absent player's raw signal inside its window is scaled by `scale` (0 erases it); with one -- the same
@@ -1312,6 +1426,8 @@ def mark_window_shapley(model, dataset, donor_dataset=None, genes=None, players=
         interactions   float32 [P, P, n_out], with interactions="sii" / "sti": the pairwise Shapley interaction index of the players (a
                        null player's row and column are 0); the batch then makes one model.mark_window_shapley_interactions call in
                        place of model.mark_window_shapley.  The index has no sampled estimator: more than 16 players raise ValueError
+        dividends, mass  float32 [2^P, n_out] each, with dividends=True: as in mark_shapley (a set that holds a null player is 0); the
+                       exact game only: more than 16 players raise ValueError
 
     Strand and coordinates come from the dataset's metadata.  The binned features come from `store` / `donor_store` as in
     mark_donor_shapley.  Parameters, gradients and optimiser state are left as they are; the pass overwrites the activations a
@@ -1336,6 +1452,9 @@ def mark_window_shapley(model, dataset, donor_dataset=None, genes=None, players=
         if not exact:
             raise ValueError("%s: interactions: %d players; the index is computed by the exact game of at most 16 players: choose a "
                              "larger width" % (who, P))
+    if dividends and not exact:
+        raise ValueError("%s: dividends: %d players; the dividends are those of the exact game of at most 16 players: choose a larger width"
+                         % (who, P))
     perms = None if exact else shapley_permutations(P, n_perm, seed)
     col0 = promoter_col0(ds)
     store = _resident_store(who, ds, genes, binsizes, model._device, store)
@@ -1352,14 +1471,16 @@ def mark_window_shapley(model, dataset, donor_dataset=None, genes=None, players=
             donor = _donor_pair(dd)
         flip = [ds.genes[g]["tss"][2] != "+" for g in ids]
         args = tuple(d[k] for k in _BATCH_KEYS)
-        inter = None
+        inter, div = None, None
         if exact:
             if interactions is None:
-                phi, info = model.mark_window_shapley(*args, players=spec, width=width, scale=scale, donor=donor, flip=flip)
+                phi, info = model.mark_window_shapley(*args, players=spec, width=width, scale=scale, donor=donor, flip=flip,
+                                                      return_coalitions=bool(dividends))
             else:
                 inter, info = model.mark_window_shapley_interactions(*args, players=spec, width=width, scale=scale, donor=donor, flip=flip,
-                                                                     index=interactions)
+                                                                     index=interactions, return_coalitions=bool(dividends))
                 phi, inter = info["phi"], inter.cpu().numpy()
+            div, mass = _batch_dividends(model, info, dividends)
             absent = info["erased" if donor is None else "donor"].cpu().numpy()
             se = np.zeros(tuple(phi.shape), dtype=np.float32)
         else:
@@ -1384,11 +1505,14 @@ def mark_window_shapley(model, dataset, donor_dataset=None, genes=None, players=
                 out["permutations"] = perms.copy()
             if inter is not None:
                 out["interactions"] = inter[i].copy()
+            if div is not None:
+                out["dividends"], out["mass"] = div[i].copy(), mass[i].copy()
             yield out
 
 
 def mark_fine_window_shapley(model, dataset, donor_dataset=None, genes=None, region="promoter", zoom=1, coarse_width=1, width=2, players="windows",
-                             n_perm=64, seed=0, scale=0.0, target=None, bsz=None, store=None, donor_store=None, interactions=None):
+                             n_perm=64, seed=0, scale=0.0, target=None, bsz=None, store=None, donor_store=None, interactions=None,
+                             dividends=False):
     """Shapley values of FINE window players for the genes of a ChromoformerDataset: which 200 bp of this peak?  Per batch the coarse
     window game runs first (model.mark_window_shapley over `region` at `coarse_width` coarsest bins per player, exact with at most 16
     players, else sampled); per gene the `zoom` coarse windows with the largest |phi| at logit `target` (default: the last) are chosen,
@@ -1415,6 +1539,9 @@ def mark_fine_window_shapley(model, dataset, donor_dataset=None, genes=None, reg
                         that rank's fine players with a real window, in their order above; the fine game then makes one
                         model.mark_fine_window_shapley_interactions call in place of model.mark_fine_window_shapley (the coarse game is
                         unchanged).  The index has no sampled estimator: more than 16 fine players raise ValueError
+        dividends, mass with dividends=True: per rank a float32 [2^P, n_out] over ALL P players of the fine game (bit p = the player of
+                        `index` p; a set that holds a player without a real window is 0), and the scale of the rounding error
+                        (dividend_bound); the exact fine game only: more than 16 fine players raise ValueError
 
     Strand, coordinates and the region's length come from the dataset's metadata: '-' strand promoters are stored mirrored (window 0 is
     still the genomic start) and the short last bin of a pCRE is weighted by the samples it holds.  Features, stores, parameters and
@@ -1448,6 +1575,9 @@ def mark_fine_window_shapley(model, dataset, donor_dataset=None, genes=None, reg
         if not exact:
             raise ValueError("%s: interactions: %d fine players; the index is computed by the exact game of at most 16 players: choose a "
                              "larger width or a smaller coarse_width" % (who, P))
+    if dividends and not exact:
+        raise ValueError("%s: dividends: %d fine players; the dividends are those of the exact game of at most 16 players: choose a larger "
+                         "width or a smaller coarse_width" % (who, P))
     perms = None if exact else shapley_permutations(P, n_perm, seed)
     coarse = [(list(range(F)), [region], (g, min(g + coarse_width, W))) for g in range(0, W, coarse_width)]
     Pc = len(coarse)
@@ -1487,17 +1617,20 @@ def mark_fine_window_shapley(model, dataset, donor_dataset=None, genes=None, reg
                             logits=logits[i].copy(), absent=np.zeros((0, model.n_out), np.float32), exact=exact))
             if interactions is not None:
                 per[-1]["interactions"] = []
+            if dividends:
+                per[-1]["dividends"], per[-1]["mass"] = [], []
         for rank in range(max([len(z) for z in ranks] + [0])):
             # a gene with fewer real coarse windows than ranks starts past its region: null players, left out below
             start = [int(z[rank]) * coarse_width * Rc if rank < len(z) else Lf for z in ranks]
             kw = dict(region=region, players=spec, width=width, n_windows=n_fw, start=start, lengths=lengths, scale=scale, donor=donor, flip=flip)
-            inter = None
+            inter, div = None, None
             if exact:
                 if interactions is None:
-                    phi, info = model.mark_fine_window_shapley(*args, **kw)
+                    phi, info = model.mark_fine_window_shapley(*args, return_coalitions=bool(dividends), **kw)
                 else:
-                    inter, info = model.mark_fine_window_shapley_interactions(*args, index=interactions, **kw)
+                    inter, info = model.mark_fine_window_shapley_interactions(*args, index=interactions, return_coalitions=bool(dividends), **kw)
                     phi, inter = info["phi"], inter.cpu().numpy()
+                div, mass = _batch_dividends(model, info, dividends)
                 absent, se = info["erased" if donor is None else "donor"].cpu().numpy(), None
             else:
                 phi, info = model.mark_fine_window_shapley_sampled(*args, permutations=perms, **kw)
@@ -1518,5 +1651,8 @@ def mark_fine_window_shapley(model, dataset, donor_dataset=None, genes=None, reg
                 per[i]["absent"] = np.concatenate([per[i]["absent"], absent[i][None]])
                 if inter is not None:
                     per[i]["interactions"].append(inter[i][np.ix_(real, real)].copy())
+                if div is not None:
+                    per[i]["dividends"].append(div[i].copy())
+                    per[i]["mass"].append(mass[i].copy())
         for p in per:
             yield p

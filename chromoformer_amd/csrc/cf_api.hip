@@ -7,6 +7,7 @@
 #include "cf_attn_maps.h"
 #include "cf_rows.h"
 #include "cf_coalition.h"
+#include "cf_dividends.h"
 #include "cf_ig.h"
 #include "cf_scan.h"
 #include "cf_marks.h"

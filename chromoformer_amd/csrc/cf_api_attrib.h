@@ -404,6 +404,75 @@ extern "C" int cf_shapley_interactions_from_rows(cf_handle* h, const float* rows
     h->n_fwd = 0;
     return launch_shapley_pairs(h, B, P, index, rows, inter, (hipStream_t)stream);
 }
+// The Harsanyi dividends of a caller's table (cf_dividends.h): k_moebius, and above one LDS tile k_moebius_high in place on its output.
+// An operator as the one above: no batch, no workspace, no activation is touched.
+extern "C" int cf_dividends_from_rows(cf_handle* h, const float* rows, int B, int P, float* div, float* mass, void* stream) {
+    const char* who = "cf_dividends_from_rows";
+    if (!h) return fail("%s: null handle", who);
+    if (!rows) return fail("%s: null rows", who);
+    if (!div) return fail("%s: null div", who);
+    if (B < 1) return fail("%s: B = %d: at least 1 gene", who, B);
+    if (P < 1 || P > kCoalMaxS) return fail("%s: P = %d outside 1..%d", who, P, kCoalMaxS);
+    static_assert(kCoalMaxS - kDivTileBits == 4, "k_moebius_high is instantiated for 1..4 stages");
+    hipStream_t st = (hipStream_t)stream;
+    MoebiusArgs ma;
+    ma.v = rows, ma.div = div, ma.mass = mass, ma.P = P, ma.n_out = h->cfg.n_out;      // n_out <= kDivMaxOut: cf_create
+    const int tables = mass ? 2 : 1, high = P - kDivTileBits;
+    h->n_fwd = 0;
+    hipLaunchKernelGGL(k_moebius, dim3(B, high > 0 ? 1 << high : 1, tables), dim3(kDivThreads), 0, st, ma);
+    LAUNCH_CHECK("k_moebius");
+    forward_one_more(h);
+    if (high <= 0) return 0;
+    const dim3 grid(B, kDivTile * ma.n_out / kDivThreads, tables), block(kDivThreads);
+    switch (high) {
+        case 1: hipLaunchKernelGGL(k_moebius_high<1>, grid, block, 0, st, ma); break;
+        case 2: hipLaunchKernelGGL(k_moebius_high<2>, grid, block, 0, st, ma); break;
+        case 3: hipLaunchKernelGGL(k_moebius_high<3>, grid, block, 0, st, ma); break;
+        default: hipLaunchKernelGGL(k_moebius_high<4>, grid, block, 0, st, ma); break;
+    }
+    LAUNCH_CHECK("k_moebius_high");
+    forward_one_more(h);
+    return 0;
+}
+// An interaction index of listed sets from the dividends (k_set_index).  The weight table of `index` with top order `order`, in
+// double, rounded to fp32:  sii wt[|S|][|U|] = 1 / (|U| - |S| + 1);  sti |S| = order: 1 / C(|U|, order), below: the dividend's bits.
+// The set words travel in the handle's word table.
+extern "C" int cf_set_interactions_from_dividends(cf_handle* h, const float* div, int B, int P, const uint32_t* sets, int n_sets, int index,
+                                                  int order, float* out, void* stream) {
+    const char* who = "cf_set_interactions_from_dividends";
+    if (!h) return fail("%s: null handle", who);
+    if (!div) return fail("%s: null div", who);
+    if (!sets) return fail("%s: null sets", who);
+    if (!out) return fail("%s: null out", who);
+    if (B < 1) return fail("%s: B = %d: at least 1 gene", who, B);
+    if (P < 1 || P > kCoalMaxS) return fail("%s: P = %d outside 1..%d", who, P, kCoalMaxS);
+    if (n_sets < 1 || n_sets > 65535) return fail("%s: n_sets = %d outside 1..65535", who, n_sets);
+    if (order < 1 || order > P) return fail("%s: order = %d outside 1..P = %d", who, order, P);
+    if (index != CF_INTERACTION_SII && index != CF_INTERACTION_STI)
+        return fail("%s: index = %d: CF_INTERACTION_SII (%d) or CF_INTERACTION_STI (%d)", who, index, CF_INTERACTION_SII, CF_INTERACTION_STI);
+    for (int s = 0; s < n_sets; ++s) {
+        if (!sets[s]) return fail("%s: sets[%d] is the empty set", who, s);
+        if (sets[s] >> P) return fail("%s: sets[%d] = 0x%x names a player >= P = %d", who, s, sets[s], P);
+        if (__builtin_popcount(sets[s]) > order) return fail("%s: sets[%d] = 0x%x holds %d players, more than order = %d", who, s, sets[s], __builtin_popcount(sets[s]), order);
+    }
+    if (h->aw.words.need(n_sets, 256, who)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(h->aw.words, sets, (size_t)n_sets * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    SetIndexArgs sa;
+    memset(&sa, 0, sizeof sa);
+    sa.div = div, sa.sets = h->aw.words, sa.out = out, sa.P = P, sa.n_out = h->cfg.n_out, sa.n_sets = n_sets;
+    const bool sti = index == CF_INTERACTION_STI;
+    sa.copy_below = sti ? order : 0;
+    double fact[kCoalMaxS + 1] = {1.0};
+    for (int k = 1; k <= P; ++k) fact[k] = fact[k - 1] * k;
+    for (int s = sti ? order : 1; s <= order; ++s)
+        for (int u = s; u <= P; ++u) sa.wt[s - 1][u - 1] = sti ? (float)(1.0 / (fact[u] / (fact[s] * fact[u - s]))) : (float)(1.0 / (u - s + 1));
+    h->n_fwd = 0;
+    hipLaunchKernelGGL(k_set_index, dim3(B, n_sets), dim3(kShapThreads), 0, st, sa);
+    LAUNCH_CHECK("k_set_index");
+    forward_one_more(h);
+    return 0;
+}
 // pair_words: the 1 + P + P (P - 1) / 2 pair-deletion coalitions (N = 2^P - 1; N without i; N without i and j, i < j);
 // launch_epistasis: k_epistasis on those rows.
 static std::vector<uint32_t> pair_words(int P) {

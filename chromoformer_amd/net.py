@@ -592,6 +592,108 @@ class ChromoformerBase(nn.Module):
                    "cf_shapley_interactions_from_rows")
         return inter
 
+    def _table_check(self, who, what, table):
+        """A [B, 2^P, n_out] float32 table on the model's device, contiguous -> (table, B, P)."""
+        if not torch.is_tensor(table) or table.dim() != 3 or table.dtype != torch.float32:
+            raise ValueError("%s: %s must be a float32 tensor [B, 2^P, n_out]" % (who, what))
+        B, n, n_out = table.shape
+        P = n.bit_length() - 1
+        if B < 1 or n != 1 << P or not 1 <= P <= 16 or n_out != self.n_out:
+            raise ValueError("%s: %s has shape %s; expected [B >= 1, 2^P with P in 1..16, n_out = %d]" % (who, what, tuple(table.shape), self.n_out))
+        if self._handle is None:
+            raise RuntimeError("%s: the model is not on a GPU (model.cuda() first); there is no CPU fallback" % who)
+        return table.to(self._device).contiguous(), B, P
+
+    @torch.no_grad()
+    def shapley_dividends(self, coalitions, return_mass=False):
+        """Harsanyi dividends (the Moebius transform) of a kept coalition table (cf_dividends_from_rows) -> div [B, 2^P, n_out] on the
+        model's device, or (div, mass) with return_mass.  `coalitions` is info["coalitions"] of any exact *_shapley call, word m at
+        column m, 1 <= P <= 16.  div[b, S] = sum over T <= S of (-1)^(|S| - |T|) v(T): what the players of S contribute TOGETHER beyond
+        every smaller group of them; the dividends of all subsets of S add back up to v(S).  The fp32 result is the in-place
+        butterfly (for k < P, for S with bit k: a[S] -= a[S ^ 1 << k]), bit for bit; the dividends of a set that holds a null player
+        are exactly 0.  mass[b, S] = sum over T <= S of |v(T)| scales the rounding error (attribution.dividend_bound): a high-order
+        dividend smaller than its bound is noise.  No forward runs and a pending backward() is left alone."""
+        rows, B, P = self._table_check("shapley_dividends", "coalitions", coalitions)
+        div = torch.empty_like(rows)      # (written in full by the library)
+        mass = torch.empty_like(rows) if return_mass else None
+        st = torch.cuda.current_stream(self._device).cuda_stream
+        _lib.check(_lib.lib().cf_dividends_from_rows(self._handle, rows.data_ptr(), B, P, div.data_ptr(), mass.data_ptr() if return_mass else None, st),
+                   "cf_dividends_from_rows")
+        return (div, mass) if return_mass else div
+
+    @torch.no_grad()
+    def set_interactions(self, dividends, order=2, index="sii", sets=None):
+        """An interaction index of sets of up to `order` players from the dividends (cf_set_interactions_from_dividends) -> (inter
+        [B, n_sets, n_out] on the model's device, sets uint32 [n_sets]).  dividends: shapley_dividends' result; sets: words (bit p =
+        player p), each with 1..order players; default attribution.interaction_sets(P, order), every such set by size and word.
+        index "sii": the Shapley interaction index of any order (order 1 the Shapley values, order 2 the pairwise sii of
+        shapley_interactions, within rounding); "sti": Shapley-Taylor of top order `order` -- sets below it carry their dividend's
+        bits, and all sets together sum to logits - absent.  Weights: attribution.set_interaction_weights.  No forward runs."""
+        from .attribution import interaction_index, interaction_sets
+        who = "set_interactions"
+        code = interaction_index(index, who)
+        div, B, P = self._table_check(who, "dividends", dividends)
+        order = int(order)
+        if not 1 <= order <= P:
+            raise ValueError("%s: order = %d outside 1..P = %d" % (who, order, P))
+        if sets is None:
+            words = interaction_sets(P, order)
+        else:
+            raw = np.asarray(sets.cpu() if hasattr(sets, "cpu") else sets)
+            if raw.ndim != 1 or raw.size < 1 or raw.dtype.kind not in "iu" or raw.min() < 0 or raw.max() >= 1 << P:
+                raise ValueError("%s: sets must be a non-empty 1-D integer array of words below 2^P = %d" % (who, 1 << P))
+            words = np.ascontiguousarray(raw.astype(np.uint32))
+        inter = torch.empty(B, len(words), self.n_out, device=self._device)      # (written in full by the library)
+        st = torch.cuda.current_stream(self._device).cuda_stream
+        _lib.check(_lib.lib().cf_set_interactions_from_dividends(self._handle, div.data_ptr(), B, P, words.ctypes.data, len(words), code, order,
+                                                                 inter.data_ptr(), st), "cf_set_interactions_from_dividends")
+        return inter, words
+
+    def _dividends_info(self, phi, info, names):
+        """(div, info) of a *_dividends call from its sibling's (phi, info with the coalitions)."""
+        from .attribution import set_names
+        div, mass = self.shapley_dividends(info["coalitions"], return_mass=True)
+        info = dict(info, phi=phi, mass=mass, names=list(names))
+        info["sets"] = set_names(np.arange(div.shape[1], dtype=np.uint32), names)
+        return div, info
+
+    @torch.no_grad()
+    def pcre_dividends(self, *args, **kwargs):
+        """pcre_shapley(..., return_coalitions=True) with the same arguments, then shapley_dividends on its table -> (div, info): div
+        [B, 2^i_max, n_out], word m at column m; info is pcre_shapley's (logits, promoter_only, delta, coalitions) plus phi (its
+        Shapley values, bit for bit), mass (shapley_dividends), names ("pcre0", ...) and sets (the 2^P set names by word, "" for the
+        empty set).  A dummy slot is a null player: every set that holds it has dividend exactly 0."""
+        phi, info = self.pcre_shapley(*args, **dict(kwargs, return_coalitions=True))
+        return self._dividends_info(phi, info, ["pcre%d" % j for j in range(self.i_max)])
+
+    @torch.no_grad()
+    def mark_dividends(self, *args, **kwargs):
+        """mark_shapley(..., return_coalitions=True) with the same arguments, then shapley_dividends -> (div, info) as pcre_dividends;
+        info is mark_shapley's (logits, erased, players, delta, coalitions) plus phi, mass, names and sets."""
+        phi, info = self.mark_shapley(*args, **dict(kwargs, return_coalitions=True))
+        return self._dividends_info(phi, info, info["players"])
+
+    @torch.no_grad()
+    def mark_donor_dividends(self, *args, **kwargs):
+        """mark_donor_shapley(..., return_coalitions=True) with the same arguments, then shapley_dividends -> (div, info) as
+        mark_dividends; the absent key is "donor"."""
+        phi, info = self.mark_donor_shapley(*args, **dict(kwargs, return_coalitions=True))
+        return self._dividends_info(phi, info, info["players"])
+
+    @torch.no_grad()
+    def mark_window_dividends(self, *args, **kwargs):
+        """mark_window_shapley(..., return_coalitions=True) with the same arguments (at most 16 window players), then
+        shapley_dividends -> (div, info) as mark_dividends."""
+        phi, info = self.mark_window_shapley(*args, **dict(kwargs, return_coalitions=True))
+        return self._dividends_info(phi, info, info["players"])
+
+    @torch.no_grad()
+    def mark_fine_window_dividends(self, *args, **kwargs):
+        """mark_fine_window_shapley(..., return_coalitions=True) with the same arguments (at most 16 fine window players), then
+        shapley_dividends -> (div, info) as mark_dividends."""
+        phi, info = self.mark_fine_window_shapley(*args, **dict(kwargs, return_coalitions=True))
+        return self._dividends_info(phi, info, info["players"])
+
     @torch.no_grad()
     def pcre_epistasis(self, promoter_feats, promoter_pad_masks=None, pcre_feats=None, pcre_pad_masks=None, interaction_masks=None,
                        interaction_freq=None):
@@ -1174,12 +1276,14 @@ class ChromoformerBase(nn.Module):
         bs, _keep, book = self._attrib_call("mark_shapley_interactions", (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq))
         return self._mark_run_interactions("cf_mark_shapley_interactions", bs, opts, names, "erased", book, index, return_coalitions)
 
-    def mark_shapley_dataset(self, dataset, genes=None, players="marks", scale=0.0, epistasis=False, bsz=None, store=None, interactions=None):
-        """mark_shapley (and optionally mark_epistasis, or mark_shapley_interactions in its place) over the genes of a ChromoformerDataset
-        (chromoformer_amd.attribution.mark_shapley, a generator of per-gene dicts)."""
+    def mark_shapley_dataset(self, dataset, genes=None, players="marks", scale=0.0, epistasis=False, bsz=None, store=None, interactions=None,
+                             dividends=False):
+        """mark_shapley (and optionally mark_epistasis, or mark_shapley_interactions in its place; with dividends=True the Harsanyi
+        dividends of the same table too) over the genes of a ChromoformerDataset (chromoformer_amd.attribution.mark_shapley, a generator
+        of per-gene dicts)."""
         from .attribution import mark_shapley
         return mark_shapley(self, dataset, genes=genes, players=players, scale=scale, epistasis=epistasis, bsz=bsz, store=store,
-                            interactions=interactions)
+                            interactions=interactions, dividends=dividends)
 
     def _mark_donor_opts(self, who, donor, players, B):
         """players (a mark_players spec) and the donor of a batch of B genes -> (cf_mark_donor_opts, what it points to, names).  donor:
@@ -1316,12 +1420,13 @@ class ChromoformerBase(nn.Module):
         return self._mark_run_interactions("cf_mark_donor_shapley_interactions", bs, opts, names, "donor", book, index, return_coalitions)
 
     def mark_donor_shapley_dataset(self, dataset, donor_dataset, genes=None, players="marks", epistasis=False, bsz=None, store=None, donor_store=None,
-                                   interactions=None):
-        """mark_donor_shapley (and optionally mark_donor_epistasis) over the genes of two ChromoformerDatasets, the gene's cell type
-        and the donor's (chromoformer_amd.attribution.mark_donor_shapley, a generator of per-gene dicts)."""
+                                   interactions=None, dividends=False):
+        """mark_donor_shapley (and optionally mark_donor_epistasis, the interaction index, the dividends) over the genes of two
+        ChromoformerDatasets, the gene's cell type and the donor's (chromoformer_amd.attribution.mark_donor_shapley, a generator of
+        per-gene dicts)."""
         from .attribution import mark_donor_shapley
         return mark_donor_shapley(self, dataset, donor_dataset, genes=genes, players=players, epistasis=epistasis, bsz=bsz, store=store,
-                                  donor_store=donor_store, interactions=interactions)
+                                  donor_store=donor_store, interactions=interactions, dividends=dividends)
 
     def _mark_wide_opts(self, who, players, scale, donor, B):
         """players (a mark_players_wide spec), scale and donor (None: the scale rule; else the forms of _mark_donor_opts) for a batch of
@@ -1561,12 +1666,12 @@ class ChromoformerBase(nn.Module):
         return self._mark_run_pairs_sampled("cf_mark_window_shapley_interactions_sampled", bs, opts, names, perms, focal, index, book, return_rows)
 
     def mark_window_shapley_dataset(self, dataset, donor_dataset=None, genes=None, players="promoter", width=1, n_perm=64, seed=0, scale=0.0,
-                                    bsz=None, store=None, donor_store=None, interactions=None):
+                                    bsz=None, store=None, donor_store=None, interactions=None, dividends=False):
         """Shapley values of window players over the genes of a ChromoformerDataset, against a donor cell type's dataset if one is
         given, windows in genomic coordinates (chromoformer_amd.attribution.mark_window_shapley, a generator of per-gene dicts)."""
         from .attribution import mark_window_shapley
         return mark_window_shapley(self, dataset, donor_dataset, genes=genes, players=players, width=width, n_perm=n_perm, seed=seed,
-                                   scale=scale, bsz=bsz, store=store, donor_store=donor_store, interactions=interactions)
+                                   scale=scale, bsz=bsz, store=store, donor_store=donor_store, interactions=interactions, dividends=dividends)
 
     def _mark_fine_opts(self, who, B, region, players, width, n_windows, start, lengths, scale, donor, flip):
         """The options of the fine window game for a batch of B genes -> (P, cf_mark_fine_opts, what it points to, names)."""
@@ -1733,14 +1838,14 @@ class ChromoformerBase(nn.Module):
 
     def mark_fine_window_shapley_dataset(self, dataset, donor_dataset=None, genes=None, region="promoter", zoom=1, coarse_width=1, width=2,
                                          players="windows", n_perm=64, seed=0, scale=0.0, target=None, bsz=None, store=None, donor_store=None,
-                                         interactions=None):
+                                         interactions=None, dividends=False):
         """Shapley values of fine window players over the genes of a ChromoformerDataset, zooming from the coarse window game, against a
         donor cell type's dataset if one is given, windows in genomic coordinates (chromoformer_amd.attribution.mark_fine_window_shapley,
         a generator of per-gene dicts)."""
         from .attribution import mark_fine_window_shapley
         return mark_fine_window_shapley(self, dataset, donor_dataset, genes=genes, region=region, zoom=zoom, coarse_width=coarse_width, width=width,
                                         players=players, n_perm=n_perm, seed=seed, scale=scale, target=target, bsz=bsz, store=store,
-                                        donor_store=donor_store, interactions=interactions)
+                                        donor_store=donor_store, interactions=interactions, dividends=dividends)
 
     def raw_signal_gradients(self, dataset, genes=None, target=None, times_input=False, bsz=None):
         """Raw-signal saliency of the genes of a ChromoformerDataset: the gradient (or gradient x input) of logit column `target` with

@@ -275,6 +275,41 @@ def write_mark_donor_values(model, store, donor_store, bsz, gene_ids, shapley_ou
         inter.flush()
 
 
+def write_dividends(model, store, donor_store, bsz, gene_ids, path, game="mark", regression=False, players="marks", scale=0.0):
+    """Harsanyi dividends of an exact game of every gene of a device-resident store, in store order, in LOGIT space of the
+    prediction's column, into `path`, an .npz with gene_ids [n], players [P] (names), sets [2^P] (the set names by word, "" for the empty
+    set), dividends [n, 2^P] float32 (word m at column m; they add up to the logit of every coalition) and mass [n, 2^P] (the scale of
+    a dividend's rounding error, attribution.dividend_bound).  game: "pcre" (model.pcre_dividends), "mark" (model.mark_dividends; players
+    and scale apply) or "mark_donor" (model.mark_donor_dividends against donor_store, the same genes in the same order; players
+    applies).  Per batch: one gather per store and one such call (its own 2^P forwards)."""
+    from .attribution import _BATCH_KEYS, _donor_pair
+    n = len(store)
+    if game not in ("pcre", "mark", "mark_donor"):
+        raise ValueError("write_dividends: unknown game %r; choose from ['pcre', 'mark', 'mark_donor']" % (game,))
+    if game == "mark_donor" and (donor_store is None or len(donor_store) != n):
+        raise ValueError("write_dividends: the donor store must hold the store's %d genes" % n)
+    t = 0 if regression else 1
+    div, mass, names, sets = None, None, None, None
+    for lo in range(0, n, bsz):
+        B = min(bsz, n - lo)
+        idx = list(range(lo, lo + B))
+        d = store.batch(idx)
+        args = tuple(d[k] for k in _BATCH_KEYS)
+        if game == "pcre":
+            x, info = model.pcre_dividends(*args)
+        elif game == "mark":
+            x, info = model.mark_dividends(*args, players=players, scale=scale)
+        else:
+            x, info = model.mark_donor_dividends(*args, donor=_donor_pair(donor_store.batch(idx)), players=players)
+        if div is None:
+            div, mass = np.empty((n, x.shape[1]), np.float32), np.empty((n, x.shape[1]), np.float32)
+            names, sets = info["names"], info["sets"]
+        div[lo:lo + B] = x[..., t].cpu().numpy()
+        mass[lo:lo + B] = info["mass"][..., t].cpu().numpy()
+    with open(path, "wb") as f:      # (a file object: np.savez would append .npz to a name without it)
+        np.savez(f, gene_ids=np.array(list(gene_ids)), players=np.array(names), sets=np.array(sets), dividends=div, mass=mass)
+
+
 def write_mark_sampled_values(model, store, donor_store, bsz, gene_ids, path, regression=False, players="cells", n_perm=64, seed=0, scale=0.0):
     """Permutation-sampled Shapley values of up to 128 histone-mark players (model.mark_shapley_sampled) of every gene of a
     device-resident store, in store order, in LOGIT space of the prediction's column, into `path`, an .npz with gene_ids [n], players
@@ -616,7 +651,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
             fine_window_donor_shapley_out=None, fine_window_region="promoter", fine_window_width=2, fine_window_players="windows",
             fine_window_zoom=1, fine_window_perms=64, fine_window_seed=0, fine_window_scale=0.0, pcre_interactions_out=None,
             mark_interactions_out=None, mark_donor_interactions_out=None, interaction_index="sii", mark_sampled_interactions_out=None,
-            mark_donor_sampled_interactions_out=None, mark_focal=4):
+            mark_donor_sampled_interactions_out=None, mark_focal=4, pcre_dividends_out=None, mark_dividends_out=None,
+            mark_donor_dividends_out=None):
     """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file.  attention_dir / embeddings_out: also
     write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps); pcre_ablation_out:
     the predictions with each pCRE deleted (write_pcre_ablation); ig_dir: integrated gradients of every gene
@@ -649,7 +685,9 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     mark_sampled_interactions_out / mark_donor_sampled_interactions_out: the SAMPLED interaction index of each gene's focal players
     among up to 128 mark players, one .npz, under the scale rule (mark_scale applies) / against the donor
     (write_mark_sampled_interactions; mark_focal -- an int: each gene's strongest players by |phi|; a list of names or indices: those
-    for every gene --, mark_sampled_players, mark_perms, mark_seed and interaction_index apply)."""
+    for every gene --, mark_sampled_players, mark_perms, mark_seed and interaction_index apply); pcre_dividends_out /
+    mark_dividends_out / mark_donor_dividends_out: the Harsanyi dividends of every set of pCREs / histone marks / marks against the
+    donor, one .npz in logit space (write_dividends; mark_players applies to the mark games, mark_scale to mark_dividends_out)."""
     from .attribution import interaction_index as _index_check
     _index_check(interaction_index, "predict")      # (before anything is computed)
     pairs_ds, pairs_kw = None, {}
@@ -672,7 +710,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         require_raw_signals(raw_ds)      # (before anything is computed)
     from . import pack
     donor_out = (mark_donor_shapley_out or mark_donor_epistasis_out or mark_donor_sampled_shapley_out or window_donor_shapley_out
-                 or fine_window_donor_shapley_out or mark_donor_interactions_out or mark_donor_sampled_interactions_out)
+                 or fine_window_donor_shapley_out or mark_donor_interactions_out or mark_donor_sampled_interactions_out
+                 or mark_donor_dividends_out)
     if pairs_kw:      # (the geometry the generator checks the model against)
         pairs_ds = ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False)
     raw_donor_ds = None
@@ -698,7 +737,7 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         if not donor_npy_dir:
             raise ValueError("predict: mark_donor_shapley_out / mark_donor_epistasis_out / mark_donor_sampled_shapley_out / "
                              "window_donor_shapley_out / fine_window_donor_shapley_out / mark_donor_interactions_out / "
-                             "mark_donor_sampled_interactions_out need donor_npy_dir")
+                             "mark_donor_sampled_interactions_out / mark_donor_dividends_out need donor_npy_dir")
         donor_ds = ChromoformerDataset(donor_meta or meta_path, donor_npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False)
         same_regions(ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False), donor_ds)
     packed = pack.find(npy_dir, store_path, list(binsizes), i_max, w_prom, w_max, 7, genes, meta=meta)
@@ -727,6 +766,10 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     if mark_shapley_out or mark_epistasis_out or mark_interactions_out:
         write_mark_values(model, store, bsz, genes, mark_shapley_out, mark_epistasis_out, regression, mark_players, mark_scale,
                           mark_interactions_out, interaction_index)
+    if pcre_dividends_out:
+        write_dividends(model, store, None, bsz, genes, pcre_dividends_out, "pcre", regression)
+    if mark_dividends_out:
+        write_dividends(model, store, None, bsz, genes, mark_dividends_out, "mark", regression, mark_players, mark_scale)
     if donor_out:
         donor_packed = pack.find(donor_npy_dir, donor_store_path, list(binsizes), i_max, w_prom, w_max, 7, genes, meta=donor_ds.meta)
         donor_store = (donor_packed.store(genes, device=dev, regression=False) if donor_packed is not None
@@ -734,6 +777,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         if mark_donor_shapley_out or mark_donor_epistasis_out or mark_donor_interactions_out:
             write_mark_donor_values(model, store, donor_store, bsz, genes, mark_donor_shapley_out, mark_donor_epistasis_out, regression, mark_players,
                                     mark_donor_interactions_out, interaction_index)
+        if mark_donor_dividends_out:
+            write_dividends(model, store, donor_store, bsz, genes, mark_donor_dividends_out, "mark_donor", regression, mark_players)
         if mark_donor_sampled_shapley_out:
             write_mark_sampled_values(model, store, donor_store, bsz, genes, mark_donor_sampled_shapley_out, regression, mark_sampled_players,
                                       mark_perms, mark_seed)
@@ -899,6 +944,15 @@ def build_parser():
     ap.add_argument("--mark-focal", default=None, help="the focal players of --mark-sampled-interactions-out / "
                     "--mark-donor-sampled-interactions-out: a number K (default 4): each gene's K strongest players by |phi| of a sampled Shapley "
                     "estimate on the same orders; or player names separated by commas (mark3@pcre0,mark0@promoter): those for every gene")
+    ap.add_argument("--pcre-dividends-out", default=None, help="also write the Harsanyi dividends (the Moebius transform of the coalition "
+                    "table) of every set of pCRE slots to this .npz file, in metadata order and in LOGIT space of the prediction's column: "
+                    "gene_ids, players (names), sets [2^P] (set names by word), dividends [n_genes, 2^P] (they add up to the logit of every "
+                    "coalition: which pCREs act alone, which together, in which combinations) and mass (the scale of a dividend's rounding "
+                    "error) (model.pcre_dividends)")
+    ap.add_argument("--mark-dividends-out", default=None, help="the same for the histone marks (model.mark_dividends).  --mark-players and "
+                    "--mark-scale apply")
+    ap.add_argument("--mark-donor-dividends-out", default=None, help="the same against the donor cell type of --donor-npy-dir: an absent mark "
+                    "takes the donor's signal (model.mark_donor_dividends).  --mark-players applies")
     from .attribution import WINDOW_PLAYER_SPECS
     ap.add_argument("--window-shapley-out", default=None, help="also write the Shapley values of WINDOW players -- stretches of a region, in "
                     "coarsest bins -- to this .npz file, in metadata order and in LOGIT space of the prediction's column: gene_ids, players "
@@ -968,7 +1022,7 @@ def main(argv=None):
     for name, v in (("width", args.fine_scan_width), ("stride", args.fine_scan_stride), ("zoom", args.fine_scan_zoom)):
         if v is not None and v < 1:
             ap.error("--fine-scan-%s must be at least 1" % name)
-    donor_exact = args.mark_donor_shapley_out or args.mark_donor_epistasis_out or args.mark_donor_interactions_out
+    donor_exact = args.mark_donor_shapley_out or args.mark_donor_epistasis_out or args.mark_donor_interactions_out or args.mark_donor_dividends_out
     pairs_out = args.mark_sampled_interactions_out or args.mark_donor_sampled_interactions_out
     if args.interaction_index is not None and not (args.pcre_interactions_out or args.mark_interactions_out or args.mark_donor_interactions_out
                                                    or pairs_out):
@@ -1004,20 +1058,21 @@ def main(argv=None):
     sampled_out = args.mark_sampled_shapley_out or args.mark_donor_sampled_shapley_out
     if donor_out and not args.donor_npy_dir:
         ap.error("--mark-donor-shapley-out / --mark-donor-epistasis-out / --mark-donor-sampled-shapley-out / --window-donor-shapley-out / "
-                 "--fine-window-donor-shapley-out / --mark-donor-interactions-out / --mark-donor-sampled-interactions-out need --donor-npy-dir")
+                 "--fine-window-donor-shapley-out / --mark-donor-interactions-out / --mark-donor-sampled-interactions-out / "
+                 "--mark-donor-dividends-out need --donor-npy-dir")
     if not donor_out and not args.raw_donor_ig_dir and (args.donor_npy_dir or args.donor_meta or args.donor_store):
         ap.error("--donor-npy-dir / --donor-meta / --donor-store need --mark-donor-shapley-out, --mark-donor-epistasis-out or "
                  "--mark-donor-sampled-shapley-out (or --window-donor-shapley-out, --fine-window-donor-shapley-out, "
-                 "--mark-donor-interactions-out, --mark-donor-sampled-interactions-out)")
+                 "--mark-donor-interactions-out, --mark-donor-sampled-interactions-out, --mark-donor-dividends-out)")
     if not sampled_out and not pairs_out and (args.mark_sampled_players is not None or args.mark_perms is not None or args.mark_seed is not None):
         ap.error("--mark-sampled-players / --mark-perms / --mark-seed need --mark-sampled-shapley-out or --mark-donor-sampled-shapley-out"
                  " (or --mark-sampled-interactions-out, --mark-donor-sampled-interactions-out)")
     if args.mark_perms is not None and args.mark_perms < 1:
         ap.error("--mark-perms must be at least 1")
-    if not args.mark_shapley_out and not args.mark_epistasis_out and not args.mark_interactions_out and ((args.mark_scale is not None and not args.mark_sampled_shapley_out
+    if not args.mark_shapley_out and not args.mark_epistasis_out and not args.mark_interactions_out and not args.mark_dividends_out and ((args.mark_scale is not None and not args.mark_sampled_shapley_out
                                                                                                           and not args.mark_sampled_interactions_out)
                                                                                                          or (args.mark_players is not None and not donor_exact)):
-        ap.error("--mark-players / --mark-scale need --mark-shapley-out, --mark-epistasis-out or --mark-interactions-out"
+        ap.error("--mark-players / --mark-scale need --mark-shapley-out, --mark-epistasis-out, --mark-interactions-out or --mark-dividends-out"
                  " (--mark-players also applies to --mark-donor-shapley-out / --mark-donor-epistasis-out, --mark-scale to"
                  " --mark-sampled-shapley-out)")
     if args.mark_scale is not None and not (args.mark_scale >= 0 and np.isfinite(args.mark_scale)):
@@ -1097,7 +1152,9 @@ def main(argv=None):
                          pcre_interactions_out=args.pcre_interactions_out, mark_interactions_out=args.mark_interactions_out,
                          mark_donor_interactions_out=args.mark_donor_interactions_out, interaction_index=args.interaction_index or "sii",
                          mark_sampled_interactions_out=args.mark_sampled_interactions_out,
-                         mark_donor_sampled_interactions_out=args.mark_donor_sampled_interactions_out, mark_focal=mark_focal)
+                         mark_donor_sampled_interactions_out=args.mark_donor_sampled_interactions_out, mark_focal=mark_focal,
+                         pcre_dividends_out=args.pcre_dividends_out, mark_dividends_out=args.mark_dividends_out,
+                         mark_donor_dividends_out=args.mark_donor_dividends_out)
     print("Predicting expressions for %d genes." % len(meta))
     meta["prediction"] = pred
     meta.to_csv(args.output, index=False)

@@ -264,6 +264,33 @@ int cf_pcre_epistasis(cf_handle* h, const cf_batch* batch, float* eps, float* lo
 #define CF_INTERACTION_SII 0
 #define CF_INTERACTION_STI 1
 int cf_shapley_interactions_from_rows(cf_handle* h, const float* rows, int B, int P, int index, float* inter, void* stream);
+/* Harsanyi dividends (the Moebius transform) of the same table, and interaction indices of any order from them (interpretation).
+ *   m(S) = sum over T <= S of (-1)^(|S| - |T|) v(T),      v(S) = sum over T <= S of m(T):      one number per set of players.
+ * cf_dividends_from_rows: rows, div and the optional mass [B, 2^P, n_out] (device; word m at column m; n_out is the handle's),
+ * 1 <= P <= 16.  The fp32 result is DEFINED by the in-place recurrence
+ *   for k = 0 .. P - 1, for every word S with bit k set:  a[S] = a[S] - a[S ^ (1 << k)]       one fp32 subtraction each
+ * so it equals a float32 restatement bit for bit: div[0] = v(0), div[{i}] = v({i}) - v(0) (the sti diagonal of k_shapley_pairs),
+ * div[{i, j}] = (v(ij) - v(j)) - (v(i) - v(0)) for i < j (its delta_ij(0)), and every dividend of a set that holds a null player (rows
+ * bit-equal with and without it, finite) is exactly +0.  mass(S) = sum over T <= S of |v(T)| is the same butterfly with + on |v|: the
+ * scale of the rounding error, |div(S) - exact| <= ((1 + 2^-24)^|S| - 1) mass(S).  k_moebius (tiles of 4,096 words in LDS, stages
+ * 0..11) and, for P > 12, k_moebius_high (the remaining stages in registers, in place): cf_launch_counts fwd = 1 for P <= 12, 2 above,
+ * with or without mass.  rows may not alias div or mass.  Refused by name, before anything is launched: a null handle / rows / div,
+ * B < 1, P outside 1..16.
+ * cf_set_interactions_from_dividends: sets is a HOST array of n_sets words (read before the call returns; they travel in the
+ * handle's word table), each with 1 <= |S| <= order;  out[b, s, o] = sum over U >= S_s of wt[|S_s|][|U|] div[b, U, o], the weights
+ * computed in double, rounded to fp32 and passed by value:
+ *   CF_INTERACTION_SII  wt = 1 / (|U| - |S| + 1)        order 1: the Shapley value; order 2: the pairwise sii
+ *   CF_INTERACTION_STI  |S| < order: the dividend itself (its bits, no arithmetic); |S| = order: wt = 1 / C(|U|, order); the sum over
+ *                       all non-empty sets of size <= order is v(N) - v(0) up to rounding
+ * One k_set_index, a workgroup per (gene, set): a thread sums its supersets in ascending stride, one rounded product and one rounded
+ * add per term (no contraction), then k_shapley's tree: deterministic; a set that holds a null player is exactly 0.  out
+ * [B, n_sets, n_out].  fwd = 1.  Both are operators as cf_shapley_interactions_from_rows: no batch, no activation is touched, a
+ * pending backward is left alone.  Refused by name, before anything is launched: a null handle / div / sets / out, B < 1, P outside
+ * 1..16, n_sets outside 1..65535, order outside 1..P, an index other than the two constants, the empty set, a set word with a bit
+ * >= P or more than `order` bits (the error names the set's position). */
+int cf_dividends_from_rows(cf_handle* h, const float* rows, int B, int P, float* div, float* mass /* or NULL */, void* stream);
+int cf_set_interactions_from_dividends(cf_handle* h, const float* div, int B, int P, const uint32_t* sets /* host */, int n_sets, int index,
+                                       int order, float* out /* [B, n_sets, n_out] */, void* stream);
 /* cf_pcre_shapley's rows (S = i_max players, all 2^S coalitions through the same routine, logits_all as there), then k_shapley_pairs;
  * phi [B, S, n_out] is optional: if given, k_shapley runs on the same rows too.  fwd = that of cf_pcre_coalitions with n_coal = 2^S, plus
  * 1 per reducer launched (1, or 2 with phi).  Refused by name, before anything is launched: what cf_pcre_shapley refuses (phi may be
