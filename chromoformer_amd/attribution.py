@@ -938,6 +938,56 @@ def _resident_store(who, ds, genes, binsizes, dev, store=None):
     return store
 
 
+def _open(who, model, dataset, genes, bsz, donor_dataset=None):
+    """The opening of the dataset generators -> (binsizes, n_bins, genes, chunk size): the model is on the device and the dataset has
+    its geometry, the genes are in its metadata and, with a donor dataset, both hold them over the same regions.  Host checks only."""
+    binsizes = [int(b) for b in dataset.binsizes]
+    n_bins = _geometry_check(who, model, dataset, binsizes)
+    genes, chunk = _genes_check(who, model, dataset, genes, bsz)
+    if donor_dataset is not None:
+        same_regions(dataset, donor_dataset, genes)
+    return binsizes, n_bins, genes, chunk
+
+
+def _batches(who, model, dataset, genes, chunk, binsizes, store=None, donor_dataset=None, donor_store=None):
+    """The resident stores of the dataset and, if given, of the donor (_resident_store), then per chunk of `genes` -> (the gene ids,
+    their store indices, the batch dict, forward()'s six arguments, the donor pair or None, the donor's batch dict or None).  A
+    generator: nothing is loaded before the first next(), so a caller's refusals come first."""
+    store = _resident_store(who, dataset, genes, binsizes, model._device, store)
+    if donor_dataset is not None:
+        donor_store = _resident_store(who, donor_dataset, genes, binsizes, model._device, donor_store)
+    for lo in range(0, len(genes), chunk):
+        ids = genes[lo:lo + chunk]
+        idx = list(range(lo, lo + len(ids)))
+        d = store.batch(idx)
+        dd = donor_store.batch(idx) if donor_dataset is not None else None
+        yield ids, idx, d, tuple(d[k] for k in _BATCH_KEYS), None if dd is None else _donor_pair(dd), dd
+
+
+def _exact_game(model, prefix, args, kw, interactions, dividends):
+    """One exact game of a batch (prefix "mark", "mark_donor", "mark_window" or "mark_fine_window") -> (phi, interactions or None, info,
+    dividends, mass): one model.<prefix>_shapley(*args, **kw), or with `interactions` (an index name) one
+    model.<prefix>_shapley_interactions in its place, phi from info["phi"]; with `dividends` the call keeps its coalition table and
+    model.shapley_dividends turns it into (dividends, mass) [B, 2^P, n_out], else (None, None).  Host arrays but for info, the call's."""
+    if interactions is None:
+        inter, (phi, info) = None, getattr(model, prefix + "_shapley")(*args, return_coalitions=bool(dividends), **kw)
+    else:
+        inter, info = getattr(model, prefix + "_shapley_interactions")(*args, index=interactions, return_coalitions=bool(dividends), **kw)
+        phi, inter = info["phi"], inter.cpu().numpy()
+    div, mass = None, None
+    if dividends:
+        div, mass = (t.cpu().numpy() for t in model.shapley_dividends(info["coalitions"], return_mass=True))
+    return phi.cpu().numpy(), inter, info, div, mass
+
+
+def _optional_keys(out, i, eps=None, interactions=None, dividends=None, mass=None):
+    """Gene i's rows of a batch's optional arrays into its dict `out`, each under its argument's name where it is given -> out."""
+    for key, a in (("eps", eps), ("interactions", interactions), ("dividends", dividends), ("mass", mass)):
+        if a is not None:
+            out[key] = a[i].copy()
+    return out
+
+
 def perturbation_scan(model, dataset, genes=None, regions="promoter", scale=0.0, width=1, mark_sets=None, bsz=None, store=None):
     """In-silico perturbation scan of the genes of a ChromoformerDataset (one model.perturbation_scan_regions per batch, windows in
     genomic coordinates): what the prediction becomes with the marks of a mark set scaled by `scale` in raw-signal space -- 0 erases, 2
@@ -963,22 +1013,16 @@ def perturbation_scan(model, dataset, genes=None, regions="promoter", scale=0.0,
 
     from .data import promoter_col0
     ds = dataset
-    binsizes = [int(b) for b in ds.binsizes]
-    n_bins = _geometry_check("perturbation_scan", model, ds, binsizes)
-    genes, chunk = _genes_check("perturbation_scan", model, ds, genes, bsz)
-    S, F, dev = ds.i_max, ds.n_feats, model._device
+    binsizes, n_bins, genes, chunk = _open("perturbation_scan", model, ds, genes, bsz)
+    S, F = ds.i_max, ds.n_feats
     order = scan_regions_expand(regions, S) if isinstance(regions, str) else [int(r) for r in regions]      # (the caller's order is kept)
     regions = scan_regions_expand(order, S)
     mark_sets = scan_mark_sets(mark_sets, F)
     rc = int(np.argmin(n_bins))
     W, bc = n_bins[rc], binsizes[rc]
     col0 = promoter_col0(ds)
-    store = _resident_store("perturbation_scan", ds, genes, binsizes, dev, store)
-    for lo in range(0, len(genes), chunk):
-        ids = genes[lo:lo + chunk]
+    for ids, _, d, args, _, _ in _batches("perturbation_scan", model, ds, genes, chunk, binsizes, store):
         B = len(ids)
-        d = store.batch(list(range(lo, lo + B)))
-        args = tuple(d[k] for k in _BATCH_KEYS)
         flip = [ds.genes[g]["tss"][2] != "+" for g in ids]
         per = [dict(gene_id=g, logits=None, mark_sets=list(mark_sets), regions=[], windows=[], scan=[]) for g in ids]
         has_of = {region: [region == 0 or region - 1 < len(ds.genes[g]["pcres"]) for g in ids] for region in regions}
@@ -1050,10 +1094,8 @@ def perturbation_scan_fine(model, dataset, genes=None, region="promoter", zoom=N
     from .data import promoter_col0
     who = "perturbation_scan_fine"
     ds = dataset
-    binsizes = [int(b) for b in ds.binsizes]
-    n_bins = _geometry_check(who, model, ds, binsizes)
-    genes, chunk = _genes_check(who, model, ds, genes, bsz)
-    S, F, dev = ds.i_max, ds.n_feats, model._device
+    binsizes, n_bins, genes, chunk = _open(who, model, ds, genes, bsz)
+    S, F = ds.i_max, ds.n_feats
     region = _region_index(who, region, S)
     mark_sets = scan_mark_sets(mark_sets, F)
     K = len(mark_sets)
@@ -1068,12 +1110,7 @@ def perturbation_scan_fine(model, dataset, genes=None, region="promoter", zoom=N
     Rc = Lf // W
     target = model.n_out - 1 if target is None else int(target)
     col0 = promoter_col0(ds)
-    store = _resident_store(who, ds, genes, binsizes, dev, store)
-    for lo in range(0, len(genes), chunk):
-        ids = genes[lo:lo + chunk]
-        B = len(ids)
-        d = store.batch(list(range(lo, lo + B)))
-        args = tuple(d[k] for k in _BATCH_KEYS)
+    for ids, _, _, args, _, _ in _batches(who, model, ds, genes, chunk, binsizes, store):
         flip = [region == 0 and ds.genes[g]["tss"][2] != "+" for g in ids]
         regs = [_gene_region(ds, g, region, col0) for g in ids]
         lengths = [r[2] - r[1] if r else 0 for r in regs]
@@ -1138,44 +1175,18 @@ def mark_shapley(model, dataset, genes=None, players="marks", scale=0.0, epistas
     matches, else from the raw .npy files binned on the device.  Parameters, gradients and optimiser state are left as they are; the
     pass overwrites the activations a grad-enabled model(...) keeps for its backward."""
     ds = dataset
-    binsizes = [int(b) for b in ds.binsizes]
-    _geometry_check("mark_shapley", model, ds, binsizes)
-    genes, chunk = _genes_check("mark_shapley", model, ds, genes, bsz)
+    binsizes, _, genes, chunk = _open("mark_shapley", model, ds, genes, bsz)
     spec = players if isinstance(players, str) else list(players)
     names = mark_players(spec, ds.n_feats, ds.i_max)[2]      # (refusals before anything is loaded)
     if interactions is not None:
         interaction_index(interactions, "mark_shapley")
-    store = _resident_store("mark_shapley", ds, genes, binsizes, model._device, store)
-    for lo in range(0, len(genes), chunk):
-        ids = genes[lo:lo + chunk]
-        d = store.batch(list(range(lo, lo + len(ids))))
-        args = tuple(d[k] for k in _BATCH_KEYS)
-        inter = None
-        if interactions is None:
-            phi, info = model.mark_shapley(*args, players=spec, scale=scale, return_coalitions=bool(dividends))
-        else:
-            inter, info = model.mark_shapley_interactions(*args, players=spec, scale=scale, index=interactions, return_coalitions=bool(dividends))
-            phi, inter = info["phi"], inter.cpu().numpy()
-        div, mass = _batch_dividends(model, info, dividends)
-        phi, logits, erased = phi.cpu().numpy(), info["logits"].cpu().numpy(), info["erased"].cpu().numpy()
+    for ids, _, _, args, _, _ in _batches("mark_shapley", model, ds, genes, chunk, binsizes, store):
+        phi, inter, info, div, mass = _exact_game(model, "mark", args, dict(players=spec, scale=scale), interactions, dividends)
+        logits, erased = info["logits"].cpu().numpy(), info["erased"].cpu().numpy()
         eps = model.mark_epistasis(*args, players=spec, scale=scale)[0].cpu().numpy() if epistasis else None
         for i, g in enumerate(ids):
             out = dict(gene_id=g, phi=phi[i].copy(), logits=logits[i].copy(), erased=erased[i].copy(), players=list(names))
-            if epistasis:
-                out["eps"] = eps[i].copy()
-            if inter is not None:
-                out["interactions"] = inter[i].copy()
-            if div is not None:
-                out["dividends"], out["mass"] = div[i].copy(), mass[i].copy()
-            yield out
-
-
-def _batch_dividends(model, info, dividends):
-    """(dividends, mass) of a batch as host arrays [B, 2^P, n_out] from the coalition table its exact Shapley call kept, or (None, None)."""
-    if not dividends:
-        return None, None
-    div, mass = model.shapley_dividends(info["coalitions"], return_mass=True)
-    return div.cpu().numpy(), mass.cpu().numpy()
+            yield _optional_keys(out, i, eps, inter, div, mass)
 
 
 def same_regions(dataset, donor_dataset, genes=None):
@@ -1234,43 +1245,22 @@ def mark_donor_shapley(model, dataset, donor_dataset, genes=None, players="marks
     grad-enabled model(...) keeps for its backward."""
     import torch
     ds, dn = dataset, donor_dataset
-    binsizes = [int(b) for b in ds.binsizes]
-    _geometry_check("mark_donor_shapley", model, ds, binsizes)
-    genes, chunk = _genes_check("mark_donor_shapley", model, ds, genes, bsz)
-    same_regions(ds, dn, genes)
+    who = "mark_donor_shapley"
+    binsizes, _, genes, chunk = _open(who, model, ds, genes, bsz, dn)
     spec = players if isinstance(players, str) else list(players)
     names = mark_players(spec, ds.n_feats, ds.i_max)[2]      # (refusals before anything is loaded)
     if interactions is not None:
-        interaction_index(interactions, "mark_donor_shapley")
-    store = _resident_store("mark_donor_shapley", ds, genes, binsizes, model._device, store)
-    donor_store = _resident_store("mark_donor_shapley", dn, genes, binsizes, model._device, donor_store)
-    for lo in range(0, len(genes), chunk):
-        ids = genes[lo:lo + chunk]
-        idx = list(range(lo, lo + len(ids)))
-        d, dd = store.batch(idx), donor_store.batch(idx)
-        args = tuple(d[k] for k in _BATCH_KEYS)
-        donor = _donor_pair(dd)
-        inter = None
-        if interactions is None:
-            phi, info = model.mark_donor_shapley(*args, donor=donor, players=spec, return_coalitions=bool(dividends))
-        else:
-            inter, info = model.mark_donor_shapley_interactions(*args, donor=donor, players=spec, index=interactions, return_coalitions=bool(dividends))
-            phi, inter = info["phi"], inter.cpu().numpy()
-        div, mass = _batch_dividends(model, info, dividends)
-        phi, logits, don = phi.cpu().numpy(), info["logits"].cpu().numpy(), info["donor"].cpu().numpy()
+        interaction_index(interactions, who)
+    for ids, _, _, args, donor, dd in _batches(who, model, ds, genes, chunk, binsizes, store, dn, donor_store):
+        phi, inter, info, div, mass = _exact_game(model, "mark_donor", args, dict(donor=donor, players=spec), interactions, dividends)
+        logits, don = info["logits"].cpu().numpy(), info["donor"].cpu().numpy()
         eps = model.mark_donor_epistasis(*args, donor=donor, players=spec)[0].cpu().numpy() if epistasis else None
         with torch.no_grad():
             pred = model(*(dd[k] for k in _BATCH_KEYS)).cpu().numpy()
         for i, g in enumerate(ids):
             out = dict(gene_id=g, phi=phi[i].copy(), logits=logits[i].copy(), donor=don[i].copy(), donor_prediction=pred[i].copy(),
                        players=list(names))
-            if epistasis:
-                out["eps"] = eps[i].copy()
-            if inter is not None:
-                out["interactions"] = inter[i].copy()
-            if div is not None:
-                out["dividends"], out["mass"] = div[i].copy(), mass[i].copy()
-            yield out
+            yield _optional_keys(out, i, eps, inter, div, mass)
 
 
 def mark_shapley_sampled(model, dataset, donor_dataset=None, genes=None, players="cells", n_perm=64, seed=0, scale=0.0, bsz=None, store=None,
@@ -1294,26 +1284,12 @@ def mark_shapley_sampled(model, dataset, donor_dataset=None, genes=None, players
     as they are; the pass overwrites the activations a grad-enabled model(...) keeps for its backward."""
     ds, dn = dataset, donor_dataset
     who = "mark_shapley_sampled"
-    binsizes = [int(b) for b in ds.binsizes]
-    _geometry_check(who, model, ds, binsizes)
-    genes, chunk = _genes_check(who, model, ds, genes, bsz)
-    if dn is not None:
-        same_regions(ds, dn, genes)
+    binsizes, _, genes, chunk = _open(who, model, ds, genes, bsz, dn)
     spec = players if isinstance(players, str) else list(players)
     names = mark_players_wide(spec, ds.n_feats, ds.i_max)[2]      # (refusals before anything is loaded)
     perms = shapley_permutations(len(names), n_perm, seed)
-    store = _resident_store(who, ds, genes, binsizes, model._device, store)
-    if dn is not None:
-        donor_store = _resident_store(who, dn, genes, binsizes, model._device, donor_store)
-    for lo in range(0, len(genes), chunk):
-        ids = genes[lo:lo + chunk]
-        idx = list(range(lo, lo + len(ids)))
-        d = store.batch(idx)
-        donor = None
-        if dn is not None:
-            dd = donor_store.batch(idx)
-            donor = _donor_pair(dd)
-        phi, info = model.mark_shapley_sampled(*(d[k] for k in _BATCH_KEYS), players=spec, permutations=perms, scale=scale, donor=donor)
+    for ids, _, _, args, donor, _ in _batches(who, model, ds, genes, chunk, binsizes, store, dn, donor_store):
+        phi, info = model.mark_shapley_sampled(*args, players=spec, permutations=perms, scale=scale, donor=donor)
         phi, se, logits, absent = phi.cpu().numpy(), info["stderr"].cpu().numpy(), info["logits"].cpu().numpy(), info["absent"].cpu().numpy()
         for i, g in enumerate(ids):
             yield dict(gene_id=g, phi=phi[i].copy(), stderr=se[i].copy(), logits=logits[i].copy(), absent=absent[i].copy(), players=list(names),
@@ -1347,11 +1323,7 @@ def mark_shapley_interactions_sampled(model, dataset, donor_dataset=None, genes=
     as they are; the pass overwrites the activations a grad-enabled model(...) keeps for its backward."""
     ds, dn = dataset, donor_dataset
     who = "mark_shapley_interactions_sampled"
-    binsizes = [int(b) for b in ds.binsizes]
-    _geometry_check(who, model, ds, binsizes)
-    genes, chunk = _genes_check(who, model, ds, genes, bsz)
-    if dn is not None:
-        same_regions(ds, dn, genes)
+    binsizes, _, genes, chunk = _open(who, model, ds, genes, bsz, dn)
     spec = players if isinstance(players, str) else list(players)
     names = mark_players_wide(spec, ds.n_feats, ds.i_max)[2]      # (refusals before anything is loaded)
     P = len(names)
@@ -1363,28 +1335,26 @@ def mark_shapley_interactions_sampled(model, dataset, donor_dataset=None, genes=
     elif not 1 <= int(top) <= P:
         raise ValueError("%s: top = %r outside 1..%d" % (who, top, P))
     perms = shapley_permutations(P, n_perm, seed)
-    store = _resident_store(who, ds, genes, binsizes, model._device, store)
+    store = _resident_store(who, ds, genes, binsizes, model._device, store)      # (here: both iterators below read the same stores)
     if dn is not None:
         donor_store = _resident_store(who, dn, genes, binsizes, model._device, donor_store)
-    for lo in range(0, len(genes), chunk):
-        ids = genes[lo:lo + chunk]
-        idx = list(range(lo, lo + len(ids)))
-        lead = None
-        if focal is None:
-            d = store.batch(idx)
-            donor = _donor_pair(donor_store.batch(idx)) if dn is not None else None
-            phi = model.mark_shapley_sampled(*(d[k] for k in _BATCH_KEYS), players=spec, permutations=perms, scale=scale, donor=donor)[0]
-            lead = np.argsort(-np.abs(phi[..., -1].cpu().numpy()), axis=1, kind="stable")[:, :int(top)]
-        for i, g in enumerate(ids):
-            d = store.batch([lo + i])
-            donor = _donor_pair(donor_store.batch([lo + i])) if dn is not None else None
-            mine = focal if focal is not None else lead[i].astype(np.int32)
-            inter, info = model.mark_shapley_interactions_sampled(*(d[k] for k in _BATCH_KEYS), players=spec, focal=mine, index=index,
-                                                                  permutations=perms, scale=scale, donor=donor)
-            host = lambda t: t[0].cpu().numpy().copy()      # noqa: E731
-            yield dict(gene_id=g, interactions=host(inter), stderr=host(info["stderr"]), phi=host(info["phi"]), phi_stderr=host(info["phi_stderr"]),
-                       focal=np.array(mine, dtype=np.int32), focal_names=[names[int(p)] for p in mine], logits=host(info["logits"]),
-                       absent=host(info["absent"]), players=list(names), index=index, permutations=perms.copy())
+
+    def focal_of():      # per gene its focal players: `focal`, else the leaders among its chunk's sampled Shapley values
+        if focal is not None:
+            yield from (focal for _ in genes)
+            return
+        for _, _, _, args, donor, _ in _batches(who, model, ds, genes, chunk, binsizes, store, dn, donor_store):
+            phi = model.mark_shapley_sampled(*args, players=spec, permutations=perms, scale=scale, donor=donor)[0]
+            yield from np.argsort(-np.abs(phi[..., -1].cpu().numpy()), axis=1, kind="stable")[:, :int(top)].astype(np.int32)
+
+    # a chunk's batch is loaded when its first gene asks for its focal players, then each gene's own batch
+    for mine, ((g,), _, _, args, donor, _) in zip(focal_of(), _batches(who, model, ds, genes, 1, binsizes, store, dn, donor_store)):
+        inter, info = model.mark_shapley_interactions_sampled(*args, players=spec, focal=mine, index=index, permutations=perms, scale=scale,
+                                                              donor=donor)
+        host = lambda t: t[0].cpu().numpy().copy()      # noqa: E731
+        yield dict(gene_id=g, interactions=host(inter), stderr=host(info["stderr"]), phi=host(info["phi"]), phi_stderr=host(info["phi_stderr"]),
+                   focal=np.array(mine, dtype=np.int32), focal_names=[names[int(p)] for p in mine], logits=host(info["logits"]),
+                   absent=host(info["absent"]), players=list(names), index=index, permutations=perms.copy())
 
 
 def window_player_coordinates(marks_regions_windows, regions, n_real, binsize):
@@ -1435,11 +1405,7 @@ def mark_window_shapley(model, dataset, donor_dataset=None, genes=None, players=
     from .data import promoter_col0
     ds, dn = dataset, donor_dataset
     who = "mark_window_shapley"
-    binsizes = [int(b) for b in ds.binsizes]
-    n_bins = _geometry_check(who, model, ds, binsizes)
-    genes, chunk = _genes_check(who, model, ds, genes, bsz)
-    if dn is not None:
-        same_regions(ds, dn, genes)
+    binsizes, n_bins, genes, chunk = _open(who, model, ds, genes, bsz, dn)
     spec = players if isinstance(players, str) else list(players)
     rc = int(np.argmin(n_bins))
     W, bc = n_bins[rc], binsizes[rc]
@@ -1457,36 +1423,18 @@ def mark_window_shapley(model, dataset, donor_dataset=None, genes=None, players=
                          % (who, P))
     perms = None if exact else shapley_permutations(P, n_perm, seed)
     col0 = promoter_col0(ds)
-    store = _resident_store(who, ds, genes, binsizes, model._device, store)
-    if dn is not None:
-        donor_store = _resident_store(who, dn, genes, binsizes, model._device, donor_store)
-    for lo in range(0, len(genes), chunk):
-        ids = genes[lo:lo + chunk]
+    for ids, _, d, args, donor, _ in _batches(who, model, ds, genes, chunk, binsizes, store, dn, donor_store):
         B = len(ids)
-        idx = list(range(lo, lo + B))
-        d = store.batch(idx)
-        donor = None
-        if dn is not None:
-            dd = donor_store.batch(idx)
-            donor = _donor_pair(dd)
-        flip = [ds.genes[g]["tss"][2] != "+" for g in ids]
-        args = tuple(d[k] for k in _BATCH_KEYS)
-        inter, div = None, None
+        kw = dict(players=spec, width=width, scale=scale, donor=donor, flip=[ds.genes[g]["tss"][2] != "+" for g in ids])
+        inter, div, mass = None, None, None
         if exact:
-            if interactions is None:
-                phi, info = model.mark_window_shapley(*args, players=spec, width=width, scale=scale, donor=donor, flip=flip,
-                                                      return_coalitions=bool(dividends))
-            else:
-                inter, info = model.mark_window_shapley_interactions(*args, players=spec, width=width, scale=scale, donor=donor, flip=flip,
-                                                                     index=interactions, return_coalitions=bool(dividends))
-                phi, inter = info["phi"], inter.cpu().numpy()
-            div, mass = _batch_dividends(model, info, dividends)
+            phi, inter, info, div, mass = _exact_game(model, "mark_window", args, kw, interactions, dividends)
             absent = info["erased" if donor is None else "donor"].cpu().numpy()
-            se = np.zeros(tuple(phi.shape), dtype=np.float32)
+            se = np.zeros(phi.shape, dtype=np.float32)
         else:
-            phi, info = model.mark_window_shapley_sampled(*args, players=spec, width=width, permutations=perms, scale=scale, donor=donor, flip=flip)
-            absent, se = info["absent"].cpu().numpy(), info["stderr"].cpu().numpy()
-        phi, logits = phi.cpu().numpy(), info["logits"].cpu().numpy()
+            phi, info = model.mark_window_shapley_sampled(*args, permutations=perms, **kw)
+            phi, absent, se = phi.cpu().numpy(), info["absent"].cpu().numpy(), info["stderr"].cpu().numpy()
+        logits = info["logits"].cpu().numpy()
         pm = d["promoter_pad_masks"][bc].reshape(B, -1, W)
         pm = pm[:, pm.shape[1] // 2].cpu().numpy() == 0                       # the centre row of a full [L, L] mask, or the compact row
         cm = d["pcre_pad_masks"][bc].reshape(B, ds.i_max, -1, W)
@@ -1503,11 +1451,7 @@ def mark_window_shapley(model, dataset, donor_dataset=None, genes=None, players=
                        absent=absent[i].copy(), players=list(names), windows=windows, null=null)
             if not exact:
                 out["permutations"] = perms.copy()
-            if inter is not None:
-                out["interactions"] = inter[i].copy()
-            if div is not None:
-                out["dividends"], out["mass"] = div[i].copy(), mass[i].copy()
-            yield out
+            yield _optional_keys(out, i, None, inter, div, mass)
 
 
 def mark_fine_window_shapley(model, dataset, donor_dataset=None, genes=None, region="promoter", zoom=1, coarse_width=1, width=2, players="windows",
@@ -1549,11 +1493,7 @@ def mark_fine_window_shapley(model, dataset, donor_dataset=None, genes=None, reg
     from .data import promoter_col0
     ds, dn = dataset, donor_dataset
     who = "mark_fine_window_shapley"
-    binsizes = [int(b) for b in ds.binsizes]
-    n_bins = _geometry_check(who, model, ds, binsizes)
-    genes, chunk = _genes_check(who, model, ds, genes, bsz)
-    if dn is not None:
-        same_regions(ds, dn, genes)
+    binsizes, n_bins, genes, chunk = _open(who, model, ds, genes, bsz, dn)
     S, F = ds.i_max, ds.n_feats
     region = _region_index(who, region, S)
     zoom, coarse_width, width = int(zoom), int(coarse_width), int(width)
@@ -1584,19 +1524,7 @@ def mark_fine_window_shapley(model, dataset, donor_dataset=None, genes=None, reg
     cperms = None if Pc <= 16 else shapley_permutations(Pc, n_perm, seed)
     target = model.n_out - 1 if target is None else int(target)
     col0 = promoter_col0(ds)
-    store = _resident_store(who, ds, genes, binsizes, model._device, store)
-    if dn is not None:
-        donor_store = _resident_store(who, dn, genes, binsizes, model._device, donor_store)
-    for lo in range(0, len(genes), chunk):
-        ids = genes[lo:lo + chunk]
-        B = len(ids)
-        idx = list(range(lo, lo + B))
-        d = store.batch(idx)
-        donor = None
-        if dn is not None:
-            dd = donor_store.batch(idx)
-            donor = _donor_pair(dd)
-        args = tuple(d[k] for k in _BATCH_KEYS)
+    for ids, _, _, args, donor, _ in _batches(who, model, ds, genes, chunk, binsizes, store, dn, donor_store):
         flip = [region == 0 and ds.genes[g]["tss"][2] != "+" for g in ids]
         regs = [_gene_region(ds, g, region, col0) for g in ids]
         lengths = [r[2] - r[1] if r else 0 for r in regs]
@@ -1625,17 +1553,11 @@ def mark_fine_window_shapley(model, dataset, donor_dataset=None, genes=None, reg
             kw = dict(region=region, players=spec, width=width, n_windows=n_fw, start=start, lengths=lengths, scale=scale, donor=donor, flip=flip)
             inter, div = None, None
             if exact:
-                if interactions is None:
-                    phi, info = model.mark_fine_window_shapley(*args, return_coalitions=bool(dividends), **kw)
-                else:
-                    inter, info = model.mark_fine_window_shapley_interactions(*args, index=interactions, return_coalitions=bool(dividends), **kw)
-                    phi, inter = info["phi"], inter.cpu().numpy()
-                div, mass = _batch_dividends(model, info, dividends)
+                phi, inter, info, div, mass = _exact_game(model, "mark_fine_window", args, kw, interactions, dividends)
                 absent, se = info["erased" if donor is None else "donor"].cpu().numpy(), None
             else:
                 phi, info = model.mark_fine_window_shapley_sampled(*args, permutations=perms, **kw)
-                absent, se = info["absent"].cpu().numpy(), info["stderr"].cpu().numpy()
-            phi = phi.cpu().numpy()
+                phi, absent, se = phi.cpu().numpy(), info["absent"].cpu().numpy(), info["stderr"].cpu().numpy()
             for i, r in enumerate(regs):
                 if rank >= len(ranks[i]):
                     continue

@@ -46,18 +46,55 @@ def modernise_keys(state):
     return out
 
 
+def _savez(path, **arrays):
+    """np.savez to exactly `path` (through a file object: given a name without .npz, np.savez would append it)."""
+    with open(path, "wb") as f:
+        np.savez(f, **arrays)
+
+
+def _slot_batches(who, model, store, bsz):
+    """The genes of a device-resident store, in store order, in batches of at most bsz -> (lo, B, slot) per batch: genes lo .. lo + B - 1
+    gathered on the device (cf_gather_batch) into a Slot of B genes, one Slot per size.  The gather's error word is read when the
+    caller comes back for the next batch, after its own work on this one: an error raises RuntimeError naming `who`, the writer."""
+    import ctypes as C
+
+    from . import _lib
+    n, dev, L = len(store), model._device, _lib.lib()
+    struct = store.struct()
+    order = torch.arange(n, dtype=torch.int32, device=dev)
+    slots = {}
+    st = torch.cuda.current_stream(dev).cuda_stream
+    for lo in range(0, n, bsz):
+        B = min(bsz, n - lo)
+        slot = slots.get(B) or slots.setdefault(B, Slot(model, B))
+        cursor = torch.tensor([0, 1, 0, 0], dtype=torch.int32).to(dev)
+        _lib.check(L.cf_gather_batch(model._handle, C.byref(struct), order[lo:].data_ptr(), cursor.data_ptr(), C.byref(slot.struct), None, st),
+                   "cf_gather_batch")
+        yield lo, B, slot
+        if int(cursor[2].item()):
+            raise RuntimeError("%s: the device-side gather reported errors at gene %d (store / order mismatch)" % (who, lo))
+
+
+def _dict_batches(store, donor_store, bsz):
+    """The genes of a device-resident store, in store order, in batches of at most bsz -> (lo, B, forward()'s six arguments from
+    store.batch, the donor pair from donor_store.batch or None without a donor store, the donor's batch dict or None) per batch."""
+    from .attribution import _BATCH_KEYS, _donor_pair
+    for lo in range(0, len(store), bsz):
+        idx = list(range(lo, min(lo + bsz, len(store))))
+        d = store.batch(idx)
+        dd = donor_store.batch(idx) if donor_store is not None else None
+        yield lo, len(idx), tuple(d[k] for k in _BATCH_KEYS), None if dd is None else _donor_pair(dd), dd
+
+
 def write_attention_maps(model, store, bsz, attention_dir=None, embeddings_out=None):
     """Attention maps (`attention_dir`/{embed,pairwise_interaction,regulation}_{binsize}.npy) and / or the regulatory embedding
     (`embeddings_out`, [n_genes, 3 * d_emb]) of every gene of a device-resident store, in store order.  Per batch: one device gather
     into a Slot and one model.attention_maps; the rows go straight into .npy memory maps (nothing is gathered in host memory)."""
-    import ctypes as C
     import os
-
-    from . import _lib
     which = (("embed", "pairwise_interaction", "regulation") if attention_dir else ()) + (("regulatory_embedding",) if embeddings_out else ())
     if not which:
         return
-    n, dev, L = len(store), model._device, _lib.lib()
+    n = len(store)
     embed, pair, reg = model._kws
     S, T = model.i_max, model.i_max + 1
     outs = {}
@@ -71,19 +108,8 @@ def write_attention_maps(model, store, bsz, attention_dir=None, embeddings_out=N
     if embeddings_out:
         outs["regulatory_embedding", None] = np.lib.format.open_memmap(embeddings_out, mode="w+", dtype=np.float32,
                                                                        shape=(n, len(model.binsizes) * model.d_emb))
-    struct = store.struct()
-    order = torch.arange(n, dtype=torch.int32, device=dev)
-    slots = {}
-    st = torch.cuda.current_stream(dev).cuda_stream
-    for lo in range(0, n, bsz):
-        B = min(bsz, n - lo)
-        slot = slots.get(B) or slots.setdefault(B, Slot(model, B))
-        cursor = torch.tensor([0, 1, 0, 0], dtype=torch.int32).to(dev)
-        _lib.check(L.cf_gather_batch(model._handle, C.byref(struct), order[lo:].data_ptr(), cursor.data_ptr(), C.byref(slot.struct), None, st),
-                   "cf_gather_batch")
+    for lo, B, slot in _slot_batches("write_attention_maps", model, store, bsz):
         _, maps = model.attention_maps(slot, which=which)
-        if int(cursor[2].item()):
-            raise RuntimeError("write_attention_maps: the device-side gather reported errors at gene %d (store / order mismatch)" % lo)
         for (key, b), mm in outs.items():
             mm[lo:lo + B] = (maps[key] if b is None else maps[key][b]).cpu().numpy()
     for mm in outs.values():
@@ -96,26 +122,10 @@ def write_pcre_ablation(model, store, bsz, path, regression=False):
     (column 0), pCRE slot j deleted (column 1 + j) and the promoter alone (last column).  Per batch: one device gather into a Slot
     and one model.pcre_ablation.  The logits (8 bytes per gene and column) are kept on the host; each column goes through the
     very sigmoid call predict() makes on the [n_genes, 2] logits, so column 0 is the prediction bit for bit."""
-    import ctypes as C
-
-    from . import _lib
-    n, dev, L = len(store), model._device, _lib.lib()
-    V = model.i_max + 2
+    n, V = len(store), model.i_max + 2
     logits = torch.empty(n, V, model.n_out)
-    struct = store.struct()
-    order = torch.arange(n, dtype=torch.int32, device=dev)
-    slots = {}
-    st = torch.cuda.current_stream(dev).cuda_stream
-    for lo in range(0, n, bsz):
-        B = min(bsz, n - lo)
-        slot = slots.get(B) or slots.setdefault(B, Slot(model, B))
-        cursor = torch.tensor([0, 1, 0, 0], dtype=torch.int32).to(dev)
-        _lib.check(L.cf_gather_batch(model._handle, C.byref(struct), order[lo:].data_ptr(), cursor.data_ptr(), C.byref(slot.struct), None, st),
-                   "cf_gather_batch")
-        out = model.pcre_ablation(slot)
-        if int(cursor[2].item()):
-            raise RuntimeError("write_pcre_ablation: the device-side gather reported errors at gene %d (store / order mismatch)" % lo)
-        logits[lo:lo + B] = out.cpu()
+    for lo, B, slot in _slot_batches("write_pcre_ablation", model, store, bsz):
+        logits[lo:lo + B] = model.pcre_ablation(slot).cpu()
     mm = np.lib.format.open_memmap(path, mode="w+", dtype=np.float32, shape=(n, V))
     for v in range(V):
         col = logits[:, v].contiguous()          # [n_genes, n_out], laid out as the logits predict() turns into its column
@@ -123,156 +133,84 @@ def write_pcre_ablation(model, store, bsz, path, regression=False):
     mm.flush()
 
 
-def write_pcre_coalition_values(model, store, bsz, shapley_out=None, epistasis_out=None, regression=False, interactions_out=None, index="sii"):
-    """Exact Shapley values and / or pair-deletion epistasis of the pCREs of every gene of a device-resident store, in store order,
-    in LOGIT space of the prediction's column (1 for the classifier, 0 for the regressor: the efficiency identity
-    phi.sum(1) = logits - promoter_only holds there, not after the sigmoid).  shapley_out: an .npz with phi [n_genes, i_max],
-    logits [n_genes], promoter_only [n_genes] and n_pcres [n_genes] (the slots that are no dummies); epistasis_out: a float32 .npy
-    [n_genes, i_max, i_max]; interactions_out: a float32 .npy [n_genes, i_max, i_max], the pairwise Shapley interaction index `index`
-    ("sii" / "sti").  Per batch: one device gather into a Slot, one model.pcre_shapley and / or one model.pcre_epistasis; with
-    interactions_out one model.pcre_shapley_interactions, which serves shapley_out too (the 2^i_max forwards run once)."""
-    import ctypes as C
-
-    from . import _lib
-    n, dev, L = len(store), model._device, _lib.lib()
-    S, t = model.i_max, 0 if regression else 1
-    phi, logits, alone = torch.empty(n, S), torch.empty(n), torch.empty(n)
-    n_pcres = torch.empty(n, dtype=torch.int32)
-    eps = np.lib.format.open_memmap(epistasis_out, mode="w+", dtype=np.float32, shape=(n, S, S)) if epistasis_out else None
-    inter = np.lib.format.open_memmap(interactions_out, mode="w+", dtype=np.float32, shape=(n, S, S)) if interactions_out else None
-    struct = store.struct()
-    order = torch.arange(n, dtype=torch.int32, device=dev)
-    slots = {}
-    st = torch.cuda.current_stream(dev).cuda_stream
-    for lo in range(0, n, bsz):
-        B = min(bsz, n - lo)
-        slot = slots.get(B) or slots.setdefault(B, Slot(model, B))
-        cursor = torch.tensor([0, 1, 0, 0], dtype=torch.int32).to(dev)
-        _lib.check(L.cf_gather_batch(model._handle, C.byref(struct), order[lo:].data_ptr(), cursor.data_ptr(), C.byref(slot.struct), None, st),
-                   "cf_gather_batch")
-        if inter is not None:
-            x, info = model.pcre_shapley_interactions(slot, index=index)
-            inter[lo:lo + B] = x[..., t].cpu().numpy()
-            p = info["phi"]
-        elif shapley_out:
-            p, info = model.pcre_shapley(slot)
-        if shapley_out:
-            phi[lo:lo + B] = p[..., t].cpu()
-            logits[lo:lo + B] = info["logits"][:, t].cpu()
-            alone[lo:lo + B] = info["promoter_only"][:, t].cpu()
-            dummy = torch.stack([m[:, 0, 1:] != 0 for m in slot.im]).all(0)      # a dummy slot: its key masked for the promoter row, every resolution
-            n_pcres[lo:lo + B] = (~dummy).sum(1).to(torch.int32).cpu()
-        if eps is not None:
-            eps[lo:lo + B] = model.pcre_epistasis(slot)[0][..., t].cpu().numpy()
-        if int(cursor[2].item()):
-            raise RuntimeError("write_pcre_coalition_values: the device-side gather reported errors at gene %d (store / order mismatch)" % lo)
-    if shapley_out:
-        with open(shapley_out, "wb") as f:      # (a file object: np.savez would append .npz to a name without it)
-            np.savez(f, phi=phi.numpy(), logits=logits.numpy(), promoter_only=alone.numpy(), n_pcres=n_pcres.numpy())
-    if eps is not None:
-        eps.flush()
-    if inter is not None:
-        inter.flush()
+_EXACT_GAMES = {      # the exact games of the writers, by the prefix of their model methods (<game>_shapley, _epistasis, _dividends, ...):
+    # kw: the keyword arguments those methods take; absent: info's key (and the .npz column) of the prediction with every player absent;
+    # extra: the game's own column of the Shapley .npz
+    "pcre": dict(kw=(), absent="promoter_only", extra="n_pcres"),
+    "mark": dict(kw=("players", "scale"), absent="erased", extra=None),
+    "mark_donor": dict(kw=("donor", "players"), absent="donor", extra="donor_prediction"),
+}
 
 
-def write_mark_values(model, store, bsz, gene_ids, shapley_out=None, epistasis_out=None, regression=False, players="marks", scale=0.0,
-                      interactions_out=None, index="sii"):
-    """Exact Shapley values and / or pair epistasis of the histone marks of every gene of a device-resident store, in store order, in
-    LOGIT space of the prediction's column (1 for the classifier, 0 for the regressor: efficiency holds there, not after the
-    sigmoid).  shapley_out: an .npz with gene_ids [n], players [P] (names), phi [n, P], logits [n] and erased [n] (phi sums to
-    their difference); epistasis_out: a float32 .npy [n, P, P]; interactions_out: a float32 .npy [n, P, P], the pairwise Shapley
-    interaction index `index` ("sii" / "sti").  Per batch: one device gather into a Slot, one model.mark_shapley and / or one
-    model.mark_epistasis; with interactions_out one model.mark_shapley_interactions, which serves shapley_out too."""
-    import ctypes as C
+def _game_kw(game, players, scale, donor):
+    """The keyword arguments of an exact game's model methods."""
+    given = dict(players=players, scale=scale, donor=donor)
+    return {k: given[k] for k in _EXACT_GAMES[game]["kw"]}
 
-    from . import _lib
-    from .attribution import mark_players
-    n, dev, L = len(store), model._device, _lib.lib()
-    names = mark_players(players, model.n_feats, model.i_max)[2]
-    P, t = len(names), 0 if regression else 1
-    phi, logits, erased = torch.empty(n, P), torch.empty(n), torch.empty(n)
+
+def write_exact_values(model, game, store, donor_store, bsz, gene_ids, shapley_out=None, epistasis_out=None, interactions_out=None,
+                       regression=False, players="marks", scale=0.0, index="sii"):
+    """Exact Shapley values, pair epistasis and / or pairwise Shapley interaction indices of one game of every gene of a device-resident
+    store, in store order, in LOGIT space of the prediction's column (1 for the classifier, 0 for the regressor: the efficiency identity
+    phi.sum(1) = logits - absent holds there, not after the sigmoid).  game (_EXACT_GAMES):
+
+        "pcre"         the pCREs (P = i_max).  shapley_out: an .npz with phi [n, P], logits [n], promoter_only [n] and n_pcres [n] (the
+                       slots that are no dummies)
+        "mark"         the histone marks; players (attribution.mark_players) and scale apply.  shapley_out: an .npz with gene_ids [n],
+                       players [P] (names), phi [n, P], logits [n] and erased [n]
+        "mark_donor"   the marks against donor_store, the same genes in the same order in a donor cell type; players applies.
+                       shapley_out: gene_ids, players, phi, logits, donor [n] (every player's marks from the donor, under the gene's
+                       masks and frequencies) and donor_prediction [n] (the plain forward of the donor's own batch)
+
+    epistasis_out: a float32 .npy [n, P, P]; interactions_out: a float32 .npy [n, P, P], the index `index` ("sii" / "sti").  Per batch:
+    one device gather into a Slot (the donor game: one store.batch per store), one model.<game>_shapley and / or one
+    model.<game>_epistasis; with interactions_out one model.<game>_shapley_interactions, which serves shapley_out too (the 2^P forwards
+    run once); the donor game's shapley_out adds one plain forward of the donor's batch."""
+    from .attribution import _BATCH_KEYS, mark_players
+    who, desc = "write_exact_values", _EXACT_GAMES[game]
+    n, t, with_donor = len(store), 0 if regression else 1, "donor" in desc["kw"]
+    if with_donor and len(donor_store) != n:
+        raise ValueError("%s: the donor store holds %d genes, the store %d" % (who, len(donor_store), n))
+    names = mark_players(players, model.n_feats, model.i_max)[2] if "players" in desc["kw"] else None
+    P = model.i_max if names is None else len(names)
+    phi, logits, absent = torch.empty(n, P), torch.empty(n), torch.empty(n)
+    extra = torch.empty(n, dtype=torch.int32 if game == "pcre" else torch.float32)
     eps = np.lib.format.open_memmap(epistasis_out, mode="w+", dtype=np.float32, shape=(n, P, P)) if epistasis_out else None
     inter = np.lib.format.open_memmap(interactions_out, mode="w+", dtype=np.float32, shape=(n, P, P)) if interactions_out else None
-    struct = store.struct()
-    order = torch.arange(n, dtype=torch.int32, device=dev)
-    slots = {}
-    st = torch.cuda.current_stream(dev).cuda_stream
-    for lo in range(0, n, bsz):
-        B = min(bsz, n - lo)
-        slot = slots.get(B) or slots.setdefault(B, Slot(model, B))
-        cursor = torch.tensor([0, 1, 0, 0], dtype=torch.int32).to(dev)
-        _lib.check(L.cf_gather_batch(model._handle, C.byref(struct), order[lo:].data_ptr(), cursor.data_ptr(), C.byref(slot.struct), None, st),
-                   "cf_gather_batch")
+    if with_donor:
+        batches = _dict_batches(store, donor_store, bsz)
+    else:      # (the Slot alone: the packed form of the methods' first argument)
+        batches = ((lo, B, (slot,), None, None) for lo, B, slot in _slot_batches(who, model, store, bsz))
+    for lo, B, args, feats, dd in batches:
+        kw = _game_kw(game, players, scale, feats)
         if inter is not None:
-            x, info = model.mark_shapley_interactions(slot, players=players, scale=scale, index=index)
+            x, info = getattr(model, game + "_shapley_interactions")(*args, index=index, **kw)
             inter[lo:lo + B] = x[..., t].cpu().numpy()
             p = info["phi"]
         elif shapley_out:
-            p, info = model.mark_shapley(slot, players=players, scale=scale)
+            p, info = getattr(model, game + "_shapley")(*args, **kw)
         if shapley_out:
             phi[lo:lo + B] = p[..., t].cpu()
             logits[lo:lo + B] = info["logits"][:, t].cpu()
-            erased[lo:lo + B] = info["erased"][:, t].cpu()
+            absent[lo:lo + B] = info[desc["absent"]][:, t].cpu()
+            if game == "pcre":
+                dummy = torch.stack([m[:, 0, 1:] != 0 for m in args[0].im]).all(0)      # a dummy slot: its key masked for the promoter row, every resolution
+                extra[lo:lo + B] = (~dummy).sum(1).to(torch.int32).cpu()
+            elif with_donor:
+                with torch.no_grad():
+                    extra[lo:lo + B] = model(*(dd[k] for k in _BATCH_KEYS))[:, t].cpu()
         if eps is not None:
-            eps[lo:lo + B] = model.mark_epistasis(slot, players=players, scale=scale)[0][..., t].cpu().numpy()
-        if int(cursor[2].item()):
-            raise RuntimeError("write_mark_values: the device-side gather reported errors at gene %d (store / order mismatch)" % lo)
+            eps[lo:lo + B] = getattr(model, game + "_epistasis")(*args, **kw)[0][..., t].cpu().numpy()
     if shapley_out:
-        with open(shapley_out, "wb") as f:      # (a file object: np.savez would append .npz to a name without it)
-            np.savez(f, gene_ids=np.array(list(gene_ids)), players=np.array(names), phi=phi.numpy(), logits=logits.numpy(), erased=erased.numpy())
-    if eps is not None:
-        eps.flush()
-    if inter is not None:
-        inter.flush()
-
-
-def write_mark_donor_values(model, store, donor_store, bsz, gene_ids, shapley_out=None, epistasis_out=None, regression=False, players="marks",
-                            interactions_out=None, index="sii"):
-    """Exact Shapley values and / or pair epistasis of the histone marks against a donor cell type, for every gene of two
-    device-resident stores that hold the same genes in the same order, in LOGIT space of the prediction's column.  shapley_out: an .npz
-    with gene_ids [n], players [P] (names), phi [n, P], logits [n], donor [n] (every player's marks from the donor, under the gene's
-    masks and frequencies; phi sums to logits - donor) and donor_prediction [n] (the plain forward of the donor's own batch);
-    epistasis_out: a float32 .npy [n, P, P]; interactions_out: a float32 .npy [n, P, P], the pairwise Shapley interaction index
-    `index` ("sii" / "sti").  Per batch: one gather per store, one model.mark_donor_shapley and / or one model.mark_donor_epistasis,
-    one plain forward of the donor's batch; with interactions_out one model.mark_donor_shapley_interactions, which serves shapley_out
-    too."""
-    from .attribution import _BATCH_KEYS, _donor_pair, mark_players
-    n = len(store)
-    if len(donor_store) != n:
-        raise ValueError("write_mark_donor_values: the donor store holds %d genes, the store %d" % (len(donor_store), n))
-    names = mark_players(players, model.n_feats, model.i_max)[2]
-    P, t = len(names), 0 if regression else 1
-    phi, logits, donor, pred = torch.empty(n, P), torch.empty(n), torch.empty(n), torch.empty(n)
-    eps = np.lib.format.open_memmap(epistasis_out, mode="w+", dtype=np.float32, shape=(n, P, P)) if epistasis_out else None
-    inter = np.lib.format.open_memmap(interactions_out, mode="w+", dtype=np.float32, shape=(n, P, P)) if interactions_out else None
-    for lo in range(0, n, bsz):
-        B = min(bsz, n - lo)
-        idx = list(range(lo, lo + B))
-        d, dd = store.batch(idx), donor_store.batch(idx)
-        args = tuple(d[k] for k in _BATCH_KEYS)
-        feats = _donor_pair(dd)
-        if inter is not None:
-            x, info = model.mark_donor_shapley_interactions(*args, donor=feats, players=players, index=index)
-            inter[lo:lo + B] = x[..., t].cpu().numpy()
-            p = info["phi"]
-        elif shapley_out:
-            p, info = model.mark_donor_shapley(*args, donor=feats, players=players)
-        if shapley_out:
-            phi[lo:lo + B] = p[..., t].cpu()
-            logits[lo:lo + B] = info["logits"][:, t].cpu()
-            donor[lo:lo + B] = info["donor"][:, t].cpu()
-            with torch.no_grad():
-                pred[lo:lo + B] = model(*(dd[k] for k in _BATCH_KEYS))[:, t].cpu()
-        if eps is not None:
-            eps[lo:lo + B] = model.mark_donor_epistasis(*args, donor=feats, players=players)[0][..., t].cpu().numpy()
-    if shapley_out:
-        with open(shapley_out, "wb") as f:      # (a file object: np.savez would append .npz to a name without it)
-            np.savez(f, gene_ids=np.array(list(gene_ids)), players=np.array(names), phi=phi.numpy(), logits=logits.numpy(), donor=donor.numpy(),
-                     donor_prediction=pred.numpy())
-    if eps is not None:
-        eps.flush()
-    if inter is not None:
-        inter.flush()
+        cols = {"phi": phi.numpy(), "logits": logits.numpy(), desc["absent"]: absent.numpy()}
+        if desc["extra"]:
+            cols[desc["extra"]] = extra.numpy()
+        if names is not None:
+            cols = dict(gene_ids=np.array(list(gene_ids)), players=np.array(names), **cols)
+        _savez(shapley_out, **cols)
+    for mm in (eps, inter):
+        if mm is not None:
+            mm.flush()
 
 
 def write_dividends(model, store, donor_store, bsz, gene_ids, path, game="mark", regression=False, players="marks", scale=0.0):
@@ -282,32 +220,22 @@ def write_dividends(model, store, donor_store, bsz, gene_ids, path, game="mark",
     a dividend's rounding error, attribution.dividend_bound).  game: "pcre" (model.pcre_dividends), "mark" (model.mark_dividends; players
     and scale apply) or "mark_donor" (model.mark_donor_dividends against donor_store, the same genes in the same order; players
     applies).  Per batch: one gather per store and one such call (its own 2^P forwards)."""
-    from .attribution import _BATCH_KEYS, _donor_pair
     n = len(store)
-    if game not in ("pcre", "mark", "mark_donor"):
-        raise ValueError("write_dividends: unknown game %r; choose from ['pcre', 'mark', 'mark_donor']" % (game,))
-    if game == "mark_donor" and (donor_store is None or len(donor_store) != n):
+    if game not in _EXACT_GAMES:
+        raise ValueError("write_dividends: unknown game %r; choose from %s" % (game, list(_EXACT_GAMES)))
+    with_donor = "donor" in _EXACT_GAMES[game]["kw"]
+    if with_donor and (donor_store is None or len(donor_store) != n):
         raise ValueError("write_dividends: the donor store must hold the store's %d genes" % n)
     t = 0 if regression else 1
     div, mass, names, sets = None, None, None, None
-    for lo in range(0, n, bsz):
-        B = min(bsz, n - lo)
-        idx = list(range(lo, lo + B))
-        d = store.batch(idx)
-        args = tuple(d[k] for k in _BATCH_KEYS)
-        if game == "pcre":
-            x, info = model.pcre_dividends(*args)
-        elif game == "mark":
-            x, info = model.mark_dividends(*args, players=players, scale=scale)
-        else:
-            x, info = model.mark_donor_dividends(*args, donor=_donor_pair(donor_store.batch(idx)), players=players)
+    for lo, B, args, feats, _ in _dict_batches(store, donor_store if with_donor else None, bsz):
+        x, info = getattr(model, game + "_dividends")(*args, **_game_kw(game, players, scale, feats))
         if div is None:
             div, mass = np.empty((n, x.shape[1]), np.float32), np.empty((n, x.shape[1]), np.float32)
             names, sets = info["names"], info["sets"]
         div[lo:lo + B] = x[..., t].cpu().numpy()
         mass[lo:lo + B] = info["mass"][..., t].cpu().numpy()
-    with open(path, "wb") as f:      # (a file object: np.savez would append .npz to a name without it)
-        np.savez(f, gene_ids=np.array(list(gene_ids)), players=np.array(names), sets=np.array(sets), dividends=div, mass=mass)
+    _savez(path, gene_ids=np.array(list(gene_ids)), players=np.array(names), sets=np.array(sets), dividends=div, mass=mass)
 
 
 def write_mark_sampled_values(model, store, donor_store, bsz, gene_ids, path, regression=False, players="cells", n_perm=64, seed=0, scale=0.0):
@@ -317,7 +245,7 @@ def write_mark_sampled_values(model, store, donor_store, bsz, gene_ids, path, re
     phi over the orders: the sampling error is reported, not bounded), logits [n] and absent [n] (every player absent; phi sums to
     their difference).  donor_store None: an absent player's raw signal is scaled by `scale`; else a store of the same genes in the
     same order in the donor cell type, whose signal it takes.  Per batch: one gather per store and one model.mark_shapley_sampled."""
-    from .attribution import _BATCH_KEYS, _donor_pair, mark_players_wide, shapley_permutations
+    from .attribution import mark_players_wide, shapley_permutations
     n = len(store)
     if donor_store is not None and len(donor_store) != n:
         raise ValueError("write_mark_sampled_values: the donor store holds %d genes, the store %d" % (len(donor_store), n))
@@ -325,22 +253,14 @@ def write_mark_sampled_values(model, store, donor_store, bsz, gene_ids, path, re
     P, t = len(names), 0 if regression else 1
     perms = shapley_permutations(P, n_perm, seed)
     phi, se, logits, absent = torch.empty(n, P), torch.empty(n, P), torch.empty(n), torch.empty(n)
-    for lo in range(0, n, bsz):
-        B = min(bsz, n - lo)
-        idx = list(range(lo, lo + B))
-        d = store.batch(idx)
-        feats = None
-        if donor_store is not None:
-            dd = donor_store.batch(idx)
-            feats = _donor_pair(dd)
-        p, info = model.mark_shapley_sampled(*(d[k] for k in _BATCH_KEYS), players=players, permutations=perms, scale=scale, donor=feats)
+    for lo, B, args, feats, _ in _dict_batches(store, donor_store, bsz):
+        p, info = model.mark_shapley_sampled(*args, players=players, permutations=perms, scale=scale, donor=feats)
         phi[lo:lo + B] = p[..., t].cpu()
         se[lo:lo + B] = info["stderr"][..., t].cpu()
         logits[lo:lo + B] = info["logits"][:, t].cpu()
         absent[lo:lo + B] = info["absent"][:, t].cpu()
-    with open(path, "wb") as f:      # (a file object: np.savez would append .npz to a name without it)
-        np.savez(f, gene_ids=np.array(list(gene_ids)), players=np.array(names), permutations=perms, phi=phi.numpy(), stderr=se.numpy(),
-                 logits=logits.numpy(), absent=absent.numpy())
+    _savez(path, gene_ids=np.array(list(gene_ids)), players=np.array(names), permutations=perms, phi=phi.numpy(), stderr=se.numpy(),
+           logits=logits.numpy(), absent=absent.numpy())
 
 
 def write_mark_sampled_interactions(model, ds, donor_ds, store, donor_store, bsz, gene_ids, path, regression=False, players="cells", top=4, focal=None,
@@ -356,12 +276,11 @@ def write_mark_sampled_interactions(model, ds, donor_ds, store, donor_store, bsz
     t = 0 if regression else 1
     res = list(mark_shapley_interactions_sampled(model, ds, donor_ds, genes=list(gene_ids), players=players, top=top, focal=focal, index=index,
                                                  n_perm=n_perm, seed=seed, scale=scale, bsz=bsz, store=store, donor_store=donor_store))
-    with open(path, "wb") as f:      # (a file object: np.savez would append .npz to a name without it)
-        np.savez(f, gene_ids=np.array(list(gene_ids)), players=np.array(res[0]["players"]), index=np.array(index), permutations=res[0]["permutations"],
-                 focal=np.stack([r["focal"] for r in res]), interactions=np.stack([r["interactions"][..., t] for r in res]),
-                 stderr=np.stack([r["stderr"][..., t] for r in res]), phi=np.stack([r["phi"][..., t] for r in res]),
-                 phi_stderr=np.stack([r["phi_stderr"][..., t] for r in res]), logits=np.array([r["logits"][t] for r in res], dtype=np.float32),
-                 absent=np.array([r["absent"][t] for r in res], dtype=np.float32))
+    _savez(path, gene_ids=np.array(list(gene_ids)), players=np.array(res[0]["players"]), index=np.array(index), permutations=res[0]["permutations"],
+           focal=np.stack([r["focal"] for r in res]), interactions=np.stack([r["interactions"][..., t] for r in res]),
+           stderr=np.stack([r["stderr"][..., t] for r in res]), phi=np.stack([r["phi"][..., t] for r in res]),
+           phi_stderr=np.stack([r["phi_stderr"][..., t] for r in res]), logits=np.array([r["logits"][t] for r in res], dtype=np.float32),
+           absent=np.array([r["absent"][t] for r in res], dtype=np.float32))
 
 
 def write_mark_window_values(model, ds, donor_ds, store, donor_store, bsz, gene_ids, path, regression=False, players="promoter", width=1, n_perm=64,
@@ -388,8 +307,7 @@ def write_mark_window_values(model, ds, donor_ds, store, donor_store, bsz, gene_
                null=np.stack([r["null"] for r in rows]), chroms=chroms.astype(str), windows=windows)
     if "permutations" in rows[0]:
         out["permutations"] = rows[0]["permutations"]
-    with open(path, "wb") as f:      # (a file object: np.savez would append .npz to a name without it)
-        np.savez(f, **out)
+    _savez(path, **out)
 
 
 def write_mark_fine_window_values(model, ds, donor_ds, store, donor_store, bsz, gene_ids, path, regression=False, region="promoter", width=2,
@@ -426,8 +344,7 @@ def write_mark_fine_window_values(model, ds, donor_ds, store, donor_store, bsz, 
             out["stderr"][at] = r["stderr"][:, t]
         if len(r["windows"]):
             out["windows"][at] = np.array([w[1:] for w in r["windows"]], dtype=np.int64)
-    with open(path, "wb") as f:      # (a file object: np.savez would append .npz to a name without it)
-        np.savez(f, **out)
+    _savez(path, **out)
 
 
 def write_integrated_gradients(model, store, bsz, ig_dir, n_steps=50, method="gausslegendre", target=None):
@@ -435,12 +352,8 @@ def write_integrated_gradients(model, store, bsz, ig_dir, n_steps=50, method="ga
     [n, L, F], pcre_feats_{b}.npy [n, i_max, L, F], interaction_freq.npy [n, T, T] and delta.npy [n] (float32 .npy memory maps;
     nothing is gathered in host memory).  Zero baseline, every float input interpolated.  Per batch: one device gather into a Slot
     and one model.integrated_gradients."""
-    import ctypes as C
     import os
-
-    from . import _lib
-    n, dev, L = len(store), model._device, _lib.lib()
-    S, T, F = model.i_max, model.i_max + 1, model.n_feats
+    n, S, T, F = len(store), model.i_max, model.i_max + 1, model.n_feats
     os.makedirs(ig_dir, exist_ok=True)
 
     def mm(name, shape):
@@ -452,19 +365,8 @@ def write_integrated_gradients(model, store, bsz, ig_dir, n_steps=50, method="ga
         outs["pcre_feats", b] = mm("pcre_feats_%d" % b, (S, nb, F))
     outs["interaction_freq", None] = mm("interaction_freq", (T, T))
     outs["delta", None] = mm("delta", ())
-    struct = store.struct()
-    order = torch.arange(n, dtype=torch.int32, device=dev)
-    slots = {}
-    st = torch.cuda.current_stream(dev).cuda_stream
-    for lo in range(0, n, bsz):
-        B = min(bsz, n - lo)
-        slot = slots.get(B) or slots.setdefault(B, Slot(model, B))
-        cursor = torch.tensor([0, 1, 0, 0], dtype=torch.int32).to(dev)
-        _lib.check(L.cf_gather_batch(model._handle, C.byref(struct), order[lo:].data_ptr(), cursor.data_ptr(), C.byref(slot.struct), None, st),
-                   "cf_gather_batch")
+    for lo, B, slot in _slot_batches("write_integrated_gradients", model, store, bsz):
         attr, info = model.integrated_gradients(slot, target=target, n_steps=n_steps, method=method)
-        if int(cursor[2].item()):
-            raise RuntimeError("write_integrated_gradients: the device-side gather reported errors at gene %d (store / order mismatch)" % lo)
         attr["delta"] = info["delta"]
         for (key, b), m in outs.items():
             m[lo:lo + B] = (attr[key] if b is None else attr[key][b]).cpu().numpy()
@@ -487,12 +389,8 @@ def write_perturbation_scan(model, store, bsz, path, gene_ids, strands, regressi
         pcres        float32 [n, i_max, n_sets, W], with regions="all": the same per pCRE slot (NaN for dummy slots)
 
     Per batch: one device gather into a Slot and one model.perturbation_scan_regions over the scanned regions."""
-    import ctypes as C
-
-    from . import _lib
     from .attribution import scan_mark_sets, scan_regions_expand, scan_row
-    n, dev, L = len(store), model._device, _lib.lib()
-    S, F = model.i_max, model.n_feats
+    n, S, F = len(store), model.i_max, model.n_feats
     mark_sets = scan_mark_sets(mark_sets, F)
     K = len(mark_sets)
     rc = int(np.argmin(model.n_bins))
@@ -501,17 +399,8 @@ def write_perturbation_scan(model, store, bsz, path, gene_ids, strands, regressi
     scanned = scan_regions_expand("all" if regions == "all" else "promoter", S, "write_perturbation_scan")
     logits = torch.empty(len(scanned), n, V, model.n_out)
     live = torch.zeros(len(scanned), n, W, dtype=torch.bool)      # window g of the region holds a real bin
-    struct = store.struct()
-    order = torch.arange(n, dtype=torch.int32, device=dev)
-    flip = torch.tensor([s != "+" for s in strands], dtype=torch.uint8, device=dev)
-    slots = {}
-    st = torch.cuda.current_stream(dev).cuda_stream
-    for lo in range(0, n, bsz):
-        B = min(bsz, n - lo)
-        slot = slots.get(B) or slots.setdefault(B, Slot(model, B))
-        cursor = torch.tensor([0, 1, 0, 0], dtype=torch.int32).to(dev)
-        _lib.check(L.cf_gather_batch(model._handle, C.byref(struct), order[lo:].data_ptr(), cursor.data_ptr(), C.byref(slot.struct), None, st),
-                   "cf_gather_batch")
+    flip = torch.tensor([s != "+" for s in strands], dtype=torch.uint8, device=model._device)
+    for lo, B, slot in _slot_batches("write_perturbation_scan", model, store, bsz):
         out, _ = model.perturbation_scan_regions(slot, regions=scanned, scale=scale, width=width, mark_sets=mark_sets, flip=flip[lo:lo + B])
         logits[:, lo:lo + B] = out.cpu()
         for k, region in enumerate(scanned):
@@ -520,8 +409,6 @@ def write_perturbation_scan(model, store, bsz, path, gene_ids, strands, regressi
             first = torch.where(m, pos, W).amin(1)
             last = torch.where(m, pos, -1).amax(1)
             live[k, lo:lo + B] = pos[None, :] < (last - first + 1).clamp(min=0)[:, None]
-        if int(cursor[2].item()):
-            raise RuntimeError("write_perturbation_scan: the device-side gather reported errors at gene %d (store / order mismatch)" % lo)
 
     def column(lg):          # [n, n_out], laid out as the logits predict() turns into its column
         lg = lg.contiguous()
@@ -539,8 +426,7 @@ def write_perturbation_scan(model, store, bsz, path, gene_ids, strands, regressi
     arrays = dict(gene_ids=np.array(list(gene_ids)), mark_sets=sets, prediction=vals[0, :, scan_row(0, None, None, K, W)].copy(), promoter=scan[0])
     if regions == "all":
         arrays["pcres"] = np.ascontiguousarray(scan[1:].transpose(1, 0, 2, 3))
-    with open(path, "wb") as f:
-        np.savez(f, **arrays)
+    _savez(path, **arrays)
 
 
 def write_perturbation_scan_fine(model, dataset, store, bsz, path, gene_ids, regression=False, region="promoter", width=1, stride=None, zoom=None,
@@ -583,8 +469,7 @@ def write_perturbation_scan_fine(model, dataset, store, bsz, path, gene_ids, reg
             arrays["zoom"][i, :len(d["zoom"])] = d["zoom"]
             arrays["coarse_windows"][i, :m] = np.array([w[1:] for w in d["coarse_windows"]], dtype=np.int64).reshape(m, 2)
             arrays["coarse"][i, :, :m] = col(d["coarse_scan"])
-    with open(path, "wb") as f:
-        np.savez(f, **arrays)
+    _savez(path, **arrays)
 
 
 def require_raw_signals(dataset, genes=None):
@@ -638,6 +523,11 @@ def write_raw_integrated_gradients(model, dataset, bsz, ig_dir, n_steps=50, meth
         np.savez(os.path.join(ig_dir, "%s.npz" % d["gene_id"]), **arrays)
 
 
+# the outputs that read the donor cell type, predict()'s arguments and main()'s options alike, in the order the refusals list them
+_DONOR_OUTS = ("mark_donor_shapley_out", "mark_donor_epistasis_out", "mark_donor_sampled_shapley_out", "window_donor_shapley_out",
+               "fine_window_donor_shapley_out", "mark_donor_interactions_out", "mark_donor_sampled_interactions_out", "mark_donor_dividends_out")
+
+
 def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123, i_max=8, w_prom=40000, w_max=40000,
             binsizes=(2000, 500, 100), progress=False, store_path=None, attention_dir=None, embeddings_out=None,
             pcre_ablation_out=None, ig_dir=None, ig_steps=50, ig_method="gausslegendre", ig_target=None, raw_saliency_dir=None,
@@ -661,10 +551,10 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     raw_ig_dir: integrated gradients with respect to the raw signals, one .npz per gene (write_raw_integrated_gradients; ig_steps,
     ig_method and ig_target apply; needs the raw .npy files too); scan_out: the in-silico perturbation scan of every gene, one .npz
     (write_perturbation_scan; scan_scale, scan_width and scan_regions apply; served by a packed store as well); pcre_shapley_out /
-    pcre_epistasis_out: exact Shapley values / pair-deletion epistasis of the pCREs, in logit space (write_pcre_coalition_values);
+    pcre_epistasis_out: exact Shapley values / pair-deletion epistasis of the pCREs, in logit space (write_exact_values, game "pcre");
     mark_shapley_out / mark_epistasis_out: exact Shapley values / pair epistasis of the histone marks, in logit space
-    (write_mark_values; mark_players and mark_scale apply); mark_donor_shapley_out / mark_donor_epistasis_out: the same against a donor
-    cell type (write_mark_donor_values; mark_players applies), whose signals are read from donor_npy_dir with the metadata donor_meta
+    (game "mark"; mark_players and mark_scale apply); mark_donor_shapley_out / mark_donor_epistasis_out: the same against a donor
+    cell type (game "mark_donor"; mark_players applies), whose signals are read from donor_npy_dir with the metadata donor_meta
     (default: meta_path) or the packed store donor_store_path -- both cell types must hold the genes' regions at the same coordinates
     (attribution.same_regions); mark_sampled_shapley_out / mark_donor_sampled_shapley_out: permutation-sampled Shapley values of up
     to 128 mark players, by default one per (mark, region) pair, under the scale rule (mark_scale applies) / against the donor
@@ -709,11 +599,17 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         raw_ds = ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=regression)
         require_raw_signals(raw_ds)      # (before anything is computed)
     from . import pack
-    donor_out = (mark_donor_shapley_out or mark_donor_epistasis_out or mark_donor_sampled_shapley_out or window_donor_shapley_out
-                 or fine_window_donor_shapley_out or mark_donor_interactions_out or mark_donor_sampled_interactions_out
-                 or mark_donor_dividends_out)
+    given = locals()      # (the arguments by name)
+    donor_out = any(given[name] for name in _DONOR_OUTS)
+    plain = []
+
+    def plain_ds():      # the run's dataset with regression=False: strand, coordinates and geometry for the generators; built at its first use
+        if not plain:
+            plain.append(ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False))
+        return plain[0]
+
     if pairs_kw:      # (the geometry the generator checks the model against)
-        pairs_ds = ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False)
+        pairs_ds = plain_ds()
     raw_donor_ds = None
     if raw_donor_ig_dir:      # (before anything is computed)
         from .attribution import same_regions
@@ -726,20 +622,18 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     if window_shapley_out or window_donor_shapley_out:      # (strand and coordinates; refusals before anything is computed)
         from .attribution import window_players as window_game
         window_game(window_players, 7, i_max, w_max // max(binsizes), window_width)
-        window_ds = ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False)
+        window_ds = plain_ds()
     fine_window_ds = None
     if fine_window_shapley_out or fine_window_donor_shapley_out:      # (strand, coordinates, lengths; refusals before anything is computed)
         from .attribution import fine_window_players as fine_window_game
         fine_window_game(fine_window_players, 7, fine_window_width, -(-(max(binsizes) // min(binsizes)) // max(int(fine_window_width), 1)))
-        fine_window_ds = ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False)
+        fine_window_ds = plain_ds()
     if donor_out:      # (before anything is computed)
         from .attribution import same_regions
         if not donor_npy_dir:
-            raise ValueError("predict: mark_donor_shapley_out / mark_donor_epistasis_out / mark_donor_sampled_shapley_out / "
-                             "window_donor_shapley_out / fine_window_donor_shapley_out / mark_donor_interactions_out / "
-                             "mark_donor_sampled_interactions_out / mark_donor_dividends_out need donor_npy_dir")
+            raise ValueError("predict: %s need donor_npy_dir" % " / ".join(_DONOR_OUTS))
         donor_ds = ChromoformerDataset(donor_meta or meta_path, donor_npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False)
-        same_regions(ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False), donor_ds)
+        same_regions(plain_ds(), donor_ds)
     packed = pack.find(npy_dir, store_path, list(binsizes), i_max, w_prom, w_max, 7, genes, meta=meta)
     dev = torch.device("cuda", torch.cuda.current_device())
     if packed is not None:
@@ -762,10 +656,11 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     if pcre_ablation_out:
         write_pcre_ablation(model, store, bsz, pcre_ablation_out, regression)
     if pcre_shapley_out or pcre_epistasis_out or pcre_interactions_out:
-        write_pcre_coalition_values(model, store, bsz, pcre_shapley_out, pcre_epistasis_out, regression, pcre_interactions_out, interaction_index)
+        write_exact_values(model, "pcre", store, None, bsz, genes, pcre_shapley_out, pcre_epistasis_out, pcre_interactions_out, regression,
+                           index=interaction_index)
     if mark_shapley_out or mark_epistasis_out or mark_interactions_out:
-        write_mark_values(model, store, bsz, genes, mark_shapley_out, mark_epistasis_out, regression, mark_players, mark_scale,
-                          mark_interactions_out, interaction_index)
+        write_exact_values(model, "mark", store, None, bsz, genes, mark_shapley_out, mark_epistasis_out, mark_interactions_out, regression,
+                           mark_players, mark_scale, interaction_index)
     if pcre_dividends_out:
         write_dividends(model, store, None, bsz, genes, pcre_dividends_out, "pcre", regression)
     if mark_dividends_out:
@@ -775,8 +670,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         donor_store = (donor_packed.store(genes, device=dev, regression=False) if donor_packed is not None
                        else GeneStore(donor_ds, progress=progress, device=dev, resident=True))
         if mark_donor_shapley_out or mark_donor_epistasis_out or mark_donor_interactions_out:
-            write_mark_donor_values(model, store, donor_store, bsz, genes, mark_donor_shapley_out, mark_donor_epistasis_out, regression, mark_players,
-                                    mark_donor_interactions_out, interaction_index)
+            write_exact_values(model, "mark_donor", store, donor_store, bsz, genes, mark_donor_shapley_out, mark_donor_epistasis_out,
+                               mark_donor_interactions_out, regression, mark_players, index=interaction_index)
         if mark_donor_dividends_out:
             write_dividends(model, store, donor_store, bsz, genes, mark_donor_dividends_out, "mark_donor", regression, mark_players)
         if mark_donor_sampled_shapley_out:
@@ -808,8 +703,7 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     if ig_dir:
         write_integrated_gradients(model, store, bsz, ig_dir, ig_steps, ig_method, ig_target)
     if fine_scan_out:      # (strand, coordinates and region lengths come from the metadata)
-        fine_ds = ChromoformerDataset(meta_path, npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False)
-        write_perturbation_scan_fine(model, fine_ds, store, bsz, fine_scan_out, genes, regression, fine_scan_region, fine_scan_width, fine_scan_stride,
+        write_perturbation_scan_fine(model, plain_ds(), store, bsz, fine_scan_out, genes, regression, fine_scan_region, fine_scan_width, fine_scan_stride,
                                      fine_scan_zoom, fine_scan_scale)
     if scan_out:
         write_perturbation_scan(model, store, bsz, scan_out, genes, meta.strand.tolist(), regression, scan_scale, scan_width, scan_regions)
@@ -989,172 +883,119 @@ def build_parser():
     return ap
 
 
+_DEFAULTS = dict(      # what predict() gets for an option that was not given; main() tells "not given" by None until its checks are through
+    ig_steps=50, ig_method="gausslegendre", ig_target=None, raw_saliency_target=None, scan_scale=0.0, scan_width=1, scan_regions="promoter",
+    fine_scan_region="promoter", fine_scan_width=1, fine_scan_stride=None, fine_scan_zoom=None, fine_scan_scale=0.0, mark_players="marks",
+    mark_scale=0.0, mark_sampled_players="cells", mark_perms=64, mark_seed=0, mark_focal=4, interaction_index="sii", window_players="promoter",
+    window_width=1, window_perms=64, window_seed=0, window_scale=0.0, fine_window_region="promoter", fine_window_width=2,
+    fine_window_players="windows", fine_window_zoom=1, fine_window_perms=64, fine_window_seed=0, fine_window_scale=0.0)
+_MARK_OUTS = ("mark_shapley_out", "mark_epistasis_out", "mark_interactions_out", "mark_dividends_out")
+_DONOR_EXACT_OUTS = ("mark_donor_shapley_out", "mark_donor_epistasis_out", "mark_donor_interactions_out", "mark_donor_dividends_out")
+_SAMPLED_OUTS = ("mark_sampled_shapley_out", "mark_donor_sampled_shapley_out")
+_PAIRS_OUTS = ("mark_sampled_interactions_out", "mark_donor_sampled_interactions_out")
+_WINDOW_OUTS = ("window_shapley_out", "window_donor_shapley_out")
+_FINE_WINDOW_OUTS = ("fine_window_shapley_out", "fine_window_donor_shapley_out")
+_MARK_NEED = ("--mark-players / --mark-scale need --mark-shapley-out, --mark-epistasis-out, --mark-interactions-out or --mark-dividends-out"
+              " (--mark-players also applies to --mark-donor-shapley-out / --mark-donor-epistasis-out, --mark-scale to"
+              " --mark-sampled-shapley-out)")
+_NEEDS = [      # (flags, the flags they apply to, the refusal where one of the former is given and none of the latter), in the order checked
+    (("raw_saliency_target", "raw_saliency_times_input"), ("raw_saliency_dir",),
+     "--raw-saliency-target / --raw-saliency-times-input need --raw-saliency-dir"),
+    (("ig_steps", "ig_method", "ig_target"), ("ig_dir", "raw_ig_dir", "raw_donor_ig_dir"),
+     "--ig-steps / --ig-method / --ig-target need --ig-dir or --raw-ig-dir (or --raw-donor-ig-dir)"),
+    (("scan_scale", "scan_width", "scan_regions"), ("scan_out",), "--scan-scale / --scan-width / --scan-regions need --scan-out"),
+    (("fine_scan_region", "fine_scan_width", "fine_scan_stride", "fine_scan_zoom", "fine_scan_scale"), ("fine_scan_out",),
+     "--fine-scan-region / --fine-scan-width / --fine-scan-stride / --fine-scan-zoom / --fine-scan-scale need --fine-scan-out"),
+    (("interaction_index",), ("pcre_interactions_out", "mark_interactions_out", "mark_donor_interactions_out") + _PAIRS_OUTS,
+     "--interaction-index needs --pcre-interactions-out, --mark-interactions-out or --mark-donor-interactions-out"
+     " (or --mark-sampled-interactions-out, --mark-donor-sampled-interactions-out)"),
+    (("mark_focal",), _PAIRS_OUTS, "--mark-focal needs --mark-sampled-interactions-out or --mark-donor-sampled-interactions-out"),
+    (("raw_donor_ig_dir",), ("donor_npy_dir",), "--raw-donor-ig-dir needs --donor-npy-dir"),
+    (_DONOR_OUTS, ("donor_npy_dir",), "%s need --donor-npy-dir" % " / ".join("--" + name.replace("_", "-") for name in _DONOR_OUTS)),
+    (("donor_npy_dir", "donor_meta", "donor_store"), _DONOR_OUTS + ("raw_donor_ig_dir",),
+     "--donor-npy-dir / --donor-meta / --donor-store need --mark-donor-shapley-out, --mark-donor-epistasis-out or "
+     "--mark-donor-sampled-shapley-out (or --window-donor-shapley-out, --fine-window-donor-shapley-out, "
+     "--mark-donor-interactions-out, --mark-donor-sampled-interactions-out, --mark-donor-dividends-out)"),
+    (("mark_sampled_players", "mark_perms", "mark_seed"), _SAMPLED_OUTS + _PAIRS_OUTS,
+     "--mark-sampled-players / --mark-perms / --mark-seed need --mark-sampled-shapley-out or --mark-donor-sampled-shapley-out"
+     " (or --mark-sampled-interactions-out, --mark-donor-sampled-interactions-out)"),
+    (("mark_scale",), _MARK_OUTS + ("mark_sampled_shapley_out", "mark_sampled_interactions_out"), _MARK_NEED),
+    (("mark_players",), _MARK_OUTS + _DONOR_EXACT_OUTS, _MARK_NEED),
+    (("window_players", "window_width", "window_perms", "window_seed"), _WINDOW_OUTS,
+     "--window-players / --window-width / --window-perms / --window-seed need --window-shapley-out or --window-donor-shapley-out"),
+    (("window_scale",), ("window_shapley_out",), "--window-scale needs --window-shapley-out (the donor rule has no scale)"),
+    (("fine_window_region", "fine_window_width", "fine_window_players", "fine_window_zoom", "fine_window_perms", "fine_window_seed"), _FINE_WINDOW_OUTS,
+     "--fine-window-region / --fine-window-width / --fine-window-players / --fine-window-zoom / --fine-window-perms / "
+     "--fine-window-seed need --fine-window-shapley-out or --fine-window-donor-shapley-out"),
+    (("fine_window_scale",), ("fine_window_shapley_out",), "--fine-window-scale needs --fine-window-shapley-out (the donor rule has no scale)"),
+]
+
+
 def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
-    if not args.raw_saliency_dir and (args.raw_saliency_target is not None or args.raw_saliency_times_input):
-        ap.error("--raw-saliency-target / --raw-saliency-times-input need --raw-saliency-dir")
-    if args.raw_saliency_target is not None and not 0 <= args.raw_saliency_target < (1 if args.regression else 2):
-        ap.error("--raw-saliency-target must be in [0, %d)" % (1 if args.regression else 2))
-    if not args.ig_dir and not args.raw_ig_dir and not args.raw_donor_ig_dir and (args.ig_steps is not None or args.ig_method is not None
-                                                                                  or args.ig_target is not None):
-        ap.error("--ig-steps / --ig-method / --ig-target need --ig-dir or --raw-ig-dir (or --raw-donor-ig-dir)")
-    if args.ig_steps is not None and args.ig_steps < (2 if args.ig_method == "riemann_trapezoid" else 1):
+
+    def given(name):      # (an option of _DEFAULTS: it was given; an output, a directory or a switch: it is set)
+        return getattr(args, name) is not None if name in _DEFAULTS else bool(getattr(args, name))
+
+    for flags, owners, message in _NEEDS:
+        if any(given(name) for name in flags) and not any(given(name) for name in owners):
+            ap.error(message)
+    for name, default in _DEFAULTS.items():
+        if getattr(args, name) is None:
+            setattr(args, name, default)
+    n_out = 1 if args.regression else 2
+    if args.raw_saliency_target is not None and not 0 <= args.raw_saliency_target < n_out:
+        ap.error("--raw-saliency-target must be in [0, %d)" % n_out)
+    if args.ig_steps < (2 if args.ig_method == "riemann_trapezoid" else 1):
         ap.error("--ig-steps must be at least %d" % (2 if args.ig_method == "riemann_trapezoid" else 1))
-    if args.ig_target is not None and not 0 <= args.ig_target < (1 if args.regression else 2):
-        ap.error("--ig-target must be in [0, %d)" % (1 if args.regression else 2))
-    if not args.scan_out and (args.scan_scale is not None or args.scan_width is not None or args.scan_regions is not None):
-        ap.error("--scan-scale / --scan-width / --scan-regions need --scan-out")
-    if args.scan_scale is not None and not (args.scan_scale >= 0 and np.isfinite(args.scan_scale)):
-        ap.error("--scan-scale must be a finite factor >= 0")
-    if args.scan_width is not None and args.scan_width < 1:
-        ap.error("--scan-width must be at least 1")
-    fine_opts = (args.fine_scan_region, args.fine_scan_width, args.fine_scan_stride, args.fine_scan_zoom, args.fine_scan_scale)
-    if not args.fine_scan_out and any(v is not None for v in fine_opts):
-        ap.error("--fine-scan-region / --fine-scan-width / --fine-scan-stride / --fine-scan-zoom / --fine-scan-scale need --fine-scan-out")
-    fine_region = "promoter"
-    if args.fine_scan_region not in (None, "promoter"):
-        if not args.fine_scan_region.isdigit() or int(args.fine_scan_region) >= 8:
-            ap.error("--fine-scan-region must be promoter or a pCRE slot in [0, 8)")
-        fine_region = int(args.fine_scan_region)
-    if args.fine_scan_scale is not None and not (args.fine_scan_scale >= 0 and np.isfinite(args.fine_scan_scale)):
-        ap.error("--fine-scan-scale must be a finite factor >= 0")
-    for name, v in (("width", args.fine_scan_width), ("stride", args.fine_scan_stride), ("zoom", args.fine_scan_zoom)):
-        if v is not None and v < 1:
-            ap.error("--fine-scan-%s must be at least 1" % name)
-    donor_exact = args.mark_donor_shapley_out or args.mark_donor_epistasis_out or args.mark_donor_interactions_out or args.mark_donor_dividends_out
-    pairs_out = args.mark_sampled_interactions_out or args.mark_donor_sampled_interactions_out
-    if args.interaction_index is not None and not (args.pcre_interactions_out or args.mark_interactions_out or args.mark_donor_interactions_out
-                                                   or pairs_out):
-        ap.error("--interaction-index needs --pcre-interactions-out, --mark-interactions-out or --mark-donor-interactions-out"
-                 " (or --mark-sampled-interactions-out, --mark-donor-sampled-interactions-out)")
-    mark_focal = 4
-    if args.mark_focal is not None:
-        if not pairs_out:
-            ap.error("--mark-focal needs --mark-sampled-interactions-out or --mark-donor-sampled-interactions-out")
+    if args.ig_target is not None and not 0 <= args.ig_target < n_out:
+        ap.error("--ig-target must be in [0, %d)" % n_out)
+    for name in ("scan_scale", "fine_scan_scale", "mark_scale", "window_scale", "fine_window_scale"):
+        if not (getattr(args, name) >= 0 and np.isfinite(getattr(args, name))):
+            ap.error("--%s must be a finite factor >= 0" % name.replace("_", "-"))
+    for name in ("scan_width", "fine_scan_width", "fine_scan_stride", "fine_scan_zoom", "mark_perms", "window_width", "window_perms",
+                 "fine_window_width", "fine_window_zoom", "fine_window_perms"):
+        if getattr(args, name) is not None and getattr(args, name) < 1:
+            ap.error("--%s must be at least 1" % name.replace("_", "-"))
+    for name in ("fine_scan_region", "fine_window_region"):
+        region = getattr(args, name)
+        if region != "promoter":
+            if not region.isdigit() or int(region) >= 8:
+                ap.error("--%s must be promoter or a pCRE slot in [0, 8)" % name.replace("_", "-"))
+            setattr(args, name, int(region))
+    if isinstance(args.mark_focal, str):
         if args.mark_focal.strip().lstrip("+-").isdigit():
-            mark_focal = int(args.mark_focal)
-            if mark_focal < 1:
+            args.mark_focal = int(args.mark_focal)
+            if args.mark_focal < 1:
                 ap.error("--mark-focal must be at least 1 player (or a list of player names)")
         else:
-            mark_focal = [s.strip() for s in args.mark_focal.split(",")]
-    if pairs_out:      # (the players' names: a bad count or name is a usage error)
+            args.mark_focal = [s.strip() for s in args.mark_focal.split(",")]
+    if any(given(name) for name in _PAIRS_OUTS):      # (the players' names: a bad count or name is a usage error)
         from .attribution import focal_players, mark_players_wide
-        pair_names = mark_players_wide(args.mark_sampled_players or "cells", 7, 8)[2]      # (predict()'s n_feats and default i_max)
+        pair_names = mark_players_wide(args.mark_sampled_players, 7, 8)[2]      # (predict()'s n_feats and default i_max)
         try:
-            if isinstance(mark_focal, int):
-                if mark_focal > len(pair_names):
-                    raise ValueError("K = %d exceeds the %d players" % (mark_focal, len(pair_names)))
+            if isinstance(args.mark_focal, int):
+                if args.mark_focal > len(pair_names):
+                    raise ValueError("K = %d exceeds the %d players" % (args.mark_focal, len(pair_names)))
             else:
-                focal_players(mark_focal, pair_names, len(pair_names))
+                focal_players(args.mark_focal, pair_names, len(pair_names))
         except ValueError as e:
             ap.error("--mark-focal: %s" % e)
-    donor_out = (donor_exact or args.mark_donor_sampled_shapley_out or args.window_donor_shapley_out or args.fine_window_donor_shapley_out
-                 or args.mark_donor_sampled_interactions_out)
-    if args.raw_donor_ig_dir and not args.donor_npy_dir:
-        ap.error("--raw-donor-ig-dir needs --donor-npy-dir")
     if args.raw_donor_ig_dir and args.donor_store:
         ap.error("--raw-donor-ig-dir reads the donor's raw .npy signals; --donor-store does not serve it")
-    sampled_out = args.mark_sampled_shapley_out or args.mark_donor_sampled_shapley_out
-    if donor_out and not args.donor_npy_dir:
-        ap.error("--mark-donor-shapley-out / --mark-donor-epistasis-out / --mark-donor-sampled-shapley-out / --window-donor-shapley-out / "
-                 "--fine-window-donor-shapley-out / --mark-donor-interactions-out / --mark-donor-sampled-interactions-out / "
-                 "--mark-donor-dividends-out need --donor-npy-dir")
-    if not donor_out and not args.raw_donor_ig_dir and (args.donor_npy_dir or args.donor_meta or args.donor_store):
-        ap.error("--donor-npy-dir / --donor-meta / --donor-store need --mark-donor-shapley-out, --mark-donor-epistasis-out or "
-                 "--mark-donor-sampled-shapley-out (or --window-donor-shapley-out, --fine-window-donor-shapley-out, "
-                 "--mark-donor-interactions-out, --mark-donor-sampled-interactions-out, --mark-donor-dividends-out)")
-    if not sampled_out and not pairs_out and (args.mark_sampled_players is not None or args.mark_perms is not None or args.mark_seed is not None):
-        ap.error("--mark-sampled-players / --mark-perms / --mark-seed need --mark-sampled-shapley-out or --mark-donor-sampled-shapley-out"
-                 " (or --mark-sampled-interactions-out, --mark-donor-sampled-interactions-out)")
-    if args.mark_perms is not None and args.mark_perms < 1:
-        ap.error("--mark-perms must be at least 1")
-    if not args.mark_shapley_out and not args.mark_epistasis_out and not args.mark_interactions_out and not args.mark_dividends_out and ((args.mark_scale is not None and not args.mark_sampled_shapley_out
-                                                                                                          and not args.mark_sampled_interactions_out)
-                                                                                                         or (args.mark_players is not None and not donor_exact)):
-        ap.error("--mark-players / --mark-scale need --mark-shapley-out, --mark-epistasis-out, --mark-interactions-out or --mark-dividends-out"
-                 " (--mark-players also applies to --mark-donor-shapley-out / --mark-donor-epistasis-out, --mark-scale to"
-                 " --mark-sampled-shapley-out)")
-    if args.mark_scale is not None and not (args.mark_scale >= 0 and np.isfinite(args.mark_scale)):
-        ap.error("--mark-scale must be a finite factor >= 0")
-    window_out = args.window_shapley_out or args.window_donor_shapley_out
-    if not window_out and (args.window_players is not None or args.window_width is not None or args.window_perms is not None
-                           or args.window_seed is not None):
-        ap.error("--window-players / --window-width / --window-perms / --window-seed need --window-shapley-out or --window-donor-shapley-out")
-    if args.window_scale is not None and not args.window_shapley_out:
-        ap.error("--window-scale needs --window-shapley-out (the donor rule has no scale)")
-    if args.window_scale is not None and not (args.window_scale >= 0 and np.isfinite(args.window_scale)):
-        ap.error("--window-scale must be a finite factor >= 0")
-    if args.window_width is not None and args.window_width < 1:
-        ap.error("--window-width must be at least 1")
-    if args.window_perms is not None and args.window_perms < 1:
-        ap.error("--window-perms must be at least 1")
-    if window_out:
-        from .attribution import window_players
-        try:
-            window_players(args.window_players or "promoter", 7, 8, 20, 1 if args.window_width is None else args.window_width)
-        except ValueError as e:
-            ap.error(str(e))
-    fine_window_out = args.fine_window_shapley_out or args.fine_window_donor_shapley_out
-    if not fine_window_out and any(v is not None for v in (args.fine_window_region, args.fine_window_width, args.fine_window_players,
-                                                           args.fine_window_zoom, args.fine_window_perms, args.fine_window_seed)):
-        ap.error("--fine-window-region / --fine-window-width / --fine-window-players / --fine-window-zoom / --fine-window-perms / "
-                 "--fine-window-seed need --fine-window-shapley-out or --fine-window-donor-shapley-out")
-    if args.fine_window_scale is not None and not args.fine_window_shapley_out:
-        ap.error("--fine-window-scale needs --fine-window-shapley-out (the donor rule has no scale)")
-    if args.fine_window_scale is not None and not (args.fine_window_scale >= 0 and np.isfinite(args.fine_window_scale)):
-        ap.error("--fine-window-scale must be a finite factor >= 0")
-    fine_window_region = "promoter"
-    if args.fine_window_region not in (None, "promoter"):
-        if not args.fine_window_region.isdigit() or int(args.fine_window_region) >= 8:
-            ap.error("--fine-window-region must be promoter or a pCRE slot in [0, 8)")
-        fine_window_region = int(args.fine_window_region)
-    for name, v in (("width", args.fine_window_width), ("zoom", args.fine_window_zoom), ("perms", args.fine_window_perms)):
-        if v is not None and v < 1:
-            ap.error("--fine-window-%s must be at least 1" % name)
-    if fine_window_out:
-        from .attribution import fine_window_players
-        try:
-            width = 2 if args.fine_window_width is None else args.fine_window_width
-            fine_window_players(args.fine_window_players or "windows", 7, width, -(-20 // width))
-        except ValueError as e:
-            ap.error(str(e))
+    try:      # (the window games' players at predict()'s default geometry: too many is a usage error)
+        if any(given(name) for name in _WINDOW_OUTS):
+            from .attribution import window_players
+            window_players(args.window_players, 7, 8, 20, args.window_width)
+        if any(given(name) for name in _FINE_WINDOW_OUTS):
+            from .attribution import fine_window_players
+            fine_window_players(args.fine_window_players, 7, args.fine_window_width, -(-20 // args.fine_window_width))
+    except ValueError as e:
+        ap.error(str(e))
+    kw = {name: value for name, value in vars(args).items() if name not in ("meta", "npy_dir", "weights", "regression", "output", "store", "donor_store")}
     meta, pred = predict(args.meta, args.npy_dir, args.weights, args.regression, progress=True, store_path=args.store,
-                         attention_dir=args.attention_dir, embeddings_out=args.embeddings_out, pcre_ablation_out=args.pcre_ablation_out,
-                         ig_dir=args.ig_dir, ig_steps=50 if args.ig_steps is None else args.ig_steps,
-                         ig_method=args.ig_method or "gausslegendre", ig_target=args.ig_target, raw_saliency_dir=args.raw_saliency_dir,
-                         raw_saliency_target=args.raw_saliency_target, raw_saliency_times_input=args.raw_saliency_times_input,
-                         raw_ig_dir=args.raw_ig_dir, scan_out=args.scan_out, scan_scale=0.0 if args.scan_scale is None else args.scan_scale,
-                         scan_width=1 if args.scan_width is None else args.scan_width, scan_regions=args.scan_regions or "promoter",
-                         pcre_shapley_out=args.pcre_shapley_out, pcre_epistasis_out=args.pcre_epistasis_out,
-                         mark_shapley_out=args.mark_shapley_out, mark_epistasis_out=args.mark_epistasis_out,
-                         mark_players=args.mark_players or "marks", mark_scale=0.0 if args.mark_scale is None else args.mark_scale,
-                         donor_npy_dir=args.donor_npy_dir, donor_meta=args.donor_meta, donor_store_path=args.donor_store,
-                         mark_donor_shapley_out=args.mark_donor_shapley_out, mark_donor_epistasis_out=args.mark_donor_epistasis_out,
-                         mark_sampled_shapley_out=args.mark_sampled_shapley_out, mark_donor_sampled_shapley_out=args.mark_donor_sampled_shapley_out,
-                         mark_sampled_players=args.mark_sampled_players or "cells", mark_perms=64 if args.mark_perms is None else args.mark_perms,
-                         mark_seed=0 if args.mark_seed is None else args.mark_seed, window_shapley_out=args.window_shapley_out,
-                         window_donor_shapley_out=args.window_donor_shapley_out, window_players=args.window_players or "promoter",
-                         window_width=1 if args.window_width is None else args.window_width,
-                         window_perms=64 if args.window_perms is None else args.window_perms,
-                         window_seed=0 if args.window_seed is None else args.window_seed,
-                         window_scale=0.0 if args.window_scale is None else args.window_scale, raw_donor_ig_dir=args.raw_donor_ig_dir,
-                         fine_scan_out=args.fine_scan_out, fine_scan_region=fine_region,
-                         fine_scan_width=1 if args.fine_scan_width is None else args.fine_scan_width, fine_scan_stride=args.fine_scan_stride,
-                         fine_scan_zoom=args.fine_scan_zoom, fine_scan_scale=0.0 if args.fine_scan_scale is None else args.fine_scan_scale,
-                         fine_window_shapley_out=args.fine_window_shapley_out, fine_window_donor_shapley_out=args.fine_window_donor_shapley_out,
-                         fine_window_region=fine_window_region, fine_window_width=2 if args.fine_window_width is None else args.fine_window_width,
-                         fine_window_players=args.fine_window_players or "windows",
-                         fine_window_zoom=1 if args.fine_window_zoom is None else args.fine_window_zoom,
-                         fine_window_perms=64 if args.fine_window_perms is None else args.fine_window_perms,
-                         fine_window_seed=0 if args.fine_window_seed is None else args.fine_window_seed,
-                         fine_window_scale=0.0 if args.fine_window_scale is None else args.fine_window_scale,
-                         pcre_interactions_out=args.pcre_interactions_out, mark_interactions_out=args.mark_interactions_out,
-                         mark_donor_interactions_out=args.mark_donor_interactions_out, interaction_index=args.interaction_index or "sii",
-                         mark_sampled_interactions_out=args.mark_sampled_interactions_out,
-                         mark_donor_sampled_interactions_out=args.mark_donor_sampled_interactions_out, mark_focal=mark_focal,
-                         pcre_dividends_out=args.pcre_dividends_out, mark_dividends_out=args.mark_dividends_out,
-                         mark_donor_dividends_out=args.mark_donor_dividends_out)
+                         donor_store_path=args.donor_store, **kw)
     print("Predicting expressions for %d genes." % len(meta))
     meta["prediction"] = pred
     meta.to_csv(args.output, index=False)
