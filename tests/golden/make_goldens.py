@@ -430,8 +430,31 @@ def g6_training_run():
     print("wrote train_run.npz")
 
 
+def model_api():
+    """model_api.json: the public surface of the four model classes of chromoformer_amd.net -- per class the sorted public attribute
+    names (what torch.nn.Module itself supplies left out, so that the fixture does not depend on the torch version) and
+    str(inspect.signature) of every public callable; and "refusals": exception type and message of every call in the table of
+    tests/test_model_api_cpu.py on a model that was never moved to a device.  Not part of the default run: written on the commit whose
+    surface is to be kept (`make_goldens.py api`), read by that test, which holds the walk and the calls."""
+    import inspect
+
+    from chromoformer_amd import net
+    from tests import test_model_api_cpu as api
+    out = {"refusals": {k: api.refusal(case) for k, case in api.REFUSALS.items()}}
+    for cls in api.CLASSES:
+        c = getattr(net, cls)
+        names = api.public_names(c)
+        out[cls] = {"attributes": names, "signatures": {n: str(inspect.signature(getattr(c, n))) for n in names if callable(getattr(c, n))}}
+    with open(os.path.join(HERE, "model_api.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("wrote model_api.json:", {k: len(v) if k == "refusals" else len(v["signatures"]) for k, v in out.items()})
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["g3", "g2", "g1", "g5", "g6"]
+    if "api" in which:
+        model_api()
     if "g6" in which:
         g6_training_run()
     if "g3" in which:
