@@ -129,6 +129,18 @@ class cf_mark_fine_opts(C.Structure):
                 ("donor_promoter_feats", C.c_void_p * MAX_RES), ("donor_pcre_feats", C.c_void_p * MAX_RES), ("feats_out", C.c_void_p * MAX_RES)]
 
 
+class cf_backselect_opts(C.Structure):
+    _fields_ = [("mode", C.c_int), ("target", C.c_int), ("direction", C.c_int), ("frac", C.c_float), ("threshold", C.c_void_p)]
+
+
+class cf_backselect_out(C.Structure):
+    _fields_ = [("order", C.c_void_p), ("values", C.c_void_p), ("size", C.c_void_p), ("subset", C.c_void_p), ("rows", C.c_void_p),
+                ("threshold", C.c_void_p), ("direction", C.c_void_p)]
+
+
+BACKSELECT_MODE = {"backward": 0, "forward": 1}      # CF_BACKSELECT_BACKWARD / CF_BACKSELECT_FORWARD
+
+
 class cf_store(C.Structure):
     _fields_ = [
         ("n_genes", C.c_longlong),
@@ -229,6 +241,14 @@ SYMBOLS = {
                                                             C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6),
     "cf_perm_interactions_from_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
                                        + [C.c_void_p] * 5),
+    "cf_mark_backselect": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_wide_opts), C.POINTER(cf_backselect_opts),
+                                     C.POINTER(cf_backselect_out), C.c_void_p]),
+    "cf_mark_window_backselect": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_window_opts), C.POINTER(cf_backselect_opts),
+                                            C.POINTER(cf_backselect_out), C.c_void_p]),
+    "cf_mark_fine_backselect": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_fine_opts), C.POINTER(cf_backselect_opts),
+                                          C.POINTER(cf_backselect_out), C.c_void_p]),
+    "cf_backselect_from_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(cf_backselect_opts),
+                                          C.POINTER(cf_backselect_out), C.c_void_p]),
     "cf_adamw_step":(C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_longlong, C.c_void_p]),
     "cf_debug_copy": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p]),
     "cf_debug_names": (C.c_char_p, [C.c_void_p]),

@@ -1296,6 +1296,53 @@ def mark_shapley_sampled(model, dataset, donor_dataset=None, genes=None, players
                        permutations=perms.copy())
 
 
+def backselect_row_count(P):
+    """The forwards per gene of a back-selection over P players: the two end rows, then P - t candidates in round t = 0 .. P - 2."""
+    P = int(P)
+    if P < 1:
+        raise ValueError("backselect_row_count: P = %d: at least 1 player" % P)
+    return P * (P + 1) // 2 + 1
+
+
+def backselect_words(order, mode="backward"):
+    """The coalitions a selection order visits -> uint32 [P + 1, kw], kw = ceil(P / 32), bit p % 32 of word p / 32 = player p present
+    (mark_wide_words' layout): row t is the set after t moves -- backward: everybody less order[:t]; forward: order[:t]."""
+    order = np.asarray(order)
+    P = order.size
+    if order.ndim != 1 or P < 1 or sorted(order.tolist()) != list(range(P)):
+        raise ValueError("backselect_words: order must be a permutation of 0..P-1")
+    if mode not in ("backward", "forward"):
+        raise ValueError("backselect_words: mode = %r: 'backward' or 'forward'" % (mode,))
+    kw = (P + 31) // 32
+    cur = 0 if mode == "forward" else (1 << P) - 1
+    words = np.zeros((P + 1, kw), dtype=np.uint32)
+    for t in range(P + 1):
+        for k in range(kw):
+            words[t, k] = (cur >> (32 * k)) & 0xFFFFFFFF
+        if t < P:
+            cur ^= 1 << int(order[t])
+    return words
+
+
+def subset_bools(words, P):
+    """Coalition words [..., kw] (an integer tensor, bit p % 32 of word p / 32 = player p) -> bool [..., P]: a change of layout."""
+    import torch
+    p = torch.arange(P, device=words.device)
+    return ((words.to(torch.int64)[..., p // 32] >> (p % 32)) & 1).bool()
+
+
+def subset_names(subset, names):
+    """The names of the players of a subset: a bool array [P], or a coalition as a Python int / its uint32 words."""
+    if isinstance(subset, (int, np.integer)):
+        return [n for p, n in enumerate(names) if int(subset) >> p & 1]
+    a = np.asarray(subset.cpu() if hasattr(subset, "cpu") else subset)
+    if a.dtype != np.bool_:
+        a = np.array([int(a.reshape(-1)[p // 32]) >> (p % 32) & 1 for p in range(len(names))], dtype=bool)
+    if a.shape != (len(names),):
+        raise ValueError("subset_names: the subset has shape %s for %d players" % (a.shape, len(names)))
+    return [n for n, keep in zip(names, a) if keep]
+
+
 def mark_shapley_interactions_sampled(model, dataset, donor_dataset=None, genes=None, players="cells", top=4, focal=None, index="sii", n_perm=64,
                                       seed=0, scale=0.0, bsz=None, store=None, donor_store=None):
     """Sampled pairwise Shapley interaction indices of each gene's leading histone-mark players, for the genes of a

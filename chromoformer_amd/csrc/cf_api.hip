@@ -16,6 +16,7 @@
 #include "cf_mark_pairs.h"
 #include "cf_mark_windows.h"
 #include "cf_mark_fine.h"
+#include "cf_backselect.h"
 #include "cf_x0_gather.h"
 
 #include <algorithm>

@@ -361,7 +361,7 @@ struct cf_handle {
         float* logits = nullptr;               // [max_batch, n_out]: the chunk's logits
         float* slice_sums = nullptr;           // [max_batch, kIgSlices]: per-slice sums of a gene's attributions (k_ig_delta)
         const unsigned* deletion_words = nullptr;      // [i_max + 2]: the coalition words of cf_pcre_ablation's variants, written once
-        DevBuf<unsigned> words;                // the 32-bit table of a call: coalition words | quadrature nodes, then weights | mark sets | mark-coalition words, then player words (the sampled game: then the inverse permutations, bytes; sampled interactions: then the column table); grows on demand
+        DevBuf<unsigned> words;                // the 32-bit table of a call: coalition words | quadrature nodes, then weights | mark sets | mark-coalition words, then player words (the sampled game: then the inverse permutations, bytes; sampled interactions: then the column table; back-selection: then the current coalitions, the per-gene candidate words and s_b); grows on demand
         DevBuf<float> own_rows;                // [max_batch, per, n_out]: the rows of a Shapley / epistasis call without a caller's buffer; grows on demand
         DevBuf<float> slot_rows;               // [n_res][B * (V - 1), d_emb]: the changed Regulation input row of every variant of one pCRE slot (scan); grows on demand
     } aw;

@@ -178,8 +178,10 @@ static int mark_upload(cf_handle* h, const MarkGame& g, const uint32_t* keep, in
 // The B * n_coal rows of a mark-coalition call (gene-major; row (b, k) is coalition k of the table mark_upload wrote), every row
 // through the whole forward: chunk_forward with the expand kernel of the game's kind and rule, on the argument struct of that kind.
 // k_attc2 takes as many regions per workgroup as for the caller's B genes (ag_genes), as scan_region_rows: the result does not depend
-// on max_batch.
-static int mark_rows(cf_handle* h, const cf_batch* bt, const MarkGame& g, int n_coal, float* logits, hipStream_t st) {
+// on max_batch.  `own`: a table of n_coal coalitions PER GENE at own + b * stride (the back-selection), the player words staying where
+// mark_upload put them behind `n_up` shared coalitions; null: the shared table mark_upload wrote, n_coal coalitions.
+static int mark_rows(cf_handle* h, const cf_batch* bt, const MarkGame& g, int n_coal, float* logits, hipStream_t st, const unsigned* own = nullptr,
+                     long long stride = 0, int n_up = 0) {
     const cf_config& c = h->cfg;
     const int nres = c.n_res, B = bt->B, P = g.P;
     MarkExpandArgs ea;      // what every kind reads
@@ -194,8 +196,9 @@ static int mark_rows(cf_handle* h, const cf_batch* bt, const MarkGame& g, int n_
     }
     ea.freq_in = bt->interaction_freq;
     ea.freq_out = h->aw.row[2 * kMaxRes];
-    ea.words = h->aw.words;
-    ea.players = h->aw.words + (size_t)n_coal * g.kw;
+    ea.words = own ? own : (const unsigned*)h->aw.words;
+    ea.word_stride = own ? stride : 0;
+    ea.players = h->aw.words + (size_t)(own ? n_up : n_coal) * g.kw;
     ea.scale = g.scale;
     ea.n_coal = n_coal, ea.P = P, ea.F = c.n_feats;
     auto donor_feats = [&](const float** pf, const float** cf) {
@@ -474,6 +477,110 @@ extern "C" int cf_perm_interactions_from_rows(cf_handle* h, const float* rows, i
     if (focal_upload(h, t, 0, &rank_at, &col_at, st)) return -1;
     h->n_fwd = 0;
     return launch_perm_pairs(h, B, P, n_out, n_perm, focal, n_focal, index, rows, (size_t)t.R, rank_at, col_at, inter, se, phi, phi_se, st);
+}
+
+// Greedy player selection on a checked game (cf_backselect.h).  What the calls check beside their game, by name: null opts / outputs,
+// mode, direction, target, frac, the four required outputs.
+static int backselect_check(const cf_backselect_opts* o, const cf_backselect_out* out, int n_out, const char* who) {
+    if (!o) return fail("%s: null backselect opts", who);
+    if (!out) return fail("%s: null outputs", who);
+    if (o->mode != CF_BACKSELECT_BACKWARD && o->mode != CF_BACKSELECT_FORWARD)
+        return fail("%s: mode = %d: CF_BACKSELECT_BACKWARD (%d) or CF_BACKSELECT_FORWARD (%d)", who, o->mode, CF_BACKSELECT_BACKWARD, CF_BACKSELECT_FORWARD);
+    if (o->direction < -1 || o->direction > 1) return fail("%s: direction = %d: 0 (from the two end rows), +1 or -1", who, o->direction);
+    if (o->target < 0 || o->target >= n_out) return fail("%s: target = %d outside [0, n_out = %d)", who, o->target, n_out);
+    if (!std::isfinite(o->frac)) return fail("%s: frac = %g: a finite number", who, (double)o->frac);
+    if (!out->order || !out->values || !out->size || !out->subset) return fail("%s: null order / values / size / subset", who);
+    return 0;
+}
+// The two end rows (nobody, everybody: the shared table mark_upload wrote), then per round t = 0 .. P - 2 one k_backselect_step -- the
+// pick among the previous round's rows and the gene's P - t candidate words -- and the B (P - t) rows of the round through mark_rows on
+// the per-gene table; one more k_backselect_step for the last pick, then k_backselect_finish.  Launches, with n_fwd those of
+// cf_forward(save = 0) and M = max_batch:
+//   P + 1 + (1 + n_fwd) (ceil(2 B / M) + sum over t = 0 .. P - 2 of ceil(B (P - t) / M))
+// cur [B, kw], the candidates [B, P, kw] and s_b [B] live behind the player words in the word table; the rows in the caller's buffer or
+// the handle's own.  The host sees no logit: no synchronisation, no copy back.
+static int mark_backselect_impl(cf_handle* h, const cf_batch* bt, const MarkGame& g, const cf_backselect_opts* o, const cf_backselect_out* out,
+                                void* stream, const char* who) {
+    const int B = bt->B, P = g.P, kw = g.kw, n_out = h->cfg.n_out;
+    if (backselect_check(o, out, n_out, who)) return -1;
+    if (g.fine)
+        for (int r = 0; r < kMaxRes; ++r)
+            if (g.fine->feats_out[r]) return fail("%s: feats_out[%d]: the rounds have different row counts; the back-selection writes no features", who, r);
+    float* rows = coalition_out_rows(h, out->rows, 1 + (long long)P * (P + 1) / 2, who);
+    if (!rows) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<uint32_t> ends(2 * (size_t)kw, 0u);
+    for (int p = 0; p < P; ++p) ends[kw + (p >> 5)] |= 1u << (p & 31);
+    if (mark_upload(h, g, ends.data(), 2, (size_t)B * kw * (1 + P) + B, st, who)) return -1;
+    const long long launches0 = g_launches;
+    if (mark_rows(h, bt, g, 2, rows, st)) return -1;
+    BackselectArgs sa;
+    memset(&sa, 0, sizeof sa);
+    sa.ends = rows;
+    sa.cur = (unsigned*)h->aw.words + 2 * kw + mark_player_words(g);
+    sa.cand = sa.cur + (size_t)B * kw;
+    sa.dir = reinterpret_cast<int*>(sa.cand + (size_t)B * P * kw);
+    sa.order = out->order, sa.values = out->values, sa.dir_out = out->direction;
+    sa.P = P, sa.kw = kw, sa.n_out = n_out, sa.mode = o->mode, sa.target = o->target, sa.direction = o->direction;
+    float* at = rows + (size_t)B * 2 * n_out;
+    for (int t = 0; t < P; ++t) {
+        sa.t = t;
+        hipLaunchKernelGGL(k_backselect_step, dim3(B), dim3(kBsThreads), 0, st, sa);
+        LAUNCH_CHECK("k_backselect_step");
+        if (t == P - 1) break;
+        if (mark_rows(h, bt, g, P - t, at, st, sa.cand, (long long)P * kw, 2)) return -1;
+        sa.prev = at;
+        at += (size_t)B * (P - t) * n_out;
+    }
+    BackselectFinishArgs fa;
+    memset(&fa, 0, sizeof fa);
+    fa.ends = rows, fa.dir = sa.dir, fa.order = out->order, fa.values = out->values, fa.size = out->size, fa.subset = out->subset;
+    fa.threshold = o->threshold, fa.thr_out = out->threshold, fa.frac = o->frac;
+    fa.P = P, fa.kw = kw, fa.n_out = n_out, fa.mode = o->mode, fa.target = o->target;
+    hipLaunchKernelGGL(k_backselect_finish, dim3(B), dim3(kBsThreads), 0, st, fa);
+    LAUNCH_CHECK("k_backselect_finish");
+    forward_counted(h, launches0);
+    return 0;
+}
+// The same selection on a caller's table [B, 2^P, n_out]: no batch, no workspace, nothing of the handle is read and no activation written.
+extern "C" int cf_backselect_from_rows(cf_handle* h, const float* rows, int B, int P, int n_out, const cf_backselect_opts* o, const cf_backselect_out* out,
+                                       void* stream) {
+    const char* who = "cf_backselect_from_rows";
+    if (!h) return fail("%s: null handle", who);
+    if (!rows) return fail("%s: null rows", who);
+    if (B < 1) return fail("%s: B = %d: at least 1 gene", who, B);
+    if (P < 1 || P > kCoalMaxS) return fail("%s: P = %d outside 1..%d", who, P, kCoalMaxS);
+    if (n_out < 1) return fail("%s: n_out = %d: at least 1 output", who, n_out);
+    if (backselect_check(o, out, n_out, who)) return -1;
+    BackselectTableArgs ta;
+    memset(&ta, 0, sizeof ta);
+    ta.v = rows, ta.order = out->order, ta.values = out->values, ta.size = out->size, ta.subset = out->subset;
+    ta.threshold = o->threshold, ta.thr_out = out->threshold, ta.dir_out = out->direction, ta.frac = o->frac;
+    ta.P = P, ta.n_out = n_out, ta.mode = o->mode, ta.target = o->target, ta.direction = o->direction;
+    h->n_fwd = 0;
+    hipLaunchKernelGGL(k_backselect_table, dim3(B), dim3(kBsTableThreads), 0, (hipStream_t)stream, ta);
+    LAUNCH_CHECK("k_backselect_table");
+    forward_one_more(h);
+    return 0;
+}
+// one entry point per kind with kw words per coalition (the narrow game is cf_mark_backselect with at most 32 players)
+extern "C" int cf_mark_backselect(cf_handle* h, const cf_batch* bt, const cf_mark_wide_opts* o, const cf_backselect_opts* bo, const cf_backselect_out* out,
+                                  void* stream) {
+    const char* who = "cf_mark_backselect";
+    MarkGame g;
+    return mark_wide_game(h, bt, o, &g, who) ? -1 : mark_backselect_impl(h, bt, g, bo, out, stream, who);
+}
+extern "C" int cf_mark_window_backselect(cf_handle* h, const cf_batch* bt, const cf_mark_window_opts* o, const cf_backselect_opts* bo,
+                                         const cf_backselect_out* out, void* stream) {
+    const char* who = "cf_mark_window_backselect";
+    MarkGame g;
+    return mark_window_game(h, bt, o, &g, who) ? -1 : mark_backselect_impl(h, bt, g, bo, out, stream, who);
+}
+extern "C" int cf_mark_fine_backselect(cf_handle* h, const cf_batch* bt, const cf_mark_fine_opts* o, const cf_backselect_opts* bo,
+                                       const cf_backselect_out* out, void* stream) {
+    const char* who = "cf_mark_fine_backselect";
+    MarkGame g;
+    return mark_fine_game(h, bt, o, &g, (hipStream_t)stream, who) ? -1 : mark_backselect_impl(h, bt, g, bo, out, stream, who);
 }
 
 // The entry points: the game of the family, then its call.  The scale rule's one-word game;

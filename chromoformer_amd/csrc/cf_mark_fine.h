@@ -92,7 +92,7 @@ __device__ __forceinline__ void fine_table(const MarkFineArgs& fa, FineTable& t,
     }
     const int kw = (P + 31) >> 5;
     for (int k = tid; k < 3 * P; k += kIgxThreads) t.pl[k] = a.players[k];
-    if (tid < kw) t.kept[tid] = a.words[(gv - (long long)b * a.n_coal) * kw + tid];
+    if (tid < kw) t.kept[tid] = a.words[b * a.word_stride + (gv - (long long)b * a.n_coal) * kw + tid];
     __syncthreads();
     const int nf = t.ext[3];
     const long long st = fa.start[b];

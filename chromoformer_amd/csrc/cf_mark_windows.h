@@ -26,7 +26,7 @@
 //                  float4 copy (the donor is not loaded); in a touched region every element takes the word of ITS row -- a float4
 //                  spans up to two rows and two regions when F is no multiple of 4.  A segment whose length is no multiple of 4
 //                  floats (or F < 4) goes element by element.
-// No atomics, no scratch, 6,688 bytes of LDS (extents 204, table 4,352, flags 68, staged words 2,064); 46 / 36 VGPRs (scale / donor
+// No atomics, no scratch, 6,688 bytes of LDS (extents 204, table 4,352, flags 68, staged words 2,064); 48 / 36 VGPRs (scale / donor
 // rule), 8 waves per SIMD.  The float4 walk is its own, not mark_copy's: an element's word comes from a table
 // lookup per row here, from one word per region there.
 #pragma once
@@ -77,7 +77,7 @@ __device__ __forceinline__ void win_table(const MarkWindowArgs& wa, WinTable& t,
     }
     const int kw = (P + 31) >> 5;
     for (int k = tid; k < 4 * P; k += kIgxThreads) t.pl[k] = a.players[k];
-    if (tid < kw) t.kept[tid] = a.words[(gv - (long long)b * a.n_coal) * kw + tid];
+    if (tid < kw) t.kept[tid] = a.words[b * a.word_stride + (gv - (long long)b * a.n_coal) * kw + tid];
     __syncthreads();
     const unsigned* m = t.kept;
     const unsigned* pl = t.pl;

@@ -17,7 +17,9 @@
 //   * Limits are the scan's: u < ~80 (expm1f overflows past 88); a negative feature with 1 + s m <= 0 gives NaN.
 //
 // Rows are (gene, coalition) pairs, gene-major (gv = b * n_coal + k, words [k kw, (k + 1) kw) of a device table), in chunks of at most
-// max_batch rows.  One kernel, no atomics, no scratch, 68 bytes of LDS:
+// max_batch rows.  The table is shared by the genes (word_stride = 0: every entry point but the back-selection) or holds n_coal coalitions
+// per gene, gene b's at words + b word_stride (cf_backselect.h, whose next rows depend on the gene's previous logits): a runtime field of
+// MarkExpandArgs that all six expand kernels read -- one 64-bit multiply-add on the scalar unit per workgroup, no second set of kernels.  One kernel, no atomics, no scratch, 68 bytes of LDS:
 //   k_mark_expand   per (chunk row, resolution, slice): the T = i_max + 1 words gone(rho) once per workgroup from the row's kw coalition
 //                   words and the 2 P player words; then its slice of the row's promoter and pCRE features (every element written once,
 //                   float4 where the row allows; the mark of element e is e % F; a region with gone = 0 is a plain copy); slice 0 also
@@ -54,6 +56,7 @@ struct MarkExpandArgs {
     const float* freq_in;              // [B, T, T]
     float* freq_out;
     const unsigned* words;             // device [n_coal * kw], kw = ceil(P / 32): bit p set: player p present
+    long long word_stride;             // 0: one table for all genes; else gene b's n_coal coalitions start at words + b * word_stride
     const unsigned* players;           // device [2 P]: marks_p, then regions_p
     long long g0;                      // first row of the chunk
     float scale;
@@ -101,7 +104,7 @@ __device__ __forceinline__ float partial_tail(float uj, double t, int K0, int K1
 __device__ __forceinline__ void mark_gone(const MarkExpandArgs& a, long long gv, int b, unsigned* gone) {
     const int tid = threadIdx.x, P = a.P;
     if (tid <= a.rows.S) {
-        const unsigned* __restrict__ m = a.words + (gv - (long long)b * a.n_coal) * ((P + 31) >> 5);
+        const unsigned* __restrict__ m = a.words + b * a.word_stride + (gv - (long long)b * a.n_coal) * ((P + 31) >> 5);
         unsigned g = 0;
         for (int p0 = 0; p0 < P; p0 += 32) {
             const unsigned absent = ~m[p0 >> 5];      // one load per word, not per player: the walk is serial and latency-bound

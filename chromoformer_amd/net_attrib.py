@@ -3,7 +3,8 @@ histone marks (coalitions, exact and sampled Shapley values, epistasis, interact
 perturbation scans.  AttributionMixin is a plain mixin of net.ChromoformerBase, which supplies construction, packing, the forward and
 the training methods; every method here runs in the library (csrc/), there is no PyTorch fallback.
 
-The 25 game methods are one runner, _game, over two small tables: _FAMILIES (who the players are) and _KINDS (what is computed)."""
+The 25 game methods are one runner, _game, over two small tables: _FAMILIES (who the players are) and _KINDS (what is computed); the
+functions of chromoformer_amd.backselect run the kind "backselect" through the same runner."""
 from __future__ import annotations
 
 import ctypes as C
@@ -90,6 +91,20 @@ def _pairs_sampled_info(o, g):
     return inter, info
 
 
+def _backselect_info(o, g):
+    """See backselect.mark_backselect.  rows: round-major blocks, views of one buffer."""
+    B, P, n_out, flat = o["order"].shape[0], g.P, o["values"].shape[2], o["rows"].view(-1, o["values"].shape[2])
+    ends = flat[:2 * B].view(B, 2, n_out)
+    info = {"values": o["values"], "size": o["size"], "subset": A.subset_bools(o["subset"], P), "names": g.names, "logits": ends[:, 1].clone(),
+            "absent": ends[:, 0].clone(), "threshold": o["thr"], "direction": o["dir"], "mode": g.select.mode, "target": g.select.target}
+    if g.table:
+        info["rows"], at = [ends], 2 * B
+        for t in range(P - 1):
+            info["rows"].append(flat[at:at + B * (P - t)].view(B, P - t, n_out))
+            at += B * (P - t)
+    return o["order"], info
+
+
 # The kinds of call a family offers.  Per kind: the outputs the library writes in full, each [B, *shape(g), n_out], the first being the
 # table of forwards (one row of feats_out each); the C arguments between the options and the stream (an output, a host value of the
 # call `g`, or #name: its length); (result, info) from the outputs; and the exact game's refusal of more than 16 players, if it is one.
@@ -106,6 +121,10 @@ _KINDS = {
     "shapley_interactions_sampled": ((("rows", lambda g: (len(g.words),)), ("inter", lambda g: (len(g.focal), g.P)),
                                       ("se", lambda g: (len(g.focal), g.P)), ("phi", lambda g: (g.P,)), ("phi_se", lambda g: (g.P,))),
                                      "perms #perms focal #focal code inter se phi phi_se rows", _pairs_sampled_info, None),
+    # (an output with a dtype is [B, *shape(g)] of that dtype, no n_out; the two structs are filled once the outputs exist)
+    "backselect": ((("rows", lambda g: (A.backselect_row_count(g.P),)), ("values", lambda g: (g.P + 1,)), ("order", lambda g: (g.P,), torch.int32),
+                    ("size", lambda g: (), torch.int32), ("subset", lambda g: ((g.P + 31) // 32,), torch.int32), ("thr", lambda g: (), torch.float32),
+                    ("dir", lambda g: (), torch.int32)), "bopts bout", _backselect_info, None),
 }
 
 # What five docstrings say about `inter`, filled per method with the absent key, the sibling method and the line about the players.
@@ -151,11 +170,11 @@ class AttributionMixin:
         return bs, book
 
     def _game(self, who, family, kind, batch, keep=None, index=None, focal=None, perms=None, table=False, feats=False, players=None, width=1,
-              scale=0.0, donor=None, flip=None, fine=None):
+              scale=0.0, donor=None, flip=None, fine=None, select=None):
         """The one body of the game methods: method `who` is call `kind` (_KINDS) of `family` (_FAMILIES) on `batch`, the six arguments
         of forward().  keep / index / focal / perms = (n_perm, seed, permutations): the kind's arguments; table: return_coalitions or
         return_rows; feats: return_feats; players .. flip: the family's options; fine = (region, n_windows, start, lengths) of the fine
-        game.  What can be refused without the batch is refused before the device is asked for (the fine game needs `start` to know its
+        game; select = (mode, frac, threshold, target, direction) of a back-selection.  What can be refused without the batch is refused before the device is asked for (the fine game needs `start` to know its
         players); book() runs once every argument has been accepted, directly in front of the library call."""
         struct, parse, fields, parse_words, keep_what, absent = _FAMILIES[family]
         outputs, c_args, result, too_many = _KINDS[kind]
@@ -163,6 +182,8 @@ class AttributionMixin:
         g = SimpleNamespace(P=self.i_max, names=None, index=index, table=table, focal=focal)      # the host values of the call
         if kind == "coalitions" and keep is None:
             raise ValueError("%s: keep is required: %s" % (who, keep_what))
+        if kind == "backselect":
+            g.select = self._backselect_args(who, *select)
         if "interactions" in kind:
             g.code = A.interaction_index(index, stem[3:])
         if kind == "shapley_interactions_sampled" and focal is None:
@@ -203,7 +224,11 @@ class AttributionMixin:
             if absent == "either":
                 absent = "erased" if donor is None else "donor"
         g.absent = absent
-        out = {name: torch.empty(bs.B, *shape(g), self.n_out, device=self._device) for name, shape in outputs}      # (written in full by the library)
+        out = {o[0]: torch.empty(bs.B, *o[1](g), self.n_out, device=self._device) if len(o) == 2 else
+               torch.empty(bs.B, *o[1](g), dtype=o[2], device=self._device) for o in outputs}      # (written in full by the library)
+        if kind == "backselect":
+            g.bopts, g.bout, kept = self._backselect_structs(who, g.select, bs.B, out)
+            alive += kept
         feats = self._feats_out(opts, bs.B, out[outputs[0][0]].shape[1]) if feats else None
 
         def c_arg(a):
@@ -222,6 +247,52 @@ class AttributionMixin:
             return res, feats
         res[1]["feats"] = feats
         return res
+
+    def _backselect_args(self, who, mode, frac, threshold, target, direction):
+        """The options of a back-selection, checked on the host -> namespace(mode, code, frac, threshold, target, direction)."""
+        if mode not in _lib.BACKSELECT_MODE:
+            raise ValueError("%s: mode = %r: 'backward' (remove players from everybody) or 'forward' (add players to nobody)" % (who, mode))
+        if direction not in ("auto", 1, -1):
+            raise ValueError("%s: direction = %r: 'auto' (from the two end rows), 1 or -1" % (who, direction))
+        target = (1 if self.n_out == 2 else 0) if target is None else int(target)
+        if not 0 <= target < self.n_out:
+            raise ValueError("%s: target = %d outside [0, n_out = %d)" % (who, target, self.n_out))
+        frac = float(frac)
+        if not np.isfinite(frac):
+            raise ValueError("%s: frac = %r: a finite number (the share of logits - absent a sufficient set keeps)" % (who, frac))
+        return SimpleNamespace(mode=mode, code=_lib.BACKSELECT_MODE[mode], frac=frac, threshold=threshold, target=target,
+                               direction=0 if direction == "auto" else int(direction))
+
+    def _backselect_structs(self, who, s, B, out):
+        """cf_backselect_opts and cf_backselect_out of a call on B genes -> (byref opts, byref out, what they point to besides `out`)."""
+        o, w, thr = _lib.cf_backselect_opts(), _lib.cf_backselect_out(), None
+        o.mode, o.target, o.direction, o.frac = s.code, s.target, s.direction, s.frac
+        if s.threshold is not None:
+            thr = torch.as_tensor(s.threshold, dtype=torch.float32).to(self._device).contiguous()
+            if thr.shape != (B,):
+                raise ValueError("%s: threshold has shape %s; expected [B = %d] floats, one per gene" % (who, tuple(thr.shape), B))
+            o.threshold = thr.data_ptr()
+        for field, name in (("order", "order"), ("values", "values"), ("size", "size"), ("subset", "subset"), ("rows", "rows"),
+                            ("threshold", "thr"), ("direction", "dir")):
+            if name in out:
+                setattr(w, field, out[name].data_ptr())
+        return C.byref(o), C.byref(w), (o, w, thr)
+
+    def _backselect_table(self, coalitions, mode, frac, threshold, target, direction, names):
+        """The body of backselect.backselect: cf_backselect_from_rows on a kept coalition table."""
+        who = "backselect"
+        s = self._backselect_args(who, mode, frac, threshold, target, direction)
+        rows, B, P = self._table_check(who, "coalitions", coalitions)
+        g = SimpleNamespace(P=P, names=names, select=s, table=False)
+        out = {"values": torch.empty(B, P + 1, self.n_out, device=self._device), "order": torch.empty(B, P, dtype=torch.int32, device=self._device),
+               "size": torch.empty(B, dtype=torch.int32, device=self._device), "subset": torch.empty(B, 1, dtype=torch.int32, device=self._device),
+               "thr": torch.empty(B, device=self._device), "dir": torch.empty(B, dtype=torch.int32, device=self._device)}
+        bopts, bout, _alive = self._backselect_structs(who, s, B, out)
+        st = torch.cuda.current_stream(self._device).cuda_stream
+        _lib.check(_lib.lib().cf_backselect_from_rows(self._handle, rows.data_ptr(), B, P, self.n_out, bopts, bout, st), "cf_backselect_from_rows")
+        full = (1 << P) - 1
+        out["rows"] = torch.stack((rows[:, 0], rows[:, full]), 1)      # nobody, everybody: what _backselect_info reads of a game's rows
+        return _backselect_info(out, g)
 
     def _game_opts(self, who, opts, fields, arrays, scale, flip, donor, need_donor, B):
         """The fields the options structs of the mark games share, filled for a batch of B genes -> what they point to besides `arrays`.

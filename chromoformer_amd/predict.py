@@ -263,6 +263,37 @@ def write_mark_sampled_values(model, store, donor_store, bsz, gene_ids, path, re
            logits=logits.numpy(), absent=absent.numpy())
 
 
+def write_mark_backselect(model, store, donor_store, bsz, gene_ids, path, regression=False, players="cells", mode="backward", frac=0.9, scale=0.0):
+    """Greedy player selection among up to 128 histone-mark players (backselect.mark_backselect) of every gene of a device-resident store,
+    in store order, on the prediction's logit column, into `path`, an .npz with gene_ids [n], players [P] (names), mode, frac, order
+    int32 [n, P] (the player of each move), curve [n, P + 1] (the logit after t moves), size [n] and subset bool [n, P] (the smallest
+    sufficient set on the path), threshold [n], direction [n], logits [n] and absent [n].  donor_store None: an absent player's raw
+    signal is scaled by `scale`; else a store of the same genes in the same order in the donor cell type, whose signal it takes.
+    Per batch: one gather per store and one backselect.mark_backselect."""
+    from .attribution import mark_players_wide
+    from .backselect import mark_backselect
+    n = len(store)
+    if donor_store is not None and len(donor_store) != n:
+        raise ValueError("write_mark_backselect: the donor store holds %d genes, the store %d" % (len(donor_store), n))
+    names = mark_players_wide(players, model.n_feats, model.i_max)[2]
+    P, t = len(names), 0 if regression else 1
+    order, curve, size, subset = torch.empty(n, P, dtype=torch.int32), torch.empty(n, P + 1), torch.empty(n, dtype=torch.int32), torch.empty(n, P, dtype=torch.bool)
+    thr, sign, logits, absent = torch.empty(n), torch.empty(n, dtype=torch.int32), torch.empty(n), torch.empty(n)
+    for lo, B, args, feats, _ in _dict_batches(store, donor_store, bsz):
+        o, info = mark_backselect(model, *args, players=players, mode=mode, frac=frac, target=t, scale=scale, donor=feats)
+        order[lo:lo + B] = o.cpu()
+        curve[lo:lo + B] = info["values"][..., t].cpu()
+        size[lo:lo + B] = info["size"].cpu()
+        subset[lo:lo + B] = info["subset"].cpu()
+        thr[lo:lo + B] = info["threshold"].cpu()
+        sign[lo:lo + B] = info["direction"].cpu()
+        logits[lo:lo + B] = info["logits"][:, t].cpu()
+        absent[lo:lo + B] = info["absent"][:, t].cpu()
+    _savez(path, gene_ids=np.array(list(gene_ids)), players=np.array(names), mode=np.array(mode), frac=np.float32(frac), order=order.numpy(),
+           curve=curve.numpy(), size=size.numpy(), subset=subset.numpy(), threshold=thr.numpy(), direction=sign.numpy(), logits=logits.numpy(),
+           absent=absent.numpy())
+
+
 def write_mark_sampled_interactions(model, ds, donor_ds, store, donor_store, bsz, gene_ids, path, regression=False, players="cells", top=4, focal=None,
                                     index="sii", n_perm=64, seed=0, scale=0.0):
     """Sampled pairwise Shapley interaction indices of each gene's focal mark players (attribution.mark_shapley_interactions_sampled:
@@ -524,6 +555,7 @@ def write_raw_integrated_gradients(model, dataset, bsz, ig_dir, n_steps=50, meth
 
 
 # the outputs that read the donor cell type, predict()'s arguments and main()'s options alike, in the order the refusals list them
+_BACKSELECT_DONOR_OUTS = ("mark_donor_backselect_out",)      # (reads the donor too; apart, so that the refusals below keep their wording)
 _DONOR_OUTS = ("mark_donor_shapley_out", "mark_donor_epistasis_out", "mark_donor_sampled_shapley_out", "window_donor_shapley_out",
                "fine_window_donor_shapley_out", "mark_donor_interactions_out", "mark_donor_sampled_interactions_out", "mark_donor_dividends_out")
 
@@ -542,7 +574,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
             fine_window_zoom=1, fine_window_perms=64, fine_window_seed=0, fine_window_scale=0.0, pcre_interactions_out=None,
             mark_interactions_out=None, mark_donor_interactions_out=None, interaction_index="sii", mark_sampled_interactions_out=None,
             mark_donor_sampled_interactions_out=None, mark_focal=4, pcre_dividends_out=None, mark_dividends_out=None,
-            mark_donor_dividends_out=None):
+            mark_donor_dividends_out=None, mark_backselect_out=None, mark_donor_backselect_out=None, mark_backselect_players="cells",
+            backselect_mode="backward", backselect_frac=0.9):
     """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file.  attention_dir / embeddings_out: also
     write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps); pcre_ablation_out:
     the predictions with each pCRE deleted (write_pcre_ablation); ig_dir: integrated gradients of every gene
@@ -577,7 +610,15 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     (write_mark_sampled_interactions; mark_focal -- an int: each gene's strongest players by |phi|; a list of names or indices: those
     for every gene --, mark_sampled_players, mark_perms, mark_seed and interaction_index apply); pcre_dividends_out /
     mark_dividends_out / mark_donor_dividends_out: the Harsanyi dividends of every set of pCREs / histone marks / marks against the
-    donor, one .npz in logit space (write_dividends; mark_players applies to the mark games, mark_scale to mark_dividends_out)."""
+    donor, one .npz in logit space (write_dividends; mark_players applies to the mark games, mark_scale to mark_dividends_out);
+    mark_backselect_out / mark_donor_backselect_out: the greedy selection order, the deletion curve and the smallest sufficient subset
+    of up to 128 mark players, one .npz, under the scale rule (mark_scale applies) / against the donor (write_mark_backselect;
+    mark_backselect_players, backselect_mode and backselect_frac apply)."""
+    if mark_backselect_out or mark_donor_backselect_out:      # (refusals before anything is computed)
+        from .attribution import mark_players_wide as _wide
+        _wide(mark_backselect_players, 7, i_max)
+        if backselect_mode not in ("backward", "forward") or not np.isfinite(backselect_frac):
+            raise ValueError("predict: backselect_mode = %r ('backward' / 'forward'), backselect_frac = %r (finite)" % (backselect_mode, backselect_frac))
     from .attribution import interaction_index as _index_check
     _index_check(interaction_index, "predict")      # (before anything is computed)
     pairs_ds, pairs_kw = None, {}
@@ -600,7 +641,7 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         require_raw_signals(raw_ds)      # (before anything is computed)
     from . import pack
     given = locals()      # (the arguments by name)
-    donor_out = any(given[name] for name in _DONOR_OUTS)
+    donor_out = any(given[name] for name in _DONOR_OUTS + _BACKSELECT_DONOR_OUTS)
     plain = []
 
     def plain_ds():      # the run's dataset with regression=False: strand, coordinates and geometry for the generators; built at its first use
@@ -680,6 +721,9 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         if mark_donor_sampled_interactions_out:
             write_mark_sampled_interactions(model, pairs_ds, donor_ds, store, donor_store, bsz, genes, mark_donor_sampled_interactions_out, regression,
                                             **pairs_kw)
+        if mark_donor_backselect_out:
+            write_mark_backselect(model, store, donor_store, bsz, genes, mark_donor_backselect_out, regression, mark_backselect_players,
+                                  backselect_mode, backselect_frac)
         if window_donor_shapley_out:
             write_mark_window_values(model, window_ds, donor_ds, store, donor_store, bsz, genes, window_donor_shapley_out, regression, window_players,
                                      window_width, window_perms, window_seed)
@@ -694,6 +738,9 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     if mark_sampled_interactions_out:
         write_mark_sampled_interactions(model, pairs_ds, None, store, None, bsz, genes, mark_sampled_interactions_out, regression, scale=mark_scale,
                                         **pairs_kw)
+    if mark_backselect_out:
+        write_mark_backselect(model, store, None, bsz, genes, mark_backselect_out, regression, mark_backselect_players, backselect_mode,
+                              backselect_frac, mark_scale)
     if window_shapley_out:
         write_mark_window_values(model, window_ds, None, store, None, bsz, genes, window_shapley_out, regression, window_players, window_width,
                                  window_perms, window_seed, window_scale)
@@ -827,6 +874,20 @@ def build_parser():
                     "[n_genes, i_max + 1, 7]), or the specs of --mark-players")
     ap.add_argument("--mark-perms", type=int, default=None, help="sampled orders of adding the players (default 64); each costs P - 1 forwards per gene")
     ap.add_argument("--mark-seed", type=int, default=None, help="seed of the sampled orders (default 0)")
+    ap.add_argument("--mark-backselect-out", default=None, help="also write the greedy player selection of up to 128 histone-mark players to "
+                    "this .npz file, in metadata order, on the prediction's logit column: gene_ids, players (names), mode, frac, order "
+                    "[n_genes, P] (the player of each move), curve [n_genes, P + 1] (the logit after t moves: the deletion curve), size and "
+                    "subset [n_genes, P] (the smallest sufficient set on the path: which few cells are enough on their own), threshold, "
+                    "direction, logits and absent (chromoformer_amd.backselect.mark_backselect; deterministic, P (P + 1) / 2 + 1 forwards per gene).  "
+                    "--mark-scale applies")
+    ap.add_argument("--mark-donor-backselect-out", default=None, help="the same against the donor cell type of --donor-npy-dir: an absent "
+                    "player takes the donor's signal")
+    ap.add_argument("--mark-backselect-players", default=None, choices=MARK_WIDE_PLAYER_SPECS, help="the players of --mark-backselect-out / "
+                    "--mark-donor-backselect-out: one per (mark, region) pair (cells, the default), or the specs of --mark-players")
+    ap.add_argument("--backselect-mode", default=None, choices=("backward", "forward"), help="backward (default): start from every player and "
+                    "remove the least needed one per round; forward: start from none and add the most useful one")
+    ap.add_argument("--backselect-frac", type=float, default=None, help="a set is sufficient when it keeps this share of logits - absent "
+                    "(default 0.9)")
     ap.add_argument("--mark-sampled-interactions-out", default=None, help="also write the SAMPLED pairwise Shapley interaction index of each gene's "
                     "focal mark players with every player to this .npz file, in metadata order and in LOGIT space of the prediction's column: "
                     "gene_ids, players (names), index, permutations, focal [n_genes, n_focal], interactions and stderr [n_genes, n_focal, P] (the "
@@ -888,7 +949,9 @@ _DEFAULTS = dict(      # what predict() gets for an option that was not given; m
     fine_scan_region="promoter", fine_scan_width=1, fine_scan_stride=None, fine_scan_zoom=None, fine_scan_scale=0.0, mark_players="marks",
     mark_scale=0.0, mark_sampled_players="cells", mark_perms=64, mark_seed=0, mark_focal=4, interaction_index="sii", window_players="promoter",
     window_width=1, window_perms=64, window_seed=0, window_scale=0.0, fine_window_region="promoter", fine_window_width=2,
-    fine_window_players="windows", fine_window_zoom=1, fine_window_perms=64, fine_window_seed=0, fine_window_scale=0.0)
+    fine_window_players="windows", fine_window_zoom=1, fine_window_perms=64, fine_window_seed=0, fine_window_scale=0.0,
+    mark_backselect_players="cells", backselect_mode="backward", backselect_frac=0.9)
+_BACKSELECT_OUTS = ("mark_backselect_out",) + _BACKSELECT_DONOR_OUTS
 _MARK_OUTS = ("mark_shapley_out", "mark_epistasis_out", "mark_interactions_out", "mark_dividends_out")
 _DONOR_EXACT_OUTS = ("mark_donor_shapley_out", "mark_donor_epistasis_out", "mark_donor_interactions_out", "mark_donor_dividends_out")
 _SAMPLED_OUTS = ("mark_sampled_shapley_out", "mark_donor_sampled_shapley_out")
@@ -912,14 +975,17 @@ _NEEDS = [      # (flags, the flags they apply to, the refusal where one of the 
     (("mark_focal",), _PAIRS_OUTS, "--mark-focal needs --mark-sampled-interactions-out or --mark-donor-sampled-interactions-out"),
     (("raw_donor_ig_dir",), ("donor_npy_dir",), "--raw-donor-ig-dir needs --donor-npy-dir"),
     (_DONOR_OUTS, ("donor_npy_dir",), "%s need --donor-npy-dir" % " / ".join("--" + name.replace("_", "-") for name in _DONOR_OUTS)),
-    (("donor_npy_dir", "donor_meta", "donor_store"), _DONOR_OUTS + ("raw_donor_ig_dir",),
+    (_BACKSELECT_DONOR_OUTS, ("donor_npy_dir",), "--mark-donor-backselect-out needs --donor-npy-dir"),
+    (("mark_backselect_players", "backselect_mode", "backselect_frac"), _BACKSELECT_OUTS,
+     "--mark-backselect-players / --backselect-mode / --backselect-frac need --mark-backselect-out or --mark-donor-backselect-out"),
+    (("donor_npy_dir", "donor_meta", "donor_store"), _DONOR_OUTS + _BACKSELECT_DONOR_OUTS + ("raw_donor_ig_dir",),
      "--donor-npy-dir / --donor-meta / --donor-store need --mark-donor-shapley-out, --mark-donor-epistasis-out or "
      "--mark-donor-sampled-shapley-out (or --window-donor-shapley-out, --fine-window-donor-shapley-out, "
      "--mark-donor-interactions-out, --mark-donor-sampled-interactions-out, --mark-donor-dividends-out)"),
     (("mark_sampled_players", "mark_perms", "mark_seed"), _SAMPLED_OUTS + _PAIRS_OUTS,
      "--mark-sampled-players / --mark-perms / --mark-seed need --mark-sampled-shapley-out or --mark-donor-sampled-shapley-out"
      " (or --mark-sampled-interactions-out, --mark-donor-sampled-interactions-out)"),
-    (("mark_scale",), _MARK_OUTS + ("mark_sampled_shapley_out", "mark_sampled_interactions_out"), _MARK_NEED),
+    (("mark_scale",), _MARK_OUTS + ("mark_sampled_shapley_out", "mark_sampled_interactions_out", "mark_backselect_out"), _MARK_NEED),
     (("mark_players",), _MARK_OUTS + _DONOR_EXACT_OUTS, _MARK_NEED),
     (("window_players", "window_width", "window_perms", "window_seed"), _WINDOW_OUTS,
      "--window-players / --window-width / --window-perms / --window-seed need --window-shapley-out or --window-donor-shapley-out"),
@@ -954,6 +1020,8 @@ def main(argv=None):
     for name in ("scan_scale", "fine_scan_scale", "mark_scale", "window_scale", "fine_window_scale"):
         if not (getattr(args, name) >= 0 and np.isfinite(getattr(args, name))):
             ap.error("--%s must be a finite factor >= 0" % name.replace("_", "-"))
+    if not np.isfinite(args.backselect_frac):
+        ap.error("--backselect-frac must be a finite number")
     for name in ("scan_width", "fine_scan_width", "fine_scan_stride", "fine_scan_zoom", "mark_perms", "window_width", "window_perms",
                  "fine_window_width", "fine_window_zoom", "fine_window_perms"):
         if getattr(args, name) is not None and getattr(args, name) < 1:

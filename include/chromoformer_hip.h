@@ -801,6 +801,75 @@ int cf_mark_fine_shapley_interactions_sampled(cf_handle* h, const cf_batch* batc
  * given.  Refusals: null handle / rows, B < 1, n_out < 1, P > 128 and those above. */
 int cf_perm_interactions_from_rows(cf_handle* h, const float* rows, int B, int P, int n_out, const uint8_t* perms, int n_perm, const int* focal,
                                    int n_focal, int index, float* inter, float* se, float* phi, float* phi_se, void* stream);
+/* Greedy player SELECTION (interpretation): which few players are enough on their own to make this call, and in what order does the
+ * prediction fall apart when players are taken away?  The sufficient-input-subset question: backward selection, then the smallest
+ * suffix of the removal order that still carries the prediction, with the deletion / insertion curve that comes with it.
+ * Deterministic, no sampling error; P (P + 1) / 2 + 1 forwards per gene (2,017 at P = 63).
+ *   mode CF_BACKSELECT_BACKWARD  the path starts from everybody and every move REMOVES one player
+ *   mode CF_BACKSELECT_FORWARD   the path starts from nobody and every move ADDS one player
+ * Round t = 0 .. P - 2 evaluates, per gene, the P - t coalitions one move away from the gene's current one (candidates in ascending
+ * player order) and moves to the candidate with the largest key s_b * v[target], an fp32 product:
+ *   s_b      +1 if everybody[target] >= nobody[target], else -1; direction = +1 / -1 overrides it for every gene
+ *   ties     the candidates are scanned in ascending player index with strict >: the lowest index wins.  A NaN key counts as -inf;
+ *            if every key is -inf the lowest index wins
+ * The last move is forced.  order[b, i] is the player of move i; values[b, t] the logits after t moves (values[b, 0] the start row,
+ * values[b, P] the other end row: both carry the bits of the nobody / everybody rows, everybody = cf_forward(save = 0)).
+ *   thr      threshold[b] if given, else nobody + frac (everybody - nobody) on column target, evaluated as fp32
+ *            add(nobody, mul(frac, sub(everybody, nobody))), each operation rounded
+ *   sufficient   a set with value v is sufficient when s_b * (v - thr) >= 0 (fp32 sub, then mul; a NaN is not); the set of everybody
+ *            is sufficient by definition
+ *   size[b]  the smallest k such that the set of k players on the path is sufficient, counted from the small end (the path need not
+ *            be monotone); subset[b] that set, kw = ceil(P / 32) words, bit p % 32 of word p / 32 = player p
+ * Backward mode: the subset is the LAST size[b] players of order[b] (the sufficient input subset); forward mode: the first size[b]. */
+#define CF_BACKSELECT_BACKWARD 0
+#define CF_BACKSELECT_FORWARD 1
+typedef struct cf_backselect_opts {
+    int mode;                                        /* CF_BACKSELECT_BACKWARD / CF_BACKSELECT_FORWARD */
+    int target;                                      /* the logit column of the key and of the threshold, 0 .. n_out - 1 */
+    int direction;                                   /* 0: s_b from the two end rows; +1 / -1: for every gene */
+    float frac;                                      /* finite; read when threshold is NULL */
+    const float* threshold;                          /* device [B] or NULL */
+} cf_backselect_opts;                                /* 24 bytes */
+typedef struct cf_backselect_out {                   /* device buffers */
+    int* order;                                      /* [B, P] */
+    float* values;                                   /* [B, P + 1, n_out] */
+    int* size;                                       /* [B] */
+    uint32_t* subset;                                /* [B, kw] */
+    float* rows;                                     /* optional: every evaluated row, round-major -- block 0 [B, 2, n_out] (nobody,
+                                                        everybody), block 1 + t [B, P - t, n_out], t = 0 .. P - 2: B (P (P + 1) / 2 + 1)
+                                                        rows.  NULL: the handle-owned buffer of cf_pcre_shapley.  Not read by
+                                                        cf_backselect_from_rows */
+    float* threshold;                                /* optional [B]: thr as used */
+    int* direction;                                  /* optional [B]: s_b as used */
+} cf_backselect_out;                                 /* 56 bytes */
+/* cf_mark_backselect: the game of cf_mark_coalitions_wide (players, both rules; with at most 32 players one word per coalition, the
+ * narrow game).  The two end rows run first (nobody, then everybody).  Then per round t one k_backselect_step -- one workgroup per gene:
+ * the pick among the gene's rows of round t - 1 and the gene's P - t candidate words of round t, written into a per-gene word table on
+ * the device -- and the B (P - t) rows of the round (gene-major) through the chunk loop of cf_mark_coalitions_wide, whose expand kernel
+ * reads gene b's words at b * P * kw; one more k_backselect_step makes the last pick, k_backselect_finish the rest.  The host sees no
+ * logit: no synchronisation and no copy to the host inside the call.
+ *   cf_launch_counts fwd = P + 1 + (1 + n_fwd) * (ceil(2 B / max_batch) + sum over t = 0 .. P - 2 of ceil(B (P - t) / max_batch)),
+ *   n_fwd = what cf_forward(save = 0) issues.
+ * The current coalitions, the candidate words and s_b travel in the device table the handle owns, behind the player words (grown on
+ * demand); no other device buffer is added.  Deterministic (no atomics); k_attc2's regions per workgroup are chosen as for the
+ * caller's B genes, so the result does not depend on max_batch.  Every row carries the bits cf_mark_coalitions_wide gives for its word.
+ * Overwrites the activations a cf_forward(save >= 1) kept.  Parameters, gradients and moments are untouched.
+ * Refused by name, before anything is launched: what cf_mark_coalitions_wide refuses (n_players < 1 among it); null bopts / out; a
+ * mode or direction outside its values; target outside [0, n_out); a frac that is not finite; a null order, values, size or subset. */
+int cf_mark_backselect(cf_handle* h, const cf_batch* batch, const cf_mark_wide_opts* opts, const cf_backselect_opts* bopts,
+                       const cf_backselect_out* out, void* stream);
+/* The same for window players (cf_mark_window_coalitions' game) and fine window players (cf_mark_fine_coalitions' game; a non-null
+ * feats_out is refused: the rounds have different row counts). */
+int cf_mark_window_backselect(cf_handle* h, const cf_batch* batch, const cf_mark_window_opts* opts, const cf_backselect_opts* bopts,
+                              const cf_backselect_out* out, void* stream);
+int cf_mark_fine_backselect(cf_handle* h, const cf_batch* batch, const cf_mark_fine_opts* opts, const cf_backselect_opts* bopts,
+                            const cf_backselect_out* out, void* stream);
+/* The same selection and finish on a caller's device table rows [B, 2^P, n_out], word m at column m, 1 <= P <= 16 (the logits_all of
+ * any exact *_shapley call): k_backselect_table, one workgroup per gene runs all rounds; no forward, no batch, no workspace, nothing
+ * of the handle is read.  subset is [B] (one word).  fwd = 1.  Refusals: null handle / rows, B < 1, P outside 1..16, n_out < 1 and
+ * those of bopts / out above. */
+int cf_backselect_from_rows(cf_handle* h, const float* rows, int B, int P, int n_out, const cf_backselect_opts* bopts, const cf_backselect_out* out,
+                            void* stream);
 /* torch.optim.AdamW.step (train.py:157, 196): decoupled weight decay, bias correction
  * from `step` (1-based), over [0, n_active). */
 int cf_adamw_step(cf_handle* h, float lr, float beta1, float beta2, float eps, float weight_decay,
