@@ -107,6 +107,11 @@ class cf_mark_opts(C.Structure):
     _fields_ = [("n_players", C.c_int), ("player_marks", C.c_void_p), ("player_regions", C.c_void_p), ("scale", C.c_float)]
 
 
+class cf_contact_opts(C.Structure):
+    _fields_ = [("n_players", C.c_int), ("player_drop", C.c_void_p), ("player_contact", C.c_void_p), ("scale", C.c_float),
+                ("donor_freq", C.c_void_p)]
+
+
 class cf_mark_donor_opts(C.Structure):
     _fields_ = [("n_players", C.c_int), ("player_marks", C.c_void_p), ("player_regions", C.c_void_p),
                 ("donor_promoter_feats", C.c_void_p * MAX_RES), ("donor_pcre_feats", C.c_void_p * MAX_RES)]
@@ -198,6 +203,11 @@ SYMBOLS = {
     "cf_set_interactions_from_dividends": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                      C.c_void_p]),
     "cf_pcre_shapley_interactions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cf_contact_coalitions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_contact_opts), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "cf_contact_shapley": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_contact_opts), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cf_contact_epistasis": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_contact_opts), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cf_contact_shapley_interactions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_contact_opts), C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]),
     "cf_integrated_gradients": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_ig_opts), C.POINTER(cf_input_grads), C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_integrated_gradients_raw": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_ig_opts), C.POINTER(cf_input_grads),

@@ -143,6 +143,60 @@ def mark_coalition_words(keep, n_players, who="mark_coalitions"):
     return coalition_words(keep, n_players, who, item="player", limit="n_players")
 
 
+CONTACT_PLAYER_SPECS = ("contacts", "pcres", "pcres_and_contacts", "all")
+
+
+def contact_players(spec, i_max):
+    """The players of the contact game (chromoformer_amd.contact: contact_coalitions / contact_shapley / contact_epistasis) ->
+    (drop uint32 [P], contact uint32 [P], names): bit j of drop[p] set = pCRE slot j is deleted while player p is absent; bit j of
+    contact[p] set = slot j's promoter contact frequency is edited while player p is absent.  spec:
+
+      "contacts"            P = i_max: player j is slot j's contact ("contact0", ...)
+      "pcres"               P = i_max: player j deletes slot j ("pcre0", ...): the pCRE game, the cross-check against pcre_shapley
+      "pcres_and_contacts"  P = 2 i_max: players 0 .. i_max - 1 delete slot j ("pcre0", ...), players i_max .. 2 i_max - 1 edit its
+                            contact ("contact0", ...): chromatin state against contact, slot by slot; i_max <= 8
+      "all"                 P = 1: one player holding every contact ("contacts"): the model without Hi-C
+      a list of (drop_slots, contact_slots) pairs of index iterables (either may be empty, not both); players may overlap
+
+    More than 16 players, an empty player or a slot outside [0, i_max) raise ValueError naming contact_players."""
+    who, S = "contact_players", int(i_max)
+    slots = list(range(S))
+    if isinstance(spec, str):
+        if spec == "contacts":
+            pairs, names = [([], [j]) for j in slots], ["contact%d" % j for j in slots]
+        elif spec == "pcres":
+            pairs, names = [([j], []) for j in slots], ["pcre%d" % j for j in slots]
+        elif spec == "pcres_and_contacts":
+            if S > 8:
+                raise ValueError("%s: players 'pcres_and_contacts' needs 2 i_max = %d players and the exact game takes 1..16 (2^P rows "
+                                 "per gene): with i_max = %d > 8 choose 'contacts' or give a list of (drop_slots, contact_slots) pairs "
+                                 "for the slots of interest" % (who, 2 * S, S))
+            pairs = [([j], []) for j in slots] + [([], [j]) for j in slots]
+            names = ["pcre%d" % j for j in slots] + ["contact%d" % j for j in slots]
+        elif spec == "all":
+            pairs, names = [([], slots)], ["contacts"]
+        else:
+            raise ValueError("%s: players %r; choose from %s or give a list of (drop_slots, contact_slots) pairs" % (who, spec, CONTACT_PLAYER_SPECS))
+    else:
+        try:
+            pairs = [(sorted({int(j) for j in ds}), sorted({int(j) for j in cs})) for ds, cs in spec]
+        except (TypeError, ValueError):
+            raise ValueError("%s: players must be one of %s or a list of (drop_slots, contact_slots) pairs of index iterables, got %r"
+                             % (who, CONTACT_PLAYER_SPECS, spec)) from None
+        names = ["drop(%s)+contact(%s)" % (",".join(map(str, ds)), ",".join(map(str, cs))) for ds, cs in pairs]
+    if not 1 <= len(pairs) <= 16:
+        raise ValueError("%s: %d players; the exact game takes 1..16" % (who, len(pairs)))
+    for p, (ds, cs) in enumerate(pairs):
+        if not ds and not cs:
+            raise ValueError("%s: player %d is empty: at least one pCRE slot to delete or one contact to edit" % (who, p))
+        for what, js in (("drop", ds), ("contact", cs)):
+            if js and (js[0] < 0 or js[-1] >= S):
+                raise ValueError("%s: player %d names %s slot(s) %s outside [0, i_max = %d)" % (who, p, what, js, S))
+    drop = np.array([sum(1 << j for j in ds) for ds, _ in pairs], dtype=np.uint32)
+    contact = np.array([sum(1 << j for j in cs) for _, cs in pairs], dtype=np.uint32)
+    return drop, contact, names
+
+
 MARK_WIDE_PLAYER_SPECS = MARK_PLAYER_SPECS + ("cells",)
 MARK_WIDE_MAX_PLAYERS = 128
 
@@ -964,15 +1018,17 @@ def _batches(who, model, dataset, genes, chunk, binsizes, store=None, donor_data
         yield ids, idx, d, tuple(d[k] for k in _BATCH_KEYS), None if dd is None else _donor_pair(dd), dd
 
 
-def _exact_game(model, prefix, args, kw, interactions, dividends):
-    """One exact game of a batch (prefix "mark", "mark_donor", "mark_window" or "mark_fine_window") -> (phi, interactions or None, info,
+def _exact_game(model, prefix, args, kw, interactions, dividends, methods=None):
+    """One exact game of a batch (prefix "mark", "mark_donor", "mark_window" or "mark_fine_window"; "contact" with `methods`, the
+    holder of <prefix>_shapley and <prefix>_shapley_interactions where that is not the model) -> (phi, interactions or None, info,
     dividends, mass): one model.<prefix>_shapley(*args, **kw), or with `interactions` (an index name) one
     model.<prefix>_shapley_interactions in its place, phi from info["phi"]; with `dividends` the call keeps its coalition table and
     model.shapley_dividends turns it into (dividends, mass) [B, 2^P, n_out], else (None, None).  Host arrays but for info, the call's."""
+    methods = model if methods is None else methods
     if interactions is None:
-        inter, (phi, info) = None, getattr(model, prefix + "_shapley")(*args, return_coalitions=bool(dividends), **kw)
+        inter, (phi, info) = None, getattr(methods, prefix + "_shapley")(*args, return_coalitions=bool(dividends), **kw)
     else:
-        inter, info = getattr(model, prefix + "_shapley_interactions")(*args, index=interactions, return_coalitions=bool(dividends), **kw)
+        inter, info = getattr(methods, prefix + "_shapley_interactions")(*args, index=interactions, return_coalitions=bool(dividends), **kw)
         phi, inter = info["phi"], inter.cpu().numpy()
     div, mass = None, None
     if dividends:
@@ -1260,6 +1316,69 @@ def mark_donor_shapley(model, dataset, donor_dataset, genes=None, players="marks
         for i, g in enumerate(ids):
             out = dict(gene_id=g, phi=phi[i].copy(), logits=logits[i].copy(), donor=don[i].copy(), donor_prediction=pred[i].copy(),
                        players=list(names))
+            yield _optional_keys(out, i, eps, inter, div, mass)
+
+
+def contact_shapley(model, dataset, donor_dataset=None, genes=None, players="contacts", scale=0.0, marks="own", epistasis=False,
+                    interactions=None, dividends=False, bsz=None, store=None, donor_store=None):
+    """Exact Shapley values of contact players for the genes of a ChromoformerDataset (one contact.contact_shapley per batch, with
+    epistasis=True also one contact.contact_epistasis): does a pCRE matter through its chromatin state or through its contact with the
+    promoter?  An absent player deletes its pCRE slots and / or edits their promoter contact frequencies (contact_players): scaled by
+    `scale` (0 erases the contact, the default), or, with `donor_dataset` (another cell type over the same regions: same_regions runs
+    first), replaced by the donor's frequencies.  A generator over `genes` (ids; default: the dataset's) in chunks of at most
+    min(bsz, model.max_batch) genes; per gene it yields a dict of host arrays:
+
+        gene_id            the id
+        phi                float32 [P, n_out]: the players' Shapley values, in logit space; phi.sum(0) = logits - erased (or - donor) up
+                           to rounding; exactly 0 for a dummy slot's players
+        logits             float32 [n_out]: every player present
+        erased             float32 [n_out], without a donor dataset: every player absent
+        donor              float32 [n_out], with a donor dataset: every player absent (its contacts the donor's)
+        players            the players' names (contact_players)
+        freq               float32 [i_max]: the gene's promoter-pCRE contact frequencies, slot by slot
+        donor_freq         float32 [i_max], with a donor dataset: the donor's
+        pcres              the (chrom, start, end) of the gene's live slots
+        eps                float32 [P, P, n_out], with epistasis=True: the pair epistasis, the leave-one-out effects on the diagonal
+        interactions       float32 [P, P, n_out], with interactions="sii" / "sti": the pairwise Shapley interaction index; the batch then
+                           makes one contact.contact_shapley_interactions call in place of contact.contact_shapley
+        dividends, mass    float32 [2^P, n_out] each, with dividends=True: as in mark_shapley
+
+    marks="own" (default) plays the game on the gene's own features.  marks="donor" (a donor dataset is required) plays it on the donor's
+    features under the gene's masks: `logits` is then mark_donor_shapley's `donor` row and, with players that hold every contact, the
+    every-player-absent row is the donor dataset's own forward -- the two games' phi together account for logits - donor_prediction
+    of mark_donor_shapley.  The Embedding + Pairwise stage runs once per gene; the rows cost what pcre_shapley's cost.  The binned
+    features come from `store` / `donor_store` as in mark_donor_shapley.  Parameters, gradients and optimiser state are left as they
+    are; the pass overwrites the activations a grad-enabled model(...) keeps for its backward."""
+    from . import contact as games
+    ds, dn = dataset, donor_dataset
+    who = "contact_shapley"
+    if marks not in ("own", "donor"):
+        raise ValueError("%s: marks = %r: 'own' (the gene's features) or 'donor' (the donor dataset's, under the gene's masks)" % (who, marks))
+    if marks == "donor" and dn is None:
+        raise ValueError("%s: marks='donor' needs a donor_dataset" % who)
+    binsizes, _, genes, chunk = _open(who, model, ds, genes, bsz, dn)
+    spec = players if isinstance(players, str) else list(players)
+    names = contact_players(spec, ds.i_max)[2]      # (refusals before anything is loaded)
+    if interactions is not None:
+        interaction_index(interactions, who)
+    S, absent = ds.i_max, "erased" if dn is None else "donor"
+    for ids, _, d, args, donor, dd in _batches(who, model, ds, genes, chunk, binsizes, store, dn, donor_store):
+        kw = dict(players=spec, scale=scale)
+        if dn is not None:
+            kw["donor_freq"] = dd["interaction_freq"].contiguous()
+            if marks == "donor":
+                args = (donor[0], args[1], donor[1]) + tuple(args[3:])
+        phi, inter, info, div, mass = _exact_game(model, "contact", args, kw, interactions, dividends, games.bound(model))
+        logits, gone = info["logits"].cpu().numpy(), info[absent].cpu().numpy()
+        eps = games.contact_epistasis(model, *args, **kw)[0].cpu().numpy() if epistasis else None
+        freq = d["interaction_freq"][:, 0, 1:].cpu().numpy()
+        dfreq = None if dn is None else dd["interaction_freq"][:, 0, 1:].cpu().numpy()
+        for i, g in enumerate(ids):
+            out = dict(gene_id=g, phi=phi[i].copy(), logits=logits[i].copy(), players=list(names), freq=freq[i].copy(),
+                       pcres=[tuple(p) for p in ds.genes[g]["pcres"][:S]])
+            out[absent] = gone[i].copy()
+            if dfreq is not None:
+                out["donor_freq"] = dfreq[i].copy()
             yield _optional_keys(out, i, eps, inter, div, mass)
 
 

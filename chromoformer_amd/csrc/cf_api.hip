@@ -7,6 +7,7 @@
 #include "cf_attn_maps.h"
 #include "cf_rows.h"
 #include "cf_coalition.h"
+#include "cf_contact.h"
 #include "cf_dividends.h"
 #include "cf_ig.h"
 #include "cf_scan.h"
@@ -41,6 +42,7 @@ using namespace cf;
 #include "cf_api_fwd.h"
 #include "cf_api_bwd.h"
 #include "cf_api_attrib.h"
+#include "cf_api_contact.h"
 #include "cf_api_marks.h"
 
 // ------------------------------------------------------------------------------------

@@ -276,8 +276,11 @@ static int chunk_forward(cf_handle* h, cf_batch* cb, long long rows, float* logi
 // The shared host routine of cf_pcre_ablation and the coalition entry points (cf_coalition.h): the trunk once on the B genes,
 // k_pcre_stash, then per chunk of at most max_batch of the B * n_coal rows (gene-major; row (b, k) is word tab[k], a device table) one
 // k_coalition_expand and the Regulation + head launches of an inference forward on that chunk, writing the chunk's contiguous slice of
-// `logits`.  The callers have checked the batch and called attrib_ws.
-static int coalition_rows(cf_handle* h, const cf_batch* bt, const unsigned* tab, int n_coal, float* logits, hipStream_t st) {
+// `logits`.  The callers have checked the batch and called attrib_ws.  coalition_rows_by is the routine with the expand launch as a
+// parameter -- launch(ea, n) issues the one expand launch of a chunk of n rows on the filled CoalExpandArgs --: coalition_rows passes
+// k_coalition_expand, the contact games (cf_api_contact.h) k_contact_expand.
+template <class Launch>
+static int coalition_rows_by(cf_handle* h, const cf_batch* bt, const unsigned* tab, int n_coal, float* logits, hipStream_t st, Launch launch) {
     const cf_config& c = h->cfg;
     const int B = bt->B, T = c.i_max + 1, nres = c.n_res;
     const long long launches0 = g_launches;
@@ -299,11 +302,17 @@ static int coalition_rows(cf_handle* h, const cf_batch* bt, const unsigned* tab,
     ea.n_coal = n_coal, ea.T = T, ea.row4 = T * c.d_emb / 4;
     if (chunk_forward(h, &cb, (long long)B * n_coal, logits, false, B, st, [&](long long g0, int n) {
             ea.g0 = g0;
-            return launch_expand(k_coalition_expand, "k_coalition_expand", dim3(n, nres), kAblThreads, ea, st);
+            return launch(ea, n);
         }))
         return -1;
     forward_counted(h, launches0);
     return 0;
+}
+static int coalition_rows(cf_handle* h, const cf_batch* bt, const unsigned* tab, int n_coal, float* logits, hipStream_t st) {
+    const int nres = h->cfg.n_res;
+    return coalition_rows_by(h, bt, tab, n_coal, logits, st, [&](const CoalExpandArgs& ea, int n) {
+        return launch_expand(k_coalition_expand, "k_coalition_expand", dim3(n, nres), kAblThreads, ea, st);
+    });
 }
 
 // The fixed table of attrib_ws through coalition_rows: variant v of gene b is row (b, v).

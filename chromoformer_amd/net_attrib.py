@@ -4,7 +4,8 @@ perturbation scans.  AttributionMixin is a plain mixin of net.ChromoformerBase, 
 the training methods; every method here runs in the library (csrc/), there is no PyTorch fallback.
 
 The 25 game methods are one runner, _game, over two small tables: _FAMILIES (who the players are) and _KINDS (what is computed); the
-functions of chromoformer_amd.backselect run the kind "backselect" through the same runner."""
+functions of chromoformer_amd.backselect run the kind "backselect" through the same runner, those of chromoformer_amd.contact the
+family "contact"."""
 from __future__ import annotations
 
 import ctypes as C
@@ -23,6 +24,8 @@ from . import attribution as A
 _WORDS, _WIDE = "the coalition words (bit p set: player p present)", "the coalitions (bit p set: player p present)"
 _FAMILIES = {
     "pcre": (None, None, (), A.coalition_words, "the coalition words (bit j set: pCRE slot j kept)", "promoter_only"),
+    "contact": (_lib.cf_contact_opts, lambda spec, n_feats, i_max: A.contact_players(spec, i_max), ("player_drop", "player_contact"),
+                A.mark_coalition_words, _WORDS, "either"),
     "mark": (_lib.cf_mark_opts, A.mark_players, ("player_marks", "player_regions"), A.mark_coalition_words, _WORDS, "erased"),
     "mark_donor": (_lib.cf_mark_donor_opts, A.mark_players, ("player_marks", "player_regions"), A.mark_coalition_words, _WORDS, "donor"),
     "mark_wide": (_lib.cf_mark_wide_opts, A.mark_players_wide, ("player_marks", "player_regions"), A.mark_wide_words, _WIDE, "either"),
@@ -127,7 +130,8 @@ _KINDS = {
                     ("dir", lambda g: (), torch.int32)), "bopts bout", _backselect_info, None),
 }
 
-# What five docstrings say about `inter`, filled per method with the absent key, the sibling method and the line about the players.
+# What five docstrings say about `inter`, filled per method with the absent key, the sibling method and the line about the players
+# (contact.contact_shapley_interactions fills it too).
 _INTER_DOC = """inter               [B, P, P, n_out], exactly symmetric.  Off the diagonal, with S over the coalitions that hold neither player,
                               I_ij = sum_S w(|S|) ((v(S + i + j) - v(S + j)) - (v(S + i) - v(S))): how much i's marginal contribution
                               changes with j present, averaged over every context -- negative for redundant players, positive for
@@ -303,6 +307,8 @@ class AttributionMixin:
         if hasattr(opts, "scale"):
             opts.scale = float(scale)
         alive = (self._set_flip(who, opts, flip, B),) if hasattr(opts, "flip") else ()
+        if hasattr(opts, "donor_freq"):      # (the contact games: the donor is a frequency tensor)
+            return alive + self._donor_freq(who, opts, donor, B)
         if need_donor or donor is not None:
             alive += self._donor_feats(who, donor, B, opts)
         return alive
@@ -967,6 +973,26 @@ class AttributionMixin:
         batch = (promoter_feats, promoter_pad_masks, pcre_feats, pcre_pad_masks, interaction_masks, interaction_freq)
         return self._game("mark_shapley_interactions", "mark", "shapley_interactions", batch, players=players, scale=scale, index=index,
                           table=return_coalitions)
+
+    def _donor_freq(self, who, opts, donor_freq, B):
+        """The donor rule of the contact games: donor_freq (None: the scale rule) checked, its pointer written into opts.donor_freq ->
+        what it points to.  A contiguous float32 tensor [B, T, T] (or [B, 1, T, T]) on the model's device, T = i_max + 1."""
+        if donor_freq is None:
+            return ()
+        T, t = self.i_max + 1, donor_freq
+        what = "%s: donor_freq" % who
+        if not torch.is_tensor(t):
+            raise ValueError("%s is not a tensor" % what)
+        if t.dtype != torch.float32:
+            raise ValueError("%s is %s; the donor's bits are taken as they are: float32 is required" % (what, t.dtype))
+        if t.device != self._device:
+            raise ValueError("%s is on %s, the model on %s" % (what, t.device, self._device))
+        if t.numel() != B * T * T or t.dim() < 3 or t.shape[0] != B or tuple(t.shape[-2:]) != (T, T):
+            raise ValueError("%s has shape %s; expected %s" % (what, tuple(t.shape), (B, T, T)))
+        if not t.is_contiguous():
+            raise ValueError("%s is not contiguous" % what)
+        opts.donor_freq = t.data_ptr()
+        return (t,)
 
     def mark_shapley_dataset(self, dataset, genes=None, players="marks", scale=0.0, epistasis=False, bsz=None, store=None, interactions=None,
                              dividends=False):

@@ -378,6 +378,40 @@ def write_mark_fine_window_values(model, ds, donor_ds, store, donor_store, bsz, 
     _savez(path, **out)
 
 
+def write_contact_values(model, ds, donor_ds, store, donor_store, bsz, gene_ids, shapley_out, interactions_out=None, dividends_out=None,
+                         regression=False, players="contacts", scale=0.0, marks="own", index="sii"):
+    """Exact Shapley values of contact players (contact.contact_shapley_dataset: an absent player deletes its pCRE slots and / or edits
+    their promoter contact frequencies) of every gene of a device-resident store, in store order, in LOGIT space of the prediction's
+    column, into `shapley_out`, an .npz with gene_ids [n], players [P] (names), phi [n, P], logits [n] (every player present), erased [n]
+    (every player absent) or, with donor_ds, donor [n], freq [n, i_max] (the genes' contact frequencies) and n_pcres [n]; with donor_ds
+    (the donor rule: an absent contact takes the donor cell type's frequency) also donor_freq [n, i_max] and marks ("own" / "donor":
+    whose features the game was played on).  interactions_out: a float32 .npy [n, P, P], the pairwise index `index` (the batch's one
+    call then serves phi too); dividends_out: an .npz with gene_ids, players, sets [2^P], dividends and mass [n, 2^P], from the table of
+    the same call.  ds / donor_ds: the datasets the stores were built from; donor_ds None: the scale rule (`scale` applies)."""
+    from .attribution import set_names
+    from .contact import contact_shapley_dataset
+    t = 0 if regression else 1
+    rows = list(contact_shapley_dataset(model, ds, donor_ds, genes=list(gene_ids), players=players, scale=scale, marks=marks,
+                                              interactions=index if interactions_out else None, dividends=bool(dividends_out), bsz=bsz, store=store,
+                                              donor_store=donor_store))
+    names, absent = rows[0]["players"], "erased" if donor_ds is None else "donor"
+    ids = np.array(list(gene_ids))
+    if shapley_out:
+        out = dict(gene_ids=ids, players=np.array(names), phi=np.stack([r["phi"][:, t] for r in rows]),
+                   logits=np.array([r["logits"][t] for r in rows], dtype=np.float32), freq=np.stack([r["freq"] for r in rows]),
+                   n_pcres=np.array([len(r["pcres"]) for r in rows], dtype=np.int32))
+        out[absent] = np.array([r[absent][t] for r in rows], dtype=np.float32)
+        if donor_ds is not None:
+            out["donor_freq"], out["marks"] = np.stack([r["donor_freq"] for r in rows]), np.array(marks)
+        _savez(shapley_out, **out)
+    if interactions_out:
+        np.save(interactions_out, np.stack([r["interactions"][..., t] for r in rows]).astype(np.float32))
+    if dividends_out:
+        sets = set_names(np.arange(1 << len(names), dtype=np.uint32), names)
+        _savez(dividends_out, gene_ids=ids, players=np.array(names), sets=np.array(sets), dividends=np.stack([r["dividends"][..., t] for r in rows]),
+               mass=np.stack([r["mass"][..., t] for r in rows]))
+
+
 def write_integrated_gradients(model, store, bsz, ig_dir, n_steps=50, method="gausslegendre", target=None):
     """Integrated gradients of every gene of a device-resident store, in store order, into `ig_dir`: promoter_feats_{b}.npy
     [n, L, F], pcre_feats_{b}.npy [n, i_max, L, F], interaction_freq.npy [n, T, T] and delta.npy [n] (float32 .npy memory maps;
@@ -555,6 +589,7 @@ def write_raw_integrated_gradients(model, dataset, bsz, ig_dir, n_steps=50, meth
 
 
 # the outputs that read the donor cell type, predict()'s arguments and main()'s options alike, in the order the refusals list them
+_CONTACT_DONOR_OUTS = ("contact_donor_shapley_out",)          # (reads the donor too; apart, as the next)
 _BACKSELECT_DONOR_OUTS = ("mark_donor_backselect_out",)      # (reads the donor too; apart, so that the refusals below keep their wording)
 _DONOR_OUTS = ("mark_donor_shapley_out", "mark_donor_epistasis_out", "mark_donor_sampled_shapley_out", "window_donor_shapley_out",
                "fine_window_donor_shapley_out", "mark_donor_interactions_out", "mark_donor_sampled_interactions_out", "mark_donor_dividends_out")
@@ -575,7 +610,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
             mark_interactions_out=None, mark_donor_interactions_out=None, interaction_index="sii", mark_sampled_interactions_out=None,
             mark_donor_sampled_interactions_out=None, mark_focal=4, pcre_dividends_out=None, mark_dividends_out=None,
             mark_donor_dividends_out=None, mark_backselect_out=None, mark_donor_backselect_out=None, mark_backselect_players="cells",
-            backselect_mode="backward", backselect_frac=0.9):
+            backselect_mode="backward", backselect_frac=0.9, contact_shapley_out=None, contact_players="contacts", contact_scale=0.0,
+            contact_interactions_out=None, contact_dividends_out=None, contact_donor_shapley_out=None, contact_donor_marks="own"):
     """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file.  attention_dir / embeddings_out: also
     write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps); pcre_ablation_out:
     the predictions with each pCRE deleted (write_pcre_ablation); ig_dir: integrated gradients of every gene
@@ -613,7 +649,21 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     donor, one .npz in logit space (write_dividends; mark_players applies to the mark games, mark_scale to mark_dividends_out);
     mark_backselect_out / mark_donor_backselect_out: the greedy selection order, the deletion curve and the smallest sufficient subset
     of up to 128 mark players, one .npz, under the scale rule (mark_scale applies) / against the donor (write_mark_backselect;
-    mark_backselect_players, backselect_mode and backselect_frac apply)."""
+    mark_backselect_players, backselect_mode and backselect_frac apply); contact_shapley_out / contact_interactions_out /
+    contact_dividends_out: exact Shapley values / the pairwise interaction index interaction_index / the Harsanyi dividends of contact
+    players, whose absence scales the promoter-pCRE contact frequencies by contact_scale (write_contact_values; contact_players --
+    "contacts", "pcres", "pcres_and_contacts" or "all" -- applies); contact_donor_shapley_out: the Shapley values of the same players
+    against the donor cell type's contact frequencies, on the gene's own features or, with contact_donor_marks="donor", on the
+    donor's (contact_players applies)."""
+    if contact_shapley_out or contact_interactions_out or contact_dividends_out or contact_donor_shapley_out:      # (refusals before anything is computed)
+        from .attribution import contact_players as _contact
+        _contact(contact_players, i_max)
+        if contact_interactions_out and len(_contact(contact_players, i_max)[2]) < 2:
+            raise ValueError("predict: contact_interactions_out needs at least 2 players; contact_players = %r has 1" % (contact_players,))
+        if not np.isfinite(contact_scale):
+            raise ValueError("predict: contact_scale = %r: a finite factor" % (contact_scale,))
+        if contact_donor_marks not in ("own", "donor"):
+            raise ValueError("predict: contact_donor_marks = %r: 'own' or 'donor'" % (contact_donor_marks,))
     if mark_backselect_out or mark_donor_backselect_out:      # (refusals before anything is computed)
         from .attribution import mark_players_wide as _wide
         _wide(mark_backselect_players, 7, i_max)
@@ -641,7 +691,7 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         require_raw_signals(raw_ds)      # (before anything is computed)
     from . import pack
     given = locals()      # (the arguments by name)
-    donor_out = any(given[name] for name in _DONOR_OUTS + _BACKSELECT_DONOR_OUTS)
+    donor_out = any(given[name] for name in _DONOR_OUTS + _BACKSELECT_DONOR_OUTS + _CONTACT_DONOR_OUTS)
     plain = []
 
     def plain_ds():      # the run's dataset with regression=False: strand, coordinates and geometry for the generators; built at its first use
@@ -672,7 +722,7 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     if donor_out:      # (before anything is computed)
         from .attribution import same_regions
         if not donor_npy_dir:
-            raise ValueError("predict: %s need donor_npy_dir" % " / ".join(_DONOR_OUTS))
+            raise ValueError("predict: %s need donor_npy_dir" % " / ".join(_DONOR_OUTS + _CONTACT_DONOR_OUTS))
         donor_ds = ChromoformerDataset(donor_meta or meta_path, donor_npy_dir, genes, 7, i_max, list(binsizes), w_prom, w_max, regression=False)
         same_regions(plain_ds(), donor_ds)
     packed = pack.find(npy_dir, store_path, list(binsizes), i_max, w_prom, w_max, 7, genes, meta=meta)
@@ -721,6 +771,9 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
         if mark_donor_sampled_interactions_out:
             write_mark_sampled_interactions(model, pairs_ds, donor_ds, store, donor_store, bsz, genes, mark_donor_sampled_interactions_out, regression,
                                             **pairs_kw)
+        if contact_donor_shapley_out:
+            write_contact_values(model, plain_ds(), donor_ds, store, donor_store, bsz, genes, contact_donor_shapley_out, None, None, regression,
+                                 contact_players, marks=contact_donor_marks)
         if mark_donor_backselect_out:
             write_mark_backselect(model, store, donor_store, bsz, genes, mark_donor_backselect_out, regression, mark_backselect_players,
                                   backselect_mode, backselect_frac)
@@ -732,6 +785,9 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
                                           fine_window_region, fine_window_width, fine_window_players, fine_window_zoom, fine_window_perms,
                                           fine_window_seed)
         del donor_store
+    if contact_shapley_out or contact_interactions_out or contact_dividends_out:
+        write_contact_values(model, plain_ds(), None, store, None, bsz, genes, contact_shapley_out, contact_interactions_out, contact_dividends_out,
+                             regression, contact_players, contact_scale, index=interaction_index)
     if mark_sampled_shapley_out:
         write_mark_sampled_values(model, store, None, bsz, genes, mark_sampled_shapley_out, regression, mark_sampled_players, mark_perms, mark_seed,
                                   mark_scale)
@@ -908,6 +964,29 @@ def build_parser():
                     "--mark-scale apply")
     ap.add_argument("--mark-donor-dividends-out", default=None, help="the same against the donor cell type of --donor-npy-dir: an absent mark "
                     "takes the donor's signal (model.mark_donor_dividends).  --mark-players applies")
+    from .attribution import CONTACT_PLAYER_SPECS
+    ap.add_argument("--contact-shapley-out", default=None, help="also write the exact Shapley values of CONTACT players -- the promoter-pCRE "
+                    "contact frequencies of the pCRE slots, and / or the slots themselves -- to this .npz file, in metadata order and in LOGIT "
+                    "space of the prediction's column: gene_ids, players (names), phi [n_genes, P] (0 for dummy slots), logits, erased (every "
+                    "player absent; phi sums to their difference), freq [n_genes, i_max] and n_pcres (contact.contact_shapley): does a pCRE matter "
+                    "through its chromatin state or through its contact with the promoter?")
+    ap.add_argument("--contact-players", default=None, choices=CONTACT_PLAYER_SPECS, help="the players of the --contact-* outputs: each slot's "
+                    "contact (contacts, the default), each slot deleted (pcres: the pCRE game), both, slot by slot (pcres_and_contacts: 16 "
+                    "players) or one player holding every contact (all: the model without Hi-C)")
+    ap.add_argument("--contact-scale", type=float, default=None, help="what an absent contact's frequency is scaled by: 0 erases it (default), "
+                    "2 doubles it; any finite value")
+    ap.add_argument("--contact-interactions-out", default=None, help="also write the pairwise Shapley interaction index of the contact players "
+                    "to this .npy file: [n_genes, P, P] in logit space, symmetric (contact.contact_shapley_interactions).  --contact-players, "
+                    "--contact-scale and --interaction-index apply")
+    ap.add_argument("--contact-dividends-out", default=None, help="also write the Harsanyi dividends of every set of contact players to this "
+                    ".npz file: gene_ids, players, sets [2^P], dividends and mass [n_genes, 2^P] (contact.contact_dividends).  --contact-players "
+                    "and --contact-scale apply")
+    ap.add_argument("--contact-donor-shapley-out", default=None, help="the Shapley values of the contact players against the donor cell type of "
+                    "--donor-npy-dir: an absent contact takes the donor's frequency.  The keys of --contact-shapley-out with donor in place of "
+                    "erased, plus donor_freq and marks.  --contact-players applies")
+    ap.add_argument("--contact-donor-marks", default=None, choices=("own", "donor"), help="--contact-donor-shapley-out plays on the gene's own "
+                    "features (own, the default) or on the donor's under the gene's masks (donor: logits is then the donor row of "
+                    "--mark-donor-shapley-out, and the two games together account for the whole difference between the two cell types)")
     from .attribution import WINDOW_PLAYER_SPECS
     ap.add_argument("--window-shapley-out", default=None, help="also write the Shapley values of WINDOW players -- stretches of a region, in "
                     "coarsest bins -- to this .npz file, in metadata order and in LOGIT space of the prediction's column: gene_ids, players "
@@ -950,8 +1029,10 @@ _DEFAULTS = dict(      # what predict() gets for an option that was not given; m
     mark_scale=0.0, mark_sampled_players="cells", mark_perms=64, mark_seed=0, mark_focal=4, interaction_index="sii", window_players="promoter",
     window_width=1, window_perms=64, window_seed=0, window_scale=0.0, fine_window_region="promoter", fine_window_width=2,
     fine_window_players="windows", fine_window_zoom=1, fine_window_perms=64, fine_window_seed=0, fine_window_scale=0.0,
-    mark_backselect_players="cells", backselect_mode="backward", backselect_frac=0.9)
+    mark_backselect_players="cells", backselect_mode="backward", backselect_frac=0.9, contact_players="contacts", contact_scale=0.0,
+    contact_donor_marks="own")
 _BACKSELECT_OUTS = ("mark_backselect_out",) + _BACKSELECT_DONOR_OUTS
+_CONTACT_OUTS = ("contact_shapley_out", "contact_interactions_out", "contact_dividends_out")
 _MARK_OUTS = ("mark_shapley_out", "mark_epistasis_out", "mark_interactions_out", "mark_dividends_out")
 _DONOR_EXACT_OUTS = ("mark_donor_shapley_out", "mark_donor_epistasis_out", "mark_donor_interactions_out", "mark_donor_dividends_out")
 _SAMPLED_OUTS = ("mark_sampled_shapley_out", "mark_donor_sampled_shapley_out")
@@ -969,16 +1050,22 @@ _NEEDS = [      # (flags, the flags they apply to, the refusal where one of the 
     (("scan_scale", "scan_width", "scan_regions"), ("scan_out",), "--scan-scale / --scan-width / --scan-regions need --scan-out"),
     (("fine_scan_region", "fine_scan_width", "fine_scan_stride", "fine_scan_zoom", "fine_scan_scale"), ("fine_scan_out",),
      "--fine-scan-region / --fine-scan-width / --fine-scan-stride / --fine-scan-zoom / --fine-scan-scale need --fine-scan-out"),
-    (("interaction_index",), ("pcre_interactions_out", "mark_interactions_out", "mark_donor_interactions_out") + _PAIRS_OUTS,
+    (("interaction_index",), ("pcre_interactions_out", "mark_interactions_out", "mark_donor_interactions_out", "contact_interactions_out") + _PAIRS_OUTS,
      "--interaction-index needs --pcre-interactions-out, --mark-interactions-out or --mark-donor-interactions-out"
      " (or --mark-sampled-interactions-out, --mark-donor-sampled-interactions-out)"),
     (("mark_focal",), _PAIRS_OUTS, "--mark-focal needs --mark-sampled-interactions-out or --mark-donor-sampled-interactions-out"),
     (("raw_donor_ig_dir",), ("donor_npy_dir",), "--raw-donor-ig-dir needs --donor-npy-dir"),
     (_DONOR_OUTS, ("donor_npy_dir",), "%s need --donor-npy-dir" % " / ".join("--" + name.replace("_", "-") for name in _DONOR_OUTS)),
     (_BACKSELECT_DONOR_OUTS, ("donor_npy_dir",), "--mark-donor-backselect-out needs --donor-npy-dir"),
+    (_CONTACT_DONOR_OUTS, ("donor_npy_dir",), "--contact-donor-shapley-out needs --donor-npy-dir"),
+    (("contact_players",), _CONTACT_OUTS + _CONTACT_DONOR_OUTS,
+     "--contact-players needs --contact-shapley-out, --contact-interactions-out, --contact-dividends-out or --contact-donor-shapley-out"),
+    (("contact_scale",), _CONTACT_OUTS,
+     "--contact-scale needs --contact-shapley-out, --contact-interactions-out or --contact-dividends-out (the donor rule has no scale)"),
+    (("contact_donor_marks",), _CONTACT_DONOR_OUTS, "--contact-donor-marks needs --contact-donor-shapley-out"),
     (("mark_backselect_players", "backselect_mode", "backselect_frac"), _BACKSELECT_OUTS,
      "--mark-backselect-players / --backselect-mode / --backselect-frac need --mark-backselect-out or --mark-donor-backselect-out"),
-    (("donor_npy_dir", "donor_meta", "donor_store"), _DONOR_OUTS + _BACKSELECT_DONOR_OUTS + ("raw_donor_ig_dir",),
+    (("donor_npy_dir", "donor_meta", "donor_store"), _DONOR_OUTS + _BACKSELECT_DONOR_OUTS + _CONTACT_DONOR_OUTS + ("raw_donor_ig_dir",),
      "--donor-npy-dir / --donor-meta / --donor-store need --mark-donor-shapley-out, --mark-donor-epistasis-out or "
      "--mark-donor-sampled-shapley-out (or --window-donor-shapley-out, --fine-window-donor-shapley-out, "
      "--mark-donor-interactions-out, --mark-donor-sampled-interactions-out, --mark-donor-dividends-out)"),
@@ -1022,6 +1109,10 @@ def main(argv=None):
             ap.error("--%s must be a finite factor >= 0" % name.replace("_", "-"))
     if not np.isfinite(args.backselect_frac):
         ap.error("--backselect-frac must be a finite number")
+    if not np.isfinite(args.contact_scale):
+        ap.error("--contact-scale must be a finite factor")
+    if args.contact_interactions_out and args.contact_players == "all":
+        ap.error("--contact-interactions-out needs at least 2 players; --contact-players all has 1")
     for name in ("scan_width", "fine_scan_width", "fine_scan_stride", "fine_scan_zoom", "mark_perms", "window_width", "window_perms",
                  "fine_window_width", "fine_window_zoom", "fine_window_perms"):
         if getattr(args, name) is not None and getattr(args, name) < 1:

@@ -296,6 +296,54 @@ int cf_set_interactions_from_dividends(cf_handle* h, const float* div, int B, in
  * 1 per reducer launched (1, or 2 with phi).  Refused by name, before anything is launched: what cf_pcre_shapley refuses (phi may be
  * null), a null inter, an index other than the two constants, i_max < 2. */
 int cf_pcre_shapley_interactions(cf_handle* h, const cf_batch* batch, int index, float* inter, float* phi, float* logits_all, void* stream);
+/* Contact games (interpretation): coalition forwards whose players delete pCRE slots and / or edit the promoter-pCRE contact frequencies
+ * -- does an enhancer matter through its chromatin state or through its contact with the promoter?  A player p has two 32-bit words over
+ * the pCRE slots (HOST arrays of n_players words, read before the call returns): bit j of player_drop[p] set = slot j is deleted while p
+ * is absent; bit j of player_contact[p] set = slot j's contact is edited while p is absent.  Players may overlap.  A coalition is one
+ * word, bit p set = player p PRESENT.  Row (b, m), with D the OR of player_drop and C the OR of player_contact over the absent players,
+ * is the inference forward of gene b with
+ *   deletion      for every j in D: row and column j + 1 of the interaction mask set at every resolution (the rule of cf_pcre_coalitions);
+ *   contact edit  entry (q, k) of interaction_freq[b] edited when token q or token k is j + 1 for some j in C -- token 0, the promoter, is
+ *                 never named; row and column both, mirroring the mask rule (the kernels read all T x T entries) --, once per entry:
+ *                   donor_freq == NULL   scale * f, one fp32 multiplication: 0 erases, 2 doubles, 1 is a bit-exact no-op, any finite
+ *                                        value is accepted (the bias is signed);
+ *                   donor_freq != NULL   donor_freq[b, q, k]: a device [B, T, T] fp32 tensor, the same genes' frequencies in another
+ *                                        cell type or a hypothetical contact map (scale is not read);
+ *   everything else gene b's own.  The full word 2^P - 1 is the prediction, bit-equal to cf_forward(save = 0).
+ * Three facts hold bit for bit: a game whose players only drop is the pCRE game (the rows of cf_pcre_coalitions on the complementary
+ * masks); a masked score is replaced, not biased, so next to an absent player that drops slot j a player that edits slot j's contact is
+ * null (every Harsanyi dividend of a set holding `contact j` without `pcre j` is exactly 0); a dummy slot, scale = 1 and a donor_freq
+ * equal to the batch's own are null players.
+ * Launches: those of cf_pcre_coalitions with k_contact_expand in place of k_coalition_expand -- the trunk once, k_pcre_stash once, per
+ * chunk of at most max_batch rows one k_contact_expand (workgroup per chunk row and resolution; every output element written once, no
+ * atomics) and the Regulation + head launches:
+ *   cf_launch_counts fwd = n_trunk + 1 + ceil(B * n_coal / max_batch) * (1 + n_reg_head), plus 1 per reducer.
+ * The coalition words and the 2 * n_players player words travel in the handle's word table; stash, chunk buffers and the handle-owned
+ * row buffer are those of cf_pcre_ablation / cf_pcre_shapley: no other allocation.  Overwrites the activations a cf_forward(save >= 1)
+ * kept.  Deterministic; the result does not depend on max_batch.
+ * cf_contact_coalitions: keep is a HOST array of n_coal words; logits [B, n_coal, n_out], gene-major.
+ * cf_contact_shapley: all 2^P coalitions (word m at column m), then k_shapley: phi [B, P, n_out]; logits_all [B, 2^P, n_out] or NULL
+ * (the handle-owned buffer).  cf_contact_epistasis: the pair-deletion rows of cf_pcre_epistasis on the P players, then k_epistasis: eps
+ * [B, P, P, n_out]; logits_pairs [B, 1 + P + P (P - 1) / 2, n_out] or NULL.  cf_contact_shapley_interactions: the 2^P rows, then
+ * k_shapley_pairs (and k_shapley if phi is given), index as in cf_shapley_interactions_from_rows.  Dividends, set indices and
+ * back-selection: the *_from_rows operators on a kept table.
+ * Refused by name, before anything is launched: a null handle / batch / opts / output, B > max_batch, n_players outside 1..16, null
+ * player arrays, a player with both words 0, a player bit >= i_max, a non-finite scale, n_coal < 1, a null keep, a keep word naming a
+ * player >= n_players, fewer than 2 players for cf_contact_epistasis and cf_contact_shapley_interactions, an index other than the two
+ * constants. */
+typedef struct cf_contact_opts {
+    int n_players;                   /* 1..16 */
+    const uint32_t* player_drop;     /* host [n_players]: bit j = pCRE slot j deleted while the player is absent */
+    const uint32_t* player_contact;  /* host [n_players]: bit j = pCRE slot j's contact edited while the player is absent */
+    float scale;                     /* the scale rule (donor_freq == NULL) */
+    const float* donor_freq;         /* device [B, T, T], or NULL */
+} cf_contact_opts;
+int cf_contact_coalitions(cf_handle* h, const cf_batch* batch, const cf_contact_opts* opts, const uint32_t* keep, int n_coal, float* logits,
+                          void* stream);
+int cf_contact_shapley(cf_handle* h, const cf_batch* batch, const cf_contact_opts* opts, float* phi, float* logits_all, void* stream);
+int cf_contact_epistasis(cf_handle* h, const cf_batch* batch, const cf_contact_opts* opts, float* eps, float* logits_pairs, void* stream);
+int cf_contact_shapley_interactions(cf_handle* h, const cf_batch* batch, const cf_contact_opts* opts, int index, float* inter, float* phi,
+                                    float* logits_all, void* stream);
 /* Integrated gradients (interpretation).  For the target logit column t, nodes a_k and weights w_k (k < n_steps) on [0, 1], per
  * interpolated input x with baseline xb (T = i_max + 1):
  *   x_k   = xb + a_k (x - xb)                         fp32, each operation rounded
