@@ -97,6 +97,11 @@ class cf_scan_regions_opts(C.Structure):
                 ("flip", C.c_void_p)]
 
 
+class cf_transplant_opts(C.Structure):
+    _fields_ = [("n_cand", C.c_int), ("n_freq", C.c_int), ("lib_feats", C.c_void_p * MAX_RES), ("lib_mask", C.c_void_p * MAX_RES),
+                ("freq", C.c_void_p), ("slot", C.c_void_p), ("slot_all", C.c_int), ("slot_out", C.c_void_p)]
+
+
 class cf_scan_fine_opts(C.Structure):
     _fields_ = [("region", C.c_int), ("n_sets", C.c_int), ("mark_sets", C.c_void_p), ("scale", C.c_float), ("flip", C.c_void_p),
                 ("width", C.c_int), ("stride", C.c_int), ("n_windows", C.c_int), ("start", C.c_void_p), ("lengths", C.c_void_p),
@@ -216,6 +221,7 @@ SYMBOLS = {
                                                     C.POINTER(cf_input_grads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_perturbation_scan": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_scan_opts), C.c_void_p, C.c_void_p]),
     "cf_perturbation_scan_regions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_scan_regions_opts), C.c_void_p, C.c_void_p]),
+    "cf_pcre_transplant": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_transplant_opts), C.c_void_p, C.c_void_p]),
     "cf_perturbation_scan_fine": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_scan_fine_opts), C.c_void_p, C.c_void_p]),
     "cf_mark_coalitions": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_opts), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "cf_mark_shapley": (C.c_int, [C.c_void_p, C.POINTER(cf_batch), C.POINTER(cf_mark_opts), C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -11,6 +11,7 @@
 #include "cf_dividends.h"
 #include "cf_ig.h"
 #include "cf_scan.h"
+#include "cf_transplant.h"
 #include "cf_marks.h"
 #include "cf_scan_fine.h"
 #include "cf_marks_wide.h"
@@ -43,6 +44,7 @@ using namespace cf;
 #include "cf_api_bwd.h"
 #include "cf_api_attrib.h"
 #include "cf_api_contact.h"
+#include "cf_api_transplant.h"
 #include "cf_api_marks.h"
 
 // ------------------------------------------------------------------------------------

@@ -363,7 +363,7 @@ struct cf_handle {
         const unsigned* deletion_words = nullptr;      // [i_max + 2]: the coalition words of cf_pcre_ablation's variants, written once
         DevBuf<unsigned> words;                // the 32-bit table of a call: coalition words | quadrature nodes, then weights | mark sets | mark-coalition words, then player words (the sampled game: then the inverse permutations, bytes; sampled interactions: then the column table; back-selection: then the current coalitions, the per-gene candidate words and s_b); grows on demand
         DevBuf<float> own_rows;                // [max_batch, per, n_out]: the rows of a Shapley / epistasis call without a caller's buffer; grows on demand
-        DevBuf<float> slot_rows;               // [n_res][B * (V - 1), d_emb]: the changed Regulation input row of every variant of one pCRE slot (scan); grows on demand
+        DevBuf<float> slot_rows;               // [n_res][B * (V - 1), d_emb]: the changed Regulation input row of every variant of one pCRE slot (scan), or with V - 1 = C of every candidate of a transplant screen; grows on demand
     } aw;
     bool ig_trunk_once = true;                 // frequency-only IG runs the trunk once (CF_IG_TRUNK_ONCE=0 at cf_create: the general path, for A/B checks)
     bool scan_pack = true;                     // pCRE variants run slot-packed (CF_SCAN_PACK=0 at cf_create: the per-region path, for A/B checks)

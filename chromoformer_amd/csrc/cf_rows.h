@@ -1,5 +1,5 @@
 // cf_rows.h -- a chunk of rows copied from the caller's batch: what the expand kernels of the attribution entry points share
-// (cf_coalition.h, cf_ig.h, cf_scan.h, cf_scan_fine.h and the mark games cf_marks.h, cf_mark_windows.h, cf_mark_fine.h; included by
+// (cf_coalition.h, cf_ig.h, cf_scan.h, cf_transplant.h, cf_scan_fine.h and the mark games cf_marks.h, cf_mark_windows.h, cf_mark_fine.h; included by
 // cf_api.hip in front of them).  Chunk row i is a copy of gene b; blockIdx.y is the resolution r.  Bytes only, kRowThreads threads per
 // workgroup.  Also here: rows_masks_freq, the three copies that close the mark and scan expand kernels, and win_extent, the real rows of
 // a pad-mask row by one wave (the window and fine games).

@@ -412,6 +412,26 @@ def write_contact_values(model, ds, donor_ds, store, donor_store, bsz, gene_ids,
                mass=np.stack([r["mass"][..., t] for r in rows]))
 
 
+def write_transplant(model, ds, store, bsz, gene_ids, bed, out, regression=False, freqs=(1.0, 5.0, 10.0), slot="append"):
+    """pCRE transplant screen (transplant.pcre_transplant_dataset) of every gene of a device-resident store, in store order, into `out`,
+    an .npz: gene_ids [n], prediction [n], transplant [n, C, Q] -- the prediction with candidate c of the BED file `bed`
+    (`chrom start end [name]` lines; the raw chrom:start-end.npy files are in the dataset's directory) in the gene's slot at contact
+    frequency freqs[q], in the prediction column's quantity --, slot [n] (-1 = not placed), placed [n], candidates [C] (names),
+    freqs [Q].  ds: the dataset the store was built from."""
+    from .transplant import library_from_regions, pcre_transplant_dataset, read_bed
+    library = library_from_regions(ds, read_bed(bed))
+    rows = list(pcre_transplant_dataset(model, ds, library, list(freqs), slot=slot, genes=list(gene_ids), bsz=bsz, store=store))
+
+    def quantity(lg):
+        lg = np.asarray(lg, dtype=np.float32)
+        return lg[..., 0] if regression else torch.sigmoid(torch.from_numpy(lg)).numpy()[..., 1]
+
+    _savez(out, gene_ids=np.array(list(gene_ids)), prediction=quantity(np.stack([r["logits"] for r in rows])),
+           transplant=quantity(np.stack([r["transplant"] for r in rows])), slot=np.array([r["slot"] for r in rows], dtype=np.int32),
+           placed=np.array([r["placed"] for r in rows], dtype=bool), candidates=np.array(library.names),
+           freqs=np.array(list(freqs), dtype=np.float32))
+
+
 def write_integrated_gradients(model, store, bsz, ig_dir, n_steps=50, method="gausslegendre", target=None):
     """Integrated gradients of every gene of a device-resident store, in store order, into `ig_dir`: promoter_feats_{b}.npy
     [n, L, F], pcre_feats_{b}.npy [n, i_max, L, F], interaction_freq.npy [n, T, T] and delta.npy [n] (float32 .npy memory maps;
@@ -611,7 +631,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
             mark_donor_sampled_interactions_out=None, mark_focal=4, pcre_dividends_out=None, mark_dividends_out=None,
             mark_donor_dividends_out=None, mark_backselect_out=None, mark_donor_backselect_out=None, mark_backselect_players="cells",
             backselect_mode="backward", backselect_frac=0.9, contact_shapley_out=None, contact_players="contacts", contact_scale=0.0,
-            contact_interactions_out=None, contact_dividends_out=None, contact_donor_shapley_out=None, contact_donor_marks="own"):
+            contact_interactions_out=None, contact_dividends_out=None, contact_donor_shapley_out=None, contact_donor_marks="own",
+            transplant_bed=None, transplant_out=None, transplant_freq=(1.0, 5.0, 10.0), transplant_slot="append"):
     """-> (meta DataFrame, predictions float32 [n_genes]) in the order of the metadata file.  attention_dir / embeddings_out: also
     write the attention maps / regulatory embeddings of every gene, in the same order (write_attention_maps); pcre_ablation_out:
     the predictions with each pCRE deleted (write_pcre_ablation); ig_dir: integrated gradients of every gene
@@ -654,7 +675,18 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
     players, whose absence scales the promoter-pCRE contact frequencies by contact_scale (write_contact_values; contact_players --
     "contacts", "pcres", "pcres_and_contacts" or "all" -- applies); contact_donor_shapley_out: the Shapley values of the same players
     against the donor cell type's contact frequencies, on the gene's own features or, with contact_donor_marks="donor", on the
-    donor's (contact_players applies)."""
+    donor's (contact_players applies); transplant_bed + transplant_out: the pCRE transplant screen of the BED file's regions, each in
+    the slot transplant_slot ("append" or a slot) of every gene at the contact frequencies transplant_freq (write_transplant)."""
+    if transplant_bed or transplant_out:      # (refusals before anything is computed)
+        from .transplant import broadcast_freq, read_bed, slot_argument
+        if not (transplant_bed and transplant_out):
+            raise ValueError("predict: transplant_bed and transplant_out go together")
+        read_bed(transplant_bed)
+        transplant_freq = [float(f) for f in np.atleast_1d(np.asarray(transplant_freq, dtype=np.float64))]
+        broadcast_freq(transplant_freq, 1, 1, "predict")
+        if not isinstance(transplant_slot, (str, int, np.integer)):
+            raise ValueError("predict: transplant_slot = %r: 'append' or a slot" % (transplant_slot,))
+        slot_argument(transplant_slot, 1, i_max, "predict")
     if contact_shapley_out or contact_interactions_out or contact_dividends_out or contact_donor_shapley_out:      # (refusals before anything is computed)
         from .attribution import contact_players as _contact
         _contact(contact_players, i_max)
@@ -805,6 +837,8 @@ def predict(meta_path, npy_dir, weights=None, regression=False, bsz=32, seed=123
                                       fine_window_width, fine_window_players, fine_window_zoom, fine_window_perms, fine_window_seed, fine_window_scale)
     if ig_dir:
         write_integrated_gradients(model, store, bsz, ig_dir, ig_steps, ig_method, ig_target)
+    if transplant_out:      # (the candidates' raw files are binned by the dataset's own code)
+        write_transplant(model, plain_ds(), store, bsz, genes, transplant_bed, transplant_out, regression, transplant_freq, transplant_slot)
     if fine_scan_out:      # (strand, coordinates and region lengths come from the metadata)
         write_perturbation_scan_fine(model, plain_ds(), store, bsz, fine_scan_out, genes, regression, fine_scan_region, fine_scan_width, fine_scan_stride,
                                      fine_scan_zoom, fine_scan_scale)
@@ -1020,6 +1054,15 @@ def build_parser():
     ap.add_argument("--fine-window-seed", type=int, default=None, help="seed of the sampled orders (default 0)")
     ap.add_argument("--fine-window-scale", type=float, default=None, help="what an absent player's raw signal is scaled by inside its window: 0 "
                     "erases it (default); --fine-window-shapley-out only")
+    ap.add_argument("--transplant-bed", default=None, help="pCRE transplant screen: a BED file of candidate regions, `chrom start end [name]` "
+                    "lines, whose raw chrom:start-end.npy files are in --npy-dir; each is tried in one pCRE slot of every gene "
+                    "(transplant.pcre_transplant).  Needs --transplant-out")
+    ap.add_argument("--transplant-out", default=None, help="write the transplant screen to this .npz file, in metadata order: prediction "
+                    "[n_genes], transplant [n_genes, C, Q] (the prediction with candidate c in the gene's slot at contact frequency q), slot "
+                    "(-1: not placed), placed, candidates, freqs.  Needs --transplant-bed")
+    ap.add_argument("--transplant-freq", default=None, help="the contact frequencies of the screen, comma-separated (default 1,5,10)")
+    ap.add_argument("--transplant-slot", default=None, help="append (default: each gene's first free slot; a gene without one is not "
+                    "placed) or a slot in [0, 8), whose pCRE is replaced")
     return ap
 
 
@@ -1030,7 +1073,7 @@ _DEFAULTS = dict(      # what predict() gets for an option that was not given; m
     window_width=1, window_perms=64, window_seed=0, window_scale=0.0, fine_window_region="promoter", fine_window_width=2,
     fine_window_players="windows", fine_window_zoom=1, fine_window_perms=64, fine_window_seed=0, fine_window_scale=0.0,
     mark_backselect_players="cells", backselect_mode="backward", backselect_frac=0.9, contact_players="contacts", contact_scale=0.0,
-    contact_donor_marks="own")
+    contact_donor_marks="own", transplant_freq="1,5,10", transplant_slot="append")
 _BACKSELECT_OUTS = ("mark_backselect_out",) + _BACKSELECT_DONOR_OUTS
 _CONTACT_OUTS = ("contact_shapley_out", "contact_interactions_out", "contact_dividends_out")
 _MARK_OUTS = ("mark_shapley_out", "mark_epistasis_out", "mark_interactions_out", "mark_dividends_out")
@@ -1081,6 +1124,9 @@ _NEEDS = [      # (flags, the flags they apply to, the refusal where one of the 
      "--fine-window-region / --fine-window-width / --fine-window-players / --fine-window-zoom / --fine-window-perms / "
      "--fine-window-seed need --fine-window-shapley-out or --fine-window-donor-shapley-out"),
     (("fine_window_scale",), ("fine_window_shapley_out",), "--fine-window-scale needs --fine-window-shapley-out (the donor rule has no scale)"),
+    (("transplant_bed",), ("transplant_out",), "--transplant-bed needs --transplant-out"),
+    (("transplant_out",), ("transplant_bed",), "--transplant-out needs --transplant-bed"),
+    (("transplant_freq", "transplant_slot"), ("transplant_out",), "--transplant-freq / --transplant-slot need --transplant-out"),
 ]
 
 
@@ -1123,6 +1169,22 @@ def main(argv=None):
             if not region.isdigit() or int(region) >= 8:
                 ap.error("--%s must be promoter or a pCRE slot in [0, 8)" % name.replace("_", "-"))
             setattr(args, name, int(region))
+    try:
+        args.transplant_freq = [float(s) for s in args.transplant_freq.split(",")]
+        if not args.transplant_freq or not np.isfinite(args.transplant_freq).all():
+            raise ValueError
+    except ValueError:
+        ap.error("--transplant-freq must be a comma-separated list of finite frequencies")
+    if args.transplant_slot != "append":
+        if not args.transplant_slot.isdigit() or int(args.transplant_slot) >= 8:
+            ap.error("--transplant-slot must be append or a pCRE slot in [0, 8)")
+        args.transplant_slot = int(args.transplant_slot)
+    if args.transplant_bed:
+        from .transplant import read_bed
+        try:
+            read_bed(args.transplant_bed)
+        except (OSError, ValueError) as e:
+            ap.error("--transplant-bed: %s" % e)
     if isinstance(args.mark_focal, str):
         if args.mark_focal.strip().lstrip("+-").isdigit():
             args.mark_focal = int(args.mark_focal)

@@ -499,6 +499,52 @@ typedef struct cf_scan_regions_opts {
  * mark_sets, B > max_batch, width < 1, n_sets < 1, a negative or non-finite scale, a mark bit >= n_feats, non-nested n_bins, armed
  * riders), regions == 0, a region bit above i_max. */
 int cf_perturbation_scan_regions(cf_handle* h, const cf_batch* batch, const cf_scan_regions_opts* opts, float* logits, void* stream);
+/* pCRE transplant screen (interpretation): what would a gene's prediction be if another enhancer were brought into contact with its
+ * promoter, and how does the answer depend on contact strength?  A library of C candidate regions -- features [C, n_bins[r], n_feats]
+ * and centre pad-mask rows [C, n_bins[r]] (non-zero = masked) per resolution -- is tried in ONE pCRE slot of every gene, each candidate
+ * at Q contact frequencies.  logits: [B, 1 + C * Q, n_out], gene-major; row (b, 0) is gene b verbatim (cf_forward(save = 0), bit-equal),
+ * row (b, 1 + c * Q + q) is the inference forward of gene b with candidate c in slot j = the gene's slot at f = freq[b, c, q]:
+ *   features     pcre_feats[r][b, j] = lib_feats[r][c] and the slot's centre pad-mask row = lib_mask[r][c] at every resolution (for a
+ *                full [B, S, 1, L, L] mask: rows_promoter | lib columns; the forward reads the centre row, which lies inside every
+ *                promoter's real rows).  A candidate without a real bin is a fully masked row: the uniform softmax of a dummy slot;
+ *   interaction  per resolution, with dead(t) = interaction_mask[r][b, t, t] for t != j + 1:  entries (j + 1, t) and (t, j + 1) become
+ *                dead(t), entry (j + 1, j + 1) becomes 0, every other entry is unchanged -- on the dataset's block masks: the mask
+ *                after replacing partner j (j < n_part) or appending one (j = n_part);
+ *   frequencies  entry (0, j + 1) becomes f, every other entry of row and column j + 1 becomes 0, the rest is unchanged: what the
+ *                dataset writes for a partner with score f.
+ * The slot: slot[b] (device data; a value outside [-1, i_max) is read as -1), or slot_all for every gene when slot == NULL, where
+ * slot_all = -1 is "append": the first token t >= 1 whose diagonal entry of the coarsest resolution's interaction mask is set, formed
+ * on the device.  Slot -1 (explicit, or a gene with every token live under "append") = not placed: every row of that gene carries the
+ * bits of row 0.  slot_out [B], if given, receives the slot used per gene.
+ * A slot's Pairwise output depends on the promoter and on that slot alone and the Regulation stack has no positional encoding, so
+ * i_max candidates ride as the slots of one pseudo-gene through one trunk pass and a candidate's trunk row serves all Q frequencies.
+ * With S = i_max, U = ceil(C / S): the trunk runs once on the B genes and its output is stashed (k_pcre_stash), then
+ *   pack phase   pseudo rows (b, u), gene-major, in chunks of at most max_batch: k_transplant_pack writes gene b's promoter (all L rows
+ *                of a full mask with embed.n_layers > 1) and candidate u * S + s into slot s (past C: a dummy, zero features and a fully
+ *                masked row) into the chunk buffers of cf_integrated_gradients; the trunk part of cf_forward(save = 0) runs on the chunk
+ *                (k_attc2's regions per workgroup as for the caller's B genes); k_scan_unpack copies rows 1..S of each pseudo-gene's
+ *                output to the handle-owned buffer of cf_perturbation_scan_regions, here [n_res][B * C, d_emb];
+ *   row phase    rows (b, v) in output order, in chunks of at most max_batch: k_transplant_rows writes the stash back with row j + 1
+ *                taken from that buffer for v >= 1 of a placed gene, the edited interaction masks and frequencies; the Regulation +
+ *                head launches of cf_forward(save = 0) write the chunk's slice.
+ *   cf_launch_counts fwd = (n_trunk + 1) + ceil(B * U / max_batch) * (n_trunk + 2) + ceil(B * (1 + C * Q) / max_batch) * (1 + n_reg_head)
+ * (n_trunk, n_reg_head: see cf_pcre_ablation).  Deterministic (no atomics); the result does not depend on max_batch.  Overwrites the
+ * activations a cf_forward(save >= 1) kept: no cf_backward* may follow without a new saving forward.  Parameters, gradients and moments
+ * are untouched.  Limits: one slot per row (no combinations of transplants); promoters are not transplanted; candidates are never
+ * stored mirrored; there is no feats_out.
+ * Refused by name, before anything is launched: a null handle / batch / opts / logits / freq, a null lib_feats[r] / lib_mask[r] for
+ * r < n_res or a non-null one for r >= n_res, B > max_batch, n_cand < 1, n_freq < 1, B * (1 + C * Q) beyond int, slot_all outside
+ * [-1, i_max), armed riders. */
+typedef struct cf_transplant_opts {
+    int n_cand, n_freq;                         /* C >= 1, Q >= 1 */
+    const float*   lib_feats[CF_MAX_RES];       /* device [C, L_r, F] fp32 */
+    const uint8_t* lib_mask[CF_MAX_RES];        /* device [C, L_r] */
+    const float*   freq;                        /* device [B, C, Q] */
+    const int*     slot;                        /* device [B], each in [-1, i_max), or NULL: slot_all for every gene */
+    int            slot_all;                    /* a slot, or -1 = "append" */
+    int*           slot_out;                    /* device [B] or NULL: the slot used per gene, -1 = not placed */
+} cf_transplant_opts;
+int cf_pcre_transplant(cf_handle* h, const cf_batch* batch, const cf_transplant_opts* opts, float* logits, void* stream);
 /* Fine-resolution perturbation scan (interpretation): the scan above with windows given in bins of the FINEST resolution -- "where
  * inside this coarse bin?".  The perturbation is the scan's (the window's raw samples of a mark set scaled by s); a fine window covers
  * a coarser bin only in part, and such a bin is recomputed from its finest children, weighted by sample counts.
